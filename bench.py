@@ -10,11 +10,15 @@ BatchNorm, reference init under torch.manual_seed(0)) forward to feat (B,N,1286)
 given dfeat to every HS-stack parameter; for N>1 ranks the gradient mean over RCCL is inside the step.
 Workload at N=1: BASELINE.json configs[1] shape, B=16 N=1028 fp32.  Weak scaling: 16 clouds per GPU.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times the K
+steps and prints the headline (value, ms_per_step); its "roofline" and "step_roofline" are null and it carries no
+"cpu_baseline".  --full adds what takes runs of its own:
   roofline     -- the dominant libhsp kernel of the step: algorithmic bytes per launch / live HIP-event
                   average duration over the timed region vs the 8 TB/s HBM peak;
   cpu_baseline -- (rank 0, N=1 only) the CPU oracle restatement (oracle/ref_cpu.py, kind "port") timed on
-                  the host cores on a bounded sample of the same workload.  Reported, never a target.
+                  the host cores on a bounded sample of the same workload.  Reported, never a target;
+  and, in config, the full training step (unit U3), the bf16 dense-cloud and other-GEMM-mode figures.
+--dump-outputs DIR writes what the timed path computed in its last step (feat, every parameter gradient) as .npy files.
 """
 import argparse
 import json
@@ -207,8 +211,8 @@ def side_run(extra_args, env_extra=None, timeout=600):
     for k_ in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k_, None)
     env.update(env_extra or {})
-    out = subprocess.run([sys.executable, os.path.abspath(__file__), "--gpus", "1", "--no-u3", "--no-cpu-baseline", "--no-side"]
-                         + extra_args, env=env, capture_output=True, text=True, timeout=timeout)
+    out = subprocess.run([sys.executable, os.path.abspath(__file__), "--gpus", "1", "--full", "--no-u3", "--no-cpu-baseline",
+                          "--no-side"] + extra_args, env=env, capture_output=True, text=True, timeout=timeout)
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     if out.returncode != 0 or not lines:
         raise RuntimeError(f"side run {extra_args} failed (rc {out.returncode}): {out.stderr[-300:]}")
@@ -216,18 +220,20 @@ def side_run(extra_args, env_extra=None, timeout=600):
 
 
 def relaunch_multi_gpu(n):
-    """`python bench.py --gpus N` without a launcher: start N ranks (one per GPU) under torch.distributed.run and hand over;
-    refuses when fewer than N devices are visible (a silent 1-rank run would print n_gpus: 1 for an N-GPU request)"""
+    """`python bench.py --gpus N` without a launcher: start N ranks (one per GPU) under torch.distributed.run in a child
+    process and exit with its status; refuses when fewer than N devices are visible (a silent 1-rank run would print
+    n_gpus: 1 for an N-GPU request)"""
     have = torch.cuda.device_count()
     if have < n:
         sys.exit(f"bench.py: --gpus {n} but only {have} GPU(s) visible")
     import socket
+    import subprocess
     with socket.socket() as sk:
         sk.bind(("127.0.0.1", 0))
         port = sk.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
-    os.execv(sys.executable, cmd)
+    sys.exit(subprocess.call(cmd))
 
 
 def dry_run(args, rank, world, device, result_out):
@@ -327,6 +333,32 @@ def roofline_of(kname, kkey, kd, bf16, traffic, graph_calls=None):
     return roof
 
 
+DUMP_FEAT_ROWS = 8192               # feat rows kept when the whole (B*N, 1286) output is larger (8192 rows = 42 MB in fp32)
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(out_dir, net, feat, grads):
+    """what the timed path hands its caller after its last step, as float32 DIR/<name>.npy: ``feat`` (B,N,C) whole when it
+    has at most DUMP_FEAT_ROWS (cloud, point) rows, else ``feat_sample`` = a fixed sample of that many rows (torch.randperm
+    under seed 0, kept in row order), and ``grad.<parameter name>`` for every parameter of the network"""
+    import numpy as np
+    names = {id(p): n for n, p in net.named_parameters()}
+    rows = feat.detach().reshape(-1, feat.shape[-1])
+    if rows.shape[0] > DUMP_FEAT_ROWS:
+        pick = torch.randperm(rows.shape[0], generator=torch.Generator().manual_seed(0))[:DUMP_FEAT_ROWS].sort().values
+        arrays = {"feat_sample": rows[pick.to(rows.device)]}
+    else:
+        arrays = {"feat": feat.detach()}
+    for p, g in grads:
+        arrays["grad." + names[id(p)]] = g if g is not None else torch.zeros_like(p)
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs: {total} bytes > {DUMP_LIMIT_BYTES}"
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -340,7 +372,14 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-u3", action="store_true", help="skip the full-training-step (unit U3) figure appended to config")
     ap.add_argument("--cpu-sample", type=int, default=16, help="clouds in the CPU-baseline sample (one per-GPU batch)")
-    ap.add_argument("--breakdown", action="store_true", help="print the per-kernel table to stderr")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the per-kernel roofline (the K steps re-issued eagerly), the "
+                         "step median over >= 50 steps, the full training step (U3), the bf16 / other-GEMM-mode side runs and "
+                         "the CPU baseline (--no-u3, --no-side, --no-cpu-baseline drop single parts)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what their last step computed (feat or a fixed sample of its rows, every "
+                         "parameter gradient) as float32 DIR/<name>.npy")
+    ap.add_argument("--breakdown", action="store_true", help="print the per-kernel table to stderr (implies --full)")
     ap.add_argument("--no-graph", action="store_true", help="issue the step eagerly instead of replaying a hipGraph")
     ap.add_argument("--no-gemm-tuning", action="store_true", help="leave hipBLASLt/rocBLAS on their default heuristics")
     ap.add_argument("--dry-run", action="store_true",
@@ -349,6 +388,7 @@ def main():
     ap.add_argument("--no-side", action="store_true",
                     help="skip the secondary figures appended to config (bf16 dense clouds, the no-BLAS-library step)")
     args = ap.parse_args()
+    args.full = args.full or args.breakdown
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         relaunch_multi_gpu(args.gpus)                   # does not return
 
@@ -386,6 +426,7 @@ def main():
     if bf16:
         dfeat = dfeat.bfloat16()
     torch.manual_seed(1 + rank)                         # Pool_layer randperm stream (per rank)
+    eager_out = {}
 
     def eager_step():
         for p in params:
@@ -394,6 +435,8 @@ def main():
         feat.backward(dfeat)
         if reducer is not None:
             reducer.finish()
+        if args.dump_outputs:
+            eager_out["feat"] = feat.detach()
 
     graphed = None
     exchange_info = {"reason": "eager step (--no-graph or no capture)"}
@@ -453,9 +496,9 @@ def main():
     for _ in range(args.warmup):
         step()
     fence()
-    timer = ops.KernelTimer() if rank == 0 else None
+    timer = ops.KernelTimer() if rank == 0 and args.full else None
     if graphed is None:
-        ops.set_timer(timer)                            # eager: per-kernel HIP events inside the timed region
+        ops.set_timer(timer)                            # eager + --full: per-kernel HIP events inside the timed region
     # per-step HIP events on the stream the step is issued on (hipEvent timing, median of >= 50 steps)
     evs = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
     t0 = time.perf_counter()
@@ -466,8 +509,17 @@ def main():
     fence()
     dt = time.perf_counter() - t0
     ops.set_timer(None)
+    if args.dump_outputs and rank == 0:
+        if graphed is None:
+            feat, grads = eager_out["feat"], [(p, p.grad) for p in params]
+        elif graphed.flat_grad is not None:             # data parallel: the exchanged (mean) gradients in the flat buffer
+            feat, grads = graphed.feat, list(zip(graphed.params, graphed.grad_views()))
+        else:
+            feat, grads = graphed.feat, [(p, p.grad) for p in params]
+        dump_outputs(args.dump_outputs, net, feat, grads)
     step_ms = [evs[i].elapsed_time(evs[i + 1]) for i in range(args.steps)]
-    extra = max(0, 50 - args.steps)                     # the median is always over >= 50 steps; `value` stays the K-step wall clock
+    # --full: the median is always over >= 50 steps (a plain run: over its K timed steps); `value` stays the K-step wall clock
+    extra = max(0, 50 - args.steps) if args.full else 0
     if extra:
         evs = [torch.cuda.Event(enable_timing=True) for _ in range(extra + 1)]
         evs[0].record()
@@ -478,7 +530,7 @@ def main():
         step_ms += [evs[i].elapsed_time(evs[i + 1]) for i in range(extra)]
     step_ms.sort()
     median_ms = step_ms[len(step_ms) // 2]
-    if graphed is not None and rank == 0:
+    if graphed is not None and rank == 0 and args.full:
         # HIP events cannot be recorded inside a graph replay: the per-kernel durations of the roofline
         # line come from the same K steps issued eagerly right after the timed region (same kernels, same
         # buffers); profiles/ holds the rocprofv3 trace of the graph replays themselves.
@@ -493,7 +545,8 @@ def main():
         all_reduce_(tmax, op=dist.ReduceOp.MAX)
     dt = tmax.item()
 
-    if rank == 0:
+    roof = roof_all = step_roof = hsp_ms = None         # --full figures
+    if rank == 0 and args.full:
         summ = timer.summary()
         graph_calls = {}
         if graphed is not None and not bf16 and B == 16 and N == 1028:
@@ -557,6 +610,7 @@ def main():
                       f"{d['total_ms'] / args.steps:8.3f} ms/step  alg {d['abytes'] / 1e6:8.2f} MB "
                       f"-> {d['abytes'] / (d['avg_us'] * 1e-6) / 1e9:8.1f} GB/s", file=sys.stderr)
             print(f"libhsp kernels {hsp_ms:.3f} ms/step of {1e3 * dt / args.steps:.3f} ms/step", file=sys.stderr)
+    if rank == 0:
         line = {
             "metric": f"point-clouds/sec (N={N}) HS-layer fwd+bwd",     # BASELINE.json's metric at the default N=1028
             "value": round(world * B * args.steps / dt, 2),
@@ -565,7 +619,7 @@ def main():
             "steps": args.steps,
             "warmup": args.warmup,
             "ms_per_step": round(1e3 * dt / args.steps, 4),
-            "ms_per_step_median": round(median_ms, 4),          # HIP-event median over max(K, 50) steps
+            "ms_per_step_median": round(median_ms, 4),          # HIP-event median over K steps (--full: max(K, 50))
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,
@@ -576,7 +630,7 @@ def main():
                                       "train-mode BN, random-init weights (BASELINE configs[3] shape when B=64 N=4096)" if bf16 else
                                       "fp32, train-mode BN, random-init weights (BASELINE configs[1] shape)"),
                        "global_batch": world * B, "points": N, "parallelism": f"dp{world}", "process_group": parallel_describe(), "hipgraph": graphed is not None, "split_graph": bool(graphed is not None and graphed.split), "grad_exchange": ("none" if not use_dist else "2 all-reduces, first overlapped with backward" if graphed is not None and graphed.split else "1 all-reduce after backward" if graphed is not None else "bucketed, hook-driven"), "grad_exchange_choice": exchange_info,
-                       "libhsp_ms_per_step": round(hsp_ms, 4),
+                       "libhsp_ms_per_step": None if hsp_ms is None else round(hsp_ms, 4),
                        **({"bf16_tolerance": "feat vs the fp32 path: <= 6e-2 of scale / 8e-2 rms (tests/test_gpu_bf16.py); per layer vs the "
                                              "CPU oracle 1e-2; free-running neighbour-set agreement floors 0.05-0.2: a stress configuration, "
                                              "not a parity claim"} if bf16 else {}),
@@ -592,14 +646,14 @@ def main():
             "roofline_longest_calls": roof_all,
             "step_roofline": step_roof,
         }
-        if world == 1 and not args.no_u3 and not bf16:
+        if args.full and world == 1 and not args.no_u3 and not bf16:
             try:                                        # BASELINE configs[1] as worded: the FULL training step, same run
                 del graphed
                 torch.cuda.empty_cache()
                 line["config"].update(u3_full_step(B, N, device))
             except Exception as exc:                    # never lose the headline line to the extra figure
                 line["config"]["u3_error"] = f"{type(exc).__name__}: {exc}"[:200]
-        if world == 1 and not args.no_side and not bf16 and B == 16 and N == 1028:
+        if args.full and world == 1 and not args.no_side and not bf16 and B == 16 and N == 1028:
             # secondary figures of the same run, each from a child process: BASELINE configs[3] (bf16 feature storage, dense
             # clouds) and the fp32 step with NO BLAS-library GEMM (HSP_GEMM=own: gemm_wave / gemm_rows / wgrad everywhere)
             try:
@@ -617,7 +671,7 @@ def main():
                 line["config"].update({f"{other}_gemm_ms_per_step": d["ms_per_step"], f"{other}_gemm_clouds_per_s": d["value"]})
             except Exception as exc:
                 line["config"]["other_gemm_error"] = f"{type(exc).__name__}: {exc}"[:200]
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(N, args.cpu_sample)
         print(json.dumps(line), file=result_out, flush=True)
     if dist.is_initialized():

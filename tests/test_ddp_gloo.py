@@ -15,7 +15,8 @@ def _free_port():
 
 
 def _worker(rank, world, port, q):
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank),
+                      CUDA_VISIBLE_DEVICES="", HIP_VISIBLE_DEVICES="")   # CPU ranks, also on a machine with a GPU
     from hs_pose_amd.parallel import GradReducer, init_distributed, shard_range
     r, w, dev = init_distributed()
     assert (r, w) == (rank, world) and dev.type == "cpu"
@@ -99,7 +100,8 @@ class _FakeGraphedStep:
 
 
 def _worker_graphed(rank, world, port, q):
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank),
+                      CUDA_VISIBLE_DEVICES="", HIP_VISIBLE_DEVICES="")   # CPU ranks, also on a machine with a GPU
     from hs_pose_amd import parallel
     from hs_pose_amd.parallel import graphed_step_with_exchange, init_distributed
     init_distributed()
@@ -185,7 +187,8 @@ class _TimedFake(_FakeGraphedStep):
 
 
 def _worker_choice(rank, world, port, q):
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank),
+                      CUDA_VISIBLE_DEVICES="", HIP_VISIBLE_DEVICES="")   # CPU ranks, also on a machine with a GPU
     from hs_pose_amd.parallel import choose_exchange_form, init_distributed
     init_distributed()
     got = {}

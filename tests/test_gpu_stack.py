@@ -210,8 +210,8 @@ def test_bench_data_parallel_path_smoke(dev, split):
     env = dict(os.environ, HSP_FORCE_DIST="1", HSP_SPLIT_GRAPH=split, MASTER_ADDR="127.0.0.1",
                MASTER_PORT=str(29533 + {"0": 0, "1": 1, "probe": 2}[split]), RANK="0", WORLD_SIZE="1", LOCAL_RANK="0")
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "2", "--batch", "2",
-                          "--points", "256", "--no-cpu-baseline", "--no-gemm-tuning"], env=env, capture_output=True, text=True,
-                         timeout=300)
+                          "--points", "256", "--no-cpu-baseline", "--no-gemm-tuning", "--full"], env=env, capture_output=True,
+                         text=True, timeout=300)
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
     assert line["config"]["hipgraph"] is True and line["value"] > 0 and line["n_gpus"] == 1
@@ -222,6 +222,37 @@ def test_bench_data_parallel_path_smoke(dev, split):
     else:
         assert line["config"]["split_graph"] is (split == "1")
     assert set(line["roofline"]) >= {"bound", "achieved", "peak", "unit", "frac", "traffic"}
+
+
+def test_bench_plain_line_and_dump_outputs(dev, flags, tmp_path):
+    """a plain bench.py run prints the headline only (no --full figures) and --dump-outputs writes the last timed step's
+    feat (whole at this size) and every parameter gradient as float32 .npy; two runs with the same arguments agree"""
+    import json, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    outs = []
+    for run in ("a", "b"):
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2",
+                              "--batch", "2", "--points", "256", "--dump-outputs", str(tmp_path / run)],
+                             capture_output=True, text=True, timeout=300)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, out.stdout
+        line = json.loads(lines[0])
+        assert line["steps"] == 3 and line["warmup"] == 2 and line["value"] > 0 and line["ms_per_step"] > 0
+        assert line["metric"].startswith("point-clouds/sec (N=256)") and line["dtype"] == "f32" and line["higher_is_better"] is True
+        assert line["roofline"] is None and "cpu_baseline" not in line and "u3_ms_per_step" not in line["config"]
+        files = sorted(os.listdir(tmp_path / run))
+        outs.append({f[:-4]: np.load(tmp_path / run / f) for f in files})
+    from hs_pose_amd.FaceRecon import FaceRecon
+    flags.train = 0                                    # bench.py's network: the backbone without the train-only heads
+    names = {"grad." + n for n, _ in FaceRecon().named_parameters()}
+    a, b = outs
+    assert set(a) == names | {"feat"} and a["feat"].shape == (2, 256, 1286)
+    assert all(v.dtype == np.float32 for v in a.values()) and sum(v.nbytes for v in a.values()) <= 64_000_000
+    assert np.abs(a["feat"]).max() > 0 and np.abs(a["feat"] - b["feat"]).max() <= 1e-5 * np.abs(a["feat"]).max()
+    for k in names:
+        assert a[k].shape == b[k].shape
+        assert np.abs(a[k] - b[k]).max() <= 1e-4 * max(np.abs(a[k]).max(), 1e-30), k
 
 
 @pytest.mark.skipif(torch.cuda.device_count() < 2, reason="needs >= 2 GPUs on the node (RCCL over xGMI)")

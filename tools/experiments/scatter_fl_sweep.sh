@@ -6,5 +6,5 @@ for v in base fl8 fl16; do
   rocprofv3 --kernel-trace --output-format csv -d /tmp/o_$v -- python $R/tools/time_scatter.py > /dev/null 2>&1
   T=$(find /tmp/o_$v -name '*kernel_trace.csv' | head -1)
   python $R/tools/trace_grep.py $T scatter_tile
-  python $R/bench.py --no-cpu-baseline --no-u3 --no-side | cut -c1-110
+  python $R/bench.py --full --no-cpu-baseline --no-u3 --no-side | cut -c1-110
 done

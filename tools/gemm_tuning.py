@@ -50,7 +50,7 @@ def enable(tune_missing=True, max_tuning_ms=30):
 
 def save(path=None):
     """write the merged table (shipped entries + what this process tuned) -- how tools/tuning/ is regenerated:
-    HSP_TUNABLEOP_OUT=<file> python tools/bench_train_step.py ; python tools/bench_infer.py ; python bench.py"""
+    HSP_TUNABLEOP_OUT=<file> python tools/bench_train_step.py ; python tools/bench_infer.py ; python bench.py --full"""
     path = path or os.environ.get("HSP_TUNABLEOP_OUT")
     fn = getattr(torch.cuda.tunable, "write_file", None)    # (this torch build appends to the file as it tunes)
     if _enabled and path and fn is not None:

@@ -6,7 +6,7 @@ R=$GRAFT_REPO_ROOT
 for c in FETCH_SIZE WRITE_SIZE; do
   OUT=$R/gpurun_out/pmc_$1_$c
   mkdir -p $OUT
-  rocprofv3 --kernel-trace --pmc $c --output-format csv -d $OUT -- python $R/bench.py --steps 4 --warmup 2 --no-graph --no-cpu-baseline > $OUT/bench.log 2>&1
+  rocprofv3 --kernel-trace --pmc $c --output-format csv -d $OUT -- python $R/bench.py --full --steps 4 --warmup 2 --no-graph --no-cpu-baseline > $OUT/bench.log 2>&1
   f=$(find $OUT -name '*counter_collection.csv' | head -1)
   cp "$f" $R/gpurun_out/pmc_$1_$c.csv
   tail -1 $OUT/bench.log | cut -c1-120

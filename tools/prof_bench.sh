@@ -4,7 +4,7 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/prof_$1
 mkdir -p $OUT
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -- python $R/bench.py --steps 50 --warmup 10 > $OUT/bench.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -- python $R/bench.py --full --steps 50 --warmup 10 > $OUT/bench.log 2>&1
 f=$(find $OUT -name '*kernel_stats.csv' | head -1)
 cp $f $OUT/kernel_stats.csv
 tail -1 $OUT/bench.log | cut -c1-200
