@@ -18,7 +18,13 @@ from .config import FLAGS
 
 def _conv_bn_relu_rows(seq, x, n_blocks, first=None):
     """Apply n_blocks x (Conv1d k=1, BatchNorm1d, ReLU) of an nn.Sequential to (R, C) rows.  first: the first Conv1d's output when
-    the caller already has it, as (rows, BatchNorm first-pass buffer) (``ops.fan_linear_rows``)."""
+    the caller already has it, as (rows, BatchNorm first-pass buffer) (``ops.fan_linear_rows``).  bf16 rows (or a bf16 ``first``:
+    then the first block's finished output, ``ops_bf16.fan_bn`` / ``cloud_cat_bn``): one ``ops_bf16.dense_bn`` node per block."""
+    if (x.dtype if x is not None else getattr(first, "dtype", None)) == torch.bfloat16:
+        for i in range(n_blocks):
+            conv, bn = seq[3 * i], seq[3 * i + 1]
+            x = first if (i == 0 and first is not None) else ops_bf16.dense_bn(x, conv.weight.squeeze(-1), conv.bias, bn)
+        return x
     for i in range(n_blocks):
         conv, bn = seq[3 * i], seq[3 * i + 1]
         y, part = first if (i == 0 and first is not None) else ops.linear_rows(x, conv.weight.squeeze(-1), conv.bias, bn_partials=True)
@@ -70,27 +76,52 @@ class FaceRecon(nn.Module):
     def set_feature_dtype(self, dtype):
         """torch.bfloat16: the HS stack stores its feature rows, ``fm`` and activation gradients in bf16 and runs its dense
         products on the bf16 matrix cores (BASELINE configs[3]; hs_pose_amd/ops_bf16.py says what stays fp32); ``feat``
-        comes out bf16.  The parameters stay fp32 masters -- call again after anything that re-seats them (moving the
-        module, building the fused optimizer).  torch.float32 restores the default path."""
+        comes out bf16.  With FLAGS.train the reconstruction and face heads follow (bf16 rows between their layers, fp32 where a
+        product feeds BatchNorm and in the 3- / 30-wide outputs; ops_bf16).  The parameters stay fp32 masters -- call again after
+        anything that re-seats them (moving the module, building the fused optimizer; ``train.TrainDriver`` does it).
+        torch.float32 restores the default path.  ``exact_train`` / the eval-mode reference-order arithmetic and
+        HSP_DETERMINISTIC are fp32-only."""
+        return self._apply_feature_dtype(dtype)
+
+    def _apply_feature_dtype(self, dtype, extra_specs=()):
+        """set_feature_dtype; ``extra_specs``: working copies of other layers (PoseNet9D's pose heads) refreshed by the same launch"""
         if dtype not in (torch.float32, torch.bfloat16):
             raise ValueError("feature dtype: torch.float32 or torch.bfloat16")
-        if dtype == torch.bfloat16 and FLAGS.train:             # (checked before anything is changed: the module stays fp32)
-            raise NotImplementedError("bf16 feature rows: the HS stack (feat); the train-only heads take fp32 rows")
         self.feature_dtype = dtype
         self.conv_0.out_dtype = dtype
         for layer in (self.conv_1, self.conv_2, self.conv_3):          # BatchNorm follows: fp32 rows out of the bf16 layer
             layer.out_fp32 = dtype == torch.bfloat16
         self._bf16 = None
         if dtype == torch.bfloat16:
-            # DETACHED views: a view with a grad_fn would create (and keep alive) the parameter's gradient accumulator bound
-            # to whatever stream is current here, and a later backward inside a hipGraph capture would then hop to that
-            # stream (an event on the null stream inside a capture crashes hipStreamEndCapture)
-            specs = [(self.conv_0.conv2.weight.detach().squeeze(-1), True, True)]
-            for layer in (self.conv_1, self.conv_2, self.conv_3, self.conv_4):
-                specs += [(layer.weights.detach(), True, True), (layer.STE_layer.weight.detach().squeeze(-1), True, True),
-                          (layer.conv2.weight.detach().squeeze(-1), True, True)]
-            self._bf16 = ops_bf16.Bf16Params(specs)
+            self._bf16 = ops_bf16.Bf16Params(self._bf16_specs_all() + list(extra_specs))
         return self
+
+    def _bf16_specs_all(self):
+        """working-copy specs of the stack's products and (FLAGS.train) of the heads'"""
+        # DETACHED views: a view with a grad_fn would create (and keep alive) the parameter's gradient accumulator bound
+        # to whatever stream is current here, and a later backward inside a hipGraph capture would then hop to that
+        # stream (an event on the null stream inside a capture crashes hipStreamEndCapture)
+        specs = [(self.conv_0.conv2.weight.detach().squeeze(-1), True, True)]
+        for layer in (self.conv_1, self.conv_2, self.conv_3, self.conv_4):
+            specs += [(layer.weights.detach(), True, True), (layer.STE_layer.weight.detach().squeeze(-1), True, True),
+                      (layer.conv2.weight.detach().squeeze(-1), True, True)]
+        return specs + self.head_bf16_specs()
+
+    def head_bf16_specs(self):
+        """working-copy specs (ops_bf16.Bf16Params) of the train-only heads' products: the (N,K) copy each forward product reads
+        -- on a 16-byte pitch for conv1d_block[0]'s K = 1286, only the x block [512, 768) of face_head[0] (f_global's columns are a
+        per-cloud fp32 bias, the coordinates an fp32 epilogue) -- and the transpose each input gradient reads (none for the 3- /
+        30-wide last layers)"""
+        if not FLAGS.train:
+            return []
+        w = lambda m: m.weight.detach().squeeze(-1)             # noqa: E731  (detached views: see set_feature_dtype)
+        cg = self.conv_4.out_channel                            # f_global's width; then h (256) and the 3 coordinates
+        cx = self.face_head[0].weight.shape[1] - cg - 3
+        specs = [(w(self.conv1d_block[0]), True, True, True), (w(self.conv1d_block[3]), True, True),
+                 (w(self.conv1d_block[6]), True, True), (w(self.recon_head[0]), True, True), (w(self.recon_head[3]), True, False),
+                 (w(self.face_head[0])[:, cg:cg + cx], True, True), (w(self.face_head[3]), True, True),
+                 (w(self.face_head[6]), True, True), (w(self.face_head[9]), True, False)]
+        return specs
 
     def forward(self, vertices: "tensor (bs, vetice_num, 3)", cat_id: "tensor (bs, 1)"):
         """-> (recon (bs,N,3) | None, face (bs,N,face_recon_c) | None, feat (bs,N,1286))"""
@@ -188,7 +219,11 @@ class FaceRecon(nn.Module):
             last = self.recon_head[3]
             recon = ops.linear_rows(r, last.weight.squeeze(-1), last.bias).view(bs, vertice_num, -1)
             w0 = self.face_head[0].weight.squeeze(-1)
-            if ops.cloud_cat_linear_ok(f_global, h, vertices, w0):
+            if h.dtype == torch.bfloat16:
+                # bf16: cat[f_global, h, xyz] as ops._CloudCatLinear forms it, its BatchNorm + ReLU in the same node
+                f0 = ops_bf16.cloud_cat_bn(f_global, h, vertices, w0, self.face_head[0].bias, self.face_head[1])
+                f = _conv_bn_relu_rows(self.face_head, None, 3, first=f0)
+            elif ops.cloud_cat_linear_ok(f_global, h, vertices, w0):
                 # cat[f_global over the cloud, h, xyz] (FaceRecon.py:113-116) is never formed: f_global's columns of the first
                 # Conv1d act as a per-cloud bias of a K = 259 product
                 y0 = ops.cloud_cat_linear(f_global, h, vertices, w0, self.face_head[0].bias)

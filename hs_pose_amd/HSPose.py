@@ -110,6 +110,15 @@ class HSPose(nn.Module):
         from .fused_losses import total_loss
         return total_loss(loss_dict)
 
+    @property
+    def feature_dtype(self):
+        return self.posenet.feature_dtype
+
+    def set_feature_dtype(self, dtype):
+        """the network's feature rows in ``dtype`` (torch.bfloat16 or torch.float32): PoseNet9D.set_feature_dtype.  Returns self."""
+        self.posenet.set_feature_dtype(dtype)
+        return self
+
     graphed_posenet = None
     # device batches take the fused loss kernels; False keeps the torch-op composition of losses.py (the readable statement: tests)
     fused_losses = True
@@ -118,7 +127,12 @@ class HSPose(nn.Module):
         """capture ``posenet`` forward / backward for training batches of this shape (hs_pose_amd.graph.GraphedNetwork);
         ``forward`` then replays the graphs whenever a training batch has a captured shape and runs eagerly otherwise
         (call it once per shape, e.g. also for the last, smaller batch of an epoch).
-        Call it before the first eager backward of the network, with FLAGS.train set as in training."""
+        Call it before the first eager backward of the network, with FLAGS.train set as in training.  fp32 networks only (a
+        bf16 network captures its whole step with graph.GraphedTrainStep)."""
+        if self.feature_dtype != torch.float32:
+            from ._lib import HspError
+            raise HspError("enable_graphed_posenet: fp32 feature rows only; capture a bf16 network's step with "
+                           "graph.GraphedTrainStep")
         from .graph import GraphedNetwork
         runners = dict(self.graphed_posenet or {})
         runners[tuple(PC.shape)] = GraphedNetwork(self.posenet, PC, obj_id)

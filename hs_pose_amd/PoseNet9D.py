@@ -5,7 +5,7 @@ import os
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import ops, ops_bf16
 from .config import FLAGS
 from .FaceRecon import FaceRecon
 from .PoseR import Rot_green, Rot_red
@@ -48,6 +48,27 @@ class PoseNet9D(nn.Module):
         self.face_recon = FaceRecon()
         self.ts = Pose_Ts()
 
+    @property
+    def feature_dtype(self):
+        return self.face_recon.feature_dtype
+
+    def set_feature_dtype(self, dtype):
+        """torch.bfloat16: the whole network on bf16 feature rows -- the HS stack (FaceRecon.set_feature_dtype), with FLAGS.train
+        its reconstruction / face heads, and the three pose heads' conv1 / conv2 (bf16 rows between layers, fp32 where a product
+        feeds BatchNorm; the per-cloud conv3 / conv4 and everything after them stay fp32).  Parameters stay fp32 masters (the
+        state_dict is unchanged); ONE ops_bf16.Bf16Params refreshes every working copy per step.  Call again after anything that
+        re-seats the parameters (``train.TrainDriver`` does after building the fused optimizer).  torch.float32 restores the
+        default path.  ``exact_train`` / the eval-mode reference-order arithmetic and HSP_DETERMINISTIC are fp32-only.
+        Returns self."""
+        specs = []
+        if dtype == torch.bfloat16:
+            k_feat = self.ts.conv1.weight.shape[1] - 3                   # conv1 of the translation head reads cat[feat, xyz]
+            for h in (self.rot_green, self.rot_red):
+                specs += h.bf16_specs()
+            specs += self.ts.bf16_specs(k_feat)
+        self.face_recon._apply_feature_dtype(dtype, specs)              # (one Bf16Params, one refresh per step)
+        return self
+
     def forward(self, points, obj_id):
         if self.face_recon._x3 is None:
             self.face_recon._x3 = ops.X3Planes()
@@ -60,8 +81,16 @@ class PoseNet9D(nn.Module):
         ``_forward`` and returns the reconstruction block's.  None (the caller then runs its own layer) when the shapes /
         GEMM mode are not the fused kernels'."""
         heads = (self.rot_green, self.rot_red, self.ts)
-        layers = [(h.conv1.weight.squeeze(-1), h.conv1.bias) for h in heads]
         blk = self.face_recon.conv1d_block[0] if FLAGS.train else None
+        if rows.dtype == torch.bfloat16:
+            # bf16: one node for the four layers and their BatchNorm + ReLU; the input gradient summed in fp32, rounded once
+            layers = [(h.conv1.weight.squeeze(-1), h.conv1.bias, h.bn1) for h in heads]
+            if blk is not None:
+                layers.append((blk.weight.squeeze(-1), blk.bias, self.face_recon.conv1d_block[1]))
+            outs = ops_bf16.fan_bn(rows, xyz, layers)
+            self._first = outs[:3]
+            return outs[3] if blk is not None else None
+        layers = [(h.conv1.weight.squeeze(-1), h.conv1.bias) for h in heads]
         if blk is not None:
             layers.append((blk.weight.squeeze(-1), blk.bias))
         if not ops.fan_linear_rows_ok(rows, xyz, [w for w, _ in layers]):

@@ -8,7 +8,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import ops
+from . import ops, ops_bf16
 from .config import FLAGS
 
 
@@ -31,8 +31,19 @@ class _PointMLPHead(nn.Module):
 
     def forward_rows(self, x: "(B, N, f)", first=None):
         """first: (conv1's output rows (B*N, 1024), BatchNorm first-pass buffer) when the caller computed it with the other
-        layers that read the same rows (``ops.fan_linear_rows``, PoseNet9D); x then only gives the shape"""
+        layers that read the same rows (``ops.fan_linear_rows``, PoseNet9D); x then only gives the shape.  bf16 x: ``first`` is
+        conv1's finished (bf16) output (``ops_bf16.fan_bn``)"""
         b, n, c = x.shape
+        if x.dtype == torch.bfloat16:
+            # bf16 rows: conv1 / conv2 each one node with its BatchNorm + ReLU (ops_bf16.dense_bn; ``first``: conv1's finished
+            # output from ops_bf16.fan_bn), the max over the points to fp32 per-cloud rows, conv3 / conv4 fp32 as below
+            h = first if first is not None else ops_bf16.dense_bn(x.reshape(b * n, c), self.conv1.weight.squeeze(-1),
+                                                                   self.conv1.bias, self.bn1)
+            h = ops_bf16.dense_bn(h, self.conv2.weight.squeeze(-1), self.conv2.bias, self.bn2)
+            h = ops.points_max(h.view(b, n, -1))                                 # (B,256) fp32
+            h = ops.bn_relu(ops.linear_rows(h, self.conv3.weight.squeeze(-1), self.conv3.bias), self.bn3)
+            h = self.drop1(h)
+            return ops.linear_rows(h, self.conv4.weight.squeeze(-1), self.conv4.bias).contiguous()
         if first is None:
             first = ops.linear_rows(x.reshape(b * n, c), self.conv1.weight.squeeze(-1), self.conv1.bias, bn_partials=True)
         # fused BatchNorm + ReLU; the products leave the BatchNorms' first pass (per-tile column sums) in their epilogues
@@ -43,6 +54,13 @@ class _PointMLPHead(nn.Module):
         h = ops.bn_relu(ops.linear_rows(h, self.conv3.weight.squeeze(-1), self.conv3.bias), self.bn3)
         h = self.drop1(h)
         return ops.linear_rows(h, self.conv4.weight.squeeze(-1), self.conv4.bias).contiguous()
+
+    def bf16_specs(self, k_feat=None):
+        """working copies (ops_bf16.Bf16Params) of conv1 (its first ``k_feat`` columns on a 16-byte pitch: the bf16 product
+        reads feat, the coordinate columns ride as an fp32 epilogue) and conv2; conv3 / conv4 read fp32 per-cloud rows"""
+        w1 = self.conv1.weight.detach().squeeze(-1)
+        w1 = w1[:, :k_feat] if k_feat is not None else w1
+        return [(w1, True, True, True), (self.conv2.weight.detach().squeeze(-1), True, True)]
 
     def forward(self, x: "(B, f, N)"):
         return self.forward_rows(x.transpose(1, 2))

@@ -76,6 +76,16 @@ SIGNATURES = {
     "hsp_bn_relu_apply_mixed": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
     "hsp_bn_relu_bwd_mixed": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "hsp_cast_params_bf16": (_i, [_vp, _i, _i, _vp]),
+    "hsp_cast_params_pitched_bf16": (_i, [_vp, _i, _i, _vp]),
+    "hsp_wgrad_ragged_bf16": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _sz, _vp]),
+    "hsp_wgrad_ragged_partial_bf16": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _sz, _vp, _vp]),
+    "hsp_gemm_rows_acc_bf16": (_i, [_vp, _i, _vp, _i, _i, _vp, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _i, _vp, _sz, _vp]),
+    "hsp_points_max_fwd_bf16": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
+    "hsp_gemm_rows_bn_tiles_bf16": (_i, [_i, _i, _i]),
+    "hsp_gemm_rows_bn_bf16": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
+    "hsp_bn_relu_fwd_partials_mixed": (_i, [_vp, _i, _i, _vp, _vp, ctypes.c_float, ctypes.c_float, _i, _vp, _vp, _vp, _vp, _vp, _vp,
+                                            _vp, _i, _vp, _vp]),
+    "hsp_points_max_bwd_bf16": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
     "hsp_knn_bf16": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "hsp_rf_surface_fwd_bf16": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "hsp_rf_surface_bwd_bf16": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),

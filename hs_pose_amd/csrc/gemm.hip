@@ -288,7 +288,10 @@ __global__ __launch_bounds__(256) void step_fold_kernel(const StepFoldTab tab) {
 // The kernel is HBM-bound (one pass over A and B): 8 loads of 16 bytes per thread in flight, 2 workgroups per CU.
 using bf16x8_t = __attribute__((ext_vector_type(8))) __bf16;
 
-template <bool COLSUM>
+// RAGGED: M need not be a multiple of 128 (the heads' first layers read the 1286 columns of feat): the last row tile loads the
+// 8-column chunks below ceil8(M) <= lda -- feat's rows sit on a 16-byte pitch with zeroed pad columns -- the chunks above it
+// enter as zeros, and the partial tile keeps its rows below M.
+template <bool COLSUM, bool RAGGED = false>
 __global__ __launch_bounds__(256) void wgrad_bf16_mfma_kernel(const unsigned short* __restrict__ A, int lda,
                                                               const unsigned short* __restrict__ B, int ldb, int M, int N,
                                                               int K, int kslice, float* __restrict__ part,
@@ -298,7 +301,7 @@ __global__ __launch_bounds__(256) void wgrad_bf16_mfma_kernel(const unsigned sho
     constexpr int STAGE = 2 * OP_BYTES;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int tiles_m = M >> 7, tiles = tiles_m * (N >> 7);
+    const int tiles_m = RAGGED ? (M + 127) >> 7 : M >> 7, tiles = tiles_m * (N >> 7);
     const int slice = blockIdx.x / tiles, t = blockIdx.x - slice * tiles;
     const int tn = t / tiles_m, tm = t - tn * tiles_m;
     const int m0 = tm << 7, n0 = tn << 7;
@@ -310,6 +313,7 @@ __global__ __launch_bounds__(256) void wgrad_bf16_mfma_kernel(const unsigned sho
     const int kb8 = id >> 4, mc = id & 15;
     const unsigned short* src = half ? B + n0 + mc * 8 : A + m0 + mc * 8;
     const int ld = half ? ldb : lda;
+    const bool live = !RAGGED || half || m0 + mc * 8 < M;          // (RAGGED: a chunk wholly past M is not loaded)
     char* const img = smem + half * OP_BYTES;
 
     uint4 r[8];
@@ -321,7 +325,7 @@ __global__ __launch_bounds__(256) void wgrad_bf16_mfma_kernel(const unsigned sho
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const int row = kr + j < k1 ? kr + j : k1 - 1;                  // clamped (branch-free); zeroed in stash
-            r[j] = *reinterpret_cast<const uint4*>(src + (size_t)row * ld);
+            r[j] = live ? *reinterpret_cast<const uint4*>(src + (size_t)row * ld) : make_uint4(0u, 0u, 0u, 0u);
         }
     };
     auto stash = [&](int b, int buf) {
@@ -412,7 +416,7 @@ __global__ __launch_bounds__(256) void wgrad_bf16_mfma_kernel(const unsigned sho
 #pragma unroll
             for (int q = 0; q < 16; ++q) {
                 const int row = m0 + wm0 + 32 * x + (q & 3) + 8 * (q >> 2) + 4 * lh;
-                pc[(size_t)row * N + n0 + wn0 + 32 * y + li] = acc[x][y][q];
+                if (!RAGGED || row < M) pc[(size_t)row * N + n0 + wn0 + 32 * y + li] = acc[x][y][q];
             }
     if (COLSUM && tm == 0) {
         float* red = reinterpret_cast<float*>(smem);          // [8 k octets][128 columns]  (all stages are dead here)
@@ -693,26 +697,32 @@ static int wgrad_launch(const FT* A, int lda, const FT* B, int ldb, int M, int N
 
 template <typename FT>
 static int wgrad_impl(const FT* A, int lda, const FT* B, int ldb, int M, int N, int K, float* C, int ldc,
-                      float* colsum_B, void* ws, size_t ws_bytes, hspStream_t stream, HspWgradPending* pending = nullptr) {
+                      float* colsum_B, void* ws, size_t ws_bytes, hspStream_t stream, HspWgradPending* pending = nullptr,
+                      bool bf16_ragged = false) {
     if (!A || !B || !C || M <= 0 || N <= 0 || K <= 0 || lda < M || ldb < N || ldc < N) return HSP_ERR_BAD_ARG;
-    const bool ragged = sizeof(FT) == 4 && wgrad_ragged_m(M, N);                       // fp32 rows, x3 form only
-    if (ragged && !wgrad_x3_ok(A, lda, B, ldb, M, N)) return HSP_ERR_UNSUPPORTED;
+    // ragged M: fp32 rows on the x3 form; bf16 rows (hsp_wgrad_ragged_bf16 only) on the bf16-MFMA form, A's rows on a 16-byte
+    // pitch that covers ceil8(M)
+    const bool ragged = (sizeof(FT) == 4 || bf16_ragged) && wgrad_ragged_m(M, N);
+    if (ragged && sizeof(FT) == 4 && !wgrad_x3_ok(A, lda, B, ldb, M, N)) return HSP_ERR_UNSUPPORTED;
+    if (ragged && sizeof(FT) == 2 &&
+        ((lda & 7) || (ldb & 7) || lda < ((M + 7) & ~7) || ((reinterpret_cast<size_t>(A) | reinterpret_cast<size_t>(B)) & 15)))
+        return HSP_ERR_UNSUPPORTED;
     if (!ragged && ((M & 63) || (N & 63) || (lda & 1) || (ldb & 1))) return HSP_ERR_UNSUPPORTED;   // 64x64 wave tiles, float2 loads
     if (!ws || ws_bytes < hsp_wgrad_workspace_bytes(M, N, K)) return HSP_ERR_WORKSPACE;
     int ks, kb;
     hipStream_t st = as_stream(stream);
     if constexpr (sizeof(FT) == 2) {
-        if (wgrad_bf16_mfma_ok(A, lda, B, ldb, M, N)) {
+        if (ragged || wgrad_bf16_mfma_ok(A, lda, B, ldb, M, N)) {
             const int sk2 = wgrad_bf16_pick(M, N, K, &ks);
             float* part = reinterpret_cast<float*>(ws);
             float* cs_part = part + (size_t)sk2 * M * N;
-            const int grid = (M >> 7) * (N >> 7) * sk2;
+            const int grid = ((M + 127) >> 7) * (N >> 7) * sk2;
             const int lds = 4 * 128 * 128;
             const unsigned short* a = reinterpret_cast<const unsigned short*>(A);
             const unsigned short* b = reinterpret_cast<const unsigned short*>(B);
-#define WG_BF16_LAUNCH(CS)                                                                                                      \
+#define WG_BF16_LAUNCH(CS, RG)                                                                                                  \
     do {                                                                                                                       \
-        auto kern = wgrad_bf16_mfma_kernel<CS>;                                                                                \
+        auto kern = wgrad_bf16_mfma_kernel<CS, RG>;                                                                            \
         static bool attr_set = false;                                                                                          \
         if (!attr_set) {                                                                                                       \
             hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds); \
@@ -721,7 +731,11 @@ static int wgrad_impl(const FT* A, int lda, const FT* B, int ldb, int M, int N, 
         }                                                                                                                      \
         hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, a, lda, b, ldb, M, N, K, ks, part, cs_part);                   \
     } while (0)
-            if (colsum_B) WG_BF16_LAUNCH(true); else WG_BF16_LAUNCH(false);
+            if (ragged) {
+                if (colsum_B) WG_BF16_LAUNCH(true, true); else WG_BF16_LAUNCH(false, true);
+            } else {
+                if (colsum_B) WG_BF16_LAUNCH(true, false); else WG_BF16_LAUNCH(false, false);
+            }
 #undef WG_BF16_LAUNCH
             int rc = check_launch();
             if (rc) return rc;
@@ -772,6 +786,19 @@ extern "C" int hsp_wgrad_f32(const float* A, int lda, const float* B, int ldb, i
 extern "C" int hsp_wgrad_bf16(const hsp_bf16_t* A, int lda, const hsp_bf16_t* B, int ldb, int M, int N, int K, float* C,
                               int ldc, float* colsum_B, void* ws, size_t ws_bytes, hspStream_t stream) {
     return wgrad_impl<bf16_t>(A, lda, B, ldb, M, N, K, C, ldc, colsum_B, ws, ws_bytes, stream);
+}
+
+/* ragged form: M need not be a multiple of 64 (N a multiple of 128, A on a 16-byte pitch >= ceil8(M)); other shapes as
+ * hsp_wgrad_bf16 */
+extern "C" int hsp_wgrad_ragged_bf16(const hsp_bf16_t* A, int lda, const hsp_bf16_t* B, int ldb, int M, int N, int K, float* C,
+                                     int ldc, float* colsum_B, void* ws, size_t ws_bytes, hspStream_t stream) {
+    return wgrad_impl<bf16_t>(A, lda, B, ldb, M, N, K, C, ldc, colsum_B, ws, ws_bytes, stream, nullptr, true);
+}
+extern "C" int hsp_wgrad_ragged_partial_bf16(const hsp_bf16_t* A, int lda, const hsp_bf16_t* B, int ldb, int M, int N, int K,
+                                             float* C, int ldc, float* colsum_B, void* ws, size_t ws_bytes,
+                                             HspWgradPending* pending, hspStream_t stream) {
+    if (!pending) return HSP_ERR_BAD_ARG;
+    return wgrad_impl<bf16_t>(A, lda, B, ldb, M, N, K, C, ldc, colsum_B, ws, ws_bytes, stream, pending, true);
 }
 
 /* split forms: the partial-sum launch only (the fold is left pending), and one fold launch for up to 4 pending problems */

@@ -49,11 +49,13 @@ struct GemmRowsArgs {
     void* C; int ldc;
     int M, N;
     const float* bias;                     // (N) fp32 or null
-    const void* resid; int ldr;            // (M,N) of the output type or null
+    const void* resid; int ldr;            // (M,N) of the operand type (fp32 when r_f32) or null
+    int r_f32;                             // bf16 operands: resid is fp32 (a sum carried in fp32 across several products)
     const float* cbias; int rows_per_cloud;  // (ceil(M / rows_per_cloud), N) fp32 or null
     float alpha;                           // scales the accumulated products (before bias / resid / cloud bias)
     const float* xyz3; const float* w3;    // rank-3 fp32 update + xyz3[row] . w3[col] ((M,3), (N,3)) or null
     int c_f32;                             // bf16 operands: write C as fp32 (a tensor that feeds BatchNorm keeps its mantissa)
+    float* bn_shift; float* bn_part;       // BNP kernels: the BatchNorm first pass of C (shift (N), per row tile [tiles_m][2][N])
     int nsplit; float* ws;                 // split-K: nsplit > 1 -> raw fp32 partial tiles to ws[split][M][N], folded (with the
                                            // whole epilogue) by gemm_rows_reduce_kernel
     int tiles_m, tiles_n;
@@ -73,7 +75,10 @@ __device__ __forceinline__ unsigned short f32_to_bf16(float f) {              //
 // LB1 / LB2: layout of B1 / B2 -- 1 "nt" (N,K) k contiguous, 2 "nn" (K,N) n contiguous (fp32 only), 0 (LB2) = no 2nd source.
 // MODE 1: every operand 16-byte aligned (base and row pitch): 16-byte staging loads; MODE 2: 8-byte aligned (an even fp32
 // pitch such as 1286): 8-byte pieces; MODE 0: 4-byte pieces (any alignment).
-template <typename T, int WM, int WN, int LB1, int LB2, int MODE>
+// BNP: the result also leaves the first pass of the train-mode BatchNorm that follows it (bf16 operands, fp32 C, no split-K):
+// per row tile of BM rows the shifted column sums sum (c - s), sum (c - s)^2 -- shift s[n] = bias[n] + cloud_bias[0][n], written
+// to bn_shift -- in the [tile][2][N] layout bn_finalize_kernel folds (norm.hip; fixed order: lane halves, then the row waves)
+template <typename T, int WM, int WN, int LB1, int LB2, int MODE, bool BNP = false>
 __global__ __launch_bounds__(256) void gemm_rows_kernel(const GemmRowsArgs g) {
     constexpr int ES = sizeof(T);
     constexpr int EPC = 16 / ES;                 // elements per 16-byte chunk
@@ -289,7 +294,10 @@ __global__ __launch_bounds__(256) void gemm_rows_kernel(const GemmRowsArgs g) {
     // ---- write a finished item: accumulator r of (x,y) <-> row wm0 + 32x + (r&3) + 8(r>>2) + 4 lh, column wn0 + 32y + li
     // (a row-per-lane form -- MFMA operands swapped, 8-byte stores of 4 consecutive columns -- was measured slower: a store
     // instruction then touches 32 rows instead of 2)
+    float bn1_out[WN], bn2_out[WN];                   // (BNP) per column of this lane: sum (v - shift), sum (v - shift)^2
     auto epilogue = [&](int m0, int n0, int ks) {
+#pragma unroll
+        for (int y = 0; y < WN; ++y) { bn1_out[y] = 0.f; bn2_out[y] = 0.f; }
         if (g.nsplit > 1) {                                   // raw partial tile; the reduce kernel applies the epilogue
             float* wsp = g.ws + (size_t)ks * g.M * g.N;
 #pragma unroll
@@ -319,6 +327,11 @@ __global__ __launch_bounds__(256) void gemm_rows_kernel(const GemmRowsArgs g) {
             const float bv = (g.bias && cok) ? g.bias[col] : 0.f;
             float w30 = 0.f, w31 = 0.f, w32 = 0.f;
             if (g.xyz3 && cok) { w30 = g.w3[col * 3]; w31 = g.w3[col * 3 + 1]; w32 = g.w3[col * 3 + 2]; }
+            float bsh = 0.f;
+            if constexpr (BNP) {
+                bsh = bv + ((g.cbias && cok) ? g.cbias[col] : 0.f);
+                if (m0 == 0 && wm0 == 0 && lh == 0 && cok) g.bn_shift[col] = bsh;
+            }
 #pragma unroll
             for (int x = 0; x < WM; ++x) {
                 float keep[16];                               // (bf16 output) finished values, packed in pairs below
@@ -330,7 +343,7 @@ __global__ __launch_bounds__(256) void gemm_rows_kernel(const GemmRowsArgs g) {
                     keep[r] = 0.f;
                     if (!cok || row >= g.M) continue;
                     if (g.resid) {
-                        if (ES == 4) v += reinterpret_cast<const float*>(g.resid)[(size_t)row * g.ldr + col];
+                        if (ES == 4 || g.r_f32) v += reinterpret_cast<const float*>(g.resid)[(size_t)row * g.ldr + col];
                         else v += bf16_to_f32(reinterpret_cast<const unsigned short*>(g.resid)[(size_t)row * g.ldr + col]);
                     }
                     if (g.xyz3) {      // the K = 3 product on raw fp32 coordinates (HSlayer_surface's STE, gcn3d.py:85)
@@ -341,6 +354,11 @@ __global__ __launch_bounds__(256) void gemm_rows_kernel(const GemmRowsArgs g) {
                         int c = c0;
                         if (row >= nb) c = c0 + 1 + (row - nb) / rpc;      // rare: the tile spans clouds
                         v += g.cbias[(size_t)c * g.N + col];
+                    }
+                    if constexpr (BNP) {
+                        const float d = v - bsh;
+                        bn1_out[y] += d;
+                        bn2_out[y] += d * d;
                     }
                     if (ES == 4 || g.c_f32) reinterpret_cast<float*>(g.C)[(size_t)row * g.ldc + col] = v;
                     else if (!pack2) reinterpret_cast<unsigned short*>(g.C)[(size_t)row * g.ldc + col] = f32_to_bf16(v);
@@ -411,6 +429,26 @@ __global__ __launch_bounds__(256) void gemm_rows_kernel(const GemmRowsArgs g) {
             cur ^= 1;
         }
         epilogue(it.m0, it.n0, it.ks);
+        if constexpr (BNP) {
+            // the tile's column sums: lane halves by a shuffle, the two row waves through a small LDS array of their own (the
+            // staging buffers hold the next item's first block by now)
+            __shared__ float red[2][2][64 * WN];
+#pragma unroll
+            for (int y = 0; y < WN; ++y) {
+                const float a = bn1_out[y] + __shfl_xor(bn1_out[y], 32, 64), b = bn2_out[y] + __shfl_xor(bn2_out[y], 32, 64);
+                if (lh == 0) {
+                    red[wave >> 1][0][wn0 + 32 * y + li] = a;
+                    red[wave >> 1][1][wn0 + 32 * y + li] = b;
+                }
+            }
+            __syncthreads();
+            const int tm = it.m0 / (64 * WM);
+            if (tid < 64 * WN && it.n0 + tid < g.N) {
+                g.bn_part[((size_t)tm * 2 + 0) * g.N + it.n0 + tid] = red[0][0][tid] + red[1][0][tid];
+                g.bn_part[((size_t)tm * 2 + 1) * g.N + it.n0 + tid] = red[0][1][tid] + red[1][1][tid];
+            }
+            __syncthreads();                              // (red is rewritten by the next item)
+        }
     }
 }
 
@@ -427,7 +465,7 @@ __global__ __launch_bounds__(256) void gemm_rows_reduce_kernel(const GemmRowsArg
         float v = g.alpha * (s0 + s1);
         if (g.bias) v += g.bias[col];
         if (g.resid) {
-            if (sizeof(T) == 4) v += reinterpret_cast<const float*>(g.resid)[(size_t)row * g.ldr + col];
+            if (sizeof(T) == 4 || g.r_f32) v += reinterpret_cast<const float*>(g.resid)[(size_t)row * g.ldr + col];
             else v += bf16_to_f32(reinterpret_cast<const unsigned short*>(g.resid)[(size_t)row * g.ldr + col]);
         }
         if (g.xyz3) {
@@ -467,7 +505,7 @@ static int launch_cfg(const GemmRowsArgs& a, int lb1, int lb2, float* a_ws, size
     {   // split-K when the tiles alone cannot fill the chip and K is deep (the input-gradient products: 64 tiles x K = 4608)
         constexpr int BKE = 128 / ES;
         const int TT = (a.K1 + BKE - 1) / BKE + (lb2 ? (a.K2 + BKE - 1) / BKE : 0);
-        int ns = gemm_rows_pick_split((long long)g.tiles_m * g.tiles_n, TT);
+        int ns = a.bn_part ? 1 : gemm_rows_pick_split((long long)g.tiles_m * g.tiles_n, TT);
         if ((size_t)ns * a.M * a.N * sizeof(float) > a_ws_bytes) ns = 1;          // no (or too small a) workspace: unsplit
         g.nsplit = ns;
         g.ws = ns > 1 ? a_ws : nullptr;
@@ -480,9 +518,9 @@ static int launch_cfg(const GemmRowsArgs& a, int lb1, int lb2, float* a_ws, size
     if (nb > tiles) nb = tiles;
     nb = (nb + 7) / 8 * 8;
     const dim3 grid((unsigned)nb), block(256);
-#define GR_LAUNCH(L1, L2)                                                                                               \
+#define GR_LAUNCH(L1, L2, BNP)                                                                                          \
     do {                                                                                                               \
-        auto kern = gemm_rows_kernel<T, WM, WN, L1, L2, MODE>;                                                         \
+        auto kern = gemm_rows_kernel<T, WM, WN, L1, L2, MODE, BNP>;                                                    \
         static bool attr_set = false;                                                                                  \
         if (!attr_set) {                                                                                               \
             hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                                    \
@@ -501,13 +539,17 @@ static int launch_cfg(const GemmRowsArgs& a, int lb1, int lb2, float* a_ws, size
     } while (0)
     // layouts on this path: X W ("nn"), x W^T ("nt"), X Wste^T + F Wa^T ("nt" + "nt"), g Wste + gfm W^T ("nn" + "nt")
     if constexpr (ES == 4) {
-        if (lb1 == 1 && lb2 == 0) GR_LAUNCH(1, 0);
-        if (lb1 == 2 && lb2 == 0) GR_LAUNCH(2, 0);
-        if (lb1 == 1 && lb2 == 1) GR_LAUNCH(1, 1);
-        if (lb1 == 2 && lb2 == 1) GR_LAUNCH(2, 1);
+        if (lb1 == 1 && lb2 == 0) GR_LAUNCH(1, 0, false);
+        if (lb1 == 2 && lb2 == 0) GR_LAUNCH(2, 0, false);
+        if (lb1 == 1 && lb2 == 1) GR_LAUNCH(1, 1, false);
+        if (lb1 == 2 && lb2 == 1) GR_LAUNCH(2, 1, false);
     } else {
-        if (lb1 == 1 && lb2 == 0) GR_LAUNCH(1, 0);
-        if (lb1 == 1 && lb2 == 1) GR_LAUNCH(1, 1);
+        if (g.bn_part) {                           // (single source, fp32 C: the heads' Conv1d ahead of a BatchNorm)
+            if (lb1 == 1 && lb2 == 0 && g.c_f32) GR_LAUNCH(1, 0, true);
+            return HSP_ERR_UNSUPPORTED;
+        }
+        if (lb1 == 1 && lb2 == 0) GR_LAUNCH(1, 0, false);
+        if (lb1 == 1 && lb2 == 1) GR_LAUNCH(1, 1, false);
     }
 #undef GR_LAUNCH
     return HSP_ERR_UNSUPPORTED;
@@ -540,7 +582,8 @@ template <typename T>
 static int gemm_rows_dispatch(const void* A1, int lda1, const void* B1, int ldb1, int l1, int K1, const void* A2, int lda2,
                               const void* B2, int ldb2, int l2, int K2, int M, int N, const float* bias, const void* resid,
                               int ldr, const float* cbias, int rpc, float alpha, const float* xyz3, const float* w3, void* C, int ldc,
-                              int c_f32, void* ws, size_t ws_bytes, hspStream_t stream) {
+                              int c_f32, void* ws, size_t ws_bytes, hspStream_t stream, int r_f32 = 0,
+                              float* bn_shift = nullptr, float* bn_part = nullptr) {
     constexpr int ES = sizeof(T);
     if (!A1 || !B1 || !C || M <= 0 || N <= 0 || K1 <= 0 || lda1 < K1 || ldc < N) return HSP_ERR_BAD_ARG;
     if (l1 != 0 && l1 != 1) return HSP_ERR_BAD_ARG;
@@ -570,6 +613,8 @@ static int gemm_rows_dispatch(const void* A1, int lda1, const void* B1, int ldb1
     if ((xyz3 == nullptr) != (w3 == nullptr)) return HSP_ERR_BAD_ARG;
     g.xyz3 = xyz3; g.w3 = w3;
     g.c_f32 = c_f32;
+    g.r_f32 = r_f32;
+    g.bn_shift = bn_shift; g.bn_part = bn_part;
     int lb1 = l1 == 0 ? 1 : 2, lb2 = two ? (l2 == 0 ? 1 : 2) : 0;
     if (two && lb1 == 1 && lb2 == 2) {
         const void* t; int ti;
@@ -590,11 +635,20 @@ static int gemm_rows_dispatch(const void* A1, int lda1, const void* B1, int ldb1
 // ---- fp32 master parameters -> bf16 working copies, all tensors of a step in ONE launch --------------------------------
 // entry e: src (rows, cols) fp32 with row pitch ld -> dst (rows, cols) bf16 and / or dstT (cols, rows) bf16 (the (N,K) form
 // the bf16 GEMM wants of a (K,N) matrix).  32 x 32 tiles through LDS: both copies are written in 64-byte row segments.
-__global__ __launch_bounds__(256) void cast_params_kernel(const HspCastDesc* __restrict__ tab, int n) {
+// (pitched form: dst rows ldd apart, dstT rows lddT apart -- a (1024, 1286) copy on a 1288 pitch is the 16-byte aligned (N,K)
+// operand the bf16 GEMM wants for the heads' first layers; the plain form writes dense copies)
+__device__ __forceinline__ int cast_ldd(const HspCastDesc& d) { return d.cols; }
+__device__ __forceinline__ int cast_lddT(const HspCastDesc& d) { return d.rows; }
+__device__ __forceinline__ int cast_ldd(const HspCastPitchedDesc& d) { return d.ldd; }
+__device__ __forceinline__ int cast_lddT(const HspCastPitchedDesc& d) { return d.lddT; }
+
+template <typename Desc>
+__global__ __launch_bounds__(256) void cast_params_kernel(const Desc* __restrict__ tab, int n) {
     __shared__ float tile[32][33];
     int e = 0;
     while (e + 1 < n && (int)blockIdx.x >= tab[e + 1].tile0) ++e;
-    const HspCastDesc d = tab[e];
+    const Desc d = tab[e];
+    const int ldd = cast_ldd(d), lddT = cast_lddT(d);
     const int t = (int)blockIdx.x - d.tile0;
     const int tcols = (d.cols + 31) >> 5;
     const int r0 = (t / tcols) * 32, c0 = (t % tcols) * 32;
@@ -607,7 +661,7 @@ __global__ __launch_bounds__(256) void cast_params_kernel(const HspCastDesc* __r
         float v = 0.f;
         if (r < d.rows && c < d.cols) {
             v = d.src[(size_t)r * d.ld + c];
-            if (dst) dst[(size_t)r * d.cols + c] = (bf16_t)f32_to_bf16_bits(v);
+            if (dst) dst[(size_t)r * ldd + c] = (bf16_t)f32_to_bf16_bits(v);
         }
         tile[ly + 8 * j][lx] = v;
     }
@@ -616,7 +670,7 @@ __global__ __launch_bounds__(256) void cast_params_kernel(const HspCastDesc* __r
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const int c = c0 + ly + 8 * j, r = r0 + lx;
-        if (r < d.rows && c < d.cols) dstT[(size_t)c * d.rows + r] = (bf16_t)f32_to_bf16_bits(tile[lx][ly + 8 * j]);
+        if (r < d.rows && c < d.cols) dstT[(size_t)c * lddT + r] = (bf16_t)f32_to_bf16_bits(tile[lx][ly + 8 * j]);
     }
 }
 
@@ -626,7 +680,13 @@ using namespace hsp;
 
 extern "C" int hsp_cast_params_bf16(const HspCastDesc* table_dev, int n, int total_tiles, hspStream_t stream) {
     if (!table_dev || n <= 0 || total_tiles <= 0) return HSP_ERR_BAD_ARG;
-    hipLaunchKernelGGL(cast_params_kernel, dim3(total_tiles), dim3(256), 0, as_stream(stream), table_dev, n);
+    hipLaunchKernelGGL(cast_params_kernel<HspCastDesc>, dim3(total_tiles), dim3(256), 0, as_stream(stream), table_dev, n);
+    return check_launch();
+}
+
+extern "C" int hsp_cast_params_pitched_bf16(const HspCastPitchedDesc* table_dev, int n, int total_tiles, hspStream_t stream) {
+    if (!table_dev || n <= 0 || total_tiles <= 0) return HSP_ERR_BAD_ARG;
+    hipLaunchKernelGGL(cast_params_kernel<HspCastPitchedDesc>, dim3(total_tiles), dim3(256), 0, as_stream(stream), table_dev, n);
     return check_launch();
 }
 
@@ -658,4 +718,34 @@ extern "C" int hsp_gemm_rows_bf16(const hsp_bf16_t* A1, int lda1, const hsp_bf16
     return gemm_rows_dispatch<unsigned short>(A1, lda1, B1, ldb1, 0, K1, A2, lda2, B2, ldb2, 0, K2, M, N, bias, resid, ldr,
                                               cloud_bias, rows_per_cloud, alpha, xyz3, w3, C, ldc, c_is_f32 ? 1 : 0, ws, ws_bytes,
                                               stream);
+}
+
+/* bf16 operands, fp32 residual: C = A1 B1^T (+ A2 B2^T) + resid with resid fp32 and C fp32 or bf16 -- a sum of more than two
+ * products carried in fp32 and rounded once (the input gradient of feat, which four layers read) */
+extern "C" int hsp_gemm_rows_acc_bf16(const hsp_bf16_t* A1, int lda1, const hsp_bf16_t* B1, int ldb1, int K1,
+                                      const hsp_bf16_t* A2, int lda2, const hsp_bf16_t* B2, int ldb2, int K2, int M, int N,
+                                      const float* resid, int ldr, void* C, int ldc, int c_is_f32, void* ws, size_t ws_bytes,
+                                      hspStream_t stream) {
+    return gemm_rows_dispatch<unsigned short>(A1, lda1, B1, ldb1, 0, K1, A2, lda2, B2, ldb2, 0, K2, M, N, nullptr, resid, ldr,
+                                              nullptr, 0, 1.f, nullptr, nullptr, C, ldc, c_is_f32 ? 1 : 0, ws, ws_bytes, stream, 1);
+}
+
+/* BatchNorm row tiles of hsp_gemm_rows_bn_bf16's result (the row tile of the shape's kernel: 64 or 128 rows) */
+extern "C" int hsp_gemm_rows_bn_tiles_bf16(int M, int N, int K) {
+    if (M <= 0 || N <= 0 || K <= 0) return 0;
+    const int bm = prefer_small_tile(M, N, (K + 63) / 64) ? 64 : 128;
+    return (M + bm - 1) / bm;
+}
+
+/* C (fp32) = A B^T + bias (+ cloud_bias[row / rows_per_cloud]) (+ xyz3 . w3) for bf16 rows A (M,K) and a bf16 (N,K) weight, AND the
+ * first pass of the train-mode BatchNorm over C: bn_shift[n] = bias[n] + cloud_bias[0][n] (0 where absent) and
+ * bn_part[tiles][2][N] = per row tile, sum (c - shift) and sum (c - shift)^2 over the tile's rows, tiles =
+ * hsp_gemm_rows_bn_tiles_bf16(M, N, K) <= 512 -- the layout of hsp_gemm_x3_bias_bn_f32; fold with hsp_bn_relu_fwd_partials(_mixed) */
+extern "C" int hsp_gemm_rows_bn_bf16(const hsp_bf16_t* A, int lda, const hsp_bf16_t* B, int ldb, int K, int M, int N,
+                                     const float* bias, const float* cloud_bias, int rows_per_cloud, const float* xyz3, const float* w3,
+                                     float* C, int ldc, float* bn_shift, float* bn_part, hspStream_t stream) {
+    if (!bn_shift || !bn_part) return HSP_ERR_BAD_ARG;
+    if (hsp_gemm_rows_bn_tiles_bf16(M, N, K) > 512) return HSP_ERR_UNSUPPORTED;
+    return gemm_rows_dispatch<unsigned short>(A, lda, B, ldb, 0, K, nullptr, 0, nullptr, 0, 0, 0, M, N, bias, nullptr, 0, cloud_bias,
+                                              rows_per_cloud, 1.f, xyz3, w3, C, ldc, 1, nullptr, 0, stream, 0, bn_shift, bn_part);
 }

@@ -350,6 +350,23 @@ extern "C" int hsp_bn_relu_fwd_partials(const float* x, int R, int C, const floa
                        gamma, beta, relu, y);
     return check_launch();
 }
+/* the same with bf16 output rows (fp32 x: the "mixed" form) -- the fold of a bf16 product's epilogue (hsp_gemm_rows_bn_bf16) */
+extern "C" int hsp_bn_relu_fwd_partials_mixed(const float* x, int R, int C, const float* gamma, const float* beta, float eps,
+                                              float momentum, int relu, hsp_bf16_t* y, float* save_mean, float* save_invstd,
+                                              float* running_mean, float* running_var, long long* num_batches_tracked,
+                                              const float* partial, int nblk, const float* shift, hspStream_t stream) {
+    if (!x || !gamma || !beta || !y || !save_mean || !save_invstd || !partial || !shift || nblk <= 0 || nblk > BN_MAX_PARTIALS)
+        return HSP_ERR_BAD_ARG;
+    int rc = bn_check(R, C);
+    if (rc) return rc;
+    hipStream_t st = as_stream(stream);
+    hipLaunchKernelGGL((bn_finalize_kernel<0, float>), dim3((C + 15) / 16), dim3(1024), 0, st, partial, nblk, R, C, shift, eps, momentum,
+                       save_mean, save_invstd, running_mean, running_var, num_batches_tracked);
+    const long long total4 = (long long)R * (C >> 2);
+    hipLaunchKernelGGL((bn_apply_kernel<bf16_t, float>), dim3(stream_grid4(total4)), dim3(256), 0, st, x, total4, C, save_mean,
+                       save_invstd, gamma, beta, relu, reinterpret_cast<bf16_t*>(y));
+    return check_launch();
+}
 extern "C" int hsp_bn_relu_fwd_bf16(const hsp_bf16_t* x, int R, int C, const float* gamma, const float* beta, float eps,
                                     float momentum, int relu, hsp_bf16_t* y, float* save_mean, float* save_invstd,
                                     float* running_mean, float* running_var, long long* num_batches_tracked, void* ws,

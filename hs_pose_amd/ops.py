@@ -512,7 +512,11 @@ def pool_layer(feat, xyz, idx, qsel, k):
 
 
 def points_max(x):
-    """max over dim 1 of a point-major (B,N,C) tensor -> (B,C)   (the heads' torch.max(x, 2)[0])."""
+    """max over dim 1 of a point-major (B,N,C) tensor -> (B,C)   (the heads' torch.max(x, 2)[0]); bf16 rows: fp32 (B,C)
+    (ops_bf16)."""
+    if x.dtype == torch.bfloat16:
+        from . import ops_bf16
+        return ops_bf16.points_max(x)
     return _PointsMax.apply(x)
 
 
@@ -653,7 +657,8 @@ def _rf_bwd_dirs_call(name, args_before_ws, ws, wsb, keep, key, abytes):
     sf.dirs.append((pend, ws) + tuple(_hold(t) for t in keep))
 
 
-def _wgrad_custom(A2, B2, out, colsum):
+def _wgrad_custom(A2, B2, out, colsum, entry="hsp_wgrad"):
+    """entry: the family of entry points (``hsp_wgrad`` or, bf16 rows with a ragged M, ``hsp_wgrad_ragged``)"""
     K, M = A2.shape
     N = B2.shape[1]
     cs = torch.empty(N, dtype=torch.float32, device=A2.device) if colsum else None
@@ -668,13 +673,13 @@ def _wgrad_custom(A2, B2, out, colsum):
     if sink is not None:
         from ._lib import HspWgradPending
         pend = HspWgradPending()
-        _run("hsp_wgrad_partial_" + sfx, (_p(A2), A2.stride(0), _p(B2), B2.stride(0), M, N, K, _p(out), out.stride(0), _p(cs),
-                                          _p(ws), wsb, ctypes.byref(pend), _stream()),
+        _run(f"{entry}_partial_{sfx}", (_p(A2), A2.stride(0), _p(B2), B2.stride(0), M, N, K, _p(out), out.stride(0), _p(cs),
+                                        _p(ws), wsb, ctypes.byref(pend), _stream()),
              key=f"M{M}N{N}K{K}", abytes=es * K * (M + N) + 4 * M * N, aflops=2 * M * N * K)
         sink.append((pend, ws, _hold(out), _hold(cs)))
     else:
-        _run("hsp_wgrad_" + sfx, (_p(A2), A2.stride(0), _p(B2), B2.stride(0), M, N, K, _p(out), out.stride(0), _p(cs),
-                                  _p(ws), wsb, _stream()),
+        _run(f"{entry}_{sfx}", (_p(A2), A2.stride(0), _p(B2), B2.stride(0), M, N, K, _p(out), out.stride(0), _p(cs),
+                                _p(ws), wsb, _stream()),
              key=f"M{M}N{N}K{K}", abytes=es * K * (M + N) + 4 * M * N, aflops=2 * M * N * K)
     return (out, cs) if colsum else out
 
@@ -1848,7 +1853,12 @@ def cat_rows_pitched(parts):
 def linear_rows(x2, weight, bias=None, bn_partials=False):
     """F.linear(x2, weight, bias) for (R, Cin) rows with a graph-replayable backward.  ``bn_partials``: returns (y, part) where
     ``part`` is the first pass of a train-mode BatchNorm over y left by the product's epilogue -- hand it to
-    ``bn_relu(y, bn, partial=part)`` -- or an empty tensor when this shape / mode does not produce it."""
+    ``bn_relu(y, bn, partial=part)`` -- or an empty tensor when this shape / mode does not produce it.
+    bf16 rows: fp32 y on the bf16 matrix cores (ops_bf16; ``part`` always empty)."""
+    if x2.dtype == torch.bfloat16:
+        from . import ops_bf16
+        y = ops_bf16.linear_rows(x2, weight, bias)
+        return (y, torch.empty(0, dtype=torch.float32, device=x2.device)) if bn_partials else y
     if bn_partials:
         return _LinearRows.apply(x2, weight, bias, True)
     return _LinearRows.apply(x2, weight, bias)

@@ -32,6 +32,9 @@ class TrainDriver:
             data_parallel = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
         self.data_parallel = bool(data_parallel)
         self.optimizer = optimizer if optimizer is not None else build_optimizer(network.build_params(training_stage_freeze=[]))
+        if getattr(network, "feature_dtype", torch.float32) == torch.bfloat16:
+            # the fused optimizer re-seats the parameters in its flat buffers: fresh bf16 working copies of the new storage
+            network.set_feature_dtype(torch.bfloat16)
         if scheduler is None:
             if total_iters is None:
                 acc = int(accumulate if accumulate is not None else getattr(FLAGS, "accumulate", 1))

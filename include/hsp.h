@@ -398,6 +398,12 @@ int hsp_colsum_rows_xyz_bf16(const hsp_bf16_t *x, const float *xyz, int B, int N
  * rounding to nearest even.  tile0 = number of 32 x 32 tiles of the entries before e; table_dev lives in DEVICE memory. */
 typedef struct HspCastDesc { const float *src; void *dst; void *dstT; int rows, cols, ld, tile0; } HspCastDesc;
 int hsp_cast_params_bf16(const HspCastDesc *table_dev, int n, int total_tiles, hspStream_t stream);
+/* the same with row pitches for the copies (ldd for dst, lddT for dstT, in elements): 16-byte aligned rows for a K = 1286
+ * weight (the heads' first layers on feat) */
+typedef struct HspCastPitchedDesc {
+    const float *src; void *dst; void *dstT; int rows, cols, ld, tile0, ldd, lddT;
+} HspCastPitchedDesc;
+int hsp_cast_params_pitched_bf16(const HspCastPitchedDesc *table_dev, int n, int total_tiles, hspStream_t stream);
 
 /* ---- weight-gradient GEMM ---------------------------------------------------------------------
  * replaces the parameter-gradient matmuls autograd runs for `feature_map @ self.weights + self.bias`
@@ -610,6 +616,34 @@ int hsp_wgrad_bf16(const hsp_bf16_t *A, int lda, const hsp_bf16_t *B, int ldb, i
                    float *colsum_B, void *ws, size_t ws_bytes, hspStream_t stream);
 int hsp_wgrad_partial_bf16(const hsp_bf16_t *A, int lda, const hsp_bf16_t *B, int ldb, int M, int N, int K, float *C, int ldc,
                            float *colsum_B, void *ws, size_t ws_bytes, HspWgradPending *pending, hspStream_t stream);
+/* ragged M (not a multiple of 64; N a multiple of 128): A's rows on a 16-byte pitch >= ceil8(M), e.g. the 1286 columns of feat
+ * on its 1288 pitch.  Other shapes as hsp_wgrad_bf16; same workspace rule (hsp_wgrad_workspace_bytes) and fold */
+int hsp_wgrad_ragged_bf16(const hsp_bf16_t *A, int lda, const hsp_bf16_t *B, int ldb, int M, int N, int K, float *C, int ldc,
+                          float *colsum_B, void *ws, size_t ws_bytes, hspStream_t stream);
+int hsp_wgrad_ragged_partial_bf16(const hsp_bf16_t *A, int lda, const hsp_bf16_t *B, int ldb, int M, int N, int K, float *C,
+                                  int ldc, float *colsum_B, void *ws, size_t ws_bytes, HspWgradPending *pending,
+                                  hspStream_t stream);
+/* hsp_gemm_rows_bf16 with an fp32 residual (no bias / cloud bias / xyz3): C = A1 B1^T (+ A2 B2^T) + resid, C fp32 (c_is_f32)
+ * or bf16 -- a sum over more than two products carried in fp32 and rounded once */
+int hsp_gemm_rows_acc_bf16(const hsp_bf16_t *A1, int lda1, const hsp_bf16_t *B1, int ldb1, int K1, const hsp_bf16_t *A2,
+                           int lda2, const hsp_bf16_t *B2, int ldb2, int K2, int M, int N, const float *resid, int ldr, void *C,
+                           int ldc, int c_is_f32, void *ws, size_t ws_bytes, hspStream_t stream);
+/* bf16 product with the BatchNorm first pass in its epilogue: C (fp32) = A B^T + bias (+ cloud_bias[row / rows_per_cloud])
+ * (+ xyz3 . w3), bn_shift[n] = bias[n] + cloud_bias[0][n], bn_part[tiles][2][N] = per row tile sum (c - shift), sum (c - shift)^2
+ * (the layout of hsp_gemm_x3_bias_bn_f32), tiles = hsp_gemm_rows_bn_tiles_bf16(M, N, K) <= 512; fold with
+ * hsp_bn_relu_fwd_partials_mixed (bf16 rows out) or hsp_bn_relu_fwd_partials */
+int hsp_gemm_rows_bn_tiles_bf16(int M, int N, int K);
+int hsp_gemm_rows_bn_bf16(const hsp_bf16_t *A, int lda, const hsp_bf16_t *B, int ldb, int K, int M, int N, const float *bias,
+                          const float *cloud_bias, int rows_per_cloud, const float *xyz3, const float *w3, float *C, int ldc,
+                          float *bn_shift, float *bn_part, hspStream_t stream);
+int hsp_bn_relu_fwd_partials_mixed(const float *x, int R, int C, const float *gamma, const float *beta, float eps, float momentum,
+                                   int relu, hsp_bf16_t *y, float *save_mean, float *save_invstd, float *running_mean,
+                                   float *running_var, long long *num_batches_tracked, const float *partial, int nblk,
+                                   const float *shift, hspStream_t stream);
+/* (B,N,C) bf16 rows -> fp32 (B,C) max and winning row (the fp32 kernel's rule on the widened values); backward: bf16 (B,N,C) */
+int hsp_points_max_fwd_bf16(const hsp_bf16_t *x, int B, int N, int C, float *out, int32_t *argrow, hspStream_t stream);
+int hsp_points_max_bwd_bf16(const float *grad_out, const int32_t *argrow, int B, int N, int C, hsp_bf16_t *grad_x,
+                            hspStream_t stream);
 /* "mixed": x fp32 (the pre-BatchNorm layer output is kept in fp32: with |mean| >> std per channel a bf16 x would leave
  * the normalised value only a few significant bits), y / dy / dx bf16 */
 int hsp_bn_relu_fwd_mixed(const float *x, int R, int C, const float *gamma, const float *beta, float eps, float momentum,

@@ -20,6 +20,7 @@ def main():
     ap.add_argument("--instances", type=int, nargs="+", default=[1, 4, 6])
     ap.add_argument("--images", type=int, default=200)
     ap.add_argument("--points", type=int, default=1028)
+    ap.add_argument("--dtype", choices=("f32", "bf16"), default="f32", help="feature rows of the whole network (set_feature_dtype)")
     args = ap.parse_args()
     from tools import gemm_tuning
     from hs_pose_amd.config import FLAGS
@@ -31,6 +32,8 @@ def main():
     FLAGS.reset(); FLAGS.train = 0
     torch.manual_seed(0)
     net = HSPose("PoseNet_only").to(dev).eval()
+    if args.dtype == "bf16":
+        net.set_feature_dtype(torch.bfloat16)
     for n in args.instances:
         g = torch.Generator().manual_seed(n)
         PC = (torch.randn(n, args.points, 3, generator=g) * 0.05 + torch.tensor([0.0, 0.0, 0.8])).to(dev)

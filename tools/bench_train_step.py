@@ -25,6 +25,7 @@ def main():
     ap.add_argument("--points", type=int, default=1028)
     ap.add_argument("--no-graph", action="store_true", help="issue the step eagerly (CPU-bound) instead of replaying a hipGraph")
     ap.add_argument("--graph-net", action="store_true", help="eager step with posenet forward/backward replayed from two hipGraphs")
+    ap.add_argument("--dtype", choices=("f32", "bf16"), default="f32", help="feature rows of the whole network (set_feature_dtype)")
     args = ap.parse_args()
     from tools import gemm_tuning                # (library-GEMM tuning table: only matters under HSP_GEMM=library)
     from hs_pose_amd.config import FLAGS
@@ -36,6 +37,8 @@ def main():
     FLAGS.reset(); FLAGS.train = 1
     torch.manual_seed(0)
     net = HSPose("PoseNet_only").to(dev).train()
+    if args.dtype == "bf16":
+        net.set_feature_dtype(torch.bfloat16)    # (the driver re-applies it after the fused optimizer re-seats the parameters)
     drv = TrainDriver(net, total_iters=150 * 1500, check_nan=False)
     case = {k: v.to(dev) for k, v in oc.hspose_train_case(args.batch, args.points, 7).items()}
 
