@@ -261,22 +261,27 @@ __global__ __launch_bounds__(ORLT_WG) void orl_tile_kernel(const FT* __restrict_
     ORL_STAMP(31);
 }
 
+// sum over the chunks of p[chunk * stride]: THE order of every per-cloud column sum's second stage (chunk_fold_kernel, and
+// colsum_cloud_kernel, which folds its own chunks out of LDS) -- eight running sums over chunk, combined pairwise.
+// 8 independent partial sums: 8 loads in flight per round trip (the fold is a latency chain, not bandwidth)
+__device__ __forceinline__ float chunk_fold8(const float* __restrict__ p, int nchunk, int stride) {
+    float s[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    int ch = 0;
+    for (; ch + 7 < nchunk; ch += 8) {
+#pragma unroll
+        for (int u = 0; u < 8; ++u) s[u] += p[(size_t)(ch + u) * stride];
+    }
+    for (; ch < nchunk; ++ch) s[ch & 7] += p[(size_t)ch * stride];
+    return ((s[0] + s[1]) + (s[2] + s[3])) + ((s[4] + s[5]) + (s[6] + s[7]));
+}
+
 // out[b][c] = scale * sum_chunk part[b][chunk][c]   (also the generic "column sum per cloud" second stage)
 __global__ __launch_bounds__(256) void chunk_fold_kernel(const float* __restrict__ part, int B, int nchunk, int C,
                                                          float scale, float* __restrict__ out) {
     const int e = blockIdx.x * 256 + threadIdx.x;
     if (e >= B * C) return;
     const int b = e / C, c = e - b * C;
-    const float* p = part + (size_t)b * nchunk * C + c;
-    // 8 independent partial sums: 8 loads in flight per round trip (the fold is a latency chain, not bandwidth)
-    float s[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    int ch = 0;
-    for (; ch + 7 < nchunk; ch += 8) {
-#pragma unroll
-        for (int u = 0; u < 8; ++u) s[u] += p[(size_t)(ch + u) * C];
-    }
-    for (; ch < nchunk; ++ch) s[ch & 7] += p[(size_t)ch * C];
-    out[e] = (((s[0] + s[1]) + (s[2] + s[3])) + ((s[4] + s[5]) + (s[6] + s[7]))) * scale;
+    out[e] = chunk_fold8(part + (size_t)b * nchunk * C + c, nchunk, C) * scale;
 }
 
 // part[b][chunk][c] = sum of x[b][i][c] over the chunk's rows (first stage of a per-cloud column sum)
@@ -347,6 +352,63 @@ __global__ __launch_bounds__(256) void colsum_xyz_partial_kernel(const FT* __res
             for (int l = 1; l < RL; ++l) { const float4 v = red[q][l * cq + g]; a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w; }
             *reinterpret_cast<float4*>(part + (((size_t)b * nchunk + chunk) * 4 + q) * C + (g << 2)) = a;
         }
+    }
+}
+
+// Both stages of the per-cloud column sum (XYZ: and of its three coordinate moments) in ONE launch, with the bits of the
+// two-launch form: a workgroup of 1024 threads owns (cloud, C/8 columns) and walks the SAME chunks in rounds of 32.  A chunk is
+// 32 threads = the RL = 256 / (C/4) row lanes x the tile's C/32 float4 columns, so every thread does exactly the work of one
+// thread of colsum_partial_kernel / colsum_xyz_partial_kernel (the same rows, in the same order, the same row-lane fold through
+// LDS); the chunk sums stay in LDS and chunk_fold8 sums them in chunk_fold_kernel's order.  No partial workspace, no second
+// dependent launch (a fold is a 4-5 us launch for a fraction of a microsecond of adds).
+// grid (8, B), dynamic LDS = (1024 + (XYZ ? 4 : 1) * nchunk * C/32) float4
+template <bool XYZ>
+__global__ __launch_bounds__(1024) void colsum_cloud_kernel(const float* __restrict__ x, const float* __restrict__ xyz, int N, int C,
+                                                            int nchunk, int rows, float* __restrict__ out) {
+    extern __shared__ float4 cc_smem[];
+    constexpr int NS = XYZ ? 4 : 1;
+    const int cq = C >> 2, RL = 256 / cq, G = cq >> 3;
+    const int tid = threadIdx.x;
+    const int gl = tid % G, rl = (tid / G) % RL, cs = tid / (G * RL);      // tid = (cs * RL + rl) * G + gl
+    const int g = blockIdx.x * G + gl, b = blockIdx.y;
+    float4* red = cc_smem;                                                 // [1024]
+    float4* cp = cc_smem + 1024;                                           // [NS][nchunk][G]
+    for (int c0 = 0; c0 < nchunk; c0 += 32) {
+        const int chunk = c0 + cs;
+        const int r0 = chunk * rows, r1 = chunk < nchunk ? min(N, r0 + rows) : 0;
+        float4 s[NS];
+#pragma unroll
+        for (int q = 0; q < NS; ++q) s[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int i = r0 + rl; i < r1; i += RL) {
+            const float4 v = *reinterpret_cast<const float4*>(x + ((size_t)b * N + i) * C + (g << 2));
+            s[0].x += v.x; s[0].y += v.y; s[0].z += v.z; s[0].w += v.w;
+            if constexpr (XYZ) {
+                const float* p3 = xyz + ((size_t)b * N + i) * 3;
+                const float w[3] = {p3[0], p3[1], p3[2]};
+#pragma unroll
+                for (int q = 0; q < 3; ++q) {                  // (plain v_fma_f32 spelled out: see colsum_xyz_partial_kernel)
+                    s[q + 1].x = fma_plain(v.x, w[q], s[q + 1].x); s[q + 1].y = fma_plain(v.y, w[q], s[q + 1].y);
+                    s[q + 1].z = fma_plain(v.z, w[q], s[q + 1].z); s[q + 1].w = fma_plain(v.w, w[q], s[q + 1].w);
+                }
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < NS; ++q) {
+            red[tid] = s[q];
+            __syncthreads();
+            if (rl == 0 && chunk < nchunk) {
+                float4 a = s[q];
+                for (int l = 1; l < RL; ++l) { const float4 v = red[(cs * RL + l) * G + gl]; a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w; }
+                cp[((size_t)q * nchunk + chunk) * G + gl] = a;
+            }
+            __syncthreads();                                   // red is reused by the next slot / round; cp complete after the last
+        }
+    }
+    const int TC = G << 2;
+    if (tid < NS * TC) {
+        const int q = tid / TC, c = tid - q * TC;
+        out[(size_t)b * NS * C + (size_t)q * C + blockIdx.x * TC + c] =
+            chunk_fold8(reinterpret_cast<const float*>(cp) + (size_t)q * nchunk * TC + c, nchunk, TC);
     }
 }
 
@@ -1179,6 +1241,31 @@ extern "C" int hsp_colsum_rows_xyz(const float* x, const float* xyz, int B, int 
 extern "C" int hsp_colsum_rows_xyz_bf16(const hsp_bf16_t* x, const float* xyz, int B, int N, int C, float* out4, void* ws,
                                         size_t ws_bytes, hspStream_t stream) {
     return colsum_rows_xyz_impl<bf16_t>(x, xyz, B, N, C, out4, ws, ws_bytes, stream);
+}
+
+/* hsp_colsum_rows (xyz == NULL: out (B, C)) / hsp_colsum_rows_xyz (out (B, 4, C)) in ONE launch and without a workspace, bit
+ * for bit (colsum_cloud_kernel).  hsp_colsum_cloud_ok: 1 where that form takes the shape -- C a multiple of 32 with C/4 | 256,
+ * row-lane buffer + the chunk sums of a cloud's column tile within 64 KB of LDS; elsewhere the two-launch entry points remain. */
+static size_t colsum_cloud_lds(int B, int N, int C, int with_xyz) {
+    const int rows = chunk_rows(B, N, C);
+    return (1024 + (size_t)(with_xyz ? 4 : 1) * ((N + rows - 1) / rows) * (C >> 5)) * sizeof(float4);
+}
+extern "C" int hsp_colsum_cloud_ok(int B, int N, int C, int with_xyz) {
+    if (B <= 0 || B > 65535 || N <= 0 || C <= 0 || (C & 31) || !colsum_vec4(C)) return 0;
+    return colsum_cloud_lds(B, N, C, with_xyz) <= 64 * 1024 ? 1 : 0;
+}
+extern "C" int hsp_colsum_cloud_f32(const float* x, const float* xyz, int B, int N, int C, float* out, hspStream_t stream) {
+    if (!x || !out || B <= 0 || N <= 0 || C <= 0) return HSP_ERR_BAD_ARG;
+    if (!hsp_colsum_cloud_ok(B, N, C, xyz != nullptr)) return HSP_ERR_UNSUPPORTED;
+    hipStream_t st = as_stream(stream);
+    const int rows = chunk_rows(B, N, C);
+    const int nchunk = (N + rows - 1) / rows;
+    const size_t lds = colsum_cloud_lds(B, N, C, xyz != nullptr);
+    if (xyz)
+        hipLaunchKernelGGL(colsum_cloud_kernel<true>, dim3(8, B), dim3(1024), lds, st, x, xyz, N, C, nchunk, rows, out);
+    else
+        hipLaunchKernelGGL(colsum_cloud_kernel<false>, dim3(8, B), dim3(1024), lds, st, x, xyz, N, C, nchunk, rows, out);
+    return check_launch();
 }
 
 extern "C" int hsp_colsum_rows_bf16(const hsp_bf16_t* x, int B, int N, int C, float* out, void* ws, size_t ws_bytes,

@@ -849,14 +849,16 @@ __global__ __launch_bounds__(256) void small_rows_nn_kernel(const float* __restr
 // memory round trip) and fold through LDS in wave order.  "nt" lanes fetch 16 bytes = 4 consecutive k of their row: MFMA e of a
 // group of four multiplies the k set {e, 4+e, 8+e, 12+e} -- the same permutation on both operands, the same products.
 using f32x4v = __attribute__((ext_vector_type(4))) float;
+// (the body, with the block's place in the (column group, row block) grid as arguments: small_rows_mfma_kernel and the nn block
+// range of small_pair_kernel run the same instructions)
 template <bool NN>
-__global__ __launch_bounds__(256) void small_rows_mfma_kernel(const float* __restrict__ A, int lda, const float* __restrict__ W, int ldw,
-                                                              int M, int N, int K, float alpha, float* __restrict__ out, int ldo) {
-    __shared__ float red[3][64][4];
+__device__ __forceinline__ void small_rows_mfma_body(const float* __restrict__ A, int lda, const float* __restrict__ W, int ldw,
+                                                     int M, int N, int K, float alpha, float* __restrict__ out, int ldo,
+                                                     int bx, int by, float (*red)[64][4]) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int j = lane & 15, kk = lane >> 4;
-    const int mbase = blockIdx.y * 16;                         // 16-row blocks along grid.y (M up to 64: one row per cloud)
-    const int n = blockIdx.x * 16 + j, nc = min(n, N - 1), mc = min(mbase + j, M - 1);
+    const int mbase = by * 16;                                 // 16-row blocks along grid.y (M up to 64: one row per cloud)
+    const int n = bx * 16 + j, nc = min(n, N - 1), mc = min(mbase + j, M - 1);
     const float amask = mbase + j < M ? 1.f : 0.f;
     const int kper = K >> 2, k0 = wave * kper;
     f32x4v acc = {0.f, 0.f, 0.f, 0.f};
@@ -908,22 +910,30 @@ __global__ __launch_bounds__(256) void small_rows_mfma_kernel(const float* __res
     }
 }
 
-// out (Ma, Nb) = a^T c over the B (<= 16) per-cloud rows: a (B, Ma), c (B, Nb)
-__global__ __launch_bounds__(256) void small_outer_kernel(const float* __restrict__ a, int lda, const float* __restrict__ c, int ldc_,
-                                                          int B, int Ma, int Nb, float* __restrict__ out, int ldo,
-                                                          const float* __restrict__ mom, int ldm, int Cm, float* __restrict__ gste) {
+template <bool NN>
+__global__ __launch_bounds__(256) void small_rows_mfma_kernel(const float* __restrict__ A, int lda, const float* __restrict__ W, int ldw,
+                                                              int M, int N, int K, float alpha, float* __restrict__ out, int ldo) {
+    __shared__ float red[3][64][4];
+    small_rows_mfma_body<NN>(A, lda, W, ldw, M, N, K, alpha, out, ldo, blockIdx.x, blockIdx.y, red);
+}
+
+// out (Ma, Nb) = a^T c over the B (<= 64) per-cloud rows: a (B, Ma), c (B, Nb); block blk of nblk
+__device__ __forceinline__ void small_outer_body(const float* __restrict__ a, int lda, const float* __restrict__ c, int ldc_,
+                                                 int B, int Ma, int Nb, float* __restrict__ out, int ldo,
+                                                 const float* __restrict__ mom, int ldm, int Cm, float* __restrict__ gste,
+                                                 int blk, int nblk) {
     const long long total = (long long)Ma * Nb;
     // rider job (HSlayer_surface): gste[c][j] = sum_b mom[b][j * Cm + c], j = 0..2 -- the per-cloud coordinate moments of g
     // (hsp_colsum_rows_xyz) summed over the batch, in cloud order
     if (mom) {
-        for (int e = blockIdx.x * 256 + threadIdx.x; e < 3 * Cm; e += gridDim.x * 256) {
+        for (int e = blk * 256 + threadIdx.x; e < 3 * Cm; e += nblk * 256) {
             float s = 0.f;
             for (int b = 0; b < B; ++b) s += mom[(size_t)b * ldm + e];
             const int j = e / Cm, cc = e - j * Cm;
             gste[cc * 3 + j] = s;
         }
     }
-    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
+    for (long long e = (long long)blk * 256 + threadIdx.x; e < total; e += (long long)nblk * 256) {
         const int i = (int)(e / Nb), j = (int)(e - (long long)i * Nb);
         float s = 0.f;
         for (int b0 = 0; b0 < B; b0 += 16) {                   // 32 loads in flight, then the chain in row order
@@ -938,6 +948,32 @@ __global__ __launch_bounds__(256) void small_outer_kernel(const float* __restric
                 if (b0 + u < B) s = __fmaf_rn(av[u], cv[u], s);
         }
         out[(size_t)i * ldo + j] = s;
+    }
+}
+
+__global__ __launch_bounds__(256) void small_outer_kernel(const float* __restrict__ a, int lda, const float* __restrict__ c, int ldc_,
+                                                          int B, int Ma, int Nb, float* __restrict__ out, int ldo,
+                                                          const float* __restrict__ mom, int ldm, int Cm, float* __restrict__ gste) {
+    small_outer_body(a, lda, c, ldc_, B, Ma, Nb, out, ldo, mom, ldm, Cm, gste, blockIdx.x, gridDim.x);
+}
+
+// The two products of a layer's backward that read only the per-cloud row gt (B, Ma) -- gfg = alpha gt W (the "nn" form above)
+// and gWb = gt^T fg (small_outer, its STE rider included) -- as two block ranges of ONE launch: they are independent of each
+// other, each is a few microseconds of a dependent launch, and each block runs the body of the kernel it replaces (same bits).
+// Blocks [0, n_nn): the nn product's (column group, row block) grid, first because its chain is the longer one; then n_outer.
+__global__ __launch_bounds__(256) void small_pair_kernel(const float* __restrict__ gt, int ldgt, int B, int Ma,
+                                                         const float* __restrict__ W, int ldw, int Nn, float alpha,
+                                                         float* __restrict__ out_nn, int ldnn,
+                                                         const float* __restrict__ c, int ldc_, int Nb, float* __restrict__ out_o, int ldo,
+                                                         const float* __restrict__ mom, int ldm, int Cm, float* __restrict__ gste,
+                                                         int n_nn, int n_outer) {
+    __shared__ float red[3][64][4];
+    const int blk = blockIdx.x;
+    if (blk < n_nn) {
+        const int gx = (Nn + 15) >> 4;
+        small_rows_mfma_body<true>(gt, ldgt, W, ldw, B, Nn, Ma, alpha, out_nn, ldnn, blk % gx, blk / gx, red);
+    } else {
+        small_outer_body(gt, ldgt, c, ldc_, B, Ma, Nb, out_o, ldo, mom, ldm, Cm, gste, blk - n_nn, n_outer);
     }
 }
 
@@ -982,6 +1018,25 @@ extern "C" int hsp_small_outer_f32(const float* a, int lda, const float* c, int 
     if (g > HSP_NUM_CU * 8) g = HSP_NUM_CU * 8;
     hipLaunchKernelGGL(small_outer_kernel, dim3((unsigned)g), dim3(256), 0, as_stream(stream), a, lda, c, ldc, B, Ma, Nb, out, ldo,
                        mom, ldm, Cm, gste);
+    return check_launch();
+}
+
+/* hsp_small_rows_f32 (w_layout 1: out_nn (B, Nn) = alpha * gt (B, Ma) W (Ma, Nn)) and hsp_small_outer_f32 (out_o (Ma, Nb) =
+ * gt^T c, mom / gste as there) on the same per-cloud rows gt in ONE launch, bit for bit.  Ma a multiple of 128 (the nn product's
+ * MFMA form), B <= 64. */
+extern "C" int hsp_small_pair_f32(const float* gt, int ldgt, int B, int Ma, const float* W, int ldw, int Nn, float alpha,
+                                  float* out_nn, int ldnn, const float* c, int ldc, int Nb, float* out_o, int ldo,
+                                  const float* mom, int ldm, int Cm, float* gste, hspStream_t stream) {
+    if (!gt || !W || !out_nn || !c || !out_o || B <= 0 || Ma <= 0 || Nn <= 0 || Nb <= 0 || ldgt < Ma || ldw < Nn || ldnn < Nn ||
+        ldc < Nb || ldo < Nb)
+        return HSP_ERR_BAD_ARG;
+    if (mom && (!gste || Cm <= 0 || ldm < 3 * Cm)) return HSP_ERR_BAD_ARG;
+    if (B > 64 || Ma % 128 != 0 || Ma > 2048) return HSP_ERR_UNSUPPORTED;
+    const int n_nn = ((Nn + 15) / 16) * ((B + 15) / 16);
+    long long g = ((long long)Ma * Nb + 255) / 256;
+    if (g > HSP_NUM_CU * 8) g = HSP_NUM_CU * 8;
+    hipLaunchKernelGGL(small_pair_kernel, dim3((unsigned)(n_nn + g)), dim3(256), 0, as_stream(stream), gt, ldgt, B, Ma, W, ldw, Nn,
+                       alpha, out_nn, ldnn, c, ldc, Nb, out_o, ldo, mom, ldm, Cm, gste, n_nn, (int)g);
     return check_launch();
 }
 

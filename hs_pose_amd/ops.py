@@ -1220,6 +1220,38 @@ def colsum_rows_xyz(g, xyz):
     return mom
 
 
+# The per-cloud chain of a layer's backward -- gt = sum_i g, gWb = gt^T fg, gfg / N = gt Wb / N -- is two launches
+# (hsp_colsum_cloud_f32, hsp_small_pair_f32) where it was four (column sum: partials + fold, hsp_small_outer_f32,
+# hsp_small_rows_f32); same bits.  Test-only: LAUNCH_DIET = False issues the four, and a callable in _between_launches_hook is
+# called with the intermediate tensor between the chain's launches (tests/test_gpu_launch_diet.py).
+LAUNCH_DIET = True
+_between_launches_hook = None
+
+
+def _orl_bwd_small_ok(B, N, C, with_xyz):
+    """shapes the two-launch form of the per-cloud backward chain takes"""
+    return (LAUNCH_DIET and B <= 64 and C % 128 == 0 and C <= 2048
+            and lib().hsp_colsum_cloud_ok(B, N, C, 1 if with_xyz else 0) == 1)
+
+
+def _orl_bwd_small(g, xyz, fg, Wb, gWb, gste=None):
+    """gfg / N (B,C) = (sum_i g) Wb / N; writes gWb (C,C) = (sum_i g)^T fg and, with ``xyz``, gste (C,3) = g^T xyz"""
+    B, N, C = g.shape
+    ns = 4 if xyz is not None else 1
+    mom = torch.empty(B, ns * C, dtype=torch.float32, device=g.device)
+    _run("hsp_colsum_cloud_f32", (_p(g), _p(xyz), B, N, C, _p(mom), _stream()), key=f"B{B}N{N}C{C}{'x' if xyz is not None else ''}",
+         abytes=B * N * (4 * C + (12 if xyz is not None else 0)))
+    if _between_launches_hook is not None:
+        _between_launches_hook(mom)
+    gfg = torch.empty(B, C, dtype=torch.float32, device=g.device)
+    _run("hsp_small_pair_f32", (_p(mom), _ld(mom), B, C, _p(Wb), _ld(Wb), Wb.shape[1], 1.0 / N, _p(gfg), _ld(gfg),
+                                _p(fg), _ld(fg), fg.shape[1], _p(gWb), _ld(gWb),
+                                _p(mom[:, C:]) if xyz is not None else None, _ld(mom) if xyz is not None else 0,
+                                C if xyz is not None else 0, _p(gste), _stream()),
+         key=f"B{B}C{C}", abytes=4 * (B * 3 * C + 2 * C * C))
+    return gfg
+
+
 def _orl_bwd_accumulate_raw(gfg_over_n, idx_x, arg, k, gF3, extra=None):
     """gF3[b,m,c] += extra[b,m,c] + gfg_over_n[b,c] * #{i : idx_x[b,i,arg[b,i,c]] == m}     (in place, one pass)"""
     B, N, C = gF3.shape
@@ -1425,15 +1457,22 @@ class _HSLayer(torch.autograd.Function):
         C = F3.shape[2]
         g2, X2, F2 = g.view(B * N, C), X.view(B * N, Cin), F3.view(B * N, C)
         Wa, Wb = w_conv2[:, :C], w_conv2[:, C:]
-        gt = colsum_rows(g)                                                    # (B,C) = sum_i g
+        small = _orl_bwd_small_ok(B, N, C, False)
         g_conv2 = torch.empty_like(w_conv2)
+        if small:
+            gfg_n = _orl_bwd_small(g, None, fg, Wb, g_conv2[:, C:])            # gt = sum_i g, gWb = gt^T fg, gt Wb / N: two launches
+        else:
+            gt = colsum_rows(g)                                                # (B,C) = sum_i g
         with WgradBatch(), x3_scope(ctx.x3):                                   # the three parameter gradients: one fold launch
             g_ste = torch.empty(C, Cin, dtype=torch.float32, device=g.device)
             wgrad_pair(g2, F2, g_conv2[:, :C], g2, X2, g_ste)                  # gWa (in place, ldc = 2C) and gWste: one split-K launch
-            _tiny_tn(gt, fg, g_conv2[:, C:])                                   # gWb = gt^T fg (tiny), straight into its column block
+            if not small:
+                _tiny_tn(gt, fg, g_conv2[:, C:])                               # gWb = gt^T fg (tiny), straight into its column block
             gF3 = torch.empty(B, N, C, dtype=torch.float32, device=g.device)
             _mm_nn(g2, Wa, out=gF3.view(B * N, C))                             # g Wa ...
-            _orl_bwd_accumulate_raw(_mm_nn(gt, Wb, alpha=1.0 / N), idx_x, arg_o, k, gF3, extra=g)  # ... + g + ORL scatter, one pass
+            if not small:
+                gfg_n = _mm_nn(gt, Wb, alpha=1.0 / N)
+            _orl_bwd_accumulate_raw(gfg_n, idx_x, arg_o, k, gF3, extra=g)      # ... + g + ORL scatter, one pass
             gfm, gD = _rf_conv_bwd_raw(xyz, idx_f, directions, fm.view(B, N, -1), arg, gF3, S)
             gfm2 = gfm.view(B * N, -1)
             gW, gb = wgrad(X2, gfm2, colsum=True)                              # X^T gfm and the bias gradient
@@ -1504,7 +1543,12 @@ class _SurfaceLayer(torch.autograd.Function):
         Wa, Wb = w_conv2[:, :C], w_conv2[:, C:]
         g_conv2 = torch.empty_like(w_conv2)
         own_ste = _ste_moments_ok(C)
-        if own_ste:
+        small = own_ste and _orl_bwd_small_ok(B, N, C, True)
+        if small:
+            # the same chain (column sums + coordinate moments, gWb with the STE rider, gt Wb / N) in two launches
+            g_ste = torch.empty(C, 3, dtype=torch.float32, device=g.device)
+            gfg_n = _orl_bwd_small(g, xyz, fg, Wb, g_conv2[:, C:], gste=g_ste)
+        elif own_ste:
             # gt = sum_i g and the per-cloud coordinate moments of g in one pass; the STE gradient g^T xyz is their sum over the
             # batch, taken as a rider of the gt^T fg launch: no library GEMM for the (C, 3) product
             mom = colsum_rows_xyz(g, xyz)
@@ -1514,14 +1558,18 @@ class _SurfaceLayer(torch.autograd.Function):
             gt = colsum_rows(g)
         with WgradBatch():                                  # (its fold goes out with the step's folds inside a StepFolds scope)
             wgrad(g2, F2, out=g_conv2[:, :C])
-        if own_ste:
+        if small:
+            pass                                            # (gWb and the STE gradient came out of the pair launch above)
+        elif own_ste:
             _tiny_tn(gt, fg, g_conv2[:, C:], mom=mom, gste=g_ste)
         else:
             _tiny_tn(gt, fg, g_conv2[:, C:])
         gF3 = torch.empty(B, N, C, dtype=torch.float32, device=g.device)
         with x3_scope(ctx.x3):
             _mm_nn(g2, Wa, out=gF3.view(B * N, C))
-        _orl_bwd_accumulate_raw(_mm_nn(gt, Wb, alpha=1.0 / N), idx_x, arg_o, k, gF3, extra=g)
+        if not small:
+            gfg_n = _mm_nn(gt, Wb, alpha=1.0 / N)
+        _orl_bwd_accumulate_raw(gfg_n, idx_x, arg_o, k, gF3, extra=g)
         gD = torch.empty_like(directions)
         L = lib()
         wsb = L.hsp_rf_bwd_scatter_workspace_bytes(B, SC)

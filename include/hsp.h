@@ -393,6 +393,21 @@ int hsp_colsum_rows_xyz(const float *x, const float *xyz, int B, int N, int C, f
 int hsp_colsum_rows_xyz_bf16(const hsp_bf16_t *x, const float *xyz, int B, int N, int C, float *out4, void *ws, size_t ws_bytes,
                              hspStream_t stream);
 
+/* The per-cloud chain of an HS layer's backward in two launches instead of four (fp32 training path), bit for bit what the
+ * entry points above compute -- a dependent launch of this size costs 4-6 us whatever it does:
+ *   hsp_colsum_cloud_f32: hsp_colsum_rows (xyz == NULL: out (B, C)) or hsp_colsum_rows_xyz (out (B, 4, C)) with both stages in
+ *                         one launch and no workspace: a workgroup per (cloud, C/8 columns) sums the same chunks in the same
+ *                         order and folds them itself.  hsp_colsum_cloud_ok: 1 where it takes the shape (C a multiple of 32
+ *                         with C/4 | 256, at most 65535 clouds, the chunk sums of a column tile fit in LDS), else 0
+ *   hsp_small_pair_f32:   hsp_small_rows_f32 with w_layout 1 (out_nn (B, Nn) = alpha * gt (B, Ma) W (Ma, Nn)) and
+ *                         hsp_small_outer_f32 (out_o (Ma, Nb) = gt^T c; mom / ldm / Cm / gste as there) as two block ranges of
+ *                         one launch.  Ma a multiple of 128 and <= 2048, B <= 64; other shapes: HSP_ERR_UNSUPPORTED */
+int hsp_colsum_cloud_ok(int B, int N, int C, int with_xyz);
+int hsp_colsum_cloud_f32(const float *x, const float *xyz, int B, int N, int C, float *out, hspStream_t stream);
+int hsp_small_pair_f32(const float *gt, int ldgt, int B, int Ma, const float *W, int ldw, int Nn, float alpha, float *out_nn,
+                       int ldnn, const float *c, int ldc, int Nb, float *out_o, int ldo, const float *mom, int ldm, int Cm,
+                       float *gste, hspStream_t stream);
+
 /* fp32 master parameters -> bf16 working copies for the *_bf16 entry points, every tensor of a step in one launch:
  * entry e copies src (rows, cols; row pitch ld) to dst (rows, cols) and / or dstT (cols, rows) -- either may be NULL --
  * rounding to nearest even.  tile0 = number of 32 x 32 tiles of the entries before e; table_dev lives in DEVICE memory. */

@@ -75,7 +75,7 @@ def enable(monkeypatch=None, tune=False):
                      ("_grad_in_rows", grad_in_rows), ("_tiny_tn", tiny_tn), ("wgrad", wgrad), ("gemm_mode", "library"),
                      # the own-kernel fusions: off
                      ("_wgrad_ragged_ok", never), ("linear_bn_part_ok", never), ("_layer_out_bn_ok", never), ("_ste_moments_ok", never),
-                     ("_thin_wgrad_ok", never), ("fan_linear_rows_ok", never), ("cloud_cat_linear_ok", never),
+                     ("_thin_wgrad_ok", never), ("_orl_bwd_small_ok", never), ("fan_linear_rows_ok", never), ("cloud_cat_linear_ok", never),
                      ("x3_refresh", lambda: None)):
         if monkeypatch is not None and not hasattr(ops, name):
             monkeypatch.setattr(ops, name, fn, raising=False)
