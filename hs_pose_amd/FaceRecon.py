@@ -75,7 +75,8 @@ class FaceRecon(nn.Module):
 
     def set_feature_dtype(self, dtype):
         """torch.bfloat16: the HS stack stores its feature rows, ``fm`` and activation gradients in bf16 and runs its dense
-        products on the bf16 matrix cores (BASELINE configs[3]; hs_pose_amd/ops_bf16.py says what stays fp32); ``feat``
+        products on the bf16 matrix cores (BASELINE configs[3]; the same ops.hs_layer / ops.surface_layer nodes as on fp32 rows,
+        hs_pose_amd/ops_bf16.py says what stays fp32); ``feat``
         comes out bf16.  With FLAGS.train the reconstruction and face heads follow (bf16 rows between their layers, fp32 where a
         product feeds BatchNorm and in the 3- / 30-wide outputs; ops_bf16).  The parameters stay fp32 masters -- call again after
         anything that re-seats them (moving the module, building the fused optimizer; ``train.TrainDriver`` does it).

@@ -22,7 +22,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import ops, ops_bf16
+from . import ops
 
 # ------------------------------------------------------------------------------------------------
 # per-forward xyz-KNN memo
@@ -223,11 +223,8 @@ class HSlayer_surface(nn.Module):
         idx = _xyz_knn(vertices, neighbor_num)                       # RF-P
         if idx.shape[2] != neighbor_num:
             idx = idx[:, :, :neighbor_num].contiguous()
-        if relu_fork and self.out_dtype != torch.bfloat16:
-            return ops.surface_layer(vertices, idx, neighbor_num, self.support_num, self.directions, self.STE_layer.weight,
-                                     self.conv2.weight, relu=True)
-        layer = ops_bf16.surface_layer if self.out_dtype == torch.bfloat16 else ops.surface_layer
-        return layer(vertices, idx, neighbor_num, self.support_num, self.directions, self.STE_layer.weight, self.conv2.weight)
+        return ops.surface_layer(vertices, idx, neighbor_num, self.support_num, self.directions, self.STE_layer.weight,
+                                 self.conv2.weight, relu=relu_fork, out_dtype=self.out_dtype)
 
     def graph_conv(self, neighbor_index, vertices, neighbor_num):
         """fused relu(R @ D^) -> max over neighbours -> mean over supports (reference :92-107).  Takes the
@@ -274,13 +271,9 @@ class HS_layer(nn.Module):
         (fp32 rows): see ops.hs_layer -- returns (out, BatchNorm partial sums)."""
         # RF-F: neighbours in feature space (``transposed_view``: see ops.knn -- FaceRecon sets it for conv_3)
         neighbor_index = ops.knn(feature_map, neighbor_num, **({"transposed_view": True} if transposed_view else {}))
-        if feature_map.dtype == torch.bfloat16:                      # bf16 feature rows in -> out (fp32 out ahead of a BatchNorm)
-            return ops_bf16.hs_layer(vertices, feature_map, neighbor_index, _xyz_knn(vertices, neighbor_num), neighbor_num,
-                                     self.support_num, self.weights, self.bias, self.directions, self.STE_layer.weight,
-                                     self.conv2.weight, out_f32=self.out_fp32)
         return ops.hs_layer(vertices, feature_map, neighbor_index, _xyz_knn(vertices, neighbor_num), neighbor_num,
                             self.support_num, self.weights, self.bias, self.directions, self.STE_layer.weight, self.conv2.weight,
-                            bn_shift=bn_shift)
+                            bn_shift=bn_shift, out_f32=self.out_fp32)
 
     def graph_conv(self, neighbor_index, feature_map, vertices, neighbor_num):
         """reference :158-181 with the gather, theta product, max and mean fused into one kernel."""

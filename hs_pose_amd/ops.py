@@ -325,7 +325,7 @@ class _RFSurface(torch.autograd.Function):
         L = lib()
         wsb = L.hsp_rf_bwd_scatter_workspace_bytes(B, SC)
         ws = _ws(wsb, g.device)
-        _rf_bwd_dirs_call("hsp_rf_surface_bwd", (_p(xyz), _p(dirs_n), _p(arg), _p(g), B, N, ctx.S, SC // ctx.S, _p(gd)), ws, wsb,
+        _rf_bwd_dirs_call("hsp_rf_surface_bwd", "", (_p(xyz), _p(dirs_n), _p(arg), _p(g), B, N, ctx.S, SC // ctx.S, _p(gd)), ws, wsb,
                           (dirs_n, gd), key=f"B{B}N{N}S{ctx.S}C{SC // ctx.S}", abytes=B * N * (12 + 4 * (SC // ctx.S) + SC) + 24 * SC)
         return None, None, gd, None
 
@@ -441,18 +441,19 @@ class _OrlGlobal(torch.autograd.Function):
 
 
 class _PointsMax(torch.autograd.Function):
-    """(B,N,C) -> (B,C) max over the points of each cloud; the gradient goes to the first winning row."""
+    """(B,N,C) fp32 / bf16 -> fp32 (B,C) max over the points of each cloud; the gradient (in the rows' dtype) goes to the first
+    winning row."""
 
     @staticmethod
     def forward(ctx, x):
-        x = _req(x, torch.float32, "points_max.x")
+        x = _reqf(x, "points_max.x")
         B, N, C = x.shape
         out = torch.empty(B, C, dtype=torch.float32, device=x.device)
         arg = torch.empty(B, C, dtype=torch.int32, device=x.device)
-        _run("hsp_points_max_fwd", (_p(x), B, N, C, _p(out), _p(arg), _stream()), key=f"B{B}N{N}C{C}",
-             abytes=B * (4 * N * C + 8 * C))
+        _run("hsp_points_max_fwd" + _sfx(x), (_p(x), B, N, C, _p(out), _p(arg), _stream()), key=f"B{B}N{N}C{C}",
+             abytes=B * (_es(x) * N * C + 8 * C))
         ctx.save_for_backward(arg)
-        ctx.dims = (B, N, C)
+        ctx.dims, ctx.dtype = (B, N, C), x.dtype
         return out
 
     @staticmethod
@@ -460,9 +461,9 @@ class _PointsMax(torch.autograd.Function):
         (arg,) = ctx.saved_tensors
         B, N, C = ctx.dims
         g = _req(g, torch.float32, "points_max.grad")
-        gx = torch.empty(B, N, C, dtype=torch.float32, device=g.device)
-        _run("hsp_points_max_bwd", (_p(g), _p(arg), B, N, C, _p(gx), _stream()), key=f"B{B}N{N}C{C}",
-             abytes=B * (4 * N * C + 8 * C))
+        gx = torch.empty(B, N, C, dtype=ctx.dtype, device=g.device)
+        _run("hsp_points_max_bwd" + _sfx(gx), (_p(g), _p(arg), B, N, C, _p(gx), _stream()), key=f"B{B}N{N}C{C}",
+             abytes=B * (_es(gx) * N * C + 8 * C))
         return gx
 
 
@@ -512,11 +513,7 @@ def pool_layer(feat, xyz, idx, qsel, k):
 
 
 def points_max(x):
-    """max over dim 1 of a point-major (B,N,C) tensor -> (B,C)   (the heads' torch.max(x, 2)[0]); bf16 rows: fp32 (B,C)
-    (ops_bf16)."""
-    if x.dtype == torch.bfloat16:
-        from . import ops_bf16
-        return ops_bf16.points_max(x)
+    """max over dim 1 of a point-major (B,N,C) tensor -> (B,C)   (the heads' torch.max(x, 2)[0]); bf16 rows: fp32 (B,C)."""
     return _PointsMax.apply(x)
 
 
@@ -542,6 +539,15 @@ def orl_global(feat, idx, k):
 #             gF = g + g Wa  (+= ORL scatter of gfg/N, accumulated by the kernel) ; gWa = g^T F
 #             gfm, gD = graph_conv_bwd(gF) ; gW = X^T gfm ; gb = colsum(gfm)
 #             gX = g Wste + gfm W^T ; gWste = g^T X
+# The same chain runs on fp32 and on bf16 feature rows (hs_pose_amd/ops_bf16.py says what bf16 stores); each kernel wrapper picks
+# its entry point by the rows' dtype and each product its weight operand (``_weight_of``).  Where a dtype departs from the chain:
+#   fp32 only   the eval-mode forward in the reference's operation order and the C++ one-call inference forms (exact_scope)
+#               bn_shift: the out product also leaves the BatchNorm's first pass (a second output)
+#               the x3 weight planes of the forward's registry, kept for the backward (ctx.x3)
+#               gt, gWb, gfg in two launches (_orl_bwd_small_ok); gWa and gWste in one (wgrad_pair); gather-form backward kernels
+#               under DETERMINISTIC; the surface layer's relu fork and its gWa fold batched with the step's folds
+#   bf16 only   out_f32: the output is written in fp32 (a BatchNorm follows); an fp32 incoming gradient is rounded to bf16 once
+#               surface layer: the STE gradient from the coordinate moments only up to 64 clouds, else g^T xyz in fp32 by torch
 # ------------------------------------------------------------------------------------------------
 
 def _wgrad_fallback(A2, B2, out, colsum):
@@ -642,18 +648,17 @@ def _hold(t):
     return None if t is None else t.untyped_storage()
 
 
-def _rf_bwd_dirs_call(name, args_before_ws, ws, wsb, keep, key, abytes):
-    """run a receptive-field backward entry point ``name`` (args ..., ws, ws_bytes, stream); inside a ``StepFolds`` scope its
-    ``_partial`` form, whose direction-gradient fold goes out with the step's other folds.  keep: tensors the pending fold
-    reads / writes (kept alive until it has run)."""
+def _rf_bwd_dirs_call(base, sfx, args_before_ws, ws, wsb, keep, key, abytes):
+    """run the receptive-field backward entry point ``base + sfx`` (args ..., ws, ws_bytes, stream); inside a ``StepFolds`` scope
+    its form ``base + "_partial" + sfx``, whose direction-gradient fold goes out with the step's other folds.  keep: tensors the
+    pending fold reads / writes (kept alive until it has run)."""
     sf = StepFolds.current
     if sf is None:
-        _run(name, (*args_before_ws, _p(ws), wsb, _stream()), key=key, abytes=abytes)
+        _run(base + sfx, (*args_before_ws, _p(ws), wsb, _stream()), key=key, abytes=abytes)
         return
     from ._lib import HspDirsPending
     pend = HspDirsPending()
-    pname = name.replace("_bf16", "") + "_partial" + ("_bf16" if name.endswith("_bf16") else "")
-    _run(pname, (*args_before_ws, _p(ws), wsb, ctypes.byref(pend), _stream()), key=key, abytes=abytes)
+    _run(base + "_partial" + sfx, (*args_before_ws, _p(ws), wsb, ctypes.byref(pend), _stream()), key=key, abytes=abytes)
     sf.dirs.append((pend, ws) + tuple(_hold(t) for t in keep))
 
 
@@ -692,17 +697,26 @@ def wgrad(A2, B2, out=None, colsum=False):
     N = B2.shape[1]
     if out is None:
         out = torch.empty(M, N, dtype=torch.float32, device=A2.device)
-    if _wgrad_ragged_ok(A2, B2, out) or _wgrad_ok(A2, B2, out):
+    bf16 = A2.dtype == torch.bfloat16
+    if _wgrad_ragged_ok(A2, B2, out):          # (fp32: hsp_wgrad_f32 takes the ragged M itself; bf16: an entry point of its own)
+        return _wgrad_custom(A2, B2, out, colsum, entry="hsp_wgrad_ragged" if bf16 else "hsp_wgrad")
+    if _wgrad_ok(A2, B2, out):
         return _wgrad_custom(A2, B2, out, colsum)
+    if bf16:                                   # (the general tile kernel below is the fp32 rows' fallback only)
+        raise HspError("bf16 weight gradient: channel counts must be multiples of 64")
     return _wgrad_fallback(A2, B2, out, colsum)
 
 
 def _wgrad_ragged_ok(A2, B2, out):
     """A2^T B2 with M = A2.shape[1] NOT a multiple of 64 (the heads' first layers: K = 1286 / 1289 / 771 input columns,
     PoseR.py:27, PoseTs.py:32, FaceRecon.py:38,116) on the x3 kernel: fp32 rows of A2 on a 16-byte pitch that covers ceil4(M)
-    (``assemble_feat`` / ``cat_rows_pitched`` lay them out so), N a multiple of 128"""
+    (``assemble_feat`` / ``cat_rows_pitched`` lay them out so), N a multiple of 128.  bf16 rows (``hsp_wgrad_ragged_bf16``): any
+    M that is no multiple of 64, both operands on a 16-byte pitch (feat's 1286 columns on their 1288 pitch)"""
     K, M = A2.shape
     N = B2.shape[1]
+    if A2.dtype == torch.bfloat16:
+        return (M % 64 != 0 and N % 128 == 0 and A2.stride(1) == 1 and B2.stride(1) == 1 and A2.stride(0) % 8 == 0
+                and B2.stride(0) % 8 == 0)
     return (M % 64 != 0 and M >= 128 and N % 128 == 0
             and -(-M // 128) * (N // 128) >= 4 and A2.dtype == torch.float32 and B2.dtype == torch.float32 and A2.is_cuda
             and A2.stride(1) == 1 and B2.stride(1) == 1 and out.stride(1) == 1 and A2.stride(0) % 4 == 0 and B2.stride(0) % 4 == 0
@@ -713,15 +727,15 @@ def _wgrad_ok(A2, B2, out):
     K, M = A2.shape
     N = B2.shape[1]
     return (M % 64 == 0 and N % 64 == 0 and A2.stride(1) == 1 and B2.stride(1) == 1 and out.stride(1) == 1
-            and A2.stride(0) % 2 == 0 and B2.stride(0) % 2 == 0 and A2.dtype == torch.float32 and A2.is_cuda)
+            and A2.stride(0) % 2 == 0 and B2.stride(0) % 2 == 0 and A2.dtype in _FEAT_DTYPES and A2.is_cuda)
 
 
 def wgrad_pair(A0, B0, out0, A1, B1, out1):
     """(A0^T B0 -> out0, A1^T B1 -> out1) inside a ``WgradBatch``: ONE split-K launch for both when each is a K-sliced problem the
     hand-written kernel takes (the two parameter gradients of an HS layer that depend only on the incoming gradient: g^T F and
-    g^T X -- each alone leaves most of the chip idle); otherwise two ``wgrad`` calls."""
+    g^T X -- each alone leaves most of the chip idle); otherwise, and for bf16 rows (the pair kernel is fp32), two ``wgrad`` calls."""
     batch = WgradBatch.current
-    if batch is None or not _wgrad_ok(A0, B0, out0) or not _wgrad_ok(A1, B1, out1):
+    if batch is None or A0.dtype != torch.float32 or not _wgrad_ok(A0, B0, out0) or not _wgrad_ok(A1, B1, out1):
         wgrad(A0, B0, out=out0)
         wgrad(A1, B1, out=out1)
         return
@@ -1071,6 +1085,9 @@ def gemm_own(A1, B1, nn1=False, A2=None, B2=None, nn2=False, bias=None, resid=No
     (csrc/gemm_wave.hip) when the output is large against a short K -- many tiles that each live for a few k-blocks: fm = X W + b
     and the g Wa products; measured 13-14 us against 15-19 us, 24-48 us against 36-67 us -- and the LDS-staged tile kernel
     (csrc/gemm_rows.hip: any K / alignment, split-K) otherwise."""
+    if A1.dtype == torch.bfloat16 and not relu:      # bf16 rows: one kernel family; every choice below is between fp32 kernels
+        return gemm_rows(A1, B1, nn1, A2, B2, nn2, bias=bias, resid=resid, cloud_bias=cloud_bias, rows_per_cloud=rows_per_cloud,
+                         out=out, alpha=alpha, xyz3=xyz3, w3=w3)
     M, K1 = A1.shape
     N = B1.shape[1] if nn1 else B1.shape[0]
     K2 = A2.shape[1] if A2 is not None else 0
@@ -1102,37 +1119,70 @@ def gemm_own(A1, B1, nn1=False, A2=None, B2=None, nn2=False, bias=None, resid=No
     return torch.relu_(res) if relu else res
 
 
+# parameter (by storage pointer) -> (bf16 copy, bf16 transposed copy, weak reference to the owning ops_bf16.Bf16Params)
+_copies = {}
+
+
+def copies_of(param):
+    """(bf16 copy, bf16 transposed copy) of a WHOLE 2-D parameter, as ``ops_bf16.Bf16Params`` registered and last refreshed them"""
+    hit = _copies.get(param.data_ptr())
+    if hit is not None:                       # the address may have been re-used by another tensor since: the shape must match
+        c, ct = hit[0], hit[1]
+        shape = tuple(param.shape)
+        if (c is not None and tuple(c.shape) != shape) or (ct is not None and tuple(ct.shape) != shape[::-1]):
+            hit = None
+    if hit is None:
+        raise HspError("bf16 path: no bf16 working copy registered for this parameter (set the dtype on the whole network: "
+                       "HSPose.set_feature_dtype / PoseNet9D.set_feature_dtype, or FaceRecon.set_feature_dtype for a backbone alone)")
+    return hit[0], hit[1]
+
+
+def _weight_of(rows, W, nn, cols=None):
+    """(operand, nn flag) of the product of ``rows`` with the parameter matrix W -- (N,K), or (K,N) with ``nn`` --, or with its
+    column block ``cols`` (a slice).  fp32 rows read the parameter itself; bf16 rows its working copy in (N,K) form (the
+    transposed copy of a (K,N) matrix: the bf16 kernel takes no other form).  The copies are registered per whole parameter,
+    hence ``cols`` instead of a view."""
+    if rows.dtype == torch.float32:
+        return (W if cols is None else W[:, cols]), nn
+    Wc = copies_of(W)[1 if nn else 0]
+    if cols is not None:
+        Wc = Wc[cols] if nn else Wc[:, cols]
+    return Wc, False
+
+
 def _fm_rows(X2, weights, bias, out=None):
     """fm = X W + b   (gcn3d.py:171)"""
-    return gemm_own(X2, weights, True, bias=bias, out=out)
+    return gemm_own(X2, *_weight_of(X2, weights, True), bias=bias, out=out)
 
 
-def _layer_out_rows(x2, w_ste, F2, Wa, t2, out3, relu=False, bn_shift=None):
+def _layer_out_rows(x2, w_ste, F2, w_conv2, t2, out3, relu=False, bn_shift=None):
     """... ``bn_shift`` not None (own mode, x3 shapes): also returns the BatchNorm first-pass buffer of the result (else None)"""
-    if bn_shift is not None and _layer_out_bn_ok(x2, w_ste, F2, Wa, t2, out3, relu):
-        B_, N_, C_ = out3.shape
-        return gemm_x3_bn(x2, w_ste, F2, Wa, F2, t2.contiguous(), N_, out3.view(B_ * N_, C_))
-    _layer_out_rows_plain(x2, w_ste, F2, Wa, t2, out3, relu)
+    B_, N_, C_ = out3.shape
+    if bn_shift is not None and _layer_out_bn_ok(x2, w_ste, F2, w_conv2[:, :C_], t2, out3, relu):
+        return gemm_x3_bn(x2, w_ste, F2, w_conv2[:, :C_], F2, t2.contiguous(), N_, out3.view(B_ * N_, C_))
+    _layer_out_rows_plain(x2, w_ste, F2, w_conv2, t2, out3, relu)
     return None
 
 
-def _layer_out_rows_plain(x2, w_ste, F2, Wa, t2, out3, relu=False):
-    """out = x Wste^T + F Wa^T + F + t[cloud]   (gcn3d.py:149,186,156): one fused launch"""
+def _layer_out_rows_plain(x2, w_ste, F2, w_conv2, t2, out3, relu=False):
+    """out = x Wste^T + F Wa^T + F + t[cloud], conv2 = [Wa | Wb]   (gcn3d.py:149,186,156): one fused launch"""
     B, N, C = out3.shape
     out = out3.view(B * N, C)
+    Wa, _ = _weight_of(F2, w_conv2, False, slice(0, C))
     if x2.shape[1] == 3:                                  # HSlayer_surface: the K = 3 STE on raw coordinates rides in the epilogue
         gemm_own(F2, Wa, False, resid=F2, cloud_bias=t2.contiguous(), rows_per_cloud=N, out=out, xyz3=x2,
                  w3=w_ste.contiguous(), relu=relu)       # (... and so does the relu that follows conv_0)
     else:
-        gemm_own(x2, w_ste, False, F2, Wa, False, resid=F2, cloud_bias=t2.contiguous(), rows_per_cloud=N, out=out)
+        gemm_own(x2, _weight_of(x2, w_ste, False)[0], False, F2, Wa, False, resid=F2, cloud_bias=t2.contiguous(),
+                 rows_per_cloud=N, out=out)
         if relu:
             torch.relu_(out3)
     return out3
 
 
-def _mm_nn(g2, W, out=None, alpha=1.0):
-    """alpha * (g @ W) for a row-strided (K,N) matrix W"""
-    return gemm_own(g2, W, True, out=out, alpha=alpha)
+def _mm_nn(g2, W, out=None, alpha=1.0, cols=None):
+    """alpha * (g @ W) for a row-strided (K,N) matrix W, or (``cols``) for that column block of the parameter W"""
+    return gemm_own(g2, *_weight_of(g2, W, True, cols), out=out, alpha=alpha)
 
 
 def _mm_nt(x2, W, bias=None, out=None):
@@ -1142,7 +1192,7 @@ def _mm_nt(x2, W, bias=None, out=None):
 
 def _grad_in_rows(g2, w_ste, gfm2, weights, out):
     """gX = g Wste + gfm W^T   (input gradient of gcn3d.py:149 and :171)"""
-    return gemm_own(g2, w_ste, True, gfm2, weights, False, out=out)
+    return gemm_own(g2, *_weight_of(g2, w_ste, True), gfm2, *_weight_of(gfm2, weights, False), out=out)
 
 
 def small_rows(A, W, nn=False, out=None, alpha=1.0):
@@ -1176,15 +1226,16 @@ def _tiny_tn(a, b, out, mom=None, gste=None):
 
 
 def _orl_fwd_raw(F3, idx_x, k):
-    """(fg (B,C), argmax (B,N,C) uint8): mean over points of the neighbourhood max, one pass, no (B,N,C) max tensor"""
+    """(fg (B,C) fp32, argmax (B,N,C) uint8): mean over points of the neighbourhood max of fp32 / bf16 rows, one pass, no (B,N,C)
+    max tensor"""
     B, N, C = F3.shape
     fg = torch.empty(B, C, dtype=torch.float32, device=F3.device)
     arg = torch.empty(B, N, C, dtype=torch.uint8, device=F3.device)
     L = lib()
     wsb = L.hsp_orl_workspace_bytes(B, N, C)
     ws = _ws(wsb, F3.device)
-    _run("hsp_orl_global_fwd", (_p(F3), _p(idx_x), B, N, k, idx_x.shape[2], C, _p(fg), _p(arg), _p(ws), wsb, _stream()),
-         key=f"B{B}N{N}k{k}C{C}", abytes=B * N * (4 * C + 4 * k + C))
+    _run("hsp_orl_global_fwd" + _sfx(F3), (_p(F3), _p(idx_x), B, N, k, idx_x.shape[2], C, _p(fg), _p(arg), _p(ws), wsb, _stream()),
+         key=f"B{B}N{N}k{k}C{C}", abytes=B * N * (_es(F3) * C + 4 * k + C))
     return fg, arg
 
 
@@ -1196,15 +1247,16 @@ def _residual_bias(out3, f3, t2):
 
 
 def colsum_rows(x3):
-    """(B,C) = x3.sum(dim=1) for a contiguous (B,N,C) fp32 tensor: deterministic two-stage column sum"""
+    """fp32 (B,C) = x3.sum(dim=1) for a contiguous (B,N,C) fp32 / bf16 tensor: deterministic two-stage column sum"""
     B, N, C = x3.shape
-    if ((C % 4 or 256 % (C // 4)) and C > 256) or not x3.is_contiguous():
+    if x3.dtype == torch.float32 and (((C % 4 or 256 % (C // 4)) and C > 256) or not x3.is_contiguous()):
         return x3.sum(dim=1)
     out = torch.empty(B, C, dtype=torch.float32, device=x3.device)
     L = lib()
     wsb = L.hsp_orl_workspace_bytes(B, N, C)
     ws = _ws(wsb, x3.device)
-    _run("hsp_colsum_rows", (_p(x3), B, N, C, _p(out), _p(ws), wsb, _stream()), key=f"B{B}N{N}C{C}", abytes=4 * B * N * C)
+    _run("hsp_colsum_rows" + _sfx(x3), (_p(x3), B, N, C, _p(out), _p(ws), wsb, _stream()), key=f"B{B}N{N}C{C}",
+         abytes=_es(x3) * B * N * C)
     return out
 
 
@@ -1253,9 +1305,10 @@ def _orl_bwd_small(g, xyz, fg, Wb, gWb, gste=None):
 
 
 def _orl_bwd_accumulate_raw(gfg_over_n, idx_x, arg, k, gF3, extra=None):
-    """gF3[b,m,c] += extra[b,m,c] + gfg_over_n[b,c] * #{i : idx_x[b,i,arg[b,i,c]] == m}     (in place, one pass)"""
+    """gF3[b,m,c] += extra[b,m,c] + gfg_over_n[b,c] * #{i : idx_x[b,i,arg[b,i,c]] == m}     (in place, one pass); fp32 / bf16 rows
+    (the reverse-edge form of DETERMINISTIC is fp32-only)"""
     B, N, C = gF3.shape
-    if DETERMINISTIC:
+    if DETERMINISTIC and gF3.dtype == torch.float32:
         tmp = torch.empty_like(gF3)
         off, edge = rev_index(idx_x, k, N)
         _run("hsp_gather_max_bwd_csr", (_p(gfg_over_n), 1, _p(arg), _p(off), _p(edge), B, N, N, k, C, _p(tmp), _stream()),
@@ -1264,45 +1317,53 @@ def _orl_bwd_accumulate_raw(gfg_over_n, idx_x, arg, k, gF3, extra=None):
         if extra is not None:
             gF3.add_(extra)
     else:
-        _run("hsp_gather_max_bwd", (_p(gfg_over_n), 1, _p(idx_x), _vp(0), _p(arg), B, N, N, N, idx_x.shape[2], C,
-                                    _p(gF3), 1, _p(extra), _stream()),
-             key=f"B{B}Ns{N}Nq{N}C{C}bc+", abytes=B * N * (12 * C + 4 * idx_x.shape[2] + C))
+        _run("hsp_gather_max_bwd" + _sfx(gF3), (_p(gfg_over_n), 1, _p(idx_x), _vp(0), _p(arg), B, N, N, N, idx_x.shape[2], C,
+                                                _p(gF3), 1, _p(extra), _stream()),
+             key=f"B{B}Ns{N}Nq{N}C{C}bc+", abytes=B * N * (3 * _es(gF3) * C + 4 * idx_x.shape[2] + C))
 
 
 def _rf_conv_fwd_raw(xyz, idx, directions, fm, S, need_bwd=True):
-    """(out (B,N,C), argrow (B,N,SC) uint16, fwin (B,N,SC) | None).  fwin = the winners' support values, all the
-    column-tile backward needs of fm once a cloud's fm outgrows L2 (hsp_rf_conv_wants_fwin); smaller layers and
-    the gather-form backward (DETERMINISTIC) read fm itself."""
+    """(out (B,N,C), argrow (B,N,SC) uint16, fwin (B,N,SC) | None) for fp32 / bf16 ``fm`` (out and fwin in its dtype).  fwin = the
+    winners' support values, all the column-tile backward needs of fm once a cloud's fm outgrows L2 (hsp_rf_conv_wants_fwin);
+    smaller layers and the gather-form backward (DETERMINISTIC, fp32 rows only) read fm itself."""
     B, N, k = idx.shape
     SC = directions.shape[1]
     C = SC // S
-    out = torch.empty(B, N, C, dtype=torch.float32, device=xyz.device)
+    sfx, es = _sfx(fm), _es(fm)
+    out = torch.empty(B, N, C, dtype=fm.dtype, device=xyz.device)
     arg = torch.empty(B, N, SC, dtype=torch.uint16, device=xyz.device)
-    want = need_bwd and not DETERMINISTIC and lib().hsp_rf_conv_wants_fwin(N, S, C)
-    fwin = torch.empty(B, N, SC, dtype=torch.float32, device=xyz.device) if want else None
+    want = need_bwd and (sfx or not DETERMINISTIC) and getattr(lib(), "hsp_rf_conv_wants_fwin" + sfx)(N, S, C)
+    fwin = torch.empty(B, N, SC, dtype=fm.dtype, device=xyz.device) if want else None
     key = f"B{B}N{N}k{k}S{S}C{C}"
-    # algorithmic bytes per point (DESIGN.md section 4): (S+1) C 4 + 4 k + 12 in, 4 C + S C out (a one-byte arg-max slot).  The
-    # kernel itself writes a uint16 winning ROW per slot (the backward then needs neither idx nor the slot -> one gather fewer) and,
-    # when a cloud's fm outgrows L2, the winners' support values: its designed stream is recorded next to the algorithmic count
-    design_stream_bytes[("hsp_rf_conv_fwd", key)] = B * N * (12 + 4 * k + 4 * (S + 1) * C + 4 * C + 2 * SC
-                                                             + (4 * SC if fwin is not None else 0)) + 12 * SC
-    _run("hsp_rf_conv_fwd", (_p(xyz), _p(idx), _p(directions), _p(fm), B, N, k, S, C, _p(out), _p(arg), _p(fwin),
-                             _stream()),
-         key=key, abytes=B * N * (12 + 4 * k + 4 * (S + 1) * C + 4 * C + SC) + 12 * SC)
+    # what the kernel streams by design: a uint16 winning ROW per slot (the backward then needs neither idx nor the slot -> one
+    # gather fewer) and, when a cloud's fm outgrows L2, the winners' support values
+    stream = B * N * (12 + 4 * k + es * (S + 1) * C + es * C + 2 * SC + (es * SC if fwin is not None else 0)) + 12 * SC
+    if sfx:
+        ab = stream          # deliberate: the bf16 call's figure counts the two-byte slot and fwin, and no design stream is recorded
+    else:
+        # algorithmic bytes per point (DESIGN.md section 4): (S+1) C 4 + 4 k + 12 in, 4 C + S C out (a one-byte arg-max slot); the
+        # designed stream is recorded next to that count
+        design_stream_bytes[("hsp_rf_conv_fwd", key)] = stream
+        ab = B * N * (12 + 4 * k + 4 * (S + 1) * C + 4 * C + SC) + 12 * SC
+    _run("hsp_rf_conv_fwd" + sfx, (_p(xyz), _p(idx), _p(directions), _p(fm), B, N, k, S, C, _p(out), _p(arg), _p(fwin), _stream()),
+         key=key, abytes=ab)
     return out, arg, fwin
 
 
 def _rf_conv_bwd_raw(xyz, idx, directions, fm, arg, gF3, S):
-    """fm: either fm (B,N,(S+1)C) or the forward's fwin (B,N,SC) (told apart by the width)."""
-    B, N, k = idx.shape
+    """fm: either fm (B,N,(S+1)C) or the forward's fwin (B,N,SC) (told apart by the width); fp32 / bf16 rows (bf16 has no
+    gather form: it takes the column-tile scatter whatever DETERMINISTIC says, and needs no ``idx``)."""
+    B, N, _ = gF3.shape
     SC = directions.shape[1]
     C = SC // S
-    gfm = torch.empty(B, N, (S + 1) * C, dtype=torch.float32, device=gF3.device)
+    sfx, es = _sfx(gF3), _es(gF3)
+    gfm = torch.empty(B, N, (S + 1) * C, dtype=gF3.dtype, device=gF3.device)
     gd = torch.empty_like(directions)
     L = lib()
-    if DETERMINISTIC:
+    if DETERMINISTIC and not sfx:
         wsb = L.hsp_rf_bwd_workspace_bytes(SC)
         ws = _ws(wsb, gF3.device)
+        k = idx.shape[2]
         off, edge = rev_index(idx, k, N)
         # (section 4: S C + 4 S C + 4 C in -- arg slot, the winners' support values, grad_out -- and 4 (S+1) C out per point)
         design_stream_bytes[("hsp_rf_conv_bwd", f"B{B}N{N}k{k}S{S}C{C}")] = B * N * (12 + 8 * k + 6 * SC + 4 * C + 4 * (S + 1) * C) + 24 * SC
@@ -1313,10 +1374,16 @@ def _rf_conv_bwd_raw(xyz, idx, directions, fm, arg, gF3, S):
         wsb = L.hsp_rf_bwd_scatter_workspace_bytes(B, SC)
         ws = _ws(wsb, gF3.device)
         is_fwin = fm.shape[-1] == SC
-        design_stream_bytes[("hsp_rf_conv_bwd_scatter", f"B{B}N{N}S{S}C{C}")] = B * N * (12 + 6 * SC + 4 * C + 4 * (S + 1) * C) + 24 * SC
-        _rf_bwd_dirs_call("hsp_rf_conv_bwd_scatter", (_p(xyz), _p(directions), _p(None if is_fwin else fm), _p(fm if is_fwin else None),
-                                                      _p(arg), _p(gF3), B, N, S, C, _p(gfm), _p(gd)), ws, wsb, (directions, gd),
-                          key=f"B{B}N{N}S{S}C{C}", abytes=B * N * (12 + 5 * SC + 4 * C + 4 * (S + 1) * C) + 24 * SC)
+        key = f"B{B}N{N}S{S}C{C}"
+        stream = B * N * (12 + (2 + es) * SC + es * C + es * (S + 1) * C) + 24 * SC       # (two-byte winning-row slots)
+        if sfx:
+            ab = stream      # deliberate, as in the forward: the bf16 figure is the stream itself, none recorded
+        else:
+            design_stream_bytes[("hsp_rf_conv_bwd_scatter", key)] = stream
+            ab = B * N * (12 + 5 * SC + 4 * C + 4 * (S + 1) * C) + 24 * SC
+        _rf_bwd_dirs_call("hsp_rf_conv_bwd_scatter", sfx, (_p(xyz), _p(directions), _p(None if is_fwin else fm),
+                                                           _p(fm if is_fwin else None), _p(arg), _p(gF3), B, N, S, C, _p(gfm), _p(gd)),
+                          ws, wsb, (directions, gd), key=key, abytes=ab)
     return gfm, gd
 
 
@@ -1402,13 +1469,15 @@ def _layer_out_exact(F2, w_conv2, fg, N, out3, ste=None, xyz3=None, w3=None, rel
 
 
 class _HSLayer(torch.autograd.Function):
+    """HS_layer.forward (gcn3d.py:143-156) on fp32 or bf16 feature rows; parameters are the fp32 masters (gradients fp32)."""
+
     @staticmethod
-    def forward(ctx, xyz, X, idx_f, idx_x, k, S, weights, bias, directions, w_ste3, w_conv23, bn_shift=None):
+    def forward(ctx, xyz, X, idx_f, idx_x, k, S, weights, bias, directions, w_ste3, w_conv23, bn_shift=None, out_f32=False):
         # Conv1d weights arrive in their native (out, in, 1) shape and their gradients are returned in it:
         # a squeezed view would make AccumulateGrad clone every gradient (one D2D copy per tensor and step)
         w_ste, w_conv2 = w_ste3.squeeze(-1), w_conv23.squeeze(-1)
         xyz = _req(xyz, torch.float32, "hs_layer.xyz")
-        X = _req(X, torch.float32, "hs_layer.X")
+        X = _reqf(X, "hs_layer.X")
         idx_f = _req(idx_f, torch.int32, "hs_layer.idx_f")
         idx_x = _req(idx_x, torch.int32, "hs_layer.idx_x")
         directions = _req(directions, torch.float32, "hs_layer.directions")
@@ -1416,7 +1485,7 @@ class _HSLayer(torch.autograd.Function):
         SC = directions.shape[1]
         C = SC // S
         X2 = X.view(B * N, Cin)
-        exact = _exact and bn_shift is None and _exact_layer_ok(N, Cin, C, (X2, weights, w_ste, w_conv2))
+        exact = _exact and bn_shift is None and _exact_layer_ok(N, Cin, C, (X2, weights, w_ste, w_conv2))     # (fp32 rows only)
         # exact: fm = (X W, a k-ordered chain) + b -- gcn3d.py:171 as the reference's CPU GEMM rounds it
         fm = gemm_wave(X2, weights, True, bias=bias) if exact else _fm_rows(X2, weights, bias)      # (BN, (S+1)C)
         need_bwd = any(ctx.needs_input_grad)
@@ -1425,18 +1494,19 @@ class _HSLayer(torch.autograd.Function):
             fm = fwin                                                          # fm itself is no longer needed
         fm = fm.view(B, N, -1)
         F2 = F3.view(B * N, C)
-        out3 = torch.empty(B, N, C, dtype=torch.float32, device=X.device)      # (returned as is: not a view)
+        # (returned as is: not a view.  bf16 rows ahead of a BatchNorm, ``out_f32``: written in fp32 -- the per-channel mean is
+        # often >> the std, bf16 would leave the normalised value a handful of significant bits; the gradient comes back bf16)
+        out3 = torch.empty(B, N, C, dtype=torch.float32 if out_f32 else X.dtype, device=X.device)
         if exact:
             fg, arg_o = _orl_fwd_exact(F3, idx_x, k)
             _layer_out_exact(F2, w_conv2, fg, N, out3, ste=gemm_wave(X2, w_ste, False))
             part = None
         else:
-            fg, arg_o = _orl_fwd_raw(F3, idx_x, k)                             # (B,C)
-            t2 = _mm_nt(fg, w_conv2[:, C:])                                    # (B,C): the per-cloud half of conv2
-            part = _layer_out_rows(X2, w_ste, F2, w_conv2[:, :C], t2, out3, bn_shift=bn_shift)   # X Wste^T + F Wa^T + F + t[b]
+            fg, arg_o = _orl_fwd_raw(F3, idx_x, k)                             # fp32 (B,C)
+            t2 = _mm_nt(fg, w_conv2[:, C:])                                    # fp32 (B,C): the per-cloud half of conv2
+            part = _layer_out_rows(X2, w_ste, F2, w_conv2, t2, out3, bn_shift=bn_shift)          # X Wste^T + F Wa^T + F + t[b]
         ctx.save_for_backward(xyz, X, idx_f, idx_x, fm, arg, F3, arg_o, fg, weights, directions, w_ste3, w_conv23)
         ctx.k, ctx.S, ctx.x3 = k, S, x3_planes
-        ctx.with_part = bn_shift is not None
         if bn_shift is not None:
             # second output: the BatchNorm partial sums of out3 (or an empty tensor when the product that ran does not leave
             # them); not differentiable
@@ -1452,40 +1522,43 @@ class _HSLayer(torch.autograd.Function):
         xyz, X, idx_f, idx_x, fm, arg, F3, arg_o, fg, weights, directions, w_ste3, w_conv23 = ctx.saved_tensors
         w_ste, w_conv2 = w_ste3.squeeze(-1), w_conv23.squeeze(-1)
         k, S = ctx.k, ctx.S
-        g = _req(g, torch.float32, "hs_layer.grad")
+        f32 = X.dtype == torch.float32
+        if not f32 and g.dtype == torch.float32:      # fp32 output (ahead of a BatchNorm): autograd hands its gradient back in fp32
+            g = g.bfloat16()
+        g = _reqf(g, "hs_layer.grad", like=X)
         B, N, Cin = X.shape
         C = F3.shape[2]
         g2, X2, F2 = g.view(B * N, C), X.view(B * N, Cin), F3.view(B * N, C)
-        Wa, Wb = w_conv2[:, :C], w_conv2[:, C:]
-        small = _orl_bwd_small_ok(B, N, C, False)
+        Wb = w_conv2[:, C:]
+        small = f32 and _orl_bwd_small_ok(B, N, C, False)
         g_conv2 = torch.empty_like(w_conv2)
         if small:
             gfg_n = _orl_bwd_small(g, None, fg, Wb, g_conv2[:, C:])            # gt = sum_i g, gWb = gt^T fg, gt Wb / N: two launches
         else:
-            gt = colsum_rows(g)                                                # (B,C) = sum_i g
+            gt = colsum_rows(g)                                                # fp32 (B,C) = sum_i g
         with WgradBatch(), x3_scope(ctx.x3):                                   # the three parameter gradients: one fold launch
             g_ste = torch.empty(C, Cin, dtype=torch.float32, device=g.device)
             wgrad_pair(g2, F2, g_conv2[:, :C], g2, X2, g_ste)                  # gWa (in place, ldc = 2C) and gWste: one split-K launch
             if not small:
                 _tiny_tn(gt, fg, g_conv2[:, C:])                               # gWb = gt^T fg (tiny), straight into its column block
-            gF3 = torch.empty(B, N, C, dtype=torch.float32, device=g.device)
-            _mm_nn(g2, Wa, out=gF3.view(B * N, C))                             # g Wa ...
+            gF3 = torch.empty(B, N, C, dtype=g.dtype, device=g.device)
+            _mm_nn(g2, w_conv2, out=gF3.view(B * N, C), cols=slice(0, C))      # g Wa ...
             if not small:
                 gfg_n = _mm_nn(gt, Wb, alpha=1.0 / N)
             _orl_bwd_accumulate_raw(gfg_n, idx_x, arg_o, k, gF3, extra=g)      # ... + g + ORL scatter, one pass
             gfm, gD = _rf_conv_bwd_raw(xyz, idx_f, directions, fm.view(B, N, -1), arg, gF3, S)
             gfm2 = gfm.view(B * N, -1)
             gW, gb = wgrad(X2, gfm2, colsum=True)                              # X^T gfm and the bias gradient
-            gX3 = torch.empty(B, N, Cin, dtype=torch.float32, device=g.device)
+            gX3 = torch.empty(B, N, Cin, dtype=g.dtype, device=g.device)
             _grad_in_rows(g2, w_ste, gfm2, weights, gX3.view(B * N, Cin))      # g Wste + gfm W^T
-        return None, gX3, None, None, None, None, gW, gb, gD, g_ste.unsqueeze_(-1), g_conv2.unsqueeze_(-1), None
+        return None, gX3, None, None, None, None, gW, gb, gD, g_ste.unsqueeze_(-1), g_conv2.unsqueeze_(-1), None, None
 
 
 class _SurfaceLayer(torch.autograd.Function):
-    """HSlayer_surface.forward (gcn3d.py:79-90) as one node; xyz carries no gradient."""
+    """HSlayer_surface.forward (gcn3d.py:79-90) as one node producing fp32 or bf16 rows; xyz carries no gradient."""
 
     @staticmethod
-    def forward(ctx, xyz, idx_x, k, S, directions, w_ste3, w_conv23, relu=False):
+    def forward(ctx, xyz, idx_x, k, S, directions, w_ste3, w_conv23, relu=False, out_dtype=torch.float32):
         w_ste, w_conv2 = w_ste3.squeeze(-1), w_conv23.squeeze(-1)
         xyz = _req(xyz, torch.float32, "surface_layer.xyz")
         idx_x = _req(idx_x, torch.int32, "surface_layer.idx")
@@ -1495,19 +1568,22 @@ class _SurfaceLayer(torch.autograd.Function):
         C = SC // S
         if idx_x.shape[2] != k:
             raise HspError("surface_layer: idx must have exactly k columns")
-        F3 = torch.empty(B, N, C, dtype=torch.float32, device=xyz.device)
+        F3 = torch.empty(B, N, C, dtype=out_dtype, device=xyz.device)
         arg = torch.empty(B, N, SC, dtype=torch.uint16, device=xyz.device)
-        _run("hsp_rf_surface_fwd", (_p(xyz), _p(idx_x), _p(directions), B, N, k, S, C, _p(F3), _p(arg), _stream()),
-             key=f"B{B}N{N}k{k}S{S}C{C}", abytes=B * N * (12 + 4 * k + 4 * C + SC) + 12 * SC)
+        # (deliberate: the fp32 figures count a one-byte arg-max slot -- DESIGN.md section 4 --, the bf16 ones the two-byte
+        # winning-row slot the kernels write; here and in the backward)
+        slot = 1 if out_dtype == torch.float32 else 2
+        _run("hsp_rf_surface_fwd" + _sfx(F3), (_p(xyz), _p(idx_x), _p(directions), B, N, k, S, C, _p(F3), _p(arg), _stream()),
+             key=f"B{B}N{N}k{k}S{S}C{C}", abytes=B * N * (12 + 4 * k + _es(F3) * C + slot * SC) + 12 * SC)
         F2, x2 = F3.view(B * N, C), xyz.view(B * N, 3)
-        out3 = torch.empty(B, N, C, dtype=torch.float32, device=xyz.device)
-        if _exact and _exact_layer_ok(N, 3, C, (w_conv2,)):
+        out3 = torch.empty(B, N, C, dtype=out_dtype, device=xyz.device)
+        if _exact and _exact_layer_ok(N, 3, C, (w_conv2, F2)):                # (fp32 rows only)
             fg, arg_o = _orl_fwd_exact(F3, idx_x, k)
             _layer_out_exact(F2, w_conv2, fg, N, out3, xyz3=x2, w3=w_ste.contiguous(), relu=relu)
         else:
             fg, arg_o = _orl_fwd_raw(F3, idx_x, k)
             t2 = _mm_nt(fg, w_conv2[:, C:])
-            _layer_out_rows(x2, w_ste, F2, w_conv2[:, :C], t2, out3, relu=relu)
+            _layer_out_rows(x2, w_ste, F2, w_conv2, t2, out3, relu=relu)
         ctx.k, ctx.S, ctx.relu, ctx.x3 = k, S, relu, x3_planes
         if relu:
             # relu(conv_0(...)) (FaceRecon.py:88) inside the node: the relu rides in the product's epilogue, the result is handed
@@ -1524,7 +1600,7 @@ class _SurfaceLayer(torch.autograd.Function):
             xyz, idx_x, arg, F3, arg_o, fg, directions, w_conv23, y = ctx.saved_tensors
             gs = [t for t in gs if t is not None]
             if not gs:
-                return (None,) * 8
+                return (None,) * 9
             B, N, C = F3.shape
             (ga, lda) = _rows_pitch(gs[0], C)
             (gb, ldb) = _rows_pitch(gs[1], C) if len(gs) > 1 else (None, 0)
@@ -1536,14 +1612,15 @@ class _SurfaceLayer(torch.autograd.Function):
             g = gs[0]
         w_conv2 = w_conv23.squeeze(-1)
         k, S = ctx.k, ctx.S
-        g = _req(g, torch.float32, "surface_layer.grad")
+        g = _reqf(g, "surface_layer.grad", like=F3)
+        f32 = g.dtype == torch.float32
         B, N, C = F3.shape
         SC = directions.shape[1]
         g2, F2, x2 = g.view(B * N, C), F3.view(B * N, C), xyz.view(B * N, 3)
-        Wa, Wb = w_conv2[:, :C], w_conv2[:, C:]
+        Wb = w_conv2[:, C:]
         g_conv2 = torch.empty_like(w_conv2)
-        own_ste = _ste_moments_ok(C)
-        small = own_ste and _orl_bwd_small_ok(B, N, C, True)
+        own_ste = _ste_moments_ok(C) and (f32 or B <= 64)
+        small = f32 and own_ste and _orl_bwd_small_ok(B, N, C, True)
         if small:
             # the same chain (column sums + coordinate moments, gWb with the STE rider, gt Wb / N) in two launches
             g_ste = torch.empty(C, 3, dtype=torch.float32, device=g.device)
@@ -1556,17 +1633,20 @@ class _SurfaceLayer(torch.autograd.Function):
             g_ste = torch.empty(C, 3, dtype=torch.float32, device=g.device)
         else:
             gt = colsum_rows(g)
-        with WgradBatch():                                  # (its fold goes out with the step's folds inside a StepFolds scope)
-            wgrad(g2, F2, out=g_conv2[:, :C])
+        if f32:
+            with WgradBatch():                              # (its fold goes out with the step's folds inside a StepFolds scope)
+                wgrad(g2, F2, out=g_conv2[:, :C])
+        else:
+            wgrad(g2, F2, out=g_conv2[:, :C])               # (bf16: hsp_wgrad_bf16 folds itself, one launch)
         if small:
             pass                                            # (gWb and the STE gradient came out of the pair launch above)
         elif own_ste:
             _tiny_tn(gt, fg, g_conv2[:, C:], mom=mom, gste=g_ste)
         else:
             _tiny_tn(gt, fg, g_conv2[:, C:])
-        gF3 = torch.empty(B, N, C, dtype=torch.float32, device=g.device)
+        gF3 = torch.empty(B, N, C, dtype=g.dtype, device=g.device)
         with x3_scope(ctx.x3):
-            _mm_nn(g2, Wa, out=gF3.view(B * N, C))
+            _mm_nn(g2, w_conv2, out=gF3.view(B * N, C), cols=slice(0, C))
         if not small:
             gfg_n = _mm_nn(gt, Wb, alpha=1.0 / N)
         _orl_bwd_accumulate_raw(gfg_n, idx_x, arg_o, k, gF3, extra=g)
@@ -1574,38 +1654,45 @@ class _SurfaceLayer(torch.autograd.Function):
         L = lib()
         wsb = L.hsp_rf_bwd_scatter_workspace_bytes(B, SC)
         ws = _ws(wsb, g.device)
-        _rf_bwd_dirs_call("hsp_rf_surface_bwd", (_p(xyz), _p(directions), _p(arg), _p(gF3), B, N, S, C, _p(gD)), ws, wsb,
-                          (directions, gD), key=f"B{B}N{N}S{S}C{C}", abytes=B * N * (12 + 4 * C + SC) + 24 * SC)
+        _rf_bwd_dirs_call("hsp_rf_surface_bwd", _sfx(g), (_p(xyz), _p(directions), _p(arg), _p(gF3), B, N, S, C, _p(gD)), ws, wsb,
+                          (directions, gD), key=f"B{B}N{N}S{S}C{C}",
+                          abytes=B * N * (12 + _es(g) * C + (1 if f32 else 2) * SC) + 24 * SC)
         if not own_ste:
-            g_ste = wgrad(g2, x2)
-        return None, None, None, None, gD, g_ste.unsqueeze_(-1), g_conv2.unsqueeze_(-1), None
+            # (C,3): three columns -- not a matrix-core shape
+            g_ste = wgrad(g2, x2) if f32 else g2.float().t() @ x2
+        return None, None, None, None, gD, g_ste.unsqueeze_(-1), g_conv2.unsqueeze_(-1), None, None
 
 
-def hs_layer(xyz, X, idx_f, idx_x, k, S, weights, bias, directions, w_ste, w_conv2, bn_shift=None):
-    """HS_layer.forward (gcn3d.py:143-156) given the feature-space (idx_f, exactly k columns) and xyz-space
-    (idx_x, >= k columns) neighbour indices; w_ste (Cout,Cin,1), w_conv2 (Cout,2*Cout,1): the Conv1d weights.
-    ``bn_shift`` not None (a train-mode BatchNorm follows): returns (out, partial) where ``partial`` holds the first pass of that
-    BatchNorm's statistics, left by the out product's epilogue (empty when that product did not run on the kernel that does
-    it); pass both to ``bn_relu(out, bn, partial=partial)``."""
-    if bn_shift is None:
+def hs_layer(xyz, X, idx_f, idx_x, k, S, weights, bias, directions, w_ste, w_conv2, bn_shift=None, out_f32=False):
+    """HS_layer.forward (gcn3d.py:143-156) on fp32 or bf16 feature rows X, given the feature-space (idx_f, exactly k columns) and
+    xyz-space (idx_x, >= k columns) neighbour indices; w_ste (Cout,Cin,1), w_conv2 (Cout,2*Cout,1): the Conv1d weights.
+    ``bn_shift`` not None (fp32 rows, a train-mode BatchNorm follows): returns (out, partial) where ``partial`` holds the first pass
+    of that BatchNorm's statistics, left by the out product's epilogue (empty when that product did not run on the kernel that
+    does it); pass both to ``bn_relu(out, bn, partial=partial)``.  ``out_f32`` (bf16 rows, a BatchNorm follows): fp32 output."""
+    if X.dtype == torch.bfloat16:
+        bn_shift = None
+    elif bn_shift is None:
         if (_ext_inference() and _f32c(xyz, X, weights, bias, directions, w_ste, w_conv2) and idx_f.dtype == torch.int32
                 and idx_x.dtype == torch.int32 and idx_f.is_contiguous() and idx_x.is_contiguous()
                 and _exact_layer_ok(X.shape[1], X.shape[2], directions.shape[1] // S, (X, weights))):
             from ._ext import ext                      # inference: the layer's launch sequence issued from C++ in one call
             return ext().hs_layer_forward(xyz, X, idx_f, idx_x, k, S, weights, bias, directions, w_ste, w_conv2)
-        return _HSLayer.apply(xyz, X, idx_f, idx_x, k, S, weights, bias, directions, w_ste, w_conv2)
-    return _HSLayer.apply(xyz, X, idx_f, idx_x, k, S, weights, bias, directions, w_ste, w_conv2, bn_shift)
+    return _HSLayer.apply(xyz, X, idx_f, idx_x, k, S, weights, bias, directions, w_ste, w_conv2, bn_shift,
+                          bool(out_f32) and X.dtype == torch.bfloat16)
 
 
-def surface_layer(xyz, idx_x, k, S, directions, w_ste, w_conv2, relu=False):
-    """HSlayer_surface.forward (gcn3d.py:79-90) given the xyz neighbour index (exactly k columns).  ``relu``: apply the relu
-    that follows the layer (FaceRecon.py:88) inside the node and return the result TWICE (one tensor per consumer)."""
-    if (_ext_inference() and _f32c(xyz, directions, w_ste, w_conv2) and idx_x.dtype == torch.int32 and idx_x.is_contiguous()
-            and idx_x.shape[2] == k and _exact_layer_ok(xyz.shape[1], 3, directions.shape[1] // S, (w_conv2.squeeze(-1),))):
+def surface_layer(xyz, idx_x, k, S, directions, w_ste, w_conv2, relu=False, out_dtype=torch.float32):
+    """HSlayer_surface.forward (gcn3d.py:79-90) given the xyz neighbour index (exactly k columns), in fp32 or (``out_dtype``) bf16
+    rows.  ``relu`` (fp32 rows): apply the relu that follows the layer (FaceRecon.py:88) inside the node and return the result
+    TWICE (one tensor per consumer)."""
+    relu = relu and out_dtype == torch.float32
+    if (out_dtype == torch.float32 and _ext_inference() and _f32c(xyz, directions, w_ste, w_conv2) and idx_x.dtype == torch.int32
+            and idx_x.is_contiguous() and idx_x.shape[2] == k
+            and _exact_layer_ok(xyz.shape[1], 3, directions.shape[1] // S, (w_conv2.squeeze(-1),))):
         from ._ext import ext
         y = ext().surface_layer_forward(xyz, idx_x, k, S, directions, w_ste, w_conv2, relu)
         return (y, y.view_as(y)) if relu else y
-    return _SurfaceLayer.apply(xyz, idx_x, k, S, directions, w_ste, w_conv2, relu)
+    return _SurfaceLayer.apply(xyz, idx_x, k, S, directions, w_ste, w_conv2, relu, out_dtype)
 
 
 class _LinearRows(torch.autograd.Function):

@@ -65,14 +65,14 @@ def test_knn_bf16_vs_fp32_on_same_rows(dev, ref, B, N, C, k):
 
 @pytest.mark.parametrize("B,N,k,S,C", [(2, 257, 20, 7, 256), (2, 1028, 20, 7, 128), (1, 4096, 20, 7, 128), (2, 64, 8, 3, 32)])
 def test_rf_conv_bf16_equals_rounded_fp32_twin(dev, ref, B, N, k, S, C):
-    from hs_pose_amd import ops, ops_bf16
+    from hs_pose_amd import ops
     from hs_pose_amd._lib import lib
     xyz = _h(ref, (B, N, 3), 21, 0.05).to(dev)
     dirs = _h(ref, (3, S * C), 22, 0.3).to(dev)
     fm = _h(ref, (B, N, (S + 1) * C), 23, 1.0).to(dev).bfloat16()
     feat = torch.relu(_h(ref, (B, N, 64), 24, 1.0)).to(dev)
     idx = ops.knn(feat, k)
-    out_b, arg_b, fwin_b = ops_bf16._rf_conv_fwd(xyz, idx, dirs, fm, S, True)
+    out_b, arg_b, fwin_b = ops._rf_conv_fwd_raw(xyz, idx, dirs, fm, S, True)
     out_f, arg_f, fwin_f = ops._rf_conv_fwd_raw(xyz, idx, dirs, fm.float(), S, True)
     assert torch.equal(arg_b, arg_f)
     assert torch.equal(out_b, out_f.bfloat16())
@@ -81,7 +81,7 @@ def test_rf_conv_bf16_equals_rounded_fp32_twin(dev, ref, B, N, k, S, C):
     g = _h(ref, (B, N, C), 25, 1.0).to(dev).bfloat16()
     saved_b = fwin_b if fwin_b is not None else fm
     saved_f = fwin_f if fwin_f is not None else fm.float()
-    gfm_b, gd_b = ops_bf16._rf_conv_bwd(xyz, dirs, saved_b, arg_b, g, S)
+    gfm_b, gd_b = ops._rf_conv_bwd_raw(xyz, idx, dirs, saved_b, arg_b, g, S)
     gfm_f, gd_f = ops._rf_conv_bwd_raw(xyz, idx, dirs, saved_f, arg_f, g.float(), S)
     scale = gfm_f.abs().max().item()
     err = (gfm_b.float() - gfm_f).abs()
@@ -90,7 +90,7 @@ def test_rf_conv_bf16_equals_rounded_fp32_twin(dev, ref, B, N, k, S, C):
 
 
 def test_surface_gather_orl_bn_concat_bf16_twins(dev, ref):
-    from hs_pose_amd import ops, ops_bf16
+    from hs_pose_amd import ops
     B, N, k, S, C = 2, 1028, 20, 7, 128
     xyz = _h(ref, (B, N, 3), 31, 0.05).to(dev)
     idx = ops.knn(xyz, k)
@@ -104,10 +104,10 @@ def test_surface_gather_orl_bn_concat_bf16_twins(dev, ref):
     pb.backward(g); pf.backward(g.float())
     assert ((f.grad.float() - ff.grad).abs() <= ff.grad.abs() * 2.0 ** -8 + 1e-5).all()
     # ORL global feature: fp32 (B,C) out, identical to the twin
-    fg_b, arg_b = ops_bf16._orl_fwd(f.detach(), idx, k)
+    fg_b, arg_b = ops._orl_fwd_raw(f.detach(), idx, k)
     fg_f, arg_f = ops._orl_fwd_raw(ff.detach(), idx, k)
     assert torch.equal(arg_b, arg_f) and torch.equal(fg_b, fg_f)
-    assert torch.equal(ops_bf16._colsum(f.detach()), ops.colsum_rows(ff.detach()))
+    assert torch.equal(ops.colsum_rows(f.detach()), ops.colsum_rows(ff.detach()))
     # fused train-mode BatchNorm + ReLU: statistics in fp32 from the same values in the same order
     bn_b, bn_f = torch.nn.BatchNorm1d(C).to(dev), torch.nn.BatchNorm1d(C).to(dev)
     with torch.no_grad():
@@ -160,10 +160,10 @@ def test_wgrad_bf16(dev, ref, K, M, N, colsum, pitch):
     """A^T B (+ column sums of B) of bf16 point rows: exact bf16 x bf16 products accumulated in fp32 -- on the bf16 matrix cores
     when M, N are multiples of 128 (8 x 8 register transposes into the LDS operand image), else by widening onto the fp32
     ones.  Against float64, within fp32 accumulation error of the summed magnitudes; `pitch`: rows are slices of wider tensors."""
-    from hs_pose_amd import ops_bf16
+    from hs_pose_amd import ops
     A = _h(ref, (K, M + pitch), 51, 1.0).to(dev).bfloat16()[:, :M]
     Bm = _h(ref, (K, N + pitch), 52, 1.0).to(dev).bfloat16()[:, pitch:]
-    out = ops_bf16._wgrad(A, Bm, colsum=colsum)
+    out = ops.wgrad(A, Bm, colsum=colsum)
     gw, cs = out if colsum else (out, None)
     want = A.double().t() @ Bm.double()
     mag = A.double().abs().t() @ Bm.double().abs()
@@ -171,7 +171,7 @@ def test_wgrad_bf16(dev, ref, K, M, N, colsum, pitch):
     if colsum:
         wc, mc = Bm.double().sum(0), Bm.double().abs().sum(0)
         assert ((cs.double() - wc).abs() <= 1e-6 * mc + 1e-6).all()
-    again = ops_bf16._wgrad(A, Bm, colsum=colsum)
+    again = ops.wgrad(A, Bm, colsum=colsum)
     assert torch.equal(gw, again[0] if colsum else again)          # fixed summation order
 
 
@@ -261,7 +261,7 @@ def test_hs_layer_bf16_vs_cpu_oracle(dev, ref, flags, lname, N, Cin, k):
     """every HS layer of the stack at the cloud sizes of BASELINE configs[3] (N = 4096 -> 1024 -> 256) against the fp32 CPU
     ORACLE (oracle/ref_cpu.py) evaluated on the bf16-rounded input and weights, with the oracle's own neighbour list:
     forward 1e-2 of scale (the layer rounds fm, F and out to bf16)."""
-    from hs_pose_amd import gcn3d, ops, ops_bf16
+    from hs_pose_amd import gcn3d, ops
     from hs_pose_amd.FaceRecon import FaceRecon
     flags.train = 0
     torch.manual_seed(0)
@@ -277,7 +277,7 @@ def test_hs_layer_bf16_vs_cpu_oracle(dev, ref, flags, lname, N, Cin, k):
     idx_f = ref.knn_index(X.float(), k).to(torch.int32).to(dev)
     net._bf16.refresh()
     with gcn3d.knn_scope():
-        got = ops_bf16.hs_layer(
+        got = ops.hs_layer(
             xyz.to(dev), X.to(dev), idx_f, ops.knn(xyz.to(dev), k), k, 7, layer.weights, layer.bias, layer.directions,
             layer.STE_layer.weight, layer.conv2.weight)
     err = (got.float().cpu() - want).abs().max().item() / want.abs().max().item()

@@ -161,7 +161,7 @@ def test_orl_global_slab_form(dev, dtype, B, N, C, k):
     whose slab is past the 144 KB limit, keep the chunked form; 128 is the smallest cloud that takes it, B = 9 the plain tile -> XCD map):
     the winning slot is torch.max's (first maximum) for every (point, channel), the mean agrees to fp32 summation-order error.
     Duplicated rows make equal maxima common (the tiled-cloud case)."""
-    from hs_pose_amd import ops, ops_bf16
+    from hs_pose_amd import ops
     g = torch.Generator().manual_seed(N + C)
     xyz = (torch.randn(B, N, 3, generator=g) * 0.05).to(dev)
     feat = torch.randn(B, N, C, generator=g)
@@ -170,7 +170,7 @@ def test_orl_global_slab_form(dev, dtype, B, N, C, k):
     idx = ops.knn(xyz, k)
     if dtype == "bf16":
         fb = feat.bfloat16()
-        fg, arg = ops_bf16._orl_fwd(fb, idx, k)
+        fg, arg = ops._orl_fwd_raw(fb, idx, k)
         vals = fb.float()
     else:
         fg, arg = ops._orl_fwd_raw(feat, idx, k)

@@ -4,7 +4,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "oracle")]
 import torch
 import ref_cpu as oc
-from hs_pose_amd import ops, ops_bf16, gcn3d
+from hs_pose_amd import ops, gcn3d
 from hs_pose_amd.config import FLAGS
 from hs_pose_amd.FaceRecon import FaceRecon
 dev = torch.device("cuda:0")
@@ -24,18 +24,18 @@ def rel(a, b):
 
 c0 = net.conv_0
 of = ops.surface_layer(xyz, idx_x, k, S, c0.directions, c0.STE_layer.weight, c0.conv2.weight)
-ob = ops_bf16.surface_layer(xyz, idx_x, k, S, c0.directions, c0.STE_layer.weight, c0.conv2.weight)
+ob = ops.surface_layer(xyz, idx_x, k, S, c0.directions, c0.STE_layer.weight, c0.conv2.weight, out_dtype=torch.bfloat16)
 print("conv_0 out:", rel(ob, of), " |out| rms", of.pow(2).mean().sqrt().item(), "max", of.abs().max().item())
 X = torch.relu(of)
 for name, Xin in (("conv_1 (same bf16-rounded input)", X.bfloat16()),):
     l = net.conv_1
     idx_f = ops.knn(Xin.float(), k)
     of1 = ops.hs_layer(xyz, Xin.float(), idx_f, idx_x, k, S, l.weights, l.bias, l.directions, l.STE_layer.weight, l.conv2.weight)
-    ob1 = ops_bf16.hs_layer(xyz, Xin, idx_f, idx_x, k, S, l.weights, l.bias, l.directions, l.STE_layer.weight, l.conv2.weight)
+    ob1 = ops.hs_layer(xyz, Xin, idx_f, idx_x, k, S, l.weights, l.bias, l.directions, l.STE_layer.weight, l.conv2.weight)
     print(name, "out:", rel(ob1, of1), " |out| rms", of1.pow(2).mean().sqrt().item(), "max", of1.abs().max().item())
     # pieces
     X2 = Xin.view(B * N, -1)
-    W_b, WT_b = ops_bf16.copies_of(l.weights)
+    W_b, WT_b = ops.copies_of(l.weights)
     fm_b = ops.gemm_rows(X2, WT_b, bias=l.bias)
     fm_f = torch.addmm(l.bias, X2.float(), l.weights)
     print("   fm:", rel(fm_b, fm_f))

@@ -5,7 +5,7 @@ import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch
-from hs_pose_amd import ops, ops_bf16
+from hs_pose_amd import ops
 from hs_pose_amd._lib import lib
 from hs_pose_amd.ops import _p, _run, _stream
 

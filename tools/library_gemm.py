@@ -21,15 +21,18 @@ def enable(monkeypatch=None, tune=False):
     def fm_rows(X2, weights, bias, out=None):
         return torch.addmm(bias, X2, weights) if out is None else torch.addmm(bias, X2, weights, out=out)
 
-    def layer_out_rows_plain(x2, w_ste, F2, Wa, t2, out3, relu=False):
+    def layer_out_rows_plain(x2, w_ste, F2, w_conv2, t2, out3, relu=False):
         B, N, C = out3.shape
         out = out3.view(B * N, C)
+        Wa = w_conv2[:, :C]
         torch.mm(x2, w_ste.t(), out=out)
         out.addmm_(F2, Wa.t())
         ops._residual_bias(out3, F2.view(B, N, C), t2)
         return torch.relu_(out3) if relu else out3
 
-    def mm_nn(g2, W, out=None, alpha=1.0):
+    def mm_nn(g2, W, out=None, alpha=1.0, cols=None):
+        if cols is not None:
+            W = W[:, cols]
         if out is None:
             out = torch.empty(g2.shape[0], W.shape[1], dtype=g2.dtype, device=g2.device)
         if alpha == 1.0:
