@@ -27,6 +27,7 @@ SIGNATURES = {
     "hsp_rf_bwd_scatter_workspace_bytes": (_sz, [_i, _i]),
     "hsp_rf_conv_bwd_scatter": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "hsp_rev_build": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "hsp_rev_build_multi": (_i, [_i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "hsp_gather_max_bwd_csr": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "hsp_gather_max_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "hsp_pool_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
@@ -57,6 +58,8 @@ SIGNATURES = {
     "hsp_gather_rows_fwd": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp]),
     "hsp_gather_rows_bwd": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "hsp_gather_rows_bwd_csr": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "hsp_gather_rows_bwd_csr_multi": (_i, [_i, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp]),
+    "hsp_gather_rows_bwd_csr_multi_bf16": (_i, [_i, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp]),
     "hsp_gemm_rows_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "hsp_gemm_rows_f32": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _i, ctypes.c_float, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
     "hsp_gemm_rows_bf16": (_i, [_vp, _i, _vp, _i, _i, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _i, ctypes.c_float, _vp, _vp, _vp, _i, _i, _vp, _sz, _vp]),
@@ -149,6 +152,7 @@ SIGNATURES = {
     "hsp_rf_surface_bwd_partial_bf16": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _sz, _vp, _vp]),
     "hsp_rf_conv_bwd_scatter_partial_bf16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp, _vp]),
     "hsp_wgrad_partial_pair_f32": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp, _sz] * 2 + [_vp, _vp]),
+    "hsp_wgrad_partial_pair_colsum_f32": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp, _sz] * 2 + [_vp, _vp, _i, _i, _i, _vp, _vp]),
     "hsp_pose_augment": (_i, [_vp] * 14 + [_i, _i, _i] + [ctypes.c_float] * 4 + [_vp] * 5),
 }
 

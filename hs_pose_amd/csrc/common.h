@@ -38,6 +38,9 @@ int knn_feat_select_flags(const float* x, int B, int N, int C, int k, int drop, 
 int knn3_select_flags(const float* x, int B, int N, int k, int drop, int k2, int32_t* idx, int32_t* idx2, uint8_t* tie,
                       hipStream_t st, bool* needs_tie_pass);
 
+// gather.hip -> gemm.hip: 1 where hsp_colsum_cloud_f32(x, NULL, B, N, C) takes the shape, with its rows per chunk and chunk count
+int colsum_cloud_plan(int B, int N, int C, int* rows, int* nchunk);
+
 // persistent grid: a multiple of the XCD count so that block % 8 == XCD for every block
 inline int persistent_blocks(long long work_items, int blocks_per_cu) {
     long long g = (long long)HSP_NUM_CU * blocks_per_cu;

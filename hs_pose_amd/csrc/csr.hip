@@ -22,14 +22,13 @@ namespace hsp {
 // EDGES_IN_LDS: the edge array is assembled and sorted in LDS and written out once, coalesced (the per-row
 // insertion sort is a chain of dependent accesses: ~100 cycles a step in LDS, 1-2 us a step in global memory)
 template <bool EDGES_IN_LDS>
-__global__ __launch_bounds__(REV_THREADS) void rev_build_kernel(const int32_t* __restrict__ idx, int Nq, int Nsrc,
-                                                                int k, int kstride, int32_t* __restrict__ rev_off,
-                                                                int32_t* __restrict__ rev_edge) {
+__device__ __forceinline__ void rev_build_body(const int b, const int32_t* __restrict__ idx, int Nq, int Nsrc,
+                                               int k, int kstride, int32_t* __restrict__ rev_off,
+                                               int32_t* __restrict__ rev_edge, int* __restrict__ wsum) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     int* cnt = reinterpret_cast<int*>(smem);            // Nsrc + 1 (histogram, then cursor)
     int* led = cnt + Nsrc + 1;                          // E edges (EDGES_IN_LDS)
-    __shared__ int wsum[REV_THREADS / 64];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int32_t* ib = idx + (size_t)b * Nq * kstride;
     int32_t* off = rev_off + (size_t)b * (Nsrc + 1);
     int32_t* edge = rev_edge + (size_t)b * Nq * k;
@@ -118,6 +117,25 @@ __global__ __launch_bounds__(REV_THREADS) void rev_build_kernel(const int32_t* _
     }
 }
 
+template <bool EDGES_IN_LDS>
+__global__ __launch_bounds__(REV_THREADS) void rev_build_kernel(const int32_t* __restrict__ idx, int Nq, int Nsrc,
+                                                                int k, int kstride, int32_t* __restrict__ rev_off,
+                                                                int32_t* __restrict__ rev_edge) {
+    __shared__ int wsum[REV_THREADS / 64];
+    rev_build_body<EDGES_IN_LDS>((int)blockIdx.x, idx, Nq, Nsrc, k, kstride, rev_off, rev_edge, wsum);
+}
+
+// up to 4 maps over the same B clouds in ONE launch: workgroup (b, map) runs rev_build_body on its own map (independent
+// 6 us launches of B workgroups each otherwise)
+struct RevBuildMap { const int32_t* idx; int32_t* rev_off; int32_t* rev_edge; int Nq, Nsrc, k, kstride, in_lds; };
+struct RevBuildTab { RevBuildMap m[4]; };
+__global__ __launch_bounds__(REV_THREADS) void rev_build_multi_kernel(const RevBuildTab tab) {
+    __shared__ int wsum[REV_THREADS / 64];
+    const RevBuildMap m = tab.m[blockIdx.y];                // workgroup-uniform
+    if (m.in_lds) rev_build_body<true>((int)blockIdx.x, m.idx, m.Nq, m.Nsrc, m.k, m.kstride, m.rev_off, m.rev_edge, wsum);
+    else rev_build_body<false>((int)blockIdx.x, m.idx, m.Nq, m.Nsrc, m.k, m.kstride, m.rev_off, m.rev_edge, wsum);
+}
+
 }  // namespace hsp
 
 using namespace hsp;
@@ -137,5 +155,29 @@ extern "C" int hsp_rev_build(const int32_t* idx, int B, int Nq, int Nsrc, int k,
     }
     hipLaunchKernelGGL(kern, dim3(B), dim3(REV_THREADS), lds, as_stream(stream), idx, Nq, Nsrc, k, kstride, rev_off,
                        rev_edge);
+    return check_launch();
+}
+
+extern "C" int hsp_rev_build_multi(int nmaps, const int32_t* const* idx, int B, const int* Nq, const int* Nsrc, const int* k,
+                                   const int* kstride, int32_t* const* rev_off, int32_t* const* rev_edge, hspStream_t stream) {
+    if (nmaps <= 0 || nmaps > 4 || !idx || !Nq || !Nsrc || !k || !kstride || !rev_off || !rev_edge || B <= 0 || B > 65535)
+        return HSP_ERR_BAD_ARG;
+    RevBuildTab tab;
+    size_t lds = 0;
+    for (int i = 0; i < nmaps; ++i) {
+        if (!idx[i] || !rev_off[i] || !rev_edge[i] || Nq[i] <= 0 || Nsrc[i] <= 0 || k[i] <= 0 || kstride[i] < k[i]) return HSP_ERR_BAD_ARG;
+        const size_t lds0 = (size_t)(Nsrc[i] + 1) * sizeof(int);
+        if (lds0 > 140 * 1024) return HSP_ERR_UNSUPPORTED;
+        const size_t lds1 = lds0 + (size_t)Nq[i] * k[i] * sizeof(int);
+        const bool in_lds = lds1 <= 140 * 1024;
+        lds = lds > (in_lds ? lds1 : lds0) ? lds : (in_lds ? lds1 : lds0);
+        tab.m[i] = RevBuildMap{idx[i], rev_off[i], rev_edge[i], Nq[i], Nsrc[i], k[i], kstride[i], in_lds ? 1 : 0};
+    }
+    if (lds > 60 * 1024) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(rev_build_multi_kernel),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) { set_last_hip_error(e); return HSP_ERR_LAUNCH; }
+    }
+    hipLaunchKernelGGL(rev_build_multi_kernel, dim3(B, nmaps), dim3(REV_THREADS), lds, as_stream(stream), tab);
     return check_launch();
 }

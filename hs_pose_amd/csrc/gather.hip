@@ -8,6 +8,7 @@
 //             the concatenated feature tensor (FaceRecon.py:107).
 // All are pure HBM/L2 streaming kernels: one lane per float4 of a row, 16-byte accesses.
 #include "common.h"
+#include "colsum_cloud.h"
 #include <type_traits>
 
 namespace hsp {
@@ -261,20 +262,6 @@ __global__ __launch_bounds__(ORLT_WG) void orl_tile_kernel(const FT* __restrict_
     ORL_STAMP(31);
 }
 
-// sum over the chunks of p[chunk * stride]: THE order of every per-cloud column sum's second stage (chunk_fold_kernel, and
-// colsum_cloud_kernel, which folds its own chunks out of LDS) -- eight running sums over chunk, combined pairwise.
-// 8 independent partial sums: 8 loads in flight per round trip (the fold is a latency chain, not bandwidth)
-__device__ __forceinline__ float chunk_fold8(const float* __restrict__ p, int nchunk, int stride) {
-    float s[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    int ch = 0;
-    for (; ch + 7 < nchunk; ch += 8) {
-#pragma unroll
-        for (int u = 0; u < 8; ++u) s[u] += p[(size_t)(ch + u) * stride];
-    }
-    for (; ch < nchunk; ++ch) s[ch & 7] += p[(size_t)ch * stride];
-    return ((s[0] + s[1]) + (s[2] + s[3])) + ((s[4] + s[5]) + (s[6] + s[7]));
-}
-
 // out[b][c] = scale * sum_chunk part[b][chunk][c]   (also the generic "column sum per cloud" second stage)
 __global__ __launch_bounds__(256) void chunk_fold_kernel(const float* __restrict__ part, int B, int nchunk, int C,
                                                          float scale, float* __restrict__ out) {
@@ -305,12 +292,6 @@ __global__ __launch_bounds__(256) void colsum_partial_kernel(const FT* __restric
         for (int l = 1; l < RL; ++l) { const float4 v = red[l * cq + g]; s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w; }
         *reinterpret_cast<float4*>(part + ((size_t)b * nchunk + chunk) * C + (g << 2)) = s;
     }
-}
-
-__device__ __forceinline__ float fma_plain(float a, float b, float c) {
-    float r;
-    asm volatile("v_fma_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-    return r;
 }
 
 // colsum + the three coordinate moments of the rows in one pass (HSlayer_surface backward: gt = sum_i g and the STE weight
@@ -355,61 +336,13 @@ __global__ __launch_bounds__(256) void colsum_xyz_partial_kernel(const FT* __res
     }
 }
 
-// Both stages of the per-cloud column sum (XYZ: and of its three coordinate moments) in ONE launch, with the bits of the
-// two-launch form: a workgroup of 1024 threads owns (cloud, C/8 columns) and walks the SAME chunks in rounds of 32.  A chunk is
-// 32 threads = the RL = 256 / (C/4) row lanes x the tile's C/32 float4 columns, so every thread does exactly the work of one
-// thread of colsum_partial_kernel / colsum_xyz_partial_kernel (the same rows, in the same order, the same row-lane fold through
-// LDS); the chunk sums stay in LDS and chunk_fold8 sums them in chunk_fold_kernel's order.  No partial workspace, no second
-// dependent launch (a fold is a 4-5 us launch for a fraction of a microsecond of adds).
-// grid (8, B), dynamic LDS = (1024 + (XYZ ? 4 : 1) * nchunk * C/32) float4
+// both stages of the per-cloud column sum in ONE launch (colsum_cloud.h): grid (8, B), 1024 threads, one round of 32 chunks at
+// a time; dynamic LDS = (1024 + (XYZ ? 4 : 1) * nchunk * C/32) float4
 template <bool XYZ>
 __global__ __launch_bounds__(1024) void colsum_cloud_kernel(const float* __restrict__ x, const float* __restrict__ xyz, int N, int C,
                                                             int nchunk, int rows, float* __restrict__ out) {
     extern __shared__ float4 cc_smem[];
-    constexpr int NS = XYZ ? 4 : 1;
-    const int cq = C >> 2, RL = 256 / cq, G = cq >> 3;
-    const int tid = threadIdx.x;
-    const int gl = tid % G, rl = (tid / G) % RL, cs = tid / (G * RL);      // tid = (cs * RL + rl) * G + gl
-    const int g = blockIdx.x * G + gl, b = blockIdx.y;
-    float4* red = cc_smem;                                                 // [1024]
-    float4* cp = cc_smem + 1024;                                           // [NS][nchunk][G]
-    for (int c0 = 0; c0 < nchunk; c0 += 32) {
-        const int chunk = c0 + cs;
-        const int r0 = chunk * rows, r1 = chunk < nchunk ? min(N, r0 + rows) : 0;
-        float4 s[NS];
-#pragma unroll
-        for (int q = 0; q < NS; ++q) s[q] = make_float4(0.f, 0.f, 0.f, 0.f);
-        for (int i = r0 + rl; i < r1; i += RL) {
-            const float4 v = *reinterpret_cast<const float4*>(x + ((size_t)b * N + i) * C + (g << 2));
-            s[0].x += v.x; s[0].y += v.y; s[0].z += v.z; s[0].w += v.w;
-            if constexpr (XYZ) {
-                const float* p3 = xyz + ((size_t)b * N + i) * 3;
-                const float w[3] = {p3[0], p3[1], p3[2]};
-#pragma unroll
-                for (int q = 0; q < 3; ++q) {                  // (plain v_fma_f32 spelled out: see colsum_xyz_partial_kernel)
-                    s[q + 1].x = fma_plain(v.x, w[q], s[q + 1].x); s[q + 1].y = fma_plain(v.y, w[q], s[q + 1].y);
-                    s[q + 1].z = fma_plain(v.z, w[q], s[q + 1].z); s[q + 1].w = fma_plain(v.w, w[q], s[q + 1].w);
-                }
-            }
-        }
-#pragma unroll
-        for (int q = 0; q < NS; ++q) {
-            red[tid] = s[q];
-            __syncthreads();
-            if (rl == 0 && chunk < nchunk) {
-                float4 a = s[q];
-                for (int l = 1; l < RL; ++l) { const float4 v = red[(cs * RL + l) * G + gl]; a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w; }
-                cp[((size_t)q * nchunk + chunk) * G + gl] = a;
-            }
-            __syncthreads();                                   // red is reused by the next slot / round; cp complete after the last
-        }
-    }
-    const int TC = G << 2;
-    if (tid < NS * TC) {
-        const int q = tid / TC, c = tid - q * TC;
-        out[(size_t)b * NS * C + (size_t)q * C + blockIdx.x * TC + c] =
-            chunk_fold8(reinterpret_cast<const float*>(cp) + (size_t)q * nchunk * TC + c, nchunk, TC);
-    }
+    colsum_cloud_body<XYZ, 1024, 1>(cc_smem, (int)blockIdx.x, (int)blockIdx.y, x, xyz, N, C, nchunk, rows, out);
 }
 
 // the same first stage for widths the float4 form does not take (C not a multiple of 4, or C/4 not dividing 256;
@@ -1041,44 +974,126 @@ extern "C" int hsp_gather_rows_bwd(const float* grad_out, int grad_stride, const
 // SOURCE row m and sums the gradient rows of the queries that selected it, in ascending query order (no atomics,
 // bit-reproducible), reading every gradient row segment whole.  The column-tile scatter form reads a 64-byte
 // slice of every 5 KB gradient row per tile: 30-45 us where this takes under 10.
-template <typename FT>
-__global__ __launch_bounds__(256) void gather_rows_bwd_csr_kernel(const FT* __restrict__ gout, int gstride,
-                                                                  const int32_t* __restrict__ rev_off,
-                                                                  const int32_t* __restrict__ rev_edge, int B,
-                                                                  int Nsrc, int Nq, int C,
-                                                                  FT* __restrict__ gfeat) {
-    const int pairs = C >> 1;                               // float2 columns (gradient rows are 8-byte aligned)
-    const int tpr = pairs < 256 ? pairs : 256;              // threads per row
+// VEC consecutive elements of a gradient row, widened to fp32 (VEC = 2: 8 / 4 bytes, VEC = 4: 16 / 8 bytes per access)
+template <typename FT, int VEC>
+__device__ __forceinline__ void grow_ld(const FT* __restrict__ p, float (&v)[VEC]) {
+    if constexpr (sizeof(FT) == 4 && VEC == 2) {
+        const float2 t = *reinterpret_cast<const float2*>(p);
+        v[0] = t.x; v[1] = t.y;
+    } else if constexpr (sizeof(FT) == 4) {
+        const float4 t = *reinterpret_cast<const float4*>(p);
+        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+    } else if constexpr (VEC == 2) {
+        const unsigned w = *reinterpret_cast<const unsigned*>(p);
+        v[0] = __uint_as_float(w << 16); v[1] = __uint_as_float(w & 0xffff0000u);
+    } else {
+        const uint2 w = *reinterpret_cast<const uint2*>(p);
+        v[0] = __uint_as_float(w.x << 16); v[1] = __uint_as_float(w.x & 0xffff0000u);
+        v[2] = __uint_as_float(w.y << 16); v[3] = __uint_as_float(w.y & 0xffff0000u);
+    }
+}
+template <typename FT, int VEC>
+__device__ __forceinline__ void grow_st(FT* __restrict__ p, const float (&v)[VEC]) {
+    if constexpr (sizeof(FT) == 4 && VEC == 2) {
+        *reinterpret_cast<float2*>(p) = make_float2(v[0], v[1]);
+    } else if constexpr (sizeof(FT) == 4) {
+        *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
+    } else if constexpr (VEC == 2) {
+        *reinterpret_cast<unsigned*>(p) = f32_to_bf16_bits(v[0]) | (f32_to_bf16_bits(v[1]) << 16);
+    } else {
+        *reinterpret_cast<uint2*>(p) = make_uint2(f32_to_bf16_bits(v[0]) | (f32_to_bf16_bits(v[1]) << 16),
+                                                  f32_to_bf16_bits(v[2]) | (f32_to_bf16_bits(v[3]) << 16));
+    }
+}
+
+// the work of workgroup ``bid``: 256 / tpr source rows, a thread owns VEC columns of one of them (tpr = min(C / VEC, 256)
+// threads per row).  A list is walked 8 edges at a time while 8 remain, then 4 at a time (the last group padded with its own
+// last edge, loaded and not added); every column is acc = 0; acc += v in edge order whatever the grouping.
+template <typename FT, int VEC>
+__device__ __forceinline__ void gather_rows_bwd_csr_body(const int bid, const FT* __restrict__ gout, int gstride,
+                                                         const int32_t* __restrict__ rev_off,
+                                                         const int32_t* __restrict__ rev_edge, int B, int Nsrc, int Nq, int C,
+                                                         FT* __restrict__ gfeat) {
+    const int cols = C / VEC;                               // VEC-element columns (gradient rows are aligned for them)
+    const int tpr = cols < 256 ? cols : 256;                // threads per row
     const int RB = 256 / tpr;
     const int rl = threadIdx.x / tpr, t = threadIdx.x - rl * tpr;
-    const long long row = (long long)blockIdx.x * RB + rl;  // b*Nsrc + m
+    const long long row = (long long)bid * RB + rl;         // b*Nsrc + m
     if (rl >= RB || row >= (long long)B * Nsrc) return;
     const int m = (int)(row % Nsrc), b = (int)(row / Nsrc);
     const int32_t* off = rev_off + (size_t)b * (Nsrc + 1);
     const int32_t* edge = rev_edge + (size_t)b * Nq;
     const int o0 = off[m], o1 = off[m + 1];
     const FT* gb = gout + (size_t)b * Nq * gstride;
-    for (int p = t; p < pairs; p += tpr) {
-        float2 acc = make_float2(0.f, 0.f);
-        for (int e = o0; e < o1; e += 4) {                  // 4 rows in flight, added in edge order
-            float2 v[4];
+    for (int p = t; p < cols; p += tpr) {
+        float acc[VEC];
 #pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int q = edge[min(e + u, o1 - 1)];
-                if constexpr (sizeof(FT) == 4) {
-                    v[u] = *reinterpret_cast<const float2*>(gb + (size_t)q * gstride + 2 * p);
-                } else {
-                    const unsigned w = *reinterpret_cast<const unsigned*>(gb + (size_t)q * gstride + 2 * p);
-                    v[u] = make_float2(__uint_as_float(w << 16), __uint_as_float(w & 0xffff0000u));
-                }
-            }
+        for (int c = 0; c < VEC; ++c) acc[c] = 0.f;
+        int e = o0;
+        for (; e + 8 <= o1; e += 8) {                       // 8 rows in flight, added in edge order
+            float v[8][VEC];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) grow_ld<FT, VEC>(gb + (size_t)edge[e + u] * gstride + VEC * p, v[u]);
+#pragma unroll
+            for (int u = 0; u < 8; ++u)
+#pragma unroll
+                for (int c = 0; c < VEC; ++c) acc[c] += v[u][c];
+        }
+        for (; e < o1; e += 4) {                            // 4 rows in flight
+            float v[4][VEC];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) grow_ld<FT, VEC>(gb + (size_t)edge[min(e + u, o1 - 1)] * gstride + VEC * p, v[u]);
 #pragma unroll
             for (int u = 0; u < 4; ++u)
-                if (e + u < o1) { acc.x += v[u].x; acc.y += v[u].y; }
+                if (e + u < o1) {
+#pragma unroll
+                    for (int c = 0; c < VEC; ++c) acc[c] += v[u][c];
+                }
         }
-        if constexpr (sizeof(FT) == 4) *reinterpret_cast<float2*>(gfeat + (size_t)row * C + 2 * p) = acc;
-        else *reinterpret_cast<unsigned*>(gfeat + (size_t)row * C + 2 * p) = f32_to_bf16_bits(acc.x) | (f32_to_bf16_bits(acc.y) << 16);
+        grow_st<FT, VEC>(gfeat + (size_t)row * C + VEC * p, acc);
     }
+}
+
+template <typename FT>
+__global__ __launch_bounds__(256) void gather_rows_bwd_csr_kernel(const FT* __restrict__ gout, int gstride,
+                                                                  const int32_t* __restrict__ rev_off,
+                                                                  const int32_t* __restrict__ rev_edge, int B,
+                                                                  int Nsrc, int Nq, int C,
+                                                                  FT* __restrict__ gfeat) {
+    gather_rows_bwd_csr_body<FT, 2>((int)blockIdx.x, gout, gstride, rev_off, rev_edge, B, Nsrc, Nq, C, gfeat);
+}
+
+// up to 4 such gathers out of one gradient tensor (the gathered segments of the feat concat) in ONE launch: segment s owns
+// the workgroups [first[s], first[s + 1]); each runs gather_rows_bwd_csr_body on its own segment.  The launches were a
+// latency chain each (a handful of dependent loads per thread, 1.7 TB/s); in one grid their chains overlap.
+struct GatherBwdSeg {
+    const void* gout; const int32_t* rev_off; const int32_t* rev_edge; void* gfeat;
+    int gstride, nsrc, nq, width, vec;
+};
+struct GatherBwdDesc { GatherBwdSeg seg[4]; int first[5]; int nseg; };
+
+template <typename FT>
+__global__ __launch_bounds__(256) void gather_rows_bwd_csr_multi_kernel(const GatherBwdDesc d, int B) {
+    const int bid = (int)blockIdx.x;
+    int s = 0;
+    while (s + 1 < d.nseg && bid >= d.first[s + 1]) ++s;    // wave-uniform
+    const GatherBwdSeg sg = d.seg[s];
+    const FT* gout = reinterpret_cast<const FT*>(sg.gout);
+    FT* gfeat = reinterpret_cast<FT*>(sg.gfeat);
+    if (sg.vec == 4)
+        gather_rows_bwd_csr_body<FT, 4>(bid - d.first[s], gout, sg.gstride, sg.rev_off, sg.rev_edge, B, sg.nsrc, sg.nq, sg.width, gfeat);
+    else
+        gather_rows_bwd_csr_body<FT, 2>(bid - d.first[s], gout, sg.gstride, sg.rev_off, sg.rev_edge, B, sg.nsrc, sg.nq, sg.width, gfeat);
+}
+
+// widths / alignments gather_rows_bwd_csr_body<FT, VEC> takes: VEC-element columns, whole rows per workgroup
+template <typename FT>
+static bool gather_bwd_csr_vec_ok(int VEC, const FT* grad_out, int grad_stride, int C, const FT* grad_feat) {
+    if ((C % VEC) || (grad_stride % VEC)) return false;
+    const size_t al = (size_t)VEC * sizeof(FT) - 1;
+    if ((reinterpret_cast<uintptr_t>(grad_out) & al) || (VEC > 2 && (reinterpret_cast<uintptr_t>(grad_feat) & al))) return false;
+    const int cols = C / VEC;
+    return 256 % (cols < 256 ? cols : 256) == 0;
 }
 
 template <typename FT>
@@ -1087,8 +1102,7 @@ static int gather_rows_bwd_csr_impl(const FT* grad_out, int grad_stride, const i
                                     hspStream_t stream) {
     if (!grad_out || !rev_off || !rev_edge || !grad_feat || B <= 0 || Nsrc <= 0 || Nq <= 0 || C <= 0 || grad_stride < C)
         return HSP_ERR_BAD_ARG;
-    if ((C & 1) || (grad_stride & 1) || (reinterpret_cast<uintptr_t>(grad_out) & (2 * sizeof(FT) - 1)) ||
-        (256 % ((C >> 1) < 256 ? (C >> 1) : 256)))
+    if (!gather_bwd_csr_vec_ok<FT>(2, grad_out, grad_stride, C, grad_feat))
         return HSP_ERR_UNSUPPORTED;                         // two-element columns, whole rows per workgroup
     const int tpr = (C >> 1) < 256 ? (C >> 1) : 256;
     const int RB = 256 / tpr;
@@ -1096,6 +1110,50 @@ static int gather_rows_bwd_csr_impl(const FT* grad_out, int grad_stride, const i
     hipLaunchKernelGGL(gather_rows_bwd_csr_kernel<FT>, dim3((unsigned)((rows + RB - 1) / RB)), dim3(256), 0, as_stream(stream),
                        grad_out, grad_stride, rev_off, rev_edge, B, Nsrc, Nq, C, grad_feat);
     return check_launch();
+}
+
+template <typename FT>
+static int gather_rows_bwd_csr_multi_impl(int nseg, const FT* const* grad_out, int grad_stride, const int32_t* const* rev_off,
+                                          const int32_t* const* rev_edge, int B, const int* Nsrc, int Nq, const int* C,
+                                          FT* const* grad_feat, hspStream_t stream) {
+    if (nseg <= 0 || nseg > 4 || !grad_out || !rev_off || !rev_edge || !Nsrc || !C || !grad_feat || B <= 0 || Nq <= 0)
+        return HSP_ERR_BAD_ARG;
+    for (int s = 0; s < nseg; ++s)
+        if (!grad_out[s] || !rev_off[s] || !rev_edge[s] || !grad_feat[s] || Nsrc[s] <= 0 || C[s] <= 0 || grad_stride < C[s])
+            return HSP_ERR_BAD_ARG;
+    // longest lists (fewest source rows) first: their workgroups are the last to finish
+    int order[4] = {0, 1, 2, 3};
+    for (int i = 1; i < nseg; ++i)
+        for (int j = i; j > 0 && Nsrc[order[j]] < Nsrc[order[j - 1]]; --j) { const int t = order[j]; order[j] = order[j - 1]; order[j - 1] = t; }
+    GatherBwdDesc d;
+    d.nseg = nseg;
+    long long blocks = 0;
+    for (int i = 0; i < nseg; ++i) {
+        const int s = order[i];
+        if (!gather_bwd_csr_vec_ok<FT>(2, grad_out[s], grad_stride, C[s], grad_feat[s])) return HSP_ERR_UNSUPPORTED;
+        const int vec = gather_bwd_csr_vec_ok<FT>(4, grad_out[s], grad_stride, C[s], grad_feat[s]) ? 4 : 2;
+        const int cols = C[s] / vec;
+        const int RB = 256 / (cols < 256 ? cols : 256);
+        d.seg[i] = GatherBwdSeg{grad_out[s], rev_off[s], rev_edge[s], grad_feat[s], grad_stride, Nsrc[s], Nq, C[s], vec};
+        d.first[i] = (int)blocks;
+        blocks += ((long long)B * Nsrc[s] + RB - 1) / RB;
+        if (blocks > 0x7fffffffLL) return HSP_ERR_UNSUPPORTED;
+    }
+    d.first[nseg] = (int)blocks;
+    hipLaunchKernelGGL(gather_rows_bwd_csr_multi_kernel<FT>, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), d, B);
+    return check_launch();
+}
+extern "C" int hsp_gather_rows_bwd_csr_multi(int nseg, const float* const* grad_out, int grad_stride,
+                                             const int32_t* const* rev_off, const int32_t* const* rev_edge, int B,
+                                             const int* Nsrc, int Nq, const int* C, float* const* grad_feat, hspStream_t stream) {
+    return gather_rows_bwd_csr_multi_impl<float>(nseg, grad_out, grad_stride, rev_off, rev_edge, B, Nsrc, Nq, C, grad_feat, stream);
+}
+extern "C" int hsp_gather_rows_bwd_csr_multi_bf16(int nseg, const hsp_bf16_t* const* grad_out, int grad_stride,
+                                                  const int32_t* const* rev_off, const int32_t* const* rev_edge, int B,
+                                                  const int* Nsrc, int Nq, const int* C, hsp_bf16_t* const* grad_feat,
+                                                  hspStream_t stream) {
+    return gather_rows_bwd_csr_multi_impl<bf16_t>(nseg, reinterpret_cast<const bf16_t* const*>(grad_out), grad_stride, rev_off, rev_edge, B,
+                                                  Nsrc, Nq, C, reinterpret_cast<bf16_t* const*>(grad_feat), stream);
 }
 extern "C" int hsp_gather_rows_bwd_csr(const float* grad_out, int grad_stride, const int32_t* rev_off,
                                        const int32_t* rev_edge, int B, int Nsrc, int Nq, int C, float* grad_feat,
@@ -1250,6 +1308,15 @@ static size_t colsum_cloud_lds(int B, int N, int C, int with_xyz) {
     const int rows = chunk_rows(B, N, C);
     return (1024 + (size_t)(with_xyz ? 4 : 1) * ((N + rows - 1) / rows) * (C >> 5)) * sizeof(float4);
 }
+namespace hsp {
+// gemm.hip (the column sum as a rider of the weight-gradient pair launch): the chunking of hsp_colsum_cloud_f32(x, NULL, ...)
+int colsum_cloud_plan(int B, int N, int C, int* rows, int* nchunk) {
+    if (!hsp_colsum_cloud_ok(B, N, C, 0)) return 0;
+    *rows = chunk_rows(B, N, C);
+    *nchunk = (N + *rows - 1) / *rows;
+    return 1;
+}
+}  // namespace hsp
 extern "C" int hsp_colsum_cloud_ok(int B, int N, int C, int with_xyz) {
     if (B <= 0 || B > 65535 || N <= 0 || C <= 0 || (C & 31) || !colsum_vec4(C)) return 0;
     return colsum_cloud_lds(B, N, C, with_xyz) <= 64 * 1024 ? 1 : 0;

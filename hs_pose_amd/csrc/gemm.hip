@@ -19,6 +19,7 @@
 // arbitrary leading dimension (so a gradient can land in a column block of a larger tensor).
 #include "common.h"
 #include "folds.h"
+#include "colsum_cloud.h"
 
 namespace hsp {
 
@@ -179,8 +180,23 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const FT* __restrict__ A, in
 // two problems of the K-sliced form (KB = 4, no column sum) in ONE launch: workgroups [0, blocks0) work on problem 0, the
 // rest on problem 1.  An HS layer's backward has two such products that depend only on the incoming gradient -- g^T F (conv2's
 // first half) and g^T X (the STE weight) --, each too small to fill the chip on its own.
+// A third block range, [blocks01, gridDim.x), may ride along: the per-cloud column sum of g (B, N, C) -- the head of the same
+// backward's per-cloud chain, which depends on nothing the products write and was a launch of 128 workgroups on its own.  Rider
+// workgroup r owns cloud r / per_cloud and ``tpb`` of its 8 column tiles, one after the other (colsum_cloud_body, 256 threads,
+// four chunks at once), in the first few KB of the launch's LDS; the host sizes it into the resident slots the pair leaves free.
 struct WgradProb { const float* A; const float* B; float* part; int lda, ldb, M, N, K, SK, kslice; };
-__global__ __launch_bounds__(256) void wgrad_pair_kernel(const WgradProb p0, const WgradProb p1, int blocks0) {
+struct ColsumRider { const float* x; float* out; int N, C, nchunk, rows, tpb, per_cloud; };
+__global__ __launch_bounds__(256) void wgrad_pair_kernel(const WgradProb p0, const WgradProb p1, int blocks0, int blocks01,
+                                                         const ColsumRider r) {
+    if ((int)blockIdx.x >= blocks01) {                       // workgroup-uniform
+        extern __shared__ __attribute__((aligned(16))) char smem[];
+        const int rb = (int)blockIdx.x - blocks01;
+        const int b = rb / r.per_cloud, t0 = (rb - b * r.per_cloud) * r.tpb;
+        for (int t = 0; t < r.tpb; ++t)                      // (the body ends on a barrier or on reads of what the next tile's
+            colsum_cloud_body<false, 256, 4>(reinterpret_cast<float4*>(smem), t0 + t, b, r.x, nullptr, r.N, r.C, r.nchunk, r.rows,
+                                             r.out);         //  first barrier protects)
+        return;
+    }
     const bool second = (int)blockIdx.x >= blocks0;
     const WgradProb& p = second ? p1 : p0;
     wgrad_body<false, 4, float>((int)blockIdx.x - (second ? blocks0 : 0), p.A, p.lda, p.B, p.ldb, p.M, p.N, p.K, p.SK, p.kslice,
@@ -814,16 +830,18 @@ extern "C" int hsp_wgrad_partial_bf16(const hsp_bf16_t* A, int lda, const hsp_bf
     return wgrad_impl<bf16_t>(A, lda, B, ldb, M, N, K, C, ldc, colsum_B, ws, ws_bytes, stream, pending);
 }
 /* two weight gradients that share nothing but the launch: both K-sliced (few output tiles), no column sums; any other pair is
- * issued as two hsp_wgrad_partial_f32 launches */
-extern "C" int hsp_wgrad_partial_pair_f32(const float* A0, int lda0, const float* B0, int ldb0, int M0, int N0, int K0, float* C0,
-                                          int ldc0, void* ws0, size_t ws_bytes0, const float* A1, int lda1, const float* B1,
-                                          int ldb1, int M1, int N1, int K1, float* C1, int ldc1, void* ws1, size_t ws_bytes1,
-                                          HspWgradPending* pending, hspStream_t stream) {
+ * issued as two hsp_wgrad_partial_f32 launches.  cs_x != NULL: with the per-cloud column sum of cs_x (cs_B, cs_N, cs_C) -> cs_out
+ * as a rider of the pair launch, or HSP_ERR_UNSUPPORTED with nothing launched */
+static int wgrad_pair_impl(const float* A0, int lda0, const float* B0, int ldb0, int M0, int N0, int K0, float* C0, int ldc0, void* ws0,
+                           size_t ws_bytes0, const float* A1, int lda1, const float* B1, int ldb1, int M1, int N1, int K1, float* C1,
+                           int ldc1, void* ws1, size_t ws_bytes1, HspWgradPending* pending, const float* cs_x, int cs_B, int cs_N,
+                           int cs_C, float* cs_out, hspStream_t stream) {
     if (!pending) return HSP_ERR_BAD_ARG;
     int ks0, kb0, ks1, kb1;
     const bool shapes_ok = A0 && B0 && C0 && A1 && B1 && C1 && M0 > 0 && N0 > 0 && K0 > 0 && M1 > 0 && N1 > 0 && K1 > 0 &&
                            !((M0 | N0 | M1 | N1) & 63) && !((lda0 | ldb0 | lda1 | ldb1) & 1) && lda0 >= M0 && ldb0 >= N0 &&
                            lda1 >= M1 && ldb1 >= N1 && ldc0 >= N0 && ldc1 >= N1;
+    if (cs_x && !shapes_ok) return HSP_ERR_UNSUPPORTED;
     if (shapes_ok) {
         int sk0 = wgrad_pick_sk(M0, N0, K0, &ks0, &kb0), sk1 = wgrad_pick_sk(M1, N1, K1, &ks1, &kb1);
         if (kb0 == 4 && kb1 == 4) {
@@ -854,6 +872,22 @@ extern "C" int hsp_wgrad_partial_pair_f32(const float* A0, int lda0, const float
             const WgradProb p1{A1, B1, reinterpret_cast<float*>(ws1), lda1, ldb1, M1, N1, K1, sk1, ks1};
             const int blocks0 = (M0 >> 6) * (N0 >> 6) * (sk0 / 4), blocks1 = (M1 >> 6) * (N1 >> 6) * (sk1 / 4);
             const size_t lds = (size_t)4 * 4 * 16 * 64 * sizeof(float) + (size_t)4 * 64 * sizeof(float2);
+            ColsumRider rider{nullptr, nullptr, 0, 0, 0, 0, 1, 1};
+            int rider_blocks = 0;
+            if (cs_x) {
+                // the rider takes the resident slots the pair leaves free (2 workgroups per CU): as few column tiles per
+                // workgroup as fit -- a workgroup that owns more tiles runs that much longer
+                int rows, nchunk;
+                if (!cs_out || cs_B <= 0 || cs_N <= 0 || cs_C <= 0) return HSP_ERR_BAD_ARG;
+                if (!colsum_cloud_plan(cs_B, cs_N, cs_C, &rows, &nchunk)) return HSP_ERR_UNSUPPORTED;
+                if (((size_t)4 * 256 + (size_t)nchunk * (cs_C >> 5)) * sizeof(float4) > lds) return HSP_ERR_UNSUPPORTED;
+                const long long room = 2LL * HSP_NUM_CU - blocks0 - blocks1;
+                int tpb = 1;
+                while (tpb <= 8 && (long long)cs_B * (8 / tpb) > room) tpb <<= 1;
+                if (tpb > 8) return HSP_ERR_UNSUPPORTED;
+                rider = ColsumRider{cs_x, cs_out, cs_N, cs_C, nchunk, rows, tpb, 8 / tpb};
+                rider_blocks = cs_B * (8 / tpb);
+            }
             static bool attr_set = false;
             if (!attr_set) {
                 hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_pair_kernel),
@@ -861,7 +895,8 @@ extern "C" int hsp_wgrad_partial_pair_f32(const float* A0, int lda0, const float
                 if (e != hipSuccess) { set_last_hip_error(e); return HSP_ERR_LAUNCH; }
                 attr_set = true;
             }
-            hipLaunchKernelGGL(wgrad_pair_kernel, dim3(blocks0 + blocks1), dim3(256), lds, as_stream(stream), p0, p1, blocks0);
+            hipLaunchKernelGGL(wgrad_pair_kernel, dim3(blocks0 + blocks1 + rider_blocks), dim3(256), lds, as_stream(stream), p0, p1,
+                               blocks0, blocks0 + blocks1, rider);
             int rc = check_launch();
             if (rc) return rc;
             pending[0] = HspWgradPending{p0.part, nullptr, C0, nullptr, sk0 / 4, M0, N0, ldc0};
@@ -869,9 +904,26 @@ extern "C" int hsp_wgrad_partial_pair_f32(const float* A0, int lda0, const float
             return HSP_OK;
         }
     }
+    if (cs_x) return HSP_ERR_UNSUPPORTED;
     int rc = wgrad_impl<float>(A0, lda0, B0, ldb0, M0, N0, K0, C0, ldc0, nullptr, ws0, ws_bytes0, stream, pending);
     if (rc) return rc;
     return wgrad_impl<float>(A1, lda1, B1, ldb1, M1, N1, K1, C1, ldc1, nullptr, ws1, ws_bytes1, stream, pending + 1);
+}
+extern "C" int hsp_wgrad_partial_pair_f32(const float* A0, int lda0, const float* B0, int ldb0, int M0, int N0, int K0, float* C0,
+                                          int ldc0, void* ws0, size_t ws_bytes0, const float* A1, int lda1, const float* B1,
+                                          int ldb1, int M1, int N1, int K1, float* C1, int ldc1, void* ws1, size_t ws_bytes1,
+                                          HspWgradPending* pending, hspStream_t stream) {
+    return wgrad_pair_impl(A0, lda0, B0, ldb0, M0, N0, K0, C0, ldc0, ws0, ws_bytes0, A1, lda1, B1, ldb1, M1, N1, K1, C1, ldc1, ws1,
+                           ws_bytes1, pending, nullptr, 0, 0, 0, nullptr, stream);
+}
+extern "C" int hsp_wgrad_partial_pair_colsum_f32(const float* A0, int lda0, const float* B0, int ldb0, int M0, int N0, int K0,
+                                                 float* C0, int ldc0, void* ws0, size_t ws_bytes0, const float* A1, int lda1,
+                                                 const float* B1, int ldb1, int M1, int N1, int K1, float* C1, int ldc1, void* ws1,
+                                                 size_t ws_bytes1, HspWgradPending* pending, const float* x, int B, int N, int C,
+                                                 float* out, hspStream_t stream) {
+    if (!x || !out) return HSP_ERR_BAD_ARG;
+    return wgrad_pair_impl(A0, lda0, B0, ldb0, M0, N0, K0, C0, ldc0, ws0, ws_bytes0, A1, lda1, B1, ldb1, M1, N1, K1, C1, ldc1, ws1,
+                           ws_bytes1, pending, x, B, N, C, out, stream);
 }
 
 extern "C" int hsp_wgrad_fold(const HspWgradPending* pending, int n, hspStream_t stream) {

@@ -99,9 +99,14 @@ def set_timer(t):
     return prev
 
 
-def _run(name, args, key="", abytes=0, aflops=0):
+_ERR_UNSUPPORTED = -2       # include/hsp.h: HSP_ERR_UNSUPPORTED
+
+
+def _run(name, args, key="", abytes=0, aflops=0, may_decline=False):
     """call libhsp entry point ``name``; raise on a non-zero return code.  abytes / aflops: the call's
-    algorithmic bytes and (for GEMM-shaped, MFMA-bound kernels) flops, for bench.py's roofline line."""
+    algorithmic bytes and (for GEMM-shaped, MFMA-bound kernels) flops, for bench.py's roofline line.
+    ``may_decline``: HSP_ERR_UNSUPPORTED (nothing was launched) is returned as False instead of raised -- for merged launches
+    whose caller then issues the separate ones; True otherwise."""
     fn = getattr(lib(), name)
     t = _timer
     if t is not None and (t.only is None or name in t.only):
@@ -110,10 +115,14 @@ def _run(name, args, key="", abytes=0, aflops=0):
         e0.record()
         rc = fn(*args)
         e1.record()
-        t.records.append((name, key, abytes, aflops, e0, e1))
+        if not (may_decline and rc == _ERR_UNSUPPORTED):
+            t.records.append((name, key, abytes, aflops, e0, e1))
     else:
         rc = fn(*args)
+    if may_decline and rc == _ERR_UNSUPPORTED:
+        return False
     check(rc, name)
+    return True
 
 
 # ------------------------------------------------------------------------------------------------
@@ -292,6 +301,35 @@ def rev_index(idx, k, n_src):
          key=f"B{B}Nq{Nq}k{k}", abytes=B * (8 * Nq * k + 4 * n_src))
     cache[(k, n_src)] = (off, edge)
     return off, edge
+
+
+def rev_index_multi(items):
+    """``rev_index`` for a list of (idx, k, n_src) over the same B clouds: the maps the memo does not hold yet are built by ONE
+    ``hsp_rev_build_multi`` launch (up to four; more, or a single one, go through ``rev_index``).  Returns the (off, edge) pairs."""
+    missing = []
+    for idx, k, n_src in items:
+        cache = getattr(idx, "_hsp_rev", None)
+        if (cache is None or (k, n_src) not in cache) and not any(m[0] is idx and m[1:] == (k, n_src) for m in missing):
+            missing.append((idx, k, n_src))
+    if 2 <= len(missing) <= 4 and len({m[0].shape[0] for m in missing}) == 1:
+        n = len(missing)
+        B = missing[0][0].shape[0]
+        dims = [((idx.shape[1], 1) if idx.dim() == 2 else (idx.shape[1], idx.shape[2])) for idx, _, _ in missing]
+        offs = [torch.empty(B, n_src + 1, dtype=torch.int32, device=idx.device) for idx, _, n_src in missing]
+        edges = [torch.empty(B, nq * k, dtype=torch.int32, device=idx.device) for (idx, k, _), (nq, _) in zip(missing, dims)]
+        ptrs = lambda ts: ctypes.cast((ctypes.c_void_p * n)(*[t.data_ptr() for t in ts]), _vp)
+        ints = lambda vs: ctypes.cast((ctypes.c_int * n)(*vs), _vp)
+        _run("hsp_rev_build_multi", (n, ptrs([m[0] for m in missing]), B, ints([d[0] for d in dims]), ints([m[2] for m in missing]),
+                                     ints([m[1] for m in missing]), ints([d[1] for d in dims]), ptrs(offs), ptrs(edges), _stream()),
+             key=f"B{B}" + "+".join(f"Nq{d[0]}k{m[1]}" for m, d in zip(missing, dims)),
+             abytes=B * sum(8 * d[0] * m[1] + 4 * m[2] for m, d in zip(missing, dims)))
+        for (idx, k, n_src), off, edge in zip(missing, offs, edges):
+            cache = getattr(idx, "_hsp_rev", None)
+            if cache is None:
+                cache = {}
+                idx._hsp_rev = cache
+            cache[(k, n_src)] = (off, edge)
+    return [rev_index(idx, k, n_src) for idx, k, n_src in items]
 
 
 # ------------------------------------------------------------------------------------------------
@@ -730,15 +768,17 @@ def _wgrad_ok(A2, B2, out):
             and A2.stride(0) % 2 == 0 and B2.stride(0) % 2 == 0 and A2.dtype in _FEAT_DTYPES and A2.is_cuda)
 
 
-def wgrad_pair(A0, B0, out0, A1, B1, out1):
+def wgrad_pair(A0, B0, out0, A1, B1, out1, colsum_of=None):
     """(A0^T B0 -> out0, A1^T B1 -> out1) inside a ``WgradBatch``: ONE split-K launch for both when each is a K-sliced problem the
     hand-written kernel takes (the two parameter gradients of an HS layer that depend only on the incoming gradient: g^T F and
-    g^T X -- each alone leaves most of the chip idle); otherwise, and for bf16 rows (the pair kernel is fp32), two ``wgrad`` calls."""
+    g^T X -- each alone leaves most of the chip idle); otherwise, and for bf16 rows (the pair kernel is fp32), two ``wgrad`` calls.
+    ``colsum_of`` = (g (B,N,C) fp32, mom (B,C)): ask for mom = the per-cloud column sums of g (``hsp_colsum_cloud_f32``'s bits) as a
+    rider of that launch; returns True where it rode along, False (mom untouched, the products issued as without it) elsewhere."""
     batch = WgradBatch.current
     if batch is None or A0.dtype != torch.float32 or not _wgrad_ok(A0, B0, out0) or not _wgrad_ok(A1, B1, out1):
         wgrad(A0, B0, out=out0)
         wgrad(A1, B1, out=out1)
-        return
+        return False
     from ._lib import HspWgradPending
     L = lib()
     (K0, M0), N0 = A0.shape, B0.shape[1]
@@ -746,13 +786,21 @@ def wgrad_pair(A0, B0, out0, A1, B1, out1):
     wsb0, wsb1 = L.hsp_wgrad_workspace_bytes(M0, N0, K0), L.hsp_wgrad_workspace_bytes(M1, N1, K1)
     ws0, ws1 = _ws(wsb0, A0.device), _ws(wsb1, A0.device)
     pend = (HspWgradPending * 2)()
-    _run("hsp_wgrad_partial_pair_f32", (_p(A0), A0.stride(0), _p(B0), B0.stride(0), M0, N0, K0, _p(out0), out0.stride(0), _p(ws0), wsb0,
-                                        _p(A1), A1.stride(0), _p(B1), B1.stride(0), M1, N1, K1, _p(out1), out1.stride(0), _p(ws1), wsb1,
-                                        pend, _stream()),
-         key=f"M{M0}N{N0}K{K0}+M{M1}N{N1}K{K1}", abytes=4 * (K0 * (M0 + N0) + M0 * N0 + K1 * (M1 + N1) + M1 * N1),
-         aflops=2 * (M0 * N0 * K0 + M1 * N1 * K1))
+    pair = (_p(A0), A0.stride(0), _p(B0), B0.stride(0), M0, N0, K0, _p(out0), out0.stride(0), _p(ws0), wsb0,
+            _p(A1), A1.stride(0), _p(B1), B1.stride(0), M1, N1, K1, _p(out1), out1.stride(0), _p(ws1), wsb1, pend)
+    key, ab = f"M{M0}N{N0}K{K0}+M{M1}N{N1}K{K1}", 4 * (K0 * (M0 + N0) + M0 * N0 + K1 * (M1 + N1) + M1 * N1)
+    rode = False
+    if colsum_of is not None:
+        gx, mom = colsum_of
+        Bc, Nc, Cc = gx.shape
+        rode = _run("hsp_wgrad_partial_pair_colsum_f32", (*pair, _p(gx), Bc, Nc, Cc, _p(mom), _stream()),
+                    key=key + f"+cs B{Bc}N{Nc}C{Cc}", abytes=ab + 4 * Bc * Nc * Cc, aflops=2 * (M0 * N0 * K0 + M1 * N1 * K1),
+                    may_decline=True)
+    if not rode:
+        _run("hsp_wgrad_partial_pair_f32", (*pair, _stream()), key=key, abytes=ab, aflops=2 * (M0 * N0 * K0 + M1 * N1 * K1))
     batch.items.append((HspWgradPending.from_buffer_copy(pend[0]), ws0, _hold(out0)))
     batch.items.append((HspWgradPending.from_buffer_copy(pend[1]), ws1, _hold(out1)))
+    return rode
 
 
 def _ld(t):
@@ -1286,13 +1334,23 @@ def _orl_bwd_small_ok(B, N, C, with_xyz):
             and lib().hsp_colsum_cloud_ok(B, N, C, 1 if with_xyz else 0) == 1)
 
 
-def _orl_bwd_small(g, xyz, fg, Wb, gWb, gste=None):
-    """gfg / N (B,C) = (sum_i g) Wb / N; writes gWb (C,C) = (sum_i g)^T fg and, with ``xyz``, gste (C,3) = g^T xyz"""
+# COLSUM_RIDER = True: an HS layer's node goes one further -- its column sum rides in the launch of the two weight gradients that
+# depend only on the incoming gradient (hsp_wgrad_partial_pair_colsum_f32), which then comes first; hsp_small_pair_f32 follows as
+# its own call.  Same bits, -12 us per step at B = 16, N = 1028.  Off by default: it changes the
+# node's call list (three calls become two, in another order), which tests/test_gpu_one_layer_path.py pins literally for fp32
+# rows; tests/test_gpu_backward_merge.py runs both orders.
+COLSUM_RIDER = False
+
+
+def _orl_bwd_small(g, xyz, fg, Wb, gWb, gste=None, mom=None):
+    """gfg / N (B,C) = (sum_i g) Wb / N; writes gWb (C,C) = (sum_i g)^T fg and, with ``xyz``, gste (C,3) = g^T xyz.
+    ``mom``: the column sums (B,C) where an earlier launch already left them (no ``xyz``)"""
     B, N, C = g.shape
     ns = 4 if xyz is not None else 1
-    mom = torch.empty(B, ns * C, dtype=torch.float32, device=g.device)
-    _run("hsp_colsum_cloud_f32", (_p(g), _p(xyz), B, N, C, _p(mom), _stream()), key=f"B{B}N{N}C{C}{'x' if xyz is not None else ''}",
-         abytes=B * N * (4 * C + (12 if xyz is not None else 0)))
+    if mom is None:
+        mom = torch.empty(B, ns * C, dtype=torch.float32, device=g.device)
+        _run("hsp_colsum_cloud_f32", (_p(g), _p(xyz), B, N, C, _p(mom), _stream()), key=f"B{B}N{N}C{C}{'x' if xyz is not None else ''}",
+             abytes=B * N * (4 * C + (12 if xyz is not None else 0)))
     if _between_launches_hook is not None:
         _between_launches_hook(mom)
     gfg = torch.empty(B, C, dtype=torch.float32, device=g.device)
@@ -1532,13 +1590,22 @@ class _HSLayer(torch.autograd.Function):
         Wb = w_conv2[:, C:]
         small = f32 and _orl_bwd_small_ok(B, N, C, False)
         g_conv2 = torch.empty_like(w_conv2)
-        if small:
+        rider = small and COLSUM_RIDER
+        if rider:
+            pass                                                               # (gt rides in the pair launch below)
+        elif small:
             gfg_n = _orl_bwd_small(g, None, fg, Wb, g_conv2[:, C:])            # gt = sum_i g, gWb = gt^T fg, gt Wb / N: two launches
         else:
             gt = colsum_rows(g)                                                # fp32 (B,C) = sum_i g
         with WgradBatch(), x3_scope(ctx.x3):                                   # the three parameter gradients: one fold launch
             g_ste = torch.empty(C, Cin, dtype=torch.float32, device=g.device)
-            wgrad_pair(g2, F2, g_conv2[:, :C], g2, X2, g_ste)                  # gWa (in place, ldc = 2C) and gWste: one split-K launch
+            if rider:
+                mom = torch.empty(B, C, dtype=torch.float32, device=g.device)
+                rode = wgrad_pair(g2, F2, g_conv2[:, :C], g2, X2, g_ste, colsum_of=(g, mom))
+                # (declined -- the rider did not fit beside the pair: the column sum as a launch of its own, after the pair)
+                gfg_n = _orl_bwd_small(g, None, fg, Wb, g_conv2[:, C:], mom=mom if rode else None)
+            else:
+                wgrad_pair(g2, F2, g_conv2[:, :C], g2, X2, g_ste)              # gWa (in place, ldc = 2C) and gWste: one split-K launch
             if not small:
                 _tiny_tn(gt, fg, g_conv2[:, C:])                               # gWb = gt^T fg (tiny), straight into its column block
             gF3 = torch.empty(B, N, C, dtype=g.dtype, device=g.device)
@@ -2213,6 +2280,11 @@ def gather_rows(feat, idx):
 
 ONE_HOT_WIDTH = 6          # categories of a kind-3 (one-hot) segment; FaceRecon sets it from FLAGS.obj_c
 
+# The backward of the feat concat's gathered segments is two launches (hsp_rev_build_multi for the reverse maps the memo lacks,
+# hsp_gather_rows_bwd_csr_multi for the gathers) where it was one hsp_rev_build per map and one hsp_gather_rows_bwd_csr per
+# segment; same bits.  Test-only: CONCAT_BWD_MERGE = False issues the separate launches (tests/test_gpu_backward_merge.py).
+CONCAT_BWD_MERGE = True
+
 # feat row pitch: columns padded to a multiple of this many elements (8 = 16 bytes of bf16, 32 of fp32); 1 = no padding
 FEAT_PITCH_ALIGN = 8
 
@@ -2266,11 +2338,39 @@ class _AssembleFeat(torch.autograd.Function):
         return out
 
     @staticmethod
+    def _csr_ok(gs, w, W, es):
+        """segment shapes the gather form over the reverse map takes"""
+        return w % 2 == 0 and W % 2 == 0 and (w // 2 >= 256 or 256 % (w // 2) == 0) and gs.data_ptr() % (2 * es) == 0
+
+    @staticmethod
     def backward(ctx, g):
         if not g.is_contiguous():
             g = g.contiguous()
         B, N, W = g.shape
         saved = list(ctx.saved_tensors)
+        es = _es(g)
+        # the gathered segments that take the gather form: their reverse maps in one launch, their gathers in one launch
+        merged = {}
+        if CONCAT_BWD_MERGE:
+            col, it, todo = 0, iter(saved), []
+            for s_, (kd, w) in enumerate(zip(ctx.kinds, ctx.widths)):
+                idx = next(it) if ctx.has_idx[s_] else None
+                gs = g[:, :, col:col + w]
+                if kd == 1 and ctx.needs_input_grad[2 + s_] and _AssembleFeat._csr_ok(gs, w, W, es):
+                    todo.append((s_, idx, ctx.nsrc[s_], w, gs))
+                col += w
+            if 2 <= len(todo) <= 4:
+                n = len(todo)
+                revs = rev_index_multi([(idx, 1, Ns) for _, idx, Ns, _, _ in todo])
+                outs = [torch.empty(B, Ns, w, dtype=g.dtype, device=g.device) for _, _, Ns, w, _ in todo]
+                ptrs = lambda ts: ctypes.cast((ctypes.c_void_p * n)(*[t.data_ptr() for t in ts]), _vp)
+                ints = lambda vs: ctypes.cast((ctypes.c_int * n)(*vs), _vp)
+                if _run("hsp_gather_rows_bwd_csr_multi" + _sfx(g),
+                        (n, ptrs([t[4] for t in todo]), W, ptrs([r[0] for r in revs]), ptrs([r[1] for r in revs]), B,
+                         ints([t[2] for t in todo]), N, ints([t[3] for t in todo]), ptrs(outs), _stream()),
+                        key=f"B{B}Nq{N}" + "+".join(f"Ns{t[2]}C{t[3]}" for t in todo),
+                        abytes=B * sum(es * t[2] * t[3] + N * (4 + es * t[3]) for t in todo), may_decline=True):
+                    merged = {t[0]: o for t, o in zip(todo, outs)}     # (declined: the separate launches below)
         grads, col = [], 0
         for s_, (kd, w) in enumerate(zip(ctx.kinds, ctx.widths)):
             gs = g[:, :, col:col + w]
@@ -2280,12 +2380,14 @@ class _AssembleFeat(torch.autograd.Function):
                     saved.pop(0)
             elif kd == 0:
                 grads.append(gs)                                   # strided view: consumers take it as is / copy
+            elif kd == 1 and s_ in merged:
+                saved.pop(0)
+                grads.append(merged[s_])
             elif kd == 1:
                 idx = saved.pop(0)
                 Ns = ctx.nsrc[s_]
                 gfeat = torch.empty(B, Ns, w, dtype=g.dtype, device=g.device)
-                es = _es(g)
-                if w % 2 == 0 and W % 2 == 0 and (w // 2 >= 256 or 256 % (w // 2) == 0) and gs.data_ptr() % (2 * es) == 0:
+                if _AssembleFeat._csr_ok(gs, w, W, es):
                     # gather form over the reverse map (memoised on idx: fm_2 and fm_3 share one); deterministic
                     off, edge = rev_index(idx, 1, Ns)
                     _run("hsp_gather_rows_bwd_csr" + _sfx(g), (_p(gs), W, _p(off), _p(edge), B, Ns, N, w, _p(gfeat), _stream()),

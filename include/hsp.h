@@ -181,6 +181,10 @@ int hsp_rf_conv_bwd(const float *xyz, const float *dirs, const float *fm, const 
  */
 int hsp_rev_build(const int32_t *idx, int B, int Nq, int Nsrc, int k, int kstride, int32_t *rev_off,
                   int32_t *rev_edge, hspStream_t stream);
+/* nmaps <= 4 such indices over the same B clouds in ONE launch (map i: idx[i], Nq[i], Nsrc[i], k[i], kstride[i] ->
+ * rev_off[i], rev_edge[i]); the outputs of hsp_rev_build map by map. */
+int hsp_rev_build_multi(int nmaps, const int32_t *const *idx, int B, const int *Nq, const int *Nsrc, const int *k,
+                        const int *kstride, int32_t *const *rev_off, int32_t *const *rev_edge, hspStream_t stream);
 
 /* ---- neighbourhood max-pool (ORL global branch, Pool_layer) ----------------------------------
  * replaces indexing_neighbor_new(...) + max(dim=2)    gcn3d.py:214-216, :236-240
@@ -289,6 +293,14 @@ int hsp_gather_rows_bwd(const float *grad_out, int grad_stride, const int32_t *i
  * a time -- the faster form when grad_out is a column block of a much wider tensor (the 1286-wide feature). */
 int hsp_gather_rows_bwd_csr(const float *grad_out, int grad_stride, const int32_t *rev_off, const int32_t *rev_edge,
                             int B, int Nsrc, int Nq, int C, float *grad_feat, hspStream_t stream);
+/* nseg <= 4 such gathers out of ONE gradient tensor (row pitch grad_stride, Nq rows per cloud; segment s: grad_out[s] = the
+ * tensor's base + the segment's column offset, rev_off[s] / rev_edge[s], Nsrc[s], C[s] -> grad_feat[s]) in ONE launch, the
+ * bits of hsp_gather_rows_bwd_csr segment by segment: the backward of the feat concat's gathered segments.  A thread moves
+ * 16 bytes where the segment's width, pitch and addresses allow, else two elements.  HSP_ERR_UNSUPPORTED where
+ * hsp_gather_rows_bwd_csr declines one of the segments (nothing is launched). */
+int hsp_gather_rows_bwd_csr_multi(int nseg, const float *const *grad_out, int grad_stride, const int32_t *const *rev_off,
+                                  const int32_t *const *rev_edge, int B, const int *Nsrc, int Nq, const int *C,
+                                  float *const *grad_feat, hspStream_t stream);
 
 /* ---- dense per-point products (forward / input-gradient GEMMs with fused tails) ----------------
  * replaces the matmuls / Conv1d(k=1) of an HS layer and of the heads and the element-wise tail around them:
@@ -474,6 +486,15 @@ int hsp_wgrad_partial_pair_f32(const float *A0, int lda0, const float *B0, int l
                                void *ws0, size_t ws_bytes0, const float *A1, int lda1, const float *B1, int ldb1, int M1, int N1,
                                int K1, float *C1, int ldc1, void *ws1, size_t ws_bytes1, HspWgradPending *pending,
                                hspStream_t stream);
+/* the same launch with out (B, C) = hsp_colsum_cloud_f32(x (B,N,C), NULL) riding in it, bit for bit: the head of the layer's
+ * per-cloud backward chain depends on nothing the two products write.  The rider takes the resident workgroup slots the pair
+ * leaves free.  HSP_ERR_UNSUPPORTED, with nothing launched, where the pair is not a single launch, hsp_colsum_cloud_ok(B, N, C, 0)
+ * is 0 or the rider does not fit beside the pair: issue hsp_colsum_cloud_f32 and hsp_wgrad_partial_pair_f32 then. */
+int hsp_wgrad_partial_pair_colsum_f32(const float *A0, int lda0, const float *B0, int ldb0, int M0, int N0, int K0, float *C0,
+                                      int ldc0, void *ws0, size_t ws_bytes0, const float *A1, int lda1, const float *B1, int ldb1,
+                                      int M1, int N1, int K1, float *C1, int ldc1, void *ws1, size_t ws_bytes1,
+                                      HspWgradPending *pending, const float *x, int B, int N, int C, float *out,
+                                      hspStream_t stream);
 int hsp_wgrad_f32(const float *A, int lda, const float *B, int ldb, int M, int N, int K, float *C, int ldc,
                   float *colsum_B, void *ws, size_t ws_bytes, hspStream_t stream);
 int hsp_wgrad_partial_f32(const float *A, int lda, const float *B, int ldb, int M, int N, int K, float *C, int ldc,
@@ -627,6 +648,9 @@ int hsp_concat_rows_bf16(int nseg, const void *const *src, const int32_t *const 
 int hsp_gather_rows_bwd_csr_bf16(const hsp_bf16_t *grad_out, int grad_stride, const int32_t *rev_off,
                                  const int32_t *rev_edge, int B, int Nsrc, int Nq, int C, hsp_bf16_t *grad_feat,
                                  hspStream_t stream);
+int hsp_gather_rows_bwd_csr_multi_bf16(int nseg, const hsp_bf16_t *const *grad_out, int grad_stride,
+                                       const int32_t *const *rev_off, const int32_t *const *rev_edge, int B, const int *Nsrc,
+                                       int Nq, const int *C, hsp_bf16_t *const *grad_feat, hspStream_t stream);
 int hsp_wgrad_bf16(const hsp_bf16_t *A, int lda, const hsp_bf16_t *B, int ldb, int M, int N, int K, float *C, int ldc,
                    float *colsum_B, void *ws, size_t ws_bytes, hspStream_t stream);
 int hsp_wgrad_partial_bf16(const hsp_bf16_t *A, int lda, const hsp_bf16_t *B, int ldb, int M, int N, int K, float *C, int ldc,
