@@ -276,9 +276,11 @@ __global__ __launch_bounds__(256, 2) void gemm_x3_kernel(const X3Args g) {
             // the residual + per-cloud-bias part of ROW 0 of the result (data of this step only: a replayed graph and an eager
             // step compute identical bits; a running statistic would not give that); the heads' Linear + BatchNorm form
             // (EPI 9) shifts by the layer's bias: what is left in the sums is x W^T of post-ReLU rows, whose column mean can be a
-            // few standard deviations -- the variance then carries (mean / std)^2 * 2^-24 of relative error (1.5e-6 at 5 sigma),
-            // two orders below the tolerance the BatchNorm outputs are held to; a per-tile data shift would need a third row
-            // in bn_part and a Chan merge in bn_finalize
+            // few standard deviations.  With rho = |mean - shift| / std the variance then carries 4 ... 5 x rho^2 * 2^-24 of
+            // relative error (measured, 256 rows: 2.6e-6 at rho 3, 2.3e-5 at 10, 2.9e-4 at 30, 2.8e-3 at 100;
+            // tests/test_gpu_bn_reference.py part C2) and x-hat half of that: inside the 2e-5 the BatchNorm outputs are held to
+            // up to rho of about 10, outside it at 30.  A per-tile data shift would need a third row in
+            // bn_part and a Chan merge in bn_finalize (what the three-launch form of norm.hip does per row chunk)
             if constexpr (HAS_RES) bsh = g.resid[colc] + g.cbias[colc];
             else bsh = bvv;
             if (tm == 0 && wm0 == 0 && lh == 0 && cok) g.bn_shift[col] = bsh;

@@ -10,8 +10,12 @@
 //             num_batches_tracked) -> apply + ReLU                        (3 launches, x read twice)
 //   backward  dz = dy*[y>0]; partial (sum dz, sum dz*xhat) -> finalize (d gamma, d beta)
 //             -> dx = gamma*invstd*(dz - mean(dz) - xhat*mean(dz*xhat))   (3 launches)
-// Sums are "shifted" by the first row of the tensor (sum (x-s), sum (x-s)^2), which keeps fp32
-// cancellation harmless when |mean| >> std; partials are folded in a fixed order (deterministic).
+// Sums are "shifted" (sum (x-s), sum (x-s)^2), which keeps fp32 cancellation harmless when |mean| >> std. The three-launch
+// forward shifts every row chunk by the chunk's OWN first row and folds the chunks as (n, mean, M2) (Chan et al.), so one
+// untypical row costs its chunk of >= 32 rows a few digits and the statistics nothing: with one shift for the whole tensor
+// (row 0) the variance carried several times ((mean - shift) / std)^2 * 2^-24 of relative error -- y was 4e-3 off for a row 0
+// that is 30 sigma out (tests/test_gpu_bn_reference.py, part C). The fold of a producer's epilogue sums (hsp_bn_relu_fwd_partials)
+// still has one shift per column: DESIGN.md section 2.0 says how far that holds. Every fold runs in a fixed order (deterministic).
 // HBM-bound: forward algorithmic bytes = 4*R*C in + 4*R*C out; backward 8*R*C in + 4*R*C out.
 #include "common.h"
 
@@ -34,7 +38,8 @@ __device__ __forceinline__ float4 bn_ld4_pitch(const FT* p, int ld) {
 #define BN_MAX_PARTIALS 512       // row chunks (workgroups of the partial kernels); folded 16-way parallel by finalize
 
 // partial[blk][0][c] = sum_r v1, partial[blk][1][c] = sum_r v2 over the rows of chunk blk, where
-//   MODE 0 (forward stats):  v1 = x - shift,  v2 = (x - shift)^2            shift = x[0][c]
+//   MODE 0 (forward stats):  v1 = x - shift,  v2 = (x - shift)^2            shift = x[r0][c], r0 the chunk's first row
+//                            (bn_finalize_kernel<0, ., true> reads the same element again: no third row in `partial`)
 //   MODE 1 (backward):       v1 = dz,         v2 = dz * xhat                dz = relu ? dy*[a>0] : dy
 // FT: storage type of the row tensors x / dy / y / dx (statistics, affine parameters and partial sums are fp32)
 // XT: storage type of x (the BatchNorm INPUT) -- fp32 with bf16 y / dy / dx in the "mixed" form
@@ -57,7 +62,7 @@ __global__ __launch_bounds__(BN_THREADS) void bn_partial_kernel(const XT* __rest
     float4 s1 = make_float4(0.f, 0.f, 0.f, 0.f), s2 = s1;
     float4 sh = make_float4(0.f, 0.f, 0.f, 0.f), mu = sh, is = sh, ga = sh, be = sh;
     if (MODE == 0) {
-        sh = Feat<XT>::ld4(x + (g << 2));
+        sh = Feat<XT>::ld4(x + (size_t)r0 * C + (g << 2));
     } else {
         mu = *reinterpret_cast<const float4*>(mean + (g << 2));
         is = *reinterpret_cast<const float4*>(invstd + (g << 2));
@@ -107,12 +112,15 @@ __global__ __launch_bounds__(BN_THREADS) void bn_partial_kernel(const XT* __rest
 // one thread per channel: fold the partials (ascending block order), then
 //   MODE 0: mean, biased var -> invstd; running stats (momentum, unbiased var); num_batches_tracked += 1
 //   MODE 1: dgamma = sum dz*xhat, dbeta = sum dz; also keep both means for the dx pass
-template <int MODE, typename FT>
+// CHUNK_SHIFT (MODE 0): the partials are bn_partial_kernel<0>'s -- chunk b covers rows [b * rpb, min(R, (b + 1) * rpb)) and is
+// shifted by its first row, x[b * rpb][c]; false: one shift per column for every partial, passed through `x` ([tiles][2][C] of a
+// product's epilogue, tiles of any height)
+template <int MODE, typename FT, bool CHUNK_SHIFT = false>
 __global__ __launch_bounds__(1024) void bn_finalize_kernel(const float* __restrict__ partial, int nblk, int R, int C,
                                                            const FT* __restrict__ x, float eps, float momentum,
                                                            float* __restrict__ out_a, float* __restrict__ out_b,
                                                            float* __restrict__ run_mean, float* __restrict__ run_var,
-                                                           long long* __restrict__ num_batches) {
+                                                           long long* __restrict__ num_batches, int rpb = 0) {
     // workgroup = 16 channels x 64 slices of the partials: every thread sums its <= BN_MAX_PARTIALS/64 = 8 partials with all
     // loads in flight (one L2 round trip; a single thread walking 64 partials is a 10 us chain), then the 64 slices are
     // folded through LDS in a fixed order (deterministic).  (16 x 64 rather than 64 x 16: four times the workgroups --
@@ -120,37 +128,98 @@ __global__ __launch_bounds__(1024) void bn_finalize_kernel(const float* __restri
     __shared__ float red[64][2][16];
     const int lc = threadIdx.x & 15, sl = threadIdx.x >> 4;
     const int c = blockIdx.x * 16 + lc;
-    float a1 = 0.f, a2 = 0.f;
-    if (c < C) {
-        float u1[4] = {0.f, 0.f, 0.f, 0.f}, u2[4] = {0.f, 0.f, 0.f, 0.f};
-        int b = sl;
-        for (; b + 192 < nblk; b += 256) {                  // 8 loads in flight
+    float mean = 0.f, var = 0.f, s1 = 0.f, s2 = 0.f;
+    if constexpr (MODE == 0 && CHUNK_SHIFT) {
+        // n-way form of Chan's merge, two folds: chunk b has n_b rows, mean e_b + m0 and M2_b = s2_b - s1_b^2 / n_b, with m0 (the
+        // mean of chunk 0) the common reference of the chunk means;  ms = sum n_b e_b / R,  mean = m0 + ms,
+        // M2 = sum M2_b + sum n_b (e_b - ms)^2 -- no difference of large numbers beyond the one inside a chunk
+        __shared__ float msh[16];
+        constexpr int U = BN_MAX_PARTIALS / 64;
+        float p1[U], p2[U], xs[U], e[U], nb[U];
+        float a1 = 0.f, a2 = 0.f, m0 = 0.f;
 #pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                u1[u] += partial[(size_t)(b + 64 * u) * 2 * C + c];
-                u2[u] += partial[(size_t)(b + 64 * u) * 2 * C + C + c];
+        for (int u = 0; u < U; ++u) e[u] = nb[u] = 0.f;
+        if (c < C) {
+            m0 = Feat<FT>::ld(x + c) + partial[c] / (float)min(rpb, R);
+#pragma unroll
+            for (int u = 0; u < U; ++u) {                   // <= 24 loads in flight
+                const int b = sl + 64 * u;
+                p1[u] = p2[u] = xs[u] = 0.f;
+                if (b < nblk) {
+                    p1[u] = partial[(size_t)b * 2 * C + c];
+                    p2[u] = partial[(size_t)b * 2 * C + C + c];
+                    xs[u] = Feat<FT>::ld(x + (size_t)b * rpb * C + c);
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int b = sl + 64 * u;
+                if (b < nblk) {
+                    nb[u] = (float)min(rpb, R - b * rpb);
+                    const float inv = 1.0f / nb[u];
+                    e[u] = (xs[u] - m0) + p1[u] * inv;
+                    a1 += nb[u] * e[u];
+                    a2 += fmaxf(p2[u] - p1[u] * p1[u] * inv, 0.f);
+                }
             }
         }
-        for (; b < nblk; b += 64) {
-            u1[0] += partial[(size_t)b * 2 * C + c];
-            u2[0] += partial[(size_t)b * 2 * C + C + c];
-        }
-        a1 = (u1[0] + u1[1]) + (u1[2] + u1[3]);
-        a2 = (u2[0] + u2[1]) + (u2[2] + u2[3]);
-    }
-    red[sl][0][lc] = a1;
-    red[sl][1][lc] = a2;
-    __syncthreads();
-    if (sl != 0 || c >= C) return;
-    float s1 = red[0][0][lc], s2 = red[0][1][lc];
+        red[sl][0][lc] = a1;
+        red[sl][1][lc] = a2;
+        __syncthreads();
+        if (sl == 0) {
+            s1 = red[0][0][lc]; s2 = red[0][1][lc];
 #pragma unroll 8
-    for (int t = 1; t < 64; ++t) { s1 += red[t][0][lc]; s2 += red[t][1][lc]; }
+            for (int t = 1; t < 64; ++t) { s1 += red[t][0][lc]; s2 += red[t][1][lc]; }
+            msh[lc] = s1 / (float)R;
+        }
+        __syncthreads();
+        const float ms = msh[lc];
+        float d2 = 0.f;
+#pragma unroll
+        for (int u = 0; u < U; ++u) d2 += nb[u] * (e[u] - ms) * (e[u] - ms);
+        red[sl][0][lc] = d2;                                 // (red[.][0] was last read before the barrier above)
+        __syncthreads();
+        if (sl != 0 || c >= C) return;
+        float m2 = red[0][0][lc];
+#pragma unroll 8
+        for (int t = 1; t < 64; ++t) m2 += red[t][0][lc];
+        mean = m0 + ms;
+        var = (s2 + m2) / (float)R;
+    } else {
+        float a1 = 0.f, a2 = 0.f;
+        if (c < C) {
+            float u1[4] = {0.f, 0.f, 0.f, 0.f}, u2[4] = {0.f, 0.f, 0.f, 0.f};
+            int b = sl;
+            for (; b + 192 < nblk; b += 256) {                  // 8 loads in flight
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    u1[u] += partial[(size_t)(b + 64 * u) * 2 * C + c];
+                    u2[u] += partial[(size_t)(b + 64 * u) * 2 * C + C + c];
+                }
+            }
+            for (; b < nblk; b += 64) {
+                u1[0] += partial[(size_t)b * 2 * C + c];
+                u2[0] += partial[(size_t)b * 2 * C + C + c];
+            }
+            a1 = (u1[0] + u1[1]) + (u1[2] + u1[3]);
+            a2 = (u2[0] + u2[1]) + (u2[2] + u2[3]);
+        }
+        red[sl][0][lc] = a1;
+        red[sl][1][lc] = a2;
+        __syncthreads();
+        if (sl != 0 || c >= C) return;
+        s1 = red[0][0][lc]; s2 = red[0][1][lc];
+#pragma unroll 8
+        for (int t = 1; t < 64; ++t) { s1 += red[t][0][lc]; s2 += red[t][1][lc]; }
+        if (MODE == 0) {
+            const float invR = 1.0f / (float)R;
+            const float ms = s1 * invR;                              // mean of (x - shift)
+            var = s2 * invR - ms * ms;
+            if (var < 0.f) var = 0.f;
+            mean = Feat<FT>::ld(x + c) + ms;
+        }
+    }
     if (MODE == 0) {
-        const float invR = 1.0f / (float)R;
-        const float ms = s1 * invR;                              // mean of (x - shift)
-        float var = s2 * invR - ms * ms;
-        if (var < 0.f) var = 0.f;
-        const float mean = Feat<FT>::ld(x + c) + ms;
         out_a[c] = mean;
         out_b[c] = 1.0f / sqrtf(var + eps);
         if (run_mean) {
@@ -278,8 +347,8 @@ static int bn_relu_fwd_impl(const XT* x, int R, int C, const float* gamma, const
     const int nblk = bn_blocks(R);
     hipLaunchKernelGGL((bn_partial_kernel<0, FT, XT>), dim3(nblk), dim3(BN_THREADS), 0, st, x, (const FT*)nullptr, R, C, nullptr, nullptr,
                        nullptr, nullptr, 0, part, bn_rows_per_block(R));
-    hipLaunchKernelGGL((bn_finalize_kernel<0, XT>), dim3((C + 15) / 16), dim3(1024), 0, st, part, nblk, R, C, x, eps, momentum,
-                       save_mean, save_invstd, running_mean, running_var, num_batches_tracked);
+    hipLaunchKernelGGL((bn_finalize_kernel<0, XT, true>), dim3((C + 15) / 16), dim3(1024), 0, st, part, nblk, R, C, x, eps, momentum,
+                       save_mean, save_invstd, running_mean, running_var, num_batches_tracked, bn_rows_per_block(R));
     const long long total4 = (long long)R * (C >> 2);
     hipLaunchKernelGGL((bn_apply_kernel<FT, XT>), dim3(stream_grid4(total4)), dim3(256), 0, st, x, total4, C, save_mean, save_invstd,
                        gamma, beta, relu, y);

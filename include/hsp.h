@@ -505,7 +505,10 @@ int hsp_wgrad_partial_f32(const float *A, int lda, const float *B, int ldb, int 
  * x (R,C) point rows (R = B*N), batch statistics over R (biased variance for the normalisation, eps),
  * running_mean/var updated in place with `momentum` (unbiased variance) and *num_batches_tracked += 1
  * when the pointers are non-NULL -- nn.BatchNorm1d semantics.  y = relu ? max(0, bn(x)) : bn(x).
- * save_mean / save_invstd (C) feed the backward.  ws: hsp_bn_workspace_bytes(R, C).
+ * save_mean / save_invstd (C) feed the backward.  ws: hsp_bn_workspace_bytes(R, C) = [chunks][2][C] floats, chunks =
+ * ceil(R / max(32, ceil(R / 512))) <= 512 row chunks.  The forward's statistics: every chunk sums (x - s) and (x - s)^2 with
+ * s its OWN first row (read again from x by the fold, so the workspace holds no third row) and the chunks are merged as
+ * (n, mean, M2) in a fixed order -- deterministic, and a row far from its column's mean costs no digits of the variance.
  */
 size_t hsp_bn_workspace_bytes(int R, int C);
 int hsp_bn_relu_fwd(const float *x, int R, int C, const float *gamma, const float *beta, float eps,
