@@ -153,6 +153,9 @@ SIGNATURES = {
     "hsp_rf_conv_bwd_scatter_partial_bf16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp, _vp]),
     "hsp_wgrad_partial_pair_f32": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp, _sz] * 2 + [_vp, _vp]),
     "hsp_wgrad_partial_pair_colsum_f32": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp, _sz] * 2 + [_vp, _vp, _i, _i, _i, _vp, _vp]),
+    "hsp_rf_fwd_plan": (_i, [_i, _i, _i, _vp]),
+    "hsp_rf_bwd_scatter_plan": (_i, [_i, _i, _i, _i, _i, _vp]),
+    "hsp_scatter_tile_plan": (_i, [_i, _i, _i, _vp]),
     "hsp_pose_augment": (_i, [_vp] * 14 + [_i, _i, _i] + [ctypes.c_float] * 4 + [_vp] * 5),
 }
 

@@ -637,17 +637,30 @@ static int pick_scatter_cols(int Nsrc, int C) {
     return 0;
 }
 
+// threads per workgroup: 1024 while the grid covers at most half the CUs, 512 up to one workgroup per CU (measured at B = 16:
+// N = 1028, C = 128 -- 128 workgroups -- 17.7 -> 15.6 us with 1024 threads, the flush 9 200 -> 3 500 clocks; N = 257, C = 256 --
+// 256 workgroups -- no better with 1024 than with 256: 9.3 vs 8.9 us)
+static int scatter_tile_threads(int tc, int B, int C) {
+    const long long wgs = (long long)(C / tc) * B;
+    return 2 * wgs <= HSP_NUM_CU ? 1024 : wgs <= HSP_NUM_CU ? 512 : 256;
+}
+
+// the plan of the column-tile scatter: tile width (0: no tile fits, the caller falls back or declines) and workgroup size.  The
+// one source of truth of launch_scatter_tile's callers and of hsp_scatter_tile_plan.
+extern "C" int hsp_scatter_tile_plan(int B, int Nsrc, int C, int* threads) {
+    int tc = 0;
+    if (B > 0 && Nsrc > 0 && C > 0 && !(C & 3)) tc = pick_scatter_cols(Nsrc, C);
+    if (threads) *threads = tc ? scatter_tile_threads(tc, B, C) : 0;
+    return tc;
+}
+
 template <int MODE, typename FT>
 static int launch_scatter_tile(int tc, const FT* gout, const float* gbc, int gstride, int gbcast, const int32_t* idx,
                                int idx_shared, const int32_t* qsel, const uint8_t* argmax, int B, int Nsrc, int Nidx, int Nq,
                                int kstride, int C, FT* gfeat, int accumulate, const FT* extra, hipStream_t st) {
     const size_t lds = (size_t)Nsrc * tc * 4;
     dim3 grid(C / tc, B);
-    // threads per workgroup: 1024 while the grid covers at most half the CUs, 512 up to one workgroup per CU (measured at B = 16:
-    // N = 1028, C = 128 -- 128 workgroups -- 17.7 -> 15.6 us with 1024 threads, the flush 9 200 -> 3 500 clocks; N = 257, C = 256 --
-    // 256 workgroups -- no better with 1024 than with 256: 9.3 vs 8.9 us)
-    const long long wgs = (long long)(C / tc) * B;
-    const int nt = 2 * wgs <= HSP_NUM_CU ? 1024 : wgs <= HSP_NUM_CU ? 512 : 256;
+    const int nt = scatter_tile_threads(tc, B, C);
 #define SC_LAUNCH_NT(TC, NT_)                                                                                      \
     {                                                                                                              \
         auto kern = scatter_tile_bwd_kernel<TC, MODE, FT, NT_>;                                                    \

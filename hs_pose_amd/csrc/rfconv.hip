@@ -110,11 +110,11 @@ __global__ __launch_bounds__(RF_THREADS) void rf_fwd_kernel(const float* __restr
         for (int i = it.i0; i < N; i += it.istep) {
             const size_t pt = (size_t)b * N + i;
             __syncthreads();                                   // previous point's LDS reads are done
-            if (tid < k) {
-                const int m = idx[pt * k + tid];
-                sIdx[tid] = m;
+            for (int t = tid; t < k; t += RF_THREADS) {         // (k may exceed the workgroup: the host bounds only the LDS)
+                const int m = idx[pt * k + t];
+                sIdx[t] = m;
                 const float3 r = unit_dir(xb[i * 3], xb[i * 3 + 1], xb[i * 3 + 2], xb[m * 3], xb[m * 3 + 1], xb[m * 3 + 2]);
-                sR[tid] = make_float4(r.x, r.y, r.z, 0.f);
+                sR[t] = make_float4(r.x, r.y, r.z, 0.f);
             }
             __syncthreads();
 #pragma unroll
@@ -186,7 +186,8 @@ __global__ __launch_bounds__(RF_THREADS) void rf_fwd_kernel(const float* __restr
 // consecutive points share ONE barrier interval: the threads that have no column group in the last of the NCH slots
 // (S*C/4 = 224 groups on 256 threads at C = 128) build the directions of point i+1 into the other half of a double
 // buffer while the gather of point i runs, and the average of point i-1 is taken from the other maxima buffer at the
-// start of the interval.  Same arithmetic, same results bit for bit (tests/test_gpu_layers.py compares the schedules).
+// start of the interval.  Same arithmetic as rf_fwd_kernel; no shape runs under both schedules (hsp_rf_fwd_plan picks one per
+// (k, S, C)), so tests/test_gpu_rf_reference.py holds each of them to the same fp64 reference and asserts the plan it entered.
 // dynamic LDS: 2 * (S*C + 6 k) floats.  Needs S*C/4 - (NCH-1)*256 + k <= 256.
 // ------------------------------------------------------------------------------------------------
 template <bool SURFACE, int NCH, bool WF, typename FT>
@@ -567,7 +568,7 @@ __global__ __launch_bounds__(RF_TILE_THREADS) void rf_bwd_tile_kernel(
             int lg = 0;
             while ((1 << lg) < N) ++lg;
             int e = 30 - ex - lg;
-            e = e > 120 ? 120 : (e < -120 ? -120 : e);
+            e = e > 126 ? 126 : (e < -126 ? -126 : e);      // (2^e and 2^-e both normal floats; |grad| / S down to ~2^-96 keeps the full quantum)
             fx_scale = ldexpf(1.f, e);
             fx_inv = ldexpf(1.f, -e);
         }
@@ -691,6 +692,29 @@ static int rf_check(const void* a, const void* b, const void* c, int B, int N, i
     return HSP_OK;
 }
 
+// which forward kernel a (k, S, C) runs: column slots per thread (0: declined) and the schedule.  The one source of truth of
+// rf_fwd and of hsp_rf_fwd_plan.
+struct RfFwdPlan { int nch; bool pipe; size_t lds; };
+static RfFwdPlan rf_fwd_plan(int k, int S, int C) {
+    RfFwdPlan p{0, false, 0};
+    if (k <= 0 || S <= 0 || C <= 0 || (C & 3) || (long long)S * C > 4096 || k > 16384) return p;   // S*C <= 4096: 4 slots
+    const size_t lds = (size_t)(S * C + 5 * k) * 4;
+    if (lds > 64 * 1024) return p;
+    p.nch = ((S * C >> 2) + RF_THREADS - 1) / RF_THREADS;
+    p.lds = lds;
+    // the pipelined schedule (three points' phases per barrier interval) wherever the last slot leaves k threads free
+    const int spare0 = (S * C >> 2) - (p.nch - 1) * RF_THREADS;
+    const size_t lds_pipe = 2 * (size_t)(S * C + 6 * k) * 4;
+    if (spare0 + k <= RF_THREADS && lds_pipe <= 64 * 1024) { p.pipe = true; p.lds = lds_pipe; }
+    return p;
+}
+
+extern "C" int hsp_rf_fwd_plan(int k, int S, int C, int* pipelined) {
+    const RfFwdPlan p = rf_fwd_plan(k, S, C);
+    if (pipelined) *pipelined = p.pipe ? 1 : 0;
+    return p.nch;
+}
+
 template <bool SURFACE, typename FT>
 static int rf_fwd(const float* xyz, const int32_t* idx, const float* dirs, const FT* fm, int B, int N, int k,
                   int S, int C, FT* out, uint16_t* argrow, FT* fwin, hspStream_t stream) {
@@ -700,42 +724,36 @@ static int rf_fwd(const float* xyz, const int32_t* idx, const float* dirs, const
     // (A channel-split schedule -- C / 2 channels per pass so that a cloud's fm slice stays in the XCD's L2 -- halves the fabric
     // reads (FETCH_SIZE 252 -> 121 MB at B=16 N=1028) but the kernel is VALU-issue-bound: 121 vs 101 us in round 2, and again
     // slower inside the matrix-core form of round 4, tools/experiments/.  Removed.)
-    const size_t lds = (size_t)(S * C + 5 * k) * 4;
-    if (lds > 64 * 1024) return HSP_ERR_UNSUPPORTED;
+    const RfFwdPlan plan = rf_fwd_plan(k, S, C);
+    if (!plan.nch) return HSP_ERR_UNSUPPORTED;            // S*C <= 4096, (S*C + 5 k) floats of LDS
+    const int nch = plan.nch;
     // workgroups per CU: 8 for the large layers; small clouds amortise a workgroup's prologue (direction loads + normalisation)
     // over more points with 6 / 4 (measured at B = 16: N = 257 55.3 -> 52.4 us, N = 64 24.3 -> 23.6 us)
     const long long npts = (long long)B * N;
     const int grid = persistent_blocks(npts, npts < 2048 ? 4 : npts < 8192 ? 6 : 8);
-    const int nch = ((S * C >> 2) + RF_THREADS - 1) / RF_THREADS;
-    if (nch > 4) return HSP_ERR_UNSUPPORTED;              // S*C <= 4096
-    {
-        // the pipelined schedule (three points' phases per barrier interval) wherever the last slot leaves k threads free
-        const int spare0 = (S * C >> 2) - (nch - 1) * RF_THREADS;
-        const size_t lds_pipe = 2 * (size_t)(S * C + 6 * k) * 4;
-        if (spare0 + k <= RF_THREADS && lds_pipe <= 64 * 1024) {
+    if (plan.pipe) {
 #define RF_PIPE_LAUNCH(NCH)                                                                                        \
     if (!SURFACE && fwin)                                                                                          \
-        hipLaunchKernelGGL((rf_fwd_pipe_kernel<SURFACE, NCH, !SURFACE, FT>), dim3(grid), dim3(RF_THREADS), lds_pipe, \
+        hipLaunchKernelGGL((rf_fwd_pipe_kernel<SURFACE, NCH, !SURFACE, FT>), dim3(grid), dim3(RF_THREADS), plan.lds, \
                            as_stream(stream), xyz, idx, dirs, fm, B, N, k, S, C, out, argrow, fwin);               \
     else                                                                                                           \
-        hipLaunchKernelGGL((rf_fwd_pipe_kernel<SURFACE, NCH, false, FT>), dim3(grid), dim3(RF_THREADS), lds_pipe,   \
+        hipLaunchKernelGGL((rf_fwd_pipe_kernel<SURFACE, NCH, false, FT>), dim3(grid), dim3(RF_THREADS), plan.lds,   \
                            as_stream(stream), xyz, idx, dirs, fm, B, N, k, S, C, out, argrow, fwin)
-            switch (nch) {
-                case 1: RF_PIPE_LAUNCH(1); break;
-                case 2: RF_PIPE_LAUNCH(2); break;
-                case 3: RF_PIPE_LAUNCH(3); break;
-                default: RF_PIPE_LAUNCH(4); break;
-            }
-#undef RF_PIPE_LAUNCH
-            return check_launch();
+        switch (nch) {
+            case 1: RF_PIPE_LAUNCH(1); break;
+            case 2: RF_PIPE_LAUNCH(2); break;
+            case 3: RF_PIPE_LAUNCH(3); break;
+            default: RF_PIPE_LAUNCH(4); break;
         }
+#undef RF_PIPE_LAUNCH
+        return check_launch();
     }
 #define RF_FWD_LAUNCH(NCH)                                                                                        \
     if (!SURFACE && fwin)                                                                                          \
-        hipLaunchKernelGGL((rf_fwd_kernel<SURFACE, NCH, !SURFACE, FT>), dim3(grid), dim3(RF_THREADS), lds, as_stream(stream), \
+        hipLaunchKernelGGL((rf_fwd_kernel<SURFACE, NCH, !SURFACE, FT>), dim3(grid), dim3(RF_THREADS), plan.lds, as_stream(stream), \
                            xyz, idx, dirs, fm, B, N, k, S, C, out, argrow, fwin);                                 \
     else                                                                                                           \
-        hipLaunchKernelGGL((rf_fwd_kernel<SURFACE, NCH, false, FT>), dim3(grid), dim3(RF_THREADS), lds, as_stream(stream), \
+        hipLaunchKernelGGL((rf_fwd_kernel<SURFACE, NCH, false, FT>), dim3(grid), dim3(RF_THREADS), plan.lds, as_stream(stream), \
                            xyz, idx, dirs, fm, B, N, k, S, C, out, argrow, fwin)
     switch (nch) {
         case 1: RF_FWD_LAUNCH(1); break;
@@ -841,6 +859,23 @@ static bool rf_use_row_split(int N, int C, bool surface, int tc_whole) {
     return ((size_t)nr * 16 + 3 * (size_t)nr) * 4 <= 156u * 1024;
 }
 
+// which tile kernel a shape runs: tile width (0: declined) and the number of row ranges (2: the half-cloud form).  The one source
+// of truth of rf_bwd_scatter and of hsp_rf_bwd_scatter_plan.
+struct RfBwdPlan { int tc, rs; };
+static RfBwdPlan rf_bwd_plan(int B, int N, int S, int C, bool surface) {
+    const int tc = pick_tile_cols(N, C, surface, B, S * C);
+    if (rf_use_row_split(N, C, surface, tc)) return RfBwdPlan{16, 2};
+    return RfBwdPlan{tc, tc ? 1 : 0};
+}
+
+extern "C" int hsp_rf_bwd_scatter_plan(int B, int N, int S, int C, int surface, int* row_split) {
+    RfBwdPlan p{0, 0};
+    if (B > 0 && N > 0 && N <= 65535 && S > 0 && C > 0 && !(C & 3) && (long long)S * C <= (1 << 24))
+        p = rf_bwd_plan(B, N, S, C, surface != 0);
+    if (row_split) *row_split = p.rs;
+    return p.tc;
+}
+
 template <bool SURFACE, bool FWIN, typename FT>
 static int rf_bwd_scatter(const float* xyz, const float* dirs, const FT* fm, const uint16_t* argrow,
                           const FT* gout, int B, int N, int S, int C, FT* gfm, float* gdirs, void* ws,
@@ -850,10 +885,11 @@ static int rf_bwd_scatter(const float* xyz, const float* dirs, const FT* fm, con
     if (!gout || !gdirs || (!SURFACE && (!fm || !gfm))) return HSP_ERR_BAD_ARG;
     const int SC = S * C;
     if (!ws || ws_bytes < hsp_rf_bwd_scatter_workspace_bytes(B, SC)) return HSP_ERR_WORKSPACE;
-    const int tc = pick_tile_cols(N, C, SURFACE, B, S * C);
+    const RfBwdPlan plan = rf_bwd_plan(B, N, S, C, SURFACE);
+    const int tc = plan.tc;
     hipStream_t st = as_stream(stream);
     float* part = reinterpret_cast<float*>(ws);
-    if (rf_use_row_split(N, C, SURFACE, tc)) {
+    if (plan.rs == 2) {
         const int nr = (N + 1) / 2;
         const size_t lds2 = ((size_t)nr * 16 + 3 * (size_t)nr) * 4;
         auto kern = rf_bwd_tile_kernel<16, SURFACE, FWIN, FT, 2>;

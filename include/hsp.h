@@ -148,24 +148,43 @@ int hsp_rf_surface_bwd(const float *xyz, const float *dirs, const uint16_t *argr
  * hsp_rf_conv_bwd_scatter reads as a stream (inference passes NULL).
  */
 int hsp_rf_conv_wants_fwin(int N, int S, int C);
+/* Which forward kernel a (k, S, C) runs, for every hsp_rf_*_fwd* entry point (the dispatch decides by the same function): returns the
+ * column slots per thread, 1 ... 4 = ceil(S*C / 1024), or 0 where the call is declined (HSP_ERR_UNSUPPORTED: C % 4, S*C > 4096,
+ * (S*C + 5 k) floats > 64 KiB of LDS); *pipelined (may be NULL) = 1 for the pipelined schedule, taken wherever
+ * S*C/4 - (slots-1)*256 + k <= 256, else 0 for the plain one (which serves any k the LDS holds, k > 256 included). */
+int hsp_rf_fwd_plan(int k, int S, int C, int *pipelined);
 int hsp_rf_conv_fwd(const float *xyz, const int32_t *idx, const float *dirs, const float *fm, int B,
                     int N, int k, int S, int C, float *out, uint16_t *argrow, float *fwin,
                     hspStream_t stream);
 /* Backward, COLUMN-TILE LDS-SCATTER form (the default of the Python mirror): a (cloud, 16-column) tile
- * of grad_fm plus the cloud's xyz live in LDS; gradients are routed to row argrow[b,i,j] with ds_add_f32
+ * of grad_fm plus the cloud's xyz live in LDS; gradients are routed to row argrow[b,i,j] with integer LDS adds
  * (immune to the in-degree hubs of feature-space graphs) and every row segment is written once.
- * grad_fm (B,N,(S+1)*C) and grad_dirs (3,S*C) are OVERWRITTEN.  The LDS adds make grad_fm
- * order-dependent in the last bits; hsp_rf_conv_bwd is the bit-reproducible twin.
+ * grad_fm (B,N,(S+1)*C) and grad_dirs (3,S*C) are OVERWRITTEN.  hsp_rf_conv_bwd is the gather-form twin.
  * fwin: the forward's (B,N,S*C) winner support values (then fm may be NULL), or NULL: the values are
  * gathered from fm (B,N,(S+1)*C).  hsp_rf_conv_wants_fwin(N,S,C) says which is faster (fwin once a cloud's
  * fm outgrows the L2 share it gets).
- * ws: hsp_rf_bwd_scatter_workspace_bytes(B, S*C). */
+ * ws: hsp_rf_bwd_scatter_workspace_bytes(B, S*C).
+ * The tile accumulates in 32-bit fixed point: per (cloud, column tile) the quantum is q = 2^(ex + ceil(log2 N) - 30), 2^ex the
+ * power of two above max |grad_out| / S over the tile's channels, so a grad_fm support cell is a multiple of q, carries at
+ * most q/2 of rounding per routed term, cannot overflow (a cell receives at most one term per point, |theta| <= 1), and is
+ * the same bits on every run.  A tile whose gradients are all zero gives exact zeros.
+ * Non-finite gradients: a NaN at grad_out[b,i,c] arrives in the centre column grad_fm[b,i,c] as it is (a copy); every cell
+ * that this element does not feed -- all of grad_fm but the support cells (argrow[b,i,s*C+c], C+s*C+c), all of grad_dirs but
+ * the columns s*C+c -- is finite and correct (a NaN is ignored where the tile's scale is chosen).  What the fed cells
+ * hold is unspecified. */
 int hsp_rf_conv_bwd_scatter(const float *xyz, const float *dirs, const float *fm, const float *fwin,
                             const uint16_t *argrow,
                             const float *grad_out, int B, int N, int S, int C, float *grad_fm,
                             float *grad_dirs, void *ws, size_t ws_bytes, hspStream_t stream);
+/* Which tile kernel hsp_rf_conv_bwd_scatter* (surface = 0) / hsp_rf_surface_bwd* (surface != 0) run for a shape (the dispatch
+ * decides by the same function): returns the tile width in columns (64, 32, 16, 8 or 4) or 0 where the call is declined
+ * (HSP_ERR_UNSUPPORTED); *row_split (may be NULL) = 1 for one whole-cloud tile per workgroup, 2 for the two half-cloud tiles
+ * of 16 columns that dense clouds take, 0 with a decline. */
+int hsp_rf_bwd_scatter_plan(int B, int N, int S, int C, int surface, int *row_split);
 /* Backward, GATHER form over rev_off/rev_edge = hsp_rev_build(idx) of the SAME idx the forward used:
  * every grad_fm row is summed in ascending edge order (no atomics, bit-reproducible).
+ * The rows of one neighbour list idx[b,i,:] must be DISTINCT: a hit is "the winner of (i, j) is this row", so a row listed
+ * in two slots of the same list would be counted once per slot.  (KNN lists are; the scatter form has no such requirement.)
  * ws: hsp_rf_bwd_workspace_bytes(S*C). */
 size_t hsp_rf_bwd_workspace_bytes(int SC);
 int hsp_rf_conv_bwd(const float *xyz, const float *dirs, const float *fm, const uint16_t *argrow,
@@ -203,6 +222,11 @@ int hsp_gather_max_fwd(const float *feat, const int32_t *idx, const int32_t *qse
  * (Nq ints, shared by the batch) + argmax, and xyz_sel (B,Nq,3) = xyz[:, qsel] (the reference's vertices[:, sample_idx]). */
 int hsp_pool_fwd(const float *feat, const float *xyz, const int32_t *idx, const int32_t *qsel, int B, int N, int Nq, int k,
                  int kstride, int C, float *out, uint8_t *argmax, float *xyz_sel, hspStream_t stream);
+/* The plan of the column-tile LDS scatter behind hsp_gather_max_bwd* and hsp_gather_rows_bwd (their dispatch decides by the same functions):
+ * returns the tile width (16, 8 or 4 columns: the widest that divides C with Nsrc * width * 4 bytes <= 144 KiB) or 0 where no
+ * tile fits (then fp32 falls back to memset + global atomics, without `extra`; bf16 declines); *threads (may be NULL) = the
+ * workgroup size, 1024 / 512 / 256 by the grid (C / width) * B against the 256 CUs. */
+int hsp_scatter_tile_plan(int B, int Nsrc, int C, int *threads);
 int hsp_gather_max_bwd(const float *grad_out, int grad_bcast, const int32_t *idx, const int32_t *qsel,
                        const uint8_t *argmax, int B, int Nsrc, int Nidx, int Nq, int kstride, int C,
                        float *grad_feat, int accumulate /* !=0: add into grad_feat instead of overwriting */,
