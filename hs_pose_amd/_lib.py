@@ -35,6 +35,7 @@ SIGNATURES = {
     "hsp_points_max_fwd": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
     "hsp_points_max_bwd": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
     "hsp_orl_workspace_bytes": (_sz, [_i, _i, _i]),
+    "hsp_orl_counts_offset": (ctypes.c_longlong, [_i, _i, _i, _i, _i, _sz]),
     "hsp_knn_exact_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "hsp_knn_exact_f32": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp, _vp]),
     "hsp_knn_xyz_workspace_bytes": (_sz, [_i, _i]),

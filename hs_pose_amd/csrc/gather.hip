@@ -151,10 +151,19 @@ __device__ __forceinline__ float max3_raw(float a, float b, float c) {
 // K is a template constant (the HS layers' k = 20 is the only instance): every neighbour loop is straight-line code -- run-time "n < k"
 // guards turned the first form into 180 branches -- and all K rows of a (point, 4 channels) sit in registers (80 of the 128 VGPRs a
 // 512-thread workgroup has)
-template <typename FT, int K>
+//
+// CNT (fp32 rows): the kernel also COUNTS the winners -- counts[b][m][c] = #{i : idx[b][i][argmax[b][i][c]] == m}, all the ORL
+// backward needs of the forward (gF += count * gfg / N: orl_counts_bwd_kernel, one stream pass instead of the LDS scatter that
+// re-derived the counts from argmax and the lists).  The 16 spare bytes of a 48-byte slab row ARE the row's 8 counters: 16 bits a
+// channel, channels 2w / 2w + 1 in the low / high half of word w (a count is at most N < 65536: no carry crosses the halves), zeroed
+// at staging, bumped by one ds_add_u32 per (point, channel) at the winning row's offset -- which the strip already holds --, and
+// written as the 16 bytes counts[b][m][c0 .. c0 + 8) of a (B, N, C) uint16 tensor after the sweep.  fg == nullptr: counts (and the
+// arg-max bytes) only, for clouds whose fg comes from the chunked form.
+template <typename FT, int K, bool CNT = false>
 __global__ __launch_bounds__(ORLT_WG) void orl_tile_kernel(const FT* __restrict__ feat, const int32_t* __restrict__ idx, int B, int N,
                                                            int C, uint8_t* __restrict__ argmax, float* __restrict__ fg,
-                                                           float inv_n) {
+                                                           float inv_n, unsigned short* __restrict__ counts = nullptr) {
+    static_assert(!CNT || sizeof(FT) == 4, "the counters live in the padding of the fp32 slab rows");
     static_assert(K % 2 == 0 && K >= 4, "a wave's 32 K staged indices are K / 2 per lane");
     constexpr int k = K;
     extern __shared__ __attribute__((aligned(16))) float4 orl_tile[];      // N slab rows, then ORLT_WG / 64 strips of 32 k ushorts
@@ -175,6 +184,7 @@ __global__ __launch_bounds__(ORLT_WG) void orl_tile_kernel(const FT* __restrict_
         if constexpr (sizeof(FT) == 4) {
             *reinterpret_cast<float4*>(slab0 + i * ROWB) = Feat<FT>::ld4(fb + (size_t)i * C);
             *reinterpret_cast<float4*>(slab0 + i * ROWB + 16) = Feat<FT>::ld4(fb + (size_t)i * C + 4);
+            if constexpr (CNT) *reinterpret_cast<uint4*>(slab0 + i * ROWB + 32) = make_uint4(0u, 0u, 0u, 0u);
         } else {
             const uint4 v = *reinterpret_cast<const uint4*>(fb + (size_t)i * C);
             *reinterpret_cast<uint2*>(slab0 + i * ROWB) = make_uint2(v.x, v.y);
@@ -214,7 +224,13 @@ __global__ __launch_bounds__(ORLT_WG) void orl_tile_kernel(const FT* __restrict_
 #pragma unroll
             for (int n = 0; n < K; ++n) {
                 const char* rp = slab + ((unsigned)my[n] << SH);
-                if constexpr (sizeof(FT) == 4) f[n] = *reinterpret_cast<const float4*>(rp);
+                if constexpr (sizeof(FT) == 4) {
+                    // one ds_read_b128, spelled as a vector load: a float4 struct load reaches the back end as four scalar loads
+                    // that it may or may not fuse again (beside the counter adds it did not: 13 -> 20 us at N = 1028)
+                    typedef float v4f __attribute__((ext_vector_type(4)));
+                    const v4f v = *reinterpret_cast<const v4f*>(rp);
+                    f[n] = make_float4(v.x, v.y, v.z, v.w);
+                }
                 else {
                     const uint2 u2 = *reinterpret_cast<const uint2*>(rp);
                     f[n] = make_float4(__uint_as_float(u2.x << 16), __uint_as_float(u2.x & 0xffff0000u), __uint_as_float(u2.y << 16),
@@ -242,6 +258,13 @@ __global__ __launch_bounds__(ORLT_WG) void orl_tile_kernel(const FT* __restrict_
             *reinterpret_cast<uchar4*>(argmax + ((size_t)b * N + i) * C + c0 + (q << 2)) =
                 make_uchar4((unsigned char)a0, (unsigned char)a1, (unsigned char)a2, (unsigned char)a3);
             s.x += best.x; s.y += best.y; s.z += best.z; s.w += best.w;
+            if constexpr (CNT) {                               // this lane's 4 channels: words 2 q, 2 q + 1 of the winning rows' counters
+                char* const cb = slab0 + 32 + q * 8;
+                atomicAdd(reinterpret_cast<unsigned*>(cb + ((unsigned)my[a0] << SH)), 1u);
+                atomicAdd(reinterpret_cast<unsigned*>(cb + ((unsigned)my[a1] << SH)), 0x10000u);
+                atomicAdd(reinterpret_cast<unsigned*>(cb + ((unsigned)my[a2] << SH) + 4), 1u);
+                atomicAdd(reinterpret_cast<unsigned*>(cb + ((unsigned)my[a3] << SH) + 4), 0x10000u);
+            }
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         ORL_STAMP(4 + 3 * (i0 / PASS));
@@ -254,12 +277,40 @@ __global__ __launch_bounds__(ORLT_WG) void orl_tile_kernel(const FT* __restrict_
     }
     if (lane < 2) red[wave * 2 + q] = s;
     __syncthreads();
-    if (tid < 2) {
+    if (tid < 2 && fg) {
         float4 t = red[q];
         for (int w = 1; w < ORLT_WG / 64; ++w) { const float4 v = red[w * 2 + q]; t.x += v.x; t.y += v.y; t.z += v.z; t.w += v.w; }
         *reinterpret_cast<float4*>(fg + (size_t)b * C + c0 + (q << 2)) = make_float4(t.x * inv_n, t.y * inv_n, t.z * inv_n, t.w * inv_n);
     }
+    if constexpr (CNT) {                                       // (the barrier above: every wave's adds have landed)
+        unsigned short* cw = counts + (size_t)b * N * C + c0;
+        for (int i = tid; i < N; i += ORLT_WG)
+            *reinterpret_cast<uint4*>(cw + (size_t)i * C) = *reinterpret_cast<const uint4*>(slab0 + i * ROWB + 32);
+    }
     ORL_STAMP(31);
+}
+
+// The ORL backward from those counts: gfeat[b][m][:] = gbc[b][:] * counts[b][m][:] (+ gfeat[b][m][:]) (+ extra[b][m][:]) -- a pure
+// stream over (B N, C / 4) float4 units; the expression and its order are the flush of scatter_tile_bwd_kernel's broadcast branch
+// (the build runs with -ffp-contract=off), so the two give the same bits.
+template <typename FT>
+__global__ __launch_bounds__(256) void orl_counts_bwd_kernel(const float* __restrict__ gbc, const unsigned short* __restrict__ counts,
+                                                             unsigned N, unsigned C, unsigned total, FT* __restrict__ gfeat,
+                                                             int accumulate, const FT* __restrict__ extra) {
+    const unsigned cq = C >> 2;                                // (32-bit unit index: the host declines total >= 2^31)
+    for (unsigned u = blockIdx.x * 256 + threadIdx.x; u < total; u += gridDim.x * 256) {
+        const unsigned row = u / cq, g = u - row * cq, b = row / N;
+        const size_t e = u;
+        const uint2 cw = *reinterpret_cast<const uint2*>(counts + e * 4);
+        const float4 gb = *reinterpret_cast<const float4*>(gbc + (size_t)b * C + (g << 2));
+        const float4 o = accumulate ? Feat<FT>::ld4(gfeat + e * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+        const float4 x = extra ? Feat<FT>::ld4(extra + e * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+        float4 v = make_float4(gb.x * (int)(cw.x & 0xffffu), gb.y * (int)(cw.x >> 16), gb.z * (int)(cw.y & 0xffffu),
+                               gb.w * (int)(cw.y >> 16));
+        if (accumulate) { v.x += o.x; v.y += o.y; v.z += o.z; v.w += o.w; }
+        if (extra) { v.x += x.x; v.y += x.y; v.z += x.z; v.w += x.w; }
+        Feat<FT>::st4(gfeat + e * 4, v);
+    }
 }
 
 // out[b][c] = scale * sum_chunk part[b][chunk][c]   (also the generic "column sum per cloud" second stage)
@@ -913,6 +964,16 @@ template <typename FT>
 static int gather_max_bwd_impl(const void* grad_out, int grad_bcast, const int32_t* idx, const int32_t* qsel,
                                const uint8_t* argmax, int B, int Nsrc, int Nidx, int Nq, int kstride, int C,
                                FT* grad_feat, int accumulate, const FT* extra, hspStream_t stream) {
+    if (grad_bcast == 2) {
+        // `argmax` holds the forward's winner counts (B, Nsrc, C) uint16 (hsp_orl_counts_offset): one stream pass, no idx / qsel
+        if (!grad_out || !argmax || !grad_feat || B <= 0 || Nsrc <= 0 || C <= 0) return HSP_ERR_BAD_ARG;
+        const long long total = (long long)B * Nsrc * (C >> 2);
+        if ((C & 3) || (reinterpret_cast<uintptr_t>(argmax) & 7) || total > 0x7fffffffLL) return HSP_ERR_UNSUPPORTED;
+        hipLaunchKernelGGL(orl_counts_bwd_kernel<FT>, dim3(stream_grid(total)), dim3(256), 0, as_stream(stream),
+                           reinterpret_cast<const float*>(grad_out), reinterpret_cast<const unsigned short*>(argmax), (unsigned)Nsrc,
+                           (unsigned)C, (unsigned)total, grad_feat, accumulate, extra);
+        return check_launch();
+    }
     if (!grad_out || !idx || !argmax || !grad_feat || B <= 0 || Nsrc <= 0 || Nidx <= 0 || Nq <= 0 || kstride <= 0 || C <= 0)
         return HSP_ERR_BAD_ARG;
     if (!qsel && Nq != Nidx) return HSP_ERR_BAD_ARG;
@@ -1238,6 +1299,18 @@ extern "C" size_t hsp_orl_workspace_bytes(int B, int N, int C) {
     return (size_t)B * ((N + rows - 1) / rows) * C * sizeof(float);
 }
 
+// where the slab kernel leaves the winner counts of a call in its workspace, or -1: fp32 rows, k = 20 on contiguous lists, the
+// cloud's 8-channel slab within the LDS limit, and room for (B, N, C) uint16 after today's region rounded up to 256 bytes.
+// (256 % (C / 4): hsp_orl_global_fwd itself takes no other C -- its chunked form, which a cloud under 128 points still runs
+// for fg, spreads a row's C / 4 units over a 256-thread workgroup -- so such a call produces nothing, counts included)
+extern "C" long long hsp_orl_counts_offset(int B, int N, int k, int kstride, int C, size_t ws_bytes) {
+    const size_t base = hsp_orl_workspace_bytes(B, N, C);
+    if (!base || k != 20 || kstride != k || (C % ORLT_TC) || (256 % (C >> 2)) || N >= 65536) return -1;
+    if ((size_t)N * 48 + (ORLT_WG / 2) * (size_t)k * sizeof(short) > 144 * 1024) return -1;
+    const size_t off = (base + 255) & ~(size_t)255;
+    return ws_bytes >= off + (size_t)B * N * C * sizeof(short) ? (long long)off : -1;
+}
+
 template <typename FT>
 static int orl_global_fwd_impl(const FT* feat, const int32_t* idx, int B, int N, int k, int kstride, int C,
                                float* fg, uint8_t* argmax, void* ws, size_t ws_bytes, hspStream_t stream) {
@@ -1246,13 +1319,40 @@ static int orl_global_fwd_impl(const FT* feat, const int32_t* idx, int B, int N,
     if (!ws || ws_bytes < hsp_orl_workspace_bytes(B, N, C)) return HSP_ERR_WORKSPACE;
     hipStream_t st = as_stream(stream);
     const size_t lds_tile = (size_t)N * (sizeof(FT) == 4 ? 48 : 24) + (ORLT_WG / 2) * (size_t)k * sizeof(short);   // slab + the waves' list strips
-    if ((C % ORLT_TC) == 0 && lds_tile <= 144 * 1024 && N >= 128 && N <= 21845 && k == 20 && kstride == k) {   // fg written by the kernel itself
+    const bool tile = (C % ORLT_TC) == 0 && lds_tile <= 144 * 1024 && N >= 128 && N <= 21845 && k == 20 && kstride == k;
+    if constexpr (sizeof(FT) == 4) {
+        // a workspace with room for them asks for the winner counts (hsp_orl_counts_offset); fg / argmax are those of the plain call
+        // (the counts rows are 16-byte stores: a workspace that is not so aligned -- some larger scratch buffer of a caller who never
+        // asked for counts -- gets the plain call, as before)
+        const long long coff = (reinterpret_cast<uintptr_t>(ws) & 15) ? -1 : hsp_orl_counts_offset(B, N, k, kstride, C, ws_bytes);
+        if (coff >= 0) {
+            unsigned short* counts = reinterpret_cast<unsigned short*>(static_cast<char*>(ws) + coff);
+            auto kern = orl_tile_kernel<FT, 20, true>;
+            if (lds_tile > 64 * 1024) {
+                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024);
+                if (e != hipSuccess) { set_last_hip_error(e); return HSP_ERR_LAUNCH; }
+            }
+            if (!tile) {
+                // a cloud under 128 points keeps the chunked form's fg (its fold order); the slab kernel then only counts
+                const int rows = chunk_rows(B, N, C);
+                const int nchunk = (N + rows - 1) / rows;
+                float* part = reinterpret_cast<float*>(ws);
+                hipLaunchKernelGGL(orl_partial_kernel<FT>, dim3(nchunk, B), dim3(256), 0, st, feat, idx, N, k, kstride, C, argmax, part, nchunk, rows);
+                hipLaunchKernelGGL(chunk_fold_kernel, dim3((B * C + 255) / 256), dim3(256), 0, st, part, B, nchunk, C, 1.0f / (float)N, fg);
+            }
+            hipLaunchKernelGGL(kern, dim3(C / ORLT_TC * B), dim3(ORLT_WG), lds_tile, st, feat, idx, B, N, C, argmax,
+                               tile ? fg : static_cast<float*>(nullptr), 1.0f / (float)N, counts);
+            return check_launch();
+        }
+    }
+    if (tile) {                                              // fg written by the kernel itself
         auto kern = orl_tile_kernel<FT, 20>;
         if (lds_tile > 64 * 1024) {                          // per device, so on every such launch (a process may drive several GPUs)
             hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024);
             if (e != hipSuccess) { set_last_hip_error(e); return HSP_ERR_LAUNCH; }
         }
-        hipLaunchKernelGGL(kern, dim3(C / ORLT_TC * B), dim3(ORLT_WG), lds_tile, st, feat, idx, B, N, C, argmax, fg, 1.0f / (float)N);
+        hipLaunchKernelGGL(kern, dim3(C / ORLT_TC * B), dim3(ORLT_WG), lds_tile, st, feat, idx, B, N, C, argmax, fg, 1.0f / (float)N,
+                           static_cast<unsigned short*>(nullptr));
         return check_launch();
     }
     const int rows = chunk_rows(B, N, C);

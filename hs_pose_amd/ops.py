@@ -1273,18 +1273,44 @@ def _tiny_tn(a, b, out, mom=None, gste=None):
     return out
 
 
-def _orl_fwd_raw(F3, idx_x, k):
-    """(fg (B,C) fp32, argmax (B,N,C) uint8): mean over points of the neighbourhood max of fp32 / bf16 rows, one pass, no (B,N,C)
-    max tensor"""
+# ORL_COUNTS = True: the layer nodes ask the ORL forward for its winner counts (a larger workspace, hsp_orl_counts_offset) and run
+# the ORL backward from them as one stream pass (hsp_gather_max_bwd, grad_bcast = 2) instead of the LDS scatter that re-derives the
+# counts from the arg-max bytes and the lists.  Same call names in the same order, same bits; the forward declines (k != 20, strided
+# lists, bf16 rows, a cloud past the slab's LDS limit) -> today's calls.  The switch exists for A/B runs and tests.
+# ORL_COUNTS_MIN_N: the nodes ask from this many points on.  Under 128 points the forward keeps its chunked form for fg and runs the
+# slab kernel as a third launch only to count; measured (B = 16, forward + backward pair in a replayed graph) that costs more than
+# the stream pass saves: N = 100, C = 128: 12.2 -> 14.4 us, N = 64, C = 256: 10.5 -> 12.9 us, N = 127, C = 128: 11.3 -> 12.9 us
+# (N = 257, C = 256: 17.4 -> 11.2 us).
+ORL_COUNTS = True
+ORL_COUNTS_MIN_N = 128
+
+
+def _orl_fwd_counts_raw(F3, idx_x, k, ask=True):
+    """(fg (B,C) fp32, argmax (B,N,C) uint8, counts): mean over points of the neighbourhood max of fp32 / bf16 rows, one pass, no
+    (B,N,C) max tensor.  counts: the winner counts (B,N,C) uint16 of this call for ``_orl_bwd_accumulate_raw`` (a view of a
+    workspace tensor of its own), or None -- always three results -- where they are not asked for (``ask``: a forward nothing
+    will differentiate has no use for them), ORL_COUNTS is off or the forward does not produce them"""
     B, N, C = F3.shape
     fg = torch.empty(B, C, dtype=torch.float32, device=F3.device)
     arg = torch.empty(B, N, C, dtype=torch.uint8, device=F3.device)
     L = lib()
     wsb = L.hsp_orl_workspace_bytes(B, N, C)
+    off = -1
+    if ask and ORL_COUNTS and F3.dtype == torch.float32:
+        full = ((wsb + 255) & ~255) + 2 * B * N * C
+        off = L.hsp_orl_counts_offset(B, N, k, idx_x.shape[2], C, full)
+        if off >= 0:
+            wsb = full
     ws = _ws(wsb, F3.device)
+    cnt = ws[off:off + 2 * B * N * C].view(torch.uint16).view(B, N, C) if off >= 0 else None
     _run("hsp_orl_global_fwd" + _sfx(F3), (_p(F3), _p(idx_x), B, N, k, idx_x.shape[2], C, _p(fg), _p(arg), _p(ws), wsb, _stream()),
-         key=f"B{B}N{N}k{k}C{C}", abytes=B * N * (_es(F3) * C + 4 * k + C))
-    return fg, arg
+         key=f"B{B}N{N}k{k}C{C}", abytes=B * N * (_es(F3) * C + 4 * k + C + (2 * C if cnt is not None else 0)))
+    return fg, arg, cnt
+
+
+def _orl_fwd_raw(F3, idx_x, k):
+    """(fg, argmax) of ``_orl_fwd_counts_raw`` on the plain workspace: no counts asked for"""
+    return _orl_fwd_counts_raw(F3, idx_x, k, ask=False)[:2]
 
 
 def _residual_bias(out3, f3, t2):
@@ -1362,9 +1388,10 @@ def _orl_bwd_small(g, xyz, fg, Wb, gWb, gste=None, mom=None):
     return gfg
 
 
-def _orl_bwd_accumulate_raw(gfg_over_n, idx_x, arg, k, gF3, extra=None):
+def _orl_bwd_accumulate_raw(gfg_over_n, idx_x, arg, k, gF3, extra=None, counts=None):
     """gF3[b,m,c] += extra[b,m,c] + gfg_over_n[b,c] * #{i : idx_x[b,i,arg[b,i,c]] == m}     (in place, one pass); fp32 / bf16 rows
-    (the reverse-edge form of DETERMINISTIC is fp32-only)"""
+    (the reverse-edge form of DETERMINISTIC is fp32-only).  ``counts``: that number as the forward left it (``_orl_fwd_counts_raw``) --
+    then a stream pass, same bits"""
     B, N, C = gF3.shape
     if DETERMINISTIC and gF3.dtype == torch.float32:
         tmp = torch.empty_like(gF3)
@@ -1374,6 +1401,10 @@ def _orl_bwd_accumulate_raw(gfg_over_n, idx_x, arg, k, gF3, extra=None):
         gF3.add_(tmp)
         if extra is not None:
             gF3.add_(extra)
+    elif counts is not None:
+        _run("hsp_gather_max_bwd" + _sfx(gF3), (_p(gfg_over_n), 2, _vp(0), _vp(0), _p(counts), B, N, N, N, idx_x.shape[2], C,
+                                                _p(gF3), 1, _p(extra), _stream()),
+             key=f"B{B}Ns{N}Nq{N}C{C}cnt+", abytes=B * N * C * (3 * _es(gF3) + 2))
     else:
         _run("hsp_gather_max_bwd" + _sfx(gF3), (_p(gfg_over_n), 1, _p(idx_x), _vp(0), _p(arg), B, N, N, N, idx_x.shape[2], C,
                                                 _p(gF3), 1, _p(extra), _stream()),
@@ -1557,13 +1588,14 @@ class _HSLayer(torch.autograd.Function):
         out3 = torch.empty(B, N, C, dtype=torch.float32 if out_f32 else X.dtype, device=X.device)
         if exact:
             fg, arg_o = _orl_fwd_exact(F3, idx_x, k)
+            cnt_o = None
             _layer_out_exact(F2, w_conv2, fg, N, out3, ste=gemm_wave(X2, w_ste, False))
             part = None
         else:
-            fg, arg_o = _orl_fwd_raw(F3, idx_x, k)                             # fp32 (B,C)
+            fg, arg_o, cnt_o = _orl_fwd_counts_raw(F3, idx_x, k, ask=need_bwd and N >= ORL_COUNTS_MIN_N)    # fp32 (B,C)
             t2 = _mm_nt(fg, w_conv2[:, C:])                                    # fp32 (B,C): the per-cloud half of conv2
             part = _layer_out_rows(X2, w_ste, F2, w_conv2, t2, out3, bn_shift=bn_shift)          # X Wste^T + F Wa^T + F + t[b]
-        ctx.save_for_backward(xyz, X, idx_f, idx_x, fm, arg, F3, arg_o, fg, weights, directions, w_ste3, w_conv23)
+        ctx.save_for_backward(xyz, X, idx_f, idx_x, fm, arg, F3, arg_o, fg, weights, directions, w_ste3, w_conv23, cnt_o)
         ctx.k, ctx.S, ctx.x3 = k, S, x3_planes
         if bn_shift is not None:
             # second output: the BatchNorm partial sums of out3 (or an empty tensor when the product that ran does not leave
@@ -1577,7 +1609,7 @@ class _HSLayer(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g, _gpart=None):
-        xyz, X, idx_f, idx_x, fm, arg, F3, arg_o, fg, weights, directions, w_ste3, w_conv23 = ctx.saved_tensors
+        xyz, X, idx_f, idx_x, fm, arg, F3, arg_o, fg, weights, directions, w_ste3, w_conv23, cnt_o = ctx.saved_tensors
         w_ste, w_conv2 = w_ste3.squeeze(-1), w_conv23.squeeze(-1)
         k, S = ctx.k, ctx.S
         f32 = X.dtype == torch.float32
@@ -1612,7 +1644,7 @@ class _HSLayer(torch.autograd.Function):
             _mm_nn(g2, w_conv2, out=gF3.view(B * N, C), cols=slice(0, C))      # g Wa ...
             if not small:
                 gfg_n = _mm_nn(gt, Wb, alpha=1.0 / N)
-            _orl_bwd_accumulate_raw(gfg_n, idx_x, arg_o, k, gF3, extra=g)      # ... + g + ORL scatter, one pass
+            _orl_bwd_accumulate_raw(gfg_n, idx_x, arg_o, k, gF3, extra=g, counts=cnt_o)    # ... + g + the ORL term, one pass
             gfm, gD = _rf_conv_bwd_raw(xyz, idx_f, directions, fm.view(B, N, -1), arg, gF3, S)
             gfm2 = gfm.view(B * N, -1)
             gW, gb = wgrad(X2, gfm2, colsum=True)                              # X^T gfm and the bias gradient
@@ -1646,25 +1678,26 @@ class _SurfaceLayer(torch.autograd.Function):
         out3 = torch.empty(B, N, C, dtype=out_dtype, device=xyz.device)
         if _exact and _exact_layer_ok(N, 3, C, (w_conv2, F2)):                # (fp32 rows only)
             fg, arg_o = _orl_fwd_exact(F3, idx_x, k)
+            cnt_o = None
             _layer_out_exact(F2, w_conv2, fg, N, out3, xyz3=x2, w3=w_ste.contiguous(), relu=relu)
         else:
-            fg, arg_o = _orl_fwd_raw(F3, idx_x, k)
+            fg, arg_o, cnt_o = _orl_fwd_counts_raw(F3, idx_x, k, ask=any(ctx.needs_input_grad) and N >= ORL_COUNTS_MIN_N)
             t2 = _mm_nt(fg, w_conv2[:, C:])
             _layer_out_rows(x2, w_ste, F2, w_conv2, t2, out3, relu=relu)
         ctx.k, ctx.S, ctx.relu, ctx.x3 = k, S, relu, x3_planes
         if relu:
             # relu(conv_0(...)) (FaceRecon.py:88) inside the node: the relu rides in the product's epilogue, the result is handed
             # out TWICE (conv_1 and the concat read it) and the two gradients + the relu mask meet in ONE pass in backward
-            ctx.save_for_backward(xyz, idx_x, arg, F3, arg_o, fg, directions, w_conv23, out3)
+            ctx.save_for_backward(xyz, idx_x, arg, F3, arg_o, fg, directions, w_conv23, cnt_o, out3)
             ctx.set_materialize_grads(False)
             return out3, out3.view_as(out3)
-        ctx.save_for_backward(xyz, idx_x, arg, F3, arg_o, fg, directions, w_conv23)
+        ctx.save_for_backward(xyz, idx_x, arg, F3, arg_o, fg, directions, w_conv23, cnt_o)
         return out3
 
     @staticmethod
     def backward(ctx, *gs):
         if ctx.relu:
-            xyz, idx_x, arg, F3, arg_o, fg, directions, w_conv23, y = ctx.saved_tensors
+            xyz, idx_x, arg, F3, arg_o, fg, directions, w_conv23, cnt_o, y = ctx.saved_tensors
             gs = [t for t in gs if t is not None]
             if not gs:
                 return (None,) * 9
@@ -1675,7 +1708,7 @@ class _SurfaceLayer(torch.autograd.Function):
             _run("hsp_add_relu_bwd", (_p(ga), lda, _p(gb), ldb, _p(y), B * N, C, _p(g), _stream()), key=f"R{B * N}C{C}",
                  abytes=4 * (2 + len(gs)) * B * N * C)
         else:
-            xyz, idx_x, arg, F3, arg_o, fg, directions, w_conv23 = ctx.saved_tensors
+            xyz, idx_x, arg, F3, arg_o, fg, directions, w_conv23, cnt_o = ctx.saved_tensors
             g = gs[0]
         w_conv2 = w_conv23.squeeze(-1)
         k, S = ctx.k, ctx.S
@@ -1716,7 +1749,7 @@ class _SurfaceLayer(torch.autograd.Function):
             _mm_nn(g2, w_conv2, out=gF3.view(B * N, C), cols=slice(0, C))
         if not small:
             gfg_n = _mm_nn(gt, Wb, alpha=1.0 / N)
-        _orl_bwd_accumulate_raw(gfg_n, idx_x, arg_o, k, gF3, extra=g)
+        _orl_bwd_accumulate_raw(gfg_n, idx_x, arg_o, k, gF3, extra=g, counts=cnt_o)
         gD = torch.empty_like(directions)
         L = lib()
         wsb = L.hsp_rf_bwd_scatter_workspace_bytes(B, SC)

@@ -227,6 +227,11 @@ int hsp_pool_fwd(const float *feat, const float *xyz, const int32_t *idx, const 
  * tile fits (then fp32 falls back to memset + global atomics, without `extra`; bf16 declines); *threads (may be NULL) = the
  * workgroup size, 1024 / 512 / 256 by the grid (C / width) * B against the 256 CUs. */
 int hsp_scatter_tile_plan(int B, int Nsrc, int C, int *threads);
+/* grad_bcast == 2 (hsp_gather_max_bwd and _bf16): `argmax` points at the winner counts (B,Nsrc,C) uint16 that hsp_orl_global_fwd
+ * left in its workspace (hsp_orl_counts_offset; 8-byte aligned) instead of the arg-max bytes; grad_out is the (B,C) fp32 row as for
+ * grad_bcast == 1.  idx and qsel are ignored and may be NULL, Nidx / Nq / kstride are ignored.  One streaming launch, no LDS, no
+ * atomics: grad_feat = grad_out[b] * count (+ grad_feat if accumulate) (+ extra), the same expression in the same order as the
+ * flush of the LDS scatter, hence the same bits as grad_bcast == 1 on the arg-max bytes of the same forward call. */
 int hsp_gather_max_bwd(const float *grad_out, int grad_bcast, const int32_t *idx, const int32_t *qsel,
                        const uint8_t *argmax, int B, int Nsrc, int Nidx, int Nq, int kstride, int C,
                        float *grad_feat, int accumulate /* !=0: add into grad_feat instead of overwriting */,
@@ -249,8 +254,28 @@ int hsp_points_max_bwd(const float *grad_out, const int32_t *argrow, int B, int 
 
 /* ORL global feature in one pass (get_ORL_global, gcn3d.py:211-218, before the repeat):
  * fg (B,C) = mean_i max_{n<k} feat[b, idx[b,i,n], :], argmax (B,N,C) uint8; the (B,N,C) max tensor is never
- * written.  idx (B,N,kstride).  ws: hsp_orl_workspace_bytes(B,N,C).  Backward: hsp_gather_max_bwd(grad_bcast=1). */
+ * written.  idx (B,N,kstride).  ws: hsp_orl_workspace_bytes(B,N,C).  Backward: hsp_gather_max_bwd(grad_bcast=1).
+ *
+ * Winner counts (fp32 rows): a LARGER workspace asks hsp_orl_global_fwd to also leave counts (B,N,C) uint16,
+ * counts[b][m][c] = #{i : idx[b][i][argmax[b][i][c]] == m} -- all the backward needs of this call -- at byte offset
+ * hsp_orl_counts_offset(B, N, k, kstride, C, ws_bytes) of ws.  The offset is hsp_orl_workspace_bytes rounded up to 256, and
+ * ws_bytes must cover B*N*C*2 bytes after it; the query returns -1, and the call writes no counts, when ws_bytes is smaller
+ * or the call does not take the LDS slab kernel: k != 20, kstride != k, C % 8, a cloud whose slab is past the LDS limit
+ * (N > 2858), or a C the forward itself declines (C / 4 must divide 256, as without counts: HSP_ERR_UNSUPPORTED).
+ * ws must be 16-BYTE ALIGNED for counts (the query does not see the pointer): a call whose ws is large enough but not so
+ * aligned is the plain call -- it succeeds and writes NO counts -- so a caller that wants them aligns ws, and a caller that
+ * passes some larger scratch buffer without wanting them loses nothing but, when aligned, has B*N*C*2 bytes written there.
+ * fg and argmax are bit for bit those of the call with the plain workspace size.
+ * Clouds under 128 points (k = 20): the plain call is the chunked form (two launches); with counts the slab kernel runs AFTER
+ * it as a third launch, only to count: fg stays the chunked form's (its fold order), the arg-max bytes are rewritten by the
+ * slab kernel so that they are the winners the counts count.  The two kernels pick the same winner for ordinary numbers and
+ * differ only where the comment at max3_raw (csrc/gather.hip) says they do, on NaN activations -- there argmax/counts follow
+ * the slab kernel and fg the chunked one.  Whether the extra launch pays is the caller's choice: hs_pose_amd.ops asks for
+ * counts only from 128 points on.
+ * Backward from the counts: hsp_gather_max_bwd(grad_bcast=2).  hsp_orl_global_fwd_bf16 never writes counts (its slab rows
+ * have no room for them) and ignores the extra bytes. */
 size_t hsp_orl_workspace_bytes(int B, int N, int C);
+long long hsp_orl_counts_offset(int B, int N, int k, int kstride, int C, size_t ws_bytes);
 int hsp_orl_global_fwd(const float *feat, const int32_t *idx, int B, int N, int k, int kstride, int C,
                        float *fg, uint8_t *argmax, void *ws, size_t ws_bytes, hspStream_t stream);
 /* The same feature with the REFERENCE's summation order: ATen's cascade sum over the points (16-row level-0 chunks, levels dumped
