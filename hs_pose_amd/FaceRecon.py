@@ -151,8 +151,9 @@ class FaceRecon(nn.Module):
             ops.x3_refresh()                          # fp32 weights -> the three bf16 slices of the x3 products (one launch)
         with gcn3d.knn_scope():
             # the two coarse levels' vertices, neighbour lists and up-sampling maps in one launch, up front (they depend on the
-            # coordinates and the host-drawn pool rows only)
-            up = (gcn3d.prefetch_levels(vertices, k, self.pool_1.neighbor_num, rates=(self.pool_1.pooling_rate, self.pool_2.pooling_rate))
+            # coordinates and the pool rows -- host-drawn, or under the 'fps' sampler picked from the coordinates -- only)
+            up = (gcn3d.prefetch_levels(vertices, k, self.pool_1.neighbor_num, rates=(self.pool_1.pooling_rate, self.pool_2.pooling_rate),
+                                        samplers=(self.pool_1.sampler, self.pool_2.sampler))
                   if self.pool_1.neighbor_num == self.pool_2.neighbor_num else None)
             od = self.feature_dtype if self.feature_dtype == torch.bfloat16 else None
             fork0 = od is None and not self.keep_backward_cut and torch.is_grad_enabled()

@@ -31,6 +31,8 @@ class _Flags:
         prop_pm_w=2.0, prop_sym_w=1.0, prop_r_reg_w=1.0,                                # config.py:91-93
         lr=1e-4,              # config.py:96
         lr_pose=1.0,          # config.py:98
+        pool_sampler='random',  # (not in the reference) Pool_layer's down-sampler: 'random' -- the reference's randperm slice --
+                                # or 'fps' -- per-cloud farthest-point sampling on the device (gcn3d.Pool_layer)
     )
 
     def __init__(self):

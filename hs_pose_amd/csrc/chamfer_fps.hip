@@ -193,6 +193,97 @@ __global__ __launch_bounds__(THREADS) void fps_reg_kernel(const float* __restric
     }
 }
 
+// ---- the levels form: Pool_layer's farthest-point sampler (gcn3d.Pool_layer(sampler="fps")) -------------------------------------
+// The pick chain of fps_reg_kernel with ONE rule added: a picked row is never picked again.  A picked row's distance-to-set is set
+// to -1 and the key's value word is compared SIGNED, so such a row ranks below every unpicked row (whose distance is >= +0) in the
+// same single 64-bit compare; among unpicked rows the order is fps_reg_kernel's (largest value, then lowest index).  On a cloud
+// whose plain picks are all distinct the picks are therefore the plain kernel's, bit for bit; on a tiled cloud with fewer distinct
+// points than picks the remaining picks are the lowest-index unpicked rows.  The picked coordinates -- in LDS already -- are written
+// as the level-1 cloud v1 (B,N1,3) in pick order and its first N2 rows as v2 (B,N2,3): farthest-point picks are nested, so the
+// sampler run on v1 returns 0 .. N2-1.
+__device__ __forceinline__ long long dpp_max_i64(long long k, const int ctrl_sel) {
+    unsigned lo = (unsigned)k, hi = (unsigned)((unsigned long long)k >> 32), olo, ohi;
+    switch (ctrl_sel) {                                     // dpp_ctrl must be an immediate
+        case 0: olo = __builtin_amdgcn_update_dpp(lo, lo, 0xB1, 0xF, 0xF, false);      // quad_perm [1,0,3,2]
+                ohi = __builtin_amdgcn_update_dpp(hi, hi, 0xB1, 0xF, 0xF, false); break;
+        case 1: olo = __builtin_amdgcn_update_dpp(lo, lo, 0x4E, 0xF, 0xF, false);      // quad_perm [2,3,0,1]
+                ohi = __builtin_amdgcn_update_dpp(hi, hi, 0x4E, 0xF, 0xF, false); break;
+        case 2: olo = __builtin_amdgcn_update_dpp(lo, lo, 0x141, 0xF, 0xF, false);     // row_half_mirror
+                ohi = __builtin_amdgcn_update_dpp(hi, hi, 0x141, 0xF, 0xF, false); break;
+        default: olo = __builtin_amdgcn_update_dpp(lo, lo, 0x140, 0xF, 0xF, false);    // row_mirror
+                 ohi = __builtin_amdgcn_update_dpp(hi, hi, 0x140, 0xF, 0xF, false); break;
+    }
+    const long long o = (long long)(((unsigned long long)ohi << 32) | olo);
+    return o > k ? o : k;
+}
+
+template <int THREADS, int PPT>
+__global__ __launch_bounds__(THREADS) void fps_levels_kernel(const float* __restrict__ xyz, int N, int N1, int N2,
+                                                             int32_t* __restrict__ sel1, float* __restrict__ v1,
+                                                             float* __restrict__ v2) {
+    constexpr int W = THREADS / HSP_WAVE;
+    extern __shared__ __attribute__((aligned(16))) float s_xyz[];          // N * 3
+    __shared__ long long slot[2][W];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const float* p = xyz + (size_t)b * N * 3;
+    for (int e = tid; e < N * 3; e += THREADS) s_xyz[e] = p[e];
+    float px[PPT], py[PPT], pz[PPT], dt[PPT];
+#pragma unroll
+    for (int k = 0; k < PPT; ++k) {
+        const int j = tid + k * THREADS;
+        const bool in = j < N;
+        px[k] = in ? p[j * 3] : 0.f;
+        py[k] = in ? p[j * 3 + 1] : 0.f;
+        pz[k] = in ? p[j * 3 + 2] : 0.f;
+        dt[k] = INFINITY;
+    }
+    __syncthreads();
+    int cur = 0;
+    for (int s = 0; s < N1; ++s) {
+        const float cx = s_xyz[cur * 3], cy = s_xyz[cur * 3 + 1], cz = s_xyz[cur * 3 + 2];
+        if (tid < 3) {                                      // the pick and its coordinates (lane e: coordinate e)
+            const float c = tid == 0 ? cx : tid == 1 ? cy : cz;
+            if (tid == 0) sel1[(size_t)b * N1 + s] = cur;
+            v1[((size_t)b * N1 + s) * 3 + tid] = c;
+            if (s < N2) v2[((size_t)b * N2 + s) * 3 + tid] = c;
+        }
+        long long key = LLONG_MIN;                          // (value bits, signed) << 32 | ~index
+#pragma unroll
+        for (int k = 0; k < PPT; ++k) {
+            const int j = tid + k * THREADS;
+            const float dx = sub_rn(px[k], cx), dy = sub_rn(py[k], cy), dz = sub_rn(pz[k], cz);
+            const float d = sqrtf(add_rn(add_rn(mul_rn(dx, dx), mul_rn(dy, dy)), mul_rn(dz, dz)));   // as fps_reg_kernel
+            const float v = j == cur ? -1.f : fminf(dt[k], d);           // picked: -1 for good (fminf(-1, d) == -1)
+            dt[k] = v;
+            const long long kk = (long long)(((unsigned long long)__float_as_uint(v) << 32) | (unsigned)(~j));
+            if (j < N && kk > key) key = kk;
+        }
+        key = dpp_max_i64(key, 0);
+        key = dpp_max_i64(key, 1);
+        key = dpp_max_i64(key, 2);
+        key = dpp_max_i64(key, 3);                          // every lane holds its 16-lane row's best
+        long long wk = LLONG_MIN;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const unsigned lo = __builtin_amdgcn_readlane((unsigned)key, r * 16);
+            const unsigned hi = __builtin_amdgcn_readlane((unsigned)((unsigned long long)key >> 32), r * 16);
+            const long long rk = (long long)(((unsigned long long)hi << 32) | lo);
+            wk = rk > wk ? rk : wk;
+        }
+        if (W > 1) {
+            if (lane == 0) slot[s & 1][wv] = wk;
+            __syncthreads();
+#pragma unroll
+            for (int w = 0; w < W; ++w) {
+                const long long o = slot[s & 1][w];
+                wk = o > wk ? o : wk;
+            }
+        }
+        cur = (int)(~(unsigned)wk);
+    }
+}
+
 // any N: one 1024-thread workgroup per cloud; dist-to-set lives in a global workspace (L2 resident);
 // each round = distance update + workgroup arg-max (max value, then lowest index).
 #define FPS_THREADS 1024
@@ -323,4 +414,30 @@ extern "C" int hsp_fps_f64(const double* xyz, int B, int N, int n_samples, int32
     hipLaunchKernelGGL(fps_generic_kernel<double>, dim3(B), dim3(FPS_THREADS), 0, as_stream(stream), xyz, N, n_samples,
                        sel, reinterpret_cast<double*>(ws));
     return check_launch();
+}
+
+extern "C" int hsp_fps_levels_f32(const float* xyz, int B, int N0, int N1, int N2, int32_t* sel1, float* v1, float* v2,
+                                  hspStream_t stream) {
+    if (!xyz || !sel1 || !v1 || B <= 0 || N0 <= 0 || N1 <= 0 || N1 > N0 || N2 < 0 || N2 > N1 || (N2 > 0 && !v2))
+        return HSP_ERR_BAD_ARG;
+    if (N0 > 12288) return HSP_ERR_UNSUPPORTED;               // beyond the register-resident kernel (nothing launched)
+    hipStream_t st = as_stream(stream);
+    const size_t lds = (size_t)N0 * 3 * sizeof(float);
+#define FPS_LV(THREADS, PPT)                                                                                           \
+    do {                                                                                                               \
+        auto kern = fps_levels_kernel<THREADS, PPT>;                                                                   \
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                                        \
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                      \
+        if (e != hipSuccess) { set_last_hip_error(e); return HSP_ERR_LAUNCH; }                                         \
+        hipLaunchKernelGGL(kern, dim3(B), dim3(THREADS), lds, st, xyz, N0, N1, N2, sel1, v1, v2);                      \
+        return check_launch();                                                                                         \
+    } while (0)
+    if (N0 <= 64 * 2) FPS_LV(64, 2);                           // (the shapes of hsp_fps_f32's register kernel)
+    if (N0 <= 256 * 2) FPS_LV(256, 2);
+    if (N0 <= 256 * 5) FPS_LV(256, 5);
+    if (N0 <= 256 * 8) FPS_LV(256, 8);
+    if (N0 <= 256 * 16) FPS_LV(256, 16);
+    if (N0 <= 1024 * 8) FPS_LV(1024, 8);
+    FPS_LV(1024, 12);
+#undef FPS_LV
 }

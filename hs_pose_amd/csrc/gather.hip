@@ -49,8 +49,8 @@ __device__ __forceinline__ void gather_max_rows(const FT* __restrict__ fb, const
 template <typename FT>
 __global__ __launch_bounds__(256) void gather_max_fwd_kernel(const FT* __restrict__ feat,
                                                              const int32_t* __restrict__ idx,
-                                                             const int32_t* __restrict__ qsel, int B, int Nsrc,
-                                                             int Nidx, int Nq, int k, int kstride, int C,
+                                                             const int32_t* __restrict__ qsel, int qstride, int B,
+                                                             int Nsrc, int Nidx, int Nq, int k, int kstride, int C,
                                                              FT* __restrict__ out,
                                                              uint8_t* __restrict__ argmax,
                                                              const float* __restrict__ xyz = nullptr,
@@ -62,7 +62,7 @@ __global__ __launch_bounds__(256) void gather_max_fwd_kernel(const FT* __restric
         const long long row = e / cq;            // b*Nq + q
         const int q = (int)(row % Nq);
         const int b = (int)(row / Nq);
-        const int qi = qsel ? qsel[q] : q;
+        const int qi = qsel ? qsel[(size_t)b * qstride + q] : q;      // qstride 0: one list for the batch; Nq: a list per cloud
         if (xyz_sel && g < 3)                    // Pool_layer: the kept points' coordinates ride along (vertices[:, sample_idx], gcn3d.py:244)
             xyz_sel[row * 3 + g] = xyz[((size_t)b * Nidx + qi) * 3 + g];
         const int32_t* nb = idx + ((size_t)b * Nidx + qi) * kstride;
@@ -487,7 +487,7 @@ __global__ __launch_bounds__(256) void concat_rows_kernel(ConcatDesc d, int B, i
 // scatter-add of the pooled gradient to the winning source rows (grad_feat pre-zeroed)
 __global__ __launch_bounds__(256) void gather_max_bwd_kernel(const float* __restrict__ gout, int gbcast,
                                                              const int32_t* __restrict__ idx,
-                                                             const int32_t* __restrict__ qsel,
+                                                             const int32_t* __restrict__ qsel, int qstride,
                                                              const uint8_t* __restrict__ argmax, int B, int Nsrc,
                                                              int Nidx, int Nq, int kstride, int C,
                                                              float* __restrict__ gfeat) {
@@ -498,7 +498,7 @@ __global__ __launch_bounds__(256) void gather_max_bwd_kernel(const float* __rest
         const long long row = e / cq;
         const int q = (int)(row % Nq);
         const int b = (int)(row / Nq);
-        const int qi = qsel ? qsel[q] : q;
+        const int qi = qsel ? qsel[(size_t)b * qstride + q] : q;
         const int32_t* nb = idx + ((size_t)b * Nidx + qi) * kstride;
         const float4 gv = *reinterpret_cast<const float4*>(gout + (gbcast ? (size_t)b * C : (size_t)row * C) + (g << 2));
         const uchar4 am = *reinterpret_cast<const uchar4*>(argmax + row * C + (g << 2));
@@ -527,7 +527,7 @@ __global__ __launch_bounds__(NT) void scatter_tile_bwd_kernel(const FT* __restri
                                                                int gstride,
                                                                int gbcast, const int32_t* __restrict__ idx,
                                                                int idx_shared, const int32_t* __restrict__ qsel,
-                                                               const uint8_t* __restrict__ argmax, int Nsrc,
+                                                               int qstride, const uint8_t* __restrict__ argmax, int Nsrc,
                                                                int Nidx, int Nq, int kstride, int C,
                                                                FT* __restrict__ gfeat, int accumulate,
                                                                const FT* __restrict__ extra) {
@@ -584,7 +584,7 @@ __global__ __launch_bounds__(NT) void scatter_tile_bwd_kernel(const FT* __restri
             for (int u = 0; u < FL; ++u) {
                 const int q = min(q0 + u * PL, Nq - 1);
                 const size_t row = (size_t)b * Nq + q;
-                const int qi = qsel ? qsel[q] : q;
+                const int qi = qsel ? qsel[(size_t)b * qstride + q] : q;
                 nb[u] = idx + ((size_t)b * Nidx + qi) * kstride;
                 am[u] = *reinterpret_cast<const uchar4*>(argmax + row * C + j);
                 gv[u] = gbcast ? make_float4(0.f, 0.f, 0.f, 0.f) : Feat<FT>::ld4(gout + row * gstride + j);
@@ -707,8 +707,8 @@ extern "C" int hsp_scatter_tile_plan(int B, int Nsrc, int C, int* threads) {
 
 template <int MODE, typename FT>
 static int launch_scatter_tile(int tc, const FT* gout, const float* gbc, int gstride, int gbcast, const int32_t* idx,
-                               int idx_shared, const int32_t* qsel, const uint8_t* argmax, int B, int Nsrc, int Nidx, int Nq,
-                               int kstride, int C, FT* gfeat, int accumulate, const FT* extra, hipStream_t st) {
+                               int idx_shared, const int32_t* qsel, int qstride, const uint8_t* argmax, int B, int Nsrc, int Nidx,
+                               int Nq, int kstride, int C, FT* gfeat, int accumulate, const FT* extra, hipStream_t st) {
     const size_t lds = (size_t)Nsrc * tc * 4;
     dim3 grid(C / tc, B);
     const int nt = scatter_tile_threads(tc, B, C);
@@ -720,8 +720,8 @@ static int launch_scatter_tile(int tc, const FT* gout, const float* gbc, int gst
                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);              \
             if (e != hipSuccess) { set_last_hip_error(e); return HSP_ERR_LAUNCH; }                                 \
         }                                                                                                          \
-        hipLaunchKernelGGL(kern, grid, dim3(NT_), lds, st, gout, gbc, gstride, gbcast, idx, idx_shared, qsel, argmax, Nsrc, \
-                           Nidx, Nq, kstride, C, gfeat, accumulate, extra);                                        \
+        hipLaunchKernelGGL(kern, grid, dim3(NT_), lds, st, gout, gbc, gstride, gbcast, idx, idx_shared, qsel, qstride, argmax, \
+                           Nsrc, Nidx, Nq, kstride, C, gfeat, accumulate, extra);                                  \
     }
 #define SC_LAUNCH(TC)                                                                                              \
     {                                                                                                              \
@@ -924,44 +924,65 @@ __global__ __launch_bounds__(256) void points_max_bwd_kernel(const float* __rest
 
 using namespace hsp;
 
+// qsel_stride: 0 -- qsel (Nq) is one list shared by the batch; >= Nq -- cloud b reads qsel[b * qsel_stride + q]
+static bool qsel_ok(const int32_t* qsel, int qsel_stride, int Nq) {
+    return qsel_stride == 0 || (qsel && qsel_stride >= Nq);
+}
+
 template <typename FT>
-static int gather_max_fwd_impl(const FT* feat, const int32_t* idx, const int32_t* qsel, int B, int Nsrc,
+static int gather_max_fwd_impl(const FT* feat, const int32_t* idx, const int32_t* qsel, int qsel_stride, int B, int Nsrc,
                                int Nidx, int Nq, int k, int kstride, int C, FT* out, uint8_t* argmax,
                                hspStream_t stream) {
     if (!feat || !idx || !out || !argmax || B <= 0 || Nsrc <= 0 || Nidx <= 0 || Nq <= 0 || k <= 0 || kstride < k || C <= 0)
         return HSP_ERR_BAD_ARG;
-    if (!qsel && Nq != Nidx) return HSP_ERR_BAD_ARG;
+    if ((!qsel && Nq != Nidx) || !qsel_ok(qsel, qsel_stride, Nq)) return HSP_ERR_BAD_ARG;
     if ((C & 3) || k > 255) return HSP_ERR_UNSUPPORTED;
     const long long total = (long long)B * Nq * (C >> 2);
     hipLaunchKernelGGL(gather_max_fwd_kernel<FT>, dim3(stream_grid(total)), dim3(256), 0, as_stream(stream), feat, idx,
-                       qsel, B, Nsrc, Nidx, Nq, k, kstride, C, out, argmax);
+                       qsel, qsel_stride, B, Nsrc, Nidx, Nq, k, kstride, C, out, argmax);
     return check_launch();
+}
+extern "C" int hsp_gather_max_fwd_sel(const float* feat, const int32_t* idx, const int32_t* qsel, int qsel_stride, int B, int Nsrc,
+                                      int Nidx, int Nq, int k, int kstride, int C, float* out, uint8_t* argmax,
+                                      hspStream_t stream) {
+    return gather_max_fwd_impl<float>(feat, idx, qsel, qsel_stride, B, Nsrc, Nidx, Nq, k, kstride, C, out, argmax, stream);
+}
+extern "C" int hsp_gather_max_fwd_sel_bf16(const hsp_bf16_t* feat, const int32_t* idx, const int32_t* qsel, int qsel_stride, int B,
+                                           int Nsrc, int Nidx, int Nq, int k, int kstride, int C, hsp_bf16_t* out, uint8_t* argmax,
+                                           hspStream_t stream) {
+    return gather_max_fwd_impl<bf16_t>(feat, idx, qsel, qsel_stride, B, Nsrc, Nidx, Nq, k, kstride, C, out, argmax, stream);
 }
 extern "C" int hsp_gather_max_fwd(const float* feat, const int32_t* idx, const int32_t* qsel, int B, int Nsrc,
                                   int Nidx, int Nq, int k, int kstride, int C, float* out, uint8_t* argmax,
                                   hspStream_t stream) {
-    return gather_max_fwd_impl<float>(feat, idx, qsel, B, Nsrc, Nidx, Nq, k, kstride, C, out, argmax, stream);
+    return hsp_gather_max_fwd_sel(feat, idx, qsel, 0, B, Nsrc, Nidx, Nq, k, kstride, C, out, argmax, stream);
 }
 extern "C" int hsp_gather_max_fwd_bf16(const hsp_bf16_t* feat, const int32_t* idx, const int32_t* qsel, int B, int Nsrc,
                                        int Nidx, int Nq, int k, int kstride, int C, hsp_bf16_t* out, uint8_t* argmax,
                                        hspStream_t stream) {
-    return gather_max_fwd_impl<bf16_t>(feat, idx, qsel, B, Nsrc, Nidx, Nq, k, kstride, C, out, argmax, stream);
+    return hsp_gather_max_fwd_sel_bf16(feat, idx, qsel, 0, B, Nsrc, Nidx, Nq, k, kstride, C, out, argmax, stream);
 }
 
 /* Pool_layer in one launch (gcn3d.py:236-245): max over the k listed neighbours of the kept rows qsel + the kept rows' coordinates */
-extern "C" int hsp_pool_fwd(const float* feat, const float* xyz, const int32_t* idx, const int32_t* qsel, int B, int N, int Nq,
-                            int k, int kstride, int C, float* out, uint8_t* argmax, float* xyz_sel, hspStream_t stream) {
+extern "C" int hsp_pool_fwd_sel(const float* feat, const float* xyz, const int32_t* idx, const int32_t* qsel, int qsel_stride, int B,
+                                int N, int Nq, int k, int kstride, int C, float* out, uint8_t* argmax, float* xyz_sel,
+                                hspStream_t stream) {
     if (!feat || !xyz || !idx || !qsel || !out || !argmax || !xyz_sel || B <= 0 || N <= 0 || Nq <= 0 || k <= 0 || kstride < k || C < 12)
         return HSP_ERR_BAD_ARG;
+    if (!qsel_ok(qsel, qsel_stride, Nq)) return HSP_ERR_BAD_ARG;
     if ((C & 3) || k > 255) return HSP_ERR_UNSUPPORTED;
     const long long total = (long long)B * Nq * (C >> 2);
-    hipLaunchKernelGGL(gather_max_fwd_kernel<float>, dim3(stream_grid(total)), dim3(256), 0, as_stream(stream), feat, idx, qsel, B,
-                       N, N, Nq, k, kstride, C, out, argmax, xyz, xyz_sel);
+    hipLaunchKernelGGL(gather_max_fwd_kernel<float>, dim3(stream_grid(total)), dim3(256), 0, as_stream(stream), feat, idx, qsel,
+                       qsel_stride, B, N, N, Nq, k, kstride, C, out, argmax, xyz, xyz_sel);
     return check_launch();
+}
+extern "C" int hsp_pool_fwd(const float* feat, const float* xyz, const int32_t* idx, const int32_t* qsel, int B, int N, int Nq,
+                            int k, int kstride, int C, float* out, uint8_t* argmax, float* xyz_sel, hspStream_t stream) {
+    return hsp_pool_fwd_sel(feat, xyz, idx, qsel, 0, B, N, Nq, k, kstride, C, out, argmax, xyz_sel, stream);
 }
 
 template <typename FT>
-static int gather_max_bwd_impl(const void* grad_out, int grad_bcast, const int32_t* idx, const int32_t* qsel,
+static int gather_max_bwd_impl(const void* grad_out, int grad_bcast, const int32_t* idx, const int32_t* qsel, int qsel_stride,
                                const uint8_t* argmax, int B, int Nsrc, int Nidx, int Nq, int kstride, int C,
                                FT* grad_feat, int accumulate, const FT* extra, hspStream_t stream) {
     if (grad_bcast == 2) {
@@ -976,14 +997,14 @@ static int gather_max_bwd_impl(const void* grad_out, int grad_bcast, const int32
     }
     if (!grad_out || !idx || !argmax || !grad_feat || B <= 0 || Nsrc <= 0 || Nidx <= 0 || Nq <= 0 || kstride <= 0 || C <= 0)
         return HSP_ERR_BAD_ARG;
-    if (!qsel && Nq != Nidx) return HSP_ERR_BAD_ARG;
+    if ((!qsel && Nq != Nidx) || !qsel_ok(qsel, qsel_stride, Nq)) return HSP_ERR_BAD_ARG;
     if (C & 3) return HSP_ERR_UNSUPPORTED;
     hipStream_t st = as_stream(stream);
     // the per-query gradient has the feature type; the broadcast row (ORL: d fg / N per cloud) is always fp32
     if (const int tc = pick_scatter_cols(Nsrc, C))
         return launch_scatter_tile<0, FT>(tc, grad_bcast ? nullptr : reinterpret_cast<const FT*>(grad_out),
                                           grad_bcast ? reinterpret_cast<const float*>(grad_out) : nullptr, C, grad_bcast, idx, 0,
-                                          qsel, argmax, B, Nsrc, Nidx, Nq, kstride, C, grad_feat, accumulate, extra, st);
+                                          qsel, qsel_stride, argmax, B, Nsrc, Nidx, Nq, kstride, C, grad_feat, accumulate, extra, st);
     if constexpr (sizeof(FT) == 4) {
         if (extra) return HSP_ERR_UNSUPPORTED;             // the global-atomic fallback has no fused add
         if (!accumulate) {
@@ -992,22 +1013,35 @@ static int gather_max_bwd_impl(const void* grad_out, int grad_bcast, const int32
         }
         const long long total = (long long)B * Nq * (C >> 2);
         hipLaunchKernelGGL(gather_max_bwd_kernel, dim3(stream_grid(total)), dim3(256), 0, st,
-                           reinterpret_cast<const float*>(grad_out), grad_bcast, idx, qsel, argmax, B, Nsrc, Nidx, Nq, kstride, C,
-                           grad_feat);
+                           reinterpret_cast<const float*>(grad_out), grad_bcast, idx, qsel, qsel_stride, argmax, B, Nsrc, Nidx, Nq,
+                           kstride, C, grad_feat);
         return check_launch();
     }
     return HSP_ERR_UNSUPPORTED;                            // bf16: the LDS tile form only (Nsrc * 16 bytes <= 144 KiB)
 }
+extern "C" int hsp_gather_max_bwd_sel(const float* grad_out, int grad_bcast, const int32_t* idx, const int32_t* qsel, int qsel_stride,
+                                      const uint8_t* argmax, int B, int Nsrc, int Nidx, int Nq, int kstride, int C,
+                                      float* grad_feat, int accumulate, const float* extra, hspStream_t stream) {
+    return gather_max_bwd_impl<float>(grad_out, grad_bcast, idx, qsel, qsel_stride, argmax, B, Nsrc, Nidx, Nq, kstride, C, grad_feat,
+                                      accumulate, extra, stream);
+}
+extern "C" int hsp_gather_max_bwd_sel_bf16(const void* grad_out, int grad_bcast, const int32_t* idx, const int32_t* qsel,
+                                           int qsel_stride, const uint8_t* argmax, int B, int Nsrc, int Nidx, int Nq, int kstride,
+                                           int C, hsp_bf16_t* grad_feat, int accumulate, const hsp_bf16_t* extra,
+                                           hspStream_t stream) {
+    return gather_max_bwd_impl<bf16_t>(grad_out, grad_bcast, idx, qsel, qsel_stride, argmax, B, Nsrc, Nidx, Nq, kstride, C, grad_feat,
+                                       accumulate, extra, stream);
+}
 extern "C" int hsp_gather_max_bwd(const float* grad_out, int grad_bcast, const int32_t* idx, const int32_t* qsel,
                                   const uint8_t* argmax, int B, int Nsrc, int Nidx, int Nq, int kstride, int C,
                                   float* grad_feat, int accumulate, const float* extra, hspStream_t stream) {
-    return gather_max_bwd_impl<float>(grad_out, grad_bcast, idx, qsel, argmax, B, Nsrc, Nidx, Nq, kstride, C, grad_feat,
-                                      accumulate, extra, stream);
+    return hsp_gather_max_bwd_sel(grad_out, grad_bcast, idx, qsel, 0, argmax, B, Nsrc, Nidx, Nq, kstride, C, grad_feat, accumulate,
+                                  extra, stream);
 }
 extern "C" int hsp_gather_max_bwd_bf16(const void* grad_out, int grad_bcast, const int32_t* idx, const int32_t* qsel,
                                        const uint8_t* argmax, int B, int Nsrc, int Nidx, int Nq, int kstride, int C,
                                        hsp_bf16_t* grad_feat, int accumulate, const hsp_bf16_t* extra, hspStream_t stream) {
-    return gather_max_bwd_impl<bf16_t>(grad_out, grad_bcast, idx, qsel, argmax, B, Nsrc, Nidx, Nq, kstride, C, grad_feat,
+    return hsp_gather_max_bwd_sel_bf16(grad_out, grad_bcast, idx, qsel, 0, argmax, B, Nsrc, Nidx, Nq, kstride, C, grad_feat,
                                        accumulate, extra, stream);
 }
 
@@ -1034,7 +1068,7 @@ extern "C" int hsp_gather_rows_bwd(const float* grad_out, int grad_stride, const
     hipStream_t st = as_stream(stream);
     if ((C & 3) == 0 && (grad_stride & 1) == 0 && (reinterpret_cast<uintptr_t>(grad_out) & 7) == 0)
         if (const int tc = pick_scatter_cols(Nsrc, C))
-            return launch_scatter_tile<1, float>(tc, grad_out, nullptr, grad_stride, 0, idx, idx_shared, nullptr, nullptr, B,
+            return launch_scatter_tile<1, float>(tc, grad_out, nullptr, grad_stride, 0, idx, idx_shared, nullptr, 0, nullptr, B,
                                                  Nsrc, Nq, Nq, 1, C, grad_feat, 0, nullptr, st);
     hipError_t e = hipMemsetAsync(grad_feat, 0, (size_t)B * Nsrc * C * sizeof(float), st);
     if (e != hipSuccess) { set_last_hip_error(e); return HSP_ERR_LAUNCH; }

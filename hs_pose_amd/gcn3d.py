@@ -23,6 +23,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops
+from .config import FLAGS
 
 # ------------------------------------------------------------------------------------------------
 # per-forward xyz-KNN memo
@@ -52,18 +53,65 @@ def knn_scope():
 _levels = None          # id(level-0 vertices) / id(v1) -> dict(vertices, sel, v_pool); "up": [up1, up2]
 
 
-def prefetch_levels(vertices, k, pool_k=None, rates=(4, 4)):
+SAMPLERS = ("random", "fps")
+
+
+def resolve_sampler(sampler):
+    """the sampler a Pool_layer uses NOW: its own choice, or (None) config.FLAGS.pool_sampler -- read at forward time"""
+    s = FLAGS.pool_sampler if sampler is None else sampler
+    if s not in SAMPLERS:
+        raise ValueError(f"pool sampler: expected one of {SAMPLERS}, got {s!r}")
+    return s
+
+
+def module_sampler(module):
+    """'random' / 'fps': the sampler every Pool_layer of ``module`` uses now (hs_pose_amd.graph decides by it whether a replay
+    needs host-drawn indices); a mix of the two under one captured graph is refused."""
+    found = {resolve_sampler(m.sampler) for m in module.modules() if isinstance(m, Pool_layer)}
+    if len(found) > 1:
+        raise ValueError("Pool_layers of one captured module use different samplers")
+    return found.pop() if found else "random"
+
+
+def _prefetch_levels_fps(vertices, k, pool_k):
+    """prefetch_levels under the 'fps' sampler: ONE launch picks each cloud's level-1 rows and writes both coarse clouds
+    (ops.fps_levels; farthest-point picks are nested, so level 2 keeps rows 0 .. n2-1 of level 1 -- the shared-list pooling path),
+    then the levels' neighbour searches and the up-sampling maps, by the same kernels the layers would call themselves
+    (ops.knn_xyz / ops.nn1).  No host generator, no pool_index_feed."""
+    global _levels
+    n0 = vertices.shape[1]
+    n1 = int(n0 / 4)
+    n2 = int(n1 / 4)
+    k1, k2 = min(k, n1 // 8), min(k, n2 // 8)
+    if vertices.shape[2] != 3 or n2 < 1 or k1 < 1 or k2 < 1 or k1 + 1 > n1 or k2 + 1 > n2 or n0 > ops.FPS_LEVELS_MAX_N:
+        return None                                          # (the layers then sample and search on their own)
+    sel1, v1, v2 = ops.fps_levels(vertices, n1, n2)
+    _xyz_knn(v1, k1)                                         # with Pool_layer's short list where k1 > POOL_K (one search, two lists)
+    if pool_k != POOL_K or k1 <= POOL_K:
+        _xyz_knn(v1, pool_k)
+    _xyz_knn(v2, k2)
+    _levels = {id(vertices): (vertices, sel1, v1), id(v1): (v1, torch.arange(n2, dtype=torch.int32, device=vertices.device), v2),
+               "up": (ops.nn1(vertices, v1), ops.nn1(vertices, v2))}
+    return _levels["up"]
+
+
+def prefetch_levels(vertices, k, pool_k=None, rates=(4, 4), samplers=(None, None)):
     """FaceRecon's two Pool_layers keep rows that are drawn on the HOST (torch.randperm, gcn3d.py:243) and depend on nothing the
     network computes, so everything the forward will ask of the two coarse clouds -- their vertices, their neighbour lists, the
     nearest-point maps of the up-sampling -- can be computed from the input cloud at once (ops.geometry_levels).  Draws (or takes
     from the pool_index_feed) both index sets in the reference's order, fills the knn_scope memo for the two levels and remembers
     the kept rows for the Pool_layers.  Returns (up1, up2) or None when the shapes are not the fused kernel's (nothing is consumed
-    then, and the layers do their own searches as before).  Call inside knn_scope()."""
+    then, and the layers do their own searches as before).  Call inside knn_scope().  ``samplers``: the two Pool_layers' samplers
+    (None: config.FLAGS.pool_sampler); both 'fps': the rows are picked on the device, per cloud (_prefetch_levels_fps); one of each:
+    no prefetch."""
     global _levels
     _levels = None
     if _knn_memo is None or vertices.dtype != torch.float32 or vertices.requires_grad or not vertices.is_cuda:
         return None
     pool_k = POOL_K if pool_k is None else pool_k
+    how = {resolve_sampler(s_) for s_ in samplers}
+    if how != {"random"}:
+        return _prefetch_levels_fps(vertices, k, pool_k) if how == {"fps"} and tuple(rates) == (4, 4) else None
     n0 = vertices.shape[1]
     n1 = int(n0 / 4)
     n2 = int(n1 / 4)
@@ -288,12 +336,20 @@ class HS_layer(nn.Module):
 class Pool_layer(nn.Module):
     """reference gcn3d.py:220-246: max over the 4 nearest (rank 0 dropped), then ONE torch.randperm
     draw on the CPU default generator shared by the whole batch (same RNG consumption as the
-    reference, so fixed-seed runs pick the same points)."""
+    reference, so fixed-seed runs pick the same points).
 
-    def __init__(self, pooling_rate: int = 4, neighbor_num: int = 4):
+    ``sampler``: 'random' -- the above --, 'fps' -- every cloud keeps the ``int(N / pooling_rate)`` rows that farthest-point
+    sampling picks on its own ``vertices[b]`` (ops.fps_levels: the contract of ops.fps, and a picked row is never picked again),
+    computed on the device: no host generator, no pool_index_feed, the output a function of the cloud alone --, or None: follow
+    config.FLAGS.pool_sampler (default 'random'), read at every forward."""
+
+    def __init__(self, pooling_rate: int = 4, neighbor_num: int = 4, sampler=None):
         super().__init__()
         self.pooling_rate = pooling_rate
         self.neighbor_num = neighbor_num
+        if sampler is not None:
+            resolve_sampler(sampler)
+        self.sampler = sampler
 
     def forward(self, vertices: "(bs, vertice_num, 3)", feature_map: "(bs, vertice_num, channel_num)"):
         """-> vertices_pool (bs, pool_num, 3), feature_map_pool (bs, pool_num, channel_num)"""
@@ -301,7 +357,7 @@ class Pool_layer(nn.Module):
         neighbor_index = _xyz_knn(vertices, self.neighbor_num)
         pool_num = int(vertice_num / self.pooling_rate)
         pre = _levels.get(id(vertices)) if _levels is not None else None
-        if pre is not None and pre[0] is vertices and pre[1].numel() == pool_num and self.pooling_rate == 4:
+        if pre is not None and pre[0] is vertices and pre[1].shape[-1] == pool_num and self.pooling_rate == 4:
             # the kept rows were drawn, and the pooled vertices gathered, by prefetch_levels: only the features are pooled here
             # (the SAME vertices tensor is handed on, so the next level finds its prefetched neighbour lists)
             _, sel, v_pool = pre
@@ -310,6 +366,16 @@ class Pool_layer(nn.Module):
             else:
                 feature_map_pool = ops.gather_max(feature_map, neighbor_index, self.neighbor_num, qsel=sel)
             return v_pool, feature_map_pool
+        if resolve_sampler(self.sampler) == "fps":
+            # this cloud's own farthest-point picks (per cloud: a (bs, pool_num) selector) and their coordinates
+            sel, vertices_pool, _ = ops.fps_levels(vertices, pool_num, 0)
+            if vertices.requires_grad:                       # (the sampler's copy of the coordinates carries no gradient)
+                vertices_pool = ops.gather_rows(vertices, sel)
+            if feature_map.dtype == torch.float32 and feature_map.shape[2] >= 12 and not vertices.requires_grad:
+                feature_map_pool, _ = ops.pool_layer(feature_map, vertices, neighbor_index, sel, self.neighbor_num)
+            else:
+                feature_map_pool = ops.gather_max(feature_map, neighbor_index, self.neighbor_num, qsel=sel)
+            return vertices_pool, feature_map_pool
         if _pool_feed is not None:
             sel = next(_pool_feed)
             assert sel.numel() == pool_num and sel.dtype == torch.int32

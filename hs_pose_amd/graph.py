@@ -13,8 +13,11 @@
 Static shapes, static input / gradient buffers.  The only host work of the reference's forward -- the two
 ``torch.randperm`` draws of the Pool_layers on the CPU default generator (gcn3d.py:243) -- happens BEFORE each replay,
 in the same order and on the same generator as the reference, and is uploaded into static index buffers the captured
-kernels read.
+kernels read.  Under the 'fps' pool sampler (config.FLAGS.pool_sampler / gcn3d.Pool_layer(sampler=...), as it stands when the
+object is built) the kept rows are picked INSIDE the captured graph from the clouds in the static input buffers: no draw, no
+upload and no index buffers, a replay begins with no host work at all.
 """
+import contextlib
 import os
 
 import torch
@@ -48,11 +51,24 @@ def alloc_pool_indices(n_points, device):
     return views
 
 
+def pool_index_buffers(module, n_points, device):
+    """the static Pool_layer index buffers a captured ``module`` needs: ``alloc_pool_indices`` under the 'random' sampler, None
+    under 'fps' (the rows are picked inside the graph)"""
+    return None if gcn3d.module_sampler(module) == "fps" else alloc_pool_indices(n_points, device)
+
+
+def pool_feed(bufs):
+    """the scope a captured body runs its forward in: the index buffers fed to the Pool_layers, or nothing to feed (None)"""
+    return gcn3d.pool_index_feed(bufs) if bufs is not None else contextlib.nullcontext()
+
+
 def upload_pool_indices(bufs, n_points):
     """draw the Pool_layer permutations (host generator, reference order) and queue their upload on the current
     stream WITHOUT blocking the host: the copy comes from a ring of pinned staging buffers (hs_pose_amd/staging.py),
     stream-ordered after the previous replay and before the next, so the host can enqueue step i+1 while step i is still
     running.  Buffers made by ``alloc_pool_indices`` travel in ONE copy (a copy kernel per pool cost ~5 us of every step)."""
+    if bufs is None:                                     # 'fps' sampler: nothing is drawn on the host
+        return
     draws = draw_pool_indices(n_points)
     flat = getattr(bufs[0], "_hsp_flat", None)
     if flat is not None:
@@ -110,7 +126,7 @@ class GraphedStep:
         B, N, _ = centred.shape
         self.n_points = N
         dev = centred.device
-        self.pool_idx = alloc_pool_indices(N, dev)
+        self.pool_idx = pool_index_buffers(face_recon, N, dev)
         self.params = [p for p in face_recon.parameters() if p.requires_grad]
         self.feat = None
         self.flat_grad = self.flat_late = self.flat_early = None
@@ -152,7 +168,7 @@ class GraphedStep:
     def _body(self):
         for p in self.params:
             p.grad = None
-        with gcn3d.pool_index_feed(self.pool_idx):
+        with pool_feed(self.pool_idx):
             _, _, feat = self.net(self.centred, self.obj)
         with ops.StepFolds():                           # every p.grad is None: the backward's folds go out in one launch
             feat.backward(self.dfeat)
@@ -166,7 +182,7 @@ class GraphedStep:
         """late = the parameters the cut tensors do not depend on (their gradients are complete after the first part).
         ``flat_grad`` is laid out [late | early] so each part is one contiguous all-reduce."""
         self.net.keep_backward_cut = True
-        with gcn3d.pool_index_feed(self.pool_idx):
+        with pool_feed(self.pool_idx):
             _, _, feat = self.net(self.centred, self.obj)
         cut = list(self.net.backward_cut)
         self.net.backward_cut = None
@@ -181,7 +197,7 @@ class GraphedStep:
     def _body_first(self):
         for p in self.params:
             p.grad = None
-        with gcn3d.pool_index_feed(self.pool_idx):
+        with pool_feed(self.pool_idx):
             _, _, feat = self.net(self.centred, self.obj)
         self.feat = feat.detach()
         cut = list(self.net.backward_cut)
@@ -271,7 +287,7 @@ class GraphedTrainStep:
         self.n_points = N
         dev = PC.device
         self.noise = torch.zeros_like(PC)
-        self.pool_idx = alloc_pool_indices(N, dev)
+        self.pool_idx = pool_index_buffers(network, N, dev)
         self.loss_dict, self.total = None, None
         self._host_draws()
         prev_timer = ops.set_timer(None)
@@ -316,7 +332,7 @@ class GraphedTrainStep:
         params, views = self._params_and_views()
         for p in params:
             p.grad = None
-        with gcn3d.pool_index_feed(self.pool_idx), augment.jitter_noise_feed(self.noise):
+        with pool_feed(self.pool_idx), augment.jitter_noise_feed(self.noise):
             _, ld = self.net(do_loss=True, **self.batch)
         total = self.net.total_loss(ld)                     # (the sum over the four sub-dictionaries, engine/train.py:84-90)
         with ops.StepFolds():
@@ -373,7 +389,7 @@ class GraphedInference:
         n, N, _ = PC.shape
         self.n_points = N
         dev = PC.device
-        self.pool_idx = alloc_pool_indices(N, dev)
+        self.pool_idx = pool_index_buffers(network, N, dev)
         if network.training:
             raise RuntimeError("GraphedInference: put the network in eval() mode first")
         self._draw()
@@ -397,7 +413,7 @@ class GraphedInference:
 
     @torch.no_grad()
     def _body(self):
-        with gcn3d.pool_index_feed(self.pool_idx):
+        with pool_feed(self.pool_idx):
             out = self.net(PC=self.PC, obj_id=self.obj_id, mean_shape=self.mean_shape, sym=self.sym)
         self.pred_RT = self._generate_RT([out['p_green_R'], out['p_red_R']], [out['f_green_R'], out['f_red_R']],
                                          out['Pred_T'], mode='vec', sym=self.sym)
@@ -465,7 +481,7 @@ class GraphedNetwork:
         B, N, _ = PC.shape
         self.n_points = N
         dev = PC.device
-        self.pool_idx = alloc_pool_indices(N, dev)
+        self.pool_idx = pool_index_buffers(posenet, N, dev)
         self.params = [p for p in posenet.parameters() if p.requires_grad]
         self._anchor = torch.zeros(1, device=dev, requires_grad=True)
         upload_pool_indices(self.pool_idx, N)
@@ -500,7 +516,7 @@ class GraphedNetwork:
             ops.set_timer(prev_timer)
 
     def _forward(self):
-        with gcn3d.pool_index_feed(self.pool_idx):
+        with pool_feed(self.pool_idx):
             return self.net(self.PC, self.obj_id)
 
     def __call__(self, PC, obj_id):

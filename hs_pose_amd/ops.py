@@ -413,37 +413,62 @@ def rf_conv(xyz, idx, directions, fm, S):
 # neighbourhood max-pool
 # ------------------------------------------------------------------------------------------------
 
+def _qsel_dims(qsel, B, name):
+    """(qsel, Nq, qsel_stride) of a kept-row selector: (Nq,) -- one list shared by the batch, stride 0 -- or (B, Nq) -- a list per
+    cloud, stride Nq (the ``_sel`` entry points of include/hsp.h); any other shape is an error."""
+    qsel = _req(qsel, torch.int32, name)
+    if qsel.dim() == 1 and qsel.numel() > 0:
+        return qsel, qsel.shape[0], 0
+    if qsel.dim() == 2 and qsel.shape[0] == B and qsel.shape[1] > 0:
+        return qsel, qsel.shape[1], qsel.shape[1]
+    raise HspError(f"{name}: expected kept rows of shape (Nq,) -- shared by the batch -- or (B={B}, Nq) -- per cloud --, "
+                   f"got {tuple(qsel.shape)}")
+
+
 class _GatherMax(torch.autograd.Function):
     @staticmethod
     def forward(ctx, feat, idx, qsel, k):
         feat = _reqf(feat, "gather_max.feat")
         idx = _req(idx, torch.int32, "gather_max.idx")
-        if qsel is not None:
-            qsel = _req(qsel, torch.int32, "gather_max.qsel")
         B, Nsrc, C = feat.shape
         Nidx, kstride = idx.shape[1], idx.shape[2]
-        Nq = qsel.numel() if qsel is not None else Nidx
+        Nq, qstride = Nidx, 0
+        if qsel is not None:
+            qsel, Nq, qstride = _qsel_dims(qsel, B, "gather_max.qsel")
         out = torch.empty(B, Nq, C, dtype=feat.dtype, device=feat.device)
         arg = torch.empty(B, Nq, C, dtype=torch.uint8, device=feat.device)
         es = _es(feat)
-        _run("hsp_gather_max_fwd" + _sfx(feat), (_p(feat), _p(idx), _p(qsel), B, Nsrc, Nidx, Nq, k, kstride, C, _p(out),
-                                                 _p(arg), _stream()),
-             key=f"B{B}Ns{Nsrc}Nq{Nq}k{k}C{C}", abytes=B * (es * Nsrc * C + Nq * (4 * k + (es + 1) * C)))
+        key, ab = f"B{B}Ns{Nsrc}Nq{Nq}k{k}C{C}", B * (es * Nsrc * C + Nq * (4 * k + (es + 1) * C))
+        if qstride:                                         # kept rows per cloud
+            _run("hsp_gather_max_fwd_sel" + _sfx(feat), (_p(feat), _p(idx), _p(qsel), qstride, B, Nsrc, Nidx, Nq, k, kstride, C,
+                                                         _p(out), _p(arg), _stream()), key=key + "pc", abytes=ab + 4 * (B - 1) * Nq)
+        else:
+            _run("hsp_gather_max_fwd" + _sfx(feat), (_p(feat), _p(idx), _p(qsel), B, Nsrc, Nidx, Nq, k, kstride, C, _p(out),
+                                                     _p(arg), _stream()), key=key, abytes=ab)
         ctx.save_for_backward(idx, qsel, arg)
-        ctx.dims = (B, Nsrc, Nidx, Nq, kstride, C)
+        ctx.dims = (B, Nsrc, Nidx, Nq, kstride, C, qstride)
         return out
 
     @staticmethod
     def backward(ctx, g):
         idx, qsel, arg = ctx.saved_tensors
-        B, Nsrc, Nidx, Nq, kstride, C = ctx.dims
+        B, Nsrc, Nidx, Nq, kstride, C, qstride = ctx.dims
         g = _reqf(g, "gather_max.grad")
         gfeat = torch.empty(B, Nsrc, C, dtype=g.dtype, device=g.device)
-        es = _es(g)
-        _run("hsp_gather_max_bwd" + _sfx(g), (_p(g), 0, _p(idx), _p(qsel), _p(arg), B, Nsrc, Nidx, Nq, kstride, C, _p(gfeat),
-                                              0, _vp(0), _stream()),
-             key=f"B{B}Ns{Nsrc}Nq{Nq}C{C}", abytes=B * (es * Nsrc * C + Nq * (4 * kstride + (es + 1) * C)))
+        _pool_bwd_raw(g, idx, qsel, qstride, arg, B, Nsrc, Nidx, Nq, kstride, C, gfeat)
         return gfeat, None, None, None
+
+
+def _pool_bwd_raw(g, idx, qsel, qstride, arg, B, Nsrc, Nidx, Nq, kstride, C, gfeat):
+    """the pooling backward of gather_max / pool_layer: gfeat (B,Nsrc,C) overwritten; ``qstride`` as _qsel_dims returns it"""
+    es = _es(g)
+    key, ab = f"B{B}Ns{Nsrc}Nq{Nq}C{C}", B * (es * Nsrc * C + Nq * (4 * kstride + (es + 1) * C))
+    if qstride:
+        _run("hsp_gather_max_bwd_sel" + _sfx(g), (_p(g), 0, _p(idx), _p(qsel), qstride, _p(arg), B, Nsrc, Nidx, Nq, kstride, C,
+                                                  _p(gfeat), 0, _vp(0), _stream()), key=key + "pc", abytes=ab + 4 * (B - 1) * Nq)
+    else:
+        _run("hsp_gather_max_bwd" + _sfx(g), (_p(g), 0, _p(idx), _p(qsel), _p(arg), B, Nsrc, Nidx, Nq, kstride, C, _p(gfeat),
+                                              0, _vp(0), _stream()), key=key, abytes=ab)
 
 
 class _OrlGlobal(torch.autograd.Function):
@@ -513,16 +538,21 @@ class _PoolLayer(torch.autograd.Function):
         feat = _req(feat, torch.float32, "pool.feat")
         xyz = _req(xyz, torch.float32, "pool.xyz")
         idx = _req(idx, torch.int32, "pool.idx")
-        qsel = _req(qsel, torch.int32, "pool.qsel")
         B, N, C = feat.shape
-        Nq, kstride = qsel.numel(), idx.shape[2]
+        qsel, Nq, qstride = _qsel_dims(qsel, B, "pool.qsel")
+        kstride = idx.shape[2]
         out = torch.empty(B, Nq, C, dtype=torch.float32, device=feat.device)
         arg = torch.empty(B, Nq, C, dtype=torch.uint8, device=feat.device)
         vsel = torch.empty(B, Nq, 3, dtype=torch.float32, device=feat.device)
-        _run("hsp_pool_fwd", (_p(feat), _p(xyz), _p(idx), _p(qsel), B, N, Nq, k, kstride, C, _p(out), _p(arg), _p(vsel), _stream()),
-             key=f"B{B}N{N}Nq{Nq}k{k}C{C}", abytes=B * (4 * N * C + Nq * (4 * k + 5 * C + 24)))
+        key, ab = f"B{B}N{N}Nq{Nq}k{k}C{C}", B * (4 * N * C + Nq * (4 * k + 5 * C + 24))
+        if qstride:                                         # kept rows per cloud
+            _run("hsp_pool_fwd_sel", (_p(feat), _p(xyz), _p(idx), _p(qsel), qstride, B, N, Nq, k, kstride, C, _p(out), _p(arg),
+                                      _p(vsel), _stream()), key=key + "pc", abytes=ab + 4 * (B - 1) * Nq)
+        else:
+            _run("hsp_pool_fwd", (_p(feat), _p(xyz), _p(idx), _p(qsel), B, N, Nq, k, kstride, C, _p(out), _p(arg), _p(vsel),
+                                  _stream()), key=key, abytes=ab)
         ctx.save_for_backward(idx, qsel, arg)
-        ctx.dims = (B, N, idx.shape[1], Nq, kstride, C)
+        ctx.dims = (B, N, idx.shape[1], Nq, kstride, C, qstride)
         ctx.mark_non_differentiable(vsel)
         ctx.set_materialize_grads(False)          # (else autograd fills a zero gradient for vsel every step: two fill kernels)
         return out, vsel
@@ -530,17 +560,16 @@ class _PoolLayer(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g, _gv):
         idx, qsel, arg = ctx.saved_tensors
-        B, Nsrc, Nidx, Nq, kstride, C = ctx.dims
+        B, Nsrc, Nidx, Nq, kstride, C, qstride = ctx.dims
         g = _req(g, torch.float32, "pool.grad")
         gfeat = torch.empty(B, Nsrc, C, dtype=torch.float32, device=g.device)
-        _run("hsp_gather_max_bwd", (_p(g), 0, _p(idx), _p(qsel), _p(arg), B, Nsrc, Nidx, Nq, kstride, C, _p(gfeat), 0, _vp(0),
-                                    _stream()),
-             key=f"B{B}Ns{Nsrc}Nq{Nq}C{C}", abytes=B * (4 * Nsrc * C + Nq * (4 * kstride + 5 * C)))
+        _pool_bwd_raw(g, idx, qsel, qstride, arg, B, Nsrc, Nidx, Nq, kstride, C, gfeat)
         return gfeat, None, None, None, None
 
 
 def pool_layer(feat, xyz, idx, qsel, k):
-    """(feature_map_pool (B,Nq,C), vertices_pool (B,Nq,3)) of Pool_layer for fp32 rows; xyz carries no gradient."""
+    """(feature_map_pool (B,Nq,C), vertices_pool (B,Nq,3)) of Pool_layer for fp32 rows; xyz carries no gradient.  ``qsel``: the kept
+    rows, (Nq,) shared by the batch or (B,Nq) per cloud (the compiled no-grad form takes the shared list only)."""
     if (_timer is None and not torch.is_grad_enabled() and feat.is_cuda and feat.dtype == torch.float32 and feat.is_contiguous()
             and xyz.dtype == torch.float32 and xyz.is_contiguous() and idx.dtype == torch.int32 and idx.is_contiguous()
             and qsel.dtype == torch.int32 and qsel.dim() == 1 and qsel.is_contiguous() and _ext_ok()):
@@ -556,7 +585,8 @@ def points_max(x):
 
 
 def gather_max(feat, idx, k, qsel=None):
-    """max over the first k listed neighbours of each (selected) row -> (B,Nq,C)."""
+    """max over the first k listed neighbours of each (selected) row -> (B,Nq,C); ``qsel``: (Nq,) shared by the batch or (B,Nq)
+    per cloud."""
     return _GatherMax.apply(feat, idx, qsel, k)
 
 
@@ -2503,6 +2533,32 @@ def fps(xyz, n_samples):
     _run("hsp_fps_f64" if f64 else "hsp_fps_f32", (_p(xyz), B, N, n_samples, _p(sel), _p(ws), wsb, _stream()),
          key=f"B{B}N{N}n{n_samples}", abytes=B * ((24 if f64 else 12) * N + 4 * n_samples))
     return sel
+
+
+FPS_LEVELS_MAX_N = 12288      # hsp_fps_levels_f32: the register-resident kernel's range
+
+
+def fps_levels(vertices, n1, n2):
+    """Pool_layer's farthest-point sampler for both levels in one launch (hsp_fps_levels_f32): (sel1 int32 (B,n1), v1 (B,n1,3),
+    v2 (B,n2,3)) -- the rows ``fps`` picks per cloud with one rule added, a picked row is never picked again (so a tiled cloud
+    yields n1 different rows), their coordinates in pick order, and the first n2 of those (the sampler run on v1 returns
+    0 .. n2-1).  n2 = 0: v2 is None.  A cloud beyond the kernel's range raises: the plain ``fps`` cannot keep the added rule."""
+    x = _req(vertices.detach(), torch.float32, "fps_levels.vertices")
+    if x.dim() != 3 or x.shape[2] != 3:
+        raise HspError("fps_levels: expects (B,N,3) coordinates")
+    B, N, _ = x.shape
+    n1, n2 = int(n1), int(n2)
+    if not (0 < n1 <= N and 0 <= n2 <= n1):
+        raise HspError(f"fps_levels: need 0 < n1 <= N and 0 <= n2 <= n1, got N={N}, n1={n1}, n2={n2}")
+    if N > FPS_LEVELS_MAX_N:
+        raise HspError(f"fps_levels: N={N} is beyond the sampler's range (N <= {FPS_LEVELS_MAX_N}); there is no other "
+                       "farthest-point form that never re-picks a row, and no fall-back to random sampling")
+    sel1 = torch.empty(B, n1, dtype=torch.int32, device=x.device)
+    v1 = torch.empty(B, n1, 3, dtype=torch.float32, device=x.device)
+    v2 = torch.empty(B, n2, 3, dtype=torch.float32, device=x.device) if n2 else None
+    _run("hsp_fps_levels_f32", (_p(x), B, N, n1, n2, _p(sel1), _p(v1), _p(v2), _stream()),
+         key=f"B{B}N{N}/{n1}/{n2}", abytes=B * (12 * N + 16 * n1 + 12 * n2))
+    return sel1, v1, v2
 
 
 # ------------------------------------------------------------------------------------------------

@@ -237,6 +237,20 @@ int hsp_gather_max_bwd(const float *grad_out, int grad_bcast, const int32_t *idx
                        float *grad_feat, int accumulate /* !=0: add into grad_feat instead of overwriting */,
                        const float *extra /* optional (B,Nsrc,C) tensor added in the same pass, or NULL */,
                        hspStream_t stream);
+/* The pooling entry points with a row selector PER CLOUD (gcn3d.Pool_layer(sampler="fps"): every cloud keeps the rows its own
+ * farthest-point sampling picks).  Same arguments, semantics and kernels as hsp_gather_max_fwd / hsp_pool_fwd / hsp_gather_max_bwd
+ * and their bf16 twins, plus qsel_stride: 0 -- qsel (Nq) is one list shared by the batch (the entry points above forward here with
+ * 0); >= Nq -- cloud b keeps the rows qsel[b * qsel_stride + q] (a dense (B,Nq) selector has qsel_stride == Nq).  Any other
+ * stride, or a non-zero stride with qsel == NULL: HSP_ERR_BAD_ARG.  A list may name a source row more than once (a tiled cloud):
+ * each listing is one output row of its own and one more contribution to the backward's sum.  The entries are device data and
+ * are not range-checked: every entry must lie in [0, Nidx). */
+int hsp_gather_max_fwd_sel(const float *feat, const int32_t *idx, const int32_t *qsel, int qsel_stride, int B, int Nsrc,
+                           int Nidx, int Nq, int k, int kstride, int C, float *out, uint8_t *argmax, hspStream_t stream);
+int hsp_pool_fwd_sel(const float *feat, const float *xyz, const int32_t *idx, const int32_t *qsel, int qsel_stride, int B, int N,
+                     int Nq, int k, int kstride, int C, float *out, uint8_t *argmax, float *xyz_sel, hspStream_t stream);
+int hsp_gather_max_bwd_sel(const float *grad_out, int grad_bcast, const int32_t *idx, const int32_t *qsel, int qsel_stride,
+                           const uint8_t *argmax, int B, int Nsrc, int Nidx, int Nq, int kstride, int C, float *grad_feat,
+                           int accumulate, const float *extra, hspStream_t stream);
 /* the same result in GATHER form over hsp_rev_build(idx, k) (qsel == NULL case, Nq rows of idx):
  * each grad_feat row written once, no atomics. */
 int hsp_gather_max_bwd_csr(const float *grad_out, int grad_bcast, const uint8_t *argmax, const int32_t *rev_off,
@@ -657,6 +671,17 @@ int hsp_fps_f32(const float *xyz, int B, int N, int n_samples, int32_t *sel, voi
                 hspStream_t stream);
 int hsp_fps_f64(const double *xyz, int B, int N, int n_samples, int32_t *sel, void *ws, size_t ws_bytes,
                 hspStream_t stream);
+/* The LEVELS form: the sampler of gcn3d.Pool_layer(sampler="fps") for both Pool_layers of the stack in one launch.
+ * xyz (B,N0,3) -> sel1 (B,N1) int32, the rows hsp_fps_f32's rule picks (fp32, (x*x + y*y) + z*z, correctly rounded sqrt, running
+ * minimum of the distance to the picked set, start at row 0, first maximum wins) with ONE rule added: A PICKED ROW IS NEVER PICKED
+ * AGAIN -- its distance-to-set ranks below every unpicked row's, a zero included.  On a cloud whose picks are all distinct under
+ * hsp_fps_f32 the picks are hsp_fps_f32's, bit for bit; on a cloud with fewer distinct points than picks (a short crop tiled up to
+ * N0 rows), where hsp_fps_f32 returns row 0 over and over, the remaining picks are the lowest-index unpicked rows, so sel1 always
+ * names N1 different rows.  v1 (B,N1,3) = xyz[b, sel1[b]] in pick order.  Farthest-point picks are nested: the same sampler run on
+ * v1 returns 0 .. N2-1, so the second level is a prefix, and v2 (B,N2,3) = v1[:, :N2] is written here as well (N2 == 0: v2 may be
+ * NULL).  0 < N1 <= N0, 0 <= N2 <= N1.  N0 > 12288 (beyond the register-resident kernel): HSP_ERR_UNSUPPORTED, nothing launched. */
+int hsp_fps_levels_f32(const float *xyz, int B, int N0, int N1, int N2, int32_t *sel1, float *v1, float *v2,
+                       hspStream_t stream);
 
 /* ---- bf16 feature storage (BASELINE configs[3]: dense clouds, bf16 features / weights / fm / gradients) -----------
  * Twins of the entry points above for feature tensors stored as bfloat16 (hsp_bf16_t = the upper 16 bits of an fp32).
@@ -685,6 +710,11 @@ int hsp_gather_max_fwd_bf16(const hsp_bf16_t *feat, const int32_t *idx, const in
 int hsp_gather_max_bwd_bf16(const void *grad_out, int grad_bcast, const int32_t *idx, const int32_t *qsel,
                             const uint8_t *argmax, int B, int Nsrc, int Nidx, int Nq, int kstride, int C,
                             hsp_bf16_t *grad_feat, int accumulate, const hsp_bf16_t *extra, hspStream_t stream);
+int hsp_gather_max_fwd_sel_bf16(const hsp_bf16_t *feat, const int32_t *idx, const int32_t *qsel, int qsel_stride, int B, int Nsrc,
+                                int Nidx, int Nq, int k, int kstride, int C, hsp_bf16_t *out, uint8_t *argmax, hspStream_t stream);
+int hsp_gather_max_bwd_sel_bf16(const void *grad_out, int grad_bcast, const int32_t *idx, const int32_t *qsel, int qsel_stride,
+                                const uint8_t *argmax, int B, int Nsrc, int Nidx, int Nq, int kstride, int C,
+                                hsp_bf16_t *grad_feat, int accumulate, const hsp_bf16_t *extra, hspStream_t stream);
 int hsp_orl_global_fwd_bf16(const hsp_bf16_t *feat, const int32_t *idx, int B, int N, int k, int kstride, int C, float *fg,
                             uint8_t *argmax, void *ws, size_t ws_bytes, hspStream_t stream);
 int hsp_colsum_rows_bf16(const hsp_bf16_t *x, int B, int N, int C, float *out, void *ws, size_t ws_bytes,
