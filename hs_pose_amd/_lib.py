@@ -163,6 +163,10 @@ SIGNATURES = {
     "hsp_rf_fwd_plan": (_i, [_i, _i, _i, _vp]),
     "hsp_rf_bwd_scatter_plan": (_i, [_i, _i, _i, _i, _i, _vp]),
     "hsp_scatter_tile_plan": (_i, [_i, _i, _i, _vp]),
+    "hsp_wgrad_plan": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "hsp_wgrad_pair_plan": (_i, [_i, _i, _i, _i, _i, _i, _vp]),
+    "hsp_gemm_rows_plan": (_i, [_i, _i, _i, _i, _i, _i, _vp]),
+    "hsp_gemm_x3_plan": (_i, [_i, _i, _i, _i, _i, _i, _vp]),
     "hsp_pose_augment": (_i, [_vp] * 14 + [_i, _i, _i] + [ctypes.c_float] * 4 + [_vp] * 5),
 }
 

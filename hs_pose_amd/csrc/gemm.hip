@@ -605,12 +605,15 @@ __global__ __launch_bounds__(256, 2) void wgrad_x3_kernel(const float* __restric
     }
 }
 
-static bool wgrad_x3_ok(const void* A, int lda, const void* B, int ldb, int M, int N) {
+static bool wgrad_ptrs16(const void* A, const void* B) {
+    return ((reinterpret_cast<size_t>(A) | reinterpret_cast<size_t>(B)) & 15) == 0;
+}
+static bool wgrad_x3_ok(bool ptrs16, int lda, int ldb, int M, int N) {
     // (>= 4 output tiles: a single 128 x 128 tile leaves the K slices as the only parallelism -- 65 workgroups at K = 16448 --
     // and the fp32 kernel's 4-slices-per-workgroup form is faster there: 9.8 vs 18.3 us)
     // (ragged M: the last column quad of A is read whole, so its rows must reach ceil4(M))
     return (N & 127) == 0 && ((M + 127) >> 7) * (N >> 7) >= 4 && (lda & 3) == 0 && (ldb & 3) == 0 && lda >= ((M + 3) & ~3) &&
-           ((reinterpret_cast<size_t>(A) | reinterpret_cast<size_t>(B)) & 15) == 0;
+           ptrs16;
 }
 // shapes only the x3 form takes: M not a multiple of 64 (the heads' K = 1286 / 1289 / 771 first layers)
 static bool wgrad_ragged_m(int M, int N) { return (M & 63) != 0 && (N & 127) == 0 && M >= 128; }
@@ -636,9 +639,8 @@ static int wgrad_bf16_pick(int M, int N, int K, int* kslice) {
     *kslice = ks;
     return (K + ks - 1) / ks;
 }
-static bool wgrad_bf16_mfma_ok(const void* A, int lda, const void* B, int ldb, int M, int N) {
-    return (M & 127) == 0 && (N & 127) == 0 && (lda & 7) == 0 && (ldb & 7) == 0 &&
-           ((reinterpret_cast<size_t>(A) | reinterpret_cast<size_t>(B)) & 15) == 0;
+static bool wgrad_bf16_mfma_ok(bool ptrs16, int lda, int ldb, int M, int N) {
+    return (M & 127) == 0 && (N & 127) == 0 && (lda & 7) == 0 && (ldb & 7) == 0 && ptrs16;
 }
 
 // (slices, rows per slice, waves of a workgroup along K)
@@ -673,6 +675,63 @@ static int wgrad_pick_sk(int M, int N, int K, int* kslice, int* kblock) {
     return sk;
 }
 
+// The form a weight-gradient call takes and its K cut: the one decision of wgrad_impl and of hsp_wgrad_plan.
+// es: bytes per stored element (4 | 2); ptrs16: A and B both 16-byte aligned; bf16_ragged: the hsp_wgrad_ragged_* entries.
+// HSP_OK, or the HSP_ERR_UNSUPPORTED wgrad_impl returns for the shape.
+struct WgradPlan { int form, sk, ks, nparts; bool ragged; };   // form: HSP_WGRAD_FORM_*; sk slices of ks rows; nparts partial sums
+static int wgrad_plan(int es, bool bf16_ragged, bool ptrs16, int lda, int ldb, int M, int N, int K, WgradPlan* p) {
+    // ragged M: fp32 rows on the x3 form; bf16 rows (hsp_wgrad_ragged_bf16 only) on the bf16-MFMA form, A's rows on a 16-byte
+    // pitch that covers ceil8(M)
+    const bool ragged = (es == 4 || bf16_ragged) && wgrad_ragged_m(M, N);
+    if (ragged && es == 4 && !wgrad_x3_ok(ptrs16, lda, ldb, M, N)) return HSP_ERR_UNSUPPORTED;
+    if (ragged && es == 2 && ((lda & 7) || (ldb & 7) || lda < ((M + 7) & ~7) || !ptrs16)) return HSP_ERR_UNSUPPORTED;
+    if (!ragged && ((M & 63) || (N & 63) || (lda & 1) || (ldb & 1))) return HSP_ERR_UNSUPPORTED;   // 64x64 wave tiles, float2 loads
+    int ks, kb;
+    if ((es == 2 && (ragged || wgrad_bf16_mfma_ok(ptrs16, lda, ldb, M, N))) || (es == 4 && wgrad_x3_ok(ptrs16, lda, ldb, M, N))) {
+        const int sk2 = wgrad_bf16_pick(M, N, K, &ks);
+        *p = WgradPlan{es == 2 ? HSP_WGRAD_FORM_BF16 : HSP_WGRAD_FORM_X3, sk2, ks, sk2, ragged};
+        return HSP_OK;
+    }
+    const int sk = wgrad_pick_sk(M, N, K, &ks, &kb);
+    *p = WgradPlan{kb == 4 ? HSP_WGRAD_FORM_F32_KB4 : HSP_WGRAD_FORM_F32_KB1, sk, ks, sk / kb, false};
+    return HSP_OK;
+}
+
+// The cut of a pair of K-sliced weight gradients: the one decision of wgrad_pair_impl and of hsp_wgrad_pair_plan.  true: both
+// problems take the 4-slices-per-workgroup form and share one launch, sk* / ks* as launched (after the shrink loop).
+static bool wgrad_pair_plan(int M0, int N0, int K0, int M1, int N1, int K1, int* sk0_, int* ks0_, int* sk1_, int* ks1_) {
+    int ks0, kb0, ks1, kb1;
+    int sk0 = wgrad_pick_sk(M0, N0, K0, &ks0, &kb0), sk1 = wgrad_pick_sk(M1, N1, K1, &ks1, &kb1);
+    if (kb0 == 4 && kb1 == 4) {
+        // the two problems share ONE grid and the kernel's 66 KB of LDS let two workgroups live on a CU: 512 at once.  Each
+        // problem alone is sized for ~512 workgroups, so the pair came to 528 / 704 / 768 -- a second, mostly empty round that
+        // costs a whole slice time.  Fewer, longer K slices keep the pair inside one round (same kernel, same fold; the
+        // workspace rule is unchanged: fewer partials than it allows for).
+        constexpr int G = 4 * WG_UNROLL;
+        const int t0 = (M0 >> 6) * (N0 >> 6), t1 = (M1 >> 6) * (N1 >> 6);
+        int total = t0 * (sk0 / 4) + t1 * (sk1 / 4);
+        for (int it = 0; it < 8 && total > 2 * HSP_NUM_CU && sk0 > 8 && sk1 > 8; ++it) {
+            const double f = (double)(2 * HSP_NUM_CU) / total;
+            auto shrink = [&](int K, int& sk, int& ks) {
+                int want = (int)(sk * f) & ~3;
+                if (want >= sk) want = sk - 4;
+                if (want < 8) want = 8;
+                ks = ((K + want - 1) / want + G - 1) / G * G;
+                sk = (((K + ks - 1) / ks) + 3) & ~3;
+            };
+            shrink(K0, sk0, ks0);
+            shrink(K1, sk1, ks1);
+            total = t0 * (sk0 / 4) + t1 * (sk1 / 4);
+        }
+    }
+    *sk0_ = sk0; *ks0_ = ks0; *sk1_ = sk1; *ks1_ = ks1;
+    return kb0 == 4 && kb1 == 4;
+}
+static bool wgrad_pair_shapes_ok(int lda0, int ldb0, int M0, int N0, int K0, int lda1, int ldb1, int M1, int N1, int K1) {
+    return M0 > 0 && N0 > 0 && K0 > 0 && M1 > 0 && N1 > 0 && K1 > 0 && !((M0 | N0 | M1 | N1) & 63) &&
+           !((lda0 | ldb0 | lda1 | ldb1) & 1) && lda0 >= M0 && ldb0 >= N0 && lda1 >= M1 && ldb1 >= N1;
+}
+
 }  // namespace hsp
 
 using namespace hsp;
@@ -686,12 +745,36 @@ extern "C" size_t hsp_wgrad_workspace_bytes(int M, int N, int K) {
     }
     const int sk = wgrad_pick_sk(M, N, K, &ks, &kb);
     size_t parts = (size_t)(sk / kb);
-    if ((M & 127) == 0 && (N & 127) == 0) {                    // the bf16-MFMA form may cut K finer
+    if ((N & 127) == 0) {      // the bf16-MFMA form (M a multiple of 128) and the x3 form (any M: 64, 192, ...) may cut K finer
         int ks2;
         const size_t p2 = (size_t)wgrad_bf16_pick(M, N, K, &ks2);
         if (p2 > parts) parts = p2;
     }
     return parts * ((size_t)M * N + N) * sizeof(float);
+}
+
+extern "C" int hsp_wgrad_plan(int M, int N, int K, int elem_bytes, int aligned16, int lda, int ldb, int ragged_entry, int* out) {
+    if (!out || M <= 0 || N <= 0 || K <= 0 || lda < M || ldb < N || (elem_bytes != 2 && elem_bytes != 4)) return HSP_ERR_BAD_ARG;
+    WgradPlan pl;
+    const int rc = wgrad_plan(elem_bytes, ragged_entry != 0, aligned16 != 0, lda, ldb, M, N, K, &pl);
+    if (rc) return rc;
+    out[0] = pl.form; out[1] = pl.sk; out[2] = pl.ks; out[3] = pl.nparts;
+    return HSP_OK;
+}
+
+extern "C" int hsp_wgrad_pair_plan(int M0, int N0, int K0, int M1, int N1, int K1, int* out) {
+    if (!out) return HSP_ERR_BAD_ARG;
+    if (!wgrad_pair_shapes_ok(M0, N0, M0, N0, K0, M1, N1, M1, N1, K1)) return HSP_ERR_UNSUPPORTED;
+    int sk0, ks0, sk1, ks1;
+    const bool one = wgrad_pair_plan(M0, N0, K0, M1, N1, K1, &sk0, &ks0, &sk1, &ks1);
+    out[0] = one ? 1 : 0;
+    if (one) {
+        out[1] = sk0; out[2] = ks0; out[3] = sk1; out[4] = ks1;
+        out[5] = (M0 >> 6) * (N0 >> 6) * (sk0 / 4); out[6] = (M1 >> 6) * (N1 >> 6) * (sk1 / 4);
+    } else {
+        for (int i = 1; i < 7; ++i) out[i] = 0;
+    }
+    return HSP_OK;
 }
 
 template <bool COLSUM, typename FT>
@@ -716,20 +799,15 @@ static int wgrad_impl(const FT* A, int lda, const FT* B, int ldb, int M, int N, 
                       float* colsum_B, void* ws, size_t ws_bytes, hspStream_t stream, HspWgradPending* pending = nullptr,
                       bool bf16_ragged = false) {
     if (!A || !B || !C || M <= 0 || N <= 0 || K <= 0 || lda < M || ldb < N || ldc < N) return HSP_ERR_BAD_ARG;
-    // ragged M: fp32 rows on the x3 form; bf16 rows (hsp_wgrad_ragged_bf16 only) on the bf16-MFMA form, A's rows on a 16-byte
-    // pitch that covers ceil8(M)
-    const bool ragged = (sizeof(FT) == 4 || bf16_ragged) && wgrad_ragged_m(M, N);
-    if (ragged && sizeof(FT) == 4 && !wgrad_x3_ok(A, lda, B, ldb, M, N)) return HSP_ERR_UNSUPPORTED;
-    if (ragged && sizeof(FT) == 2 &&
-        ((lda & 7) || (ldb & 7) || lda < ((M + 7) & ~7) || ((reinterpret_cast<size_t>(A) | reinterpret_cast<size_t>(B)) & 15)))
-        return HSP_ERR_UNSUPPORTED;
-    if (!ragged && ((M & 63) || (N & 63) || (lda & 1) || (ldb & 1))) return HSP_ERR_UNSUPPORTED;   // 64x64 wave tiles, float2 loads
+    WgradPlan pl;
+    const int prc = wgrad_plan((int)sizeof(FT), bf16_ragged, wgrad_ptrs16(A, B), lda, ldb, M, N, K, &pl);
+    if (prc) return prc;
     if (!ws || ws_bytes < hsp_wgrad_workspace_bytes(M, N, K)) return HSP_ERR_WORKSPACE;
-    int ks, kb;
+    const int ks = pl.ks;
     hipStream_t st = as_stream(stream);
     if constexpr (sizeof(FT) == 2) {
-        if (ragged || wgrad_bf16_mfma_ok(A, lda, B, ldb, M, N)) {
-            const int sk2 = wgrad_bf16_pick(M, N, K, &ks);
+        if (pl.form == HSP_WGRAD_FORM_BF16) {
+            const int sk2 = pl.sk;
             float* part = reinterpret_cast<float*>(ws);
             float* cs_part = part + (size_t)sk2 * M * N;
             const int grid = ((M + 127) >> 7) * (N >> 7) * sk2;
@@ -747,7 +825,7 @@ static int wgrad_impl(const FT* A, int lda, const FT* B, int ldb, int M, int N, 
         }                                                                                                                      \
         hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, a, lda, b, ldb, M, N, K, ks, part, cs_part);                   \
     } while (0)
-            if (ragged) {
+            if (pl.ragged) {
                 if (colsum_B) WG_BF16_LAUNCH(true, true); else WG_BF16_LAUNCH(false, true);
             } else {
                 if (colsum_B) WG_BF16_LAUNCH(true, false); else WG_BF16_LAUNCH(false, false);
@@ -763,8 +841,8 @@ static int wgrad_impl(const FT* A, int lda, const FT* B, int ldb, int M, int N, 
         }
     }
     if constexpr (sizeof(FT) == 4) {
-        if (wgrad_x3_ok(A, lda, B, ldb, M, N)) {
-            const int sk2 = wgrad_bf16_pick(M, N, K, &ks);
+        if (pl.form == HSP_WGRAD_FORM_X3) {
+            const int sk2 = pl.sk;
             float* part = reinterpret_cast<float*>(ws);
             float* cs_part = part + (size_t)sk2 * M * N;
             const int grid = ((M + 127) >> 7) * (N >> 7) * sk2;
@@ -780,8 +858,8 @@ static int wgrad_impl(const FT* A, int lda, const FT* B, int ldb, int M, int N, 
             return check_launch();
         }
     }
-    const int sk = wgrad_pick_sk(M, N, K, &ks, &kb);
-    const int nparts = sk / kb;
+    const int sk = pl.sk, kb = pl.form == HSP_WGRAD_FORM_F32_KB4 ? 4 : 1;
+    const int nparts = pl.nparts;
     float* part = reinterpret_cast<float*>(ws);
     float* cs_part = part + (size_t)nparts * M * N;
     int rc = colsum_B ? wgrad_launch<true, FT>(A, lda, B, ldb, M, N, K, sk, ks, kb, part, cs_part, st)
@@ -837,36 +915,13 @@ static int wgrad_pair_impl(const float* A0, int lda0, const float* B0, int ldb0,
                            int ldc1, void* ws1, size_t ws_bytes1, HspWgradPending* pending, const float* cs_x, int cs_B, int cs_N,
                            int cs_C, float* cs_out, hspStream_t stream) {
     if (!pending) return HSP_ERR_BAD_ARG;
-    int ks0, kb0, ks1, kb1;
-    const bool shapes_ok = A0 && B0 && C0 && A1 && B1 && C1 && M0 > 0 && N0 > 0 && K0 > 0 && M1 > 0 && N1 > 0 && K1 > 0 &&
-                           !((M0 | N0 | M1 | N1) & 63) && !((lda0 | ldb0 | lda1 | ldb1) & 1) && lda0 >= M0 && ldb0 >= N0 &&
-                           lda1 >= M1 && ldb1 >= N1 && ldc0 >= N0 && ldc1 >= N1;
+    int sk0, ks0, sk1, ks1;
+    const bool shapes_ok = A0 && B0 && C0 && A1 && B1 && C1 && ldc0 >= N0 && ldc1 >= N1 &&
+                           wgrad_pair_shapes_ok(lda0, ldb0, M0, N0, K0, lda1, ldb1, M1, N1, K1);
     if (cs_x && !shapes_ok) return HSP_ERR_UNSUPPORTED;
     if (shapes_ok) {
-        int sk0 = wgrad_pick_sk(M0, N0, K0, &ks0, &kb0), sk1 = wgrad_pick_sk(M1, N1, K1, &ks1, &kb1);
-        if (kb0 == 4 && kb1 == 4) {
-            // the two problems share ONE grid and the kernel's 66 KB of LDS let two workgroups live on a CU: 512 at once.  Each
-            // problem alone is sized for ~512 workgroups, so the pair came to 528 / 704 / 768 -- a second, mostly empty round that
-            // costs a whole slice time.  Fewer, longer K slices keep the pair inside one round (same kernel, same fold; the
-            // workspace rule is unchanged: fewer partials than it allows for).
-            constexpr int G = 4 * WG_UNROLL;
-            const int t0 = (M0 >> 6) * (N0 >> 6), t1 = (M1 >> 6) * (N1 >> 6);
-            int total = t0 * (sk0 / 4) + t1 * (sk1 / 4);
-            for (int it = 0; it < 8 && total > 2 * HSP_NUM_CU && sk0 > 8 && sk1 > 8; ++it) {
-                const double f = (double)(2 * HSP_NUM_CU) / total;
-                auto shrink = [&](int K, int& sk, int& ks) {
-                    int want = (int)(sk * f) & ~3;
-                    if (want >= sk) want = sk - 4;
-                    if (want < 8) want = 8;
-                    ks = ((K + want - 1) / want + G - 1) / G * G;
-                    sk = (((K + ks - 1) / ks) + 3) & ~3;
-                };
-                shrink(K0, sk0, ks0);
-                shrink(K1, sk1, ks1);
-                total = t0 * (sk0 / 4) + t1 * (sk1 / 4);
-            }
-        }
-        if (kb0 == 4 && kb1 == 4 && ws0 && ws1 && ws_bytes0 >= hsp_wgrad_workspace_bytes(M0, N0, K0) &&
+        const bool one = wgrad_pair_plan(M0, N0, K0, M1, N1, K1, &sk0, &ks0, &sk1, &ks1);
+        if (one && ws0 && ws1 && ws_bytes0 >= hsp_wgrad_workspace_bytes(M0, N0, K0) &&
             ws_bytes1 >= hsp_wgrad_workspace_bytes(M1, N1, K1)) {
             const WgradProb p0{A0, B0, reinterpret_cast<float*>(ws0), lda0, ldb0, M0, N0, K0, sk0, ks0};
             const WgradProb p1{A1, B1, reinterpret_cast<float*>(ws1), lda1, ldb1, M1, N1, K1, sk1, ks1};

@@ -495,6 +495,9 @@ static int gemm_rows_pick_split(long long tiles, int TT) {
     return (TT + per - 1) / per;                   // every split non-empty
 }
 
+// staging load width of the kernel by the operands' common alignment: 1 = 16-byte, 2 = 8-byte, 0 = 4-byte pieces
+static int gemm_rows_stage_mode(int al) { return al == 16 ? 1 : al == 8 ? 2 : 0; }
+
 template <typename T, int WM, int WN, int MODE>
 static int launch_cfg(const GemmRowsArgs& a, int lb1, int lb2, float* a_ws, size_t a_ws_bytes, hipStream_t st) {
     constexpr int BM = 64 * WM, BN = 64 * WN;
@@ -503,9 +506,7 @@ static int launch_cfg(const GemmRowsArgs& a, int lb1, int lb2, float* a_ws, size
     g.tiles_m = (a.M + BM - 1) / BM;
     g.tiles_n = (a.N + BN - 1) / BN;
     {   // split-K when the tiles alone cannot fill the chip and K is deep (the input-gradient products: 64 tiles x K = 4608)
-        constexpr int BKE = 128 / ES;
-        const int TT = (a.K1 + BKE - 1) / BKE + (lb2 ? (a.K2 + BKE - 1) / BKE : 0);
-        int ns = a.bn_part ? 1 : gemm_rows_pick_split((long long)g.tiles_m * g.tiles_n, TT);
+        int ns = a.bn_part ? 1 : a.nsplit;                     // (a.nsplit: gemm_rows_plan_of's split for this tile)
         if ((size_t)ns * a.M * a.N * sizeof(float) > a_ws_bytes) ns = 1;          // no (or too small a) workspace: unsplit
         g.nsplit = ns;
         g.ws = ns > 1 ? a_ws : nullptr;
@@ -578,6 +579,18 @@ static bool prefer_small_tile(int M, int N, int TT = 1 << 30) {
     return cost(64, 64, 1.06) < cost(128, 128, 1.0);
 }
 
+// The tile edge, the k-blocks of 128 bytes over both sources and the K split of a call: the one decision of the dispatch, of
+// hsp_gemm_rows_workspace_bytes and of hsp_gemm_rows_plan (K2 = 0: one source; symmetric in the sources)
+struct RowsPlan { int bm, TT, ns; };
+static RowsPlan gemm_rows_plan_of(int M, int N, int K1, int K2, int es) {
+    const int bke = 128 / es;
+    RowsPlan p;
+    p.TT = (K1 + bke - 1) / bke + (K2 > 0 ? (K2 + bke - 1) / bke : 0);
+    p.bm = prefer_small_tile(M, N, p.TT) ? 64 : 128;
+    p.ns = gemm_rows_pick_split((long long)((M + p.bm - 1) / p.bm) * ((N + p.bm - 1) / p.bm), p.TT);
+    return p;
+}
+
 template <typename T>
 static int gemm_rows_dispatch(const void* A1, int lda1, const void* B1, int ldb1, int l1, int K1, const void* A2, int lda2,
                               const void* B2, int ldb2, int l2, int K2, int M, int N, const float* bias, const void* resid,
@@ -624,10 +637,10 @@ static int gemm_rows_dispatch(const void* A1, int lda1, const void* B1, int ldb1
     }
     if (two && lb1 == 2 && lb2 == 2) return HSP_ERR_UNSUPPORTED;
     hipStream_t st = as_stream(stream);
-    const int TTall = (K1 + 128 / ES - 1) / (128 / ES) + (two ? (K2 + 128 / ES - 1) / (128 / ES) : 0);
-    bool small = prefer_small_tile(M, N, TTall);
-    const int mode = al == 16 ? 1 : al == 8 ? 2 : 0;           // staging load width
-    g.nsplit = 1;
+    const RowsPlan pl = gemm_rows_plan_of(M, N, K1, two ? K2 : 0, ES);
+    const bool small = pl.bm == 64;
+    const int mode = gemm_rows_stage_mode(al);                 // staging load width
+    g.nsplit = pl.ns;                                          // (launch_cfg falls back to 1 without the workspace for it)
     if (small) return launch_mode<T, 1, 1>(g, lb1, lb2, mode, reinterpret_cast<float*>(ws), ws ? ws_bytes : 0, st);
     return launch_mode<T, 2, 2>(g, lb1, lb2, mode, reinterpret_cast<float*>(ws), ws ? ws_bytes : 0, st);
 }
@@ -690,14 +703,24 @@ extern "C" int hsp_cast_params_pitched_bf16(const HspCastPitchedDesc* table_dev,
     return check_launch();
 }
 
+/* the tile, the staging mode and the split a call takes, by the functions the dispatch calls */
+extern "C" int hsp_gemm_rows_plan(int M, int N, int K1, int K2, int elem_bytes, int align, int* out) {
+    if (!out || M <= 0 || N <= 0 || K1 <= 0 || K2 < 0 || (elem_bytes != 2 && elem_bytes != 4) ||
+        (align != 16 && align != 8 && align != 4))
+        return HSP_ERR_BAD_ARG;
+    if (elem_bytes == 2 && align != 16) return HSP_ERR_UNSUPPORTED;       // bf16 operands: 16-byte aligned rows
+    const RowsPlan pl = gemm_rows_plan_of(M, N, K1, K2, elem_bytes);
+    out[0] = pl.bm;
+    out[1] = gemm_rows_stage_mode(align);
+    out[2] = pl.ns;
+    out[3] = pl.TT;
+    return HSP_OK;
+}
+
 /* split-K workspace: 16 fp32 partial copies of C at most (0 = the shape never splits) */
 extern "C" size_t hsp_gemm_rows_workspace_bytes(int M, int N, int K1, int K2, int elem_bytes) {
     if (M <= 0 || N <= 0 || K1 <= 0 || (elem_bytes != 2 && elem_bytes != 4)) return 0;
-    const int bke = 128 / elem_bytes;
-    const int TT = (K1 + bke - 1) / bke + (K2 > 0 ? (K2 + bke - 1) / bke : 0);
-    const bool small = prefer_small_tile(M, N, TT);
-    const int bm = small ? 64 : 128;
-    const int ns = gemm_rows_pick_split((long long)((M + bm - 1) / bm) * ((N + bm - 1) / bm), TT);
+    const int ns = gemm_rows_plan_of(M, N, K1, K2, elem_bytes).ns;
     return ns > 1 ? (size_t)ns * M * N * sizeof(float) : 0;
 }
 

@@ -608,6 +608,32 @@ static int x3_pick_wm(int M, int N) {
     return t128 >= 2 * HSP_NUM_CU ? 2 : 1;
 }
 
+// the panel form: K = 128, columns in whole 128-wide panels, enough row tiles per panel slot to amortise the weight fragments.
+// Row slots per panel (R > 0) where the call takes it, else 0; epi0: bias 1 | resid 2 | cloud_bias 4
+static int x3_panel_slots(int M, int N, int K1, bool two, int epi0, bool bn, int ldc) {
+    if (bn || two || epi0 > 1 || K1 != 128 || N % 128 != 0 || (long long)(M + 32) * ldc * 4 >= (1ll << 31)) return 0;
+    const int P = N / 128;
+    const int R = (2 * HSP_NUM_CU / P) / HSP_NUM_XCD * HSP_NUM_XCD;  // two workgroups per CU; a multiple of the XCD count
+    const int nt = (M + 31) / 32;
+    const int rounds = R ? (nt + R - 1) / R : 0;
+    return (R && rounds >= 3 && (double)nt / ((double)rounds * R) >= 0.75) ? R : 0;
+}
+
+// The kernel, the tile height, the k-blocks and the K split of a call: the one decision of gemm_x3_impl, of
+// hsp_gemm_x3_workspace_bytes and of hsp_gemm_x3_plan.  K2 = 0: one source; epi: bias 1 | resid 2 | cloud_bias 4; bn: the
+// BatchNorm-partials entries (no panel form; bn_out, the layer's out product, runs 64-row tiles).  panel_R > 0: the panel kernel
+// with that many row slots per panel, and the rest describes the tile kernel the call would otherwise take.
+struct X3Plan { int panel_R, wm, TT, ns; };
+static X3Plan x3_plan_of(int M, int N, int K1, int K2, int epi, bool bn, bool bn_out, int ldc) {
+    X3Plan p;
+    p.panel_R = x3_panel_slots(M, N, K1, K2 > 0, epi, bn, ldc);
+    p.wm = bn_out ? 1 : x3_pick_wm(M, N);
+    const int bm = 64 * p.wm;
+    p.TT = (K1 + X3_BK - 1) / X3_BK + (K2 > 0 ? (K2 + X3_BK - 1) / X3_BK : 0);
+    p.ns = epi ? 1 : x3_pick_split((long long)((M + bm - 1) / bm) * ((N + X3_BN - 1) / X3_BN), p.TT);
+    return p;
+}
+
 }  // namespace hsp
 
 using namespace hsp;
@@ -627,11 +653,21 @@ extern "C" int hsp_gemm_x3_supported(int M, int N, int K1, int K2) {
     return (t64 >= 128 || TT >= 32) ? 1 : 0;
 }
 
+/* the kernel, the tile height, the split and the reduce path a call takes, by the functions the dispatch calls */
+extern "C" int hsp_gemm_x3_plan(int M, int N, int K1, int K2, int epi, int ldc, int* out) {
+    if (!out || ldc < N || epi < 0 || epi > 7) return HSP_ERR_BAD_ARG;
+    if (!hsp_gemm_x3_supported(M, N, K1, K2)) return HSP_ERR_UNSUPPORTED;
+    const X3Plan pl = x3_plan_of(M, N, K1, K2, epi, false, false, ldc);
+    if (pl.panel_R) { out[0] = 1; out[1] = 0; out[2] = 1; out[3] = 0; return HSP_OK; }
+    const int ns = pl.ns;
+    out[0] = 0; out[1] = pl.wm; out[2] = ns;
+    out[3] = ns > 1 ? (((N & 3) == 0 && (ldc & 3) == 0) ? 4 : 1) : 0;
+    return HSP_OK;
+}
+
 extern "C" size_t hsp_gemm_x3_workspace_bytes(int M, int N, int K1, int K2) {
     if (!hsp_gemm_x3_supported(M, N, K1, K2)) return 0;
-    const int wm = x3_pick_wm(M, N), bm = 64 * wm;
-    const int TT = (K1 + X3_BK - 1) / X3_BK + (K2 > 0 ? (K2 + X3_BK - 1) / X3_BK : 0);
-    const int ns = x3_pick_split((long long)((M + bm - 1) / bm) * ((N + X3_BN - 1) / X3_BN), TT);
+    const int ns = x3_plan_of(M, N, K1, K2 > 0 ? K2 : 0, 0, false, false, N).ns;     // (the split of the tile kernel without an epilogue)
     return ns > 1 ? (size_t)ns * M * N * sizeof(float) : 0;
 }
 
@@ -663,17 +699,15 @@ static int gemm_x3_impl(const float* A1, int lda1, const hsp_bf16_t* P1, int ldp
     const bool bn_out = bn && resid && cloud_bias && !bias, bn_lin = bn && bias && !resid && !cloud_bias && !two;
     if (bn && (!bn_part || !(bn_out || bn_lin))) return HSP_ERR_UNSUPPORTED;
     hipStream_t st = as_stream(stream);
-    {   // the panel form: K = 128, columns in whole 128-wide panels, enough row tiles per panel slot to amortise the weight fragments
-        const int epi0 = (bias ? 1 : 0) | (resid ? 2 : 0) | (cloud_bias ? 4 : 0);
-        if (!bn && !two && epi0 <= 1 && K1 == 128 && N % 128 == 0 && (long long)(M + 32) * ldc * 4 < (1ll << 31)) {
-            const int P = N / 128;
-            const int R = (2 * HSP_NUM_CU / P) / HSP_NUM_XCD * HSP_NUM_XCD;  // two workgroups per CU; a multiple of the XCD count
-            const int nt = (M + 31) / 32;
-            const int rounds = R ? (nt + R - 1) / R : 0;
-            if (R && rounds >= 3 && (double)nt / ((double)rounds * R) >= 0.75) {
-                g.tiles_m = nt; g.tiles_n = P; g.nsplit = 1; g.ws = nullptr;
-                const dim3 pgrid((unsigned)(P * R)), pblock(256);
-                const size_t lds = (size_t)2 * 3 * 32 * 128 * 2;             // 48 KB
+    const int epi = (bias ? 1 : 0) | (resid ? 2 : 0) | (cloud_bias ? 4 : 0);
+    const X3Plan pl = x3_plan_of(M, N, K1, K2, epi, bn, bn_out, ldc);
+    {   // the panel form (x3_panel_slots)
+        const int epi0 = epi, R = pl.panel_R;
+        if (R) {
+            const int P = N / 128, nt = (M + 31) / 32;
+            g.tiles_m = nt; g.tiles_n = P; g.nsplit = 1; g.ws = nullptr;
+            const dim3 pgrid((unsigned)(P * R)), pblock(256);
+            const size_t lds = (size_t)2 * 3 * 32 * 128 * 2;             // 48 KB
 #define X3_PANEL(EPI_)                                                                                                    \
     do {                                                                                                                  \
         auto kern = gemm_x3_panel_kernel<EPI_>;                                                                           \
@@ -685,18 +719,15 @@ static int gemm_x3_impl(const float* A1, int lda1, const hsp_bf16_t* P1, int ldp
         }                                                                                                                 \
         hipLaunchKernelGGL(kern, pgrid, pblock, lds, st, g);                                                              \
     } while (0)
-                if (epi0) X3_PANEL(1);
-                else X3_PANEL(0);
+            if (epi0) X3_PANEL(1);
+            else X3_PANEL(0);
 #undef X3_PANEL
-                return check_launch();
-            }
+            return check_launch();
         }
     }
-    const int wm = bn_out ? 1 : x3_pick_wm(M, N), bm = 64 * wm;
+    const int wm = pl.wm, bm = 64 * wm;
     g.tiles_m = (M + bm - 1) / bm; g.tiles_n = (N + X3_BN - 1) / X3_BN;
-    const int TT = (K1 + X3_BK - 1) / X3_BK + (two ? (K2 + X3_BK - 1) / X3_BK : 0);
-    const int epi = (bias ? 1 : 0) | (resid ? 2 : 0) | (cloud_bias ? 4 : 0);
-    int ns = epi ? 1 : x3_pick_split((long long)g.tiles_m * g.tiles_n, TT);
+    int ns = pl.ns;
     if (ns > 1 && (!ws || (size_t)ns * M * N * sizeof(float) > ws_bytes)) ns = 1;
     g.nsplit = ns; g.ws = ns > 1 ? reinterpret_cast<float*>(ws) : nullptr;
     const long long items = (long long)g.tiles_m * g.tiles_n * ns;

@@ -389,6 +389,12 @@ int hsp_gemm_rows_f32(const float *A1, int lda1, const float *B1, int ldb1, int 
  * products), which then split K over up to 16 workgroups per tile and fold the partial tiles in a second launch; with
  * ws == NULL (or too small) the product runs unsplit */
 size_t hsp_gemm_rows_workspace_bytes(int M, int N, int K1, int K2, int elem_bytes);
+/* host-only: what hsp_gemm_rows_f32 (elem_bytes 4) / hsp_gemm_rows_*bf16 (2) run for a shape (the dispatch decides by the same
+ * functions): out[4] = tile edge (64 | 128), staging mode (1: 16-byte, 2: 8-byte, 0: 4-byte pieces), K splits with a workspace
+ * of hsp_gemm_rows_workspace_bytes (1 = unsplit), k-blocks of 128 bytes over both sources.  align: the smallest of 16 | 8 | 4
+ * that every operand's base pointer and row pitch in bytes is a multiple of.  K2 = 0: one source; the split of a dual-source
+ * call does not depend on the order of its sources.  HSP_ERR_UNSUPPORTED: bf16 operands off a 16-byte alignment. */
+int hsp_gemm_rows_plan(int M, int N, int K1, int K2, int elem_bytes, int align, int *out);
 int hsp_gemm_rows_bf16(const hsp_bf16_t *A1, int lda1, const hsp_bf16_t *B1, int ldb1, int K1,
                        const hsp_bf16_t *A2, int lda2, const hsp_bf16_t *B2, int ldb2, int K2, int M, int N,
                        const float *bias, const hsp_bf16_t *resid, int ldr, const float *cloud_bias,
@@ -432,6 +438,12 @@ typedef struct HspSplitDesc { const float *src; void *dst; int rows, cols, ld, t
 int hsp_split_params_x3(const HspSplitDesc *table_dev, int n, int total_tiles, hspStream_t stream);
 int hsp_gemm_x3_supported(int M, int N, int K1, int K2);
 size_t hsp_gemm_x3_workspace_bytes(int M, int N, int K1, int K2);
+/* host-only: what hsp_gemm_x3_f32 runs for a shape (the dispatch decides by the same functions).  epi: bias 1 | resid 2 |
+ * cloud_bias 4; K2 = 0: one source.  out[4] = 1 for the panel kernel (K1 = 128, N in whole 128-column panels, 32-row tiles,
+ * >= 3 rounds filled to >= 0.75) else 0 for the tile kernel; the tile height in 64-row units (1 | 2; 0 with the panel kernel);
+ * K splits with a workspace of hsp_gemm_x3_workspace_bytes (1 = unsplit: any epilogue, or too few k-blocks); the fold's path,
+ * 4 = float4 (N and ldc multiples of 4), 1 = scalar, 0 = no fold.  HSP_ERR_UNSUPPORTED where hsp_gemm_x3_supported is 0. */
+int hsp_gemm_x3_plan(int M, int N, int K1, int K2, int epi, int ldc, int *out);
 int hsp_gemm_x3_f32(const float *A1, int lda1, const hsp_bf16_t *P1, int ldp1, long long ps1, int K1,
                     const float *A2, int lda2, const hsp_bf16_t *P2, int ldp2, long long ps2, int K2, int M, int N,
                     const float *bias, const float *resid, int ldr, const float *cloud_bias, int rows_per_cloud,
@@ -504,6 +516,21 @@ int hsp_cast_params_pitched_bf16(const HspCastPitchedDesc *table_dev, int n, int
  * a fixed order (deterministic).  ws: hsp_wgrad_workspace_bytes(M,N,K).
  */
 size_t hsp_wgrad_workspace_bytes(int M, int N, int K);
+/* host-only: the form and the K cut of a weight-gradient call (every hsp_wgrad_* entry decides by the same function).
+ * elem_bytes: 4 (the *_f32 entries) | 2 (*_bf16); aligned16: A and B both start on 16 bytes; lda / ldb in elements;
+ * ragged_entry != 0: the hsp_wgrad_ragged_* entries.  out[4] = form, K slices, rows per slice (a multiple of 16; of 64 on the
+ * matrix-core forms), partial sums in the workspace (slices / 4 on HSP_WGRAD_FORM_F32_KB4, else the slices);
+ * partials * (M*N + N) * 4 <= hsp_wgrad_workspace_bytes(M, N, K).  Returns the HSP_ERR_UNSUPPORTED of the entry where it declines. */
+#define HSP_WGRAD_FORM_F32_KB1 0   /* fp32 MFMA, a wave per (tile, slice) */
+#define HSP_WGRAD_FORM_F32_KB4 1   /* fp32 MFMA, the 4 waves of a workgroup on 4 consecutive slices of one tile, folded in LDS */
+#define HSP_WGRAD_FORM_BF16 2      /* bf16 rows on the bf16 MFMA (128 x 128 tiles) */
+#define HSP_WGRAD_FORM_X3 3        /* fp32 rows as three bf16 slices on the bf16 MFMA */
+int hsp_wgrad_plan(int M, int N, int K, int elem_bytes, int aligned16, int lda, int ldb, int ragged_entry, int *out);
+/* host-only: the cut of hsp_wgrad_partial_pair_(colsum_)f32 for dense operands: out[7] = 1 where both problems share one launch
+ * (both on HSP_WGRAD_FORM_F32_KB4; else 0, two hsp_wgrad_partial_f32 launches, see hsp_wgrad_plan, and the rest is 0), K slices and
+ * rows per slice of problem 0, of problem 1 -- as launched, after the slices were lengthened to keep the pair inside one round of
+ * 2 workgroups per CU --, workgroups of problem 0, of problem 1.  HSP_ERR_UNSUPPORTED: M or N off a multiple of 64. */
+int hsp_wgrad_pair_plan(int M0, int N0, int K0, int M1, int N1, int K1, int *out);
 /* split forms for a backward that computes several parameter gradients (an HS layer has three): hsp_wgrad_partial_* runs the
  * split-K launch only and describes the pending fold in *pending (a HOST struct; the workspace must stay alive and untouched
  * until the fold); hsp_wgrad_fold folds up to HSP_FOLD_MAX_WGRAD pending problems in ONE launch (same fixed order, same
