@@ -78,6 +78,8 @@ SIGNATURES = {
     "hsp_gemm_x3_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "hsp_gemm_x3_f32": (_i, [_vp, _i, _vp, _i, ctypes.c_longlong, _i, _vp, _i, _vp, _i, ctypes.c_longlong, _i, _i, _i, _vp, _vp, _i, _vp, _i,
                              ctypes.c_float, _vp, _i, _vp, _sz, _vp]),
+    "hsp_gemm_takes": (_i, [_vp, _i]),
+    "hsp_gemm_route": (_i, [_vp]),
     "hsp_small_rows_f32": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, ctypes.c_float, _vp, _i, _vp]),
     "hsp_small_outer_f32": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _i, _vp, _vp]),
     "hsp_colsum_rows_xyz": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
@@ -225,6 +227,18 @@ class HspWgradPending(ctypes.Structure):
     """include/hsp.h: HspWgradPending (a HOST struct)"""
     _fields_ = [("part", ctypes.c_void_p), ("cs_part", ctypes.c_void_p), ("C", ctypes.c_void_p), ("colsum", ctypes.c_void_p),
                 ("nparts", ctypes.c_int), ("M", ctypes.c_int), ("N", ctypes.c_int), ("ldc", ctypes.c_int)]
+
+
+class HspGemmCall(ctypes.Structure):
+    """include/hsp.h: HspGemmCall (a HOST struct)"""
+    _fields_ = ([(n, ctypes.c_void_p) for n in ("A1", "B1", "A2", "B2", "resid", "C")] + [(n, ctypes.c_int) for n in (
+        "M", "N", "K1", "K2", "b1_layout", "b2_layout", "elem_bytes", "lda1", "ldb1", "lda2", "ldb2", "ldr", "ldc",
+        "bias", "cloud_bias", "xyz3", "relu", "alpha_one", "rows_per_cloud", "bn", "allow_x3")])
+
+
+# include/hsp.h: HSP_GEMM_ROUTE_* / HSP_GEMM_BN_*
+ROUTE_NONE, ROUTE_SMALL_ROWS, ROUTE_X3, ROUTE_X3_BN, ROUTE_WAVE, ROUTE_TILE = range(6)
+BN_NONE, BN_OUT, BN_LINEAR = range(3)
 
 
 class HspDirsPending(ctypes.Structure):

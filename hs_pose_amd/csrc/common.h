@@ -41,6 +41,14 @@ int knn3_select_flags(const float* x, int B, int N, int k, int drop, int k2, int
 // gather.hip -> gemm.hip: 1 where hsp_colsum_cloud_f32(x, NULL, B, N, C) takes the shape, with its rows per chunk and chunk count
 int colsum_cloud_plan(int B, int N, int C, int* rows, int* nchunk);
 
+// gemm_wave.hip / gemm_rows.hip -> gemm_x3.hip (hsp_gemm_takes, hsp_gemm_route): 1 where hsp_gemm_wave_f32 (cfg = relu << 29) /
+// the hsp_gemm_rows_* dispatch runs the call -- the functions those entry points decline by
+bool gemm_wave_takes(const HspGemmCall& c);
+bool gemm_rows_takes(const HspGemmCall& c);
+
+// base pointer and row pitch of an operand on 16 bytes (a NULL base: the pitch alone)
+inline bool al16(const void* q, long long ld, int es) { return ((reinterpret_cast<size_t>(q) | ((size_t)ld * es)) & 15) == 0; }
+
 // persistent grid: a multiple of the XCD count so that block % 8 == XCD for every block
 inline int persistent_blocks(long long work_items, int blocks_per_cu) {
     long long g = (long long)HSP_NUM_CU * blocks_per_cu;

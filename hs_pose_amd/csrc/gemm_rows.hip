@@ -591,6 +591,28 @@ static RowsPlan gemm_rows_plan_of(int M, int N, int K1, int K2, int es) {
     return p;
 }
 
+// The calls the dispatch runs, with the operands' common alignment (16 | 8 | 4): the one decision of gemm_rows_dispatch and of
+// hsp_gemm_takes / hsp_gemm_route (gemm_rows_takes)
+static bool rows_takes(const HspGemmCall& c, int* al_) {
+    const int es = c.elem_bytes;
+    const bool two = c.A2 != nullptr;
+    if (es == 2 && (c.b1_layout == 1 || (two && c.b2_layout == 1))) return false;          // bf16: "nt" operands only
+    int al = std::min(align_of(c.A1, c.lda1, es), align_of(c.B1, c.ldb1, es));
+    if (two) al = std::min(al, std::min(align_of(c.A2, c.lda2, es), align_of(c.B2, c.ldb2, es)));
+    if (al < 16 && es == 2) return false;                                                   // bf16 operands: 16-byte aligned rows
+    if (al < 16)                                                                            // 8- or 4-byte pieces
+        for (const void* q : {c.A1, c.B1, c.A2, c.B2})
+            if (reinterpret_cast<size_t>(q) % 4) return false;
+    if (two && c.b1_layout == 1 && c.b2_layout == 1) return false;                          // ("nn" + "nn" is not instantiated)
+    *al_ = al;
+    return true;
+}
+
+bool gemm_rows_takes(const HspGemmCall& c) {
+    int al;
+    return (c.elem_bytes == 4 || c.elem_bytes == 2) && rows_takes(c, &al);
+}
+
 template <typename T>
 static int gemm_rows_dispatch(const void* A1, int lda1, const void* B1, int ldb1, int l1, int K1, const void* A2, int lda2,
                               const void* B2, int ldb2, int l2, int K2, int M, int N, const float* bias, const void* resid,
@@ -605,19 +627,14 @@ static int gemm_rows_dispatch(const void* A1, int lda1, const void* B1, int ldb1
     if (two && (!B2 || K2 <= 0 || lda2 < K2 || (l2 != 0 && l2 != 1) || ldb2 < (l2 == 0 ? K2 : N))) return HSP_ERR_BAD_ARG;
     if (resid && ldr < N) return HSP_ERR_BAD_ARG;
     if (cbias && rpc <= 0) return HSP_ERR_BAD_ARG;
-    if (ES == 2 && (l1 == 1 || (two && l2 == 1))) return HSP_ERR_UNSUPPORTED;     // bf16: "nt" operands only
+    HspGemmCall c{};
+    c.A1 = A1; c.B1 = B1; c.A2 = A2; c.B2 = B2; c.lda1 = lda1; c.ldb1 = ldb1; c.lda2 = lda2; c.ldb2 = ldb2;
+    c.b1_layout = l1; c.b2_layout = l2; c.elem_bytes = ES;
+    int al;
+    if (!rows_takes(c, &al)) return HSP_ERR_UNSUPPORTED;
     GemmRowsArgs g{};
     g.A1 = A1; g.B1 = B1; g.lda1 = lda1; g.ldb1 = ldb1; g.K1 = K1;
-    int al = std::min(align_of(A1, lda1, ES), align_of(B1, ldb1, ES));
-    if (two) {
-        g.A2 = A2; g.B2 = B2; g.lda2 = lda2; g.ldb2 = ldb2; g.K2 = K2;
-        al = std::min(al, std::min(align_of(A2, lda2, ES), align_of(B2, ldb2, ES)));
-    }
-    if (al < 16 && ES == 4) {                                  // 8- or 4-byte pieces
-        const void* ps[4] = {A1, B1, A2, B2};
-        for (const void* q : ps)
-            if (reinterpret_cast<size_t>(q) % 4) return HSP_ERR_UNSUPPORTED;
-    }
+    if (two) { g.A2 = A2; g.B2 = B2; g.lda2 = lda2; g.ldb2 = ldb2; g.K2 = K2; }
     // a dual-source call whose second source is a (K,N)-with-(N,K) pair is issued with the sources swapped
     // (the sum is commutative), which keeps the instantiated layout pairs to ("nt","nt") and ("nn","nt")
     g.C = C; g.ldc = ldc; g.M = M; g.N = N; g.bias = bias; g.resid = resid; g.ldr = ldr; g.cbias = cbias;
@@ -635,7 +652,6 @@ static int gemm_rows_dispatch(const void* A1, int lda1, const void* B1, int ldb1
         ti = g.lda1; g.lda1 = g.lda2; g.lda2 = ti;  ti = g.ldb1; g.ldb1 = g.ldb2; g.ldb2 = ti;  ti = g.K1; g.K1 = g.K2; g.K2 = ti;
         lb1 = 2; lb2 = 1;
     }
-    if (two && lb1 == 2 && lb2 == 2) return HSP_ERR_UNSUPPORTED;
     hipStream_t st = as_stream(stream);
     const RowsPlan pl = gemm_rows_plan_of(M, N, K1, two ? K2 : 0, ES);
     const bool small = pl.bm == 64;

@@ -434,8 +434,6 @@ static bool gw_plan(int M, int N, int K1, int K2, int cfg, GwPlan* p) {
 
 using namespace hsp;
 
-static inline bool has_rc_check(const void* r, const void* c) { return r && c; }
-
 /* host-only: the cut chosen for a shape -> out[10] = RB, NCB, waves per SIMD, tiles_m, tiles_n, tiles per wave, waves,
  * first leftover tile, 32 x 32 blocks of the leftover tiles, 0; returns 0 when the shape is not covered */
 extern "C" int hsp_gemm_wave_plan_info(int M, int N, int K1, int K2, int cfg, int* out) {
@@ -506,6 +504,38 @@ extern "C" int hsp_layer_out_exact_f32(const float* F, int ldf, const float* Wa,
     return check_launch();
 }
 
+// The call hsp_gemm_wave_f32 runs, with its cut and its instantiated form: the one decision of the entry point and of
+// hsp_gemm_takes / hsp_gemm_route (gemm_wave_takes).  cfg as for the entry point; c.relu is its bit 29.
+//   0 fm   "nn"        + bias                      1 g W      "nn"                      2 x W^T  "nt"
+//   3 x W^T "nt" + bias                            4 out      "nt" + "nt", residual + cloud bias
+//   5 out0  "nt", residual + cloud bias + xyz3 (7: + relu)                              6 gX       "nn" + "nt"
+static bool gw_takes(const HspGemmCall& c, int cfg, GwPlan* p, int* form_) {
+    const bool two = c.A2 != nullptr, has_rc = c.resid && c.cloud_bias, plain = !c.bias && !c.resid && !c.cloud_bias && !c.xyz3;
+    if (c.elem_bytes != 4 || !gw_plan(c.M, c.N, c.K1, two ? c.K2 : 0, cfg, p)) return false;
+    if (!al16(c.A1, c.lda1, 4) || !al16(c.B1, c.ldb1, 4) || !al16(c.C, c.ldc, 4) ||
+        (two && (!al16(c.A2, c.lda2, 4) || !al16(c.B2, c.ldb2, 4))) || (c.resid && !al16(c.resid, c.ldr, 4)))
+        return false;
+    const bool bias_only = c.bias && !c.resid && !c.cloud_bias && !c.xyz3;
+    int form = -1;
+    if (!two && c.b1_layout == 1 && bias_only) form = 0;
+    else if (!two && c.b1_layout == 1 && plain) form = 1;
+    else if (!two && c.b1_layout == 0 && plain) form = 2;
+    else if (!two && c.b1_layout == 0 && bias_only) form = 3;
+    else if (two && c.b1_layout == 0 && c.b2_layout == 0 && !c.bias && has_rc && !c.xyz3) form = 4;
+    else if (!two && c.b1_layout == 0 && !c.bias && has_rc && c.xyz3) form = c.relu ? 7 : 5;
+    else if (two && c.b1_layout == 1 && c.b2_layout == 0 && plain) form = 6;
+    if (form < 0 || (c.relu && form != 7)) return false;               // relu: the surface form only
+    if (has_rc && c.rows_per_cloud < 32 * p->RB) return false;         // a tile may span at most two clouds
+    *form_ = form;
+    return true;
+}
+
+bool hsp::gemm_wave_takes(const HspGemmCall& c) {
+    GwPlan p;
+    int form;
+    return gw_takes(c, c.relu ? 1 << 29 : 0, &p, &form);
+}
+
 extern "C" int hsp_gemm_wave_f32(const float* A1, int lda1, const float* B1, int ldb1, int b1_layout, int K1,
                                  const float* A2, int lda2, const float* B2, int ldb2, int b2_layout, int K2, int M, int N,
                                  const float* bias, const float* resid, int ldr, const float* cloud_bias,
@@ -520,12 +550,15 @@ extern "C" int hsp_gemm_wave_f32(const float* A1, int lda1, const float* B1, int
     if (resid && ldr < N) return HSP_ERR_BAD_ARG;
     if (cloud_bias && rows_per_cloud <= 0) return HSP_ERR_BAD_ARG;
     if ((xyz3 == nullptr) != (w3 == nullptr)) return HSP_ERR_BAD_ARG;
+    HspGemmCall c{};
+    c.A1 = A1; c.B1 = B1; c.A2 = A2; c.B2 = B2; c.resid = resid; c.C = C;
+    c.M = M; c.N = N; c.K1 = K1; c.K2 = K2; c.b1_layout = b1_layout; c.b2_layout = b2_layout; c.elem_bytes = 4;
+    c.lda1 = lda1; c.ldb1 = ldb1; c.lda2 = lda2; c.ldb2 = ldb2; c.ldr = ldr; c.ldc = ldc;
+    c.bias = bias != nullptr; c.cloud_bias = cloud_bias != nullptr; c.xyz3 = xyz3 != nullptr; c.relu = (cfg >> 29) & 1;
+    c.alpha_one = alpha == 1.0f; c.rows_per_cloud = rows_per_cloud;
     GwPlan p;
-    if (!gw_plan(M, N, K1, K2, cfg, &p)) return HSP_ERR_UNSUPPORTED;
-    auto al16 = [](const void* q, int ld) { return ((reinterpret_cast<size_t>(q) | ((size_t)ld * 4)) & 15) == 0; };
-    if (!al16(A1, lda1) || !al16(B1, ldb1) || !al16(C, ldc) || (two && (!al16(A2, lda2) || !al16(B2, ldb2))) ||
-        (resid && !al16(resid, ldr)))
-        return HSP_ERR_UNSUPPORTED;
+    int form;
+    if (!gw_takes(c, cfg, &p, &form)) return HSP_ERR_UNSUPPORTED;                    // -> hsp_gemm_rows_f32
     GwArgs g{};
     g.A[0] = A1; g.B[0] = B1; g.lda[0] = lda1; g.ldb[0] = ldb1; g.K[0] = K1; g.lb[0] = b1_layout;
     g.A[1] = A2; g.B[1] = B2; g.lda[1] = lda2; g.ldb[1] = ldb2; g.K[1] = K2; g.lb[1] = b2_layout;
@@ -535,24 +568,8 @@ extern "C" int hsp_gemm_wave_f32(const float* A1, int lda1, const float* B1, int
     g.TM = p.TM; g.TN = p.TN; g.T0 = K1 / 8; g.T1 = K2 / 8;
     g.base = p.base; g.nwaves = p.nwaves; g.u_rem = p.u_rem; g.npieces = p.npieces;
     g.order = (cfg >> 28) & 1;
-    if (((cfg >> 29) & 1) && !(xyz3 && has_rc_check(resid, cloud_bias))) return HSP_ERR_UNSUPPORTED;   // relu: surface form only
     const dim3 grid((unsigned)((p.nwaves + 3) / 4)), block(256);
     hipStream_t st = as_stream(stream);
-    // instantiated forms (anything else: HSP_ERR_UNSUPPORTED -> hsp_gemm_rows_f32):
-    //   0 fm   "nn"        + bias                      1 g W      "nn"                      2 x W^T  "nt"
-    //   3 x W^T "nt" + bias                            4 out      "nt" + "nt", residual + cloud bias
-    //   5 out0  "nt", residual + cloud bias + xyz3 (7: + relu, cfg bit 29)     6 gX       "nn" + "nt"
-    const bool has_rc = resid && cloud_bias;
-    int form = -1;
-    if (!two && b1_layout == 1 && bias && !resid && !cloud_bias && !xyz3) form = 0;
-    else if (!two && b1_layout == 1 && !bias && !resid && !cloud_bias && !xyz3) form = 1;
-    else if (!two && b1_layout == 0 && !bias && !resid && !cloud_bias && !xyz3) form = 2;
-    else if (!two && b1_layout == 0 && bias && !resid && !cloud_bias && !xyz3) form = 3;
-    else if (two && b1_layout == 0 && b2_layout == 0 && !bias && has_rc && !xyz3) form = 4;
-    else if (!two && b1_layout == 0 && !bias && has_rc && xyz3) form = ((cfg >> 29) & 1) ? 7 : 5;       // 7: + relu
-    else if (two && b1_layout == 1 && b2_layout == 0 && !bias && !resid && !cloud_bias && !xyz3) form = 6;
-    if (form < 0) return HSP_ERR_UNSUPPORTED;
-    if (has_rc && g.rpc < 32 * p.RB) return HSP_ERR_UNSUPPORTED;       // a tile may span at most two clouds
 #define GW_K(R, C_, W_, L0, L1, T_, E_) hipLaunchKernelGGL((gemm_wave_kernel<R, C_, W_, L0, L1, T_, E_>), grid, block, 0, st, g)
 #define GW_LAUNCH(R, C_, W_)                                   \
     do {                                                       \

@@ -671,10 +671,34 @@ extern "C" size_t hsp_gemm_x3_workspace_bytes(int M, int N, int K1, int K2) {
     return ns > 1 ? (size_t)ns * M * N * sizeof(float) : 0;
 }
 
+// The calls the x3 entry points run (c.bn: hsp_gemm_x3_f32, hsp_gemm_x3_bn_f32 or hsp_gemm_x3_bias_bn_f32), with their plan: the one
+// decision of gemm_x3_impl and of hsp_gemm_takes / hsp_gemm_route.  (The weight planes are the entry point's own business.)
+static bool x3_takes(const HspGemmCall& c, X3Plan* pl) {
+    const bool two = c.A2 != nullptr, bn_out = c.bn == HSP_GEMM_BN_OUT, bn_lin = c.bn == HSP_GEMM_BN_LINEAR;
+    const int M = c.M, N = c.N, K2 = two ? c.K2 : 0;
+    if (c.elem_bytes != 4 || c.xyz3 || (c.bn && c.relu) || !hsp_gemm_x3_supported(M, N, c.K1, K2)) return false;
+    if ((long long)M * c.lda1 * 4 >= (1ll << 31) || (two && (long long)M * c.lda2 * 4 >= (1ll << 31))) return false;
+    if (!al16(c.A1, c.lda1, 4) || (two && !al16(c.A2, c.lda2, 4))) return false;
+    // instantiated epilogues: 0 none, 1 bias, 2 residual (one source: the input-gradient chain of layers that share their input
+    // rows -- C may BE resid: an element is read and written by the same thread), 6 residual + per-cloud bias (the layer's out
+    // product), 14 = 6 + BatchNorm partials
+    // 4: per-cloud bias alone (one source: a Linear whose input is cat[per-cloud vector, rows] -- the vector's columns become a bias)
+    const int epi = (c.bias ? 1 : 0) | (c.resid ? 2 : 0) | (c.cloud_bias ? 4 : 0);
+    if (epi != 0 && epi != 1 && epi != 6 && !(epi == 2 && !two && c.alpha_one) && !(epi == 4 && !two)) return false;
+    // BatchNorm partials: the layer's out product (residual + per-cloud bias; 64-row tiles) or a Linear with bias (one source)
+    if ((bn_out && epi != 6) || (bn_lin && (epi != 1 || two)) || (c.bn && !c.alpha_one)) return false;
+    *pl = x3_plan_of(M, N, c.K1, K2, epi, c.bn != 0, bn_out, c.ldc);
+    if (pl->panel_R) return true;
+    const int bm = 64 * pl->wm;
+    const long long tiles_m = (M + bm - 1) / bm;
+    if (c.bn && tiles_m > 512) return false;                                    // (BN_MAX_PARTIALS of norm.hip)
+    return tiles_m * ((N + X3_BN - 1) / X3_BN) * pl->ns <= (1ll << 30);
+}
+
 static int gemm_x3_impl(const float* A1, int lda1, const hsp_bf16_t* P1, int ldp1, long long ps1, int K1,
                         const float* A2, int lda2, const hsp_bf16_t* P2, int ldp2, long long ps2, int K2, int M, int N,
                         const float* bias, const float* resid, int ldr, const float* cloud_bias, int rows_per_cloud,
-                        float alpha, float* C, int ldc, void* ws, size_t ws_bytes, float* bn_shift, float* bn_part,
+                        float alpha, float* C, int ldc, void* ws, size_t ws_bytes, float* bn_shift, float* bn_part, int bn_form,
                         hspStream_t stream) {
     if (!A1 || !P1 || !C || M <= 0 || N <= 0 || K1 <= 0 || lda1 < K1 || ldc < N) return HSP_ERR_BAD_ARG;
     const bool two = A2 != nullptr;
@@ -682,25 +706,24 @@ static int gemm_x3_impl(const float* A1, int lda1, const hsp_bf16_t* P1, int ldp
     if (!two) K2 = 0;
     if (resid && ldr < N) return HSP_ERR_BAD_ARG;
     if (cloud_bias && rows_per_cloud <= 0) return HSP_ERR_BAD_ARG;
-    if (!hsp_gemm_x3_supported(M, N, K1, K2)) return HSP_ERR_UNSUPPORTED;
-    if ((long long)M * lda1 * 4 >= (1ll << 31) || (two && (long long)M * lda2 * 4 >= (1ll << 31))) return HSP_ERR_UNSUPPORTED;
-    auto al16 = [](const void* q, long long ld, int es) { return ((reinterpret_cast<size_t>(q) | ((size_t)ld * es)) & 15) == 0; };
+    HspGemmCall c{};
+    c.A1 = A1; c.A2 = A2; c.resid = resid; c.C = C; c.M = M; c.N = N; c.K1 = K1; c.K2 = K2; c.elem_bytes = 4;
+    c.lda1 = lda1; c.lda2 = lda2; c.ldr = ldr; c.ldc = ldc; c.bias = bias != nullptr; c.cloud_bias = cloud_bias != nullptr;
+    c.alpha_one = alpha == 1.0f; c.rows_per_cloud = rows_per_cloud; c.bn = bn_form;
+    X3Plan pl;
+    if (!x3_takes(c, &pl)) return HSP_ERR_UNSUPPORTED;
     const int kp1 = (K1 + X3_BK - 1) / X3_BK * X3_BK, kp2 = (K2 + X3_BK - 1) / X3_BK * X3_BK;
-    if (!al16(A1, lda1, 4) || !al16(P1, ldp1, 2) || (ps1 & 7) || ldp1 < kp1) return HSP_ERR_UNSUPPORTED;
-    if (two && (!al16(A2, lda2, 4) || !al16(P2, ldp2, 2) || (ps2 & 7) || ldp2 < kp2)) return HSP_ERR_UNSUPPORTED;
+    if (!al16(P1, ldp1, 2) || (ps1 & 7) || ldp1 < kp1) return HSP_ERR_UNSUPPORTED;
+    if (two && (!al16(P2, ldp2, 2) || (ps2 & 7) || ldp2 < kp2)) return HSP_ERR_UNSUPPORTED;
     X3Args g{};
     g.A[0] = A1; g.P[0] = P1; g.lda[0] = lda1; g.ldp[0] = ldp1; g.K[0] = K1; g.ps[0] = ps1;
     g.A[1] = A2; g.P[1] = P2; g.lda[1] = lda2; g.ldp[1] = ldp2; g.K[1] = K2; g.ps[1] = ps2;
     g.C = C; g.ldc = ldc; g.M = M; g.N = N; g.bias = bias; g.resid = resid; g.ldr = ldr;
     g.cbias = cloud_bias; g.rpc = rows_per_cloud > 0 ? rows_per_cloud : 1; g.alpha = alpha;
     g.bn_shift = bn_shift; g.bn_part = bn_part;
-    const bool bn = bn_shift != nullptr;
-    // BatchNorm partials: the layer's out product (residual + per-cloud bias; 64-row tiles) or a Linear with bias (one source)
-    const bool bn_out = bn && resid && cloud_bias && !bias, bn_lin = bn && bias && !resid && !cloud_bias && !two;
-    if (bn && (!bn_part || !(bn_out || bn_lin))) return HSP_ERR_UNSUPPORTED;
+    const bool bn_out = bn_form == HSP_GEMM_BN_OUT, bn_lin = bn_form == HSP_GEMM_BN_LINEAR;
     hipStream_t st = as_stream(stream);
     const int epi = (bias ? 1 : 0) | (resid ? 2 : 0) | (cloud_bias ? 4 : 0);
-    const X3Plan pl = x3_plan_of(M, N, K1, K2, epi, bn, bn_out, ldc);
     {   // the panel form (x3_panel_slots)
         const int epi0 = epi, R = pl.panel_R;
         if (R) {
@@ -730,21 +753,13 @@ static int gemm_x3_impl(const float* A1, int lda1, const hsp_bf16_t* P1, int ldp
     int ns = pl.ns;
     if (ns > 1 && (!ws || (size_t)ns * M * N * sizeof(float) > ws_bytes)) ns = 1;
     g.nsplit = ns; g.ws = ns > 1 ? reinterpret_cast<float*>(ws) : nullptr;
-    const long long items = (long long)g.tiles_m * g.tiles_n * ns;
-    if (items > (1ll << 30)) return HSP_ERR_UNSUPPORTED;
-    const dim3 grid((unsigned)items), block(256);
-    // instantiated epilogues: 0 none, 1 bias, 2 residual (one source: the input-gradient chain of layers that share their input
-    // rows -- C may BE resid: an element is read and written by the same thread), 6 residual + per-cloud bias (the layer's out
-    // product), 14 = 6 + BatchNorm partials
-    // 4: per-cloud bias alone (one source: a Linear whose input is cat[per-cloud vector, rows] -- the vector's columns become a bias)
-    if (epi != 0 && epi != 1 && epi != 6 && !(epi == 2 && !two && alpha == 1.0f) && !(epi == 4 && !two)) return HSP_ERR_UNSUPPORTED;
+    const dim3 grid((unsigned)((long long)g.tiles_m * g.tiles_n * ns)), block(256);
     if (bn_out) {
         if (two) hipLaunchKernelGGL((gemm_x3_kernel<1, true, 14, 0>), grid, block, 3 * (size_t)(64 + X3_BN) * 64, st, g);
         else hipLaunchKernelGGL((gemm_x3_kernel<1, false, 14, 0>), grid, block, 3 * (size_t)(64 + X3_BN) * 64, st, g);
         return check_launch();
     }
     if (bn_lin) {
-        if (g.tiles_m > 512) return HSP_ERR_UNSUPPORTED;                       // (BN_MAX_PARTIALS of norm.hip)
         if (wm == 2) hipLaunchKernelGGL((gemm_x3_kernel<2, false, 9, 0>), grid, block, 3 * (size_t)(128 + X3_BN) * 64, st, g);
         else hipLaunchKernelGGL((gemm_x3_kernel<1, false, 9, 0>), grid, block, 3 * (size_t)(64 + X3_BN) * 64, st, g);
         return check_launch();
@@ -793,7 +808,7 @@ extern "C" int hsp_gemm_x3_bias_bn_f32(const float* A1, int lda1, const hsp_bf16
                                        const float* bias, float* C, int ldc, float* bn_shift, float* bn_part, hspStream_t stream) {
     if (!bn_shift || !bn_part || !bias) return HSP_ERR_BAD_ARG;
     return gemm_x3_impl(A1, lda1, P1, ldp1, ps1, K1, nullptr, 0, nullptr, 0, 0, 0, M, N, bias, nullptr, 0, nullptr, 0, 1.0f, C, ldc,
-                        nullptr, 0, bn_shift, bn_part, stream);
+                        nullptr, 0, bn_shift, bn_part, HSP_GEMM_BN_LINEAR, stream);
 }
 
 // ================================================================================================================================
@@ -1012,31 +1027,42 @@ __global__ __launch_bounds__(256) void small_pair_kernel(const float* __restrict
 
 }  // namespace hsp
 
+static size_t small_rows_nn_lds(int M, int K) { return ((size_t)M * K + 3 * 64 * SR_MAXM) * 4; }
+
+// The calls hsp_small_rows_f32 runs (one source, no rider; *mfma: on its matrix-core form): the one decision of the entry point
+// and of hsp_gemm_takes / hsp_gemm_route
+static bool small_rows_takes(const HspGemmCall& c, bool* mfma) {
+    if (c.elem_bytes != 4 || c.A2 || c.bias || c.resid || c.cloud_bias || c.xyz3 || c.bn) return false;
+    if (c.K1 > 2048 || c.M > 64) return false;
+    *mfma = c.K1 % 128 == 0 && (c.b1_layout == 1 || (al16(c.A1, c.lda1, 4) && al16(c.B1, c.ldb1, 4)));
+    if (*mfma) return true;
+    return c.M <= SR_MAXM && (c.b1_layout == 0 || small_rows_nn_lds(c.M, c.K1) <= 64 * 1024);
+}
+
 /* out (M, N) = alpha * A (M, K) op(W): w_layout 0 = W is (N, K) ("nt"), 1 = W is (K, N) ("nn"); M <= 16 rows (one per cloud),
  * K <= 2048.  gcn3d.py:186 (the f_global half of conv2) and its input gradient. */
 extern "C" int hsp_small_rows_f32(const float* A, int lda, const float* W, int ldw, int w_layout, int M, int N, int K, float alpha,
                                   float* out, int ldo, hspStream_t stream) {
     if (!A || !W || !out || M <= 0 || N <= 0 || K <= 0 || lda < K || ldo < N) return HSP_ERR_BAD_ARG;
-    if (K > 2048 || M > 64) return HSP_ERR_UNSUPPORTED;
-    hipStream_t st = as_stream(stream);
     if (w_layout != 0 && w_layout != 1) return HSP_ERR_BAD_ARG;
-    const bool al = ((reinterpret_cast<size_t>(A) | reinterpret_cast<size_t>(W) | ((size_t)lda * 4) | ((size_t)ldw * 4)) & 15) == 0;
-    if (K % 128 == 0 && (w_layout == 1 || al)) {
+    HspGemmCall c{};
+    c.A1 = A; c.B1 = W; c.C = out; c.M = M; c.N = N; c.K1 = K; c.b1_layout = w_layout; c.elem_bytes = 4;
+    c.lda1 = lda; c.ldb1 = ldw; c.ldc = ldo; c.alpha_one = alpha == 1.0f;
+    bool mfma;
+    if (!small_rows_takes(c, &mfma)) return HSP_ERR_UNSUPPORTED;
+    hipStream_t st = as_stream(stream);
+    if (mfma) {
         const dim3 grid((N + 15) / 16, (M + 15) / 16);
         if (w_layout == 1)
             hipLaunchKernelGGL(small_rows_mfma_kernel<true>, grid, dim3(256), 0, st, A, lda, W, ldw, M, N, K, alpha, out, ldo);
         else
             hipLaunchKernelGGL(small_rows_mfma_kernel<false>, grid, dim3(256), 0, st, A, lda, W, ldw, M, N, K, alpha, out, ldo);
-        return check_launch();
-    }
-    if (M > SR_MAXM) return HSP_ERR_UNSUPPORTED;
-    if (w_layout == 0)
+    } else if (w_layout == 0) {
         hipLaunchKernelGGL(small_rows_nt_kernel, dim3((N + 7) / 8), dim3(256), (size_t)M * K * 4, st, A, lda, W, ldw, M, N, K, alpha, out, ldo);
-    else if (w_layout == 1) {
-        const size_t lds = ((size_t)M * K + 3 * 64 * SR_MAXM) * 4;
-        if (lds > 64 * 1024) return HSP_ERR_UNSUPPORTED;
-        hipLaunchKernelGGL(small_rows_nn_kernel, dim3((N + 63) / 64), dim3(256), lds, st, A, lda, W, ldw, M, N, K, alpha, out, ldo);
-    } else return HSP_ERR_BAD_ARG;
+    } else {
+        hipLaunchKernelGGL(small_rows_nn_kernel, dim3((N + 63) / 64), dim3(256), small_rows_nn_lds(M, K), st, A, lda, W, ldw, M, N, K,
+                           alpha, out, ldo);
+    }
     return check_launch();
 }
 
@@ -1078,7 +1104,7 @@ extern "C" int hsp_gemm_x3_f32(const float* A1, int lda1, const hsp_bf16_t* P1, 
                                const float* bias, const float* resid, int ldr, const float* cloud_bias, int rows_per_cloud,
                                float alpha, float* C, int ldc, void* ws, size_t ws_bytes, hspStream_t stream) {
     return gemm_x3_impl(A1, lda1, P1, ldp1, ps1, K1, A2, lda2, P2, ldp2, ps2, K2, M, N, bias, resid, ldr, cloud_bias, rows_per_cloud,
-                        alpha, C, ldc, ws, ws_bytes, nullptr, nullptr, stream);
+                        alpha, C, ldc, ws, ws_bytes, nullptr, nullptr, HSP_GEMM_BN_NONE, stream);
 }
 
 /* the layer's out product (residual + per-cloud bias) that ALSO leaves the first pass of the train-mode BatchNorm that follows
@@ -1089,7 +1115,53 @@ extern "C" int hsp_gemm_x3_bn_f32(const float* A1, int lda1, const hsp_bf16_t* P
                                   const float* A2, int lda2, const hsp_bf16_t* P2, int ldp2, long long ps2, int K2, int M, int N,
                                   const float* resid, int ldr, const float* cloud_bias, int rows_per_cloud, float* C, int ldc,
                                   float* bn_shift, float* bn_part, hspStream_t stream) {
-    if (!bn_shift || !bn_part || (M + 63) / 64 > 512) return HSP_ERR_BAD_ARG;
+    if (!bn_shift || !bn_part) return HSP_ERR_BAD_ARG;
     return gemm_x3_impl(A1, lda1, P1, ldp1, ps1, K1, A2, lda2, P2, ldp2, ps2, K2, M, N, nullptr, resid, ldr, cloud_bias,
-                        rows_per_cloud, 1.0f, C, ldc, nullptr, 0, bn_shift, bn_part, stream);
+                        rows_per_cloud, 1.0f, C, ldc, nullptr, 0, bn_shift, bn_part, HSP_GEMM_BN_OUT, stream);
+}
+
+
+// ---- which kernel a product call goes to ----------------------------------------------------------------------------------------
+static bool gemm_takes(const HspGemmCall& c, int route) {
+    X3Plan pl;
+    bool mfma;
+    switch (route) {
+        case HSP_GEMM_ROUTE_SMALL_ROWS: return small_rows_takes(c, &mfma);
+        case HSP_GEMM_ROUTE_X3: return c.bn == HSP_GEMM_BN_NONE && x3_takes(c, &pl);
+        case HSP_GEMM_ROUTE_X3_BN: return c.bn != HSP_GEMM_BN_NONE && x3_takes(c, &pl);
+        case HSP_GEMM_ROUTE_WAVE: return c.bn == HSP_GEMM_BN_NONE && gemm_wave_takes(c);
+        case HSP_GEMM_ROUTE_TILE: return c.bn == HSP_GEMM_BN_NONE && gemm_rows_takes(c);
+    }
+    return false;
+}
+
+static bool gemm_call_ok(const HspGemmCall* c) {
+    return c && c->A1 && c->B1 && c->M > 0 && c->N > 0 && c->K1 > 0 && (!c->A2 || (c->B2 && c->K2 > 0)) &&
+           (c->elem_bytes == 4 || c->elem_bytes == 2);
+}
+
+extern "C" int hsp_gemm_takes(const HspGemmCall* c, int route) { return gemm_call_ok(c) && gemm_takes(*c, route) ? 1 : 0; }
+
+extern "C" int hsp_gemm_route(const HspGemmCall* call) {
+    if (!gemm_call_ok(call)) return HSP_GEMM_ROUTE_NONE;
+    HspGemmCall c = *call;
+    const bool epi = c.bias || c.resid || c.cloud_bias, has_rc = c.resid && c.cloud_bias;
+    // x3 before wave before tile.  x3 from 256 rows on (the layer's out product with BatchNorm partials: from clouds of 64 rows
+    // on); an epilogue rules out split-K, and under 128 tiles of 64 rows that leaves too few workgroups
+    const bool x3 = c.allow_x3 && (c.bn == HSP_GEMM_BN_OUT ? c.rows_per_cloud >= 64 : c.M >= 256) &&
+                    !(epi && (long long)((c.M + 63) / 64) * ((c.N + 127) / 128) < 128);
+    if (c.bn != HSP_GEMM_BN_NONE) {
+        if (x3 && gemm_takes(c, HSP_GEMM_ROUTE_X3_BN)) return HSP_GEMM_ROUTE_X3_BN;
+        c.bn = HSP_GEMM_BN_NONE;
+        return hsp_gemm_route(&c);
+    }
+    if (gemm_takes(c, HSP_GEMM_ROUTE_SMALL_ROWS)) return HSP_GEMM_ROUTE_SMALL_ROWS;    // a row per cloud: one small launch
+    if (x3 && gemm_takes(c, HSP_GEMM_ROUTE_X3)) return HSP_GEMM_ROUTE_X3;
+    // the LDS-free wave kernel when the output is large against a short K -- many tiles that each live for a few k-blocks: fm =
+    // X W + b and the g Wa products; measured 13-14 us against 15-19 us, 24-48 us against 36-67 us -- the LDS-staged tile kernel
+    // (any K / alignment, split-K) otherwise
+    const int K = c.K1 + (c.A2 ? c.K2 : 0);
+    if (K <= 512 && (long long)c.M * c.N >= 512 * 1024 && (!has_rc || c.rows_per_cloud >= 64) && gemm_takes(c, HSP_GEMM_ROUTE_WAVE))
+        return HSP_GEMM_ROUTE_WAVE;
+    return gemm_takes(c, HSP_GEMM_ROUTE_TILE) ? HSP_GEMM_ROUTE_TILE : HSP_GEMM_ROUTE_NONE;
 }

@@ -9,7 +9,8 @@ import os
 
 import torch
 
-from ._lib import HspError, check, lib
+from ._lib import (BN_LINEAR, BN_OUT, ROUTE_SMALL_ROWS, ROUTE_TILE, ROUTE_WAVE, ROUTE_X3, ROUTE_X3_BN, HspError, HspGemmCall, check,
+                   lib)
 
 _vp = ctypes.c_void_p
 
@@ -765,37 +766,44 @@ def wgrad(A2, B2, out=None, colsum=False):
     N = B2.shape[1]
     if out is None:
         out = torch.empty(M, N, dtype=torch.float32, device=A2.device)
-    bf16 = A2.dtype == torch.bfloat16
-    if _wgrad_ragged_ok(A2, B2, out):          # (fp32: hsp_wgrad_f32 takes the ragged M itself; bf16: an entry point of its own)
-        return _wgrad_custom(A2, B2, out, colsum, entry="hsp_wgrad_ragged" if bf16 else "hsp_wgrad")
-    if _wgrad_ok(A2, B2, out):
-        return _wgrad_custom(A2, B2, out, colsum)
-    if bf16:                                   # (the general tile kernel below is the fp32 rows' fallback only)
-        raise HspError("bf16 weight gradient: channel counts must be multiples of 64")
+    entry = _wgrad_entry_of(A2, B2, out)
+    if entry:
+        return _wgrad_custom(A2, B2, out, colsum, entry=entry)
+    if A2.dtype == torch.bfloat16:             # (the general tile kernel below is the fp32 rows' fallback only)
+        raise HspError("bf16 weight gradient: shape or row pitch outside the split-K kernels (hsp_wgrad_plan)")
     return _wgrad_fallback(A2, B2, out, colsum)
 
 
-def _wgrad_ragged_ok(A2, B2, out):
-    """A2^T B2 with M = A2.shape[1] NOT a multiple of 64 (the heads' first layers: K = 1286 / 1289 / 771 input columns,
-    PoseR.py:27, PoseTs.py:32, FaceRecon.py:38,116) on the x3 kernel: fp32 rows of A2 on a 16-byte pitch that covers ceil4(M)
-    (``assemble_feat`` / ``cat_rows_pitched`` lay them out so), N a multiple of 128.  bf16 rows (``hsp_wgrad_ragged_bf16``): any
-    M that is no multiple of 64, both operands on a 16-byte pitch (feat's 1286 columns on their 1288 pitch)"""
-    K, M = A2.shape
-    N = B2.shape[1]
-    if A2.dtype == torch.bfloat16:
-        return (M % 64 != 0 and N % 128 == 0 and A2.stride(1) == 1 and B2.stride(1) == 1 and A2.stride(0) % 8 == 0
-                and B2.stride(0) % 8 == 0)
-    return (M % 64 != 0 and M >= 128 and N % 128 == 0
-            and -(-M // 128) * (N // 128) >= 4 and A2.dtype == torch.float32 and B2.dtype == torch.float32 and A2.is_cuda
-            and A2.stride(1) == 1 and B2.stride(1) == 1 and out.stride(1) == 1 and A2.stride(0) % 4 == 0 and B2.stride(0) % 4 == 0
-            and A2.stride(0) >= (M + 3) // 4 * 4 and A2.data_ptr() % 16 == 0 and B2.data_ptr() % 16 == 0)
+def _wgrad_plan(M, N, K, lda, ldb, dtype, al16, ragged_entry=0):
+    return lib().hsp_wgrad_plan(M, N, K, 2 if dtype == torch.bfloat16 else 4, int(al16), lda, ldb, ragged_entry,
+                                (ctypes.c_int * 4)()) == 0
 
 
-def _wgrad_ok(A2, B2, out):
-    K, M = A2.shape
-    N = B2.shape[1]
-    return (M % 64 == 0 and N % 64 == 0 and A2.stride(1) == 1 and B2.stride(1) == 1 and out.stride(1) == 1
-            and A2.stride(0) % 2 == 0 and B2.stride(0) % 2 == 0 and A2.dtype in _FEAT_DTYPES and A2.is_cuda)
+def _wgrad_entry(M, N, K, lda, ldb, dtype, al16=True):
+    """the entry-point family that takes A^T B for rows A (K, M), B (K, N) on pitches lda / ldb (al16: both start on 16 bytes), or
+    None: the dispatch's own answer (``hsp_wgrad_plan``).  M off the 64-wide tiles (the heads' first layers: 1286 / 1289 / 771
+    input columns, PoseR.py:27, PoseTs.py:32, FaceRecon.py:38,116): ``hsp_wgrad_f32`` takes fp32 rows itself, bf16 rows have an
+    entry point of their own."""
+    if dtype not in _FEAT_DTYPES:
+        return None
+    if _wgrad_plan(M, N, K, lda, ldb, dtype, al16):
+        return "hsp_wgrad"
+    if dtype == torch.bfloat16 and _wgrad_plan(M, N, K, lda, ldb, dtype, al16, 1):
+        return "hsp_wgrad_ragged"
+    return None
+
+
+def _wgrad_sliced(M, N, K, lda, ldb, dtype, al16=True):
+    """``_wgrad_entry`` for the K-sliced problems alone (both extents in whole 64-wide tiles: the pair launch's own shape rule)"""
+    return (_wgrad_plan(M, N, K, lda, ldb, dtype, al16)
+            and lib().hsp_wgrad_pair_plan(M, N, K, M, N, K, (ctypes.c_int * 7)()) == 0)
+
+
+def _wgrad_entry_of(A2, B2, out, ask=None):
+    if not (A2.is_cuda and A2.stride(1) == 1 and B2.stride(1) == 1 and out.stride(1) == 1):
+        return None
+    return (ask or _wgrad_entry)(A2.shape[1], B2.shape[1], A2.shape[0], A2.stride(0), B2.stride(0), A2.dtype,
+                                 (A2.data_ptr() | B2.data_ptr()) % 16 == 0)
 
 
 def wgrad_pair(A0, B0, out0, A1, B1, out1, colsum_of=None):
@@ -805,7 +813,8 @@ def wgrad_pair(A0, B0, out0, A1, B1, out1, colsum_of=None):
     ``colsum_of`` = (g (B,N,C) fp32, mom (B,C)): ask for mom = the per-cloud column sums of g (``hsp_colsum_cloud_f32``'s bits) as a
     rider of that launch; returns True where it rode along, False (mom untouched, the products issued as without it) elsewhere."""
     batch = WgradBatch.current
-    if batch is None or A0.dtype != torch.float32 or not _wgrad_ok(A0, B0, out0) or not _wgrad_ok(A1, B1, out1):
+    if (batch is None or A0.dtype != torch.float32 or not _wgrad_entry_of(A0, B0, out0, _wgrad_sliced)
+            or not _wgrad_entry_of(A1, B1, out1, _wgrad_sliced)):
         wgrad(A0, B0, out=out0)
         wgrad(A1, B1, out=out1)
         return False
@@ -1041,21 +1050,20 @@ def x3_refresh():
         x3_planes.refresh()
 
 
-def gemm_x3_ok(A1, B1, A2, B2, bias, resid, cloud_bias, xyz3, out, M, N):
-    if not GEMM_X3 or xyz3 is not None or N < 64 or A1.dtype != torch.float32:
-        return False
-    K2 = A2.shape[1] if A2 is not None else 0
-    if not lib().hsp_gemm_x3_supported(M, N, A1.shape[1], K2):
-        return False
-    epi = (1 if bias is not None else 0) | (2 if resid is not None else 0) | (4 if cloud_bias is not None else 0)
-    if epi not in (0, 1, 6) and not (epi in (2, 4) and A2 is None):
-        return False
-    if epi and ((M + 63) // 64) * ((N + 127) // 128) < 128:            # (an epilogue rules out split-K: too few workgroups)
-        return False
-    for t_ in (A1, A2):
-        if t_ is not None and (t_.data_ptr() % 16 or (t_.stride(0) * 4) % 16):
-            return False
-    return True
+def _gemm_route(A1, B1, nn1=False, A2=None, B2=None, nn2=False, bias=None, resid=None, cloud_bias=None, rows_per_cloud=0, out=None,
+                alpha=1.0, xyz3=None, relu=False, bn=0):
+    """the kernel family (``_lib.ROUTE_*``) a product of the ``gemm_rows`` contract goes to: the library's answer
+    (``hsp_gemm_route``, include/hsp.h) to the call described as an ``HspGemmCall``.  out None: a dense result the wrapper allocates;
+    bn: the BatchNorm-partials form asked for (``_lib.BN_*``)"""
+    N = B1.shape[1] if nn1 else B1.shape[0]
+    two = A2 is not None
+    call = HspGemmCall(A1.data_ptr(), B1.data_ptr(), A2.data_ptr() if two else None, B2.data_ptr() if two else None,
+                       resid.data_ptr() if resid is not None else None, out.data_ptr() if out is not None else None,
+                       A1.shape[0], N, A1.shape[1], A2.shape[1] if two else 0, int(nn1), int(nn2), A1.element_size(),
+                       _ld(A1), _ld(B1), _ld(A2) if two else 0, _ld(B2) if two else 0, _ld(resid) if resid is not None else 0,
+                       _ld(out) if out is not None else N, bias is not None, cloud_bias is not None, xyz3 is not None, bool(relu),
+                       alpha == 1.0, int(rows_per_cloud), bn, GEMM_X3)
+    return lib().hsp_gemm_route(ctypes.byref(call))
 
 
 def gemm_x3_bn(A1, B1, A2, B2, resid, cloud_bias, rows_per_cloud, out):
@@ -1079,9 +1087,9 @@ def gemm_x3_bn(A1, B1, A2, B2, resid, cloud_bias, rows_per_cloud, out):
 def linear_bn_part_ok(x2, W, bias):
     """a Linear (R, K) x (N, K)^T + bias whose product can also leave the first pass of the train-mode BatchNorm behind it
     (``hsp_gemm_x3_bias_bn_f32``)"""
-    R, N = x2.shape[0], W.shape[0]
-    return (bias is not None and R >= 256 and x2.dtype == torch.float32 and N % 4 == 0 and 256 % (N // 4) == 0
-            and gemm_x3_ok(x2, W, None, None, bias, None, None, None, None, R, N) and lib().hsp_gemm_x3_bn_tiles(R, N) <= 512)
+    N = W.shape[0]
+    return (bias is not None and N % 4 == 0 and 256 % (N // 4) == 0
+            and _gemm_route(x2, W, bias=bias, bn=BN_LINEAR) == ROUTE_X3_BN)
 
 
 def linear_bn_part(x2, W, bias):
@@ -1138,9 +1146,9 @@ def gemm_x3(A1, B1, nn1=False, A2=None, B2=None, nn2=False, bias=None, resid=Non
 
 def _layer_out_bn_ok(x2, w_ste, F2, Wa, t2, out3, relu):
     """the layer's out product can also leave the first pass of the BatchNorm behind it (``gemm_x3_bn``)"""
-    return (x2.shape[1] != 3 and not relu
-            and gemm_x3_ok(x2, w_ste, F2, Wa, None, F2, t2, None, None, x2.shape[0], out3.shape[2])
-            and (x2.shape[0] + 63) // 64 <= 512 and out3.shape[1] >= 64)
+    return (x2.shape[1] != 3                  # (HSlayer_surface: the STE on raw coordinates rides in the plain product's epilogue)
+            and _gemm_route(x2, w_ste, False, F2, Wa, False, resid=F2, cloud_bias=t2, rows_per_cloud=out3.shape[1], relu=relu,
+                            bn=BN_OUT) == ROUTE_X3_BN)
 
 
 def _ste_moments_ok(C):
@@ -1162,38 +1170,23 @@ def gemm_own(A1, B1, nn1=False, A2=None, B2=None, nn2=False, bias=None, resid=No
     """the fp32 product of ``gemm_rows`` on whichever hand-written kernel suits the shape: the LDS-free wave-level kernel
     (csrc/gemm_wave.hip) when the output is large against a short K -- many tiles that each live for a few k-blocks: fm = X W + b
     and the g Wa products; measured 13-14 us against 15-19 us, 24-48 us against 36-67 us -- and the LDS-staged tile kernel
-    (csrc/gemm_rows.hip: any K / alignment, split-K) otherwise."""
+    (csrc/gemm_rows.hip: any K / alignment, split-K) otherwise.  Which one: ``hsp_gemm_route``, the functions the entry points
+    themselves decline by plus the thresholds between kernels that would both run (csrc/gemm_x3.hip)."""
     if A1.dtype == torch.bfloat16 and not relu:      # bf16 rows: one kernel family; every choice below is between fp32 kernels
         return gemm_rows(A1, B1, nn1, A2, B2, nn2, bias=bias, resid=resid, cloud_bias=cloud_bias, rows_per_cloud=rows_per_cloud,
                          out=out, alpha=alpha, xyz3=xyz3, w3=w3)
-    M, K1 = A1.shape
-    N = B1.shape[1] if nn1 else B1.shape[0]
-    K2 = A2.shape[1] if A2 is not None else 0
-    if ((M <= 16 or (M <= 64 and K1 % 128 == 0 and (nn1 or all(_al16(t) for t in (A1, B1))))) and A2 is None and bias is None
-            and resid is None and cloud_bias is None and xyz3 is None and K1 <= 2048
-            and A1.dtype == torch.float32 and A1.stride(1) == 1 and B1.stride(1) == 1):
-        return small_rows(A1, B1, nn1, out=out, alpha=alpha)          # a row per cloud: one small launch
-    # (the x3 kernel stores -- and reads its residual -- element by element: its output rows need no 16-byte pitch; a result it
-    # allocates itself for N = 1286 has none either)
-    if M >= 256 and gemm_x3_ok(A1, B1, A2, B2, bias, resid, cloud_bias, xyz3, out, M, N) and (out is None or out.stride(1) == 1):
-        res = gemm_x3(A1, B1, nn1, A2, B2, nn2, bias=bias, resid=resid, cloud_bias=cloud_bias, rows_per_cloud=rows_per_cloud,
-                      out=out, alpha=alpha)
-        return torch.relu_(res) if relu else res
-    two, rc = A2 is not None, resid is not None and cloud_bias is not None
-    plain = bias is None and resid is None and cloud_bias is None and xyz3 is None
-    # the forms gemm_wave.hip instantiates: fm (nn + bias), g W (nn), x W^T (nt [+ bias]), out (nt + nt, residual + cloud bias),
-    # surface out (nt, residual + cloud bias + xyz3), gX (nn + nt)
-    form = ((not two and nn1 and (plain or (bias is not None and resid is None and cloud_bias is None and xyz3 is None)))
-            or (not two and not nn1 and (plain or (bias is not None and resid is None and cloud_bias is None and xyz3 is None)))
-            or (two and not nn1 and not nn2 and bias is None and rc and xyz3 is None)
-            or (not two and not nn1 and bias is None and rc and xyz3 is not None)
-            or (two and nn1 and not nn2 and plain))
-    if (form and A1.dtype == torch.float32 and K1 + K2 <= 512 and M * N >= 512 * 1024 and K1 % 32 == 0 and K2 % 32 == 0
-            and N % 32 == 0 and (not rc or rows_per_cloud >= 64) and all(_al16(t) for t in (A1, B1, A2, B2, resid, out))):
-        return gemm_wave(A1, B1, nn1, A2, B2, nn2, bias=bias, resid=resid, cloud_bias=cloud_bias, rows_per_cloud=rows_per_cloud,
-                         out=out, alpha=alpha, xyz3=xyz3, w3=w3, cfg=(1 << 29) if relu else 0)
-    res = gemm_rows(A1, B1, nn1, A2, B2, nn2, bias=bias, resid=resid, cloud_bias=cloud_bias, rows_per_cloud=rows_per_cloud,
-                    out=out, alpha=alpha, xyz3=xyz3, w3=w3)
+    kw = dict(bias=bias, resid=resid, cloud_bias=cloud_bias, rows_per_cloud=rows_per_cloud, out=out, alpha=alpha)
+    route = _gemm_route(A1, B1, nn1, A2, B2, nn2, xyz3=xyz3, relu=relu, **kw)
+    if route == ROUTE_SMALL_ROWS:
+        res = small_rows(A1, B1, nn1, out=out, alpha=alpha)           # a row per cloud: one small launch
+    elif route == ROUTE_X3:
+        res = gemm_x3(A1, B1, nn1, A2, B2, nn2, **kw)
+    elif route == ROUTE_WAVE:
+        return gemm_wave(A1, B1, nn1, A2, B2, nn2, xyz3=xyz3, w3=w3, cfg=(1 << 29) if relu else 0, **kw)   # (relu in the epilogue)
+    elif route == ROUTE_TILE:
+        res = gemm_rows(A1, B1, nn1, A2, B2, nn2, xyz3=xyz3, w3=w3, **kw)
+    else:
+        raise HspError(f"gemm_own: no kernel takes this product (hsp_gemm_route: {tuple(A1.shape)} {A1.dtype} rows)")
     return torch.relu_(res) if relu else res
 
 
@@ -1861,7 +1854,7 @@ class _LinearRows(torch.autograd.Function):
         R, Cout = g.shape
         Cin = x2.shape[1]
         gb = None
-        if (Cout % 64 == 0 and Cin % 64 == 0) or _wgrad_ragged_ok(x2, g, g):
+        if _wgrad_entry(Cin, Cout, R, x2.stride(0), g.stride(0), torch.float32, (x2.data_ptr() | g.data_ptr()) % 16 == 0):
             gwt, gb = wgrad(x2, g, colsum=True)                 # (Cin, Cout) = dW^T, column sums of g = db
             gw = gwt.t()
         elif _thin_wgrad_ok(Cout, Cin, R, g):
@@ -1953,7 +1946,7 @@ def fan_linear_rows_ok(x, xyz, weights):
     for w in weights:
         if w.dim() != 2 or w.shape[0] % 128 or w.shape[1] not in (K, K + 3) or (w.shape[1] == K + 3 and xyz is None):
             return False
-        if not _wgrad_ragged_ok(x, torch.empty(0, w.shape[0], device=x.device), x) and not (K % 64 == 0 and w.shape[0] % 64 == 0):
+        if not _wgrad_entry(K, w.shape[0], R, x.stride(0), w.shape[0], torch.float32):
             return False
     return True
 

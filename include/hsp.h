@@ -495,6 +495,36 @@ int hsp_small_pair_f32(const float *gt, int ldgt, int B, int Ma, const float *W,
                        int ldnn, const float *c, int ldc, int Nb, float *out_o, int ldo, const float *mom, int ldm, int Cm,
                        float *gste, hspStream_t stream);
 
+/* ---- which of the kernels above takes a product call (host-only: no HIP call, no operand is dereferenced) ------------------
+ * HspGemmCall (a HOST struct) describes a call of the hsp_gemm_rows_f32 contract: extents, layouts and pitches as there;
+ * A2 == NULL: one source (K2 is ignored); resid == NULL: no residual; C == NULL: the caller allocates the result dense (ldc = N,
+ * on 16 bytes); elem_bytes 4 | 2; bias / cloud_bias / xyz3 / relu: != 0 where the call has that rider; alpha_one: alpha == 1;
+ * bn: the BatchNorm-partials form asked for (HSP_GEMM_BN_OUT: hsp_gemm_x3_bn_f32, HSP_GEMM_BN_LINEAR:
+ * hsp_gemm_x3_bias_bn_f32); allow_x3 == 0 keeps the product off csrc/gemm_x3.hip's matrix-core kernels.
+ *   hsp_gemm_takes(call, route): 1 where the entry point of that family runs the call -- the function that entry point itself
+ *       returns HSP_ERR_UNSUPPORTED by (hsp_gemm_x3_supported / hsp_gemm_wave_supported are its shape-only clause) -- else 0
+ *   hsp_gemm_route(call): the family the call goes to: the first of small rows, x3 (with the partials where bn asks for them
+ *       and the kernel leaves them; else the route of the same call without), wave, tile that takes it AND is the faster
+ *       choice for the shape (x3: M >= 256 and, with an epilogue, >= 128 tiles; wave: K1 + K2 <= 512, M N >= 512 K, clouds of
+ *       >= 64 rows); HSP_GEMM_ROUTE_NONE where no kernel takes it */
+#define HSP_GEMM_ROUTE_NONE 0
+#define HSP_GEMM_ROUTE_SMALL_ROWS 1   /* hsp_small_rows_f32 */
+#define HSP_GEMM_ROUTE_X3 2           /* hsp_gemm_x3_f32 */
+#define HSP_GEMM_ROUTE_X3_BN 3        /* hsp_gemm_x3_bn_f32 / hsp_gemm_x3_bias_bn_f32, by HspGemmCall.bn */
+#define HSP_GEMM_ROUTE_WAVE 4         /* hsp_gemm_wave_f32 (relu: cfg bit 29) */
+#define HSP_GEMM_ROUTE_TILE 5         /* hsp_gemm_rows_f32 / hsp_gemm_rows_bf16 */
+#define HSP_GEMM_BN_NONE 0
+#define HSP_GEMM_BN_OUT 1
+#define HSP_GEMM_BN_LINEAR 2
+typedef struct HspGemmCall {
+    const void *A1, *B1, *A2, *B2, *resid, *C;
+    int M, N, K1, K2, b1_layout, b2_layout, elem_bytes;
+    int lda1, ldb1, lda2, ldb2, ldr, ldc;
+    int bias, cloud_bias, xyz3, relu, alpha_one, rows_per_cloud, bn, allow_x3;
+} HspGemmCall;
+int hsp_gemm_takes(const HspGemmCall *call, int route);
+int hsp_gemm_route(const HspGemmCall *call);
+
 /* fp32 master parameters -> bf16 working copies for the *_bf16 entry points, every tensor of a step in one launch:
  * entry e copies src (rows, cols; row pitch ld) to dst (rows, cols) and / or dstT (cols, rows) -- either may be NULL --
  * rounding to nearest even.  tile0 = number of 32 x 32 tiles of the entries before e; table_dev lives in DEVICE memory. */

@@ -1,5 +1,5 @@
 """The case table of the dense-product reference tests: the smallest shapes on each side of each pick rule of csrc/gemm.hip,
-with the plan each is meant to enter.  tests/test_gemm_plans_host.py asserts the plans on the CPU (the plan queries are host
+with the plan each is meant to enter, and (ROUTES) product calls with the kernel family hsp_gemm_route sends each to.  tests/test_gemm_plans_host.py asserts the plans on the CPU (the plan queries are host
 code); tests/test_gpu_gemm_reference.py asserts them again and runs the kernels."""
 import ctypes
 from collections import namedtuple
@@ -67,6 +67,11 @@ WGRAD = (
     + [_w("rbf16", M, 128, 257, _c8(M) + pad, form=BF16, slices=2) for M, pad in ((129, 0), (136, 0), (136, 8), (1286, 0))]
 )
 
+# ragged bf16 rows hsp_wgrad_ragged_bf16 declines (ops.wgrad used to send them there): fewer than 128 output rows, base pointers off
+# 16 bytes, N off the 128-wide tiles; and a pitch off 16 bytes
+WGRAD_DECLINED = [_w("rbf16", 100, 128, 257, 104), _w("rbf16", 129, 128, 257, 136, al16=0), _w("rbf16", 129, 192, 257, 136),
+                  _w("rbf16", 129, 128, 257, 132)]
+
 # hsp_wgrad_partial_pair_f32: (M0, N0, K0, M1, N1, K1, one launch, shrunk)
 PAIRS = [
     (128, 128, 256, 128, 128, 256, True, False),
@@ -133,3 +138,113 @@ def check_pair_plan(L, p):
         assert (sk < alone[1]) == shrunk, f"{p}: {sk} slices in the pair, {alone[1]} alone"
     assert (b0 + b1 <= 512) or not shrunk
     return sk0, ks0, sk1, ks1
+
+
+# ---- hsp_gemm_route: product calls and the kernel family each goes to ----------------------------------------------------------
+NONE, SMALL, X3R, X3_BN, WAVE, TILE = range(6)     # include/hsp.h: HSP_GEMM_ROUTE_*
+BN_OUT, BN_LIN = 1, 2                               # include/hsp.h: HSP_GEMM_BN_*
+
+# lay: the weight layouts, "nt" (N,K) | "nn" (K,N), one per source ("nn+nt": two sources); epi: b bias, r residual, c per-cloud
+# bias, x the xyz3 rider; off: None, "C0" (no result yet: the caller allocates it dense) or (operand, "ptr" | "ld"): that operand's
+# base address / row pitch moved off 16 bytes (by 4 bytes / one element); x3: ops.GEMM_X3; es: bytes per element
+G = namedtuple("G", "M N K1 K2 lay epi want alpha rpc off relu bn x3 es")
+
+
+def _g(M, N, K1, K2=0, lay="nt", epi="", want=None, alpha=1.0, rpc=0, off=None, relu=False, bn=0, x3=1, es=4):
+    return G(M, N, K1, K2, lay + ("+nt" if K2 and "+" not in lay else ""), epi, want, alpha, rpc, off, relu, bn, x3, es)
+
+
+def _network(B, N0):
+    """every dense product of the training step at B clouds of N0 points: the surface layer, the four HS layers (fm = X W + b; out
+    = x Wste^T + F Wa^T + F + t[cloud], alone and with the BatchNorm partials; g Wa; gX = g Wste + gfm W^T; the per-cloud t = fg
+    Wb^T and its input gradient), the heads' Conv1d(k=1) layers on 1286 / 1289 / 771 / 259 and narrower inputs (forward, with
+    the BatchNorm partials, input gradient, input gradient accumulated into a residual) and the per-cloud towers.  An epilogue
+    with fewer than 128 tiles of 64 rows keeps a product off x3; more than 512 BatchNorm row tiles keep the partials off."""
+    N1, N2 = (N0 + 3) // 4, (N0 + 3) // 4 // 4
+    rows = [_g(B * N0, 128, 128, epi="rcx", rpc=N0, relu=True, want=WAVE)]
+    for Np, Cin, C in ((N0, 128, 128), (N1, 128, 256), (N1, 256, 256), (N2, 256, 512)):
+        M = B * Np
+        epi_x3 = -(-M // 64) * (C // 128) >= 128
+        out = X3R if epi_x3 else TILE
+        rows += [
+            _g(M, 8 * C, Cin, lay="nn", epi="b", want=X3R),
+            _g(M, C, Cin, C, epi="rc", rpc=Np, want=out),
+            _g(M, C, Cin, C, epi="rc", rpc=Np, bn=BN_OUT, off="C0", want=X3_BN if epi_x3 and -(-M // 64) <= 512 else out),
+            _g(M, C, C, lay="nn", want=X3R if M >= 4096 else WAVE),
+            _g(M, Cin, C, 8 * C, lay="nn+nt", want=X3R),
+            _g(B, C, C, want=SMALL),
+            _g(B, C, C, lay="nn", alpha=1.0 / Np, off="C0", want=SMALL),
+        ]
+    M = B * N0
+    for K, N in ((1286, 1024), (1289, 1024), (1286, 512), (771, 512), (259, 512), (1024, 256), (512, 512), (512, 256), (256, 128)):
+        rows += [
+            _g(M, N, K, epi="b", off="C0", want=X3R),
+            _g(M, N, K, epi="b", off="C0", bn=BN_LIN, want=X3_BN if -(-M // 128) <= 512 else X3R),
+            _g(M, K, N, lay="nn", want=X3R),
+            _g(M, K, N, lay="nn", epi="r", want=X3R),
+        ]
+    return rows + [_g(B, 256, 256, epi="b", want=TILE), _g(B, 4, 256, epi="b", want=TILE), _g(M, 3, 128, epi="b", want=TILE)]
+
+
+_OUT = dict(M=16448, N=128, K1=128, K2=128, epi="rc", rpc=1028)          # the layer's out product, every operand in use
+ROUTES = (
+    _network(16, 1028) + _network(64, 4096)
+    # small rows: <= 16 rows, or <= 64 on its matrix-core form (K a multiple of 128; "nt" needs 16-byte rows); K <= 2048; no rider
+    + [_g(16, 64, 1000, want=SMALL), _g(17, 64, 1000, want=TILE), _g(17, 64, 1024, want=SMALL), _g(64, 64, 128, want=SMALL),
+       _g(65, 64, 128, want=TILE), _g(17, 64, 128, off=("A1", "ptr"), want=TILE), _g(17, 64, 128, off=("B1", "ld"), want=TILE),
+       _g(17, 64, 128, lay="nn", off=("A1", "ptr"), want=SMALL), _g(16, 64, 2048, want=SMALL), _g(16, 64, 2049, want=TILE),
+       _g(16, 64, 128, epi="b", want=TILE), _g(16, 64, 128, 128, want=TILE),
+       # ("nn" off the matrix-core form: the rows and 3072 partial sums share 64 KB of LDS -- ops.gemm_own used to send the
+       # second there, where the entry point declines it)
+       _g(16, 64, 832, lay="nn", want=SMALL), _g(16, 64, 833, lay="nn", want=TILE), _g(16, 64, 1000, lay="nn", want=TILE)]
+    # x3: from 256 rows on; hsp_gemm_x3_supported's two clauses (128 tiles of 64 rows, or 32 k-blocks); with an epilogue 128 tiles
+    + [_g(255, 4096, 128, want=WAVE), _g(256, 4096, 128, want=X3R), _g(8128, 128, 1024, want=X3R), _g(8128, 128, 992, want=TILE),
+       _g(8129, 128, 992, want=X3R), _g(8128, 128, 1024, epi="b", want=TILE), _g(8129, 128, 1024, epi="b", want=X3R),
+       _g(256, 4096, 128, x3=0, want=WAVE), _g(256, 4096, 128, epi="rcx", rpc=64, want=WAVE), _g(8129, 63, 1024, want=TILE),
+       # a residual alone: one source and alpha == 1 (ops.gemm_own used to send any alpha there)
+       _g(16448, 1286, 1024, lay="nn", epi="r", want=X3R), _g(16448, 1286, 1024, lay="nn", epi="r", alpha=0.5, want=TILE),
+       _g(16448, 1286, 512, 512, lay="nn+nt", epi="r", want=TILE), _g(16448, 1286, 1024, epi="c", rpc=1028, want=X3R),
+       _g(16448, 1286, 1024, epi="br", want=TILE)]
+    # the wave kernel (x3 off): K1 + K2 <= 512, M N >= 512 K, clouds of >= 64 rows, its seven forms, N and K multiples of 32
+    + [_g(4096, 128, 512, x3=0, want=WAVE), _g(4096, 128, 544, x3=0, want=TILE), _g(4096, 128, 256, 256, x3=0, epi="rc", rpc=64, want=WAVE),
+       _g(4096, 128, 256, 288, x3=0, epi="rc", rpc=64, want=TILE), _g(4095, 128, 128, x3=0, want=TILE), _g(4097, 128, 128, x3=0, want=WAVE),
+       _g(4096, 128, 128, 128, x3=0, epi="rc", rpc=63, want=TILE), _g(4096, 128, 128, 128, x3=0, epi="rc", rpc=64, want=WAVE),
+       _g(4096, 128, 128, x3=0, epi="r", want=TILE), _g(4096, 128, 128, 128, x3=0, lay="nt+nn", want=TILE),
+       _g(4096, 128, 128, x3=0, relu=True, want=TILE), _g(4096, 160, 128, x3=0, want=WAVE), _g(4096, 144, 128, x3=0, want=TILE),
+       _g(4096, 128, 144, x3=0, want=TILE)]
+    # an operand off 16 bytes: x3 needs its activation rows there and nothing else, the wave kernel every operand
+    + [_g(**_OUT, want=X3R), _g(**_OUT, x3=0, want=WAVE)]
+    + [_g(**_OUT, off=(o, k), want=TILE if o in ("A1", "A2") else X3R) for o in ("A1", "B1", "A2", "B2", "resid", "C") for k in ("ptr", "ld")]
+    + [_g(**_OUT, off=(o, k), x3=0, want=TILE) for o in ("A1", "B1", "A2", "B2", "resid", "C") for k in ("ptr", "ld")]
+    # the BatchNorm partials: the out product from clouds of 64 rows on, a Linear from 256 rows on, 512 row tiles at most
+    + [_g(16384, 128, 128, 128, epi="rc", rpc=64, bn=BN_OUT, want=X3_BN), _g(16128, 128, 128, 128, epi="rc", rpc=63, bn=BN_OUT, want=X3R),
+       _g(32768, 128, 128, 128, epi="rc", rpc=64, bn=BN_OUT, want=X3_BN), _g(32769, 128, 128, 128, epi="rc", rpc=64, bn=BN_OUT, want=X3R),
+       _g(16384, 128, 128, 128, epi="rc", rpc=64, bn=BN_OUT, relu=True, want=X3R), _g(16384, 128, 128, 128, epi="rc", rpc=64, bn=BN_OUT, x3=0, want=WAVE),
+       _g(256, 4096, 128, epi="b", bn=BN_LIN, want=X3_BN), _g(255, 4096, 128, epi="b", bn=BN_LIN, want=WAVE),
+       _g(65536, 1024, 128, epi="b", bn=BN_LIN, want=X3_BN), _g(65537, 1024, 128, epi="b", bn=BN_LIN, want=X3R),
+       _g(16448, 1024, 1286, bn=BN_LIN, want=X3R)]
+    # bf16 rows: the tile kernel, (N,K) weights only; two (K,N) weights: x3 (its planes are (N,K) whatever the weight) or no kernel
+    + [_g(16448, 128, 128, es=2, want=TILE), _g(16448, 128, 128, es=2, lay="nn", want=NONE), _g(16448, 128, 128, 128, lay="nn+nn", want=X3R),
+       _g(16448, 128, 128, 128, lay="nn+nn", x3=0, want=NONE),
+       _g(16448, 128, 128, es=2, off=("A1", "ld"), want=NONE)]
+)
+
+
+def gemm_call(c):
+    """the HspGemmCall of a ROUTES row: operands at made-up addresses on pitches rounded up to 16 bytes"""
+    from hs_pose_amd._lib import HspGemmCall
+    per16 = 16 // c.es
+    lays = [int(x == "nn") for x in c.lay.split("+")] + [0]
+
+    def op(name, cols, addr):
+        ld = -(-cols // per16) * per16
+        if c.off is not None and c.off[0] == name:
+            addr, ld = (addr + 4, ld) if c.off[1] == "ptr" else (addr, ld + 1)
+        return addr, ld
+
+    (a1, lda1), (b1, ldb1) = op("A1", c.K1, 0x100000), op("B1", c.N if lays[0] else c.K1, 0x200000)
+    (a2, lda2), (b2, ldb2) = (op("A2", c.K2, 0x300000), op("B2", c.N if lays[1] else c.K2, 0x400000)) if c.K2 else ((None, 0), (None, 0))
+    r, ldr = op("resid", c.N, 0x500000) if "r" in c.epi else (None, 0)
+    out, ldc = (None, c.N) if c.off == "C0" else op("C", c.N, 0x600000)
+    return HspGemmCall(a1, b1, a2, b2, r, out, c.M, c.N, c.K1, c.K2, lays[0], lays[1], c.es, lda1, ldb1, lda2, ldb2, ldr, ldc,
+                       "b" in c.epi, "c" in c.epi, "x" in c.epi, c.relu, c.alpha == 1.0, c.rpc, c.bn, c.x3)

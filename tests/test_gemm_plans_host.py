@@ -1,5 +1,5 @@
-"""CPU: the plan queries of the dense products (hsp_wgrad_plan, hsp_wgrad_pair_plan, hsp_gemm_rows_plan, hsp_gemm_x3_plan: host
-code, the dispatch decides by the same functions).  Every case of tests/_gemm_cases.py enters the plan it was placed for, and the
+"""CPU: the plan queries of the dense products (hsp_wgrad_plan, hsp_wgrad_pair_plan, hsp_gemm_rows_plan, hsp_gemm_x3_plan,
+hsp_gemm_route: host code, the dispatch decides by the same functions).  Every case of tests/_gemm_cases.py enters the plan it was placed for, and the
 facts the kernels rely on hold over a sweep of shapes: slices are whole pairs of prefetch groups (16 rows), the
 4-slices-per-workgroup form has a multiple of 4 slices, and no plan writes more partial sums than the workspace query of the same
 arguments promises -- the pair launch after its shrink loop included.
@@ -24,9 +24,30 @@ def test_wgrad_case_enters_its_plan(c):
     gc.check_wgrad_plan(_L(), c)
 
 
+@pytest.mark.parametrize("c", gc.WGRAD_DECLINED, ids=lambda c: f"{c.entry}-{c.M}x{c.N}x{c.K}-{c.lda}-{c.ldb}-{c.al16}")
+def test_wgrad_case_is_declined_by_its_plan(c):
+    assert gc.wgrad_plan(_L(), c)[0] == -2
+
+
 @pytest.mark.parametrize("p", gc.PAIRS, ids=lambda p: "-".join(str(v) for v in p[:6]))
 def test_pair_case_enters_its_plan(p):
     gc.check_pair_plan(_L(), p)
+
+
+def _gid(c):
+    return "-".join(str(v) for v in c[:6]) + f"-a{c.alpha:g}-r{c.rpc}-{c.off}-{int(c.relu)}{c.bn}{c.x3}{c.es}"
+
+
+@pytest.mark.parametrize("c", gc.ROUTES, ids=_gid)
+def test_product_call_goes_to_its_kernel(c):
+    """hsp_gemm_route sends every row of ROUTES to the family it names, and that family's own takes function agrees"""
+    L, call = _L(), gc.gemm_call(c)
+    route = L.hsp_gemm_route(ctypes.byref(call))
+    assert route == c.want, f"{c}: route {route}"
+    if c.bn and route != gc.X3_BN:                 # the partials declined: the route of the plain call
+        call.bn = 0
+        assert L.hsp_gemm_route(ctypes.byref(call)) == route
+    assert route == gc.NONE or L.hsp_gemm_takes(ctypes.byref(call), route) == 1
 
 
 def _sweep_K():

@@ -187,6 +187,17 @@ class Ws:
         return bool((self.buf[self.nbytes:] == 0xA5).all())
 
 
+def _takes(route, M, N, srcs, out, resid=None, bias=None, cb=None, xyz=None, alpha=1.0, rpc=0):
+    """hsp_gemm_takes(route) for the call a test is about to make: srcs = [(A view, weight-side view, layout, K), ...], every
+    operand where the entry point will read / write it"""
+    from hs_pose_amd._lib import HspGemmCall
+    (a1, b1, l1, K1), (a2, b2, l2, K2) = srcs if len(srcs) == 2 else (srcs[0], (None, None, 0, 0))
+    ptr, ld = (lambda t: t.data_ptr() if t is not None else None), (lambda t: t.stride(0) if t is not None else 0)
+    call = HspGemmCall(ptr(a1), ptr(b1), ptr(a2), ptr(b2), ptr(resid), ptr(out), M, N, K1, K2, l1, l2, 4, ld(a1), ld(b1), ld(a2), ld(b2),
+                       ld(resid), ld(out), bias is not None, cb is not None, xyz is not None, False, alpha == 1.0, rpc, 0, 1)
+    return _L().hsp_gemm_takes(ctypes.byref(call), route)
+
+
 # ---- the bound --------------------------------------------------------------------------------------------------------------------
 
 def _ratio(what, err, terms):
@@ -287,6 +298,15 @@ def test_wgrad(dev, c):
             if colsum:
                 _hold(cs.v[0], wcs, Tcs, what + " colsum", FORM_NAME[form] + " colsum", A_SUM)
                 first = (out.v.clone(), cs.v.clone())
+
+
+@pytest.mark.parametrize("c", gc.WGRAD_DECLINED, ids=_ids)
+def test_wgrad_declines_what_its_plan_declines(dev, c):
+    assert gc.wgrad_plan(_L(), c)[0] == -2
+    a, b = _operands(c.K, c.M, c.N, 1, False, _dtype(c))
+    rc, out, cs, ws = _run_wgrad(c, a, b, True, dev)
+    assert rc == -2 and out.intact() and cs.intact() and ws.intact()
+    assert torch.isnan(out.v).all() and torch.isnan(cs.v).all() and bool((ws.buf == 0xA5).all()), "a declined call wrote"
 
 
 def test_wgrad_workspace_one_byte_short_is_declined(dev):
@@ -802,6 +822,10 @@ X3 = [
     X(1120, 4096, (128, 0), None, "b", 0, 1.0, 1, (0, 1, 1, 0)),           # 35 row tiles fill 0.73 of three rounds: the tile kernel
 ]
 X3_REFUSED = [(1, 64, 992, 0), (8128, 64, 992, 0), (960, 1024, 1, 0), (960, 1024, 480, 480), (100, 63, 2000, 0)]
+# shapes hsp_gemm_x3_supported admits in calls the kernel has no form for: a residual alone with alpha != 1 (ops.gemm_own used to
+# send it there) or with two sources, bias + residual
+X3_REFUSED_CALLS = [X(65, 64, (1000, 0), None, "r", 0, 0.5, 1, None), X(63, 128, (512, 0), (512, 0), "r", 0, 1.0, 4, None),
+                    X(129, 65, (993, 0), None, "br", 0, 1.0, 1, None)]
 
 
 def x3_plan(c, ldc):
@@ -828,6 +852,8 @@ def _run_x3(c, d, dev, short=0):
     wsb = L.hsp_gemm_x3_workspace_bytes(c.M, c.N, c.s1[0], c.s2[0] if c.s2 else 0)
     ws = Ws(wsb, dev)
     (a1, la1, _, p1, lp1, ps1, K1), (a2, la2, _, p2, lp2, ps2, K2) = srcs
+    out.takes = _takes(gc.X3R, c.M, c.N, [(a1, p1, 0, K1)] + ([(a2, p2, 0, K2)] if a2 is not None else []), out.v, resid, bias, cb,
+                       alpha=c.alpha, rpc=c.rpc)
     rc = L.hsp_gemm_x3_f32(_vp(a1), la1, _vp(p1), lp1, ps1, K1, _vp(a2), la2, _vp(p2), lp2, ps2, K2, c.M, c.N, _vp(bias), _vp(resid),
                            c.N + 3, _vp(cb), c.rpc, c.alpha, _vp(out.v), ldc, _vp(ws.buf), wsb - short, _stream())
     torch.cuda.synchronize()
@@ -863,7 +889,8 @@ def test_gemm_x3_f32(dev, c):
         d, want, T = _rows_case(c, cancel)
         what = f"{_xid(c)} {'cancel' if cancel else 'range'}"
         rc, out, ws = _run_x3(c, d, dev)
-        assert rc == 0 and out.intact() and ws.intact(), f"{what}: rc {rc}, or a write outside the output / past the workspace"
+        assert out.takes == 1 and rc == 0, f"{what}: hsp_gemm_takes {out.takes}, the entry point {rc}"
+        assert out.intact() and ws.intact(), f"{what}: a write outside the output / past the workspace"
         _hold(out.v, want, T, what, kind, A_X3)
         if ns > 1:
             assert torch.equal(_run_x3(c, d, dev)[1].v, out.v), f"{what}: the fixed-order fold gave other bits on a second call"
@@ -883,7 +910,11 @@ def test_gemm_x3_refuses_below_both_clauses(dev):
         c = X(M, N, (K1, 0), (K2, 0) if K2 else None, "", 0, 1.0, 1, None)
         d = _rows_data(c, 1, False, torch.float32)
         rc, o, ws = _run_x3(c, d, dev)
-        assert rc == -2 and o.intact() and torch.isnan(o.v).all() and bool((ws.buf == 0xA5).all())
+        assert o.takes == 0 and rc == -2 and o.intact() and torch.isnan(o.v).all() and bool((ws.buf == 0xA5).all())
+    for c in X3_REFUSED_CALLS:
+        assert L.hsp_gemm_x3_supported(c.M, c.N, c.s1[0], c.s2[0] if c.s2 else 0) == 1
+        rc, o, ws = _run_x3(c, _rows_data(c, 1, False, torch.float32), dev)
+        assert o.takes == 0 and rc == -2 and o.intact() and torch.isnan(o.v).all() and bool((ws.buf == 0xA5).all()), _xid(c)
 
 
 @pytest.mark.parametrize("edge", [False, True], ids=["inside", "last-rows"])
@@ -952,6 +983,7 @@ def _run_small_rows(a, w, lay, alpha, al, dev):
     av = _in_moat(a, (K + 3) // 4 * 4 + pad, dev)
     wv = _in_moat(w, (w.shape[1] + 3) // 4 * 4 + pad, dev)
     out = Out(M, N, N + 1, dev)
+    out.takes = _takes(gc.SMALL, M, N, [(av, wv, lay, K)], out.v, alpha=alpha)
     rc = _L().hsp_small_rows_f32(_vp(av), av.stride(0), _vp(wv), wv.stride(0), lay, M, N, K, alpha, _vp(out.v), N + 1, _stream())
     torch.cuda.synchronize()
     return rc, out
@@ -1002,7 +1034,7 @@ def test_small_rows(dev, M, N, K, lay, alpha, al, form):
         a, w = _small_rows_data(M, N, K, lay, cancel, 300 + SMALL_ROWS.index((M, N, K, lay, alpha, al, form)))
         want, T = _small_rows_ref(a, w, lay, alpha)
         rc, out = _run_small_rows(a, w, lay, alpha, al, dev)
-        assert rc == 0 and out.intact()
+        assert out.takes == 1 and rc == 0 and out.intact()
         _hold(out.v, want, T, f"small_rows {M}x{N}x{K} {'nn' if lay else 'nt'} {form}", "small_rows, " + form, A_SMALL)
     if form == "mfma" and M > 1:                                                     # non-finite rows stay rows, the last one included
         a, w = a.clone(), w.clone()
@@ -1024,9 +1056,17 @@ def test_small_rows(dev, M, N, K, lay, alpha, al, form):
 
 
 def test_small_rows_declines_many_rows_off_the_mfma_form(dev):
-    a, w = _small_rows_data(64, 16, 100, 0, False, 1)
-    rc, out = _run_small_rows(a, w, 0, 1.0, True, dev)
-    assert rc == -2 and out.intact() and torch.isnan(out.v).all()
+    """... and "nn" rows off that form that do not fit its 64 KB of LDS with the partial sums (832 columns of 16 rows do: SMALL_ROWS
+    has no such row, so the fit is run here); ops.gemm_own used to send the latter there"""
+    for M, N, K, lay, takes in ((64, 16, 100, 0, 0), (16, 8, 833, 1, 0), (16, 8, 1000, 1, 0), (16, 8, 832, 1, 1)):
+        a, w = _small_rows_data(M, N, K, lay, False, 1)
+        rc, out = _run_small_rows(a, w, lay, 1.0, True, dev)
+        assert out.takes == takes and out.intact()
+        if takes:
+            assert rc == 0
+            _hold(out.v, *_small_rows_ref(a, w, lay, 1.0), f"small_rows {M}x{N}x{K} nn lanes", "small_rows, lanes", A_SMALL)
+        else:
+            assert rc == -2 and torch.isnan(out.v).all()
 
 
 def _run_outer(a, c, mom, Cm, dev, pair=None):
@@ -1113,6 +1153,8 @@ def _run_wave(c, d, cfg, dev):
     xyz = _in_moat(d.xyz, 3, dev) if d.xyz is not None else None
     w3 = _in_moat(d.w3, 3, dev) if d.w3 is not None else None
     (a1, la1, b1, lb1, l1, K1), (a2, la2, b2, lb2, l2, K2) = ops_
+    out.takes = _takes(gc.WAVE, c.M, c.N, [(a1, b1, l1, K1)] + ([(a2, b2, l2, K2)] if a2 is not None else []), out.v, resid, bias, cb, xyz,
+                       c.alpha, c.rpc)
     rc = L.hsp_gemm_wave_f32(_vp(a1), la1, _vp(b1), lb1, l1, K1, _vp(a2), la2, _vp(b2), lb2, l2, K2, c.M, c.N, _vp(bias), _vp(resid),
                              c.N + 4, _vp(cb), c.rpc, c.alpha, _vp(xyz), _vp(w3), _vp(out.v), c.N + 4, cfg, _stream())
     torch.cuda.synchronize()
@@ -1154,7 +1196,21 @@ def test_gemm_wave_f32(dev, c, cfg):
             assert rc == -2 and out.intact() and torch.isnan(out.v).all(), f"{what}: not declined cleanly"
             continue
         assert rc == 0 and out.intact(), f"{what}: rc {rc}, or a write outside the output"
+        assert cfg or out.takes == 1, f"{what}: hsp_gemm_takes declines what the entry point ran"      # (the query knows no forced tile)
         _hold(out.v, want, T, what, "gemm_wave", A_WAVE)
+
+
+# calls gw_plan cuts that the kernel has no form for, or whose clouds are shorter than a tile: a residual alone, bias + the out
+# product's riders, "nt" + "nn", clouds of 31 rows
+WAVE_REFUSED = [R(129, 128, (32, 0), None, "r", 0, 1.0, 16, None), R(129, 128, (32, 0), (64, 0), "brc", 100, 1.0, 16, None),
+                R(64, 128, (32, 0), (96, 1), "", 0, 1.0, 16, None), R(129, 128, (32, 0), (64, 0), "rc", 31, 1.0, 16, None)]
+
+
+@pytest.mark.parametrize("c", WAVE_REFUSED, ids=_rid)
+def test_gemm_wave_declines_what_its_query_declines(dev, c):
+    assert _L().hsp_gemm_wave_supported(c.M, c.N, c.s1[0], c.s2[0] if c.s2 else 0, 0) == 1
+    rc, out = _run_wave(c, _rows_data(c, 1, False, torch.float32), 0, dev)
+    assert out.takes == 0 and rc == -2 and out.intact() and torch.isnan(out.v).all()
 
 
 @pytest.mark.parametrize("edge", [False, True], ids=["inside", "last-rows"])

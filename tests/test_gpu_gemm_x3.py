@@ -68,7 +68,8 @@ def test_gemm_x3_matches_fp64(dev, M, N, K1, nn1, K2, nn2, epi, rpc):
     resid = rnd(M, N) if epi == "rc" else None
     cb = rnd((M + rpc - 1) // rpc, N) if epi == "rc" else None
     alpha = 0.5 if epi == "none" else 1.0
-    assert ops.gemm_x3_ok(A1, B1, A2, B2, bias, resid, cb, None, None, M, N)
+    assert ops._gemm_route(A1, B1, nn1, A2, B2, nn2, bias=bias, resid=resid, cloud_bias=cb, rows_per_cloud=rpc,
+                           alpha=alpha) == ops.ROUTE_X3
     got = ops.gemm_x3(A1, B1, nn1, A2, B2, nn2, bias=bias, resid=resid, cloud_bias=cb, rows_per_cloud=rpc, alpha=alpha)
     want = _ref64(A1, B1, nn1, A2, B2, nn2, bias, resid, cb, rpc, alpha)
     # yardstick: the fp32 library product of the same operands

@@ -379,7 +379,11 @@ def test_wgrad_ragged_m(dev, ref, K, M, N, pad_nan):
         Afull[:, M:] = float("nan")
     A = Afull[:, :M]
     Bm = ref.hash_tensor((K, N), 22, 1.0).to(dev)
-    assert ops._wgrad_ragged_ok(A, Bm, Bm)
+    import ctypes
+    from hs_pose_amd._lib import lib
+    plan = (ctypes.c_int * 4)()                        # the ragged plan: the x3 form, and M off the 64-wide tiles of every other
+    assert M % 64 and ops._wgrad_entry_of(A, Bm, Bm) == "hsp_wgrad"
+    assert lib().hsp_wgrad_plan(M, N, K, 4, 1, pitch, N, 0, plan) == 0 and plan[0] == 3         # HSP_WGRAD_FORM_X3
     guard = torch.full((M + 8, N), 7.0, device=dev)
     out, cs = ops.wgrad(A, Bm, out=guard[:M], colsum=True)
     want = A.double().t() @ Bm.double()

@@ -6,7 +6,7 @@ import torch
 from hs_pose_amd import ops
 from tools import library_gemm
 _ORIG = {n_: getattr(ops, n_) for n_ in ("_fm_rows", "_layer_out_rows_plain", "_mm_nn", "_mm_nt", "_grad_in_rows", "_tiny_tn", "wgrad",
-                                       "_wgrad_ragged_ok", "linear_bn_part_ok", "_layer_out_bn_ok", "_ste_moments_ok", "_thin_wgrad_ok",
+                                       "_wgrad_entry", "linear_bn_part_ok", "_layer_out_bn_ok", "_ste_moments_ok", "_thin_wgrad_ok",
                                        "fan_linear_rows_ok", "cloud_cat_linear_ok", "x3_refresh")}
 
 dev = torch.device("cuda:0")

@@ -13,8 +13,10 @@ def enable(monkeypatch=None, tune=False):
     from hs_pose_amd import ops
 
     def put(name, fn):
+        if not hasattr(ops, name) and name != "gemm_mode":          # a stale name would quietly leave a fusion on
+            raise AttributeError(f"library_gemm: hs_pose_amd.ops has no {name} to replace")
         if monkeypatch is not None:
-            monkeypatch.setattr(ops, name, fn)
+            monkeypatch.setattr(ops, name, fn, raising=False)
         else:
             setattr(ops, name, fn)
 
@@ -57,11 +59,14 @@ def enable(monkeypatch=None, tune=False):
             gste.copy_(mom[:, Cm:].sum(dim=0).view(3, Cm).t())
         return out
 
-    own_wgrad = ops.wgrad
+    own_wgrad, sliced = ops.wgrad, ops._wgrad_sliced
+
+    def wgrad_entry(*a):                                                # (the ragged forms are the hand-written kernels' own)
+        return "hsp_wgrad" if sliced(*a) else None
 
     def wgrad(A2, B2, out=None, colsum=False):
         K, M = A2.shape
-        if ops._wgrad_ok(A2, B2, out if out is not None else A2):       # the parameter gradients stay on the split-K kernels
+        if ops._wgrad_entry_of(A2, B2, out if out is not None else A2):  # the parameter gradients stay on the split-K kernels
             return own_wgrad(A2, B2, out=out, colsum=colsum)             # (as in every round's library-mode figure)
         if out is None:
             out = torch.empty(M, B2.shape[1], dtype=torch.float32, device=A2.device)
@@ -77,13 +82,10 @@ def enable(monkeypatch=None, tune=False):
     for name, fn in (("_fm_rows", fm_rows), ("_layer_out_rows_plain", layer_out_rows_plain), ("_mm_nn", mm_nn), ("_mm_nt", mm_nt),
                      ("_grad_in_rows", grad_in_rows), ("_tiny_tn", tiny_tn), ("wgrad", wgrad), ("gemm_mode", "library"),
                      # the own-kernel fusions: off
-                     ("_wgrad_ragged_ok", never), ("linear_bn_part_ok", never), ("_layer_out_bn_ok", never), ("_ste_moments_ok", never),
+                     ("_wgrad_entry", wgrad_entry), ("linear_bn_part_ok", never), ("_layer_out_bn_ok", never), ("_ste_moments_ok", never),
                      ("_thin_wgrad_ok", never), ("_orl_bwd_small_ok", never), ("fan_linear_rows_ok", never), ("cloud_cat_linear_ok", never),
                      ("x3_refresh", lambda: None)):
-        if monkeypatch is not None and not hasattr(ops, name):
-            monkeypatch.setattr(ops, name, fn, raising=False)
-        else:
-            put(name, fn)
+        put(name, fn)
     if tune:
         from tools import gemm_tuning
         gemm_tuning.enable()

@@ -16,7 +16,7 @@ for N, K, nn, A in ((1024, 1286, False, feat), (256, 1024, False, None), (1286, 
     out = torch.empty(M, N, device=dev)
     fl = 2.0 * M * N * K
     res = {}
-    if ops.gemm_x3_ok(A, W, None, None, None if nn else b, None, None, None, out, M, N):
+    if ops._gemm_route(A, W, nn, bias=None if nn else b, out=out) == ops.ROUTE_X3:
         res["x3"] = timeit(lambda: ops.gemm_x3(A, W, nn, bias=None if nn else b, out=out))
     res["rows"] = timeit(lambda: ops.gemm_rows(A, W, nn, bias=None if nn else b, out=out))
     res["lib"] = timeit(lambda: (torch.mm(A, W, out=out) if nn else torch.addmm(b, A, W.t(), out=out)))
