@@ -16,6 +16,7 @@ class _Flags:
         Ts_c=6,               # config.py:34
         feat_face=768,        # config.py:35
         face_recon_c=6 * 5,   # config.py:37
+        img_size=256,         # config.py:19  side of the instance crop
         gcn_sup_num=7,        # config.py:39  support directions S
         gcn_n_num=20,         # config.py:40  neighbours k
         random_points=1028,   # config.py:43

@@ -7,6 +7,10 @@
 //    row-major order (the order of torch's boolean indexing) and returns the counts the host needs to
 //    draw; stage 2 back-projects only the chosen pixels.  The reference materialises three H x W maps and
 //    a variable-length (L,3) tensor per image and synchronises once per image; here: one sync per batch.
+//  * frame -> instance clouds: replaces the loader's crop chain in front of that (evaluation/load_data_eval.py:207-254):
+//    get_bbox window, three cv2.warpAffine(INTER_NEAREST) over the frame, boolean compaction.  Same two stages one step
+//    earlier: stage 1 walks the crop pixels of every instance through the warp's integer map and compacts the source ids of
+//    the valid ones; stage 2 back-projects the chosen ones straight from the frame.
 //  * (R|t) assembly: replaces generate_RT(..., mode='vec') (tools/geom_utils.py:232-244 with
 //    tools/rot_utils.py:39-100): confidence-weighted orthogonalisation of the two predicted axes and
 //    the 4x4 pose matrix, one lane per object instead of ~40 tiny launches.
@@ -98,8 +102,17 @@ __global__ __launch_bounds__(256) void pc_gather_kernel(const float* __restrict_
     pc[(size_t)e * 3 + 2] = __fdiv_rn(d, 1000.0f);
 }
 
-// dataset-side variant (datasets/load_data.py:322-333 then :275): numpy promotes to float64 --
+// dataset-side arithmetic (datasets/load_data.py:322-333 then :275): numpy promotes to float64 --
 // ((u - cx) * d / fx evaluated in double with a double K), rounds to fp32, then / 1000 in fp32.
+__device__ __forceinline__ void backproject_f64(double u, double v, double d, const double* __restrict__ K,
+                                                float* __restrict__ o) {
+    const double x = __ddiv_rn(__dmul_rn(__dsub_rn(u, K[2]), d), K[0]);
+    const double y = __ddiv_rn(__dmul_rn(__dsub_rn(v, K[5]), d), K[4]);
+    o[0] = __fdiv_rn((float)x, 1000.0f);
+    o[1] = __fdiv_rn((float)y, 1000.0f);
+    o[2] = __fdiv_rn((float)d, 1000.0f);
+}
+
 __global__ __launch_bounds__(256) void depth_to_pcl_kernel(const float* __restrict__ depth,
                                                            const float* __restrict__ xymap,
                                                            const double* __restrict__ camK,
@@ -110,14 +123,160 @@ __global__ __launch_bounds__(256) void depth_to_pcl_kernel(const float* __restri
     if (e >= B * S) return;
     const int b = e / S;
     const int p = pix[(size_t)b * HW + choose[e]];
-    const double d = (double)depth[(size_t)b * HW + p];
-    const double u = (double)xymap[((size_t)b * 2 + 0) * HW + p], v = (double)xymap[((size_t)b * 2 + 1) * HW + p];
-    const double* K = camK + (size_t)b * 9;
-    const double x = __ddiv_rn(__dmul_rn(__dsub_rn(u, K[2]), d), K[0]);
-    const double y = __ddiv_rn(__dmul_rn(__dsub_rn(v, K[5]), d), K[4]);
-    pc[(size_t)e * 3 + 0] = __fdiv_rn((float)x, 1000.0f);
-    pc[(size_t)e * 3 + 1] = __fdiv_rn((float)y, 1000.0f);
-    pc[(size_t)e * 3 + 2] = __fdiv_rn((float)d, 1000.0f);
+    backproject_f64((double)xymap[((size_t)b * 2 + 0) * HW + p], (double)xymap[((size_t)b * 2 + 1) * HW + p],
+                    (double)depth[(size_t)b * HW + p], camK + (size_t)b * 9, pc + (size_t)e * 3);
+}
+
+// ---- detections of one frame -> instance clouds (evaluation/load_data_eval.py:207-254) --------------------------------
+// The loader warps the coordinate grid, the mask and the depth of the frame into an O x O crop per instance with
+// cv2.warpAffine(INTER_NEAREST).  A nearest-neighbour warp of the coordinate grid returns the coordinates of the pixel it
+// sampled, so the three crops are three views of ONE integer map crop pixel -> frame pixel; it is evaluated here and the crops
+// never exist.  The map, in warpAffine's fixed-point form (10 fractional bits), for xf = (m0, b1, b2) of the inverse transform:
+//     X = (rint(b1 * 1024) + 512 + rint(m0 * u * 1024)) >> 10,   Y = (rint(b2 * 1024) + 512 + rint(m0 * v * 1024)) >> 10
+// rint in float64 (half to even), arithmetic shift; outside the frame the warp's constant border reads 0: never valid.
+// The terms are clamped to +-2^52 so that the sums stay inside int64 whatever the host passes (a clamped term is far outside
+// any frame with H * W < 2^31 unless the other term is as absurd).
+__device__ __forceinline__ long long roi_fix(double x) {
+    return (long long)fmin(fmax(rint(x * 1024.0), -4503599627370496.0), 4503599627370496.0);
+}
+
+// frame pixel id Y * W + X that crop pixel q = v * O + u reads, or -1 outside the frame
+__device__ __forceinline__ int roi_source(double m0, long long bx, long long by, int q, int O, int H, int W) {
+    const int v = q / O, u = q - v * O;
+    const long long X = (bx + roi_fix(m0 * (double)u)) >> 10;
+    const long long Y = (by + roi_fix(m0 * (double)v)) >> 10;
+    if (X < 0 || X >= W || Y < 0 || Y >= H) return -1;
+    return (int)Y * W + (int)X;
+}
+
+// the 16 consecutive crop pixels of one thread: source ids, bit i of dbits = depth > 0, of mbits = depth > 0 and mask set
+template <typename D>
+__device__ __forceinline__ void roi_scan16(const D* __restrict__ depth, const uint8_t* __restrict__ mask,
+                                           const int32_t* __restrict__ inst_id, const double* __restrict__ xf, int j,
+                                           int lo, int OO, int O, int H, int W, int src[16], unsigned& mbits,
+                                           unsigned& dbits) {
+    const double m0 = xf[(size_t)j * 3];
+    const long long bx = roi_fix(xf[(size_t)j * 3 + 1]) + 512, by = roi_fix(xf[(size_t)j * 3 + 2]) + 512;
+    const int want = inst_id ? inst_id[j] : 0;
+    mbits = 0;
+    dbits = 0;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        const int q = lo + i;
+        int p = -1;
+        if (q < OO) p = roi_source(m0, bx, by, q, O, H, W);
+        src[i] = p;
+        if (p >= 0 && depth[p] > (D)0) {
+            const int m = mask[p];
+            dbits |= 1u << i;
+            if (inst_id ? m == want : m != 0) mbits |= 1u << i;
+        }
+    }
+}
+
+// same two-launch shape as pc_count_kernel / pc_write_kernel, over the O * O crop pixels of instance blockIdx.y:
+//   roi_count_kernel  cnt[j][chunk] = {mask-and-depth valid, depth valid} of the chunk
+//   roi_write_kernel  offset = earlier chunks' first counts, scan inside the chunk, source ids written in crop row-major order;
+//                     the last chunk's workgroup writes both totals
+template <typename D>
+__global__ __launch_bounds__(256) void roi_count_kernel(const D* __restrict__ depth, const uint8_t* __restrict__ mask,
+                                                        long long mask_stride, const int32_t* __restrict__ inst_id,
+                                                        const double* __restrict__ xf, int H, int W, int O, int nchunk,
+                                                        int32_t* __restrict__ cnt) {
+    __shared__ int wsum[4][2];
+    const int j = blockIdx.y, chunk = blockIdx.x, tid = threadIdx.x;
+    const int OO = O * O;
+    int src[16];
+    unsigned mbits, dbits;
+    roi_scan16(depth, mask + (size_t)j * mask_stride, inst_id, xf, j, chunk * PC_CHUNK + tid * 16, OO, O, H, W, src, mbits,
+               dbits);
+    int cm = __popc(mbits), cd = __popc(dbits);
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        cm += __shfl_xor(cm, m);
+        cd += __shfl_xor(cd, m);
+    }
+    if ((tid & 63) == 0) {
+        wsum[tid >> 6][0] = cm;
+        wsum[tid >> 6][1] = cd;
+    }
+    __syncthreads();
+    if (tid < 2) cnt[((size_t)j * nchunk + chunk) * 2 + tid] = (wsum[0][tid] + wsum[1][tid]) + (wsum[2][tid] + wsum[3][tid]);
+}
+
+template <typename D>
+__global__ __launch_bounds__(256) void roi_write_kernel(const D* __restrict__ depth, const uint8_t* __restrict__ mask,
+                                                        long long mask_stride, const int32_t* __restrict__ inst_id,
+                                                        const double* __restrict__ xf, int H, int W, int O, int nchunk,
+                                                        const int32_t* __restrict__ cnt, int32_t* __restrict__ out_src,
+                                                        int32_t* __restrict__ count) {
+    __shared__ int red[4][2];
+    __shared__ int wpre[4];
+    const int j = blockIdx.y, chunk = blockIdx.x, tid = threadIdx.x;
+    const int lane = tid & 63, wv = tid >> 6;
+    const int OO = O * O;
+    const bool last = chunk == nchunk - 1;
+    // offset of this chunk = sum of the first counts of the instance's earlier chunks; the last chunk also totals the second ones
+    int part = 0, partd = 0;
+    for (int c = tid; c < chunk; c += 256) part += cnt[((size_t)j * nchunk + c) * 2];
+    if (last)
+        for (int c = tid; c < nchunk; c += 256) partd += cnt[((size_t)j * nchunk + c) * 2 + 1];
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        part += __shfl_xor(part, m);
+        partd += __shfl_xor(partd, m);
+    }
+    if (lane == 0) {
+        red[wv][0] = part;
+        red[wv][1] = partd;
+    }
+    int src[16];
+    unsigned mbits, dbits;
+    roi_scan16(depth, mask + (size_t)j * mask_stride, inst_id, xf, j, chunk * PC_CHUNK + tid * 16, OO, O, H, W, src, mbits,
+               dbits);
+    const int c = __popc(mbits);
+    int incl = c;                                            // inclusive scan inside the wave
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const int v = __shfl_up(incl, d);
+        if (lane >= d) incl += v;
+    }
+    if (lane == 63) wpre[wv] = incl;
+    __syncthreads();
+    const int base = (red[0][0] + red[1][0]) + (red[2][0] + red[3][0]);
+    int woff = 0;
+    for (int w = 0; w < wv; ++w) woff += wpre[w];
+    int off = base + woff + incl - c;
+    int32_t* out = out_src + (size_t)j * OO;
+#pragma unroll
+    for (int i = 0; i < 16; ++i)
+        if ((mbits >> i) & 1u) out[off++] = src[i];
+    if (last && tid == 255) {
+        count[j * 2 + 0] = base + woff + incl;
+        count[j * 2 + 1] = (red[0][1] + red[1][1]) + (red[2][1] + red[3][1]);
+    }
+}
+
+// pc[j,s,:] for frame pixel p = src[j, choose[j,s]]: the grid values the reference warps are u = float(p % W), v = float(p / W)
+// (exact), then the loader's arithmetic.  An index outside its row or frame (a choose beyond the instance's count) gives NaN.
+template <typename D>
+__global__ __launch_bounds__(256) void frame_to_pcl_kernel(const D* __restrict__ depth, int H, int W,
+                                                           const double* __restrict__ camK, int camK_rows,
+                                                           const int32_t* __restrict__ src, long long src_stride,
+                                                           const int32_t* __restrict__ choose, int n, int S,
+                                                           float* __restrict__ pc) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= n * S) return;
+    const int j = e / S;
+    float* o = pc + (size_t)e * 3;
+    const int c = choose[e];
+    const int p = (c >= 0 && c < src_stride) ? src[(size_t)j * src_stride + c] : -1;
+    if (p < 0 || p >= H * W) {
+        o[0] = o[1] = o[2] = __builtin_nanf("");
+        return;
+    }
+    const int v = p / W, u = p - v * W;
+    backproject_f64((double)(float)u, (double)(float)v, (double)depth[p], camK + (camK_rows > 1 ? (size_t)j * 9 : 0), o);
 }
 
 __device__ __forceinline__ void rodrigues_apply(const float rx[3], float s, float c, const float v[3], float o[3]) {
@@ -210,6 +369,67 @@ extern "C" int hsp_depth_to_pcl(const float* depth, const float* xymap, const do
     hipLaunchKernelGGL(depth_to_pcl_kernel, dim3((B * S + 255) / 256), dim3(256), 0, as_stream(stream), depth, xymap,
                        camK, pix, choose, B, HW, S, pc);
     return check_launch();
+}
+
+extern "C" size_t hsp_roi_compact_workspace_bytes(int n, int O) {
+    if (n <= 0 || O <= 0 || O > 46340) return 0;
+    return (size_t)n * ((O * O + PC_CHUNK - 1) / PC_CHUNK) * 2 * sizeof(int32_t);
+}
+
+template <typename D>
+static int roi_compact(const D* depth, const uint8_t* mask, long long mask_stride, const int32_t* inst_id, const double* xf,
+                       int n, int H, int W, int O, int32_t* src, int32_t* count, void* ws, size_t ws_bytes,
+                       hspStream_t stream) {
+    if (!depth || !mask || !xf || !src || !count || n <= 0 || H <= 0 || W <= 0 || O <= 0) return HSP_ERR_BAD_ARG;
+    if ((long long)H * W > 2147483647LL || (mask_stride != 0 && mask_stride != (long long)H * W)) return HSP_ERR_BAD_ARG;
+    if (O > 46340 || n > 65535) return HSP_ERR_UNSUPPORTED;
+    if (!ws || ws_bytes < hsp_roi_compact_workspace_bytes(n, O)) return HSP_ERR_WORKSPACE;
+    const int nchunk = (O * O + PC_CHUNK - 1) / PC_CHUNK;
+    hipStream_t st = as_stream(stream);
+    int32_t* cnt = reinterpret_cast<int32_t*>(ws);
+    hipLaunchKernelGGL(roi_count_kernel<D>, dim3(nchunk, n), dim3(256), 0, st, depth, mask, mask_stride, inst_id, xf, H, W, O,
+                       nchunk, cnt);
+    int rc = check_launch();
+    if (rc) return rc;
+    hipLaunchKernelGGL(roi_write_kernel<D>, dim3(nchunk, n), dim3(256), 0, st, depth, mask, mask_stride, inst_id, xf, H, W, O,
+                       nchunk, cnt, src, count);
+    return check_launch();
+}
+
+extern "C" int hsp_roi_compact_f32(const float* depth, const uint8_t* mask, long long mask_stride, const int32_t* inst_id,
+                                   const double* xf, int n, int H, int W, int O, int32_t* src, int32_t* count, void* ws,
+                                   size_t ws_bytes, hspStream_t stream) {
+    return roi_compact(depth, mask, mask_stride, inst_id, xf, n, H, W, O, src, count, ws, ws_bytes, stream);
+}
+
+extern "C" int hsp_roi_compact_u16(const uint16_t* depth, const uint8_t* mask, long long mask_stride, const int32_t* inst_id,
+                                   const double* xf, int n, int H, int W, int O, int32_t* src, int32_t* count, void* ws,
+                                   size_t ws_bytes, hspStream_t stream) {
+    return roi_compact(depth, mask, mask_stride, inst_id, xf, n, H, W, O, src, count, ws, ws_bytes, stream);
+}
+
+template <typename D>
+static int frame_to_pcl(const D* depth, int H, int W, const double* camK, int camK_rows, const int32_t* src,
+                        long long src_stride, const int32_t* choose, int n, int S, float* pc, hspStream_t stream) {
+    if (!depth || !camK || !src || !choose || !pc || n <= 0 || S <= 0 || H <= 0 || W <= 0 || src_stride <= 0)
+        return HSP_ERR_BAD_ARG;
+    if ((long long)H * W > 2147483647LL || (camK_rows != 1 && camK_rows != n) || (long long)n * S > 2147483647LL)
+        return HSP_ERR_BAD_ARG;
+    hipLaunchKernelGGL(frame_to_pcl_kernel<D>, dim3((n * S + 255) / 256), dim3(256), 0, as_stream(stream), depth, H, W, camK,
+                       camK_rows, src, src_stride, choose, n, S, pc);
+    return check_launch();
+}
+
+extern "C" int hsp_frame_to_pcl_f32(const float* depth, int H, int W, const double* camK, int camK_rows, const int32_t* src,
+                                    long long src_stride, const int32_t* choose, int n, int S, float* pc,
+                                    hspStream_t stream) {
+    return frame_to_pcl(depth, H, W, camK, camK_rows, src, src_stride, choose, n, S, pc, stream);
+}
+
+extern "C" int hsp_frame_to_pcl_u16(const uint16_t* depth, int H, int W, const double* camK, int camK_rows,
+                                    const int32_t* src, long long src_stride, const int32_t* choose, int n, int S, float* pc,
+                                    hspStream_t stream) {
+    return frame_to_pcl(depth, H, W, camK, camK_rows, src, src_stride, choose, n, S, pc, stream);
 }
 
 extern "C" int hsp_generate_rt(const float* p_green, const float* p_red, const float* f_green, const float* f_red,

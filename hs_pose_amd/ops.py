@@ -2627,3 +2627,68 @@ def depth_to_pcl(depth, xymap, camK64, pix, choose):
     _run("hsp_depth_to_pcl", (_p(depth), _p(xymap), _p(camK64), _p(pix), _p(choose), B, HW, S, _p(pc), _stream()),
          key=f"B{B}S{S}", abytes=B * S * 32)
     return pc
+
+
+_FRAME_DEPTH = {torch.float32: "_f32", torch.uint16: "_u16"}
+
+
+def _req_frame_depth(depth, name):
+    if not isinstance(depth, torch.Tensor) or not depth.is_cuda:
+        raise HspError(f"{name}: expected a GPU tensor (hs_pose_amd has no CPU path), got "
+                       f"{getattr(depth, 'device', type(depth))}")
+    if depth.dtype not in _FRAME_DEPTH or depth.dim() != 2 or depth.numel() == 0 or depth.numel() >= 2 ** 31:
+        raise HspError(f"{name}: expected an (H,W) float32 or uint16 frame with H*W < 2^31, got {tuple(depth.shape)} "
+                       f"{depth.dtype}")
+    return depth.detach() if depth.is_contiguous() else depth.detach().contiguous()
+
+
+def roi_compact(depth, mask, xf, out_size, inst_ids=None):
+    """the crop chain of load_data_eval.py:215-252 without the crops: depth (H,W) fp32 or uint16, mask uint8 (n,H,W) (one
+    mask per instance) or (H,W) (one label image for all), xf (n,3) float64 = (m0, b1, b2) of the inverse crop transform
+    (include/hsp.h), inst_ids (n) int32 or None (a pixel belongs to instance j if mask == inst_ids[j]; None: if mask != 0)
+    -> (src (n, O*O) int32, count (n,2) int32): the frame pixel ids of the crop pixels with depth > 0 and the mask set, in
+    crop row-major order, and [mask-and-depth valid, depth valid]; entries of src past count[j,0] are undefined."""
+    depth = _req_frame_depth(depth, "roi_compact.depth")
+    mask = _req(mask.detach() if isinstance(mask, torch.Tensor) else mask, torch.uint8, "roi_compact.mask")
+    xf = _req(xf, torch.float64, "roi_compact.xf")
+    H, W = depth.shape
+    O = int(out_size)
+    if xf.dim() != 2 or xf.shape[1] != 3 or xf.shape[0] == 0:
+        raise HspError("roi_compact: expects xf (n,3) float64 with n >= 1")
+    n = xf.shape[0]
+    if tuple(mask.shape) not in ((n, H, W), (H, W)):
+        raise HspError(f"roi_compact: expects mask ({n},{H},{W}) or ({H},{W}), got {tuple(mask.shape)}")
+    if not 0 < O <= 46340 or n > 65535:
+        raise HspError(f"roi_compact: out_size {O} / n {n} out of range (0 < out_size <= 46340, n <= 65535)")
+    if inst_ids is not None:
+        inst_ids = _req(inst_ids, torch.int32, "roi_compact.inst_ids")
+        if inst_ids.shape != (n,):
+            raise HspError(f"roi_compact: expects inst_ids ({n},), got {tuple(inst_ids.shape)}")
+    src = torch.empty(n, O * O, dtype=torch.int32, device=depth.device)
+    count = torch.empty(n, 2, dtype=torch.int32, device=depth.device)
+    wsb = lib().hsp_roi_compact_workspace_bytes(n, O)
+    ws = _ws(wsb, depth.device)
+    _run("hsp_roi_compact" + _FRAME_DEPTH[depth.dtype],
+         (_p(depth), _p(mask), H * W if mask.dim() == 3 else 0, _p(inst_ids), _p(xf), n, H, W, O, _p(src), _p(count), _p(ws),
+          wsb, _stream()),
+         key=f"n{n}O{O}", abytes=n * O * O * (depth.element_size() + 1 + 4))
+    return src, count
+
+
+def frame_to_pcl(depth, camK64, src, choose):
+    """back-project the chosen crop pixels straight from the frame (load_data_eval.py:253-254): depth (H,W) fp32 or uint16,
+    camK (1|n,3,3) float64, src (n,L) int32 from roi_compact, choose (n,S) int32 -> (n,S,3) fp32 metres."""
+    depth = _req_frame_depth(depth, "frame_to_pcl.depth")
+    camK64 = _req(camK64.detach() if isinstance(camK64, torch.Tensor) else camK64, torch.float64, "frame_to_pcl.camK")
+    src = _req(src, torch.int32, "frame_to_pcl.src")
+    choose = _req(choose, torch.int32, "frame_to_pcl.choose")
+    H, W = depth.shape
+    if src.dim() != 2 or choose.dim() != 2 or src.shape[0] != choose.shape[0] or src.shape[0] == 0 or choose.shape[1] == 0 \
+            or camK64.numel() not in (9, 9 * src.shape[0]):
+        raise HspError("frame_to_pcl: expects depth (H,W), camK (1|n,3,3) f64, src (n,L), choose (n,S) with n, S >= 1")
+    n, S = choose.shape
+    pc = torch.empty(n, S, 3, dtype=torch.float32, device=depth.device)
+    _run("hsp_frame_to_pcl" + _FRAME_DEPTH[depth.dtype],
+         (_p(depth), H, W, _p(camK64), camK64.numel() // 9, _p(src), src.shape[1], _p(choose), n, S, _p(pc), _stream()),
+         key=f"n{n}S{S}", abytes=n * S * (8 + depth.element_size() + 12))
+    return pc

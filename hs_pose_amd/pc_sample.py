@@ -7,6 +7,12 @@ pixel -- pc_sample.py:59-60).  The device work is two launches for the whole bat
 (``hsp_pc_compact`` / ``hsp_pc_gather``, csrc/frontend.hip) with ONE device->host copy (the per-image
 valid-pixel counts the host needs before it can draw) instead of the reference's per-image chain of
 H x W maps, boolean-index compactions and implicit syncs.
+
+``frame_to_pcl`` is the step in front of that for a whole camera frame: the evaluation loader's per-instance crop chain
+(evaluation/load_data_eval.py:207-254 -- ``get_bbox``, three ``cv2.warpAffine(INTER_NEAREST)`` over the frame, the two validity
+sums, ``_depth_to_pcl`` and ``_sample_points``) on a frame that is uploaded once: ``roi_window`` on the host, then
+``hsp_roi_compact`` / ``hsp_frame_to_pcl`` (two stages, ONE device->host copy of the counts in between, the draws on numpy's
+global generator like ``_sample_points``).  The crops themselves are never built.
 """
 import numpy as np
 import torch
@@ -72,3 +78,81 @@ def depth_to_pcl(depth, K, xymap, mask, n_pts=None, min_pts=50):
         choose[i] = sample_point_ids(int(counts[i]), n_pts)
     choose_d = torch.from_numpy(choose).to(depth.device, non_blocking=True)
     return ops.depth_to_pcl(d, xymap.reshape(B, 2, HW), K64.contiguous(), pix, choose_d)
+
+
+def roi_window(bbox, im_H, im_W):
+    """The square crop window of a detection: ``get_bbox`` (tools/eval_utils.py:159-187, its hard-wired 480 x 640 frame
+    included) followed by load_data_eval.py:221-228.  bbox = (y1, x1, y2, x2) integers -> (center (2,) float32 = (cx, cy),
+    scale float).  Integer arithmetic only: the window's corners are integers, so the centre is an integer or a half."""
+    y1, x1, y2, x2 = (int(v) for v in bbox)
+    if (y1, x1, y2, x2) != tuple(bbox):
+        raise ValueError(f"roi_window: expects an integer box (y1, x1, y2, x2), got {tuple(bbox)}")
+    half = min((max(y2 - y1, x2 - x1) // 40 + 1) * 40, 440) // 2
+    rmin, rmax = (y1 + y2) // 2 - half, (y1 + y2) // 2 + half
+    cmin, cmax = (x1 + x2) // 2 - half, (x1 + x2) // 2 + half
+    if rmin < 0:
+        rmin, rmax = 0, rmax - rmin
+    if cmin < 0:
+        cmin, cmax = 0, cmax - cmin
+    if rmax > 480:
+        rmin, rmax = rmin - (rmax - 480), 480
+    if cmax > 640:
+        cmin, cmax = cmin - (cmax - 640), 640
+    scale = min(max(rmax - rmin, cmax - cmin), max(int(im_H), int(im_W)))
+    return np.array([(cmin + cmax) * 0.5, (rmin + rmax) * 0.5], dtype=np.float32), float(scale)
+
+
+def roi_windows(bboxes, im_H, im_W):
+    """``roi_window`` of every row of bboxes (n,4) -> (centers (n,2) float32, scales (n,) float64)."""
+    wins = [roi_window(tuple(np.asarray(b).tolist()), im_H, im_W) for b in bboxes]
+    centers = np.stack([w[0] for w in wins]) if wins else np.zeros((0, 2), np.float32)
+    return centers, np.array([w[1] for w in wins], dtype=np.float64)
+
+
+def roi_transform(centers, scales, out_size):
+    """(n,3) float64 rows (m0, b1, b2): the inverse of ``crop_resize_by_warp_affine``'s matrix with rot = 0
+    (tools/dataset_utils.py:80-135), in the order of operations include/hsp.h fixes (every step one float64 rounding)."""
+    c = np.asarray(centers, dtype=np.float64).reshape(-1, 2)
+    s = np.asarray(scales, dtype=np.float64).reshape(-1)
+    if c.shape[0] != s.shape[0] or not (np.isfinite(c).all() and np.isfinite(s).all() and (s > 0).all()):
+        raise ValueError("roi_transform: expects n finite centres (n,2) and n finite scales > 0")
+    O = float(out_size)
+    a = O / s
+    tx = O / 2 - a * c[:, 0]
+    ty = O / 2 - a * c[:, 1]
+    D = 1.0 / (a * a)
+    m0 = a * D
+    return np.stack([m0, -m0 * tx, -m0 * ty], axis=1)
+
+
+def frame_to_pcl(depth, masks, centers, scales, K, n_pts=None, out_size=None, inst_ids=None, min_pts=2):
+    """The evaluation loader's crops and clouds for all detections of one frame (load_data_eval.py:230-254; with ``inst_ids``
+    and ``min_pts=50`` the training loader's, datasets/load_data.py:234-278 without ``defor_2D``).
+
+    depth (H,W) fp32 or uint16 mm on the device, masks uint8/bool (n,H,W) on the device -- or one (H,W) label image with
+    inst_ids (n,) --, centers (n,2) / scales (n,) on the host (``roi_windows``, or the loader's DZI draws), K (3,3) or (n,3,3)
+    -> (n, n_pts, 3) fp32 metres, or None if an instance has <= 1 crop pixels with depth or fewer than min_pts with depth and
+    mask (the loader skips such a frame; decided before anything is drawn).  n_pts defaults to FLAGS.random_points, out_size to
+    FLAGS.img_size.  One device->host copy; per instance, in order, the draws of ``sample_point_ids``."""
+    n_pts = int(FLAGS.random_points if n_pts is None else n_pts)
+    O = int(FLAGS.img_size if out_size is None else out_size)
+    xf = roi_transform(centers, scales, O)
+    n = xf.shape[0]
+    dev = depth.device
+    if n == 0:
+        return torch.zeros(0, n_pts, 3, dtype=torch.float32, device=dev)
+    if masks.dtype == torch.bool:
+        masks = masks.view(torch.uint8)
+    ids_d = None
+    if inst_ids is not None:
+        ids_d = torch.as_tensor(np.asarray(inst_ids).astype(np.int32)).to(dev, non_blocking=True)
+    K64 = torch.as_tensor(K, dtype=torch.float64).reshape(-1, 9).to(dev, non_blocking=True)
+    src, count = ops.roi_compact(depth, masks, torch.from_numpy(xf).to(dev, non_blocking=True), O, ids_d)
+    counts = count.cpu().numpy()                               # the one sync of the front end
+    if (counts[:, 1] <= 1).any() or (counts[:, 0] < min_pts).any():
+        return None
+    choose = np.empty((n, n_pts), dtype=np.int32)
+    for j in range(n):
+        choose[j] = sample_point_ids(int(counts[j, 0]), n_pts)
+    choose_d = torch.from_numpy(choose).to(dev, non_blocking=True)
+    return ops.frame_to_pcl(depth, K64.contiguous(), src, choose_d)

@@ -674,6 +674,41 @@ int hsp_pc_gather(const float *depth, const float *coor2d, const float *camK, co
 int hsp_depth_to_pcl(const float *depth, const float *xymap, const double *camK, const int32_t *pix,
                      const int32_t *choose, int B, int HW, int S, float *pc, hspStream_t stream);
 
+/* ---- detections of a depth frame -> instance clouds -------------------------------------------------
+ * replaces the crop chain of the evaluation loader, evaluation/load_data_eval.py:215-254: get_2d_coord_np (:215), three
+ * crop_resize_by_warp_affine(..., INTER_NEAREST) over the frame (:231-243, tools/dataset_utils.py:80-93 with rot = 0), the two
+ * validity sums (:246-252) and the boolean compaction inside _depth_to_pcl (:309-320); with inst_id also the training
+ * loader's `mask == inst_id` (datasets/load_data.py:239-240).  The crops are never built: a nearest-neighbour warp of the coordinate
+ * grid returns the coordinates of the pixel it sampled, so the three crops are views of one integer map from crop pixel
+ * (u, v) (column, row) to frame pixel (X, Y), warpAffine's fixed-point form
+ *     X = (rint(b1 * 1024) + 512 + rint(m0 * u * 1024)) >> 10,   Y = (rint(b2 * 1024) + 512 + rint(m0 * v * 1024)) >> 10
+ * (rint: float64, half to even; >>: arithmetic; each rint term clamped to +-2^52), where xf (n,3) DOUBLE = (m0, b1, b2) is the
+ * inverse of the forward matrix a = O / scale, tx = O/2 - a * cx, ty = O/2 - a * cy: D = 1 / (a * a), m0 = a * D, b1 = -m0 * tx,
+ * b2 = -m0 * ty, computed by the host in float64.  (X, Y) outside the frame reads the constant border 0: never valid.
+ * depth (H,W) fp32 (_f32) or 16-bit unsigned (_u16, what the PNG loader yields), H * W < 2^31; mask uint8 with an ELEMENT
+ * stride per instance: H * W = one mask per instance (n,H,W), 0 = one label image shared by all.  inst_id (n) int32 or NULL:
+ * a pixel belongs to instance j if mask == inst_id[j], with NULL if mask != 0.
+ * src (n, O*O) int32 = frame pixel id Y * W + X of every crop pixel with depth > 0 and the mask set, in crop row-major order
+ * (v, u); entries past the count are undefined; a source pixel sampled by several crop pixels (scale < O) appears once per crop
+ * pixel, like in the reference.  count (n,2) int32 = [mask-and-depth valid, depth valid] (the loader's two rejection tests).
+ * n <= 65535, O <= 46340. */
+size_t hsp_roi_compact_workspace_bytes(int n, int O);   /* per-chunk count pairs of the two-launch compaction */
+int hsp_roi_compact_f32(const float *depth, const uint8_t *mask, long long mask_stride, const int32_t *inst_id,
+                        const double *xf, int n, int H, int W, int O, int32_t *src, int32_t *count, void *ws,
+                        size_t ws_bytes, hspStream_t stream);
+int hsp_roi_compact_u16(const uint16_t *depth, const uint8_t *mask, long long mask_stride, const int32_t *inst_id,
+                        const double *xf, int n, int H, int W, int O, int32_t *src, int32_t *count, void *ws,
+                        size_t ws_bytes, hspStream_t stream);
+/* replaces _depth_to_pcl(roi_depth, out_camK, roi_coord_2d, roi_mask) / 1000.0 and the gather of _sample_points,
+ * evaluation/load_data_eval.py:253-254, :294-320, on the frame itself: for p = src[j, choose[j,s]] the pixel coordinates are
+ * u = float(p % W), v = float(p / W) (the float32 grid values the reference warps, exact), then hsp_depth_to_pcl's arithmetic.
+ * camK (camK_rows, 9) DOUBLE with camK_rows = 1 (one camera for all) or n; src rows of pitch src_stride; choose (n,S) int32
+ * -> pc (n,S,3) fp32 metres.  An index outside its src row or outside the frame gives NaN. */
+int hsp_frame_to_pcl_f32(const float *depth, int H, int W, const double *camK, int camK_rows, const int32_t *src,
+                         long long src_stride, const int32_t *choose, int n, int S, float *pc, hspStream_t stream);
+int hsp_frame_to_pcl_u16(const uint16_t *depth, int H, int W, const double *camK, int camK_rows, const int32_t *src,
+                         long long src_stride, const int32_t *choose, int n, int S, float *pc, hspStream_t stream);
+
 /* ---- pose matrix assembly -----------------------------------------------------------------------
  * replaces generate_RT([p_green,p_red],[f_green,f_red], T, 'vec', sym)     tools/geom_utils.py:232-244
  * (with to_R_matrices / get_vertical_rot_vec_in_batch / get_rot_mat_y_first, tools/rot_utils.py:39-100)
