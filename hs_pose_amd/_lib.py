@@ -140,6 +140,7 @@ SIGNATURES = {
     "hsp_roi_compact_u16": (_i, [_vp, _vp, ctypes.c_longlong, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "hsp_frame_to_pcl_f32": (_i, [_vp, _i, _i, _vp, _i, _vp, ctypes.c_longlong, _vp, _i, _i, _vp, _vp]),
     "hsp_frame_to_pcl_u16": (_i, [_vp, _i, _i, _vp, _i, _vp, ctypes.c_longlong, _vp, _i, _i, _vp, _vp]),
+    "hsp_sample_ids": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "hsp_generate_rt": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
     "hsp_sumsq_workspace_bytes": (_sz, [ctypes.c_longlong]),
     "hsp_sumsq_f32": (_i, [_vp, ctypes.c_longlong, _vp, _vp, _sz, _vp]),

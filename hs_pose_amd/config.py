@@ -34,6 +34,9 @@ class _Flags:
         lr_pose=1.0,          # config.py:98
         pool_sampler='random',  # (not in the reference) Pool_layer's down-sampler: 'random' -- the reference's randperm slice --
                                 # or 'fps' -- per-cloud farthest-point sampling on the device (gcn3d.Pool_layer)
+        pc_sampler='host',      # (not in the reference) who draws the rows an instance cloud keeps (pc_sample.py): 'host' -- the
+                                # reference's draws on numpy's global generator -- or 'device' -- a keyed counter-based draw
+                                # inside the front end (pc_sample.DeviceSampler), no count copy and no sync
     )
 
     def __init__(self):

@@ -11,6 +11,8 @@
 //    get_bbox window, three cv2.warpAffine(INTER_NEAREST) over the frame, boolean compaction.  Same two stages one step
 //    earlier: stage 1 walks the crop pixels of every instance through the warp's integer map and compacts the source ids of
 //    the valid ones; stage 2 back-projects the chosen ones straight from the frame.
+//  * the chosen rows themselves, optionally: a keyed counter-based draw on the device between the two stages (hsp_sample_ids)
+//    in place of the host's, so that neither front end has to bring its counts to the host.
 //  * (R|t) assembly: replaces generate_RT(..., mode='vec') (tools/geom_utils.py:232-244 with
 //    tools/rot_utils.py:39-100): confidence-weighted orthogonalisation of the two predicted axes and
 //    the 4x4 pose matrix, one lane per object instead of ~40 tiny launches.
@@ -279,6 +281,67 @@ __global__ __launch_bounds__(256) void frame_to_pcl_kernel(const D* __restrict__
     backproject_f64((double)(float)u, (double)(float)v, (double)depth[p], camK + (camK_rows > 1 ? (size_t)j * 9 : 0), o);
 }
 
+// ---- the rows each instance keeps, drawn on the device (include/hsp.h: hsp_sample_ids states the construction) ------------
+// A stand-alone launch between the compaction and the back-projection: one lane per (instance, kept row), uint32 arithmetic
+// only.  The permutation is a 4-round balanced Feistel network over the smallest even width that holds the count, cycle-walked
+// into [0, c): O(S) work per instance whatever c, no selection pass, no scratch.
+__device__ __forceinline__ uint32_t fmix32(uint32_t h) {
+    h ^= h >> 16;
+    h *= 0x85ebca6bu;
+    h ^= h >> 13;
+    h *= 0xc2b2ae35u;
+    h ^= h >> 16;
+    return h;
+}
+
+__device__ __forceinline__ uint32_t absorb(uint32_t h, uint32_t w) { return fmix32((h ^ w) + 0x9e3779b9u); }
+
+__global__ __launch_bounds__(256) void sample_ids_kernel(const int32_t* __restrict__ count, int stride, int n, int S,
+                                                         int min_pts, int min_depth_pts, int short_mode,
+                                                         const unsigned long long* __restrict__ key,
+                                                         int32_t* __restrict__ choose, int32_t* __restrict__ status) {
+    const unsigned eu = blockIdx.x * 256u + threadIdx.x;      // (n * S < 2^31: the last block's tail stays below 2^32)
+    if (eu >= (unsigned)(n * S)) return;
+    const int e = (int)eu;
+    const int j = e / S, s = e - j * S;
+    const int c = count[(size_t)j * stride];
+    int st = c < min_pts ? 1 : 0;
+    if (stride == 2 && count[(size_t)j * 2 + 1] < min_depth_pts) st |= 2;
+    if (s == 0) status[j] = st;
+    int out;
+    if (st != 0 || c <= 0) {
+        out = -1;
+    } else if (short_mode == 0 && c <= S) {
+        out = s % c;
+    } else {
+        const unsigned long long seed = key[0], call = key[1];
+        uint32_t kj = absorb(0u, (uint32_t)seed);
+        kj = absorb(kj, (uint32_t)(seed >> 32));
+        kj = absorb(kj, (uint32_t)call);
+        kj = absorb(kj, (uint32_t)(call >> 32));
+        kj = absorb(kj, (uint32_t)j);
+        if (c < S) {
+            out = (int)(((unsigned long long)absorb(absorb(kj, 0xffffffffu), (uint32_t)s) * (unsigned long long)c) >> 32);
+        } else {
+            const uint32_t k0 = absorb(kj, 0u), k1 = absorb(kj, 1u), k2 = absorb(kj, 2u), k3 = absorb(kj, 3u);
+            const int bits = c <= 1 ? 0 : 32 - __clz(c - 1);
+            const int half = max(1, (bits + 1) / 2);
+            const uint32_t mask = (1u << half) - 1u;
+            uint32_t x = (uint32_t)s;
+            do {
+                uint32_t L = x >> half, R = x & mask, t;
+                t = L ^ (fmix32(R ^ k0) & mask); L = R; R = t;
+                t = L ^ (fmix32(R ^ k1) & mask); L = R; R = t;
+                t = L ^ (fmix32(R ^ k2) & mask); L = R; R = t;
+                t = L ^ (fmix32(R ^ k3) & mask); L = R; R = t;
+                x = (L << half) | R;
+            } while (x >= (uint32_t)c);
+            out = (int)x;
+        }
+    }
+    choose[e] = out;
+}
+
 __device__ __forceinline__ void rodrigues_apply(const float rx[3], float s, float c, const float v[3], float o[3]) {
     // rows of to_rot_matrix_in_batch (rot_utils.py:67-75) times v
     const float t = 1.f - c;
@@ -430,6 +493,17 @@ extern "C" int hsp_frame_to_pcl_u16(const uint16_t* depth, int H, int W, const d
                                     const int32_t* src, long long src_stride, const int32_t* choose, int n, int S, float* pc,
                                     hspStream_t stream) {
     return frame_to_pcl(depth, H, W, camK, camK_rows, src, src_stride, choose, n, S, pc, stream);
+}
+
+extern "C" int hsp_sample_ids(const int32_t* count, int count_stride, int n, int S, int min_pts, int min_depth_pts,
+                              int short_mode, const unsigned long long* key, int32_t* choose, int32_t* status,
+                              hspStream_t stream) {
+    if (!count || !key || !choose || !status || n <= 0 || n > 65535 || S <= 0) return HSP_ERR_BAD_ARG;
+    if ((count_stride != 1 && count_stride != 2) || (short_mode != 0 && short_mode != 1)) return HSP_ERR_BAD_ARG;
+    if ((long long)n * S > 2147483647LL) return HSP_ERR_BAD_ARG;
+    hipLaunchKernelGGL(sample_ids_kernel, dim3((unsigned)(((long long)n * S + 255) / 256)), dim3(256), 0, as_stream(stream), count, count_stride, n,
+                       S, min_pts, min_depth_pts, short_mode, key, choose, status);
+    return check_launch();
 }
 
 extern "C" int hsp_generate_rt(const float* p_green, const float* p_red, const float* f_green, const float* f_red,

@@ -2,15 +2,58 @@
 
 The reference's loop builds one 1028-point cloud per detected instance on the CPU (evaluation/load_data_eval.py:207-254) and then
 runs the network and ``generate_RT`` on them (evaluation/evaluate.py:90-106).  ``FramePipeline`` chains the package's pieces for
-both: ``pc_sample.roi_windows`` (host integers) -> ``pc_sample.frame_to_pcl`` (two kernels on the frame, one device->host copy of
-the counts, the sample draws on numpy's global generator) -> a ``graph.GraphedInference`` kept per instance count.  Nothing is
-captured around the front end: its draws need the counts on the host.
+both: ``pc_sample.roi_windows`` (host integers) -> the frame front end -> a ``graph.GraphedInference`` kept per instance count.
+
+With the host sampler (the default, ``FLAGS.pc_sampler = 'host'``) the front end is ``pc_sample.frame_to_pcl``: two kernels on
+the frame, one device->host copy of the counts, the sample draws on numpy's global generator.  Nothing can be captured around
+it: its draws need the counts on the host.  With a device sampler (``sampler='device'`` or a ``pc_sample.DeviceSampler``) it is
+``pc_sample.frame_to_pcl_device``: three kernels, issued eagerly ahead of the replay with nothing copied back, or -- with
+``one_graph=True`` -- captured together with the network, so that a frame is a few small uploads and ONE replay.
 """
 import numpy as np
 import torch
 
-from . import pc_sample
+from . import ops, pc_sample
+from .config import FLAGS
 from .graph import GraphedInference
+
+
+class _FrameGraph:
+    """roi_compact -> sample_ids -> frame_to_pcl -> network -> generate_RT of one (instance count, frame shape, depth dtype,
+    mask form) as one captured graph over static buffers: the frame, the masks (or the label image and its ids), the crop
+    transforms, K, the class rows and the sampler's key.  Everything is issued on the capture stream, in order; the kernels'
+    workspaces and outputs come from the capture's pool."""
+
+    def __init__(self, pipe, sampler, depth, masks, ids, xf, K, obj_id, n_pts, O):
+        dev = depth.device
+        self.depth, self.masks = depth.clone(), masks.clone()
+        self.ids = None if ids is None else pc_sample._upload(ids, np.int32, dev)
+        self.xf = pc_sample._upload(xf, np.float64, dev)
+        self.K = pc_sample._upload(K, np.float64, dev)
+        self.obj_id = pc_sample._upload(obj_id, np.int64, dev)
+        self.status = None
+        key = sampler.key
+        pipe._stand_in_cloud(n_pts, dev)                         # (made here: an upload cannot happen inside the capture)
+
+        def front_end():
+            src, count = ops.roi_compact(self.depth, self.masks, self.xf, O, self.ids)
+            choose, self.status = ops.sample_ids(count, n_pts, key, pipe.min_pts, 2, 0)
+            return pipe._network_input(ops.frame_to_pcl(self.depth, self.K, src, choose), self.status)
+
+        n = xf.shape[0]
+        self.graphed = GraphedInference(pipe.net, torch.empty(n, n_pts, 3, device=dev), self.obj_id,
+                                        pipe.mean_shapes[self.obj_id], pipe.sym_infos[self.obj_id], prologue=front_end)
+
+    def load(self, pipe, depth, masks, ids, xf, K, obj_id):
+        dev = depth.device
+        self.depth.copy_(depth, non_blocking=True)
+        self.masks.copy_(masks, non_blocking=True)
+        if ids is not None:
+            pc_sample._upload(ids, np.int32, dev, out=self.ids)
+        pc_sample._upload(xf, np.float64, dev, out=self.xf)
+        pc_sample._upload(K, np.float64, dev, out=self.K)
+        pc_sample._upload(obj_id, np.int64, dev, out=self.obj_id)
+        self.graphed.load(mean_shape=pipe.mean_shapes[self.obj_id], sym=pipe.sym_infos[self.obj_id])
 
 
 class FramePipeline:
@@ -19,31 +62,94 @@ class FramePipeline:
     (``get_sym_info``), row ``c`` for the detector's class id ``c + 1`` (the loader's ``cat_id_0base``).
 
     ``pipe(depth, masks, bboxes, class_ids, K) -> (pred_RT (n,4,4), pred_s (n,3))`` for depth (H,W) fp32 or uint16 mm and
-    masks (n,H,W) uint8/bool on the device, bboxes (n,4) integer (y1, x1, y2, x2) and class_ids (n,) on the host
-    (``pred_bboxes`` / ``pred_class_ids``), K (3,3).  Zero-row outputs for n = 0 (evaluate.py:85-89); None when
-    ``frame_to_pcl`` rejects the frame (the loader returns None for it).  The outputs are the caller's (copies of the graph's
-    static buffers).  The first frame with a new instance count captures its graph (a few ms, see GraphedInference)."""
+    masks (n,H,W) uint8/bool on the device (or one (H,W) label image with ``inst_ids`` (n,)), bboxes (n,4) integer
+    (y1, x1, y2, x2) and class_ids (n,) on the host (``pred_bboxes`` / ``pred_class_ids``), K (3,3).  Zero-row outputs for n = 0
+    (evaluate.py:85-89); None when the front end rejects the frame (the loader returns None for it).  The outputs are the
+    caller's (copies of the graph's static buffers).  The first frame with a new instance count captures its graph (a few ms,
+    see GraphedInference).
 
-    def __init__(self, network, mean_shapes, sym_infos, n_pts=None, out_size=None, min_pts=2):
+    ``sampler``: None (follow ``FLAGS.pc_sampler`` at each call), 'host', 'device' or a ``pc_sample.DeviceSampler``.  With a
+    device sampler nothing is copied back before the poses: ``sync=True`` reads the per-instance status once, after everything
+    is queued, and returns None for a rejected frame as above; ``sync=False`` never waits and returns
+    ``(pred_RT, pred_s, status (n,) int32)`` as device tensors -- the rows of an instance whose status is not 0 mean nothing
+    (the network ran on a stand-in cloud for it).  ``one_graph=True`` (device sampler only) captures the front end with the
+    network: one graph per (instance count, frame shape, depth dtype, mask form), one replay per frame."""
+
+    def __init__(self, network, mean_shapes, sym_infos, n_pts=None, out_size=None, min_pts=2, sampler=None, one_graph=False,
+                 sync=True):
         self.net, self.mean_shapes, self.sym_infos = network, mean_shapes, sym_infos
         self.n_pts, self.out_size, self.min_pts = n_pts, out_size, min_pts
+        self.sampler, self.one_graph, self.sync = sampler, bool(one_graph), bool(sync)
         self.graphs = {}                                         # instance count -> GraphedInference
+        self.frame_graphs = {}                                   # one_graph: (sampler, n, frame shape, dtype, ...) -> _FrameGraph
+        self._stand_in = None
 
-    def __call__(self, depth, masks, bboxes, class_ids, K):
+    def _network_input(self, PC, status):
+        """the clouds the network is given: a rejected instance's rows are NaN by contract, and the neighbour search is not
+        meant for those -- such an instance gets a fixed, well-spread stand-in cloud, its outputs are discarded or flagged"""
+        return torch.where((status != 0)[:, None, None], self._stand_in_cloud(PC.shape[1], PC.device), PC)
+
+    def _stand_in_cloud(self, n_pts, dev):
+        if self._stand_in is None or self._stand_in.shape[0] != n_pts or self._stand_in.device != dev:
+            g = torch.Generator().manual_seed(0)
+            self._stand_in = ((torch.rand(n_pts, 3, generator=g) - 0.5) * 0.2).to(dev)
+        return self._stand_in
+
+    def __call__(self, depth, masks, bboxes, class_ids, K, inst_ids=None):
         n = len(bboxes)
         dev = depth.device
+        sampler = pc_sample.resolve_sampler(self.sampler, dev)
+        if sampler is None and (self.one_graph or not self.sync):
+            raise ValueError("FramePipeline: one_graph=True and sync=False need a device sampler (sampler='device', a DeviceSampler, "
+                             "or FLAGS.pc_sampler = 'device'): the host draws wait for the counts")
         if n == 0:
-            return torch.zeros(0, 4, 4, device=dev), torch.zeros(0, 3, device=dev)
+            out = torch.zeros(0, 4, 4, device=dev), torch.zeros(0, 3, device=dev)
+            return out if self.sync else out + (torch.zeros(0, dtype=torch.int32, device=dev),)
         centers, scales = pc_sample.roi_windows(bboxes, depth.shape[0], depth.shape[1])
-        PC = pc_sample.frame_to_pcl(depth, masks, centers, scales, K, self.n_pts, self.out_size, min_pts=self.min_pts)
-        if PC is None:
-            return None
-        obj_id = torch.as_tensor(np.asarray(class_ids).astype(np.int64) - 1).to(dev, non_blocking=True)
-        mean_shape, sym = self.mean_shapes[obj_id], self.sym_infos[obj_id]
-        graphed = self.graphs.get(n)
-        if graphed is None:
-            graphed = self.graphs[n] = GraphedInference(self.net, PC, obj_id, mean_shape, sym)
+        if sampler is None:
+            PC = pc_sample.frame_to_pcl(depth, masks, centers, scales, K, self.n_pts, self.out_size, inst_ids, self.min_pts, 'host')
+            if PC is None:
+                return None
+            obj_id = torch.as_tensor(np.asarray(class_ids).astype(np.int64) - 1).to(dev, non_blocking=True)
+            status = None
+        elif self.one_graph:
+            graphed, status = self._replay_frame(sampler, depth, masks, inst_ids, centers, scales, K, class_ids)
+            PC = None
         else:
-            graphed.load(PC, obj_id, mean_shape, sym)
-        pred_RT, pred_s, _ = graphed.run()
-        return pred_RT.clone(), pred_s.clone()
+            PC, status = pc_sample.frame_to_pcl_device(depth, masks, centers, scales, K, self.n_pts, self.out_size, inst_ids,
+                                                       self.min_pts, sampler)
+            PC = self._network_input(PC, status)
+            obj_id = pc_sample._upload(np.asarray(class_ids).astype(np.int64) - 1, np.int64, dev)
+        if PC is not None:                                       # the network's own graph, behind the eager front end
+            mean_shape, sym = self.mean_shapes[obj_id], self.sym_infos[obj_id]
+            graphed = self.graphs.get(n)
+            if graphed is None:
+                graphed = self.graphs[n] = GraphedInference(self.net, PC, obj_id, mean_shape, sym)
+            else:
+                graphed.load(PC, obj_id, mean_shape, sym)
+            graphed.run()
+        pred_RT, pred_s = graphed.pred_RT.clone(), graphed.pred_s.clone()
+        if not self.sync:
+            return pred_RT, pred_s, status.clone()
+        if status is not None and bool(status.any()):            # the one wait of the device form, behind everything queued
+            return None
+        return pred_RT, pred_s
+
+    def _replay_frame(self, sampler, depth, masks, inst_ids, centers, scales, K, class_ids):
+        n_pts = int(FLAGS.random_points if self.n_pts is None else self.n_pts)
+        O = int(FLAGS.img_size if self.out_size is None else self.out_size)
+        xf = pc_sample.roi_transform(centers, scales, O)
+        if masks.dtype == torch.bool:
+            masks = masks.view(torch.uint8)
+        K = (K.detach().cpu().numpy() if isinstance(K, torch.Tensor) else np.asarray(K)).astype(np.float64).reshape(-1, 9)
+        ids = None if inst_ids is None else np.asarray(inst_ids).astype(np.int32)
+        obj_id = np.asarray(class_ids).astype(np.int64) - 1
+        key = (sampler, xf.shape[0], tuple(depth.shape), depth.dtype, masks.dim(), ids is None, K.shape[0], n_pts, O)
+        fg = self.frame_graphs.get(key)
+        if fg is None:
+            fg = self.frame_graphs[key] = _FrameGraph(self, sampler, depth, masks, ids, xf, K, obj_id, n_pts, O)
+        else:
+            fg.load(self, depth, masks, ids, xf, K, obj_id)
+        sampler.advance()
+        fg.graphed.run()
+        return fg.graphed, fg.status

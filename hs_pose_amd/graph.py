@@ -380,12 +380,18 @@ class GraphedInference:
     ``PC`` (n,N,3), ``obj_id`` (n,) or (n,1), ``mean_shape`` (n,3), ``sym`` (n,4) are static device buffers
     (``load`` copies new data in); ``run()`` draws the two Pool_layer permutations on the host generator like the
     reference's forward does, replays, and returns the static ``(pred_RT (n,4,4), pred_s (n,3), output_dict)``.
-    A detector producing a varying instance count keeps one object per count (a capture is a few ms)."""
+    A detector producing a varying instance count keeps one object per count (a capture is a few ms).
 
-    def __init__(self, network, PC, obj_id, mean_shape, sym, warmup=2):
+    ``prologue``: a callable issued at the head of the captured body, on the capture stream, whose result (n,N,3) IS the
+    cloud the network reads -- the step in front of the network captured with it (frame.FramePipeline(one_graph=True): the
+    frame front end).  It reads static buffers of its owner's; ``PC`` then only gives the shape and ``load(PC=...)`` has no
+    effect."""
+
+    def __init__(self, network, PC, obj_id, mean_shape, sym, warmup=2, prologue=None):
         from .geom_utils import generate_RT
         self.net, self._generate_RT = network, generate_RT
         self.PC, self.obj_id, self.mean_shape, self.sym = PC, obj_id, mean_shape, sym
+        self._prologue = prologue
         n, N, _ = PC.shape
         self.n_points = N
         dev = PC.device
@@ -413,6 +419,8 @@ class GraphedInference:
 
     @torch.no_grad()
     def _body(self):
+        if self._prologue is not None:
+            self.PC = self._prologue()
         with pool_feed(self.pool_idx):
             out = self.net(PC=self.PC, obj_id=self.obj_id, mean_shape=self.mean_shape, sym=self.sym)
         self.pred_RT = self._generate_RT([out['p_green_R'], out['p_red_R']], [out['f_green_R'], out['f_red_R']],

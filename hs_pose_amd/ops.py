@@ -2629,6 +2629,28 @@ def depth_to_pcl(depth, xymap, camK64, pix, choose):
     return pc
 
 
+def sample_ids(count, S, key, min_pts, min_depth_pts=0, short_mode=0):
+    """the rows each instance keeps, drawn on the device from its count (include/hsp.h: hsp_sample_ids): count (n,) int32 from
+    pc_compact or (n,2) int32 from roi_compact, key (2,) int64 on the device holding the uint64 pair (seed, call)
+    -> (choose (n,S) int32, status (n,) int32).  status bit 0: count < min_pts, bit 1: second count < min_depth_pts; such a row
+    of choose is all -1.  short_mode 0 tiles a count <= S (``_sample_points``), 1 draws with replacement (``PC_sample``)."""
+    count = _req(count, torch.int32, "sample_ids.count")
+    key = _req(key, torch.int64, "sample_ids.key")
+    S = int(S)
+    if count.dim() not in (1, 2) or (count.dim() == 2 and count.shape[1] != 2) or count.shape[0] == 0 or key.numel() != 2:
+        raise HspError(f"sample_ids: expects count (n,) or (n,2) with n >= 1 and key (2,), got {tuple(count.shape)}, "
+                       f"{tuple(key.shape)}")
+    n = count.shape[0]
+    if n > 65535 or S < 1 or n * S >= 2 ** 31 or short_mode not in (0, 1):
+        raise HspError(f"sample_ids: n {n} / S {S} / short_mode {short_mode} out of range (n <= 65535, S >= 1, n * S < 2^31, "
+                       "short_mode 0 or 1)")
+    choose = torch.empty(n, S, dtype=torch.int32, device=count.device)
+    status = torch.empty(n, dtype=torch.int32, device=count.device)
+    _run("hsp_sample_ids", (_p(count), count.dim(), n, S, int(min_pts), int(min_depth_pts), int(short_mode), _p(key), _p(choose),
+                            _p(status), _stream()), key=f"n{n}S{S}", abytes=n * (4 * count.dim() + 4 * S + 4) + 16)
+    return choose, status
+
+
 _FRAME_DEPTH = {torch.float32: "_f32", torch.uint16: "_u16"}
 
 

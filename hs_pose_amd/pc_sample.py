@@ -13,17 +13,99 @@ H x W maps, boolean-index compactions and implicit syncs.
 sums, ``_depth_to_pcl`` and ``_sample_points``) on a frame that is uploaded once: ``roi_window`` on the host, then
 ``hsp_roi_compact`` / ``hsp_frame_to_pcl`` (two stages, ONE device->host copy of the counts in between, the draws on numpy's
 global generator like ``_sample_points``).  The crops themselves are never built.
+
+Who draws is a switch: ``sampler=`` on the three functions, by default ``FLAGS.pc_sampler``.  ``'host'`` (the default) is all of
+the above, draw for draw.  ``'device'`` -- or a ``DeviceSampler`` of one's own -- draws the rows between the two stages with
+``hsp_sample_ids`` from a seeded counter-based generator: the same DISTRIBUTION (a uniform subset without replacement when long,
+tiling or a uniform draw with replacement when short), not the same draws; the counts stay on the device, nothing is copied
+back and nothing waits until the caller reads the result, and numpy's generator is never touched.  ``frame_to_pcl_device`` is
+that form bare: clouds and per-instance status, both on the device.
 """
 import numpy as np
 import torch
 
-from . import ops
+from . import ops, staging
 from .config import FLAGS
 
+_U64 = (1 << 64) - 1
 
-def PC_sample(obj_mask, Depth, camK, coor2d):
+
+class DeviceSampler:
+    """The key of the device draws (include/hsp.h: hsp_sample_ids): a seed and a call counter, two uint64 in a device buffer
+    the kernel reads -- so a captured launch sees each replay's values -- and their host copy.  ``advance()`` once per sampling
+    launch or replay: it queues the upload of (seed, counter) from pinned memory on the current stream without blocking (the
+    pattern of ``graph.upload_pool_indices``) and bumps the counter; the launch that follows draws under that pair.  Equal
+    states give equal draws: ``get_state()`` / ``set_state()`` / ``manual_seed()`` (counter back to 0)."""
+
+    def __init__(self, seed, device):
+        self.device = torch.device(device)
+        self.key = torch.zeros(2, dtype=torch.int64, device=self.device)
+        self.manual_seed(seed)
+
+    def manual_seed(self, seed):
+        self.seed, self.calls = int(seed) & _U64, 0
+        return self
+
+    def get_state(self):
+        """(seed, counter): the pair the next ``advance()`` uploads"""
+        return self.seed, self.calls
+
+    def set_state(self, state):
+        self.seed, self.calls = int(state[0]) & _U64, int(state[1]) & _U64
+
+    def advance(self):
+        words = [w - (1 << 64) if w >> 63 else w for w in (self.seed, self.calls)]      # the uint64 bits in an int64 buffer
+
+        def fill(pinned):
+            pinned[0], pinned[1] = words
+        if self.device.type == "cuda":
+            staging.upload(fill, (2,), torch.int64, self.device, out=self.key)
+        else:                                                    # (a host-side key: for inspection, the kernels are GPU-only)
+            fill(self.key)
+        self.calls = (self.calls + 1) & _U64
+        return self.key
+
+
+_default_samplers = {}
+
+
+def default_sampler(device):
+    """the module's sampler of ``device``, made on first use and seeded from ``torch.initial_seed()`` (never from a draw on
+    numpy's generator: the device form leaves that generator alone)"""
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    s = _default_samplers.get(device)
+    if s is None:
+        s = _default_samplers[device] = DeviceSampler(torch.initial_seed(), device)
+    return s
+
+
+def resolve_sampler(sampler, device):
+    """``sampler=`` of the front ends -> None (the host draws) or a DeviceSampler: None follows ``FLAGS.pc_sampler``, 'host',
+    'device' (the module's default sampler), or a DeviceSampler"""
+    if sampler is None:
+        sampler = getattr(FLAGS, "pc_sampler", "host")
+    if isinstance(sampler, DeviceSampler):
+        return sampler
+    if sampler == "host":
+        return None
+    if sampler == "device":
+        return default_sampler(device)
+    raise ValueError(f"pc sampler: expects 'host', 'device' or a DeviceSampler, got {sampler!r}")
+
+
+def _gather_safe(choose, pix, HW):
+    """``hsp_pc_gather`` / ``hsp_depth_to_pcl`` index ``pix`` with ``choose`` unchecked and a rejected row of ``choose`` is -1:
+    point such rows at entry 0 and make entry 0 a pixel id where nothing was compacted (only then is it out of range)."""
+    pix[:, 0].clamp_(0, HW - 1)
+    return choose.clamp_(min=0)
+
+
+def PC_sample(obj_mask, Depth, camK, coor2d, sampler=None):
     """obj_mask (bs,1,H,W) (or (bs,2,H,W) mask logits), Depth (bs,1,H,W) in mm, camK (bs,3,3),
-    coor2d (bs,2,H,W) pixel coordinates -> PC (bs, FLAGS.random_points, 3) in metres."""
+    coor2d (bs,2,H,W) pixel coordinates -> PC (bs, FLAGS.random_points, 3) in metres.  ``sampler``: see the module text; the
+    device form reads the rejection status once everything is queued."""
     if obj_mask.shape[1] == 2:                                 # predicted mask (pc_sample.py:16-18)
         # argmax(softmax(m)) == argmax(m); first index on ties like torch.max
         obj_mask = (obj_mask[:, 1] > obj_mask[:, 0])
@@ -33,6 +115,12 @@ def PC_sample(obj_mask, Depth, camK, coor2d):
     bs, H, W = Depth.shape[0], Depth.shape[2], Depth.shape[3]
     mask = obj_mask.reshape(bs, H * W).float()
     pix, count = ops.pc_compact(mask, Depth.reshape(bs, H * W))
+    sampler = resolve_sampler(sampler, Depth.device)
+    if sampler is not None:
+        choose_d, status = ops.sample_ids(count, samplenum, sampler.advance(), 2, 0, 1)
+        pc = ops.pc_gather(Depth.reshape(bs, H * W), coor2d.reshape(bs, 2, H * W), camK, pix,
+                           _gather_safe(choose_d, pix, H * W))
+        return (None, None) if bool(status.any()) else pc
     counts = count.cpu().numpy()                               # the one sync of the front end
     choose = np.empty((bs, samplenum), dtype=np.int32)
     for i in range(bs):
@@ -55,13 +143,13 @@ def sample_point_ids(total_pts_num, n_pts):
     return np.arange(total_pts_num)
 
 
-def depth_to_pcl(depth, K, xymap, mask, n_pts=None, min_pts=50):
+def depth_to_pcl(depth, K, xymap, mask, n_pts=None, min_pts=50, sampler=None):
     """Batched mirror of the loader's cloud extraction: ``_depth_to_pcl(depth, K, xymap, mask) / 1000.0``
     (load_data.py:275, :322-333), the ``len(pcl_in) < 50`` rejection (:276) and ``_sample_points`` (:278).
 
     depth (B,1,H,W) or (B,H,W) fp32 mm, K (3,3) or (B,3,3) (float64 like the loader's intrinsics),
     xymap (B,2,H,W), mask (B,1,H,W) -> (B,n_pts,3) fp32 metres, or None if any image has < min_pts
-    valid pixels (the loader skips such an item).  n_pts defaults to FLAGS.random_points."""
+    valid pixels (the loader skips such an item).  n_pts defaults to FLAGS.random_points.  ``sampler``: see the module text."""
     n_pts = int(FLAGS.random_points if n_pts is None else n_pts)
     B = depth.shape[0]
     HW = depth[0].numel()
@@ -70,6 +158,11 @@ def depth_to_pcl(depth, K, xymap, mask, n_pts=None, min_pts=50):
     if K64.shape[0] == 1 and B > 1:
         K64 = K64.expand(B, 9)
     pix, count = ops.pc_compact(mask.reshape(B, HW).float(), d)
+    sampler = resolve_sampler(sampler, depth.device)
+    if sampler is not None:
+        choose_d, status = ops.sample_ids(count, n_pts, sampler.advance(), min_pts, 0, 0)
+        pc = ops.depth_to_pcl(d, xymap.reshape(B, 2, HW), K64.contiguous(), pix, _gather_safe(choose_d, pix, HW))
+        return None if bool(status.any()) else pc
     counts = count.cpu().numpy()
     choose = np.empty((B, n_pts), dtype=np.int32)
     for i in range(B):
@@ -125,7 +218,42 @@ def roi_transform(centers, scales, out_size):
     return np.stack([m0, -m0 * tx, -m0 * ty], axis=1)
 
 
-def frame_to_pcl(depth, masks, centers, scales, K, n_pts=None, out_size=None, inst_ids=None, min_pts=2):
+def _upload(a, dtype, dev, out=None):
+    """a small host array -> the device (into ``out`` when given) through the pinned ring (staging.py): queued behind the
+    stream, not waited for"""
+    a = np.ascontiguousarray(a, dtype=dtype)
+    t = torch.from_numpy(a)
+    return staging.upload(lambda pinned: pinned.copy_(t), t.shape, t.dtype, dev, out=out)
+
+
+def frame_to_pcl_device(depth, masks, centers, scales, K, n_pts=None, out_size=None, inst_ids=None, min_pts=2, sampler=None):
+    """``frame_to_pcl`` with the rows drawn on the device: the same arguments, ``sampler`` a DeviceSampler (None or 'device':
+    the module's) -> (PC (n, n_pts, 3) fp32 metres, status (n,) int32), both on the device.  status bit 0: fewer than min_pts
+    crop pixels with depth and mask; bit 1: <= 1 with depth; the rows of such an instance are NaN and the frame is one the
+    loader skips.  Three launches and the uploads of the small host arrays, all queued: no device->host copy, no wait."""
+    n_pts = int(FLAGS.random_points if n_pts is None else n_pts)
+    O = int(FLAGS.img_size if out_size is None else out_size)
+    xf = roi_transform(centers, scales, O)
+    n = xf.shape[0]
+    dev = depth.device
+    sampler = resolve_sampler("device" if sampler is None else sampler, dev)
+    if sampler is None:
+        raise ValueError("frame_to_pcl_device: expects a device sampler; the host draws are frame_to_pcl's")
+    if n == 0:
+        return torch.zeros(0, n_pts, 3, dtype=torch.float32, device=dev), torch.zeros(0, dtype=torch.int32, device=dev)
+    if masks.dtype == torch.bool:
+        masks = masks.view(torch.uint8)
+    ids_d = None if inst_ids is None else _upload(np.asarray(inst_ids), np.int32, dev)
+    if isinstance(K, torch.Tensor) and K.is_cuda:
+        K64 = K.to(torch.float64).reshape(-1, 9).contiguous()
+    else:
+        K64 = _upload(np.asarray(K, dtype=np.float64).reshape(-1, 9), np.float64, dev)
+    src, count = ops.roi_compact(depth, masks, _upload(xf, np.float64, dev), O, ids_d)
+    choose, status = ops.sample_ids(count, n_pts, sampler.advance(), min_pts, 2, 0)
+    return ops.frame_to_pcl(depth, K64, src, choose), status
+
+
+def frame_to_pcl(depth, masks, centers, scales, K, n_pts=None, out_size=None, inst_ids=None, min_pts=2, sampler=None):
     """The evaluation loader's crops and clouds for all detections of one frame (load_data_eval.py:230-254; with ``inst_ids``
     and ``min_pts=50`` the training loader's, datasets/load_data.py:234-278 without ``defor_2D``).
 
@@ -133,7 +261,12 @@ def frame_to_pcl(depth, masks, centers, scales, K, n_pts=None, out_size=None, in
     inst_ids (n,) --, centers (n,2) / scales (n,) on the host (``roi_windows``, or the loader's DZI draws), K (3,3) or (n,3,3)
     -> (n, n_pts, 3) fp32 metres, or None if an instance has <= 1 crop pixels with depth or fewer than min_pts with depth and
     mask (the loader skips such a frame; decided before anything is drawn).  n_pts defaults to FLAGS.random_points, out_size to
-    FLAGS.img_size.  One device->host copy; per instance, in order, the draws of ``sample_point_ids``."""
+    FLAGS.img_size.  One device->host copy; per instance, in order, the draws of ``sample_point_ids``.  ``sampler``: see the
+    module text; the device form is ``frame_to_pcl_device`` with its status read once everything is queued."""
+    dsampler = resolve_sampler(sampler, depth.device)
+    if dsampler is not None:
+        PC, status = frame_to_pcl_device(depth, masks, centers, scales, K, n_pts, out_size, inst_ids, min_pts, dsampler)
+        return None if bool(status.any()) else PC
     n_pts = int(FLAGS.random_points if n_pts is None else n_pts)
     O = int(FLAGS.img_size if out_size is None else out_size)
     xf = roi_transform(centers, scales, O)

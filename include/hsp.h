@@ -709,6 +709,42 @@ int hsp_frame_to_pcl_f32(const float *depth, int H, int W, const double *camK, i
 int hsp_frame_to_pcl_u16(const uint16_t *depth, int H, int W, const double *camK, int camK_rows, const int32_t *src,
                          long long src_stride, const int32_t *choose, int n, int S, float *pc, hspStream_t stream);
 
+/* ---- the rows each instance keeps, drawn on the device ----------------------------------------------
+ * The opt-in counterpart of the host draws the three front ends above are fed by default (np.random.permutation /
+ * np.random.choice on numpy's global generator, the reference's generator consumption): the same DISTRIBUTION from a keyed,
+ * counter-based generator, not the same draws.  One launch, integer arithmetic only, no workspace, no atomics; the
+ * back-projection entry points above consume its choose as they consume the host's.
+ *
+ * count: the counts of hsp_pc_compact (count_stride 1) or the pairs of hsp_roi_compact (count_stride 2), on the device.
+ * key: DEVICE pointer to two uint64 {seed, call}; read by the kernel, so a captured launch sees the values of each replay.
+ * choose (n,S) int32, status (n) int32.  n <= 65535, S >= 1, n * S < 2^31, count_stride 1 or 2, short_mode 0 or 1; anything
+ * else is HSP_ERR_BAD_ARG before any launch.
+ *
+ * Per instance j, with c = count[j * count_stride]:
+ *   status[j] = (c < min_pts ? 1 : 0) | (count_stride == 2 && count[j * 2 + 1] < min_depth_pts ? 2 : 0)
+ *   status[j] != 0 or c <= 0:      choose[j,s] = -1 for every s (hsp_frame_to_pcl_* then writes NaN; hsp_pc_gather and
+ *                                  hsp_depth_to_pcl must not be given such a row)
+ *   short_mode 0 and c <= S:       choose[j,s] = s % c          (_sample_points: tiling when short, identity at c == S)
+ *   short_mode 1 and c <  S:       choose[j,s] = (uint64(absorb(absorb(kj, 0xffffffff), s)) * c) >> 32     (with replacement)
+ *   otherwise (c > S; c == S under short_mode 1):   choose[j,s] = P(s), the first S values of a permutation P of [0, c)
+ *
+ * All arithmetic below is on uint32 and wraps modulo 2^32.
+ *   fmix32(h):     h ^= h >> 16;  h *= 0x85ebca6b;  h ^= h >> 13;  h *= 0xc2b2ae35;  h ^= h >> 16       (murmur3's finaliser)
+ *   absorb(h, w) = fmix32((h ^ w) + 0x9e3779b9)
+ *   instance key:  kj = absorb(absorb(absorb(absorb(absorb(0, seed & 0xffffffff), seed >> 32), call & 0xffffffff), call >> 32), j)
+ *   round keys:    k[r] = absorb(kj, r), r = 0..3
+ *   width:         bits = 0 for c <= 1, else the number of bits of c - 1 (smallest with 2^bits >= c);
+ *                  half = max(1, (bits + 1) / 2) (integer division), mask = 2^half - 1: a balanced Feistel network over
+ *                  2 * half <= 32 bits, a domain of less than 4 c values for c >= 2
+ *   one pass E(x): L = x >> half, R = x & mask;  for r = 0, 1, 2, 3 in this order:  t = L ^ (fmix32(R ^ k[r]) & mask), L = R, R = t;
+ *                  E(x) = (L << half) | R
+ *   P(s):          x = E(s);  while x >= c:  x = E(x)      (cycle walking: E is a bijection of [0, 2^(2 half)), so P is one of
+ *                  [0, c) and the walk returns below c)
+ * For c of a few units the 4 rounds reach only some of the c! orders; the sampler is meant for counts of tens to hundreds of
+ * thousands of which about a thousand are kept. */
+int hsp_sample_ids(const int32_t *count, int count_stride, int n, int S, int min_pts, int min_depth_pts, int short_mode,
+                   const unsigned long long *key, int32_t *choose, int32_t *status, hspStream_t stream);
+
 /* ---- pose matrix assembly -----------------------------------------------------------------------
  * replaces generate_RT([p_green,p_red],[f_green,f_red], T, 'vec', sym)     tools/geom_utils.py:232-244
  * (with to_R_matrices / get_vertical_rot_vec_in_batch / get_rot_mat_y_first, tools/rot_utils.py:39-100)

@@ -8,6 +8,12 @@ Device and CPU forms are timed ALTERNATELY in rounds like tools/time_pool_sample
 between device events after a synchronise (the CPU form: wall clock only); the figures are the median over the rounds with the
 min - max spread.  The frame, masks and K are on the device before the clock starts (a frame is uploaded once, whatever n).
 The device kernels are also timed on their own (ops.KernelTimer).  Run on the GPU box:  python tools/time_frame_frontend.py
+
+Beside the host-sampler front end (the default: the counts come to the host, numpy draws) the same rounds time the
+device-sampler one (pc_sample.frame_to_pcl_device: hsp_sample_ids between the two kernels, nothing copied back), and -- frame to
+poses, a network with random weights behind the front end -- frame.FramePipeline in its three forms: host sampler, device
+sampler issued eagerly, device sampler with the whole frame captured as one graph (``pipeline_*_wall_ms``; each call ends by
+reading the per-instance status, or, for the host form, waits for the counts in mid-frame).  ``--no-pipeline`` leaves those out.
 """
 import argparse
 import json
@@ -43,13 +49,28 @@ def main():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--cpu-steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--no-pipeline", action="store_true", help="front end only: skip the frame-to-poses forms")
     ap.add_argument("--out", default=None, help="also write the JSON result to this file")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "time_frame_frontend.py measures the HIP path; it needs a GPU"
     import test_frame_host as fh
     from hs_pose_amd import ops, pc_sample
+    from hs_pose_amd.config import FLAGS
+    from hs_pose_amd.frame import FramePipeline
+    from hs_pose_amd.HSPose import HSPose
 
     dev = torch.device("cuda:0")
+    sampler = pc_sample.DeviceSampler(1, dev)
+    pipes = {}
+    if not args.no_pipeline:
+        FLAGS.reset()
+        FLAGS.train = 0
+        torch.manual_seed(0)
+        net = HSPose("PoseNet_only").to(dev).eval()
+        mean_shapes, sym_infos = torch.full((6, 3), 0.2, device=dev), torch.zeros(6, 4, device=dev)
+        pipes = {"host": FramePipeline(net, mean_shapes, sym_infos, sampler="host"),
+                 "device": FramePipeline(net, mean_shapes, sym_infos, sampler=sampler),
+                 "one_graph": FramePipeline(net, mean_shapes, sym_infos, sampler=sampler, one_graph=True)}
     K = np.array([[591.0125, 0.0, 322.525], [0.0, 590.16775, 244.11084], [0.0, 0.0, 1.0]], dtype=np.float64)
     O, n_pts = 256, 1028
     res = {"H": 480, "W": 640, "O": O, "n_pts": n_pts, "rounds": args.rounds, "steps_per_round": args.steps,
@@ -60,7 +81,16 @@ def main():
 
         def device_form():
             centers, scales = pc_sample.roi_windows(bboxes, 480, 640)
-            return pc_sample.frame_to_pcl(depth_d, masks_d, centers, scales, K, n_pts=n_pts, out_size=O)
+            return pc_sample.frame_to_pcl(depth_d, masks_d, centers, scales, K, n_pts=n_pts, out_size=O, sampler="host")
+
+        def sampler_form():
+            centers, scales = pc_sample.roi_windows(bboxes, 480, 640)
+            return pc_sample.frame_to_pcl_device(depth_d, masks_d, centers, scales, K, n_pts=n_pts, out_size=O, sampler=sampler)
+
+        cls = np.arange(n) % 6 + 1
+        forms = {"sampler": sampler_form}
+        for name, pipe in pipes.items():
+            forms["pipeline_" + name] = lambda pipe=pipe: pipe(depth_d, masks_d, bboxes, cls, K)
 
         def cpu_form():
             centers, scales = pc_sample.roi_windows(bboxes, 480, 640)
@@ -73,8 +103,18 @@ def main():
         assert a is not None and np.array_equal(a.cpu().numpy(), b), "device and restatement disagree"
         for _ in range(args.warmup):
             device_form()
+            for f in forms.values():
+                assert f() is not None
         dms, dwall, cwall = [], [], []
+        fwall = {name: [] for name in forms}
         for _ in range(args.rounds):
+            for name, f in forms.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(args.steps):
+                    f()
+                torch.cuda.synchronize()
+                fwall[name].append(1e3 * (time.perf_counter() - t0) / args.steps)
             torch.cuda.synchronize()
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             t0 = time.perf_counter()
@@ -89,11 +129,12 @@ def main():
             for _ in range(args.cpu_steps):
                 cpu_form()
             cwall.append(1e3 * (time.perf_counter() - t0) / args.cpu_steps)
-        timer = ops.KernelTimer(only=("hsp_roi_compact_u16", "hsp_frame_to_pcl_u16"))
+        timer = ops.KernelTimer(only=("hsp_roi_compact_u16", "hsp_frame_to_pcl_u16", "hsp_sample_ids"))
         prev = ops.set_timer(timer)
         try:
             for _ in range(args.steps):
                 device_form()
+                sampler_form()
             torch.cuda.synchronize()
         finally:
             ops.set_timer(prev)
@@ -102,6 +143,8 @@ def main():
             return {"median": round(statistics.median(v), 4), "min": round(min(v), 4), "max": round(max(v), 4)}
         res[f"n{n}"] = {"device_stream_ms": stat(dms), "device_wall_ms": stat(dwall), "cpu_restatement_wall_ms": stat(cwall),
                         "kernels_us": {name: round(d["avg_us"], 2) for (name, _), d in timer.summary().items()}}
+        for name, v in fwall.items():
+            res[f"n{n}"][("device_sampler" if name == "sampler" else name) + "_wall_ms"] = stat(v)
     line = json.dumps(res)
     print(line)
     if args.out:
