@@ -141,6 +141,13 @@ SIGNATURES = {
     "hsp_frame_to_pcl_f32": (_i, [_vp, _i, _i, _vp, _i, _vp, ctypes.c_longlong, _vp, _i, _i, _vp, _vp]),
     "hsp_frame_to_pcl_u16": (_i, [_vp, _i, _i, _vp, _i, _vp, ctypes.c_longlong, _vp, _i, _i, _vp, _vp]),
     "hsp_sample_ids": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "hsp_roi_defor_workspace_bytes": (_sz, [_i, _i]),
+    "hsp_roi_defor": (_i, [_vp, ctypes.c_longlong, _vp, _vp, _i, _i, _i, _i, _i, ctypes.c_ulonglong, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "hsp_crop_compact_workspace_bytes": (_sz, [_i, _i]),
+    "hsp_crop_compact_f32": (_i, [_vp, ctypes.c_longlong, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "hsp_crop_compact_u16": (_i, [_vp, ctypes.c_longlong, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "hsp_frames_to_pcl_f32": (_i, [_vp, ctypes.c_longlong, _i, _i, _vp, _i, _vp, ctypes.c_longlong, _vp, _i, _i, _vp, _vp]),
+    "hsp_frames_to_pcl_u16": (_i, [_vp, ctypes.c_longlong, _i, _i, _vp, _i, _vp, ctypes.c_longlong, _vp, _i, _i, _vp, _vp]),
     "hsp_generate_rt": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
     "hsp_sumsq_workspace_bytes": (_sz, [ctypes.c_longlong]),
     "hsp_sumsq_f32": (_i, [_vp, ctypes.c_longlong, _vp, _vp, _sz, _vp]),

@@ -23,6 +23,10 @@ class _Flags:
         sample_method='basic',  # config.py:44
         train=1,              # config.py:48
         batch_size=16,        # config.py:55
+        DZI_PAD_SCALE=1.5, DZI_TYPE='uniform', DZI_SCALE_RATIO=0.25, DZI_SHIFT_RATIO=0.25,   # config.py:13-16  the crop window's draws
+        roi_mask_pro=0.5,     # config.py:23  share of the items whose cropped mask defor_2D perturbs
+        roi_mask_r=3,         # config.py:22  defor_2D's iteration count -- which the reference's call never applies: it lands in
+                              # cv2.erode's dst argument and ONE iteration runs (pc_sample.train_batch_to_pcl: mask_iters=1)
         aug_pc_pro=0.2, aug_pc_r=0.2, aug_rt_pro=0.3, aug_bb_pro=0.3, aug_bc_pro=0.3,   # config.py:24-28
         fsnet_loss_type='l1',                                                          # config.py:64
         rot_1_w=8.0, rot_2_w=8.0, rot_regular=4.0, tran_w=8.0, size_w=8.0, recon_w=8.0, r_con_w=1.0,   # config.py:66-72

@@ -13,6 +13,8 @@
 //    the valid ones; stage 2 back-projects the chosen ones straight from the frame.
 //  * the chosen rows themselves, optionally: a keyed counter-based draw on the device between the two stages (hsp_sample_ids)
 //    in place of the host's, so that neither front end has to bring its counts to the host.
+//  * a training batch -> instance clouds: the same chain for B frames with one instance each and the loader's defor_2D on the
+//    cropped mask in between (datasets/load_data.py:234-278): hsp_roi_defor, hsp_crop_compact, hsp_frames_to_pcl.
 //  * (R|t) assembly: replaces generate_RT(..., mode='vec') (tools/geom_utils.py:232-244 with
 //    tools/rot_utils.py:39-100): confidence-weighted orthogonalisation of the two predicted axes and
 //    the 4x4 pose matrix, one lane per object instead of ~40 tiny launches.
@@ -296,6 +298,34 @@ __device__ __forceinline__ uint32_t fmix32(uint32_t h) {
 
 __device__ __forceinline__ uint32_t absorb(uint32_t h, uint32_t w) { return fmix32((h ^ w) + 0x9e3779b9u); }
 
+// kj of instance j under the key {seed, call}
+__device__ __forceinline__ uint32_t instance_key(const unsigned long long* __restrict__ key, int j) {
+    const unsigned long long seed = key[0], call = key[1];
+    uint32_t kj = absorb(0u, (uint32_t)seed);
+    kj = absorb(kj, (uint32_t)(seed >> 32));
+    kj = absorb(kj, (uint32_t)call);
+    kj = absorb(kj, (uint32_t)(call >> 32));
+    return absorb(kj, (uint32_t)j);
+}
+
+// P(s) for s < c, c >= 1: the cycle-walked 4-round Feistel permutation of [0, c) with round keys absorb(k, 0..3)
+__device__ __forceinline__ uint32_t feistel_permute(uint32_t s, uint32_t c, uint32_t k) {
+    const uint32_t k0 = absorb(k, 0u), k1 = absorb(k, 1u), k2 = absorb(k, 2u), k3 = absorb(k, 3u);
+    const int bits = c <= 1u ? 0 : 32 - __clz((int)(c - 1u));
+    const int half = max(1, (bits + 1) / 2);
+    const uint32_t mask = (1u << half) - 1u;
+    uint32_t x = s;
+    do {
+        uint32_t L = x >> half, R = x & mask, t;
+        t = L ^ (fmix32(R ^ k0) & mask); L = R; R = t;
+        t = L ^ (fmix32(R ^ k1) & mask); L = R; R = t;
+        t = L ^ (fmix32(R ^ k2) & mask); L = R; R = t;
+        t = L ^ (fmix32(R ^ k3) & mask); L = R; R = t;
+        x = (L << half) | R;
+    } while (x >= c);
+    return x;
+}
+
 __global__ __launch_bounds__(256) void sample_ids_kernel(const int32_t* __restrict__ count, int stride, int n, int S,
                                                          int min_pts, int min_depth_pts, int short_mode,
                                                          const unsigned long long* __restrict__ key,
@@ -314,32 +344,301 @@ __global__ __launch_bounds__(256) void sample_ids_kernel(const int32_t* __restri
     } else if (short_mode == 0 && c <= S) {
         out = s % c;
     } else {
-        const unsigned long long seed = key[0], call = key[1];
-        uint32_t kj = absorb(0u, (uint32_t)seed);
-        kj = absorb(kj, (uint32_t)(seed >> 32));
-        kj = absorb(kj, (uint32_t)call);
-        kj = absorb(kj, (uint32_t)(call >> 32));
-        kj = absorb(kj, (uint32_t)j);
-        if (c < S) {
+        const uint32_t kj = instance_key(key, j);
+        if (c < S)
             out = (int)(((unsigned long long)absorb(absorb(kj, 0xffffffffu), (uint32_t)s) * (unsigned long long)c) >> 32);
-        } else {
-            const uint32_t k0 = absorb(kj, 0u), k1 = absorb(kj, 1u), k2 = absorb(kj, 2u), k3 = absorb(kj, 3u);
-            const int bits = c <= 1 ? 0 : 32 - __clz(c - 1);
-            const int half = max(1, (bits + 1) / 2);
-            const uint32_t mask = (1u << half) - 1u;
-            uint32_t x = (uint32_t)s;
-            do {
-                uint32_t L = x >> half, R = x & mask, t;
-                t = L ^ (fmix32(R ^ k0) & mask); L = R; R = t;
-                t = L ^ (fmix32(R ^ k1) & mask); L = R; R = t;
-                t = L ^ (fmix32(R ^ k2) & mask); L = R; R = t;
-                t = L ^ (fmix32(R ^ k3) & mask); L = R; R = t;
-                x = (L << half) | R;
-            } while (x >= (uint32_t)c);
-            out = (int)x;
-        }
+        else
+            out = (int)feistel_permute((uint32_t)s, (uint32_t)c, kj);
     }
     choose[e] = out;
+}
+
+// ---- the training loader's chain (datasets/load_data.py:228-278): a batch of frames, the mask perturbed before the cut ------
+// include/hsp.h ("the training loader's front end") states the mask rule.  hsp_roi_defor writes the crop-space masks, before
+// and after defor_2D, as one byte per crop pixel; hsp_crop_compact is the compaction above reading that byte in place of the
+// frame's mask, hsp_frames_to_pcl the back-projection above with a frame per instance.  Both two-launch kernels keep the
+// shape of roi_count_kernel / roi_write_kernel: 16 consecutive crop pixels per thread, per-chunk counts in the workspace.
+
+// 16 consecutive bytes of a row of (n, O*O) uint8 as four words, byte i in bits 8 * (i & 3) of word i >> 2: one 16-byte access
+// where the address allows it and all 16 lie inside the row, single bytes (inside the row only) otherwise
+__device__ __forceinline__ void load16(const uint8_t* __restrict__ p, int left, uint32_t w[4]) {
+    if (left >= 16 && (reinterpret_cast<uintptr_t>(p) & 15) == 0) {
+        const uint4 t = *reinterpret_cast<const uint4*>(p);
+        w[0] = t.x; w[1] = t.y; w[2] = t.z; w[3] = t.w;
+        return;
+    }
+    w[0] = w[1] = w[2] = w[3] = 0u;
+#pragma unroll
+    for (int i = 0; i < 16; ++i)
+        if (i < left) w[i >> 2] |= (uint32_t)p[i] << (8 * (i & 3));
+}
+
+__device__ __forceinline__ void store16(uint8_t* __restrict__ p, int left, const uint32_t w[4]) {
+    if (left >= 16 && (reinterpret_cast<uintptr_t>(p) & 15) == 0) {
+        *reinterpret_cast<uint4*>(p) = make_uint4(w[0], w[1], w[2], w[3]);
+        return;
+    }
+#pragma unroll
+    for (int i = 0; i < 16; ++i)
+        if (i < left) p[i] = (uint8_t)(w[i >> 2] >> (8 * (i & 3)));
+}
+
+// the 16 consecutive crop pixels of one thread: bit i of mbits = m, of bbits = on the band (E != D over the triangle i + j <= r
+// up and to the left, positions outside the crop left out).  Every footprint pixel is walked through the map again: at most
+// (r + 1)(r + 2) / 2 mask reads per pixel (3 at r = 1), neighbours' reads meet in the cache.
+__device__ __forceinline__ void defor_scan16(const uint8_t* __restrict__ mask, const int32_t* __restrict__ inst_id,
+                                             const double* __restrict__ xf, int j, int lo, int OO, int O, int H, int W, int r,
+                                             unsigned& mbits, unsigned& bbits) {
+    const double m0 = xf[(size_t)j * 3];
+    const long long bx = roi_fix(xf[(size_t)j * 3 + 1]) + 512, by = roi_fix(xf[(size_t)j * 3 + 2]) + 512;
+    const int want = inst_id ? inst_id[j] : 0;
+    mbits = 0;
+    bbits = 0;
+    int v = lo / O, u = lo - v * O;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        if (lo + i < OO) {
+            unsigned e = 1u, d = 0u;
+            const int rb = min(r, v);
+            for (int b = 0; b <= rb; ++b) {
+                const long long Y = (by + roi_fix(m0 * (double)(v - b))) >> 10;
+                const bool yin = Y >= 0 && Y < H;
+                const int ra = min(r - b, u);
+                for (int a = 0; a <= ra; ++a) {
+                    const long long X = (bx + roi_fix(m0 * (double)(u - a))) >> 10;
+                    unsigned val = 0u;
+                    if (yin && X >= 0 && X < W) {
+                        const int m = mask[(size_t)Y * W + (size_t)X];
+                        val = (inst_id ? m == want : m != 0) ? 1u : 0u;
+                    }
+                    e &= val;
+                    d |= val;
+                    if ((a | b) == 0) mbits |= val << i;
+                }
+            }
+            bbits |= (e ^ d) << i;
+            if (++u == O) {
+                u = 0;
+                ++v;
+            }
+        }
+    }
+}
+
+//   defor_count_kernel  cnt[j][chunk] = band pixels of the chunk
+//   defor_write_kernel  l = all chunks' counts, rank = earlier chunks' counts + scan inside the chunk; the gate, the subset, the
+//                       bytes; the last chunk's workgroup writes band[j]
+__global__ __launch_bounds__(256) void defor_count_kernel(const uint8_t* __restrict__ mask, long long mask_stride,
+                                                          const int32_t* __restrict__ inst_id, const double* __restrict__ xf,
+                                                          int H, int W, int O, int nchunk, int r, int32_t* __restrict__ cnt) {
+    __shared__ int wsum[4];
+    const int j = blockIdx.y, chunk = blockIdx.x, tid = threadIdx.x;
+    unsigned mbits, bbits;
+    defor_scan16(mask + (size_t)j * mask_stride, inst_id, xf, j, chunk * PC_CHUNK + tid * 16, O * O, O, H, W, r, mbits, bbits);
+    int c = __popc(bbits);
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) c += __shfl_xor(c, m);
+    if ((tid & 63) == 0) wsum[tid >> 6] = c;
+    __syncthreads();
+    if (tid == 0) cnt[(size_t)j * nchunk + chunk] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+}
+
+__global__ __launch_bounds__(256) void defor_write_kernel(const uint8_t* __restrict__ mask, long long mask_stride,
+                                                          const int32_t* __restrict__ inst_id, const double* __restrict__ xf,
+                                                          int H, int W, int O, int nchunk, int r, unsigned long long gate,
+                                                          const unsigned long long* __restrict__ key,
+                                                          const int32_t* __restrict__ cnt, uint8_t* __restrict__ crop_mask,
+                                                          int32_t* __restrict__ band) {
+    __shared__ int red[4][2];
+    __shared__ int wpre[4];
+    const int j = blockIdx.y, chunk = blockIdx.x, tid = threadIdx.x;
+    const int lane = tid & 63, wv = tid >> 6;
+    const int OO = O * O;
+    int part = 0, tot = 0;                                   // band pixels of the earlier chunks, and of all of them
+    for (int c = tid; c < nchunk; c += 256) {
+        const int v = cnt[(size_t)j * nchunk + c];
+        tot += v;
+        if (c < chunk) part += v;
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        part += __shfl_xor(part, m);
+        tot += __shfl_xor(tot, m);
+    }
+    if (lane == 0) {
+        red[wv][0] = part;
+        red[wv][1] = tot;
+    }
+    const int lo = chunk * PC_CHUNK + tid * 16;
+    unsigned mbits, bbits;
+    defor_scan16(mask + (size_t)j * mask_stride, inst_id, xf, j, lo, OO, O, H, W, r, mbits, bbits);
+    const int c = __popc(bbits);
+    int incl = c;                                            // inclusive scan inside the wave
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const int v = __shfl_up(incl, d);
+        if (lane >= d) incl += v;
+    }
+    if (lane == 63) wpre[wv] = incl;
+    __syncthreads();
+    const int base = (red[0][0] + red[1][0]) + (red[2][0] + red[3][0]);
+    const int l = (red[0][1] + red[1][1]) + (red[2][1] + red[3][1]);
+    int woff = 0;
+    for (int w = 0; w < wv; ++w) woff += wpre[w];
+    const uint32_t kj = instance_key(key, j);
+    const bool deformed = l >= 1 && (unsigned long long)absorb(absorb(kj, 0xfffffffeu), 0u) < gate;
+    unsigned one = mbits;                                    // bit 0 of the 16 bytes
+    if (deformed) {
+        const uint32_t kd = absorb(kj, 0xfffffffdu), zeros = (uint32_t)l / 2u;
+        uint32_t t = (uint32_t)(base + woff + incl - c);     // row-major rank of this thread's first band pixel
+        one |= bbits;
+        for (unsigned rest = bbits; rest; rest &= rest - 1u, ++t)
+            if (feistel_permute(t, (uint32_t)l, kd) < zeros) one &= ~(rest & (0u - rest));
+    }
+    uint32_t w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int i = 0; i < 16; ++i) w[i >> 2] |= (((one >> i) & 1u) | (((mbits >> i) & 1u) << 1)) << (8 * (i & 3));
+    store16(crop_mask + (size_t)j * OO + min(lo, OO), OO - min(lo, OO), w);
+    if (chunk == nchunk - 1 && tid == 255) {
+        band[j * 2 + 0] = l;
+        band[j * 2 + 1] = deformed ? 1 : 0;
+    }
+}
+
+// roi_scan16 with the mask bits taken from the crop-space byte: mbits = depth > 0 and bit 0, pbits = depth > 0 and bit 1
+template <typename D>
+__device__ __forceinline__ void crop_scan16(const D* __restrict__ depth, const uint8_t* __restrict__ cmask,
+                                            const double* __restrict__ xf, int j, int lo, int OO, int O, int H, int W,
+                                            int src[16], unsigned& mbits, unsigned& dbits, unsigned& pbits) {
+    const double m0 = xf[(size_t)j * 3];
+    const long long bx = roi_fix(xf[(size_t)j * 3 + 1]) + 512, by = roi_fix(xf[(size_t)j * 3 + 2]) + 512;
+    uint32_t w[4];
+    load16(cmask + min(lo, OO), OO - min(lo, OO), w);
+    mbits = 0;
+    dbits = 0;
+    pbits = 0;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        const int q = lo + i;
+        int p = -1;
+        if (q < OO) p = roi_source(m0, bx, by, q, O, H, W);
+        src[i] = p;
+        if (p >= 0 && depth[p] > (D)0) {
+            const uint32_t c = w[i >> 2] >> (8 * (i & 3));
+            dbits |= 1u << i;
+            mbits |= (c & 1u) << i;
+            pbits |= ((c >> 1) & 1u) << i;
+        }
+    }
+}
+
+//   crop_count_kernel  cnt[j][chunk] = {bit 0 and depth, depth, bit 1 and depth} of the chunk
+//   crop_write_kernel  as roi_write_kernel; the last chunk's workgroup writes the three totals
+template <typename D>
+__global__ __launch_bounds__(256) void crop_count_kernel(const D* __restrict__ depth, long long depth_stride,
+                                                         const uint8_t* __restrict__ crop_mask, const double* __restrict__ xf,
+                                                         int H, int W, int O, int nchunk, int32_t* __restrict__ cnt) {
+    __shared__ int wsum[4][3];
+    const int j = blockIdx.y, chunk = blockIdx.x, tid = threadIdx.x;
+    const int OO = O * O;
+    int src[16];
+    unsigned mbits, dbits, pbits;
+    crop_scan16(depth + (size_t)j * depth_stride, crop_mask + (size_t)j * OO, xf, j, chunk * PC_CHUNK + tid * 16, OO, O, H, W,
+                src, mbits, dbits, pbits);
+    int cm = __popc(mbits), cd = __popc(dbits), cp = __popc(pbits);
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        cm += __shfl_xor(cm, m);
+        cd += __shfl_xor(cd, m);
+        cp += __shfl_xor(cp, m);
+    }
+    if ((tid & 63) == 0) {
+        wsum[tid >> 6][0] = cm;
+        wsum[tid >> 6][1] = cd;
+        wsum[tid >> 6][2] = cp;
+    }
+    __syncthreads();
+    if (tid < 3) cnt[((size_t)j * nchunk + chunk) * 3 + tid] = (wsum[0][tid] + wsum[1][tid]) + (wsum[2][tid] + wsum[3][tid]);
+}
+
+template <typename D>
+__global__ __launch_bounds__(256) void crop_write_kernel(const D* __restrict__ depth, long long depth_stride,
+                                                         const uint8_t* __restrict__ crop_mask, const double* __restrict__ xf,
+                                                         int H, int W, int O, int nchunk, const int32_t* __restrict__ cnt,
+                                                         int32_t* __restrict__ out_src, int32_t* __restrict__ count,
+                                                         int32_t* __restrict__ pre) {
+    __shared__ int red[4][3];
+    __shared__ int wpre[4];
+    const int j = blockIdx.y, chunk = blockIdx.x, tid = threadIdx.x;
+    const int lane = tid & 63, wv = tid >> 6;
+    const int OO = O * O;
+    const bool last = chunk == nchunk - 1;
+    int part = 0, partd = 0, partp = 0;
+    for (int c = tid; c < chunk; c += 256) part += cnt[((size_t)j * nchunk + c) * 3];
+    if (last)
+        for (int c = tid; c < nchunk; c += 256) {
+            partd += cnt[((size_t)j * nchunk + c) * 3 + 1];
+            partp += cnt[((size_t)j * nchunk + c) * 3 + 2];
+        }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        part += __shfl_xor(part, m);
+        partd += __shfl_xor(partd, m);
+        partp += __shfl_xor(partp, m);
+    }
+    if (lane == 0) {
+        red[wv][0] = part;
+        red[wv][1] = partd;
+        red[wv][2] = partp;
+    }
+    int src[16];
+    unsigned mbits, dbits, pbits;
+    crop_scan16(depth + (size_t)j * depth_stride, crop_mask + (size_t)j * OO, xf, j, chunk * PC_CHUNK + tid * 16, OO, O, H, W,
+                src, mbits, dbits, pbits);
+    const int c = __popc(mbits);
+    int incl = c;                                            // inclusive scan inside the wave
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const int v = __shfl_up(incl, d);
+        if (lane >= d) incl += v;
+    }
+    if (lane == 63) wpre[wv] = incl;
+    __syncthreads();
+    const int base = (red[0][0] + red[1][0]) + (red[2][0] + red[3][0]);
+    int woff = 0;
+    for (int w = 0; w < wv; ++w) woff += wpre[w];
+    int off = base + woff + incl - c;
+    int32_t* out = out_src + (size_t)j * OO;
+#pragma unroll
+    for (int i = 0; i < 16; ++i)
+        if ((mbits >> i) & 1u) out[off++] = src[i];
+    if (last && tid == 255) {
+        count[j * 2 + 0] = base + woff + incl;
+        count[j * 2 + 1] = (red[0][1] + red[1][1]) + (red[2][1] + red[3][1]);
+        pre[j] = (red[0][2] + red[1][2]) + (red[2][2] + red[3][2]);
+    }
+}
+
+// frame_to_pcl_kernel with the frame of instance j at depth + j * depth_stride
+template <typename D>
+__global__ __launch_bounds__(256) void frames_to_pcl_kernel(const D* __restrict__ depth, long long depth_stride, int H, int W,
+                                                            const double* __restrict__ camK, int camK_rows,
+                                                            const int32_t* __restrict__ src, long long src_stride,
+                                                            const int32_t* __restrict__ choose, int n, int S,
+                                                            float* __restrict__ pc) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= n * S) return;
+    const int j = e / S;
+    float* o = pc + (size_t)e * 3;
+    const int c = choose[e];
+    const int p = (c >= 0 && c < src_stride) ? src[(size_t)j * src_stride + c] : -1;
+    if (p < 0 || p >= H * W) {
+        o[0] = o[1] = o[2] = __builtin_nanf("");
+        return;
+    }
+    const int v = p / W, u = p - v * W;
+    backproject_f64((double)(float)u, (double)(float)v, (double)depth[(size_t)j * depth_stride + p],
+                    camK + (camK_rows > 1 ? (size_t)j * 9 : 0), o);
 }
 
 __device__ __forceinline__ void rodrigues_apply(const float rx[3], float s, float c, const float v[3], float o[3]) {
@@ -504,6 +803,95 @@ extern "C" int hsp_sample_ids(const int32_t* count, int count_stride, int n, int
     hipLaunchKernelGGL(sample_ids_kernel, dim3((unsigned)(((long long)n * S + 255) / 256)), dim3(256), 0, as_stream(stream), count, count_stride, n,
                        S, min_pts, min_depth_pts, short_mode, key, choose, status);
     return check_launch();
+}
+
+// what the three entry points of the training chain refuse alike: n, O, the frame size and an element stride per instance
+static bool train_shape_ok(int n, int H, int W, int O, long long stride) {
+    if (n <= 0 || n > 65535 || H <= 0 || W <= 0 || O <= 0 || O > 46340) return false;
+    if ((long long)H * W > 2147483647LL) return false;
+    return stride == 0 || stride == (long long)H * W;
+}
+
+extern "C" size_t hsp_roi_defor_workspace_bytes(int n, int O) {
+    if (n <= 0 || O <= 0 || O > 46340) return 0;
+    return (size_t)n * ((O * O + PC_CHUNK - 1) / PC_CHUNK) * sizeof(int32_t);
+}
+
+extern "C" int hsp_roi_defor(const uint8_t* mask, long long mask_stride, const int32_t* inst_id, const double* xf, int n, int H,
+                             int W, int O, int iters, unsigned long long gate, const unsigned long long* key,
+                             uint8_t* crop_mask, int32_t* band, void* ws, size_t ws_bytes, hspStream_t stream) {
+    if (!mask || !xf || !key || !crop_mask || !band || !train_shape_ok(n, H, W, O, mask_stride)) return HSP_ERR_BAD_ARG;
+    if (iters < 1 || iters > 8 || gate > (1ULL << 32)) return HSP_ERR_BAD_ARG;
+    if (!ws || ws_bytes < hsp_roi_defor_workspace_bytes(n, O)) return HSP_ERR_WORKSPACE;
+    const int nchunk = (O * O + PC_CHUNK - 1) / PC_CHUNK;
+    hipStream_t st = as_stream(stream);
+    int32_t* cnt = reinterpret_cast<int32_t*>(ws);
+    hipLaunchKernelGGL(defor_count_kernel, dim3(nchunk, n), dim3(256), 0, st, mask, mask_stride, inst_id, xf, H, W, O, nchunk,
+                       iters, cnt);
+    int rc = check_launch();
+    if (rc) return rc;
+    hipLaunchKernelGGL(defor_write_kernel, dim3(nchunk, n), dim3(256), 0, st, mask, mask_stride, inst_id, xf, H, W, O, nchunk,
+                       iters, gate, key, cnt, crop_mask, band);
+    return check_launch();
+}
+
+extern "C" size_t hsp_crop_compact_workspace_bytes(int n, int O) {
+    if (n <= 0 || O <= 0 || O > 46340) return 0;
+    return (size_t)n * ((O * O + PC_CHUNK - 1) / PC_CHUNK) * 3 * sizeof(int32_t);
+}
+
+template <typename D>
+static int crop_compact(const D* depth, long long depth_stride, const uint8_t* crop_mask, const double* xf, int n, int H, int W,
+                        int O, int32_t* src, int32_t* count, int32_t* pre, void* ws, size_t ws_bytes, hspStream_t stream) {
+    if (!depth || !crop_mask || !xf || !src || !count || !pre || !train_shape_ok(n, H, W, O, depth_stride))
+        return HSP_ERR_BAD_ARG;
+    if (!ws || ws_bytes < hsp_crop_compact_workspace_bytes(n, O)) return HSP_ERR_WORKSPACE;
+    const int nchunk = (O * O + PC_CHUNK - 1) / PC_CHUNK;
+    hipStream_t st = as_stream(stream);
+    int32_t* cnt = reinterpret_cast<int32_t*>(ws);
+    hipLaunchKernelGGL(crop_count_kernel<D>, dim3(nchunk, n), dim3(256), 0, st, depth, depth_stride, crop_mask, xf, H, W, O,
+                       nchunk, cnt);
+    int rc = check_launch();
+    if (rc) return rc;
+    hipLaunchKernelGGL(crop_write_kernel<D>, dim3(nchunk, n), dim3(256), 0, st, depth, depth_stride, crop_mask, xf, H, W, O,
+                       nchunk, cnt, src, count, pre);
+    return check_launch();
+}
+
+extern "C" int hsp_crop_compact_f32(const float* depth, long long depth_stride, const uint8_t* crop_mask, const double* xf,
+                                    int n, int H, int W, int O, int32_t* src, int32_t* count, int32_t* pre, void* ws,
+                                    size_t ws_bytes, hspStream_t stream) {
+    return crop_compact(depth, depth_stride, crop_mask, xf, n, H, W, O, src, count, pre, ws, ws_bytes, stream);
+}
+
+extern "C" int hsp_crop_compact_u16(const uint16_t* depth, long long depth_stride, const uint8_t* crop_mask, const double* xf,
+                                    int n, int H, int W, int O, int32_t* src, int32_t* count, int32_t* pre, void* ws,
+                                    size_t ws_bytes, hspStream_t stream) {
+    return crop_compact(depth, depth_stride, crop_mask, xf, n, H, W, O, src, count, pre, ws, ws_bytes, stream);
+}
+
+template <typename D>
+static int frames_to_pcl(const D* depth, long long depth_stride, int H, int W, const double* camK, int camK_rows,
+                         const int32_t* src, long long src_stride, const int32_t* choose, int n, int S, float* pc,
+                         hspStream_t stream) {
+    if (!depth || !camK || !src || !choose || !pc || S <= 0 || src_stride <= 0 || !train_shape_ok(n, H, W, 1, depth_stride))
+        return HSP_ERR_BAD_ARG;
+    if ((camK_rows != 1 && camK_rows != n) || (long long)n * S > 2147483647LL) return HSP_ERR_BAD_ARG;
+    hipLaunchKernelGGL(frames_to_pcl_kernel<D>, dim3((n * S + 255) / 256), dim3(256), 0, as_stream(stream), depth, depth_stride,
+                       H, W, camK, camK_rows, src, src_stride, choose, n, S, pc);
+    return check_launch();
+}
+
+extern "C" int hsp_frames_to_pcl_f32(const float* depth, long long depth_stride, int H, int W, const double* camK,
+                                     int camK_rows, const int32_t* src, long long src_stride, const int32_t* choose, int n, int S,
+                                     float* pc, hspStream_t stream) {
+    return frames_to_pcl(depth, depth_stride, H, W, camK, camK_rows, src, src_stride, choose, n, S, pc, stream);
+}
+
+extern "C" int hsp_frames_to_pcl_u16(const uint16_t* depth, long long depth_stride, int H, int W, const double* camK,
+                                     int camK_rows, const int32_t* src, long long src_stride, const int32_t* choose, int n,
+                                     int S, float* pc, hspStream_t stream) {
+    return frames_to_pcl(depth, depth_stride, H, W, camK, camK_rows, src, src_stride, choose, n, S, pc, stream);
 }
 
 extern "C" int hsp_generate_rt(const float* p_green, const float* p_red, const float* f_green, const float* f_red,

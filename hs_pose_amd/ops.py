@@ -2714,3 +2714,95 @@ def frame_to_pcl(depth, camK64, src, choose):
          (_p(depth), H, W, _p(camK64), camK64.numel() // 9, _p(src), src.shape[1], _p(choose), n, S, _p(pc), _stream()),
          key=f"n{n}S{S}", abytes=n * S * (8 + depth.element_size() + 12))
     return pc
+
+
+def _req_frames_depth(depth, n, name):
+    """one (H,W) frame for all n instances or a frame each, (n,H,W)"""
+    if not isinstance(depth, torch.Tensor) or not depth.is_cuda:
+        raise HspError(f"{name}: expected a GPU tensor (hs_pose_amd has no CPU path), got "
+                       f"{getattr(depth, 'device', type(depth))}")
+    if depth.dtype not in _FRAME_DEPTH or depth.dim() not in (2, 3) or depth.numel() == 0 \
+            or depth.shape[-2] * depth.shape[-1] >= 2 ** 31 or (depth.dim() == 3 and depth.shape[0] != n):
+        raise HspError(f"{name}: expected an (H,W) or ({n},H,W) float32 or uint16 depth with H*W < 2^31, got "
+                       f"{tuple(depth.shape)} {depth.dtype}")
+    return depth.detach() if depth.is_contiguous() else depth.detach().contiguous()
+
+
+def roi_defor(mask, xf, out_size, key, inst_ids=None, iters=1, gate=0):
+    """the cropped masks of a training batch before and after ``defor_2D`` (include/hsp.h: the mask rule): mask uint8 (n,H,W)
+    -- a mask per instance, or with inst_ids a label image per instance -- or (H,W) (one label image for all), xf (n,3) float64,
+    key (2,) int64 on the device (the sampler's), iters 1..8, gate 0..2^32 -> (crop_mask (n, O*O) uint8: bit 0 the deformed
+    mask, bit 1 the mask before; band (n,2) int32 = [band pixels, deformed])."""
+    mask = _req(mask.detach() if isinstance(mask, torch.Tensor) else mask, torch.uint8, "roi_defor.mask")
+    xf = _req(xf, torch.float64, "roi_defor.xf")
+    key = _req(key, torch.int64, "roi_defor.key")
+    O, iters, gate = int(out_size), int(iters), int(gate)
+    if xf.dim() != 2 or xf.shape[1] != 3 or xf.shape[0] == 0 or key.numel() != 2:
+        raise HspError("roi_defor: expects xf (n,3) float64 with n >= 1 and key (2,)")
+    n = xf.shape[0]
+    if mask.dim() not in (2, 3) or (mask.dim() == 3 and mask.shape[0] != n) or mask.numel() == 0:
+        raise HspError(f"roi_defor: expects mask ({n},H,W) or (H,W), got {tuple(mask.shape)}")
+    H, W = mask.shape[-2:]
+    if not 0 < O <= 46340 or n > 65535 or H * W >= 2 ** 31 or not 1 <= iters <= 8 or not 0 <= gate <= 2 ** 32:
+        raise HspError(f"roi_defor: out_size {O} / n {n} / frame {H}x{W} / iters {iters} / gate {gate} out of range (0 < out_size <= "
+                       "46340, n <= 65535, H*W < 2^31, 1 <= iters <= 8, 0 <= gate <= 2^32)")
+    if inst_ids is not None:
+        inst_ids = _req(inst_ids, torch.int32, "roi_defor.inst_ids")
+        if inst_ids.shape != (n,):
+            raise HspError(f"roi_defor: expects inst_ids ({n},), got {tuple(inst_ids.shape)}")
+    crop_mask = torch.empty(n, O * O, dtype=torch.uint8, device=mask.device)
+    band = torch.empty(n, 2, dtype=torch.int32, device=mask.device)
+    wsb = lib().hsp_roi_defor_workspace_bytes(n, O)
+    ws = _ws(wsb, mask.device)
+    _run("hsp_roi_defor", (_p(mask), H * W if mask.dim() == 3 else 0, _p(inst_ids), _p(xf), n, H, W, O, iters, gate, _p(key),
+                           _p(crop_mask), _p(band), _p(ws), wsb, _stream()),
+         key=f"n{n}O{O}r{iters}", abytes=n * O * O * 2)
+    return crop_mask, band
+
+
+def crop_compact(depth, crop_mask, xf, out_size):
+    """``roi_compact`` with the mask taken from roi_defor's bytes and a frame per instance: depth (H,W) or (n,H,W) fp32 or
+    uint16, crop_mask (n, O*O) uint8, xf (n,3) float64 -> (src (n, O*O) int32, ids into the instance's own frame; count (n,2)
+    int32 = [bit-0-and-depth valid, depth valid]; pre (n,) int32 = bit-1-and-depth valid, the count before the deformation)."""
+    xf = _req(xf, torch.float64, "crop_compact.xf")
+    if xf.dim() != 2 or xf.shape[1] != 3 or xf.shape[0] == 0:
+        raise HspError("crop_compact: expects xf (n,3) float64 with n >= 1")
+    n, O = xf.shape[0], int(out_size)
+    depth = _req_frames_depth(depth, n, "crop_compact.depth")
+    crop_mask = _req(crop_mask, torch.uint8, "crop_compact.crop_mask")
+    H, W = depth.shape[-2:]
+    if not 0 < O <= 46340 or n > 65535:
+        raise HspError(f"crop_compact: out_size {O} / n {n} out of range (0 < out_size <= 46340, n <= 65535)")
+    if tuple(crop_mask.shape) != (n, O * O):
+        raise HspError(f"crop_compact: expects crop_mask ({n},{O * O}), got {tuple(crop_mask.shape)}")
+    src = torch.empty(n, O * O, dtype=torch.int32, device=depth.device)
+    count = torch.empty(n, 2, dtype=torch.int32, device=depth.device)
+    pre = torch.empty(n, dtype=torch.int32, device=depth.device)
+    wsb = lib().hsp_crop_compact_workspace_bytes(n, O)
+    ws = _ws(wsb, depth.device)
+    _run("hsp_crop_compact" + _FRAME_DEPTH[depth.dtype],
+         (_p(depth), H * W if depth.dim() == 3 else 0, _p(crop_mask), _p(xf), n, H, W, O, _p(src), _p(count), _p(pre), _p(ws),
+          wsb, _stream()),
+         key=f"n{n}O{O}", abytes=n * O * O * (depth.element_size() + 1 + 4))
+    return src, count, pre
+
+
+def frames_to_pcl(depth, camK64, src, choose):
+    """``frame_to_pcl`` with a frame per instance: depth (H,W) or (n,H,W) fp32 or uint16, camK (1|n,3,3) float64, src (n,L)
+    int32 from crop_compact, choose (n,S) int32 -> (n,S,3) fp32 metres; NaN rows where choose is -1."""
+    src = _req(src, torch.int32, "frames_to_pcl.src")
+    choose = _req(choose, torch.int32, "frames_to_pcl.choose")
+    camK64 = _req(camK64.detach() if isinstance(camK64, torch.Tensor) else camK64, torch.float64, "frames_to_pcl.camK")
+    if src.dim() != 2 or choose.dim() != 2 or src.shape[0] != choose.shape[0] or src.shape[0] == 0 or choose.shape[1] == 0 \
+            or src.shape[0] > 65535 or camK64.numel() not in (9, 9 * src.shape[0]):
+        raise HspError("frames_to_pcl: expects depth (H,W) or (n,H,W), camK (1|n,3,3) f64, src (n,L), choose (n,S) with "
+                       "1 <= n <= 65535, S >= 1")
+    n, S = choose.shape
+    depth = _req_frames_depth(depth, n, "frames_to_pcl.depth")
+    H, W = depth.shape[-2:]
+    pc = torch.empty(n, S, 3, dtype=torch.float32, device=depth.device)
+    _run("hsp_frames_to_pcl" + _FRAME_DEPTH[depth.dtype],
+         (_p(depth), H * W if depth.dim() == 3 else 0, H, W, _p(camK64), camK64.numel() // 9, _p(src), src.shape[1], _p(choose),
+          n, S, _p(pc), _stream()),
+         key=f"n{n}S{S}", abytes=n * S * (8 + depth.element_size() + 12))
+    return pc

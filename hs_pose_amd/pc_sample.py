@@ -20,6 +20,11 @@ the above, draw for draw.  ``'device'`` -- or a ``DeviceSampler`` of one's own -
 tiling or a uniform draw with replacement when short), not the same draws; the counts stay on the device, nothing is copied
 back and nothing waits until the caller reads the result, and numpy's generator is never touched.  ``frame_to_pcl_device`` is
 that form bare: clouds and per-instance status, both on the device.
+
+``dzi_windows`` + ``train_batch_to_pcl`` are the training loader's chain (datasets/load_data.py:228-278) for a batch of items,
+each with its own frame: ``aug_bbox_DZI``'s windows on the host, draw for draw, then the crops, ``defor_2D``'s perturbation of
+the cropped mask, the three rejection tests, the cloud and its rows on the device (``hsp_roi_defor`` / ``hsp_crop_compact`` /
+``hsp_sample_ids`` / ``hsp_frames_to_pcl``), under a device sampler only.
 """
 import numpy as np
 import torch
@@ -289,3 +294,95 @@ def frame_to_pcl(depth, masks, centers, scales, K, n_pts=None, out_size=None, in
         choose[j] = sample_point_ids(int(counts[j, 0]), n_pts)
     choose_d = torch.from_numpy(choose).to(dev, non_blocking=True)
     return ops.frame_to_pcl(depth, K64.contiguous(), src, choose_d)
+
+
+def dzi_windows(bboxes_xyxy, im_H, im_W):
+    """The crop windows of a training batch: ``aug_bbox_DZI`` (tools/dataset_utils.py:24-61) of every row of bboxes_xyxy (B,4)
+    = (x1, y1, x2, y2) -> (centers (B,2) float64 = (cx, cy), scales (B,) float64).  With ``FLAGS.DZI_TYPE`` 'uniform' the
+    reference's draws on numpy's global generator in its order -- per box one ``random_sample()``, then ``random_sample(2)`` --
+    and its arithmetic, operation for operation; 'roi10d' and 'truncnorm' are not built; any other type gives the undrawn
+    centre and side (the reference's ``else`` branch)."""
+    kind = str(FLAGS.DZI_TYPE).lower()
+    if kind in ("roi10d", "truncnorm"):
+        raise NotImplementedError(f"dzi_windows: DZI_TYPE {FLAGS.DZI_TYPE!r} is not built ('uniform', or any other name for no draw)")
+    boxes = np.asarray(bboxes_xyxy)
+    if boxes.ndim != 2 or boxes.shape[1] != 4:
+        raise ValueError(f"dzi_windows: expects boxes (B,4) = (x1, y1, x2, y2), got {boxes.shape}")
+    centers, scales = np.zeros((len(boxes), 2), np.float64), np.zeros(len(boxes), np.float64)
+    for k, (x1, y1, x2, y2) in enumerate(boxes):
+        cx = 0.5 * (x1 + x2)
+        cy = 0.5 * (y1 + y2)
+        bh = y2 - y1
+        bw = x2 - x1
+        if kind == "uniform":
+            scale_ratio = 1 + FLAGS.DZI_SCALE_RATIO * (2 * np.random.random_sample() - 1)
+            shift_ratio = FLAGS.DZI_SHIFT_RATIO * (2 * np.random.random_sample(2) - 1)
+            centers[k] = cx + bw * shift_ratio[0], cy + bh * shift_ratio[1]
+            scale = max(y2 - y1, x2 - x1) * scale_ratio * FLAGS.DZI_PAD_SCALE
+        else:
+            centers[k] = cx, cy
+            scale = max(y2 - y1, x2 - x1)
+        scales[k] = min(scale, max(im_H, im_W)) * 1.0
+    return centers, scales
+
+
+def mask_gate(pro):
+    """``defor_2D``'s ``rand_pro`` as the integer the kernel compares a 32-bit draw with (include/hsp.h: the mask rule):
+    floor(pro * 2^32) clipped to [0, 2^32] -- 0 never deforms, 2^32 always does"""
+    return int(min(max(np.floor(float(pro) * 4294967296.0), 0.0), 4294967296.0))
+
+
+def train_batch_to_pcl(depth, labels, inst_ids, centers, scales, K, n_pts=None, out_size=None, min_pts=50, mask_pro=None,
+                       mask_iters=1, sampler=None):
+    """The training loader's crops, mask perturbation and clouds for a batch of items (datasets/load_data.py:234-278 behind
+    ``aug_bbox_DZI``), all on the device: ``hsp_roi_defor`` -> ``hsp_crop_compact`` -> ``hsp_sample_ids`` ->
+    ``hsp_frames_to_pcl``, a linear chain with no device->host copy and no wait.
+
+    depth (B,H,W) -- a frame per item -- or (H,W), fp32 or uint16 mm on the device; labels uint8/bool on the device: (B,H,W) or
+    (H,W) label images with inst_ids (B,), or with inst_ids None one mask per item (B,H,W); centers (B,2) / scales (B,) on the
+    host (``dzi_windows``); K (3,3) or (B,3,3) -> (PC (B, n_pts, 3) fp32 metres, status (B,) int32), both on the device.
+    status: ``hsp_sample_ids``'s bits -- 1: fewer than min_pts crop pixels with depth under the DEFORMED mask (:276), 2: <= 1
+    with depth (:254) -- plus 4: <= 1 with depth under the mask BEFORE the deformation (:257).  The rows of an item whose
+    status is not 0 are NaN: the loader skips such an item.  mask_pro defaults to FLAGS.roi_mask_pro, n_pts to
+    FLAGS.random_points, out_size to FLAGS.img_size; mask_iters is the rule's r, and 1 is what the reference's call runs
+    whatever FLAGS.roi_mask_r says.
+
+    The draws -- who is deformed, which band pixels go, which rows are kept -- are the device sampler's (None: the module's),
+    one ``advance()`` per call: the reference's distributions, not its draws; numpy's generator is never touched.  There is no
+    host-draw form: the reference interleaves the window, mask and row draws item by item.
+
+    Inside ``torch.cuda.graph`` the call uploads nothing: give it inst_ids (B,) int32, the transform rows
+    ``roi_transform(centers, scales, out_size)`` (B,3) float64 in place of centers with scales None, and K float64 as device
+    tensors made before the capture; the sampler is not advanced by the captured call -- ``sampler.advance()`` before each replay,
+    as ``frame._FrameGraph`` does."""
+    n_pts = int(FLAGS.random_points if n_pts is None else n_pts)
+    O = int(FLAGS.img_size if out_size is None else out_size)
+    dev = depth.device
+    sampler = resolve_sampler("device" if sampler is None else sampler, dev)
+    if sampler is None:
+        raise ValueError("train_batch_to_pcl: expects a device sampler; there is no host-draw form of this chain")
+    capturing = dev.type == "cuda" and torch.cuda.is_current_stream_capturing()
+
+    def on_device(a, dtype, what):
+        if isinstance(a, torch.Tensor) and a.is_cuda:
+            return a
+        if capturing:
+            raise ValueError(f"train_batch_to_pcl: inside a graph capture {what} must already be on the device")
+        return _upload(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a), dtype, dev)
+
+    if scales is None:
+        xf = on_device(centers, np.float64, "the transform rows")
+    else:
+        xf = on_device(roi_transform(centers, scales, O), np.float64, "the transform rows (pass them as centers, scales=None)")
+    ids_d = None if inst_ids is None else on_device(inst_ids, np.int32, "inst_ids")
+    K64 = on_device(K, np.float64, "K").to(torch.float64).reshape(-1, 9)
+    if labels.dtype == torch.bool:
+        labels = labels.view(torch.uint8)
+    gate = mask_gate(FLAGS.roi_mask_pro if mask_pro is None else mask_pro)
+    key = sampler.key if capturing else sampler.advance()
+    crop_mask, _ = ops.roi_defor(labels, xf, O, key, ids_d, mask_iters, gate)
+    src, count, pre = ops.crop_compact(depth, crop_mask, xf, O)
+    choose, status = ops.sample_ids(count, n_pts, key, min_pts, 2, 0)
+    early = pre <= 1
+    PC = ops.frames_to_pcl(depth, K64, src, torch.where(early[:, None], -1, choose))
+    return PC, status | (early.to(torch.int32) << 2)

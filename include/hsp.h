@@ -745,6 +745,62 @@ int hsp_frame_to_pcl_u16(const uint16_t *depth, int H, int W, const double *camK
 int hsp_sample_ids(const int32_t *count, int count_stride, int n, int S, int min_pts, int min_depth_pts, int short_mode,
                    const unsigned long long *key, int32_t *choose, int32_t *status, hspStream_t stream);
 
+/* ---- the training loader's front end: a batch of frames, the mask perturbed before the cloud is cut -------
+ * replaces datasets/load_data.py:234-278 behind aug_bbox_DZI: the three nearest-neighbour crops, defor_2D
+ * (datasets/data_augmentation.py:9-32) on the cropped mask, the three rejection tests (:254, :257, :276), _depth_to_pcl and the
+ * gather of _sample_points.  Instance j of the batch has its own window xf[j] (the map and the transform of hsp_roi_compact),
+ * its own mask and, with an element stride of H * W, its own frame; the crops are never built.  Four calls, queued in order:
+ *   hsp_roi_defor -> hsp_crop_compact_* -> hsp_sample_ids(count, 2, ...) -> hsp_frames_to_pcl_*
+ * Plain C++, vector stores, no atomics.  Every call: n <= 65535, O <= 46340, H * W < 2^31, a stride 0 or H * W; anything else
+ * is HSP_ERR_BAD_ARG before any launch.
+ *
+ * THE MASK RULE (the definition; cv2 was never run against it).  m(u, v), u the column and v the row of the O x O crop, is 1
+ * where the frame pixel the map gives for (u, v) carries the instance (mask == inst_id[j], with inst_id NULL mask != 0), and 0
+ * where that pixel lies outside the frame (the warp's constant border).  With r = iters (1..8) and the footprint
+ * T_r = {(i, j) : i, j >= 0, i + j <= r}:
+ *   E(u, v) = AND of m(u - i, v - j) over T_r,   D(u, v) = OR of the same pixels,
+ * both over the positions INSIDE THE CROP only (u - i >= 0, v - j >= 0): a position outside the crop is left out (erode's
+ * +inf and dilate's -inf border), unlike a crop pixel whose source is outside the frame, which is there and reads 0.
+ * band = (E != D); l = the number of band pixels.  T_1 is getStructuringElement(MORPH_ELLIPSE, (2, 2)) = [[0,1],[1,1]] with the
+ * default anchor (1, 1), T_r its r-fold iteration.  The reference passes rand_r in cv2.erode's third positional argument, which
+ * is dst, not iterations: it runs ONE iteration whatever FLAGS.roi_mask_r says, so iters = 1 is the reference's behaviour.
+ * The draws are hsp_sample_ids's: key {seed, call} on the device, kj its instance key of j, absorb and P as defined there.
+ *   gate:    the instance is deformed iff l >= 1 and uint64(absorb(absorb(kj, 0xfffffffe), 0)) < gate, gate in [0, 2^32]
+ *            (= floor(rand_pro * 2^32) clipped; the reference deforms unless np.random.rand() > rand_pro)
+ *   subset:  kd = absorb(kj, 0xfffffffd); P = the cycle-walked 4-round Feistel permutation of [0, l) with round keys
+ *            absorb(kd, r), r = 0..3 (hsp_sample_ids's P with kd in place of kj and c = l).  The band pixel of row-major rank t
+ *            among the band pixels becomes 0 iff P(t) < l / 2 (integer division), else 1; off the band the mask is unchanged.
+ *            Exactly l / 2 zeros on a uniformly drawn subset: np.random.choice(l, l // 2, replace=False)'s DISTRIBUTION, not
+ *            its draws.  (0xfffffffe / 0xfffffffd keep these apart from the row draws under absorb(kj, 0..3 | 0xffffffff).)
+ * An instance that is not deformed keeps m.
+ *
+ * hsp_roi_defor: mask uint8 with an element stride per instance and inst_id as in hsp_roi_compact (H * W without ids: a mask
+ * per instance; 0 with ids: one label image for all; H * W with ids: a label image per instance); xf (n,3) DOUBLE.
+ * crop_mask (n, O*O) uint8: bit 0 = the mask after the rule, bit 1 = m.  band (n,2) int32 = [l, deformed ? 1 : 0].
+ * iters outside 1..8 or gate > 2^32: HSP_ERR_BAD_ARG. */
+size_t hsp_roi_defor_workspace_bytes(int n, int O);     /* per-chunk band counts of the two-launch form */
+int hsp_roi_defor(const uint8_t *mask, long long mask_stride, const int32_t *inst_id, const double *xf, int n, int H, int W,
+                  int O, int iters, unsigned long long gate, const unsigned long long *key, uint8_t *crop_mask,
+                  int32_t *band, void *ws, size_t ws_bytes, hspStream_t stream);
+/* hsp_roi_compact_* with the mask taken from crop_mask (crop space) and a depth_stride in ELEMENTS per instance: 0 = one frame
+ * for all, H * W = a frame per instance (n,H,W).  src (n, O*O) and count (n,2) as hsp_roi_compact defines them with bit 0 as the
+ * mask; src ids are relative to the instance's own frame.  pre (n) int32 = crop pixels with depth > 0 and bit 1: the loader's
+ * roi_m_d_valid sum (:256-258), taken before the deformation. */
+size_t hsp_crop_compact_workspace_bytes(int n, int O);  /* per-chunk count triples of the two-launch compaction */
+int hsp_crop_compact_f32(const float *depth, long long depth_stride, const uint8_t *crop_mask, const double *xf, int n, int H,
+                         int W, int O, int32_t *src, int32_t *count, int32_t *pre, void *ws, size_t ws_bytes,
+                         hspStream_t stream);
+int hsp_crop_compact_u16(const uint16_t *depth, long long depth_stride, const uint8_t *crop_mask, const double *xf, int n, int H,
+                         int W, int O, int32_t *src, int32_t *count, int32_t *pre, void *ws, size_t ws_bytes,
+                         hspStream_t stream);
+/* hsp_frame_to_pcl_* with the same depth_stride: src[j, .] indexes the frame at depth + j * depth_stride. */
+int hsp_frames_to_pcl_f32(const float *depth, long long depth_stride, int H, int W, const double *camK, int camK_rows,
+                          const int32_t *src, long long src_stride, const int32_t *choose, int n, int S, float *pc,
+                          hspStream_t stream);
+int hsp_frames_to_pcl_u16(const uint16_t *depth, long long depth_stride, int H, int W, const double *camK, int camK_rows,
+                          const int32_t *src, long long src_stride, const int32_t *choose, int n, int S, float *pc,
+                          hspStream_t stream);
+
 /* ---- pose matrix assembly -----------------------------------------------------------------------
  * replaces generate_RT([p_green,p_red],[f_green,f_red], T, 'vec', sym)     tools/geom_utils.py:232-244
  * (with to_R_matrices / get_vertical_rot_vec_in_batch / get_rot_mat_y_first, tools/rot_utils.py:39-100)
