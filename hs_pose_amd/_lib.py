@@ -177,6 +177,7 @@ SIGNATURES = {
     "hsp_wgrad_partial_pair_colsum_f32": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp, _sz] * 2 + [_vp, _vp, _i, _i, _i, _vp, _vp]),
     "hsp_rf_fwd_plan": (_i, [_i, _i, _i, _vp]),
     "hsp_rf_bwd_scatter_plan": (_i, [_i, _i, _i, _i, _i, _vp]),
+    "hsp_rf_bwd_set_schedule": (_i, [_i]),
     "hsp_scatter_tile_plan": (_i, [_i, _i, _i, _vp]),
     "hsp_wgrad_plan": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "hsp_wgrad_pair_plan": (_i, [_i, _i, _i, _i, _i, _i, _vp]),

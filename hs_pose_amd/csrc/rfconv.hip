@@ -13,6 +13,7 @@
 #include "common.h"
 #include "folds.h"
 #include <stdlib.h>
+#include <atomic>
 
 namespace hsp {
 
@@ -21,11 +22,7 @@ namespace hsp {
 // F.normalize(directions, dim=0) for the 4 columns j..j+3 of the raw (3, S*C) parameter
 // (reference gcn3d.py:100,166): D / max(||D||_col, 1e-12).  Folded into every kernel so the normalised
 // copy is never materialised and its Jacobian is applied by rf_dirs_reduce_kernel.
-__device__ __forceinline__ void load_dirs_normed(const float* __restrict__ dirs, int SC, int j, float4& d0,
-                                                 float4& d1, float4& d2) {
-    d0 = *reinterpret_cast<const float4*>(dirs + j);
-    d1 = *reinterpret_cast<const float4*>(dirs + SC + j);
-    d2 = *reinterpret_cast<const float4*>(dirs + 2 * SC + j);
+__device__ __forceinline__ void normalise_dirs(float4& d0, float4& d1, float4& d2) {
 #define RF_NRM(X)                                                                                    \
     {                                                                                                \
         const float n2 = norm2_chain(d0.X, d1.X, d2.X);                                              \
@@ -34,6 +31,13 @@ __device__ __forceinline__ void load_dirs_normed(const float* __restrict__ dirs,
     }
     RF_NRM(x) RF_NRM(y) RF_NRM(z) RF_NRM(w)
 #undef RF_NRM
+}
+__device__ __forceinline__ void load_dirs_normed(const float* __restrict__ dirs, int SC, int j, float4& d0,
+                                                 float4& d1, float4& d2) {
+    d0 = *reinterpret_cast<const float4*>(dirs + j);
+    d1 = *reinterpret_cast<const float4*>(dirs + SC + j);
+    d2 = *reinterpret_cast<const float4*>(dirs + 2 * SC + j);
+    normalise_dirs(d0, d1, d2);
 }
 
 // relu(theta) of the forward kernels.  theta = R^ . D^ is the cosine of two unit vectors, so relu == clamp to [0, 1] up to the
@@ -494,18 +498,106 @@ __global__ __launch_bounds__(RF_THREADS) void rf_conv_bwd_csr_kernel(
 // order-independent: the scatter form is now bit-reproducible as well.
 #define RF_ACC_ADD(P, V) atomicAdd(reinterpret_cast<int*>(P), __float2int_rn((V) * fx_scale))
 
+// The tile's fixed-point scale from a thread's max |grad_out| over the rows it visits: folded over the workgroup (fmaxf drops a
+// NaN, so the fold's order cannot matter), / S, then the power of two that leaves ceil(log2 N) bits of headroom.
+// Holds one __syncthreads.
+__device__ __forceinline__ void rf_tile_scale(float vm, float invS, int N, float* wmax, int tid, float& fx_scale, float& fx_inv) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) vm = fmaxf(vm, __shfl_xor(vm, o));
+    if ((tid & 63) == 0) wmax[tid >> 6] = vm;
+    __syncthreads();
+    vm = wmax[0];
+#pragma unroll
+    for (int w = 1; w < RF_TILE_THREADS / 64; ++w) vm = fmaxf(vm, wmax[w]);
+    vm *= invS;
+    if (vm > 0.f && vm < 3.0e38f) {            // (0 / inf / NaN gradients: scale 1 -- nothing sensible to preserve)
+        int ex;
+        frexpf(vm, &ex);                        // vm < 2^ex
+        int lg = 0;
+        while ((1 << lg) < N) ++lg;
+        int e = 30 - ex - lg;
+        e = e > 126 ? 126 : (e < -126 ? -126 : e);      // (2^e and 2^-e both normal floats; |grad| / S down to ~2^-96 keeps the full quantum)
+        fx_scale = ldexpf(1.f, e);
+        fx_inv = ldexpf(1.f, -e);
+    }
+}
+
+__device__ __forceinline__ float absmax4(float4 v) { return fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))); }
+
+// four values of a row AS LOADED: the batched schedule keeps these in its register batches and widens a bf16 piece where it is
+// used, so that no conversion stands between a load and the loads issued after it
+template <typename FT> struct Raw4;
+template <> struct Raw4<float> {
+    typedef float4 T;
+    static __device__ __forceinline__ T ld(const float* p) { return *reinterpret_cast<const float4*>(p); }
+    static __device__ __forceinline__ float4 wide(T v) { return v; }
+    static __device__ __forceinline__ void st(float* p, T v) { *reinterpret_cast<float4*>(p) = v; }
+};
+template <> struct Raw4<bf16_t> {
+    typedef uint2 T;
+    static __device__ __forceinline__ T ld(const bf16_t* p) { return *reinterpret_cast<const uint2*>(p); }
+    static __device__ __forceinline__ float4 wide(T u) {
+        return make_float4(__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xffff0000u), __uint_as_float(u.y << 16),
+                           __uint_as_float(u.y & 0xffff0000u));
+    }
+    static __device__ __forceinline__ void st(bf16_t* p, T v) { *reinterpret_cast<uint2*>(p) = v; }
+};
+typedef float rf_v4f __attribute__((ext_vector_type(4)));
+
+// one point's four columns: route ga * relu(theta) to the winning rows' cells, add to the direction gradient
+#define RF_T1(X, E, FV)                                                                              \
+        {                                                                                            \
+            const int m = (int)am.X - r0;                                                            \
+            if (RS == 1 || (unsigned)m < (unsigned)(r1 - r0)) {                                      \
+                const float3 r = unit_dir_fast(px, py, pz, sx[m * 3], sx[m * 3 + 1], sx[m * 3 + 2]); \
+                const float z = __fmaf_rn(r.z, d2.X, __fmaf_rn(r.y, d1.X, mul_rn(r.x, d0.X)));       \
+                if (z > 0.f) {                                                                       \
+                    if (!SURFACE) RF_ACC_ADD(acc + m * TC + cg * 4 + E, ga.X * z);                   \
+                    const float w = ga.X * FV;                                                       \
+                    g0.X += w * r.x; g1.X += w * r.y; g2.X += w * r.z;                               \
+                }                                                                                    \
+            }                                                                                        \
+        }
+
 // FWIN: the support values come from the forward's fwin stream; else they are gathered from fm (fine while a
 // cloud's fm stays L2-resident: small N)
 // RS > 1 (dense clouds: N = 4096): the tile holds only the source rows [r0, r0 + N/RS) of the cloud -- RS workgroups (grid z)
 // sweep the same points and each keeps the elements whose winning row falls in its range.  What LDS buys is bytes of
 // accumulator: lines touched per launch = N * SC * RS / TC, and acc = (N / RS) * TC * 4 bytes, so two 128 KB half-cloud
 // tiles of 16 columns touch half the lines of one 64 KB whole-cloud tile of 4 (the only whole-cloud width that fits).
-template <int TC, bool SURFACE, bool FWIN, typename FT, int RS = 1>
-__global__ __launch_bounds__(RF_TILE_THREADS) void rf_bwd_tile_kernel(
+// D, RG: the SCHEDULE (what is computed, and in which order each thread adds, is the same under every value):
+//   D = 0   the first form ("legacy", hsp_rf_bwd_set_schedule(1)): every phase a loop of one load and its wait -- staging xyz,
+//           the scale's pass over grad_out, a sweep that prefetches one point ahead and reads grad_out a second time, and the
+//           centre columns copied by the first C / TC tiles of a cloud after their flush.
+//   D > 0   the batched form: every independent load of the set-up -- directions, xyz, the centre columns' share, the scale
+//           pass's grad_out rows, the sweep's first D stages -- is issued as fixed-size register batches with clamped addresses
+//           BEFORE anything waits (the tile is zeroed and the directions normalised under that one round trip); the sweep runs
+//           a D-deep register ring of (argrow, fwin[, grad_out][, the point]) stages, unrolled by D so that it rotates by
+//           renaming; the centre columns are spread over all tiles of the cloud.
+//   RG > 0  (D > 0, not SURFACE, RS == 1, ceil(N / PL) <= RG): the scale pass's grad_out rows ARE the sweep's -- same thread,
+//           same rows, same columns -- so they stay in registers and the sweep, fully unrolled, has no grad_out stream.
+//   RG = 0  grad_out travels in the ring; the scale pass is batched rf_max_batch rows deep.
+// rows per batch of the scale pass where grad_out is not resident (the half-cloud form: N = 4096, 32 rows per thread)
+__host__ __device__ constexpr int rf_max_batch(int tc) { return tc >= 32 ? 4 : 8; }
+// xyz floats per thread and batch (16 columns at N = 1028: 3084 floats over 512 threads, one batch; a 32- / 64-column tile holds
+// at most 585 / 305 points and has fewer registers to spend), centre-column pieces per thread and batch (N = 1028, C = 128: 588
+// per tile; N = 257, C = 256: 294)
+__host__ __device__ constexpr int rf_xyz_batch(int tc) { return tc == 64 ? 2 : (tc == 32 ? 4 : 8); }
+__host__ __device__ constexpr int rf_centre_batch(int tc) { return tc >= 32 ? 1 : 2; }
+// waves per SIMD the batched form must keep (it has more in flight than the legacy form, and hipcc spends registers freely up
+// to the launch bound): 4 = two workgroups per CU where the LDS tile allows no more (16 columns at N = 1028: 128 VGPRs); 6 = the
+// three workgroups per CU of the 32- / 64-column tiles (80 VGPRs); 8 = four for the surface kernel, which has no tile (64 VGPRs)
+__host__ __device__ constexpr int rf_tile_waves(int tc, bool surface, int rs, int d) {
+    return d == 0 || rs > 1 ? 1 : (surface ? 8 : (tc >= 32 ? 6 : 4));
+}
+template <int TC, bool SURFACE, bool FWIN, typename FT, int RS = 1, int D = 0, int RG = 0>
+__global__ __launch_bounds__(RF_TILE_THREADS, rf_tile_waves(TC, SURFACE, RS, D)) void rf_bwd_tile_kernel(
     const float* __restrict__ xyz, const float* __restrict__ dirs, const FT* __restrict__ fwin,
     const uint16_t* __restrict__ argrow, const FT* __restrict__ gout, int B, int N, int S, int C,
     FT* __restrict__ gfm, float* __restrict__ gd_part) {
+    static_assert(RG == 0 || (D > 0 && !SURFACE && RS == 1), "resident grad_out rows: batched whole-cloud conv tiles only");
     extern __shared__ __attribute__((aligned(16))) char smem[];
+    __shared__ float wmax[RF_TILE_THREADS / 64];
     const int NR = RS > 1 ? (N + RS - 1) / RS : N;                     // source rows of this tile
     const int r0 = RS > 1 ? (int)blockIdx.z * NR : 0;
     const int r1 = min(N, r0 + NR);
@@ -542,41 +634,175 @@ __global__ __launch_bounds__(RF_TILE_THREADS) void rf_bwd_tile_kernel(
     const int c = j % C;
     const float invS = 1.0f / (float)S;
     const float* xb = xyz + (size_t)b * N * 3;
+    float fx_scale = 1.f, fx_inv = 1.f;
+    float4 d0, d1, d2;
+    float4 g0 = make_float4(0.f, 0.f, 0.f, 0.f), g1 = g0, g2 = g0;
+    const FT* fsup = (SURFACE || FWIN) ? nullptr : fwin + (size_t)b * N * fstride + C + j;   // (fwin is fm then)
+    if constexpr (D > 0) {
+        typedef typename Raw4<FT>::T RawT;
+        constexpr int RF_XB = rf_xyz_batch(TC), RF_CB = rf_centre_batch(TC);
+        constexpr bool RES = RG > 0;
+        constexpr int NG = RES ? RG : rf_max_batch(TC);          // grad_out rows of the set-up batch
+        constexpr int NST = RES ? RG : D;               // stage registers (RES: one per sweep iteration, D of them in flight)
+        const size_t row0 = (size_t)b * N;
+        const int nlast = N - 1;
+        struct Stage { ushort4 am; RawT fw, ga; float px, py, pz; };
+        auto load_stage = [&](int p) {                  // clamped: no branch around the loads
+            Stage s;
+            p = p < nlast ? p : nlast;
+            s.am = *reinterpret_cast<const ushort4*>(argrow + (row0 + p) * SC + j);
+            s.fw = RawT(); s.ga = RawT(); s.px = s.py = s.pz = 0.f;
+            if (!SURFACE && FWIN) s.fw = Raw4<FT>::ld(fwin + (row0 + p) * SC + j);
+            if (!RES) s.ga = Raw4<FT>::ld(gout + (row0 + p) * C + c);
+            if (RS > 1) { s.px = xb[p * 3]; s.py = xb[p * 3 + 1]; s.pz = xb[p * 3 + 2]; }   // the point itself: a coalesced stream
+            return s;
+        };
+        // ---- 1. issue: nothing below waits before the last of these loads is out
+        d0 = *reinterpret_cast<const float4*>(dirs + j);
+        d1 = *reinterpret_cast<const float4*>(dirs + SC + j);
+        d2 = *reinterpret_cast<const float4*>(dirs + 2 * SC + j);
+        const int n3 = 3 * (r1 - r0);
+        const float* xsrc = xb + r0 * 3;
+        float xv[RF_XB];
+#pragma unroll
+        for (int u = 0; u < RF_XB; ++u) {
+            const int q = tid + u * RF_TILE_THREADS;
+            xv[u] = xsrc[q < n3 ? q : n3 - 1];
+        }
+        // the centre columns grad_fm[b,m,c] = g[b,m,c] of this tile's rows, in 4-value pieces: every tile of the cloud copies an
+        // equal, contiguous share of them
+        const int C4 = C >> 2, Q = (r1 - r0) * C4, per = (Q + (int)gridDim.x - 1) / (int)gridDim.x;
+        const int q_lo = tile * per, q_hi = min(Q, q_lo + per);
+        RawT cv[RF_CB];
+        size_t cdst[RF_CB];
+        auto centre_load = [&](int qb) {
+#pragma unroll
+            for (int u = 0; u < RF_CB; ++u) {
+                int q = qb + tid + u * RF_TILE_THREADS;
+                q = q < Q ? q : Q - 1;
+                const int m = q / C4, c4 = q - m * C4;
+                cv[u] = Raw4<FT>::ld(gout + (row0 + r0 + m) * C + c4 * 4);
+                cdst[u] = (row0 + r0 + m) * fstride + c4 * 4;
+            }
+        };
+        auto centre_store = [&](int qb) {
+#pragma unroll
+            for (int u = 0; u < RF_CB; ++u)
+                if (qb + tid + u * RF_TILE_THREADS < q_hi) Raw4<FT>::st(gfm + cdst[u], cv[u]);
+        };
+        RawT gres[NG];
+        if (!SURFACE) {
+            centre_load(q_lo);
+#pragma unroll
+            for (int t = 0; t < NG; ++t) {
+                const int p = pl + t * PL;
+                gres[t] = Raw4<FT>::ld(gout + (row0 + (p < nlast ? p : nlast)) * C + c);
+            }
+        }
+        Stage st[NST];
+#pragma unroll
+        for (int u = 0; u < (D < NST ? D : NST); ++u) st[u] = load_stage(pl + u * PL);
+        // ---- 2. under that round trip: zero the tile (one 128-bit LDS store per piece), normalise the directions
+        if (!SURFACE)
+            for (int q = tid; q < NR * G; q += RF_TILE_THREADS) *reinterpret_cast<rf_v4f*>(acc + q * 4) = rf_v4f{0.f, 0.f, 0.f, 0.f};
+        normalise_dirs(d0, d1, d2);
+        // ---- 3. consume
+#pragma unroll
+        for (int u = 0; u < RF_XB; ++u) {
+            const int q = tid + u * RF_TILE_THREADS;
+            if (q < n3) sx[q] = xv[u];
+        }
+        for (int q0 = tid + RF_XB * RF_TILE_THREADS; q0 < n3; q0 += RF_XB * RF_TILE_THREADS) {      // (N > 1365)
+#pragma unroll
+            for (int u = 0; u < RF_XB; ++u) {
+                const int q = q0 + u * RF_TILE_THREADS;
+                xv[u] = xsrc[q < n3 ? q : n3 - 1];
+            }
+#pragma unroll
+            for (int u = 0; u < RF_XB; ++u) {
+                const int q = q0 + u * RF_TILE_THREADS;
+                if (q < n3) sx[q] = xv[u];
+            }
+        }
+        if (!SURFACE) {
+            centre_store(q_lo);
+            for (int qb = q_lo + RF_CB * RF_TILE_THREADS; qb < q_hi; qb += RF_CB * RF_TILE_THREADS) {
+                centre_load(qb);
+                centre_store(qb);
+            }
+            // fixed-point scale of this tile: max |grad_out| / S over the (point, channel) values it is going to route (a clamped
+            // row is one of them)
+            float vm = 0.f;
+#pragma unroll
+            for (int t = 0; t < NG; ++t) vm = fmaxf(vm, absmax4(Raw4<FT>::wide(gres[t])));
+            if (!RES)
+                for (int p0 = pl + NG * PL; p0 < N; p0 += NG * PL) {
+                    RawT mv[NG];
+#pragma unroll
+                    for (int t = 0; t < NG; ++t) {
+                        const int p = p0 + t * PL;
+                        mv[t] = Raw4<FT>::ld(gout + (row0 + (p < nlast ? p : nlast)) * C + c);
+                    }
+#pragma unroll
+                    for (int t = 0; t < NG; ++t) vm = fmaxf(vm, absmax4(Raw4<FT>::wide(mv[t])));
+                }
+            rf_tile_scale(vm, invS, N, wmax, tid, fx_scale, fx_inv);
+        }
+        __syncthreads();
+        // ---- 4. sweep: each thread takes its points pl, pl + PL, ... in that order (the direction gradient's rounding)
+        auto point = [&](const Stage& s, RawT graw, int p) {
+            const ushort4 am = s.am;
+            float4 ga = Raw4<FT>::wide(graw);
+            float f0 = 1.f, f1 = 1.f, f2 = 1.f, f3 = 1.f;
+            if (!SURFACE && FWIN) {
+                const float4 fw = Raw4<FT>::wide(s.fw);
+                f0 = fw.x; f1 = fw.y; f2 = fw.z; f3 = fw.w;
+            }
+            if (!SURFACE && !FWIN) {
+                f0 = Feat<FT>::ld(fsup + (size_t)am.x * fstride + 0);
+                f1 = Feat<FT>::ld(fsup + (size_t)am.y * fstride + 1);
+                f2 = Feat<FT>::ld(fsup + (size_t)am.z * fstride + 2);
+                f3 = Feat<FT>::ld(fsup + (size_t)am.w * fstride + 3);
+            }
+            ga.x *= invS; ga.y *= invS; ga.z *= invS; ga.w *= invS;
+            float px, py, pz;
+            if (RS > 1) { px = s.px; py = s.py; pz = s.pz; }
+            else { px = sx[p * 3]; py = sx[p * 3 + 1]; pz = sx[p * 3 + 2]; }
+            RF_T1(x, 0, f0) RF_T1(y, 1, f1) RF_T1(z, 2, f2) RF_T1(w, 3, f3)
+        };
+        if constexpr (RES) {
+#pragma unroll
+            for (int t = 0; t < RG; ++t) {
+                if (t * PL >= N) break;
+                if (t + D < RG) st[t + D] = load_stage(pl + (t + D) * PL);
+                const int p = pl + t * PL;
+                if (p < N) point(st[t], gres[t], p);
+            }
+        } else {
+            for (int p0 = pl; p0 < N; p0 += D * PL) {
+#pragma unroll
+                for (int u = 0; u < D; ++u) {
+                    const int p = p0 + u * PL;
+                    const Stage cur = st[u];
+                    st[u] = load_stage(p + D * PL);
+                    if (p < N) point(cur, cur.ga, p);
+                }
+            }
+        }
+    } else {
     if (!SURFACE)
         for (int q = tid; q < NR * G; q += RF_TILE_THREADS) *reinterpret_cast<float4*>(acc + q * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
     for (int q = tid; q < 3 * (r1 - r0); q += RF_TILE_THREADS) sx[q] = xb[r0 * 3 + q];
     // fixed-point scale of this tile: max |grad_out| / S over the (point, channel) values it is going to route
-    float fx_scale = 1.f, fx_inv = 1.f;
     if (!SURFACE) {
-        __shared__ float wmax[RF_TILE_THREADS / 64];
         float vm = 0.f;
         for (int p = pl; p < N; p += PL) {
             const float4 gq = Feat<FT>::ld4(gout + ((size_t)b * N + p) * C + c);
             vm = fmaxf(vm, fmaxf(fmaxf(fabsf(gq.x), fabsf(gq.y)), fmaxf(fabsf(gq.z), fabsf(gq.w))));
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) vm = fmaxf(vm, __shfl_xor(vm, o));
-        if ((tid & 63) == 0) wmax[tid >> 6] = vm;
-        __syncthreads();
-        vm = wmax[0];
-#pragma unroll
-        for (int w = 1; w < RF_TILE_THREADS / 64; ++w) vm = fmaxf(vm, wmax[w]);
-        vm *= invS;
-        if (vm > 0.f && vm < 3.0e38f) {            // (0 / inf / NaN gradients: scale 1 -- nothing sensible to preserve)
-            int ex;
-            frexpf(vm, &ex);                        // vm < 2^ex
-            int lg = 0;
-            while ((1 << lg) < N) ++lg;
-            int e = 30 - ex - lg;
-            e = e > 126 ? 126 : (e < -126 ? -126 : e);      // (2^e and 2^-e both normal floats; |grad| / S down to ~2^-96 keeps the full quantum)
-            fx_scale = ldexpf(1.f, e);
-            fx_inv = ldexpf(1.f, -e);
-        }
+        rf_tile_scale(vm, invS, N, wmax, tid, fx_scale, fx_inv);
     }
-    float4 d0, d1, d2;
     load_dirs_normed(dirs, SC, j, d0, d1, d2);
-    float4 g0 = make_float4(0.f, 0.f, 0.f, 0.f), g1 = g0, g2 = g0;
-    const FT* fsup = (SURFACE || FWIN) ? nullptr : fwin + (size_t)b * N * fstride + C + j;   // (fwin is fm then)
     __syncthreads();
     // software pipeline: the next point's winning rows / their support values / gradient are in flight while
     // this one is processed; with FWIN every global read of the loop is a coalesced stream
@@ -606,22 +832,10 @@ __global__ __launch_bounds__(RF_TILE_THREADS) void rf_bwd_tile_kernel(
         float px, py, pz;
         if (RS > 1) { px = xb[p * 3]; py = xb[p * 3 + 1]; pz = xb[p * 3 + 2]; }      // the point itself: a coalesced stream
         else { px = sx[p * 3]; py = sx[p * 3 + 1]; pz = sx[p * 3 + 2]; }
-#define RF_T1(X, E, FV)                                                                              \
-        {                                                                                            \
-            const int m = (int)am.X - r0;                                                            \
-            if (RS == 1 || (unsigned)m < (unsigned)(r1 - r0)) {                                      \
-                const float3 r = unit_dir_fast(px, py, pz, sx[m * 3], sx[m * 3 + 1], sx[m * 3 + 2]); \
-                const float z = __fmaf_rn(r.z, d2.X, __fmaf_rn(r.y, d1.X, mul_rn(r.x, d0.X)));       \
-                if (z > 0.f) {                                                                       \
-                    if (!SURFACE) RF_ACC_ADD(acc + m * TC + cg * 4 + E, ga.X * z);                   \
-                    const float w = ga.X * FV;                                                       \
-                    g0.X += w * r.x; g1.X += w * r.y; g2.X += w * r.z;                               \
-                }                                                                                    \
-            }                                                                                        \
-        }
         RF_T1(x, 0, f0) RF_T1(y, 1, f1) RF_T1(z, 2, f2) RF_T1(w, 3, f3)
-#undef RF_T1
     }
+    }
+#undef RF_T1
     __syncthreads();
     if (!SURFACE) {
         // flush the tile: one 16-byte store per (row, group)
@@ -631,7 +845,7 @@ __global__ __launch_bounds__(RF_TILE_THREADS) void rf_bwd_tile_kernel(
             Feat<FT>::st4(gfm + ((size_t)b * N + r0 + m) * fstride + C + j0 + g4 * 4,
                           make_float4((float)iv.x * fx_inv, (float)iv.y * fx_inv, (float)iv.z * fx_inv, (float)iv.w * fx_inv));
         }
-        if (j0 < C) {   // the first C/TC tiles also copy the centre columns grad_fm[b,m,c] = g[b,m,c]
+        if (D == 0 && j0 < C) {   // legacy: the first C/TC tiles also copy the centre columns grad_fm[b,m,c] = g[b,m,c]
             for (int q = tid; q < (r1 - r0) * G; q += RF_TILE_THREADS) {
                 const int m = q / G, g4 = q - m * G;
                 Feat<FT>::st4(gfm + ((size_t)b * N + r0 + m) * fstride + j0 + g4 * 4,
@@ -876,6 +1090,54 @@ extern "C" int hsp_rf_bwd_scatter_plan(int B, int N, int S, int C, int surface, 
     return p.tc;
 }
 
+// The tile kernel's schedule (rf_bwd_tile_kernel: D, RG).  Ring depth and resident rows per instance, from the VGPR count of
+// each: the 16-column whole-cloud tile is LDS-bound at two workgroups per CU and has 128 VGPRs to spend;
+// the 32- and 64-column tiles stay inside the 80 VGPRs that keep three workgroups per CU; the half-cloud form (one workgroup per
+// CU) and the surface kernel (no tile in LDS) carry grad_out in the ring.
+static std::atomic<int> g_rf_bwd_legacy{0};
+
+extern "C" int hsp_rf_bwd_set_schedule(int legacy) {
+    if (legacy != 0 && legacy != 1) return HSP_ERR_BAD_ARG;
+    return g_rf_bwd_legacy.exchange(legacy);
+}
+
+template <int TC, bool SURFACE, int RS> struct RfSched {
+    // (the 32-column tile: depth 1 is what fits 80 VGPRs beside five resident rows; depth 2 at two workgroups per CU measured slower)
+    static constexpr int depth = RS > 1 ? 4 : (SURFACE ? 2 : (TC == 32 ? 1 : (TC == 64 ? 2 : 3)));
+    static constexpr int depth_stream = (!SURFACE && RS == 1 && TC >= 32) ? 1 : depth;      // (grad_out in the ring: four more registers a stage)
+    static constexpr int resident = (SURFACE || RS > 1) ? 0 : (TC == 16 ? 9 : (TC == 32 ? 5 : (TC == 64 ? 2 : 0)));   // rows per thread
+};
+
+template <typename K, typename... A>
+static int rf_tile_issue(K kern, dim3 grid, size_t lds, hipStream_t st, A... args) {
+    if (lds > 64 * 1024) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) { set_last_hip_error(e); return HSP_ERR_LAUNCH; }
+    }
+    hipLaunchKernelGGL(kern, grid, dim3(RF_TILE_THREADS), lds, st, args...);
+    return check_launch();
+}
+
+// one (tile width, row ranges) under the schedule in force when the call is issued (a captured graph keeps what it was captured with)
+template <int TC, bool SURFACE, bool FWIN, typename FT, int RS, typename... A>
+static int rf_tile_launch(bool legacy, int N, dim3 grid, size_t lds, hipStream_t st, A... args) {
+    typedef RfSched<TC, SURFACE, RS> Sch;
+    if (legacy) return rf_tile_issue(rf_bwd_tile_kernel<TC, SURFACE, FWIN, FT, RS, 0, 0>, grid, lds, st, args...);
+    constexpr int PL = RF_TILE_THREADS / (TC / 4);
+    if constexpr (Sch::resident > 0) {
+        if ((N + PL - 1) / PL <= Sch::resident)
+            return rf_tile_issue(rf_bwd_tile_kernel<TC, SURFACE, FWIN, FT, RS, Sch::depth, Sch::resident>, grid, lds, st, args...);
+    }
+    if constexpr (Sch::resident > 0 && TC == 16) {
+        // pick_tile_cols gives a whole cloud 16 columns only while (16 + 3) N floats fit 80 KB: N <= 1077, nine rows per thread.
+        // No streamed instance is built for it; a plan that widened would be declined here, loudly, until one is.
+        static_assert(80 * 1024 / ((16 + 3) * 4) <= Sch::resident * PL, "the 16-column whole-cloud tile must always be resident");
+        return HSP_ERR_UNSUPPORTED;
+    } else {
+        return rf_tile_issue(rf_bwd_tile_kernel<TC, SURFACE, FWIN, FT, RS, Sch::depth_stream, 0>, grid, lds, st, args...);
+    }
+}
+
 template <bool SURFACE, bool FWIN, typename FT>
 static int rf_bwd_scatter(const float* xyz, const float* dirs, const FT* fm, const uint16_t* argrow,
                           const FT* gout, int B, int N, int S, int C, FT* gfm, float* gdirs, void* ws,
@@ -889,14 +1151,12 @@ static int rf_bwd_scatter(const float* xyz, const float* dirs, const FT* fm, con
     const int tc = plan.tc;
     hipStream_t st = as_stream(stream);
     float* part = reinterpret_cast<float*>(ws);
+    const bool legacy = g_rf_bwd_legacy.load() != 0;
     if (plan.rs == 2) {
         const int nr = (N + 1) / 2;
         const size_t lds2 = ((size_t)nr * 16 + 3 * (size_t)nr) * 4;
-        auto kern = rf_bwd_tile_kernel<16, SURFACE, FWIN, FT, 2>;
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
-        if (e != hipSuccess) { set_last_hip_error(e); return HSP_ERR_LAUNCH; }
-        hipLaunchKernelGGL(kern, dim3(SC / 16, B, 2), dim3(RF_TILE_THREADS), lds2, st, xyz, dirs, fm, argrow, gout, B, N, S, C, gfm, part);
-        rc = check_launch();
+        rc = rf_tile_launch<16, SURFACE, FWIN, FT, 2>(legacy, N, dim3(SC / 16, B, 2), lds2, st, xyz, dirs, fm, argrow, gout, B, N, S, C,
+                                                      gfm, part);
         if (rc) return rc;
         if (pending) { *pending = HspDirsPending{part, dirs, gdirs, 2 * B, SC}; return HSP_OK; }
         hipLaunchKernelGGL(rf_dirs_reduce_kernel, dim3((SC + 63) / 64), dim3(1024), 0, st, part, 2 * B, SC, dirs, gdirs);
@@ -906,20 +1166,10 @@ static int rf_bwd_scatter(const float* xyz, const float* dirs, const FT* fm, con
     size_t lds = ((SURFACE ? 0 : (size_t)N * tc) + 3 * (size_t)N) * 4;
     if (lds < RF_TILE_THREADS * 12 * 4) lds = RF_TILE_THREADS * 12 * 4;
     dim3 grid(SC / tc, B);
-#define RF_TILE_LAUNCH(TC)                                                                                          \
-    {                                                                                                               \
-        auto kern = rf_bwd_tile_kernel<TC, SURFACE, FWIN, FT>;                                                                \
-        if (lds > 64 * 1024) {                                                                                      \
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                                 \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);               \
-            if (e != hipSuccess) { set_last_hip_error(e); return HSP_ERR_LAUNCH; }                                  \
-        }                                                                                                           \
-        hipLaunchKernelGGL(kern, grid, dim3(RF_TILE_THREADS), lds, st, xyz, dirs, fm, argrow, gout, B, N, S, C, gfm, part); \
-    }
+#define RF_TILE_LAUNCH(TC) rc = rf_tile_launch<TC, SURFACE, FWIN, FT, 1>(legacy, N, grid, lds, st, xyz, dirs, fm, argrow, gout, B, N, S, C, gfm, part);
     if (tc == 64) RF_TILE_LAUNCH(64) else if (tc == 32) RF_TILE_LAUNCH(32) else if (tc == 16) RF_TILE_LAUNCH(16)
     else if (tc == 8) RF_TILE_LAUNCH(8) else RF_TILE_LAUNCH(4)
 #undef RF_TILE_LAUNCH
-    rc = check_launch();
     if (rc) return rc;
     if (pending) { *pending = HspDirsPending{part, dirs, gdirs, B, SC}; return HSP_OK; }
     hipLaunchKernelGGL(rf_dirs_reduce_kernel, dim3((SC + 63) / 64), dim3(1024), 0, st, part, B, SC, dirs, gdirs);

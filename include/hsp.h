@@ -181,6 +181,14 @@ int hsp_rf_conv_bwd_scatter(const float *xyz, const float *dirs, const float *fm
  * (HSP_ERR_UNSUPPORTED); *row_split (may be NULL) = 1 for one whole-cloud tile per workgroup, 2 for the two half-cloud tiles
  * of 16 columns that dense clouds take, 0 with a decline. */
 int hsp_rf_bwd_scatter_plan(int B, int N, int S, int C, int surface, int *row_split);
+/* How the tile kernel of hsp_rf_conv_bwd_scatter* / hsp_rf_surface_bwd* (and their _partial forms) schedules its loads; what it
+ * computes is the same bits under both values.  legacy = 0 (the default): every independent load of a workgroup's set-up is issued
+ * as register batches before anything waits, grad_out is read once where the rows a thread visits fit its registers, the sweep
+ * runs a register ring several points deep and the centre columns are copied by all tiles of a cloud.  legacy = 1: the first
+ * form (one load per wait, a sweep one point ahead, grad_out read twice, the first C / tile-width tiles copy the centre
+ * columns), kept for the A/B and the tests.  Process-wide; read when a call is issued, so a captured graph keeps the schedule it
+ * was captured with.  Returns the previous value, or HSP_ERR_BAD_ARG (and changes nothing) for anything but 0 / 1. */
+int hsp_rf_bwd_set_schedule(int legacy);
 /* Backward, GATHER form over rev_off/rev_edge = hsp_rev_build(idx) of the SAME idx the forward used:
  * every grad_fm row is summed in ascending edge order (no atomics, bit-reproducible).
  * The rows of one neighbour list idx[b,i,:] must be DISTINCT: a hit is "the winner of (i, j) is this row", so a row listed

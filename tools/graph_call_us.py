@@ -12,7 +12,7 @@ CALLS = {
     "hsp_knn_f32[B16N1028C128k20]": [("hsp::knn_feat_kernel<21, true>", "8192x16"), ("hsp::knn_feat_sym_tail_kernel", "256x16"),
                                      ("hsp::quad32_kernel", "526336x1")],
     "hsp_rf_conv_fwd[B16N1028k20S7C128]": [("hsp::rf_fwd_pipe_kernel<false, 1, true, float>", "524288x1")],
-    "hsp_rf_conv_bwd_scatter[B16N1028S7C128]": [("hsp::rf_bwd_tile_kernel<16, false, true, float, 1>", "28672x16")],
+    "hsp_rf_conv_bwd_scatter[B16N1028S7C128]": [("hsp::rf_bwd_tile_kernel<16, false, true, float, 1, 3, 9>", "28672x16")],
     "hsp_rf_surface_fwd[B16N1028k20S7C128]": [("hsp::rf_fwd_pipe_kernel<true, 1, false, float>", "524288x1")],
     "hsp_geometry_all_f32[B16N1028/257/64k20]": [("hsp::knn3_wave_kernel<17>", "16640x16"), ("hsp::geometry_levels_kernel<5>", "504320x1")],
 }
