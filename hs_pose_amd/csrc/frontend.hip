@@ -1,70 +1,110 @@
-// frontend.hip -- the steps either side of the network at inference for gfx950.
+// frontend.hip -- the steps either side of the network for gfx950.
 //
-//  * depth -> point cloud: replaces the device work of PC_sample (reference
-//    network/point_sample/pc_sample.py:8-77): fuse = mask * (depth > 0); back-project the masked
-//    pixels with the intrinsics; keep `samplenum` of them chosen by the HOST (np.random.choice, same RNG
-//    consumption as the reference); / 1000.  Stage 1 compacts the masked pixel ids of every image in
-//    row-major order (the order of torch's boolean indexing) and returns the counts the host needs to
-//    draw; stage 2 back-projects only the chosen pixels.  The reference materialises three H x W maps and
-//    a variable-length (L,3) tensor per image and synchronises once per image; here: one sync per batch.
-//  * frame -> instance clouds: replaces the loader's crop chain in front of that (evaluation/load_data_eval.py:207-254):
-//    get_bbox window, three cv2.warpAffine(INTER_NEAREST) over the frame, boolean compaction.  Same two stages one step
-//    earlier: stage 1 walks the crop pixels of every instance through the warp's integer map and compacts the source ids of
-//    the valid ones; stage 2 back-projects the chosen ones straight from the frame.
-//  * the chosen rows themselves, optionally: a keyed counter-based draw on the device between the two stages (hsp_sample_ids)
-//    in place of the host's, so that neither front end has to bring its counts to the host.
-//  * a training batch -> instance clouds: the same chain for B frames with one instance each and the loader's defor_2D on the
+// In front of it, a set of pixels is listed in row-major order and the chosen ones are back-projected:
+//  * depth -> point cloud: the device work of PC_sample (reference network/point_sample/pc_sample.py:8-77):
+//    fuse = mask * (depth > 0), the masked pixels back-projected with the intrinsics, `samplenum` of them kept, / 1000.
+//    hsp_pc_compact lists the masked pixel ids of every image (the order of torch's boolean indexing) with their counts;
+//    hsp_pc_gather / hsp_depth_to_pcl back-project only the chosen ones.  One sync per batch where the reference has one per image.
+//  * frame -> instance clouds: the evaluation loader's crop chain in front of that (evaluation/load_data_eval.py:207-254):
+//    get_bbox window, three cv2.warpAffine(INTER_NEAREST) over the frame, boolean compaction.  hsp_roi_compact walks the crop
+//    pixels of every instance through the warp's integer map and lists the source ids of the valid ones; hsp_frame_to_pcl
+//    back-projects the chosen ones straight from the frame.
+//  * a training batch -> instance clouds: that chain for B frames with one instance each and the loader's defor_2D on the
 //    cropped mask in between (datasets/load_data.py:234-278): hsp_roi_defor, hsp_crop_compact, hsp_frames_to_pcl.
+//  * the chosen rows themselves, optionally: a keyed counter-based draw on the device between the two stages (hsp_sample_ids)
+//    in place of the host's, so that no front end has to bring its counts to the host.
+// Behind it:
 //  * (R|t) assembly: replaces generate_RT(..., mode='vec') (tools/geom_utils.py:232-244 with
 //    tools/rot_utils.py:39-100): confidence-weighted orthogonalisation of the two predicted axes and
 //    the 4x4 pose matrix, one lane per object instead of ~40 tiny launches.
+// The listing is ONE skeleton (chunk_count, prefix_sums, chunk_rank, store_ids) under four per-pixel predicates -- hsp_pc_compact,
+// hsp_roi_compact, hsp_crop_compact, hsp_roi_defor --; each form's section says what it adds.
+#include <tuple>
+
 #include "common.h"
 
 namespace hsp {
 
-#define PC_CHUNK 4096          // pixels per workgroup: 256 threads x 16 consecutive pixels (row-major order is kept)
+// ---- the skeleton: row-major stream compaction in two launches --------------------------------------------------------------
+// The pixels of item blockIdx.y (an image, an instance's crop) are cut into chunks of PC_CHUNK, one workgroup each: 256 threads
+// x 16 consecutive pixels, so thread order is pixel order.  A form's predicate turns a thread's 16 pixels into NC bit masks, bit
+// i for pixel i; the set bits of mask 0 are what gets listed, the others are only counted.
+//   count launch  grid (nchunk, n): cnt[(j * nchunk + chunk) * NC + t] = set bits of mask t in the chunk
+//   write launch  grid (nchunk, n): evaluates the predicate again; a thread's rank = mask-0 counts of the earlier chunks + of the
+//                                   earlier waves of the workgroup + of the earlier lanes of the wave; the set pixels' ids are
+//                                   stored from that rank on; the last chunk's workgroup writes the item's totals
+// No atomics, nothing indexed dynamically.  (One workgroup per image moved 75 GB/s: 16 workgroups on 256 CUs.)
+#define PC_CHUNK 4096
 
-__device__ __forceinline__ bool pc_valid(float m, float d) { return m * (d > 0.f ? 1.f : 0.f) > 0.f; }
-
-// row-major stream compaction of {p : mask[p] > 0 && depth[p] > 0}, many workgroups per image, two launches:
-//   pc_count_kernel   grid (nchunk, B): valid pixels of each 4096-pixel chunk -> cnt[b][chunk]
-//   pc_write_kernel   grid (nchunk, B): offset = sum of the earlier chunks' counts, scan inside the chunk, ids written;
-//                                       the last chunk's workgroup writes the image's total
-// (one workgroup per image moved 75 GB/s: 16 workgroups on 256 CUs)
-__global__ __launch_bounds__(256) void pc_count_kernel(const float* __restrict__ mask, const float* __restrict__ depth,
-                                                       int HW, int nchunk, int32_t* __restrict__ cnt) {
-    __shared__ int wsum[4];
-    const int b = blockIdx.y, chunk = blockIdx.x, tid = threadIdx.x;
-    const float* mb = mask + (size_t)b * HW;
-    const float* db = depth + (size_t)b * HW;
-    const int lo = min(chunk * PC_CHUNK + tid * 16, HW), hi = min(lo + 16, HW);
-    int c = 0;
-    for (int p = lo; p < hi; ++p) c += pc_valid(mb[p], db[p]) ? 1 : 0;
+// every lane gets the wave's sums; the N butterflies go step by step side by side, so their exchanges overlap
+template <int N>
+__device__ __forceinline__ void wave_sum(int (&v)[N]) {
 #pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) c += __shfl_xor(c, m);
-    if ((tid & 63) == 0) wsum[tid >> 6] = c;
-    __syncthreads();
-    if (tid == 0) cnt[(size_t)b * nchunk + chunk] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+    for (int m = 32; m >= 1; m >>= 1) {
+#pragma unroll
+        for (int t = 0; t < N; ++t) v[t] += __shfl_xor(v[t], m);
+    }
 }
 
-__global__ __launch_bounds__(256) void pc_write_kernel(const float* __restrict__ mask, const float* __restrict__ depth,
-                                                       int HW, int nchunk, const int32_t* __restrict__ cnt,
-                                                       int32_t* __restrict__ pix, int32_t* __restrict__ count) {
-    __shared__ int red[4];
-    __shared__ int wpre[4];
-    const int b = blockIdx.y, chunk = blockIdx.x, tid = threadIdx.x;
-    const int lane = tid & 63, wv = tid >> 6;
-    // offset of this chunk = sum of the counts of the image's earlier chunks
-    int part = 0;
-    for (int c = tid; c < chunk; c += 256) part += cnt[(size_t)b * nchunk + c];
+template <int NC>
+__device__ __forceinline__ void chunk_count(const unsigned (&bits)[NC], int nchunk, int32_t* __restrict__ cnt) {
+    __shared__ int wsum[4][NC];
+    const int tid = threadIdx.x;
+    int c[NC];
 #pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) part += __shfl_xor(part, m);
-    if (lane == 0) red[wv] = part;
-    const float* mb = mask + (size_t)b * HW;
-    const float* db = depth + (size_t)b * HW;
-    const int lo = min(chunk * PC_CHUNK + tid * 16, HW), hi = min(lo + 16, HW);
-    unsigned bits = 0;
-    for (int p = lo; p < hi; ++p) bits |= (pc_valid(mb[p], db[p]) ? 1u : 0u) << (p - lo);
+    for (int t = 0; t < NC; ++t) c[t] = __popc(bits[t]);
+    wave_sum(c);
+#pragma unroll
+    for (int t = 0; t < NC; ++t)
+        if ((tid & 63) == 0) wsum[tid >> 6][t] = c[t];
+    __syncthreads();
+    if (tid < NC)
+        cnt[((size_t)blockIdx.y * nchunk + blockIdx.x) * NC + tid] = (wsum[0][tid] + wsum[1][tid]) + (wsum[2][tid] + wsum[3][tid]);
+}
+
+// the write launch's LDS: NS sums over the chunk counts (one partial per wave) and the waves' mask-0 counts
+template <int NS>
+struct ChunkLds {
+    int red[4][NS];
+    int wpre[4];
+    __device__ __forceinline__ int sum(int s) const { return (red[0][s] + red[1][s]) + (red[2][s] + red[3][s]); }
+};
+
+// First half of a write kernel, BEFORE the thread evaluates its predicate (these loads go out first).  Sum 0 is always the
+// mask-0 counts of the item's earlier chunks.  With SELF, sum 1 is the mask-0 counts of all chunks, in every workgroup; without,
+// sums 1 .. NC-1 are the totals of masks 1 .. NC-1, in the last chunk's workgroup only (0 elsewhere).
+template <int NC, bool SELF>
+__device__ __forceinline__ void prefix_sums(const int32_t* __restrict__ cnt, int nchunk, ChunkLds<(SELF ? NC + 1 : NC)>& sh) {
+    constexpr int NS = SELF ? NC + 1 : NC;
+    const int chunk = blockIdx.x, tid = threadIdx.x;
+    const int32_t* row = cnt + (size_t)blockIdx.y * nchunk * NC;
+    int part[NS] = {};
+    if (SELF) {
+        for (int c = tid; c < nchunk; c += 256) {
+            const int v = row[(size_t)c * NC];
+            part[1] += v;
+            if (c < chunk) part[0] += v;
+        }
+    } else {
+        for (int c = tid; c < chunk; c += 256) part[0] += row[(size_t)c * NC];
+        if (NC > 1 && chunk == nchunk - 1)
+            for (int c = tid; c < nchunk; c += 256) {
+#pragma unroll
+                for (int t = 1; t < NC; ++t) part[t] += row[(size_t)c * NC + t];
+            }
+    }
+    wave_sum(part);
+#pragma unroll
+    for (int s = 0; s < NS; ++s)
+        if ((tid & 63) == 0) sh.red[tid >> 6][s] = part[s];
+}
+
+// Second half, after the predicate: the exclusive row-major rank of the thread's first set pixel among the item's; `end` is the
+// rank past its last (thread 255 of the last chunk: the item's mask-0 total).  Holds the kernel's one __syncthreads();
+// sh.sum(s) may be read after it.
+template <int NS>
+__device__ __forceinline__ int chunk_rank(unsigned bits, ChunkLds<NS>& sh, int& end) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int c = __popc(bits);
     int incl = c;                                            // inclusive scan inside the wave
 #pragma unroll
@@ -72,16 +112,53 @@ __global__ __launch_bounds__(256) void pc_write_kernel(const float* __restrict__
         const int v = __shfl_up(incl, d);
         if (lane >= d) incl += v;
     }
-    if (lane == 63) wpre[wv] = incl;
+    if (lane == 63) sh.wpre[wv] = incl;
     __syncthreads();
-    const int base = (red[0] + red[1]) + (red[2] + red[3]);
     int woff = 0;
-    for (int w = 0; w < wv; ++w) woff += wpre[w];
-    int off = base + woff + incl - c;
-    int32_t* out = pix + (size_t)b * HW;
-    for (int p = lo; p < hi; ++p)
-        if ((bits >> (p - lo)) & 1u) out[off++] = p;
-    if (chunk == nchunk - 1 && tid == 255) count[b] = base + woff + incl;
+    for (int w = 0; w < wv; ++w) woff += sh.wpre[w];
+    end = sh.sum(0) + woff + incl;
+    return end - c;
+}
+
+// the ids of the thread's set pixels, in order, from rank off on
+__device__ __forceinline__ void store_ids(int32_t* __restrict__ out, int off, unsigned bits, const int (&src)[16]) {
+#pragma unroll
+    for (int i = 0; i < 16; ++i)
+        if ((bits >> i) & 1u) out[off++] = src[i];
+}
+
+// ---- depth -> point cloud: the pixels of image b with mask * (depth > 0) > 0, listed by their own ids -------------------------
+__device__ __forceinline__ bool pc_valid(float m, float d) { return m * (d > 0.f ? 1.f : 0.f) > 0.f; }
+
+__device__ __forceinline__ unsigned pc_scan16(const float* __restrict__ mb, const float* __restrict__ db, int lo, int hi) {
+    unsigned bits = 0;
+    for (int p = lo; p < hi; ++p) bits |= (pc_valid(mb[p], db[p]) ? 1u : 0u) << (p - lo);
+    return bits;
+}
+
+__global__ __launch_bounds__(256) void pc_count_kernel(const float* __restrict__ mask, const float* __restrict__ depth,
+                                                       int HW, int nchunk, int32_t* __restrict__ cnt) {
+    const int b = blockIdx.y;
+    const int lo = min(blockIdx.x * PC_CHUNK + threadIdx.x * 16, HW), hi = min(lo + 16, HW);
+    const unsigned bits[1] = {pc_scan16(mask + (size_t)b * HW, depth + (size_t)b * HW, lo, hi)};
+    chunk_count(bits, nchunk, cnt);
+}
+
+__global__ __launch_bounds__(256) void pc_write_kernel(const float* __restrict__ mask, const float* __restrict__ depth,
+                                                       int HW, int nchunk, const int32_t* __restrict__ cnt,
+                                                       int32_t* __restrict__ pix, int32_t* __restrict__ count) {
+    __shared__ ChunkLds<1> sh;
+    const int b = blockIdx.y;
+    prefix_sums<1, false>(cnt, nchunk, sh);
+    const int lo = min(blockIdx.x * PC_CHUNK + threadIdx.x * 16, HW), hi = min(lo + 16, HW);
+    const unsigned bits = pc_scan16(mask + (size_t)b * HW, depth + (size_t)b * HW, lo, hi);
+    int end;
+    const int off = chunk_rank(bits, sh, end);
+    int src[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) src[i] = lo + i;
+    store_ids(pix + (size_t)b * HW, off, bits, src);
+    if (blockIdx.x == nchunk - 1 && threadIdx.x == 255) count[b] = end;
 }
 
 // PC[b,s,:] = ( (u - cx) * d / fx, (v - cy) * d / fy, d ) / 1000   for pixel pix[b, choose[b,s]]
@@ -144,68 +221,67 @@ __device__ __forceinline__ long long roi_fix(double x) {
     return (long long)fmin(fmax(rint(x * 1024.0), -4503599627370496.0), 4503599627370496.0);
 }
 
+// the map of instance j and which mask values are its own: m == inst_id[j], or without inst_id m != 0
+struct CropMap {
+    double m0;
+    long long bx, by;
+    bool by_id;
+    int want;
+    __device__ __forceinline__ long long X(int u) const { return (bx + roi_fix(m0 * (double)u)) >> 10; }
+    __device__ __forceinline__ long long Y(int v) const { return (by + roi_fix(m0 * (double)v)) >> 10; }
+    __device__ __forceinline__ bool owns(int m) const { return by_id ? m == want : m != 0; }
+};
+
+__device__ __forceinline__ CropMap crop_map(const double* __restrict__ xf, const int32_t* __restrict__ inst_id, int j) {
+    CropMap cm;
+    cm.m0 = xf[(size_t)j * 3];
+    cm.bx = roi_fix(xf[(size_t)j * 3 + 1]) + 512;
+    cm.by = roi_fix(xf[(size_t)j * 3 + 2]) + 512;
+    cm.by_id = inst_id != nullptr;
+    cm.want = inst_id ? inst_id[j] : 0;
+    return cm;
+}
+
 // frame pixel id Y * W + X that crop pixel q = v * O + u reads, or -1 outside the frame
-__device__ __forceinline__ int roi_source(double m0, long long bx, long long by, int q, int O, int H, int W) {
+__device__ __forceinline__ int roi_source(const CropMap& cm, int q, int O, int H, int W) {
     const int v = q / O, u = q - v * O;
-    const long long X = (bx + roi_fix(m0 * (double)u)) >> 10;
-    const long long Y = (by + roi_fix(m0 * (double)v)) >> 10;
+    const long long X = cm.X(u), Y = cm.Y(v);
     if (X < 0 || X >= W || Y < 0 || Y >= H) return -1;
     return (int)Y * W + (int)X;
 }
 
-// the 16 consecutive crop pixels of one thread: source ids, bit i of dbits = depth > 0, of mbits = depth > 0 and mask set
+// hsp_roi_compact: the skeleton over the O * O crop pixels of instance blockIdx.y, NC = 2, source ids listed.
+// The 16 consecutive crop pixels of one thread: source ids, bits[1] = depth > 0, bits[0] = depth > 0 and the mask value owned
 template <typename D>
-__device__ __forceinline__ void roi_scan16(const D* __restrict__ depth, const uint8_t* __restrict__ mask,
-                                           const int32_t* __restrict__ inst_id, const double* __restrict__ xf, int j,
-                                           int lo, int OO, int O, int H, int W, int src[16], unsigned& mbits,
-                                           unsigned& dbits) {
-    const double m0 = xf[(size_t)j * 3];
-    const long long bx = roi_fix(xf[(size_t)j * 3 + 1]) + 512, by = roi_fix(xf[(size_t)j * 3 + 2]) + 512;
-    const int want = inst_id ? inst_id[j] : 0;
-    mbits = 0;
-    dbits = 0;
+__device__ __forceinline__ void roi_scan16(const D* __restrict__ depth, const uint8_t* __restrict__ mask, const CropMap& cm,
+                                           int lo, int OO, int O, int H, int W, int (&src)[16], unsigned (&bits)[2]) {
+    bits[0] = 0;
+    bits[1] = 0;
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
         const int q = lo + i;
         int p = -1;
-        if (q < OO) p = roi_source(m0, bx, by, q, O, H, W);
+        if (q < OO) p = roi_source(cm, q, O, H, W);
         src[i] = p;
         if (p >= 0 && depth[p] > (D)0) {
             const int m = mask[p];
-            dbits |= 1u << i;
-            if (inst_id ? m == want : m != 0) mbits |= 1u << i;
+            bits[1] |= 1u << i;
+            if (cm.owns(m)) bits[0] |= 1u << i;
         }
     }
 }
 
-// same two-launch shape as pc_count_kernel / pc_write_kernel, over the O * O crop pixels of instance blockIdx.y:
-//   roi_count_kernel  cnt[j][chunk] = {mask-and-depth valid, depth valid} of the chunk
-//   roi_write_kernel  offset = earlier chunks' first counts, scan inside the chunk, source ids written in crop row-major order;
-//                     the last chunk's workgroup writes both totals
 template <typename D>
 __global__ __launch_bounds__(256) void roi_count_kernel(const D* __restrict__ depth, const uint8_t* __restrict__ mask,
                                                         long long mask_stride, const int32_t* __restrict__ inst_id,
                                                         const double* __restrict__ xf, int H, int W, int O, int nchunk,
                                                         int32_t* __restrict__ cnt) {
-    __shared__ int wsum[4][2];
-    const int j = blockIdx.y, chunk = blockIdx.x, tid = threadIdx.x;
-    const int OO = O * O;
+    const int j = blockIdx.y;
     int src[16];
-    unsigned mbits, dbits;
-    roi_scan16(depth, mask + (size_t)j * mask_stride, inst_id, xf, j, chunk * PC_CHUNK + tid * 16, OO, O, H, W, src, mbits,
-               dbits);
-    int cm = __popc(mbits), cd = __popc(dbits);
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        cm += __shfl_xor(cm, m);
-        cd += __shfl_xor(cd, m);
-    }
-    if ((tid & 63) == 0) {
-        wsum[tid >> 6][0] = cm;
-        wsum[tid >> 6][1] = cd;
-    }
-    __syncthreads();
-    if (tid < 2) cnt[((size_t)j * nchunk + chunk) * 2 + tid] = (wsum[0][tid] + wsum[1][tid]) + (wsum[2][tid] + wsum[3][tid]);
+    unsigned bits[2];
+    roi_scan16(depth, mask + (size_t)j * mask_stride, crop_map(xf, inst_id, j), blockIdx.x * PC_CHUNK + threadIdx.x * 16, O * O,
+               O, H, W, src, bits);
+    chunk_count(bits, nchunk, cnt);
 }
 
 template <typename D>
@@ -214,61 +290,32 @@ __global__ __launch_bounds__(256) void roi_write_kernel(const D* __restrict__ de
                                                         const double* __restrict__ xf, int H, int W, int O, int nchunk,
                                                         const int32_t* __restrict__ cnt, int32_t* __restrict__ out_src,
                                                         int32_t* __restrict__ count) {
-    __shared__ int red[4][2];
-    __shared__ int wpre[4];
-    const int j = blockIdx.y, chunk = blockIdx.x, tid = threadIdx.x;
-    const int lane = tid & 63, wv = tid >> 6;
+    __shared__ ChunkLds<2> sh;
+    const int j = blockIdx.y;
     const int OO = O * O;
-    const bool last = chunk == nchunk - 1;
-    // offset of this chunk = sum of the first counts of the instance's earlier chunks; the last chunk also totals the second ones
-    int part = 0, partd = 0;
-    for (int c = tid; c < chunk; c += 256) part += cnt[((size_t)j * nchunk + c) * 2];
-    if (last)
-        for (int c = tid; c < nchunk; c += 256) partd += cnt[((size_t)j * nchunk + c) * 2 + 1];
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        part += __shfl_xor(part, m);
-        partd += __shfl_xor(partd, m);
-    }
-    if (lane == 0) {
-        red[wv][0] = part;
-        red[wv][1] = partd;
-    }
+    prefix_sums<2, false>(cnt, nchunk, sh);
     int src[16];
-    unsigned mbits, dbits;
-    roi_scan16(depth, mask + (size_t)j * mask_stride, inst_id, xf, j, chunk * PC_CHUNK + tid * 16, OO, O, H, W, src, mbits,
-               dbits);
-    const int c = __popc(mbits);
-    int incl = c;                                            // inclusive scan inside the wave
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int v = __shfl_up(incl, d);
-        if (lane >= d) incl += v;
-    }
-    if (lane == 63) wpre[wv] = incl;
-    __syncthreads();
-    const int base = (red[0][0] + red[1][0]) + (red[2][0] + red[3][0]);
-    int woff = 0;
-    for (int w = 0; w < wv; ++w) woff += wpre[w];
-    int off = base + woff + incl - c;
-    int32_t* out = out_src + (size_t)j * OO;
-#pragma unroll
-    for (int i = 0; i < 16; ++i)
-        if ((mbits >> i) & 1u) out[off++] = src[i];
-    if (last && tid == 255) {
-        count[j * 2 + 0] = base + woff + incl;
-        count[j * 2 + 1] = (red[0][1] + red[1][1]) + (red[2][1] + red[3][1]);
+    unsigned bits[2];
+    roi_scan16(depth, mask + (size_t)j * mask_stride, crop_map(xf, inst_id, j), blockIdx.x * PC_CHUNK + threadIdx.x * 16, OO, O,
+               H, W, src, bits);
+    int end;
+    const int off = chunk_rank(bits[0], sh, end);
+    store_ids(out_src + (size_t)j * OO, off, bits[0], src);
+    if (blockIdx.x == nchunk - 1 && threadIdx.x == 255) {
+        count[j * 2 + 0] = end;
+        count[j * 2 + 1] = sh.sum(1);
     }
 }
 
-// pc[j,s,:] for frame pixel p = src[j, choose[j,s]]: the grid values the reference warps are u = float(p % W), v = float(p / W)
-// (exact), then the loader's arithmetic.  An index outside its row or frame (a choose beyond the instance's count) gives NaN.
+// pc[j,s,:] for pixel p = src[j, choose[j,s]] of the frame of instance j, depth + j * depth_stride (0: one frame for all): the
+// grid values the reference warps are u = float(p % W), v = float(p / W) (exact), then the loader's arithmetic.  An index
+// outside its row or frame (a choose beyond the instance's count) gives NaN.
 template <typename D>
-__global__ __launch_bounds__(256) void frame_to_pcl_kernel(const D* __restrict__ depth, int H, int W,
-                                                           const double* __restrict__ camK, int camK_rows,
-                                                           const int32_t* __restrict__ src, long long src_stride,
-                                                           const int32_t* __restrict__ choose, int n, int S,
-                                                           float* __restrict__ pc) {
+__global__ __launch_bounds__(256) void frames_to_pcl_kernel(const D* __restrict__ depth, long long depth_stride, int H, int W,
+                                                            const double* __restrict__ camK, int camK_rows,
+                                                            const int32_t* __restrict__ src, long long src_stride,
+                                                            const int32_t* __restrict__ choose, int n, int S,
+                                                            float* __restrict__ pc) {
     const int e = blockIdx.x * 256 + threadIdx.x;
     if (e >= n * S) return;
     const int j = e / S;
@@ -280,7 +327,8 @@ __global__ __launch_bounds__(256) void frame_to_pcl_kernel(const D* __restrict__
         return;
     }
     const int v = p / W, u = p - v * W;
-    backproject_f64((double)(float)u, (double)(float)v, (double)depth[p], camK + (camK_rows > 1 ? (size_t)j * 9 : 0), o);
+    backproject_f64((double)(float)u, (double)(float)v, (double)depth[(size_t)j * depth_stride + p],
+                    camK + (camK_rows > 1 ? (size_t)j * 9 : 0), o);
 }
 
 // ---- the rows each instance keeps, drawn on the device (include/hsp.h: hsp_sample_ids states the construction) ------------
@@ -355,9 +403,8 @@ __global__ __launch_bounds__(256) void sample_ids_kernel(const int32_t* __restri
 
 // ---- the training loader's chain (datasets/load_data.py:228-278): a batch of frames, the mask perturbed before the cut ------
 // include/hsp.h ("the training loader's front end") states the mask rule.  hsp_roi_defor writes the crop-space masks, before
-// and after defor_2D, as one byte per crop pixel; hsp_crop_compact is the compaction above reading that byte in place of the
-// frame's mask, hsp_frames_to_pcl the back-projection above with a frame per instance.  Both two-launch kernels keep the
-// shape of roi_count_kernel / roi_write_kernel: 16 consecutive crop pixels per thread, per-chunk counts in the workspace.
+// and after defor_2D, as one byte per crop pixel; hsp_crop_compact lists the valid crop pixels under that byte; the clouds come
+// from the back-projection above with a frame per instance.
 
 // 16 consecutive bytes of a row of (n, O*O) uint8 as four words, byte i in bits 8 * (i & 3) of word i >> 2: one 16-byte access
 // where the address allows it and all 16 lie inside the row, single bytes (inside the row only) otherwise
@@ -383,15 +430,13 @@ __device__ __forceinline__ void store16(uint8_t* __restrict__ p, int left, const
         if (i < left) p[i] = (uint8_t)(w[i >> 2] >> (8 * (i & 3)));
 }
 
-// the 16 consecutive crop pixels of one thread: bit i of mbits = m, of bbits = on the band (E != D over the triangle i + j <= r
+// hsp_roi_defor: the skeleton with NC = 1 over the band pixels, but what it writes is a byte per crop pixel, not ids: every
+// workgroup needs the band's size l, so every workgroup totals its counter (SELF), and a band pixel's rank decides its bit.
+// The 16 consecutive crop pixels of one thread: bit i of mbits = m, of bbits = on the band (E != D over the triangle i + j <= r
 // up and to the left, positions outside the crop left out).  Every footprint pixel is walked through the map again: at most
 // (r + 1)(r + 2) / 2 mask reads per pixel (3 at r = 1), neighbours' reads meet in the cache.
-__device__ __forceinline__ void defor_scan16(const uint8_t* __restrict__ mask, const int32_t* __restrict__ inst_id,
-                                             const double* __restrict__ xf, int j, int lo, int OO, int O, int H, int W, int r,
-                                             unsigned& mbits, unsigned& bbits) {
-    const double m0 = xf[(size_t)j * 3];
-    const long long bx = roi_fix(xf[(size_t)j * 3 + 1]) + 512, by = roi_fix(xf[(size_t)j * 3 + 2]) + 512;
-    const int want = inst_id ? inst_id[j] : 0;
+__device__ __forceinline__ void defor_scan16(const uint8_t* __restrict__ mask, const CropMap& cm, int lo, int OO, int O, int H,
+                                             int W, int r, unsigned& mbits, unsigned& bbits) {
     mbits = 0;
     bbits = 0;
     int v = lo / O, u = lo - v * O;
@@ -401,16 +446,13 @@ __device__ __forceinline__ void defor_scan16(const uint8_t* __restrict__ mask, c
             unsigned e = 1u, d = 0u;
             const int rb = min(r, v);
             for (int b = 0; b <= rb; ++b) {
-                const long long Y = (by + roi_fix(m0 * (double)(v - b))) >> 10;
+                const long long Y = cm.Y(v - b);
                 const bool yin = Y >= 0 && Y < H;
                 const int ra = min(r - b, u);
                 for (int a = 0; a <= ra; ++a) {
-                    const long long X = (bx + roi_fix(m0 * (double)(u - a))) >> 10;
+                    const long long X = cm.X(u - a);
                     unsigned val = 0u;
-                    if (yin && X >= 0 && X < W) {
-                        const int m = mask[(size_t)Y * W + (size_t)X];
-                        val = (inst_id ? m == want : m != 0) ? 1u : 0u;
-                    }
+                    if (yin && X >= 0 && X < W) val = cm.owns(mask[(size_t)Y * W + (size_t)X]) ? 1u : 0u;
                     e &= val;
                     d |= val;
                     if ((a | b) == 0) mbits |= val << i;
@@ -425,72 +467,38 @@ __device__ __forceinline__ void defor_scan16(const uint8_t* __restrict__ mask, c
     }
 }
 
-//   defor_count_kernel  cnt[j][chunk] = band pixels of the chunk
-//   defor_write_kernel  l = all chunks' counts, rank = earlier chunks' counts + scan inside the chunk; the gate, the subset, the
-//                       bytes; the last chunk's workgroup writes band[j]
 __global__ __launch_bounds__(256) void defor_count_kernel(const uint8_t* __restrict__ mask, long long mask_stride,
                                                           const int32_t* __restrict__ inst_id, const double* __restrict__ xf,
-                                                          int H, int W, int O, int nchunk, int r, int32_t* __restrict__ cnt) {
-    __shared__ int wsum[4];
-    const int j = blockIdx.y, chunk = blockIdx.x, tid = threadIdx.x;
-    unsigned mbits, bbits;
-    defor_scan16(mask + (size_t)j * mask_stride, inst_id, xf, j, chunk * PC_CHUNK + tid * 16, O * O, O, H, W, r, mbits, bbits);
-    int c = __popc(bbits);
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) c += __shfl_xor(c, m);
-    if ((tid & 63) == 0) wsum[tid >> 6] = c;
-    __syncthreads();
-    if (tid == 0) cnt[(size_t)j * nchunk + chunk] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+                                                          int H, int W, int O, int r, int nchunk, int32_t* __restrict__ cnt) {
+    const int j = blockIdx.y;
+    unsigned mbits, bits[1];
+    defor_scan16(mask + (size_t)j * mask_stride, crop_map(xf, inst_id, j), blockIdx.x * PC_CHUNK + threadIdx.x * 16, O * O, O, H,
+                 W, r, mbits, bits[0]);
+    chunk_count(bits, nchunk, cnt);
 }
 
+// its own epilogue: the gate, the subset of the band that becomes 0, the bytes; the last chunk's workgroup writes band[j]
 __global__ __launch_bounds__(256) void defor_write_kernel(const uint8_t* __restrict__ mask, long long mask_stride,
                                                           const int32_t* __restrict__ inst_id, const double* __restrict__ xf,
-                                                          int H, int W, int O, int nchunk, int r, unsigned long long gate,
+                                                          int H, int W, int O, int r, int nchunk,
+                                                          const int32_t* __restrict__ cnt, unsigned long long gate,
                                                           const unsigned long long* __restrict__ key,
-                                                          const int32_t* __restrict__ cnt, uint8_t* __restrict__ crop_mask,
-                                                          int32_t* __restrict__ band) {
-    __shared__ int red[4][2];
-    __shared__ int wpre[4];
-    const int j = blockIdx.y, chunk = blockIdx.x, tid = threadIdx.x;
-    const int lane = tid & 63, wv = tid >> 6;
+                                                          uint8_t* __restrict__ crop_mask, int32_t* __restrict__ band) {
+    __shared__ ChunkLds<2> sh;
+    const int j = blockIdx.y;
     const int OO = O * O;
-    int part = 0, tot = 0;                                   // band pixels of the earlier chunks, and of all of them
-    for (int c = tid; c < nchunk; c += 256) {
-        const int v = cnt[(size_t)j * nchunk + c];
-        tot += v;
-        if (c < chunk) part += v;
-    }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        part += __shfl_xor(part, m);
-        tot += __shfl_xor(tot, m);
-    }
-    if (lane == 0) {
-        red[wv][0] = part;
-        red[wv][1] = tot;
-    }
-    const int lo = chunk * PC_CHUNK + tid * 16;
+    prefix_sums<1, true>(cnt, nchunk, sh);
+    const int lo = blockIdx.x * PC_CHUNK + threadIdx.x * 16;
     unsigned mbits, bbits;
-    defor_scan16(mask + (size_t)j * mask_stride, inst_id, xf, j, lo, OO, O, H, W, r, mbits, bbits);
-    const int c = __popc(bbits);
-    int incl = c;                                            // inclusive scan inside the wave
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int v = __shfl_up(incl, d);
-        if (lane >= d) incl += v;
-    }
-    if (lane == 63) wpre[wv] = incl;
-    __syncthreads();
-    const int base = (red[0][0] + red[1][0]) + (red[2][0] + red[3][0]);
-    const int l = (red[0][1] + red[1][1]) + (red[2][1] + red[3][1]);
-    int woff = 0;
-    for (int w = 0; w < wv; ++w) woff += wpre[w];
+    defor_scan16(mask + (size_t)j * mask_stride, crop_map(xf, inst_id, j), lo, OO, O, H, W, r, mbits, bbits);
+    int end;
+    uint32_t t = (uint32_t)chunk_rank(bbits, sh, end);   // row-major rank of this thread's first band pixel
+    const int l = sh.sum(1);
     const uint32_t kj = instance_key(key, j);
     const bool deformed = l >= 1 && (unsigned long long)absorb(absorb(kj, 0xfffffffeu), 0u) < gate;
     unsigned one = mbits;                                    // bit 0 of the 16 bytes
     if (deformed) {
         const uint32_t kd = absorb(kj, 0xfffffffdu), zeros = (uint32_t)l / 2u;
-        uint32_t t = (uint32_t)(base + woff + incl - c);     // row-major rank of this thread's first band pixel
         one |= bbits;
         for (unsigned rest = bbits; rest; rest &= rest - 1u, ++t)
             if (feistel_permute(t, (uint32_t)l, kd) < zeros) one &= ~(rest & (0u - rest));
@@ -499,66 +507,48 @@ __global__ __launch_bounds__(256) void defor_write_kernel(const uint8_t* __restr
 #pragma unroll
     for (int i = 0; i < 16; ++i) w[i >> 2] |= (((one >> i) & 1u) | (((mbits >> i) & 1u) << 1)) << (8 * (i & 3));
     store16(crop_mask + (size_t)j * OO + min(lo, OO), OO - min(lo, OO), w);
-    if (chunk == nchunk - 1 && tid == 255) {
+    if (blockIdx.x == nchunk - 1 && threadIdx.x == 255) {
         band[j * 2 + 0] = l;
         band[j * 2 + 1] = deformed ? 1 : 0;
     }
 }
 
-// roi_scan16 with the mask bits taken from the crop-space byte: mbits = depth > 0 and bit 0, pbits = depth > 0 and bit 1
+// hsp_crop_compact: hsp_roi_compact's predicate with the mask taken from the crop-space byte and a third mask counted, NC = 3:
+// bits[1] = depth > 0, bits[0] = depth > 0 and bit 0 (the deformed mask), bits[2] = depth > 0 and bit 1 (the mask before)
 template <typename D>
-__device__ __forceinline__ void crop_scan16(const D* __restrict__ depth, const uint8_t* __restrict__ cmask,
-                                            const double* __restrict__ xf, int j, int lo, int OO, int O, int H, int W,
-                                            int src[16], unsigned& mbits, unsigned& dbits, unsigned& pbits) {
-    const double m0 = xf[(size_t)j * 3];
-    const long long bx = roi_fix(xf[(size_t)j * 3 + 1]) + 512, by = roi_fix(xf[(size_t)j * 3 + 2]) + 512;
+__device__ __forceinline__ void crop_scan16(const D* __restrict__ depth, const uint8_t* __restrict__ cmask, const CropMap& cm,
+                                            int lo, int OO, int O, int H, int W, int (&src)[16], unsigned (&bits)[3]) {
     uint32_t w[4];
     load16(cmask + min(lo, OO), OO - min(lo, OO), w);
-    mbits = 0;
-    dbits = 0;
-    pbits = 0;
+    bits[0] = 0;
+    bits[1] = 0;
+    bits[2] = 0;
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
         const int q = lo + i;
         int p = -1;
-        if (q < OO) p = roi_source(m0, bx, by, q, O, H, W);
+        if (q < OO) p = roi_source(cm, q, O, H, W);
         src[i] = p;
         if (p >= 0 && depth[p] > (D)0) {
             const uint32_t c = w[i >> 2] >> (8 * (i & 3));
-            dbits |= 1u << i;
-            mbits |= (c & 1u) << i;
-            pbits |= ((c >> 1) & 1u) << i;
+            bits[1] |= 1u << i;
+            bits[0] |= (c & 1u) << i;
+            bits[2] |= ((c >> 1) & 1u) << i;
         }
     }
 }
 
-//   crop_count_kernel  cnt[j][chunk] = {bit 0 and depth, depth, bit 1 and depth} of the chunk
-//   crop_write_kernel  as roi_write_kernel; the last chunk's workgroup writes the three totals
 template <typename D>
 __global__ __launch_bounds__(256) void crop_count_kernel(const D* __restrict__ depth, long long depth_stride,
                                                          const uint8_t* __restrict__ crop_mask, const double* __restrict__ xf,
                                                          int H, int W, int O, int nchunk, int32_t* __restrict__ cnt) {
-    __shared__ int wsum[4][3];
-    const int j = blockIdx.y, chunk = blockIdx.x, tid = threadIdx.x;
+    const int j = blockIdx.y;
     const int OO = O * O;
     int src[16];
-    unsigned mbits, dbits, pbits;
-    crop_scan16(depth + (size_t)j * depth_stride, crop_mask + (size_t)j * OO, xf, j, chunk * PC_CHUNK + tid * 16, OO, O, H, W,
-                src, mbits, dbits, pbits);
-    int cm = __popc(mbits), cd = __popc(dbits), cp = __popc(pbits);
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        cm += __shfl_xor(cm, m);
-        cd += __shfl_xor(cd, m);
-        cp += __shfl_xor(cp, m);
-    }
-    if ((tid & 63) == 0) {
-        wsum[tid >> 6][0] = cm;
-        wsum[tid >> 6][1] = cd;
-        wsum[tid >> 6][2] = cp;
-    }
-    __syncthreads();
-    if (tid < 3) cnt[((size_t)j * nchunk + chunk) * 3 + tid] = (wsum[0][tid] + wsum[1][tid]) + (wsum[2][tid] + wsum[3][tid]);
+    unsigned bits[3];
+    crop_scan16(depth + (size_t)j * depth_stride, crop_mask + (size_t)j * OO, crop_map(xf, nullptr, j),
+                blockIdx.x * PC_CHUNK + threadIdx.x * 16, OO, O, H, W, src, bits);
+    chunk_count(bits, nchunk, cnt);
 }
 
 template <typename D>
@@ -567,78 +557,22 @@ __global__ __launch_bounds__(256) void crop_write_kernel(const D* __restrict__ d
                                                          int H, int W, int O, int nchunk, const int32_t* __restrict__ cnt,
                                                          int32_t* __restrict__ out_src, int32_t* __restrict__ count,
                                                          int32_t* __restrict__ pre) {
-    __shared__ int red[4][3];
-    __shared__ int wpre[4];
-    const int j = blockIdx.y, chunk = blockIdx.x, tid = threadIdx.x;
-    const int lane = tid & 63, wv = tid >> 6;
+    __shared__ ChunkLds<3> sh;
+    const int j = blockIdx.y;
     const int OO = O * O;
-    const bool last = chunk == nchunk - 1;
-    int part = 0, partd = 0, partp = 0;
-    for (int c = tid; c < chunk; c += 256) part += cnt[((size_t)j * nchunk + c) * 3];
-    if (last)
-        for (int c = tid; c < nchunk; c += 256) {
-            partd += cnt[((size_t)j * nchunk + c) * 3 + 1];
-            partp += cnt[((size_t)j * nchunk + c) * 3 + 2];
-        }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        part += __shfl_xor(part, m);
-        partd += __shfl_xor(partd, m);
-        partp += __shfl_xor(partp, m);
-    }
-    if (lane == 0) {
-        red[wv][0] = part;
-        red[wv][1] = partd;
-        red[wv][2] = partp;
-    }
+    prefix_sums<3, false>(cnt, nchunk, sh);
     int src[16];
-    unsigned mbits, dbits, pbits;
-    crop_scan16(depth + (size_t)j * depth_stride, crop_mask + (size_t)j * OO, xf, j, chunk * PC_CHUNK + tid * 16, OO, O, H, W,
-                src, mbits, dbits, pbits);
-    const int c = __popc(mbits);
-    int incl = c;                                            // inclusive scan inside the wave
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int v = __shfl_up(incl, d);
-        if (lane >= d) incl += v;
+    unsigned bits[3];
+    crop_scan16(depth + (size_t)j * depth_stride, crop_mask + (size_t)j * OO, crop_map(xf, nullptr, j),
+                blockIdx.x * PC_CHUNK + threadIdx.x * 16, OO, O, H, W, src, bits);
+    int end;
+    const int off = chunk_rank(bits[0], sh, end);
+    store_ids(out_src + (size_t)j * OO, off, bits[0], src);
+    if (blockIdx.x == nchunk - 1 && threadIdx.x == 255) {
+        count[j * 2 + 0] = end;
+        count[j * 2 + 1] = sh.sum(1);
+        pre[j] = sh.sum(2);
     }
-    if (lane == 63) wpre[wv] = incl;
-    __syncthreads();
-    const int base = (red[0][0] + red[1][0]) + (red[2][0] + red[3][0]);
-    int woff = 0;
-    for (int w = 0; w < wv; ++w) woff += wpre[w];
-    int off = base + woff + incl - c;
-    int32_t* out = out_src + (size_t)j * OO;
-#pragma unroll
-    for (int i = 0; i < 16; ++i)
-        if ((mbits >> i) & 1u) out[off++] = src[i];
-    if (last && tid == 255) {
-        count[j * 2 + 0] = base + woff + incl;
-        count[j * 2 + 1] = (red[0][1] + red[1][1]) + (red[2][1] + red[3][1]);
-        pre[j] = (red[0][2] + red[1][2]) + (red[2][2] + red[3][2]);
-    }
-}
-
-// frame_to_pcl_kernel with the frame of instance j at depth + j * depth_stride
-template <typename D>
-__global__ __launch_bounds__(256) void frames_to_pcl_kernel(const D* __restrict__ depth, long long depth_stride, int H, int W,
-                                                            const double* __restrict__ camK, int camK_rows,
-                                                            const int32_t* __restrict__ src, long long src_stride,
-                                                            const int32_t* __restrict__ choose, int n, int S,
-                                                            float* __restrict__ pc) {
-    const int e = blockIdx.x * 256 + threadIdx.x;
-    if (e >= n * S) return;
-    const int j = e / S;
-    float* o = pc + (size_t)e * 3;
-    const int c = choose[e];
-    const int p = (c >= 0 && c < src_stride) ? src[(size_t)j * src_stride + c] : -1;
-    if (p < 0 || p >= H * W) {
-        o[0] = o[1] = o[2] = __builtin_nanf("");
-        return;
-    }
-    const int v = p / W, u = p - v * W;
-    backproject_f64((double)(float)u, (double)(float)v, (double)depth[(size_t)j * depth_stride + p],
-                    camK + (camK_rows > 1 ? (size_t)j * 9 : 0), o);
 }
 
 __device__ __forceinline__ void rodrigues_apply(const float rx[3], float s, float c, const float v[3], float o[3]) {
@@ -697,24 +631,40 @@ __global__ __launch_bounds__(64) void generate_rt_kernel(const float* __restrict
 
 using namespace hsp;
 
+static int chunks_of(int pixels) { return (pixels + PC_CHUNK - 1) / PC_CHUNK; }
+
+// the two launches of a compaction over grid (nchunk, n): count_k(in..., nchunk, cnt), then write_k(in..., nchunk, cnt, out...)
+template <typename CountK, typename WriteK, typename... In, typename... Out>
+static int compact_launch(CountK count_k, WriteK write_k, int n, int pixels, void* ws, hspStream_t stream,
+                          const std::tuple<In...>& in, Out... out) {
+    const int nchunk = chunks_of(pixels);
+    const dim3 grid(nchunk, n);
+    hipStream_t st = as_stream(stream);
+    int32_t* cnt = reinterpret_cast<int32_t*>(ws);
+    std::apply([&](In... a) { hipLaunchKernelGGL(count_k, grid, dim3(256), 0, st, a..., nchunk, cnt); }, in);
+    int rc = check_launch();
+    if (rc) return rc;
+    std::apply([&](In... a) { hipLaunchKernelGGL(write_k, grid, dim3(256), 0, st, a..., nchunk, cnt, out...); }, in);
+    return check_launch();
+}
+
+// NC counters per chunk of each of n crops of O x O pixels
+static size_t crop_workspace_bytes(int n, int O, int NC) {
+    if (n <= 0 || O <= 0 || O > 46340) return 0;
+    return (size_t)n * chunks_of(O * O) * NC * sizeof(int32_t);
+}
+
 extern "C" size_t hsp_pc_compact_workspace_bytes(int B, int HW) {
     if (B <= 0 || HW <= 0) return 0;
-    return (size_t)B * ((HW + PC_CHUNK - 1) / PC_CHUNK) * sizeof(int32_t);
+    return (size_t)B * chunks_of(HW) * sizeof(int32_t);
 }
 
 extern "C" int hsp_pc_compact(const float* mask, const float* depth, int B, int HW, int32_t* pix, int32_t* count,
                               void* ws, size_t ws_bytes, hspStream_t stream) {
     if (!mask || !depth || !pix || !count || B <= 0 || HW <= 0) return HSP_ERR_BAD_ARG;
     if (!ws || ws_bytes < hsp_pc_compact_workspace_bytes(B, HW)) return HSP_ERR_WORKSPACE;
-    const int nchunk = (HW + PC_CHUNK - 1) / PC_CHUNK;
-    if (nchunk > 65535) return HSP_ERR_UNSUPPORTED;
-    hipStream_t st = as_stream(stream);
-    int32_t* cnt = reinterpret_cast<int32_t*>(ws);
-    hipLaunchKernelGGL(pc_count_kernel, dim3(nchunk, B), dim3(256), 0, st, mask, depth, HW, nchunk, cnt);
-    int rc = check_launch();
-    if (rc) return rc;
-    hipLaunchKernelGGL(pc_write_kernel, dim3(nchunk, B), dim3(256), 0, st, mask, depth, HW, nchunk, cnt, pix, count);
-    return check_launch();
+    if (chunks_of(HW) > 65535) return HSP_ERR_UNSUPPORTED;
+    return compact_launch(pc_count_kernel, pc_write_kernel, B, HW, ws, stream, std::make_tuple(mask, depth, HW), pix, count);
 }
 
 extern "C" int hsp_pc_gather(const float* depth, const float* coor2d, const float* camK, const int32_t* pix,
@@ -733,10 +683,7 @@ extern "C" int hsp_depth_to_pcl(const float* depth, const float* xymap, const do
     return check_launch();
 }
 
-extern "C" size_t hsp_roi_compact_workspace_bytes(int n, int O) {
-    if (n <= 0 || O <= 0 || O > 46340) return 0;
-    return (size_t)n * ((O * O + PC_CHUNK - 1) / PC_CHUNK) * 2 * sizeof(int32_t);
-}
+extern "C" size_t hsp_roi_compact_workspace_bytes(int n, int O) { return crop_workspace_bytes(n, O, 2); }
 
 template <typename D>
 static int roi_compact(const D* depth, const uint8_t* mask, long long mask_stride, const int32_t* inst_id, const double* xf,
@@ -746,16 +693,8 @@ static int roi_compact(const D* depth, const uint8_t* mask, long long mask_strid
     if ((long long)H * W > 2147483647LL || (mask_stride != 0 && mask_stride != (long long)H * W)) return HSP_ERR_BAD_ARG;
     if (O > 46340 || n > 65535) return HSP_ERR_UNSUPPORTED;
     if (!ws || ws_bytes < hsp_roi_compact_workspace_bytes(n, O)) return HSP_ERR_WORKSPACE;
-    const int nchunk = (O * O + PC_CHUNK - 1) / PC_CHUNK;
-    hipStream_t st = as_stream(stream);
-    int32_t* cnt = reinterpret_cast<int32_t*>(ws);
-    hipLaunchKernelGGL(roi_count_kernel<D>, dim3(nchunk, n), dim3(256), 0, st, depth, mask, mask_stride, inst_id, xf, H, W, O,
-                       nchunk, cnt);
-    int rc = check_launch();
-    if (rc) return rc;
-    hipLaunchKernelGGL(roi_write_kernel<D>, dim3(nchunk, n), dim3(256), 0, st, depth, mask, mask_stride, inst_id, xf, H, W, O,
-                       nchunk, cnt, src, count);
-    return check_launch();
+    return compact_launch(roi_count_kernel<D>, roi_write_kernel<D>, n, O * O, ws, stream,
+                          std::make_tuple(depth, mask, mask_stride, inst_id, xf, H, W, O), src, count);
 }
 
 extern "C" int hsp_roi_compact_f32(const float* depth, const uint8_t* mask, long long mask_stride, const int32_t* inst_id,
@@ -770,28 +709,31 @@ extern "C" int hsp_roi_compact_u16(const uint16_t* depth, const uint8_t* mask, l
     return roi_compact(depth, mask, mask_stride, inst_id, xf, n, H, W, O, src, count, ws, ws_bytes, stream);
 }
 
+// hsp_frame_to_pcl's refusals and the launch: one frame for all instances with depth_stride 0, and no bound on n beyond
+// n * S < 2^31
 template <typename D>
-static int frame_to_pcl(const D* depth, int H, int W, const double* camK, int camK_rows, const int32_t* src,
-                        long long src_stride, const int32_t* choose, int n, int S, float* pc, hspStream_t stream) {
+static int frame_to_pcl(const D* depth, long long depth_stride, int H, int W, const double* camK, int camK_rows,
+                        const int32_t* src, long long src_stride, const int32_t* choose, int n, int S, float* pc,
+                        hspStream_t stream) {
     if (!depth || !camK || !src || !choose || !pc || n <= 0 || S <= 0 || H <= 0 || W <= 0 || src_stride <= 0)
         return HSP_ERR_BAD_ARG;
     if ((long long)H * W > 2147483647LL || (camK_rows != 1 && camK_rows != n) || (long long)n * S > 2147483647LL)
         return HSP_ERR_BAD_ARG;
-    hipLaunchKernelGGL(frame_to_pcl_kernel<D>, dim3((n * S + 255) / 256), dim3(256), 0, as_stream(stream), depth, H, W, camK,
-                       camK_rows, src, src_stride, choose, n, S, pc);
+    hipLaunchKernelGGL(frames_to_pcl_kernel<D>, dim3((n * S + 255) / 256), dim3(256), 0, as_stream(stream), depth, depth_stride,
+                       H, W, camK, camK_rows, src, src_stride, choose, n, S, pc);
     return check_launch();
 }
 
 extern "C" int hsp_frame_to_pcl_f32(const float* depth, int H, int W, const double* camK, int camK_rows, const int32_t* src,
                                     long long src_stride, const int32_t* choose, int n, int S, float* pc,
                                     hspStream_t stream) {
-    return frame_to_pcl(depth, H, W, camK, camK_rows, src, src_stride, choose, n, S, pc, stream);
+    return frame_to_pcl(depth, 0, H, W, camK, camK_rows, src, src_stride, choose, n, S, pc, stream);
 }
 
 extern "C" int hsp_frame_to_pcl_u16(const uint16_t* depth, int H, int W, const double* camK, int camK_rows,
                                     const int32_t* src, long long src_stride, const int32_t* choose, int n, int S, float* pc,
                                     hspStream_t stream) {
-    return frame_to_pcl(depth, H, W, camK, camK_rows, src, src_stride, choose, n, S, pc, stream);
+    return frame_to_pcl(depth, 0, H, W, camK, camK_rows, src, src_stride, choose, n, S, pc, stream);
 }
 
 extern "C" int hsp_sample_ids(const int32_t* count, int count_stride, int n, int S, int min_pts, int min_depth_pts,
@@ -812,10 +754,7 @@ static bool train_shape_ok(int n, int H, int W, int O, long long stride) {
     return stride == 0 || stride == (long long)H * W;
 }
 
-extern "C" size_t hsp_roi_defor_workspace_bytes(int n, int O) {
-    if (n <= 0 || O <= 0 || O > 46340) return 0;
-    return (size_t)n * ((O * O + PC_CHUNK - 1) / PC_CHUNK) * sizeof(int32_t);
-}
+extern "C" size_t hsp_roi_defor_workspace_bytes(int n, int O) { return crop_workspace_bytes(n, O, 1); }
 
 extern "C" int hsp_roi_defor(const uint8_t* mask, long long mask_stride, const int32_t* inst_id, const double* xf, int n, int H,
                              int W, int O, int iters, unsigned long long gate, const unsigned long long* key,
@@ -823,22 +762,11 @@ extern "C" int hsp_roi_defor(const uint8_t* mask, long long mask_stride, const i
     if (!mask || !xf || !key || !crop_mask || !band || !train_shape_ok(n, H, W, O, mask_stride)) return HSP_ERR_BAD_ARG;
     if (iters < 1 || iters > 8 || gate > (1ULL << 32)) return HSP_ERR_BAD_ARG;
     if (!ws || ws_bytes < hsp_roi_defor_workspace_bytes(n, O)) return HSP_ERR_WORKSPACE;
-    const int nchunk = (O * O + PC_CHUNK - 1) / PC_CHUNK;
-    hipStream_t st = as_stream(stream);
-    int32_t* cnt = reinterpret_cast<int32_t*>(ws);
-    hipLaunchKernelGGL(defor_count_kernel, dim3(nchunk, n), dim3(256), 0, st, mask, mask_stride, inst_id, xf, H, W, O, nchunk,
-                       iters, cnt);
-    int rc = check_launch();
-    if (rc) return rc;
-    hipLaunchKernelGGL(defor_write_kernel, dim3(nchunk, n), dim3(256), 0, st, mask, mask_stride, inst_id, xf, H, W, O, nchunk,
-                       iters, gate, key, cnt, crop_mask, band);
-    return check_launch();
+    return compact_launch(defor_count_kernel, defor_write_kernel, n, O * O, ws, stream,
+                          std::make_tuple(mask, mask_stride, inst_id, xf, H, W, O, iters), gate, key, crop_mask, band);
 }
 
-extern "C" size_t hsp_crop_compact_workspace_bytes(int n, int O) {
-    if (n <= 0 || O <= 0 || O > 46340) return 0;
-    return (size_t)n * ((O * O + PC_CHUNK - 1) / PC_CHUNK) * 3 * sizeof(int32_t);
-}
+extern "C" size_t hsp_crop_compact_workspace_bytes(int n, int O) { return crop_workspace_bytes(n, O, 3); }
 
 template <typename D>
 static int crop_compact(const D* depth, long long depth_stride, const uint8_t* crop_mask, const double* xf, int n, int H, int W,
@@ -846,16 +774,8 @@ static int crop_compact(const D* depth, long long depth_stride, const uint8_t* c
     if (!depth || !crop_mask || !xf || !src || !count || !pre || !train_shape_ok(n, H, W, O, depth_stride))
         return HSP_ERR_BAD_ARG;
     if (!ws || ws_bytes < hsp_crop_compact_workspace_bytes(n, O)) return HSP_ERR_WORKSPACE;
-    const int nchunk = (O * O + PC_CHUNK - 1) / PC_CHUNK;
-    hipStream_t st = as_stream(stream);
-    int32_t* cnt = reinterpret_cast<int32_t*>(ws);
-    hipLaunchKernelGGL(crop_count_kernel<D>, dim3(nchunk, n), dim3(256), 0, st, depth, depth_stride, crop_mask, xf, H, W, O,
-                       nchunk, cnt);
-    int rc = check_launch();
-    if (rc) return rc;
-    hipLaunchKernelGGL(crop_write_kernel<D>, dim3(nchunk, n), dim3(256), 0, st, depth, depth_stride, crop_mask, xf, H, W, O,
-                       nchunk, cnt, src, count, pre);
-    return check_launch();
+    return compact_launch(crop_count_kernel<D>, crop_write_kernel<D>, n, O * O, ws, stream,
+                          std::make_tuple(depth, depth_stride, crop_mask, xf, H, W, O), src, count, pre);
 }
 
 extern "C" int hsp_crop_compact_f32(const float* depth, long long depth_stride, const uint8_t* crop_mask, const double* xf,
@@ -870,16 +790,13 @@ extern "C" int hsp_crop_compact_u16(const uint16_t* depth, long long depth_strid
     return crop_compact(depth, depth_stride, crop_mask, xf, n, H, W, O, src, count, pre, ws, ws_bytes, stream);
 }
 
+// a frame per instance (or one for all) under the training chain's bounds
 template <typename D>
 static int frames_to_pcl(const D* depth, long long depth_stride, int H, int W, const double* camK, int camK_rows,
                          const int32_t* src, long long src_stride, const int32_t* choose, int n, int S, float* pc,
                          hspStream_t stream) {
-    if (!depth || !camK || !src || !choose || !pc || S <= 0 || src_stride <= 0 || !train_shape_ok(n, H, W, 1, depth_stride))
-        return HSP_ERR_BAD_ARG;
-    if ((camK_rows != 1 && camK_rows != n) || (long long)n * S > 2147483647LL) return HSP_ERR_BAD_ARG;
-    hipLaunchKernelGGL(frames_to_pcl_kernel<D>, dim3((n * S + 255) / 256), dim3(256), 0, as_stream(stream), depth, depth_stride,
-                       H, W, camK, camK_rows, src, src_stride, choose, n, S, pc);
-    return check_launch();
+    if (!train_shape_ok(n, H, W, 1, depth_stride)) return HSP_ERR_BAD_ARG;
+    return frame_to_pcl(depth, depth_stride, H, W, camK, camK_rows, src, src_stride, choose, n, S, pc, stream);
 }
 
 extern "C" int hsp_frames_to_pcl_f32(const float* depth, long long depth_stride, int H, int W, const double* camK,

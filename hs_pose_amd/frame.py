@@ -14,7 +14,6 @@ import numpy as np
 import torch
 
 from . import ops, pc_sample
-from .config import FLAGS
 from .graph import GraphedInference
 
 
@@ -136,13 +135,8 @@ class FramePipeline:
         return pred_RT, pred_s
 
     def _replay_frame(self, sampler, depth, masks, inst_ids, centers, scales, K, class_ids):
-        n_pts = int(FLAGS.random_points if self.n_pts is None else self.n_pts)
-        O = int(FLAGS.img_size if self.out_size is None else self.out_size)
-        xf = pc_sample.roi_transform(centers, scales, O)
-        if masks.dtype == torch.bool:
-            masks = masks.view(torch.uint8)
-        K = (K.detach().cpu().numpy() if isinstance(K, torch.Tensor) else np.asarray(K)).astype(np.float64).reshape(-1, 9)
-        ids = None if inst_ids is None else np.asarray(inst_ids).astype(np.int32)
+        n_pts, O, xf, masks, ids, K = pc_sample._frame_args(masks, centers, scales, K.cpu() if isinstance(K, torch.Tensor) else K,
+                                                            self.n_pts, self.out_size, inst_ids)
         obj_id = np.asarray(class_ids).astype(np.int64) - 1
         key = (sampler, xf.shape[0], tuple(depth.shape), depth.dtype, masks.dim(), ids is None, K.shape[0], n_pts, O)
         fg = self.frame_graphs.get(key)

@@ -2654,14 +2654,40 @@ def sample_ids(count, S, key, min_pts, min_depth_pts=0, short_mode=0):
 _FRAME_DEPTH = {torch.float32: "_f32", torch.uint16: "_u16"}
 
 
-def _req_frame_depth(depth, name):
+def _req_depth(depth, name, n=None):
+    """a float32 or uint16 depth on the device, contiguous: a single (H,W) frame only (n None), or one (H,W) frame for all n
+    instances or a frame each, (n,H,W)"""
     if not isinstance(depth, torch.Tensor) or not depth.is_cuda:
         raise HspError(f"{name}: expected a GPU tensor (hs_pose_amd has no CPU path), got "
                        f"{getattr(depth, 'device', type(depth))}")
-    if depth.dtype not in _FRAME_DEPTH or depth.dim() != 2 or depth.numel() == 0 or depth.numel() >= 2 ** 31:
-        raise HspError(f"{name}: expected an (H,W) float32 or uint16 frame with H*W < 2^31, got {tuple(depth.shape)} "
-                       f"{depth.dtype}")
+    if depth.dtype not in _FRAME_DEPTH or depth.dim() not in ((2,) if n is None else (2, 3)) or depth.numel() == 0 \
+            or depth.shape[-2] * depth.shape[-1] >= 2 ** 31 or (depth.dim() == 3 and depth.shape[0] != n):
+        what = "an (H,W) float32 or uint16 frame" if n is None else f"an (H,W) or ({n},H,W) float32 or uint16 depth"
+        raise HspError(f"{name}: expected {what} with H*W < 2^31, got {tuple(depth.shape)} {depth.dtype}")
     return depth.detach() if depth.is_contiguous() else depth.detach().contiguous()
+
+
+def _compact(name, depth, each, xf, out_size, head, n_out):
+    """what ``roi_compact`` and ``crop_compact`` share: xf (n,3) float64, out_size and n in range, depth a single frame or
+    (``each``) also a frame per instance; ``head(depth, n, H, W, O)`` checks the form's own arguments and returns them as the
+    entry point lists them between depth and xf; src (n, O*O), count (n,2) and for n_out 3 a third (n,) output, all int32."""
+    xf = _req(xf, torch.float64, f"{name}.xf")
+    if xf.dim() != 2 or xf.shape[1] != 3 or xf.shape[0] == 0:
+        raise HspError(f"{name}: expects xf (n,3) float64 with n >= 1")
+    n, O = xf.shape[0], int(out_size)
+    depth = _req_depth(depth, f"{name}.depth", n if each else None)
+    H, W = depth.shape[-2:]
+    if not 0 < O <= 46340 or n > 65535:
+        raise HspError(f"{name}: out_size {O} / n {n} out of range (0 < out_size <= 46340, n <= 65535)")
+    head = head(depth, n, H, W, O)
+    outs = [torch.empty(shape, dtype=torch.int32, device=depth.device) for shape in ((n, O * O), (n, 2), (n,))[:n_out]]
+    wsb = getattr(lib(), f"hsp_{name}_workspace_bytes")(n, O)
+    ws = _ws(wsb, depth.device)
+    _run(f"hsp_{name}" + _FRAME_DEPTH[depth.dtype],
+         (_p(depth), *(a if isinstance(a, int) else _p(a) for a in head), _p(xf), n, H, W, O, *map(_p, outs), _p(ws), wsb,
+          _stream()),
+         key=f"n{n}O{O}", abytes=n * O * O * (depth.element_size() + 1 + 4))
+    return tuple(outs)
 
 
 def roi_compact(depth, mask, xf, out_size, inst_ids=None):
@@ -2670,62 +2696,41 @@ def roi_compact(depth, mask, xf, out_size, inst_ids=None):
     (include/hsp.h), inst_ids (n) int32 or None (a pixel belongs to instance j if mask == inst_ids[j]; None: if mask != 0)
     -> (src (n, O*O) int32, count (n,2) int32): the frame pixel ids of the crop pixels with depth > 0 and the mask set, in
     crop row-major order, and [mask-and-depth valid, depth valid]; entries of src past count[j,0] are undefined."""
-    depth = _req_frame_depth(depth, "roi_compact.depth")
-    mask = _req(mask.detach() if isinstance(mask, torch.Tensor) else mask, torch.uint8, "roi_compact.mask")
-    xf = _req(xf, torch.float64, "roi_compact.xf")
-    H, W = depth.shape
-    O = int(out_size)
-    if xf.dim() != 2 or xf.shape[1] != 3 or xf.shape[0] == 0:
-        raise HspError("roi_compact: expects xf (n,3) float64 with n >= 1")
-    n = xf.shape[0]
-    if tuple(mask.shape) not in ((n, H, W), (H, W)):
-        raise HspError(f"roi_compact: expects mask ({n},{H},{W}) or ({H},{W}), got {tuple(mask.shape)}")
-    if not 0 < O <= 46340 or n > 65535:
-        raise HspError(f"roi_compact: out_size {O} / n {n} out of range (0 < out_size <= 46340, n <= 65535)")
-    if inst_ids is not None:
-        inst_ids = _req(inst_ids, torch.int32, "roi_compact.inst_ids")
-        if inst_ids.shape != (n,):
-            raise HspError(f"roi_compact: expects inst_ids ({n},), got {tuple(inst_ids.shape)}")
-    src = torch.empty(n, O * O, dtype=torch.int32, device=depth.device)
-    count = torch.empty(n, 2, dtype=torch.int32, device=depth.device)
-    wsb = lib().hsp_roi_compact_workspace_bytes(n, O)
-    ws = _ws(wsb, depth.device)
-    _run("hsp_roi_compact" + _FRAME_DEPTH[depth.dtype],
-         (_p(depth), _p(mask), H * W if mask.dim() == 3 else 0, _p(inst_ids), _p(xf), n, H, W, O, _p(src), _p(count), _p(ws),
-          wsb, _stream()),
-         key=f"n{n}O{O}", abytes=n * O * O * (depth.element_size() + 1 + 4))
-    return src, count
+    def head(depth, n, H, W, O):
+        m = _req(mask.detach() if isinstance(mask, torch.Tensor) else mask, torch.uint8, "roi_compact.mask")
+        if tuple(m.shape) not in ((n, H, W), (H, W)):
+            raise HspError(f"roi_compact: expects mask ({n},{H},{W}) or ({H},{W}), got {tuple(m.shape)}")
+        ids = None if inst_ids is None else _req(inst_ids, torch.int32, "roi_compact.inst_ids")
+        if ids is not None and ids.shape != (n,):
+            raise HspError(f"roi_compact: expects inst_ids ({n},), got {tuple(ids.shape)}")
+        return m, H * W if m.dim() == 3 else 0, ids
+    return _compact("roi_compact", depth, False, xf, out_size, head, 2)
+
+
+def _to_pcl(name, depth, each, camK64, src, choose):
+    """what ``frame_to_pcl`` and ``frames_to_pcl`` share; ``each``: a frame per instance is allowed and n is bounded"""
+    src = _req(src, torch.int32, f"{name}.src")
+    choose = _req(choose, torch.int32, f"{name}.choose")
+    camK64 = _req(camK64.detach() if isinstance(camK64, torch.Tensor) else camK64, torch.float64, f"{name}.camK")
+    if src.dim() != 2 or choose.dim() != 2 or src.shape[0] != choose.shape[0] or src.shape[0] == 0 or choose.shape[1] == 0 \
+            or (each and src.shape[0] > 65535) or camK64.numel() not in (9, 9 * src.shape[0]):
+        raise HspError(f"{name}: expects depth (H,W){' or (n,H,W)' if each else ''}, camK (1|n,3,3) f64, src (n,L), choose (n,S) "
+                       f"with {'1 <= n <= 65535, S >= 1' if each else 'n, S >= 1'}")
+    n, S = choose.shape
+    depth = _req_depth(depth, f"{name}.depth", n if each else None)
+    H, W = depth.shape[-2:]
+    pc = torch.empty(n, S, 3, dtype=torch.float32, device=depth.device)
+    stride = (H * W if depth.dim() == 3 else 0,) if each else ()
+    _run(f"hsp_{name}" + _FRAME_DEPTH[depth.dtype],
+         (_p(depth), *stride, H, W, _p(camK64), camK64.numel() // 9, _p(src), src.shape[1], _p(choose), n, S, _p(pc), _stream()),
+         key=f"n{n}S{S}", abytes=n * S * (8 + depth.element_size() + 12))
+    return pc
 
 
 def frame_to_pcl(depth, camK64, src, choose):
     """back-project the chosen crop pixels straight from the frame (load_data_eval.py:253-254): depth (H,W) fp32 or uint16,
     camK (1|n,3,3) float64, src (n,L) int32 from roi_compact, choose (n,S) int32 -> (n,S,3) fp32 metres."""
-    depth = _req_frame_depth(depth, "frame_to_pcl.depth")
-    camK64 = _req(camK64.detach() if isinstance(camK64, torch.Tensor) else camK64, torch.float64, "frame_to_pcl.camK")
-    src = _req(src, torch.int32, "frame_to_pcl.src")
-    choose = _req(choose, torch.int32, "frame_to_pcl.choose")
-    H, W = depth.shape
-    if src.dim() != 2 or choose.dim() != 2 or src.shape[0] != choose.shape[0] or src.shape[0] == 0 or choose.shape[1] == 0 \
-            or camK64.numel() not in (9, 9 * src.shape[0]):
-        raise HspError("frame_to_pcl: expects depth (H,W), camK (1|n,3,3) f64, src (n,L), choose (n,S) with n, S >= 1")
-    n, S = choose.shape
-    pc = torch.empty(n, S, 3, dtype=torch.float32, device=depth.device)
-    _run("hsp_frame_to_pcl" + _FRAME_DEPTH[depth.dtype],
-         (_p(depth), H, W, _p(camK64), camK64.numel() // 9, _p(src), src.shape[1], _p(choose), n, S, _p(pc), _stream()),
-         key=f"n{n}S{S}", abytes=n * S * (8 + depth.element_size() + 12))
-    return pc
-
-
-def _req_frames_depth(depth, n, name):
-    """one (H,W) frame for all n instances or a frame each, (n,H,W)"""
-    if not isinstance(depth, torch.Tensor) or not depth.is_cuda:
-        raise HspError(f"{name}: expected a GPU tensor (hs_pose_amd has no CPU path), got "
-                       f"{getattr(depth, 'device', type(depth))}")
-    if depth.dtype not in _FRAME_DEPTH or depth.dim() not in (2, 3) or depth.numel() == 0 \
-            or depth.shape[-2] * depth.shape[-1] >= 2 ** 31 or (depth.dim() == 3 and depth.shape[0] != n):
-        raise HspError(f"{name}: expected an (H,W) or ({n},H,W) float32 or uint16 depth with H*W < 2^31, got "
-                       f"{tuple(depth.shape)} {depth.dtype}")
-    return depth.detach() if depth.is_contiguous() else depth.detach().contiguous()
+    return _to_pcl("frame_to_pcl", depth, False, camK64, src, choose)
 
 
 def roi_defor(mask, xf, out_size, key, inst_ids=None, iters=1, gate=0):
@@ -2764,45 +2769,15 @@ def crop_compact(depth, crop_mask, xf, out_size):
     """``roi_compact`` with the mask taken from roi_defor's bytes and a frame per instance: depth (H,W) or (n,H,W) fp32 or
     uint16, crop_mask (n, O*O) uint8, xf (n,3) float64 -> (src (n, O*O) int32, ids into the instance's own frame; count (n,2)
     int32 = [bit-0-and-depth valid, depth valid]; pre (n,) int32 = bit-1-and-depth valid, the count before the deformation)."""
-    xf = _req(xf, torch.float64, "crop_compact.xf")
-    if xf.dim() != 2 or xf.shape[1] != 3 or xf.shape[0] == 0:
-        raise HspError("crop_compact: expects xf (n,3) float64 with n >= 1")
-    n, O = xf.shape[0], int(out_size)
-    depth = _req_frames_depth(depth, n, "crop_compact.depth")
-    crop_mask = _req(crop_mask, torch.uint8, "crop_compact.crop_mask")
-    H, W = depth.shape[-2:]
-    if not 0 < O <= 46340 or n > 65535:
-        raise HspError(f"crop_compact: out_size {O} / n {n} out of range (0 < out_size <= 46340, n <= 65535)")
-    if tuple(crop_mask.shape) != (n, O * O):
-        raise HspError(f"crop_compact: expects crop_mask ({n},{O * O}), got {tuple(crop_mask.shape)}")
-    src = torch.empty(n, O * O, dtype=torch.int32, device=depth.device)
-    count = torch.empty(n, 2, dtype=torch.int32, device=depth.device)
-    pre = torch.empty(n, dtype=torch.int32, device=depth.device)
-    wsb = lib().hsp_crop_compact_workspace_bytes(n, O)
-    ws = _ws(wsb, depth.device)
-    _run("hsp_crop_compact" + _FRAME_DEPTH[depth.dtype],
-         (_p(depth), H * W if depth.dim() == 3 else 0, _p(crop_mask), _p(xf), n, H, W, O, _p(src), _p(count), _p(pre), _p(ws),
-          wsb, _stream()),
-         key=f"n{n}O{O}", abytes=n * O * O * (depth.element_size() + 1 + 4))
-    return src, count, pre
+    def head(depth, n, H, W, O):
+        cm = _req(crop_mask, torch.uint8, "crop_compact.crop_mask")
+        if tuple(cm.shape) != (n, O * O):
+            raise HspError(f"crop_compact: expects crop_mask ({n},{O * O}), got {tuple(cm.shape)}")
+        return H * W if depth.dim() == 3 else 0, cm
+    return _compact("crop_compact", depth, True, xf, out_size, head, 3)
 
 
 def frames_to_pcl(depth, camK64, src, choose):
     """``frame_to_pcl`` with a frame per instance: depth (H,W) or (n,H,W) fp32 or uint16, camK (1|n,3,3) float64, src (n,L)
     int32 from crop_compact, choose (n,S) int32 -> (n,S,3) fp32 metres; NaN rows where choose is -1."""
-    src = _req(src, torch.int32, "frames_to_pcl.src")
-    choose = _req(choose, torch.int32, "frames_to_pcl.choose")
-    camK64 = _req(camK64.detach() if isinstance(camK64, torch.Tensor) else camK64, torch.float64, "frames_to_pcl.camK")
-    if src.dim() != 2 or choose.dim() != 2 or src.shape[0] != choose.shape[0] or src.shape[0] == 0 or choose.shape[1] == 0 \
-            or src.shape[0] > 65535 or camK64.numel() not in (9, 9 * src.shape[0]):
-        raise HspError("frames_to_pcl: expects depth (H,W) or (n,H,W), camK (1|n,3,3) f64, src (n,L), choose (n,S) with "
-                       "1 <= n <= 65535, S >= 1")
-    n, S = choose.shape
-    depth = _req_frames_depth(depth, n, "frames_to_pcl.depth")
-    H, W = depth.shape[-2:]
-    pc = torch.empty(n, S, 3, dtype=torch.float32, device=depth.device)
-    _run("hsp_frames_to_pcl" + _FRAME_DEPTH[depth.dtype],
-         (_p(depth), H * W if depth.dim() == 3 else 0, H, W, _p(camK64), camK64.numel() // 9, _p(src), src.shape[1], _p(choose),
-          n, S, _p(pc), _stream()),
-         key=f"n{n}S{S}", abytes=n * S * (8 + depth.element_size() + 12))
-    return pc
+    return _to_pcl("frames_to_pcl", depth, True, camK64, src, choose)

@@ -231,28 +231,34 @@ def _upload(a, dtype, dev, out=None):
     return staging.upload(lambda pinned: pinned.copy_(t), t.shape, t.dtype, dev, out=out)
 
 
+def _frame_args(masks, centers, scales, K, n_pts, out_size, inst_ids):
+    """what every form of the frame front end makes of its arguments before anything goes to the device -> (n_pts, O, xf (n,3)
+    float64, masks as uint8, ids (n,) int32 or None, K float64 (1|n, 9)), numpy's; a K that is on the device is left as given"""
+    n_pts = int(FLAGS.random_points if n_pts is None else n_pts)
+    O = int(FLAGS.img_size if out_size is None else out_size)
+    xf = roi_transform(centers, scales, O)
+    if masks.dtype == torch.bool:
+        masks = masks.view(torch.uint8)
+    ids = None if inst_ids is None else np.asarray(inst_ids).astype(np.int32)
+    if not (isinstance(K, torch.Tensor) and K.is_cuda):
+        K = (K.detach().numpy() if isinstance(K, torch.Tensor) else np.asarray(K)).astype(np.float64).reshape(-1, 9)
+    return n_pts, O, xf, masks, ids, K
+
+
 def frame_to_pcl_device(depth, masks, centers, scales, K, n_pts=None, out_size=None, inst_ids=None, min_pts=2, sampler=None):
     """``frame_to_pcl`` with the rows drawn on the device: the same arguments, ``sampler`` a DeviceSampler (None or 'device':
     the module's) -> (PC (n, n_pts, 3) fp32 metres, status (n,) int32), both on the device.  status bit 0: fewer than min_pts
     crop pixels with depth and mask; bit 1: <= 1 with depth; the rows of such an instance are NaN and the frame is one the
     loader skips.  Three launches and the uploads of the small host arrays, all queued: no device->host copy, no wait."""
-    n_pts = int(FLAGS.random_points if n_pts is None else n_pts)
-    O = int(FLAGS.img_size if out_size is None else out_size)
-    xf = roi_transform(centers, scales, O)
-    n = xf.shape[0]
+    n_pts, O, xf, masks, ids, K = _frame_args(masks, centers, scales, K, n_pts, out_size, inst_ids)
     dev = depth.device
     sampler = resolve_sampler("device" if sampler is None else sampler, dev)
     if sampler is None:
         raise ValueError("frame_to_pcl_device: expects a device sampler; the host draws are frame_to_pcl's")
-    if n == 0:
+    if xf.shape[0] == 0:
         return torch.zeros(0, n_pts, 3, dtype=torch.float32, device=dev), torch.zeros(0, dtype=torch.int32, device=dev)
-    if masks.dtype == torch.bool:
-        masks = masks.view(torch.uint8)
-    ids_d = None if inst_ids is None else _upload(np.asarray(inst_ids), np.int32, dev)
-    if isinstance(K, torch.Tensor) and K.is_cuda:
-        K64 = K.to(torch.float64).reshape(-1, 9).contiguous()
-    else:
-        K64 = _upload(np.asarray(K, dtype=np.float64).reshape(-1, 9), np.float64, dev)
+    ids_d = None if ids is None else _upload(ids, np.int32, dev)
+    K64 = K.to(torch.float64).reshape(-1, 9).contiguous() if isinstance(K, torch.Tensor) else _upload(K, np.float64, dev)
     src, count = ops.roi_compact(depth, masks, _upload(xf, np.float64, dev), O, ids_d)
     choose, status = ops.sample_ids(count, n_pts, sampler.advance(), min_pts, 2, 0)
     return ops.frame_to_pcl(depth, K64, src, choose), status
@@ -272,18 +278,12 @@ def frame_to_pcl(depth, masks, centers, scales, K, n_pts=None, out_size=None, in
     if dsampler is not None:
         PC, status = frame_to_pcl_device(depth, masks, centers, scales, K, n_pts, out_size, inst_ids, min_pts, dsampler)
         return None if bool(status.any()) else PC
-    n_pts = int(FLAGS.random_points if n_pts is None else n_pts)
-    O = int(FLAGS.img_size if out_size is None else out_size)
-    xf = roi_transform(centers, scales, O)
+    n_pts, O, xf, masks, ids, K = _frame_args(masks, centers, scales, K, n_pts, out_size, inst_ids)
     n = xf.shape[0]
     dev = depth.device
     if n == 0:
         return torch.zeros(0, n_pts, 3, dtype=torch.float32, device=dev)
-    if masks.dtype == torch.bool:
-        masks = masks.view(torch.uint8)
-    ids_d = None
-    if inst_ids is not None:
-        ids_d = torch.as_tensor(np.asarray(inst_ids).astype(np.int32)).to(dev, non_blocking=True)
+    ids_d = None if ids is None else torch.from_numpy(ids).to(dev, non_blocking=True)
     K64 = torch.as_tensor(K, dtype=torch.float64).reshape(-1, 9).to(dev, non_blocking=True)
     src, count = ops.roi_compact(depth, masks, torch.from_numpy(xf).to(dev, non_blocking=True), O, ids_d)
     counts = count.cpu().numpy()                               # the one sync of the front end

@@ -36,6 +36,22 @@ def test_pc_compact_sizes(dev, ref, HW):
         assert np.array_equal(pix[b, :len(want)].cpu().numpy(), want)
 
 
+def test_pc_compact_past_256_chunks(dev):
+    """258 chunks: the write kernel's sum over the earlier chunks' counts, one count per thread, makes a second trip"""
+    from hs_pose_amd import ops
+    HW = 257 * 4096 + 5
+    rng = np.random.RandomState(41)
+    m = (rng.rand(1, HW) < 0.3).astype(np.float32)
+    d = (rng.rand(1, HW) * 900.0).astype(np.float32)
+    d[rng.rand(1, HW) < 0.2] = 0.0
+    m[0, -1], d[0, -1] = 1.0, 5.0                                               # (the five-pixel last chunk is not empty)
+    pix, count = ops.pc_compact(torch.from_numpy(m).to(dev), torch.from_numpy(d).to(dev))
+    want = np.flatnonzero((m[0] > 0) & (d[0] > 0))
+    assert (want >= 256 * 4096).sum() > 1000 and want[-1] == HW - 1
+    assert int(count[0]) == len(want)
+    assert np.array_equal(pix[0, :len(want)].cpu().numpy(), want)
+
+
 def test_pc_compact_all_and_none(dev, ref):
     """every pixel valid (the ids fill the whole row) and no pixel valid (count 0), several chunks per image"""
     from hs_pose_amd import ops

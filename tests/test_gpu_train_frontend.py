@@ -191,6 +191,53 @@ def test_real_size(dev):
     _check_compact(ops.crop_compact(torch.from_numpy(depth).to(dev), cm_d, xf_d, O), depth, cm, xf, O)
 
 
+def test_past_256_chunks(dev):
+    """one instance at O = 1040 on a 96 x 128 frame: 1 081 600 crop pixels in 265 chunks, so the write kernels' sums over the
+    chunk counts (one count per thread, 256 threads) make a second trip, in all three forms that read a crop; and the
+    back-projection of one frame by both of its entry points, bit for bit"""
+    from hs_pose_amd import ops
+    Hh, Ww, O = 96, 128, 1040
+    OO, past = O * O, 256 * 4096
+    xf = fh.ref_xf((64.0, 48.0), 90.0, O)
+    assert (fh.ref_source(xf, O, Hh, Ww) >= 0).all()                             # the whole crop maps inside the frame
+    yy, xx = np.mgrid[0:Hh, 0:Ww]
+    mask = ((yy // 3 + xx // 3) % 4 != 0).astype(np.uint8)
+    rng = np.random.RandomState(1)
+    depth32 = (rng.rand(Hh, Ww) * 2000).astype(np.float32)
+    depth32[rng.rand(Hh, Ww) < 0.2] = 0
+    xf_d = torch.tensor([xf], dtype=torch.float64, device=dev)
+    mask_d = torch.from_numpy(mask[None]).to(dev)
+    m = rr.crop_m(mask != 0, xf, O)
+    seed, call = KEYS[0]
+    key = _key(seed, call, dev)
+    cms = {}
+    for gate in (2 ** 32, 0):
+        cm_d, band = ops.roi_defor(mask_d, xf_d, O, key, None, 1, gate)
+        want, info = rr.defor(m, 1, gate, seed, call, 0)
+        assert band.cpu().tolist() == [info] and info == [30775, int(gate != 0)]
+        assert np.array_equal(cm_d.cpu().numpy().reshape(O, O), want), gate
+        cms[gate] = cm_d, want
+    E, D = rr.erode_dilate(m, 1)
+    assert (np.flatnonzero((E != D).reshape(-1)) >= past).sum() == 961           # band ranks past the 256th chunk
+    K_d = torch.from_numpy(K_REAL).to(dev)
+    for depth in (depth32, depth32.astype(np.uint16)):
+        depth_d = torch.from_numpy(depth).to(dev)
+        want, counts = fh.ref_compact(depth, mask != 0, xf, O)
+        p = fh.ref_source(xf, O, Hh, Ww).reshape(-1)
+        per_chunk = np.bincount(np.flatnonzero((depth.reshape(-1)[p] > 0) & (mask.reshape(-1)[p] != 0)) // 4096, minlength=265)
+        assert per_chunk.sum() == counts[0] > 600000 and per_chunk.min() >= 100 and per_chunk[256:].sum() > 10000
+        src_d, count = ops.roi_compact(depth_d, mask_d, xf_d, O)
+        assert src_d.shape == (1, OO) and count.cpu().tolist() == [counts]
+        assert np.array_equal(src_d[0, :counts[0]].cpu().numpy(), want)
+        for gate, (cm_d, cbytes) in cms.items():
+            _check_compact(ops.crop_compact(depth_d[None], cm_d, xf_d, O), depth[None], cbytes.reshape(1, OO), [np.array(xf)], O)
+        choose = torch.tensor([[0, counts[0] - 1, -1, counts[0] // 2, OO + 3, 1, OO]], dtype=torch.int32, device=dev)
+        one = ops.frame_to_pcl(depth_d, K_d, src_d, choose)
+        many = ops.frames_to_pcl(depth_d, K_d, src_d, choose)
+        assert one.shape == many.shape == (1, 7, 3) and torch.equal(one.view(torch.int32), many.view(torch.int32))
+        assert torch.isnan(one[0, [2, 4, 6]]).all() and torch.isfinite(one[0, [0, 1, 3, 5]]).all()
+
+
 def _put_depth(frame, xf, O, crop_pixels, value):
     """give the frame pixels behind the listed crop pixels (flat ids) a depth"""
     p = fh.ref_source(xf, O, *frame.shape).reshape(-1)[crop_pixels]
