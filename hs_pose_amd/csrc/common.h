@@ -26,6 +26,19 @@ inline int check_launch() {
 
 inline hipStream_t as_stream(hspStream_t s) { return reinterpret_cast<hipStream_t>(s); }
 
+// launch with `lds` bytes of dynamic LDS.  Above 64 KiB the kernel's limit has to be raised first, and it is on EVERY such launch:
+// the attribute is a per-device setting, so a per-process "already set" flag is wrong once a process drives several devices.
+// (callers refuse what exceeds the CU's 160 KiB themselves, before anything is launched)
+template <typename... P, typename... A>
+inline int launch_lds(void (*kern)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t st, A... args) {
+    if (lds > 64 * 1024) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) { set_last_hip_error(e); return HSP_ERR_LAUNCH; }
+    }
+    hipLaunchKernelGGL(kern, grid, block, lds, st, args...);
+    return check_launch();
+}
+
 // knn.hip -> knn_exact.hip: the xyz search by (distance, index) plus per-row flags: bit 0 "two of the k + drop + 1 nearest are equally
 // far", bit 1 the same for the k2 + drop + 1 nearest
 // (idx2 (B,N,k2), may be null: the first k2 entries of every list again -- the short list of every unflagged row)

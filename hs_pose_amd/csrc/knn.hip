@@ -9,9 +9,10 @@
 //            feature-space tiles reproduce torch.bmm bit for bit; the xyz path spells it out.
 //   quad   = ATen row-sum order (quad_kernel below), dist = ((inner*-2)+quad[j])+quad[i]
 //   select = ascending (distance, index); strict '<' keeps the lower index on exact ties.
-#include "common.h"
+#include "knn_common.h"
 #include "tie_pass.h"
 #include <float.h>
+#include <type_traits>
 
 namespace hsp {
 
@@ -127,6 +128,21 @@ __device__ __forceinline__ void merge_write(const int2* __restrict__ lists, int 
     if (tie_row && valid && sub == 0) *tie_row = (tie ? 1 : 0) | (tie2 ? 2 : 0);
 }
 
+// rows [0, n) of a cloud into LDS as (x, y, z, |p|^2), by a workgroup of `block` threads (the caller owns the barriers).
+// (knn3_kernel stages its chunks with a loop of its own: through this helper its 27 instances came out with 4 VGPRs more)
+// sel / sel_outer (may be null): row j is row sel[j] of the level it was drawn from, which is row sel_outer[.] of the cloud xb;
+// vout (may be null): the rows' coordinates are also written out (the level's vertices).
+__device__ __forceinline__ void stage_cloud(float4* pts, const float* __restrict__ xb, const int32_t* __restrict__ sel,
+                                            const int32_t* __restrict__ sel_outer, float* __restrict__ vout, int n, int block) {
+    for (int j = threadIdx.x; j < n; j += block) {
+        int r = sel ? sel[j] : j;
+        r = sel_outer ? sel_outer[r] : r;
+        const float px = xb[r * 3 + 0], py = xb[r * 3 + 1], pz = xb[r * 3 + 2];
+        pts[j] = make_float4(px, py, pz, quad3(px, py, pz));
+        if (vout) { vout[j * 3] = px; vout[j * 3 + 1] = py; vout[j * 3 + 2] = pz; }
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // xyz path (C == 3): the cloud (x,y,z,|p|^2) sits in LDS; T lanes share one query, each scanning
 // every T-th candidate (one broadcast ds_read_b128 per candidate); lists are merged by tournament.
@@ -166,7 +182,7 @@ __global__ __launch_bounds__(256) void knn3_kernel(const float* __restrict__ x, 
             for (int j = t; j < cn; j += T) {
                 const float4 c = pts[j];
                 const float inner = dot3_chain(qx, qy, qz, c.x, c.y, c.z);
-                const float d = add_rn(add_rn(mul_rn(inner, -2.0f), c.w), qq);
+                const float d = dist_expand(inner, c.w, qq);
                 top.insert(d, c0 + j);
             }
         }
@@ -183,6 +199,33 @@ __global__ __launch_bounds__(256) void knn3_kernel(const float* __restrict__ x, 
 __device__ __forceinline__ unsigned sortable_key(float f) {
     const unsigned u = __float_as_uint(f);
     return u ^ ((u >> 31) ? 0xffffffffu : 0x80000000u);
+}
+
+// The pruning bound of the wave-per-query selections: tau[u] >= the ms-th smallest of the 64 lane minima lmin[u] of query u, so ms
+// distinct candidates are <= tau[u] and everything above it is out.  Radix select over ballots, most significant key bit first.
+// (the bound only has to be >= the ms-th smallest minimum: the descent stops after the sign, the exponent and five mantissa
+// bits and fills the rest with ones -- tau up to 3 % high, a survivor or two more for the ranking, 18 ballot rounds fewer)
+// The descent is a chain of vector-compare -> scalar-count -> scalar-select steps that waits on itself: NQ = 2 queries side by side
+// are two independent chains that interleave and take about the time of one.
+template <int NQ>
+__device__ __forceinline__ void wave_radix_bound(const float (&lmin)[NQ], int ms, float (&tau)[NQ]) {
+    unsigned key[NQ], prefix[NQ];
+    int need[NQ];
+#pragma unroll
+    for (int u = 0; u < NQ; ++u) { key[u] = sortable_key(lmin[u]); prefix[u] = 0; need[u] = ms; }
+    for (int bit = 31; bit >= KNN_TAU_LOW_BIT; --bit) {
+#pragma unroll
+        for (int u = 0; u < NQ; ++u) {
+            const bool zero = (key[u] ^ prefix[u]) < (1u << bit);    // bits 31..bit+1 equal the prefix (whose lower bits are 0), bit `bit` is 0
+            const int c0 = __popcll(__ballot(zero));
+            if (need[u] > c0) { need[u] -= c0; prefix[u] |= 1u << bit; }
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < NQ; ++u) {
+        const unsigned pf = prefix[u] | ((1u << KNN_TAU_LOW_BIT) - 1u);
+        tau[u] = __uint_as_float(pf ^ ((pf >> 31) ? 0x80000000u : 0xffffffffu));   // key -> float
+    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -220,13 +263,7 @@ __device__ __forceinline__ void knn3_wave_body(char* smem, const float* __restri
     // does (54.7 vs 33.8 + 20.6 us) and a tiled cloud 3x slower (994 vs 335 us: the workgroup's waves queue on the lock).
     char* tie_mem = reinterpret_cast<char*>(reinterpret_cast<float*>(reinterpret_cast<int2*>(pts + N) + 4 * KNN3W_SV) + 4 * 64);
     TkE* tq = reinterpret_cast<TkE*>(tie_mem + (size_t)wave * 16 * N);
-    for (int j = tid; j < N; j += 256) {
-        int r = sel ? sel[j] : j;                             // row j of this level = row sel[j] of the level it was drawn from,
-        r = sel_outer ? sel_outer[r] : r;                     // which is row sel_outer[.] of the cloud xb
-        const float px = xb[r * 3 + 0], py = xb[r * 3 + 1], pz = xb[r * 3 + 2];
-        pts[j] = make_float4(px, py, pz, quad3(px, py, pz));
-        if (vout && qblock == 0) { vout[j * 3] = px; vout[j * 3 + 1] = py; vout[j * 3 + 2] = pz; }   // the level's vertices
-    }
+    stage_cloud(pts, xb, sel, sel_outer, qblock == 0 ? vout : nullptr, N, 256);
     __syncthreads();
     const int m = k + drop;
     const int ms = tie && msel > m ? msel : m;                       // ranks looked at
@@ -235,33 +272,21 @@ __device__ __forceinline__ void knn3_wave_body(char* smem, const float* __restri
         if (q >= N) break;
         const float4 qp = pts[q];
         float d[S];
-        float lmin = INFINITY;
+        float lmin[1] = {INFINITY}, tau[1];
 #pragma unroll
         for (int s = 0; s < S; ++s) {
             const int j = lane + 64 * s;
             const float4 c = pts[j < N ? j : N - 1];
             const float inner = dot3_chain(qp.x, qp.y, qp.z, c.x, c.y, c.z);
-            const float dv = add_rn(add_rn(mul_rn(inner, -2.0f), c.w), qp.w);
+            const float dv = dist_expand(inner, c.w, qp.w);
             d[s] = j < N ? fminf(dv, FLT_MAX) : INFINITY;       // NaN / +inf of a real row -> FLT_MAX: still selectable, so
-            lmin = fminf(lmin, d[s]);                           // every output slot is written with a valid index
+            lmin[0] = fminf(lmin[0], d[s]);                     // every output slot is written with a valid index
         }
-        // the ms-th smallest of the 64 lane minima: ms distinct candidates are <= tau
-        const unsigned key = sortable_key(lmin);
-        unsigned prefix = 0;
-        int need = ms;
-        // (the bound only has to be >= the ms-th smallest minimum: the descent stops after the sign, the exponent and five mantissa
-        // bits and fills the rest with ones -- tau up to 3 % high, a survivor or two more for the ranking, 18 ballot rounds fewer)
-        for (int bit = 31; bit >= KNN_TAU_LOW_BIT; --bit) {
-            const bool zero = (key ^ prefix) < (1u << bit);       // bits 31..bit+1 equal the prefix (whose lower bits are 0), bit `bit` is 0
-            const int c0 = __popcll(__ballot(zero));
-            if (need > c0) { need -= c0; prefix |= 1u << bit; }
-        }
-        prefix |= (1u << KNN_TAU_LOW_BIT) - 1u;
-        const float tau = __uint_as_float(prefix ^ ((prefix >> 31) ? 0x80000000u : 0xffffffffu));
+        wave_radix_bound<1>(lmin, ms, tau);
         int n = 0;
 #pragma unroll
         for (int s = 0; s < S; ++s) {
-            const bool keep = d[s] <= tau;                    // +inf padding never passes a finite tau
+            const bool keep = d[s] <= tau[0];                 // +inf padding never passes a finite tau
             const unsigned long long bal = __ballot(keep);
             if (bal == 0ull) continue;                        // (wave-uniform: most slots of a dense cloud hold no survivor)
             const int pos = n + __popcll(bal & ((1ull << lane) - 1ull));
@@ -515,26 +540,16 @@ __device__ __forceinline__ void knn_select_wave(const float* dl, int2* sv, int N
     const int lane = threadIdx.x & 63;
     const int m = k + drop;
     const int ms = tie && m + 1 <= N ? m + 1 : m;
-    float lmin = INFINITY;
+    float lmin[1] = {INFINITY}, tau[1];
     // real rows with a NaN / +inf distance count as FLT_MAX (ties by index): m valid candidates always exist, every
     // output slot is written (see merge_write)
-    for (int j = lane; j < N; j += 64) lmin = fminf(lmin, fminf(dl[j], FLT_MAX));
-    // radix select, most significant bit first: the m-th smallest of the 64 keys
-    const unsigned key = sortable_key(lmin);
-    unsigned prefix = 0;
-    int need = ms;
-    for (int bit = 31; bit >= KNN_TAU_LOW_BIT; --bit) {     // (a bound, not the exact value: see knn3_wave_body)
-        const bool zero = (key ^ prefix) < (1u << bit);
-        const int c0 = __popcll(__ballot(zero));
-        if (need > c0) { need -= c0; prefix |= 1u << bit; }
-    }
-    prefix |= (1u << KNN_TAU_LOW_BIT) - 1u;
-    const float tau = __uint_as_float(prefix ^ ((prefix >> 31) ? 0x80000000u : 0xffffffffu));   // key -> float
+    for (int j = lane; j < N; j += 64) lmin[0] = fminf(lmin[0], fminf(dl[j], FLT_MAX));
+    wave_radix_bound<1>(lmin, ms, tau);          // (a bound on, not the exact value of, the ms-th smallest of the 64 minima)
     int n = 0;
     for (int j0 = 0; j0 < N; j0 += 64) {
         const int j = j0 + lane;
         const float d = j < N ? fminf(dl[j], FLT_MAX) : INFINITY;
-        const bool keep = j < N && d <= tau;
+        const bool keep = j < N && d <= tau[0];
         const unsigned long long bal = __ballot(keep);
         if (keep) sv[n + __popcll(bal & ((1ull << lane) - 1ull))] = make_int2(__float_as_int(d), j);
         n += __popcll(bal);
@@ -568,9 +583,8 @@ __device__ __forceinline__ void knn_select_wave(const float* dl, int2* sv, int N
 // The same selection with the candidates' distances in REGISTERS (S per lane, N <= 64 S) and the survivors ranked lane-against-lane:
 // knn_select_wave walks the survivor list in LDS once per survivor (a dependent ds_read per step: ~100 clocks x ~28 survivors, and
 // ~10 000 clocks a query measured with nine waves selecting side by side); here lane e holds survivor e and the list is broadcast
-// from registers (v_readlane_b32 with a scalar index: no memory round trip), one 64-bit compare per pair.  The radix descent is a
-// chain of vector-compare -> scalar-count -> scalar-select steps that waits on itself, so a wave runs NQ (1 or 2) queries through it
-// side by side: two independent chains interleave and take about the time of one.  Same bound, same (distance, index) ranks,
+// from registers (v_readlane_b32 with a scalar index: no memory round trip), one 64-bit compare per pair.  A wave runs NQ (1 or 2)
+// queries through the radix descent side by side (wave_radix_bound).  Same bound, same (distance, index) ranks,
 // same tie flag as knn_select_wave; more than 64 survivors (heavily duplicated rows) fall back on it.
 // dl[u], out[u], tie[u]: query u's distances / output row / flag byte; sv: max(64 * NQ, N) int2 of scratch.
 template <int S, int NQ, bool TIE>
@@ -580,41 +594,27 @@ __device__ __forceinline__ void knn_select_wave_regs(const float* const (&dl)[NQ
     const int m = k + drop;
     const int ms = TIE && m + 1 <= N ? m + 1 : m;
     float v[NQ][S];
-    unsigned key[NQ];
+    float lmin[NQ], tau[NQ];
 #pragma unroll
     for (int u = 0; u < NQ; ++u) {
-        float lmin = INFINITY;
+        lmin[u] = INFINITY;
 #pragma unroll
         for (int s_ = 0; s_ < S; ++s_) {
             const int j = lane + 64 * s_;
             const float raw = dl[u][j < N ? j : N - 1];               // (clamped address: all S loads of both queries in flight together)
             // NaN / +inf of a real row -> FLT_MAX (see knn_select_wave); -0.0 -> +0.0 (equal as floats, not as key bits)
             v[u][s_] = j < N ? add_rn(fminf(raw, FLT_MAX), 0.0f) : INFINITY;
-            lmin = fminf(lmin, v[u][s_]);
-        }
-        key[u] = sortable_key(lmin);
-    }
-    unsigned prefix[NQ];
-    int need[NQ];
-#pragma unroll
-    for (int u = 0; u < NQ; ++u) { prefix[u] = 0; need[u] = ms; }
-    for (int bit = 31; bit >= KNN_TAU_LOW_BIT; --bit) {
-#pragma unroll
-        for (int u = 0; u < NQ; ++u) {
-            const bool zero = (key[u] ^ prefix[u]) < (1u << bit);    // bits 31..bit+1 equal the prefix and bit `bit` is 0
-            const int c0 = __popcll(__ballot(zero));
-            if (need[u] > c0) { need[u] -= c0; prefix[u] |= 1u << bit; }
+            lmin[u] = fminf(lmin[u], v[u][s_]);
         }
     }
+    wave_radix_bound<NQ>(lmin, ms, tau);
     int n[NQ];
 #pragma unroll
     for (int u = 0; u < NQ; ++u) {
-        const unsigned pf = prefix[u] | ((1u << KNN_TAU_LOW_BIT) - 1u);
-        const float tau = __uint_as_float(pf ^ ((pf >> 31) ? 0x80000000u : 0xffffffffu));
         n[u] = 0;
 #pragma unroll
         for (int s_ = 0; s_ < S; ++s_) {
-            const bool keep = v[u][s_] <= tau;                    // +inf padding never passes a finite tau
+            const bool keep = v[u][s_] <= tau[u];                 // +inf padding never passes a finite tau
             const unsigned long long bal = __ballot(keep);
             const int pos = n[u] + __popcll(bal & ((1ull << lane) - 1ull));
             if (keep && pos < 64) sv[u * 64 + pos] = make_int2(__float_as_int(v[u][s_]), lane + 64 * s_);
@@ -716,35 +716,13 @@ __device__ __forceinline__ void knn_feat_tail_body(char* smem, const float* __re
     const float qn = quadb[q];
     for (int j0 = tid; j0 < N; j0 += 4 * 256) {
         // four candidates per pass (clamped rows: a clamped duplicate is discarded below), independent chains
-        const int j1 = j0 + 256, j2 = j0 + 512, j3 = j0 + 768;
-        const float* r0 = xb + (size_t)j0 * C;
-        const float* r1 = xb + (size_t)min(j1, N - 1) * C;
-        const float* r2 = xb + (size_t)min(j2, N - 1) * C;
-        const float* r3 = xb + (size_t)min(j3, N - 1) * C;
-        float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-        int c = 0;
-        for (; c + 3 < C; c += 4) {                         // 16-byte row segments (C % 4 == 0 keeps them aligned)
-            const float4 qv = *reinterpret_cast<const float4*>(sq + c);
-            const float4 v0 = *reinterpret_cast<const float4*>(r0 + c);
-            const float4 v1 = *reinterpret_cast<const float4*>(r1 + c);
-            const float4 v2 = *reinterpret_cast<const float4*>(r2 + c);
-            const float4 v3 = *reinterpret_cast<const float4*>(r3 + c);
-            a0 = __fmaf_rn(qv.w, v0.w, __fmaf_rn(qv.z, v0.z, __fmaf_rn(qv.y, v0.y, __fmaf_rn(qv.x, v0.x, a0))));
-            a1 = __fmaf_rn(qv.w, v1.w, __fmaf_rn(qv.z, v1.z, __fmaf_rn(qv.y, v1.y, __fmaf_rn(qv.x, v1.x, a1))));
-            a2 = __fmaf_rn(qv.w, v2.w, __fmaf_rn(qv.z, v2.z, __fmaf_rn(qv.y, v2.y, __fmaf_rn(qv.x, v2.x, a2))));
-            a3 = __fmaf_rn(qv.w, v3.w, __fmaf_rn(qv.z, v3.z, __fmaf_rn(qv.y, v3.y, __fmaf_rn(qv.x, v3.x, a3))));
-        }
-        for (; c < C; ++c) {
-            const float qc = sq[c];
-            a0 = __fmaf_rn(qc, r0[c], a0);
-            a1 = __fmaf_rn(qc, r1[c], a1);
-            a2 = __fmaf_rn(qc, r2[c], a2);
-            a3 = __fmaf_rn(qc, r3[c], a3);
-        }
-        dl[j0] = add_rn(add_rn(mul_rn(a0, -2.0f), quadb[j0]), qn);
-        if (j1 < N) dl[j1] = add_rn(add_rn(mul_rn(a1, -2.0f), quadb[j1]), qn);
-        if (j2 < N) dl[j2] = add_rn(add_rn(mul_rn(a2, -2.0f), quadb[j2]), qn);
-        if (j3 < N) dl[j3] = add_rn(add_rn(mul_rn(a3, -2.0f), quadb[j3]), qn);
+        const float* const r[4] = {xb + (size_t)j0 * C, xb + (size_t)min(j0 + 256, N - 1) * C, xb + (size_t)min(j0 + 512, N - 1) * C,
+                                   xb + (size_t)min(j0 + 768, N - 1) * C};
+        float a[4] = {0.f, 0.f, 0.f, 0.f};
+        chain4_rows(sq, r, C & ~3, C, a);                   // 16-byte row segments: knn_feat_rem_mode sends only C % 4 == 0 here
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+            if (j0 + 256 * u < N) dl[j0 + 256 * u] = dist_expand(a[u], quadb[j0 + 256 * u], qn);
     }
     __syncthreads();
     if (dmat) for (int j = tid; j < N; j += 256) dmat[((size_t)b * N + j) * N + q] = dl[j];
@@ -799,7 +777,7 @@ __global__ __launch_bounds__(256) void knn_feat_sym_tail_kernel(const float* __r
         const float* rc = rows + (size_t)(1 + lane) * C;
         float a = 0.f;
         for (int c = 0; c < C; ++c) a = __fmaf_rn(rows[c], rc[c], a);
-        dl[nfull + lane] = add_rn(add_rn(mul_rn(a, -2.0f), quadb[nfull + lane]), quadb[q]);
+        dl[nfull + lane] = dist_expand(a, quadb[nfull + lane], quadb[q]);
     }
     __builtin_amdgcn_wave_barrier();
     if (dmat) for (int j = lane; j < N; j += 64) dmat[((size_t)b * N + j) * N + q] = dl[j];
@@ -819,6 +797,47 @@ __global__ __launch_bounds__(256) void knn_feat_sym_tail_kernel(const float* __r
 // grid (ceil(N/32), B), block 256.
 // ------------------------------------------------------------------------------------------------
 #define KF_CT_STRIDE 68   // candidate chunk row stride in floats (64 + 4: 16B aligned, odd # of 16B slots)
+
+// A finished 32 x 32 tile folded into this lane's list (knn_feat_kernel, knn_feat_bf16_kernel): the 16 distances of the lane (rows
+// ascend with r; qc: |c|^2 of the tile's rows 4 h .. as staged, +inf past N) go to the wave's stash (16 x 64 floats) and acc is
+// zeroed.  A candidate can only matter if d <= thr (the shared bound and this list's worst); the survivors (few once the lists
+// have warmed up) are inserted by a drain loop that runs max-over-lanes(#survivors) times instead of once per candidate.
+// between(): runs once the stash is complete, before the drain (the fp32 kernel's distance-matrix store).  c0: candidate of r = 0.
+template <int K1, typename Between>
+__device__ __forceinline__ void kf_fold_tile(f32x16& acc, const float* qc_rows, float qq, float thr, float* stash, int lane, int c0,
+                                             TopList<K1>& top, Between&& between) {
+    unsigned m = 0;
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        const float4 qc = *reinterpret_cast<const float4*>(qc_rows + 8 * g);
+        const float qcv[4] = {qc.x, qc.y, qc.z, qc.w};
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int r = 4 * g + u;
+            const float d = dist_expand(acc[r], qcv[u], qq);   // +inf past N
+            stash[r * 64 + lane] = d;
+            m |= d <= thr ? (1u << r) : 0u;          // conservative: insert() re-checks d < worst
+            acc[r] = 0.f;
+        }
+    }
+    __builtin_amdgcn_wave_barrier();
+    between();
+    // software-pipelined: the next survivor is fetched from the stash while the current one is inserted
+    bool has = m != 0;
+    int r = has ? __builtin_ctz(m) : 0;              // ascending r == ascending candidate index
+    m &= m - 1;                                      // 0 stays 0
+    float v = stash[r * 64 + lane];
+#pragma unroll
+    for (int it = 0; it < 16; ++it) {                // wave-uniform early-out, straight-line bodies
+        if (!__any(has)) break;
+        const bool has_n = m != 0;
+        const int r_n = has_n ? __builtin_ctz(m) : 0;
+        m &= m - 1;
+        const float v_n = stash[r_n * 64 + lane];
+        top.insert_always(has ? v : INFINITY, c0 + (r & 3) + 8 * (r >> 2));
+        has = has_n; r = r_n; v = v_n;
+    }
+}
 
 // FULLK: C is a multiple of 64 (every shape of the HS stack).  Candidate chunks are then fetched with raw
 // buffer loads: one descriptor per cloud, a loop-invariant per-lane voffset and a scalar soffset per
@@ -966,10 +985,7 @@ __global__ __launch_bounds__(256, 3) void knn_feat_kernel(const float* __restric
         __builtin_amdgcn_wave_barrier();
 
         if (chunk == nchunks - 1) {
-            // tile finished: fold the 16 distances of this lane into its list (rows ascend with r).
-            // A candidate can only matter if d <= tau_q, the shared bound below, and d < this list's worst;
-            // the survivors (few once the lists have warmed up) are inserted by a drain loop that runs
-            // max-over-lanes(#survivors) times instead of once per candidate.
+            // tile finished: fold the 16 distances of this lane into its list (kf_fold_tile), against tau_q, the shared bound below
             qsm[col] = tile * 32 + col < N ? __uint_as_float(qraw) : INFINITY;   // both halves: same value
             __builtin_amdgcn_wave_barrier();
             if (dtail && tile == ntiles - 1) {
@@ -983,7 +999,7 @@ __global__ __launch_bounds__(256, 3) void knn_feat_kernel(const float* __restric
                     for (int u = 0; u < 4; ++u)
                         if (h * 4 + u < rem)
                             dtail[((size_t)b * rem + h * 4 + u) * nfull + q] =
-                                add_rn(add_rn(mul_rn(acc[u], -2.0f), qq), qcv[u]);
+                                dist_expand(acc[u], qq, qcv[u]);
                 }
             }
             float thr = top.d[K1 - 1];
@@ -995,44 +1011,16 @@ __global__ __launch_bounds__(256, 3) void knn_feat_kernel(const float* __restric
                 thr = fminf(thr, tau);
             }
             float* stash = ctile;                           // the chunk is consumed: 16 x 64 floats fit
-            unsigned m = 0;
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const float4 qc = *reinterpret_cast<const float4*>(qsm + 8 * g + 4 * h);
-                const float qcv[4] = {qc.x, qc.y, qc.z, qc.w};
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const int r = 4 * g + u;
-                    const float d = add_rn(add_rn(mul_rn(acc[r], -2.0f), qcv[u]), qq);   // +inf past N
-                    stash[r * 64 + lane] = d;
-                    m |= d <= thr ? (1u << r) : 0u;          // conservative: insert() re-checks d < worst
-                    acc[r] = 0.f;
-                }
-            }
-            __builtin_amdgcn_wave_barrier();
             const int c0 = tile * 32 + 4 * h;
-            if (dmat && qvalid) {                           // (exact scope, small batches) the distance matrix, [candidate][query]:
+            kf_fold_tile(acc, qsm + 4 * h, qq, thr, stash, lane, c0, top, [&] {
+                if (dmat && qvalid) {                       // (exact scope, small batches) the distance matrix, [candidate][query]:
 #pragma unroll
-                for (int r = 0; r < 16; ++r) {              // 32 queries = 128 contiguous bytes per store
-                    const int cand = c0 + (r & 3) + 8 * (r >> 2);
-                    if (cand < N) dmat[((size_t)b * N + cand) * N + q] = stash[r * 64 + lane];
+                    for (int r = 0; r < 16; ++r) {          // 32 queries = 128 contiguous bytes per store
+                        const int cand = c0 + (r & 3) + 8 * (r >> 2);
+                        if (cand < N) dmat[((size_t)b * N + cand) * N + q] = stash[r * 64 + lane];
+                    }
                 }
-            }
-            // software-pipelined: the next survivor is fetched from the stash while the current one is inserted
-            bool has = m != 0;
-            int r = has ? __builtin_ctz(m) : 0;              // ascending r == ascending candidate index
-            m &= m - 1;                                      // 0 stays 0
-            float v = stash[r * 64 + lane];
-#pragma unroll
-            for (int it = 0; it < 16; ++it) {                // wave-uniform early-out, straight-line bodies
-                if (!__any(has)) break;
-                const bool has_n = m != 0;
-                const int r_n = has_n ? __builtin_ctz(m) : 0;
-                m &= m - 1;
-                const float v_n = stash[r_n * 64 + lane];
-                top.insert_always(has ? v : INFINITY, c0 + (r & 3) + 8 * (r >> 2));
-                has = has_n; r = r_n; v = v_n;
-            }
+            });
             if (SHARE) pub[col * 8 + wave * 2 + h] = (wave * 2 + h < (K1 & 7)) ? top.d[A_HI] : top.d[A_LO];
             __builtin_amdgcn_wave_barrier();
         }
@@ -1187,14 +1175,14 @@ __global__ __launch_bounds__(640) void knn_feat_small_kernel(const float* __rest
                 }
             }
 #pragma unroll
-            for (int g = 0; g < 8; ++g) {
-                const float4 a4 = *reinterpret_cast<const float4*>(arow + 4 * g);
-                const float4 b4 = *reinterpret_cast<const float4*>(brow + 4 * g);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.x, b4.x, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.y, b4.y, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.z, b4.z, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.w, b4.w, acc, 0, 0, 0);
-            }
+        for (int g = 0; g < 8; ++g) {
+            const float4 a4 = *reinterpret_cast<const float4*>(arow + 4 * g);
+            const float4 b4 = *reinterpret_cast<const float4*>(brow + 4 * g);
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.x, b4.x, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.y, b4.y, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.z, b4.z, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.w, b4.w, acc, 0, 0, 0);
+        }
             __builtin_amdgcn_wave_barrier();
         }
         KNN_STAMP(2);
@@ -1283,7 +1271,7 @@ __global__ __launch_bounds__(640) void knn_feat_small_kernel(const float* __rest
                 const float qcv[4] = {qc.x, qc.y, qc.z, qc.w};
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
-                    const float d = add_rn(add_rn(mul_rn(acc[4 * g + u], -2.0f), qcv[u]), qq);
+                    const float d = dist_expand(acc[4 * g + u], qcv[u], qq);
                     drow[8 * g + u] = d;                                                  // (rows past N: +inf, never read)
                     if (mrow && wave * 32 + 8 * g + 4 * h + u < N) mrow[(size_t)(8 * g + u) * N] = d;
                 }
@@ -1295,7 +1283,7 @@ __global__ __launch_bounds__(640) void knn_feat_small_kernel(const float* __rest
             for (int r = 0; r < 16; ++r) {
                 const int q = wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
                 if (q >= q0 && q < q0 + QT) {
-                    const float d = add_rn(add_rn(mul_rn(acc[r], -2.0f), qcand), quadl[q]);
+                    const float d = dist_expand(acc[r], qcand, quadl[q]);
                     dl[(q - q0) * DS + c] = d;
                     if (dmat) dmat[((size_t)b * N + c) * N + q] = d;
                 }
@@ -1305,7 +1293,7 @@ __global__ __launch_bounds__(640) void knn_feat_small_kernel(const float* __rest
         const int tq = lane / rem, tc = lane - tq * rem;
         const int q = mtiles * 32 + tq, c = mtiles * 32 + tc;
         if (tq < rem && q >= q0 && q < q0 + QT) {
-            const float d = add_rn(add_rn(mul_rn(ra, -2.0f), quadl[c]), quadl[q]);
+            const float d = dist_expand(ra, quadl[c], quadl[q]);
             dl[(q - q0) * DS + c] = d;
             if (dmat) dmat[((size_t)b * N + c) * N + q] = d;
         }
@@ -1342,16 +1330,14 @@ __global__ __launch_bounds__(640) void knn_feat_small_kernel(const float* __rest
 // top-1 nearest source row per target row (C == 3); d = (s2[j] + t2[i]) - 2*inner   (gcn3d.py:34)
 // grid (ceil(Nt/256), B), block 256, dynamic LDS = Ns*16
 // ------------------------------------------------------------------------------------------------
+// get_nearest_index's own order (gcn3d.py:34), not a variant of dist_expand: (|s|^2 + |t|^2) - 2 * inner
+__device__ __forceinline__ float nn1_dist(float inner, float s2, float t2) { return sub_rn(add_rn(s2, t2), mul_rn(2.0f, inner)); }
+
 __device__ __forceinline__ void nn1_body(char* smem, const float* __restrict__ tb, int Nt, const float* __restrict__ sb,
                                          const int32_t* __restrict__ sel, const int32_t* __restrict__ sel_outer, int Ns,
                                          int32_t* __restrict__ idx_b, int tblock) {
     float4* pts = reinterpret_cast<float4*>(smem);
-    for (int j = threadIdx.x; j < Ns; j += 256) {
-        int r = sel ? sel[j] : j;                                  // (source row j as a row of the cloud sb: see knn3_wave_body)
-        r = sel_outer ? sel_outer[r] : r;
-        const float px = sb[r * 3], py = sb[r * 3 + 1], pz = sb[r * 3 + 2];
-        pts[j] = make_float4(px, py, pz, quad3(px, py, pz));
-    }
+    stage_cloud(pts, sb, sel, sel_outer, nullptr, Ns, 256);      // (source row j as a row of the cloud sb: see knn3_wave_body)
     __syncthreads();
     const int i = tblock * 256 + threadIdx.x;
     if (i >= Nt) return;
@@ -1363,7 +1349,7 @@ __device__ __forceinline__ void nn1_body(char* smem, const float* __restrict__ t
     for (int j = 0; j < Ns; ++j) {
         const float4 c = pts[j];
         const float inner = dot3_chain(tx, ty, tz, c.x, c.y, c.z);
-        const float d = sub_rn(add_rn(c.w, t2), mul_rn(2.0f, inner));
+        const float d = nn1_dist(inner, c.w, t2);
         if (j == 0 || d < best) { best = d; bi = j; }
     }
     idx_b[i] = bi;
@@ -1457,21 +1443,32 @@ static int pick_k1(int m) {
     return 0;
 }
 
+// one launch per list length: f receives pick_k1's value as std::integral_constant<int, K1>
+template <typename F>
+static int dispatch_k1(int K1, F&& f) {
+    switch (K1) {
+        case 3: return f(std::integral_constant<int, 3>{});
+        case 5: return f(std::integral_constant<int, 5>{});
+        case 6: return f(std::integral_constant<int, 6>{});
+        case 9: return f(std::integral_constant<int, 9>{});
+        case 10: return f(std::integral_constant<int, 10>{});
+        case 17: return f(std::integral_constant<int, 17>{});
+        case 21: return f(std::integral_constant<int, 21>{});
+        case 22: return f(std::integral_constant<int, 22>{});
+        case 33: return f(std::integral_constant<int, 33>{});
+        default: return HSP_ERR_UNSUPPORTED;
+    }
+}
+
 template <int K1, int T>
 static int launch_knn3(const float* x, int B, int N, int k, int drop, int32_t* idx, hipStream_t st, int msel, uint8_t* tie,
                        int msel2, int32_t* idx2, int k2) {
     const int chunk = N < 4096 ? N : 4096;
     size_t lds = (size_t)chunk * 16;
     if (lds < (size_t)256 * K1 * 8) lds = (size_t)256 * K1 * 8;
-    auto kern = knn3_kernel<K1, T>;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) { set_last_hip_error(e); return HSP_ERR_LAUNCH; }
-    }
     constexpr int Q = 256 / T;
-    dim3 grid((N + Q - 1) / Q, B);
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, x, N, k, drop, idx, chunk, msel, tie, msel2, idx2, k2);
-    return check_launch();
+    return launch_lds(knn3_kernel<K1, T>, dim3((N + Q - 1) / Q, B), dim3(256), lds, st, x, N, k, drop, idx, chunk, msel, tie, msel2, idx2,
+                      k2);
 }
 
 // small clouds replay their flagged rows inside the selection kernel; larger ones keep the separate pass (see knn3_wave_kernel)
@@ -1483,17 +1480,11 @@ static int launch_knn3_wave(const float* x, int B, int N, int k, int drop, int32
     const int tie_inline = tie ? knn3_wave_tie_inline(N) : 0;
     const size_t lds = (size_t)N * 16 + (size_t)4 * KNN3W_SV * 8 + 4 * 64 * 4 +
                        (tie_inline ? (size_t)16 * N * 4 : 0);
-    auto kern = knn3_wave_kernel<S>;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) { set_last_hip_error(e); return HSP_ERR_LAUNCH; }
-    }
     // queries per wave: four amortise the cloud's staging; a small batch (the coarse levels) takes one so that its few thousand
     // queries spread over the chip instead of queueing four deep behind 272 workgroups
     const int QW = (long long)B * N >= 8192 ? KNN3W_QW : 1;
-    hipLaunchKernelGGL(kern, dim3((N + 4 * QW - 1) / (4 * QW), B), dim3(256), lds, st, x, N, k, drop, idx, msel, tie, msel2, idx2, k2,
-                       tie_inline, QW);
-    return check_launch();
+    return launch_lds(knn3_wave_kernel<S>, dim3((N + 4 * QW - 1) / (4 * QW), B), dim3(256), lds, st, x, N, k, drop, idx, msel, tie, msel2,
+                      idx2, k2, tie_inline, QW);
 }
 
 template <int K1>
@@ -1562,18 +1553,12 @@ static int knn_feat_small_qt(int B, int N, int C) {           // 0: not this ker
 static int launch_knn_feat_small(int QT, const float* x, const float* quad_in, float* quad_out, int B, int N, int C, int k, int drop,
                                  int32_t* idx, hipStream_t st, uint8_t* tie, float* dmat) {
     const size_t lds = knn_feat_small_lds(N, C, QT);
-    auto kern = knn_feat_small_kernel;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) { set_last_hip_error(e); return HSP_ERR_LAUNCH; }
-    }
     const int ntiles = (N + 31) / 32;
     const int rem = N & 31;
     const int mtiles = (rem > 0 && rem <= 4) ? N / 32 : ntiles;      // MFMA tiles; a short remainder goes to one wave's fma chains
     const int nw = ntiles > 8 ? ntiles : 8;
-    hipLaunchKernelGGL(kern, dim3((N + QT - 1) / QT, B), dim3(64 * nw), lds, st, x, quad_in, quad_out, N, C, k, drop, idx, tie, dmat,
-                       mtiles, QT);
-    return check_launch();
+    return launch_lds(knn_feat_small_kernel, dim3((N + QT - 1) / QT, B), dim3(64 * nw), lds, st, x, quad_in, quad_out, N, C, k, drop, idx,
+                      tie, dmat, mtiles, QT);
 }
 
 template <int K1>
@@ -1585,25 +1570,14 @@ static int launch_knn_feat(const float* x, const float* quad, float* dtail, int 
     const int mode = knn_feat_rem_mode(B, N, C);
     const int rem = mode == KF_REM_TILE ? 0 : (N & 31);
     const int full_tiles = (N - rem + 31) / 32;
-    if (lds > 64 * 1024) {
-        if (lds > 160 * 1024) return HSP_ERR_UNSUPPORTED;
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) { set_last_hip_error(e); return HSP_ERR_LAUNCH; }
-    }
+    if (lds > 160 * 1024) return HSP_ERR_UNSUPPORTED;
     const int ntail = mode == KF_REM_WG ? rem : 0;
-    hipLaunchKernelGGL(kern, dim3(full_tiles + ntail, B), dim3(256), lds, st, x, quad, N, C, k, drop, idx, full_tiles,
-                       ntail, mode == KF_REM_SYM ? dtail : nullptr, msel, tie, dmat);
-    int rc = check_launch();
+    int rc = launch_lds(kern, dim3(full_tiles + ntail, B), dim3(256), lds, st, x, quad, N, C, k, drop, idx, full_tiles, ntail,
+                        mode == KF_REM_SYM ? dtail : nullptr, msel, tie, dmat);
     if (rc || mode != KF_REM_SYM) return rc;
     const size_t lds_s = (size_t)4 * (12 * ((size_t)N + 3) + (size_t)(1 + rem) * C * 4);
-    if (lds_s > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(knn_feat_sym_tail_kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_s);
-        if (e != hipSuccess) { set_last_hip_error(e); return HSP_ERR_LAUNCH; }
-    }
-    hipLaunchKernelGGL(knn_feat_sym_tail_kernel, dim3((rem + 3) / 4, B), dim3(256), lds_s, st, x, quad, dtail, N, C, k,
-                       drop, N - rem, idx, tie, dmat);
-    return check_launch();
+    return launch_lds(knn_feat_sym_tail_kernel, dim3((rem + 3) / 4, B), dim3(256), lds_s, st, x, quad, dtail, N, C, k, drop, N - rem, idx,
+                      tie, dmat);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1719,36 +1693,7 @@ __global__ __launch_bounds__(256, 2) void knn_feat_bf16_kernel(const bf16_t* __r
         }
         float thr = top.d[K1 - 1];
         if (SHARE) thr = fminf(thr, fmaxf(pub[(wave * 32 + col) * 2], pub[(wave * 32 + col) * 2 + 1]));
-        unsigned m = 0;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const float4 qc = *reinterpret_cast<const float4*>(qsm + buf * 32 + 8 * g + 4 * h);
-            const float qcv[4] = {qc.x, qc.y, qc.z, qc.w};
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int r = 4 * g + u;
-                const float d = add_rn(add_rn(mul_rn(acc[r], -2.0f), qcv[u]), qq);   // +inf past N
-                stash[r * 64 + lane] = d;
-                m |= d <= thr ? (1u << r) : 0u;
-                acc[r] = 0.f;
-            }
-        }
-        __builtin_amdgcn_wave_barrier();
-        const int c0 = tile * 32 + 4 * h;
-        bool has = m != 0;
-        int r = has ? __builtin_ctz(m) : 0;
-        m &= m - 1;
-        float v = stash[r * 64 + lane];
-#pragma unroll
-        for (int it = 0; it < 16; ++it) {
-            if (!__any(has)) break;
-            const bool has_n = m != 0;
-            const int r_n = has_n ? __builtin_ctz(m) : 0;
-            m &= m - 1;
-            const float v_n = stash[r_n * 64 + lane];
-            top.insert_always(has ? v : INFINITY, c0 + (r & 3) + 8 * (r >> 2));
-            has = has_n; r = r_n; v = v_n;
-        }
+        kf_fold_tile(acc, qsm + buf * 32 + 4 * h, qq, thr, stash, lane, tile * 32 + 4 * h, top, [] {});
         if (SHARE) pub[(wave * 32 + col) * 2 + h] = h == 0 ? top.d[A0 - 1] : top.d[A1 > 0 ? A1 - 1 : 0];
         if (tile + 1 < ntiles) stage(buf ^ 1);                   // the other buffer: last read in the previous iteration
         __syncthreads();
@@ -1772,13 +1717,7 @@ static int launch_knn_feat_bf16(const bf16_t* x, const float* quad, int B, int N
     const size_t lds_lists = (size_t)256 * K1 * 8;
     if (lds_lists > lds) lds = lds_lists;
     if (lds > 160 * 1024) return HSP_ERR_UNSUPPORTED;
-    auto kern = knn_feat_bf16_kernel<K1>;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) { set_last_hip_error(e); return HSP_ERR_LAUNCH; }
-    }
-    hipLaunchKernelGGL(kern, dim3((N + 127) / 128, B), dim3(256), lds, st, x, quad, N, C, k, drop, idx);
-    return check_launch();
+    return launch_lds(knn_feat_bf16_kernel<K1>, dim3((N + 127) / 128, B), dim3(256), lds, st, x, quad, N, C, k, drop, idx);
 }
 
 // xyz search of csrc/knn_exact.hip: ranks [drop, k + drop) by (distance, index) into idx (B,N,k) and, per row (tie, B*N bytes),
@@ -1790,18 +1729,7 @@ int knn3_select_flags(const float* x, int B, int N, int k, int drop, int k2, int
     const int m = k + drop;
     const int msel = m + 1 < N ? m + 1 : N;
     const int msel2 = k2 > 0 ? k2 + drop + 1 : 0;              // (k2 < k: inside msel)
-    switch (pick_k1(msel)) {
-        case 3: return launch_knn3_t<3>(x, B, N, k, drop, idx, st, msel, tie, msel2, idx2, k2);
-        case 5: return launch_knn3_t<5>(x, B, N, k, drop, idx, st, msel, tie, msel2, idx2, k2);
-        case 6: return launch_knn3_t<6>(x, B, N, k, drop, idx, st, msel, tie, msel2, idx2, k2);
-        case 9: return launch_knn3_t<9>(x, B, N, k, drop, idx, st, msel, tie, msel2, idx2, k2);
-        case 10: return launch_knn3_t<10>(x, B, N, k, drop, idx, st, msel, tie, msel2, idx2, k2);
-        case 17: return launch_knn3_t<17>(x, B, N, k, drop, idx, st, msel, tie, msel2, idx2, k2);
-        case 21: return launch_knn3_t<21>(x, B, N, k, drop, idx, st, msel, tie, msel2, idx2, k2);
-        case 22: return launch_knn3_t<22>(x, B, N, k, drop, idx, st, msel, tie, msel2, idx2, k2);
-        case 33: return launch_knn3_t<33>(x, B, N, k, drop, idx, st, msel, tie, msel2, idx2, k2);
-        default: return HSP_ERR_UNSUPPORTED;
-    }
+    return dispatch_k1(pick_k1(msel), [&](auto K) { return launch_knn3_t<K()>(x, B, N, k, drop, idx, st, msel, tie, msel2, idx2, k2); });
 }
 
 }  // namespace hsp
@@ -1829,31 +1757,14 @@ extern "C" int hsp_quad_outer_f32(const float* x, int B, int N, int C, float* qu
 // of the k + drop + 1 nearest hold equal distances (csrc/knn_exact.hip replays those rows in torch.topk's order)
 static int knn_f32_impl(const float* x, int B, int N, int C, int k, int drop_first, int32_t* idx, void* ws,
                         size_t ws_bytes, int quad_mode, hspStream_t stream, uint8_t* tie = nullptr, float* dmat = nullptr) {
-    if (!x || !idx || B <= 0 || N <= 0 || C <= 0 || k <= 0) return HSP_ERR_BAD_ARG;
     const int drop = drop_first ? 1 : 0;
+    if (!knn_args_ok(x, idx, B, N, C, k, drop, HSP_MAX_K)) return HSP_ERR_BAD_ARG;
     const int m = k + drop;
-    if (m > N || k > HSP_MAX_K) return HSP_ERR_BAD_ARG;
     const int msel = tie && C != 3 ? (m + 1 < N ? m + 1 : N) : 0;
     const int K1 = pick_k1(msel > m ? msel : m);
     if (!K1) return HSP_ERR_UNSUPPORTED;
     hipStream_t st = as_stream(stream);
-#define HSP_K1_SWITCH(CALL)                                  \
-    switch (K1) {                                            \
-        case 3: return CALL(3);                              \
-        case 5: return CALL(5);                              \
-        case 6: return CALL(6);                              \
-        case 9: return CALL(9);                              \
-        case 10: return CALL(10);                            \
-        case 17: return CALL(17);                            \
-        case 21: return CALL(21);                            \
-        case 22: return CALL(22);                            \
-        default: return CALL(33);                            \
-    }
-    if (C == 3) {
-#define CALL3(K) launch_knn3_t<K>(x, B, N, k, drop, idx, st)
-        HSP_K1_SWITCH(CALL3)
-#undef CALL3
-    }
+    if (C == 3) return dispatch_k1(K1, [&](auto K) { return launch_knn3_t<K()>(x, B, N, k, drop, idx, st); });
     if (hsp_knn_workspace_bytes(B, N, C, k) > ws_bytes || !ws) return HSP_ERR_WORKSPACE;
     float* quad = reinterpret_cast<float*>(ws);
     const long long rows = (long long)B * N;
@@ -1880,10 +1791,7 @@ static int knn_f32_impl(const float* x, int B, int N, int C, int k, int drop_fir
         rc = check_launch();
     }
     if (rc) return rc;
-#define CALLF(K) launch_knn_feat<K>(x, quad, quad + rows, B, N, C, k, drop, idx, st, msel, tie, dmat)
-    HSP_K1_SWITCH(CALLF)
-#undef CALLF
-#undef HSP_K1_SWITCH
+    return dispatch_k1(K1, [&](auto K) { return launch_knn_feat<K()>(x, quad, quad + rows, B, N, C, k, drop, idx, st, msel, tie, dmat); });
 }
 
 extern "C" int hsp_knn_f32(const float* x, int B, int N, int C, int k, int drop_first, int32_t* idx, void* ws,
@@ -1905,10 +1813,9 @@ int knn_feat_select_flags(const float* x, int B, int N, int C, int k, int drop, 
 
 extern "C" int hsp_knn_bf16(const hsp_bf16_t* x, int B, int N, int C, int k, int drop_first, int32_t* idx, void* ws,
                             size_t ws_bytes, hspStream_t stream) {
-    if (!x || !idx || B <= 0 || N <= 0 || C <= 0 || k <= 0) return HSP_ERR_BAD_ARG;
     const int drop = drop_first ? 1 : 0;
+    if (!knn_args_ok(x, idx, B, N, C, k, drop, HSP_MAX_K)) return HSP_ERR_BAD_ARG;
     const int m = k + drop;
-    if (m > N || k > HSP_MAX_K) return HSP_ERR_BAD_ARG;
     if ((C & 31) || (reinterpret_cast<size_t>(x) & 15)) return HSP_ERR_UNSUPPORTED;
     const int K1 = pick_k1(m);
     if (!K1) return HSP_ERR_UNSUPPORTED;
@@ -1919,14 +1826,10 @@ extern "C" int hsp_knn_bf16(const hsp_bf16_t* x, int B, int N, int C, int k, int
     hipLaunchKernelGGL(quad_bf16_kernel, dim3((unsigned)((rows * 8 + 255) / 256)), dim3(256), 0, st, x, rows, C, quad);
     int rc = check_launch();
     if (rc) return rc;
-    switch (K1 == 6 ? 9 : K1 == 10 ? 17 : K1 == 22 ? 33 : K1) {
-        case 3: return launch_knn_feat_bf16<3>(x, quad, B, N, C, k, drop, idx, st);
-        case 5: return launch_knn_feat_bf16<5>(x, quad, B, N, C, k, drop, idx, st);
-        case 9: return launch_knn_feat_bf16<9>(x, quad, B, N, C, k, drop, idx, st);
-        case 17: return launch_knn_feat_bf16<17>(x, quad, B, N, C, k, drop, idx, st);
-        case 21: return launch_knn_feat_bf16<21>(x, quad, B, N, C, k, drop, idx, st);
-        default: return launch_knn_feat_bf16<33>(x, quad, B, N, C, k, drop, idx, st);
-    }
+    return dispatch_k1(K1 == 6 ? 9 : K1 == 10 ? 17 : K1 == 22 ? 33 : K1, [&](auto K) {
+        if constexpr (K() == 6 || K() == 10 || K() == 22) return (int)HSP_ERR_UNSUPPORTED;     // (remapped above: no such bf16 kernels)
+        else return launch_knn_feat_bf16<K()>(x, quad, B, N, C, k, drop, idx, st);
+    });
 }
 
 static int geometry_impl(const float* xyz, int B, int N0, const int32_t* sel1, int N1, const int32_t* sel2, int N2, int k1, int kpool,
@@ -1943,15 +1846,7 @@ static int geometry_impl(const float* xyz, int B, int N0, const int32_t* sel1, i
     if (tie0 && lds < (size_t)4 * 16 * N0) lds = (size_t)4 * 16 * N0;
     if (lds > 160 * 1024) return HSP_ERR_UNSUPPORTED;
     const dim3 grid(a.nbtie + (a.nb1 + a.nb2 + 2 * a.nbt) * B);
-    auto launch = [&](auto kern) {
-        if (lds > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) { set_last_hip_error(e); return HSP_ERR_LAUNCH; }
-        }
-        hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, a);
-        return check_launch();
-    };
-    return Nm <= 64 * 5 ? launch(geometry_levels_kernel<5>) : launch(geometry_levels_kernel<9>);
+    return launch_lds(Nm <= 64 * 5 ? geometry_levels_kernel<5> : geometry_levels_kernel<9>, grid, dim3(256), lds, st, a);
 }
 
 static bool geometry_levels_ok(int N0, int N1, int N2, int k1, int k2, int drop) {
@@ -2005,10 +1900,5 @@ extern "C" int hsp_nn1_f32(const float* tgt, int Nt, const float* src, int Ns, i
     if (!tgt || !src || !idx || B <= 0 || Nt <= 0 || Ns <= 0) return HSP_ERR_BAD_ARG;
     const size_t lds = (size_t)Ns * 16;
     if (lds > 160 * 1024) return HSP_ERR_UNSUPPORTED;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(nn1_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) { set_last_hip_error(e); return HSP_ERR_LAUNCH; }
-    }
-    hipLaunchKernelGGL(nn1_kernel, dim3((Nt + 255) / 256, B), dim3(256), lds, as_stream(stream), tgt, Nt, src, Ns, idx);
-    return check_launch();
+    return launch_lds(nn1_kernel, dim3((Nt + 255) / 256, B), dim3(256), lds, as_stream(stream), tgt, Nt, src, Ns, idx);
 }

@@ -15,7 +15,7 @@
 //      otherwise all N distances of the row go to LDS and the wave runs libstdc++'s algorithm on them: the partition passes
 //      of nth_element as ballot sweeps (tkw_partition_pivot), the short tails (median of three, insertion sort, the final
 //      std::sort of m - 1 entries, the heap forms) by one lane.
-#include "common.h"
+#include "knn_common.h"
 #include <stdlib.h>
 #include "tie_pass.h"
 
@@ -70,9 +70,8 @@ __global__ __launch_bounds__(64) void knn_feat_ties_rows_kernel(const float* __r
                 }
             } else
             for (int j0 = lane; j0 < N; j0 += 4 * 64) {
-                const float* r[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) r[u] = xb + (size_t)(j0 + 64 * u < N ? j0 + 64 * u : N - 1) * C;
+                const float* const r[4] = {xb + (size_t)j0 * C, xb + (size_t)(j0 + 64 < N ? j0 + 64 : N - 1) * C,
+                                           xb + (size_t)(j0 + 128 < N ? j0 + 128 : N - 1) * C, xb + (size_t)(j0 + 192 < N ? j0 + 192 : N - 1) * C};
                 float acc[4] = {0.f, 0.f, 0.f, 0.f};
                 if ((C & 15) == 0) {
                     for (int c = 0; c < C; c += 16) {                    // torch.bmm: k-ordered chain from 0; 16 loads in flight per lane
@@ -89,28 +88,15 @@ __global__ __launch_bounds__(64) void knn_feat_ties_rows_kernel(const float* __r
                                 acc[u] = __fmaf_rn(a.w, v[t][u].w, __fmaf_rn(a.z, v[t][u].z, __fmaf_rn(a.y, v[t][u].y, __fmaf_rn(a.x, v[t][u].x, acc[u]))));
                         }
                     }
-                } else if ((C & 3) == 0) {
-                    for (int c = 0; c < C; c += 4) {
-                        const float4 a = *reinterpret_cast<const float4*>(sq + c);
-#pragma unroll
-                        for (int u = 0; u < 4; ++u) {
-                            const float4 v = *reinterpret_cast<const float4*>(r[u] + c);
-                            acc[u] = __fmaf_rn(a.w, v.w, __fmaf_rn(a.z, v.z, __fmaf_rn(a.y, v.y, __fmaf_rn(a.x, v.x, acc[u]))));
-                        }
-                    }
                 } else {
-                    for (int c = 0; c < C; ++c) {
-                        const float a = sq[c];
-#pragma unroll
-                        for (int u = 0; u < 4; ++u) acc[u] = __fmaf_rn(a, r[u][c], acc[u]);
-                    }
+                    chain4_rows(sq, r, (C & 3) == 0 ? C : 0, C, acc);      // (rows are 16-byte aligned only where C % 4 == 0)
                 }
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
                     const int j = j0 + 64 * u;
                     if (j < N) {
                         TkE e;                                           // gcn3d.py:21, left to right; NaN / +inf -> FLT_MAX (a total order)
-                        e.v = fminf(add_rn(add_rn(mul_rn(acc[u], -2.0f), qb[j]), qi), 3.402823466e+38f);
+                        e.v = fminf(dist_expand(acc[u], qb[j], qi), 3.402823466e+38f);
                         e.i = j;
                         q[j] = e;
                     }
@@ -149,6 +135,15 @@ extern "C" int hsp_debug_set_tie_prof(void* dev_buf) {
 }
 #endif
 
+// the fixed grid of single-wave workgroups of a tie pass: as many as stay resident with `lds` bytes each, at most one per
+// rows_per_wave rows
+static int tie_pass_grid(long long rows, size_t lds, int rows_per_wave) {
+    const int per_cu = (int)(160 * 1024 / (lds > 16 * 1024 ? lds : 16 * 1024));      // resident single-wave workgroups per CU
+    const long long cap = (long long)HSP_NUM_CU * (per_cu < 1 ? 1 : per_cu);
+    const long long want = (rows + rows_per_wave - 1) / rows_per_wave;
+    return (int)(want < cap ? want : cap);
+}
+
 extern "C" size_t hsp_knn_xyz_workspace_bytes(int B, int N) {
     if (B <= 0 || N <= 0) return 0;
     return ((size_t)B * N + 255) & ~(size_t)255;
@@ -156,10 +151,9 @@ extern "C" size_t hsp_knn_xyz_workspace_bytes(int B, int N) {
 
 extern "C" int hsp_knn_xyz_f32(const float* xyz, int B, int N, int k, int k2, int drop_first, int32_t* idx, int32_t* idx2, void* ws,
                                size_t ws_bytes, int* tie_rows, hspStream_t stream) {
-    if (!xyz || !idx || B <= 0 || N <= 0 || k <= 0 || k2 < 0 || k2 > k || (k2 > 0) != (idx2 != nullptr)) return HSP_ERR_BAD_ARG;
     const int drop = drop_first ? 1 : 0;
+    if (!knn_args_ok(xyz, idx, B, N, 3, k, drop, HSP_MAX_K) || k2 < 0 || k2 > k || (k2 > 0) != (idx2 != nullptr)) return HSP_ERR_BAD_ARG;
     const int m = k + drop;
-    if (m > N || k > HSP_MAX_K) return HSP_ERR_BAD_ARG;
     if (m + 1 > 33) return HSP_ERR_UNSUPPORTED;
     if (!ws || ws_bytes < hsp_knn_xyz_workspace_bytes(B, N)) return HSP_ERR_WORKSPACE;
     uint8_t* tie = reinterpret_cast<uint8_t*>(ws);
@@ -170,20 +164,9 @@ extern "C" int hsp_knn_xyz_f32(const float* xyz, int B, int N, int k, int k2, in
     bool needs_pass = true;
     int rc = knn3_select_flags(xyz, B, N, k, drop, k2, idx, idx2, tie, as_stream(stream), &needs_pass);
     if (rc || !needs_pass) return rc;                      // (tie_rows is only counted by the separate pass)
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(knn_xyz_ties_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)lds);
-        if (e != hipSuccess) { set_last_hip_error(e); return HSP_ERR_LAUNCH; }
-    }
-    const long long rows = (long long)B * N;
-    const int per_cu = (int)(160 * 1024 / (lds > 16 * 1024 ? lds : 16 * 1024));      // resident single-wave workgroups per CU
-    const long long cap = (long long)HSP_NUM_CU * (per_cu < 1 ? 1 : per_cu);
     // one wave per 8 rows at most: a tie-free batch then dispatches a few hundred workgroups, not thousands (6 us -> 3 us at N = 257)
-    const long long want = (rows + 7) / 8;
-    const int grid = (int)(want < cap ? want : cap);
-    hipLaunchKernelGGL(knn_xyz_ties_kernel, dim3(grid), dim3(64), lds, as_stream(stream), xyz, tie, B, N, k, k2, drop, idx, idx2,
-                       tie_rows);
-    return check_launch();
+    return launch_lds(knn_xyz_ties_kernel, dim3(tie_pass_grid((long long)B * N, lds, 8)), dim3(64), lds, as_stream(stream), xyz, tie, B, N,
+                      k, k2, drop, idx, idx2, tie_rows);
 }
 
 // the selection kernel leaves the (B, N, N) distances for the tie pass while that is a small buffer (an image's instances at
@@ -210,10 +193,9 @@ extern "C" int hsp_knn_quadmode_f32(const float* x, int B, int N, int C, int k, 
 
 extern "C" int hsp_knn_exact_f32(const float* x, int B, int N, int C, int k, int drop_first, int quad_mode, int32_t* idx, void* ws,
                                  size_t ws_bytes, int* tie_rows, hspStream_t stream) {
-    if (!x || !idx || B <= 0 || N <= 0 || C <= 0 || k <= 0) return HSP_ERR_BAD_ARG;
     const int drop = drop_first ? 1 : 0;
+    if (!knn_args_ok(x, idx, B, N, C, k, drop, INT_MAX)) return HSP_ERR_BAD_ARG;       // (no HSP_MAX_K test here: mc > 33 below)
     const int m = k + drop;
-    if (m > N) return HSP_ERR_BAD_ARG;
     const int mc = m + 1 < N ? m + 1 : N;
     if (mc > 33 || mc > 64) return HSP_ERR_UNSUPPORTED;
     if (!ws || ws_bytes < hsp_knn_exact_workspace_bytes(B, N, C, k, drop_first)) return HSP_ERR_WORKSPACE;
@@ -227,18 +209,8 @@ extern "C" int hsp_knn_exact_f32(const float* x, int B, int N, int C, int k, int
     if (rc) return rc;
     const size_t lds = (size_t)N * (sizeof(TkE) + 2 * sizeof(int)) + (size_t)((C + 3) & ~3) * sizeof(float);
     if (lds > 160 * 1024) return HSP_ERR_UNSUPPORTED;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(knn_feat_ties_rows_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)lds);
-        if (e != hipSuccess) { set_last_hip_error(e); return HSP_ERR_LAUNCH; }
-    }
     const float* quad = reinterpret_cast<const float*>(ws);                           // knn_feat_select_flags left |x|^2 there
-    const long long rows = (long long)B * N;
-    const int per_cu = (int)(160 * 1024 / (lds > 16 * 1024 ? lds : 16 * 1024));
     // (as many waves as fit: ~2 % of the rows of real activations are flagged, and two of them in one wave double the pass)
-    const long long cap = (long long)HSP_NUM_CU * (per_cu < 1 ? 1 : per_cu);
-    const int grid = (int)(rows < cap ? rows : cap);
-    hipLaunchKernelGGL(knn_feat_ties_rows_kernel, dim3(grid), dim3(64), lds, as_stream(stream), x, quad, tie, dmat, B, N, C, k, drop, idx,
-                       tie_rows);
-    return check_launch();
+    return launch_lds(knn_feat_ties_rows_kernel, dim3(tie_pass_grid((long long)B * N, lds, 1)), dim3(64), lds, as_stream(stream), x, quad,
+                      tie, dmat, B, N, C, k, drop, idx, tie_rows);
 }

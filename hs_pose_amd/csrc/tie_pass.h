@@ -2,7 +2,7 @@
 // csrc/knn.hip (the coordinate search replays a tie-ridden row in place): libstdc++'s nth_element / sort / partial_sort restated
 // (ATen TopKImpl.h takes them under a comparator that only sees the value), see knn_exact.hip's header comment.
 #pragma once
-#include "common.h"
+#include "knn_common.h"
 
 namespace hsp {
 
@@ -509,7 +509,7 @@ __device__ inline void tie_rows_xyz(char* scratch, const float* __restrict__ x, 
                         const float inner = dot3_chain(qx, qy, qz, px[u], py[u], pz[u]);
                         // (NaN / +inf -> FLT_MAX as in the selection kernels: the partition loops need a total order)
                         TkE e;
-                        e.v = fminf(add_rn(add_rn(mul_rn(inner, -2.0f), quad3(px[u], py[u], pz[u])), qq), 3.402823466e+38f);
+                        e.v = fminf(dist_expand(inner, quad3(px[u], py[u], pz[u]), qq), 3.402823466e+38f);
                         e.i = j;
                         if (j < N) q[j] = e;
                     }

@@ -9,7 +9,7 @@ Tolerance definition (stated once, used below):
     to one bf16 ulp (2^-8 relative) plus the twin's own order noise.
   * hsp_knn_bf16: bf16 x bf16 products are exact in fp32, the MFMA adds 16 of them per step in its own order, so indices
     need not equal an fp32-chain evaluation on near ties: the neighbour-SET agreement is reported and held above 97 % of
-    rows on well-separated data.
+    rows on well-separated data.  On integer rows, where every sum is exact in any order, the lists equal the C oracle's.
   * one HS layer against the fp32 CPU oracle on the bf16-rounded inputs / weights at N = 4096: 1e-2 of scale (measured
     3.5e-3: fm, F and out are each rounded once).
   * whole stack against the fp32 path at B = 2, N = 4096 (and 1028), fp32 path's feature-space neighbour lists replayed
@@ -61,6 +61,33 @@ def test_knn_bf16_vs_fp32_on_same_rows(dev, ref, B, N, C, k):
     dk = torch.gather(d, 2, want)[:, :, -1:]
     dg = torch.gather(d, 2, got)
     assert (dg <= dk * (1 + 1e-3) + 1e-3).all()
+
+
+@pytest.mark.parametrize("B,N,C,k,tie_rich", [
+    (2, 129, 32, 20, True),     # two query workgroups, 5 candidate tiles with a 1-row last tile, 2 k-steps, K1 = 21
+    (1, 64, 256, 2, False),     # widest C, four staging pieces, K1 = 3
+    (2, 160, 64, 5, False),     # m = 6: the 6 -> 9 remap
+    (1, 257, 128, 20, True),    # the stack's shape
+])
+def test_knn_bf16_exact_on_integer_rows(dev, ref, oc, B, N, C, k, tie_rich):
+    """hsp_knn_bf16 pinned EXACTLY where its arithmetic is exact in any summation order: rows of integers 0..6 (exact in bf16), so
+    every |x|^2 and inner product is an integer far below 2^24 and the MFMA's own order inside a 16-product step cannot matter.
+    The lists must equal the C oracle's (distance, lowest index first) bit for bit -- ties included: the share of rows with a tie
+    among their m + 1 nearest is printed and, as a condition on the INPUT (not a tolerance), held above one half on the two
+    tie-rich shapes, so the shared tile fold, the pruning bound and the tournament merge are all exercised on equal distances."""
+    from hs_pose_amd import ops
+    ints = np.floor(ref.hash_unit(B * N * C, 4000 + N + C + k) * float(1 << 24)) % 7
+    x = torch.from_numpy(ints.astype(np.float32)).reshape(B, N, C)
+    xb = x.to(dev).bfloat16()
+    assert torch.equal(xb.float().cpu(), x)
+    want = oc.knn(x.numpy(), k, 1)
+    _, dist = oc.knn(x.numpy(), k + 2, 0, with_dist=True)          # the m + 1 = k + 2 nearest, rank 0 included
+    tie_share = float((dist[:, :, 1:] == dist[:, :, :-1]).any(axis=2).mean())
+    print(f"knn_bf16 exact B{B} N{N} C{C} k{k}: rows with a tie among the m + 1 nearest {tie_share:.4f}")
+    if tie_rich:
+        assert tie_share > 0.5
+    got = ops.knn(xb, k).cpu().numpy()
+    assert np.array_equal(got, want), f"{(got != want).sum()} of {got.size} differ"
 
 
 @pytest.mark.parametrize("B,N,k,S,C", [(2, 257, 20, 7, 256), (2, 1028, 20, 7, 128), (1, 4096, 20, 7, 128), (2, 64, 8, 3, 32)])
