@@ -261,16 +261,12 @@ __global__ __launch_bounds__(256, 2) void gemm_x3_kernel(const X3Args g) {
     }
     constexpr bool HAS_BIAS = EPI & 1, HAS_RES = (EPI & 2) && EPI != 2, HAS_CB = EPI & 4, HAS_BN = EPI & 8;
     float bn1[2] = {0.f, 0.f}, bn2[2] = {0.f, 0.f};           // per column of this lane: sum (v - shift), sum (v - shift)^2
-    // per-cloud bias: a tile of BM rows spans at most two clouds when rows_per_cloud >= BM (boundary compare, no division)
-    const int c0 = m0 / g.rpc, nb = (c0 + 1) * g.rpc;
-    const bool two_clouds = g.rpc >= BM;
+    float bvv[2] = {0.f, 0.f}, bsh[2] = {0.f, 0.f};
 #pragma unroll
     for (int y = 0; y < 2; ++y) {
         const int col = n0 + wn0 + 32 * y + li;
-        const bool cok = col < g.N;
         const int colc = min(col, g.N - 1);
-        float bvv = 0.f, cb0 = 0.f, cb1 = 0.f, bsh = 0.f;
-        if constexpr (HAS_BIAS) bvv = g.bias[colc];
+        if constexpr (HAS_BIAS) bvv[y] = g.bias[colc];
         if constexpr (HAS_BN) {
             // the shift of the shifted sums: any per-column value every tile agrees on and that sits near the column's mean --
             // the residual + per-cloud-bias part of ROW 0 of the result (data of this step only: a replayed graph and an eager
@@ -281,45 +277,91 @@ __global__ __launch_bounds__(256, 2) void gemm_x3_kernel(const X3Args g) {
             // tests/test_gpu_bn_reference.py part C2) and x-hat half of that: inside the 2e-5 the BatchNorm outputs are held to
             // up to rho of about 10, outside it at 30.  A per-tile data shift would need a third row in
             // bn_part and a Chan merge in bn_finalize (what the three-launch form of norm.hip does per row chunk)
-            if constexpr (HAS_RES) bsh = g.resid[colc] + g.cbias[colc];
-            else bsh = bvv;
-            if (tm == 0 && wm0 == 0 && lh == 0 && cok) g.bn_shift[col] = bsh;
+            if constexpr (HAS_RES) bsh[y] = g.resid[colc] + g.cbias[colc];
+            else bsh[y] = bvv[y];
+            if (tm == 0 && wm0 == 0 && lh == 0 && col < g.N) g.bn_shift[col] = bsh[y];
         }
-        if constexpr (HAS_CB) {
-            cb0 = g.cbias[(size_t)c0 * g.N + colc];
-            cb1 = g.cbias[(size_t)min(c0 + 1, (g.M - 1) / g.rpc) * g.N + colc];
+    }
+    {
+        // NO memory operation sits inside a run-time branch (hipcc drains the whole queue
+        // -- on gfx9 the stores too -- at the join of such a branch: once per ELEMENT in the form this replaces): the one run-time
+        // decision, how the rows find their cloud, is taken once per workgroup around the whole body; every residual load and
+        // per-cloud-bias gather of a 32-row block is in flight before the first add that needs one; residual loads and stores go
+        // through buffer descriptors of THIS TILE's rows (base = row m0, so every offset is tile-local), whose range check answers
+        // rows >= M with 0 / drops their stores, and columns >= N are sent out of range (0x80000000: the tile's bytes end below
+        // that and nothing wraps, x3_takes holds the pitches under 2^22) -- no clamp, no select, no wait between the stores.
+        // The arithmetic per element is the one it was, in the same order: (alpha * acc + bias) + resid, + cbias.
+        const int rows_left = min(BM, g.M - m0);
+        const __amdgpu_buffer_rsrc_t rsC = __builtin_amdgcn_make_buffer_rsrc(
+            g.C + (size_t)m0 * g.ldc, 0, (int)((((size_t)rows_left - 1) * g.ldc + g.N) * 4), 0x00020000);
+        const __amdgpu_buffer_rsrc_t rsR = __builtin_amdgcn_make_buffer_rsrc(
+            const_cast<float*>(HAS_RES ? g.resid + (size_t)m0 * g.ldr : g.C), 0,
+            HAS_RES ? (int)((((size_t)rows_left - 1) * g.ldr + g.N) * 4) : 0, 0x00020000);
+        const unsigned ldc4 = (unsigned)g.ldc * 4u, ldr4 = (unsigned)g.ldr * 4u;
+        unsigned voffC[2], voffR[2];
+        int colc[2];
+#pragma unroll
+        for (int y = 0; y < 2; ++y) {
+            const int col = n0 + wn0 + 32 * y + li;
+            colc[y] = min(col, g.N - 1);
+            voffC[y] = col < g.N ? (unsigned)(wm0 + 4 * lh) * ldc4 + (unsigned)col * 4u : 0x80000000u;
+            voffR[y] = col < g.N ? (unsigned)(wm0 + 4 * lh) * ldr4 + (unsigned)col * 4u : 0x80000000u;
         }
+        // per-cloud bias: a tile of BM rows spans at most two clouds when rows_per_cloud >= BM (boundary compare, no division);
+        // shorter clouds: a gather per row
+        const int c0 = m0 / g.rpc, nb = (c0 + 1) * g.rpc;
+        auto body = [&](auto PER_ROW_) {
+            constexpr bool PER_ROW = decltype(PER_ROW_)::value;
+            float cb0[2] = {0.f, 0.f}, cb1[2] = {0.f, 0.f};
+            if constexpr (HAS_CB && !PER_ROW) {
 #pragma unroll
-        for (int x = 0; x < WM; ++x) {
+                for (int y = 0; y < 2; ++y) {
+                    cb0[y] = g.cbias[(size_t)c0 * g.N + colc[y]];
+                    cb1[y] = g.cbias[(size_t)min(c0 + 1, (g.M - 1) / g.rpc) * g.N + colc[y]];
+                }
+            }
 #pragma unroll
-            for (int r4 = 0; r4 < 16; r4 += 4) {
-                float rv[4];
-                if constexpr (HAS_RES) {
+            for (int x = 0; x < WM; ++x) {
+                float rv[2][16], cbv[2][16];
 #pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        const int row = min(m0 + wm0 + 32 * x + q + 8 * (r4 >> 2) + 4 * lh, g.M - 1);
-                        rv[q] = g.resid[(size_t)row * g.ldr + colc];
+                for (int r = 0; r < 16; ++r) {
+                    const int lrow = wm0 + 32 * x + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                    const unsigned dr = (unsigned)(32 * x + (r & 3) + 8 * (r >> 2));
+                    if constexpr (HAS_RES) {
+#pragma unroll
+                        for (int y = 0; y < 2; ++y)
+                            rv[y][r] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsR, voffR[y] + dr * ldr4, 0, 0));
+                    }
+                    if constexpr (HAS_CB && PER_ROW) {
+                        const size_t cl = (size_t)(min(m0 + lrow, g.M - 1) / g.rpc) * g.N;
+#pragma unroll
+                        for (int y = 0; y < 2; ++y) cbv[y][r] = g.cbias[cl + colc[y]];
                     }
                 }
 #pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int r = r4 + q;
-                    const int row = m0 + wm0 + 32 * x + q + 8 * (r4 >> 2) + 4 * lh;
-                    float v = g.alpha * acc[x][y][r] + bvv;
-                    if constexpr (HAS_RES) v += rv[q];
-                    if constexpr (HAS_CB) {
-                        if (two_clouds) v += row >= nb ? cb1 : cb0;
-                        else v += g.cbias[(size_t)(min(row, g.M - 1) / g.rpc) * g.N + colc];
-                    }
-                    if (row < g.M && cok) g.C[(size_t)row * g.ldc + col] = v;
-                    if constexpr (HAS_BN) {
-                        const float d = row < g.M ? v - bsh : 0.f;
-                        bn1[y] += d;
-                        bn2[y] += d * d;
+                for (int y = 0; y < 2; ++y) {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const int row = m0 + wm0 + 32 * x + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                        const unsigned dr = (unsigned)(32 * x + (r & 3) + 8 * (r >> 2));
+                        float v = g.alpha * acc[x][y][r] + bvv[y];
+                        if constexpr (HAS_RES) v += rv[y][r];
+                        if constexpr (HAS_CB) {
+                            if constexpr (PER_ROW) v += cbv[y][r];
+                            else v += row >= nb ? cb1[y] : cb0[y];
+                        }
+                        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), rsC, voffC[y] + dr * ldc4, 0, 0);
+                        if constexpr (HAS_BN) {
+                            const float d = row < g.M ? v - bsh[y] : 0.f;
+                            bn1[y] += d;
+                            bn2[y] += d * d;
+                        }
                     }
                 }
             }
-        }
+        };
+        if (!HAS_CB || g.rpc >= BM) body(std::false_type{});
+        else body(std::true_type{});
     }
     if constexpr (HAS_BN) {
         // the train-mode BatchNorm that follows the layer (FaceRecon.py:90-95) gets its first pass here: per-tile shifted column
@@ -679,6 +721,8 @@ static bool x3_takes(const HspGemmCall& c, X3Plan* pl) {
     if (c.elem_bytes != 4 || c.xyz3 || (c.bn && c.relu) || !hsp_gemm_x3_supported(M, N, c.K1, K2)) return false;
     if ((long long)M * c.lda1 * 4 >= (1ll << 31) || (two && (long long)M * c.lda2 * 4 >= (1ll << 31))) return false;
     if (!al16(c.A1, c.lda1, 4) || (two && !al16(c.A2, c.lda2, 4))) return false;
+    // (the epilogue addresses a tile's rows by 32-bit offsets from the tile's first row)
+    if (c.ldc >= (1 << 22) || (c.resid && c.ldr >= (1 << 22))) return false;
     // instantiated epilogues: 0 none, 1 bias, 2 residual (one source: the input-gradient chain of layers that share their input
     // rows -- C may BE resid: an element is read and written by the same thread), 6 residual + per-cloud bias (the layer's out
     // product), 14 = 6 + BatchNorm partials
