@@ -148,6 +148,7 @@ SIGNATURES = {
     "hsp_crop_compact_u16": (_i, [_vp, ctypes.c_longlong, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "hsp_frames_to_pcl_f32": (_i, [_vp, ctypes.c_longlong, _i, _i, _vp, _i, _vp, ctypes.c_longlong, _vp, _i, _i, _vp, _vp]),
     "hsp_frames_to_pcl_u16": (_i, [_vp, ctypes.c_longlong, _i, _i, _vp, _i, _vp, ctypes.c_longlong, _vp, _i, _i, _vp, _vp]),
+    "hsp_batch_select": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp, _vp]),
     "hsp_generate_rt": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
     "hsp_sumsq_workspace_bytes": (_sz, [ctypes.c_longlong]),
     "hsp_sumsq_f32": (_i, [_vp, ctypes.c_longlong, _vp, _vp, _sz, _vp]),
@@ -259,3 +260,12 @@ class HspDirsPending(ctypes.Structure):
     """include/hsp.h: HspDirsPending (a HOST struct)"""
     _fields_ = [("part", ctypes.c_void_p), ("dirs", ctypes.c_void_p), ("grad_dirs", ctypes.c_void_p),
                 ("nparts", ctypes.c_int), ("SC", ctypes.c_int)]
+
+
+class HspSelectSeg(ctypes.Structure):
+    """include/hsp.h: HspSelectSeg (a HOST struct)"""
+    _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("fill", ctypes.c_void_p), ("row_bytes", ctypes.c_longlong)]
+
+
+# include/hsp.h: HSP_BATCH_SELECT_MAX_SEGS / HSP_BATCH_SELECT_MAX_ITEMS
+BATCH_SELECT_MAX_SEGS, BATCH_SELECT_MAX_ITEMS = 16, 1024

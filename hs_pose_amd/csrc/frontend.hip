@@ -10,7 +10,9 @@
 //    pixels of every instance through the warp's integer map and lists the source ids of the valid ones; hsp_frame_to_pcl
 //    back-projects the chosen ones straight from the frame.
 //  * a training batch -> instance clouds: that chain for B frames with one instance each and the loader's defor_2D on the
-//    cropped mask in between (datasets/load_data.py:234-278): hsp_roi_defor, hsp_crop_compact, hsp_frames_to_pcl.
+//    cropped mask in between (datasets/load_data.py:234-278): hsp_roi_defor, hsp_crop_compact, hsp_frames_to_pcl; and the
+//    loader's "move on to the next index" for a rejected item (:254-278): hsp_batch_select picks the first good items of a
+//    batch with spares and gathers every per-item tensor, one launch.
 //  * the chosen rows themselves, optionally: a keyed counter-based draw on the device between the two stages (hsp_sample_ids)
 //    in place of the host's, so that no front end has to bring its counts to the host.
 // Behind it:
@@ -575,6 +577,67 @@ __global__ __launch_bounds__(256) void crop_write_kernel(const D* __restrict__ d
     }
 }
 
+// ---- the kept items of a training batch (include/hsp.h: hsp_batch_select states the rule) ---------------------------------------
+// One launch over grid (keep, max(nseg, 1)): workgroup (j, s) copies row sel[j] of segment s into its row j.  status is at most
+// 4 KB, so every workgroup derives its own sel[j] from it and nothing is handed from one workgroup to another: item i belongs to
+// lane i & 63 of slot i >> 6 (16 slots of 64 items, four rounds of the workgroup's four waves); a slot's good items are one
+// __ballot, their ranks the set bits below the lane plus the counts of the earlier slots.  The rows are moved as words, never
+// computed on.
+struct BatchSelectDesc { HspSelectSeg seg[HSP_BATCH_SELECT_MAX_SEGS]; };
+
+__global__ __launch_bounds__(256) void batch_select_kernel(const int32_t* __restrict__ status, int M, int keep, int nseg,
+                                                           const BatchSelectDesc d, int32_t* __restrict__ sel,
+                                                           int32_t* __restrict__ info) {
+    __shared__ int slot_cnt[16];
+    __shared__ int picked;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int j = blockIdx.x;                                   // (< keep by the grid)
+    unsigned long long good[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int i = q * 256 + tid;
+        good[q] = __ballot(i < M && status[i] == 0);
+        if (lane == 0) slot_cnt[q * 4 + wv] = __popcll(good[q]);
+    }
+    __syncthreads();
+    int V = 0, before[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int s = 0; s < 16; ++s) {
+        if ((s & 3) == wv) before[s >> 2] = V;                  // slot q * 4 + wv is this wave's in round q
+        V += slot_cnt[s];
+    }
+    if (V > 0) {
+        const int t = j % V;
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            if (((good[q] >> lane) & 1ull) && before[q] + __popcll(good[q] & ((1ull << lane) - 1ull)) == t) picked = q * 256 + tid;
+    } else if (tid == 0) {
+        picked = j;
+    }
+    __syncthreads();
+    const int from = picked;
+    if (blockIdx.y == 0 && tid == 0) {
+        sel[j] = from;
+        if (j == 0) {
+            info[0] = V;
+            info[1] = min(V, keep);
+        }
+    }
+    if ((int)blockIdx.y >= nseg) return;
+    const HspSelectSeg sg = d.seg[blockIdx.y];
+    const size_t rb = (size_t)sg.row_bytes;
+    const char* s = (V == 0 && sg.fill) ? reinterpret_cast<const char*>(sg.fill)
+                                        : reinterpret_cast<const char*>(sg.src) + (size_t)from * rb;
+    char* o = reinterpret_cast<char*>(sg.dst) + (size_t)j * rb;
+    if (((reinterpret_cast<uintptr_t>(s) | reinterpret_cast<uintptr_t>(o) | rb) & 15) == 0) {
+        for (size_t b = (size_t)tid * 16; b < rb; b += 256 * 16)
+            *reinterpret_cast<uint4*>(o + b) = *reinterpret_cast<const uint4*>(s + b);
+    } else {
+        for (size_t b = (size_t)tid * 4; b < rb; b += 256 * 4)
+            *reinterpret_cast<uint32_t*>(o + b) = *reinterpret_cast<const uint32_t*>(s + b);
+    }
+}
+
 __device__ __forceinline__ void rodrigues_apply(const float rx[3], float s, float c, const float v[3], float o[3]) {
     // rows of to_rot_matrix_in_batch (rot_utils.py:67-75) times v
     const float t = 1.f - c;
@@ -809,6 +872,24 @@ extern "C" int hsp_frames_to_pcl_u16(const uint16_t* depth, long long depth_stri
                                      int camK_rows, const int32_t* src, long long src_stride, const int32_t* choose, int n,
                                      int S, float* pc, hspStream_t stream) {
     return frames_to_pcl(depth, depth_stride, H, W, camK, camK_rows, src, src_stride, choose, n, S, pc, stream);
+}
+
+extern "C" int hsp_batch_select(const int32_t* status, int M, int keep, const HspSelectSeg* segs, int nseg, int32_t* sel,
+                                int32_t* info, hspStream_t stream) {
+    if (!status || !sel || !info || keep < 1 || keep > M || M > HSP_BATCH_SELECT_MAX_ITEMS) return HSP_ERR_BAD_ARG;
+    if (nseg < 0 || nseg > HSP_BATCH_SELECT_MAX_SEGS || (nseg > 0 && !segs)) return HSP_ERR_BAD_ARG;
+    BatchSelectDesc d = {};
+    for (int s = 0; s < nseg; ++s) {
+        const HspSelectSeg& g = segs[s];
+        if (!g.src || !g.dst || g.row_bytes <= 0 || (g.row_bytes & 3) != 0) return HSP_ERR_BAD_ARG;
+        const uintptr_t a = reinterpret_cast<uintptr_t>(g.src), b = reinterpret_cast<uintptr_t>(g.dst);
+        if (((a | b | reinterpret_cast<uintptr_t>(g.fill)) & 3) != 0) return HSP_ERR_BAD_ARG;
+        if (a < b + (uintptr_t)keep * g.row_bytes && b < a + (uintptr_t)M * g.row_bytes) return HSP_ERR_BAD_ARG;   // src and dst overlap
+        d.seg[s] = g;
+    }
+    hipLaunchKernelGGL(batch_select_kernel, dim3(keep, nseg > 0 ? nseg : 1), dim3(256), 0, as_stream(stream), status, M, keep, nseg,
+                       d, sel, info);
+    return check_launch();
 }
 
 extern "C" int hsp_generate_rt(const float* p_green, const float* p_red, const float* f_green, const float* f_red,

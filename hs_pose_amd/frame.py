@@ -81,7 +81,6 @@ class FramePipeline:
         self.sampler, self.one_graph, self.sync = sampler, bool(one_graph), bool(sync)
         self.graphs = {}                                         # instance count -> GraphedInference
         self.frame_graphs = {}                                   # one_graph: (sampler, n, frame shape, dtype, ...) -> _FrameGraph
-        self._stand_in = None
 
     def _network_input(self, PC, status):
         """the clouds the network is given: a rejected instance's rows are NaN by contract, and the neighbour search is not
@@ -89,10 +88,7 @@ class FramePipeline:
         return torch.where((status != 0)[:, None, None], self._stand_in_cloud(PC.shape[1], PC.device), PC)
 
     def _stand_in_cloud(self, n_pts, dev):
-        if self._stand_in is None or self._stand_in.shape[0] != n_pts or self._stand_in.device != dev:
-            g = torch.Generator().manual_seed(0)
-            self._stand_in = ((torch.rand(n_pts, 3, generator=g) - 0.5) * 0.2).to(dev)
-        return self._stand_in
+        return pc_sample.stand_in_cloud(n_pts, dev)
 
     def __call__(self, depth, masks, bboxes, class_ids, K, inst_ids=None):
         n = len(bboxes)

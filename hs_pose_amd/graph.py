@@ -277,11 +277,18 @@ class GraphedTrainStep:
 
     Build it BEFORE the network's first eager backward: autograd binds each parameter's gradient accumulator to the
     stream of its first use, and an accumulator bound to another stream than the capture stream is executed outside
-    the capture (the replayed graph then reads freed memory).  The warm-up iterations here run on the capture stream."""
+    the capture (the replayed graph then reads freed memory).  The warm-up iterations here run on the capture stream.
 
-    def __init__(self, network, optimizer, batch, scheduler=None, max_norm=5, warmup=3):
+    ``prologue``: a callable issued at the head of the captured body, on the capture stream, that returns a dict; its entries
+    replace the same-named entries of ``batch`` for that body -- the step in front of the network captured with it
+    (train.FrameTrainStep: the training loader's front end and the choice of the kept items).  It reads static buffers of its
+    owner's and must be issuable both eagerly (the warm-up) and under capture; ``batch`` then gives the shapes and the static
+    buffers of the other keys only, and ``load_batch`` has no effect on the replaced ones.  None: the body is the batch's."""
+
+    def __init__(self, network, optimizer, batch, scheduler=None, max_norm=5, warmup=3, prologue=None):
         self.net, self.opt, self.sched, self.max_norm = network, optimizer, scheduler, max_norm
         self.batch = batch
+        self._prologue = prologue
         PC = batch["PC"]
         B, N, _ = PC.shape
         self.n_points = N
@@ -329,11 +336,12 @@ class GraphedTrainStep:
         # Gradients are created INSIDE the capture (grad = None first) and then moved into the optimizer's flat buffer
         # with one multi-tensor copy: accumulating straight into the pre-existing flat views makes autograd synchronise
         # the capture stream with the stream those views were made on, and the replayed graph then waits forever.
+        batch = self.batch if self._prologue is None else {**self.batch, **self._prologue()}
         params, views = self._params_and_views()
         for p in params:
             p.grad = None
         with pool_feed(self.pool_idx), augment.jitter_noise_feed(self.noise):
-            _, ld = self.net(do_loss=True, **self.batch)
+            _, ld = self.net(do_loss=True, **batch)
         total = self.net.total_loss(ld)                     # (the sum over the four sub-dictionaries, engine/train.py:84-90)
         with ops.StepFolds():
             total.backward()
@@ -356,16 +364,24 @@ class GraphedTrainStep:
         for k, v in batch.items():
             self.batch[k].copy_(v, non_blocking=True)
 
-    def run(self, check_nan=False):
-        """one training step; returns False when ``check_nan`` found a NaN loss (the reference's skip, train.py:91-95)."""
+    def replay(self):
+        """the host draws and the replay: losses and gradients of one step, nothing applied yet"""
         self._host_draws()
         self.graph.replay()
-        if check_nan and bool(torch.isnan(self.total).any()):
-            return False
+
+    def apply(self):
+        """the fused optimizer launch (clip coefficient inside) and the scheduler, behind ``replay()``"""
         self.opt._gnorm_sq, self.opt._max_norm = self._gnorm_sq, self._max_norm
         self.opt.step()
         if self.sched is not None:
             self.sched.step()
+
+    def run(self, check_nan=False):
+        """one training step; returns False when ``check_nan`` found a NaN loss (the reference's skip, train.py:91-95)."""
+        self.replay()
+        if check_nan and bool(torch.isnan(self.total).any()):
+            return False
+        self.apply()
         return True
 
 

@@ -2781,3 +2781,49 @@ def frames_to_pcl(depth, camK64, src, choose):
     """``frame_to_pcl`` with a frame per instance: depth (H,W) or (n,H,W) fp32 or uint16, camK (1|n,3,3) float64, src (n,L)
     int32 from crop_compact, choose (n,S) int32 -> (n,S,3) fp32 metres; NaN rows where choose is -1."""
     return _to_pcl("frames_to_pcl", depth, True, camK64, src, choose)
+
+
+def batch_select(status, keep, segs=(), sel=None, info=None):
+    """the kept items of a training batch with spares, picked and gathered in one launch (include/hsp.h: hsp_batch_select states
+    the rule): status (M,) int32 on the device, non-zero = rejected; segs a sequence of up to 16 ``(src, dst, fill)`` with src a
+    device tensor of leading dimension M, dst None (a fresh tensor) or a contiguous tensor of src's dtype and trailing shape
+    with leading dimension keep, fill None or one row of src's trailing shape (what every row of dst gets when no item is good)
+    -> (dsts, sel (keep,) int32, info (2,) int32 = [good items, min(good items, keep)]).  sel[j] is the j-th good item, the
+    good ones repeating in order when fewer than keep are; the identity when none is.  A row is a positive multiple of 4
+    bytes.  Nothing is uploaded and nothing copied back: the call can be captured."""
+    from ._lib import BATCH_SELECT_MAX_ITEMS, BATCH_SELECT_MAX_SEGS, HspSelectSeg
+    status = _req(status, torch.int32, "batch_select.status")
+    keep, segs = int(keep), list(segs)
+    if status.dim() != 1 or not 1 <= keep <= status.shape[0] <= BATCH_SELECT_MAX_ITEMS or len(segs) > BATCH_SELECT_MAX_SEGS:
+        raise HspError(f"batch_select: expects status (M,) with 1 <= keep <= M <= {BATCH_SELECT_MAX_ITEMS} and at most "
+                       f"{BATCH_SELECT_MAX_SEGS} segments, got M {tuple(status.shape)}, keep {keep}, {len(segs)} segments")
+    M, dev = status.shape[0], status.device
+    table, dsts, held = (HspSelectSeg * max(len(segs), 1))(), [], []
+    for s, (src, dst, fill) in enumerate(segs):
+        name = f"batch_select.segs[{s}]"
+        src = _req(src.detach() if isinstance(src, torch.Tensor) else src, getattr(src, "dtype", None), name + ".src")
+        if src.dim() < 1 or src.shape[0] != M:
+            raise HspError(f"{name}: expects src with leading dimension {M}, got {tuple(src.shape)}")
+        row_bytes = (src.numel() // M) * src.element_size()
+        if row_bytes <= 0 or row_bytes % 4:
+            raise HspError(f"{name}: a row of {row_bytes} bytes ({tuple(src.shape[1:])} {src.dtype}); expects a positive multiple of 4")
+        if dst is None:
+            dst = torch.empty((keep,) + tuple(src.shape[1:]), dtype=src.dtype, device=dev)
+        elif not (isinstance(dst, torch.Tensor) and dst.is_cuda and dst.is_contiguous() and dst.dtype == src.dtype
+                  and tuple(dst.shape) == (keep,) + tuple(src.shape[1:])):
+            raise HspError(f"{name}: expects dst contiguous on the device, {(keep,) + tuple(src.shape[1:])} {src.dtype}")
+        if fill is not None:
+            fill = _req(fill.detach(), src.dtype, name + ".fill")
+            if tuple(fill.shape) != tuple(src.shape[1:]):
+                raise HspError(f"{name}: expects fill {tuple(src.shape[1:])}, got {tuple(fill.shape)}")
+        table[s] = HspSelectSeg(src.data_ptr(), dst.data_ptr(), fill.data_ptr() if fill is not None else None, row_bytes)
+        dsts.append(dst)
+        held += [src, fill]
+    sel = torch.empty(keep, dtype=torch.int32, device=dev) if sel is None else sel
+    info = torch.empty(2, dtype=torch.int32, device=dev) if info is None else info
+    for t, shape, name in ((sel, (keep,), "sel"), (info, (2,), "info")):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int32 and tuple(t.shape) == shape and t.is_contiguous()):
+            raise HspError(f"batch_select: expects {name} {shape} int32, contiguous, on the device")
+    _run("hsp_batch_select", (_p(status), M, keep, table, len(segs), _p(sel), _p(info), _stream()), key=f"M{M}k{keep}s{len(segs)}",
+         abytes=4 * M + 4 * keep + 8 + 2 * keep * sum(t.row_bytes for t in table[:len(segs)]))
+    return dsts, sel, info

@@ -24,7 +24,9 @@ that form bare: clouds and per-instance status, both on the device.
 ``dzi_windows`` + ``train_batch_to_pcl`` are the training loader's chain (datasets/load_data.py:228-278) for a batch of items,
 each with its own frame: ``aug_bbox_DZI``'s windows on the host, draw for draw, then the crops, ``defor_2D``'s perturbation of
 the cropped mask, the three rejection tests, the cloud and its rows on the device (``hsp_roi_defor`` / ``hsp_crop_compact`` /
-``hsp_sample_ids`` / ``hsp_frames_to_pcl``), under a device sampler only.
+``hsp_sample_ids`` / ``hsp_frames_to_pcl``), under a device sampler only.  ``train_batch_select`` is the loader's answer to a
+rejected item behind it -- move on to the next index (:254-278) -- for a batch that arrives with spares: the first ``keep`` good
+items and every per-item tensor of theirs in one launch (``hsp_batch_select``), nothing read back.
 """
 import numpy as np
 import torch
@@ -343,7 +345,7 @@ def train_batch_to_pcl(depth, labels, inst_ids, centers, scales, K, n_pts=None, 
     host (``dzi_windows``); K (3,3) or (B,3,3) -> (PC (B, n_pts, 3) fp32 metres, status (B,) int32), both on the device.
     status: ``hsp_sample_ids``'s bits -- 1: fewer than min_pts crop pixels with depth under the DEFORMED mask (:276), 2: <= 1
     with depth (:254) -- plus 4: <= 1 with depth under the mask BEFORE the deformation (:257).  The rows of an item whose
-    status is not 0 are NaN: the loader skips such an item.  mask_pro defaults to FLAGS.roi_mask_pro, n_pts to
+    status is not 0 are NaN: the loader skips such an item (``train_batch_select`` is that skip on the device).  mask_pro defaults to FLAGS.roi_mask_pro, n_pts to
     FLAGS.random_points, out_size to FLAGS.img_size; mask_iters is the rule's r, and 1 is what the reference's call runs
     whatever FLAGS.roi_mask_r says.
 
@@ -386,3 +388,49 @@ def train_batch_to_pcl(depth, labels, inst_ids, centers, scales, K, n_pts=None, 
     early = pre <= 1
     PC = ops.frames_to_pcl(depth, K64, src, torch.where(early[:, None], -1, choose))
     return PC, status | (early.to(torch.int32) << 2)
+
+
+_stand_ins = {}
+
+
+def stand_in_cloud(n_pts, device):
+    """the fixed, well-spread cloud (n_pts, 3) the network is given where a front end rejected the real one (a rejected item's
+    rows are NaN by contract, and the neighbour search is not meant for those): uniform in a 0.2 m cube about the origin, from
+    a generator of its own seeded 0.  Kept per (n_pts, device); the first call uploads, so make it before a capture."""
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    c = _stand_ins.get((int(n_pts), device))
+    if c is None:
+        if device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+            raise ValueError("stand_in_cloud: the first call for a size uploads the cloud; make it before the graph capture")
+        g = torch.Generator().manual_seed(0)
+        c = _stand_ins[(int(n_pts), device)] = ((torch.rand(int(n_pts), 3, generator=g) - 0.5) * 0.2).to(device)
+    return c
+
+
+def train_batch_select(PC, status, keep, extras, stand_in=None, out=None, sel=None, info=None):
+    """The loader's "move on to the next index" (datasets/load_data.py:254-278) for a batch that arrives with spares, on the
+    device: PC (M, n_pts, 3) and status (M,) int32 of ``train_batch_to_pcl``, extras a dict of per-item device tensors with
+    leading dimension M (obj_id, gt_R, gt_t, gt_s, mean_shape, sym, aug_bb, aug_rt_t, aug_rt_r, model_point, nocs_scale, or any
+    subset; at most 15) -> (batch, sel (keep,) int32, info (2,) int32): batch holds ``PC`` and every extra with leading dimension
+    keep, the rows of the first keep items whose status is 0, in order -- sel names them; with fewer than keep good items the good
+    ones repeat in order; info = [good items, min(good items, keep)] (include/hsp.h: hsp_batch_select).  No row of a rejected
+    item reaches the batch.  With NO good item sel is the identity, the extras are rows 0 .. keep-1 and every cloud is
+    ``stand_in`` (n_pts, 3) -- by default ``stand_in_cloud`` -- so that the network never sees NaN rows; info[0] == 0 says so.
+
+    One ``ops.batch_select`` launch; nothing is uploaded or read back, so the call can be captured (a default stand-in must
+    exist before the capture: call ``stand_in_cloud(n_pts, device)`` first).  The outputs are fresh tensors, or the caller's:
+    ``out`` a dict with a contiguous tensor per key of batch (``PC`` included), ``sel`` / ``info`` int32 buffers."""
+    if "PC" in extras:
+        raise ValueError("train_batch_select: 'PC' is the cloud argument, not an extra")
+    if PC.dim() != 3 or PC.shape[2] != 3:
+        raise ValueError(f"train_batch_select: expects PC (M, n_pts, 3), got {tuple(PC.shape)}")
+    if stand_in is None:
+        stand_in = stand_in_cloud(PC.shape[1], PC.device)
+    names = ["PC"] + list(extras)
+    if out is not None and set(out) != set(names):
+        raise ValueError(f"train_batch_select: out expects the keys {sorted(names)}, got {sorted(out)}")
+    segs = [(PC if k == "PC" else extras[k], None if out is None else out[k], stand_in if k == "PC" else None) for k in names]
+    dsts, sel, info = ops.batch_select(status, keep, segs, sel=sel, info=info)
+    return dict(zip(names, dsts)), sel, info

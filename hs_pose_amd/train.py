@@ -10,13 +10,19 @@ optimizer of ``hs_pose_amd.solver``:
 
 ``TrainDriver.step(total_loss)`` is the body of that loop for one batch.  With ``check_nan=False`` the NaN test
 (the loop's only host synchronisation besides logging) is skipped.
+
+``FrameTrainStep`` is that step started from raw frames: the training loader's front end (``pc_sample.train_batch_to_pcl``), the
+choice of the kept items (``pc_sample.train_batch_select``) and ``graph.GraphedTrainStep``'s body as ONE replay.
 """
 import math
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
+from . import pc_sample
 from .config import FLAGS
+from .graph import GraphedTrainStep
 from .parallel import mean_flat_gradients
 from .solver import build_lr_rate, build_optimizer
 
@@ -87,3 +93,132 @@ class TrainDriver:
         if 'scheduler' in ckpt:
             self.scheduler.load_state_dict(ckpt['scheduler'])
         return ckpt.get('epoch', -1) + 1
+
+
+class FrameTrainStep:
+    """One training step from raw frames: a batch of ``M`` items with spares goes in, the first ``keep`` good ones are picked
+    on the device, and augmentation, network, the 19 losses, backward and the squared gradient norm follow in the same
+    hipGraph; ``run()`` is one replay plus the fused optimizer launch.
+
+    ``frames``: depth (M,H,W) uint16 or fp32 mm and labels (M,H,W) uint8 on the device, inst_ids (M,), bboxes_xyxy (M,4) on the
+    host, K (3,3) or (M,3,3).  ``items``: the per-item device tensors of ``HSPose.forward`` with M rows (obj_id, gt_R, gt_t,
+    gt_s, mean_shape, sym, aug_bb, aug_rt_t, aug_rt_r, model_point, nocs_scale).  M >= keep: the loader sends keep items plus
+    spares.  Both are copied into static buffers; ``load(frames=..., items=...)`` copies the next M items in (device copies and
+    the pinned ring: nothing waits).  n_pts, out_size, min_pts and mask_pro are ``train_batch_to_pcl``'s, fixed when the
+    object is built; the sampler (None: the module's) is ``train_batch_to_pcl``'s device sampler.
+
+    Host work per ``run()``, in this fixed order: (1) ``pc_sample.dzi_windows(bboxes_xyxy, H, W)`` on numpy's generator -- M
+    windows in item order, spares included -- whose transform rows go up through the pinned ring; (2) ``sampler.advance()``;
+    (3) ``GraphedTrainStep``'s own draws on the CPU default generator: the jitter noise of keep clouds, then the two
+    ``randperm``s.  Then the replay, then the optimizer launch and ``scheduler.step()`` outside the graph.
+
+    A rejected item (``train_batch_to_pcl``'s status) is answered as the reference loader answers it, by moving on to the next
+    index: ``sel`` (keep,) int32 names the items the step trained on, ``info`` (2,) int32 = [good items, min(good items, keep)],
+    both static device tensors (include/hsp.h: hsp_batch_select); ``batch`` is the selected batch itself, clouds included, and
+    ``status`` (M,) the front end's verdict on every item, static too.  With fewer than keep good items the good ones repeat;
+    with none the network runs on ``pc_sample.stand_in_cloud`` and the extras of items 0 .. keep-1, never on NaN rows.
+
+    ``run(check=True)`` reads info and the loss's NaN flag after the replay -- one small device->host copy, the cost of
+    ``GraphedTrainStep.run(check_nan=True)`` -- and returns False, with neither optimizer step nor scheduler step, when no item
+    was good or the loss is NaN (the reference's skip, engine/train.py:91-95).  ``run(check=False)`` never waits: AN
+    ALL-REJECTED BATCH THEN TRAINS ONE STEP ON THE STAND-IN CLOUD.  ``info[0] == 0`` says when that happened; the remedy is
+    more spares.
+
+    Build it before the network's first eager backward (see ``GraphedTrainStep``).  Building draws like one ``run()`` does on
+    numpy's and torch's generators (the warm-up needs windows and noise) and leaves the sampler's state as it found it."""
+
+    def __init__(self, network, optimizer, frames, items, keep, scheduler=None, sampler=None, n_pts=None, out_size=None,
+                 min_pts=50, mask_pro=None, max_norm=5, warmup=3):
+        depth = frames["depth"]
+        dev = depth.device
+        if depth.dim() != 3 or not 1 <= int(keep) <= depth.shape[0]:
+            raise ValueError(f"FrameTrainStep: expects depth (M,H,W) with 1 <= keep <= M, got {tuple(depth.shape)}, keep {keep}")
+        self.M, self.H, self.W = depth.shape
+        self.keep = int(keep)
+        self.n_pts = int(FLAGS.random_points if n_pts is None else n_pts)
+        self.out_size = int(FLAGS.img_size if out_size is None else out_size)
+        self.sampler = pc_sample.resolve_sampler("device" if sampler is None else sampler, dev)
+        if self.sampler is None:
+            raise ValueError("FrameTrainStep: expects a device sampler; there is no host-draw form of the training front end")
+        self.depth = depth.detach().clone()
+        self.labels = frames["labels"].detach().clone()
+        self.inst_ids = torch.empty(self.M, dtype=torch.int32, device=dev)
+        self.xf = torch.empty(self.M, 3, dtype=torch.float64, device=dev)
+        self.K = torch.empty(self._K_rows(frames["K"]).shape, dtype=torch.float64, device=dev)
+        self.items = {k: v.detach().clone() for k, v in items.items()}
+        for k, v in self.items.items():
+            if not v.is_cuda or v.dim() < 1 or v.shape[0] != self.M:
+                raise ValueError(f"FrameTrainStep: items[{k!r}] expects a device tensor with {self.M} rows, got {tuple(v.shape)}")
+        self.sel = torch.zeros(self.keep, dtype=torch.int32, device=dev)
+        self.info = torch.zeros(2, dtype=torch.int32, device=dev)
+        self.status = self.batch = None
+        self._load_small(frames)
+        pc_sample.stand_in_cloud(self.n_pts, dev)               # (made here: an upload cannot happen inside the capture)
+
+        def front_end():
+            PC, self.status = pc_sample.train_batch_to_pcl(self.depth, self.labels, self.inst_ids, self.xf, None, self.K,
+                                                           n_pts=self.n_pts, out_size=self.out_size, min_pts=min_pts,
+                                                           mask_pro=mask_pro, sampler=self.sampler)
+            self.batch = pc_sample.train_batch_select(PC, self.status, self.keep, self.items, sel=self.sel, info=self.info)[0]
+            return self.batch
+
+        shapes = {"PC": torch.empty(self.keep, self.n_pts, 3, device=dev)}
+        shapes.update({k: torch.empty((self.keep,) + tuple(v.shape[1:]), dtype=v.dtype, device=dev) for k, v in self.items.items()})
+        self._windows()
+        state = self.sampler.get_state()                        # (the eager warm-up calls advance; the captured call does not)
+        self.graphed = GraphedTrainStep(network, optimizer, shapes, scheduler=scheduler, max_norm=max_norm, warmup=warmup,
+                                        prologue=front_end)
+        self.sampler.set_state(state)
+
+    @staticmethod
+    def _K_rows(K):
+        K = K.detach().cpu().numpy() if isinstance(K, torch.Tensor) else np.asarray(K)
+        return np.ascontiguousarray(K, dtype=np.float64).reshape(-1, 9)
+
+    def _load_small(self, frames):
+        dev = self.depth.device
+        if "inst_ids" in frames:
+            ids = frames["inst_ids"]
+            ids = ids.detach().cpu().numpy() if isinstance(ids, torch.Tensor) else np.asarray(ids)
+            pc_sample._upload(ids.reshape(self.M), np.int32, dev, out=self.inst_ids)
+        if "K" in frames:
+            pc_sample._upload(self._K_rows(frames["K"]), np.float64, dev, out=self.K)
+        if "bboxes_xyxy" in frames:
+            boxes = np.array(frames["bboxes_xyxy"])
+            if boxes.shape != (self.M, 4):
+                raise ValueError(f"FrameTrainStep: expects bboxes_xyxy ({self.M},4) on the host, got {boxes.shape}")
+            self.bboxes = boxes
+
+    def _windows(self):
+        centers, scales = pc_sample.dzi_windows(self.bboxes, self.H, self.W)
+        pc_sample._upload(pc_sample.roi_transform(centers, scales, self.out_size), np.float64, self.xf.device, out=self.xf)
+
+    def load(self, frames=None, items=None):
+        """copy the next M items into the static buffers: depth / labels / items device to device, inst_ids / K through the
+        pinned ring, bboxes_xyxy kept on the host for the next ``run()``'s windows; any subset of the keys"""
+        if frames is not None:
+            for k, dst in (("depth", self.depth), ("labels", self.labels)):
+                if k in frames:
+                    dst.copy_(frames[k], non_blocking=True)
+            self._load_small(frames)
+        if items is not None:
+            for k, v in items.items():
+                self.items[k].copy_(v, non_blocking=True)
+
+    @property
+    def loss_dict(self):
+        return self.graphed.loss_dict
+
+    @property
+    def total(self):
+        return self.graphed.total
+
+    def run(self, check=True):
+        """one training step from the frames in the static buffers; see the class text for ``check``"""
+        self._windows()
+        self.sampler.advance()
+        self.graphed.replay()
+        if check and bool((self.info[0] == 0) | torch.isnan(self.graphed.total).any()):
+            return False
+        self.graphed.apply()
+        return True

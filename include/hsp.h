@@ -809,6 +809,37 @@ int hsp_frames_to_pcl_u16(const uint16_t *depth, long long depth_stride, int H, 
                           const int32_t *src, long long src_stride, const int32_t *choose, int n, int S, float *pc,
                           hspStream_t stream);
 
+/* The kept items of a training batch: the loader answers a rejected item by moving on to the next index
+ * (datasets/load_data.py:254-278), so a batch always holds its full number of good items.  Here the batch arrives with spares,
+ * M >= keep items with the status of the chain above, and ONE launch picks the kept ones and gathers every per-item tensor:
+ * no device->host copy, no counter shared between workgroups, plain vector stores, no arithmetic on the data.
+ *
+ * status (M) int32 on the device: non-zero = rejected (any bit counts, negative values included).  segs: a HOST array of nseg
+ * segments, copied into the launch's arguments: src (M, row_bytes) and dst (keep, row_bytes) dense device rows that do not
+ * overlap, fill NULL or one device row of row_bytes.  sel (keep) int32, info (2) int32.
+ * 1 <= keep <= M <= HSP_BATCH_SELECT_MAX_ITEMS, 0 <= nseg <= HSP_BATCH_SELECT_MAX_SEGS (0: sel and info only), row_bytes a
+ * positive multiple of 4, src / dst / fill 4-byte aligned; anything else -- also a NULL status, sel or info, a NULL src or dst in
+ * a listed segment, a src that overlaps its dst -- is HSP_ERR_BAD_ARG before any launch.
+ *
+ * THE RULE.  V = the number of items with status 0, v_0 < v_1 < ... < v_{V-1} those items in ascending order.
+ *   info = {V, min(V, keep)}
+ *   V >= 1:  sel[j] = v_{j mod V}, j = 0 .. keep-1: the first keep good items in loader order; when the spares run out the good
+ *            ones repeat in order.  No row of a rejected item is read into a dst.
+ *   V == 0:  sel[j] = j.  A segment with a fill row gets that row in every dst row (the clouds: the network is never given the
+ *            NaN rows of a rejected item); a segment without copies rows 0 .. keep-1.
+ *   dst[j] = src[sel[j]] byte for byte (NaN payloads and integer rows pass unchanged).
+ * Rows move 16 bytes at a time where row_bytes and both rows' addresses allow, else 4. */
+#define HSP_BATCH_SELECT_MAX_SEGS 16
+#define HSP_BATCH_SELECT_MAX_ITEMS 1024
+typedef struct HspSelectSeg {
+    const void *src;              /* (M, row_bytes) */
+    void *dst;                    /* (keep, row_bytes) */
+    const void *fill;             /* NULL, or the row every dst row gets when no item is good */
+    long long row_bytes;
+} HspSelectSeg;
+int hsp_batch_select(const int32_t *status, int M, int keep, const HspSelectSeg *segs, int nseg, int32_t *sel, int32_t *info,
+                     hspStream_t stream);
+
 /* ---- pose matrix assembly -----------------------------------------------------------------------
  * replaces generate_RT([p_green,p_red],[f_green,f_red], T, 'vec', sym)     tools/geom_utils.py:232-244
  * (with to_R_matrices / get_vertical_rot_vec_in_batch / get_rot_mat_y_first, tools/rot_utils.py:39-100)
