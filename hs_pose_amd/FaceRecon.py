@@ -12,7 +12,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import gcn3d, ops, ops_bf16
+from . import gcn3d, ops, ops_bf16, pc_sample
 from .config import FLAGS
 
 
@@ -139,7 +139,8 @@ class FaceRecon(nn.Module):
         # of the bf16 x3 products, BatchNorm's first pass not fused into the layer's out product).  Off by default: the step that is
         # timed is the fast one; tests/test_gpu_stack.py holds the switched-on form to 1e-4.
         exact = (not self.training or self.exact_train) and self.feature_dtype == torch.float32
-        with ops.x3_scope(self._x3), ops.exact_scope(exact):
+        # (one scope of draws per forward: under FLAGS.step_draws = 'device' both Pool_layers' rows come from one key)
+        with ops.x3_scope(self._x3), ops.exact_scope(exact), pc_sample.draw_scope(None, vertices.device):
             return self._forward(vertices, cat_id)
 
     def _forward(self, vertices, cat_id):

@@ -14,7 +14,7 @@ import torch.nn as nn
 from .augment import data_augment
 from .config import FLAGS
 from .losses import control_loss, fs_net_loss, geo_transform_loss, prop_rot_loss, recon_6face_loss
-from .pc_sample import PC_sample
+from .pc_sample import PC_sample, draw_scope
 from .PoseNet9D import PoseNet9D
 
 
@@ -57,16 +57,19 @@ class HSPose(nn.Module):
         obj_mask = None
         sketch = None
         PC = PC.detach()
-        if FLAGS.train:
-            with torch.no_grad():
-                PC, gt_R, gt_t, gt_s = self.data_augment(PC, gt_R, gt_t, gt_s, mean_shape, sym, aug_bb, aug_rt_t,
-                                                         aug_rt_r, model_point, nocs_scale, obj_id)
+        # one scope of draws for the forward: under FLAGS.step_draws = 'device' the augmentation and the Pool_layers draw on the
+        # device under one key, advanced once here (never inside a capture); under 'host' nothing changes
+        with draw_scope(None, PC.device):
+            if FLAGS.train:
+                with torch.no_grad():
+                    PC, gt_R, gt_t, gt_s = self.data_augment(PC, gt_R, gt_t, gt_s, mean_shape, sym, aug_bb, aug_rt_t,
+                                                             aug_rt_r, model_point, nocs_scale, obj_id)
 
-        runner = self.graphed_posenet.get(tuple(PC.shape)) if self.graphed_posenet else None
-        if runner is not None and self.training and torch.is_grad_enabled():
-            net_out = runner(PC, obj_id)                      # two hipGraph replays behind one autograd node
-        else:
-            net_out = self.posenet(PC, obj_id)
+            runner = self.graphed_posenet.get(tuple(PC.shape)) if self.graphed_posenet else None
+            if runner is not None and self.training and torch.is_grad_enabled():
+                net_out = runner(PC, obj_id)                      # two hipGraph replays behind one autograd node
+            else:
+                net_out = self.posenet(PC, obj_id)
         out = dict(zip(_NET_OUTPUTS, net_out))
         # the reference's 16 keys in its order (HSPose.py:67-82): mask / sketch are always None in this training stage
         output_dict.update(mask=obj_mask, sketch=sketch, recon=out['recon'], PC=PC)

@@ -185,6 +185,9 @@ SIGNATURES = {
     "hsp_gemm_rows_plan": (_i, [_i, _i, _i, _i, _i, _i, _vp]),
     "hsp_gemm_x3_plan": (_i, [_i, _i, _i, _i, _i, _i, _vp]),
     "hsp_pose_augment": (_i, [_vp] * 14 + [_i, _i, _i] + [ctypes.c_float] * 4 + [_vp] * 5),
+    "hsp_pose_augment_keyed": (_i, [_vp] * 13 + [ctypes.c_float, _i, _i, _i] + [ctypes.c_float] * 4 + [_vp] * 5),
+    "hsp_pool_rows_draw": (_i, [_vp, _i, _i, _i, _vp, _vp]),
+    "hsp_dzi_windows": (_i, [_vp, _vp, _i, _i, _i, _i, ctypes.c_double, ctypes.c_double, ctypes.c_double, _vp, _vp]),
 }
 
 

@@ -95,10 +95,18 @@ FUSED = True      # device batches: one libhsp launch (hsp_pose_augment); False:
 def _data_augment_fused(PC, gt_R, gt_t, gt_s, mean_shape, sym, aug_bb, aug_rt_t, aug_rt_r, model_point, nocs_scale, obj_ids):
     """the same augmentation through ``hsp_pose_augment`` (csrc/losses.hip): the six uniform draws are made here, on the
     device generator and in the composition's order (flag, flag, flag, ey_up, ey_down, flag; then the jitter noise on the
-    CPU generator), so a seeded run consumes both generators exactly as the torch composition below does."""
-    from . import ops
+    CPU generator), so a seeded run consumes both generators exactly as the torch composition below does.  Under device draws
+    (``FLAGS.step_draws = 'device'`` or a ``pc_sample.draw_scope`` of a device sampler) and with no ``jitter_noise_feed`` in scope,
+    the launch is ``hsp_pose_augment_keyed``: all of them drawn in the kernel under the scope's key, no generator touched."""
+    from . import ops, pc_sample
     bs, N, _ = PC.shape
     dev = PC.device
+    if _noise_feed is None:
+        with pc_sample.draw_scope(None, dev) as device_draws:
+            if device_draws is not None:     # FLAGS.step_draws = 'device': the uniforms and the jitter are drawn in the kernel
+                return ops.pose_augment_keyed(device_draws.key, PC, gt_R, gt_t, gt_s, mean_shape, sym, aug_bb, aug_rt_t, aug_rt_r,
+                                              model_point, nocs_scale, obj_ids, FLAGS.aug_pc_r, FLAGS.aug_bb_pro,
+                                              FLAGS.aug_rt_pro, FLAGS.aug_bc_pro, FLAGS.aug_pc_pro)
     draws = torch.cat([torch.rand((bs, 1), device=dev) for _ in range(6)], dim=1).t().contiguous()      # (6, bs)
     noise = _noise_feed if _noise_feed is not None else _host_rand(PC) * FLAGS.aug_pc_r
     f = lambda t, shape: ops._req(t.detach().float().reshape(shape), torch.float32, "data_augment")

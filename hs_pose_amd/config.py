@@ -41,6 +41,11 @@ class _Flags:
         pc_sampler='host',      # (not in the reference) who draws the rows an instance cloud keeps (pc_sample.py): 'host' -- the
                                 # reference's draws on numpy's global generator -- or 'device' -- a keyed counter-based draw
                                 # inside the front end (pc_sample.DeviceSampler), no count copy and no sync
+        step_draws='host',      # (not in the reference) who makes the draws of a forward or a replay -- the Pool_layers' kept
+                                # rows, the augmentation's uniforms and jitter, the training loader's DZI windows: 'host' -- the
+                                # reference's draws on torch's and numpy's generators, uploaded before a replay -- or 'device' --
+                                # keyed draws inside the forward / the captured body (pc_sample.resolve_draws; include/hsp.h:
+                                # "keyed draws of a step"): the same distributions, not the same draws, no host generator touched
     )
 
     def __init__(self):

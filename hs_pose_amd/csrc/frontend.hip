@@ -24,6 +24,7 @@
 #include <tuple>
 
 #include "common.h"
+#include "keyed_draws.h"
 
 namespace hsp {
 
@@ -337,45 +338,6 @@ __global__ __launch_bounds__(256) void frames_to_pcl_kernel(const D* __restrict_
 // A stand-alone launch between the compaction and the back-projection: one lane per (instance, kept row), uint32 arithmetic
 // only.  The permutation is a 4-round balanced Feistel network over the smallest even width that holds the count, cycle-walked
 // into [0, c): O(S) work per instance whatever c, no selection pass, no scratch.
-__device__ __forceinline__ uint32_t fmix32(uint32_t h) {
-    h ^= h >> 16;
-    h *= 0x85ebca6bu;
-    h ^= h >> 13;
-    h *= 0xc2b2ae35u;
-    h ^= h >> 16;
-    return h;
-}
-
-__device__ __forceinline__ uint32_t absorb(uint32_t h, uint32_t w) { return fmix32((h ^ w) + 0x9e3779b9u); }
-
-// kj of instance j under the key {seed, call}
-__device__ __forceinline__ uint32_t instance_key(const unsigned long long* __restrict__ key, int j) {
-    const unsigned long long seed = key[0], call = key[1];
-    uint32_t kj = absorb(0u, (uint32_t)seed);
-    kj = absorb(kj, (uint32_t)(seed >> 32));
-    kj = absorb(kj, (uint32_t)call);
-    kj = absorb(kj, (uint32_t)(call >> 32));
-    return absorb(kj, (uint32_t)j);
-}
-
-// P(s) for s < c, c >= 1: the cycle-walked 4-round Feistel permutation of [0, c) with round keys absorb(k, 0..3)
-__device__ __forceinline__ uint32_t feistel_permute(uint32_t s, uint32_t c, uint32_t k) {
-    const uint32_t k0 = absorb(k, 0u), k1 = absorb(k, 1u), k2 = absorb(k, 2u), k3 = absorb(k, 3u);
-    const int bits = c <= 1u ? 0 : 32 - __clz((int)(c - 1u));
-    const int half = max(1, (bits + 1) / 2);
-    const uint32_t mask = (1u << half) - 1u;
-    uint32_t x = s;
-    do {
-        uint32_t L = x >> half, R = x & mask, t;
-        t = L ^ (fmix32(R ^ k0) & mask); L = R; R = t;
-        t = L ^ (fmix32(R ^ k1) & mask); L = R; R = t;
-        t = L ^ (fmix32(R ^ k2) & mask); L = R; R = t;
-        t = L ^ (fmix32(R ^ k3) & mask); L = R; R = t;
-        x = (L << half) | R;
-    } while (x >= c);
-    return x;
-}
-
 __global__ __launch_bounds__(256) void sample_ids_kernel(const int32_t* __restrict__ count, int stride, int n, int S,
                                                          int min_pts, int min_depth_pts, int short_mode,
                                                          const unsigned long long* __restrict__ key,
@@ -401,6 +363,48 @@ __global__ __launch_bounds__(256) void sample_ids_kernel(const int32_t* __restri
             out = (int)feistel_permute((uint32_t)s, (uint32_t)c, kj);
     }
     choose[e] = out;
+}
+
+// ---- the keyed draws of a step (include/hsp.h: "keyed draws of a step" states each stream) -----------------------------------
+// What a forward or a replay used to be handed by the host: the rows the Pool_layers keep and the training loader's DZI windows
+// (the augmentation's share lives with its kernel, losses.hip).  Streams j >= 2^31, apart from every row draw (j < 65536).
+
+// rows[off_l + s] = P_l(s), s < m_l: level l keeps m_l = n_l / rate of n_l rows, n_1 = m_0; one lane per kept row of either level
+__global__ __launch_bounds__(256) void pool_rows_kernel(const unsigned long long* __restrict__ key, int n0, int m0, int m1,
+                                                        int32_t* __restrict__ rows) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= m0 + m1) return;
+    const int level = e >= m0 ? 1 : 0;
+    const uint32_t s = (uint32_t)(level ? e - m0 : e), c = (uint32_t)(level ? m0 : n0);
+    rows[e] = (int)feistel_permute(s, c, instance_key(key, (int)(0x80000000u | (uint32_t)level)));
+}
+
+// aug_bbox_DZI ('uniform', tools/dataset_utils.py:24-61) and roi_transform of item k in float64, one rounding per operation in
+// the order pc_sample.dzi_windows / pc_sample.roi_transform perform them; one lane per item
+__global__ __launch_bounds__(64) void dzi_windows_kernel(const int32_t* __restrict__ bboxes, const unsigned long long* __restrict__ key,
+                                                         int M, double frame_max, double O, double pad_scale, double scale_ratio,
+                                                         double shift_ratio, double* __restrict__ xf) {
+    const int k = blockIdx.x * 64 + threadIdx.x;
+    if (k >= M) return;
+    const uint32_t kz = absorb(instance_key(key, (int)(0x82000000u | (uint32_t)k)), 0xfffffffbu);
+    const double u0 = word_to_f64(absorb(kz, 0u)), u1 = word_to_f64(absorb(kz, 1u)), u2 = word_to_f64(absorb(kz, 2u));
+    const int x1 = bboxes[k * 4], y1 = bboxes[k * 4 + 1], x2 = bboxes[k * 4 + 2], y2 = bboxes[k * 4 + 3];
+    const double cx = __dmul_rn(0.5, (double)((long long)x1 + x2)), cy = __dmul_rn(0.5, (double)((long long)y1 + y2));
+    const long long bh = (long long)y2 - y1, bw = (long long)x2 - x1;
+    const double sr = __dadd_rn(1.0, __dmul_rn(scale_ratio, __dsub_rn(__dmul_rn(2.0, u0), 1.0)));
+    const double sx = __dmul_rn(shift_ratio, __dsub_rn(__dmul_rn(2.0, u1), 1.0));
+    const double sy = __dmul_rn(shift_ratio, __dsub_rn(__dmul_rn(2.0, u2), 1.0));
+    const double ccx = __dadd_rn(cx, __dmul_rn((double)bw, sx)), ccy = __dadd_rn(cy, __dmul_rn((double)bh, sy));
+    const double side = (double)(bh > bw ? bh : bw);
+    const double scale = fmin(__dmul_rn(__dmul_rn(side, sr), pad_scale), frame_max);
+    // roi_transform: the inverse of the forward matrix a = O / scale, tx = O/2 - a * cx, ty = O/2 - a * cy
+    const double a = __ddiv_rn(O, scale), half_O = __ddiv_rn(O, 2.0);
+    const double tx = __dsub_rn(half_O, __dmul_rn(a, ccx)), ty = __dsub_rn(half_O, __dmul_rn(a, ccy));
+    const double D = __ddiv_rn(1.0, __dmul_rn(a, a));
+    const double m0 = __dmul_rn(a, D), nm0 = -m0;
+    xf[k * 3] = m0;
+    xf[k * 3 + 1] = __dmul_rn(nm0, tx);
+    xf[k * 3 + 2] = __dmul_rn(nm0, ty);
 }
 
 // ---- the training loader's chain (datasets/load_data.py:228-278): a batch of frames, the mask perturbed before the cut ------
@@ -807,6 +811,28 @@ extern "C" int hsp_sample_ids(const int32_t* count, int count_stride, int n, int
     if ((long long)n * S > 2147483647LL) return HSP_ERR_BAD_ARG;
     hipLaunchKernelGGL(sample_ids_kernel, dim3((unsigned)(((long long)n * S + 255) / 256)), dim3(256), 0, as_stream(stream), count, count_stride, n,
                        S, min_pts, min_depth_pts, short_mode, key, choose, status);
+    return check_launch();
+}
+
+extern "C" int hsp_pool_rows_draw(const unsigned long long* key, int n0, int rate, int levels, int32_t* rows,
+                                  hspStream_t stream) {
+    if (!key || !rows || n0 <= 0 || rate <= 0 || (levels != 1 && levels != 2)) return HSP_ERR_BAD_ARG;
+    const int m0 = n0 / rate, m1 = levels == 2 ? m0 / rate : 0;
+    if (m0 == 0 || (levels == 2 && m1 == 0)) return HSP_ERR_BAD_ARG;
+    hipLaunchKernelGGL(pool_rows_kernel, dim3((unsigned)(((long long)m0 + m1 + 255) / 256)), dim3(256), 0, as_stream(stream), key,
+                       n0, m0, m1, rows);
+    return check_launch();
+}
+
+extern "C" int hsp_dzi_windows(const int32_t* bboxes, const unsigned long long* key, int M, int H, int W, int out_size,
+                               double pad_scale, double scale_ratio, double shift_ratio, double* xf, hspStream_t stream) {
+    if (!bboxes || !key || !xf || M <= 0 || M > 65535 || H <= 0 || W <= 0 || out_size <= 0 || out_size > 46340)
+        return HSP_ERR_BAD_ARG;
+    if (!(pad_scale > 0.0) || !(scale_ratio >= 0.0 && scale_ratio < 1.0) || !(shift_ratio >= 0.0) || !(pad_scale < INFINITY) ||
+        !(shift_ratio < INFINITY))
+        return HSP_ERR_BAD_ARG;
+    hipLaunchKernelGGL(dzi_windows_kernel, dim3((M + 63) / 64), dim3(64), 0, as_stream(stream), bboxes, key, M,
+                       (double)(H > W ? H : W), (double)out_size, pad_scale, scale_ratio, shift_ratio, xf);
     return check_launch();
 }
 

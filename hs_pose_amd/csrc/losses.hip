@@ -18,6 +18,7 @@
 //              points pass 2 (per point: the closed-form gradients of the per-point terms + the moment-sum gradients)
 // All sums are taken in a fixed order (one workgroup per cloud, fixed tree): results are bit-reproducible run to run.
 #include "common.h"
+#include "keyed_draws.h"
 
 namespace hsp {
 namespace {
@@ -675,23 +676,29 @@ __global__ __launch_bounds__(256) void loss_points_bwd_kernel(
 // One workgroup per cloud; a thread carries a point through the four stages (no cross-point dependency), the tapered
 // model's extent (the new size) is a min / max over the model points through LDS.  draws (6,B): u_bb, u_rt, u_bc,
 // ey_up, ey_down (raw uniforms, mapped to [0.8, 1.2)), u_pc -- drawn by the caller in the reference's order.
+// KEYED (hsp_pose_augment_keyed): the same six uniforms and the jitter factors are words of cloud b's stream under the device
+// key instead (include/hsp.h: "keyed draws of a step"); draws and noise are not read.
+template <bool KEYED>
 __global__ __launch_bounds__(256) void augment_kernel(const float* __restrict__ PC, const float* gt_R, const float* gt_t,
                                                       const float* gt_s, const float* mean_shape, const float* sym,
                                                       const float* aug_bb, const float* aug_rt_t, const float* aug_rt_r,
                                                       const float* __restrict__ model_point, const float* nocs_scale,
                                                       const float* obj_id, const float* draws, const float* __restrict__ noise,
-                                                      int B, int N, int M, float p_bb, float p_rt, float p_bc, float p_pc,
+                                                      const unsigned long long* __restrict__ key, float aug_pc_r, int B, int N, int M, float p_bb, float p_rt, float p_bc, float p_pc,
                                                       float* __restrict__ PC_out, float* R_out, float* t_out, float* s_out) {
     __shared__ float red[6][256];
     const int b = blockIdx.x, tid = threadIdx.x;
     float R[9], t[3], s[3], ms[3], ar[9], at[3], k[3];
     for (int i = 0; i < 9; ++i) { R[i] = gt_R[b * 9 + i]; ar[i] = aug_rt_r[b * 9 + i]; }
     for (int i = 0; i < 3; ++i) { t[i] = gt_t[b * 3 + i]; s[i] = gt_s[b * 3 + i]; ms[i] = mean_shape[b * 3 + i]; at[i] = aug_rt_t[b * 3 + i]; }
-    const bool f_bb = draws[0 * B + b] < p_bb, f_rt = draws[1 * B + b] < p_rt;
+    const uint32_t ka = KEYED ? absorb(instance_key(key, (int)(0x81000000u | (uint32_t)b)), 0xfffffffcu) : 0u;
+    float u[6];
+    for (int i = 0; i < 6; ++i) u[i] = KEYED ? word_to_f32(absorb(ka, (uint32_t)i)) : draws[i * B + b];
+    const bool f_bb = u[0] < p_bb, f_rt = u[1] < p_rt;
     const float obj = obj_id[b];
-    const bool f_bc = draws[2 * B + b] < p_bc && (obj == 5.f || obj == 1.f);
-    const float ey_up = draws[3 * B + b] * (1.2f - 0.8f) + 0.8f, ey_down = draws[4 * B + b] * (1.2f - 0.8f) + 0.8f;
-    const bool f_pc = draws[5 * B + b] < p_pc;
+    const bool f_bc = u[2] < p_bc && (obj == 5.f || obj == 1.f);
+    const float ey_up = u[3] * (1.2f - 0.8f) + 0.8f, ey_down = u[4] * (1.2f - 0.8f) + 0.8f;
+    const bool f_pc = u[5] < p_pc;
     // 1. box scaling (data_augmentation.py:70-79): x and z share the mean factor under rotational symmetry
     {
         const float a0 = aug_bb[b * 3], a1 = aug_bb[b * 3 + 1], a2 = aug_bb[b * 3 + 2];
@@ -763,7 +770,10 @@ __global__ __launch_bounds__(256) void augment_kernel(const float* __restrict__ 
             for (int i = 0; i < 3; ++i) p[i] = (o[0] * R[3 * i] + o[1] * R[3 * i + 1] + o[2] * R[3 * i + 2]) + t[i];
         }
         if (f_pc)
-            for (int i = 0; i < 3; ++i) p[i] = p[i] + noise[pn * 3 + i] * (p[i] - t[i]);
+            for (int i = 0; i < 3; ++i) {
+                const float f = KEYED ? word_to_f32(absorb(ka, 6u + (uint32_t)(n * 3 + i))) * aug_pc_r : noise[pn * 3 + i];
+                p[i] = p[i] + f * (p[i] - t[i]);
+            }
         for (int i = 0; i < 3; ++i) PC_out[pn * 3 + i] = p[i];
     }
 }
@@ -847,9 +857,25 @@ extern "C" int hsp_pose_augment(const float* PC, const float* gt_R, const float*
     if (!PC || !gt_R || !gt_t || !gt_s || !mean_shape || !sym || !aug_bb || !aug_rt_t || !aug_rt_r || !model_point ||
         !nocs_scale || !obj_id || !draws || !noise || !PC_out || !R_out || !t_out || !s_out || B <= 0 || N <= 0 || M <= 0)
         return HSP_ERR_BAD_ARG;
-    hipLaunchKernelGGL(augment_kernel, dim3(B), dim3(256), 0, as_stream(stream), PC, gt_R, gt_t, gt_s, mean_shape, sym, aug_bb,
-                       aug_rt_t, aug_rt_r, model_point, nocs_scale, obj_id, draws, noise, B, N, M, p_bb, p_rt, p_bc, p_pc, PC_out,
-                       R_out, t_out, s_out);
+    hipLaunchKernelGGL(augment_kernel<false>, dim3(B), dim3(256), 0, as_stream(stream), PC, gt_R, gt_t, gt_s, mean_shape, sym,
+                       aug_bb, aug_rt_t, aug_rt_r, model_point, nocs_scale, obj_id, draws, noise, nullptr, 0.f, B, N, M, p_bb, p_rt,
+                       p_bc, p_pc, PC_out, R_out, t_out, s_out);
+    return check_launch();
+}
+
+extern "C" int hsp_pose_augment_keyed(const float* PC, const float* gt_R, const float* gt_t, const float* gt_s,
+                                      const float* mean_shape, const float* sym, const float* aug_bb, const float* aug_rt_t,
+                                      const float* aug_rt_r, const float* model_point, const float* nocs_scale,
+                                      const float* obj_id, const unsigned long long* key, float aug_pc_r, int B, int N, int M,
+                                      float p_bb, float p_rt, float p_bc, float p_pc, float* PC_out, float* R_out, float* t_out,
+                                      float* s_out, hspStream_t stream) {
+    if (!PC || !gt_R || !gt_t || !gt_s || !mean_shape || !sym || !aug_bb || !aug_rt_t || !aug_rt_r || !model_point ||
+        !nocs_scale || !obj_id || !key || !PC_out || !R_out || !t_out || !s_out || B <= 0 || N <= 0 || M <= 0)
+        return HSP_ERR_BAD_ARG;
+    if (B > 0x1000000 || N > 0x20000000) return HSP_ERR_BAD_ARG;        // stream index 0x81000000 | b, word index 6 + 3 N < 2^32
+    hipLaunchKernelGGL(augment_kernel<true>, dim3(B), dim3(256), 0, as_stream(stream), PC, gt_R, gt_t, gt_s, mean_shape, sym,
+                       aug_bb, aug_rt_t, aug_rt_r, model_point, nocs_scale, obj_id, nullptr, nullptr, key, aug_pc_r, B, N, M, p_bb,
+                       p_rt, p_bc, p_pc, PC_out, R_out, t_out, s_out);
     return check_launch();
 }
 

@@ -8,7 +8,9 @@ With the host sampler (the default, ``FLAGS.pc_sampler = 'host'``) the front end
 the frame, one device->host copy of the counts, the sample draws on numpy's global generator.  Nothing can be captured around
 it: its draws need the counts on the host.  With a device sampler (``sampler='device'`` or a ``pc_sample.DeviceSampler``) it is
 ``pc_sample.frame_to_pcl_device``: three kernels, issued eagerly ahead of the replay with nothing copied back, or -- with
-``one_graph=True`` -- captured together with the network, so that a frame is a few small uploads and ONE replay.
+``one_graph=True`` -- captured together with the network, so that a frame is a few small uploads and ONE replay.  What that
+replay still takes from the host is the network's two Pool_layer permutations, drawn on the CPU generator before it; with
+``draws='device'`` (or ``FLAGS.step_draws = 'device'``) they are keyed draws inside the replay under the sampler's key as well.
 """
 import numpy as np
 import torch
@@ -23,7 +25,7 @@ class _FrameGraph:
     transforms, K, the class rows and the sampler's key.  Everything is issued on the capture stream, in order; the kernels'
     workspaces and outputs come from the capture's pool."""
 
-    def __init__(self, pipe, sampler, depth, masks, ids, xf, K, obj_id, n_pts, O):
+    def __init__(self, pipe, sampler, depth, masks, ids, xf, K, obj_id, n_pts, O, draws=None):
         dev = depth.device
         self.depth, self.masks = depth.clone(), masks.clone()
         self.ids = None if ids is None else pc_sample._upload(ids, np.int32, dev)
@@ -41,7 +43,8 @@ class _FrameGraph:
 
         n = xf.shape[0]
         self.graphed = GraphedInference(pipe.net, torch.empty(n, n_pts, 3, device=dev), self.obj_id,
-                                        pipe.mean_shapes[self.obj_id], pipe.sym_infos[self.obj_id], prologue=front_end)
+                                        pipe.mean_shapes[self.obj_id], pipe.sym_infos[self.obj_id], prologue=front_end,
+                                        draws=draws or "host")
 
     def load(self, pipe, depth, masks, ids, xf, K, obj_id):
         dev = depth.device
@@ -72,14 +75,19 @@ class FramePipeline:
     is queued, and returns None for a rejected frame as above; ``sync=False`` never waits and returns
     ``(pred_RT, pred_s, status (n,) int32)`` as device tensors -- the rows of an instance whose status is not 0 mean nothing
     (the network ran on a stand-in cloud for it).  ``one_graph=True`` (device sampler only) captures the front end with the
-    network: one graph per (instance count, frame shape, depth dtype, mask form), one replay per frame."""
+    network: one graph per (instance count, frame shape, depth dtype, mask form), one replay per frame.
+
+    ``draws``: None (follow ``FLAGS.step_draws`` at each call), 'host' -- the network's two Pool_layer permutations are drawn on
+    the CPU generator before each replay --, 'device' or a DeviceSampler: they are drawn inside the replay, keyed by the
+    pipeline's device sampler where it has one (one ``advance()`` per frame keys the cloud rows and the Pool rows alike), else by
+    the resolved sampler.  With ``one_graph=True`` a frame's result is then a function of the static buffers and the key alone."""
 
     def __init__(self, network, mean_shapes, sym_infos, n_pts=None, out_size=None, min_pts=2, sampler=None, one_graph=False,
-                 sync=True):
+                 sync=True, draws=None):
         self.net, self.mean_shapes, self.sym_infos = network, mean_shapes, sym_infos
         self.n_pts, self.out_size, self.min_pts = n_pts, out_size, min_pts
-        self.sampler, self.one_graph, self.sync = sampler, bool(one_graph), bool(sync)
-        self.graphs = {}                                         # instance count -> GraphedInference
+        self.sampler, self.one_graph, self.sync, self.draws = sampler, bool(one_graph), bool(sync), draws
+        self.graphs = {}                                         # instance count (device draws: and their sampler) -> GraphedInference
         self.frame_graphs = {}                                   # one_graph: (sampler, n, frame shape, dtype, ...) -> _FrameGraph
 
     def _network_input(self, PC, status):
@@ -97,6 +105,9 @@ class FramePipeline:
         if sampler is None and (self.one_graph or not self.sync):
             raise ValueError("FramePipeline: one_graph=True and sync=False need a device sampler (sampler='device', a DeviceSampler, "
                              "or FLAGS.pc_sampler = 'device'): the host draws wait for the counts")
+        draws = pc_sample.resolve_draws(self.draws, dev)
+        if draws is not None and sampler is not None:
+            draws = sampler                                      # one key per frame
         if n == 0:
             out = torch.zeros(0, 4, 4, device=dev), torch.zeros(0, 3, device=dev)
             return out if self.sync else out + (torch.zeros(0, dtype=torch.int32, device=dev),)
@@ -108,7 +119,7 @@ class FramePipeline:
             obj_id = torch.as_tensor(np.asarray(class_ids).astype(np.int64) - 1).to(dev, non_blocking=True)
             status = None
         elif self.one_graph:
-            graphed, status = self._replay_frame(sampler, depth, masks, inst_ids, centers, scales, K, class_ids)
+            graphed, status = self._replay_frame(sampler, depth, masks, inst_ids, centers, scales, K, class_ids, draws)
             PC = None
         else:
             PC, status = pc_sample.frame_to_pcl_device(depth, masks, centers, scales, K, self.n_pts, self.out_size, inst_ids,
@@ -117,11 +128,14 @@ class FramePipeline:
             obj_id = pc_sample._upload(np.asarray(class_ids).astype(np.int64) - 1, np.int64, dev)
         if PC is not None:                                       # the network's own graph, behind the eager front end
             mean_shape, sym = self.mean_shapes[obj_id], self.sym_infos[obj_id]
-            graphed = self.graphs.get(n)
+            slot = n if draws is None else (n, draws)
+            graphed = self.graphs.get(slot)
             if graphed is None:
-                graphed = self.graphs[n] = GraphedInference(self.net, PC, obj_id, mean_shape, sym)
+                graphed = self.graphs[slot] = GraphedInference(self.net, PC, obj_id, mean_shape, sym, draws=draws or "host")
             else:
                 graphed.load(PC, obj_id, mean_shape, sym)
+            if draws is not None and draws is not sampler:       # (the device front end has advanced its sampler for this frame)
+                draws.advance()
             graphed.run()
         pred_RT, pred_s = graphed.pred_RT.clone(), graphed.pred_s.clone()
         if not self.sync:
@@ -130,14 +144,14 @@ class FramePipeline:
             return None
         return pred_RT, pred_s
 
-    def _replay_frame(self, sampler, depth, masks, inst_ids, centers, scales, K, class_ids):
+    def _replay_frame(self, sampler, depth, masks, inst_ids, centers, scales, K, class_ids, draws=None):
         n_pts, O, xf, masks, ids, K = pc_sample._frame_args(masks, centers, scales, K.cpu() if isinstance(K, torch.Tensor) else K,
                                                             self.n_pts, self.out_size, inst_ids)
         obj_id = np.asarray(class_ids).astype(np.int64) - 1
-        key = (sampler, xf.shape[0], tuple(depth.shape), depth.dtype, masks.dim(), ids is None, K.shape[0], n_pts, O)
+        key = (sampler, xf.shape[0], tuple(depth.shape), depth.dtype, masks.dim(), ids is None, K.shape[0], n_pts, O, draws)
         fg = self.frame_graphs.get(key)
         if fg is None:
-            fg = self.frame_graphs[key] = _FrameGraph(self, sampler, depth, masks, ids, xf, K, obj_id, n_pts, O)
+            fg = self.frame_graphs[key] = _FrameGraph(self, sampler, depth, masks, ids, xf, K, obj_id, n_pts, O, draws)
         else:
             fg.load(self, depth, masks, ids, xf, K, obj_id)
         sampler.advance()

@@ -22,7 +22,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import ops
+from . import ops, pc_sample
 from .config import FLAGS
 
 # ------------------------------------------------------------------------------------------------
@@ -125,9 +125,13 @@ def prefetch_levels(vertices, k, pool_k=None, rates=(4, 4), samplers=(None, None
     if _pool_feed is not None:
         sel1, sel2 = next(_pool_feed), next(_pool_feed)
         assert sel1.numel() == n1 and sel2.numel() == n2 and sel1.dtype == torch.int32
-    else:                                                    # the reference's own draws, in its order (pool_1, then pool_2)
-        sel1 = torch.randperm(n0)[:n1].to(device=vertices.device, dtype=torch.int32)
-        sel2 = torch.randperm(n1)[:n2].to(device=vertices.device, dtype=torch.int32)
+    else:
+        with pc_sample.draw_scope(None, vertices.device) as device_draws:
+            if device_draws is not None:                     # FLAGS.step_draws = 'device': both levels' rows in one keyed launch
+                sel1, sel2 = device_draws.pool_rows(n0, 4, levels=2)
+            else:                                            # the reference's own draws, in its order (pool_1, then pool_2)
+                sel1 = torch.randperm(n0)[:n1].to(device=vertices.device, dtype=torch.int32)
+                sel2 = torch.randperm(n1)[:n2].to(device=vertices.device, dtype=torch.int32)
     # with the input cloud's own search in the same pair of launches where the shapes allow (its tie pass rides in the levels' launch)
     geo = ops.geometry_all(vertices, k, pool_k, sel1, sel2, k1, pool_k, k2) if k > pool_k else None
     if geo is not None:
@@ -338,6 +342,10 @@ class Pool_layer(nn.Module):
     draw on the CPU default generator shared by the whole batch (same RNG consumption as the
     reference, so fixed-seed runs pick the same points).
 
+    With ``config.FLAGS.step_draws = 'device'`` (or inside a ``pc_sample.draw_scope`` of a device sampler) the 'random' rows are the
+    keyed draw of ``ops.pool_rows_draw`` instead: the same distribution, made on the device, the CPU generator untouched.  A
+    ``pool_index_feed`` in scope wins over either.
+
     ``sampler``: 'random' -- the above --, 'fps' -- every cloud keeps the ``int(N / pooling_rate)`` rows that farthest-point
     sampling picks on its own ``vertices[b]`` (ops.fps_levels: the contract of ops.fps, and a picked row is never picked again),
     computed on the device: no host generator, no pool_index_feed, the output a function of the cloud alone --, or None: follow
@@ -380,8 +388,11 @@ class Pool_layer(nn.Module):
             sel = next(_pool_feed)
             assert sel.numel() == pool_num and sel.dtype == torch.int32
         else:
-            sample_idx = torch.randperm(vertice_num)[:pool_num]
-            sel = sample_idx.to(device=vertices.device, dtype=torch.int32)
+            with pc_sample.draw_scope(None, vertices.device) as device_draws:
+                if device_draws is not None:                 # FLAGS.step_draws = 'device': keyed rows, drawn on the device
+                    sel = device_draws.pool_rows(vertice_num, self.pooling_rate)
+                else:
+                    sel = torch.randperm(vertice_num)[:pool_num].to(device=vertices.device, dtype=torch.int32)
         # only the kept rows are pooled (the reference pools all N rows, then selects)
         if feature_map.dtype == torch.float32 and feature_map.shape[2] >= 12 and not vertices.requires_grad:
             feature_map_pool, vertices_pool = ops.pool_layer(feature_map, vertices, neighbor_index, sel, self.neighbor_num)

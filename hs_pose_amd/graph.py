@@ -16,13 +16,19 @@ in the same order and on the same generator as the reference, and is uploaded in
 kernels read.  Under the 'fps' pool sampler (config.FLAGS.pool_sampler / gcn3d.Pool_layer(sampler=...), as it stands when the
 object is built) the kept rows are picked INSIDE the captured graph from the clouds in the static input buffers: no draw, no
 upload and no index buffers, a replay begins with no host work at all.
+
+Under device draws (``config.FLAGS.step_draws = 'device'`` or ``draws=`` on ``GraphedTrainStep`` / ``GraphedInference``, resolved
+when the object is built) the 'random' rows -- and the training step's augmentation draws -- are keyed draws made INSIDE the
+captured body (include/hsp.h: "keyed draws of a step"): the body begins with ``hsp_pool_rows_draw`` into the static index
+buffers, nothing is drawn or uploaded before a replay, and the owner's one action per replay is ``sampler.advance()``.
+``GraphedStep`` and ``GraphedNetwork`` keep the host draws.
 """
 import contextlib
 import os
 
 import torch
 
-from . import augment, gcn3d, ops, staging
+from . import augment, gcn3d, ops, pc_sample, staging
 from .config import FLAGS
 
 # Other threads of the process (RCCL's watchdog polling events, the autograd engine's workers) may call into HIP while
@@ -81,6 +87,33 @@ def upload_pool_indices(bufs, n_points):
         return
     for buf, idx in zip(bufs, draws):
         staging.upload(lambda pinned, idx=idx: pinned.copy_(idx), buf.shape, torch.int32, buf.device, out=buf)
+
+
+def draw_pool_rows(scope, bufs, n_points):
+    """device draws: the head of a captured body -- both Pool_layers' rows drawn under the scope's key straight into the static
+    index buffers (``alloc_pool_indices``) the body's ``pool_feed`` hands to the layers.  Nothing under host draws (``scope`` is
+    None) or the 'fps' sampler (``bufs`` is None)."""
+    if scope is not None and bufs is not None:
+        ops.pool_rows_draw(scope.key, n_points, 4, 2, out=bufs[0]._hsp_flat)
+
+
+class _keep_sampler_state:
+    """building a captured object runs its body eagerly (the warm-up), and an eager body advances the sampler of its device
+    draws: state and device key are put back on exit, so the first replay draws what it would have drawn had nothing been built"""
+
+    def __init__(self, sampler):
+        self.sampler = sampler
+
+    def __enter__(self):
+        if self.sampler is not None:
+            self.state, self.key = self.sampler.get_state(), self.sampler.key.clone()
+        return self
+
+    def __exit__(self, *exc):
+        if self.sampler is not None:
+            self.sampler.set_state(self.state)
+            self.sampler.key.copy_(self.key)                 # (the key on the device too: what the last advance() uploaded)
+        return False
 
 
 class _preserve_bn_stats:
@@ -283,9 +316,15 @@ class GraphedTrainStep:
     replace the same-named entries of ``batch`` for that body -- the step in front of the network captured with it
     (train.FrameTrainStep: the training loader's front end and the choice of the kept items).  It reads static buffers of its
     owner's and must be issuable both eagerly (the warm-up) and under capture; ``batch`` then gives the shapes and the static
-    buffers of the other keys only, and ``load_batch`` has no effect on the replaced ones.  None: the body is the batch's."""
+    buffers of the other keys only, and ``load_batch`` has no effect on the replaced ones.  None: the body is the batch's.
 
-    def __init__(self, network, optimizer, batch, scheduler=None, max_norm=5, warmup=3, prologue=None):
+    ``draws``: who makes the step's draws, resolved when the object is built (``pc_sample.resolve_draws``: None follows
+    ``FLAGS.step_draws``).  Under a device sampler the captured body begins with the keyed draw of both Pool_layers' rows into the
+    static index buffers and its augmentation is ``hsp_pose_augment_keyed``; there is no host work before a replay and no
+    generator is touched: THE OWNER CALLS ``draws.advance()`` BEFORE EACH ``replay()`` / ``run()`` (the 16-byte key upload), and
+    equal sampler states replay equal steps.  Building the object leaves the sampler's state as it found it."""
+
+    def __init__(self, network, optimizer, batch, scheduler=None, max_norm=5, warmup=3, prologue=None, draws=None):
         self.net, self.opt, self.sched, self.max_norm = network, optimizer, scheduler, max_norm
         self.batch = batch
         self._prologue = prologue
@@ -293,12 +332,14 @@ class GraphedTrainStep:
         B, N, _ = PC.shape
         self.n_points = N
         dev = PC.device
-        self.noise = torch.zeros_like(PC)
+        self.draws = pc_sample.resolve_draws(draws, dev)
+        self.noise = torch.zeros_like(PC) if self.draws is None else None
         self.pool_idx = pool_index_buffers(network, N, dev)
         self.loss_dict, self.total = None, None
         self._host_draws()
         prev_timer = ops.set_timer(None)
         keep = _preserve_bn_stats(network).__enter__()
+        keep_state = _keep_sampler_state(self.draws).__enter__()
         try:
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
@@ -312,10 +353,13 @@ class GraphedTrainStep:
             with torch.cuda.graph(self.graph, stream=side, **_CAPTURE):
                 self._body()
         finally:
+            keep_state.__exit__()
             keep.__exit__()
             ops.set_timer(prev_timer)
 
     def _host_draws(self):
+        if self.draws is not None:                           # device draws: everything is drawn inside the replay
+            return
         if FLAGS.train:
             # (through the pinned ring, like the pool indices: a copy from pageable memory waits for the previous replay, and the
             # host then cannot queue step i + 1 under step i -- 8 ms of replay + the graph launch's own host time per step, measured
@@ -336,12 +380,16 @@ class GraphedTrainStep:
         # Gradients are created INSIDE the capture (grad = None first) and then moved into the optimizer's flat buffer
         # with one multi-tensor copy: accumulating straight into the pre-existing flat views makes autograd synchronise
         # the capture stream with the stream those views were made on, and the replayed graph then waits forever.
-        batch = self.batch if self._prologue is None else {**self.batch, **self._prologue()}
-        params, views = self._params_and_views()
-        for p in params:
-            p.grad = None
-        with pool_feed(self.pool_idx), augment.jitter_noise_feed(self.noise):
-            _, ld = self.net(do_loss=True, **batch)
+        with pc_sample.draw_scope(self.draws or "host", self.batch["PC"].device) as scope:
+            draw_pool_rows(scope, self.pool_idx, self.n_points)
+            batch = self.batch if self._prologue is None else {**self.batch, **self._prologue()}
+            params, views = self._params_and_views()
+            for p in params:
+                p.grad = None
+            noise = augment.jitter_noise_feed(self.noise) if scope is None else contextlib.nullcontext()
+            with pool_feed(self.pool_idx), noise:
+                od, ld = self.net(do_loss=True, **batch)
+        self.output_dict = {k: v.detach() for k, v in od.items() if isinstance(v, torch.Tensor)}    # static: every replay rewrites them
         total = self.net.total_loss(ld)                     # (the sum over the four sub-dictionaries, engine/train.py:84-90)
         with ops.StepFolds():
             total.backward()
@@ -365,7 +413,8 @@ class GraphedTrainStep:
             self.batch[k].copy_(v, non_blocking=True)
 
     def replay(self):
-        """the host draws and the replay: losses and gradients of one step, nothing applied yet"""
+        """the host draws and the replay: losses and gradients of one step, nothing applied yet (device draws: the replay
+        alone, under the key of the owner's last ``draws.advance()``)"""
         self._host_draws()
         self.graph.replay()
 
@@ -401,9 +450,12 @@ class GraphedInference:
     ``prologue``: a callable issued at the head of the captured body, on the capture stream, whose result (n,N,3) IS the
     cloud the network reads -- the step in front of the network captured with it (frame.FramePipeline(one_graph=True): the
     frame front end).  It reads static buffers of its owner's; ``PC`` then only gives the shape and ``load(PC=...)`` has no
-    effect."""
+    effect.
 
-    def __init__(self, network, PC, obj_id, mean_shape, sym, warmup=2, prologue=None):
+    ``draws``: as ``GraphedTrainStep``'s -- under a device sampler the body begins with the keyed draw of the Pool_layers' rows,
+    ``run()`` is the replay alone, and the owner calls ``draws.advance()`` before it."""
+
+    def __init__(self, network, PC, obj_id, mean_shape, sym, warmup=2, prologue=None, draws=None):
         from .geom_utils import generate_RT
         self.net, self._generate_RT = network, generate_RT
         self.PC, self.obj_id, self.mean_shape, self.sym = PC, obj_id, mean_shape, sym
@@ -414,8 +466,10 @@ class GraphedInference:
         self.pool_idx = pool_index_buffers(network, N, dev)
         if network.training:
             raise RuntimeError("GraphedInference: put the network in eval() mode first")
+        self.draws = pc_sample.resolve_draws(draws, dev)
         self._draw()
         prev_timer = ops.set_timer(None)
+        keep_state = _keep_sampler_state(self.draws).__enter__()
         try:
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
@@ -428,17 +482,21 @@ class GraphedInference:
             with torch.cuda.graph(self.graph, **_CAPTURE):
                 self._body()
         finally:
+            keep_state.__exit__()
             ops.set_timer(prev_timer)
 
     def _draw(self):
-        upload_pool_indices(self.pool_idx, self.n_points)
+        if self.draws is None:                               # (device draws: the rows are drawn inside the replay)
+            upload_pool_indices(self.pool_idx, self.n_points)
 
     @torch.no_grad()
     def _body(self):
-        if self._prologue is not None:
-            self.PC = self._prologue()
-        with pool_feed(self.pool_idx):
-            out = self.net(PC=self.PC, obj_id=self.obj_id, mean_shape=self.mean_shape, sym=self.sym)
+        with pc_sample.draw_scope(self.draws or "host", self.obj_id.device) as scope:
+            draw_pool_rows(scope, self.pool_idx, self.n_points)
+            if self._prologue is not None:
+                self.PC = self._prologue()
+            with pool_feed(self.pool_idx):
+                out = self.net(PC=self.PC, obj_id=self.obj_id, mean_shape=self.mean_shape, sym=self.sym)
         self.pred_RT = self._generate_RT([out['p_green_R'], out['p_red_R']], [out['f_green_R'], out['f_red_R']],
                                          out['Pred_T'], mode='vec', sym=self.sym)
         self.pred_s = out['Pred_s'] + self.mean_shape

@@ -2651,6 +2651,75 @@ def sample_ids(count, S, key, min_pts, min_depth_pts=0, short_mode=0):
     return choose, status
 
 
+def _req_key(key, name):
+    key = _req(key, torch.int64, f"{name}.key")
+    if key.numel() != 2:
+        raise HspError(f"{name}: expects key (2,) int64 holding the uint64 pair (seed, call), got {tuple(key.shape)}")
+    return key
+
+
+def pool_rows_draw(key, n0, rate=4, levels=2, out=None):
+    """the rows ``levels`` (1 or 2) consecutive Pool_layers keep, drawn on the device under ``key`` (include/hsp.h:
+    hsp_pool_rows_draw): level l keeps m_l = int(n_l / rate) of n_l rows, n_1 = m_0 -> a list of ``levels`` int32 views of ONE
+    buffer (``out``: a flat int32 device buffer of m_0 [+ m_1] entries, the ``_hsp_flat`` of ``graph.alloc_pool_indices``)."""
+    key = _req_key(key, "pool_rows_draw")
+    n0, rate, levels = int(n0), int(rate), int(levels)
+    if n0 < 1 or rate < 1 or levels not in (1, 2):
+        raise HspError(f"pool_rows_draw: n0 {n0} / rate {rate} / levels {levels} out of range (n0, rate >= 1, levels 1 or 2)")
+    ms = [n0 // rate]
+    if levels == 2:
+        ms.append(ms[0] // rate)
+    if min(ms) < 1:
+        raise HspError(f"pool_rows_draw: a level of n0 {n0} at rate {rate} keeps no row")
+    if out is None:
+        out = torch.empty(sum(ms), dtype=torch.int32, device=key.device)
+    else:
+        out = _req(out, torch.int32, "pool_rows_draw.out")
+        if out.dim() != 1 or out.numel() != sum(ms):
+            raise HspError(f"pool_rows_draw: out expects ({sum(ms)},) int32, got {tuple(out.shape)}")
+    _run("hsp_pool_rows_draw", (_p(key), n0, rate, levels, _p(out), _stream()), key=f"n{n0}r{rate}l{levels}",
+         abytes=4 * sum(ms) + 16)
+    return list(out.split(ms))
+
+
+def pose_augment_keyed(key, PC, gt_R, gt_t, gt_s, mean_shape, sym, aug_bb, aug_rt_t, aug_rt_r, model_point, nocs_scale, obj_ids,
+                       aug_pc_r, p_bb, p_rt, p_bc, p_pc):
+    """``hsp_pose_augment`` with the six per-item uniforms and the jitter factors drawn in the kernel under ``key``
+    (include/hsp.h: hsp_pose_augment_keyed) -> (PC (B,N,3), gt_R (B,3,3), gt_t (B,3), gt_s (B,3)) fp32."""
+    key = _req_key(key, "pose_augment_keyed")
+    bs, N, _ = PC.shape
+    M = model_point.shape[1]
+    f = lambda t, shape: _req(t.detach().float().reshape(shape), torch.float32, "pose_augment_keyed")
+    args = [f(PC, (bs, N, 3)), f(gt_R, (bs, 3, 3)), f(gt_t, (bs, 3)), f(gt_s, (bs, 3)), f(mean_shape, (bs, 3)), f(sym, (bs, 4)),
+            f(aug_bb, (bs, 3)), f(aug_rt_t, (bs, 3)), f(aug_rt_r, (bs, 3, 3)), f(model_point, (bs, M, 3)), f(nocs_scale, (bs,)),
+            f(obj_ids, (bs,))]
+    dev = args[0].device
+    outs = [torch.empty(shape, dtype=torch.float32, device=dev) for shape in ((bs, N, 3), (bs, 3, 3), (bs, 3), (bs, 3))]
+    _run("hsp_pose_augment_keyed", [_p(a) for a in args] + [_p(key), float(aug_pc_r), bs, N, M, float(p_bb), float(p_rt),
+                                                            float(p_bc), float(p_pc)] + [_p(o) for o in outs] + [_stream()],
+         key=f"B{bs}N{N}", abytes=bs * N * 24)
+    return tuple(outs)
+
+
+def dzi_windows_device(bboxes, key, H, W, out_size, pad_scale, scale_ratio, shift_ratio, out=None):
+    """the DZI crop windows of a training batch as transform rows, drawn on the device under ``key`` (include/hsp.h:
+    hsp_dzi_windows): bboxes (M,4) int32 = (x1, y1, x2, y2) on the device -> xf (M,3) float64 (``out`` when given)."""
+    key = _req_key(key, "dzi_windows_device")
+    bboxes = _req(bboxes, torch.int32, "dzi_windows_device.bboxes")
+    if bboxes.dim() != 2 or bboxes.shape[1] != 4 or not 1 <= bboxes.shape[0] <= 65535:
+        raise HspError(f"dzi_windows_device: expects bboxes (M,4) int32 with 1 <= M <= 65535, got {tuple(bboxes.shape)}")
+    M = bboxes.shape[0]
+    if out is None:
+        out = torch.empty(M, 3, dtype=torch.float64, device=bboxes.device)
+    else:
+        out = _req(out, torch.float64, "dzi_windows_device.out")
+        if out.shape != (M, 3):
+            raise HspError(f"dzi_windows_device: out expects ({M},3) float64, got {tuple(out.shape)}")
+    _run("hsp_dzi_windows", (_p(bboxes), _p(key), M, int(H), int(W), int(out_size), float(pad_scale), float(scale_ratio),
+                             float(shift_ratio), _p(out), _stream()), key=f"M{M}", abytes=M * 40 + 16)
+    return out
+
+
 _FRAME_DEPTH = {torch.float32: "_f32", torch.uint16: "_u16"}
 
 

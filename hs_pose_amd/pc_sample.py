@@ -27,7 +27,14 @@ the cropped mask, the three rejection tests, the cloud and its rows on the devic
 ``hsp_sample_ids`` / ``hsp_frames_to_pcl``), under a device sampler only.  ``train_batch_select`` is the loader's answer to a
 rejected item behind it -- move on to the next index (:254-278) -- for a batch that arrives with spares: the first ``keep`` good
 items and every per-item tensor of theirs in one launch (``hsp_batch_select``), nothing read back.
+
+``resolve_draws`` / ``draw_scope`` are the switch for the OTHER draws of a forward or a replay -- the Pool_layers' kept rows, the
+augmentation's uniforms and jitter, the DZI windows: ``FLAGS.step_draws`` 'host' (default: torch's and numpy's generators, as
+the reference) or 'device' (keyed by a ``DeviceSampler``, drawn inside the forward or the captured body; include/hsp.h: "keyed
+draws of a step").  One ``advance()`` keys everything one forward or replay draws.
 """
+import contextlib
+
 import numpy as np
 import torch
 
@@ -100,6 +107,81 @@ def resolve_sampler(sampler, device):
     if sampler == "device":
         return default_sampler(device)
     raise ValueError(f"pc sampler: expects 'host', 'device' or a DeviceSampler, got {sampler!r}")
+
+
+def resolve_draws(draws, device):
+    """``draws=`` of the forwards and captured steps -> None (the host draws: torch's and numpy's generators, as the reference)
+    or the DeviceSampler that keys every draw of a forward or a replay on the device: None follows ``FLAGS.step_draws``, 'host',
+    'device' (the module's default sampler), or a DeviceSampler"""
+    if draws is None:
+        draws = getattr(FLAGS, "step_draws", "host")
+    if isinstance(draws, DeviceSampler):
+        return draws
+    if draws == "host":
+        return None
+    if draws == "device":
+        return default_sampler(device)
+    raise ValueError(f"step draws: expects 'host', 'device' or a DeviceSampler, got {draws!r}")
+
+
+class _DrawScope:
+    """the device draws of ONE forward: the sampler whose key they read, and the Pool_layers' rows (drawn for both levels by
+    the first layer that asks, handed to the second)"""
+
+    def __init__(self, sampler):
+        self.sampler, self.key = sampler, sampler.key
+        self._rows, self._asked = [], False
+
+    def pool_rows(self, n, rate, levels=None):
+        """the rows a Pool_layer keeps of ``n`` at ``rate``: level 0 for the first layer of the forward, level 1 for a second
+        one that pools what the first kept.  ``levels`` = 2: both at once -> [rows0, rows1]"""
+        if levels == 2:
+            self._asked = True
+            return ops.pool_rows_draw(self.key, n, rate, 2)
+        if self._rows and self._rows[0][0] == (n, rate):
+            return self._rows.pop(0)[1]
+        if self._asked:
+            raise ValueError("device draws: the Pool_layers of one forward are two at most, the second pooling the rows the "
+                             "first kept at the same rate (include/hsp.h: hsp_pool_rows_draw)")
+        self._asked = True
+        m = n // rate
+        if m // rate >= 1:
+            rows0, rows1 = ops.pool_rows_draw(self.key, n, rate, 2)
+            self._rows.append(((m, rate), rows1))
+            return rows0
+        return ops.pool_rows_draw(self.key, n, rate, 1)[0]
+
+
+_draw_scope = None
+
+
+@contextlib.contextmanager
+def draw_scope(draws, device):
+    """The scope of one forward's draws.  Under device draws (``resolve_draws``) it yields the ``_DrawScope`` every draw of the
+    forward is keyed by and ``active_draws()`` returns it inside; under host draws it yields None.  The outermost scope of an
+    eager forward advances the sampler once; a scope opened during a graph capture never does (the owner of the captured body
+    advances before each replay); a scope inside a scope is the outer one."""
+    global _draw_scope
+    if _draw_scope is not None:
+        yield _draw_scope[0]
+        return
+    device = torch.device(device)
+    sampler = resolve_draws(draws, device) if device.type == "cuda" else None
+    scope = None
+    if sampler is not None:
+        if not torch.cuda.is_current_stream_capturing():
+            sampler.advance()
+        scope = _DrawScope(sampler)
+    _draw_scope = (scope,)
+    try:
+        yield scope
+    finally:
+        _draw_scope = None
+
+
+def active_draws():
+    """the open scope's _DrawScope, or None: no scope is open or the host draws"""
+    return _draw_scope[0] if _draw_scope is not None else None
 
 
 def _gather_safe(choose, pix, HW):
@@ -381,7 +463,8 @@ def train_batch_to_pcl(depth, labels, inst_ids, centers, scales, K, n_pts=None, 
     if labels.dtype == torch.bool:
         labels = labels.view(torch.uint8)
     gate = mask_gate(FLAGS.roi_mask_pro if mask_pro is None else mask_pro)
-    key = sampler.key if capturing else sampler.advance()
+    scope = active_draws()                                      # (a forward's draw scope of this sampler has advanced it already)
+    key = sampler.key if capturing or (scope is not None and scope.sampler is sampler) else sampler.advance()
     crop_mask, _ = ops.roi_defor(labels, xf, O, key, ids_d, mask_iters, gate)
     src, count, pre = ops.crop_compact(depth, crop_mask, xf, O)
     choose, status = ops.sample_ids(count, n_pts, key, min_pts, 2, 0)

@@ -20,7 +20,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from . import pc_sample
+from . import ops, pc_sample
 from .config import FLAGS
 from .graph import GraphedTrainStep
 from .parallel import mean_flat_gradients
@@ -29,8 +29,11 @@ from .solver import build_lr_rate, build_optimizer
 
 class TrainDriver:
     def __init__(self, network, optimizer=None, scheduler=None, total_iters=None, accumulate=None, max_norm=5,
-                 check_nan=True, global_step=0, data_parallel=None):
-        """data_parallel (default: whenever torch.distributed is initialised with more than one rank): after every
+                 check_nan=True, global_step=0, data_parallel=None, draws=None):
+        """draws: the ``pc_sample.DeviceSampler`` that keys the run's device draws (``FLAGS.step_draws = 'device'``), if any: its
+        state then travels in the checkpoint, so a resumed run draws what the uninterrupted one would have drawn.
+
+        data_parallel (default: whenever torch.distributed is initialised with more than one rank): after every
         backward the gradients -- already in the optimizer's flat buffers -- are averaged over the ranks with one RCCL
         all-reduce per parameter group, before clipping (the reference trains on a single device, train.py:23)."""
         self.network = network
@@ -52,6 +55,9 @@ class TrainDriver:
         self.check_nan = check_nan
         self.global_step = int(global_step)
         self.skipped = 0
+        if draws is not None and not isinstance(draws, pc_sample.DeviceSampler):
+            raise ValueError(f"TrainDriver: draws expects a pc_sample.DeviceSampler or None, got {draws!r}")
+        self.draws = draws
 
     def step(self, total_loss):
         """one batch of engine/train.py's loop; returns False when the batch was skipped for a NaN loss."""
@@ -75,14 +81,18 @@ class TrainDriver:
         return True
 
     def checkpoint(self, seed, epoch):
-        """the dict engine/train.py:115-123 passes to torch.save (same keys, same sub-layouts)."""
-        return {
+        """the dict engine/train.py:115-123 passes to torch.save (same keys, same sub-layouts); with a device sampler also
+        'draws': its (seed, call) state."""
+        ckpt = {
             'seed': seed,
             'epoch': epoch,
             'posenet_state_dict': self.network.state_dict(),
             'scheduler': self.scheduler.state_dict(),
             'optimizer': self.optimizer.state_dict(),
         }
+        if self.draws is not None:
+            ckpt['draws'] = tuple(self.draws.get_state())
+        return ckpt
 
     def load_checkpoint(self, ckpt):
         """resume (engine/train.py:53-59: model weights, optimizer and scheduler state when present); returns the epoch
@@ -92,6 +102,8 @@ class TrainDriver:
             self.optimizer.load_state_dict(ckpt['optimizer'])
         if 'scheduler' in ckpt:
             self.scheduler.load_state_dict(ckpt['scheduler'])
+        if self.draws is not None and 'draws' in ckpt:
+            self.draws.set_state(ckpt['draws'])
         return ckpt.get('epoch', -1) + 1
 
 
@@ -125,10 +137,17 @@ class FrameTrainStep:
     more spares.
 
     Build it before the network's first eager backward (see ``GraphedTrainStep``).  Building draws like one ``run()`` does on
-    numpy's and torch's generators (the warm-up needs windows and noise) and leaves the sampler's state as it found it."""
+    numpy's and torch's generators (the warm-up needs windows and noise) and leaves the sampler's state as it found it.
+
+    ``draws``: None (follow ``FLAGS.step_draws`` as it stands when the object is built), 'host' -- all of the above -- or
+    'device' / a DeviceSampler: the object's sampler then keys EVERY draw of the step.  ``bboxes_xyxy`` goes to a static int32
+    device buffer (data, not a draw), the captured prologue begins with ``hsp_dzi_windows`` ('uniform' DZI only), the body with
+    the Pool_layers' keyed rows, the augmentation is ``hsp_pose_augment_keyed``, and ``run()`` is ``sampler.advance()``, the
+    replay, the check and the optimizer launch: no generator of the host's is touched, when the object is built or later, and
+    equal sampler states give equal steps."""
 
     def __init__(self, network, optimizer, frames, items, keep, scheduler=None, sampler=None, n_pts=None, out_size=None,
-                 min_pts=50, mask_pro=None, max_norm=5, warmup=3):
+                 min_pts=50, mask_pro=None, max_norm=5, warmup=3, draws=None):
         depth = frames["depth"]
         dev = depth.device
         if depth.dim() != 3 or not 1 <= int(keep) <= depth.shape[0]:
@@ -140,6 +159,10 @@ class FrameTrainStep:
         self.sampler = pc_sample.resolve_sampler("device" if sampler is None else sampler, dev)
         if self.sampler is None:
             raise ValueError("FrameTrainStep: expects a device sampler; there is no host-draw form of the training front end")
+        self.draws = self.sampler if pc_sample.resolve_draws(draws, dev) is not None else None
+        if self.draws is not None and str(FLAGS.DZI_TYPE).lower() != "uniform":
+            raise NotImplementedError(f"FrameTrainStep: the device draws build DZI_TYPE 'uniform' only, got {FLAGS.DZI_TYPE!r}")
+        self.bboxes_d = torch.zeros(self.M, 4, dtype=torch.int32, device=dev)
         self.depth = depth.detach().clone()
         self.labels = frames["labels"].detach().clone()
         self.inst_ids = torch.empty(self.M, dtype=torch.int32, device=dev)
@@ -155,7 +178,11 @@ class FrameTrainStep:
         self._load_small(frames)
         pc_sample.stand_in_cloud(self.n_pts, dev)               # (made here: an upload cannot happen inside the capture)
 
+        dzi = (float(FLAGS.DZI_PAD_SCALE), float(FLAGS.DZI_SCALE_RATIO), float(FLAGS.DZI_SHIFT_RATIO))
+
         def front_end():
+            if self.draws is not None:                          # the windows of this replay, drawn under its key
+                ops.dzi_windows_device(self.bboxes_d, self.sampler.key, self.H, self.W, self.out_size, *dzi, out=self.xf)
             PC, self.status = pc_sample.train_batch_to_pcl(self.depth, self.labels, self.inst_ids, self.xf, None, self.K,
                                                            n_pts=self.n_pts, out_size=self.out_size, min_pts=min_pts,
                                                            mask_pro=mask_pro, sampler=self.sampler)
@@ -164,10 +191,11 @@ class FrameTrainStep:
 
         shapes = {"PC": torch.empty(self.keep, self.n_pts, 3, device=dev)}
         shapes.update({k: torch.empty((self.keep,) + tuple(v.shape[1:]), dtype=v.dtype, device=dev) for k, v in self.items.items()})
-        self._windows()
+        if self.draws is None:
+            self._windows()
         state = self.sampler.get_state()                        # (the eager warm-up calls advance; the captured call does not)
         self.graphed = GraphedTrainStep(network, optimizer, shapes, scheduler=scheduler, max_norm=max_norm, warmup=warmup,
-                                        prologue=front_end)
+                                        prologue=front_end, draws=self.draws or "host")
         self.sampler.set_state(state)
 
     @staticmethod
@@ -188,6 +216,12 @@ class FrameTrainStep:
             if boxes.shape != (self.M, 4):
                 raise ValueError(f"FrameTrainStep: expects bboxes_xyxy ({self.M},4) on the host, got {boxes.shape}")
             self.bboxes = boxes
+            if self.draws is not None:
+                if not np.issubdtype(boxes.dtype, np.integer):
+                    raise ValueError(f"FrameTrainStep: under device draws bboxes_xyxy expects integers, got {boxes.dtype}")
+                if not (np.maximum(boxes[:, 2] - boxes[:, 0], boxes[:, 3] - boxes[:, 1]) > 0).all():
+                    raise ValueError("FrameTrainStep: every box of bboxes_xyxy needs a positive side (the crop scale)")
+                pc_sample._upload(boxes, np.int32, dev, out=self.bboxes_d)
 
     def _windows(self):
         centers, scales = pc_sample.dzi_windows(self.bboxes, self.H, self.W)
@@ -215,7 +249,8 @@ class FrameTrainStep:
 
     def run(self, check=True):
         """one training step from the frames in the static buffers; see the class text for ``check``"""
-        self._windows()
+        if self.draws is None:
+            self._windows()
         self.sampler.advance()
         self.graphed.replay()
         if check and bool((self.info[0] == 0) | torch.isnan(self.graphed.total).any()):

@@ -1056,6 +1056,62 @@ int hsp_pose_augment(const float *PC, const float *gt_R, const float *gt_t, cons
                      const float *noise, int B, int N, int M, float p_bb, float p_rt, float p_bc, float p_pc, float *PC_out,
                      float *R_out, float *t_out, float *s_out, hspStream_t stream);
 
+/* ---- keyed draws of a step: every random choice of a forward or a replay, made on the device ----------------------------
+ * The opt-in counterpart (config.FLAGS.step_draws = 'device') of what the host draws before a forward or a replay: the rows the
+ * two Pool_layers keep (torch.randperm on the CPU generator, gcn3d.py:243), the augmentation's six per-item uniforms and its
+ * jitter factors (torch.rand), the training loader's DZI windows (numpy's generator).  The same DISTRIBUTIONS from the keyed
+ * generator of the hsp_sample_ids section, not the same draws.  Plain C++, vector stores, integer arithmetic for the draws, no
+ * atomics, no workspace.  key: the DEVICE pointer to two uint64 {seed, call} that hsp_sample_ids reads, so a captured launch
+ * sees each replay's values; one {seed, call} pair keys every draw of one forward or replay.
+ *
+ * fmix32, absorb, the instance key kj of an index j and the cycle-walked Feistel permutation P of [0, c) under a key are those
+ * of the hsp_sample_ids section, unchanged.  Each purpose has instance indices j >= 2^31 of its own, so no stream coincides with
+ * a row draw (there j < 65536) or with another purpose:
+ *   Pool rows of level l (0 or 1):     j = 0x80000000 | l
+ *   augmentation of cloud b:           j = 0x81000000 | b        (b < 2^24)
+ *   DZI window of item i:              j = 0x82000000 | i        (i < 65535)
+ * A stream of words under kj and a tag T is  word(i) = absorb(absorb(kj, T), i), i = 0, 1, ... (uint32).
+ * A word w becomes an fp32 uniform as  float(w >> 8) * 2^-24  and a float64 uniform as  double(w) * 2^-32: both conversions are
+ * exact and give values in [0, 1).
+ *
+ * hsp_pool_rows_draw: the kept rows of `levels` (1 or 2) consecutive Pool_layers of pooling rate `rate`, ONE launch.  n_0 = n0,
+ * level l keeps m_l = n_l / rate rows (integer division: the reference's int(n / rate)) of n_l, and n_1 = m_0.  With
+ * kl = the instance key of j = 0x80000000 | l and P_l = P over [0, n_l) under kl (round keys absorb(kl, r), c = n_l):
+ *   rows[off_l + s] = P_l(s),  s = 0 .. m_l - 1,   off_0 = 0, off_1 = m_0
+ * -- the first m_l values of a permutation: an ordered subset drawn uniformly, shared by the batch like the reference's single
+ * randperm.  rows (m_0 [+ m_1]) int32, back to back.  n0 <= 0, rate <= 0, levels outside {1, 2} or an m_l of 0: HSP_ERR_BAD_ARG. */
+int hsp_pool_rows_draw(const unsigned long long *key, int n0, int rate, int levels, int32_t *rows, hspStream_t stream);
+
+/* hsp_pose_augment with its draws made in the kernel (the same kernel body): `draws` and `noise` give way to key and aug_pc_r.
+ * For cloud b, kb = the instance key of j = 0x81000000 | b and word(i) = absorb(absorb(kb, 0xfffffffc), i):
+ *   draws[q, b]     = the fp32 uniform of word(q), q = 0 .. 5        (u_bb, u_rt, u_bc, ey_up, ey_down, u_pc in this order)
+ *   noise[b, n, i]  = the fp32 uniform of word(6 + 3 n + i), times aug_pc_r in fp32 (one rounding, as the host's rand * r)
+ * and everything else is hsp_pose_augment's, operation for operation: given these draws and this noise hsp_pose_augment returns
+ * the same bits.  B <= 2^24, N <= 2^29; beyond, a NULL pointer or a size <= 0: HSP_ERR_BAD_ARG. */
+int hsp_pose_augment_keyed(const float *PC, const float *gt_R, const float *gt_t, const float *gt_s, const float *mean_shape,
+                           const float *sym, const float *aug_bb, const float *aug_rt_t, const float *aug_rt_r,
+                           const float *model_point, const float *nocs_scale, const float *obj_id,
+                           const unsigned long long *key, float aug_pc_r, int B, int N, int M, float p_bb, float p_rt,
+                           float p_bc, float p_pc, float *PC_out, float *R_out, float *t_out, float *s_out, hspStream_t stream);
+
+/* replaces aug_bbox_DZI with DZI_TYPE 'uniform' (tools/dataset_utils.py:24-61) and the crop transform behind it for the M items
+ * of a training batch: bboxes (M,4) int32 = (x1, y1, x2, y2) on the device -> xf (M,3) DOUBLE = (m0, b1, b2), the rows
+ * hsp_roi_compact / hsp_roi_defor / hsp_crop_compact read.  For item i, ki = the instance key of j = 0x82000000 | i,
+ * word(q) = absorb(absorb(ki, 0xfffffffb), q), and u0, u1, u2 = the float64 uniforms of word(0), word(1), word(2) (the
+ * reference's random_sample(), then random_sample(2)).  All in float64, every operation rounded once (nothing contracted into a
+ * fused multiply-add), in this order; integers convert exactly:
+ *   cx = 0.5 * (x1 + x2),  cy = 0.5 * (y1 + y2),  bw = x2 - x1,  bh = y2 - y1
+ *   sr = 1 + scale_ratio * (2 * u0 - 1),   sx = shift_ratio * (2 * u1 - 1),   sy = shift_ratio * (2 * u2 - 1)
+ *   cx' = cx + bw * sx,   cy' = cy + bh * sy
+ *   scale = min((max(bh, bw) * sr) * pad_scale, max(H, W))
+ *   O = out_size;  a = O / scale;  tx = O / 2 - a * cx';  ty = O / 2 - a * cy';  D = 1 / (a * a);  m0 = a * D
+ *   xf[i] = (m0, (-m0) * tx, (-m0) * ty)
+ * A box with max(bh, bw) <= 0 gives a row that is not finite (the host form refuses it); the caller keeps such boxes out.
+ * 'roi10d' / 'truncnorm' are not built.  M outside 1..65535, H, W <= 0, out_size outside 1..46340, pad_scale <= 0, scale_ratio
+ * outside [0, 1), shift_ratio < 0 or a value that is not finite: HSP_ERR_BAD_ARG. */
+int hsp_dzi_windows(const int32_t *bboxes, const unsigned long long *key, int M, int H, int W, int out_size, double pad_scale,
+                    double scale_ratio, double shift_ratio, double *xf, hspStream_t stream);
+
 /* the face head's output split (PoseNet9D.py:31-35) in one launch each way: face (R, 30) -> unit normals (R, 6, 3) =
  * face[:, :18] / its per-face 3-norm (no epsilon, as the reference), distances (R, 6) = face[:, 18:24], confidences (R, 6) =
  * sigmoid(face[:, 24:]); backward: g_face (R, 30) from the three incoming gradients (each may be NULL = zero). */
