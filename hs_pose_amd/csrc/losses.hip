@@ -11,6 +11,7 @@
 //              points pass (per cloud: loss sums, the sign sums that ARE the gradients w.r.t. the per-cloud inputs,
 //                           and the 6 x 9 weighted moment sums of the plane fits, in fp64)
 //              finish (per cloud: plane fits and the box terms; then the 19 sums over the batch, in index order)
+//                      -- the fits' normal equations, normals and centre distances stay in fp64 (struct Wide below)
 //   backward   per-cloud program again, in forward-mode automatic differentiation with ONE TANGENT DIRECTION PER LANE
 //              (68 inputs per cloud: 54 moment sums + the 14 pose numbers): every lane runs the same scalar program,
 //              lane l carries d/d(input l) -- the derivative of the whole small program falls out with no hand-derived
@@ -39,10 +40,14 @@ enum Prm { P_PR = 0 /* 9: frame of Prop_pm, [i][j] */, P_NM = 9 /* 3: mirror-pla
 __device__ __constant__ int kFacePerm[6] = {1, 0, 2, 3, 5, 4};
 
 // ---- scalar type of the per-cloud program: float, or value + one tangent ---------------------------------------------
+// The tangent is carried in fp64: the 54 moment directions of a cloud are recombined per point by points pass 2, where they
+// cancel to a fraction of their size wherever a plane fit is ill-conditioned -- independent fp32 roundings of the 54 lanes
+// would be amplified by that cancellation, errors of the (shared) fp32 values are not.
 struct Dual {
-    float v, d;
+    float v;
+    double d;
 };
-__device__ __forceinline__ Dual mk(float v, float d = 0.f) { return Dual{v, d}; }
+__device__ __forceinline__ Dual mk(float v, double d = 0.0) { return Dual{v, d}; }
 __device__ __forceinline__ Dual operator+(Dual a, Dual b) { return {a.v + b.v, a.d + b.d}; }
 __device__ __forceinline__ Dual operator-(Dual a, Dual b) { return {a.v - b.v, a.d - b.d}; }
 __device__ __forceinline__ Dual operator*(Dual a, Dual b) { return {a.v * b.v, a.d * b.v + a.v * b.d}; }
@@ -58,10 +63,50 @@ __device__ __forceinline__ Dual operator*(Dual a, float b) { return {a.v * b, a.
 __device__ __forceinline__ Dual operator*(float a, Dual b) { return {a * b.v, a * b.d}; }
 __device__ __forceinline__ Dual operator/(Dual a, float b) { return {a.v / b, a.d / b}; }
 
+// ---- scalar type of the plane fits' normal equations: double, or double value + one double tangent.  The 3x3 systems are
+// ill-conditioned where a face stands nearly parallel to the camera's z axis (its votes' x, y nearly on a line), and
+// solving by cofactors is not backward stable: in fp32 it lost ~1e-4 of the box terms and up to 1e-2 of their gradients,
+// 5-10 x what an fp32 LU loses (tests/test_gpu_loss_reference.py).  The moment sums are fp64 already; the solve stays in
+// fp64 and only its three results are narrowed.
+struct DualD {
+    double v, d;
+};
+__device__ __forceinline__ DualD operator+(DualD a, DualD b) { return {a.v + b.v, a.d + b.d}; }
+__device__ __forceinline__ DualD operator-(DualD a, DualD b) { return {a.v - b.v, a.d - b.d}; }
+__device__ __forceinline__ DualD operator*(DualD a, DualD b) { return {a.v * b.v, a.d * b.v + a.v * b.d}; }
+__device__ __forceinline__ DualD operator/(DualD a, DualD b) {
+    const double q = a.v / b.v;
+    return {q, (a.d - q * b.d) / b.v};
+}
+__device__ __forceinline__ DualD operator-(DualD a) { return {-a.v, -a.d}; }
+__device__ __forceinline__ DualD operator+(DualD a, double b) { return {a.v + b, a.d}; }
+__device__ __forceinline__ DualD operator*(DualD a, double b) { return {a.v * b, a.d * b}; }
+__device__ __forceinline__ double wval(double a) { return a; }
+__device__ __forceinline__ double wval(DualD a) { return a.v; }
+__device__ __forceinline__ double w_sqrt(double a) { return sqrt(a); }
+__device__ __forceinline__ DualD w_sqrt(DualD a) {
+    const double s = sqrt(a.v);
+    return {s, s > 0.0 ? a.d / (2.0 * s) : 0.0};
+}
+__device__ __forceinline__ double w_abs(double a) { return fabs(a); }
+__device__ __forceinline__ DualD w_abs(DualD a) { return {fabs(a.v), (a.v > 0.0 ? 1.0 : (a.v < 0.0 ? -1.0 : 0.0)) * a.d}; }
+template <class T> struct Wide {                 // T = float
+    using type = double;
+    static __device__ __forceinline__ double make(double v, bool) { return v; }
+    static __device__ __forceinline__ double widen(float x) { return x; }
+    static __device__ __forceinline__ float narrow(double x) { return (float)x; }
+};
+
+template <> struct Wide<Dual> {
+    using type = DualD;
+    static __device__ __forceinline__ DualD make(double v, bool seeded) { return {v, seeded ? 1.0 : 0.0}; }
+    static __device__ __forceinline__ DualD widen(Dual x) { return {(double)x.v, x.d}; }
+    static __device__ __forceinline__ Dual narrow(DualD x) { return {(float)x.v, x.d}; }
+};
 __device__ __forceinline__ float val(float a) { return a; }
 __device__ __forceinline__ float val(Dual a) { return a.v; }
-__device__ __forceinline__ float tan_of(float) { return 0.f; }
-__device__ __forceinline__ float tan_of(Dual a) { return a.d; }
+__device__ __forceinline__ double tan_of(float) { return 0.0; }
+__device__ __forceinline__ double tan_of(Dual a) { return a.d; }
 template <class T> __device__ __forceinline__ T lift(float v);
 template <> __device__ __forceinline__ float lift<float>(float v) { return v; }
 template <> __device__ __forceinline__ Dual lift<Dual>(float v) { return {v, 0.f}; }
@@ -344,7 +389,7 @@ __global__ __launch_bounds__(PTS_THREADS) void loss_points_kernel(
             const float err = sqrtf(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
             const float conf = expf(-303.5f * err * err);
             acc[R_RC + j] += fabsf(conf - ff);
-            const double w = ff, x = q.P[0] + fd * fn[0], y = q.P[1] + fd * fn[1], z = q.P[2] + fd * fn[2];
+            const double w = ff, x = q.P[0] + (double)fd * fn[0], y = q.P[1] + (double)fd * fn[1], z = q.P[2] + (double)fd * fn[2];
             double* m = macc + j * 9;
             m[0] += w * x * x; m[1] += w * x * y; m[2] += w * x;
             m[3] += w * y * y; m[4] += w * y; m[5] += w;
@@ -382,8 +427,8 @@ __global__ __launch_bounds__(PTS_THREADS) void loss_points_kernel(
 // tangents); their VALUES come from the point sums directly.
 template <class T>
 __device__ void cloud_program(const CloudGT& c, const HspLossCfg& cfg, int B, int N, float scale2 /* B / #kept or 1 */,
-                              const float* red, const T S[NMOM], const T g[3], const T r[3], T fg, T fr, const T Tp[3],
-                              const T sp[3], T term[NT], float* bad) {
+                              const float* red, const double* mom /* NMOM */, int mom_dir /* tangent direction, or -1 */,
+                              const T g[3], const T r[3], T fg, T fr, const T Tp[3], const T sp[3], T term[NT], float* bad) {
     const float fB = (float)B, fN = (float)N;
     const int sm = cfg.smooth_l1;
     for (int k = 0; k < NT; ++k) term[k] = lift<T>(0.f);
@@ -442,20 +487,20 @@ __device__ void cloud_program(const CloudGT& c, const HspLossCfg& cfg, int B, in
     if constexpr (sizeof(T) == sizeof(Dual)) {
         const float inv_bn = 1.f / (fB * fN);
         // geo: v = (P - T).g - canon  ->  dv = c.dg - g.dT
-        float d = 0.f;
+        double d = 0.0;
         for (int i = 0; i < 3; ++i) {
             d += red[R_SY + i] * tan_of(g[i]) - red[R_CY] * val(g[i]) * tan_of(Tp[i]);
             d += scale2 * (red[R_SX + i] * tan_of(r[i]) - red[R_CX] * val(r[i]) * tan_of(Tp[i]));
         }
         term[T_GEO].d = cfg.geo_p_w * inv_bn * d;
         // pm: v_j = sum_i c_i pR[i][j] - canon_j
-        d = 0.f;
+        d = 0.0;
         for (int i = 0; i < 3; ++i)
             for (int j = 0; j < 3; ++j)
                 d += red[R_GPM + 3 * i + j] * tan_of(pR[3 * i + j]) - red[R_CS + j] * val(pR[3 * i + j]) * tan_of(Tp[i]);
         term[T_PM].d = cfg.prop_pm_w * inv_bn / 3.f * d;
         // rt: through g (180 deg about y) or through the mirror normal, and T
-        d = 0.f;
+        d = 0.0;
         for (int i = 0; i < 3; ++i) {
             if (c.cls_y) d += red[R_GVEC + i] * tan_of(g[i]);
             if (c.cls_yx) d += red[R_GVEC + i] * tan_of(nm[i]);
@@ -465,33 +510,44 @@ __device__ void cloud_program(const CloudGT& c, const HspLossCfg& cfg, int B, in
     }
 
     // ---- recon_loss.py:555-649: planes through the votes, the box they make
-    T nrm[2][3][3], cc[2][3];                       // [up / down][axis][xyz], signed offset
+    using W = typename Wide<T>::type;
+    T nrm[2][3][3];                                 // [up / down][axis][xyz]
+    W dis[2][3];                                    // |n . T_pred + offset|: the predicted centre's distance from each fitted face
+    W Tw[3];
+    for (int i = 0; i < 3; ++i) Tw[i] = Wide<T>::widen(Tp[i]);
     T vote = lift<T>(0.f);
     bool isbad = false;
     for (int h = 0; h < 2; ++h) {
         const float sign = h == 0 ? 1.f : -1.f;
         for (int a = 0; a < 3; ++a) {
-            const T* m = S + (3 * h + a) * 9;
-            // normal equations M X = rhs, X by cofactors (the device form of torch.inverse for 3x3)
-            const T m00 = m[0], m01 = m[1], m02 = m[2], m11 = m[3], m12 = m[4], m22 = m[5];
-            const T A = m11 * m22 - m12 * m12, Bc = m02 * m12 - m01 * m22, C = m01 * m12 - m02 * m11;
-            const T D = m12 * m02 - m01 * m22, E = m00 * m22 - m02 * m02, F = m02 * m01 - m00 * m12;
-            const T G = m01 * m12 - m11 * m02, H = m01 * m02 - m00 * m12, I = m00 * m11 - m01 * m01;
-            const T det = m00 * A + m01 * D + m02 * G;
-            const T X0 = (A * m[6] + Bc * m[7] + C * m[8]) / det;
-            const T X1 = (D * m[6] + E * m[7] + F * m[8]) / det;
-            const T X2 = (G * m[6] + H * m[7] + I * m[8]) / det;
-            const T norm2 = X0 * X0 + X1 * X1 + 1.0f;
-            T dn[3] = {(X0 * X2) / (norm2 + 1e-8f), (X1 * X2) / (norm2 + 1e-8f), (-X2) / (norm2 + 1e-8f)};
-            const T dl = norm3(dn);
-            T n[3] = {dn[0] / dl, dn[1] / dl, dn[2] / dl};
-            T co = X2 / t_sqrt(norm2);
+            // normal equations M X = rhs, X by cofactors (the device form of torch.inverse for 3x3); the solve, the normal and
+            // the distance of the predicted centre from the plane (a difference of two numbers ~8 x its size) in fp64
+            W m[9];
+            for (int i = 0; i < 9; ++i) m[i] = Wide<T>::make(mom[(3 * h + a) * 9 + i], mom_dir == (3 * h + a) * 9 + i);
+            const W m00 = m[0], m01 = m[1], m02 = m[2], m11 = m[3], m12 = m[4], m22 = m[5];
+            const W A = m11 * m22 - m12 * m12, Bc = m02 * m12 - m01 * m22, C = m01 * m12 - m02 * m11;
+            const W D = m12 * m02 - m01 * m22, E = m00 * m22 - m02 * m02, F = m02 * m01 - m00 * m12;
+            const W G = m01 * m12 - m11 * m02, H = m01 * m02 - m00 * m12, I = m00 * m11 - m01 * m01;
+            const W det = m00 * A + m01 * D + m02 * G;
+            const W X0 = (A * m[6] + Bc * m[7] + C * m[8]) / det;
+            const W X1 = (D * m[6] + E * m[7] + F * m[8]) / det;
+            const W X2 = (G * m[6] + H * m[7] + I * m[8]) / det;
+            const W norm2 = X0 * X0 + X1 * X1 + 1.0;
+            const W dnw[3] = {(X0 * X2) / (norm2 + 1e-8), (X1 * X2) / (norm2 + 1e-8), (-X2) / (norm2 + 1e-8)};
+            const W dl = w_sqrt(dnw[0] * dnw[0] + dnw[1] * dnw[1] + dnw[2] * dnw[2]);
+            W nw[3] = {dnw[0] / dl, dnw[1] / dl, dnw[2] / dl};
+            W co = X2 / w_sqrt(norm2);
             const float ax[3] = {sign * c.R[a], sign * c.R[3 + a], sign * c.R[6 + a]};
-            const bool flip = val(n[0]) * ax[0] + val(n[1]) * ax[1] + val(n[2]) * ax[2] < 0.f;
-            if (flip) { for (int i = 0; i < 3; ++i) n[i] = -n[i]; co = -co; }
-            for (int i = 0; i < 3; ++i) { nrm[h][a][i] = n[i]; isbad = isbad || isnan(val(n[i])); }
-            cc[h][a] = co;
-            isbad = isbad || isnan(val(co));
+            const bool flip = wval(nw[0]) * ax[0] + wval(nw[1]) * ax[1] + wval(nw[2]) * ax[2] < 0.0;
+            if (flip) { for (int i = 0; i < 3; ++i) nw[i] = -nw[i]; co = -co; }
+            T dn[3];
+            for (int i = 0; i < 3; ++i) {
+                dn[i] = Wide<T>::narrow(dnw[i]);
+                nrm[h][a][i] = Wide<T>::narrow(nw[i]);
+                isbad = isbad || isnan(wval(nw[i]));
+            }
+            isbad = isbad || isnan(wval(co));
+            dis[h][a] = w_abs(nw[0] * Tw[0] + nw[1] * Tw[1] + nw[2] * Tw[2] + co);
             // the fitted foot point against the true one
             const float re_s = c.s[a] + c.ms[a];
             float fc[3], dots = 0.f;
@@ -518,11 +574,10 @@ __device__ void cloud_program(const CloudGT& c, const HspLossCfg& cfg, int B, in
             }
             rr = rr + eu / 3.f + ed / 3.f;
             self = self + par / 3.f;
-            const T du = t_abs(dot3(nrm[0][a], Tp) + cc[0][a]);
-            const T dd = t_abs(dot3(nrm[1][a], Tp) + cc[1][a]);
-            tt = tt + t_abs(dd - du);
-            const T hs = (sp[a] + c.ms[a]) / 2.0f;
-            ss = ss + t_abs(hs - du) + t_abs(hs - dd);
+            const W du = dis[0][a], dd = dis[1][a];
+            tt = tt + Wide<T>::narrow(w_abs(dd - du));
+            const W hs = Wide<T>::widen((sp[a] + c.ms[a]) / 2.0f);
+            ss = ss + Wide<T>::narrow(w_abs(hs - du)) + Wide<T>::narrow(w_abs(hs - dd));
             if (a != 1) self = self + t_abs(dot3(nrm[0][1], nrm[0][a])) + t_abs(dot3(nrm[1][1], nrm[1][a]));
         }
         term[T_BB_R] = rr * (cfg.recon_bb_r_w / 6.f / fB);
@@ -549,10 +604,10 @@ __global__ __launch_bounds__(256) void loss_finish_kernel(const float* gt_R, con
     for (int b = threadIdx.x; b < B; b += blockDim.x) {
         CloudGT c;
         load_gt(c, gt_R, gt_t, gt_s, mean_shape, sym, obj_id, b);
-        float g[3], r[3], T[3], s[3], S[NMOM], term[NT], bad;
+        float g[3], r[3], T[3], s[3], term[NT], bad;
         for (int i = 0; i < 3; ++i) { g[i] = p_green[b * 3 + i]; r[i] = p_red[b * 3 + i]; T[i] = pred_T[b * 3 + i]; s[i] = pred_s[b * 3 + i]; }
-        for (int i = 0; i < NMOM; ++i) S[i] = (float)mom[b * NMOM + i];
-        cloud_program<float>(c, cfg, B, N, scale2, red + b * NRED, S, g, r, f_green[b], f_red[b], T, s, term, &bad);
+        cloud_program<float>(c, cfg, B, N, scale2, red + b * NRED, mom + (size_t)b * NMOM, -1, g, r, f_green[b], f_red[b], T, s, term,
+                             &bad);
         for (int k = 0; k < NT; ++k) per_cloud[b * (NT + 1) + k] = term[k];
         per_cloud[b * (NT + 1) + NT] = bad;
     }
@@ -575,7 +630,7 @@ __global__ __launch_bounds__(128) void loss_cloud_bwd_kernel(const float* gt_R, 
                                                              const float* p_green, const float* p_red, const float* f_green,
                                                              const float* f_red, const float* pred_T, const float* pred_s,
                                                              const float* red, const double* mom, const float* gw,
-                                                             HspLossCfg cfg, int B, int N, float* d_mom /* (B,54) */,
+                                                             HspLossCfg cfg, int B, int N, double* d_mom /* (B,54) */,
                                                              float* d_green, float* d_red, float* d_fg, float* d_fr,
                                                              float* d_T, float* d_s) {
     const int b = blockIdx.x, l = threadIdx.x;
@@ -583,8 +638,7 @@ __global__ __launch_bounds__(128) void loss_cloud_bwd_kernel(const float* gt_R, 
     CloudGT c;
     load_gt(c, gt_R, gt_t, gt_s, mean_shape, sym, obj_id, b);
     auto seed = [&](float v, int dir) { return Dual{v, l == dir ? 1.f : 0.f}; };
-    Dual g[3], r[3], T[3], s[3], S[NMOM], term[NT];
-    for (int i = 0; i < NMOM; ++i) S[i] = seed((float)mom[b * NMOM + i], i);
+    Dual g[3], r[3], T[3], s[3], term[NT];
     for (int i = 0; i < 3; ++i) {
         g[i] = seed(p_green[b * 3 + i], 54 + i);
         r[i] = seed(p_red[b * 3 + i], 57 + i);
@@ -594,16 +648,17 @@ __global__ __launch_bounds__(128) void loss_cloud_bwd_kernel(const float* gt_R, 
     // the confidences are variables only in R_con (HSPose.py:84-160 detaches them everywhere else): the frames take val()
     const Dual fg = seed(f_green[b], 66), fr = seed(f_red[b], 67);
     float bad;
-    cloud_program<Dual>(c, cfg, B, N, scale2, red + b * NRED, S, g, r, fg, fr, T, s, term, &bad);
-    float grad = 0.f;
+    cloud_program<Dual>(c, cfg, B, N, scale2, red + b * NRED, mom + (size_t)b * NMOM, l < NMOM ? l : -1, g, r, fg, fr, T, s, term,
+                        &bad);
+    double grad = 0.0;
     for (int k = 0; k < NT; ++k) grad += gw[k] * term[k].d;
     if (l < NMOM) d_mom[b * NMOM + l] = grad;
-    else if (l < 57) d_green[b * 3 + (l - 54)] = grad;
-    else if (l < 60) d_red[b * 3 + (l - 57)] = grad;
-    else if (l < 63) d_T[b * 3 + (l - 60)] = grad;
-    else if (l < 66) d_s[b * 3 + (l - 63)] = grad;
-    else if (l == 66) d_fg[b] = grad;
-    else if (l == 67) d_fr[b] = grad;
+    else if (l < 57) d_green[b * 3 + (l - 54)] = (float)grad;
+    else if (l < 60) d_red[b * 3 + (l - 57)] = (float)grad;
+    else if (l < 63) d_T[b * 3 + (l - 60)] = (float)grad;
+    else if (l < 66) d_s[b * 3 + (l - 63)] = (float)grad;
+    else if (l == 66) d_fg[b] = (float)grad;
+    else if (l == 67) d_fr[b] = (float)grad;
 }
 
 // ---- kernel 5: points pass 2 -- per-point gradients ---------------------------------------------------------------------
@@ -611,7 +666,7 @@ __global__ __launch_bounds__(256) void loss_points_bwd_kernel(
     const float* __restrict__ PC, const float* gt_R, const float* gt_t, const float* gt_s, const float* mean_shape,
     const float* sym, const float* obj_id, const float* __restrict__ recon, const float* __restrict__ face_normal,
     const float* __restrict__ face_dis, const float* __restrict__ face_f, const float* p_green, const float* pred_T,
-    const float* __restrict__ prm, const float* __restrict__ d_mom, const float* gw, HspLossCfg cfg, int B, int N,
+    const float* __restrict__ prm, const double* __restrict__ d_mom, const float* gw, HspLossCfg cfg, int B, int N,
     float* __restrict__ d_recon, float* __restrict__ d_fn, float* __restrict__ d_fd, float* __restrict__ d_ff) {
     const int b = blockIdx.y;
     const int n = blockIdx.x * blockDim.x + threadIdx.x;
@@ -656,10 +711,11 @@ __global__ __launch_bounds__(256) void loss_points_bwd_kernel(
         const float conf = expf(-303.5f * err * err);
         const float kc = wc * sgnf(conf - ff) * (-607.0f * conf);          // d|conf - ff| = sgn * conf * (-303.5 * 2) (v . dv)
         // votes: moments -> coordinates
-        const float* G = d_mom + (size_t)b * NMOM + j * 9;
-        const float w = ff, x = q.P[0] + fd * fn[0], y = q.P[1] + fd * fn[1], z = q.P[2] + fd * fn[2];
-        const float dv[3] = {w * (2.f * x * G[0] + y * G[1] + G[2] + z * G[6]), w * (x * G[1] + 2.f * y * G[3] + G[4] + z * G[7]),
-                             w * (x * G[6] + y * G[7] + G[8])};
+        // (in fp64: the nine moment gradients of an ill-conditioned fit cancel to a fraction of their size here)
+        const double* G = d_mom + (size_t)b * NMOM + j * 9;
+        const double w = ff, x = q.P[0] + (double)fd * fn[0], y = q.P[1] + (double)fd * fn[1], z = q.P[2] + (double)fd * fn[2];
+        const float dv[3] = {(float)(w * (2.0 * x * G[0] + y * G[1] + G[2] + z * G[6])),
+                             (float)(w * (x * G[1] + 2.0 * y * G[3] + G[4] + z * G[7])), (float)(w * (x * G[6] + y * G[7] + G[8]))};
         float gfd = wd * sgnf(fd - dg);
         for (int i = 0; i < 3; ++i) {
             d_fn[(pn * 6 + nj) * 3 + i] = -wn * ng[i] + kc * fd * v[i] + dv[i] * fd;
@@ -827,7 +883,7 @@ extern "C" int hsp_pose_losses_bwd(const float* PC, const float* gt_R, const flo
                                    const float* face_normal, const float* face_dis, const float* face_f,
                                    const float* p_green, const float* p_red, const float* f_green, const float* f_red,
                                    const float* pred_T, const float* pred_s, int B, int N, const HspLossCfg* cfg,
-                                   const float* grad_terms, const void* ws, size_t ws_bytes, float* d_mom_scratch,
+                                   const float* grad_terms, const void* ws, size_t ws_bytes, double* d_mom_scratch,
                                    float* d_recon, float* d_face_normal, float* d_face_dis, float* d_face_f, float* d_green,
                                    float* d_red, float* d_f_green, float* d_f_red, float* d_T, float* d_s,
                                    hspStream_t stream) {

@@ -131,7 +131,7 @@ class _PoseLosses(torch.autograd.Function):
                 gw = gw + g_total.reshape(1).float()
         shapes = [(B, N, 3), (B, N, 6, 3), (B, N, 6), (B, N, 6), (B, 3), (B, 3), (B,), (B,), (B, 3), (B, 3)]
         outs = [torch.empty(s, dtype=torch.float32, device=dev) for s in shapes]
-        scratch = torch.empty(B * 54, dtype=torch.float32, device=dev)
+        scratch = torch.empty(B * 54, dtype=torch.float64, device=dev)
         ops._run("hsp_pose_losses_bwd", [ops._p(a) for a in ctx.args] + [B, N, ctypes.byref(ctx.cfg), ops._p(gw), ops._p(ctx.ws),
                                                                         ctx.ws.numel(), ops._p(scratch)]
                  + [ops._p(o) for o in outs] + [ops._stream()])

@@ -134,9 +134,13 @@ def _masked_mean_rescaled(values, keep):
 def _inverse3(m):
     """inverse of (...,3,3) matrices.  On the GPU by cofactors (nine fused element-wise kernels): torch.inverse goes
     through a batched LU in the solver library with a host synchronisation -- milliseconds for 48 matrices -- and so
-    does its backward.  On the CPU torch.inverse (the reference's call; keeps the CPU parity tests at 1e-6)."""
+    does its backward.  The cofactors are taken in float64: the formula is not backward stable, and on the normal equations
+    of a face that stands nearly parallel to the camera axis float32 cofactors lose up to 4e-3 of a box term where a
+    float32 LU loses 5e-5 (tests/test_gpu_loss_reference.py; csrc/losses.hip solves in float64 for the same reason).
+    On the CPU torch.inverse (the reference's call; keeps the CPU parity tests at 1e-6)."""
     if not m.is_cuda:
         return torch.inverse(m)
+    dtype, m = m.dtype, m.double()
     a, b, c = m[..., 0, 0], m[..., 0, 1], m[..., 0, 2]
     d, e, f = m[..., 1, 0], m[..., 1, 1], m[..., 1, 2]
     g, h, i = m[..., 2, 0], m[..., 2, 1], m[..., 2, 2]
@@ -145,7 +149,7 @@ def _inverse3(m):
     G, H, I = d * h - e * g, b * g - a * h, a * e - b * d
     det = a * A + b * D + c * G
     adj = torch.stack([torch.stack([A, B, C], dim=-1), torch.stack([D, E, Fc], dim=-1), torch.stack([G, H, I], dim=-1)], dim=-2)
-    return adj / det.unsqueeze(-1).unsqueeze(-1)
+    return (adj / det.unsqueeze(-1).unsqueeze(-1)).to(dtype)
 
 
 # ------------------------------------------------------------------------------------------------------------

@@ -1019,7 +1019,7 @@ int hsp_bn_relu_bwd_bf16(const hsp_bf16_t *x, const hsp_bf16_t *dy, int R, int C
  * The axis confidences are variables only in R_con and the face confidences only in recon_p_f (HSPose.py detaches them
  * elsewhere).  `cfg` is a HOST struct.  The workspace written by _fwd is read by _bwd (keep it until then).
  * _bwd: grad_terms (19) = d(objective)/d(term); every d_* buffer is OVERWRITTEN with the gradient w.r.t. that network output;
- * d_mom_scratch: B*54 floats.  Five launches in all; sums in a fixed order (bit-reproducible). */
+ * d_mom_scratch: B*54 doubles.  Five launches in all; sums in a fixed order (bit-reproducible). */
 #define HSP_LOSS_TERMS 19
 typedef struct HspLossCfg {       /* config/config.py:64-93 */
     float rot_1_w, rot_2_w, rot_regular, tran_w, size_w, r_con_w;
@@ -1038,7 +1038,7 @@ int hsp_pose_losses_bwd(const float *PC, const float *gt_R, const float *gt_t, c
                         const float *face_dis, const float *face_f, const float *p_green, const float *p_red,
                         const float *f_green, const float *f_red, const float *pred_T, const float *pred_s, int B, int N,
                         const HspLossCfg *cfg, const float *grad_terms, const void *ws, size_t ws_bytes,
-                        float *d_mom_scratch, float *d_recon, float *d_face_normal, float *d_face_dis, float *d_face_f,
+                        double *d_mom_scratch, float *d_recon, float *d_face_normal, float *d_face_dis, float *d_face_f,
                         float *d_green, float *d_red, float *d_f_green, float *d_f_red, float *d_T, float *d_s,
                         hspStream_t stream);
 

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+from _loss_ref import wire
 from conftest import golden
 
 LOSS_KEYS = {
@@ -18,32 +19,11 @@ LOSS_KEYS = {
 
 def run_losses(ref, device, flags, loss_type):
     """HSPose's loss wiring (its forward after the network call) on the closed-form batch"""
-    from hs_pose_amd import HSPose as H
     flags.fsnet_loss_type = loss_type
     gt, pred = ref.loss_case()
     gt = {k: v.to(device) for k, v in gt.items()}
     pred = {k: v.detach().to(device).requires_grad_(True) for k, v in pred.items()}
-    names = H.control_loss('PoseNet_only')
-    g_green, g_red = H.get_gt_v(gt["gt_R"])
-    p, sym, PC = pred, gt["sym"], gt["PC"]
-    ld = {
-        'fsnet_loss': H.fs_net_loss()(names[0], {'Rot1': p["p_green_R"], 'Rot1_f': p["f_green_R"], 'Rot2': p["p_red_R"],
-                                                 'Rot2_f': p["f_red_R"], 'Recon': p["recon"], 'Tran': p["Pred_T"], 'Size': p["Pred_s"]},
-                                      {'Rot1': g_green, 'Rot2': g_red, 'Recon': PC, 'Tran': gt["gt_t"], 'Size': gt["gt_s"]}, sym),
-        'recon_loss': H.recon_6face_loss()(names[1], {'F_n': p["face_normal"], 'F_d': p["face_dis"], 'F_c': p["face_f"],
-                                                      'Rot1': p["p_green_R"], 'Rot1_f': p["f_green_R"].detach(), 'Rot2': p["p_red_R"],
-                                                      'Rot2_f': p["f_red_R"].detach(), 'Tran': p["Pred_T"], 'Size': p["Pred_s"]},
-                                           {'R': gt["gt_R"], 'T': gt["gt_t"], 'Size': gt["gt_s"], 'Mean_shape': gt["mean_shape"],
-                                            'Points': PC}, sym, gt["obj_id"]),
-        'geo_loss': H.geo_transform_loss()(names[2], {'Rot1': p["p_green_R"], 'Rot2': p["p_red_R"], 'Tran': p["Pred_T"],
-                                                      'Size': p["Pred_s"], 'Rot1_f': p["f_green_R"].detach(),
-                                                      'Rot2_f': p["f_red_R"].detach()},
-                                           {'Points': PC, 'R': gt["gt_R"], 'T': gt["gt_t"], 'Mean_shape': gt["mean_shape"]}, sym),
-        'prop_loss': H.prop_rot_loss()(names[3], {'Recon': p["recon"], 'Rot1': p["p_green_R"], 'Rot2': p["p_red_R"],
-                                                  'Tran': p["Pred_T"], 'Scale': p["Pred_s"], 'Rot1_f': p["f_green_R"].detach(),
-                                                  'Rot2_f': p["f_red_R"].detach()},
-                                       {'Points': PC, 'R': gt["gt_R"], 'T': gt["gt_t"], 'Mean_shape': gt["mean_shape"]}, sym),
-    }
+    ld = wire(gt, pred)
     return ld, pred
 
 
