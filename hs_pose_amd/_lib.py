@@ -1,213 +1,136 @@
-"""ctypes binding of libhsp.so (include/hsp.h).  Loaded lazily on the first device op; a missing
-library is a hard error -- there is no fallback path."""
+"""ctypes binding of libhsp.so, derived from include/hsp.h at import: prototypes, structs and constants are read from the
+header, nothing of it is restated here.  Loaded lazily on the first device op; a missing library is a hard error -- there is no
+fallback path."""
 import ctypes
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # HSP_LIB=<path> loads another build of the same ABI (profiling variants); default: the in-tree library
 LIB_PATH = os.environ.get("HSP_LIB") or os.path.join(_HERE, "libhsp.so")
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hsp.h")
 _lib = None
-
-_vp, _i, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t
-
-# name -> (restype, argtypes); must list every symbol declared in include/hsp.h
-SIGNATURES = {
-    "hsp_version": (_i, []),
-    "hsp_error_string": (ctypes.c_char_p, [_i]),
-    "hsp_last_hip_error": (ctypes.c_char_p, []),
-    "hsp_knn_workspace_bytes": (_sz, [_i, _i, _i, _i]),
-    "hsp_knn_f32": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
-    "hsp_nn1_f32": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp]),
-    "hsp_rf_surface_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
-    "hsp_rf_bwd_workspace_bytes": (_sz, [_i]),
-    "hsp_rf_surface_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
-    "hsp_rf_conv_wants_fwin": (_i, [_i, _i, _i]),
-    "hsp_rf_conv_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
-    "hsp_rf_conv_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
-    "hsp_rf_bwd_scatter_workspace_bytes": (_sz, [_i, _i]),
-    "hsp_rf_conv_bwd_scatter": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
-    "hsp_rev_build": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
-    "hsp_rev_build_multi": (_i, [_i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "hsp_gather_max_bwd_csr": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
-    "hsp_gather_max_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
-    "hsp_pool_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
-    "hsp_gather_max_bwd": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp]),
-    "hsp_gather_max_fwd_sel": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
-    "hsp_pool_fwd_sel": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
-    "hsp_gather_max_bwd_sel": (_i, [_vp, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp]),
-    "hsp_gather_max_fwd_sel_bf16": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
-    "hsp_gather_max_bwd_sel_bf16": (_i, [_vp, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp]),
-    "hsp_fps_levels_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
-    "hsp_points_max_fwd": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
-    "hsp_points_max_bwd": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
-    "hsp_orl_workspace_bytes": (_sz, [_i, _i, _i]),
-    "hsp_orl_counts_offset": (ctypes.c_longlong, [_i, _i, _i, _i, _i, _sz]),
-    "hsp_knn_exact_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
-    "hsp_knn_exact_f32": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp, _vp]),
-    "hsp_knn_xyz_workspace_bytes": (_sz, [_i, _i]),
-    "hsp_knn_xyz_f32": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp, _vp]),
-    "hsp_geometry_levels_f32": (_i, [_vp, _i, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "hsp_geometry_all_workspace_bytes": (_sz, [_i, _i]),
-    "hsp_geometry_all_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
-                                  _vp]),
-    "hsp_knn_quadmode_f32": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _sz, _i, _vp]),
-    "hsp_quad_outer_f32": (_i, [_vp, _i, _i, _i, _vp, _vp]),
-    "hsp_center_cloud_f32": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
-    "hsp_orl_exact_workspace_bytes": (_sz, [_i, _i, _i]),
-    "hsp_orl_global_exact_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
-    "hsp_bn_eval_f32": (_i, [_vp, ctypes.c_longlong, _i, _vp, _vp, _vp, _vp, _vp, ctypes.c_float, _i, _vp, _vp]),
-    "hsp_layer_out_exact_f32": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _i, _vp]),
-    "hsp_orl_global_fwd": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
-    "hsp_colsum_rows": (_i, [_vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
-    "hsp_add_relu_bwd": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _vp, _vp]),
-    "hsp_residual_bias": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
-    "hsp_concat_rows": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
-    "hsp_gather_rows_fwd": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp]),
-    "hsp_gather_rows_bwd": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
-    "hsp_gather_rows_bwd_csr": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
-    "hsp_gather_rows_bwd_csr_multi": (_i, [_i, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp]),
-    "hsp_gather_rows_bwd_csr_multi_bf16": (_i, [_i, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp]),
-    "hsp_gemm_rows_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
-    "hsp_gemm_rows_f32": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _i, ctypes.c_float, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
-    "hsp_gemm_rows_bf16": (_i, [_vp, _i, _vp, _i, _i, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _i, ctypes.c_float, _vp, _vp, _vp, _i, _i, _vp, _sz, _vp]),
-    "hsp_gemm_wave_supported": (_i, [_i, _i, _i, _i, _i]),
-    "hsp_gemm_wave_plan_info": (_i, [_i, _i, _i, _i, _i, _vp]),
-    "hsp_gemm_wave_f32": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _i, ctypes.c_float, _vp, _vp, _vp, _i, _i, _vp]),
-    "hsp_split_params_x3": (_i, [_vp, _i, _i, _vp]),
-    "hsp_gemm_x3_supported": (_i, [_i, _i, _i, _i]),
-    "hsp_gemm_x3_workspace_bytes": (_sz, [_i, _i, _i, _i]),
-    "hsp_gemm_x3_f32": (_i, [_vp, _i, _vp, _i, ctypes.c_longlong, _i, _vp, _i, _vp, _i, ctypes.c_longlong, _i, _i, _i, _vp, _vp, _i, _vp, _i,
-                             ctypes.c_float, _vp, _i, _vp, _sz, _vp]),
-    "hsp_gemm_takes": (_i, [_vp, _i]),
-    "hsp_gemm_route": (_i, [_vp]),
-    "hsp_small_rows_f32": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, ctypes.c_float, _vp, _i, _vp]),
-    "hsp_small_outer_f32": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _i, _vp, _vp]),
-    "hsp_colsum_rows_xyz": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
-    "hsp_colsum_rows_xyz_bf16": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
-    "hsp_colsum_cloud_ok": (_i, [_i, _i, _i, _i]),
-    "hsp_colsum_cloud_f32": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
-    "hsp_small_pair_f32": (_i, [_vp, _i, _i, _i, _vp, _i, _i, ctypes.c_float, _vp, _i, _vp, _i, _i, _vp, _i, _vp, _i, _i, _vp, _vp]),
-    "hsp_bn_relu_fwd_mixed": (_i, [_vp, _i, _i, _vp, _vp, ctypes.c_float, ctypes.c_float, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "hsp_bn_relu_apply_mixed": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
-    "hsp_bn_relu_bwd_mixed": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "hsp_cast_params_bf16": (_i, [_vp, _i, _i, _vp]),
-    "hsp_cast_params_pitched_bf16": (_i, [_vp, _i, _i, _vp]),
-    "hsp_wgrad_ragged_bf16": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _sz, _vp]),
-    "hsp_wgrad_ragged_partial_bf16": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _sz, _vp, _vp]),
-    "hsp_gemm_rows_acc_bf16": (_i, [_vp, _i, _vp, _i, _i, _vp, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _i, _vp, _sz, _vp]),
-    "hsp_points_max_fwd_bf16": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
-    "hsp_gemm_rows_bn_tiles_bf16": (_i, [_i, _i, _i]),
-    "hsp_gemm_rows_bn_bf16": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
-    "hsp_bn_relu_fwd_partials_mixed": (_i, [_vp, _i, _i, _vp, _vp, ctypes.c_float, ctypes.c_float, _i, _vp, _vp, _vp, _vp, _vp, _vp,
-                                            _vp, _i, _vp, _vp]),
-    "hsp_points_max_bwd_bf16": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
-    "hsp_knn_bf16": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
-    "hsp_rf_surface_fwd_bf16": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
-    "hsp_rf_surface_bwd_bf16": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
-    "hsp_rf_conv_wants_fwin_bf16": (_i, [_i, _i, _i]),
-    "hsp_rf_conv_fwd_bf16": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
-    "hsp_rf_conv_bwd_scatter_bf16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
-    "hsp_gather_max_fwd_bf16": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
-    "hsp_gather_max_bwd_bf16": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp]),
-    "hsp_orl_global_fwd_bf16": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
-    "hsp_colsum_rows_bf16": (_i, [_vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
-    "hsp_concat_rows_pitched": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _vp]),
-    "hsp_concat_rows_bf16": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _vp]),
-    "hsp_gather_rows_bwd_csr_bf16": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
-    "hsp_wgrad_bf16": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _sz, _vp]),
-    "hsp_bn_relu_fwd_bf16": (_i, [_vp, _i, _i, _vp, _vp, ctypes.c_float, ctypes.c_float, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "hsp_bn_relu_apply_bf16": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
-    "hsp_bn_relu_bwd_bf16": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "hsp_wgrad_workspace_bytes": (_sz, [_i, _i, _i]),
-    "hsp_wgrad_f32": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _sz, _vp]),
-    "hsp_bn_workspace_bytes": (_sz, [_i, _i]),
-    "hsp_bn_relu_fwd": (_i, [_vp, _i, _i, _vp, _vp, ctypes.c_float, ctypes.c_float, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "hsp_bn_relu_apply": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
-    "hsp_bn_relu_bwd": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "hsp_gemm_x3_bn_f32": (_i, [_vp, _i, _vp, _i, ctypes.c_longlong, _i, _vp, _i, _vp, _i, ctypes.c_longlong, _i, _i, _i, _vp, _i, _vp, _i,
-                                _vp, _i, _vp, _vp, _vp]),
-    "hsp_gemm_x3_bn_tiles": (_i, [_i, _i]),
-    "hsp_gemm_x3_bias_bn_f32": (_i, [_vp, _i, _vp, _i, ctypes.c_longlong, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp]),
-    "hsp_bn_relu_fwd_partials": (_i, [_vp, _i, _i, _vp, _vp, ctypes.c_float, ctypes.c_float, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i,
-                                      _vp, _vp]),
-    "hsp_bn_relu_bwd2": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "hsp_pc_compact_workspace_bytes": (_sz, [_i, _i]),
-    "hsp_pc_compact": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
-    "hsp_pc_gather": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
-    "hsp_depth_to_pcl": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
-    "hsp_roi_compact_workspace_bytes": (_sz, [_i, _i]),
-    "hsp_roi_compact_f32": (_i, [_vp, _vp, ctypes.c_longlong, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
-    "hsp_roi_compact_u16": (_i, [_vp, _vp, ctypes.c_longlong, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
-    "hsp_frame_to_pcl_f32": (_i, [_vp, _i, _i, _vp, _i, _vp, ctypes.c_longlong, _vp, _i, _i, _vp, _vp]),
-    "hsp_frame_to_pcl_u16": (_i, [_vp, _i, _i, _vp, _i, _vp, ctypes.c_longlong, _vp, _i, _i, _vp, _vp]),
-    "hsp_sample_ids": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
-    "hsp_roi_defor_workspace_bytes": (_sz, [_i, _i]),
-    "hsp_roi_defor": (_i, [_vp, ctypes.c_longlong, _vp, _vp, _i, _i, _i, _i, _i, ctypes.c_ulonglong, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "hsp_crop_compact_workspace_bytes": (_sz, [_i, _i]),
-    "hsp_crop_compact_f32": (_i, [_vp, ctypes.c_longlong, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "hsp_crop_compact_u16": (_i, [_vp, ctypes.c_longlong, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "hsp_frames_to_pcl_f32": (_i, [_vp, ctypes.c_longlong, _i, _i, _vp, _i, _vp, ctypes.c_longlong, _vp, _i, _i, _vp, _vp]),
-    "hsp_frames_to_pcl_u16": (_i, [_vp, ctypes.c_longlong, _i, _i, _vp, _i, _vp, ctypes.c_longlong, _vp, _i, _i, _vp, _vp]),
-    "hsp_batch_select": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp, _vp]),
-    "hsp_generate_rt": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
-    "hsp_sumsq_workspace_bytes": (_sz, [ctypes.c_longlong]),
-    "hsp_sumsq_f32": (_i, [_vp, ctypes.c_longlong, _vp, _vp, _sz, _vp]),
-    "hsp_ranger_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, ctypes.c_float, ctypes.c_float, ctypes.c_float,
-                             ctypes.c_float, ctypes.c_float, _i, _i, ctypes.c_float, _i, _vp, ctypes.c_float, _vp]),
-    "hsp_chamfer_fwd": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
-    "hsp_chamfer_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
-    "hsp_fps_workspace_bytes": (_sz, [_i, _i]),
-    "hsp_fps_f32": (_i, [_vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
-    "hsp_fps_f64": (_i, [_vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
-    "hsp_axis_conf_fwd": (_i, [_vp, _i, _vp, _vp, _vp]),
-    "hsp_axis_conf_bwd": (_i, [_vp, _vp, _vp, _i, _vp, _vp]),
-    "hsp_face_split_fwd": (_i, [_vp, ctypes.c_longlong, _vp, _vp, _vp, _vp]),
-    "hsp_face_split_bwd": (_i, [_vp, _vp, _vp, _vp, ctypes.c_longlong, _vp, _vp]),
-    "hsp_pose_losses_workspace_bytes": (_sz, [_i]),
-    "hsp_pose_losses_fwd": (_i, [_vp] * 17 + [_i, _i, _vp, _vp, _vp, _sz, _vp]),
-    "hsp_pose_losses_bwd": (_i, [_vp] * 17 + [_i, _i, _vp, _vp, _vp, _sz] + [_vp] * 11 + [_vp]),
-    "hsp_wgrad_partial_f32": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _sz, _vp, _vp]),
-    "hsp_wgrad_partial_bf16": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _sz, _vp, _vp]),
-    "hsp_wgrad_fold": (_i, [_vp, _i, _vp]),
-    "hsp_step_fold": (_i, [_vp, _i, _vp, _i, _vp]),
-    "hsp_rf_surface_bwd_partial": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _sz, _vp, _vp]),
-    "hsp_rf_conv_bwd_scatter_partial": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp, _vp]),
-    "hsp_rf_surface_bwd_partial_bf16": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _sz, _vp, _vp]),
-    "hsp_rf_conv_bwd_scatter_partial_bf16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp, _vp]),
-    "hsp_wgrad_partial_pair_f32": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp, _sz] * 2 + [_vp, _vp]),
-    "hsp_wgrad_partial_pair_colsum_f32": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp, _sz] * 2 + [_vp, _vp, _i, _i, _i, _vp, _vp]),
-    "hsp_rf_fwd_plan": (_i, [_i, _i, _i, _vp]),
-    "hsp_rf_bwd_scatter_plan": (_i, [_i, _i, _i, _i, _i, _vp]),
-    "hsp_rf_bwd_set_schedule": (_i, [_i]),
-    "hsp_scatter_tile_plan": (_i, [_i, _i, _i, _vp]),
-    "hsp_wgrad_plan": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _vp]),
-    "hsp_wgrad_pair_plan": (_i, [_i, _i, _i, _i, _i, _i, _vp]),
-    "hsp_gemm_rows_plan": (_i, [_i, _i, _i, _i, _i, _i, _vp]),
-    "hsp_gemm_x3_plan": (_i, [_i, _i, _i, _i, _i, _i, _vp]),
-    "hsp_pose_augment": (_i, [_vp] * 14 + [_i, _i, _i] + [ctypes.c_float] * 4 + [_vp] * 5),
-    "hsp_pose_augment_keyed": (_i, [_vp] * 13 + [ctypes.c_float, _i, _i, _i] + [ctypes.c_float] * 4 + [_vp] * 5),
-    "hsp_pool_rows_draw": (_i, [_vp, _i, _i, _i, _vp, _vp]),
-    "hsp_dzi_windows": (_i, [_vp, _vp, _i, _i, _i, _i, ctypes.c_double, ctypes.c_double, ctypes.c_double, _vp, _vp]),
-}
-
-
-class HspLossCfg(ctypes.Structure):
-    """include/hsp.h: HspLossCfg (a HOST struct)"""
-    _fields_ = [(n, ctypes.c_float) for n in (
-        "rot_1_w", "rot_2_w", "rot_regular", "tran_w", "size_w", "r_con_w", "recon_n_w", "recon_d_w", "recon_f_w",
-        "recon_v_w", "recon_bb_r_w", "recon_bb_t_w", "recon_bb_s_w", "recon_bb_self_w", "geo_p_w", "prop_pm_w",
-        "prop_sym_w")] + [("smooth_l1", ctypes.c_int)]
-
-
-class HspSplitDesc(ctypes.Structure):
-    """include/hsp.h: HspSplitDesc (the table lives in DEVICE memory; built on the host, uploaded once)"""
-    _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("rows", ctypes.c_int), ("cols", ctypes.c_int),
-                ("ld", ctypes.c_int), ("transpose", ctypes.c_int), ("kp", ctypes.c_int), ("tile0", ctypes.c_int),
-                ("ps", ctypes.c_longlong)]
 
 
 class HspError(RuntimeError):
     pass
+
+
+# the closed table of scalar types the ABI passes by value; a fixed-width type joins it when the header comes to need it
+_SCALARS = {"int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double, "long long": ctypes.c_longlong,
+            "unsigned long long": ctypes.c_ulonglong, "size_t": ctypes.c_size_t, "int32_t": ctypes.c_int32,
+            "uint16_t": ctypes.c_uint16, "uint8_t": ctypes.c_uint8}
+_POINTEES = ("void", "char")            # further type names that may stand under a `*` only
+_STARS = r"((?:\s*\*)*)\s*"
+_DECL = re.compile(r"(.+?)" + _STARS + r"(\w+)\s*(\[\w*\])?", re.S)
+
+
+def parse_header(text):
+    """(prototypes, structs, constants) of the text of include/hsp.h: name -> (restype, [argtypes]), struct name -> [(field,
+    ctype)], HSP_NAME -> int.  Narrow and strict by design: it accepts the forms the header uses and raises ``HspError`` with the
+    offending text on anything else, so a declaration it does not understand fails at import instead of going unbound."""
+    protos, structs, consts, types = {}, {}, {}, dict(_SCALARS)
+
+    def bad(why, what):
+        return HspError(f"include/hsp.h: {why}: `{' '.join(what.split())}`")
+
+    def ctype(base, ptr, whole):
+        """the ctypes type of `base` with (ptr) or without a `*` / `[]`, in the declaration `whole`"""
+        base = " ".join(base.split())
+        if base not in types and base not in structs and not (ptr and base in _POINTEES):
+            raise bad(f"unknown type name `{base}`", whole)
+        if ptr:
+            return ctypes.c_void_p
+        if base in structs:
+            raise bad(f"struct `{base}` passed by value", whole)
+        return types[base]
+
+    def declarator(piece, whole):
+        m = _DECL.fullmatch(piece.strip())
+        if not m:
+            raise bad("declaration not understood", whole)
+        base, stars, name, array = m.groups()
+        return base, name, ctype(base, bool(stars.strip() or array), whole)
+
+    def fields(body, whole):
+        out = []
+        for decl in filter(None, (d.strip() for d in body.split(";"))):
+            first, *more = decl.split(",")
+            base, name, ct = declarator(first, whole)
+            out.append((name, ct))
+            for piece in more:                  # `const void *A1, *B1;`: each declarator carries its own `*`
+                m = re.fullmatch(_STARS + r"(\w+)", piece.strip())
+                if not m:
+                    raise bad("declaration not understood", whole)
+                out.append((m.group(2), ctype(base, bool(m.group(1).strip()), whole)))
+        return out
+
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", " ", text)
+    code, guard, in_cpp = [], None, False
+    for line in text.split("\n"):
+        s = " ".join(line.split())
+        if not s.startswith("#"):
+            if in_cpp and s not in ("", 'extern "C" {', "}"):
+                raise bad("unexpected text in the __cplusplus block", s)
+            if not in_cpp:
+                code.append(line)
+            continue
+        m = re.fullmatch(r"# ?define (HSP_\w+) (\(-?\d+\)|-?\d+)", s)
+        if m:
+            consts[m.group(1)] = int(m.group(2).strip("()"))
+        elif re.fullmatch(r"# ?ifndef \w+", s) and guard is None:
+            guard = s.split()[-1]
+        elif s == "#ifdef __cplusplus":
+            in_cpp = True
+        elif s == "#endif":
+            in_cpp = False
+        elif not (re.fullmatch(r"# ?include <\w+\.h>", s) or (guard and re.fullmatch(r"# ?define " + guard, s))):
+            raise bad("directive not understood", s)
+
+    *stmts, rest = re.sub(r"\{[^{}]*\}", lambda m: m.group(0).replace(";", "\0"), "\n".join(code)).split(";")
+    if rest.strip():
+        raise bad("declaration cut off before `;`", rest)
+    for st in (s.replace("\0", ";").strip() for s in stmts):       # st: the declaration as written, for messages
+        nc = re.sub(r"\bconst\b", " ", st)                          # `const` does not change how a value is passed
+        m = re.fullmatch(r"typedef\s+struct\s+(\w+)\s*\{(.*)\}\s*(\w+)", nc, re.S)
+        if m:
+            if m.group(1) != m.group(3) or m.group(1) in structs:
+                raise bad("struct tag and typedef name differ, or the struct is declared twice", st)
+            structs[m.group(1)] = fields(m.group(2), st)
+            continue
+        if nc.startswith("typedef"):
+            _, name, ct = declarator(nc[len("typedef"):], st)
+            types[name] = ct
+            continue
+        head, _, params = nc.partition("(")
+        m = _DECL.fullmatch(head.strip())
+        if not m or m.group(4) or not params.endswith(")") or "{" in st or m.group(3) in protos:
+            raise bad("declaration not understood, or declared twice", st)
+        ret, stars, name, _ = m.groups()
+        if re.fullmatch(r"const\s+char\s*\*\s*\w+", st.partition("(")[0].strip()):
+            res = ctypes.c_char_p
+        else:
+            res = ctype(ret, bool(stars.strip()), st)
+        protos[name] = (res, [] if params[:-1].strip() == "void" else [declarator(p, st)[2] for p in params[:-1].split(",")])
+    return protos, structs, consts
+
+
+def _read_header():
+    try:
+        with open(HEADER_PATH) as f:
+            return parse_header(f.read())
+    except OSError as e:
+        raise HspError(f"{HEADER_PATH}: the ABI header libhsp.so is bound from cannot be read ({e})") from None
+
+
+# SIGNATURES: name -> (restype, argtypes) of every entry point.  STRUCTS: name -> the struct's ctypes class.  CONSTANTS: the header's
+# HSP_<NAME> integers under <NAME>.  Structs and constants are module attributes too (HspGemmCall, GEMM_ROUTE_X3, ERR_LAUNCH, ...).
+SIGNATURES, _fields, _consts = _read_header()
+STRUCTS = {n: type(n, (ctypes.Structure,), {"_fields_": f, "__doc__": f"include/hsp.h: {n}"}) for n, f in _fields.items()}
+CONSTANTS = {n[len("HSP_"):]: v for n, v in _consts.items()}
+globals().update(STRUCTS)
+globals().update(CONSTANTS)
 
 
 def lib():
@@ -238,37 +161,4 @@ def check(rc, what):
         L = lib()
         msg = L.hsp_error_string(rc).decode()
         hip = L.hsp_last_hip_error().decode()
-        raise HspError(f"{what} failed: {msg} (code {rc})" + (f" [hip: {hip}]" if hip and rc == -4 else ""))
-
-
-class HspWgradPending(ctypes.Structure):
-    """include/hsp.h: HspWgradPending (a HOST struct)"""
-    _fields_ = [("part", ctypes.c_void_p), ("cs_part", ctypes.c_void_p), ("C", ctypes.c_void_p), ("colsum", ctypes.c_void_p),
-                ("nparts", ctypes.c_int), ("M", ctypes.c_int), ("N", ctypes.c_int), ("ldc", ctypes.c_int)]
-
-
-class HspGemmCall(ctypes.Structure):
-    """include/hsp.h: HspGemmCall (a HOST struct)"""
-    _fields_ = ([(n, ctypes.c_void_p) for n in ("A1", "B1", "A2", "B2", "resid", "C")] + [(n, ctypes.c_int) for n in (
-        "M", "N", "K1", "K2", "b1_layout", "b2_layout", "elem_bytes", "lda1", "ldb1", "lda2", "ldb2", "ldr", "ldc",
-        "bias", "cloud_bias", "xyz3", "relu", "alpha_one", "rows_per_cloud", "bn", "allow_x3")])
-
-
-# include/hsp.h: HSP_GEMM_ROUTE_* / HSP_GEMM_BN_*
-ROUTE_NONE, ROUTE_SMALL_ROWS, ROUTE_X3, ROUTE_X3_BN, ROUTE_WAVE, ROUTE_TILE = range(6)
-BN_NONE, BN_OUT, BN_LINEAR = range(3)
-
-
-class HspDirsPending(ctypes.Structure):
-    """include/hsp.h: HspDirsPending (a HOST struct)"""
-    _fields_ = [("part", ctypes.c_void_p), ("dirs", ctypes.c_void_p), ("grad_dirs", ctypes.c_void_p),
-                ("nparts", ctypes.c_int), ("SC", ctypes.c_int)]
-
-
-class HspSelectSeg(ctypes.Structure):
-    """include/hsp.h: HspSelectSeg (a HOST struct)"""
-    _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("fill", ctypes.c_void_p), ("row_bytes", ctypes.c_longlong)]
-
-
-# include/hsp.h: HSP_BATCH_SELECT_MAX_SEGS / HSP_BATCH_SELECT_MAX_ITEMS
-BATCH_SELECT_MAX_SEGS, BATCH_SELECT_MAX_ITEMS = 16, 1024
+        raise HspError(f"{what} failed: {msg} (code {rc})" + (f" [hip: {hip}]" if hip and rc == CONSTANTS["ERR_LAUNCH"] else ""))

@@ -9,8 +9,11 @@ import os
 
 import torch
 
-from ._lib import (BN_LINEAR, BN_OUT, ROUTE_SMALL_ROWS, ROUTE_TILE, ROUTE_WAVE, ROUTE_X3, ROUTE_X3_BN, HspError, HspGemmCall, check,
-                   lib)
+from ._lib import (BATCH_SELECT_MAX_ITEMS, BATCH_SELECT_MAX_SEGS, ERR_UNSUPPORTED, FOLD_MAX_DIRS, FOLD_MAX_WGRAD, HspDirsPending, HspError,
+                   HspGemmCall, HspSelectSeg, HspSplitDesc, HspWgradPending, check, lib)
+# the routes and BatchNorm forms of hsp_gemm_route under the names this module has always exported (ops.ROUTE_X3, ...)
+from ._lib import (GEMM_BN_LINEAR as BN_LINEAR, GEMM_BN_OUT as BN_OUT, GEMM_ROUTE_SMALL_ROWS as ROUTE_SMALL_ROWS, GEMM_ROUTE_TILE as ROUTE_TILE,
+                   GEMM_ROUTE_WAVE as ROUTE_WAVE, GEMM_ROUTE_X3 as ROUTE_X3, GEMM_ROUTE_X3_BN as ROUTE_X3_BN)
 
 _vp = ctypes.c_void_p
 
@@ -64,6 +67,11 @@ def _ws(nbytes, device):
     return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=device)
 
 
+def upload_table(arr, device):
+    """a ctypes array (a descriptor table of include/hsp.h structs, built on the host) as a uint8 tensor on ``device``"""
+    return torch.frombuffer(bytearray(arr), dtype=torch.uint8).to(device)
+
+
 class KernelTimer:
     """Optional per-call timing of the C-ABI entry points with HIP events recorded on the stream the
     kernels are launched on (torch's current stream).  bench.py installs one over its timed region to
@@ -100,9 +108,6 @@ def set_timer(t):
     return prev
 
 
-_ERR_UNSUPPORTED = -2       # include/hsp.h: HSP_ERR_UNSUPPORTED
-
-
 def _run(name, args, key="", abytes=0, aflops=0, may_decline=False):
     """call libhsp entry point ``name``; raise on a non-zero return code.  abytes / aflops: the call's
     algorithmic bytes and (for GEMM-shaped, MFMA-bound kernels) flops, for bench.py's roofline line.
@@ -116,11 +121,11 @@ def _run(name, args, key="", abytes=0, aflops=0, may_decline=False):
         e0.record()
         rc = fn(*args)
         e1.record()
-        if not (may_decline and rc == _ERR_UNSUPPORTED):
+        if not (may_decline and rc == ERR_UNSUPPORTED):
             t.records.append((name, key, abytes, aflops, e0, e1))
     else:
         rc = fn(*args)
-    if may_decline and rc == _ERR_UNSUPPORTED:
+    if may_decline and rc == ERR_UNSUPPORTED:
         return False
     check(rc, name)
     return True
@@ -656,7 +661,6 @@ class WgradBatch:
         return False
 
     def flush(self):
-        from ._lib import HspWgradPending
         cap = StepFolds.MAX_WGRAD
         while self.items:
             chunk, self.items = self.items[:cap], self.items[cap:]
@@ -676,7 +680,7 @@ class StepFolds:
     very tensors the nodes return; an accumulation into an existing ``.grad`` would read them before the fold):
     ``graph.GraphedStep`` and ``graph.GraphedNetwork``, whose captures replay the fold with the rest of the step."""
     current = None
-    MAX_WGRAD, MAX_DIRS = 24, 8        # include/hsp.h: HSP_FOLD_MAX_WGRAD, HSP_FOLD_MAX_DIRS
+    MAX_WGRAD, MAX_DIRS = FOLD_MAX_WGRAD, FOLD_MAX_DIRS
 
     def __init__(self, bare_wgrad=False):
         """bare_wgrad: also defer ``wgrad`` calls made outside a ``WgradBatch`` (``linear_rows``' backward, which returns a
@@ -701,7 +705,6 @@ class StepFolds:
         return False
 
     def flush(self):
-        from ._lib import HspWgradPending, HspDirsPending
         while self.wgrads or self.dirs:
             w, self.wgrads = self.wgrads[:self.MAX_WGRAD], self.wgrads[self.MAX_WGRAD:]
             d, self.dirs = self.dirs[:self.MAX_DIRS], self.dirs[self.MAX_DIRS:]
@@ -725,7 +728,6 @@ def _rf_bwd_dirs_call(base, sfx, args_before_ws, ws, wsb, keep, key, abytes):
     if sf is None:
         _run(base + sfx, (*args_before_ws, _p(ws), wsb, _stream()), key=key, abytes=abytes)
         return
-    from ._lib import HspDirsPending
     pend = HspDirsPending()
     _run(base + "_partial" + sfx, (*args_before_ws, _p(ws), wsb, ctypes.byref(pend), _stream()), key=key, abytes=abytes)
     sf.dirs.append((pend, ws) + tuple(_hold(t) for t in keep))
@@ -745,7 +747,6 @@ def _wgrad_custom(A2, B2, out, colsum, entry="hsp_wgrad"):
     sf = StepFolds.current
     sink = batch.items if batch is not None else sf.wgrads if sf is not None and sf.bare_wgrad else None
     if sink is not None:
-        from ._lib import HspWgradPending
         pend = HspWgradPending()
         _run(f"{entry}_partial_{sfx}", (_p(A2), A2.stride(0), _p(B2), B2.stride(0), M, N, K, _p(out), out.stride(0), _p(cs),
                                         _p(ws), wsb, ctypes.byref(pend), _stream()),
@@ -818,7 +819,6 @@ def wgrad_pair(A0, B0, out0, A1, B1, out1, colsum_of=None):
         wgrad(A0, B0, out=out0)
         wgrad(A1, B1, out=out1)
         return False
-    from ._lib import HspWgradPending
     L = lib()
     (K0, M0), N0 = A0.shape, B0.shape[1]
     (K1, M1), N1 = A1.shape, B1.shape[1]
@@ -992,7 +992,6 @@ class X3Planes:
         return e["planes"], e["kp"], e["N"] * e["kp"]
 
     def _table_of(self, ents):
-        from ._lib import HspSplitDesc
         tab = (HspSplitDesc * len(ents))()
         tile0 = 0
         for i, e in enumerate(ents):
@@ -1001,8 +1000,7 @@ class X3Planes:
             tab[i].rows, tab[i].cols, tab[i].ld = W.shape[0], W.shape[1], W.stride(0)
             tab[i].transpose, tab[i].kp, tab[i].tile0, tab[i].ps = int(e["transpose"]), e["kp"], tile0, e["N"] * e["kp"]
             tile0 += ((e["N"] + 31) // 32) * ((e["K"] + 63) // 64)        # pieces of 32 (n) x 64 (k) output elements
-        host = torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8)
-        return host.to(ents[0]["src"].device), tile0
+        return upload_table(tab, ents[0]["src"].device), tile0
 
     def _split(self, ents):
         tab, tiles = self._table_of(ents)
@@ -1052,9 +1050,9 @@ def x3_refresh():
 
 def _gemm_route(A1, B1, nn1=False, A2=None, B2=None, nn2=False, bias=None, resid=None, cloud_bias=None, rows_per_cloud=0, out=None,
                 alpha=1.0, xyz3=None, relu=False, bn=0):
-    """the kernel family (``_lib.ROUTE_*``) a product of the ``gemm_rows`` contract goes to: the library's answer
+    """the kernel family (``_lib.GEMM_ROUTE_*``) a product of the ``gemm_rows`` contract goes to: the library's answer
     (``hsp_gemm_route``, include/hsp.h) to the call described as an ``HspGemmCall``.  out None: a dense result the wrapper allocates;
-    bn: the BatchNorm-partials form asked for (``_lib.BN_*``)"""
+    bn: the BatchNorm-partials form asked for (``_lib.GEMM_BN_*``)"""
     N = B1.shape[1] if nn1 else B1.shape[0]
     two = A2 is not None
     call = HspGemmCall(A1.data_ptr(), B1.data_ptr(), A2.data_ptr() if two else None, B2.data_ptr() if two else None,
@@ -2860,7 +2858,6 @@ def batch_select(status, keep, segs=(), sel=None, info=None):
     -> (dsts, sel (keep,) int32, info (2,) int32 = [good items, min(good items, keep)]).  sel[j] is the j-th good item, the
     good ones repeating in order when fewer than keep are; the identity when none is.  A row is a positive multiple of 4
     bytes.  Nothing is uploaded and nothing copied back: the call can be captured."""
-    from ._lib import BATCH_SELECT_MAX_ITEMS, BATCH_SELECT_MAX_SEGS, HspSelectSeg
     status = _req(status, torch.int32, "batch_select.status")
     keep, segs = int(keep), list(segs)
     if status.dim() != 1 or not 1 <= keep <= status.shape[0] <= BATCH_SELECT_MAX_ITEMS or len(segs) > BATCH_SELECT_MAX_SEGS:

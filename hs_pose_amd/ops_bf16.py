@@ -13,12 +13,11 @@ heads, which are different nodes in the two dtypes.
 """
 import weakref
 
-import numpy as np
 import torch
 
 from . import ops
-from ._lib import HspError, lib
-from .ops import _copies, _p, _req, _run, _stream, _ws, copies_of
+from ._lib import HspCastDesc, HspCastPitchedDesc, HspError, lib
+from .ops import _copies, _p, _req, _run, _stream, _ws, copies_of, upload_table
 
 BF16 = torch.bfloat16
 
@@ -36,9 +35,7 @@ class Bf16Params:
             del _copies[key]                  # entries whose Bf16Params is gone
         self.entries = []
         self.pitched = any(len(sp) > 3 and sp[3] for sp in specs)
-        fields = [("src", np.uint64), ("dst", np.uint64), ("dstT", np.uint64), ("rows", np.int32), ("cols", np.int32),
-                  ("ld", np.int32), ("tile0", np.int32)]
-        tab = np.zeros(len(specs), dtype=np.dtype(fields + ([("ldd", np.int32), ("lddT", np.int32)] if self.pitched else [])))
+        tab = ((HspCastPitchedDesc if self.pitched else HspCastDesc) * len(specs))()
         tiles = 0
         for i, sp in enumerate(specs):
             w2, want, want_t = sp[:3]
@@ -52,11 +49,11 @@ class Bf16Params:
             _copies[w2.data_ptr()] = (c, ct, weakref.ref(self))
             row = (w2.data_ptr(), c.data_ptr() if c is not None else 0, ct.data_ptr() if ct is not None else 0, rows, cols,
                    w2.stride(0), tiles)
-            tab[i] = row + ((ldd, rows) if self.pitched else ())
+            tab[i] = row + ((ldd, rows) if self.pitched else ())          # src, dst, dstT, rows, cols, ld, tile0[, ldd, lddT]
             tiles += ((rows + 31) // 32) * ((cols + 31) // 32)
         self.total_tiles = tiles
         self.n = len(specs)
-        self.table = torch.from_numpy(tab.view(np.uint8)).to(dev)
+        self.table = upload_table(tab, dev)
         self.ptrs = [w2.data_ptr() for w2, _, _ in self.entries]
 
     def refresh(self):

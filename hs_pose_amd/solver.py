@@ -16,12 +16,11 @@ entries (views), so checkpoints written by either implementation load into the o
 import ctypes
 import math
 
-import numpy as np
 import torch
 from torch.optim.optimizer import Optimizer
 
 from . import ops
-from ._lib import HspError, lib
+from ._lib import HspError, HspRowDesc, lib
 from .config import FLAGS
 
 _ROW_CHUNK = 4096          # 1-D tensors are cut into rows of at most this many elements
@@ -66,13 +65,12 @@ class _FlatGroup:
         # (ranger2020.py:168-170): weights loaded between construction and the first step must be what Lookahead
         # interpolates towards, not the random init that was live when the optimizer was built
         self.slow_ready = False
-        tab = np.zeros(len(rows), dtype=np.dtype([("offset", np.int64), ("len", np.int32), ("gc", np.int32)]))
-        for i, (o, l, gc) in enumerate(rows):
-            tab[i] = (o, l, gc)
-        self.gc_rows = tab["gc"].copy()
-        self.rows_host = tab
-        self.rows = torch.from_numpy(tab.view(np.uint8)).to(dev)
+        self.rows_host = rows                                  # (offset, len, gc) in HspRowDesc's field order
+        self.rows = self._upload(rows)
         self.nrows = len(rows)
+
+    def _upload(self, rows):
+        return ops.upload_table((HspRowDesc * len(rows))(*rows), self.flat_p.device)
 
     @staticmethod
     def view(flat, p, off):
@@ -85,17 +83,15 @@ class _FlatGroup:
         key = (use_gc, gc_conv_only)
         cache = self.__dict__.setdefault("_rows_cache", {})
         if key not in cache:
-            tab = self.rows_host.copy()
-            if not use_gc:
-                tab["gc"] = 0
-            else:
+            gc = [use_gc and g for _, _, g in self.rows_host]
+            if use_gc:
                 i = 0
                 for p in self.params:
                     nr = p.shape[0] if p.dim() > 1 else (p.numel() + _ROW_CHUNK - 1) // _ROW_CHUNK
                     if p.dim() <= 3:
-                        tab["gc"][i:i + nr] = 0
+                        gc[i:i + nr] = [0] * nr
                     i += nr
-            cache[key] = torch.from_numpy(tab.view(np.uint8)).to(self.rows.device)
+            cache[key] = self._upload([(o, n, int(g)) for (o, n, _), g in zip(self.rows_host, gc)])
         return cache[key]
 
 

@@ -4,8 +4,10 @@ code); tests/test_gpu_gemm_reference.py asserts them again and runs the kernels.
 import ctypes
 from collections import namedtuple
 
-KB1, KB4, BF16, X3 = 0, 1, 2, 3          # include/hsp.h: HSP_WGRAD_FORM_*
-FOLD_MAX_WGRAD = 24                       # include/hsp.h: HSP_FOLD_MAX_WGRAD
+from hs_pose_amd import _lib
+
+KB1, KB4, BF16, X3 = _lib.WGRAD_FORM_F32_KB1, _lib.WGRAD_FORM_F32_KB4, _lib.WGRAD_FORM_BF16, _lib.WGRAD_FORM_X3
+FOLD_MAX_WGRAD = _lib.FOLD_MAX_WGRAD
 
 
 def _c4(m):
@@ -141,8 +143,8 @@ def check_pair_plan(L, p):
 
 
 # ---- hsp_gemm_route: product calls and the kernel family each goes to ----------------------------------------------------------
-NONE, SMALL, X3R, X3_BN, WAVE, TILE = range(6)     # include/hsp.h: HSP_GEMM_ROUTE_*
-BN_OUT, BN_LIN = 1, 2                               # include/hsp.h: HSP_GEMM_BN_*
+NONE, SMALL, X3R, X3_BN, WAVE, TILE = (getattr(_lib, "GEMM_ROUTE_" + r) for r in ("NONE", "SMALL_ROWS", "X3", "X3_BN", "WAVE", "TILE"))
+BN_OUT, BN_LIN = _lib.GEMM_BN_OUT, _lib.GEMM_BN_LINEAR
 
 # lay: the weight layouts, "nt" (N,K) | "nn" (K,N), one per source ("nn+nt": two sources); epi: b bias, r residual, c per-cloud
 # bias, x the xyz3 rider; off: None, "C0" (no result yet: the caller allocates it dense) or (operand, "ptr" | "ld"): that operand's

@@ -28,6 +28,17 @@ def test_library_exports_every_declared_symbol():
     assert L.hsp_error_string(-3) == b"workspace missing or too small"
 
 
+def test_header_declares_every_exported_symbol():
+    """the other direction: no hsp_* entry point that libhsp.so exports is missing from include/hsp.h"""
+    import shutil
+    import subprocess
+    from hs_pose_amd import _lib
+    nm = shutil.which("nm") or shutil.which("llvm-nm") or "/opt/rocm/llvm/bin/llvm-nm"
+    out = subprocess.run([nm, "-D", "--defined-only", _lib.LIB_PATH], check=True, capture_output=True, text=True).stdout
+    exported = sorted({ln.split()[-1] for ln in out.splitlines() if ln.split() and re.fullmatch(r"hsp_[a-z0-9_]+", ln.split()[-1])})
+    assert exported == _header_symbols(), "libhsp.so's exports and include/hsp.h disagree"
+
+
 def test_argument_validation_without_gpu():
     from hs_pose_amd._lib import lib
     L = lib()

@@ -75,6 +75,7 @@ import pytest
 import torch
 
 import _gemm_cases as gc
+from hs_pose_amd._lib import HspDirsPending, HspWgradPending
 
 pytestmark = pytest.mark.gpu
 
@@ -363,16 +364,6 @@ def test_wgrad_nonfinite_is_confined(dev, c, edge):
 
 # ==== the pair launch =============================================================================================================
 
-class Pending(ctypes.Structure):
-    _fields_ = [("part", ctypes.c_void_p), ("cs_part", ctypes.c_void_p), ("C", ctypes.c_void_p), ("colsum", ctypes.c_void_p),
-                ("nparts", ctypes.c_int), ("M", ctypes.c_int), ("N", ctypes.c_int), ("ldc", ctypes.c_int)]
-
-
-class DirsPending(ctypes.Structure):
-    _fields_ = [("part", ctypes.c_void_p), ("dirs", ctypes.c_void_p), ("grad_dirs", ctypes.c_void_p), ("nparts", ctypes.c_int),
-                ("SC", ctypes.c_int)]
-
-
 def _rider_shape():
     """the smallest (B, N, C) the per-cloud column sum admits, by its own query"""
     L = _L()
@@ -398,7 +389,7 @@ def test_wgrad_pair(dev, p, rider):
         ws = Ws(L.hsp_wgrad_workspace_bytes(M, N, K), dev)
         prob.append((av, bv, out, ws, want, T))
         args += [_vp(av), M + 2, _vp(bv), N + 2, M, N, K, _vp(out.v), N + 1, _vp(ws.buf), ws.nbytes]
-    pend = (Pending * 2)()
+    pend = (HspWgradPending * 2)()
     if rider:
         B, Np, C = _rider_shape()
         x = _ranged(B * Np, C, torch.Generator().manual_seed(5)).view(B, Np, C)
@@ -454,7 +445,7 @@ def _fold_problem(nparts, M, N, colsum, seed, dev):
     csp = _ranged(nparts, N, g)
     buf = torch.cat([part.flatten(), csp.flatten()]).to(dev)               # the workspace layout: partials, then their column sums
     out, cs = Out(M, N, N + 1, dev), (Out(1, N, N, dev) if colsum else None)
-    pd = Pending(buf.data_ptr(), buf.data_ptr() + 4 * nparts * M * N, out.v.data_ptr(), cs.v.data_ptr() if cs else 0, nparts, M, N, N + 1)
+    pd = HspWgradPending(buf.data_ptr(), buf.data_ptr() + 4 * nparts * M * N, out.v.data_ptr(), cs.v.data_ptr() if cs else 0, nparts, M, N, N + 1)
     return pd, buf, out, cs, _fold32(part), _fold32(csp)
 
 
@@ -476,7 +467,7 @@ def test_wgrad_fold_on_hand_made_partials(dev, N, colsum):
         for i in range(0, len(probs) - n + 1, n):
             for q in probs[i:i + n]:
                 q[2].v.fill_(NAN)
-            arr = (Pending * n)(*[q[0] for q in probs[i:i + n]])
+            arr = (HspWgradPending * n)(*[q[0] for q in probs[i:i + n]])
             assert L.hsp_wgrad_fold(arr, n, _stream()) == 0
             done += probs[i:i + n]
         torch.cuda.synchronize()
@@ -487,7 +478,7 @@ def test_wgrad_fold_of_the_most_problems_in_one_launch(dev):
     L = _L()
     n = gc.FOLD_MAX_WGRAD
     probs = [_fold_problem(NPARTS[i % len(NPARTS)], 3, (4, 68)[i % 2], i % 3 != 0, 300 + i, dev) for i in range(n)]
-    arr = (Pending * n)(*[q[0] for q in probs])
+    arr = (HspWgradPending * n)(*[q[0] for q in probs])
     assert L.hsp_wgrad_fold(arr, n + 1, _stream()) == -1
     assert L.hsp_wgrad_fold(arr, n, _stream()) == 0
     torch.cuda.synchronize()
@@ -512,9 +503,9 @@ def test_step_fold_with_both_kinds_of_entry(dev):
         g = torch.Generator().manual_seed(600 + s)
         part, dirs = _ranged(s * 3, SC, g).view(s, 3, SC), torch.randn(3, SC, generator=g)
         pb, db, out = part.to(dev), dirs.to(dev), Out(3, SC, SC, dev)
-        dprobs.append((DirsPending(pb.data_ptr(), db.data_ptr(), out.v.data_ptr(), s, SC), pb, db, out) + _dirs_fold64(part, dirs))
-    warr = (Pending * len(probs))(*[q[0] for q in probs])
-    darr = (DirsPending * len(dprobs))(*[q[0] for q in dprobs])
+        dprobs.append((HspDirsPending(pb.data_ptr(), db.data_ptr(), out.v.data_ptr(), s, SC), pb, db, out) + _dirs_fold64(part, dirs))
+    warr = (HspWgradPending * len(probs))(*[q[0] for q in probs])
+    darr = (HspDirsPending * len(dprobs))(*[q[0] for q in dprobs])
     assert L.hsp_step_fold(warr, len(probs), darr, len(dprobs), _stream()) == 0
     torch.cuda.synchronize()
     _check_folded(probs, "hsp_step_fold")
