@@ -47,6 +47,8 @@ class PoseNet9D(nn.Module):
         self.rot_red = Rot_red()
         self.face_recon = FaceRecon()
         self.ts = Pose_Ts()
+        for site, head in enumerate((self.rot_green, self.rot_red, self.ts)):     # keyed Dropout streams (include/hsp.h)
+            head.drop_site = site
 
     @property
     def feature_dtype(self):

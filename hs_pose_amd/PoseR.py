@@ -25,9 +25,20 @@ class _PointMLPHead(nn.Module):
         self.conv3 = torch.nn.Conv1d(256, 256, 1)
         self.conv4 = torch.nn.Conv1d(256, self.k, 1)
         self.drop1 = nn.Dropout(0.2)
+        self.drop_site = 0       # the head's stream of keyed Dropout draws (include/hsp.h; PoseNet9D numbers its three heads)
         self.bn1 = nn.BatchNorm1d(1024)
         self.bn2 = nn.BatchNorm1d(256)
         self.bn3 = nn.BatchNorm1d(256)
+
+    def _drop(self, h):
+        """Dropout on the fp32 (B,256) row: torch's, or -- training with FLAGS.reproducible inside a device draw scope -- the keyed
+        one, whose mask is a function of the step's key and the head's site (no draw on torch's device generator)"""
+        if self.training and FLAGS.reproducible and self.drop1.p > 0:
+            from . import pc_sample
+            scope = pc_sample.active_draws()
+            if scope is not None:
+                return ops.dropout_keyed(h, scope.key, self.drop_site, self.drop1.p)
+        return self.drop1(h)
 
     def forward_rows(self, x: "(B, N, f)", first=None):
         """first: (conv1's output rows (B*N, 1024), BatchNorm first-pass buffer) when the caller computed it with the other
@@ -42,7 +53,7 @@ class _PointMLPHead(nn.Module):
             h = ops_bf16.dense_bn(h, self.conv2.weight.squeeze(-1), self.conv2.bias, self.bn2)
             h = ops.points_max(h.view(b, n, -1))                                 # (B,256) fp32
             h = ops.bn_relu(ops.linear_rows(h, self.conv3.weight.squeeze(-1), self.conv3.bias), self.bn3)
-            h = self.drop1(h)
+            h = self._drop(h)
             return ops.linear_rows(h, self.conv4.weight.squeeze(-1), self.conv4.bias).contiguous()
         if first is None:
             first = ops.linear_rows(x.reshape(b * n, c), self.conv1.weight.squeeze(-1), self.conv1.bias, bn_partials=True)
@@ -52,7 +63,7 @@ class _PointMLPHead(nn.Module):
         h = ops.bn_relu(y2, self.bn2, partial=p2)
         h = ops.points_max(h.view(b, n, -1))                                     # (B,256)
         h = ops.bn_relu(ops.linear_rows(h, self.conv3.weight.squeeze(-1), self.conv3.bias), self.bn3)
-        h = self.drop1(h)
+        h = self._drop(h)
         return ops.linear_rows(h, self.conv4.weight.squeeze(-1), self.conv4.bias).contiguous()
 
     def bf16_specs(self, k_feat=None):

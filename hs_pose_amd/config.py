@@ -46,6 +46,12 @@ class _Flags:
                                 # reference's draws on torch's and numpy's generators, uploaded before a replay -- or 'device' --
                                 # keyed draws inside the forward / the captured body (pc_sample.resolve_draws; include/hsp.h:
                                 # "keyed draws of a step"): the same distributions, not the same draws, no host generator touched
+        reproducible=False,     # (not in the reference) bit-reproducible training steps: both pooling backwards sum each source
+                                # row's gradients in ascending query order over a reverse index of the kept rows' lists (no float
+                                # atomics; ops._pool_bwd_raw), ops.gather_rows's backward takes its gather form, and under device
+                                # draws (step_draws) the heads' Dropout mask is a keyed draw (ops.dropout_keyed) instead of a draw
+                                # on torch's device generator.  Read when a call is issued: a captured graph keeps the form it
+                                # was captured with.  DESIGN.md section 8g
     )
 
     def __init__(self):

@@ -21,15 +21,18 @@ namespace hsp {
 
 // EDGES_IN_LDS: the edge array is assembled and sorted in LDS and written out once, coalesced (the per-row
 // insertion sort is a chain of dependent accesses: ~100 cycles a step in LDS, 1-2 us a step in global memory)
-template <bool EDGES_IN_LDS>
+// SEL: query i reads the list of idx row qs[i] (a Pool_layer's kept rows; a row named twice is two queries) of the cloud's Nidx
+// rows instead of row i of its Nq
+template <bool EDGES_IN_LDS, bool SEL = false>
 __device__ __forceinline__ void rev_build_body(const int b, const int32_t* __restrict__ idx, int Nq, int Nsrc,
                                                int k, int kstride, int32_t* __restrict__ rev_off,
-                                               int32_t* __restrict__ rev_edge, int* __restrict__ wsum) {
+                                               int32_t* __restrict__ rev_edge, int* __restrict__ wsum,
+                                               const int32_t* __restrict__ qs = nullptr, int Nidx = 0) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     int* cnt = reinterpret_cast<int*>(smem);            // Nsrc + 1 (histogram, then cursor)
     int* led = cnt + Nsrc + 1;                          // E edges (EDGES_IN_LDS)
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int32_t* ib = idx + (size_t)b * Nq * kstride;
+    const int32_t* ib = idx + (size_t)b * (SEL ? Nidx : Nq) * kstride;
     int32_t* off = rev_off + (size_t)b * (Nsrc + 1);
     int32_t* edge = rev_edge + (size_t)b * Nq * k;
     int* ed = EDGES_IN_LDS ? led : edge;
@@ -39,7 +42,7 @@ __device__ __forceinline__ void rev_build_body(const int b, const int32_t* __res
     __syncthreads();
     for (int e = tid; e < E; e += REV_THREADS) {
         const int i = e / k, n = e - i * k;
-        atomicAdd(&cnt[ib[(size_t)i * kstride + n]], 1);
+        atomicAdd(&cnt[ib[(size_t)(SEL ? qs[i] : i) * kstride + n]], 1);
     }
     __syncthreads();
     // exclusive scan of cnt[0..Nsrc): thread t owns a contiguous slice; wave scan by shuffles, 16 wave totals by wave 0
@@ -79,7 +82,7 @@ __device__ __forceinline__ void rev_build_body(const int b, const int32_t* __res
         const int e = e0 + tid;
         if (e < E) {
             const int i = e / k, n = e - i * k;
-            const int pos = atomicAdd(&cnt[ib[(size_t)i * kstride + n]], 1);
+            const int pos = atomicAdd(&cnt[ib[(size_t)(SEL ? qs[i] : i) * kstride + n]], 1);
             ed[pos] = e;
         }
         __syncthreads();
@@ -94,7 +97,7 @@ __device__ __forceinline__ void rev_build_body(const int b, const int32_t* __res
         for (int p = tid; p < E; p += REV_THREADS) {
             const int e = led[p];
             const int i = e / k, n = e - i * k;
-            const int m = ib[(size_t)i * kstride + n];
+            const int m = ib[(size_t)(SEL ? qs[i] : i) * kstride + n];
             const int a = m ? cnt[m - 1] : 0, z = cnt[m];
             int c = 0;
             for (int q = a; q < z; ++q) c += led[q] < e ? 1 : 0;
@@ -123,6 +126,16 @@ __global__ __launch_bounds__(REV_THREADS) void rev_build_kernel(const int32_t* _
                                                                 int32_t* __restrict__ rev_edge) {
     __shared__ int wsum[REV_THREADS / 64];
     rev_build_body<EDGES_IN_LDS>((int)blockIdx.x, idx, Nq, Nsrc, k, kstride, rev_off, rev_edge, wsum);
+}
+
+// the map of the kept rows' lists (hsp_rev_build_sel): qsel + b * qstride is cloud b's list (qstride 0: one list for the batch)
+template <bool EDGES_IN_LDS>
+__global__ __launch_bounds__(REV_THREADS) void rev_build_sel_kernel(const int32_t* __restrict__ idx, const int32_t* __restrict__ qsel,
+                                                                    int qstride, int Nidx, int Nq, int Nsrc, int k, int kstride,
+                                                                    int32_t* __restrict__ rev_off, int32_t* __restrict__ rev_edge) {
+    __shared__ int wsum[REV_THREADS / 64];
+    rev_build_body<EDGES_IN_LDS, true>((int)blockIdx.x, idx, Nq, Nsrc, k, kstride, rev_off, rev_edge, wsum,
+                                       qsel + (size_t)blockIdx.x * qstride, Nidx);
 }
 
 // up to 4 maps over the same B clouds in ONE launch: workgroup (b, map) runs rev_build_body on its own map (independent
@@ -155,6 +168,29 @@ extern "C" int hsp_rev_build(const int32_t* idx, int B, int Nq, int Nsrc, int k,
     }
     hipLaunchKernelGGL(kern, dim3(B), dim3(REV_THREADS), lds, as_stream(stream), idx, Nq, Nsrc, k, kstride, rev_off,
                        rev_edge);
+    return check_launch();
+}
+
+extern "C" int hsp_rev_build_sel(const int32_t* idx, const int32_t* qsel, int qsel_stride, int B, int Nidx, int Nq, int Nsrc, int k,
+                                 int kstride, int32_t* rev_off, int32_t* rev_edge, hspStream_t stream) {
+    if (!idx || !rev_off || !rev_edge || B <= 0 || Nidx <= 0 || Nq <= 0 || Nsrc <= 0 || k <= 0 || kstride < k) return HSP_ERR_BAD_ARG;
+    if (!qsel) {
+        if (Nq != Nidx || qsel_stride != 0) return HSP_ERR_BAD_ARG;
+        return hsp_rev_build(idx, B, Nq, Nsrc, k, kstride, rev_off, rev_edge, stream);
+    }
+    if (qsel_stride != 0 && qsel_stride < Nq) return HSP_ERR_BAD_ARG;
+    const size_t lds0 = (size_t)(Nsrc + 1) * sizeof(int);
+    if (lds0 > 140 * 1024) return HSP_ERR_UNSUPPORTED;
+    const size_t lds1 = lds0 + (size_t)Nq * k * sizeof(int);
+    const bool in_lds = lds1 <= 140 * 1024;
+    const size_t lds = in_lds ? lds1 : lds0;
+    auto kern = in_lds ? rev_build_sel_kernel<true> : rev_build_sel_kernel<false>;
+    if (lds > 60 * 1024) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) { set_last_hip_error(e); return HSP_ERR_LAUNCH; }
+    }
+    hipLaunchKernelGGL(kern, dim3(B), dim3(REV_THREADS), lds, as_stream(stream), idx, qsel, qsel_stride, Nidx, Nq, Nsrc, k, kstride,
+                       rev_off, rev_edge);
     return check_launch();
 }
 

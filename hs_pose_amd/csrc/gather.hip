@@ -736,12 +736,21 @@ static int launch_scatter_tile(int tc, const FT* gout, const float* gbc, int gst
 // gather form of the same backward over the reverse-edge index (csr.hip): one thread per
 // (source row m, float4 column group) walks the edges e = i*k + n pointing at m and adds
 // grad_out[b,i,c] (or the per-cloud broadcast row) where argmax[b,i,c] == n.  No atomics.
-__global__ __launch_bounds__(256) void gather_max_bwd_csr_kernel(const float* __restrict__ gout, int gbcast,
+// The ORDERED pooling backward (config.FLAGS.reproducible) over hsp_rev_build_sel's map of the kept rows' lists: the edges of a
+// row ascend, so its sum runs over the queries in ascending order, one fp32 add each from +0, and is stored once (bf16: one
+// rounding).  The C / 4 threads of a row read contiguous segments of the same query rows.  Written for the in-degree of the
+// pool graphs, k Nq / Nsrc ~ 1 on average (a handful at most): a thread walks its row's list serially and there is no hub
+// handling -- a row listed by most queries is summed correctly, by one thread per column group, at that row's length in
+// dependent loads.
+// FT: storage type of gout (per-query gradients) and gfeat; the broadcast row (B,C) is always fp32
+template <typename FT>
+__global__ __launch_bounds__(256) void gather_max_bwd_csr_kernel(const FT* __restrict__ gout, const float* __restrict__ gbc,
                                                                  const uint8_t* __restrict__ argmax,
                                                                  const int32_t* __restrict__ rev_off,
                                                                  const int32_t* __restrict__ rev_edge, int B,
                                                                  int Nsrc, int Nq, int k, int C,
-                                                                 float* __restrict__ gfeat) {
+                                                                 FT* __restrict__ gfeat) {
+    const bool gbcast = gbc != nullptr;
     const int cq = C >> 2;
     const long long total = (long long)B * Nsrc * cq;
     for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
@@ -761,7 +770,7 @@ __global__ __launch_bounds__(256) void gather_max_bwd_csr_kernel(const float* __
                 const uchar4 am = *reinterpret_cast<const uchar4*>(argmax + ((size_t)b * Nq + i) * C + (g << 2));
                 c0 += am.x == n; c1 += am.y == n; c2 += am.z == n; c3 += am.w == n;
             }
-            const float4 gv = *reinterpret_cast<const float4*>(gout + (size_t)b * C + (g << 2));
+            const float4 gv = *reinterpret_cast<const float4*>(gbc + (size_t)b * C + (g << 2));
             // (count * g): equals the serial sum of count copies of g up to one rounding
             acc = make_float4(gv.x * c0, gv.y * c1, gv.z * c2, gv.w * c3);
         } else {
@@ -770,14 +779,14 @@ __global__ __launch_bounds__(256) void gather_max_bwd_csr_kernel(const float* __
                 const int i = ed / k, n = ed - i * k;
                 const size_t qrow = (size_t)b * Nq + i;
                 const uchar4 am = *reinterpret_cast<const uchar4*>(argmax + qrow * C + (g << 2));
-                const float4 gv = *reinterpret_cast<const float4*>(gout + qrow * C + (g << 2));
+                const float4 gv = Feat<FT>::ld4(gout + qrow * C + (g << 2));
                 if (am.x == n) acc.x += gv.x;
                 if (am.y == n) acc.y += gv.y;
                 if (am.z == n) acc.z += gv.z;
                 if (am.w == n) acc.w += gv.w;
             }
         }
-        *reinterpret_cast<float4*>(gfeat + row * C + (g << 2)) = acc;
+        Feat<FT>::st4(gfeat + row * C + (g << 2), acc);
     }
 }
 
@@ -1274,16 +1283,30 @@ extern "C" int hsp_gather_rows_bwd_csr_bf16(const hsp_bf16_t* grad_out, int grad
     return gather_rows_bwd_csr_impl<bf16_t>(grad_out, grad_stride, rev_off, rev_edge, B, Nsrc, Nq, C, grad_feat, stream);
 }
 
-extern "C" int hsp_gather_max_bwd_csr(const float* grad_out, int grad_bcast, const uint8_t* argmax,
-                                      const int32_t* rev_off, const int32_t* rev_edge, int B, int Nsrc, int Nq, int k,
-                                      int C, float* grad_feat, hspStream_t stream) {
+template <typename FT>
+static int gather_max_bwd_csr_impl(const void* grad_out, int grad_bcast, const uint8_t* argmax, const int32_t* rev_off,
+                                   const int32_t* rev_edge, int B, int Nsrc, int Nq, int k, int C, FT* grad_feat, hspStream_t stream) {
     if (!grad_out || !argmax || !rev_off || !rev_edge || !grad_feat || B <= 0 || Nsrc <= 0 || Nq <= 0 || k <= 0 || C <= 0)
         return HSP_ERR_BAD_ARG;
     if (C & 3) return HSP_ERR_UNSUPPORTED;
     const long long total = (long long)B * Nsrc * (C >> 2);
-    hipLaunchKernelGGL(gather_max_bwd_csr_kernel, dim3(stream_grid(total)), dim3(256), 0, as_stream(stream), grad_out,
-                       grad_bcast, argmax, rev_off, rev_edge, B, Nsrc, Nq, k, C, grad_feat);
+    // the per-query gradient has the feature type; the broadcast row is always fp32
+    hipLaunchKernelGGL(gather_max_bwd_csr_kernel<FT>, dim3(stream_grid(total)), dim3(256), 0, as_stream(stream),
+                       grad_bcast ? nullptr : reinterpret_cast<const FT*>(grad_out),
+                       grad_bcast ? reinterpret_cast<const float*>(grad_out) : nullptr, argmax, rev_off, rev_edge, B, Nsrc, Nq, k, C,
+                       grad_feat);
     return check_launch();
+}
+extern "C" int hsp_gather_max_bwd_csr(const float* grad_out, int grad_bcast, const uint8_t* argmax,
+                                      const int32_t* rev_off, const int32_t* rev_edge, int B, int Nsrc, int Nq, int k,
+                                      int C, float* grad_feat, hspStream_t stream) {
+    return gather_max_bwd_csr_impl<float>(grad_out, grad_bcast, argmax, rev_off, rev_edge, B, Nsrc, Nq, k, C, grad_feat, stream);
+}
+extern "C" int hsp_gather_max_bwd_csr_bf16(const void* grad_out, int grad_bcast, const uint8_t* argmax,
+                                           const int32_t* rev_off, const int32_t* rev_edge, int B, int Nsrc, int Nq, int k,
+                                           int C, hsp_bf16_t* grad_feat, hspStream_t stream) {
+    return gather_max_bwd_csr_impl<bf16_t>(grad_out, grad_bcast, argmax, rev_off, rev_edge, B, Nsrc, Nq, k, C,
+                                           reinterpret_cast<bf16_t*>(grad_feat), stream);
 }
 
 extern "C" int hsp_points_max_fwd(const float* x, int B, int N, int C, float* out, int32_t* argrow, hspStream_t stream) {

@@ -935,6 +935,52 @@ extern "C" int hsp_pose_augment_keyed(const float* PC, const float* gt_R, const 
     return check_launch();
 }
 
+// ---- keyed Dropout (include/hsp.h: "keyed draws of a step") ---------------------------------------------------------------------
+// The heads' Dropout with its mask drawn from the step's key instead of torch's device generator: element i = r C + c of site s
+// keeps iff the fp32 uniform of word(i) under the instance key of j = 0x83000000 | s and the tag 0xfffffffa is >= p.  One thread
+// per element ((B, 256) rows: one workgroup per cloud or so); the backward reads the saved mask, never the key.
+namespace hsp {
+__global__ __launch_bounds__(256) void dropout_keyed_fwd_kernel(const float* __restrict__ x, const unsigned long long* __restrict__ key,
+                                                                uint32_t j, float p, float scale, uint32_t total,
+                                                                float* __restrict__ out, uint8_t* __restrict__ keep) {
+    const uint32_t kt = absorb(instance_key(key, (int)j), 0xfffffffau);
+    for (unsigned long long e = (unsigned long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (unsigned long long)gridDim.x * 256) {
+        const bool kp = word_to_f32(absorb(kt, (uint32_t)e)) >= p;
+        out[e] = kp ? x[e] * scale : 0.f;
+        keep[e] = kp ? 1 : 0;
+    }
+}
+__global__ __launch_bounds__(256) void dropout_bwd_kernel(const float* __restrict__ g, const uint8_t* __restrict__ keep, float scale,
+                                                          uint32_t total, float* __restrict__ gx) {
+    for (unsigned long long e = (unsigned long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (unsigned long long)gridDim.x * 256)
+        gx[e] = g[e] * (float)keep[e] * scale;
+}
+}  // namespace hsp
+
+static bool dropout_args_ok(float p, int R, int C) { return p >= 0.f && p < 1.f && R > 0 && C > 0 && (long long)R * C < 0x100000000LL; }
+static unsigned dropout_grid(long long total) {
+    long long g = (total + 255) / 256;
+    return (unsigned)(g > HSP_NUM_CU * 8 ? HSP_NUM_CU * 8 : g);
+}
+
+extern "C" int hsp_dropout_keyed_fwd(const float* x, const unsigned long long* key, int site, float p, int R, int C, float* out,
+                                     uint8_t* keep, hspStream_t stream) {
+    if (!x || !key || !out || !keep || site < 0 || site >= 0x1000000 || !dropout_args_ok(p, R, C)) return HSP_ERR_BAD_ARG;
+    const long long total = (long long)R * C;
+    const float scale = 1.0f / (1.0f - p);                   // once, in fp32: the operand of every product
+    hipLaunchKernelGGL(hsp::dropout_keyed_fwd_kernel, dim3(dropout_grid(total)), dim3(256), 0, as_stream(stream), x, key,
+                       0x83000000u | (uint32_t)site, p, scale, (uint32_t)total, out, keep);
+    return check_launch();
+}
+extern "C" int hsp_dropout_bwd(const float* grad_out, const uint8_t* keep, float p, int R, int C, float* grad_x, hspStream_t stream) {
+    if (!grad_out || !keep || !grad_x || !dropout_args_ok(p, R, C)) return HSP_ERR_BAD_ARG;
+    const long long total = (long long)R * C;
+    const float scale = 1.0f / (1.0f - p);
+    hipLaunchKernelGGL(hsp::dropout_bwd_kernel, dim3(dropout_grid(total)), dim3(256), 0, as_stream(stream), grad_out, keep, scale,
+                       (uint32_t)total, grad_x);
+    return check_launch();
+}
+
 // ---- the face head's output split (PoseNet9D.py:31-35) ------------------------------------------------------------------------
 //   face (R, 30) -> normals (R, 6, 3) = face[:, :18] / ||.||_3 per face,  dis (R, 6) = face[:, 18:24],  conf (R, 6) = sigmoid(face[:, 24:])
 // One thread per (row, face): the reference's three slices, a norm, a division and a sigmoid are ~8 element-wise launches forward

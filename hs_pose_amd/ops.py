@@ -15,11 +15,14 @@ from ._lib import (BATCH_SELECT_MAX_ITEMS, BATCH_SELECT_MAX_SEGS, ERR_UNSUPPORTE
 from ._lib import (GEMM_BN_LINEAR as BN_LINEAR, GEMM_BN_OUT as BN_OUT, GEMM_ROUTE_SMALL_ROWS as ROUTE_SMALL_ROWS, GEMM_ROUTE_TILE as ROUTE_TILE,
                    GEMM_ROUTE_WAVE as ROUTE_WAVE, GEMM_ROUTE_X3 as ROUTE_X3, GEMM_ROUTE_X3_BN as ROUTE_X3_BN)
 
+from .config import FLAGS
+
 _vp = ctypes.c_void_p
 
-# HSP_DETERMINISTIC=1 (or ops.DETERMINISTIC = True): graph-conv backward runs in gather form over a
-# reverse-edge index (fixed summation order, bit-reproducible gradients) instead of the faster
-# column-tile LDS scatter, whose fp32 LDS adds are order-dependent in the last bits.
+# HSP_DETERMINISTIC=1 (or ops.DETERMINISTIC = True): the receptive-field and ORL backwards run in gather form over a
+# reverse-edge index (fp32 sums in ascending edge order).  The default receptive-field scatter accumulates in 32-bit fixed
+# point and the default ORL backward in integer counts, so both are fixed-order as well; the switch selects the gather forms'
+# arithmetic, not reproducibility.  It does not touch the pooling backward: that is config.FLAGS.reproducible (_pool_bwd_raw).
 DETERMINISTIC = os.environ.get("HSP_DETERMINISTIC", "0") == "1"
 
 
@@ -286,6 +289,9 @@ def nn1(target, source):
     return idx
 
 
+_REV_BUILD_LDS = 140 * 1024        # bytes of LDS hsp_rev_build's per-cloud histogram (n_src + 1 ints) may take (csrc/csr.hip)
+
+
 def rev_index(idx, k, n_src):
     """reverse-edge (CSR) index (rev_off (B,n_src+1), rev_edge (B,Nq*k)) of the first k columns of the
     int32 neighbour index idx (B,Nq,kstride); memoised on the idx tensor, so a graph shared by several
@@ -306,6 +312,31 @@ def rev_index(idx, k, n_src):
     _run("hsp_rev_build", (_p(idx), B, Nq, n_src, k, kstride, _p(off), _p(edge), _stream()),
          key=f"B{B}Nq{Nq}k{k}", abytes=B * (8 * Nq * k + 4 * n_src))
     cache[(k, n_src)] = (off, edge)
+    return off, edge
+
+
+def rev_index_sel(idx, qsel, qstride, k, n_src):
+    """``rev_index`` over the lists of a Pool_layer's kept rows (``hsp_rev_build_sel``): query q of ``qsel`` -- (Nq,) shared, qstride
+    0, or (B,Nq), qstride Nq -- reads idx row qsel[q]; edge ids q*k + n.  qsel None is ``rev_index``.  Memoised on the idx tensor per
+    (qsel, k, n_src): built once per step and Pool_layer.  The memo matches the qsel OBJECT, as ``rev_index`` trusts the idx object:
+    rewriting a kept-row buffer (or idx) in place and calling again with the same tensors returns the map of the old contents --
+    the layers make a new idx every forward, and a captured step runs the build itself on every replay."""
+    if qsel is None:
+        return rev_index(idx, k, n_src)
+    cache = getattr(idx, "_hsp_rev_sel", None)
+    if cache is None:
+        cache = []
+        idx._hsp_rev_sel = cache
+    for q, kk, ns, hit in cache:
+        if q is qsel and kk == k and ns == n_src:
+            return hit
+    B, Nidx, kstride = idx.shape
+    Nq = qsel.shape[-1]
+    off = torch.empty(B, n_src + 1, dtype=torch.int32, device=idx.device)
+    edge = torch.empty(B, Nq * k, dtype=torch.int32, device=idx.device)
+    _run("hsp_rev_build_sel", (_p(idx), _p(qsel), qstride, B, Nidx, Nq, n_src, k, kstride, _p(off), _p(edge), _stream()),
+         key=f"B{B}Nq{Nq}k{k}" + ("pc" if qstride else ""), abytes=B * (8 * Nq * k + 4 * n_src) + 4 * Nq * (B if qstride else 1))
+    cache.append((qsel, k, n_src, (off, edge)))
     return off, edge
 
 
@@ -453,6 +484,7 @@ class _GatherMax(torch.autograd.Function):
                                                      _p(arg), _stream()), key=key, abytes=ab)
         ctx.save_for_backward(idx, qsel, arg)
         ctx.dims = (B, Nsrc, Nidx, Nq, kstride, C, qstride)
+        ctx.k = k
         return out
 
     @staticmethod
@@ -461,13 +493,20 @@ class _GatherMax(torch.autograd.Function):
         B, Nsrc, Nidx, Nq, kstride, C, qstride = ctx.dims
         g = _reqf(g, "gather_max.grad")
         gfeat = torch.empty(B, Nsrc, C, dtype=g.dtype, device=g.device)
-        _pool_bwd_raw(g, idx, qsel, qstride, arg, B, Nsrc, Nidx, Nq, kstride, C, gfeat)
+        _pool_bwd_raw(g, idx, qsel, qstride, arg, B, Nsrc, Nidx, Nq, kstride, C, gfeat, ctx.k)
         return gfeat, None, None, None
 
 
-def _pool_bwd_raw(g, idx, qsel, qstride, arg, B, Nsrc, Nidx, Nq, kstride, C, gfeat):
-    """the pooling backward of gather_max / pool_layer: gfeat (B,Nsrc,C) overwritten; ``qstride`` as _qsel_dims returns it"""
+def _pool_bwd_raw(g, idx, qsel, qstride, arg, B, Nsrc, Nidx, Nq, kstride, C, gfeat, k):
+    """the pooling backward of gather_max / pool_layer: gfeat (B,Nsrc,C) overwritten; ``qstride`` as _qsel_dims returns it.  Default:
+    the column-tile LDS scatter (fp32 LDS adds in the order the waves arrive).  With FLAGS.reproducible: the ORDERED form -- the
+    gather over the reverse index of the kept rows' lists (``k`` columns of idx), every row's sum in ascending query order."""
     es = _es(g)
+    if FLAGS.reproducible:
+        off, edge = rev_index_sel(idx, qsel, qstride, k, Nsrc)
+        _run("hsp_gather_max_bwd_csr" + _sfx(g), (_p(g), 0, _p(arg), _p(off), _p(edge), B, Nsrc, Nq, k, C, _p(gfeat), _stream()),
+             key=f"B{B}Ns{Nsrc}Nq{Nq}k{k}C{C}", abytes=B * (es * Nsrc * C + 4 * (Nsrc + Nq * k) + Nq * (es + 1) * C))
+        return
     key, ab = f"B{B}Ns{Nsrc}Nq{Nq}C{C}", B * (es * Nsrc * C + Nq * (4 * kstride + (es + 1) * C))
     if qstride:
         _run("hsp_gather_max_bwd_sel" + _sfx(g), (_p(g), 0, _p(idx), _p(qsel), qstride, _p(arg), B, Nsrc, Nidx, Nq, kstride, C,
@@ -559,6 +598,7 @@ class _PoolLayer(torch.autograd.Function):
                                   _stream()), key=key, abytes=ab)
         ctx.save_for_backward(idx, qsel, arg)
         ctx.dims = (B, N, idx.shape[1], Nq, kstride, C, qstride)
+        ctx.k = k
         ctx.mark_non_differentiable(vsel)
         ctx.set_materialize_grads(False)          # (else autograd fills a zero gradient for vsel every step: two fill kernels)
         return out, vsel
@@ -569,7 +609,7 @@ class _PoolLayer(torch.autograd.Function):
         B, Nsrc, Nidx, Nq, kstride, C, qstride = ctx.dims
         g = _req(g, torch.float32, "pool.grad")
         gfeat = torch.empty(B, Nsrc, C, dtype=torch.float32, device=g.device)
-        _pool_bwd_raw(g, idx, qsel, qstride, arg, B, Nsrc, Nidx, Nq, kstride, C, gfeat)
+        _pool_bwd_raw(g, idx, qsel, qstride, arg, B, Nsrc, Nidx, Nq, kstride, C, gfeat, ctx.k)
         return gfeat, None, None, None, None
 
 
@@ -2318,9 +2358,49 @@ class _GatherRows(torch.autograd.Function):
             g = g.contiguous()
             gstride = C
         gfeat = torch.empty(B, Nsrc, C, dtype=torch.float32, device=g.device)
+        if FLAGS.reproducible and not shared and _AssembleFeat._csr_ok(g, C, gstride, 4) and 4 * (Nsrc + 1) <= _REV_BUILD_LDS:
+            # the gather form over the reverse map (ascending query order) wherever both entries take the operands -- a per-cloud
+            # map, the widths / strides / alignment of the concat backward's segments, a cloud whose histogram the reverse build
+            # holds --, decided before anything is launched; today's launch otherwise
+            off, edge = rev_index(idx, 1, Nsrc)
+            _run("hsp_gather_rows_bwd_csr", (_p(g), gstride, _p(off), _p(edge), B, Nsrc, Nq, C, _p(gfeat), _stream()),
+                 key=f"B{B}Ns{Nsrc}Nq{Nq}C{C}", abytes=B * (4 * Nsrc * C + Nq * (4 + 4 * C)))
+            return gfeat, None
         _run("hsp_gather_rows_bwd", (_p(g), gstride, _p(idx), shared, B, Nsrc, Nq, C, _p(gfeat), _stream()),
              key=f"B{B}Ns{Nsrc}Nq{Nq}C{C}", abytes=B * (4 * Nsrc * C + Nq * (4 + 4 * C)))
         return gfeat, None
+
+
+class _DropoutKeyed(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, h, key, site, p):
+        h = _req(h, torch.float32, "dropout_keyed.h")
+        key = _req(key, torch.int64, "dropout_keyed.key")
+        if h.dim() != 2 or key.numel() != 2:
+            raise HspError("dropout_keyed: expects fp32 rows (R,C) and the sampler's two-word key")
+        R, C = h.shape
+        out = torch.empty_like(h)
+        keep = torch.empty(R, C, dtype=torch.uint8, device=h.device)
+        _run("hsp_dropout_keyed_fwd", (_p(h), _p(key), int(site), float(p), R, C, _p(out), _p(keep), _stream()),
+             key=f"R{R}C{C}", abytes=9 * R * C + 16)
+        ctx.save_for_backward(keep)
+        ctx.p = float(p)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        (keep,) = ctx.saved_tensors
+        g = _req(g, torch.float32, "dropout_keyed.grad")
+        R, C = keep.shape
+        gx = torch.empty_like(g)
+        _run("hsp_dropout_bwd", (_p(g), _p(keep), ctx.p, R, C, _p(gx), _stream()), key=f"R{R}C{C}", abytes=9 * R * C)
+        return gx, None, None, None
+
+
+def dropout_keyed(h, key, site, p):
+    """training-mode Dropout(p) of the fp32 rows h (R,C) with the mask drawn under the device key (a ``DeviceSampler``'s two uint64)
+    and the stream of ``site`` (include/hsp.h: hsp_dropout_keyed_fwd); the backward multiplies by the saved mask."""
+    return _DropoutKeyed.apply(h, key, site, p)
 
 
 def gather_rows(feat, idx):

@@ -213,6 +213,17 @@ int hsp_rev_build(const int32_t *idx, int B, int Nq, int Nsrc, int k, int kstrid
 int hsp_rev_build_multi(int nmaps, const int32_t *const *idx, int B, const int *Nq, const int *Nsrc, const int *k,
                         const int *kstride, int32_t *const *rev_off, int32_t *const *rev_edge, hspStream_t stream);
 
+/* hsp_rev_build over the lists of a Pool_layer's KEPT rows: query q (of Nq) reads idx row r = qsel[b * qsel_stride + q] (of the
+ * cloud's Nidx), so for source row m the ascending edge ids e = q*k + n with idx[b, r, n] == m are
+ * rev_edge[b][rev_off[b][m] .. rev_off[b][m+1]); rev_off (B,Nsrc+1), rev_edge (B,Nq*k).  qsel_stride: 0 -- one list (Nq) shared by
+ * the batch -- or >= Nq -- a list per cloud, the rules of hsp_gather_max_fwd_sel; a list may name a row more than once, each
+ * listing is a query of its own.  qsel == NULL (then Nq == Nidx and qsel_stride == 0) is hsp_rev_build itself.  The entries of
+ * qsel and idx are device data and are not range-checked.  A NULL idx / rev_off / rev_edge, a size <= 0, kstride < k or a bad
+ * stride: HSP_ERR_BAD_ARG, nothing launched; (Nsrc + 1) * 4 bytes > 140 KiB of LDS (Nsrc > 35 839): HSP_ERR_UNSUPPORTED, as
+ * hsp_rev_build. */
+int hsp_rev_build_sel(const int32_t *idx, const int32_t *qsel, int qsel_stride, int B, int Nidx, int Nq, int Nsrc, int k,
+                      int kstride, int32_t *rev_off, int32_t *rev_edge, hspStream_t stream);
+
 /* ---- neighbourhood max-pool (ORL global branch, Pool_layer) ----------------------------------
  * replaces indexing_neighbor_new(...) + max(dim=2)    gcn3d.py:214-216, :236-240
  * feat (B,Nsrc,C); idx (B,Nidx,kstride) of which the first k columns are used; qsel (Nq) optional
@@ -264,6 +275,20 @@ int hsp_gather_max_bwd_sel(const float *grad_out, int grad_bcast, const int32_t 
 int hsp_gather_max_bwd_csr(const float *grad_out, int grad_bcast, const uint8_t *argmax, const int32_t *rev_off,
                            const int32_t *rev_edge, int B, int Nsrc, int Nq, int k, int C, float *grad_feat,
                            hspStream_t stream);
+/* The ORDERED pooling backward (config.FLAGS.reproducible): hsp_gather_max_bwd_csr and its storage-type twin over
+ * (rev_off, rev_edge) = hsp_rev_build_sel(idx, qsel, ...), k the k of that call, argmax / grad_out the (B,Nq,C) of the forward
+ * over the same kept rows.  For every cloud b, source row m and column c, in fp32:
+ *   s = +0;  for q = 0 .. Nq-1 ascending:  if idx[b, r_q, argmax[b,q,c]] == m:  s = fl32(s + float(grad_out[b,q,c]))
+ *   grad_feat[b,m,c] = s        (bf16 storage: rounded once, to nearest even)
+ * with r_q = qsel ? qsel[b * qsel_stride + q] : q.  No atomics; every grad_feat row is written exactly once (no memset, a row no
+ * query won is zeros); any Nsrc the reverse index takes, no LDS tile.  A row listed in several slots of one list counts once per
+ * query (the slot argmax names).  One thread per (source row, 4 columns) walks the row's edge list: written for the pool graphs'
+ * mean in-degree k Nq / Nsrc ~ 1, no hub handling (a long list is walked serially).  grad_bcast != 0: grad_out is the fp32 (B,C)
+ * row of hsp_gather_max_bwd and grad_feat = grad_out[b] * (number of winning queries), one rounding.  _bf16: grad_out (B,Nq,C) and
+ * grad_feat bf16, the broadcast row fp32.  C % 4 != 0: HSP_ERR_UNSUPPORTED; a NULL pointer or a size <= 0: HSP_ERR_BAD_ARG. */
+int hsp_gather_max_bwd_csr_bf16(const void *grad_out, int grad_bcast, const uint8_t *argmax, const int32_t *rev_off,
+                                const int32_t *rev_edge, int B, int Nsrc, int Nq, int k, int C, hsp_bf16_t *grad_feat,
+                                hspStream_t stream);
 
 /* ---- max over the points of a cloud (the heads' global feature) ------------------------------
  * replaces torch.max(x, 2, keepdim=True)[0]    PoseR.py:30 / :61, PoseTs.py:35, FaceRecon.py:98
@@ -1070,6 +1095,7 @@ int hsp_pose_augment(const float *PC, const float *gt_R, const float *gt_t, cons
  *   Pool rows of level l (0 or 1):     j = 0x80000000 | l
  *   augmentation of cloud b:           j = 0x81000000 | b        (b < 2^24)
  *   DZI window of item i:              j = 0x82000000 | i        (i < 65535)
+ *   Dropout of site s:                 j = 0x83000000 | s        (s < 2^24)
  * A stream of words under kj and a tag T is  word(i) = absorb(absorb(kj, T), i), i = 0, 1, ... (uint32).
  * A word w becomes an fp32 uniform as  float(w >> 8) * 2^-24  and a float64 uniform as  double(w) * 2^-32: both conversions are
  * exact and give values in [0, 1).
@@ -1111,6 +1137,19 @@ int hsp_pose_augment_keyed(const float *PC, const float *gt_R, const float *gt_t
  * outside [0, 1), shift_ratio < 0 or a value that is not finite: HSP_ERR_BAD_ARG. */
 int hsp_dzi_windows(const int32_t *bboxes, const unsigned long long *key, int M, int H, int W, int out_size, double pad_scale,
                     double scale_ratio, double shift_ratio, double *xf, hspStream_t stream);
+
+/* Keyed Dropout (config.FLAGS.reproducible under device draws): the heads' nn.Dropout (PoseR.py:27, PoseTs.py) with its mask drawn
+ * from the step's key instead of torch's device generator, whose Philox offset is part of neither the key nor the checkpoint.
+ * x, out (R,C) fp32, keep (R,C) uint8.  For site s (Rot_green 0, Rot_red 1, Pose_Ts 2), ks = the instance key of
+ * j = 0x83000000 | s, word(i) = absorb(absorb(ks, 0xfffffffa), i) with i = r * C + c, u = the fp32 uniform of word(i):
+ *   keep[r,c] = u >= p;   out[r,c] = keep ? x[r,c] * scale : 0,   scale = 1.0f / (1.0f - p) computed once on the host in fp32
+ * -- the same distribution as nn.Dropout(p) in training mode (P(keep) = 1 - p to 2^-24), not the same draws.  p outside [0, 1),
+ * site outside [0, 2^24), R * C >= 2^32, a NULL pointer or a size <= 0: HSP_ERR_BAD_ARG.
+ * hsp_dropout_bwd: grad_x = grad_out * keep * scale from the SAVED mask (scale from p as above); it never re-derives the mask
+ * from the key, so an eager caller may run two forwards before a backward. */
+int hsp_dropout_keyed_fwd(const float *x, const unsigned long long *key, int site, float p, int R, int C, float *out,
+                          uint8_t *keep, hspStream_t stream);
+int hsp_dropout_bwd(const float *grad_out, const uint8_t *keep, float p, int R, int C, float *grad_x, hspStream_t stream);
 
 /* the face head's output split (PoseNet9D.py:31-35) in one launch each way: face (R, 30) -> unit normals (R, 6, 3) =
  * face[:, :18] / its per-face 3-norm (no epsilon, as the reference), distances (R, 6) = face[:, 18:24], confidences (R, 6) =
