@@ -416,11 +416,14 @@ extern "C" int hsp_fps_f64(const double* xyz, int B, int N, int n_samples, int32
     return check_launch();
 }
 
+// the register-resident kernel: a cloud's points in the registers of one workgroup, 1024 threads x 12 at the most
+extern "C" int hsp_fps_levels_takes(int N0) { return N0 > 0 && N0 <= 12288 ? 1 : 0; }
+
 extern "C" int hsp_fps_levels_f32(const float* xyz, int B, int N0, int N1, int N2, int32_t* sel1, float* v1, float* v2,
                                   hspStream_t stream) {
     if (!xyz || !sel1 || !v1 || B <= 0 || N0 <= 0 || N1 <= 0 || N1 > N0 || N2 < 0 || N2 > N1 || (N2 > 0 && !v2))
         return HSP_ERR_BAD_ARG;
-    if (N0 > 12288) return HSP_ERR_UNSUPPORTED;               // beyond the register-resident kernel (nothing launched)
+    if (!hsp_fps_levels_takes(N0)) return HSP_ERR_UNSUPPORTED;   // (nothing launched)
     hipStream_t st = as_stream(stream);
     const size_t lds = (size_t)N0 * 3 * sizeof(float);
 #define FPS_LV(THREADS, PPT)                                                                                           \

@@ -54,6 +54,10 @@ int knn3_select_flags(const float* x, int B, int N, int k, int drop, int k2, int
 // gather.hip -> gemm.hip: 1 where hsp_colsum_cloud_f32(x, NULL, B, N, C) takes the shape, with its rows per chunk and chunk count
 int colsum_cloud_plan(int B, int N, int C, int* rows, int* nchunk);
 
+// exact.hip -> gemm_wave.hip (hsp_exact_layer_takes): the clouds and widths hsp_orl_global_exact_f32 takes
+bool orl_exact_shape_ok(int N, int C);
+// norm.hip (the fold of hsp_bn_relu_fwd_partials) -> the products that leave BatchNorm partials per row tile (gemm_x3.hip, gemm_rows.hip)
+#define HSP_BN_MAX_PARTIALS 512
 // gemm_wave.hip / gemm_rows.hip -> gemm_x3.hip (hsp_gemm_takes, hsp_gemm_route): 1 where hsp_gemm_wave_f32 (cfg = relu << 29) /
 // the hsp_gemm_rows_* dispatch runs the call -- the functions those entry points decline by
 bool gemm_wave_takes(const HspGemmCall& c);

@@ -153,14 +153,21 @@ __global__ __launch_bounds__(REV_THREADS) void rev_build_multi_kernel(const RevB
 
 using namespace hsp;
 
+// LDS of one cloud's reverse build: the histogram of n_src + 1 counters and, while they fit beside it, the cloud's edges
+#define REV_BUILD_LDS (140 * 1024)
+static size_t rev_build_lds(int Nsrc, int Nq, int k, bool* in_lds) {
+    const size_t lds0 = (size_t)(Nsrc + 1) * sizeof(int), lds1 = lds0 + (size_t)Nq * k * sizeof(int);
+    *in_lds = lds1 <= REV_BUILD_LDS;
+    return *in_lds ? lds1 : lds0;
+}
+extern "C" int hsp_rev_build_takes(int n_src) { return n_src > 0 && (size_t)n_src + 1 <= REV_BUILD_LDS / sizeof(int) ? 1 : 0; }
+
 extern "C" int hsp_rev_build(const int32_t* idx, int B, int Nq, int Nsrc, int k, int kstride, int32_t* rev_off,
                              int32_t* rev_edge, hspStream_t stream) {
     if (!idx || !rev_off || !rev_edge || B <= 0 || Nq <= 0 || Nsrc <= 0 || k <= 0 || kstride < k) return HSP_ERR_BAD_ARG;
-    const size_t lds0 = (size_t)(Nsrc + 1) * sizeof(int);
-    if (lds0 > 140 * 1024) return HSP_ERR_UNSUPPORTED;
-    const size_t lds1 = lds0 + (size_t)Nq * k * sizeof(int);
-    const bool in_lds = lds1 <= 140 * 1024;
-    const size_t lds = in_lds ? lds1 : lds0;
+    if (!hsp_rev_build_takes(Nsrc)) return HSP_ERR_UNSUPPORTED;
+    bool in_lds;
+    const size_t lds = rev_build_lds(Nsrc, Nq, k, &in_lds);
     auto kern = in_lds ? rev_build_kernel<true> : rev_build_kernel<false>;
     if (lds > 60 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -179,11 +186,9 @@ extern "C" int hsp_rev_build_sel(const int32_t* idx, const int32_t* qsel, int qs
         return hsp_rev_build(idx, B, Nq, Nsrc, k, kstride, rev_off, rev_edge, stream);
     }
     if (qsel_stride != 0 && qsel_stride < Nq) return HSP_ERR_BAD_ARG;
-    const size_t lds0 = (size_t)(Nsrc + 1) * sizeof(int);
-    if (lds0 > 140 * 1024) return HSP_ERR_UNSUPPORTED;
-    const size_t lds1 = lds0 + (size_t)Nq * k * sizeof(int);
-    const bool in_lds = lds1 <= 140 * 1024;
-    const size_t lds = in_lds ? lds1 : lds0;
+    if (!hsp_rev_build_takes(Nsrc)) return HSP_ERR_UNSUPPORTED;
+    bool in_lds;
+    const size_t lds = rev_build_lds(Nsrc, Nq, k, &in_lds);
     auto kern = in_lds ? rev_build_sel_kernel<true> : rev_build_sel_kernel<false>;
     if (lds > 60 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -202,11 +207,10 @@ extern "C" int hsp_rev_build_multi(int nmaps, const int32_t* const* idx, int B, 
     size_t lds = 0;
     for (int i = 0; i < nmaps; ++i) {
         if (!idx[i] || !rev_off[i] || !rev_edge[i] || Nq[i] <= 0 || Nsrc[i] <= 0 || k[i] <= 0 || kstride[i] < k[i]) return HSP_ERR_BAD_ARG;
-        const size_t lds0 = (size_t)(Nsrc[i] + 1) * sizeof(int);
-        if (lds0 > 140 * 1024) return HSP_ERR_UNSUPPORTED;
-        const size_t lds1 = lds0 + (size_t)Nq[i] * k[i] * sizeof(int);
-        const bool in_lds = lds1 <= 140 * 1024;
-        lds = lds > (in_lds ? lds1 : lds0) ? lds : (in_lds ? lds1 : lds0);
+        if (!hsp_rev_build_takes(Nsrc[i])) return HSP_ERR_UNSUPPORTED;
+        bool in_lds;
+        const size_t lds_i = rev_build_lds(Nsrc[i], Nq[i], k[i], &in_lds);
+        lds = lds > lds_i ? lds : lds_i;
         tab.m[i] = RevBuildMap{idx[i], rev_off[i], rev_edge[i], Nq[i], Nsrc[i], k[i], kstride[i], in_lds ? 1 : 0};
     }
     if (lds > 60 * 1024) {

@@ -215,6 +215,11 @@ __global__ __launch_bounds__(256) void center_cloud_kernel(const float* __restri
 
 using namespace hsp;
 
+namespace hsp {
+// four-column lanes; level_step = 16 holds below 2^20 rows
+bool orl_exact_shape_ok(int N, int C) { return N > 0 && C > 0 && !(C & 3) && N < (1 << 20); }
+}  // namespace hsp
+
 extern "C" size_t hsp_orl_exact_workspace_bytes(int B, int N, int C) {
     if (B <= 0 || N <= 0 || C <= 0) return 0;
     return (size_t)B * ((N + ORLX_ROWS - 1) / ORLX_ROWS) * C * sizeof(float) + (size_t)B * N * C * sizeof(float);   // chunk sums + G
@@ -223,7 +228,7 @@ extern "C" size_t hsp_orl_exact_workspace_bytes(int B, int N, int C) {
 extern "C" int hsp_orl_global_exact_f32(const float* feat, const int32_t* idx, int B, int N, int k, int kstride, int C, float* fg,
                                         uint8_t* argmax, void* ws, size_t ws_bytes, hspStream_t stream) {
     if (!feat || !idx || !fg || !argmax || B <= 0 || N <= 0 || k <= 0 || kstride < k || C <= 0) return HSP_ERR_BAD_ARG;
-    if ((C & 3) || k > 255 || N >= (1 << 20)) return HSP_ERR_UNSUPPORTED;        // (level_step = 16 holds below 2^20 rows)
+    if (!orl_exact_shape_ok(N, C) || k > 255) return HSP_ERR_UNSUPPORTED;
     if (!ws || ws_bytes < hsp_orl_exact_workspace_bytes(B, N, C)) return HSP_ERR_WORKSPACE;
     hipStream_t st = as_stream(stream);
     const int nchunk = (N + ORLX_ROWS - 1) / ORLX_ROWS;

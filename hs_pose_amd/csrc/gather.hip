@@ -842,7 +842,13 @@ __global__ __launch_bounds__(256) void gather_rows_bwd_kernel(const float* __res
 
 // points per chunk for the two-stage per-cloud reductions: enough chunks to fill the chip, at least one
 // row per row-lane, at most ORL_ROWS (the workspace is sized for the smallest chunk count = ORL_ROWS rows)
-static bool colsum_vec4(int C) { return !(C & 3) && !(256 % (C >> 2)); }
+static bool colsum_vec4(int C) { return C > 0 && !(C & 3) && !(256 % (C >> 2)); }
+// hsp_colsum_rows(_bf16): four-column lanes; fp32 rows of up to 256 columns also one column per lane.  hsp_colsum_rows_xyz(_bf16):
+// the four-column form only
+extern "C" int hsp_colsum_rows_takes(int C, int elem_bytes) {
+    return colsum_vec4(C) || (elem_bytes == 4 && C > 0 && C <= 256) ? 1 : 0;
+}
+extern "C" int hsp_colsum_rows_xyz_takes(int C) { return colsum_vec4(C) ? 1 : 0; }
 
 static int chunk_rows(int B, int N, int C) {
     const int RL = colsum_vec4(C) ? 256 / (C >> 2) : (C <= 256 ? 256 / C : 1);
@@ -1204,13 +1210,18 @@ __global__ __launch_bounds__(256) void gather_rows_bwd_csr_multi_kernel(const Ga
 }
 
 // widths / alignments gather_rows_bwd_csr_body<FT, VEC> takes: VEC-element columns, whole rows per workgroup
-template <typename FT>
-static bool gather_bwd_csr_vec_ok(int VEC, const FT* grad_out, int grad_stride, int C, const FT* grad_feat) {
-    if ((C % VEC) || (grad_stride % VEC)) return false;
-    const size_t al = (size_t)VEC * sizeof(FT) - 1;
-    if ((reinterpret_cast<uintptr_t>(grad_out) & al) || (VEC > 2 && (reinterpret_cast<uintptr_t>(grad_feat) & al))) return false;
+// (grad_align / feat_align: the two addresses modulo 16)
+static bool gather_bwd_csr_vec_ok(int VEC, int elem_bytes, int C, int grad_stride, int grad_align, int feat_align) {
+    if (C <= 0 || (C % VEC) || (grad_stride % VEC)) return false;
+    const int al = VEC * elem_bytes - 1;
+    if ((grad_align & al) || (VEC > 2 && (feat_align & al))) return false;
     const int cols = C / VEC;
     return 256 % (cols < 256 ? cols : 256) == 0;
+}
+static int align16(const void* p) { return (int)(reinterpret_cast<uintptr_t>(p) & 15); }
+// two-element columns, whole rows per workgroup
+extern "C" int hsp_gather_rows_bwd_csr_takes(int elem_bytes, int C, int grad_stride, int grad_align) {
+    return (elem_bytes == 2 || elem_bytes == 4) && grad_stride >= C && gather_bwd_csr_vec_ok(2, elem_bytes, C, grad_stride, grad_align, 0) ? 1 : 0;
 }
 
 template <typename FT>
@@ -1219,8 +1230,7 @@ static int gather_rows_bwd_csr_impl(const FT* grad_out, int grad_stride, const i
                                     hspStream_t stream) {
     if (!grad_out || !rev_off || !rev_edge || !grad_feat || B <= 0 || Nsrc <= 0 || Nq <= 0 || C <= 0 || grad_stride < C)
         return HSP_ERR_BAD_ARG;
-    if (!gather_bwd_csr_vec_ok<FT>(2, grad_out, grad_stride, C, grad_feat))
-        return HSP_ERR_UNSUPPORTED;                         // two-element columns, whole rows per workgroup
+    if (!hsp_gather_rows_bwd_csr_takes((int)sizeof(FT), C, grad_stride, align16(grad_out))) return HSP_ERR_UNSUPPORTED;
     const int tpr = (C >> 1) < 256 ? (C >> 1) : 256;
     const int RB = 256 / tpr;
     const long long rows = (long long)B * Nsrc;
@@ -1247,8 +1257,8 @@ static int gather_rows_bwd_csr_multi_impl(int nseg, const FT* const* grad_out, i
     long long blocks = 0;
     for (int i = 0; i < nseg; ++i) {
         const int s = order[i];
-        if (!gather_bwd_csr_vec_ok<FT>(2, grad_out[s], grad_stride, C[s], grad_feat[s])) return HSP_ERR_UNSUPPORTED;
-        const int vec = gather_bwd_csr_vec_ok<FT>(4, grad_out[s], grad_stride, C[s], grad_feat[s]) ? 4 : 2;
+        if (!hsp_gather_rows_bwd_csr_takes((int)sizeof(FT), C[s], grad_stride, align16(grad_out[s]))) return HSP_ERR_UNSUPPORTED;
+        const int vec = gather_bwd_csr_vec_ok(4, (int)sizeof(FT), C[s], grad_stride, align16(grad_out[s]), align16(grad_feat[s])) ? 4 : 2;
         const int cols = C[s] / vec;
         const int RB = 256 / (cols < 256 ? cols : 256);
         d.seg[i] = GatherBwdSeg{grad_out[s], rev_off[s], rev_edge[s], grad_feat[s], grad_stride, Nsrc[s], Nq, C[s], vec};
@@ -1351,7 +1361,7 @@ extern "C" int hsp_debug_set_orl_prof(void* dev_buf) {
 #endif
 
 extern "C" size_t hsp_orl_workspace_bytes(int B, int N, int C) {
-    if (B <= 0 || N <= 0 || C <= 0 || (!colsum_vec4(C) && C > 256)) return 0;
+    if (B <= 0 || N <= 0 || !hsp_colsum_rows_takes(C, 4)) return 0;
     const int rows = chunk_rows(B, N, C);
     return (size_t)B * ((N + rows - 1) / rows) * C * sizeof(float);
 }
@@ -1431,7 +1441,7 @@ extern "C" int hsp_orl_global_fwd_bf16(const hsp_bf16_t* feat, const int32_t* id
 extern "C" int hsp_colsum_rows(const float* x, int B, int N, int C, float* out, void* ws, size_t ws_bytes,
                                hspStream_t stream) {
     if (!x || !out || B <= 0 || N <= 0 || C <= 0) return HSP_ERR_BAD_ARG;
-    if (!colsum_vec4(C) && C > 256) return HSP_ERR_UNSUPPORTED;
+    if (!hsp_colsum_rows_takes(C, 4)) return HSP_ERR_UNSUPPORTED;
     if (!ws || ws_bytes < hsp_orl_workspace_bytes(B, N, C)) return HSP_ERR_WORKSPACE;
     hipStream_t st = as_stream(stream);
     const int rows = chunk_rows(B, N, C);
@@ -1452,7 +1462,7 @@ template <typename FT>
 static int colsum_rows_xyz_impl(const FT* x, const float* xyz, int B, int N, int C, float* out4, void* ws, size_t ws_bytes,
                                 hspStream_t stream) {
     if (!x || !xyz || !out4 || B <= 0 || N <= 0 || C <= 0) return HSP_ERR_BAD_ARG;
-    if (!colsum_vec4(C)) return HSP_ERR_UNSUPPORTED;
+    if (!hsp_colsum_rows_xyz_takes(C)) return HSP_ERR_UNSUPPORTED;
     if (!ws || ws_bytes < 4 * hsp_orl_workspace_bytes(B, N, C)) return HSP_ERR_WORKSPACE;
     hipStream_t st = as_stream(stream);
     const int rows = chunk_rows(B, N, C);
@@ -1508,7 +1518,7 @@ extern "C" int hsp_colsum_cloud_f32(const float* x, const float* xyz, int B, int
 extern "C" int hsp_colsum_rows_bf16(const hsp_bf16_t* x, int B, int N, int C, float* out, void* ws, size_t ws_bytes,
                                     hspStream_t stream) {
     if (!x || !out || B <= 0 || N <= 0 || C <= 0) return HSP_ERR_BAD_ARG;
-    if (!colsum_vec4(C)) return HSP_ERR_UNSUPPORTED;
+    if (!hsp_colsum_rows_takes(C, 2)) return HSP_ERR_UNSUPPORTED;
     if (!ws || ws_bytes < hsp_orl_workspace_bytes(B, N, C)) return HSP_ERR_WORKSPACE;
     hipStream_t st = as_stream(stream);
     const int rows = chunk_rows(B, N, C);

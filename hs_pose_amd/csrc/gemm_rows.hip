@@ -769,22 +769,23 @@ extern "C" int hsp_gemm_rows_acc_bf16(const hsp_bf16_t* A1, int lda1, const hsp_
                                               nullptr, 0, 1.f, nullptr, nullptr, C, ldc, c_is_f32 ? 1 : 0, ws, ws_bytes, stream, 1);
 }
 
-/* BatchNorm row tiles of hsp_gemm_rows_bn_bf16's result (the row tile of the shape's kernel: 64 or 128 rows) */
+/* BatchNorm row tiles of hsp_gemm_rows_bn_bf16's result (the row tile of the shape's kernel: 64 or 128 rows); 0 where they are more
+ * than the fold takes and the entry point declines */
 extern "C" int hsp_gemm_rows_bn_tiles_bf16(int M, int N, int K) {
     if (M <= 0 || N <= 0 || K <= 0) return 0;
     const int bm = prefer_small_tile(M, N, (K + 63) / 64) ? 64 : 128;
-    return (M + bm - 1) / bm;
+    return (M + bm - 1) / bm <= HSP_BN_MAX_PARTIALS ? (M + bm - 1) / bm : 0;
 }
 
 /* C (fp32) = A B^T + bias (+ cloud_bias[row / rows_per_cloud]) (+ xyz3 . w3) for bf16 rows A (M,K) and a bf16 (N,K) weight, AND the
  * first pass of the train-mode BatchNorm over C: bn_shift[n] = bias[n] + cloud_bias[0][n] (0 where absent) and
  * bn_part[tiles][2][N] = per row tile, sum (c - shift) and sum (c - shift)^2 over the tile's rows, tiles =
- * hsp_gemm_rows_bn_tiles_bf16(M, N, K) <= 512 -- the layout of hsp_gemm_x3_bias_bn_f32; fold with hsp_bn_relu_fwd_partials(_mixed) */
+ * hsp_gemm_rows_bn_tiles_bf16(M, N, K) > 0 -- the layout of hsp_gemm_x3_bias_bn_f32; fold with hsp_bn_relu_fwd_partials(_mixed) */
 extern "C" int hsp_gemm_rows_bn_bf16(const hsp_bf16_t* A, int lda, const hsp_bf16_t* B, int ldb, int K, int M, int N,
                                      const float* bias, const float* cloud_bias, int rows_per_cloud, const float* xyz3, const float* w3,
                                      float* C, int ldc, float* bn_shift, float* bn_part, hspStream_t stream) {
     if (!bn_shift || !bn_part) return HSP_ERR_BAD_ARG;
-    if (hsp_gemm_rows_bn_tiles_bf16(M, N, K) > 512) return HSP_ERR_UNSUPPORTED;
+    if (M > 0 && N > 0 && K > 0 && !hsp_gemm_rows_bn_tiles_bf16(M, N, K)) return HSP_ERR_UNSUPPORTED;
     return gemm_rows_dispatch<unsigned short>(A, lda, B, ldb, 0, K, nullptr, 0, nullptr, 0, 0, 0, M, N, bias, nullptr, 0, cloud_bias,
                                               rows_per_cloud, 1.f, xyz3, w3, C, ldc, 1, nullptr, 0, stream, 0, bn_shift, bn_part);
 }

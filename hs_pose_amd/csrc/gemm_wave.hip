@@ -450,6 +450,24 @@ extern "C" int hsp_gemm_wave_supported(int M, int N, int K1, int K2, int cfg) {
     return gw_plan(M, N, K1, K2, cfg, &p) ? 1 : 0;
 }
 
+// the cut of hsp_layer_out_exact_f32: conv2 over cat[F, f_global] as one chain of 2 C <= 256 or two of C <= 256 (the forms the
+// reference's CPU GEMM runs; more blocks have no form here), a wave's 32-row tile inside one cloud
+static bool layer_out_exact_plan(int M, int C, int rows_per_cloud, int two_chain, GwPlan* p) {
+    if (C > 256 || (!two_chain && 2 * C > 256)) return false;
+    return gw_plan(M, C, C, two_chain ? 0 : C, 0, p) && rows_per_cloud >= 32 * p->RB;
+}
+
+/* 1 where the reference-order entry points of one HS layer all take a cloud of N points, Cin input and C output channels: the
+ * fm and STE products (hsp_gemm_wave_f32 over K = Cin; the surface layer, Cin = 3, has neither), hsp_orl_global_exact_f32 and
+ * hsp_layer_out_exact_f32 in the chain form C selects */
+extern "C" int hsp_exact_layer_takes(int N, int Cin, int C) {
+    GwPlan p;
+    if (N <= 0 || Cin <= 0 || C <= 0) return 0;
+    if (Cin != 3 && !gw_plan(N, C, Cin, 0, 0, &p)) return 0;
+    if (!orl_exact_shape_ok(N, C)) return 0;
+    return layer_out_exact_plan(N, C, N, 2 * C > 256, &p) ? 1 : 0;
+}
+
 /* The HS layer's out product in the REFERENCE's order of operations (gcn3d.py:111-112,185-186 then :90,:156), every product a
  * k-ordered fp32 fma chain from 0 -- what the reference's CPU GEMM runs for K <= 256 -- so that the rows handed to the next
  * layer's feature-space neighbour search carry the reference's bits:
@@ -469,8 +487,7 @@ extern "C" int hsp_layer_out_exact_f32(const float* F, int ldf, const float* Wa,
     if ((ste == nullptr) == (xyz3 == nullptr) || (xyz3 && !w3)) return HSP_ERR_BAD_ARG;
     if (relu && !xyz3) return HSP_ERR_UNSUPPORTED;
     GwPlan p;
-    if (!gw_plan(M, C, C, two_chain ? 0 : C, 0, &p)) return HSP_ERR_UNSUPPORTED;
-    if (rows_per_cloud < 32 * p.RB) return HSP_ERR_UNSUPPORTED;
+    if (!layer_out_exact_plan(M, C, rows_per_cloud, two_chain, &p)) return HSP_ERR_UNSUPPORTED;
     auto al16 = [](const void* q, int ld) { return ((reinterpret_cast<size_t>(q) | ((size_t)ld * 4)) & 15) == 0; };
     if (!al16(F, ldf) || !al16(Wa, ldwa) || !al16(out, ldo) || (!two_chain && (!al16(fg, ldfg) || !al16(Wb, ldwb))) ||
         (ste && !al16(ste, ldste)))

@@ -735,7 +735,7 @@ static bool x3_takes(const HspGemmCall& c, X3Plan* pl) {
     if (pl->panel_R) return true;
     const int bm = 64 * pl->wm;
     const long long tiles_m = (M + bm - 1) / bm;
-    if (c.bn && tiles_m > 512) return false;                                    // (BN_MAX_PARTIALS of norm.hip)
+    if (c.bn && tiles_m > HSP_BN_MAX_PARTIALS) return false;
     return tiles_m * ((N + X3_BN - 1) / X3_BN) * pl->ns <= (1ll << 30);
 }
 
@@ -1110,12 +1110,16 @@ extern "C" int hsp_small_rows_f32(const float* A, int lda, const float* W, int l
     return check_launch();
 }
 
-/* out (Ma, Nb) = a^T c for per-cloud rows a (B, Ma), c (B, Nb), B <= 16: the weight gradient of the f_global half of conv2 */
+// one cloud's row per lane: at most 64 clouds.  The pair: its nn product in MFMA form besides, Ma a multiple of 128 up to 2048
+extern "C" int hsp_small_outer_takes(int B) { return B > 0 && B <= 64 ? 1 : 0; }
+extern "C" int hsp_small_pair_takes(int B, int Ma) { return hsp_small_outer_takes(B) && Ma > 0 && Ma % 128 == 0 && Ma <= 2048 ? 1 : 0; }
+
+/* out (Ma, Nb) = a^T c for per-cloud rows a (B, Ma), c (B, Nb), B <= 64: the weight gradient of the f_global half of conv2 */
 extern "C" int hsp_small_outer_f32(const float* a, int lda, const float* c, int ldc, int B, int Ma, int Nb, float* out, int ldo,
                                    const float* mom, int ldm, int Cm, float* gste, hspStream_t stream) {
     if (!a || !c || !out || B <= 0 || Ma <= 0 || Nb <= 0 || lda < Ma || ldc < Nb || ldo < Nb) return HSP_ERR_BAD_ARG;
     if (mom && (!gste || Cm <= 0 || ldm < 3 * Cm)) return HSP_ERR_BAD_ARG;
-    if (B > 64) return HSP_ERR_UNSUPPORTED;
+    if (!hsp_small_outer_takes(B)) return HSP_ERR_UNSUPPORTED;
     const long long total = (long long)Ma * Nb;
     long long g = (total + 255) / 256;
     if (g > HSP_NUM_CU * 8) g = HSP_NUM_CU * 8;
@@ -1134,7 +1138,7 @@ extern "C" int hsp_small_pair_f32(const float* gt, int ldgt, int B, int Ma, cons
         ldc < Nb || ldo < Nb)
         return HSP_ERR_BAD_ARG;
     if (mom && (!gste || Cm <= 0 || ldm < 3 * Cm)) return HSP_ERR_BAD_ARG;
-    if (B > 64 || Ma % 128 != 0 || Ma > 2048) return HSP_ERR_UNSUPPORTED;
+    if (!hsp_small_pair_takes(B, Ma)) return HSP_ERR_UNSUPPORTED;
     const int n_nn = ((Nn + 15) / 16) * ((B + 15) / 16);
     long long g = ((long long)Ma * Nb + 255) / 256;
     if (g > HSP_NUM_CU * 8) g = HSP_NUM_CU * 8;

@@ -107,12 +107,12 @@ at::Tensor knn_i32(const at::Tensor& x, int k, bool drop_first, bool exact, bool
     const int B = (int)x.size(0), N = (int)x.size(1), C = (int)x.size(2);
     TORCH_CHECK(k >= 1 && k + (drop_first ? 1 : 0) <= N, "get_neighbor_index: k out of range");
     auto idx = at::empty({B, N, k}, x.options().dtype(at::kInt));
-    if (exact && k + (drop_first ? 1 : 0) + 1 <= 33) {
+    if (exact && hsp_knn_exact_takes(B, N, C, k, drop_first)) {
         const size_t wsb = hsp_knn_exact_workspace_bytes(B, N, C, k, drop_first);
         auto ws = bytes_ws(wsb, x);
         ok(hsp_knn_exact_f32(fp(x), B, N, C, k, drop_first, transposed_view ? 1 : 0, idx.data_ptr<int32_t>(), ws.data_ptr(), wsb,
                              nullptr, cur_stream()), "hsp_knn_exact_f32");
-    } else if (C == 3 && k + (drop_first ? 1 : 0) + 1 <= 33 && N >= 2 && (size_t)N * 16 <= 160 * 1024) {
+    } else if (C == 3 && N >= 2 && hsp_knn_xyz_takes(B, N, k, drop_first)) {
         // coordinates: torch.topk's order among equal distances, like every xyz search of the package (ops.knn_xyz)
         const size_t wsb = hsp_knn_xyz_workspace_bytes(B, N);
         auto ws = bytes_ws(wsb, x);
@@ -175,8 +175,6 @@ void layer_out_exact(const at::Tensor& F2, const at::Tensor& w_conv2, const at::
                                relu ? 1 : 0, R, C, N, out2.data_ptr<float>(), C, cur_stream()), "hsp_layer_out_exact_f32");
 }
 
-bool exact_shapes(int N, int Cin, int C) { return C % 32 == 0 && (Cin == 3 || Cin % 32 == 0) && 2 * C <= 512 && N >= 32; }
-
 // HS_layer.forward (gcn3d.py:143-156), eval mode.  idx_f: the feature-space neighbour index (exactly k columns; knn_exact),
 // idx_x: the xyz one (>= k columns), w_ste (Cout,Cin[,1]), w_conv2 (Cout,2Cout[,1]).  Returns out (B,N,Cout).
 at::Tensor hs_layer_forward(at::Tensor xyz, at::Tensor X, at::Tensor idx_f, at::Tensor idx_x, int64_t k, int64_t S, at::Tensor weights,
@@ -195,7 +193,7 @@ at::Tensor hs_layer_forward(at::Tensor xyz, at::Tensor X, at::Tensor idx_f, at::
     TORCH_CHECK(bias.size(0) == (S + 1) * C, "HS_layer: bias must hold (S+1) Cout entries");
     TORCH_CHECK(idx_x.size(0) == B && idx_x.size(1) == N, "HS_layer: idx_x must be (B,N,>=k)");
     TORCH_CHECK(w_ste.size(0) == C && w_ste.size(1) == Cin && w_conv2.size(0) == C && w_conv2.size(1) == 2 * C, "HS_layer: STE / conv2 shapes");
-    TORCH_CHECK(exact_shapes(N, Cin, C), "hs_layer_forward: shape outside the reference-order forms (use the Python path)");
+    TORCH_CHECK(hsp_exact_layer_takes(N, Cin, C), "hs_layer_forward: shape outside the reference-order forms (use the Python path)");
     TORCH_CHECK(idx_x.size(2) >= k && idx_f.size(2) == k && idx_f.size(0) == B && idx_f.size(1) == N, "HS_layer: idx_f (B,N,k), idx_x (B,N,>=k)");
     auto X2 = X.view({B * N, Cin});
     auto fm = gemm_wave(X2, weights, true, &bias);                                          // gcn3d.py:171
@@ -224,7 +222,7 @@ at::Tensor surface_layer_forward(at::Tensor xyz, at::Tensor idx_x, int64_t k, in
     const int B = (int)xyz.size(0), N = (int)xyz.size(1), SC = (int)directions.size(1), C = SC / (int)S;
     TORCH_CHECK(w_ste.size(0) == C && w_ste.size(1) == 3 && w_conv2.size(0) == C && w_conv2.size(1) == 2 * C, "HSlayer_surface: STE / conv2 shapes");
     TORCH_CHECK(idx_x.size(0) == B && idx_x.size(1) == N && idx_x.size(2) == k, "HSlayer_surface: idx must be (B,N,k) with exactly k columns");
-    TORCH_CHECK(exact_shapes(N, 3, C), "surface_layer_forward: shape outside the reference-order forms (use the Python path)");
+    TORCH_CHECK(hsp_exact_layer_takes(N, 3, C), "surface_layer_forward: shape outside the reference-order forms (use the Python path)");
     auto F3 = at::empty({B, N, C}, xyz.options());
     auto arg = at::empty({B, N, SC}, xyz.options().dtype(at::kUInt16));
     ok(hsp_rf_surface_fwd(fp(xyz), idx_x.data_ptr<int32_t>(), fp(directions), B, N, (int)k, (int)S, C, F3.data_ptr<float>(),

@@ -1832,6 +1832,33 @@ extern "C" int hsp_knn_bf16(const hsp_bf16_t* x, int B, int N, int C, int k, int
     });
 }
 
+// LDS of geometry_levels_kernel: the larger level's candidates and lists, or (tie0: the input cloud's tie pass rides along) four
+// waves' candidate rows of the input cloud
+static size_t geometry_lds(int N0, int N1, int N2, bool tie0) {
+    const int Nm = N1 > N2 ? N1 : N2;
+    const size_t lds = (size_t)Nm * 16 + (size_t)4 * KNN3W_SV * 8 + 4 * 64 * 4 + (size_t)16 * Nm * 4;
+    return tie0 && lds < (size_t)4 * 16 * N0 ? (size_t)4 * 16 * N0 : lds;
+}
+
+// the wave-per-query search with its in-kernel tie replay: 64 <= N <= 576 points per level, lists of at most 31 + drop entries
+extern "C" int hsp_geometry_levels_takes(int N0, int N1, int N2, int k1, int kpool, int k2, int drop_first) {
+    const int drop = drop_first ? 1 : 0;
+    if (N0 <= 0 || k1 <= 0 || k2 <= 0 || kpool < 0 || kpool > k1) return 0;
+    if (N1 < 64 || N1 > 64 * 9 || N2 < 64 || N2 > 64 * 9 || k1 + drop + 1 > 33 || k2 + drop + 1 > 33 || k1 + drop > N1 ||
+        k2 + drop > N2 || N2 > N1 || N1 > N0)
+        return 0;
+    return geometry_lds(N0, N1, N2, false) <= 160 * 1024 ? 1 : 0;
+}
+
+// ... and level 0 on the wave search WITHOUT the in-kernel replay (its tie pass rides in the levels' launch): 576 < N0 <= 1088, a
+// batch below 131072 rows
+extern "C" int hsp_geometry_all_takes(int B, int N0, int k0, int kpool0, int N1, int N2, int k1, int kpool, int k2, int drop_first) {
+    const int drop = drop_first ? 1 : 0;
+    if (B <= 0 || k0 <= 0 || kpool0 < 0 || kpool0 > k0 || !hsp_geometry_levels_takes(N0, N1, N2, k1, kpool, k2, drop_first)) return 0;
+    if (N0 <= 64 * 9 || N0 > 64 * 17 || (long long)B * N0 >= 131072 || k0 + drop + 1 > 33 || k0 + drop > N0) return 0;
+    return geometry_lds(N0, N1, N2, true) <= 160 * 1024 ? 1 : 0;
+}
+
 static int geometry_impl(const float* xyz, int B, int N0, const int32_t* sel1, int N1, const int32_t* sel2, int N2, int k1, int kpool,
                          int k2, int drop, float* v1, float* v2, int32_t* idx1, int32_t* idx1_pool, int32_t* idx2, int32_t* up1,
                          int32_t* up2, const uint8_t* tie0, int k0, int kpool0, int32_t* idx0, int32_t* idx0_pool, hipStream_t st) {
@@ -1842,17 +1869,9 @@ static int geometry_impl(const float* xyz, int B, int N0, const int32_t* sel1, i
     a.tie0 = tie0; a.B = B; a.k0 = k0; a.kpool0 = kpool0; a.idx0 = idx0; a.idx0p = idx0_pool;
     a.nbtie = tie0 ? (int)(((long long)B * N0 + 31) / 32) : 0;  // one tie wave per 8 rows of the level-0 search
     const int Nm = N1 > N2 ? N1 : N2;
-    size_t lds = (size_t)Nm * 16 + (size_t)4 * KNN3W_SV * 8 + 4 * 64 * 4 + (size_t)16 * Nm * 4;
-    if (tie0 && lds < (size_t)4 * 16 * N0) lds = (size_t)4 * 16 * N0;
-    if (lds > 160 * 1024) return HSP_ERR_UNSUPPORTED;
     const dim3 grid(a.nbtie + (a.nb1 + a.nb2 + 2 * a.nbt) * B);
-    return launch_lds(Nm <= 64 * 5 ? geometry_levels_kernel<5> : geometry_levels_kernel<9>, grid, dim3(256), lds, st, a);
-}
-
-static bool geometry_levels_ok(int N0, int N1, int N2, int k1, int k2, int drop) {
-    // the wave-per-query search with its in-kernel tie replay: 64 <= N <= 576 points per level, lists of at most 31 + drop entries
-    return !(N1 < 64 || N1 > 64 * 9 || N2 < 64 || N2 > 64 * 9 || k1 + drop + 1 > 33 || k2 + drop + 1 > 33 || k1 + drop > N1 ||
-             k2 + drop > N2 || N2 > N1 || N1 > N0);
+    return launch_lds(Nm <= 64 * 5 ? geometry_levels_kernel<5> : geometry_levels_kernel<9>, grid, dim3(256),
+                      geometry_lds(N0, N1, N2, tie0 != nullptr), st, a);
 }
 
 extern "C" int hsp_geometry_levels_f32(const float* xyz, int B, int N0, const int32_t* sel1, int N1, const int32_t* sel2, int N2,
@@ -1861,10 +1880,9 @@ extern "C" int hsp_geometry_levels_f32(const float* xyz, int B, int N0, const in
     if (!xyz || !sel1 || !sel2 || !v1 || !v2 || !idx1 || !idx2 || !up1 || !up2 || B <= 0 || N0 <= 0 || k1 <= 0 || k2 <= 0 || kpool < 0 ||
         (kpool > 0) != (idx1_pool != nullptr) || kpool > k1)
         return HSP_ERR_BAD_ARG;
-    const int drop = drop_first ? 1 : 0;
-    if (!geometry_levels_ok(N0, N1, N2, k1, k2, drop)) return HSP_ERR_UNSUPPORTED;
-    return geometry_impl(xyz, B, N0, sel1, N1, sel2, N2, k1, kpool, k2, drop, v1, v2, idx1, idx1_pool, idx2, up1, up2, nullptr, 0, 0,
-                         nullptr, nullptr, as_stream(stream));
+    if (!hsp_geometry_levels_takes(N0, N1, N2, k1, kpool, k2, drop_first)) return HSP_ERR_UNSUPPORTED;
+    return geometry_impl(xyz, B, N0, sel1, N1, sel2, N2, k1, kpool, k2, drop_first ? 1 : 0, v1, v2, idx1, idx1_pool, idx2, up1, up2, nullptr,
+                         0, 0, nullptr, nullptr, as_stream(stream));
 }
 
 extern "C" size_t hsp_geometry_all_workspace_bytes(int B, int N0) {
@@ -1881,10 +1899,7 @@ extern "C" int hsp_geometry_all_f32(const float* xyz, int B, int N0, int k0, int
         kpool > k1 || kpool0 > k0)
         return HSP_ERR_BAD_ARG;
     const int drop = drop_first ? 1 : 0;
-    // level 0 on the wave search WITHOUT the in-kernel replay (its tie pass rides here): 576 < N0 <= 1088, a batch below 131072 rows
-    if (!geometry_levels_ok(N0, N1, N2, k1, k2, drop) || N0 <= 64 * 9 || N0 > 64 * 17 || (long long)B * N0 >= 131072 ||
-        k0 + drop + 1 > 33 || k0 + drop > N0)
-        return HSP_ERR_UNSUPPORTED;
+    if (!hsp_geometry_all_takes(B, N0, k0, kpool0, N1, N2, k1, kpool, k2, drop_first)) return HSP_ERR_UNSUPPORTED;
     if (!ws || ws_bytes < hsp_geometry_all_workspace_bytes(B, N0)) return HSP_ERR_WORKSPACE;
     uint8_t* tie = reinterpret_cast<uint8_t*>(ws);
     bool needs_pass = true;

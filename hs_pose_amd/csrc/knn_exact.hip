@@ -149,18 +149,27 @@ extern "C" size_t hsp_knn_xyz_workspace_bytes(int B, int N) {
     return ((size_t)B * N + 255) & ~(size_t)255;
 }
 
+// LDS of a tie pass's single-wave workgroup: a whole row of candidates and, in feature space (C != 3), the query's own row
+static size_t tie_pass_lds(int N, int C) {
+    return (size_t)N * (sizeof(TkE) + 2 * sizeof(int)) + (C == 3 ? 0 : (size_t)((C + 3) & ~3) * sizeof(float));
+}
+
+// lists of at most 32 entries (the selection keeps one more) and a row of candidates within the LDS: clouds of up to 10 240 points
+// in coordinates.  Beyond either the caller takes hsp_knn_f32's (distance, index) order, which has no such bound.
+static bool tie_pass_takes(int B, int N, int C, int k, int drop) {
+    return B > 0 && N > 0 && C > 0 && k > 0 && k + drop <= N && k + drop + 1 <= 33 && tie_pass_lds(N, C) <= 160 * 1024;
+}
+extern "C" int hsp_knn_xyz_takes(int B, int N, int k, int drop_first) { return tie_pass_takes(B, N, 3, k, drop_first ? 1 : 0) ? 1 : 0; }
+extern "C" int hsp_knn_exact_takes(int B, int N, int C, int k, int drop_first) { return tie_pass_takes(B, N, C, k, drop_first ? 1 : 0) ? 1 : 0; }
+
 extern "C" int hsp_knn_xyz_f32(const float* xyz, int B, int N, int k, int k2, int drop_first, int32_t* idx, int32_t* idx2, void* ws,
                                size_t ws_bytes, int* tie_rows, hspStream_t stream) {
     const int drop = drop_first ? 1 : 0;
     if (!knn_args_ok(xyz, idx, B, N, 3, k, drop, HSP_MAX_K) || k2 < 0 || k2 > k || (k2 > 0) != (idx2 != nullptr)) return HSP_ERR_BAD_ARG;
-    const int m = k + drop;
-    if (m + 1 > 33) return HSP_ERR_UNSUPPORTED;
+    if (!hsp_knn_xyz_takes(B, N, k, drop_first)) return HSP_ERR_UNSUPPORTED;        // (before anything is launched)
     if (!ws || ws_bytes < hsp_knn_xyz_workspace_bytes(B, N)) return HSP_ERR_WORKSPACE;
     uint8_t* tie = reinterpret_cast<uint8_t*>(ws);
-    // the tie pass keeps a whole row of candidates in LDS: clouds beyond 10 240 points are refused BEFORE anything is launched (the
-    // caller then takes hsp_knn_f32's (distance, index) order, which has no such bound -- ops.knn_xyz does)
-    const size_t lds = (size_t)N * (sizeof(TkE) + 2 * sizeof(int));
-    if (lds > 160 * 1024) return HSP_ERR_UNSUPPORTED;
+    const size_t lds = tie_pass_lds(N, 3);
     bool needs_pass = true;
     int rc = knn3_select_flags(xyz, B, N, k, drop, k2, idx, idx2, tie, as_stream(stream), &needs_pass);
     if (rc || !needs_pass) return rc;                      // (tie_rows is only counted by the separate pass)
@@ -194,10 +203,10 @@ extern "C" int hsp_knn_quadmode_f32(const float* x, int B, int N, int C, int k, 
 extern "C" int hsp_knn_exact_f32(const float* x, int B, int N, int C, int k, int drop_first, int quad_mode, int32_t* idx, void* ws,
                                  size_t ws_bytes, int* tie_rows, hspStream_t stream) {
     const int drop = drop_first ? 1 : 0;
-    if (!knn_args_ok(x, idx, B, N, C, k, drop, INT_MAX)) return HSP_ERR_BAD_ARG;       // (no HSP_MAX_K test here: mc > 33 below)
+    if (!knn_args_ok(x, idx, B, N, C, k, drop, INT_MAX)) return HSP_ERR_BAD_ARG;       // (no HSP_MAX_K test here: the list bound below)
+    if (!hsp_knn_exact_takes(B, N, C, k, drop_first)) return HSP_ERR_UNSUPPORTED;      // (the replay pass's LDS row included)
     const int m = k + drop;
     const int mc = m + 1 < N ? m + 1 : N;
-    if (mc > 33 || mc > 64) return HSP_ERR_UNSUPPORTED;
     if (!ws || ws_bytes < hsp_knn_exact_workspace_bytes(B, N, C, k, drop_first)) return HSP_ERR_WORKSPACE;
     if (C == 3) return hsp_knn_xyz_f32(x, B, N, k, 0, drop_first, idx, nullptr, ws, ws_bytes, tie_rows, stream);   // flags + flagged rows
     const size_t inner = (hsp_knn_workspace_bytes(B, N, C, mc) + 255) & ~(size_t)255;
@@ -207,8 +216,7 @@ extern "C" int hsp_knn_exact_f32(const float* x, int B, int N, int C, int k, int
                       : nullptr;
     int rc = knn_feat_select_flags(x, B, N, C, k, drop, quad_mode, idx, ws, inner, tie, dmat, stream);
     if (rc) return rc;
-    const size_t lds = (size_t)N * (sizeof(TkE) + 2 * sizeof(int)) + (size_t)((C + 3) & ~3) * sizeof(float);
-    if (lds > 160 * 1024) return HSP_ERR_UNSUPPORTED;
+    const size_t lds = tie_pass_lds(N, C);
     const float* quad = reinterpret_cast<const float*>(ws);                           // knn_feat_select_flags left |x|^2 there
     // (as many waves as fit: ~2 % of the rows of real activations are flagged, and two of them in one wave double the pass)
     return launch_lds(knn_feat_ties_rows_kernel, dim3(tie_pass_grid((long long)B * N, lds, 1)), dim3(64), lds, as_stream(stream), x, quad,

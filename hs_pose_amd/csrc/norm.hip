@@ -35,7 +35,7 @@ __device__ __forceinline__ float4 bn_ld4_pitch(const FT* p, int ld) {
     }
     return Feat<FT>::ld4(p);
 }
-#define BN_MAX_PARTIALS 512       // row chunks (workgroups of the partial kernels); folded 16-way parallel by finalize
+#define BN_MAX_PARTIALS HSP_BN_MAX_PARTIALS   // (512) row chunks (workgroups of the partial kernels); folded 16-way parallel by finalize
 
 // partial[blk][0][c] = sum_r v1, partial[blk][1][c] = sum_r v2 over the rows of chunk blk, where
 //   MODE 0 (forward stats):  v1 = x - shift,  v2 = (x - shift)^2            shift = x[r0][c], r0 the chunk's first row
@@ -312,8 +312,7 @@ static int bn_blocks(int R) { const int r = bn_rows_per_block(R); return (R + r 
 
 static int bn_check(int R, int C) {
     if (R <= 0 || C <= 0) return HSP_ERR_BAD_ARG;
-    if ((C & 3) || (BN_THREADS % (C >> 2)) != 0) return HSP_ERR_UNSUPPORTED;   // C in {4,8,...,1024} dividing 1024
-    return HSP_OK;
+    return hsp_bn_takes(R, C) ? HSP_OK : HSP_ERR_UNSUPPORTED;
 }
 
 static int stream_grid4(long long total4) {
@@ -327,6 +326,9 @@ static int stream_grid4(long long total4) {
 }  // namespace hsp
 
 using namespace hsp;
+
+// four-channel lanes that tile a workgroup's BN_THREADS: C in {4, 8, ..., 1024} with C / 4 dividing 256
+extern "C" int hsp_bn_takes(int R, int C) { return R > 0 && C > 0 && !(C & 3) && BN_THREADS % (C >> 2) == 0 ? 1 : 0; }
 
 extern "C" size_t hsp_bn_workspace_bytes(int R, int C) {
     if (R <= 0 || C <= 0) return 0;

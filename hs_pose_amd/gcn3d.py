@@ -83,7 +83,8 @@ def _prefetch_levels_fps(vertices, k, pool_k):
     n1 = int(n0 / 4)
     n2 = int(n1 / 4)
     k1, k2 = min(k, n1 // 8), min(k, n2 // 8)
-    if vertices.shape[2] != 3 or n2 < 1 or k1 < 1 or k2 < 1 or k1 + 1 > n1 or k2 + 1 > n2 or n0 > ops.FPS_LEVELS_MAX_N:
+    if (vertices.shape[2] != 3 or n2 < 1 or k1 < 1 or k2 < 1 or k1 + 1 > n1 or k2 + 1 > n2
+            or not ops._takes("hsp_fps_levels_takes", n0)):
         return None                                          # (the layers then sample and search on their own)
     sel1, v1, v2 = ops.fps_levels(vertices, n1, n2)
     _xyz_knn(v1, k1)                                         # with Pool_layer's short list where k1 > POOL_K (one search, two lists)
@@ -112,15 +113,16 @@ def prefetch_levels(vertices, k, pool_k=None, rates=(4, 4), samplers=(None, None
     how = {resolve_sampler(s_) for s_ in samplers}
     if how != {"random"}:
         return _prefetch_levels_fps(vertices, k, pool_k) if how == {"fps"} and tuple(rates) == (4, 4) else None
-    n0 = vertices.shape[1]
+    B, n0, C = vertices.shape
     n1 = int(n0 / 4)
     n2 = int(n1 / 4)
     k1, k2 = min(k, n1 // 8), min(k, n2 // 8)
-    # every condition of ops.geometry_levels / geometry_all is checked HERE, before an index draw is consumed (a refusal after the
+    # ops.geometry_all / geometry_levels are asked HERE whether they will run, before an index draw is consumed (a refusal after the
     # draws could not fall back without drawing again, out of the reference's order); ``rates``: the two Pool_layers' pooling rates
-    # (another rate than 4 and the layers would ignore the prefetch and draw a second time)
-    if (tuple(rates) != (4, 4) or vertices.shape[2] != 3 or not (64 <= n2 <= n1 <= 576) or k1 <= pool_k or k1 < 1 or k2 < 1
-            or k1 + 2 > 33 or k2 + 2 > 33 or k1 + 1 > n1 or k2 + 1 > n2):
+    # (another rate than 4 and the layers would ignore the prefetch and draw a second time).  with_input: the input cloud's own
+    # search goes into the same pair of launches where the shapes allow (its tie pass rides in the levels' launch)
+    with_input = k > pool_k and ops.geometry_all_takes(B, n0, C, k, pool_k, n1, n2, k1, pool_k, k2)
+    if tuple(rates) != (4, 4) or k1 <= pool_k or not (with_input or ops.geometry_levels_takes(n0, C, n1, n2, k1, pool_k, k2)):
         return None
     if _pool_feed is not None:
         sel1, sel2 = next(_pool_feed), next(_pool_feed)
@@ -132,14 +134,11 @@ def prefetch_levels(vertices, k, pool_k=None, rates=(4, 4), samplers=(None, None
             else:                                            # the reference's own draws, in its order (pool_1, then pool_2)
                 sel1 = torch.randperm(n0)[:n1].to(device=vertices.device, dtype=torch.int32)
                 sel2 = torch.randperm(n1)[:n2].to(device=vertices.device, dtype=torch.int32)
-    # with the input cloud's own search in the same pair of launches where the shapes allow (its tie pass rides in the levels' launch)
-    geo = ops.geometry_all(vertices, k, pool_k, sel1, sel2, k1, pool_k, k2) if k > pool_k else None
-    if geo is not None:
+    if with_input:
+        geo = ops.geometry_all(vertices, k, pool_k, sel1, sel2, k1, pool_k, k2)
         _knn_memo[id(vertices)] = (vertices, {k: geo["idx0"], pool_k: geo["idx0_pool"]})
     else:
         geo = ops.geometry_levels(vertices, sel1, sel2, k1, pool_k, k2)
-    if geo is None:
-        raise RuntimeError("prefetch_levels: shape check and kernel disagree")      # (indices already consumed: cannot fall back)
     v1, v2 = geo["v1"], geo["v2"]
     _knn_memo[id(v1)] = (v1, {k1: geo["idx1"], pool_k: geo["idx1_pool"]})
     _knn_memo[id(v2)] = (v2, {k2: geo["idx2"]})

@@ -5,6 +5,7 @@ buffer), passes raw device pointers + the current HIP stream through ctypes and 
 return code.  No CPU fallback: a non-GPU tensor is an error.
 """
 import ctypes
+import functools
 import os
 
 import torch
@@ -32,6 +33,14 @@ def _p(t):
 
 def _stream():
     return _vp(torch.cuda.current_stream().cuda_stream)
+
+
+@functools.lru_cache(maxsize=None)
+def _takes(name, *ints):
+    """True where the entry point that host query ``name`` of include/hsp.h speaks for runs a call of these extents (``hsp_*_takes``,
+    ``hsp_colsum_cloud_ok``: the functions the entry points themselves decline by).  Integers only -- an address goes in as its
+    remainder modulo 16 --, so the answer is a pure function of the arguments and is kept."""
+    return getattr(lib(), name)(*ints) == 1
 
 
 def _req(t, dtype, name):
@@ -148,9 +157,8 @@ def knn_xyz(xyz, k, k2=0, drop_first=True):
     if C != 3:
         raise HspError("knn_xyz: expects (B,N,3) coordinates")
     k2 = int(k2) if k2 and k2 < k else 0
-    m = k + (1 if drop_first else 0)
-    if m + 1 > 33 or N < 2 or N * 16 > 160 * 1024:         # beyond the tie pass's list length / its one-row-in-LDS bound
-                                                            # (N > 10 240): the (distance, index) order, any N
+    if N < 2 or not _takes("hsp_knn_xyz_takes", B, N, k, 1 if drop_first else 0):
+        # a single point, or beyond the tie pass's list length / its one-row-in-LDS bound: the (distance, index) order, any N
         idx = knn(x, k, drop_first, _plain_xyz=True)
         return idx, (idx[:, :, :k2].contiguous() if k2 else None)
     idx = torch.empty(B, N, k, dtype=torch.int32, device=x.device)
@@ -162,6 +170,17 @@ def knn_xyz(xyz, k, k2=0, drop_first=True):
     return idx, idx2
 
 
+def geometry_all_takes(B, N0, C, k0, kpool0, N1, N2, k1, kpool, k2):
+    """True where ``geometry_all`` runs: coordinates, both short lists asked for (the wrapper's own contract) and shapes
+    ``hsp_geometry_all_f32`` takes"""
+    return C == 3 and 0 < kpool <= k1 and 0 < kpool0 < k0 and _takes("hsp_geometry_all_takes", B, N0, k0, kpool0, N1, N2, k1, kpool, k2, 1)
+
+
+def geometry_levels_takes(N0, C, N1, N2, k1, kpool, k2):
+    """True where ``geometry_levels`` runs: coordinates, the pooling list asked for, shapes ``hsp_geometry_levels_f32`` takes"""
+    return C == 3 and 0 < kpool <= k1 and _takes("hsp_geometry_levels_takes", N0, N1, N2, k1, kpool, k2, 1)
+
+
 def geometry_all(xyz, k0, kpool0, sel1, sel2, k1, kpool, k2):
     """``knn_xyz(xyz, k0, kpool0)`` AND ``geometry_levels`` in two launches instead of three (hsp_geometry_all_f32: the input cloud's
     tie pass rides in the levels' launch).  The dict of ``geometry_levels`` plus ``idx0`` / ``idx0_pool``; None outside the fused
@@ -170,8 +189,7 @@ def geometry_all(xyz, k0, kpool0, sel1, sel2, k1, kpool, k2):
     s1, s2 = _req(sel1, torch.int32, "geometry_all.sel1"), _req(sel2, torch.int32, "geometry_all.sel2")
     B, N0, C = x.shape
     N1, N2 = s1.numel(), s2.numel()
-    if (C != 3 or not (64 <= N2 <= N1 <= 576) or not (576 < N0 <= 1088) or B * N0 >= 131072 or k1 + 2 > 33 or k2 + 2 > 33 or k0 + 2 > 33
-            or k1 + 1 > N1 or k2 + 1 > N2 or not 0 < kpool <= k1 or not 0 < kpool0 < k0):
+    if not geometry_all_takes(B, N0, C, k0, kpool0, N1, N2, k1, kpool, k2):
         return None
     dev = x.device
     i32 = dict(dtype=torch.int32, device=dev)
@@ -198,7 +216,7 @@ def geometry_levels(xyz, sel1, sel2, k1, kpool, k2):
     s1, s2 = _req(sel1, torch.int32, "geometry_levels.sel1"), _req(sel2, torch.int32, "geometry_levels.sel2")
     B, N0, C = x.shape
     N1, N2 = s1.numel(), s2.numel()
-    if C != 3 or not (64 <= N2 <= N1 <= 576) or N1 > N0 or k1 + 2 > 33 or k2 + 2 > 33 or k1 + 1 > N1 or k2 + 1 > N2 or not 0 < kpool <= k1:
+    if not geometry_levels_takes(N0, C, N1, N2, k1, kpool, k2):
         return None
     dev = x.device
     out = dict(v1=torch.empty(B, N1, 3, dtype=torch.float32, device=dev), v2=torch.empty(B, N2, 3, dtype=torch.float32, device=dev),
@@ -228,7 +246,7 @@ def knn(x, k, drop_first=True, transposed_view=False, _plain_xyz=False):
         _run("hsp_knn_bf16", (_p(x), B, N, C, k, 1 if drop_first else 0, _p(idx), _p(ws), wsb, _stream()),
              key=f"B{B}N{N}C{C}k{k}", abytes=B * N * (2 * C + 4 * k + 8), aflops=2 * B * N * N * C)
         return idx
-    if _exact and k + (1 if drop_first else 0) + 1 <= 33 and os.environ.get("HSP_EXACT_TIES", "1") != "0":
+    if _exact and _takes("hsp_knn_exact_takes", B, N, C, k, 1 if drop_first else 0) and os.environ.get("HSP_EXACT_TIES", "1") != "0":
         # eval-mode forward (exact_scope): torch.topk's own order among exactly equal distances (csrc/knn_exact.hip)
         wsb = L.hsp_knn_exact_workspace_bytes(B, N, C, k, 1 if drop_first else 0)
         ws = _ws(wsb, x.device)
@@ -287,9 +305,6 @@ def nn1(target, source):
     _run("hsp_nn1_f32", (_p(t), Nt, _p(s), s.shape[1], B, _p(idx), _stream()),
          key=f"B{B}Nt{Nt}Ns{s.shape[1]}", abytes=B * (16 * Nt + 12 * s.shape[1]))
     return idx
-
-
-_REV_BUILD_LDS = 140 * 1024        # bytes of LDS hsp_rev_build's per-cloud histogram (n_src + 1 ints) may take (csrc/csr.hip)
 
 
 def rev_index(idx, k, n_src):
@@ -1112,6 +1127,8 @@ def gemm_x3_bn(A1, B1, A2, B2, resid, cloud_bias, rows_per_cloud, out):
     N = B1.shape[0]
     P1, ldp1, ps1 = x3_planes.planes(B1, False)
     P2, ldp2, ps2 = x3_planes.planes(B2, False)
+    # (64-row tiles whatever the shape: the layout include/hsp.h gives for hsp_gemm_x3_bn_f32.  hsp_gemm_x3_bn_tiles speaks for
+    # hsp_gemm_x3_bias_bn_f32, whose tiles are 128 rows on large products)
     buf = torch.empty(1 + 2 * ((M + 63) // 64), N, dtype=torch.float32, device=A1.device)
     bn_shift, part = buf[0], buf[1:]
     _run("hsp_gemm_x3_bn_f32", (_p(A1), _ld(A1), _p(P1), ldp1, ps1, K1, _p(A2), _ld(A2), _p(P2), ldp2, ps2, A2.shape[1], M, N,
@@ -1126,7 +1143,7 @@ def linear_bn_part_ok(x2, W, bias):
     """a Linear (R, K) x (N, K)^T + bias whose product can also leave the first pass of the train-mode BatchNorm behind it
     (``hsp_gemm_x3_bias_bn_f32``)"""
     N = W.shape[0]
-    return (bias is not None and N % 4 == 0 and 256 % (N // 4) == 0
+    return (bias is not None and _takes("hsp_bn_takes", x2.shape[0], N)
             and _gemm_route(x2, W, bias=bias, bn=BN_LINEAR) == ROUTE_X3_BN)
 
 
@@ -1191,7 +1208,7 @@ def _layer_out_bn_ok(x2, w_ste, F2, Wa, t2, out3, relu):
 
 def _ste_moments_ok(C):
     """the surface layer's (C, 3) STE gradient from the coordinate moments of g (``colsum_rows_xyz``) instead of a product"""
-    return C % 4 == 0 and 256 % (C // 4) == 0
+    return _takes("hsp_colsum_rows_xyz_takes", C)
 
 
 def _thin_wgrad_ok(Cout, Cin, R, g):
@@ -1320,8 +1337,8 @@ def _tiny_tn(a, b, out, mom=None, gste=None):
     surface layer's (C,3) STE gradient as a rider (the sum over the clouds of the coordinate moments of g)"""
     B, Ma = a.shape
     Cm = mom.shape[1] // 4 if mom is not None else 0
-    if B > 64:
-        # hsp_small_outer_f32 holds one row per lane (B <= 64 clouds).  Larger per-GPU batches: the general weight-gradient
+    if not _takes("hsp_small_outer_takes", B):
+        # hsp_small_outer_f32 holds one row per lane.  Larger per-GPU batches: the general weight-gradient
         # path for a^T b (any row count), the (C, 3) coordinate-moment rider as a plain column sum over the clouds
         wgrad(a.contiguous(), b.contiguous(), out=out)
         if mom is not None:
@@ -1384,7 +1401,7 @@ def _residual_bias(out3, f3, t2):
 def colsum_rows(x3):
     """fp32 (B,C) = x3.sum(dim=1) for a contiguous (B,N,C) fp32 / bf16 tensor: deterministic two-stage column sum"""
     B, N, C = x3.shape
-    if x3.dtype == torch.float32 and (((C % 4 or 256 % (C // 4)) and C > 256) or not x3.is_contiguous()):
+    if x3.dtype == torch.float32 and (not _takes("hsp_colsum_rows_takes", C, 4) or not x3.is_contiguous()):
         return x3.sum(dim=1)
     out = torch.empty(B, C, dtype=torch.float32, device=x3.device)
     L = lib()
@@ -1417,8 +1434,8 @@ _between_launches_hook = None
 
 def _orl_bwd_small_ok(B, N, C, with_xyz):
     """shapes the two-launch form of the per-cloud backward chain takes"""
-    return (LAUNCH_DIET and B <= 64 and C % 128 == 0 and C <= 2048
-            and lib().hsp_colsum_cloud_ok(B, N, C, 1 if with_xyz else 0) == 1)
+    return (LAUNCH_DIET and _takes("hsp_small_pair_takes", B, C)
+            and _takes("hsp_colsum_cloud_ok", B, N, C, 1 if with_xyz else 0))
 
 
 # COLSUM_RIDER = True: an HS layer's node goes one further -- its column sum rides in the launch of the two weight gradients that
@@ -1585,9 +1602,10 @@ def _f32c(*ts):
 
 
 def _exact_layer_ok(N, Cin, C, tensors):
-    """shapes the exact forms cover: channel counts that are multiples of 32, conv2 over at most 512 input channels (one chain
-    or two; conv_4's 1024 are four blocks and its rows rank nothing), clouds of at least 32 points, 16-byte aligned rows"""
-    return (C % 32 == 0 and (Cin == 3 or Cin % 32 == 0) and 2 * C <= 512 and N >= 32
+    """shapes the exact forms cover (``hsp_exact_layer_takes``: channel counts that are multiples of 32, conv2 over at most 512
+    input channels -- one chain or two; conv_4's 1024 are four blocks and its rows rank nothing --, clouds of at least 32 points)
+    on 16-byte aligned fp32 rows"""
+    return (_takes("hsp_exact_layer_takes", N, Cin, C)
             and all(t is None or (t.dtype == torch.float32 and _al16(t)) for t in tensors))
 
 
@@ -1780,7 +1798,7 @@ class _SurfaceLayer(torch.autograd.Function):
         g2, F2, x2 = g.view(B * N, C), F3.view(B * N, C), xyz.view(B * N, 3)
         Wb = w_conv2[:, C:]
         g_conv2 = torch.empty_like(w_conv2)
-        own_ste = _ste_moments_ok(C) and (f32 or B <= 64)
+        own_ste = _ste_moments_ok(C) and (f32 or _takes("hsp_small_outer_takes", B))
         small = f32 and own_ste and _orl_bwd_small_ok(B, N, C, True)
         if small:
             # the same chain (column sums + coordinate moments, gWb with the STE rider, gt Wb / N) in two launches
@@ -1903,7 +1921,7 @@ class _LinearRows(torch.autograd.Function):
             gwt, gbp = wgrad(x2, gp, colsum=True)
             gw, gb = gwt[:, :Cout].t(), gbp[:Cout]
         else:
-            if R <= 64 and g.stride(1) == 1 and x2.stride(1) == 1:
+            if _takes("hsp_small_outer_takes", R) and g.stride(1) == 1 and x2.stride(1) == 1:
                 gw = _tiny_tn(g, x2, torch.empty(Cout, Cin, dtype=torch.float32, device=g.device))   # per-cloud rows (the towers' conv4)
             else:
                 gw = wgrad(g, x2)
@@ -2296,11 +2314,12 @@ def bn_relu(x, bn, relu=True, out_dtype=None, fork=False, partial=None):
     TWICE (two tensors over the same rows) for a tensor with two consumers -- their gradients then reach the BatchNorm backward
     separately and are added inside its kernels."""
     C = x.shape[-1]
+    takes = lambda: C > 0 and _takes("hsp_bn_takes", x.numel() // C, C)        # noqa: E731  (the BatchNorm kernels' widths)
     fused = (bn.training and bn.affine and bn.track_running_stats and bn.momentum is not None and x.is_cuda
-             and x.dtype in _FEAT_DTYPES and C % 4 == 0 and 256 % (C // 4) == 0)
+             and x.dtype in _FEAT_DTYPES and takes())
     want_bf16 = x.dtype == torch.bfloat16 or out_dtype == torch.bfloat16
     if not fused and want_bf16:                      # eval mode, bf16 rows out: running statistics, fused affine + ReLU
-        if bn.training or not bn.affine or C % 4 or 256 % (C // 4):
+        if bn.training or not bn.affine or not takes():
             raise HspError("bn_relu: this BatchNorm configuration is not built for bf16 rows")
         xc = _reqf(x, "bn_relu.x")
         y = torch.empty_like(xc, dtype=torch.bfloat16)
@@ -2330,6 +2349,11 @@ def bn_relu(x, bn, relu=True, out_dtype=None, fork=False, partial=None):
 # row gather
 # ------------------------------------------------------------------------------------------------
 
+def _csr_takes(g, C, gstride):
+    """True where ``hsp_gather_rows_bwd_csr(_bf16)`` takes the C-column gradient (segment) g at row stride ``gstride``"""
+    return _takes("hsp_gather_rows_bwd_csr_takes", _es(g), C, gstride, g.data_ptr() % 16)
+
+
 class _GatherRows(torch.autograd.Function):
     @staticmethod
     def forward(ctx, feat, idx):
@@ -2358,7 +2382,7 @@ class _GatherRows(torch.autograd.Function):
             g = g.contiguous()
             gstride = C
         gfeat = torch.empty(B, Nsrc, C, dtype=torch.float32, device=g.device)
-        if FLAGS.reproducible and not shared and _AssembleFeat._csr_ok(g, C, gstride, 4) and 4 * (Nsrc + 1) <= _REV_BUILD_LDS:
+        if FLAGS.reproducible and not shared and _csr_takes(g, C, gstride) and _takes("hsp_rev_build_takes", Nsrc):
             # the gather form over the reverse map (ascending query order) wherever both entries take the operands -- a per-cloud
             # map, the widths / strides / alignment of the concat backward's segments, a cloud whose histogram the reverse build
             # holds --, decided before anything is launched; today's launch otherwise
@@ -2472,11 +2496,6 @@ class _AssembleFeat(torch.autograd.Function):
         return out
 
     @staticmethod
-    def _csr_ok(gs, w, W, es):
-        """segment shapes the gather form over the reverse map takes"""
-        return w % 2 == 0 and W % 2 == 0 and (w // 2 >= 256 or 256 % (w // 2) == 0) and gs.data_ptr() % (2 * es) == 0
-
-    @staticmethod
     def backward(ctx, g):
         if not g.is_contiguous():
             g = g.contiguous()
@@ -2490,7 +2509,7 @@ class _AssembleFeat(torch.autograd.Function):
             for s_, (kd, w) in enumerate(zip(ctx.kinds, ctx.widths)):
                 idx = next(it) if ctx.has_idx[s_] else None
                 gs = g[:, :, col:col + w]
-                if kd == 1 and ctx.needs_input_grad[2 + s_] and _AssembleFeat._csr_ok(gs, w, W, es):
+                if kd == 1 and ctx.needs_input_grad[2 + s_] and _csr_takes(gs, w, W):
                     todo.append((s_, idx, ctx.nsrc[s_], w, gs))
                 col += w
             if 2 <= len(todo) <= 4:
@@ -2521,7 +2540,7 @@ class _AssembleFeat(torch.autograd.Function):
                 idx = saved.pop(0)
                 Ns = ctx.nsrc[s_]
                 gfeat = torch.empty(B, Ns, w, dtype=g.dtype, device=g.device)
-                if _AssembleFeat._csr_ok(gs, w, W, es):
+                if _csr_takes(gs, w, W):
                     # gather form over the reverse map (memoised on idx: fm_2 and fm_3 share one); deterministic
                     off, edge = rev_index(idx, 1, Ns)
                     _run("hsp_gather_rows_bwd_csr" + _sfx(g), (_p(gs), W, _p(off), _p(edge), B, Ns, N, w, _p(gfeat), _stream()),
@@ -2606,9 +2625,6 @@ def fps(xyz, n_samples):
     return sel
 
 
-FPS_LEVELS_MAX_N = 12288      # hsp_fps_levels_f32: the register-resident kernel's range
-
-
 def fps_levels(vertices, n1, n2):
     """Pool_layer's farthest-point sampler for both levels in one launch (hsp_fps_levels_f32): (sel1 int32 (B,n1), v1 (B,n1,3),
     v2 (B,n2,3)) -- the rows ``fps`` picks per cloud with one rule added, a picked row is never picked again (so a tiled cloud
@@ -2621,8 +2637,8 @@ def fps_levels(vertices, n1, n2):
     n1, n2 = int(n1), int(n2)
     if not (0 < n1 <= N and 0 <= n2 <= n1):
         raise HspError(f"fps_levels: need 0 < n1 <= N and 0 <= n2 <= n1, got N={N}, n1={n1}, n2={n2}")
-    if N > FPS_LEVELS_MAX_N:
-        raise HspError(f"fps_levels: N={N} is beyond the sampler's range (N <= {FPS_LEVELS_MAX_N}); there is no other "
+    if not _takes("hsp_fps_levels_takes", N):
+        raise HspError(f"fps_levels: N={N} is beyond the sampler's range (hsp_fps_levels_takes); there is no other "
                        "farthest-point form that never re-picks a row, and no fall-back to random sampling")
     sel1 = torch.empty(B, n1, dtype=torch.int32, device=x.device)
     v1 = torch.empty(B, n1, 3, dtype=torch.float32, device=x.device)

@@ -87,7 +87,7 @@ def _b(t, name):
 def _bn_fwd(y, bn):
     """relu(bn(y)) for fp32 rows y (R, C) -> (bf16 rows, saved mean, saved invstd); eval mode: running statistics (no saved)"""
     R, C = y.shape
-    if not _bn_ok(bn, C):
+    if not _bn_ok(bn, R, C):
         raise HspError("bf16 heads: this BatchNorm configuration is not built")
     a = torch.empty(R, C, dtype=BF16, device=y.device)
     if not bn.training:
@@ -118,8 +118,8 @@ def _eval_invstd(bn):
     return inv
 
 
-def _bn_ok(bn, C):
-    return bn.affine and bn.track_running_stats and bn.momentum is not None and C % 4 == 0 and 256 % (C // 4) == 0
+def _bn_ok(bn, R, C):
+    return bn.affine and bn.track_running_stats and bn.momentum is not None and ops._takes("hsp_bn_takes", R, C)
 
 
 def _product_bn(x, Wc, b, bn, out_cols, cloud_bias=None, rows_per_cloud=0, xyz3=None, w3=None):
@@ -132,7 +132,7 @@ def _product_bn(x, Wc, b, bn, out_cols, cloud_bias=None, rows_per_cloud=0, xyz3=
     y = torch.empty(R, C, dtype=torch.float32, device=x.device)
     L = lib()
     tiles = L.hsp_gemm_rows_bn_tiles_bf16(R, C, K)
-    if not (bn.training and _bn_ok(bn, C) and 0 < tiles <= 512):
+    if not (bn.training and _bn_ok(bn, R, C) and tiles > 0):
         ops.gemm_rows(x, Wc, bias=b, cloud_bias=cloud_bias, rows_per_cloud=rows_per_cloud, xyz3=xyz3, w3=w3, out=y)
         return (y,) + tuple(_bn_fwd(y, bn))
     buf = torch.empty(1 + 2 * tiles, C, dtype=torch.float32, device=x.device)

@@ -66,8 +66,12 @@ int hsp_knn_f32(const float *x, int B, int N, int C, int k, int drop_first, int3
  * The search flags the rows that hold two equal distances among their k + drop_first + 1 nearest and a fixed-grid pass replays only
  * those (round 5; while B N N floats stay below 512 MB the search also leaves the distance matrix in ws, so a replayed row reads its
  * distances instead of recomputing ~0.5 MB of feature rows).
- * ws: hsp_knn_exact_workspace_bytes; tie_rows (may be NULL): a device int that is incremented once per row that held a tie. */
+ * ws: hsp_knn_exact_workspace_bytes; tie_rows (may be NULL): a device int that is incremented once per row that held a tie.
+ * hsp_knn_exact_takes: 1 where hsp_knn_exact_f32 runs the search -- the function that entry point itself declines by, before its
+ * first launch: the list length above and the replay's LDS row (N candidates and, for C != 3, the query's C columns; C == 3:
+ * hsp_knn_xyz_takes) -- else 0; the caller then takes hsp_knn_f32. */
 size_t hsp_knn_exact_workspace_bytes(int B, int N, int C, int k, int drop_first);
+int hsp_knn_exact_takes(int B, int N, int C, int k, int drop_first);
 int hsp_knn_exact_f32(const float *x, int B, int N, int C, int k, int drop_first, int quad_mode, int32_t *idx, void *ws,
                       size_t ws_bytes, int *tie_rows, hspStream_t stream);
 /* get_neighbor_index on COORDINATES (C == 3), torch.topk's order among equal distances included, for up to two list lengths of
@@ -81,8 +85,11 @@ int hsp_knn_exact_f32(const float *x, int B, int N, int C, int k, int drop_first
  * caller falls back on hsp_knn_f32's (distance, index) order).
  * ws: hsp_knn_xyz_workspace_bytes (the row flags); tie_rows (may be NULL): device int, += number of flagged rows -- counted by
  * the SEPARATE replay pass only: for N <= 576 with B N < 131 072 the selection kernel replays its flagged rows inline and leaves
- * tie_rows untouched. */
+ * tie_rows untouched.
+ * hsp_knn_xyz_takes: 1 where hsp_knn_xyz_f32 runs the search (k + drop_first + 1 <= 33, N <= 10 240) -- the function that entry
+ * point itself declines by -- else 0. */
 size_t hsp_knn_xyz_workspace_bytes(int B, int N);
+int hsp_knn_xyz_takes(int B, int N, int k, int drop_first);
 int hsp_knn_xyz_f32(const float *xyz, int B, int N, int k, int k2, int drop_first, int32_t *idx, int32_t *idx2, void *ws,
                     size_t ws_bytes, int *tie_rows, hspStream_t stream);
 /* The coordinate work of the stack's two coarse levels in ONE launch (FaceRecon.py:91-101, gcn3d.py:236,243-245).  Pool_layer keeps
@@ -94,14 +101,19 @@ int hsp_knn_xyz_f32(const float *xyz, int B, int N, int k, int k2, int drop_firs
  *   up1, up2 (B,N0)                               get_nearest_index(vertices, v1 / v2)
  * Four independent small searches that cost a launch each (6-13 us, mostly latency); here they are block ranges of one grid.  Same
  * results as hsp_knn_xyz_f32 / hsp_nn1_f32 (torch.topk's order among equal distances included).  64 <= N2 <= N1 <= 576, else
- * HSP_ERR_UNSUPPORTED (the caller keeps the separate calls). */
+ * HSP_ERR_UNSUPPORTED (the caller keeps the separate calls).  hsp_geometry_levels_takes: 1 where the entry point runs the shapes
+ * (the levels' sizes, k + drop_first + 1 <= 33 per list, the kernel's LDS) -- the function that entry point itself declines by. */
+int hsp_geometry_levels_takes(int N0, int N1, int N2, int k1, int kpool, int k2, int drop_first);
 int hsp_geometry_levels_f32(const float *xyz, int B, int N0, const int32_t *sel1, int N1, const int32_t *sel2, int N2, int k1,
                             int kpool, int k2, int drop_first, float *v1, float *v2, int32_t *idx1, int32_t *idx1_pool,
                             int32_t *idx2, int32_t *up1, int32_t *up2, hspStream_t stream);
 /* hsp_knn_xyz_f32 on the input cloud (idx0 (B,N0,k0), idx0_pool (B,N0,kpool0)) AND hsp_geometry_levels_f32 in two launches instead of
  * three: the level-0 search's tie pass depends on that search's flags only, so it rides in the levels' launch as a further block
  * range (a flagged row is ~14 us of latency during which the chip would otherwise idle).  576 < N0 <= 1088 and the levels' limits,
- * else HSP_ERR_UNSUPPORTED (the caller keeps the separate calls).  ws: hsp_geometry_all_workspace_bytes (the level-0 flags). */
+ * else HSP_ERR_UNSUPPORTED (the caller keeps the separate calls).  ws: hsp_geometry_all_workspace_bytes (the level-0 flags).
+ * hsp_geometry_all_takes: 1 where the entry point runs the shapes (hsp_geometry_levels_takes, the range of N0, B N0 < 131 072, the
+ * LDS with the tie pass's rows) -- the function that entry point itself declines by, before its first launch. */
+int hsp_geometry_all_takes(int B, int N0, int k0, int kpool0, int N1, int N2, int k1, int kpool, int k2, int drop_first);
 size_t hsp_geometry_all_workspace_bytes(int B, int N0);
 int hsp_geometry_all_f32(const float *xyz, int B, int N0, int k0, int kpool0, const int32_t *sel1, int N1, const int32_t *sel2, int N2,
                          int k1, int kpool, int k2, int drop_first, int32_t *idx0, int32_t *idx0_pool, float *v1, float *v2,
@@ -206,6 +218,9 @@ int hsp_rf_conv_bwd(const float *xyz, const float *dirs, const float *fm, const 
  * rev_off (B,Nsrc+1), rev_edge (B,Nq*k): for source row m the ascending edge ids e = i*k + n with
  * idx[b,i,n] == m are rev_edge[b][rev_off[b][m] .. rev_off[b][m+1]).
  */
+/* 1 where hsp_rev_build, hsp_rev_build_sel and (per map) hsp_rev_build_multi take a cloud of n_src source rows: its histogram of
+ * n_src + 1 counters within 140 KB of LDS (n_src <= 35 839) -- the function those entry points themselves decline by */
+int hsp_rev_build_takes(int n_src);
 int hsp_rev_build(const int32_t *idx, int B, int Nq, int Nsrc, int k, int kstride, int32_t *rev_off,
                   int32_t *rev_edge, hspStream_t stream);
 /* nmaps <= 4 such indices over the same B clouds in ONE launch (map i: idx[i], Nq[i], Nsrc[i], k[i], kstride[i] ->
@@ -345,12 +360,20 @@ int hsp_bn_eval_f32(const float *x, long long R, int C, const float *running_mea
  * two_chain == 1: out = (((chain(F Wa^T)) + cloud_t[cloud]) + F) + tail with cloud_t (B,C) = chain(fg Wb^T) from
  * hsp_gemm_wave_f32.  tail = ste (M,C) (the STE product) or the K = 3 chain xyz3 . w3 (surface layer; relu allowed).
  * C % 32 == 0, 16-byte aligned rows, rows_per_cloud >= 32. */
+/* 1 where the reference-order entry points of one HS layer -- hsp_gemm_wave_f32 for the fm and STE products (Cin != 3),
+ * hsp_orl_global_exact_f32, hsp_layer_out_exact_f32 with two_chain = (2 C > 256) -- all take a cloud of N points with Cin input and C
+ * output channels: the function hsp_layer_out_exact_f32 itself declines by for its own part (its plan, C <= 256 in one or two
+ * chains, rows_per_cloud >= 32), with the other two entry points' shape rules */
+int hsp_exact_layer_takes(int N, int Cin, int C);
 int hsp_layer_out_exact_f32(const float *F, int ldf, const float *Wa, int ldwa, const float *fg, int ldfg, const float *Wb,
                             int ldwb, const float *cloud_t, int two_chain, const float *ste, int ldste, const float *xyz3,
                             const float *w3, int relu, int M, int C, int rows_per_cloud, float *out, int ldo,
                             hspStream_t stream);
 /* out (B,C) = sum_i x[b,i,:]  (the per-cloud column sum autograd takes of a gradient that was
  * broadcast over the points, e.g. d/d(fg Wb^T)); deterministic two-stage.  ws as above. */
+/* 1 where hsp_colsum_rows (elem_bytes 4) / hsp_colsum_rows_bf16 (2) take rows of C columns: C a multiple of 4 with C/4 | 256, fp32
+ * rows also any C <= 256 -- the function those entry points themselves decline by */
+int hsp_colsum_rows_takes(int C, int elem_bytes);
 int hsp_colsum_rows(const float *x, int B, int N, int C, float *out, void *ws, size_t ws_bytes,
                     hspStream_t stream);
 
@@ -387,6 +410,10 @@ int hsp_gather_rows_bwd(const float *grad_out, int grad_stride, const int32_t *i
 /* the same backward in gather form over (rev_off, rev_edge) = hsp_rev_build(idx as (B,Nq,1), k = 1): every source row
  * sums its queries' gradient rows in ascending query order (no atomics, bit-reproducible), whole row segments at
  * a time -- the faster form when grad_out is a column block of a much wider tensor (the 1286-wide feature). */
+/* 1 where hsp_gather_rows_bwd_csr(_bf16) takes a gradient of C columns of elem_bytes each at row stride grad_stride (elements)
+ * whose address is grad_align modulo 16: even C and stride, a 2-element-aligned address, C/2 >= 256 or C/2 | 256 -- the function
+ * those entry points themselves decline by; hsp_gather_rows_bwd_csr_multi(_bf16) asks it once per segment */
+int hsp_gather_rows_bwd_csr_takes(int elem_bytes, int C, int grad_stride, int grad_align);
 int hsp_gather_rows_bwd_csr(const float *grad_out, int grad_stride, const int32_t *rev_off, const int32_t *rev_edge,
                             int B, int Nsrc, int Nq, int C, float *grad_feat, hspStream_t stream);
 /* nseg <= 4 such gathers out of ONE gradient tensor (row pitch grad_stride, Nq rows per cloud; segment s: grad_out[s] = the
@@ -503,11 +530,16 @@ int hsp_gemm_x3_bias_bn_f32(const float *A1, int lda1, const hsp_bf16_t *P1, int
  *   hsp_small_outer_f32: out (Ma, Nb) = a^T c over the B <= 64 rows of a (B, Ma), c (B, Nb) (gWb = gt^T fg) */
 int hsp_small_rows_f32(const float *A, int lda, const float *W, int ldw, int w_layout, int M, int N, int K, float alpha,
                        float *out, int ldo, hspStream_t stream);
+/* 1 where hsp_small_outer_f32 takes B per-cloud rows (one row per lane: B <= 64) -- the function that entry point itself declines by */
+int hsp_small_outer_takes(int B);
 int hsp_small_outer_f32(const float *a, int lda, const float *c, int ldc, int B, int Ma, int Nb, float *out, int ldo,
                         const float *mom, int ldm, int Cm, float *gste, hspStream_t stream);
 /* (mom != NULL: the same launch also writes gste (Cm, 3) = sum over the B rows of mom (B, >= 3 Cm) [j * Cm + c] -- the STE weight
  * gradient of HSlayer_surface, g^T xyz (gcn3d.py:85), from the per-cloud coordinate moments of hsp_colsum_rows_xyz:
  * out4 (B, 4, C), slot 0 = sum_i g[b][i][:], slots 1..3 = sum_i g[b][i][:] * xyz[b][i][0..2]; ws >= 4 * hsp_orl_workspace_bytes) */
+/* 1 where hsp_colsum_rows_xyz(_bf16) takes rows of C columns (C a multiple of 4 with C/4 | 256) -- the function those entry points
+ * themselves decline by */
+int hsp_colsum_rows_xyz_takes(int C);
 int hsp_colsum_rows_xyz(const float *x, const float *xyz, int B, int N, int C, float *out4, void *ws, size_t ws_bytes,
                         hspStream_t stream);
 int hsp_colsum_rows_xyz_bf16(const hsp_bf16_t *x, const float *xyz, int B, int N, int C, float *out4, void *ws, size_t ws_bytes,
@@ -524,6 +556,9 @@ int hsp_colsum_rows_xyz_bf16(const hsp_bf16_t *x, const float *xyz, int B, int N
  *                         one launch.  Ma a multiple of 128 and <= 2048, B <= 64; other shapes: HSP_ERR_UNSUPPORTED */
 int hsp_colsum_cloud_ok(int B, int N, int C, int with_xyz);
 int hsp_colsum_cloud_f32(const float *x, const float *xyz, int B, int N, int C, float *out, hspStream_t stream);
+/* 1 where hsp_small_pair_f32 takes B per-cloud rows of Ma columns (B <= 64, Ma a multiple of 128 up to 2048) -- the function that
+ * entry point itself declines by */
+int hsp_small_pair_takes(int B, int Ma);
 int hsp_small_pair_f32(const float *gt, int ldgt, int B, int Ma, const float *W, int ldw, int Nn, float alpha, float *out_nn,
                        int ldnn, const float *c, int ldc, int Nb, float *out_o, int ldo, const float *mom, int ldm, int Cm,
                        float *gste, hspStream_t stream);
@@ -663,6 +698,9 @@ int hsp_wgrad_partial_f32(const float *A, int lda, const float *B, int ldb, int 
  * s its OWN first row (read again from x by the fold, so the workspace holds no third row) and the chunks are merged as
  * (n, mean, M2) in a fixed order -- deterministic, and a row far from its column's mean costs no digits of the variance.
  */
+/* 1 where the BatchNorm entry points below (hsp_bn_relu_fwd*, _apply*, _bwd*) take R rows of C channels: C a multiple of 4 with
+ * C/4 | 256 -- the function those entry points themselves decline by */
+int hsp_bn_takes(int R, int C);
 size_t hsp_bn_workspace_bytes(int R, int C);
 int hsp_bn_relu_fwd(const float *x, int R, int C, const float *gamma, const float *beta, float eps,
                     float momentum, int relu, float *y, float *save_mean, float *save_invstd,
@@ -928,6 +966,9 @@ int hsp_fps_f64(const double *xyz, int B, int N, int n_samples, int32_t *sel, vo
  * names N1 different rows.  v1 (B,N1,3) = xyz[b, sel1[b]] in pick order.  Farthest-point picks are nested: the same sampler run on
  * v1 returns 0 .. N2-1, so the second level is a prefix, and v2 (B,N2,3) = v1[:, :N2] is written here as well (N2 == 0: v2 may be
  * NULL).  0 < N1 <= N0, 0 <= N2 <= N1.  N0 > 12288 (beyond the register-resident kernel): HSP_ERR_UNSUPPORTED, nothing launched. */
+/* 1 where hsp_fps_levels_f32 takes a cloud of N0 points (the register-resident kernel: N0 <= 12 288) -- the function that entry
+ * point itself declines by */
+int hsp_fps_levels_takes(int N0);
 int hsp_fps_levels_f32(const float *xyz, int B, int N0, int N1, int N2, int32_t *sel1, float *v1, float *v2,
                        hspStream_t stream);
 
@@ -999,7 +1040,8 @@ int hsp_gemm_rows_acc_bf16(const hsp_bf16_t *A1, int lda1, const hsp_bf16_t *B1,
                            int ldc, int c_is_f32, void *ws, size_t ws_bytes, hspStream_t stream);
 /* bf16 product with the BatchNorm first pass in its epilogue: C (fp32) = A B^T + bias (+ cloud_bias[row / rows_per_cloud])
  * (+ xyz3 . w3), bn_shift[n] = bias[n] + cloud_bias[0][n], bn_part[tiles][2][N] = per row tile sum (c - shift), sum (c - shift)^2
- * (the layout of hsp_gemm_x3_bias_bn_f32), tiles = hsp_gemm_rows_bn_tiles_bf16(M, N, K) <= 512; fold with
+ * (the layout of hsp_gemm_x3_bias_bn_f32), tiles = hsp_gemm_rows_bn_tiles_bf16(M, N, K), which is 0 where the fold cannot take
+ * that many (more than 512) and the entry point declines; fold with
  * hsp_bn_relu_fwd_partials_mixed (bf16 rows out) or hsp_bn_relu_fwd_partials */
 int hsp_gemm_rows_bn_tiles_bf16(int M, int N, int K);
 int hsp_gemm_rows_bn_bf16(const hsp_bf16_t *A, int lda, const hsp_bf16_t *B, int ldb, int K, int M, int N, const float *bias,
