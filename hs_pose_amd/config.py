@@ -52,6 +52,10 @@ class _Flags:
                                 # draws (step_draws) the heads' Dropout mask is a keyed draw (ops.dropout_keyed) instead of a draw
                                 # on torch's device generator.  Read when a call is issued: a captured graph keeps the form it
                                 # was captured with.  DESIGN.md section 8g
+        prop_sym_cd_w=0.0,      # (not in the reference) weight of 'Prop_sym_cd', a Chamfer term between the reconstruction and the
+                                # mirrored observed cloud AS SETS (losses.prop_rot_loss, ops.recon_chamfer), beside the point-by-point
+                                # L1 of 'Prop_sym_recon': 0 -- the reference's 19 terms, the key absent -- or > 0 -- a 20th term
+                                # with an ordered, atomic-free backward.  No accuracy claim.  DESIGN.md section 8h
     )
 
     def __init__(self):

@@ -8,6 +8,7 @@
 // from the problem instead of a fixed dim3(32,16).
 // FPS: replaces tools/eval_utils.py:107-119 (per cloud): start at 0, running min, first max wins.
 #include "common.h"
+#include "sym_target.h"
 
 namespace hsp {
 
@@ -16,26 +17,18 @@ namespace hsp {
 // 64 queries per workgroup (lane = query); the 4 waves scan the 4 quarters of every staged chunk and the partial
 // (distance, index) pairs meet in LDS -- lexicographic minimum == the first minimum of a serial scan.  With one wave per
 // 64 queries a 1028-point cloud pair gives 272 waves for 1024 SIMDs; this form gives 1088.
-__global__ __launch_bounds__(256) void chamfer_nn_kernel(const float* __restrict__ a, int n,
-                                                         const float* __restrict__ c, int m,
-                                                         float* __restrict__ dist, int32_t* __restrict__ idx) {
-    __shared__ float4 pts[CH_CHUNK];
-    __shared__ float sd[4][64];
-    __shared__ int si[4][64];
-    const int b = blockIdx.y;
+// The scan itself, shared by chamfer_nn_kernel and recon_chamfer_nn_kernel: cand(j) is candidate j of the cloud (a float4, .w unused),
+// (x1, y1, z1) the lane's query.  Returns true on the lanes of wave 0, which then hold the query's (distance, first arg-min).
+template <class Cand>
+__device__ __forceinline__ bool chamfer_scan(float4* pts, float (*sd)[64], int (*si)[64], const Cand& cand, int m, float x1,
+                                             float y1, float z1, float& bd, int& bi) {
     const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int i = blockIdx.x * 64 + lane;
-    const float* ab = a + (size_t)b * n * 3;
-    const float* cb = c + (size_t)b * m * 3;
-    float x1 = 0.f, y1 = 0.f, z1 = 0.f;
-    if (i < n) { x1 = ab[i * 3]; y1 = ab[i * 3 + 1]; z1 = ab[i * 3 + 2]; }
     float best = INFINITY;
     int besti = INT_MAX;
     for (int c0 = 0; c0 < m; c0 += CH_CHUNK) {
         const int cn = min(CH_CHUNK, m - c0);
         __syncthreads();
-        for (int j = threadIdx.x; j < cn; j += 256)
-            pts[j] = make_float4(cb[(c0 + j) * 3], cb[(c0 + j) * 3 + 1], cb[(c0 + j) * 3 + 2], 0.f);
+        for (int j = threadIdx.x; j < cn; j += 256) pts[j] = cand(c0 + j);
         __syncthreads();
         const int q = (cn + 3) >> 2;
         const int j0 = wv * q, j1 = min(cn, j0 + q);
@@ -61,24 +54,240 @@ __global__ __launch_bounds__(256) void chamfer_nn_kernel(const float* __restrict
     sd[wv][lane] = best;
     si[wv][lane] = besti;
     __syncthreads();
-    if (wv == 0 && i < n) {
-        // lexicographic minimum of the partial (distance, index) pairs == the serial scan's first minimum
-        float bd = sd[0][lane];
-        int bi = si[0][lane];
+    if (wv != 0) return false;
+    // lexicographic minimum of the partial (distance, index) pairs == the serial scan's first minimum
+    bd = sd[0][lane];
+    bi = si[0][lane];
 #pragma unroll
-        for (int w = 1; w < 4; ++w) {
-            const float d = sd[w][lane];
-            const int k = si[w][lane];
-            if (d < bd || (d == bd && k < bi)) { bd = d; bi = k; }
-        }
-        if (bi == INT_MAX) {        // nothing compared below +inf (NaN / overflowing input): the reference keeps candidate 0
-            const float dx = sub_rn(cb[0], x1), dy = sub_rn(cb[1], y1), dz = sub_rn(cb[2], z1);
-            bd = add_rn(add_rn(mul_rn(dx, dx), mul_rn(dy, dy)), mul_rn(dz, dz));
-            bi = 0;
-        }
+    for (int w = 1; w < 4; ++w) {
+        const float d = sd[w][lane];
+        const int k = si[w][lane];
+        if (d < bd || (d == bd && k < bi)) { bd = d; bi = k; }
+    }
+    if (bi == INT_MAX) {        // nothing compared below +inf (NaN / overflowing input): the reference keeps candidate 0
+        const float4 p = cand(0);
+        const float dx = sub_rn(p.x, x1), dy = sub_rn(p.y, y1), dz = sub_rn(p.z, z1);
+        bd = add_rn(add_rn(mul_rn(dx, dx), mul_rn(dy, dy)), mul_rn(dz, dz));
+        bi = 0;
+    }
+    return true;
+}
+
+struct CandRows {                  // the candidates of a cloud as they lie in memory
+    const float* cb;
+    __device__ __forceinline__ float4 operator()(int j) const { return make_float4(cb[j * 3], cb[j * 3 + 1], cb[j * 3 + 2], 0.f); }
+};
+
+__global__ __launch_bounds__(256) void chamfer_nn_kernel(const float* __restrict__ a, int n,
+                                                         const float* __restrict__ c, int m,
+                                                         float* __restrict__ dist, int32_t* __restrict__ idx) {
+    __shared__ float4 pts[CH_CHUNK];
+    __shared__ float sd[4][64];
+    __shared__ int si[4][64];
+    const int b = blockIdx.y;
+    const int i = blockIdx.x * 64 + (threadIdx.x & 63);
+    const float* ab = a + (size_t)b * n * 3;
+    float x1 = 0.f, y1 = 0.f, z1 = 0.f;
+    if (i < n) { x1 = ab[i * 3]; y1 = ab[i * 3 + 1]; z1 = ab[i * 3 + 2]; }
+    float bd;
+    int bi;
+    if (chamfer_scan(pts, sd, si, CandRows{c + (size_t)b * m * 3}, m, x1, y1, z1, bd, bi) && i < n) {
         dist[(size_t)b * n + i] = bd;
         idx[(size_t)b * n + i] = bi;
     }
+}
+
+// ---- the Chamfer reconstruction term (hsp_recon_chamfer_fwd / _bwd; include/hsp.h) ---------------------------------------------
+// One launch searches both directions: workgroup x < nb of cloud b holds 64 rows of the reconstruction P = recon[b] as queries and
+// scans the target G[b], which it makes from PC[b] while it stages a chunk (sym_target.h: the rule of the loss kernels'
+// Prop_sym_recon; ~30 flops per candidate against 64 distances); workgroup x >= nb holds 64 rows of G as queries -- made by the same
+// function, so the same bits -- writes them out and scans P.  A skip cloud is not searched: G = 0, distances 0, arg-mins 0.
+struct ReconCloud {
+    SymClass k;
+    float R[9], t[3];
+};
+struct CandTarget {                // candidate j = the target of observed point j
+    const float* pc;
+    const ReconCloud* c;
+    __device__ __forceinline__ float4 operator()(int j) const {
+        const float P[3] = {pc[j * 3], pc[j * 3 + 1], pc[j * 3 + 2]};
+        float canon[3], T[3];
+        sym_canon(c->R, c->t, P, canon);
+        sym_recon_target(c->k, c->R, c->t, P, canon, T);
+        return make_float4(T[0], T[1], T[2], 0.f);
+    }
+};
+
+__global__ __launch_bounds__(256) void recon_chamfer_nn_kernel(const float* __restrict__ PC, const float* __restrict__ gt_R,
+                                                               const float* __restrict__ gt_t, const float* __restrict__ sym,
+                                                               const float* __restrict__ recon, int N, int nb,
+                                                               float* __restrict__ G, int32_t* __restrict__ idx1,
+                                                               int32_t* __restrict__ idx2, float* __restrict__ d1,
+                                                               float* __restrict__ d2) {
+    __shared__ float4 pts[CH_CHUNK];
+    __shared__ float sd[4][64];
+    __shared__ int si[4][64];
+    const int b = blockIdx.y;
+    const bool dir2 = (int)blockIdx.x >= nb;                  // workgroup-uniform
+    const int i = ((int)blockIdx.x - (dir2 ? nb : 0)) * 64 + (threadIdx.x & 63);
+    const size_t row = (size_t)b * N + i;
+    ReconCloud c;
+    c.k = sym_class(sym + b * 4);
+    for (int e = 0; e < 9; ++e) c.R[e] = gt_R[b * 9 + e];
+    for (int e = 0; e < 3; ++e) c.t[e] = gt_t[b * 3 + e];
+    const float* pc = PC + (size_t)b * N * 3;
+    const float* re = recon + (size_t)b * N * 3;
+    float* dist = dir2 ? d2 : d1;
+    int32_t* idx = dir2 ? idx2 : idx1;
+    if (c.k.skip) {                                           // (the whole workgroup: no barrier is left waiting)
+        if (threadIdx.x < 64 && i < N) {
+            dist[row] = 0.f;
+            idx[row] = 0;
+            if (dir2) { G[row * 3] = 0.f; G[row * 3 + 1] = 0.f; G[row * 3 + 2] = 0.f; }
+        }
+        return;
+    }
+    const CandTarget target{pc, &c};
+    float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (i < N) q = dir2 ? target(i) : CandRows{re}(i);
+    float bd;
+    int bi;
+    const bool mine = dir2 ? chamfer_scan(pts, sd, si, CandRows{re}, N, q.x, q.y, q.z, bd, bi)
+                           : chamfer_scan(pts, sd, si, target, N, q.x, q.y, q.z, bd, bi);
+    if (mine && i < N) {
+        dist[row] = bd;
+        idx[row] = bi;
+        if (dir2) { G[row * 3] = q.x; G[row * 3 + 1] = q.y; G[row * 3 + 2] = q.z; }
+    }
+}
+
+// term = (w * S) / (B N), S the sum of the E = 2 B N distances d[0 .. E) (d1 then d2, row-major) in ONE order: thread t of the
+// 1024 adds d[t], d[t + 1024], ... in that order starting from d[t] + 0; the 1024 partials then fold pairwise, s[t] += s[t + h]
+// for h = 512, 256, ..., 1.  Every operation rounded once.
+#define RC_SUM_THREADS 1024
+__global__ __launch_bounds__(RC_SUM_THREADS) void recon_chamfer_sum_kernel(const float* __restrict__ d, long long E, float w,
+                                                                           float bn, float* __restrict__ term) {
+    __shared__ float s[RC_SUM_THREADS];
+    const int t = threadIdx.x;
+    float acc = 0.f;
+    for (long long e = t; e < E; e += RC_SUM_THREADS) acc = add_rn(acc, d[e]);
+    s[t] = acc;
+    __syncthreads();
+    for (int h = RC_SUM_THREADS / 2; h > 0; h >>= 1) {
+        if (t < h) s[t] = add_rn(s[t], s[t + h]);
+        __syncthreads();
+    }
+    if (t == 0) term[0] = __fdiv_rn(mul_rn(w, s[0]), bn);
+}
+
+// ---- ordered backward: one output row per WAVE, its own term first, then the terms of the points that chose it in ascending
+// order of their index (the lists of hsp_rev_build, k = 1: edge id == the choosing point's index).  No atomics, no pre-zeroing.
+// The lanes fetch 64 of the row's terms at a time (the loads of a long list -- a hub row that a whole cloud chose -- are in
+// flight together instead of one dependent round trip each); every lane then adds them to the same accumulator in list order,
+// lane by lane, so the sum is the serial one whatever the list's length.
+#define CH_ROWS_PER_WG 4           // 256 threads
+
+template <class Term>              // term(j): the three addends that choosing point j contributes
+__device__ __forceinline__ void ordered_row_sum(float& ax, float& ay, float& az, const int32_t* __restrict__ off,
+                                                const int32_t* __restrict__ edge, int row, const Term& term) {
+    const int lane = threadIdx.x & 63;
+    const int e0 = __builtin_amdgcn_readfirstlane(off[row]), e1 = __builtin_amdgcn_readfirstlane(off[row + 1]);
+    for (int base = e0; base < e1; base += 64) {
+        float tx = 0.f, ty = 0.f, tz = 0.f;
+        if (base + lane < e1) term(edge[base + lane], tx, ty, tz);
+        const int cnt = min(64, e1 - base);                  // wave-uniform
+        for (int l = 0; l < cnt; ++l) {
+            ax = add_rn(ax, __int_as_float(__builtin_amdgcn_readlane(__float_as_int(tx), l)));
+            ay = add_rn(ay, __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ty), l)));
+            az = add_rn(az, __int_as_float(__builtin_amdgcn_readlane(__float_as_int(tz), l)));
+        }
+    }
+}
+
+// hsp_chamfer_bwd's arithmetic term by term: g = 2 gd, v = g (p - q); the chosen row receives -v (a - v == a + (-v) bit for bit)
+struct TermScatter {
+    const float* other;
+    const float* gd_other;
+    float px, py, pz;
+    __device__ __forceinline__ void operator()(int j, float& tx, float& ty, float& tz) const {
+        const float gj = mul_rn(gd_other[j], 2.0f);
+        tx = -mul_rn(gj, sub_rn(other[j * 3], px));
+        ty = -mul_rn(gj, sub_rn(other[j * 3 + 1], py));
+        tz = -mul_rn(gj, sub_rn(other[j * 3 + 2], pz));
+    }
+};
+__device__ __forceinline__ void chamfer_row_ordered(const float* __restrict__ own, const float* __restrict__ other, int i, int j0,
+                                                    float gd_own, const float* __restrict__ gd_other,
+                                                    const int32_t* __restrict__ off, const int32_t* __restrict__ edge,
+                                                    float* __restrict__ out) {
+    const float px = own[i * 3], py = own[i * 3 + 1], pz = own[i * 3 + 2];
+    const float g = mul_rn(gd_own, 2.0f);
+    float ax = mul_rn(g, sub_rn(px, other[j0 * 3])), ay = mul_rn(g, sub_rn(py, other[j0 * 3 + 1])),
+          az = mul_rn(g, sub_rn(pz, other[j0 * 3 + 2]));
+    ordered_row_sum(ax, ay, az, off, edge, i, TermScatter{other, gd_other, px, py, pz});
+    if ((threadIdx.x & 63) == 0) { out[i * 3] = ax; out[i * 3 + 1] = ay; out[i * 3 + 2] = az; }
+}
+
+// workgroups x < nb1: rows of gx1 over (off1, edge1) = the reverse of idx2 (n source rows); the others: rows of gx2 over
+// (off2, edge2) = the reverse of idx1 (m source rows)
+__global__ __launch_bounds__(256) void chamfer_grad_ordered_kernel(const float* __restrict__ x1, int n, const float* __restrict__ x2,
+                                                                   int m, const int32_t* __restrict__ idx1,
+                                                                   const int32_t* __restrict__ idx2, const float* __restrict__ gd1,
+                                                                   const float* __restrict__ gd2, const int32_t* __restrict__ off1,
+                                                                   const int32_t* __restrict__ edge1,
+                                                                   const int32_t* __restrict__ off2,
+                                                                   const int32_t* __restrict__ edge2, int nb1,
+                                                                   float* __restrict__ gx1, float* __restrict__ gx2) {
+    const int b = blockIdx.y;
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const float* a = x1 + (size_t)b * n * 3;
+    const float* c = x2 + (size_t)b * m * 3;
+    if ((int)blockIdx.x < nb1) {
+        const int i = blockIdx.x * CH_ROWS_PER_WG + wv;
+        if (i >= n) return;
+        chamfer_row_ordered(a, c, i, idx1[(size_t)b * n + i], gd1[(size_t)b * n + i], gd2 + (size_t)b * m,
+                            off1 + (size_t)b * (n + 1), edge1 + (size_t)b * m, gx1 + (size_t)b * n * 3);
+    } else {
+        const int j = ((int)blockIdx.x - nb1) * CH_ROWS_PER_WG + wv;
+        if (j >= m) return;
+        chamfer_row_ordered(c, a, j, idx2[(size_t)b * m + j], gd2[(size_t)b * m + j], gd1 + (size_t)b * n,
+                            off2 + (size_t)b * (m + 1), edge2 + (size_t)b * n, gx2 + (size_t)b * m * 3);
+    }
+}
+
+// the term's own backward: gx[b,i] = s * [ (P_i - G_idx1[i]) + sum over the j that chose i, ascending, of (P_i - G_j) ],
+// s = 2 * ((g * w) / (B N)) applied once at the end; a skip cloud's rows are zeros
+struct TermRecon {
+    const float* Gb;
+    float px, py, pz;
+    __device__ __forceinline__ void operator()(int j, float& tx, float& ty, float& tz) const {
+        tx = sub_rn(px, Gb[j * 3]);
+        ty = sub_rn(py, Gb[j * 3 + 1]);
+        tz = sub_rn(pz, Gb[j * 3 + 2]);
+    }
+};
+__global__ __launch_bounds__(256) void recon_chamfer_grad_kernel(const float* __restrict__ recon, const float* __restrict__ G,
+                                                                 const int32_t* __restrict__ idx1, const float* __restrict__ sym,
+                                                                 const int32_t* __restrict__ off, const int32_t* __restrict__ edge,
+                                                                 const float* __restrict__ g, float w, float bn, int N,
+                                                                 float* __restrict__ gx) {
+    const int b = blockIdx.y;
+    const int i = blockIdx.x * CH_ROWS_PER_WG + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (i >= N) return;
+    const bool writer = (threadIdx.x & 63) == 0;
+    float* out = gx + ((size_t)b * N + i) * 3;
+    if (sym_class(sym + b * 4).skip) {
+        if (writer) { out[0] = 0.f; out[1] = 0.f; out[2] = 0.f; }
+        return;
+    }
+    const float* P = recon + (size_t)b * N * 3;
+    const float* Gb = G + (size_t)b * N * 3;
+    const float px = P[i * 3], py = P[i * 3 + 1], pz = P[i * 3 + 2];
+    const int j0 = idx1[(size_t)b * N + i];
+    float ax = sub_rn(px, Gb[j0 * 3]), ay = sub_rn(py, Gb[j0 * 3 + 1]), az = sub_rn(pz, Gb[j0 * 3 + 2]);
+    ordered_row_sum(ax, ay, az, off + (size_t)b * (N + 1), edge + (size_t)b * N, i, TermRecon{Gb, px, py, pz});
+    const float s = mul_rn(2.0f, __fdiv_rn(mul_rn(g[0], w), bn));
+    if (writer) { out[0] = mul_rn(s, ax); out[1] = mul_rn(s, ay); out[2] = mul_rn(s, az); }
 }
 
 // one direction of the backward: ga += g*(p-q), gc[idx] -= g*(p-q), g = 2*gd   (both pre-zeroed)
@@ -369,6 +578,97 @@ extern "C" int hsp_chamfer_bwd(const float* xyz1, const float* xyz2, const int32
     int rc = check_launch();
     if (rc) return rc;
     hipLaunchKernelGGL(chamfer_grad_kernel, dim3((m + 255) / 256, B), dim3(256), 0, st, xyz2, m, xyz1, n, idx2, gd2, gx2, gx1);
+    return check_launch();
+}
+
+// ---- ordered backward (no float atomics) ----------------------------------------------------------------------------------------
+// the grids put a cloud on blockIdx.y
+#define CH_MAX_CLOUDS 65535
+
+extern "C" int hsp_chamfer_bwd_ordered_ok(int B, int n, int m) {
+    return B > 0 && B <= CH_MAX_CLOUDS && hsp_rev_build_takes(n) && hsp_rev_build_takes(m) ? 1 : 0;
+}
+
+extern "C" size_t hsp_chamfer_bwd_ordered_workspace_bytes(int B, int n, int m) {
+    if (B <= 0 || n <= 0 || m <= 0) return 0;
+    return (size_t)B * (2 * ((size_t)n + m) + 2) * sizeof(int32_t);
+}
+
+extern "C" int hsp_chamfer_bwd_ordered(const float* xyz1, const float* xyz2, const int32_t* idx1, const int32_t* idx2,
+                                       const float* gd1, const float* gd2, int B, int n, int m, float* gx1, float* gx2, void* ws,
+                                       size_t ws_bytes, hspStream_t stream) {
+    if (!xyz1 || !xyz2 || !idx1 || !idx2 || !gd1 || !gd2 || (!gx1 && !gx2) || B <= 0 || n <= 0 || m <= 0 || !ws ||
+        ws_bytes < hsp_chamfer_bwd_ordered_workspace_bytes(B, n, m))
+        return HSP_ERR_BAD_ARG;
+    if (!hsp_chamfer_bwd_ordered_ok(B, n, m)) return HSP_ERR_UNSUPPORTED;      // (nothing launched)
+    // ws: off1 (B,n+1) | edge1 (B,m) -- the reverse of idx2, the lists of gx1's rows -- | off2 (B,m+1) | edge2 (B,n) -- of idx1
+    int32_t* off1 = reinterpret_cast<int32_t*>(ws);
+    int32_t* edge1 = off1 + (size_t)B * (n + 1);
+    int32_t* off2 = edge1 + (size_t)B * m;
+    int32_t* edge2 = off2 + (size_t)B * (m + 1);
+    int rc;
+    if (gx1 && gx2) {
+        const int32_t* idx[2] = {idx2, idx1};
+        const int nq[2] = {m, n}, ns[2] = {n, m}, one[2] = {1, 1};
+        int32_t* off[2] = {off1, off2};
+        int32_t* edge[2] = {edge1, edge2};
+        rc = hsp_rev_build_multi(2, idx, B, nq, ns, one, one, off, edge, stream);
+    } else if (gx1) {
+        rc = hsp_rev_build(idx2, B, m, n, 1, 1, off1, edge1, stream);
+    } else {
+        rc = hsp_rev_build(idx1, B, n, m, 1, 1, off2, edge2, stream);
+    }
+    if (rc) return rc;
+    const int nb1 = gx1 ? (n + CH_ROWS_PER_WG - 1) / CH_ROWS_PER_WG : 0, nb2 = gx2 ? (m + CH_ROWS_PER_WG - 1) / CH_ROWS_PER_WG : 0;
+    hipLaunchKernelGGL(chamfer_grad_ordered_kernel, dim3(nb1 + nb2, B), dim3(256), 0, as_stream(stream), xyz1, n, xyz2, m, idx1,
+                       idx2, gd1, gd2, off1, edge1, off2, edge2, nb1, gx1, gx2);
+    return check_launch();
+}
+
+// ---- the Chamfer reconstruction term ------------------------------------------------------------------------------------------
+extern "C" size_t hsp_recon_chamfer_fwd_workspace_bytes(int B, int N) {
+    if (B <= 0 || N <= 0) return 0;
+    return 2 * (size_t)B * N * sizeof(float);
+}
+
+extern "C" int hsp_recon_chamfer_fwd(const float* PC, const float* gt_R, const float* gt_t, const float* sym, const float* recon,
+                                     int B, int N, float w, float* term, float* G, int32_t* idx1, int32_t* idx2, void* ws,
+                                     size_t ws_bytes, hspStream_t stream) {
+    if (!PC || !gt_R || !gt_t || !sym || !recon || !term || !G || !idx1 || !idx2 || B <= 0 || N <= 0 || !isfinite(w) || !ws ||
+        ws_bytes < hsp_recon_chamfer_fwd_workspace_bytes(B, N))
+        return HSP_ERR_BAD_ARG;
+    if (B > CH_MAX_CLOUDS) return HSP_ERR_UNSUPPORTED;
+    hipStream_t st = as_stream(stream);
+    float* d1 = reinterpret_cast<float*>(ws);                  // ws: d1 (B,N) | d2 (B,N)
+    float* d2 = d1 + (size_t)B * N;
+    const int nb = (N + 63) / 64;
+    hipLaunchKernelGGL(recon_chamfer_nn_kernel, dim3(2 * nb, B), dim3(256), 0, st, PC, gt_R, gt_t, sym, recon, N, nb, G, idx1, idx2,
+                       d1, d2);
+    int rc = check_launch();
+    if (rc) return rc;
+    hipLaunchKernelGGL(recon_chamfer_sum_kernel, dim3(1), dim3(RC_SUM_THREADS), 0, st, d1, 2LL * B * N, w, (float)((long long)B * N),
+                       term);
+    return check_launch();
+}
+
+extern "C" size_t hsp_recon_chamfer_bwd_workspace_bytes(int B, int N) {
+    if (B <= 0 || N <= 0) return 0;
+    return (size_t)B * (2 * (size_t)N + 1) * sizeof(int32_t);
+}
+
+extern "C" int hsp_recon_chamfer_bwd(const float* recon, const float* G, const int32_t* idx1, const int32_t* idx2, const float* sym,
+                                     const float* g, int B, int N, float w, float* gx, void* ws, size_t ws_bytes,
+                                     hspStream_t stream) {
+    if (!recon || !G || !idx1 || !idx2 || !sym || !g || !gx || B <= 0 || N <= 0 || !isfinite(w) || !ws ||
+        ws_bytes < hsp_recon_chamfer_bwd_workspace_bytes(B, N))
+        return HSP_ERR_BAD_ARG;
+    if (!hsp_chamfer_bwd_ordered_ok(B, N, N)) return HSP_ERR_UNSUPPORTED;      // (nothing launched)
+    int32_t* off = reinterpret_cast<int32_t*>(ws);             // ws: off (B,N+1) | edge (B,N): the reverse of idx2
+    int32_t* edge = off + (size_t)B * (N + 1);
+    int rc = hsp_rev_build(idx2, B, N, N, 1, 1, off, edge, stream);
+    if (rc) return rc;
+    hipLaunchKernelGGL(recon_chamfer_grad_kernel, dim3((N + CH_ROWS_PER_WG - 1) / CH_ROWS_PER_WG, B), dim3(256), 0, as_stream(stream), recon, G, idx1, sym,
+                       off, edge, g, w, (float)((long long)B * N), N, gx);
     return check_launch();
 }
 

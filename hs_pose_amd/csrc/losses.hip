@@ -20,6 +20,7 @@
 // All sums are taken in a fixed order (one workgroup per cloud, fixed tree): results are bit-reproducible run to run.
 #include "common.h"
 #include "keyed_draws.h"
+#include "sym_target.h"
 
 namespace hsp {
 namespace {
@@ -215,13 +216,10 @@ __device__ void load_gt(CloudGT& c, const float* gt_R, const float* gt_t, const 
     for (int i = 0; i < 3; ++i) { c.t[i] = gt_t[b * 3 + i]; c.s[i] = gt_s[b * 3 + i]; c.ms[i] = mean_shape[b * 3 + i]; }
     for (int i = 0; i < 4; ++i) c.sym[i] = sym[b * 4 + i];
     c.obj = obj_id[b];
-    c.rot_sym = c.sym[0] == 1.f;
+    const SymClass k = sym_class(c.sym);                  // (sym_target.h: the rule the Chamfer reconstruction term shares)
+    c.rot_sym = k.rot_sym;
     c.keep = c.sym[0] == 0.f;
-    const float mirrors = c.sym[1] + c.sym[2] + c.sym[3];
-    c.cls_y = c.rot_sym && mirrors > 0.f;
-    c.cls_yx = !c.rot_sym && c.sym[1] == 1.f;
-    c.cls_none = !c.rot_sym && c.sym[1] != 1.f;
-    c.skip = c.rot_sym && mirrors == 0.f;
+    c.cls_y = k.cls_y; c.cls_yx = k.cls_yx; c.cls_none = k.cls_none; c.skip = k.skip;
     c.axis_mask[0] = c.keep && c.obj != 5.f;
     c.axis_mask[1] = true;
     c.axis_mask[2] = c.keep;
@@ -265,21 +263,14 @@ struct PointCtx {
 };
 __device__ __forceinline__ void point_ctx(PointCtx& q, const CloudGT& c, const float* T, const float* P) {
     for (int i = 0; i < 3; ++i) { q.P[i] = P[i]; q.c[i] = P[i] - T[i]; }
-    const float d0 = P[0] - c.t[0], d1 = P[1] - c.t[1], d2 = P[2] - c.t[2];
-    for (int j = 0; j < 3; ++j) q.canon[j] = d0 * c.R[j] + d1 * c.R[3 + j] + d2 * c.R[6 + j];
+    sym_canon(c.R, c.t, P, q.canon);
 }
 // target of the reconstruction term and the mirrored point of the rt term (prop_loss.py:258-276)
 __device__ __forceinline__ void sym_targets(const PointCtx& q, const CloudGT& c, const float* g, const float* T, const float* nm,
                                             float target[3], float mirrored[3], float& u) {
     u = 0.f;
-    if (c.cls_yx || c.cls_y) {
-        float m[3] = {c.cls_yx ? q.canon[0] : -q.canon[0], q.canon[1], -q.canon[2]};      // (x, y, -z) | (-x, y, -z)
-        for (int i = 0; i < 3; ++i) target[i] = (m[0] * c.R[3 * i] + m[1] * c.R[3 * i + 1] + m[2] * c.R[3 * i + 2]) + c.t[i];
-    } else if (c.cls_none) {
-        for (int i = 0; i < 3; ++i) target[i] = q.P[i];
-    } else {
-        for (int i = 0; i < 3; ++i) target[i] = 0.f;
-    }
+    const SymClass k = {c.rot_sym, c.cls_y, c.cls_yx, c.cls_none, c.skip};
+    sym_recon_target(k, c.R, c.t, q.P, q.canon, target);
     if (c.cls_y) {
         const float cg = q.c[0] * g[0] + q.c[1] * g[1] + q.c[2] * g[2];
         for (int i = 0; i < 3; ++i) mirrored[i] = q.P[i] + 2.0f * (cg * g[i] - q.c[i]);

@@ -48,21 +48,31 @@ def _f32(t, shape, name):
     return t
 
 
+# the one term beside the 19 that a dict from ``pose_losses`` may hold: (group, key), present while FLAGS.prop_sym_cd_w > 0
+# (ops.recon_chamfer; not a term of hsp_pose_losses_fwd: TERMS, N_TERMS and HspLossCfg are the kernels' and stay as they are)
+EXTRA_TERM = ("prop_loss", "Prop_sym_cd")
+
+
 class LossDict(dict):
     """the reference's loss_dict (four sub-dictionaries of 0-dim terms) that also carries their sum (``total``) and the identity of
-    the 19 term tensors it was built with (``terms``): the sum is only valid for exactly those"""
+    the 19 term tensors it was built with (``terms``) and of the extra term ``EXTRA_TERM``, if it was built with one (``extra``):
+    the sum is only valid for exactly those"""
     total = None
     terms = None
+    extra = None
 
     def untouched(self):
-        """True while every group still holds exactly the tensors the loss kernels returned (no term dropped, replaced,
+        """True while every group still holds exactly the tensors the dict was built with (no term dropped, replaced,
         re-weighted or added)"""
         if self.terms is None or set(self.keys()) != {g for g, _ in TERMS}:
             return False
         k = 0
         for group, keys in TERMS:
             d = self[group]
-            if len(d) != len(keys):
+            with_extra = self.extra is not None and group == EXTRA_TERM[0]
+            if len(d) != len(keys) + (1 if with_extra else 0):
+                return False
+            if with_extra and d.get(EXTRA_TERM[1]) is not self.extra:
                 return False
             for key in keys:
                 if d.get(key) is not self.terms[k]:
@@ -142,7 +152,8 @@ class _PoseLosses(torch.autograd.Function):
 
 def pose_losses(net_out, PC, gt_R, gt_t, gt_s, mean_shape, sym, obj_id):
     """net_out: dict with the ten network outputs (HSPose._NET_OUTPUTS); returns the reference's loss_dict
-    {'fsnet_loss': {...}, 'recon_loss': {...}, 'geo_loss': {...}, 'prop_loss': {...}}."""
+    {'fsnet_loss': {...}, 'recon_loss': {...}, 'geo_loss': {...}, 'prop_loss': {...}}; with FLAGS.prop_sym_cd_w > 0 its 'prop_loss'
+    also holds 'Prop_sym_cd' (``EXTRA_TERM``)."""
     vals = _PoseLosses.apply(*[net_out[k] for k in _NET], PC, gt_R, gt_t, gt_s, mean_shape, sym, obj_id.reshape(-1).float())
     out, k = LossDict(), 0
     out.total = vals[N_TERMS]
@@ -152,4 +163,11 @@ def pose_losses(net_out, PC, gt_R, gt_t, gt_s, mean_shape, sym, obj_id):
         for key in keys:
             out[group][key] = vals[k]
             k += 1
+    if FLAGS.prop_sym_cd_w > 0:
+        # the 20th term (not in the reference): the reconstruction against the same target as a SET, from its own node; the
+        # total is the kernels' total plus the term, one fp32 add
+        cd = ops.recon_chamfer(net_out["recon"], PC, gt_R, gt_t, sym, FLAGS.prop_sym_cd_w)
+        out[EXTRA_TERM[0]][EXTRA_TERM[1]] = cd
+        out.extra = cd
+        out.total = out.total + cd
     return out

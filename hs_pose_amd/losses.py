@@ -274,7 +274,48 @@ class prop_rot_loss(nn.Module):
             out["Prop_sym_rt"] = FLAGS.prop_sym_w * rt
         else:
             out["Prop_occ"] = 0.0
+        if "Prop_sym" in namelist and FLAGS.prop_sym_cd_w > 0:      # (not in the reference; config.FLAGS.prop_sym_cd_w)
+            out["Prop_sym_cd"] = self.prop_sym_chamfer_loss(gt_list['Points'], pred_list['Recon'], gt_list['R'], gt_list['T'], sym,
+                                                            FLAGS.prop_sym_cd_w)
         return out
+
+    def prop_sym_chamfer_loss(self, PC, PC_re, gt_R, gt_t, sym, w):
+        """w * (sum_i min_j |G_j - P_i|^2 + sum_j min_i |P_i - G_j|^2) / (B N): the Chamfer distance between the reconstruction
+        P = PC_re and G, the ``target`` of ``prop_sym_matching_loss`` (a constant), as SETS -- whichever row carries which point.
+        Clouds that term leaves out (``skip``) are left out here: no distance, no gradient.  The minimum routes the gradient to
+        the first arg-min pair.  (ops.recon_chamfer is the same term in two launches; this is its readable statement.)"""
+        target, skip = self._sym_target(PC, gt_R, gt_t, sym)
+        G = target.detach()
+        diff = PC_re.unsqueeze(2) - G.unsqueeze(1)                                # (B, N, N, 3): [b, i, j] = P_i - G_j
+        d = (diff[..., 0] * diff[..., 0] + diff[..., 1] * diff[..., 1]) + diff[..., 2] * diff[..., 2]
+        d1 = d.min(dim=2).values                                                  # P_i to its nearest G_j
+        d2 = d.min(dim=1).values                                                  # G_j to its nearest P_i
+        keep = ~skip.view(-1, 1)
+        zero = torch.zeros_like(d1)
+        B, N = d1.shape
+        return w * (torch.where(keep, d1, zero).sum() + torch.where(keep, d2, zero).sum()) / (B * N)
+
+    @staticmethod
+    def _sym_target(PC, gt_R, gt_t, sym):
+        """(target (B,N,3), skip (B,)) of prop_loss.py:258-268: the observed cloud turned 180 degrees about the object's y axis
+        (rotational symmetry with a mirror plane), mirrored in z (x-y mirror plane only) or taken as is (no symmetry) under the
+        ground-truth pose; a handle-less mug (sym = [1,0,0,0]) is ``skip``: its target is 0 and the terms leave it out."""
+        rot_sym = sym[:, 0] == 1
+        mirrors = sym[:, 1:].sum(dim=-1)
+        cls_y = torch.logical_and(rot_sym, mirrors > 0).view(-1, 1, 1)           # 180 deg about y
+        cls_yx = torch.logical_and(~rot_sym, sym[:, 1] == 1).view(-1, 1, 1)      # mirror z
+        cls_none = torch.logical_and(~rot_sym, sym[:, 1] != 1).view(-1, 1, 1)
+        skip = torch.logical_and(rot_sym, mirrors == 0)
+        zero = torch.zeros_like(PC)
+        canon = _to_object_frame(PC, gt_R, gt_t)
+
+        def back(pts):
+            return torch.matmul(pts, gt_R.transpose(-2, -1)) + gt_t.unsqueeze(1)
+        mirror_z = torch.cat([canon[..., :2], -canon[..., 2:]], dim=-1)                       # (x, y, -z)
+        turn_y = torch.cat([-canon[..., 0:1], canon[..., 1:2], -canon[..., 2:]], dim=-1)      # (-x, y, -z)
+        target = torch.where(cls_yx, back(mirror_z), zero) + torch.where(cls_y, back(turn_y), zero) \
+            + torch.where(cls_none, PC, zero)
+        return target, skip
 
     def prop_point_matching_loss(self, points, p_g_vec, f_g_vec, p_r_vec, f_r_vec, p_t, g_R, g_t, sym):
         """points mapped to the object frame by the PREDICTED pose (axes made perpendicular by their confidences;
@@ -295,18 +336,9 @@ class prop_rot_loss(nn.Module):
         mirrors = sym[:, 1:].sum(dim=-1)
         cls_y = torch.logical_and(rot_sym, mirrors > 0).view(-1, 1, 1)           # 180 deg about y
         cls_yx = torch.logical_and(~rot_sym, sym[:, 1] == 1).view(-1, 1, 1)      # mirror z
-        cls_none = torch.logical_and(~rot_sym, sym[:, 1] != 1).view(-1, 1, 1)
-        skip = torch.logical_and(rot_sym, mirrors == 0).view(-1, 1, 1)
         zero = torch.zeros_like(PC)
-        canon = _to_object_frame(PC, gt_R, gt_t)
-
-        def back(pts):
-            return torch.matmul(pts, gt_R.transpose(-2, -1)) + gt_t.unsqueeze(1)
-        mirror_z = torch.cat([canon[..., :2], -canon[..., 2:]], dim=-1)                       # (x, y, -z)
-        turn_y = torch.cat([-canon[..., 0:1], canon[..., 1:2], -canon[..., 2:]], dim=-1)      # (-x, y, -z)
-        target = torch.where(cls_yx, back(mirror_z), zero) + torch.where(cls_y, back(turn_y), zero) \
-            + torch.where(cls_none, PC, zero)
-        recon = self.loss_func(target, torch.where(skip, torch.zeros_like(PC_re), PC_re))
+        target, skip = self._sym_target(PC, gt_R, gt_t, sym)
+        recon = self.loss_func(target, torch.where(skip.view(-1, 1, 1), torch.zeros_like(PC_re), PC_re))
 
         # the reconstruction should also be the mirror image of the input under the PREDICTED axes / translation
         centred = PC - p_t.unsqueeze(1)

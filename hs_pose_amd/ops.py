@@ -2600,14 +2600,74 @@ class _Chamfer(torch.autograd.Function):
         g2 = _req(g2 if g2 is not None else torch.zeros(B, m, device=xyz1.device), torch.float32, "chamfer.g2")
         gx1 = torch.empty_like(xyz1)
         gx2 = torch.empty_like(xyz2)
+        if FLAGS.reproducible and _takes("hsp_chamfer_bwd_ordered_ok", B, n, m):
+            # the ordered form (own term, then the choosing points in ascending order; no float atomics) wherever the library
+            # takes the clouds, decided before anything is launched; today's launches otherwise
+            wsb = lib().hsp_chamfer_bwd_ordered_workspace_bytes(B, n, m)
+            ws = _ws(wsb, xyz1.device)
+            _run("hsp_chamfer_bwd_ordered", (_p(xyz1), _p(xyz2), _p(i1), _p(i2), _p(g1), _p(g2), B, n, m, _p(gx1), _p(gx2), _p(ws),
+                                             wsb, _stream()), key=f"B{B}n{n}m{m}", abytes=B * (n + m) * 48)
+            return gx1, gx2
         _run("hsp_chamfer_bwd", (_p(xyz1), _p(xyz2), _p(i1), _p(i2), _p(g1), _p(g2), B, n, m, _p(gx1), _p(gx2),
                                  _stream()), key=f"B{B}n{n}m{m}", abytes=B * (n + m) * 32)
         return gx1, gx2
 
 
 def chamfer(xyz1, xyz2):
-    """(dist1, dist2, idx1, idx2): squared NN distances both ways + int32 arg-mins."""
+    """(dist1, dist2, idx1, idx2): squared NN distances both ways + int32 arg-mins.  The backward sums with float atomics; with
+    ``FLAGS.reproducible`` it takes the ordered form (``hsp_chamfer_bwd_ordered``) wherever the library takes the clouds."""
     return _Chamfer.apply(xyz1, xyz2)
+
+
+class _ReconChamfer(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, recon, PC, gt_R, gt_t, sym, w):
+        recon = _req(recon, torch.float32, "recon_chamfer.recon")
+        B, N, _ = recon.shape
+        dev = recon.device
+        args = []
+        for t, shape, name in ((PC, (B, N, 3), "PC"), (gt_R, (B, 3, 3), "gt_R"), (gt_t, (B, 3), "gt_t"), (sym, (B, 4), "sym")):
+            t = _req(t.detach(), torch.float32, "recon_chamfer." + name)
+            if tuple(t.shape) != shape:
+                if t.numel() != torch.Size(shape).numel():
+                    raise HspError(f"recon_chamfer.{name}: expected shape {shape}, got {tuple(t.shape)}")
+                t = t.reshape(shape)
+            args.append(t)
+        PC, gt_R, gt_t, sym = args
+        if not _takes("hsp_chamfer_bwd_ordered_ok", B, N, N):
+            raise HspError(f"recon_chamfer: B={B}, N={N} is beyond the ordered backward (hsp_chamfer_bwd_ordered_ok); there is no "
+                           f"other form of this term")
+        term = torch.empty(1, dtype=torch.float32, device=dev)
+        G = torch.empty(B, N, 3, dtype=torch.float32, device=dev)
+        i1 = torch.empty(B, N, dtype=torch.int32, device=dev)
+        i2 = torch.empty(B, N, dtype=torch.int32, device=dev)
+        wsb = lib().hsp_recon_chamfer_fwd_workspace_bytes(B, N)
+        ws = _ws(wsb, dev)
+        _run("hsp_recon_chamfer_fwd", (_p(PC), _p(gt_R), _p(gt_t), _p(sym), _p(recon), B, N, float(w), _p(term), _p(G), _p(i1),
+                                       _p(i2), _p(ws), wsb, _stream()), key=f"B{B}N{N}", abytes=B * N * 60)
+        ctx.save_for_backward(recon, G, i1, i2, sym)
+        ctx.w = float(w)
+        return term[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        recon, G, i1, i2, sym = ctx.saved_tensors
+        B, N, _ = recon.shape
+        g = _req(g, torch.float32, "recon_chamfer.grad").reshape(1)
+        gx = torch.empty_like(recon)
+        wsb = lib().hsp_recon_chamfer_bwd_workspace_bytes(B, N)
+        ws = _ws(wsb, recon.device)
+        _run("hsp_recon_chamfer_bwd", (_p(recon), _p(G), _p(i1), _p(i2), _p(sym), _p(g), B, N, ctx.w, _p(gx), _p(ws), wsb,
+                                       _stream()), key=f"B{B}N{N}", abytes=B * N * 44)
+        return gx, None, None, None, None, None
+
+
+def recon_chamfer(recon, PC, gt_R, gt_t, sym, w):
+    """the 0-dim term 'Prop_sym_cd' = w * Chamfer(recon, target) / (B N) of ``losses.prop_rot_loss.prop_sym_chamfer_loss`` in two
+    launches (``hsp_recon_chamfer_fwd``: the target is made in the kernel, both directions searched, the distances summed in a fixed
+    order), differentiable in ``recon`` only by an ordered, atomic-free backward (``hsp_recon_chamfer_bwd``).  No host sync and no
+    size decided by data: it can sit inside a captured step.  ``w`` is a Python number (read when the call is issued)."""
+    return _ReconChamfer.apply(recon, PC, gt_R, gt_t, sym, w)
 
 
 def fps(xyz, n_samples):

@@ -943,6 +943,60 @@ int hsp_chamfer_bwd(const float *xyz1, const float *xyz2, const int32_t *idx1, c
                     const float *gd1, const float *gd2, int B, int n, int m, float *gx1, float *gx2,
                     hspStream_t stream);
 
+/* ---- Chamfer distance: ordered backward, and the reconstruction term of the training step ----------------------
+ * (not in the reference.)  hsp_chamfer_bwd sums with float atomics into pre-zeroed outputs; the forms below write every
+ * output row once, from one fp32 sum in a stated order, so two runs give equal bits.
+ *
+ * hsp_chamfer_bwd_ordered: hsp_chamfer_bwd's contract (any n, m; per-point gd1 (B,n), gd2 (B,m)) and its arithmetic term by
+ * term -- g = 2 gd, v = g * (p - q), each operation rounded once --, summed per output row as
+ *     gx1[b,i] = 2 gd1[i] (x1_i - x2_idx1[i])  -  2 gd2[j] (x2_j - x1_i)   for the j with idx2[j] == i, j ASCENDING,
+ * own term first, one subtraction per j; gx2 likewise over idx1.  The lists of the rows that chose a row are
+ * hsp_rev_build(idx, k = 1) -- one launch for both maps -- and one more launch writes the rows; no memset.  gx1 or gx2
+ * (not both) may be NULL: not wanted.  idx1 / idx2 are device data in [0, m) / [0, n) and are not range-checked.
+ * ws: hsp_chamfer_bwd_ordered_workspace_bytes(B, n, m) (the two reverse maps).
+ * hsp_chamfer_bwd_ordered_ok(B, n, m): 1 where the entry takes the call -- clouds the reverse build holds
+ * (hsp_rev_build_takes(n) and (m): n, m <= 35 839) and B <= 65 535 --, the function the entry itself declines by; it is the
+ * limit of hsp_recon_chamfer_bwd as well, at n = m = N.
+ * A NULL pointer (but one of gx1 / gx2), B, n, m <= 0, ws NULL or short: HSP_ERR_BAD_ARG; a call beyond _ok:
+ * HSP_ERR_UNSUPPORTED; nothing is launched in either case.
+ *
+ * hsp_recon_chamfer_fwd: the term 'Prop_sym_cd' (config.FLAGS.prop_sym_cd_w) between the reconstruction P = recon (B,N,3) and
+ * the target G (B,N,3) of the loss kernels' Prop_sym_recon -- the observed cloud PC (B,N,3) turned 180 degrees about the
+ * object's y axis (sym[b] = [1, *] with a mirror flag set), mirrored in z ([0, 1, *]) or taken as is ([0, != 1, *]) under the
+ * ground-truth pose gt_R (B,3,3), gt_t (B,3); the rule is csrc/sym_target.h's, one copy for both -- as SETS:
+ *     d1[b,i] = min_j |G[b,j] - P[b,i]|^2,   d2[b,j] = min_i |P[b,i] - G[b,j]|^2,
+ *     term[0] = (w * S) / (float)(B N),      S = sum of d1 and d2 over the batch.
+ * Distances are hsp_chamfer_fwd's expression: candidate minus query, (dx dx + dy dy) + dz dz, each operation rounded once,
+ * strict '<', so idx1 / idx2 (B,N) are the FIRST minima (defined on the exact ties of a tiled cloud).  A cloud with
+ * sym[b] = [1, 0, 0, 0] ("skip") is left out: G[b] = 0, its distances 0, its arg-mins 0, nothing searched.
+ * Two launches for any (B, N): the first searches both directions (G is made while the candidates are staged through LDS in
+ * chunks of 2048 points, and written out by the workgroups that hold it as queries) and leaves d1 (B,N) | d2 (B,N) in ws, in
+ * that order; the second is one workgroup of 1024 threads that sums the 2 B N floats of ws in the order
+ *     acc_t = ((0 + ws[t]) + ws[t + 1024]) + ...            for thread t,
+ *     acc_t += acc_(t + h)   for t < h,   h = 512, 256, ..., 1,        S = acc_0,
+ * fixed by (B, N) alone.  G, idx1, idx2 are outputs the backward (and a test) reads; term is a device scalar.
+ * ws: hsp_recon_chamfer_fwd_workspace_bytes(B, N) = 8 B N.  Any N >= 1; B <= 65 535 (HSP_ERR_UNSUPPORTED beyond).
+ *
+ * hsp_recon_chamfer_bwd: d term / d recon of that call, hsp_chamfer_bwd_ordered specialised to it: gd = (g[0] * w) / (B N)
+ * for every point, g the device scalar arriving at the term, gx (B,N,3) only (G is a constant):
+ *     gx[b,i] = (2 gd) * [ (P_i - G_idx1[i]) + (P_i - G_j) for the j with idx2[j] == i, j ASCENDING ],
+ * the bracket summed in fp32 in that order, scaled once at the end; the rows of a skip cloud are written as zeros.  One
+ * hsp_rev_build launch and one more.  ws: hsp_recon_chamfer_bwd_workspace_bytes(B, N).
+ * Both: a NULL pointer, B, N <= 0, w not finite, ws NULL or short: HSP_ERR_BAD_ARG, nothing launched.
+ */
+int hsp_chamfer_bwd_ordered_ok(int B, int n, int m);
+size_t hsp_chamfer_bwd_ordered_workspace_bytes(int B, int n, int m);
+int hsp_chamfer_bwd_ordered(const float *xyz1, const float *xyz2, const int32_t *idx1, const int32_t *idx2,
+                            const float *gd1, const float *gd2, int B, int n, int m, float *gx1, float *gx2, void *ws,
+                            size_t ws_bytes, hspStream_t stream);
+size_t hsp_recon_chamfer_fwd_workspace_bytes(int B, int N);
+int hsp_recon_chamfer_fwd(const float *PC, const float *gt_R, const float *gt_t, const float *sym, const float *recon, int B,
+                          int N, float w, float *term, float *G, int32_t *idx1, int32_t *idx2, void *ws, size_t ws_bytes,
+                          hspStream_t stream);
+size_t hsp_recon_chamfer_bwd_workspace_bytes(int B, int N);
+int hsp_recon_chamfer_bwd(const float *recon, const float *G, const int32_t *idx1, const int32_t *idx2, const float *sym,
+                          const float *g, int B, int N, float w, float *gx, void *ws, size_t ws_bytes, hspStream_t stream);
+
 /* ---- farthest point sampling -----------------------------------------------------------------
  * replaces farthest_point_sampling(points, n)         tools/eval_utils.py:107-119 (per cloud)
  * xyz (B,N,3) -> sel (B,n_samples): start at 0, running min of the Euclidean distances, first maximum wins.
