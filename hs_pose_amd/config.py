@@ -39,8 +39,11 @@ class _Flags:
         pool_sampler='random',  # (not in the reference) Pool_layer's down-sampler: 'random' -- the reference's randperm slice --
                                 # or 'fps' -- per-cloud farthest-point sampling on the device (gcn3d.Pool_layer)
         pc_sampler='host',      # (not in the reference) who draws the rows an instance cloud keeps (pc_sample.py): 'host' -- the
-                                # reference's draws on numpy's global generator -- or 'device' -- a keyed counter-based draw
-                                # inside the front end (pc_sample.DeviceSampler), no count copy and no sync
+                                # reference's draws on numpy's global generator --, 'device' -- a keyed counter-based draw
+                                # inside the front end (pc_sample.DeviceSampler), no count copy and no sync -- or 'fps' -- no
+                                # draw: farthest-point picks over each instance's back-projected candidates (hsp_fps_ids), the
+                                # frame front end only (frame_to_pcl, frame_to_pcl_device, frame.FramePipeline); PC_sample,
+                                # depth_to_pcl and the training front end raise under it.  DESIGN.md section 8i
         step_draws='host',      # (not in the reference) who makes the draws of a forward or a replay -- the Pool_layers' kept
                                 # rows, the augmentation's uniforms and jitter, the training loader's DZI windows: 'host' -- the
                                 # reference's draws on torch's and numpy's generators, uploaded before a replay -- or 'device' --

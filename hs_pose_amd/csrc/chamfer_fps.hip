@@ -8,6 +8,7 @@
 // from the problem instead of a fixed dim3(32,16).
 // FPS: replaces tools/eval_utils.py:107-119 (per cloud): start at 0, running min, first max wins.
 #include "common.h"
+#include "fps_pick.h"
 #include "sym_target.h"
 
 namespace hsp {
@@ -409,23 +410,7 @@ __global__ __launch_bounds__(THREADS) void fps_reg_kernel(const float* __restric
 // whose plain picks are all distinct the picks are therefore the plain kernel's, bit for bit; on a tiled cloud with fewer distinct
 // points than picks the remaining picks are the lowest-index unpicked rows.  The picked coordinates -- in LDS already -- are written
 // as the level-1 cloud v1 (B,N1,3) in pick order and its first N2 rows as v2 (B,N2,3): farthest-point picks are nested, so the
-// sampler run on v1 returns 0 .. N2-1.
-__device__ __forceinline__ long long dpp_max_i64(long long k, const int ctrl_sel) {
-    unsigned lo = (unsigned)k, hi = (unsigned)((unsigned long long)k >> 32), olo, ohi;
-    switch (ctrl_sel) {                                     // dpp_ctrl must be an immediate
-        case 0: olo = __builtin_amdgcn_update_dpp(lo, lo, 0xB1, 0xF, 0xF, false);      // quad_perm [1,0,3,2]
-                ohi = __builtin_amdgcn_update_dpp(hi, hi, 0xB1, 0xF, 0xF, false); break;
-        case 1: olo = __builtin_amdgcn_update_dpp(lo, lo, 0x4E, 0xF, 0xF, false);      // quad_perm [2,3,0,1]
-                ohi = __builtin_amdgcn_update_dpp(hi, hi, 0x4E, 0xF, 0xF, false); break;
-        case 2: olo = __builtin_amdgcn_update_dpp(lo, lo, 0x141, 0xF, 0xF, false);     // row_half_mirror
-                ohi = __builtin_amdgcn_update_dpp(hi, hi, 0x141, 0xF, 0xF, false); break;
-        default: olo = __builtin_amdgcn_update_dpp(lo, lo, 0x140, 0xF, 0xF, false);    // row_mirror
-                 ohi = __builtin_amdgcn_update_dpp(hi, hi, 0x140, 0xF, 0xF, false); break;
-    }
-    const long long o = (long long)(((unsigned long long)ohi << 32) | olo);
-    return o > k ? o : k;
-}
-
+// sampler run on v1 returns 0 .. N2-1.  (The key and its wave fold: fps_pick.h.)
 template <int THREADS, int PPT>
 __global__ __launch_bounds__(THREADS) void fps_levels_kernel(const float* __restrict__ xyz, int N, int N1, int N2,
                                                              int32_t* __restrict__ sel1, float* __restrict__ v1,
@@ -468,18 +453,7 @@ __global__ __launch_bounds__(THREADS) void fps_levels_kernel(const float* __rest
             const long long kk = (long long)(((unsigned long long)__float_as_uint(v) << 32) | (unsigned)(~j));
             if (j < N && kk > key) key = kk;
         }
-        key = dpp_max_i64(key, 0);
-        key = dpp_max_i64(key, 1);
-        key = dpp_max_i64(key, 2);
-        key = dpp_max_i64(key, 3);                          // every lane holds its 16-lane row's best
-        long long wk = LLONG_MIN;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const unsigned lo = __builtin_amdgcn_readlane((unsigned)key, r * 16);
-            const unsigned hi = __builtin_amdgcn_readlane((unsigned)((unsigned long long)key >> 32), r * 16);
-            const long long rk = (long long)(((unsigned long long)hi << 32) | lo);
-            wk = rk > wk ? rk : wk;
-        }
+        long long wk = wave_max_i64(key);                   // (fps_pick.h)
         if (W > 1) {
             if (lane == 0) slot[s & 1][wv] = wk;
             __syncthreads();

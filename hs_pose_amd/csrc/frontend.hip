@@ -24,6 +24,7 @@
 #include <tuple>
 
 #include "common.h"
+#include "fps_pick.h"
 #include "keyed_draws.h"
 
 namespace hsp {
@@ -310,9 +311,22 @@ __global__ __launch_bounds__(256) void roi_write_kernel(const D* __restrict__ de
     }
 }
 
-// pc[j,s,:] for pixel p = src[j, choose[j,s]] of the frame of instance j, depth + j * depth_stride (0: one frame for all): the
-// grid values the reference warps are u = float(p % W), v = float(p / W) (exact), then the loader's arithmetic.  An index
-// outside its row or frame (a choose beyond the instance's count) gives NaN.
+// The fp32 metres of frame pixel p -- THE coordinates of a crop pixel, for the back-projection below and for the farthest-point
+// sampler that ranks candidates by them (fps_ids_kernel): the grid values the reference warps are u = float(p % W),
+// v = float(p / W) (exact), then the loader's arithmetic.  p outside the frame gives NaN.
+template <typename D>
+__device__ __forceinline__ void frame_pixel_xyz(const D* __restrict__ depth, int H, int W, const double* __restrict__ K, int p,
+                                                float* __restrict__ o) {
+    if (p < 0 || p >= H * W) {
+        o[0] = o[1] = o[2] = __builtin_nanf("");
+        return;
+    }
+    const int v = p / W, u = p - v * W;
+    backproject_f64((double)(float)u, (double)(float)v, (double)depth[p], K, o);
+}
+
+// pc[j,s,:] for pixel p = src[j, choose[j,s]] of the frame of instance j, depth + j * depth_stride (0: one frame for all).  An
+// index outside its row or frame (a choose beyond the instance's count) gives NaN.
 template <typename D>
 __global__ __launch_bounds__(256) void frames_to_pcl_kernel(const D* __restrict__ depth, long long depth_stride, int H, int W,
                                                             const double* __restrict__ camK, int camK_rows,
@@ -325,13 +339,7 @@ __global__ __launch_bounds__(256) void frames_to_pcl_kernel(const D* __restrict_
     float* o = pc + (size_t)e * 3;
     const int c = choose[e];
     const int p = (c >= 0 && c < src_stride) ? src[(size_t)j * src_stride + c] : -1;
-    if (p < 0 || p >= H * W) {
-        o[0] = o[1] = o[2] = __builtin_nanf("");
-        return;
-    }
-    const int v = p / W, u = p - v * W;
-    backproject_f64((double)(float)u, (double)(float)v, (double)depth[(size_t)j * depth_stride + p],
-                    camK + (camK_rows > 1 ? (size_t)j * 9 : 0), o);
+    frame_pixel_xyz(depth + (size_t)j * depth_stride, H, W, camK + (camK_rows > 1 ? (size_t)j * 9 : 0), p, o);
 }
 
 // ---- the rows each instance keeps, drawn on the device (include/hsp.h: hsp_sample_ids states the construction) ------------
@@ -363,6 +371,136 @@ __global__ __launch_bounds__(256) void sample_ids_kernel(const int32_t* __restri
             out = (int)feistel_permute((uint32_t)s, (uint32_t)c, kj);
     }
     choose[e] = out;
+}
+
+// ---- the rows each instance keeps, picked by farthest-point sampling (include/hsp.h: hsp_fps_ids_* states the contract) -----
+// The same place in the chain and the same outputs as sample_ids_kernel, with no draw: ONE workgroup per instance ranks the
+// instance's candidates -- at most FPS_IDS_CAP entries of its src row, thinned by a stride in crop raster order beyond that -- by
+// the coordinates hsp_frame_to_pcl_* would write for them (frame_pixel_xyz), with the pick chain of fps_levels_kernel
+// (chamfer_fps.hip): coordinates and distance-to-set in registers, FPS_IDS_THREADS x FPS_IDS_PPT, per pick one 64-bit key
+// (fps_pick.h), DPP + v_readlane inside the wave, one LDS slot per wave (double-buffered by pick parity), ONE barrier, and the 16
+// slots folded by DPP again.
+// The winner's coordinates come from an LDS copy of the candidates (not published beside the key: that would cost every lane a
+// select chain over its FPS_IDS_PPT points per pick to save a broadcast read).  The count is a run-time value: the launch is
+// shaped for the cap, and a wave updates only the slots that hold a candidate of its own (a wave-uniform switch per pick).
+// Every exit before the pick loop is taken by the whole workgroup: the two counts are read once, by two lanes, and broadcast
+// through LDS, and the branches test only those.
+// Budget: 12 x 4 registers of state + the update's temporaries = 113 VGPRs, no scratch, under the 128 a 1024-thread workgroup
+// leaves each lane; LDS 12 bytes per candidate (147 456 at the cap; the launch asks for min(cap, src_stride) of them) + 272
+// static, of 160 KB.
+// Plain C++, vector stores, no atomics, no workspace, nothing read back.
+#define FPS_IDS_THREADS 1024
+#define FPS_IDS_PPT 12
+#define FPS_IDS_CAP (FPS_IDS_THREADS * FPS_IDS_PPT)
+
+// one pick's update of a lane's first NK slots -> the lane's best key.  NK is the wave's count of slots that hold a candidate:
+// one straight-line body per count, no test per slot, so that the NK distance chains are scheduled together (a wave-uniform
+// test in front of every slot instead: 3.37 against 2.86 us a pick at the cap, measured)
+template <int NK>
+__device__ __forceinline__ long long fps_ids_update(const float (&px)[FPS_IDS_PPT], const float (&py)[FPS_IDS_PPT],
+                                                    const float (&pz)[FPS_IDS_PPT], float (&dt)[FPS_IDS_PPT], float cx, float cy,
+                                                    float cz, int cur, int tid) {
+    long long key = LLONG_MIN;
+#pragma unroll
+    for (int k = 0; k < NK; ++k) {
+        const int t = tid + k * FPS_IDS_THREADS;
+        const float dx = sub_rn(px[k], cx), dy = sub_rn(py[k], cy), dz = sub_rn(pz[k], cz);
+        const float d = sqrtf(add_rn(add_rn(mul_rn(dx, dx), mul_rn(dy, dy)), mul_rn(dz, dz)));   // as fps_levels_kernel
+        // picked: -1 for good (fminf(-1, d) == -1).  The select stands in FRONT of the minimum, on operands that cost nothing:
+        // behind it the compiler moves the whole distance under a branch on t != cur, a basic block per slot again
+        const float v = fminf(t == cur ? -1.f : dt[k], d);
+        dt[k] = v;
+        const long long kk = (long long)(((unsigned long long)__float_as_uint(v) << 32) | (unsigned)(~t));
+        if (kk > key) key = kk;                                      // (no test of t against the count: see dt's start values)
+    }
+    return key;
+}
+
+template <typename D>
+__global__ __launch_bounds__(FPS_IDS_THREADS) void fps_ids_kernel(const D* __restrict__ depth, int H, int W,
+                                                                  const double* __restrict__ camK, int camK_rows,
+                                                                  const int32_t* __restrict__ src, long long src_stride,
+                                                                  const int32_t* __restrict__ count, int S, int min_pts,
+                                                                  int min_depth_pts, int32_t* __restrict__ choose,
+                                                                  int32_t* __restrict__ status) {
+    constexpr int T = FPS_IDS_THREADS, PPT = FPS_IDS_PPT, NW = T / HSP_WAVE, CAP = FPS_IDS_CAP;
+    extern __shared__ __attribute__((aligned(16))) float s_xyz[];          // min(CAP, src_stride) * 3
+    __shared__ long long slot[2][NW];
+    __shared__ int s_cnt[2];
+    const int j = blockIdx.x, tid = threadIdx.x;
+    const int lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    if (tid < 2) s_cnt[tid] = count[(size_t)j * 2 + tid];
+    __syncthreads();
+    const int c = __builtin_amdgcn_readfirstlane(s_cnt[0]), cd = __builtin_amdgcn_readfirstlane(s_cnt[1]);
+    const int st = (c < min_pts ? 1 : 0) | (cd < min_depth_pts ? 2 : 0);
+    if (tid == 0) status[j] = st;
+    int32_t* __restrict__ out = choose + (size_t)j * S;
+    if (st != 0 || c <= 0) {                                    // (whole workgroup)
+        for (int s = tid; s < S; s += T) out[s] = -1;
+        return;
+    }
+    if (c <= S) {                                               // (whole workgroup)
+        for (int s = tid; s < S; s += T) out[s] = s % c;
+        return;
+    }
+    // a count beyond the row's pitch is the caller's error; no entry past the row is read
+    const unsigned cc = (unsigned)(c < src_stride ? c : (int)src_stride);
+    const bool thin = cc > (unsigned)CAP;
+    const int m = thin ? CAP : (int)cc;
+    const int32_t* __restrict__ row = src + (size_t)j * src_stride;
+    const double* __restrict__ K = camK + (camK_rows > 1 ? (size_t)j * 9 : 0);
+    for (int t = tid; t < m; t += T) {
+        const unsigned g = thin ? (unsigned)(((unsigned long long)t * cc) / (unsigned)CAP) : (unsigned)t;
+        frame_pixel_xyz(depth, H, W, K, row[g], s_xyz + t * 3);
+    }
+    __syncthreads();
+    float px[PPT], py[PPT], pz[PPT], dt[PPT];
+#pragma unroll
+    for (int k = 0; k < PPT; ++k) {
+        const int t = tid + k * T;
+        const bool in = t < m;
+        px[k] = in ? s_xyz[t * 3] : 0.f;
+        py[k] = in ? s_xyz[t * 3 + 1] : 0.f;
+        pz[k] = in ? s_xyz[t * 3 + 2] : 0.f;
+        dt[k] = in ? INFINITY : -1.f;                           // past the candidates: "picked" from the start -- it ranks with the
+    }                                                           // picked ones and below them all by its index, so it never wins
+    // slot k of this wave holds candidates wv * 64 + k * T ..: the first nk slots reach below m
+    const int left = m - wv * HSP_WAVE;
+    const int nk = left <= 0 ? 0 : (left + T - 1) / T;         // (<= PPT: m <= CAP)
+    int cur = 0;
+    for (int s = 0; s < S; ++s) {
+        const float cx = s_xyz[cur * 3], cy = s_xyz[cur * 3 + 1], cz = s_xyz[cur * 3 + 2];
+        if (tid == 0) out[s] = thin ? (int)(((unsigned long long)cur * cc) / (unsigned)CAP) : cur;
+        long long key;                                          // (value bits, signed) << 32 | ~index
+        switch (nk) {                                           // wave-uniform: the wave's slots that hold a candidate
+            case 0: key = LLONG_MIN; break;
+            case 1: key = fps_ids_update<1>(px, py, pz, dt, cx, cy, cz, cur, tid); break;
+            case 2: key = fps_ids_update<2>(px, py, pz, dt, cx, cy, cz, cur, tid); break;
+            case 3: key = fps_ids_update<3>(px, py, pz, dt, cx, cy, cz, cur, tid); break;
+            case 4: key = fps_ids_update<4>(px, py, pz, dt, cx, cy, cz, cur, tid); break;
+            case 5: key = fps_ids_update<5>(px, py, pz, dt, cx, cy, cz, cur, tid); break;
+            case 6: key = fps_ids_update<6>(px, py, pz, dt, cx, cy, cz, cur, tid); break;
+            case 7: key = fps_ids_update<7>(px, py, pz, dt, cx, cy, cz, cur, tid); break;
+            case 8: key = fps_ids_update<8>(px, py, pz, dt, cx, cy, cz, cur, tid); break;
+            case 9: key = fps_ids_update<9>(px, py, pz, dt, cx, cy, cz, cur, tid); break;
+            case 10: key = fps_ids_update<10>(px, py, pz, dt, cx, cy, cz, cur, tid); break;
+            case 11: key = fps_ids_update<11>(px, py, pz, dt, cx, cy, cz, cur, tid); break;
+            default: key = fps_ids_update<12>(px, py, pz, dt, cx, cy, cz, cur, tid); break;
+        }
+        long long wk = wave_max_i64(key);
+        if (lane == 0) slot[s & 1][wv] = wk;
+        __syncthreads();
+        // the fold of the NW = 16 slots: lane l reads slot l % 16, so every 16-lane row holds them all and 4 DPP steps leave the
+        // workgroup's best in every lane (16 reads folded one after the other compile to a serial chain of scalar selects here:
+        // 3.34 against 2.86 us a pick at the cap, measured)
+        static_assert(NW == 16, "one slot per lane of a DPP row");
+        wk = slot[s & 1][lane & 15];
+        wk = dpp_max_i64(wk, 0);
+        wk = dpp_max_i64(wk, 1);
+        wk = dpp_max_i64(wk, 2);
+        wk = dpp_max_i64(wk, 3);
+        cur = __builtin_amdgcn_readfirstlane((int)(~(unsigned)wk));   // (wave 0 always holds candidate 0: some key is a candidate's)
+    }
 }
 
 // ---- the keyed draws of a step (include/hsp.h: "keyed draws of a step" states each stream) -----------------------------------
@@ -812,6 +950,39 @@ extern "C" int hsp_sample_ids(const int32_t* count, int count_stride, int n, int
     hipLaunchKernelGGL(sample_ids_kernel, dim3((unsigned)(((long long)n * S + 255) / 256)), dim3(256), 0, as_stream(stream), count, count_stride, n,
                        S, min_pts, min_depth_pts, short_mode, key, choose, status);
     return check_launch();
+}
+
+extern "C" int hsp_fps_ids_cap(void) { return FPS_IDS_CAP; }
+
+// hsp_fps_ids's refusals -- hsp_sample_ids's and hsp_frame_to_pcl's -- and the launch: nothing is declined by shape
+template <typename D>
+static int fps_ids(const D* depth, int H, int W, const double* camK, int camK_rows, const int32_t* src, long long src_stride,
+                   const int32_t* count, int n, int S, int min_pts, int min_depth_pts, int32_t* choose, int32_t* status,
+                   hspStream_t stream) {
+    if (!depth || !camK || !src || !count || !choose || !status || n <= 0 || n > 65535 || S <= 0 || H <= 0 || W <= 0 ||
+        src_stride <= 0)
+        return HSP_ERR_BAD_ARG;
+    if ((long long)H * W > 2147483647LL || (camK_rows != 1 && camK_rows != n) || (long long)n * S > 2147483647LL)
+        return HSP_ERR_BAD_ARG;
+    const size_t lds = (size_t)(src_stride < FPS_IDS_CAP ? src_stride : FPS_IDS_CAP) * 3 * sizeof(float);
+    auto kern = fps_ids_kernel<D>;
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) { set_last_hip_error(e); return HSP_ERR_LAUNCH; }
+    hipLaunchKernelGGL(kern, dim3(n), dim3(FPS_IDS_THREADS), lds, as_stream(stream), depth, H, W, camK, camK_rows, src, src_stride,
+                       count, S, min_pts, min_depth_pts, choose, status);
+    return check_launch();
+}
+
+extern "C" int hsp_fps_ids_f32(const float* depth, int H, int W, const double* camK, int camK_rows, const int32_t* src,
+                               long long src_stride, const int32_t* count, int n, int S, int min_pts, int min_depth_pts,
+                               int32_t* choose, int32_t* status, hspStream_t stream) {
+    return fps_ids(depth, H, W, camK, camK_rows, src, src_stride, count, n, S, min_pts, min_depth_pts, choose, status, stream);
+}
+
+extern "C" int hsp_fps_ids_u16(const uint16_t* depth, int H, int W, const double* camK, int camK_rows, const int32_t* src,
+                               long long src_stride, const int32_t* count, int n, int S, int min_pts, int min_depth_pts,
+                               int32_t* choose, int32_t* status, hspStream_t stream) {
+    return fps_ids(depth, H, W, camK, camK_rows, src, src_stride, count, n, S, min_pts, min_depth_pts, choose, status, stream);
 }
 
 extern "C" int hsp_pool_rows_draw(const unsigned long long* key, int n0, int rate, int levels, int32_t* rows,

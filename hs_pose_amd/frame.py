@@ -11,6 +11,11 @@ it: its draws need the counts on the host.  With a device sampler (``sampler='de
 ``one_graph=True`` -- captured together with the network, so that a frame is a few small uploads and ONE replay.  What that
 replay still takes from the host is the network's two Pool_layer permutations, drawn on the CPU generator before it; with
 ``draws='device'`` (or ``FLAGS.step_draws = 'device'``) they are keyed draws inside the replay under the sampler's key as well.
+
+With ``sampler='fps'`` (``pc_sample.FpsSampler``) the middle kernel of the device front end is ``hsp_fps_ids``: the rows are the
+farthest-point picks over each instance's candidates and nothing is drawn for the clouds, in any of the three forms.  Under
+``FLAGS.pool_sampler = 'fps'`` the Pool_layers pick their rows inside the replay too, and a frame's poses are then a pure
+function of depth, masks, boxes, classes and K: no generator, no key, no host draw.
 """
 import numpy as np
 import torch
@@ -20,10 +25,10 @@ from .graph import GraphedInference
 
 
 class _FrameGraph:
-    """roi_compact -> sample_ids -> frame_to_pcl -> network -> generate_RT of one (instance count, frame shape, depth dtype,
-    mask form) as one captured graph over static buffers: the frame, the masks (or the label image and its ids), the crop
-    transforms, K, the class rows and the sampler's key.  Everything is issued on the capture stream, in order; the kernels'
-    workspaces and outputs come from the capture's pool."""
+    """roi_compact -> sample_ids (under the 'fps' sampler: fps_ids) -> frame_to_pcl -> network -> generate_RT of one (instance
+    count, frame shape, depth dtype, mask form) as one captured graph over static buffers: the frame, the masks (or the label
+    image and its ids), the crop transforms, K, the class rows and the sampler's key (the 'fps' sampler has none).  Everything
+    is issued on the capture stream, in order; the kernels' workspaces and outputs come from the capture's pool."""
 
     def __init__(self, pipe, sampler, depth, masks, ids, xf, K, obj_id, n_pts, O, draws=None):
         dev = depth.device
@@ -38,7 +43,7 @@ class _FrameGraph:
 
         def front_end():
             src, count = ops.roi_compact(self.depth, self.masks, self.xf, O, self.ids)
-            choose, self.status = ops.sample_ids(count, n_pts, key, pipe.min_pts, 2, 0)
+            choose, self.status = pc_sample.choose_rows(sampler, key, self.depth, self.K, src, count, n_pts, pipe.min_pts)
             return pipe._network_input(ops.frame_to_pcl(self.depth, self.K, src, choose), self.status)
 
         n = xf.shape[0]
@@ -70,9 +75,15 @@ class FramePipeline:
     caller's (copies of the graph's static buffers).  The first frame with a new instance count captures its graph (a few ms,
     see GraphedInference).
 
-    ``sampler``: None (follow ``FLAGS.pc_sampler`` at each call), 'host', 'device' or a ``pc_sample.DeviceSampler``.  With a
-    device sampler nothing is copied back before the poses: ``sync=True`` reads the per-instance status once, after everything
-    is queued, and returns None for a rejected frame as above; ``sync=False`` never waits and returns
+    ``sampler``: None (follow ``FLAGS.pc_sampler`` at each call), 'host', 'device', a ``pc_sample.DeviceSampler`` or 'fps'.
+    'fps' counts as a device sampler in everything below, with nothing to seed or advance: the rows of a cloud are picked by
+    farthest-point sampling (``hsp_fps_ids``).  Under ``FLAGS.pool_sampler = 'fps'`` a frame then needs no key upload and no
+    host draw and ``draws`` plays no part; under the default 'random' pool sampler the Pool_layers' rows are still drawn as
+    ``draws`` says -- on the CPU generator before each replay, or keyed by the resolved ``draws`` sampler -- so the poses are
+    deterministic only as far as those draws are.
+
+    With a device sampler nothing is copied back before the poses: ``sync=True`` reads the per-instance status once, after
+    everything is queued, and returns None for a rejected frame as above; ``sync=False`` never waits and returns
     ``(pred_RT, pred_s, status (n,) int32)`` as device tensors -- the rows of an instance whose status is not 0 mean nothing
     (the network ran on a stand-in cloud for it).  ``one_graph=True`` (device sampler only) captures the front end with the
     network: one graph per (instance count, frame shape, depth dtype, mask form), one replay per frame.
@@ -104,10 +115,10 @@ class FramePipeline:
         sampler = pc_sample.resolve_sampler(self.sampler, dev)
         if sampler is None and (self.one_graph or not self.sync):
             raise ValueError("FramePipeline: one_graph=True and sync=False need a device sampler (sampler='device', a DeviceSampler, "
-                             "or FLAGS.pc_sampler = 'device'): the host draws wait for the counts")
+                             "'fps', or FLAGS.pc_sampler = 'device' / 'fps'): the host draws wait for the counts")
         draws = pc_sample.resolve_draws(self.draws, dev)
-        if draws is not None and sampler is not None:
-            draws = sampler                                      # one key per frame
+        if draws is not None and isinstance(sampler, pc_sample.DeviceSampler):
+            draws = sampler                                      # one key per frame (the 'fps' sampler has no key to share)
         if n == 0:
             out = torch.zeros(0, 4, 4, device=dev), torch.zeros(0, 3, device=dev)
             return out if self.sync else out + (torch.zeros(0, dtype=torch.int32, device=dev),)
@@ -155,5 +166,7 @@ class FramePipeline:
         else:
             fg.load(self, depth, masks, ids, xf, K, obj_id)
         sampler.advance()
+        if draws is not None and draws is not sampler:           # (the 'fps' sampler: the Pool rows' key is the draws sampler's)
+            draws.advance()
         fg.graphed.run()
         return fg.graphed, fg.status

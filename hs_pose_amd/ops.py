@@ -2956,6 +2956,33 @@ def frame_to_pcl(depth, camK64, src, choose):
     return _to_pcl("frame_to_pcl", depth, False, camK64, src, choose)
 
 
+def fps_ids(depth, camK64, src, count, S, min_pts, min_depth_pts=2):
+    """the rows each instance keeps, picked by farthest-point sampling over its candidates' back-projected coordinates, no draw
+    (include/hsp.h: hsp_fps_ids_*): depth (H,W) fp32 or uint16, camK (1|n,3,3) float64, src (n,L) int32 and count (n,2) int32
+    from roi_compact -> (choose (n,S) int32, status (n,) int32) as ``sample_ids`` returns them.  status bit 0: count < min_pts,
+    bit 1: second count < min_depth_pts; such a row of choose is all -1; a count <= S is tiled."""
+    src = _req(src, torch.int32, "fps_ids.src")
+    count = _req(count, torch.int32, "fps_ids.count")
+    camK64 = _req(camK64.detach() if isinstance(camK64, torch.Tensor) else camK64, torch.float64, "fps_ids.camK")
+    S = int(S)
+    if src.dim() != 2 or src.shape[0] == 0 or src.shape[1] == 0 or count.shape != (src.shape[0], 2) \
+            or camK64.numel() not in (9, 9 * src.shape[0]):
+        raise HspError(f"fps_ids: expects depth (H,W), camK (1|n,3,3) f64, src (n,L) and count (n,2) with n, L >= 1, got src "
+                       f"{tuple(src.shape)}, count {tuple(count.shape)}, camK {tuple(camK64.shape)}")
+    n = src.shape[0]
+    if n > 65535 or S < 1 or n * S >= 2 ** 31:
+        raise HspError(f"fps_ids: n {n} / S {S} out of range (n <= 65535, S >= 1, n * S < 2^31)")
+    depth = _req_depth(depth, "fps_ids.depth")
+    H, W = depth.shape
+    choose = torch.empty(n, S, dtype=torch.int32, device=depth.device)
+    status = torch.empty(n, dtype=torch.int32, device=depth.device)
+    _run("hsp_fps_ids" + _FRAME_DEPTH[depth.dtype],
+         (_p(depth), H, W, _p(camK64), camK64.numel() // 9, _p(src), src.shape[1], _p(count), n, S, int(min_pts),
+          int(min_depth_pts), _p(choose), _p(status), _stream()),
+         key=f"n{n}L{src.shape[1]}S{S}", abytes=n * (min(src.shape[1], lib().hsp_fps_ids_cap()) * (4 + depth.element_size()) + 4 * S + 12))
+    return choose, status
+
+
 def roi_defor(mask, xf, out_size, key, inst_ids=None, iters=1, gate=0):
     """the cropped masks of a training batch before and after ``defor_2D`` (include/hsp.h: the mask rule): mask uint8 (n,H,W)
     -- a mask per instance, or with inst_ids a label image per instance -- or (H,W) (one label image for all), xf (n,3) float64,

@@ -19,7 +19,11 @@ the above, draw for draw.  ``'device'`` -- or a ``DeviceSampler`` of one's own -
 ``hsp_sample_ids`` from a seeded counter-based generator: the same DISTRIBUTION (a uniform subset without replacement when long,
 tiling or a uniform draw with replacement when short), not the same draws; the counts stay on the device, nothing is copied
 back and nothing waits until the caller reads the result, and numpy's generator is never touched.  ``frame_to_pcl_device`` is
-that form bare: clouds and per-instance status, both on the device.
+that form bare: clouds and per-instance status, both on the device.  ``'fps'`` -- the ``FpsSampler`` -- is the frame front end's
+alone (``frame_to_pcl``, ``frame_to_pcl_device``, ``frame.FramePipeline``): no draw at all, the rows are picked between the two
+stages by farthest-point sampling over each instance's back-projected candidates (``hsp_fps_ids``), a pure function of the
+frame, the masks, the windows and K.  ``PC_sample``, ``depth_to_pcl`` and the training front end refuse it: there the sampling
+noise is part of what the reference trains and evaluates with.
 
 ``dzi_windows`` + ``train_batch_to_pcl`` are the training loader's chain (datasets/load_data.py:228-278) for a batch of items,
 each with its own frame: ``aug_bbox_DZI``'s windows on the host, draw for draw, then the crops, ``defor_2D``'s perturbation of
@@ -80,6 +84,23 @@ class DeviceSampler:
         return self.key
 
 
+class FpsSampler:
+    """The sampler that draws nothing: the rows an instance keeps are the farthest-point picks over its candidates
+    (include/hsp.h: hsp_fps_ids_*).  No seed, no key, no state; ``advance()`` is there for the callers that advance a sampler
+    once per frame and does nothing.  One object serves every device (``FPS``); it hashes by identity like a DeviceSampler, so
+    it keys a graph cache the same way."""
+    key = None
+
+    def advance(self):
+        return None
+
+    def __repr__(self):
+        return "FpsSampler()"
+
+
+FPS = FpsSampler()
+
+
 _default_samplers = {}
 
 
@@ -96,17 +117,27 @@ def default_sampler(device):
 
 
 def resolve_sampler(sampler, device):
-    """``sampler=`` of the front ends -> None (the host draws) or a DeviceSampler: None follows ``FLAGS.pc_sampler``, 'host',
-    'device' (the module's default sampler), or a DeviceSampler"""
+    """``sampler=`` of the front ends -> None (the host draws), a DeviceSampler or the FpsSampler: None follows
+    ``FLAGS.pc_sampler``, 'host', 'device' (the module's default sampler), 'fps' (``FPS``), or a sampler object"""
     if sampler is None:
         sampler = getattr(FLAGS, "pc_sampler", "host")
-    if isinstance(sampler, DeviceSampler):
+    if isinstance(sampler, (DeviceSampler, FpsSampler)):
         return sampler
     if sampler == "host":
         return None
     if sampler == "device":
         return default_sampler(device)
-    raise ValueError(f"pc sampler: expects 'host', 'device' or a DeviceSampler, got {sampler!r}")
+    if sampler == "fps":
+        return FPS
+    raise ValueError(f"pc sampler: expects 'host', 'device', 'fps', a DeviceSampler or the FpsSampler, got {sampler!r}")
+
+
+def draws_only(sampler, who):
+    """``sampler`` as resolved, for a front end whose sampling noise is part of its contract: the 'fps' sampler is refused"""
+    if isinstance(sampler, FpsSampler):
+        raise ValueError(f"{who}: the 'fps' sampler is the frame front end's (frame_to_pcl, frame_to_pcl_device, FramePipeline); "
+                         "here the rows are drawn: 'host', 'device' or a DeviceSampler")
+    return sampler
 
 
 def resolve_draws(draws, device):
@@ -204,7 +235,7 @@ def PC_sample(obj_mask, Depth, camK, coor2d, sampler=None):
     bs, H, W = Depth.shape[0], Depth.shape[2], Depth.shape[3]
     mask = obj_mask.reshape(bs, H * W).float()
     pix, count = ops.pc_compact(mask, Depth.reshape(bs, H * W))
-    sampler = resolve_sampler(sampler, Depth.device)
+    sampler = draws_only(resolve_sampler(sampler, Depth.device), "PC_sample")
     if sampler is not None:
         choose_d, status = ops.sample_ids(count, samplenum, sampler.advance(), 2, 0, 1)
         pc = ops.pc_gather(Depth.reshape(bs, H * W), coor2d.reshape(bs, 2, H * W), camK, pix,
@@ -247,7 +278,7 @@ def depth_to_pcl(depth, K, xymap, mask, n_pts=None, min_pts=50, sampler=None):
     if K64.shape[0] == 1 and B > 1:
         K64 = K64.expand(B, 9)
     pix, count = ops.pc_compact(mask.reshape(B, HW).float(), d)
-    sampler = resolve_sampler(sampler, depth.device)
+    sampler = draws_only(resolve_sampler(sampler, depth.device), "depth_to_pcl")
     if sampler is not None:
         choose_d, status = ops.sample_ids(count, n_pts, sampler.advance(), min_pts, 0, 0)
         pc = ops.depth_to_pcl(d, xymap.reshape(B, 2, HW), K64.contiguous(), pix, _gather_safe(choose_d, pix, HW))
@@ -330,10 +361,12 @@ def _frame_args(masks, centers, scales, K, n_pts, out_size, inst_ids):
 
 
 def frame_to_pcl_device(depth, masks, centers, scales, K, n_pts=None, out_size=None, inst_ids=None, min_pts=2, sampler=None):
-    """``frame_to_pcl`` with the rows drawn on the device: the same arguments, ``sampler`` a DeviceSampler (None or 'device':
-    the module's) -> (PC (n, n_pts, 3) fp32 metres, status (n,) int32), both on the device.  status bit 0: fewer than min_pts
-    crop pixels with depth and mask; bit 1: <= 1 with depth; the rows of such an instance are NaN and the frame is one the
-    loader skips.  Three launches and the uploads of the small host arrays, all queued: no device->host copy, no wait."""
+    """``frame_to_pcl`` with the rows chosen on the device: the same arguments, ``sampler`` a DeviceSampler (None or 'device':
+    the module's) or 'fps' / the FpsSampler -> (PC (n, n_pts, 3) fp32 metres, status (n,) int32), both on the device.  status
+    bit 0: fewer than min_pts crop pixels with depth and mask; bit 1: <= 1 with depth; the rows of such an instance are NaN and
+    the frame is one the loader skips.  Three launches and the uploads of the small host arrays, all queued: no device->host
+    copy, no wait.  Under 'fps' the middle launch is ``hsp_fps_ids`` in place of ``hsp_sample_ids``: nothing is drawn and no key
+    goes up, the clouds are a function of the arguments alone."""
     n_pts, O, xf, masks, ids, K = _frame_args(masks, centers, scales, K, n_pts, out_size, inst_ids)
     dev = depth.device
     sampler = resolve_sampler("device" if sampler is None else sampler, dev)
@@ -344,8 +377,17 @@ def frame_to_pcl_device(depth, masks, centers, scales, K, n_pts=None, out_size=N
     ids_d = None if ids is None else _upload(ids, np.int32, dev)
     K64 = K.to(torch.float64).reshape(-1, 9).contiguous() if isinstance(K, torch.Tensor) else _upload(K, np.float64, dev)
     src, count = ops.roi_compact(depth, masks, _upload(xf, np.float64, dev), O, ids_d)
-    choose, status = ops.sample_ids(count, n_pts, sampler.advance(), min_pts, 2, 0)
+    choose, status = choose_rows(sampler, sampler.advance(), depth, K64, src, count, n_pts, min_pts)
     return ops.frame_to_pcl(depth, K64, src, choose), status
+
+
+def choose_rows(sampler, key, depth, K64, src, count, n_pts, min_pts):
+    """the middle launch of the frame front end -> (choose (n, n_pts) int32, status (n,) int32): ``hsp_fps_ids`` under the
+    FpsSampler, else ``hsp_sample_ids`` under ``key`` (the sampler's, as advanced by the caller); the loader's two rejection
+    tests either way"""
+    if isinstance(sampler, FpsSampler):
+        return ops.fps_ids(depth, K64, src, count, n_pts, min_pts, 2)
+    return ops.sample_ids(count, n_pts, key, min_pts, 2, 0)
 
 
 def frame_to_pcl(depth, masks, centers, scales, K, n_pts=None, out_size=None, inst_ids=None, min_pts=2, sampler=None):
@@ -357,7 +399,7 @@ def frame_to_pcl(depth, masks, centers, scales, K, n_pts=None, out_size=None, in
     -> (n, n_pts, 3) fp32 metres, or None if an instance has <= 1 crop pixels with depth or fewer than min_pts with depth and
     mask (the loader skips such a frame; decided before anything is drawn).  n_pts defaults to FLAGS.random_points, out_size to
     FLAGS.img_size.  One device->host copy; per instance, in order, the draws of ``sample_point_ids``.  ``sampler``: see the
-    module text; the device form is ``frame_to_pcl_device`` with its status read once everything is queued."""
+    module text; the device and 'fps' forms are ``frame_to_pcl_device`` with its status read once everything is queued."""
     dsampler = resolve_sampler(sampler, depth.device)
     if dsampler is not None:
         PC, status = frame_to_pcl_device(depth, masks, centers, scales, K, n_pts, out_size, inst_ids, min_pts, dsampler)
@@ -442,7 +484,7 @@ def train_batch_to_pcl(depth, labels, inst_ids, centers, scales, K, n_pts=None, 
     n_pts = int(FLAGS.random_points if n_pts is None else n_pts)
     O = int(FLAGS.img_size if out_size is None else out_size)
     dev = depth.device
-    sampler = resolve_sampler("device" if sampler is None else sampler, dev)
+    sampler = draws_only(resolve_sampler("device" if sampler is None else sampler, dev), "train_batch_to_pcl")
     if sampler is None:
         raise ValueError("train_batch_to_pcl: expects a device sampler; there is no host-draw form of this chain")
     capturing = dev.type == "cuda" and torch.cuda.is_current_stream_capturing()

@@ -156,7 +156,8 @@ class FrameTrainStep:
         self.keep = int(keep)
         self.n_pts = int(FLAGS.random_points if n_pts is None else n_pts)
         self.out_size = int(FLAGS.img_size if out_size is None else out_size)
-        self.sampler = pc_sample.resolve_sampler("device" if sampler is None else sampler, dev)
+        self.sampler = pc_sample.draws_only(pc_sample.resolve_sampler("device" if sampler is None else sampler, dev),
+                                             "FrameTrainStep")
         if self.sampler is None:
             raise ValueError("FrameTrainStep: expects a device sampler; there is no host-draw form of the training front end")
         self.draws = self.sampler if pc_sample.resolve_draws(draws, dev) is not None else None

@@ -816,6 +816,45 @@ int hsp_frame_to_pcl_u16(const uint16_t *depth, int H, int W, const double *camK
 int hsp_sample_ids(const int32_t *count, int count_stride, int n, int S, int min_pts, int min_depth_pts, int short_mode,
                    const unsigned long long *key, int32_t *choose, int32_t *status, hspStream_t stream);
 
+/* ---- the rows each instance keeps, picked by farthest-point sampling: no draw -------------------------
+ * The third, opt-in way to fill choose / status between hsp_roi_compact_* and hsp_frame_to_pcl_*: a pure function of the frame,
+ * the candidates and K -- no key, no generator.  (The loader's own docstring asks for it: evaluation/load_data_eval.py
+ * _sample_points, "Down sample the point cloud using farthest point sampling", above a random permutation.)  One launch, one
+ * workgroup per instance, plain C++ and vector stores, no atomics, no workspace, nothing read back; it can be captured.
+ *
+ * depth, H, W, camK (camK_rows, 9) DOUBLE, src rows of pitch src_stride: as hsp_frame_to_pcl_* takes them; count (n,2) int32: the
+ * pairs of hsp_roi_compact_*, on the device; choose (n,S) int32, status (n) int32.  n <= 65535, S >= 1, n * S < 2^31,
+ * H * W < 2^31, camK_rows 1 or n, src_stride >= 1, no NULL pointer; anything else is HSP_ERR_BAD_ARG before any launch.  Nothing
+ * is declined by shape: there is no HSP_ERR_UNSUPPORTED.
+ *
+ * Per instance j, with c = count[2 j]:
+ *   status[j] = (c < min_pts ? 1 : 0) | (count[2 j + 1] < min_depth_pts ? 2 : 0)            (hsp_sample_ids's at count_stride 2)
+ *   status[j] != 0 or c <= 0:   choose[j,s] = -1 for every s
+ *   c <= S:                     choose[j,s] = s % c                                          (the tiling of short_mode 0)
+ *   otherwise:                  choose[j,s] = g(pick_s), with
+ *     candidates   CAP = hsp_fps_ids_cap() = 12288, m = min(c, CAP); candidate t in [0, m) is the src entry g(t):
+ *                  g(t) = t for c <= CAP, g(t) = (uint64(t) * c) / CAP (integer division) for c > CAP -- a strided thinning in
+ *                  crop raster order, strictly increasing, g(0) = 0, g(CAP - 1) < c.  (A c beyond src_stride is the caller's
+ *                  error; it is read as src_stride, so nothing past the row is touched.)
+ *     coordinates  of candidate t: the three fp32 values hsp_frame_to_pcl_* writes for src[j, g(t)], bit for bit (one device
+ *                  function serves both)
+ *     picks        hsp_fps_levels_f32's rule on those coordinates: pick_0 = 0; every candidate keeps the running minimum of its
+ *                  distance to the picked ones, fp32 (dx*dx + dy*dy) + dz*dz under a correctly rounded sqrt; the largest wins,
+ *                  the lowest index among equals; A PICKED CANDIDATE IS NEVER PICKED AGAIN (it ranks below every unpicked one,
+ *                  a zero distance included).  Exact ties are the normal case here -- whole millimetres on a pixel grid -- and
+ *                  with fewer distinct points than S (a crop window smaller than the crop is up-sampled, so src names a source
+ *                  pixel several times) the tail of the row is the lowest-index unpicked candidates.
+ *                  (S > CAP with c > S leaves nothing unpicked after CAP picks: every later pick is candidate 0.)
+ * A src entry outside the frame has NaN coordinates (hsp_frame_to_pcl_*'s rule) and a NaN distance never replaces a minimum;
+ * hsp_roi_compact_* writes no such entry. */
+int hsp_fps_ids_cap(void);     /* 12288: the most candidates one instance's pick chain ranks */
+int hsp_fps_ids_f32(const float *depth, int H, int W, const double *camK, int camK_rows, const int32_t *src,
+                    long long src_stride, const int32_t *count, int n, int S, int min_pts, int min_depth_pts, int32_t *choose,
+                    int32_t *status, hspStream_t stream);
+int hsp_fps_ids_u16(const uint16_t *depth, int H, int W, const double *camK, int camK_rows, const int32_t *src,
+                    long long src_stride, const int32_t *count, int n, int S, int min_pts, int min_depth_pts, int32_t *choose,
+                    int32_t *status, hspStream_t stream);
+
 /* ---- the training loader's front end: a batch of frames, the mask perturbed before the cloud is cut -------
  * replaces datasets/load_data.py:234-278 behind aug_bbox_DZI: the three nearest-neighbour crops, defor_2D
  * (datasets/data_augmentation.py:9-32) on the cropped mask, the three rejection tests (:254, :257, :276), _depth_to_pcl and the
