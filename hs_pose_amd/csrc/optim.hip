@@ -73,7 +73,7 @@ __global__ __launch_bounds__(256) void ranger_rows_kernel(float* __restrict__ p,
     float clip = 1.0f;
     if (gnorm_sq) {                                        // clip_grad_norm_: coef = max_norm / (norm + 1e-6), capped at 1
         const float c = a.max_norm / (sqrtf(gnorm_sq[0]) + 1e-6f);
-        clip = c < 1.0f ? c : 1.0f;
+        clip = c > 1.0f ? 1.0f : c;                        // torch.clamp(max=1): a NaN norm stays a NaN coefficient
     }
     float* pp = p + rd.offset;
     const float* gp = g + rd.offset;
