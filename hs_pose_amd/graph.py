@@ -9,6 +9,8 @@
 * ``GraphedInference``  -- the timed body of ``evaluation/evaluate.py`` (eval forward + generate_RT).
 * ``GraphedTrainStep``  -- the whole training step incl. augmentation, losses, backward and the gradient norm as ONE graph
   (+ one fused optimizer launch): what ``bench.py`` times as unit U3.
+* ``capture_scope``     -- how all four are captured (timer off, state rolled back, warm-up on a side stream, ``thread_local``
+  capture), stated once with its reasons; the timing scripts under ``tools/`` capture through it too.
 
 Static shapes, static input / gradient buffers.  The only host work of the reference's forward -- the two
 ``torch.randperm`` draws of the Pool_layers on the CPU default generator (gcn3d.py:243) -- happens BEFORE each replay,
@@ -30,11 +32,6 @@ import torch
 
 from . import augment, gcn3d, ops, pc_sample, staging
 from .config import FLAGS
-
-# Other threads of the process (RCCL's watchdog polling events, the autograd engine's workers) may call into HIP while
-# this thread captures: only this thread's calls are checked against the capture.
-_CAPTURE = {"capture_error_mode": "thread_local"}
-
 
 def draw_pool_indices(n_points, rate=4, levels=2):
     """consume the CPU default generator exactly like FaceRecon's two Pool_layers (FaceRecon.py:91,96)."""
@@ -137,6 +134,76 @@ class _preserve_bn_stats:
         return False
 
 
+class _Capture:
+    """what ``capture_scope`` hands to its body: the warm-up stream and the two calls"""
+
+    def __init__(self):
+        self.side = torch.cuda.Stream()
+        self.side.wait_stream(torch.cuda.current_stream())
+        self._joined = False
+
+    def warm_up(self, fn, n=1):
+        """``fn()`` ``n`` times, eagerly, on the side stream"""
+        with torch.cuda.stream(self.side):
+            for _ in range(n):
+                fn()
+
+    def capture(self, fn, on_warmup_stream=False, share_pool=None):
+        """a new graph holding one ``fn()``"""
+        if not self._joined:
+            torch.cuda.current_stream().wait_stream(self.side)
+            torch.cuda.synchronize()
+            self._joined = True
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph, pool=None if share_pool is None else share_pool.pool(),
+                              stream=self.side if on_warmup_stream else None, capture_error_mode="thread_local"):
+            fn()
+        return graph
+
+
+@contextlib.contextmanager
+def capture_scope(module=None, sampler=None):
+    """The choreography of every hipGraph capture of the project, stated once.  ``with capture_scope(module, sampler) as cap:``
+    then ``cap.warm_up(fn, n)`` any number of times, then ``cap.capture(fn)`` once per graph (Python may run in between).
+
+    * Timer off.  ``ops.set_timer(None)`` for the whole scope: a KernelTimer records HIP events around every entry point, and
+      events cannot be recorded inside a capture.  The previous timer comes back on exit.
+    * State rolled back.  The warm-up runs the live ``module`` in train mode on an example batch and advances the ``sampler`` of
+      the body's device draws although no step has happened: BatchNorm statistics (``_preserve_bn_stats``) and the sampler's
+      state and key (``_keep_sampler_state``) are snapshotted on entry, each only if given, and restored on exit in reverse order
+      -- sampler, BatchNorm, timer -- whether or not the body raised.
+    * Warm-up on a side stream.  A body has to run eagerly before it is captured (lazy initialisation, the libraries'
+      workspaces and autograd's accumulators do work a capture cannot hold), and it runs on a fresh stream that waits for the
+      current one, not on the default stream, whose implicit synchronisation a capture forbids.  The streams are joined and the
+      device synchronised once, after the last warm-up work and before the first capture.
+    * ``thread_local`` error mode.  Other threads of the process (RCCL's watchdog polling events, the autograd engine's workers)
+      may call into HIP while this thread captures: only this thread's calls are checked against the capture.
+    * ``capture(on_warmup_stream=True)``.  Autograd binds each parameter's gradient accumulator to the stream of its first use,
+      and an accumulator bound to another stream than the capture stream is executed OUTSIDE the capture (the replayed graph
+      then reads freed memory).  A body whose backward accumulates into the ``.grad`` of parameters that saw no backward before
+      the warm-up is therefore captured on the stream its warm-up ran on; every other body on ``torch.cuda.graph``'s own.
+    * ``capture(share_pool=graph)``: an earlier graph of the scope whose memory pool the new one allocates from (tensors made
+      inside the first capture stay valid inputs of the second)."""
+    prev_timer = ops.set_timer(None)
+    try:
+        with _preserve_bn_stats(module) if module is not None else contextlib.nullcontext(), _keep_sampler_state(sampler):
+            yield _Capture()
+    finally:
+        ops.set_timer(prev_timer)
+
+
+def _copy_in(pairs):
+    """new data into static buffers: ``(dst, src)`` pairs, a ``src`` of None leaves its buffer as it is"""
+    for dst, src in pairs:
+        if src is not None:
+            dst.copy_(src, non_blocking=True)
+
+
+def _pack_grads(params, grads, out):
+    """the gradients as ONE flat buffer (one captured multi-tensor copy), zeros where a parameter has none"""
+    torch.cat([(g if g is not None else torch.zeros_like(p)).reshape(-1) for p, g in zip(params, grads)], out=out)
+
+
 class GraphedStep:
     """step = zero_grad; (_, _, feat) = face_recon(centred, obj); feat.backward(dfeat)   as one hipGraph.
 
@@ -168,55 +235,37 @@ class GraphedStep:
         if flat_grads or split:
             self.flat_grad = torch.zeros(sum(p.numel() for p in self.params), dtype=torch.float32, device=dev)
         self._upload_pool_indices()
-        prev_timer = ops.set_timer(None)               # HIP events cannot be recorded inside a capture
-        keep = _preserve_bn_stats(face_recon).__enter__()
-        try:
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                if split:
-                    self._find_late_params()
-                for _ in range(warmup):
-                    if split:
-                        self._body_first()
-                        self._body_second()
-                    else:
-                        self._body()
-            torch.cuda.current_stream().wait_stream(side)
-            torch.cuda.synchronize()
-            self.graph = torch.cuda.CUDAGraph()
+        with capture_scope(face_recon) as cap:
             if split:
-                self.graph2 = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(self.graph, **_CAPTURE):
-                    self._body_first()
-                with torch.cuda.graph(self.graph2, pool=self.graph.pool(), **_CAPTURE):
-                    self._body_second()
+                cap.warm_up(self._find_late_params)
+                cap.warm_up(lambda: (self._body_first(), self._body_second()), warmup)
+                self.graph = cap.capture(self._body_first)
+                self.graph2 = cap.capture(self._body_second, share_pool=self.graph)
             else:
-                with torch.cuda.graph(self.graph, **_CAPTURE):
-                    self._body()
-        finally:
-            keep.__exit__()
-            ops.set_timer(prev_timer)
+                cap.warm_up(self._body, warmup)
+                self.graph = cap.capture(self._body)
+
+    def _forward(self, zero_grads=True):
+        if zero_grads:
+            for p in self.params:
+                p.grad = None
+        with pool_feed(self.pool_idx):
+            return self.net(self.centred, self.obj)[2]
 
     def _body(self):
-        for p in self.params:
-            p.grad = None
-        with pool_feed(self.pool_idx):
-            _, _, feat = self.net(self.centred, self.obj)
+        feat = self._forward()
         with ops.StepFolds():                           # every p.grad is None: the backward's folds go out in one launch
             feat.backward(self.dfeat)
         self.feat = feat.detach()                       # (keeping the autograd graph alive would pin its accumulators' streams)
         if self.flat_grad is not None:
-            torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).reshape(-1) for p in self.params],
-                      out=self.flat_grad)
+            _pack_grads(self.params, [p.grad for p in self.params], self.flat_grad)
 
     # ---- the step cut in two (split=True) -------------------------------------------------------------------------
     def _find_late_params(self):
         """late = the parameters the cut tensors do not depend on (their gradients are complete after the first part).
         ``flat_grad`` is laid out [late | early] so each part is one contiguous all-reduce."""
         self.net.keep_backward_cut = True
-        with pool_feed(self.pool_idx):
-            _, _, feat = self.net(self.centred, self.obj)
+        feat = self._forward(zero_grads=False)
         cut = list(self.net.backward_cut)
         self.net.backward_cut = None
         below = torch.autograd.grad(cut, self.params, [torch.zeros_like(c) for c in cut], allow_unused=True)
@@ -228,40 +277,32 @@ class GraphedStep:
         self.params = self.late + self.early           # grad_views() follows the flat layout
 
     def _body_first(self):
-        for p in self.params:
-            p.grad = None
-        with pool_feed(self.pool_idx):
-            _, _, feat = self.net(self.centred, self.obj)
+        feat = self._forward()
         self.feat = feat.detach()
         cut = list(self.net.backward_cut)
         self.net.backward_cut = None
         with ops.StepFolds():
             grads = torch.autograd.grad(feat, cut + self.late, self.dfeat, allow_unused=True)
         self._cut, self._cut_grads = cut, list(grads[:len(cut)])
-        torch.cat([(g if g is not None else torch.zeros_like(p)).reshape(-1) for p, g in zip(self.late, grads[len(cut):])],
-                  out=self.flat_late)
+        _pack_grads(self.late, grads[len(cut):], self.flat_late)
 
     def _body_second(self):
         with ops.StepFolds():
             torch.autograd.backward(self._cut, self._cut_grads, inputs=self.early)
-        torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).reshape(-1) for p in self.early],
-                  out=self.flat_early)
+        _pack_grads(self.early, [p.grad for p in self.early], self.flat_early)
         self._cut = self._cut_grads = None
 
     def _upload_pool_indices(self):
         upload_pool_indices(self.pool_idx, self.n_points)
 
     def load_inputs(self, centred=None, obj=None, dfeat=None):
-        for dst, src in ((self.centred, centred), (self.obj, obj), (self.dfeat, dfeat)):
-            if src is not None:
-                dst.copy_(src, non_blocking=True)
+        _copy_in(((self.centred, centred), (self.obj, obj), (self.dfeat, dfeat)))
 
     def run(self):
         """one step: draw + upload the pool indices (host RNG, reference order), replay the graph."""
-        self._upload_pool_indices()
-        self.graph.replay()
+        self.run_first()
         if self.split:
-            self.graph2.replay()
+            self.run_second()
         return self.feat
 
     def run_first(self):
@@ -308,9 +349,8 @@ class GraphedTrainStep:
     the draw scaled in serial pieces into the pinned ring, ``run()`` is 8.2 ms -- replay + 0.15 ms -- and this is the form
     ``bench.py`` reports for unit U3.
 
-    Build it BEFORE the network's first eager backward: autograd binds each parameter's gradient accumulator to the
-    stream of its first use, and an accumulator bound to another stream than the capture stream is executed outside
-    the capture (the replayed graph then reads freed memory).  The warm-up iterations here run on the capture stream.
+    Build it BEFORE the network's first eager backward: the gradient accumulators have to be bound to the capture stream, which
+    is the stream of the warm-up here (``capture_scope``: ``on_warmup_stream``) and cannot be once an eager backward has run.
 
     ``prologue``: a callable issued at the head of the captured body, on the capture stream, that returns a dict; its entries
     replace the same-named entries of ``batch`` for that body -- the step in front of the network captured with it
@@ -337,25 +377,10 @@ class GraphedTrainStep:
         self.pool_idx = pool_index_buffers(network, N, dev)
         self.loss_dict, self.total = None, None
         self._host_draws()
-        prev_timer = ops.set_timer(None)
-        keep = _preserve_bn_stats(network).__enter__()
-        keep_state = _keep_sampler_state(self.draws).__enter__()
-        try:
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                for _ in range(warmup):
-                    self._body()
-            torch.cuda.current_stream().wait_stream(side)
-            torch.cuda.synchronize()
-            self.graph = torch.cuda.CUDAGraph()
+        with capture_scope(network, self.draws) as cap:
+            cap.warm_up(self._body, warmup)
             # capture ON THE WARM-UP STREAM: the parameters' gradient accumulators were bound to it by the warm-up backward
-            with torch.cuda.graph(self.graph, stream=side, **_CAPTURE):
-                self._body()
-        finally:
-            keep_state.__exit__()
-            keep.__exit__()
-            ops.set_timer(prev_timer)
+            self.graph = cap.capture(self._body, on_warmup_stream=True)
 
     def _host_draws(self):
         if self.draws is not None:                           # device draws: everything is drawn inside the replay
@@ -409,8 +434,7 @@ class GraphedTrainStep:
         return params, views
 
     def load_batch(self, batch):
-        for k, v in batch.items():
-            self.batch[k].copy_(v, non_blocking=True)
+        _copy_in((self.batch[k], v) for k, v in batch.items())
 
     def replay(self):
         """the host draws and the replay: losses and gradients of one step, nothing applied yet (device draws: the replay
@@ -468,22 +492,9 @@ class GraphedInference:
             raise RuntimeError("GraphedInference: put the network in eval() mode first")
         self.draws = pc_sample.resolve_draws(draws, dev)
         self._draw()
-        prev_timer = ops.set_timer(None)
-        keep_state = _keep_sampler_state(self.draws).__enter__()
-        try:
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                for _ in range(warmup):
-                    self._body()
-            torch.cuda.current_stream().wait_stream(side)
-            torch.cuda.synchronize()
-            self.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph, **_CAPTURE):
-                self._body()
-        finally:
-            keep_state.__exit__()
-            ops.set_timer(prev_timer)
+        with capture_scope(sampler=self.draws) as cap:       # (eval mode: no BatchNorm statistics move)
+            cap.warm_up(self._body, warmup)
+            self.graph = cap.capture(self._body)
 
     def _draw(self):
         if self.draws is None:                               # (device draws: the rows are drawn inside the replay)
@@ -503,9 +514,7 @@ class GraphedInference:
         self.output_dict = out
 
     def load(self, PC=None, obj_id=None, mean_shape=None, sym=None):
-        for dst, src in ((self.PC, PC), (self.obj_id, obj_id), (self.mean_shape, mean_shape), (self.sym, sym)):
-            if src is not None:
-                dst.copy_(src, non_blocking=True)
+        _copy_in(((self.PC, PC), (self.obj_id, obj_id), (self.mean_shape, mean_shape), (self.sym, sym)))
 
     def run(self):
         self._draw()
@@ -567,39 +576,32 @@ class GraphedNetwork:
         self.params = [p for p in posenet.parameters() if p.requires_grad]
         self._anchor = torch.zeros(1, device=dev, requires_grad=True)
         upload_pool_indices(self.pool_idx, N)
-        prev_timer = ops.set_timer(None)
-        keep = _preserve_bn_stats(posenet).__enter__()
-        try:
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                for _ in range(warmup):
-                    outs = self._forward()
-                    live = [o for o in outs if o is not None and o.requires_grad]
-                    torch.autograd.grad(live, self.params, [torch.zeros_like(o) for o in live], allow_unused=True)
-                del outs, live
-            torch.cuda.current_stream().wait_stream(side)
-            torch.cuda.synchronize()
-            self.graph_fwd = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph_fwd, **_CAPTURE):
-                outs = self._forward()
-            self.none_mask = [o is None for o in outs]
-            self.outs = [o for o in outs if o is not None]
+        with capture_scope(posenet) as cap:
+            cap.warm_up(self._warm, warmup)
+            self.graph_fwd = cap.capture(self._capture_forward)
             self.gouts = [torch.zeros_like(o) for o in self.outs]
-            self.graph_bwd = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph_bwd, pool=self.graph_fwd.pool(), **_CAPTURE):
-                with ops.StepFolds(bare_wgrad=True):    # (before the .contiguous() copies below read the gradients)
-                    self.pgrads = list(torch.autograd.grad(self.outs, self.params, self.gouts, allow_unused=True))
-                # contiguous static gradients (copies inside the graph where autograd hands back a transposed view): the
-                # multi-tensor add below then takes its fused path instead of one small kernel per parameter
-                self.pgrads = [g if g is None or g.is_contiguous() else g.contiguous() for g in self.pgrads]
-        finally:
-            keep.__exit__()
-            ops.set_timer(prev_timer)
+            self.graph_bwd = cap.capture(self._capture_backward, share_pool=self.graph_fwd)
 
     def _forward(self):
         with pool_feed(self.pool_idx):
             return self.net(self.PC, self.obj_id)
+
+    def _warm(self):
+        outs = self._forward()
+        live = [o for o in outs if o is not None and o.requires_grad]
+        torch.autograd.grad(live, self.params, [torch.zeros_like(o) for o in live], allow_unused=True)
+
+    def _capture_forward(self):
+        outs = self._forward()
+        self.none_mask = [o is None for o in outs]
+        self.outs = [o for o in outs if o is not None]
+
+    def _capture_backward(self):
+        with ops.StepFolds(bare_wgrad=True):            # (before the .contiguous() copies below read the gradients)
+            self.pgrads = list(torch.autograd.grad(self.outs, self.params, self.gouts, allow_unused=True))
+        # contiguous static gradients (copies inside the graph where autograd hands back a transposed view): the
+        # multi-tensor add of the node then takes its fused path instead of one small kernel per parameter
+        self.pgrads = [g if g is None or g.is_contiguous() else g.contiguous() for g in self.pgrads]
 
     def __call__(self, PC, obj_id):
         if PC.shape != self.PC.shape:

@@ -4,6 +4,7 @@ import ctypes, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from hs_pose_amd import ops
+from hs_pose_amd.graph import capture_scope
 from hs_pose_amd._lib import lib
 
 dev = torch.device("cuda:0")
@@ -12,14 +13,12 @@ L = lib()
 
 def timeit(fn, reps=10, rounds=3):
     fn(); torch.cuda.synchronize()
-    g = torch.cuda.CUDAGraph()
-    s = torch.cuda.Stream(); s.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(s):
-        fn()
-    torch.cuda.current_stream().wait_stream(s); torch.cuda.synchronize()
-    with torch.cuda.graph(g):
+    def body():
         for _ in range(reps):
             fn()
+    with capture_scope() as cap:
+        cap.warm_up(fn)
+        g = cap.capture(body)
     g.replay(); torch.cuda.synchronize()
     best = 1e9
     for _ in range(rounds):

@@ -3,20 +3,19 @@ import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from hs_pose_amd import ops
+from hs_pose_amd.graph import capture_scope
 
 dev = torch.device("cuda:0")
 
 
 def timeit(fn, reps=20):
     fn(); torch.cuda.synchronize()
-    g = torch.cuda.CUDAGraph()
-    s = torch.cuda.Stream(); s.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(s):
-        fn()
-    torch.cuda.current_stream().wait_stream(s); torch.cuda.synchronize()
-    with torch.cuda.graph(g):
+    def body():
         for _ in range(reps):
             fn()
+    with capture_scope() as cap:
+        cap.warm_up(fn)
+        g = cap.capture(body)
     g.replay(); torch.cuda.synchronize()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record(); g.replay(); e1.record(); torch.cuda.synchronize()

@@ -3,6 +3,7 @@ import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from hs_pose_amd import ops
+from hs_pose_amd.graph import capture_scope
 M, N, K = (int(v) for v in sys.argv[1:4])
 nn = sys.argv[4] == "nn"
 dt = torch.bfloat16 if "bf16" in sys.argv else torch.float32
@@ -15,14 +16,12 @@ if not nn and "pitch" in sys.argv:
 out = torch.empty(M, N, device=dev, dtype=torch.float32 if "f32out" in sys.argv else dt)
 fn = lambda: ops.gemm_rows(A, B, nn, out=out)
 fn(); torch.cuda.synchronize()
-g = torch.cuda.CUDAGraph()
-s = torch.cuda.Stream(); s.wait_stream(torch.cuda.current_stream())
-with torch.cuda.stream(s):
-    fn()
-torch.cuda.current_stream().wait_stream(s); torch.cuda.synchronize()
-with torch.cuda.graph(g):
+def body():
     for _ in range(20):
         fn()
+with capture_scope() as cap:
+    cap.warm_up(fn)
+    g = cap.capture(body)
 g.replay(); torch.cuda.synchronize()
 best = 1e9
 for _ in range(5):

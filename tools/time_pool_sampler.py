@@ -21,6 +21,7 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "oracle")]
 import torch
+from hs_pose_amd.graph import capture_scope
 
 
 def window(fn, steps):
@@ -58,15 +59,9 @@ def graph_of(fn):
     for _ in range(3):
         fn()
     torch.cuda.synchronize()
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        fn()
-    torch.cuda.current_stream().wait_stream(side)
-    torch.cuda.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        fn()
+    with capture_scope() as cap:
+        cap.warm_up(fn)
+        g = cap.capture(fn)
     return g.replay
 
 

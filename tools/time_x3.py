@@ -4,6 +4,7 @@ import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from hs_pose_amd import ops
+from hs_pose_amd.graph import capture_scope
 
 dev = torch.device("cuda:0")
 SHAPES = [(16448, 1024, 128, 0, "bias"), (4112, 2048, 128, 0, "bias"), (4112, 2048, 256, 0, "bias"), (1024, 4096, 256, 0, "bias"),
@@ -22,14 +23,12 @@ for (M, N, K1, K2, epi) in SHAPES:
     with ops.x3_scope(planes):
         fn = lambda i: ops.gemm_x3(A1, B1, True, A2, B2, False, bias=bias, out=outs[i % 4])
         fn(0); torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-        s = torch.cuda.Stream(); s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            fn(0)
-        torch.cuda.current_stream().wait_stream(s); torch.cuda.synchronize()
-        with torch.cuda.graph(g):
+        def body():
             for i in range(20):
                 fn(i)
+        with capture_scope() as cap:
+            cap.warm_up(lambda: fn(0))
+            g = cap.capture(body)
     g.replay(); torch.cuda.synchronize()
     best = 1e9
     for _ in range(5):
