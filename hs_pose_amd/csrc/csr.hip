@@ -161,6 +161,13 @@ static size_t rev_build_lds(int Nsrc, int Nq, int k, bool* in_lds) {
     return *in_lds ? lds1 : lds0;
 }
 extern "C" int hsp_rev_build_takes(int n_src) { return n_src > 0 && (size_t)n_src + 1 <= REV_BUILD_LDS / sizeof(int) ? 1 : 0; }
+// which form a map takes: 1 edges assembled in LDS, 0 in global memory, -1 declined (rev_build_lds, as the launches ask it)
+extern "C" int hsp_rev_build_edges_in_lds(int n_src, int n_q, int k) {
+    if (n_q <= 0 || k <= 0 || !hsp_rev_build_takes(n_src)) return -1;
+    bool in_lds;
+    rev_build_lds(n_src, n_q, k, &in_lds);
+    return in_lds ? 1 : 0;
+}
 
 extern "C" int hsp_rev_build(const int32_t* idx, int B, int Nq, int Nsrc, int k, int kstride, int32_t* rev_off,
                              int32_t* rev_edge, hspStream_t stream) {

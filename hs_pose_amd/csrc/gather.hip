@@ -423,7 +423,8 @@ __global__ __launch_bounds__(256) void colsum_partial_scalar_kernel(const float*
 //   kind 3: (long) src[b] == c ? 1 : 0   -- the one-hot category columns built in place from the (B) float ids
 //           (FaceRecon.py:80-85: zeros + scatter_ were three launches)
 // (bf16 build: kind 0 / 1 sources are bf16 like the output, kind 2 -- the per-cloud one-hot row -- stays fp32 and is
-// rounded on the way in; W is the output ROW PITCH, which may exceed the sum of the widths: padding columns stay untouched)
+// rounded on the way in; W is the output ROW PITCH, which may exceed the sum of the widths: the 16-byte form zeroes ALL W - used
+// padding columns of a row, the pair and scalar forms leave them untouched)
 struct ConcatSeg { const void* src; const int32_t* idx; int width; int kind; int nsrc; int col0; };
 struct ConcatDesc { ConcatSeg seg[8]; int nseg; int even; int q0[9]; };      // q0: first 16-byte chunk of each segment (even == 2)
 
@@ -454,8 +455,9 @@ __global__ __launch_bounds__(256) void concat_rows_kernel(ConcatDesc d, int B, i
                 reinterpret_cast<uint4*>(o + sg.col0)[c] = reinterpret_cast<const uint4*>(src)[c];
             }
             // padding columns of a pitched row (1286 -> 1288): zeroed, so a consumer that reads whole 16-byte chunks sees no garbage
+            // (a loop: a pitch more than 64 elements above the used width has more padding columns than the wave has lanes)
             const int used = d.seg[d.nseg - 1].col0 + d.seg[d.nseg - 1].width;
-            if (lane < W - used) Feat<FT>::st(o + used + lane, 0.f);
+            for (int c = used + lane; c < W; c += 64) Feat<FT>::st(o + c, 0.f);
         }
         return;
     }
@@ -850,13 +852,32 @@ extern "C" int hsp_colsum_rows_takes(int C, int elem_bytes) {
 }
 extern "C" int hsp_colsum_rows_xyz_takes(int C) { return colsum_vec4(C) ? 1 : 0; }
 
+// row lanes of a 256-thread workgroup: 256 / (C/4) in the four-column form, 256 / C (one column per lane) in the scalar form
+static int colsum_row_lanes(int C) { return colsum_vec4(C) ? 256 / (C >> 2) : (C <= 256 ? 256 / C : 1); }
 static int chunk_rows(int B, int N, int C) {
-    const int RL = colsum_vec4(C) ? 256 / (C >> 2) : (C <= 256 ? 256 / C : 1);
+    const int RL = colsum_row_lanes(C);
     long long r = ((long long)B * N + 511) / 512;           // ~512 workgroups ...
     if (r < (N + 31) / 32) r = (N + 31) / 32;               // ... but at most 32 chunks per cloud for the serial fold
     if (r < RL) r = RL;
     if (r > ORL_ROWS) r = ORL_ROWS;
     return (int)r;
+}
+
+// the chunking of hsp_colsum_rows(_bf16) / hsp_colsum_rows_xyz(_bf16) / hsp_colsum_cloud_f32 for a shape, from the functions the
+// launches themselves use
+extern "C" int hsp_colsum_rows_plan(int B, int N, int C, int elem_bytes, int* rows, int* nchunk, int* row_lanes, int* form) {
+    if (B <= 0 || N <= 0 || C <= 0 || (elem_bytes != 2 && elem_bytes != 4) || !rows || !nchunk || !row_lanes || !form)
+        return HSP_ERR_BAD_ARG;
+    if (!hsp_colsum_rows_takes(C, elem_bytes)) {
+        *rows = *nchunk = *row_lanes = 0;
+        *form = -1;
+        return HSP_OK;
+    }
+    *rows = chunk_rows(B, N, C);
+    *nchunk = (N + *rows - 1) / *rows;
+    *row_lanes = colsum_row_lanes(C);
+    *form = colsum_vec4(C) ? 0 : 1;
+    return HSP_OK;
 }
 
 static int stream_grid(long long threads) {

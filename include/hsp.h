@@ -221,6 +221,11 @@ int hsp_rf_conv_bwd(const float *xyz, const float *dirs, const float *fm, const 
 /* 1 where hsp_rev_build, hsp_rev_build_sel and (per map) hsp_rev_build_multi take a cloud of n_src source rows: its histogram of
  * n_src + 1 counters within 140 KB of LDS (n_src <= 35 839) -- the function those entry points themselves decline by */
 int hsp_rev_build_takes(int n_src);
+/* the form a map of n_q queries with k slots each over n_src source rows takes in those entry points: 1 -- the cloud's edges are
+ * assembled and sorted in LDS ((n_src + 1) * 4 + n_q * k * 4 bytes <= 140 KiB), 0 -- in global memory (rev_edge itself), -1 --
+ * declined (hsp_rev_build_takes(n_src) == 0, or n_q / k <= 0).  The same rev_off / rev_edge either way; answered by the
+ * function the launches pick their kernel with. */
+int hsp_rev_build_edges_in_lds(int n_src, int n_q, int k);
 int hsp_rev_build(const int32_t *idx, int B, int Nq, int Nsrc, int k, int kstride, int32_t *rev_off,
                   int32_t *rev_edge, hspStream_t stream);
 /* nmaps <= 4 such indices over the same B clouds in ONE launch (map i: idx[i], Nq[i], Nsrc[i], k[i], kstride[i] ->
@@ -374,13 +379,27 @@ int hsp_layer_out_exact_f32(const float *F, int ldf, const float *Wa, int ldwa, 
 /* 1 where hsp_colsum_rows (elem_bytes 4) / hsp_colsum_rows_bf16 (2) take rows of C columns: C a multiple of 4 with C/4 | 256, fp32
  * rows also any C <= 256 -- the function those entry points themselves decline by */
 int hsp_colsum_rows_takes(int C, int elem_bytes);
+/* The chunking of the per-cloud column sums -- hsp_colsum_rows (elem_bytes 4), hsp_colsum_rows_bf16 (2), hsp_colsum_rows_xyz(_bf16)
+ * and hsp_colsum_cloud_f32 where they take the shape -- from the functions the launches use.  A cloud's N rows are cut into
+ * *nchunk chunks of *rows rows (the last may be shorter); a workgroup sums a chunk with *row_lanes row lanes, lane l adding rows
+ * l, l + row_lanes, ... of the chunk one by one from +0; the lanes are folded in ascending order from lane 0; the chunk sums are
+ * folded as eight running sums over chunk (chunk ch into sum ch % 8, ascending) combined pairwise
+ * ((s0 + s1) + (s2 + s3)) + ((s4 + s5) + (s6 + s7)): at most ceil(rows / row_lanes) + (row_lanes - 1) + ceil(nchunk / 8) + 3
+ * additions on the path of any row.  *form: 0 -- four columns per lane (C a multiple of 4 with C/4 | 256), 1 -- one column per
+ * lane (fp32 rows of any other C <= 256), -1 -- hsp_colsum_rows_takes(C, elem_bytes) is 0 (then the other three are 0).
+ * Returns HSP_OK, or HSP_ERR_BAD_ARG (nothing written) for a size <= 0, elem_bytes other than 2 / 4 or a NULL pointer. */
+int hsp_colsum_rows_plan(int B, int N, int C, int elem_bytes, int *rows, int *nchunk, int *row_lanes, int *form);
 int hsp_colsum_rows(const float *x, int B, int N, int C, float *out, void *ws, size_t ws_bytes,
                     hspStream_t stream);
 
 /* out (B,N,C) += f (B,N,C) + t (B,C) broadcast over the points: the "+ feature" residual and the per-cloud
- * half of conv2 of an HS layer (gcn3d.py:112,186) in one pass. */
+ * half of conv2 of an HS layer (gcn3d.py:112,186) in one pass.  Association: out = fl(out + fl(f + t[b])), both additions
+ * rounded to fp32.  C % 4 != 0: HSP_ERR_UNSUPPORTED. */
 /* out (R, C) = (ga + gb) * [y > 0]: the backward of relu(conv_0(...)) (FaceRecon.py:88) fused with the sum of the two gradients
- * that reach fm_0 (conv_1 and the concat); ga / gb rows of an even pitch lda / ldb (8-byte aligned), gb may be NULL; C even */
+ * that reach fm_0 (conv_1 and the concat); ga / gb rows of an even pitch lda / ldb (8-byte aligned), gb may be NULL; C even
+ * (an odd C, lda or ldb: HSP_ERR_UNSUPPORTED).  The mask is the fp32 comparison y > 0: a positive subnormal passes the gradient,
+ * +0 and -0 give 0 -- as ATen's threshold_backward -- and y = NaN gives 0 (the comparison is false), where threshold_backward
+ * passes the gradient: a NaN activation is an upstream fault, not a case the two promise to agree on. */
 int hsp_add_relu_bwd(const float *ga, int lda, const float *gb, int ldb, const float *y, int R, int C, float *out,
                      hspStream_t stream);
 int hsp_residual_bias(float *out, const float *f, const float *t, int B, int N, int C, hspStream_t stream);
@@ -1102,7 +1121,13 @@ int hsp_orl_global_fwd_bf16(const hsp_bf16_t *feat, const int32_t *idx, int B, i
 int hsp_colsum_rows_bf16(const hsp_bf16_t *x, int B, int N, int C, float *out, void *ws, size_t ws_bytes,
                          hspStream_t stream);
 /* out_pitch: row pitch of out in elements (>= sum of widths; padding columns are zeroed when every segment is 16-byte
- * aligned -- the feat assembly -- and left untouched otherwise).  bf16 form: kind 0 / 1
+ * aligned -- the feat assembly -- and left untouched otherwise).  Three forms, the same copy in each: 16-BYTE chunks where
+ * out_pitch, the address of out and every kind 0 / 1 segment's width, first column and source address are multiples of 16 bytes
+ * (kind 2 / 3 segments of any width: they only move the columns after them) -- the one form that writes the padding, ALL
+ * out_pitch - sum of widths columns of every row, with zeros; element PAIRS where the same holds for two elements; SCALARS
+ * otherwise.  nseg outside 1 .. 8, a NULL source, a width <= 0, a kind outside 0 .. 3, a kind 1 segment without idx, or
+ * out_pitch below the sum of the widths: HSP_ERR_BAD_ARG.  A kind 3 id is truncated toward zero ((long) id == column); an id
+ * outside [0, width) gives an all-zero segment.  bf16 form: kind 0 / 1
  * sources are bf16, kind 2 (per-cloud rows) and kind 3 (the (B) float
  * category ids, expanded to one-hot columns in place) fp32 */
 int hsp_concat_rows_pitched(int nseg, const float *const *src, const int32_t *const *idx, const int *width, const int *kind,
