@@ -60,15 +60,61 @@ struct RangerArgs {
     int adaptive, lookahead, gc_after;
 };
 
-// one wave per row
+// The device's decision on one replay of the training step (include/hsp.h: the control block).  One wave, one lane, ordinary
+// loads and stores: the launches behind it on the stream read what it wrote.
+__global__ __launch_bounds__(64) void step_gate_kernel(const float* __restrict__ total, const int* __restrict__ info,
+                                                       int* __restrict__ ctl, int horizon) {
+    if (threadIdx.x != 0) return;
+    if (ctl[HSP_STEP_CTL_ARMED] == 0) {                    // warm-up runs of a capture: no step, no count
+        ctl[HSP_STEP_CTL_APPLY] = 0;
+        return;
+    }
+    ctl[HSP_STEP_CTL_REPLAYS] += 1;
+    int apply = 0;
+    const int applied = ctl[HSP_STEP_CTL_APPLIED];
+    if (isnan(total[0])) {                                 // NaN only (math.isnan, engine/train.py:91-95): +-inf is no skip
+        ctl[HSP_STEP_CTL_SKIPPED_NAN] += 1;
+    } else if (info && info[0] == 0) {                     // no good item: the network ran on the stand-in cloud
+        ctl[HSP_STEP_CTL_SKIPPED_NO_ITEM] += 1;
+    } else if (applied >= horizon) {                       // the table has no entry for this step
+        ctl[HSP_STEP_CTL_EXHAUSTED] = 1;
+    } else {
+        apply = 1;
+        ctl[HSP_STEP_CTL_INDEX] = applied;
+        ctl[HSP_STEP_CTL_APPLIED] = applied + 1;
+    }
+    ctl[HSP_STEP_CTL_APPLY] = apply;
+}
+
+struct StepEntry {          // mirrors HspStepEntry (include/hsp.h)
+    float step_lr;
+    int flags;
+};
+
+// one wave per row.  ctl == nullptr (hsp_ranger_step): step_lr / adaptive / lookahead are the host's, in `a`.  Otherwise
+// (hsp_ranger_step_gated) the wave leaves unless the gate said apply, and takes the three from the table entry the gate named;
+// everything below the head is the same code for both.
 __global__ __launch_bounds__(256) void ranger_rows_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                           float* __restrict__ m, float* __restrict__ v,
                                                           float* __restrict__ slow,
                                                           const RowDesc* __restrict__ rows, int nrows,
-                                                          const float* __restrict__ gnorm_sq, RangerArgs a) {
+                                                          const float* __restrict__ gnorm_sq,
+                                                          const StepEntry* __restrict__ table, const int* __restrict__ ctl,
+                                                          int horizon, RangerArgs a) {
     const int lane = threadIdx.x & 63;
     const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= nrows) return;
+    bool fill_slow = false;
+    if (ctl) {
+        if (ctl[HSP_STEP_CTL_APPLY] == 0) return;
+        const int idx = ctl[HSP_STEP_CTL_INDEX];
+        if (idx < 0 || idx >= horizon) return;             // (the gate never names such an entry)
+        const StepEntry en = table[idx];
+        a.step_lr = en.step_lr;
+        a.adaptive = (en.flags & HSP_STEP_ADAPTIVE) != 0;
+        a.lookahead = (en.flags & HSP_STEP_LOOKAHEAD) != 0;
+        fill_slow = (en.flags & HSP_STEP_FILL_SLOW) != 0;
+    }
     const RowDesc rd = rows[r];
     float clip = 1.0f;
     if (gnorm_sq) {                                        // clip_grad_norm_: coef = max_norm / (norm + 1e-6), capped at 1
@@ -80,6 +126,8 @@ __global__ __launch_bounds__(256) void ranger_rows_kernel(float* __restrict__ p,
     float* mp = m + rd.offset;
     float* vp = v + rd.offset;
     float* sp = slow + rd.offset;
+    if (fill_slow)                                         // first step: slow weights = the weights now (ranger2020.py:168-170);
+        for (int e = lane; e < rd.len; e += 64) sp[e] = pp[e];     // each lane reads back below only what it stored itself
     // gradient centralisation (ranger2020.py:31-41, gc_loc=True): g -= mean over all dims but the first
     float mean = 0.f;
     if (rd.gc && !a.gc_after) {
@@ -185,6 +233,29 @@ extern "C" int hsp_ranger_step(float* params, const float* grads, float* exp_avg
     a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.weight_decay = weight_decay; a.step_lr = step_lr;
     a.la_alpha = la_alpha; a.max_norm = max_norm; a.adaptive = adaptive; a.lookahead = lookahead; a.gc_after = gc_after;
     hipLaunchKernelGGL(ranger_rows_kernel, dim3((nrows + 3) / 4), dim3(256), 0, as_stream(stream), params, grads, exp_avg,
-                       exp_avg_sq, slow, reinterpret_cast<const RowDesc*>(rows), nrows, gnorm_sq, a);
+                       exp_avg_sq, slow, reinterpret_cast<const RowDesc*>(rows), nrows, gnorm_sq,
+                       static_cast<const StepEntry*>(nullptr), static_cast<const int*>(nullptr), 0, a);
+    return check_launch();
+}
+
+extern "C" int hsp_step_gate(const float* total, const int32_t* info, int32_t* ctl, int horizon, hspStream_t stream) {
+    if (!total || !ctl || horizon <= 0) return HSP_ERR_BAD_ARG;
+    hipLaunchKernelGGL(step_gate_kernel, dim3(1), dim3(64), 0, as_stream(stream), total, info, ctl, horizon);
+    return check_launch();
+}
+
+extern "C" int hsp_ranger_step_gated(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* slow,
+                                     const HspRowDesc* rows, int nrows, float beta1, float beta2, float eps,
+                                     float weight_decay, float la_alpha, int gc_after, const float* gnorm_sq, float max_norm,
+                                     const HspStepEntry* table, const int32_t* ctl, int horizon, hspStream_t stream) {
+    if (!params || !grads || !exp_avg || !exp_avg_sq || !slow || !rows || nrows <= 0) return HSP_ERR_BAD_ARG;
+    if (!table || !ctl || horizon <= 0) return HSP_ERR_BAD_ARG;
+    static_assert(sizeof(StepEntry) == sizeof(HspStepEntry), "step entry layout");
+    RangerArgs a;
+    a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.weight_decay = weight_decay; a.step_lr = 0.f;
+    a.la_alpha = la_alpha; a.max_norm = max_norm; a.adaptive = 0; a.lookahead = 0; a.gc_after = gc_after;
+    hipLaunchKernelGGL(ranger_rows_kernel, dim3((nrows + 3) / 4), dim3(256), 0, as_stream(stream), params, grads, exp_avg,
+                       exp_avg_sq, slow, reinterpret_cast<const RowDesc*>(rows), nrows, gnorm_sq,
+                       reinterpret_cast<const StepEntry*>(table), ctl, horizon, a);
     return check_launch();
 }

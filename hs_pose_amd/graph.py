@@ -7,8 +7,9 @@
 * ``GraphedNetwork``    -- ``posenet`` forward / backward of the FULL model as two graphs behind one autograd node, for
   ``engine/train.py``'s step (losses and optimizer stay eager).
 * ``GraphedInference``  -- the timed body of ``evaluation/evaluate.py`` (eval forward + generate_RT).
-* ``GraphedTrainStep``  -- the whole training step incl. augmentation, losses, backward and the gradient norm as ONE graph
-  (+ one fused optimizer launch): what ``bench.py`` times as unit U3.
+* ``GraphedTrainStep``  -- the whole training step incl. augmentation, losses, backward and the gradient norm as ONE graph,
+  followed by one fused optimizer launch from the host (``apply='host'``, the default: what ``bench.py`` times as unit U3) or
+  with the optimizer launch, the schedule and the NaN skip inside the graph too (``apply='graph'``: a replay is the step).
 * ``capture_scope``     -- how all four are captured (timer off, state rolled back, warm-up on a side stream, ``thread_local``
   capture), stated once with its reasons; the timing scripts under ``tools/`` capture through it too.
 
@@ -329,7 +330,8 @@ class GraphedTrainStep:
 
         zero_grad -> HSPose.forward(do_loss=True) (augmentation, network, 19 losses) -> sum -> backward -> squared
         gradient norm                                              [captured once, replayed]
-        optimizer.step() (clip coefficient applied inside) ; scheduler.step()      [one launch + host scalars]
+        optimizer.step() (clip coefficient applied inside) ; scheduler.step()      [one launch + host scalars; with
+                                                                    apply='graph' gated on the device, inside the replay]
 
     Host work before each replay, in the reference's order on the CPU default generator: the jitter factors of
     ``defor_3D_pc`` (``torch.rand(PC.shape) * aug_pc_r``) and the two Pool_layer ``randperm`` draws; the augmentation's
@@ -362,12 +364,34 @@ class GraphedTrainStep:
     ``FLAGS.step_draws``).  Under a device sampler the captured body begins with the keyed draw of both Pool_layers' rows into the
     static index buffers and its augmentation is ``hsp_pose_augment_keyed``; there is no host work before a replay and no
     generator is touched: THE OWNER CALLS ``draws.advance()`` BEFORE EACH ``replay()`` / ``run()`` (the 16-byte key upload), and
-    equal sampler states replay equal steps.  Building the object leaves the sampler's state as it found it."""
+    equal sampler states replay equal steps.  Building the object leaves the sampler's state as it found it.
 
-    def __init__(self, network, optimizer, batch, scheduler=None, max_norm=5, warmup=3, prologue=None, draws=None):
+    ``apply``: who applies the step.  'host' (default) is all of the above.  'graph': the body goes on, inside the capture, with
+    ``hsp_step_gate`` on the total loss (and on ``gate_info``, ``hsp_batch_select``'s info, when given) and the gated Ranger launch
+    (``solver.DeviceClock`` over ``Ranger.device_clock(scheduler, horizon)``).  ``replay()`` is then the
+    step, ``run()`` is ``replay()``, ``apply()`` raises, and ``run(check_nan=True)`` reads the device's decision back after the
+    replay -- it reports the skip, it no longer makes it.  Under device draws a ``run()`` is the owner's ``draws.advance()`` plus one
+    graph launch and nothing else.  ``horizon``: the number of applied steps tabulated (default: the rest of the scheduler's
+    ``total_iters``); a step past it is refused on the device (``exhausted``), build a new object to go on.
+      * The warm-up runs execute both new kernels UNARMED: parameters, moments, slow weights and counters stay as they were;
+        the constructor arms the gate once, after the capture.
+      * On a skipped step the BatchNorm running statistics HAVE moved: the forward ran before the loss was known.  The
+        reference behaves the same (its forward precedes its NaN test, engine/train.py:76-95).
+      * ``scheduler.step()`` and ``optimizer.step()`` are never called in this form.  THE SCHEDULER OBJECT, ``state[p]['step']``
+        AND THE GROUPS' ``lr`` ARE CURRENT ONLY AFTER ``optimizer.sync_clock()`` (one small copy and a wait; ``optimizer.state_dict()``
+        and ``TrainDriver.checkpoint()`` call it), which also returns the counters: applied, replays, skipped_nan,
+        skipped_no_item, exhausted.
+      * No gradient accumulation and no data parallelism in this form."""
+
+    def __init__(self, network, optimizer, batch, scheduler=None, max_norm=5, warmup=3, prologue=None, draws=None,
+                 apply="host", horizon=None, gate_info=None):
+        if apply not in ("host", "graph"):
+            raise ValueError(f"GraphedTrainStep: apply expects 'host' or 'graph', got {apply!r}")
         self.net, self.opt, self.sched, self.max_norm = network, optimizer, scheduler, max_norm
         self.batch = batch
         self._prologue = prologue
+        # apply='graph': tables and the UNARMED control block go up here, before the warm-up (an upload cannot be captured)
+        self.clock = optimizer.device_clock(scheduler, horizon, info=gate_info) if apply == "graph" else None
         PC = batch["PC"]
         B, N, _ = PC.shape
         self.n_points = N
@@ -381,6 +405,8 @@ class GraphedTrainStep:
             cap.warm_up(self._body, warmup)
             # capture ON THE WARM-UP STREAM: the parameters' gradient accumulators were bound to it by the warm-up backward
             self.graph = cap.capture(self._body, on_warmup_stream=True)
+        if self.clock is not None:
+            self.clock.arm()                                 # once, after the capture: from here on a replay is a step
 
     def _host_draws(self):
         if self.draws is not None:                           # device draws: everything is drawn inside the replay
@@ -424,6 +450,9 @@ class GraphedTrainStep:
         self.opt.clip_grad_norm_(self.max_norm)             # device scalar; consumed by the step() outside the graph
         self._gnorm_sq, self._max_norm = self.opt._gnorm_sq, self.opt._max_norm
         self.loss_dict, self.total = ld, total
+        if self.clock is not None:                          # apply='graph': the device decides on the loss, then steps or does not
+            self.clock.gate(total.detach())
+            self.clock.step()
 
     def _params_and_views(self):
         params, views = [], []
@@ -444,14 +473,19 @@ class GraphedTrainStep:
 
     def apply(self):
         """the fused optimizer launch (clip coefficient inside) and the scheduler, behind ``replay()``"""
+        if self.clock is not None:
+            raise RuntimeError("GraphedTrainStep(apply='graph'): the step is applied inside the replay; there is nothing to apply()")
         self.opt._gnorm_sq, self.opt._max_norm = self._gnorm_sq, self._max_norm
         self.opt.step()
         if self.sched is not None:
             self.sched.step()
 
     def run(self, check_nan=False):
-        """one training step; returns False when ``check_nan`` found a NaN loss (the reference's skip, train.py:91-95)."""
+        """one training step; returns False when ``check_nan`` found a NaN loss (the reference's skip, train.py:91-95).
+        ``apply='graph'``: the replay IS the step, and ``check_nan`` only reads the device's decision back (the one wait)."""
         self.replay()
+        if self.clock is not None:
+            return self.clock.applied_last() if check_nan else True
         if check_nan and bool(torch.isnan(self.total).any()):
             return False
         self.apply()

@@ -16,11 +16,14 @@ entries (views), so checkpoints written by either implementation load into the o
 import ctypes
 import math
 
+import numpy as np
 import torch
 from torch.optim.optimizer import Optimizer
 
 from . import ops
-from ._lib import HspError, HspRowDesc, lib
+from ._lib import (STEP_ADAPTIVE, STEP_CTL_APPLIED, STEP_CTL_APPLY, STEP_CTL_ARMED, STEP_CTL_EXHAUSTED, STEP_CTL_INDEX,
+                   STEP_CTL_REPLAYS, STEP_CTL_SKIPPED_NAN, STEP_CTL_SKIPPED_NO_ITEM, STEP_CTL_SLOTS, STEP_FILL_SLOW,
+                   STEP_LOOKAHEAD, HspError, HspRowDesc, lib)
 from .config import FLAGS
 
 _ROW_CHUNK = 4096          # 1-D tensors are cut into rows of at most this many elements
@@ -106,6 +109,122 @@ def _radam_step_size(step, beta1, beta2, thresh):
     return False, 1.0 / (1 - beta1 ** step)
 
 
+STEP_ENTRY = np.dtype([("step_lr", "<f4"), ("flags", "<i4")])       # HspStepEntry (include/hsp.h)
+
+
+def step_table(step0, epoch0, horizon, base_lr, factor, betas, k, n_sma_threshold, fill_slow=False):
+    """The host scalars of the next ``horizon`` applied steps of one parameter group, as the ``HspStepEntry`` rows
+    ``hsp_ranger_step_gated`` reads (a numpy array of ``STEP_ENTRY``).  Entry ``j`` is the step ``step0 + j + 1`` taken at the
+    learning rate ``base_lr * factor(epoch0 + j)`` -- what ``LambdaLR`` holds after ``epoch0 + j`` scheduler steps --:
+
+      step_lr   ``step_size * lr`` by the expressions of ``Ranger.step()`` (``_radam_step_size``, Python doubles), rounded to
+                fp32 once: the bits the host path hands ``hsp_ranger_step`` by value
+      flags     STEP_ADAPTIVE (N_sma > threshold) | STEP_LOOKAHEAD (step % k == 0) | on entry 0 only, with ``fill_slow``,
+                STEP_FILL_SLOW (the slow weights are taken from the weights before that step)
+
+    ``factor`` is the scheduler's own lambda, called here on the host: any schedule works, and the device does no arithmetic
+    on the clock at all (a device ``pow`` / ``cos`` would match the host's libm to an ulp only, and the step would stop being the
+    host path's bit for bit).  Pure: no device, no optimizer."""
+    horizon = int(horizon)
+    if horizon < 1:
+        raise ValueError(f"step_table: expects horizon >= 1, got {horizon}")
+    beta1, beta2 = betas
+    out = np.zeros(horizon, dtype=STEP_ENTRY)
+    for j in range(horizon):
+        step = int(step0) + j + 1
+        lr = base_lr * factor(int(epoch0) + j)
+        adaptive, step_size = _radam_step_size(step, beta1, beta2, n_sma_threshold)
+        out["step_lr"][j] = np.float32(step_size * lr)
+        out["flags"][j] = (STEP_ADAPTIVE if adaptive else 0) | (STEP_LOOKAHEAD if step % k == 0 else 0)
+    if fill_slow:
+        out["flags"][0] |= STEP_FILL_SLOW
+    return out
+
+
+class DeviceClock:
+    """The step count, the schedule and the skip decision of a ``Ranger`` kept ON THE DEVICE (``Ranger.device_clock``), so that
+    the optimizer launch can be captured in the training step's graph: one ``step_table`` per parameter group, uploaded once,
+    and the sixteen-slot control block of include/hsp.h.  ``gate(total)`` issues ``hsp_step_gate`` -- the device decides whether
+    this replay's step is applied (NaN loss, no good item, table used up: no) and names the table entry --, ``step()`` one
+    ``hsp_ranger_step_gated`` per group.  Neither reads or writes a host counter: ``state[p]['step']``, the scheduler and the
+    groups' ``lr`` are current only after ``Ranger.sync_clock()``.
+
+    The block is built UNARMED: the gate then answers "do not apply" and counts nothing, so the warm-up runs of a capture
+    execute both kernels and leave parameters, optimizer state and counters as they were.  ``arm()`` uploads armed = 1."""
+
+    COUNTERS = ("applied", "replays", "skipped_nan", "skipped_no_item", "exhausted")
+
+    def __init__(self, optimizer, scheduler, horizon, info=None):
+        self.opt, self.sched, self.info = optimizer, scheduler, info
+        if horizon is None:
+            if scheduler is None or not hasattr(scheduler, "total_iters"):
+                raise ValueError("device_clock: horizon=None needs a scheduler that records total_iters "
+                                 "(flat_and_anneal_lr_scheduler does); give the number of steps to tabulate")
+            horizon = int(scheduler.total_iters) - int(scheduler.last_epoch)
+        self.horizon = int(horizon)
+        if self.horizon < 1:
+            raise ValueError(f"device_clock: expects horizon >= 1, got {self.horizon}")
+        if info is not None and (not info.is_cuda or info.dtype != torch.int32 or info.numel() < 1):
+            raise ValueError("device_clock: info expects hsp_batch_select's int32 device tensor")
+        dev = optimizer._flat[0].flat_p.device
+        self.ctl = torch.zeros(STEP_CTL_SLOTS, dtype=torch.int32, device=dev)
+        self.tables = [torch.zeros(self.horizon * STEP_ENTRY.itemsize, dtype=torch.uint8, device=dev) for _ in optimizer._flat]
+        self.tables_host = None
+        self.rebuild()
+
+    def rebuild(self):
+        """tabulate the next ``horizon`` steps from the optimizer's and the scheduler's counts AS THEY STAND ON THE HOST, into
+        the same device buffers (a captured graph keeps reading them), and zero the device counters; the armed flag stays"""
+        opt, sch = self.opt, self.sched
+        self.epoch0 = int(sch.last_epoch) if sch is not None else 0
+        self.sched_count0 = int(getattr(sch, "_step_count", 0)) if sch is not None else 0
+        self.step0, self.slow_ready0, self.tables_host = [], [], []
+        for g, (group, fg) in enumerate(zip(opt.param_groups, opt._flat)):
+            step0 = int(opt.state[fg.params[0]]["step"])
+            base_lr, factor = (sch.base_lrs[g], sch.lr_lambdas[g]) if sch is not None else (group["lr"], lambda x: 1.0)
+            tab = step_table(step0, self.epoch0, self.horizon, base_lr, factor, group["betas"], group["k"],
+                             opt.N_sma_threshhold, fill_slow=not fg.slow_ready)
+            self.tables[g].copy_(torch.from_numpy(tab.view(np.uint8)))
+            self.step0.append(step0)
+            self.slow_ready0.append(bool(fg.slow_ready))
+            self.tables_host.append(tab)
+        self.ctl[1:].zero_()
+
+    def arm(self, on=True):
+        self.ctl[STEP_CTL_ARMED:STEP_CTL_ARMED + 1].fill_(1 if on else 0)
+
+    def gate(self, total):
+        if not total.is_cuda or total.dtype != torch.float32 or total.numel() != 1:
+            raise HspError(f"DeviceClock.gate: expects the fp32 total loss on the device, got {total.dtype} {tuple(total.shape)}")
+        ops._run("hsp_step_gate", (ops._p(total), ops._p(self.info), ops._p(self.ctl), self.horizon, ops._stream()))
+
+    def step(self):
+        opt = self.opt
+        for group, fg, table in zip(opt.param_groups, opt._flat, self.tables):
+            opt._collect_grads(fg)
+            beta1, beta2 = group["betas"]
+            rows = fg.rows_for(opt.use_gc, opt.gc_conv_only)
+            ops._run("hsp_ranger_step_gated",
+                     (ops._p(fg.flat_p), ops._p(fg.flat_g), ops._p(fg.flat_m), ops._p(fg.flat_v), ops._p(fg.flat_s),
+                      ops._p(rows), fg.nrows, beta1, beta2, group["eps"], group["weight_decay"], opt.alpha,
+                      int(not opt.gc_loc), ops._p(opt._gnorm_sq), opt._max_norm, ops._p(table), ops._p(self.ctl),
+                      self.horizon, ops._stream()),
+                     key=f"n{fg.total}", abytes=fg.total * 44)
+        opt._gnorm_sq = None
+
+    def read(self):
+        """the control block, one small device->host copy (a wait): {'armed', 'apply', 'index', 'applied', 'replays',
+        'skipped_nan', 'skipped_no_item', 'exhausted'}"""
+        c = self.ctl.cpu().tolist()
+        return dict(armed=c[STEP_CTL_ARMED], apply=c[STEP_CTL_APPLY], index=c[STEP_CTL_INDEX], applied=c[STEP_CTL_APPLIED],
+                    replays=c[STEP_CTL_REPLAYS], skipped_nan=c[STEP_CTL_SKIPPED_NAN],
+                    skipped_no_item=c[STEP_CTL_SKIPPED_NO_ITEM], exhausted=c[STEP_CTL_EXHAUSTED])
+
+    def applied_last(self):
+        """the device's decision on the last replay (a wait)"""
+        return bool(int(self.ctl[STEP_CTL_APPLY]))
+
+
 class Ranger(Optimizer):
     """RAdam + Lookahead + gradient centralisation; arguments and defaults of ranger2020.py:45-58."""
 
@@ -128,6 +247,7 @@ class Ranger(Optimizer):
         self._flat = [_FlatGroup(g["params"]) for g in self.param_groups]
         self._gnorm_sq = None            # device scalar written by clip_grad_norm_, consumed by the next step()
         self._max_norm = 0.0
+        self._clock = None               # a DeviceClock (device_clock()): the step count then lives on the device
         for fg in self._flat:
             for p, o in zip(fg.params, fg.offsets):
                 self.state[p] = dict(step=0, exp_avg=fg.view(fg.flat_m, p, o), exp_avg_sq=fg.view(fg.flat_v, p, o),
@@ -191,6 +311,9 @@ class Ranger(Optimizer):
     @torch.no_grad()
     def step(self, closure=None):
         loss = None
+        if self._clock is not None:
+            raise HspError("Ranger.step(): a device clock is attached (device_clock()): the step is DeviceClock.step(), gated on "
+                           "the device, and a host step would leave the device's count behind")
         for group, fg in zip(self.param_groups, self._flat):
             self._collect_grads(fg)
             if not fg.slow_ready:                                  # first step of this group: slow weights = weights now
@@ -213,9 +336,60 @@ class Ranger(Optimizer):
         self._gnorm_sq = None
         return loss
 
+    # -- the step clock on the device ------------------------------------------------------------------------
+    def device_clock(self, scheduler=None, horizon=None, info=None):
+        """Attach and return a ``DeviceClock``: the next ``horizon`` steps tabulated from this optimizer's step counts and
+        ``scheduler``'s epoch (a ``LambdaLR``; None: the groups' ``lr`` as they stand), and an unarmed control block.
+        ``horizon`` None: the rest of the schedule, ``scheduler.total_iters - scheduler.last_epoch``.  ``info``:
+        ``hsp_batch_select``'s device tensor when the gate is to skip a batch without a good item.
+
+        FROM HERE ON ``step()`` raises and ``scheduler.step()`` is never to be called: the counts advance on the device, and
+        ``state[p]['step']``, ``scheduler.last_epoch`` and the groups' ``lr`` are current only after ``sync_clock()``
+        (``state_dict()`` and ``TrainDriver.checkpoint()`` call it).  Not offered with gradient accumulation or more than one
+        rank: the ranks' gates could disagree."""
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            raise HspError("Ranger.device_clock: not offered with more than one rank (each rank's gate would decide on its own loss)")
+        if scheduler is not None and not hasattr(scheduler, "lr_lambdas"):
+            raise ValueError("Ranger.device_clock: expects a LambdaLR scheduler (its lr_lambdas are tabulated) or None")
+        if self._clock is not None:                        # a new clock starts from where the old one got to
+            self.sync_clock()
+        self._clock = DeviceClock(self, scheduler, horizon, info)
+        return self._clock
+
+    def sync_clock(self):
+        """One small device->host copy of the control block (a wait); the host's mirror is set to what the host-driven path would
+        hold after the ``applied`` steps the device has taken since the tables were built: every ``state[p]['step']``, the groups'
+        ``slow_ready``, ``scheduler.last_epoch`` / ``_last_lr`` / ``_step_count`` and each group's ``lr``.  Returns the counters."""
+        ck = self._clock
+        if ck is None:
+            raise HspError("Ranger.sync_clock: no device clock attached")
+        c = ck.read()
+        n = c["applied"]
+        for g, (group, fg) in enumerate(zip(self.param_groups, self._flat)):
+            for p in fg.params:
+                self.state[p]["step"] = ck.step0[g] + n
+            fg.slow_ready = ck.slow_ready0[g] or n > 0
+        sch = ck.sched
+        if sch is not None:
+            sch.last_epoch = ck.epoch0 + n
+            sch._step_count = ck.sched_count0 + n
+            lrs = [base * lmbda(sch.last_epoch) for base, lmbda in zip(sch.base_lrs, sch.lr_lambdas)]      # LambdaLR.get_lr
+            for group, lr in zip(self.param_groups, lrs):
+                group["lr"] = lr
+            sch._last_lr = lrs
+        return c
+
     # -- checkpoints -----------------------------------------------------------------------------------------
+    def state_dict(self):
+        if self._clock is not None:
+            self.sync_clock()
+        return super().state_dict()
+
     def load_state_dict(self, state_dict):
-        """accepts checkpoints of the reference Ranger (per-parameter tensors): values are copied into the flat state."""
+        """accepts checkpoints of the reference Ranger (per-parameter tensors): values are copied into the flat state.  With a
+        device clock attached its tables are rebuilt from the loaded counts and the device counters zeroed -- from the
+        scheduler AS IT STANDS: one loaded afterwards needs ``clock.rebuild()`` (``TrainDriver.load_checkpoint`` does it)."""
         super().load_state_dict(state_dict)
         for fg in self._flat:
             # a checkpoint written after >= 1 step carries every slow_buffer; one without them -- or one this optimizer wrote BEFORE
@@ -229,6 +403,8 @@ class Ranger(Optimizer):
                         v.copy_(st[name])
                     st[name] = v
                 st["step"] = int(st.get("step", 0))
+        if self._clock is not None:
+            self._clock.rebuild()
 
 
 def clip_grad_norm_(optimizer, max_norm):
@@ -277,9 +453,11 @@ def flat_and_anneal_lr_scheduler(optimizer, total_iters, warmup_iters=0, warmup_
         raise ValueError("Only 'cosine', 'linear', 'poly', 'exp', 'step' or 'none' anneal_method accepted, got {}".format(anneal_method))
     if anneal_method != "step" and not 0 <= anneal_point <= 1:
         raise ValueError("anneal_point should be in [0,1], got {}".format(anneal_point))
-    return torch.optim.lr_scheduler.LambdaLR(
+    scheduler = torch.optim.lr_scheduler.LambdaLR(
         optimizer, lambda x: flat_and_anneal_factor(x, total_iters, warmup_iters, warmup_factor, warmup_method, anneal_point,
                                                     anneal_method, target_lr_factor, poly_power, step_gamma, steps))
+    scheduler.total_iters = total_iters            # (the length of the schedule: the default horizon of Ranger.device_clock)
+    return scheduler
 
 
 def build_optimizer(params):

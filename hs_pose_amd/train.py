@@ -82,7 +82,10 @@ class TrainDriver:
 
     def checkpoint(self, seed, epoch):
         """the dict engine/train.py:115-123 passes to torch.save (same keys, same sub-layouts); with a device sampler also
-        'draws': its (seed, call) state."""
+        'draws': its (seed, call) state.  With a device clock on the optimizer (``apply='graph'``) the host's mirror of the step
+        count and the schedule is brought up to date first (``Ranger.sync_clock``: one small copy, a wait)."""
+        if getattr(self.optimizer, "_clock", None) is not None:
+            self.optimizer.sync_clock()                        # before the scheduler is read below
         ckpt = {
             'seed': seed,
             'epoch': epoch,
@@ -102,6 +105,8 @@ class TrainDriver:
             self.optimizer.load_state_dict(ckpt['optimizer'])
         if 'scheduler' in ckpt:
             self.scheduler.load_state_dict(ckpt['scheduler'])
+        if getattr(self.optimizer, "_clock", None) is not None:
+            self.optimizer._clock.rebuild()                    # tables from the loaded step count AND the loaded epoch
         if self.draws is not None and 'draws' in ckpt:
             self.draws.set_state(ckpt['draws'])
         return ckpt.get('epoch', -1) + 1
@@ -110,7 +115,8 @@ class TrainDriver:
 class FrameTrainStep:
     """One training step from raw frames: a batch of ``M`` items with spares goes in, the first ``keep`` good ones are picked
     on the device, and augmentation, network, the 19 losses, backward and the squared gradient norm follow in the same
-    hipGraph; ``run()`` is one replay plus the fused optimizer launch.
+    hipGraph; ``run()`` is one replay followed by the fused optimizer launch -- or, with ``apply='graph'``, one replay that
+    holds the optimizer launch as well.
 
     ``frames``: depth (M,H,W) uint16 or fp32 mm and labels (M,H,W) uint8 on the device, inst_ids (M,), bboxes_xyxy (M,4) on the
     host, K (3,3) or (M,3,3).  ``items``: the per-item device tensors of ``HSPose.forward`` with M rows (obj_id, gt_R, gt_t,
@@ -144,10 +150,16 @@ class FrameTrainStep:
     device buffer (data, not a draw), the captured prologue begins with ``hsp_dzi_windows`` ('uniform' DZI only), the body with
     the Pool_layers' keyed rows, the augmentation is ``hsp_pose_augment_keyed``, and ``run()`` is ``sampler.advance()``, the
     replay, the check and the optimizer launch: no generator of the host's is touched, when the object is built or later, and
-    equal sampler states give equal steps."""
+    equal sampler states give equal steps.
+
+    ``apply='graph'`` (``horizon``: see ``GraphedTrainStep``): the gate on ``info`` and the loss's NaN flag, the schedule and the
+    optimizer launch are inside the replay too.  ``run(check=False)`` is then SAFE -- an all-rejected batch or a NaN loss leaves
+    parameters and optimizer state untouched and is counted on the device (``skipped_no_item``, ``skipped_nan``) -- and never
+    waits; ``run(check=True)`` reads the device's decision back and returns it.  The scheduler object and the optimizer's step
+    counts are current only after ``optimizer.sync_clock()``; on a skipped step the BatchNorm statistics have moved."""
 
     def __init__(self, network, optimizer, frames, items, keep, scheduler=None, sampler=None, n_pts=None, out_size=None,
-                 min_pts=50, mask_pro=None, max_norm=5, warmup=3, draws=None):
+                 min_pts=50, mask_pro=None, max_norm=5, warmup=3, draws=None, apply="host", horizon=None):
         depth = frames["depth"]
         dev = depth.device
         if depth.dim() != 3 or not 1 <= int(keep) <= depth.shape[0]:
@@ -196,7 +208,8 @@ class FrameTrainStep:
             self._windows()
         state = self.sampler.get_state()                        # (the eager warm-up calls advance; the captured call does not)
         self.graphed = GraphedTrainStep(network, optimizer, shapes, scheduler=scheduler, max_norm=max_norm, warmup=warmup,
-                                        prologue=front_end, draws=self.draws or "host")
+                                        prologue=front_end, draws=self.draws or "host",
+                                        apply=apply, horizon=horizon, gate_info=self.info if apply == "graph" else None)
         self.sampler.set_state(state)
 
     @staticmethod
@@ -254,6 +267,8 @@ class FrameTrainStep:
             self._windows()
         self.sampler.advance()
         self.graphed.replay()
+        if self.graphed.clock is not None:                      # apply='graph': the device decided inside the replay
+            return self.graphed.clock.applied_last() if check else True
         if check and bool((self.info[0] == 0) | torch.isnan(self.graphed.total).any()):
             return False
         self.graphed.apply()

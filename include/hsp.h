@@ -989,6 +989,61 @@ int hsp_ranger_step(float *params, const float *grads, float *exp_avg, float *ex
                     float step_lr, int adaptive, int lookahead, float la_alpha, int gc_after,
                     const float *gnorm_sq, float max_norm, hspStream_t stream);
 
+/* ---- the step applied on the device's own decision (training step as one replay) --------------------
+ * The two scalars hsp_ranger_step takes from the host per step -- step_lr and the adaptive / Lookahead switches -- come from
+ * a device TABLE the host fills once, one HspStepEntry per applied step to come (Ranger's own doubles, rounded to fp32 once:
+ * the bits the host path would have passed), and the decision whether a step is applied at all is made on the device by
+ * hsp_step_gate.  Both launches take only pointers and constants, so they can be captured in a graph.
+ *
+ * HspStepEntry.flags: HSP_STEP_ADAPTIVE (N_sma > threshold), HSP_STEP_LOOKAHEAD (step % k == 0), HSP_STEP_FILL_SLOW (slow :=
+ * the weights as they are BEFORE this step's update: the reference creates slow_buffer as a copy of the weights at the first
+ * step, ranger2020.py:168-170).
+ *
+ * The control block `ctl`: HSP_STEP_CTL_SLOTS int32 on the device.
+ *   slot 0  HSP_STEP_CTL_ARMED            written by the host only.  0: the gate answers "do not apply" and counts nothing
+ *   slot 1  HSP_STEP_CTL_APPLY            the gate's answer for this replay, written by every gate launch
+ *   slot 2  HSP_STEP_CTL_INDEX            the table entry of the step being applied (valid while apply == 1)
+ *   slot 3  HSP_STEP_CTL_APPLIED          steps applied since the table was built
+ *   slot 4  HSP_STEP_CTL_REPLAYS          armed gate launches
+ *   slot 5  HSP_STEP_CTL_SKIPPED_NAN      of those, skipped for a NaN loss
+ *   slot 6  HSP_STEP_CTL_SKIPPED_NO_ITEM  of those, skipped because no item of the batch was good
+ *   slot 7  HSP_STEP_CTL_EXHAUSTED        1 once a step was refused because the table had no entry left
+ *   slots 8-15 reserved: no launch writes them
+ *
+ * hsp_step_gate: one launch of one wave, one lane decides, rules in this order:
+ *   1. armed == 0: apply = 0, nothing else changes
+ *   2. replays += 1
+ *   3. isnan(*total): apply = 0, skipped_nan += 1      (NaN only, like math.isnan in engine/train.py:91-95: +-inf is applied)
+ *   4. else info != NULL and info[0] == 0: apply = 0, skipped_no_item += 1      (info: hsp_batch_select's [good items, ...])
+ *   5. else applied >= horizon: apply = 0, exhausted = 1
+ *   6. else apply = 1, index = applied, applied += 1
+ * HSP_ERR_BAD_ARG: total or ctl NULL, horizon <= 0.
+ *
+ * hsp_ranger_step_gated: hsp_ranger_step whose every wave first reads ctl[HSP_STEP_CTL_APPLY]: 0 (or an index outside
+ * [0, horizon)) and the wave returns having touched nothing; otherwise step_lr, adaptive and lookahead are those of
+ * table[ctl[HSP_STEP_CTL_INDEX]], a HSP_STEP_FILL_SLOW entry copies each row's weights into slow first, and the update is
+ * the very code of hsp_ranger_step (one kernel, built without fused multiply-adds: equal inputs give equal bits).
+ * HSP_ERR_BAD_ARG: what hsp_ranger_step declines, table or ctl NULL, horizon <= 0.
+ */
+#define HSP_STEP_ADAPTIVE 1
+#define HSP_STEP_LOOKAHEAD 2
+#define HSP_STEP_FILL_SLOW 4
+#define HSP_STEP_CTL_SLOTS 16
+#define HSP_STEP_CTL_ARMED 0
+#define HSP_STEP_CTL_APPLY 1
+#define HSP_STEP_CTL_INDEX 2
+#define HSP_STEP_CTL_APPLIED 3
+#define HSP_STEP_CTL_REPLAYS 4
+#define HSP_STEP_CTL_SKIPPED_NAN 5
+#define HSP_STEP_CTL_SKIPPED_NO_ITEM 6
+#define HSP_STEP_CTL_EXHAUSTED 7
+typedef struct HspStepEntry { float step_lr; int32_t flags; } HspStepEntry;
+int hsp_step_gate(const float *total, const int32_t *info, int32_t *ctl, int horizon, hspStream_t stream);
+int hsp_ranger_step_gated(float *params, const float *grads, float *exp_avg, float *exp_avg_sq, float *slow,
+                          const HspRowDesc *rows, int nrows, float beta1, float beta2, float eps, float weight_decay,
+                          float la_alpha, int gc_after, const float *gnorm_sq, float max_norm,
+                          const HspStepEntry *table, const int32_t *ctl, int horizon, hspStream_t stream);
+
 /* ---- Chamfer distance -------------------------------------------------------------------------
  * replaces cd.forward_cuda / cd.backward_cuda    tools/pyTorchChamferDistance/chamfer_distance.cpp:27-56
  * xyz1 (B,n,3), xyz2 (B,m,3) -> dist1 (B,n), dist2 (B,m) squared NN distances, idx1/idx2 int32 arg-min
