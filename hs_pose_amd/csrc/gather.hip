@@ -322,68 +322,32 @@ __global__ __launch_bounds__(256) void chunk_fold_kernel(const float* __restrict
     out[e] = chunk_fold8(part + (size_t)b * nchunk * C + c, nchunk, C) * scale;
 }
 
-// part[b][chunk][c] = sum of x[b][i][c] over the chunk's rows (first stage of a per-cloud column sum)
-template <typename FT>
-__global__ __launch_bounds__(256) void colsum_partial_kernel(const FT* __restrict__ x, int N, int C,
+// part[b][chunk][c] = sum of x[b][i][c] over the chunk's rows (first stage of a per-cloud column sum; colsum_cloud.h holds the
+// row loop and the row-lane fold).  XYZ: the sum and the three coordinate moments of the rows in one pass (HSlayer_surface
+// backward: gt = sum_i g and the STE weight gradient g^T xyz, gcn3d.py:85): part[b][chunk][slot][c], slot 0 = sum g,
+// slot 1..3 = sum g * (x, y, z)
+template <typename FT, bool XYZ>
+__global__ __launch_bounds__(256) void colsum_partial_kernel(const FT* __restrict__ x, const float* __restrict__ xyz, int N, int C,
                                                              float* __restrict__ part, int nchunk, int rows) {
-    __shared__ float4 red[256];
+    constexpr int NS = XYZ ? 4 : 1;
+    __shared__ float4 red[NS][256];
     const int cq = C >> 2;
     const int tid = threadIdx.x;
     const int g = tid % cq, rl = tid / cq, RL = 256 / cq;
     const int b = blockIdx.y, chunk = blockIdx.x;
     const int r0 = chunk * rows, r1 = min(N, r0 + rows);
-    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int i = r0 + rl; i < r1; i += RL) {
-        const float4 v = Feat<FT>::ld4(x + ((size_t)b * N + i) * C + (g << 2));
-        s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
-    }
-    red[tid] = s;
-    __syncthreads();
-    if (rl == 0) {
-        for (int l = 1; l < RL; ++l) { const float4 v = red[l * cq + g]; s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w; }
-        *reinterpret_cast<float4*>(part + ((size_t)b * nchunk + chunk) * C + (g << 2)) = s;
-    }
-}
-
-// colsum + the three coordinate moments of the rows in one pass (HSlayer_surface backward: gt = sum_i g and the STE weight
-// gradient g^T xyz, gcn3d.py:85): part[b][chunk][slot][c], slot 0 = sum g, slot 1..3 = sum g * (x, y, z)
-template <typename FT>
-__global__ __launch_bounds__(256) void colsum_xyz_partial_kernel(const FT* __restrict__ x, const float* __restrict__ xyz, int N, int C,
-                                                                 float* __restrict__ part, int nchunk, int rows) {
-    __shared__ float4 red[4][256];
-    const int cq = C >> 2;
-    const int tid = threadIdx.x;
-    const int g = tid % cq, rl = tid / cq, RL = 256 / cq;
-    const int b = blockIdx.y, chunk = blockIdx.x;
-    const int r0 = chunk * rows, r1 = min(N, r0 + rows);
-    float4 s[4];
+    float4 s[NS];
 #pragma unroll
-    for (int q = 0; q < 4; ++q) s[q] = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int i = r0 + rl; i < r1; i += RL) {
-        const float4 v = Feat<FT>::ld4(x + ((size_t)b * N + i) * C + (g << 2));
-        const float* p3 = xyz + ((size_t)b * N + i) * 3;
-        const float w[3] = {p3[0], p3[1], p3[2]};
-        s[0].x += v.x; s[0].y += v.y; s[0].z += v.z; s[0].w += v.w;
+    for (int q = 0; q < NS; ++q) s[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+    colsum_chunk_rows<XYZ, FT>(x, xyz, (size_t)b * N, C, g, r0 + rl, r1, RL, s);
 #pragma unroll
-        for (int q = 0; q < 3; ++q) {
-            // plain v_fma_f32, spelled out: hipcc packs these into v_pk_fma_f32 with op_sel picking the coordinate out of the
-            // loaded (x, y, z) register run, and that form returned wrong LOW halves (the .x / .z sums of the y moment, lanes 16-31
-            // of each half-wave) whenever another process's MFMA kernels shared the GPU -- 3-8 % of the replays, 1-3 % off
-            // (tools/dbg_ste2.py, tests/test_gpu_dp_shared.py); never alone on the GPU.  The scalar form has not deviated once.
-            s[q + 1].x = fma_plain(v.x, w[q], s[q + 1].x); s[q + 1].y = fma_plain(v.y, w[q], s[q + 1].y);
-            s[q + 1].z = fma_plain(v.z, w[q], s[q + 1].z); s[q + 1].w = fma_plain(v.w, w[q], s[q + 1].w);
-        }
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) red[q][tid] = s[q];
+    for (int q = 0; q < NS; ++q) red[q][tid] = s[q];
     __syncthreads();
     if (rl == 0) {
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            float4 a = s[q];
-            for (int l = 1; l < RL; ++l) { const float4 v = red[q][l * cq + g]; a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w; }
-            *reinterpret_cast<float4*>(part + (((size_t)b * nchunk + chunk) * 4 + q) * C + (g << 2)) = a;
-        }
+        for (int q = 0; q < NS; ++q)
+            *reinterpret_cast<float4*>(part + (((size_t)b * nchunk + chunk) * NS + q) * C + (g << 2)) =
+                colsum_lane_fold(s[q], red[q], 0, cq, g, RL);
     }
 }
 
@@ -1469,7 +1433,7 @@ extern "C" int hsp_colsum_rows(const float* x, int B, int N, int C, float* out, 
     const int nchunk = (N + rows - 1) / rows;
     float* part = reinterpret_cast<float*>(ws);
     if (colsum_vec4(C))
-        hipLaunchKernelGGL(colsum_partial_kernel<float>, dim3(nchunk, B), dim3(256), 0, st, x, N, C, part, nchunk, rows);
+        hipLaunchKernelGGL((colsum_partial_kernel<float, false>), dim3(nchunk, B), dim3(256), 0, st, x, nullptr, N, C, part, nchunk, rows);
     else
         hipLaunchKernelGGL(colsum_partial_scalar_kernel, dim3(nchunk, B), dim3(256), 0, st, x, N, C, part, nchunk, rows);
     hipLaunchKernelGGL(chunk_fold_kernel, dim3((B * C + 255) / 256), dim3(256), 0, st, part, B, nchunk, C, 1.0f, out);
@@ -1489,7 +1453,7 @@ static int colsum_rows_xyz_impl(const FT* x, const float* xyz, int B, int N, int
     const int rows = chunk_rows(B, N, C);
     const int nchunk = (N + rows - 1) / rows;
     float* part = reinterpret_cast<float*>(ws);
-    hipLaunchKernelGGL(colsum_xyz_partial_kernel<FT>, dim3(nchunk, B), dim3(256), 0, st, x, xyz, N, C, part, nchunk, rows);
+    hipLaunchKernelGGL((colsum_partial_kernel<FT, true>), dim3(nchunk, B), dim3(256), 0, st, x, xyz, N, C, part, nchunk, rows);
     hipLaunchKernelGGL(chunk_fold_kernel, dim3((B * 4 * C + 255) / 256), dim3(256), 0, st, part, B, nchunk, 4 * C, 1.0f, out4);
     return check_launch();
 }
@@ -1545,7 +1509,7 @@ extern "C" int hsp_colsum_rows_bf16(const hsp_bf16_t* x, int B, int N, int C, fl
     const int rows = chunk_rows(B, N, C);
     const int nchunk = (N + rows - 1) / rows;
     float* part = reinterpret_cast<float*>(ws);
-    hipLaunchKernelGGL(colsum_partial_kernel<bf16_t>, dim3(nchunk, B), dim3(256), 0, st, x, N, C, part, nchunk, rows);
+    hipLaunchKernelGGL((colsum_partial_kernel<bf16_t, false>), dim3(nchunk, B), dim3(256), 0, st, x, nullptr, N, C, part, nchunk, rows);
     hipLaunchKernelGGL(chunk_fold_kernel, dim3((B * C + 255) / 256), dim3(256), 0, st, part, B, nchunk, C, 1.0f, out);
     return check_launch();
 }

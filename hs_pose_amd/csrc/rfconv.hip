@@ -14,6 +14,7 @@
 #include "folds.h"
 #include <stdlib.h>
 #include <atomic>
+#include <type_traits>
 
 namespace hsp {
 
@@ -47,13 +48,6 @@ __device__ __forceinline__ void load_dirs_normed(const float* __restrict__ dirs,
 // difference from max(x, 0): a theta that rounding pushed an ulp or two ABOVE 1 (a neighbour exactly along a support
 // direction) reads 1.0 instead of 1.0000001 (2.4e-7 relative, inside every tolerance of section 2; NaN -> 0 either way).
 // -DRF_RELU_MAX restores the plain max.
-// RF_WF_POST=1: the pipelined forward fetches the winners' support values AFTER the neighbour loop (four 4-byte gathers per
-// float4 unit) instead of carrying them through it as a fourth v_cndmask per element.  Measured in isolation (round 3, same box,
-// alternating runs): 1.894 vs 1.874 ms per step at B=16 N=1028, 15.8-16.0 vs 15.63 ms on the bf16 dense clouds -- a wave's four
-// scattered 4-byte gathers touch up to 256 cache lines, more address-path work than the 80 selects they replace.  Off.
-#ifndef RF_WF_POST
-#define RF_WF_POST 0
-#endif
 #ifdef RF_RELU_MAX
 #define RF_RELU(X) fmaxf((X), 0.f)
 #else
@@ -79,12 +73,92 @@ struct PointIter {
     }
 };
 
+// theta / z of one column: common.h's dot3_chain (the k-ordered fma chain of the reference's matmul, where the chain is spelled)
+// on a neighbour direction and one column of the three direction rows.  Every rf kernel takes theta / z through here: the
+// backward kernels' mask z > 0 has to reproduce the forward's relu(theta) bit for bit.
+template <class R3>
+__device__ __forceinline__ float rf_dot3(const R3 r, float d0, float d1, float d2) { return dot3_chain(r.x, r.y, r.z, d0, d1, d2); }
+
+// the normalised directions of a thread's NCH column groups tid, tid + 256, ... (a slot past the last group reads group 0)
+template <int NCH>
+__device__ __forceinline__ void rf_load_dirs(const float* dirs, int SC, int tid, float4 (&d0)[NCH], float4 (&d1)[NCH],
+                                             float4 (&d2)[NCH]) {
+    const int nq = SC >> 2;
+#pragma unroll
+    for (int u = 0; u < NCH; ++u) {
+        const int cq = tid + u * RF_THREADS;
+        load_dirs_normed(dirs, SC, (cq < nq ? cq : 0) << 2, d0[u], d1[u], d2[u]);
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // forward.  SURFACE=true: out = mean_s max_n relu(z);  false: out = fm_c + mean_s max_n relu(z)*fm_support
-// dynamic LDS: (S*C + 4*k + k) floats
-// ------------------------------------------------------------------------------------------------
 // WF: also record the winners' support values (fwin)
 // FT: storage type of fm / out / fwin (float, or bf16_t: arithmetic stays fp32, common.h Feat<>)
+// Two schedules (rf_fwd_kernel, rf_fwd_pipe_kernel) around ONE arithmetic: rf_group_body and rf_mean_phase.
+// ------------------------------------------------------------------------------------------------
+// One (point, float4 column group): the running max / arg-max over the k neighbours in sR / sIdx, then the group's maxima to
+// smax_j, the winning SOURCE ROWS m* = idx[b,i,n*] (uint16: the backward needs neither idx nor n) to arg_pj and, WF, the winners'
+// support values to fwin_pj (the backward's direction gradient reads them as a stream instead of gathering 4-byte values from N
+// rows: 4x the HBM traffic, measured).  fetch(n): the four support values fm[b, idx[n], C + j ..] -- the one thing the two
+// schedules do differently.
+template <bool SURFACE, bool WF, typename FT, class Fetch>
+__device__ __forceinline__ void rf_group_body(const float4 d0, const float4 d1, const float4 d2, const float4* sR, const int* sIdx,
+                                              int k, Fetch fetch, float* smax_j, uint16_t* arg_pj, FT* fwin_pj) {
+    float4 best = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+    int a0 = 0, a1 = 0, a2 = 0, a3 = 0;
+    float4 wf = make_float4(1.f, 1.f, 1.f, 1.f);          // the support value behind each winner
+#pragma unroll 4
+    for (int n = 0; n < k; ++n) {
+        const float4 r = sR[n];
+        float4 th;
+        th.x = RF_RELU(rf_dot3(r, d0.x, d1.x, d2.x));
+        th.y = RF_RELU(rf_dot3(r, d0.y, d1.y, d2.y));
+        th.z = RF_RELU(rf_dot3(r, d0.z, d1.z, d2.z));
+        th.w = RF_RELU(rf_dot3(r, d0.w, d1.w, d2.w));
+        if (!SURFACE) {
+            const float4 f = fetch(n);
+            th.x = mul_rn(th.x, f.x); th.y = mul_rn(th.y, f.y);
+            th.z = mul_rn(th.z, f.z); th.w = mul_rn(th.w, f.w);
+            if (WF) {
+                if (th.x > best.x) wf.x = f.x;
+                if (th.y > best.y) wf.y = f.y;
+                if (th.z > best.z) wf.z = f.z;
+                if (th.w > best.w) wf.w = f.w;
+            }
+        }
+        if (th.x > best.x) { best.x = th.x; a0 = n; }
+        if (th.y > best.y) { best.y = th.y; a1 = n; }
+        if (th.z > best.z) { best.z = th.z; a2 = n; }
+        if (th.w > best.w) { best.w = th.w; a3 = n; }
+    }
+    *reinterpret_cast<float4*>(smax_j) = best;
+    // fwin / argrow / out are write-once streams read again only by the backward: non-temporal stores keep them from evicting
+    // the cloud's fm rows (the gather's working set) from the XCD's L2
+    {
+        const unsigned lo = (unsigned)sIdx[a0] | ((unsigned)sIdx[a1] << 16);
+        const unsigned hi = (unsigned)sIdx[a2] | ((unsigned)sIdx[a3] << 16);
+        unsigned* ap = reinterpret_cast<unsigned*>(arg_pj);
+        __builtin_nontemporal_store(lo, ap); __builtin_nontemporal_store(hi, ap + 1);
+    }
+    if (WF) Feat<FT>::st4_nt(fwin_pj, wf);
+}
+
+// out[pt] = (fm_c[pt] +) the mean over the S supports of the point's maxima
+template <bool SURFACE, typename FT>
+__device__ __forceinline__ void rf_mean_phase(const float* smax, const FT* fm, FT* out, size_t pt, int S,
+                                              int C, float invS_div, int tid) {      // invS_div = (float)S
+    const int fstride = (S + 1) * C;
+    for (int c = tid; c < C; c += RF_THREADS) {
+        float s = smax[c];
+        for (int sp = 1; sp < S; ++sp) s = add_rn(s, smax[sp * C + c]);
+        float v = __fdiv_rn(s, invS_div);
+        if (!SURFACE) v = add_rn(Feat<FT>::ld(fm + pt * fstride + c), v);
+        Feat<FT>::st_nt(out + pt * C + c, v);
+    }
+}
+
+// The plain schedule: a point in three phases separated by barriers.  dynamic LDS: (S*C + 4*k + k) floats
 template <bool SURFACE, int NCH, bool WF, typename FT>
 __global__ __launch_bounds__(RF_THREADS) void rf_fwd_kernel(const float* __restrict__ xyz,
                                                             const int32_t* __restrict__ idx,
@@ -103,11 +177,7 @@ __global__ __launch_bounds__(RF_THREADS) void rf_fwd_kernel(const float* __restr
     const int fstride = (S + 1) * C;
     const float invS_div = (float)S;
     float4 d0[NCH], d1[NCH], d2[NCH];
-#pragma unroll
-    for (int u = 0; u < NCH; ++u) {
-        const int cq = tid + u * RF_THREADS;
-        load_dirs_normed(dirs, SC, (cq < nq ? cq : 0) << 2, d0[u], d1[u], d2[u]);
-    }
+    rf_load_dirs<NCH>(dirs, SC, tid, d0, d1, d2);
     const PointIter it(B);
     for (int b = it.b0; b < B; b += it.bstep) {
         const float* xb = xyz + (size_t)b * N * 3;
@@ -126,58 +196,14 @@ __global__ __launch_bounds__(RF_THREADS) void rf_fwd_kernel(const float* __restr
                 const int cq = tid + u * RF_THREADS;
                 if (cq < nq) {
                     const int j = cq << 2;
-                    float4 best = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
-                    int a0 = 0, a1 = 0, a2 = 0, a3 = 0;
-                    float4 wf = make_float4(1.f, 1.f, 1.f, 1.f);          // the support value behind each winner
                     const FT* fsup = SURFACE ? nullptr : fm + (size_t)b * N * fstride + C + j;
-#pragma unroll 4
-                    for (int n = 0; n < k; ++n) {
-                        const float4 r = sR[n];
-                        // theta = relu(R . D) with the k-ordered fma chain of the reference's matmul
-                        float4 th;
-                        th.x = RF_RELU(__fmaf_rn(r.z, d2[u].x, __fmaf_rn(r.y, d1[u].x, mul_rn(r.x, d0[u].x))));
-                        th.y = RF_RELU(__fmaf_rn(r.z, d2[u].y, __fmaf_rn(r.y, d1[u].y, mul_rn(r.x, d0[u].y))));
-                        th.z = RF_RELU(__fmaf_rn(r.z, d2[u].z, __fmaf_rn(r.y, d1[u].z, mul_rn(r.x, d0[u].z))));
-                        th.w = RF_RELU(__fmaf_rn(r.z, d2[u].w, __fmaf_rn(r.y, d1[u].w, mul_rn(r.x, d0[u].w))));
-                        if (!SURFACE) {
-                            const float4 f = Feat<FT>::ld4(fsup + (size_t)sIdx[n] * fstride);
-                            th.x = mul_rn(th.x, f.x); th.y = mul_rn(th.y, f.y);
-                            th.z = mul_rn(th.z, f.z); th.w = mul_rn(th.w, f.w);
-                            if (WF) {
-                                if (th.x > best.x) wf.x = f.x;
-                                if (th.y > best.y) wf.y = f.y;
-                                if (th.z > best.z) wf.z = f.z;
-                                if (th.w > best.w) wf.w = f.w;
-                            }
-                        }
-                        if (th.x > best.x) { best.x = th.x; a0 = n; }
-                        if (th.y > best.y) { best.y = th.y; a1 = n; }
-                        if (th.z > best.z) { best.z = th.z; a2 = n; }
-                        if (th.w > best.w) { best.w = th.w; a3 = n; }
-                    }
-                    // ... and that winner's support value fm[b,m*,C+j]: the backward's direction gradient reads it
-                    // as a stream instead of gathering 4-byte values from N rows (4x the HBM traffic, measured)
-                    // fwin / argrow / out are write-once streams read again only by the backward: non-temporal stores keep
-                    // them from evicting the cloud's fm rows (the gather's working set) from the XCD's L2
-                    if (WF) Feat<FT>::st4_nt(fwin + pt * SC + j, wf);
-                    *reinterpret_cast<float4*>(smax + j) = best;
-                    // the winning SOURCE ROW m* = idx[b,i,n*] (uint16): the backward needs neither idx nor n
-                    {
-                        const unsigned lo = (unsigned)sIdx[a0] | ((unsigned)sIdx[a1] << 16);
-                        const unsigned hi = (unsigned)sIdx[a2] | ((unsigned)sIdx[a3] << 16);
-                        unsigned* ap = reinterpret_cast<unsigned*>(argrow + pt * SC + j);
-                        __builtin_nontemporal_store(lo, ap); __builtin_nontemporal_store(hi, ap + 1);
-                    }
+                    auto fetch = [=](int n) { return Feat<FT>::ld4(fsup + (size_t)sIdx[n] * fstride); };     // a pointer gather
+                    rf_group_body<SURFACE, WF, FT>(d0[u], d1[u], d2[u], sR, sIdx, k, fetch, smax + j, argrow + pt * SC + j,
+                                                   WF ? fwin + pt * SC + j : nullptr);
                 }
             }
             __syncthreads();
-            for (int c = tid; c < C; c += RF_THREADS) {
-                float s = smax[c];
-                for (int sp = 1; sp < S; ++sp) s = add_rn(s, smax[sp * C + c]);
-                float v = __fdiv_rn(s, invS_div);
-                if (!SURFACE) v = add_rn(Feat<FT>::ld(fm + pt * fstride + c), v);
-                Feat<FT>::st_nt(out + pt * C + c, v);
-            }
+            rf_mean_phase<SURFACE, FT>(smax, fm, out, pt, S, C, invS_div, tid);
         }
     }
 }
@@ -190,8 +216,9 @@ __global__ __launch_bounds__(RF_THREADS) void rf_fwd_kernel(const float* __restr
 // consecutive points share ONE barrier interval: the threads that have no column group in the last of the NCH slots
 // (S*C/4 = 224 groups on 256 threads at C = 128) build the directions of point i+1 into the other half of a double
 // buffer while the gather of point i runs, and the average of point i-1 is taken from the other maxima buffer at the
-// start of the interval.  Same arithmetic as rf_fwd_kernel; no shape runs under both schedules (hsp_rf_fwd_plan picks one per
-// (k, S, C)), so tests/test_gpu_rf_reference.py holds each of them to the same fp64 reference and asserts the plan it entered.
+// start of the interval.  The arithmetic is rf_fwd_kernel's by construction; no shape runs under both schedules (hsp_rf_fwd_plan
+// picks one per (k, S, C)), so tests/test_gpu_rf_reference.py holds each of them to the same fp64 reference and asserts the plan
+// it entered.
 // dynamic LDS: 2 * (S*C + 6 k) floats.  Needs S*C/4 - (NCH-1)*256 + k <= 256.
 // ------------------------------------------------------------------------------------------------
 template <bool SURFACE, int NCH, bool WF, typename FT>
@@ -211,14 +238,10 @@ __global__ __launch_bounds__(RF_THREADS) void rf_fwd_pipe_kernel(const float* __
     const int tid = threadIdx.x;
     const int nq = SC >> 2;
     const int fstride = (S + 1) * C;
-    const float invS_div = (float)S;
     const int spare0 = nq - (NCH - 1) * RF_THREADS;           // first thread without a group in the last slot
+    const float invS_div = (float)S;
     float4 d0[NCH], d1[NCH], d2[NCH];
-#pragma unroll
-    for (int u = 0; u < NCH; ++u) {
-        const int cq = tid + u * RF_THREADS;
-        load_dirs_normed(dirs, SC, (cq < nq ? cq : 0) << 2, d0[u], d1[u], d2[u]);
-    }
+    rf_load_dirs<NCH>(dirs, SC, tid, d0, d1, d2);
     const PointIter it(B);
     auto dirs_phase = [&](int b, int i, int buf) {
         const int t = tid - spare0;
@@ -229,15 +252,6 @@ __global__ __launch_bounds__(RF_THREADS) void rf_fwd_pipe_kernel(const float* __
             sOff2[buf * k + t] = (unsigned)m * (unsigned)fstride * (unsigned)sizeof(FT);
             const float3 r = unit_dir(xb[i * 3], xb[i * 3 + 1], xb[i * 3 + 2], xb[m * 3], xb[m * 3 + 1], xb[m * 3 + 2]);
             sR2[buf * k + t] = make_float4(r.x, r.y, r.z, 0.f);
-        }
-    };
-    auto mean_phase = [&](size_t pt, const float* smax) {
-        for (int c = tid; c < C; c += RF_THREADS) {
-            float s = smax[c];
-            for (int sp = 1; sp < S; ++sp) s = add_rn(s, smax[sp * C + c]);
-            float v = __fdiv_rn(s, invS_div);
-            if (!SURFACE) v = add_rn(Feat<FT>::ld(fm + pt * fstride + c), v);
-            Feat<FT>::st_nt(out + pt * C + c, v);
         }
     };
     int b = it.b0, i = it.i0;
@@ -252,7 +266,7 @@ __global__ __launch_bounds__(RF_THREADS) void rf_fwd_pipe_kernel(const float* __
         const bool have_next = nb < B;
         const size_t pt = (size_t)b * N + i;
         __syncthreads();        // directions of this point are in place; the previous point's maxima are complete
-        if (have_prev) mean_phase(prev_pt, smax2 + (cur ^ 1) * SC);
+        if (have_prev) rf_mean_phase<SURFACE, FT>(smax2 + (cur ^ 1) * SC, fm, out, prev_pt, S, C, invS_div, tid);
         if (have_next) dirs_phase(nb, ni, cur ^ 1);
         float* smax = smax2 + cur * SC;
         const float4* sR = sR2 + cur * k;
@@ -263,9 +277,6 @@ __global__ __launch_bounds__(RF_THREADS) void rf_fwd_pipe_kernel(const float* __
             const int cq = tid + u * RF_THREADS;
             if (cq < nq) {
                 const int j = cq << 2;
-                float4 best = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
-                int a0 = 0, a1 = 0, a2 = 0, a3 = 0;
-                float4 wf = make_float4(1.f, 1.f, 1.f, 1.f);
                 // gathers through a buffer descriptor over the cloud's fm: address = base + 32-bit (column + row) byte offset, one
                 // v_add per gather instead of a 64-bit multiply-add
                 // (the base goes through v_readfirstlane: hipcc does not see that the cloud index is wave-uniform and would wrap
@@ -276,63 +287,18 @@ __global__ __launch_bounds__(RF_THREADS) void rf_fwd_pipe_kernel(const float* __
                 const __amdgpu_buffer_rsrc_t frs =
                     __builtin_amdgcn_make_buffer_rsrc(ubase, 0, (int)((size_t)N * fstride * sizeof(FT)), 0x00020000);
                 const unsigned voff = (unsigned)(C + j) * (unsigned)sizeof(FT);
-#pragma unroll 4
-                for (int n = 0; n < k; ++n) {
-                    const float4 r = sR[n];
-                    float4 th;
-                    th.x = RF_RELU(__fmaf_rn(r.z, d2[u].x, __fmaf_rn(r.y, d1[u].x, mul_rn(r.x, d0[u].x))));
-                    th.y = RF_RELU(__fmaf_rn(r.z, d2[u].y, __fmaf_rn(r.y, d1[u].y, mul_rn(r.x, d0[u].y))));
-                    th.z = RF_RELU(__fmaf_rn(r.z, d2[u].z, __fmaf_rn(r.y, d1[u].z, mul_rn(r.x, d0[u].z))));
-                    th.w = RF_RELU(__fmaf_rn(r.z, d2[u].w, __fmaf_rn(r.y, d1[u].w, mul_rn(r.x, d0[u].w))));
-                    if (!SURFACE) {
-                        float4 f;
-                        if constexpr (sizeof(FT) == 4) {
-                            const auto v = __builtin_amdgcn_raw_buffer_load_b128(frs, (int)(voff + sOff[n]), 0, 0);
-                            f = make_float4(__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]), __uint_as_float(v[3]));
-                        } else {
-                            const auto v = __builtin_amdgcn_raw_buffer_load_b64(frs, (int)(voff + sOff[n]), 0, 0);
-                            f = make_float4(__uint_as_float(v[0] << 16), __uint_as_float(v[0] & 0xffff0000u),
-                                            __uint_as_float(v[1] << 16), __uint_as_float(v[1] & 0xffff0000u));
-                        }
-                        th.x = mul_rn(th.x, f.x); th.y = mul_rn(th.y, f.y);
-                        th.z = mul_rn(th.z, f.z); th.w = mul_rn(th.w, f.w);
-                        if (WF && !RF_WF_POST) {
-                            if (th.x > best.x) wf.x = f.x;
-                            if (th.y > best.y) wf.y = f.y;
-                            if (th.z > best.z) wf.z = f.z;
-                            if (th.w > best.w) wf.w = f.w;
-                        }
-                    }
-                    if (th.x > best.x) { best.x = th.x; a0 = n; }
-                    if (th.y > best.y) { best.y = th.y; a1 = n; }
-                    if (th.z > best.z) { best.z = th.z; a2 = n; }
-                    if (th.w > best.w) { best.w = th.w; a3 = n; }
-                }
-                if (WF && RF_WF_POST && !SURFACE) {
-                    // (opt-in, measured slower: see RF_WF_POST above)
-                    constexpr unsigned ES = (unsigned)sizeof(FT);
-                    const unsigned o0 = voff + sOff[a0], o1 = voff + sOff[a1] + ES, o2 = voff + sOff[a2] + 2 * ES,
-                                   o3 = voff + sOff[a3] + 3 * ES;
+                auto fetch = [=](int n) {
                     if constexpr (sizeof(FT) == 4) {
-                        wf.x = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(frs, (int)o0, 0, 0));
-                        wf.y = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(frs, (int)o1, 0, 0));
-                        wf.z = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(frs, (int)o2, 0, 0));
-                        wf.w = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(frs, (int)o3, 0, 0));
+                        const auto v = __builtin_amdgcn_raw_buffer_load_b128(frs, (int)(voff + sOff[n]), 0, 0);
+                        return make_float4(__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]), __uint_as_float(v[3]));
                     } else {
-                        wf.x = __uint_as_float((unsigned)(unsigned short)__builtin_amdgcn_raw_buffer_load_b16(frs, (int)o0, 0, 0) << 16);
-                        wf.y = __uint_as_float((unsigned)(unsigned short)__builtin_amdgcn_raw_buffer_load_b16(frs, (int)o1, 0, 0) << 16);
-                        wf.z = __uint_as_float((unsigned)(unsigned short)__builtin_amdgcn_raw_buffer_load_b16(frs, (int)o2, 0, 0) << 16);
-                        wf.w = __uint_as_float((unsigned)(unsigned short)__builtin_amdgcn_raw_buffer_load_b16(frs, (int)o3, 0, 0) << 16);
+                        const auto v = __builtin_amdgcn_raw_buffer_load_b64(frs, (int)(voff + sOff[n]), 0, 0);
+                        return make_float4(__uint_as_float(v[0] << 16), __uint_as_float(v[0] & 0xffff0000u),
+                                           __uint_as_float(v[1] << 16), __uint_as_float(v[1] & 0xffff0000u));
                     }
-                }
-                *reinterpret_cast<float4*>(smax + j) = best;
-                {
-                    const unsigned lo = (unsigned)sIdx[a0] | ((unsigned)sIdx[a1] << 16);
-                    const unsigned hi = (unsigned)sIdx[a2] | ((unsigned)sIdx[a3] << 16);
-                    unsigned* ap = reinterpret_cast<unsigned*>(argrow + pt * SC + j);
-                    __builtin_nontemporal_store(lo, ap); __builtin_nontemporal_store(hi, ap + 1);
-                }
-                if (WF) Feat<FT>::st4_nt(fwin + pt * SC + j, wf);
+                };
+                rf_group_body<SURFACE, WF, FT>(d0[u], d1[u], d2[u], sR, sIdx, k, fetch, smax + j,
+                                               argrow + pt * SC + j, WF ? fwin + pt * SC + j : nullptr);
             }
         }
         have_prev = true; prev_pt = pt;
@@ -340,7 +306,7 @@ __global__ __launch_bounds__(RF_THREADS) void rf_fwd_pipe_kernel(const float* __
         b = nb; i = ni; have = have_next;
     }
     __syncthreads();
-    if (have_prev) mean_phase(prev_pt, smax2 + (cur ^ 1) * SC);
+    if (have_prev) rf_mean_phase<SURFACE, FT>(smax2 + (cur ^ 1) * SC, fm, out, prev_pt, S, C, invS_div, tid);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -374,13 +340,9 @@ __global__ __launch_bounds__(RF_THREADS) void rf_conv_bwd_csr_kernel(
     const int cq4 = C >> 2;
 
     float4 d0[NCH], d1[NCH], d2[NCH], gd0[NCH], gd1[NCH], gd2[NCH];
+    rf_load_dirs<NCH>(dirs, SC, tid, d0, d1, d2);
 #pragma unroll
-    for (int u = 0; u < NCH; ++u) {
-        const int cq = tid + u * RF_THREADS;
-        const int j = (cq < nq ? cq : 0) << 2;
-        load_dirs_normed(dirs, SC, j, d0[u], d1[u], d2[u]);
-        gd0[u] = gd1[u] = gd2[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
+    for (int u = 0; u < NCH; ++u) gd0[u] = gd1[u] = gd2[u] = make_float4(0.f, 0.f, 0.f, 0.f);
     const PointIter it(B);
     for (int b = it.b0; b < B; b += it.bstep) {
         const float* xb = xyz + (size_t)b * N * 3;
@@ -434,7 +396,7 @@ __global__ __launch_bounds__(RF_THREADS) void rf_conv_bwd_csr_kernel(
                                 const float4 ga = *reinterpret_cast<const float4*>(sg + t * C + c);
 #define RF_ONE(X)                                                                                         \
     if (am[t].X == n) {                                                                                   \
-        const float z = __fmaf_rn(r.z, d2[u].X, __fmaf_rn(r.y, d1[u].X, mul_rn(r.x, d0[u].X)));           \
+        const float z = rf_dot3(r, d0[u].X, d1[u].X, d2[u].X);                                            \
         if (z > 0.f) {                                                                                    \
             acc[u].X += ga.X * z;                                                                         \
             const float w = ga.X * fv[u].X;                                                               \
@@ -544,15 +506,38 @@ template <> struct Raw4<bf16_t> {
 };
 typedef float rf_v4f __attribute__((ext_vector_type(4)));
 
+// (cloud, column tile) of a workgroup of rf_bwd_tile_kernel's grid (T column tiles, B clouds[, row ranges]).  Neighbouring column
+// tiles read neighbouring 32- / 64-byte pieces of the same argrow / fwin / grad_out lines; dispatched round-robin over the 8 XCDs
+// each piece was fetched into another L2 (measured: 340 MB of HBM traffic for 164 MB algorithmic at N = 1028).  So: every tile of a
+// cloud on ONE XCD where B % 8 == 0 (grad_out is shared by its S tiles too), else groups of 4 adjacent tiles per XCD where they
+// divide evenly, as consecutive workgroups of it (block id = XCD + 8 k, observed placement), else the plain order.  A speed choice
+// only; tests/test_gpu_rf_reference.py restates which of the three a shape takes as _wg_map.
+__device__ __forceinline__ void rf_bwd_wg_map(int& b, int& tile) {
+    b = blockIdx.y; tile = blockIdx.x;
+    const int T = gridDim.x, ngrp = (T >> 2) * (int)gridDim.y;
+    if (RF_BWD_CLOUD_PER_XCD && ((int)gridDim.y & 7) == 0) {
+        const int L = blockIdx.x + T * blockIdx.y;
+        const int xcd = L & 7, k = L >> 3;
+        b = xcd + 8 * (k / T);
+        tile = k - (k / T) * T;
+    } else if ((T & 3) == 0 && (ngrp & 7) == 0) {
+        const int L = blockIdx.x + T * blockIdx.y;
+        const int xcd = L & 7, k = L >> 3;
+        const int gid = xcd + 8 * (k >> 2);
+        b = gid / (T >> 2);
+        tile = 4 * (gid - b * (T >> 2)) + (k & 3);
+    }
+}
+
 // one point's four columns: route ga * relu(theta) to the winning rows' cells, add to the direction gradient
 #define RF_T1(X, E, FV)                                                                              \
         {                                                                                            \
             const int m = (int)am.X - r0;                                                            \
             if (RS == 1 || (unsigned)m < (unsigned)(r1 - r0)) {                                      \
                 const float3 r = unit_dir_fast(px, py, pz, sx[m * 3], sx[m * 3 + 1], sx[m * 3 + 2]); \
-                const float z = __fmaf_rn(r.z, d2.X, __fmaf_rn(r.y, d1.X, mul_rn(r.x, d0.X)));       \
+                const float z = rf_dot3(r, d0.X, d1.X, d2.X);                                        \
                 if (z > 0.f) {                                                                       \
-                    if (!SURFACE) RF_ACC_ADD(acc + m * TC + cg * 4 + E, ga.X * z);                   \
+                    if (!SURFACE) RF_ACC_ADD(accg + m * TC + E, ga.X * z);                           \
                     const float w = ga.X * FV;                                                       \
                     g0.X += w * r.x; g1.X += w * r.y; g2.X += w * r.z;                               \
                 }                                                                                    \
@@ -608,26 +593,8 @@ __global__ __launch_bounds__(RF_TILE_THREADS, rf_tile_waves(TC, SURFACE, RS, D))
     const int SC = S * C;
     const int fstride = (S + 1) * C;
     const int tid = threadIdx.x;
-    // (cloud, column tile) of this workgroup.  Neighbouring column tiles read neighbouring 32- / 64-byte pieces of the same
-    // argrow / fwin / grad_out lines; dispatched round-robin over the 8 XCDs each piece was fetched into another L2 (measured:
-    // 340 MB of HBM traffic for 164 MB algorithmic at N = 1028).  Groups of 4 adjacent tiles are therefore given to ONE XCD, as
-    // consecutive workgroups of it (block id = XCD + 8 k, observed placement: a speed choice only).
-    int b = blockIdx.y, tile = blockIdx.x;
-    {
-        const int T = gridDim.x, ngrp = (T >> 2) * (int)gridDim.y;
-            if (RF_BWD_CLOUD_PER_XCD && ((int)gridDim.y & 7) == 0) {     // every tile of a cloud on one XCD (grad_out is shared by its S tiles too)
-            const int L = blockIdx.x + T * blockIdx.y;
-            const int xcd = L & 7, k = L >> 3;
-            b = xcd + 8 * (k / T);
-            tile = k - (k / T) * T;
-        } else if ((T & 3) == 0 && (ngrp & 7) == 0) {
-            const int L = blockIdx.x + T * blockIdx.y;
-            const int xcd = L & 7, k = L >> 3;
-            const int gid = xcd + 8 * (k >> 2);
-            b = gid / (T >> 2);
-            tile = 4 * (gid - b * (T >> 2)) + (k & 3);
-        }
-    }
+    int b, tile;
+    rf_bwd_wg_map(b, tile);
     const int j0 = tile * TC;
     const int cg = tid % G, pl = tid / G;
     const int j = j0 + cg * 4;
@@ -638,6 +605,27 @@ __global__ __launch_bounds__(RF_TILE_THREADS, rf_tile_waves(TC, SURFACE, RS, D))
     float4 d0, d1, d2;
     float4 g0 = make_float4(0.f, 0.f, 0.f, 0.f), g1 = g0, g2 = g0;
     const FT* fsup = (SURFACE || FWIN) ? nullptr : fwin + (size_t)b * N * fstride + C + j;   // (fwin is fm then)
+    // One point p of the sweep, under either schedule: am = its four winning rows, gq = its grad_out values, fw = their support
+    // values from the fwin stream (FWIN), ps = the point's coordinates as streamed by the schedule (RS > 1; the whole-cloud tile
+    // has them in sx).  accg = acc + cg * 4, this thread's columns of the tile, handed in by the caller: written inside this
+    // body the sum moved the legacy kernels' address code; operands by reference for the same reason.
+    auto point = [&](float* accg, const ushort4& am, const float4& gq, const float4& fw, const float3& ps, int p) {
+        float4 ga = gq;
+        float f0 = 1.f, f1 = 1.f, f2 = 1.f, f3 = 1.f;              // (SURFACE: no support value)
+        if (!SURFACE && FWIN) { f0 = fw.x; f1 = fw.y; f2 = fw.z; f3 = fw.w; }
+        if (!SURFACE && !FWIN) {
+            f0 = Feat<FT>::ld(fsup + (size_t)am.x * fstride + 0);
+            f1 = Feat<FT>::ld(fsup + (size_t)am.y * fstride + 1);
+            f2 = Feat<FT>::ld(fsup + (size_t)am.z * fstride + 2);
+            f3 = Feat<FT>::ld(fsup + (size_t)am.w * fstride + 3);
+        }
+        ga.x *= invS; ga.y *= invS; ga.z *= invS; ga.w *= invS;
+        float px, py, pz;
+        if (RS > 1) { px = ps.x; py = ps.y; pz = ps.z; }
+        else { px = sx[p * 3]; py = sx[p * 3 + 1]; pz = sx[p * 3 + 2]; }
+        RF_T1(x, 0, f0) RF_T1(y, 1, f1) RF_T1(z, 2, f2) RF_T1(w, 3, f3)
+    };
+#undef RF_T1
     if constexpr (D > 0) {
         typedef typename Raw4<FT>::T RawT;
         constexpr int RF_XB = rf_xyz_batch(TC), RF_CB = rf_centre_batch(TC);
@@ -750,25 +738,8 @@ __global__ __launch_bounds__(RF_TILE_THREADS, rf_tile_waves(TC, SURFACE, RS, D))
         }
         __syncthreads();
         // ---- 4. sweep: each thread takes its points pl, pl + PL, ... in that order (the direction gradient's rounding)
-        auto point = [&](const Stage& s, RawT graw, int p) {
-            const ushort4 am = s.am;
-            float4 ga = Raw4<FT>::wide(graw);
-            float f0 = 1.f, f1 = 1.f, f2 = 1.f, f3 = 1.f;
-            if (!SURFACE && FWIN) {
-                const float4 fw = Raw4<FT>::wide(s.fw);
-                f0 = fw.x; f1 = fw.y; f2 = fw.z; f3 = fw.w;
-            }
-            if (!SURFACE && !FWIN) {
-                f0 = Feat<FT>::ld(fsup + (size_t)am.x * fstride + 0);
-                f1 = Feat<FT>::ld(fsup + (size_t)am.y * fstride + 1);
-                f2 = Feat<FT>::ld(fsup + (size_t)am.z * fstride + 2);
-                f3 = Feat<FT>::ld(fsup + (size_t)am.w * fstride + 3);
-            }
-            ga.x *= invS; ga.y *= invS; ga.z *= invS; ga.w *= invS;
-            float px, py, pz;
-            if (RS > 1) { px = s.px; py = s.py; pz = s.pz; }
-            else { px = sx[p * 3]; py = sx[p * 3 + 1]; pz = sx[p * 3 + 2]; }
-            RF_T1(x, 0, f0) RF_T1(y, 1, f1) RF_T1(z, 2, f2) RF_T1(w, 3, f3)
+        auto stage_point = [&](const Stage& s, RawT graw, int p) {   // (a bf16 piece is widened here, where it is used)
+            point(acc + cg * 4, s.am, Raw4<FT>::wide(graw), Raw4<FT>::wide(s.fw), make_float3(s.px, s.py, s.pz), p);
         };
         if constexpr (RES) {
 #pragma unroll
@@ -776,7 +747,7 @@ __global__ __launch_bounds__(RF_TILE_THREADS, rf_tile_waves(TC, SURFACE, RS, D))
                 if (t * PL >= N) break;
                 if (t + D < RG) st[t + D] = load_stage(pl + (t + D) * PL);
                 const int p = pl + t * PL;
-                if (p < N) point(st[t], gres[t], p);
+                if (p < N) stage_point(st[t], gres[t], p);
             }
         } else {
             for (int p0 = pl; p0 < N; p0 += D * PL) {
@@ -785,7 +756,7 @@ __global__ __launch_bounds__(RF_TILE_THREADS, rf_tile_waves(TC, SURFACE, RS, D))
                     const int p = p0 + u * PL;
                     const Stage cur = st[u];
                     st[u] = load_stage(p + D * PL);
-                    if (p < N) point(cur, cur.ga, p);
+                    if (p < N) stage_point(cur, cur.ga, p);
                 }
             }
         }
@@ -815,27 +786,16 @@ __global__ __launch_bounds__(RF_TILE_THREADS, rf_tile_waves(TC, SURFACE, RS, D))
     }
     for (int p = pl; p < N; p += PL) {
         const ushort4 am = am_n;
-        float4 ga = ga_n;
-        const float4 fw = fw_n;
+        const float4 ga = ga_n, fw = fw_n;
         const int pn = p + PL < N ? p + PL : p;                      // clamped: no branch around the loads
         am_n = *reinterpret_cast<const ushort4*>(argrow + ((size_t)b * N + pn) * SC + j);
         ga_n = Feat<FT>::ld4(gout + ((size_t)b * N + pn) * C + c);
         if (!SURFACE && FWIN) fw_n = Feat<FT>::ld4(fwin + ((size_t)b * N + pn) * SC + j);
-        float f0 = fw.x, f1 = fw.y, f2 = fw.z, f3 = fw.w;
-        if (!SURFACE && !FWIN) {
-            f0 = Feat<FT>::ld(fsup + (size_t)am.x * fstride + 0);
-            f1 = Feat<FT>::ld(fsup + (size_t)am.y * fstride + 1);
-            f2 = Feat<FT>::ld(fsup + (size_t)am.z * fstride + 2);
-            f3 = Feat<FT>::ld(fsup + (size_t)am.w * fstride + 3);
-        }
-        ga.x *= invS; ga.y *= invS; ga.z *= invS; ga.w *= invS;
-        float px, py, pz;
-        if (RS > 1) { px = xb[p * 3]; py = xb[p * 3 + 1]; pz = xb[p * 3 + 2]; }      // the point itself: a coalesced stream
-        else { px = sx[p * 3]; py = sx[p * 3 + 1]; pz = sx[p * 3 + 2]; }
-        RF_T1(x, 0, f0) RF_T1(y, 1, f1) RF_T1(z, 2, f2) RF_T1(w, 3, f3)
+        float3 ps = make_float3(0.f, 0.f, 0.f);
+        if (RS > 1) ps = make_float3(xb[p * 3], xb[p * 3 + 1], xb[p * 3 + 2]);      // the point itself: a coalesced stream
+        point(acc + cg * 4, am, ga, fw, ps, p);
     }
     }
-#undef RF_T1
     __syncthreads();
     if (!SURFACE) {
         // flush the tile: one 16-byte store per (row, group)
@@ -929,6 +889,21 @@ extern "C" int hsp_rf_fwd_plan(int k, int S, int C, int* pipelined) {
     return p.nch;
 }
 
+// the run-time column slots per thread (1..4) and WF as template arguments: launch(integral_constant<int, NCH>, bool_constant<WF>)
+template <class F>
+static void rf_dispatch_nch(int nch, bool wf, F launch) {
+    auto with_wf = [&](auto n) {
+        if (wf) launch(n, std::true_type{});
+        else launch(n, std::false_type{});
+    };
+    switch (nch) {
+        case 1: with_wf(std::integral_constant<int, 1>{}); break;
+        case 2: with_wf(std::integral_constant<int, 2>{}); break;
+        case 3: with_wf(std::integral_constant<int, 3>{}); break;
+        default: with_wf(std::integral_constant<int, 4>{}); break;
+    }
+}
+
 template <bool SURFACE, typename FT>
 static int rf_fwd(const float* xyz, const int32_t* idx, const float* dirs, const FT* fm, int B, int N, int k,
                   int S, int C, FT* out, uint16_t* argrow, FT* fwin, hspStream_t stream) {
@@ -940,42 +915,17 @@ static int rf_fwd(const float* xyz, const int32_t* idx, const float* dirs, const
     // slower inside the matrix-core form of round 4, tools/experiments/.  Removed.)
     const RfFwdPlan plan = rf_fwd_plan(k, S, C);
     if (!plan.nch) return HSP_ERR_UNSUPPORTED;            // S*C <= 4096, (S*C + 5 k) floats of LDS
-    const int nch = plan.nch;
     // workgroups per CU: 8 for the large layers; small clouds amortise a workgroup's prologue (direction loads + normalisation)
     // over more points with 6 / 4 (measured at B = 16: N = 257 55.3 -> 52.4 us, N = 64 24.3 -> 23.6 us)
     const long long npts = (long long)B * N;
     const int grid = persistent_blocks(npts, npts < 2048 ? 4 : npts < 8192 ? 6 : 8);
-    if (plan.pipe) {
-#define RF_PIPE_LAUNCH(NCH)                                                                                        \
-    if (!SURFACE && fwin)                                                                                          \
-        hipLaunchKernelGGL((rf_fwd_pipe_kernel<SURFACE, NCH, !SURFACE, FT>), dim3(grid), dim3(RF_THREADS), plan.lds, \
-                           as_stream(stream), xyz, idx, dirs, fm, B, N, k, S, C, out, argrow, fwin);               \
-    else                                                                                                           \
-        hipLaunchKernelGGL((rf_fwd_pipe_kernel<SURFACE, NCH, false, FT>), dim3(grid), dim3(RF_THREADS), plan.lds,   \
-                           as_stream(stream), xyz, idx, dirs, fm, B, N, k, S, C, out, argrow, fwin)
-        switch (nch) {
-            case 1: RF_PIPE_LAUNCH(1); break;
-            case 2: RF_PIPE_LAUNCH(2); break;
-            case 3: RF_PIPE_LAUNCH(3); break;
-            default: RF_PIPE_LAUNCH(4); break;
-        }
-#undef RF_PIPE_LAUNCH
-        return check_launch();
-    }
-#define RF_FWD_LAUNCH(NCH)                                                                                        \
-    if (!SURFACE && fwin)                                                                                          \
-        hipLaunchKernelGGL((rf_fwd_kernel<SURFACE, NCH, !SURFACE, FT>), dim3(grid), dim3(RF_THREADS), plan.lds, as_stream(stream), \
-                           xyz, idx, dirs, fm, B, N, k, S, C, out, argrow, fwin);                                 \
-    else                                                                                                           \
-        hipLaunchKernelGGL((rf_fwd_kernel<SURFACE, NCH, false, FT>), dim3(grid), dim3(RF_THREADS), plan.lds, as_stream(stream), \
-                           xyz, idx, dirs, fm, B, N, k, S, C, out, argrow, fwin)
-    switch (nch) {
-        case 1: RF_FWD_LAUNCH(1); break;
-        case 2: RF_FWD_LAUNCH(2); break;
-        case 3: RF_FWD_LAUNCH(3); break;
-        default: RF_FWD_LAUNCH(4); break;
-    }
-#undef RF_FWD_LAUNCH
+    rf_dispatch_nch(plan.nch, !SURFACE && fwin, [&](auto nch, auto wf) {
+        constexpr int NCH = decltype(nch)::value;
+        constexpr bool WF = !SURFACE && decltype(wf)::value;
+        auto kern = plan.pipe ? rf_fwd_pipe_kernel<SURFACE, NCH, WF, FT> : rf_fwd_kernel<SURFACE, NCH, WF, FT>;
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(RF_THREADS), plan.lds, as_stream(stream), xyz, idx, dirs, fm, B, N, k, S, C, out,
+                           argrow, fwin);
+    });
     return check_launch();
 }
 
@@ -1032,16 +982,10 @@ extern "C" int hsp_rf_conv_bwd(const float* xyz, const float* dirs_n, const floa
     const size_t lds = (size_t)(RF_EB * (C + 8)) * 4;
     if (lds > 64 * 1024) return HSP_ERR_UNSUPPORTED;
     float* wsf = reinterpret_cast<float*>(ws);
-#define RF_CSR_LAUNCH(NCH)                                                                                        \
-    hipLaunchKernelGGL((rf_conv_bwd_csr_kernel<NCH>), dim3(grid), dim3(RF_THREADS), lds, st, xyz, dirs_n, fm, argrow, \
-                       grad_out, rev_off, rev_edge, B, N, k, S, C, grad_fm, wsf)
-    switch (nch) {
-        case 1: RF_CSR_LAUNCH(1); break;
-        case 2: RF_CSR_LAUNCH(2); break;
-        case 3: RF_CSR_LAUNCH(3); break;
-        default: RF_CSR_LAUNCH(4); break;
-    }
-#undef RF_CSR_LAUNCH
+    rf_dispatch_nch(nch, false, [&](auto n, auto) {
+        hipLaunchKernelGGL((rf_conv_bwd_csr_kernel<decltype(n)::value>), dim3(grid), dim3(RF_THREADS), lds, st, xyz, dirs_n, fm, argrow,
+                           grad_out, rev_off, rev_edge, B, N, k, S, C, grad_fm, wsf);
+    });
     rc = check_launch();
     if (rc) return rc;
     hipLaunchKernelGGL(rf_dirs_reduce_kernel, dim3((SC + 63) / 64), dim3(1024), 0, st, wsf, grid, SC, dirs_n, grad_dirs_n);
@@ -1141,7 +1085,7 @@ static int rf_tile_launch(bool legacy, int N, dim3 grid, size_t lds, hipStream_t
 template <bool SURFACE, bool FWIN, typename FT>
 static int rf_bwd_scatter(const float* xyz, const float* dirs, const FT* fm, const uint16_t* argrow,
                           const FT* gout, int B, int N, int S, int C, FT* gfm, float* gdirs, void* ws,
-                          size_t ws_bytes, hspStream_t stream, HspDirsPending* pending = nullptr) {
+                          size_t ws_bytes, hspStream_t stream, HspDirsPending* pending) {
     int rc = rf_check(xyz, dirs, argrow, B, N, 1, S, C);
     if (rc) return rc;
     if (!gout || !gdirs || (!SURFACE && (!fm || !gfm))) return HSP_ERR_BAD_ARG;
@@ -1176,74 +1120,70 @@ static int rf_bwd_scatter(const float* xyz, const float* dirs, const FT* fm, con
     return check_launch();
 }
 
+// every scatter-backward entry point: pending_required = the *_partial entries, which leave the direction-gradient fold pending
+// (hsp_step_fold runs it with the step's other folds); the support values come from the fwin stream where the caller has one,
+// else they are gathered from fm
+template <bool SURFACE, typename FT>
+static int rf_bwd_entry(const float* xyz, const float* dirs_n, const FT* fm, const FT* fwin, const uint16_t* argrow,
+                        const FT* grad_out, int B, int N, int S, int C, FT* grad_fm, float* grad_dirs_n, void* ws, size_t ws_bytes,
+                        hspStream_t stream, HspDirsPending* pending, bool pending_required) {
+    if (pending_required && !pending) return HSP_ERR_BAD_ARG;
+    if (!SURFACE && fwin)
+        return rf_bwd_scatter<SURFACE, !SURFACE, FT>(xyz, dirs_n, fwin, argrow, grad_out, B, N, S, C, grad_fm, grad_dirs_n, ws, ws_bytes,
+                                                     stream, pending);
+    return rf_bwd_scatter<SURFACE, false, FT>(xyz, dirs_n, fm, argrow, grad_out, B, N, S, C, grad_fm, grad_dirs_n, ws, ws_bytes, stream,
+                                              pending);
+}
+
 extern "C" int hsp_rf_surface_bwd(const float* xyz, const float* dirs_n, const uint16_t* argrow, const float* grad_out,
                                   int B, int N, int S, int K, float* grad_dirs_n, void* ws, size_t ws_bytes,
                                   hspStream_t stream) {
-    return rf_bwd_scatter<true, false, float>(xyz, dirs_n, nullptr, argrow, grad_out, B, N, S, K, nullptr, grad_dirs_n, ws,
-                                              ws_bytes, stream);
+    return rf_bwd_entry<true, float>(xyz, dirs_n, nullptr, nullptr, argrow, grad_out, B, N, S, K, nullptr, grad_dirs_n, ws,
+                        ws_bytes, stream, nullptr, false);
 }
 extern "C" int hsp_rf_surface_bwd_bf16(const float* xyz, const float* dirs_n, const uint16_t* argrow,
                                        const hsp_bf16_t* grad_out, int B, int N, int S, int K, float* grad_dirs_n, void* ws,
                                        size_t ws_bytes, hspStream_t stream) {
-    return rf_bwd_scatter<true, false, bf16_t>(xyz, dirs_n, nullptr, argrow, grad_out, B, N, S, K, nullptr, grad_dirs_n, ws,
-                                               ws_bytes, stream);
+    return rf_bwd_entry<true, bf16_t>(xyz, dirs_n, nullptr, nullptr, argrow, grad_out, B, N, S, K, nullptr, grad_dirs_n, ws,
+                        ws_bytes, stream, nullptr, false);
 }
-
 extern "C" int hsp_rf_conv_bwd_scatter(const float* xyz, const float* dirs_n, const float* fm, const float* fwin,
                                        const uint16_t* argrow, const float* grad_out, int B, int N, int S, int C,
                                        float* grad_fm, float* grad_dirs_n, void* ws, size_t ws_bytes,
                                        hspStream_t stream) {
-    if (fwin)
-        return rf_bwd_scatter<false, true, float>(xyz, dirs_n, fwin, argrow, grad_out, B, N, S, C, grad_fm, grad_dirs_n, ws,
-                                                  ws_bytes, stream);
-    return rf_bwd_scatter<false, false, float>(xyz, dirs_n, fm, argrow, grad_out, B, N, S, C, grad_fm, grad_dirs_n, ws,
-                                               ws_bytes, stream);
+    return rf_bwd_entry<false, float>(xyz, dirs_n, fm, fwin, argrow, grad_out, B, N, S, C, grad_fm, grad_dirs_n, ws,
+                        ws_bytes, stream, nullptr, false);
 }
 extern "C" int hsp_rf_conv_bwd_scatter_bf16(const float* xyz, const float* dirs_n, const hsp_bf16_t* fm,
                                             const hsp_bf16_t* fwin, const uint16_t* argrow, const hsp_bf16_t* grad_out,
                                             int B, int N, int S, int C, hsp_bf16_t* grad_fm, float* grad_dirs_n, void* ws,
                                             size_t ws_bytes, hspStream_t stream) {
-    if (fwin)
-        return rf_bwd_scatter<false, true, bf16_t>(xyz, dirs_n, fwin, argrow, grad_out, B, N, S, C, grad_fm, grad_dirs_n, ws,
-                                                   ws_bytes, stream);
-    return rf_bwd_scatter<false, false, bf16_t>(xyz, dirs_n, fm, argrow, grad_out, B, N, S, C, grad_fm, grad_dirs_n, ws,
-                                                ws_bytes, stream);
+    return rf_bwd_entry<false, bf16_t>(xyz, dirs_n, fm, fwin, argrow, grad_out, B, N, S, C, grad_fm, grad_dirs_n, ws,
+                        ws_bytes, stream, nullptr, false);
 }
-
-// the same backward launches with the direction-gradient fold left pending (hsp_step_fold runs it with the step's other folds)
 extern "C" int hsp_rf_surface_bwd_partial(const float* xyz, const float* dirs_n, const uint16_t* argrow, const float* grad_out,
                                           int B, int N, int S, int K, float* grad_dirs_n, void* ws, size_t ws_bytes,
                                           HspDirsPending* pending, hspStream_t stream) {
-    if (!pending) return HSP_ERR_BAD_ARG;
-    return rf_bwd_scatter<true, false, float>(xyz, dirs_n, nullptr, argrow, grad_out, B, N, S, K, nullptr, grad_dirs_n, ws,
-                                              ws_bytes, stream, pending);
+    return rf_bwd_entry<true, float>(xyz, dirs_n, nullptr, nullptr, argrow, grad_out, B, N, S, K, nullptr, grad_dirs_n, ws,
+                        ws_bytes, stream, pending, true);
 }
 extern "C" int hsp_rf_surface_bwd_partial_bf16(const float* xyz, const float* dirs_n, const uint16_t* argrow,
                                                const hsp_bf16_t* grad_out, int B, int N, int S, int K, float* grad_dirs_n,
                                                void* ws, size_t ws_bytes, HspDirsPending* pending, hspStream_t stream) {
-    if (!pending) return HSP_ERR_BAD_ARG;
-    return rf_bwd_scatter<true, false, bf16_t>(xyz, dirs_n, nullptr, argrow, grad_out, B, N, S, K, nullptr, grad_dirs_n, ws,
-                                               ws_bytes, stream, pending);
+    return rf_bwd_entry<true, bf16_t>(xyz, dirs_n, nullptr, nullptr, argrow, grad_out, B, N, S, K, nullptr, grad_dirs_n, ws,
+                        ws_bytes, stream, pending, true);
 }
 extern "C" int hsp_rf_conv_bwd_scatter_partial(const float* xyz, const float* dirs_n, const float* fm, const float* fwin,
                                                const uint16_t* argrow, const float* grad_out, int B, int N, int S, int C,
                                                float* grad_fm, float* grad_dirs_n, void* ws, size_t ws_bytes,
                                                HspDirsPending* pending, hspStream_t stream) {
-    if (!pending) return HSP_ERR_BAD_ARG;
-    if (fwin)
-        return rf_bwd_scatter<false, true, float>(xyz, dirs_n, fwin, argrow, grad_out, B, N, S, C, grad_fm, grad_dirs_n, ws,
-                                                  ws_bytes, stream, pending);
-    return rf_bwd_scatter<false, false, float>(xyz, dirs_n, fm, argrow, grad_out, B, N, S, C, grad_fm, grad_dirs_n, ws,
-                                               ws_bytes, stream, pending);
+    return rf_bwd_entry<false, float>(xyz, dirs_n, fm, fwin, argrow, grad_out, B, N, S, C, grad_fm, grad_dirs_n, ws,
+                        ws_bytes, stream, pending, true);
 }
 extern "C" int hsp_rf_conv_bwd_scatter_partial_bf16(const float* xyz, const float* dirs_n, const hsp_bf16_t* fm,
                                                     const hsp_bf16_t* fwin, const uint16_t* argrow, const hsp_bf16_t* grad_out,
                                                     int B, int N, int S, int C, hsp_bf16_t* grad_fm, float* grad_dirs_n,
                                                     void* ws, size_t ws_bytes, HspDirsPending* pending, hspStream_t stream) {
-    if (!pending) return HSP_ERR_BAD_ARG;
-    if (fwin)
-        return rf_bwd_scatter<false, true, bf16_t>(xyz, dirs_n, fwin, argrow, grad_out, B, N, S, C, grad_fm, grad_dirs_n, ws,
-                                                   ws_bytes, stream, pending);
-    return rf_bwd_scatter<false, false, bf16_t>(xyz, dirs_n, fm, argrow, grad_out, B, N, S, C, grad_fm, grad_dirs_n, ws,
-                                                ws_bytes, stream, pending);
+    return rf_bwd_entry<false, bf16_t>(xyz, dirs_n, fm, fwin, argrow, grad_out, B, N, S, C, grad_fm, grad_dirs_n, ws,
+                        ws_bytes, stream, pending, true);
 }

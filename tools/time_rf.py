@@ -39,8 +39,12 @@ def both_schedules(name, fn):
 def vp(t): return ctypes.c_void_p(t.data_ptr())
 
 
-for B, N, C, k, S in ((16, 1028, 128, 20, 7), (16, 257, 256, 20, 7), (16, 64, 512, 8, 7)):
+# the three level shapes (all plan as pipelined forwards) and, forward only, one shape whose forward plans as plain (S = 8:
+# the last column slot leaves no thread free for the next point's directions)
+for B, N, C, k, S in ((16, 1028, 128, 20, 7), (16, 257, 256, 20, 7), (16, 64, 512, 8, 7), (16, 1028, 128, 20, 8)):
     SC = S * C
+    pipelined = ctypes.c_int(0)
+    L.hsp_rf_fwd_plan(k, S, C, ctypes.byref(pipelined))
     xyz = torch.randn(B, N, 3, device=dev)
     X = torch.relu(torch.randn(B, N, C, device=dev))
     fm = torch.randn(B, N, (S + 1) * C, device=dev)
@@ -51,7 +55,9 @@ for B, N, C, k, S in ((16, 1028, 128, 20, 7), (16, 257, 256, 20, 7), (16, 64, 51
     saved = fwin if fwin is not None else fm
     def fwd(): ops._rf_conv_fwd_raw(xyz, idx, dirs, fm, S, True)
     def bwd(): ops._rf_conv_bwd_raw(xyz, idx, dirs, saved, arg, g, S)
-    print(f"rf_conv fwd B{B} N{N} C{C}: {timed(fwd):.1f} us")
+    print(f"rf_conv fwd B{B} N{N} C{C} S{S} ({'pipelined' if pipelined.value else 'plain'}): {timed(fwd):.1f} us")
+    if S != 7:
+        continue
     both_schedules(f"rf_conv bwd B{B} N{N} C{C}", bwd)
     if N == 1028:                                        # the surface layer runs on the first level only
         sarg = torch.empty(B, N, SC, dtype=torch.int16, device=dev)
