@@ -19,7 +19,7 @@ class HspError(RuntimeError):
 # the closed table of scalar types the ABI passes by value; a fixed-width type joins it when the header comes to need it
 _SCALARS = {"int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double, "long long": ctypes.c_longlong,
             "unsigned long long": ctypes.c_ulonglong, "size_t": ctypes.c_size_t, "int32_t": ctypes.c_int32,
-            "uint16_t": ctypes.c_uint16, "uint8_t": ctypes.c_uint8}
+            "uint16_t": ctypes.c_uint16, "uint8_t": ctypes.c_uint8, "int8_t": ctypes.c_int8}
 _POINTEES = ("void", "char")            # further type names that may stand under a `*` only
 _STARS = r"((?:\s*\*)*)\s*"
 _DECL = re.compile(r"(.+?)" + _STARS + r"(\w+)\s*(\[\w*\])?", re.S)

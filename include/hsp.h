@@ -1378,6 +1378,81 @@ int hsp_face_split_bwd(const float *face, const float *g_normals, const float *g
 int hsp_axis_conf_fwd(const float *h, int B, float *axis, float *conf, hspStream_t stream);
 int hsp_axis_conf_bwd(const float *h, const float *g_axis, const float *g_conf, int B, float *g_h, hspStream_t stream);
 
+/* ---- evaluation metrics: 3D IoU, degree / cm matching, average precision ---------------------------------------------------
+ * replaces compute_degree_cm_mAP (evaluation/eval_utils_v1.py:430-621) and what it calls, quirks included, in three stages.
+ *
+ * A GROUP is the predictions and the ground truths of one class in one image.  The caller lays the instances out so that a group's
+ * predictions are consecutive rows of pred_RT (.,4,4) / pred_scale (.,3) / scores, its ground truths consecutive rows of gt_RT /
+ * gt_scale / gt_handle, both in the image's own order, and the groups of one class follow each other in image order: a class's
+ * rows are then its concatenation across images.  groups (n_groups, 6) int32 on the device, one row per group:
+ *   {p_off, np, g_off, ng, pair_off, kind}
+ * p_off / g_off: first prediction / ground-truth row; np, ng <= hsp_eval_group_cap() (32: the pair table of a group is then 20 KB
+ * of LDS); pair_off: where the group's np * ng pair values start ([i * ng + j], i and j in the image's order); kind: 0 no
+ * symmetry, 1 bottle / bowl / can, 2 mug, 3 phone / eggbox / glue.  Images with neither predictions nor ground truths have no
+ * group (:485-486).  max_group is the caller's statement of the largest np or ng in the table, which lives on the device: above the
+ * cap every entry point returns HSP_ERR_UNSUPPORTED before any launch.  pred_bboxes is not an input (the reference only asserts
+ * on it).  All arithmetic is fp64 unless stated; no atomics; every output slot has one writer.
+ *
+ * hsp_eval_pairs: compute_3d_iou_new (:35-91) and compute_RT_degree_cm_symmetry (:94-167), one pair per lane.
+ *   iou: the eight corners of get_3d_bbox(scale) through RT, divided by the homogeneous row; then the reference's extremes, which
+ *   are np.amax / np.amin(axis=0) of a (3, 8) array (:47-50): the largest and smallest COORDINATE of each corner, eight intervals
+ *   in get_3d_bbox's corner order, not a box per axis -- kept, because that is the number everyone quotes.  Overlap interval c =
+ *   [max of the two minima, min of the two maxima]; intersection = the product of the eight overlap lengths, 0 where one is
+ *   negative; volumes = the products of the eight lengths; intersection / union.  For kind 1, and kind 2 where gt_handle == 0 (kinds other than 2
+ *   never read gt_handle: the reference forces it to 1, :509-513): the largest of that over pred_RT . Ry(2 pi i / 20), i = 0..19,
+ *   starting from 0.  Stored rounded to fp32 (the reference's float32 overlap table); a disjoint pair is exactly 0.
+ *   degree: both rotations divided by cbrt(det); for the symmetric pairs above the angle between the two y axes, otherwise
+ *   arccos((trace(R1 R2^T) - 1) / 2), for kind 3 the smaller of that and the same with R1 diag(-1, 1, -1); times 180 / pi.  The
+ *   arccos argument is NOT clamped: above 1 it gives NaN, as numpy does.  shift: |T1 - T2| * 100.
+ *
+ * hsp_eval_match: compute_3d_matches (:252-327) and compute_match_from_degree_cm (:385-427), one workgroup per group, one lane per
+ * threshold running the sequential greedy loop.
+ *   order (slots) int8: a group's predictions in the reference's argsort(scores)[::-1] -- descending score, equal scores by the
+ *   HIGHER original index first (numpy's stable ascending order, reversed; what its argsort gives for groups this small) --,
+ *   order[p_off + pos] = the group-local index of the prediction at position pos; score_sorted: its score.
+ *   IoU stage, for each of the T_iou thresholds (iou_thres holds them rounded to fp32, numpy >= 2's comparison of a float32 with
+ *   a Python float): predictions by position; each one's ground truths by argsort(iou_row)[::-1] (equal values by the higher index
+ *   first); matched ones skipped; STOP at the first iou < thres; match only on iou > thres.  iou_pred_match (slots, T_iou) int8:
+ *   [p_off + pos][t] = the matched ground truth's group-local index or -1; iou_gt_match (gt rows, T_iou): [g_off + j][t] = the
+ *   position of the matched prediction or -1.  (The tables are slot-major so that the lanes of a group store side by side.)
+ *   Pose stage: with pose_iou_index >= 0 (use_matches_for_pose) only the predictions and ground truths matched at that IoU
+ *   threshold take part, in their kept order; with -1 all do.  kept (n_groups, 2) int32 = how many of each.  For each of the
+ *   D1 x S1 thresholds (the lists with 360 and 100 appended by the caller; t = d * S1 + s): kept predictions by position, each
+ *   one's kept ground truths by ascending degree + shift (equal sums by the lower index, NaN last), matched ones skipped, pairs
+ *   with degree > deg_thres[d] or shift > shift_thres[s] skipped (`continue`: a NaN compares false and passes), the first one left
+ *   is taken.  pose_pred_match (slots, D1 * S1), pose_gt_match (gt rows, D1 * S1): as above with positions in the KEPT lists; a
+ *   group's slots past its kept count hold -1.  pose_score (slots): the kept predictions' scores, 0 past the kept count.
+ *
+ * hsp_eval_ap: compute_ap_from_matches_scores (:330-356), one workgroup per (class, threshold), and the mean row.
+ *   match (slots, T) int8 as written above; order (.) int32: slot numbers, class c's in [seg_off[c], seg_off[c + 1]) (seg_off
+ *   (C + 1) int32 on the device) by DESCENDING score, equal scores by ascending slot (the reference's order among equal scores of
+ *   different images is unspecified); the sort is the caller's (a stable device sort).  gt_count (C) int32 on the device: the
+ *   class's ground-truth entries -- for the pose table those the IoU filter kept.  Per class and threshold: matched > -1, running
+ *   count, precision count / (i + 1) in fp64, recall count / G in FP32, the sentinels, the running maximum of the precision from
+ *   the right, and the sum of (recall step) * precision over the points where the recall moves, added in numpy's pairwise order
+ *   (np.sum's: eight interleaved partial sums per block of up to 128 terms, blocks joined by halves, pieces of 8192 terms added
+ *   up in order), so the result is the
+ *   reference's bit for bit.  No predictions: 0.  Predictions but G == 0: NaN (numpy's 0 / 0).  aps (C + 2, T) fp64: row 0 (BG)
+ *   = 0, row c + 1 = class c, the last row = the mean of the class rows in row order (a NaN class makes it NaN).  That is
+ *   np.mean's order for fewer than 8 classes; from 8 classes on the reference's pose mean, taken over a strided 1-D slice, adds
+ *   pairwise and may differ from this row in the last bit (its IoU mean, taken along axis 0, never does).
+ *   ws: hsp_eval_ap_workspace_bytes(slots, T, C) = 8 T (slots + C), the terms of every (class, threshold).
+ *   slots >= 2^23: HSP_ERR_UNSUPPORTED (fp32 recalls of neighbouring counts must differ).
+ *
+ * All three: a NULL pointer, a size <= 0, pose_iou_index >= T_iou: HSP_ERR_BAD_ARG; nothing is launched on any refusal. */
+int hsp_eval_group_cap(void);
+int hsp_eval_pairs(const double *pred_RT, const double *pred_scale, const double *gt_RT, const double *gt_scale,
+                   const int32_t *gt_handle, const int32_t *groups, int n_groups, int max_group, float *iou, double *degree,
+                   double *shift, hspStream_t stream);
+int hsp_eval_match(const int32_t *groups, int n_groups, int max_group, const double *scores, const float *iou,
+                   const double *degree, const double *shift, const float *iou_thres, int T_iou, const double *deg_thres, int D1,
+                   const double *shift_thres, int S1, int pose_iou_index, int8_t *order, double *score_sorted,
+                   int8_t *iou_pred_match, int8_t *iou_gt_match, int8_t *pose_pred_match, int8_t *pose_gt_match,
+                   double *pose_score, int32_t *kept, hspStream_t stream);
+size_t hsp_eval_ap_workspace_bytes(int slots, int T, int C);
+int hsp_eval_ap(const int8_t *match, int slots, int T, const int32_t *order, const int32_t *seg_off, const int32_t *gt_count,
+                int C, double *aps, void *ws, size_t ws_bytes, hspStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
