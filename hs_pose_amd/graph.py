@@ -325,6 +325,18 @@ class GraphedStep:
         return out
 
 
+def check_accumulate(who, accumulate):
+    """the ``accumulate=`` argument of the graphed training steps: an int >= 1, and 1 with more than one rank (each rank's gate
+    would decide on its own loss, and the exchange of an accumulated gradient is not built).  Touches no device."""
+    if isinstance(accumulate, bool) or int(accumulate) != accumulate or int(accumulate) < 1:
+        raise ValueError(f"{who}: accumulate expects an integer >= 1, got {accumulate!r}")
+    if int(accumulate) > 1:
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            raise RuntimeError(f"{who}: accumulate > 1 is not offered with more than one rank")
+    return int(accumulate)
+
+
 class GraphedTrainStep:
     """One full training step of engine/train.py:76-104 with the device work replayed as a hipGraph:
 
@@ -381,17 +393,44 @@ class GraphedTrainStep:
         AND THE GROUPS' ``lr`` ARE CURRENT ONLY AFTER ``optimizer.sync_clock()`` (one small copy and a wait; ``optimizer.state_dict()``
         and ``TrainDriver.checkpoint()`` call it), which also returns the counters: applied, replays, skipped_nan,
         skipped_no_item, exhausted.
-      * No gradient accumulation and no data parallelism in this form."""
+      * No data parallelism in this form.
+
+    ``accumulate`` (default 1: nothing below applies, no code path changes): gradient accumulation as the reference has it,
+    quirks included (engine/train.py:99-114; tests/_accum_ref.py states the rules in plain Python).  THE
+    ARGUMENT IS NOT TAKEN FROM ``FLAGS.accumulate``: pass ``TrainDriver.accumulate``.  A counter ``micro`` plays the reference's
+    ``global_step``: it starts at ``global_step`` and advances on every replay, skipped ones included.  A replay whose loss is NaN
+    (or, with ``gate_info``, whose batch has no good item) is SKIPPED: its gradient stays out of the accumulator and nothing is
+    applied.  Otherwise the slot is TAKEN: the fresh gradient -- the body moves it into the optimizer's second flat buffer
+    (``_FlatGroup.flat_f``) and runs no ``clip_grad_norm_`` of its own -- is added to the accumulator (``flat_g``) by
+    ``hsp_grad_accumulate``, which also leaves the accumulator's squared norm beside it; the step (optimizer, scheduler, and
+    what stands for ``zero_grad``) is applied exactly when ``micro % accumulate == 0``, with the clip coefficient of the
+    ACCUMULATED gradient; on any other taken slot that coefficient is the reference's in-place clip, deferred into the next take.
+    Slot 0 steps on its own gradient alone, and a skipped stepping slot lets the accumulator grow until the next
+    ``micro % accumulate == 0``.  No memset follows a step: while nothing is pending the accumulator's contents mean nothing
+    (``optimizer.accumulated_grads()`` gives what ``p.grad`` would hold in the eager driver).
+      * ``apply='graph'``: gate (``hsp_step_gate_accum``), gated accumulate and gated Ranger launch are inside the capture;
+        ``run()`` stays the owner's ``advance()`` plus one graph launch, ``run(check_nan=True)`` returns whether the slot was
+        TAKEN, and ``optimizer.sync_clock()`` reports ``micro`` and ``pending`` with the other counters.
+      * ``apply='host'``: ``replay()`` ends at the fresh buffer; ``apply()`` issues the accumulate and, on a stepping slot,
+        ``optimizer.step()`` and ``scheduler.step()``; ``run(check_nan=True)`` skips ``apply()`` on a NaN loss and still advances
+        ``micro`` (``skip()``); the host keeps ``micro`` and ``pending`` (``optimizer._accum``).
+      * More than one rank is refused in both forms; ``TrainDriver.checkpoint()`` carries the accumulator while one is pending."""
 
     def __init__(self, network, optimizer, batch, scheduler=None, max_norm=5, warmup=3, prologue=None, draws=None,
-                 apply="host", horizon=None, gate_info=None):
+                 apply="host", horizon=None, gate_info=None, accumulate=1, global_step=0):
+        self.accumulate = check_accumulate("GraphedTrainStep", accumulate)      # (before anything touches the device)
         if apply not in ("host", "graph"):
             raise ValueError(f"GraphedTrainStep: apply expects 'host' or 'graph', got {apply!r}")
         self.net, self.opt, self.sched, self.max_norm = network, optimizer, scheduler, max_norm
         self.batch = batch
         self._prologue = prologue
         # apply='graph': tables and the UNARMED control block go up here, before the warm-up (an upload cannot be captured)
-        self.clock = optimizer.device_clock(scheduler, horizon, info=gate_info) if apply == "graph" else None
+        self.clock = (optimizer.device_clock(scheduler, horizon, info=gate_info, accumulate=self.accumulate, global_step=global_step)
+                      if apply == "graph" else None)
+        # accumulate > 1: flat_g becomes the accumulator, the fresh gradient gets a flat buffer of its own (made here, once)
+        self.accum = optimizer.accumulation(self.accumulate, global_step, max_norm, clock=self.clock) if self.accumulate > 1 else None
+        if self.accum is None:
+            optimizer._accum = None                          # (an earlier accumulating object on this optimizer no longer speaks for it)
         PC = batch["PC"]
         B, N, _ = PC.shape
         self.n_points = N
@@ -445,6 +484,9 @@ class GraphedTrainStep:
         with ops.StepFolds():
             total.backward()
         torch._foreach_copy_(views, [p.grad if p.grad is not None else torch.zeros_like(p) for p in params])
+        if self.accum is not None:
+            self._body_accumulate(ld, total)
+            return
         for p, v in zip(params, views):
             p.grad = v
         self.opt.clip_grad_norm_(self.max_norm)             # device scalar; consumed by the step() outside the graph
@@ -454,12 +496,26 @@ class GraphedTrainStep:
             self.clock.gate(total.detach())
             self.clock.step()
 
+    def _body_accumulate(self, ld, total):
+        """accumulate > 1: the fresh gradient is in ``flat_f``; ``.grad`` names the accumulator's views.  No norm of the fresh
+        gradient: the clip acts on the accumulated one (``hsp_grad_accumulate``)."""
+        fg = self.opt._flat[0]
+        for p, o in zip(fg.params, fg.offsets):
+            p.grad = fg.view(fg.flat_g, p, o)
+        self.loss_dict, self.total = ld, total
+        if self.clock is not None:                          # apply='graph': gate -> accumulate (gated) -> gated Ranger launch
+            self.clock.gate(total.detach())
+            self.accum.take()
+            self.opt._gnorm_sq, self.opt._max_norm = self.accum.norm_sq, self.accum.max_norm
+            self.clock.step()
+
     def _params_and_views(self):
         params, views = [], []
         for fg in self.opt._flat:
+            flat = fg.flat_g if self.accum is None else fg.flat_f
             for p, o in zip(fg.params, fg.offsets):
                 params.append(p)
-                views.append(fg.view(fg.flat_g, p, o))
+                views.append(fg.view(flat, p, o))
         return params, views
 
     def load_batch(self, batch):
@@ -475,18 +531,40 @@ class GraphedTrainStep:
         """the fused optimizer launch (clip coefficient inside) and the scheduler, behind ``replay()``"""
         if self.clock is not None:
             raise RuntimeError("GraphedTrainStep(apply='graph'): the step is applied inside the replay; there is nothing to apply()")
+        if self.accum is not None:                           # the taken slot of engine/train.py:105-114
+            acc = self.accum
+            acc.take(first=acc.pending == 0)
+            acc.pending += 1
+            if acc.micro % acc.accumulate == 0:
+                self.opt._gnorm_sq, self.opt._max_norm = acc.norm_sq, acc.max_norm
+                self.opt.step()
+                if self.sched is not None:
+                    self.sched.step()
+                acc.pending = 0                              # (zero_grad: the next take starts a fresh accumulator)
+            acc.micro += 1
+            return
         self.opt._gnorm_sq, self.opt._max_norm = self._gnorm_sq, self._max_norm
         self.opt.step()
         if self.sched is not None:
             self.sched.step()
 
+    def skip(self):
+        """``apply='host'``: the owner found this replay's slot skipped (NaN loss, no good item) and will not ``apply()`` it.
+        Under accumulation the slot still passes -- ``micro`` advances --; otherwise there is nothing to do."""
+        if self.accum is not None and self.clock is None:
+            self.accum.micro += 1
+
     def run(self, check_nan=False):
         """one training step; returns False when ``check_nan`` found a NaN loss (the reference's skip, train.py:91-95).
-        ``apply='graph'``: the replay IS the step, and ``check_nan`` only reads the device's decision back (the one wait)."""
+        ``apply='graph'``: the replay IS the step, and ``check_nan`` only reads the device's decision back (the one wait):
+        whether the step was applied or, under accumulation, whether the slot was taken."""
         self.replay()
         if self.clock is not None:
-            return self.clock.applied_last() if check_nan else True
+            if not check_nan:
+                return True
+            return self.clock.applied_last() if self.accum is None else self.clock.taken_last()
         if check_nan and bool(torch.isnan(self.total).any()):
+            self.skip()
             return False
         self.apply()
         return True

@@ -21,9 +21,10 @@ import torch
 from torch.optim.optimizer import Optimizer
 
 from . import ops
-from ._lib import (STEP_ADAPTIVE, STEP_CTL_APPLIED, STEP_CTL_APPLY, STEP_CTL_ARMED, STEP_CTL_EXHAUSTED, STEP_CTL_INDEX,
-                   STEP_CTL_REPLAYS, STEP_CTL_SKIPPED_NAN, STEP_CTL_SKIPPED_NO_ITEM, STEP_CTL_SLOTS, STEP_FILL_SLOW,
-                   STEP_LOOKAHEAD, HspError, HspRowDesc, lib)
+from ._lib import (STEP_ADAPTIVE, STEP_CTL_APPLIED, STEP_CTL_APPLY, STEP_CTL_ARMED, STEP_CTL_EXHAUSTED, STEP_CTL_FIRST,
+                   STEP_CTL_INDEX, STEP_CTL_MICRO, STEP_CTL_PENDING, STEP_CTL_REPLAYS, STEP_CTL_SKIPPED_NAN,
+                   STEP_CTL_SKIPPED_NO_ITEM, STEP_CTL_SLOTS, STEP_CTL_TAKE, STEP_FILL_SLOW, STEP_LOOKAHEAD, HspError,
+                   HspRowDesc, lib)
 from .config import FLAGS
 
 _ROW_CHUNK = 4096          # 1-D tensors are cut into rows of at most this many elements
@@ -71,6 +72,14 @@ class _FlatGroup:
         self.rows_host = rows                                  # (offset, len, gc) in HspRowDesc's field order
         self.rows = self._upload(rows)
         self.nrows = len(rows)
+        self.flat_f = None                                     # the FRESH gradient of a replay (gradient accumulation only)
+
+    def fresh(self):
+        """the second flat gradient buffer, made when gradient accumulation is first asked for: a replay's fresh gradient lands
+        here, and ``flat_g`` becomes the accumulator ``hsp_grad_accumulate`` adds it to"""
+        if self.flat_f is None:
+            self.flat_f = torch.zeros_like(self.flat_g)
+        return self.flat_f
 
     def _upload(self, rows):
         return ops.upload_table((HspRowDesc * len(rows))(*rows), self.flat_p.device)
@@ -150,12 +159,22 @@ class DeviceClock:
     groups' ``lr`` are current only after ``Ranger.sync_clock()``.
 
     The block is built UNARMED: the gate then answers "do not apply" and counts nothing, so the warm-up runs of a capture
-    execute both kernels and leave parameters, optimizer state and counters as they were.  ``arm()`` uploads armed = 1."""
+    execute both kernels and leave parameters, optimizer state and counters as they were.  ``arm()`` uploads armed = 1.
+
+    ``accumulate`` > 1: ``gate`` issues ``hsp_step_gate_accum`` instead, which also keeps ``micro`` -- the reference's
+    ``global_step``, starting at ``global_step`` and advancing on every armed replay -- and ``pending``, the micro-batches in the
+    accumulator (slots 8-11 of the block); the step is applied on the replays with ``micro % accumulate == 0``.  ``rebuild()``
+    leaves ``micro`` and ``pending`` as they stand on the device."""
 
     COUNTERS = ("applied", "replays", "skipped_nan", "skipped_no_item", "exhausted")
 
-    def __init__(self, optimizer, scheduler, horizon, info=None):
+    def __init__(self, optimizer, scheduler, horizon, info=None, accumulate=1, global_step=0):
         self.opt, self.sched, self.info = optimizer, scheduler, info
+        self.accumulate = int(accumulate)
+        if self.accumulate < 1:
+            raise ValueError(f"device_clock: expects accumulate >= 1, got {accumulate}")
+        if not 0 <= int(global_step) < 2 ** 31 - 1:
+            raise ValueError(f"device_clock: global_step expects a non-negative int32, got {global_step}")
         if horizon is None:
             if scheduler is None or not hasattr(scheduler, "total_iters"):
                 raise ValueError("device_clock: horizon=None needs a scheduler that records total_iters "
@@ -171,6 +190,12 @@ class DeviceClock:
         self.tables = [torch.zeros(self.horizon * STEP_ENTRY.itemsize, dtype=torch.uint8, device=dev) for _ in optimizer._flat]
         self.tables_host = None
         self.rebuild()
+        if self.accumulate > 1:
+            self.set_micro(int(global_step), 0)
+
+    def set_micro(self, micro, pending):
+        """``micro`` and ``pending`` as the host gives them (construction, a loaded checkpoint): one small upload"""
+        self.ctl[STEP_CTL_MICRO:STEP_CTL_PENDING + 1].copy_(torch.tensor([int(micro), 0, 0, int(pending)], dtype=torch.int32))
 
     def rebuild(self):
         """tabulate the next ``horizon`` steps from the optimizer's and the scheduler's counts AS THEY STAND ON THE HOST, into
@@ -188,7 +213,11 @@ class DeviceClock:
             self.step0.append(step0)
             self.slow_ready0.append(bool(fg.slow_ready))
             self.tables_host.append(tab)
-        self.ctl[1:].zero_()
+        if self.accumulate > 1:                                # micro and pending go on from where they are
+            self.ctl[1:STEP_CTL_MICRO].zero_()
+            self.ctl[STEP_CTL_TAKE:STEP_CTL_FIRST + 1].zero_()
+        else:
+            self.ctl[1:].zero_()
 
     def arm(self, on=True):
         self.ctl[STEP_CTL_ARMED:STEP_CTL_ARMED + 1].fill_(1 if on else 0)
@@ -196,6 +225,10 @@ class DeviceClock:
     def gate(self, total):
         if not total.is_cuda or total.dtype != torch.float32 or total.numel() != 1:
             raise HspError(f"DeviceClock.gate: expects the fp32 total loss on the device, got {total.dtype} {tuple(total.shape)}")
+        if self.accumulate > 1:
+            ops._run("hsp_step_gate_accum", (ops._p(total), ops._p(self.info), ops._p(self.ctl), self.horizon, self.accumulate,
+                                             ops._stream()))
+            return
         ops._run("hsp_step_gate", (ops._p(total), ops._p(self.info), ops._p(self.ctl), self.horizon, ops._stream()))
 
     def step(self):
@@ -214,15 +247,80 @@ class DeviceClock:
 
     def read(self):
         """the control block, one small device->host copy (a wait): {'armed', 'apply', 'index', 'applied', 'replays',
-        'skipped_nan', 'skipped_no_item', 'exhausted'}"""
+        'skipped_nan', 'skipped_no_item', 'exhausted'} and the accumulation slots {'micro', 'take', 'first', 'pending'}, which
+        stay 0 unless ``accumulate`` > 1"""
         c = self.ctl.cpu().tolist()
         return dict(armed=c[STEP_CTL_ARMED], apply=c[STEP_CTL_APPLY], index=c[STEP_CTL_INDEX], applied=c[STEP_CTL_APPLIED],
                     replays=c[STEP_CTL_REPLAYS], skipped_nan=c[STEP_CTL_SKIPPED_NAN],
-                    skipped_no_item=c[STEP_CTL_SKIPPED_NO_ITEM], exhausted=c[STEP_CTL_EXHAUSTED])
+                    skipped_no_item=c[STEP_CTL_SKIPPED_NO_ITEM], exhausted=c[STEP_CTL_EXHAUSTED],
+                    micro=c[STEP_CTL_MICRO], take=c[STEP_CTL_TAKE], first=c[STEP_CTL_FIRST], pending=c[STEP_CTL_PENDING])
 
     def applied_last(self):
         """the device's decision on the last replay (a wait)"""
         return bool(int(self.ctl[STEP_CTL_APPLY]))
+
+    def taken_last(self):
+        """``accumulate`` > 1: whether the last replay's gradient entered the accumulator (a wait)"""
+        return bool(int(self.ctl[STEP_CTL_TAKE]))
+
+
+class GradAccumulation:
+    """Gradient accumulation on a ``Ranger``'s flat buffers (``Ranger.accumulation``; engine/train.py:99-114).  ``flat_g`` is the
+    ACCUMULATOR -- what ``hsp_ranger_step`` / ``hsp_ranger_step_gated`` read --, ``flat_f`` (``_FlatGroup.fresh``) receives a
+    replay's fresh gradient, ``norm_sq`` is the device scalar ``hsp_grad_accumulate`` keeps beside the accumulator: its squared
+    norm, from which the next take, or the step, derives the clip coefficient.  WHILE ``pending == 0`` THE CONTENTS OF THE
+    ACCUMULATOR AND OF ``norm_sq`` MEAN NOTHING: nothing clears them after a step, the next take starts afresh.
+
+    ``micro`` (the reference's ``global_step``) and ``pending`` (micro-batches in the accumulator) live on the device when a
+    ``DeviceClock`` decides (``clock``), else here on the host.  One parameter group only."""
+
+    def __init__(self, optimizer, accumulate, global_step=0, max_norm=5, clock=None):
+        if len(optimizer._flat) != 1:
+            raise HspError("gradient accumulation on the flat buffers is built for one parameter group (HSPose.build_params' one)")
+        self.opt, self.clock = optimizer, clock
+        self.accumulate, self.max_norm = int(accumulate), float(max_norm)
+        self.micro, self.pending = int(global_step), 0
+        fg = optimizer._flat[0]
+        fg.fresh()
+        self.norm_sq = torch.zeros(1, dtype=torch.float32, device=fg.flat_g.device)
+        self.ws_bytes = lib().hsp_sumsq_workspace_bytes(fg.total)
+        self.ws = ops._ws(self.ws_bytes, fg.flat_g.device)
+
+    def take(self, first=None):
+        """``hsp_grad_accumulate``: ``flat_g = flat_g * c + flat_f`` (``first``: ``0 + flat_f``) and ``norm_sq`` of the result.
+        ``first`` None: gated -- take and first are the device clock's."""
+        fg = self.opt._flat[0]
+        ctl = self.clock.ctl if first is None else None
+        ops._run("hsp_grad_accumulate",
+                 (ops._p(fg.flat_g), ops._p(fg.flat_f), fg.total, ops._p(self.norm_sq), self.max_norm, int(bool(first)),
+                  ops._p(ctl), ops._p(self.ws), self.ws_bytes, ops._stream()),
+                 key=f"n{fg.total}", abytes=fg.total * (8 if first else 12))
+
+    def counts(self):
+        """(micro, pending): the host's, or the device clock's (a wait)"""
+        if self.clock is None:
+            return self.micro, self.pending
+        c = self.clock.read()
+        return c["micro"], c["pending"]
+
+    def state(self):
+        """what a checkpoint needs to resume bit for bit, or None while nothing is pending"""
+        micro, pending = self.counts()
+        if pending == 0:
+            return None
+        return dict(micro=micro, pending=pending, grad=self.opt._flat[0].flat_g.detach().clone(),
+                    norm_sq=self.norm_sq.detach().clone())
+
+    def load_state(self, st):
+        """``state()``'s dict; None (a checkpoint taken with nothing pending): pending = 0, micro stays what the object was
+        built with -- like the reference, which derives global_step from the epoch it resumes at"""
+        micro, pending = (int(st["micro"]), int(st["pending"])) if st is not None else (self.counts()[0], 0)
+        if st is not None:
+            self.opt._flat[0].flat_g.copy_(st["grad"])
+            self.norm_sq.copy_(st["norm_sq"])
+        self.micro, self.pending = micro, pending
+        if self.clock is not None:
+            self.clock.set_micro(micro, pending)
 
 
 class Ranger(Optimizer):
@@ -248,6 +346,7 @@ class Ranger(Optimizer):
         self._gnorm_sq = None            # device scalar written by clip_grad_norm_, consumed by the next step()
         self._max_norm = 0.0
         self._clock = None               # a DeviceClock (device_clock()): the step count then lives on the device
+        self._accum = None               # a GradAccumulation (accumulation()): flat_g is then the accumulator
         for fg in self._flat:
             for p, o in zip(fg.params, fg.offsets):
                 self.state[p] = dict(step=0, exp_avg=fg.view(fg.flat_m, p, o), exp_avg_sq=fg.view(fg.flat_v, p, o),
@@ -337,7 +436,7 @@ class Ranger(Optimizer):
         return loss
 
     # -- the step clock on the device ------------------------------------------------------------------------
-    def device_clock(self, scheduler=None, horizon=None, info=None):
+    def device_clock(self, scheduler=None, horizon=None, info=None, accumulate=1, global_step=0):
         """Attach and return a ``DeviceClock``: the next ``horizon`` steps tabulated from this optimizer's step counts and
         ``scheduler``'s epoch (a ``LambdaLR``; None: the groups' ``lr`` as they stand), and an unarmed control block.
         ``horizon`` None: the rest of the schedule, ``scheduler.total_iters - scheduler.last_epoch``.  ``info``:
@@ -345,8 +444,9 @@ class Ranger(Optimizer):
 
         FROM HERE ON ``step()`` raises and ``scheduler.step()`` is never to be called: the counts advance on the device, and
         ``state[p]['step']``, ``scheduler.last_epoch`` and the groups' ``lr`` are current only after ``sync_clock()``
-        (``state_dict()`` and ``TrainDriver.checkpoint()`` call it).  Not offered with gradient accumulation or more than one
-        rank: the ranks' gates could disagree."""
+        (``state_dict()`` and ``TrainDriver.checkpoint()`` call it).  Not offered with more than one rank: the ranks' gates could
+        disagree.  ``accumulate`` > 1: the clock also counts the micro-batches from ``global_step`` on and applies the step when
+        ``micro % accumulate == 0`` (``DeviceClock``); ``sync_clock()`` then reports ``micro`` and ``pending`` too."""
         import torch.distributed as dist
         if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
             raise HspError("Ranger.device_clock: not offered with more than one rank (each rank's gate would decide on its own loss)")
@@ -354,8 +454,33 @@ class Ranger(Optimizer):
             raise ValueError("Ranger.device_clock: expects a LambdaLR scheduler (its lr_lambdas are tabulated) or None")
         if self._clock is not None:                        # a new clock starts from where the old one got to
             self.sync_clock()
-        self._clock = DeviceClock(self, scheduler, horizon, info)
+        self._clock = DeviceClock(self, scheduler, horizon, info, accumulate, global_step)
         return self._clock
+
+    # -- gradient accumulation -------------------------------------------------------------------------------
+    def accumulation(self, accumulate, global_step=0, max_norm=5, clock=None):
+        """Attach and return a ``GradAccumulation``: from here on ``flat_g`` is the accumulator and a fresh gradient belongs in
+        ``_flat[0].flat_f``.  ``clock``: the ``DeviceClock`` (built with the same ``accumulate``) whose gate decides; None: the
+        host counts ``micro`` and ``pending``."""
+        if int(accumulate) < 1:
+            raise ValueError(f"Ranger.accumulation: expects accumulate >= 1, got {accumulate}")
+        self._accum = GradAccumulation(self, accumulate, global_step, max_norm, clock)
+        return self._accum
+
+    def accumulated_grads(self):
+        """The accumulated gradient of every parameter as ``p.grad`` would hold it in the eager driver, as fresh tensors: the
+        accumulator with the pending clip coefficient applied (the clip of an accumulate-only slot is deferred into the next
+        take), zeros while nothing is pending.  A wait when the counts live on the device."""
+        acc = getattr(self, "_accum", None)
+        if acc is None:
+            raise HspError("Ranger.accumulated_grads: no gradient accumulation attached (accumulation())")
+        fg = self._flat[0]
+        if acc.counts()[1] == 0:
+            flat = torch.zeros_like(fg.flat_g)
+        else:
+            coef = torch.clamp(torch.full_like(acc.norm_sq, acc.max_norm) / (acc.norm_sq.sqrt() + 1e-6), max=1.0)
+            flat = fg.flat_g * coef
+        return [fg.view(flat, p, o).clone() for p, o in zip(fg.params, fg.offsets)]
 
     def sync_clock(self):
         """One small device->host copy of the control block (a wait); the host's mirror is set to what the host-driven path would

@@ -22,7 +22,7 @@ import torch.distributed as dist
 
 from . import ops, pc_sample
 from .config import FLAGS
-from .graph import GraphedTrainStep
+from .graph import GraphedTrainStep, check_accumulate
 from .parallel import mean_flat_gradients
 from .solver import build_lr_rate, build_optimizer
 
@@ -83,7 +83,10 @@ class TrainDriver:
     def checkpoint(self, seed, epoch):
         """the dict engine/train.py:115-123 passes to torch.save (same keys, same sub-layouts); with a device sampler also
         'draws': its (seed, call) state.  With a device clock on the optimizer (``apply='graph'``) the host's mirror of the step
-        count and the schedule is brought up to date first (``Ranger.sync_clock``: one small copy, a wait)."""
+        count and the schedule is brought up to date first (``Ranger.sync_clock``: one small copy, a wait).  With gradient
+        accumulation attached to the optimizer (``GraphedTrainStep(accumulate=...)``) and micro-batches pending, also 'accum':
+        {'micro', 'pending', 'grad' (the accumulator), 'norm_sq'} -- the reference saves no gradients; this is for the
+        bit-reproducible resume.  With nothing pending the keys are the reference's."""
         if getattr(self.optimizer, "_clock", None) is not None:
             self.optimizer.sync_clock()                        # before the scheduler is read below
         ckpt = {
@@ -95,6 +98,10 @@ class TrainDriver:
         }
         if self.draws is not None:
             ckpt['draws'] = tuple(self.draws.get_state())
+        accum = getattr(self.optimizer, "_accum", None)
+        state = accum.state() if accum is not None else None   # (None while nothing is pending: the keys stay as they were)
+        if state is not None:
+            ckpt['accum'] = state
         return ckpt
 
     def load_checkpoint(self, ckpt):
@@ -109,6 +116,9 @@ class TrainDriver:
             self.optimizer._clock.rebuild()                    # tables from the loaded step count AND the loaded epoch
         if self.draws is not None and 'draws' in ckpt:
             self.draws.set_state(ckpt['draws'])
+        accum = getattr(self.optimizer, "_accum", None)
+        if accum is not None:                                  # after the clock's rebuild, which leaves micro / pending alone
+            accum.load_state(ckpt.get('accum'))
         return ckpt.get('epoch', -1) + 1
 
 
@@ -156,10 +166,16 @@ class FrameTrainStep:
     optimizer launch are inside the replay too.  ``run(check=False)`` is then SAFE -- an all-rejected batch or a NaN loss leaves
     parameters and optimizer state untouched and is counted on the device (``skipped_no_item``, ``skipped_nan``) -- and never
     waits; ``run(check=True)`` reads the device's decision back and returns it.  The scheduler object and the optimizer's step
-    counts are current only after ``optimizer.sync_clock()``; on a skipped step the BatchNorm statistics have moved."""
+    counts are current only after ``optimizer.sync_clock()``; on a skipped step the BatchNorm statistics have moved.
+
+    ``accumulate``, ``global_step``: ``GraphedTrainStep``'s gradient accumulation, passed on (pass ``TrainDriver.accumulate``; the
+    flag is not followed implicitly).  A slot without a good item behaves like a NaN slot in both forms: it passes, nothing enters
+    the accumulator, nothing is applied.  With ``run(check=True)`` and ``apply='graph'`` the answer is whether the slot was TAKEN."""
 
     def __init__(self, network, optimizer, frames, items, keep, scheduler=None, sampler=None, n_pts=None, out_size=None,
-                 min_pts=50, mask_pro=None, max_norm=5, warmup=3, draws=None, apply="host", horizon=None):
+                 min_pts=50, mask_pro=None, max_norm=5, warmup=3, draws=None, apply="host", horizon=None, accumulate=1,
+                 global_step=0):
+        check_accumulate("FrameTrainStep", accumulate)          # (before anything touches the device)
         depth = frames["depth"]
         dev = depth.device
         if depth.dim() != 3 or not 1 <= int(keep) <= depth.shape[0]:
@@ -209,7 +225,8 @@ class FrameTrainStep:
         state = self.sampler.get_state()                        # (the eager warm-up calls advance; the captured call does not)
         self.graphed = GraphedTrainStep(network, optimizer, shapes, scheduler=scheduler, max_norm=max_norm, warmup=warmup,
                                         prologue=front_end, draws=self.draws or "host",
-                                        apply=apply, horizon=horizon, gate_info=self.info if apply == "graph" else None)
+                                        apply=apply, horizon=horizon, gate_info=self.info if apply == "graph" else None,
+                                        accumulate=accumulate, global_step=global_step)
         self.sampler.set_state(state)
 
     @staticmethod
@@ -268,8 +285,12 @@ class FrameTrainStep:
         self.sampler.advance()
         self.graphed.replay()
         if self.graphed.clock is not None:                      # apply='graph': the device decided inside the replay
-            return self.graphed.clock.applied_last() if check else True
+            if not check:
+                return True
+            clock = self.graphed.clock
+            return clock.applied_last() if self.graphed.accum is None else clock.taken_last()
         if check and bool((self.info[0] == 0) | torch.isnan(self.graphed.total).any()):
+            self.graphed.skip()                                 # (under accumulation the slot still passes)
             return False
         self.graphed.apply()
         return True

@@ -1008,7 +1008,8 @@ int hsp_ranger_step(float *params, const float *grads, float *exp_avg, float *ex
  *   slot 5  HSP_STEP_CTL_SKIPPED_NAN      of those, skipped for a NaN loss
  *   slot 6  HSP_STEP_CTL_SKIPPED_NO_ITEM  of those, skipped because no item of the batch was good
  *   slot 7  HSP_STEP_CTL_EXHAUSTED        1 once a step was refused because the table had no entry left
- *   slots 8-15 reserved: no launch writes them
+ *   slots 8-15: hsp_step_gate and hsp_ranger_step_gated never touch them.  Slots 8-11 belong to hsp_step_gate_accum (below),
+ *   slots 12-15 are reserved: no launch writes them
  *
  * hsp_step_gate: one launch of one wave, one lane decides, rules in this order:
  *   1. armed == 0: apply = 0, nothing else changes
@@ -1043,6 +1044,61 @@ int hsp_ranger_step_gated(float *params, const float *grads, float *exp_avg, flo
                           const HspRowDesc *rows, int nrows, float beta1, float beta2, float eps, float weight_decay,
                           float la_alpha, int gc_after, const float *gnorm_sq, float max_norm,
                           const HspStepEntry *table, const int32_t *ctl, int horizon, hspStream_t stream);
+
+/* ---- gradient accumulation under the device's decision (FLAGS.accumulate, engine/train.py:99-114) ----
+ * The reference steps when global_step % accumulate == 0 and otherwise only adds the batch's gradient to .grad; it runs
+ * clip_grad_norm_ on the ACCUMULATED gradient after every backward, and a NaN loss skips the batch before its backward while
+ * global_step still advances.  Here the fresh gradient of a replay lands in a buffer of its own and is added to the accumulator --
+ * the `grads` buffer hsp_ranger_step_gated reads -- only when the gate took the slot.
+ *
+ * Further control slots (same block, same sixteen int32):
+ *   slot 8   HSP_STEP_CTL_MICRO    the reference's global_step: set by the host when the block is built, += 1 by EVERY armed
+ *                                  hsp_step_gate_accum launch, skipped and refused slots included
+ *   slot 9   HSP_STEP_CTL_TAKE     this replay's fresh gradient enters the accumulator, written by every gate launch
+ *   slot 10  HSP_STEP_CTL_FIRST    this take starts a fresh accumulator (valid while take == 1)
+ *   slot 11  HSP_STEP_CTL_PENDING  micro-batches in the accumulator after this replay
+ * While pending == 0 the contents of the accumulator and of the norm scalar mean nothing: no launch clears them after a step,
+ * the next take has first == 1 and neither reads the accumulator nor the scalar.
+ *
+ * hsp_step_gate_accum: hsp_step_gate for accumulate >= 1 micro-batches per step.  One launch of one wave, one lane decides and
+ * makes ALL state transitions; hsp_grad_accumulate and hsp_ranger_step_gated only read the block.  Rules in this order:
+ *   1. armed == 0: take = 0, apply = 0, nothing else changes
+ *   2. replays += 1; take = first = apply = 0
+ *   3. isnan(*total): skipped_nan += 1                      (NaN only: +-inf is taken)
+ *   4. else info != NULL and info[0] == 0: skipped_no_item += 1
+ *   5. else applied >= horizon: exhausted = 1               (nothing taken, nothing applied)
+ *   6. else take = 1, first = (pending == 0), pending += 1; and when micro % accumulate == 0: apply = 1, index = applied,
+ *      applied += 1, pending = 0                            (micro = 0 steps on its own gradient alone: the reference's quirk)
+ *   7. micro += 1                                           (after rules 3-6, whichever held)
+ * A skipped stepping slot applies nothing, so the accumulator keeps growing until the next micro % accumulate == 0.
+ * HSP_ERR_BAD_ARG: total or ctl NULL, horizon <= 0, accumulate <= 0.
+ *
+ * hsp_grad_accumulate: acc (n floats) takes in fresh (n floats), and norm_sq[0] becomes the squared norm of the result.
+ *   - Every element: acc[i] = first ? 0.0f + fresh[i] : fl(fl(acc[i] * c) + fresh[i]).  Two roundings, multiply then add: the
+ *     library is built with contraction off and no fused multiply-add may form here; the bits are those of scaling the
+ *     accumulator in place and then adding to it.
+ *   - c = min(1, max_norm / (sqrt(norm_sq[0]) + 1e-6)) (a NaN norm gives a NaN c), from the value norm_sq[0] holds when the call
+ *     begins: the squared norm of the accumulator as the previous take left it.  This is the reference's in-place clip of an
+ *     accumulate-only iteration, DEFERRED: the accumulator is not swept a second time to scale it, the coefficient stays pending
+ *     in norm_sq beside it and is folded into the next take.  The stepping slot's hsp_ranger_step(_gated) applies the
+ *     coefficient of the final norm itself, as it always has.  With first != 0 neither acc nor norm_sq is read.
+ *   - norm_sq[0] is overwritten at the end of the call with the sum of squares of the new acc, accumulated in the same pass and
+ *     by the same element -> lane -> partial -> fold mapping as hsp_sumsq_f32 (one device function instantiated by both): it is
+ *     bit-equal to hsp_sumsq_f32 run over acc afterwards.
+ *   - ctl NULL: `first` is the argument and the call always takes.  ctl given (the block hsp_step_gate_accum wrote): every
+ *     workgroup reads take and first from it and the argument is ignored; with take == 0 acc and norm_sq are left untouched.
+ *   - acc and fresh must not overlap and both need 16-byte alignment (else HSP_ERR_UNSUPPORTED); ws / ws_bytes as for
+ *     hsp_sumsq_f32 (hsp_sumsq_workspace_bytes(n), else HSP_ERR_WORKSPACE).  Ordinary vector loads and stores, no atomics.
+ *   - 12 B per element (8 B with first).  HSP_ERR_BAD_ARG: acc, fresh or norm_sq NULL, n <= 0.
+ */
+#define HSP_STEP_CTL_MICRO 8
+#define HSP_STEP_CTL_TAKE 9
+#define HSP_STEP_CTL_FIRST 10
+#define HSP_STEP_CTL_PENDING 11
+int hsp_step_gate_accum(const float *total, const int32_t *info, int32_t *ctl, int horizon, int accumulate,
+                        hspStream_t stream);
+int hsp_grad_accumulate(float *acc, const float *fresh, long long n, float *norm_sq, float max_norm, int first,
+                        const int32_t *ctl, void *ws, size_t ws_bytes, hspStream_t stream);
 
 /* ---- Chamfer distance -------------------------------------------------------------------------
  * replaces cd.forward_cuda / cd.backward_cuda    tools/pyTorchChamferDistance/chamfer_distance.cpp:27-56
