@@ -19,8 +19,10 @@
 //  * (R|t) assembly: replaces generate_RT(..., mode='vec') (tools/geom_utils.py:232-244 with
 //    tools/rot_utils.py:39-100): confidence-weighted orthogonalisation of the two predicted axes and
 //    the 4x4 pose matrix, one lane per object instead of ~40 tiny launches.
-// The listing is ONE skeleton (chunk_count, prefix_sums, chunk_rank, store_ids) under four per-pixel predicates -- hsp_pc_compact,
-// hsp_roi_compact, hsp_crop_compact, hsp_roi_defor --; each form's section says what it adds.
+//  * a video stream, optionally: the crop decided by the pose the previous frame left on the device instead of a detector's
+//    mask and box (hsp_pose_windows, hsp_roi_compact_box, hsp_track_update), so that a tracked frame is one replay.
+// The listing is ONE skeleton (chunk_count, prefix_sums, chunk_rank, store_ids) under five per-pixel predicates -- hsp_pc_compact,
+// hsp_roi_compact, hsp_roi_compact_box, hsp_crop_compact, hsp_roi_defor --; each form's section says what it adds.
 #include <tuple>
 
 #include "common.h"
@@ -255,10 +257,12 @@ __device__ __forceinline__ int roi_source(const CropMap& cm, int q, int O, int H
 }
 
 // hsp_roi_compact: the skeleton over the O * O crop pixels of instance blockIdx.y, NC = 2, source ids listed.
-// The 16 consecutive crop pixels of one thread: source ids, bits[1] = depth > 0, bits[0] = depth > 0 and the mask value owned
-template <typename D>
-__device__ __forceinline__ void roi_scan16(const D* __restrict__ depth, const uint8_t* __restrict__ mask, const CropMap& cm,
-                                           int lo, int OO, int O, int H, int W, int (&src)[16], unsigned (&bits)[2]) {
+// The 16 consecutive crop pixels of one thread: source ids, bits[1] = depth > 0, bits[0] = depth > 0 and own(p) -- the form's
+// test of frame pixel p, asked only where the depth is valid: the mask value owned (MaskOwn), or the point inside the tracked
+// box (BoxOwn, below)
+template <typename D, typename Own>
+__device__ __forceinline__ void roi_scan16(const D* __restrict__ depth, const Own& own, const CropMap& cm, int lo, int OO, int O,
+                                           int H, int W, int (&src)[16], unsigned (&bits)[2]) {
     bits[0] = 0;
     bits[1] = 0;
 #pragma unroll
@@ -268,12 +272,17 @@ __device__ __forceinline__ void roi_scan16(const D* __restrict__ depth, const ui
         if (q < OO) p = roi_source(cm, q, O, H, W);
         src[i] = p;
         if (p >= 0 && depth[p] > (D)0) {
-            const int m = mask[p];
             bits[1] |= 1u << i;
-            if (cm.owns(m)) bits[0] |= 1u << i;
+            if (own(p)) bits[0] |= 1u << i;
         }
     }
 }
+
+struct MaskOwn {
+    const uint8_t* __restrict__ mask;
+    const CropMap& cm;
+    __device__ __forceinline__ bool operator()(int p) const { return cm.owns(mask[p]); }
+};
 
 template <typename D>
 __global__ __launch_bounds__(256) void roi_count_kernel(const D* __restrict__ depth, const uint8_t* __restrict__ mask,
@@ -283,8 +292,9 @@ __global__ __launch_bounds__(256) void roi_count_kernel(const D* __restrict__ de
     const int j = blockIdx.y;
     int src[16];
     unsigned bits[2];
-    roi_scan16(depth, mask + (size_t)j * mask_stride, crop_map(xf, inst_id, j), blockIdx.x * PC_CHUNK + threadIdx.x * 16, O * O,
-               O, H, W, src, bits);
+    const CropMap cm = crop_map(xf, inst_id, j);
+    roi_scan16(depth, MaskOwn{mask + (size_t)j * mask_stride, cm}, cm, blockIdx.x * PC_CHUNK + threadIdx.x * 16, O * O, O, H, W,
+               src, bits);
     chunk_count(bits, nchunk, cnt);
 }
 
@@ -300,8 +310,9 @@ __global__ __launch_bounds__(256) void roi_write_kernel(const D* __restrict__ de
     prefix_sums<2, false>(cnt, nchunk, sh);
     int src[16];
     unsigned bits[2];
-    roi_scan16(depth, mask + (size_t)j * mask_stride, crop_map(xf, inst_id, j), blockIdx.x * PC_CHUNK + threadIdx.x * 16, OO, O,
-               H, W, src, bits);
+    const CropMap cm = crop_map(xf, inst_id, j);
+    roi_scan16(depth, MaskOwn{mask + (size_t)j * mask_stride, cm}, cm, blockIdx.x * PC_CHUNK + threadIdx.x * 16, OO, O, H, W, src,
+               bits);
     int end;
     const int off = chunk_rank(bits[0], sh, end);
     store_ids(out_src + (size_t)j * OO, off, bits[0], src);
@@ -340,6 +351,206 @@ __global__ __launch_bounds__(256) void frames_to_pcl_kernel(const D* __restrict_
     const int c = choose[e];
     const int p = (c >= 0 && c < src_stride) ? src[(size_t)j * src_stride + c] : -1;
     frame_pixel_xyz(depth + (size_t)j * depth_stride, H, W, camK + (camK_rows > 1 ? (size_t)j * 9 : 0), p, o);
+}
+
+// ---- instances followed from frame to frame (include/hsp.h states the contract, sentence by sentence) -----------------------
+// The crop of instance j is decided by the pose and size the last replay left on the device: hsp_pose_windows turns them into
+// the window (the transform rows the crop map reads), hsp_roi_compact_box is hsp_roi_compact with the mask replaced by "the
+// pixel's point lies inside the padded oriented box", hsp_track_update keeps the state.  Every float64 operation is spelled
+// with its _rn form: one rounding each, in the header's order.
+
+// R (row-major, [r * 3 + c]) and t of a pose as doubles; the fourth row of RT is not read
+struct PoseF64 {
+    double R[9], t[3];
+};
+
+__device__ __forceinline__ PoseF64 load_pose(const float* __restrict__ rt) {
+    PoseF64 P;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) P.R[r * 3 + c] = (double)rt[r * 4 + c];
+        P.t[r] = (double)rt[r * 4 + 3];
+    }
+    return P;
+}
+
+// h_i = (0.5 * pad) * double(size_i)
+__device__ __forceinline__ void half_extents(const float* __restrict__ size, double pad, double (&h)[3]) {
+    const double hp = __dmul_rn(0.5, pad);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) h[i] = __dmul_rn(hp, (double)size[i]);
+}
+
+__device__ __forceinline__ bool finite_f64(double x) { return fabs(x) < INFINITY; }      // (false for NaN)
+
+__global__ __launch_bounds__(64) void pose_windows_kernel(const float* __restrict__ rt, const float* __restrict__ size,
+                                                          const double* __restrict__ camK, int camK_rows, int n, double Wm1,
+                                                          double Hm1, double O, double pad, int32_t* __restrict__ boxes,
+                                                          double* __restrict__ xf, int32_t* __restrict__ wstatus) {
+    const int j = blockIdx.x * 64 + threadIdx.x;
+    if (j >= n) return;
+    const PoseF64 P = load_pose(rt + (size_t)j * 16);
+    const double* __restrict__ K = camK + (camK_rows > 1 ? (size_t)j * 9 : 0);
+    const double K0 = K[0], K2 = K[2], K4 = K[4], K5 = K[5];
+    double h[3];
+    half_extents(size + (size_t)j * 3, pad, h);
+    bool ok = finite_f64(K0) && finite_f64(K2) && finite_f64(K4) && finite_f64(K5);
+#pragma unroll
+    for (int i = 0; i < 9; ++i) ok = ok && finite_f64(P.R[i]);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) ok = ok && finite_f64(P.t[i]) && finite_f64(h[i]) && h[i] > 0.0;   // (pad is finite: a finite h is a finite size)
+    double ulo = INFINITY, uhi = -INFINITY, vlo = INFINITY, vhi = -INFINITY;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const double e0 = (k & 1) ? h[0] : -h[0], e1 = (k & 2) ? h[1] : -h[1], e2 = (k & 4) ? h[2] : -h[2];
+        double c[3];
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+            c[r] = __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(P.R[r * 3], e0), __dmul_rn(P.R[r * 3 + 1], e1)),
+                                       __dmul_rn(P.R[r * 3 + 2], e2)), P.t[r]);
+        const double u = __dadd_rn(__ddiv_rn(__dmul_rn(K0, c[0]), c[2]), K2);
+        const double v = __dadd_rn(__ddiv_rn(__dmul_rn(K4, c[1]), c[2]), K5);
+        ok = ok && c[2] > 0.0 && finite_f64(u) && finite_f64(v);
+        ulo = fmin(ulo, u); uhi = fmax(uhi, u);
+        vlo = fmin(vlo, v); vhi = fmax(vhi, v);
+    }
+    // clamped as doubles: whatever the extremes, the four values that reach the conversion lie inside the frame
+    const double x1 = fmax(0.0, floor(ulo)), y1 = fmax(0.0, floor(vlo));
+    const double x2 = fmin(Wm1, ceil(uhi)), y2 = fmin(Hm1, ceil(vhi));
+    ok = ok && x2 > x1 && y2 > y1;
+    int32_t* __restrict__ b = boxes + (size_t)j * 4;
+    double* __restrict__ o = xf + (size_t)j * 3;
+    wstatus[j] = ok ? 0 : 4;
+    if (!ok) {
+        b[0] = b[1] = b[2] = b[3] = 0;
+        o[0] = o[1] = o[2] = 0.0;
+        return;
+    }
+    b[0] = (int)x1; b[1] = (int)y1; b[2] = (int)x2; b[3] = (int)y2;
+    // integers below 2^31: the sums, the halves and the differences are exact
+    const double cx = __dmul_rn(0.5, __dadd_rn(x1, x2)), cy = __dmul_rn(0.5, __dadd_rn(y1, y2));
+    const double scale = fmax(__dsub_rn(x2, x1), __dsub_rn(y2, y1));
+    // roi_transform, as dzi_windows_kernel has it
+    const double a = __ddiv_rn(O, scale), half_O = __ddiv_rn(O, 2.0);
+    const double tx = __dsub_rn(half_O, __dmul_rn(a, cx)), ty = __dsub_rn(half_O, __dmul_rn(a, cy));
+    const double D = __ddiv_rn(1.0, __dmul_rn(a, a));
+    const double m0 = __dmul_rn(a, D), nm0 = -m0;
+    o[0] = m0;
+    o[1] = __dmul_rn(nm0, tx);
+    o[2] = __dmul_rn(nm0, ty);
+}
+
+// hsp_roi_compact_box's predicate: frame pixel p (depth valid) -> its fp32 point, as the back-projection writes it -> inside the box
+template <typename D>
+struct BoxOwn {
+    const D* __restrict__ depth;
+    const double* __restrict__ K;
+    int H, W;
+    double Rc[9];      // Rc[i * 3 + r] = R[r][i]: column i of R
+    double c[3], h[3];   // c_i = (R0i * tx + R1i * ty) + R2i * tz
+    __device__ __forceinline__ bool operator()(int p) const {
+        float o[3];
+        frame_pixel_xyz(depth, H, W, K, p, o);
+        const double px = (double)o[0], py = (double)o[1], pz = (double)o[2];
+        bool in = true;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            const double q = __dsub_rn(__dadd_rn(__dadd_rn(__dmul_rn(Rc[i * 3], px), __dmul_rn(Rc[i * 3 + 1], py)),
+                                                 __dmul_rn(Rc[i * 3 + 2], pz)), c[i]);
+            in = in && fabs(q) <= h[i];                         // (false for a NaN on either side)
+        }
+        return in;
+    }
+};
+
+template <typename D>
+__device__ __forceinline__ BoxOwn<D> box_own(const D* __restrict__ depth, const float* __restrict__ rt,
+                                             const float* __restrict__ size, double pad, const double* __restrict__ camK,
+                                             int camK_rows, int H, int W, int j) {
+    BoxOwn<D> b;
+    b.depth = depth;
+    b.K = camK + (camK_rows > 1 ? (size_t)j * 9 : 0);
+    b.H = H;
+    b.W = W;
+    const PoseF64 P = load_pose(rt + (size_t)j * 16);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+#pragma unroll
+        for (int r = 0; r < 3; ++r) b.Rc[i * 3 + r] = P.R[r * 3 + i];
+        b.c[i] = __dadd_rn(__dadd_rn(__dmul_rn(b.Rc[i * 3], P.t[0]), __dmul_rn(b.Rc[i * 3 + 1], P.t[1])),
+                           __dmul_rn(b.Rc[i * 3 + 2], P.t[2]));
+    }
+    half_extents(size + (size_t)j * 3, pad, b.h);
+    return b;
+}
+
+// the scan of a tracked instance: a flagged one (wstatus != 0, the whole workgroup alike) lists and counts nothing
+template <typename D>
+__device__ __forceinline__ void box_scan16(const D* __restrict__ depth, const float* __restrict__ rt,
+                                           const float* __restrict__ size, double pad, const double* __restrict__ camK,
+                                           int camK_rows, const int32_t* __restrict__ wstatus, const double* __restrict__ xf,
+                                           int H, int W, int O, int (&src)[16], unsigned (&bits)[2]) {
+    const int j = blockIdx.y;
+    if (wstatus != nullptr && wstatus[j] != 0) {
+        bits[0] = 0;
+        bits[1] = 0;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) src[i] = -1;
+        return;
+    }
+    roi_scan16(depth, box_own(depth, rt, size, pad, camK, camK_rows, H, W, j), crop_map(xf, nullptr, j),
+               blockIdx.x * PC_CHUNK + threadIdx.x * 16, O * O, O, H, W, src, bits);
+}
+
+template <typename D>
+__global__ __launch_bounds__(256) void box_count_kernel(const D* __restrict__ depth, const float* __restrict__ rt,
+                                                        const float* __restrict__ size, double pad,
+                                                        const double* __restrict__ camK, int camK_rows,
+                                                        const int32_t* __restrict__ wstatus, const double* __restrict__ xf, int H,
+                                                        int W, int O, int nchunk, int32_t* __restrict__ cnt) {
+    int src[16];
+    unsigned bits[2];
+    box_scan16(depth, rt, size, pad, camK, camK_rows, wstatus, xf, H, W, O, src, bits);
+    chunk_count(bits, nchunk, cnt);
+}
+
+template <typename D>
+__global__ __launch_bounds__(256) void box_write_kernel(const D* __restrict__ depth, const float* __restrict__ rt,
+                                                        const float* __restrict__ size, double pad,
+                                                        const double* __restrict__ camK, int camK_rows,
+                                                        const int32_t* __restrict__ wstatus, const double* __restrict__ xf, int H,
+                                                        int W, int O, int nchunk, const int32_t* __restrict__ cnt,
+                                                        int32_t* __restrict__ out_src, int32_t* __restrict__ count) {
+    __shared__ ChunkLds<2> sh;
+    const int j = blockIdx.y;
+    prefix_sums<2, false>(cnt, nchunk, sh);
+    int src[16];
+    unsigned bits[2];
+    box_scan16(depth, rt, size, pad, camK, camK_rows, wstatus, xf, H, W, O, src, bits);
+    int end;
+    const int off = chunk_rank(bits[0], sh, end);
+    store_ids(out_src + (size_t)j * O * O, off, bits[0], src);
+    if (blockIdx.x == nchunk - 1 && threadIdx.x == 255) {
+        count[j * 2 + 0] = end;
+        count[j * 2 + 1] = sh.sum(1);
+    }
+}
+
+// one lane per word of the state: 16 of the pose, 3 of the size, the lost counter; the words are moved, never computed on
+__global__ __launch_bounds__(256) void track_update_kernel(const uint32_t* __restrict__ rt_new, const uint32_t* __restrict__ size_new,
+                                                           const int32_t* __restrict__ status, int n, uint32_t* __restrict__ rt_state,
+                                                           uint32_t* __restrict__ size_state, int32_t* __restrict__ lost) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= n * 20) return;
+    const int j = e / 20, w = e - j * 20;
+    const bool good = status[j] == 0;
+    if (w == 19) {
+        lost[j] = good ? 0 : lost[j] + 1;
+    } else if (good) {
+        if (w < 16) rt_state[j * 16 + w] = rt_new[j * 16 + w];
+        else size_state[j * 3 + (w - 16)] = size_new[j * 3 + (w - 16)];
+    }
 }
 
 // ---- the rows each instance keeps, drawn on the device (include/hsp.h: hsp_sample_ids states the construction) ------------
@@ -912,6 +1123,57 @@ extern "C" int hsp_roi_compact_u16(const uint16_t* depth, const uint8_t* mask, l
                                    const double* xf, int n, int H, int W, int O, int32_t* src, int32_t* count, void* ws,
                                    size_t ws_bytes, hspStream_t stream) {
     return roi_compact(depth, mask, mask_stride, inst_id, xf, n, H, W, O, src, count, ws, ws_bytes, stream);
+}
+
+// what the tracked entry points refuse alike: the pose, the size, K and its row count, a finite pad > 0
+static bool track_args_ok(const float* rt, const float* size, const double* camK, int camK_rows, int n, double pad) {
+    return rt && size && camK && n > 0 && (camK_rows == 1 || camK_rows == n) && pad > 0.0 && pad < INFINITY;
+}
+
+extern "C" int hsp_pose_windows(const float* rt, const float* size, const double* camK, int camK_rows, int n, int H, int W,
+                                int O, double pad, int32_t* boxes, double* xf, int32_t* wstatus, hspStream_t stream) {
+    if (!track_args_ok(rt, size, camK, camK_rows, n, pad) || !boxes || !xf || !wstatus) return HSP_ERR_BAD_ARG;
+    if (n > 65535 || H <= 0 || W <= 0 || (long long)H * W > 2147483647LL || O <= 0 || O > 46340) return HSP_ERR_BAD_ARG;
+    hipLaunchKernelGGL(pose_windows_kernel, dim3((n + 63) / 64), dim3(64), 0, as_stream(stream), rt, size, camK, camK_rows, n,
+                       (double)(W - 1), (double)(H - 1), (double)O, pad, boxes, xf, wstatus);
+    return check_launch();
+}
+
+template <typename D>
+static int roi_compact_box(const D* depth, const float* rt, const float* size, double pad, const double* camK, int camK_rows,
+                           const int32_t* wstatus, const double* xf, int n, int H, int W, int O, int32_t* src, int32_t* count,
+                           void* ws, size_t ws_bytes, hspStream_t stream) {
+    if (!depth || !xf || !src || !count || n <= 0 || H <= 0 || W <= 0 || O <= 0) return HSP_ERR_BAD_ARG;
+    if ((long long)H * W > 2147483647LL || !track_args_ok(rt, size, camK, camK_rows, n, pad)) return HSP_ERR_BAD_ARG;
+    if (O > 46340 || n > 65535) return HSP_ERR_UNSUPPORTED;
+    if (!ws || ws_bytes < hsp_roi_compact_workspace_bytes(n, O)) return HSP_ERR_WORKSPACE;
+    return compact_launch(box_count_kernel<D>, box_write_kernel<D>, n, O * O, ws, stream,
+                          std::make_tuple(depth, rt, size, pad, camK, camK_rows, wstatus, xf, H, W, O), src, count);
+}
+
+extern "C" int hsp_roi_compact_box_f32(const float* depth, const float* rt, const float* size, double pad, const double* camK,
+                                       int camK_rows, const int32_t* wstatus, const double* xf, int n, int H, int W, int O,
+                                       int32_t* src, int32_t* count, void* ws, size_t ws_bytes, hspStream_t stream) {
+    return roi_compact_box(depth, rt, size, pad, camK, camK_rows, wstatus, xf, n, H, W, O, src, count, ws, ws_bytes, stream);
+}
+
+extern "C" int hsp_roi_compact_box_u16(const uint16_t* depth, const float* rt, const float* size, double pad,
+                                       const double* camK, int camK_rows, const int32_t* wstatus, const double* xf, int n, int H,
+                                       int W, int O, int32_t* src, int32_t* count, void* ws, size_t ws_bytes, hspStream_t stream) {
+    return roi_compact_box(depth, rt, size, pad, camK, camK_rows, wstatus, xf, n, H, W, O, src, count, ws, ws_bytes, stream);
+}
+
+extern "C" int hsp_track_update(const float* rt_new, const float* size_new, const int32_t* status, int n, float* rt_state,
+                                float* size_state, int32_t* lost, hspStream_t stream) {
+    if (!rt_new || !size_new || !status || !rt_state || !size_state || !lost || n <= 0 || n > 65535) return HSP_ERR_BAD_ARG;
+    const uintptr_t a = reinterpret_cast<uintptr_t>(rt_new), b = reinterpret_cast<uintptr_t>(rt_state);
+    const uintptr_t c = reinterpret_cast<uintptr_t>(size_new), d = reinterpret_cast<uintptr_t>(size_state);
+    if ((a < b + (uintptr_t)n * 64 && b < a + (uintptr_t)n * 64) || (c < d + (uintptr_t)n * 12 && d < c + (uintptr_t)n * 12))
+        return HSP_ERR_BAD_ARG;                                  // new and state overlap
+    hipLaunchKernelGGL(track_update_kernel, dim3((n * 20 + 255) / 256), dim3(256), 0, as_stream(stream),
+                       reinterpret_cast<const uint32_t*>(rt_new), reinterpret_cast<const uint32_t*>(size_new), status, n,
+                       reinterpret_cast<uint32_t*>(rt_state), reinterpret_cast<uint32_t*>(size_state), lost);
+    return check_launch();
 }
 
 // hsp_frame_to_pcl's refusals and the launch: one frame for all instances with depth_stride 0, and no bound on n beyond

@@ -588,14 +588,18 @@ class GraphedInference:
     frame front end).  It reads static buffers of its owner's; ``PC`` then only gives the shape and ``load(PC=...)`` has no
     effect.
 
+    ``epilogue``: a callable issued at the tail of the captured body, given this object once ``pred_RT`` / ``pred_s`` are
+    made -- the step behind the poses captured with them (frame.FrameTracker: the tracked state takes the new poses).  The
+    warm-up runs it too: an owner whose epilogue writes state puts that state back after the construction.
+
     ``draws``: as ``GraphedTrainStep``'s -- under a device sampler the body begins with the keyed draw of the Pool_layers' rows,
     ``run()`` is the replay alone, and the owner calls ``draws.advance()`` before it."""
 
-    def __init__(self, network, PC, obj_id, mean_shape, sym, warmup=2, prologue=None, draws=None):
+    def __init__(self, network, PC, obj_id, mean_shape, sym, warmup=2, prologue=None, draws=None, epilogue=None):
         from .geom_utils import generate_RT
         self.net, self._generate_RT = network, generate_RT
         self.PC, self.obj_id, self.mean_shape, self.sym = PC, obj_id, mean_shape, sym
-        self._prologue = prologue
+        self._prologue, self._epilogue = prologue, epilogue
         n, N, _ = PC.shape
         self.n_points = N
         dev = PC.device
@@ -624,6 +628,8 @@ class GraphedInference:
                                          out['Pred_T'], mode='vec', sym=self.sym)
         self.pred_s = out['Pred_s'] + self.mean_shape
         self.output_dict = out
+        if self._epilogue is not None:
+            self._epilogue(self)
 
     def load(self, PC=None, obj_id=None, mean_shape=None, sym=None):
         _copy_in(((self.PC, PC), (self.obj_id, obj_id), (self.mean_shape, mean_shape), (self.sym, sym)))

@@ -2890,10 +2890,11 @@ def _req_depth(depth, name, n=None):
     return depth.detach() if depth.is_contiguous() else depth.detach().contiguous()
 
 
-def _compact(name, depth, each, xf, out_size, head, n_out):
-    """what ``roi_compact`` and ``crop_compact`` share: xf (n,3) float64, out_size and n in range, depth a single frame or
-    (``each``) also a frame per instance; ``head(depth, n, H, W, O)`` checks the form's own arguments and returns them as the
-    entry point lists them between depth and xf; src (n, O*O), count (n,2) and for n_out 3 a third (n,) output, all int32."""
+def _compact(name, depth, each, xf, out_size, head, n_out, ws_of=None):
+    """what ``roi_compact``, ``roi_compact_box`` and ``crop_compact`` share: xf (n,3) float64, out_size and n in range, depth a
+    single frame or (``each``) also a frame per instance; ``head(depth, n, H, W, O)`` checks the form's own arguments and
+    returns them as the entry point lists them between depth and xf (tensors, None, or numbers passed by value); src (n, O*O),
+    count (n,2) and for n_out 3 a third (n,) output, all int32.  ``ws_of``: the form whose workspace query serves this one."""
     xf = _req(xf, torch.float64, f"{name}.xf")
     if xf.dim() != 2 or xf.shape[1] != 3 or xf.shape[0] == 0:
         raise HspError(f"{name}: expects xf (n,3) float64 with n >= 1")
@@ -2904,10 +2905,10 @@ def _compact(name, depth, each, xf, out_size, head, n_out):
         raise HspError(f"{name}: out_size {O} / n {n} out of range (0 < out_size <= 46340, n <= 65535)")
     head = head(depth, n, H, W, O)
     outs = [torch.empty(shape, dtype=torch.int32, device=depth.device) for shape in ((n, O * O), (n, 2), (n,))[:n_out]]
-    wsb = getattr(lib(), f"hsp_{name}_workspace_bytes")(n, O)
+    wsb = getattr(lib(), f"hsp_{ws_of or name}_workspace_bytes")(n, O)
     ws = _ws(wsb, depth.device)
     _run(f"hsp_{name}" + _FRAME_DEPTH[depth.dtype],
-         (_p(depth), *(a if isinstance(a, int) else _p(a) for a in head), _p(xf), n, H, W, O, *map(_p, outs), _p(ws), wsb,
+         (_p(depth), *(a if isinstance(a, (int, float)) else _p(a) for a in head), _p(xf), n, H, W, O, *map(_p, outs), _p(ws), wsb,
           _stream()),
          key=f"n{n}O{O}", abytes=n * O * O * (depth.element_size() + 1 + 4))
     return tuple(outs)
@@ -2928,6 +2929,74 @@ def roi_compact(depth, mask, xf, out_size, inst_ids=None):
             raise HspError(f"roi_compact: expects inst_ids ({n},), got {tuple(ids.shape)}")
         return m, H * W if m.dim() == 3 else 0, ids
     return _compact("roi_compact", depth, False, xf, out_size, head, 2)
+
+
+def _req_track(name, RT, size, camK64, pad):
+    """the pose, size, K and pad the tracked entry points share (include/hsp.h: instances followed from frame to frame):
+    RT (n,4,4) or (n,16) and size (n,3) fp32, camK (1|n,3,3) float64, all on the device; pad finite and > 0
+    -> (RT, size, camK64, pad, n)"""
+    RT = _req(RT.detach() if isinstance(RT, torch.Tensor) else RT, torch.float32, f"{name}.RT")
+    size = _req(size.detach() if isinstance(size, torch.Tensor) else size, torch.float32, f"{name}.size")
+    camK64 = _req(camK64.detach() if isinstance(camK64, torch.Tensor) else camK64, torch.float64, f"{name}.camK")
+    n, pad = size.shape[0] if size.dim() == 2 else 0, float(pad)
+    if not 1 <= n <= 65535 or tuple(size.shape) != (n, 3) or tuple(RT.shape) not in ((n, 4, 4), (n, 16)) \
+            or camK64.numel() not in (9, 9 * n):
+        raise HspError(f"{name}: expects RT (n,4,4) and size (n,3) fp32 with 1 <= n <= 65535 and camK (1|n,3,3) f64, got "
+                       f"{tuple(RT.shape)}, {tuple(size.shape)}, {tuple(camK64.shape)}")
+    if not 0.0 < pad < float("inf"):
+        raise HspError(f"{name}: pad {pad} out of range (finite and > 0)")
+    return RT, size, camK64, pad, n
+
+
+def pose_windows(RT, size, camK64, H, W, out_size, pad):
+    """the crop windows of tracked instances from their last poses (include/hsp.h: hsp_pose_windows): RT (n,4,4) and size
+    (n,3) fp32, camK (1|n,3,3) float64 -> (boxes (n,4) int32 = (x1, y1, x2, y2), xf (n,3) float64 = the transform rows
+    ``roi_compact_box`` reads, wstatus (n,) int32: 4 where the pose gives no window, its boxes and xf rows are zeros)."""
+    RT, size, camK64, pad, n = _req_track("pose_windows", RT, size, camK64, pad)
+    H, W, O = int(H), int(W), int(out_size)
+    if H < 1 or W < 1 or H * W >= 2 ** 31 or not 0 < O <= 46340:
+        raise HspError(f"pose_windows: frame {H}x{W} / out_size {O} out of range (H, W >= 1, H*W < 2^31, 0 < out_size <= 46340)")
+    dev = RT.device
+    boxes = torch.empty(n, 4, dtype=torch.int32, device=dev)
+    xf = torch.empty(n, 3, dtype=torch.float64, device=dev)
+    wstatus = torch.empty(n, dtype=torch.int32, device=dev)
+    _run("hsp_pose_windows", (_p(RT), _p(size), _p(camK64), camK64.numel() // 9, n, H, W, O, pad, _p(boxes), _p(xf), _p(wstatus),
+                              _stream()), key=f"n{n}", abytes=n * (64 + 12 + 72 + 16 + 24 + 4))
+    return boxes, xf, wstatus
+
+
+def roi_compact_box(depth, RT, size, pad, camK64, xf, out_size, wstatus=None):
+    """``roi_compact`` with the mask replaced by "the pixel's point lies inside the padded oriented box of the pose"
+    (include/hsp.h: hsp_roi_compact_box_*): depth (H,W) fp32 or uint16, RT (n,4,4) and size (n,3) fp32, camK (1|n,3,3) float64,
+    xf (n,3) float64 and wstatus (n,) int32 or None from ``pose_windows`` -> (src (n, O*O) int32, count (n,2) int32) as
+    ``roi_compact`` returns them; an instance whose wstatus is not 0 counts (0, 0)."""
+    RT, size, camK64, pad, n = _req_track("roi_compact_box", RT, size, camK64, pad)
+
+    def head(depth, n_xf, H, W, O):
+        ws_ = None if wstatus is None else _req(wstatus, torch.int32, "roi_compact_box.wstatus")
+        if n_xf != n or (ws_ is not None and ws_.shape != (n,)):
+            raise HspError(f"roi_compact_box: expects xf ({n},3) and wstatus ({n},) or None, got xf ({n_xf},3)"
+                           + ("" if ws_ is None else f", wstatus {tuple(ws_.shape)}"))
+        return RT, size, pad, camK64, camK64.numel() // 9, ws_
+    return _compact("roi_compact_box", depth, False, xf, out_size, head, 2, ws_of="roi_compact")
+
+
+def track_update(RT_new, size_new, status, RT_state, size_state, lost):
+    """the tracked state after a frame, in place (include/hsp.h: hsp_track_update): where status is 0 ``RT_state`` (n,4,4) /
+    ``size_state`` (n,3) take ``RT_new`` / ``size_new`` and ``lost`` (n,) int32 becomes 0; elsewhere they stay and lost += 1."""
+    RT_new = _req(RT_new.detach(), torch.float32, "track_update.RT_new")
+    size_new = _req(size_new.detach(), torch.float32, "track_update.size_new")
+    status = _req(status, torch.int32, "track_update.status")
+    n = status.shape[0] if status.dim() == 1 else 0
+    if not 1 <= n <= 65535 or RT_new.numel() != n * 16 or tuple(size_new.shape) != (n, 3):
+        raise HspError(f"track_update: expects RT_new (n,4,4), size_new (n,3), status (n,) with 1 <= n <= 65535, got "
+                       f"{tuple(RT_new.shape)}, {tuple(size_new.shape)}, {tuple(status.shape)}")
+    for t, dtype, numel, name in ((RT_state, torch.float32, n * 16, "RT_state"), (size_state, torch.float32, n * 3, "size_state"),
+                                  (lost, torch.int32, n, "lost")):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype and t.numel() == numel and t.is_contiguous()):
+            raise HspError(f"track_update: expects {name} with {numel} {dtype} entries, contiguous, on the device")
+    _run("hsp_track_update", (_p(RT_new), _p(size_new), _p(status), n, _p(RT_state), _p(size_state), _p(lost), _stream()),
+         key=f"n{n}", abytes=n * (2 * 76 + 12))
 
 
 def _to_pcl(name, depth, each, camK64, src, choose):

@@ -390,6 +390,54 @@ def choose_rows(sampler, key, depth, K64, src, count, n_pts, min_pts):
     return ops.sample_ids(count, n_pts, key, min_pts, 2, 0)
 
 
+def track_pad(pad):
+    """``pad=`` of the tracked front end -> the factor on the tracked size: None follows ``FLAGS.DZI_PAD_SCALE`` (1.5, the
+    padding the training crops are cut with)"""
+    pad = float(FLAGS.DZI_PAD_SCALE if pad is None else pad)
+    if not 0.0 < pad < float("inf"):
+        raise ValueError(f"track pad: expects a finite factor > 0, got {pad!r}")
+    return pad
+
+
+def track_chain(depth, RT, size, K64, n_pts, O, min_pts, pad, sampler, key):
+    """the four launches of the tracked front end on device tensors alone (nothing uploaded, the sampler not advanced: ``key``
+    is its key as the caller advanced it) -> (PC, status); what ``track_to_pcl_device`` issues and ``frame.FrameTracker``
+    captures"""
+    H, W = depth.shape
+    _, xf, wstatus = ops.pose_windows(RT, size, K64, H, W, O, pad)
+    src, count = ops.roi_compact_box(depth, RT, size, pad, K64, xf, O, wstatus)
+    choose, status = choose_rows(sampler, key, depth, K64, src, count, n_pts, min_pts)
+    return ops.frame_to_pcl(depth, K64, src, choose), status | wstatus
+
+
+def track_to_pcl_device(depth, RT, size, K, n_pts=None, out_size=None, min_pts=50, pad=None, sampler=None):
+    """``frame_to_pcl_device`` without masks and boxes: the crop of instance j is decided by its last pose.  depth (H,W) fp32
+    or uint16 mm, RT (n,4,4) fp32 rigid poses in metres and size (n,3) fp32 metres on the device (what the previous frame's
+    ``generate_RT`` and ``Pred_s + mean_shape`` left there), K (3,3) or (n,3,3) -> (PC (n, n_pts, 3) fp32 metres, status (n,)
+    int32), both on the device.  The window is the projection of the oriented box of half extents 0.5 * pad * size about the
+    pose, the mask is that box in metres (include/hsp.h: instances followed from frame to frame).  status: ``hsp_sample_ids``'s
+    bits 1 and 2 under ``min_pts`` (50: the training loader's rule, load_data.py:276), plus 4: the pose gives no window (behind
+    the camera, off the frame, not finite, a size <= 0); the rows of an instance whose status is not 0 are NaN.  ``pad``: None
+    follows ``FLAGS.DZI_PAD_SCALE``.  ``sampler``: a DeviceSampler (None or 'device': the module's) or 'fps'.  Four launches --
+    windows, compaction, rows, clouds --, all queued: nothing is copied back and nothing waits.  Inside a graph capture K must be
+    a float64 device tensor and the sampler is not advanced (``sampler.advance()`` before each replay)."""
+    n_pts = int(FLAGS.random_points if n_pts is None else n_pts)
+    O = int(FLAGS.img_size if out_size is None else out_size)
+    dev = depth.device
+    sampler = resolve_sampler("device" if sampler is None else sampler, dev)
+    if sampler is None:
+        raise ValueError("track_to_pcl_device: expects a device sampler; the host draws wait for the counts")
+    capturing = dev.type == "cuda" and torch.cuda.is_current_stream_capturing()
+    if isinstance(K, torch.Tensor) and K.is_cuda:
+        K64 = K.to(torch.float64).reshape(-1, 9).contiguous()
+    elif capturing:
+        raise ValueError("track_to_pcl_device: inside a graph capture K must already be on the device")
+    else:
+        K64 = _upload((K.detach().numpy() if isinstance(K, torch.Tensor) else np.asarray(K)).reshape(-1, 9), np.float64, dev)
+    key = sampler.key if capturing else sampler.advance()
+    return track_chain(depth, RT, size, K64, n_pts, O, min_pts, track_pad(pad), sampler, key)
+
+
 def frame_to_pcl(depth, masks, centers, scales, K, n_pts=None, out_size=None, inst_ids=None, min_pts=2, sampler=None):
     """The evaluation loader's crops and clouds for all detections of one frame (load_data_eval.py:230-254; with ``inst_ids``
     and ``min_pts=50`` the training loader's, datasets/load_data.py:234-278 without ``defor_2D``).

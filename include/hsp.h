@@ -874,6 +874,63 @@ int hsp_fps_ids_u16(const uint16_t *depth, int H, int W, const double *camK, int
                     long long src_stride, const int32_t *count, int n, int S, int min_pts, int min_depth_pts, int32_t *choose,
                     int32_t *status, hspStream_t stream);
 
+/* ---- instances followed from frame to frame: the crop decided by the last pose, no mask ---------------------
+ * The opt-in front end of a video stream: where hsp_roi_compact_* cuts instance j out of the frame by a detector's mask and a
+ * window the host made of the detector's box, these cut it by the pose and size the previous frame's replay left on the
+ * device.  The oriented box of half extents h = (0.5 * pad) * size about the pose, projected with K, gives the window; the
+ * same box in metres is the mask.  Nothing is read back: windows, flags and the tracked state live on the device.
+ *
+ * Arithmetic, all three entry points: float64, every operation named below is ONE rounding, in the order written (the
+ * kernels spell them __dmul_rn / __dadd_rn / __dsub_rn / __ddiv_rn, so no contraction moves a bit); a float32 input enters
+ * by its exact conversion.  RT (n,16) fp32 row-major is a rigid pose in metres, what hsp_generate_rt writes: R = RT[0..2][0..2],
+ * t = (RT[3], RT[7], RT[11]); the fourth row is not read.  size (n,3) fp32 metres.  camK (camK_rows, 9) DOUBLE with camK_rows
+ * 1 (one camera for all) or n; K0, K2, K4, K5 are read.  pad finite and > 0.
+ *
+ * hsp_pose_windows: one launch, one lane per instance.  boxes (n,4) int32 = (x1, y1, x2, y2), xf (n,3) DOUBLE (the transform
+ * rows hsp_roi_compact_* reads), wstatus (n) int32.  Per instance:
+ *   half extents  h_i = (0.5 * pad) * double(size_i), i = 0, 1, 2
+ *   corner k      k = 0..7, e_i = +h_i where bit i of k is set, -h_i where it is clear
+ *                 X = ((R00 * e0 + R01 * e1) + R02 * e2) + t_x, Y and Z likewise with R's second and third row
+ *                 u = (K0 * X) / Z + K2,   v = (K4 * Y) / Z + K5
+ *   box           x1 = max(0, floor(min u)), y1 = max(0, floor(min v)), x2 = min(W - 1, ceil(max u)), y2 = min(H - 1, ceil(max v))
+ *                 over the eight corners, clamped in float64 before the conversion to integer
+ *   wstatus       4 ("no window") when any of R, t, size, K0, K2, K4, K5 or any u, v is not finite, any h_i <= 0, any corner
+ *                 has Z <= 0, or x2 <= x1 or y2 <= y1 (a box off the frame ends here); boxes and xf of the instance are then
+ *                 zeros.  0 otherwise.
+ *   window        centre (cx, cy) = ((x1 + x2) / 2, (y1 + y2) / 2), scale s = max(x2 - x1, y2 - y1): the evaluation loader's rule
+ *                 (evaluation/load_data_eval.py:221-228) without get_bbox's snapping to multiples of 40
+ *   xf            a = O / s, tx = O / 2 - a * cx, ty = O / 2 - a * cy, D = 1 / (a * a), m0 = a * D, xf = (m0, -m0 * tx, -m0 * ty):
+ *                 pc_sample.roi_transform's order, as hsp_dzi_windows has it on the device
+ * n <= 65535, H, W >= 1, H * W < 2^31, 0 < O <= 46340.
+ *
+ * hsp_roi_compact_box_*: hsp_roi_compact_* with a geometric mask -- the same crop map, the same src (n, O*O) order, the same
+ * count (n,2) = [inside-and-depth valid, depth valid], the same workspace (hsp_roi_compact_workspace_bytes), the same limits.
+ * A crop pixel that maps to frame pixel p with depth > 0 is depth valid; it is inside iff, with (px, py, pz) the three fp32
+ * values hsp_frame_to_pcl_* writes for p (one device function serves both: these are the values the network will see),
+ *   q_i = ((R0i * px + R1i * py) + R2i * pz) - ((R0i * tx + R1i * ty) + R2i * tz)          (every product of two fp32 is exact)
+ *   |q_i| <= h_i for i = 0, 1, 2, h as above; a NaN is never inside.
+ * xf and wstatus are hsp_pose_windows's; wstatus may be NULL (no instance is flagged).  An instance with wstatus != 0 lists
+ * nothing and counts (0, 0).
+ *
+ * hsp_track_update: the state a stream carries from one replay to the next, one launch.  Where status[j] == 0 the state takes
+ * the new pose and size (words copied, not computed on) and lost[j] = 0; elsewhere the state stays as it is and lost[j] += 1.
+ * rt_new (n,16) / size_new (n,3) / rt_state / size_state fp32, status / lost (n) int32; new and state must not overlap.
+ *
+ * Status bits of the chain: 1 and 2 are hsp_sample_ids's (hsp_fps_ids_*'s), 4 is wstatus's; the caller ORs them.
+ * A NULL pointer (wstatus of hsp_roi_compact_box_* apart), a size out of range or a bad pad is HSP_ERR_BAD_ARG before any
+ * launch; O > 46340 or n > 65535 in hsp_roi_compact_box_* is HSP_ERR_UNSUPPORTED and a short workspace HSP_ERR_WORKSPACE, as
+ * in hsp_roi_compact_*. */
+int hsp_pose_windows(const float *rt, const float *size, const double *camK, int camK_rows, int n, int H, int W, int O,
+                     double pad, int32_t *boxes, double *xf, int32_t *wstatus, hspStream_t stream);
+int hsp_roi_compact_box_f32(const float *depth, const float *rt, const float *size, double pad, const double *camK,
+                            int camK_rows, const int32_t *wstatus, const double *xf, int n, int H, int W, int O, int32_t *src,
+                            int32_t *count, void *ws, size_t ws_bytes, hspStream_t stream);
+int hsp_roi_compact_box_u16(const uint16_t *depth, const float *rt, const float *size, double pad, const double *camK,
+                            int camK_rows, const int32_t *wstatus, const double *xf, int n, int H, int W, int O, int32_t *src,
+                            int32_t *count, void *ws, size_t ws_bytes, hspStream_t stream);
+int hsp_track_update(const float *rt_new, const float *size_new, const int32_t *status, int n, float *rt_state,
+                     float *size_state, int32_t *lost, hspStream_t stream);
+
 /* ---- the training loader's front end: a batch of frames, the mask perturbed before the cloud is cut -------
  * replaces datasets/load_data.py:234-278 behind aug_bbox_DZI: the three nearest-neighbour crops, defor_2D
  * (datasets/data_augmentation.py:9-32) on the cropped mask, the three rejection tests (:254, :257, :276), _depth_to_pcl and the
