@@ -318,6 +318,13 @@ __device__ static double pairwise_sum(const double* a, int n) {
     }
 }
 
+// np.sum of a contiguous a[0 .. n): it hands its add loop at most 8192 elements at a time and adds the pieces up in order
+__device__ static double numpy_sum(const double* a, int n) {
+    double acc = 0.0;
+    for (int k = 0; k < n; k += 8192) acc += pairwise_sum(a + k, min(8192, n - k));
+    return acc;
+}
+
 // one workgroup per (threshold, class): compute_ap_from_matches_scores over the class's slots in score order
 __global__ __launch_bounds__(EVAL_AP_THREADS) void eval_ap_kernel(const int8_t* __restrict__ match, int T, const int32_t* __restrict__ order,
                                                                   const int32_t* __restrict__ seg_off, const int32_t* __restrict__ gt_cnt,
@@ -368,20 +375,17 @@ __global__ __launch_bounds__(EVAL_AP_THREADS) void eval_ap_kernel(const int8_t* 
     }
     if (tid == 0 && total != G) terms[total] = (1.0 - (double)__fdiv_rn((float)total, (float)G)) * 0.0;   // the step up to the sentinel 1
     __syncthreads();
-    if (tid == 0) {                  // np.sum hands its add loop at most 8192 elements at a time and adds the pieces up in order
-        const int nterms = total + (total != G);
-        double acc = 0.0;
-        for (int k = 0; k < nterms; k += 8192) acc += pairwise_sum(terms + k, min(8192, nterms - k));
-        *out = acc;
-    }
+    if (tid == 0) *out = numpy_sum(terms, total + (total != G));
 }
 
-// row 0 (BG) = 0, the last row = the mean of the class rows in row order (np.mean of fewer than 8 values: a running sum / count)
+// row 0 (BG) = 0, the last row = np.mean(aps[1:-1], axis=0): with more than one column numpy adds row after row, a running sum per
+// column; a single column is one contiguous run, which it adds as np.sum does (from 8 classes on that is not the running sum)
 __global__ void eval_ap_mean_kernel(double* __restrict__ aps, int T, int C) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= T) return;
     double s = 0.0;
-    for (int c = 1; c <= C; ++c) s += aps[(size_t)c * T + t];
+    if (T == 1) s = numpy_sum(aps + 1, C);
+    else for (int c = 1; c <= C; ++c) s += aps[(size_t)c * T + t];
     aps[t] = 0.0;
     aps[(size_t)(C + 1) * T + t] = s / (double)C;
 }

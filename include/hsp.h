@@ -1546,7 +1546,8 @@ int hsp_axis_conf_bwd(const float *h, const float *g_axis, const float *g_conf, 
  *   (np.sum's: eight interleaved partial sums per block of up to 128 terms, blocks joined by halves, pieces of 8192 terms added
  *   up in order), so the result is the
  *   reference's bit for bit.  No predictions: 0.  Predictions but G == 0: NaN (numpy's 0 / 0).  aps (C + 2, T) fp64: row 0 (BG)
- *   = 0, row c + 1 = class c, the last row = the mean of the class rows in row order (a NaN class makes it NaN).  That is
+ *   = 0, row c + 1 = class c, the last row = np.mean(aps[1:-1], axis=0) (a NaN class makes it NaN): for T > 1 the class rows added
+ *   in row order, for T == 1 -- one contiguous run -- in np.sum's order above.  The row order is
  *   np.mean's order for fewer than 8 classes; from 8 classes on the reference's pose mean, taken over a strided 1-D slice, adds
  *   pairwise and may differ from this row in the last bit (its IoU mean, taken along axis 0, never does).
  *   ws: hsp_eval_ap_workspace_bytes(slots, T, C) = 8 T (slots + C), the terms of every (class, threshold).

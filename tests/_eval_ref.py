@@ -119,9 +119,48 @@ def match_group(scores, iou, deg, shift, iou_thr, deg_thr, shift_thr, pose_index
     return dict(order=np.array(order, np.int8), iou_pred=ipm, iou_gt=igm, pose_pred=ppm, pose_gt=pgm, kp=kp, kg=kg)
 
 
-def average_precision(hit, n_gt):
+def _sum_block(a):
+    """at most 128 terms: below 8 in index order; otherwise eight interleaved partial sums, folded, then the tail in index order"""
+    n = len(a)
+    if n < 8:
+        res = np.float64(0.0)
+        for v in a:
+            res = res + v
+        return res
+    r = [a[j] for j in range(8)]
+    full = n - n % 8
+    for i in range(8, full, 8):
+        for j in range(8):
+            r[j] = r[j] + a[i + j]
+    res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]))
+    for i in range(full, n):
+        res = res + a[i]
+    return res
+
+
+def _sum_halves(a):
+    """above 128 terms: halves, the left one a multiple of 8 long"""
+    n = len(a)
+    if n <= 128:
+        return _sum_block(a)
+    n2 = n // 2
+    n2 -= n2 % 8
+    return _sum_halves(a[:n2]) + _sum_halves(a[n2:])
+
+
+def contract_sum(terms):
+    """The sum of a 1-D fp64 array in the order include/hsp.h promises for hsp_eval_ap (np.sum's, restated in scalar additions so
+    that it does not depend on the numpy that runs it): pieces of at most 8192 elements, each summed pairwise, added up in order."""
+    a = np.ascontiguousarray(terms, np.float64).reshape(-1)
+    acc = np.float64(0.0)
+    for k in range(0, len(a), 8192):
+        acc = acc + _sum_halves(a[k:k + 8192])
+    return acc
+
+
+def average_precision(hit, n_gt, summer=np.sum):
     """hit (R, n) bool: per row (one threshold each), whether each prediction is matched, predictions in descending score order.
-    -> (R,) average precisions"""
+    ``summer``: what adds a row's terms up (np.sum, or contract_sum for the stated order).  -> (R,) average precisions"""
     R, n = hit.shape
     cnt = np.cumsum(hit, axis=1)
     with np.errstate(invalid="ignore", divide="ignore"):
@@ -133,7 +172,7 @@ def average_precision(hit, n_gt):
     env = np.maximum.accumulate(prec[:, ::-1], axis=1)[:, ::-1]       # the largest precision from here on
     moved = rec[:, :-1] != rec[:, 1:]
     terms = (rec[:, 1:] - rec[:, :-1]) * env[:, 1:]
-    return np.array([np.sum(terms[r][moved[r]]) for r in range(R)])
+    return np.array([summer(terms[r][moved[r]]) for r in range(R)])
 
 
 def evaluate(results, synset_names, degree_thresholds, shift_thresholds, iou_3d_thresholds, iou_pose_thres=0.1,

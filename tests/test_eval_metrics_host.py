@@ -70,6 +70,26 @@ def test_fixture_holds_its_cases_and_margins(golden):
     assert list(only["order"][po[g]:po[g] + 3]) in ([1, 2, 0], [2, 0, 1])
 
 
+@pytest.mark.parametrize("n", [0, 1, 7, 8, 9, 127, 128, 129, 255, 256, 257, 1000, 8191, 8192, 8193, 8200, 16384, 16385, 20000])
+def test_contract_sum_is_this_numpys_sum(n):
+    """The GPU tests hold hsp_eval_ap to _eval_ref.contract_sum, the header's order in scalar additions; the golden arrays come from
+    np.sum.  The two must be the same bits on the numpy that runs the suite: one that adds differently fails here, not on the GPU.
+    Positive terms of mixed magnitude, so that nearly every order of additions rounds differently.  Likewise the mean row of a
+    one-column table (hsp_eval_ap's T == 1) against np.mean along axis 0, which is a contiguous run from 8 classes on."""
+    rng = np.random.default_rng(1000 + n)
+    for _ in range(3):
+        a = rng.uniform(size=n) * rng.uniform(size=n)
+        got, want = _eval_ref.contract_sum(a), np.sum(a)
+        assert got == want, f"n = {n}: contract_sum {float(got)!r}, np.sum {float(want)!r}"
+        if n:
+            table = np.zeros((n + 2, 1))
+            table[1:-1, 0] = a
+            assert got / n == np.mean(table[1:-1], axis=0)[0], n
+    hit = rng.uniform(size=(3, n)) < 0.5
+    G = int(hit.sum(axis=1).max()) + 3
+    assert np.array_equal(_eval_ref.average_precision(hit, G, summer=_eval_ref.contract_sum), _eval_ref.average_precision(hit, G))
+
+
 def test_pack_results_round_trip(golden):
     from hs_pose_amd.evaluation import pack_results, unpack_results
     results = golden[0]
