@@ -2999,6 +2999,84 @@ def track_update(RT_new, size_new, status, RT_state, size_state, lost):
          key=f"n{n}", abytes=n * (2 * 76 + 12))
 
 
+def _req_instances(name, frame_id, label, n=None):
+    """frame_id and label (n,) int32 on the device, n <= 65535 -> (frame_id, label, n)"""
+    frame_id = _req(frame_id, torch.int32, f"{name}.frame_id")
+    label = _req(label, torch.int32, f"{name}.label")
+    n = frame_id.numel() if n is None else n
+    if frame_id.shape != (n,) or label.shape != (n,) or n > 65535:
+        raise HspError(f"{name}: expects frame_id and label ({n},) int32 with n <= 65535, got {tuple(frame_id.shape)}, "
+                       f"{tuple(label.shape)}")
+    return frame_id, label, n
+
+
+def render_depth(verts, tris, mesh, mesh_id, frame_id, label, RT, scale, camK64, F, H, W, over=False, depth=None, labels=None,
+                 dtype=torch.uint16):
+    """depth frames and label images rendered from meshes and poses (include/hsp.h: hsp_render_depth_*): verts (V,3) fp32,
+    tris (T,3) and mesh (n_mesh,4) int32 -- a packed mesh set, ``render.MeshSet`` --, mesh_id / frame_id / label (n,) int32,
+    RT (n,4,4) or (n,16) and scale (n,3) fp32, camK (1|F,3,3) float64, all on the device -> (depth (F,H,W) uint16 or fp32
+    millimetres, labels (F,H,W) uint8).  ``depth`` / ``labels``: caller-owned frames to draw into (they fix the dtype); with
+    ``over`` the instances are composited over what the frames hold, else the frames are cleared first.  n may be 0."""
+    verts = _req(verts, torch.float32, "render_depth.verts")
+    tris = _req(tris, torch.int32, "render_depth.tris")
+    mesh = _req(mesh, torch.int32, "render_depth.mesh")
+    mesh_id = _req(mesh_id, torch.int32, "render_depth.mesh_id")
+    frame_id, label, n = _req_instances("render_depth", frame_id, label, mesh_id.numel())
+    RT = _req(RT.detach(), torch.float32, "render_depth.RT")
+    scale = _req(scale.detach(), torch.float32, "render_depth.scale")
+    camK64 = _req(camK64.detach(), torch.float64, "render_depth.camK")
+    F, H, W = int(F), int(H), int(W)
+    if verts.dim() != 2 or verts.shape[1] != 3 or tris.dim() != 2 or tris.shape[1] != 3 or mesh.dim() != 2 or mesh.shape[1] != 4 \
+            or 0 in (verts.shape[0], tris.shape[0], mesh.shape[0]) or mesh_id.shape != (n,) or RT.numel() != n * 16 \
+            or tuple(scale.shape) != (n, 3):
+        raise HspError(f"render_depth: expects verts (V,3), tris (T,3), mesh (n_mesh,4), mesh_id (n,), RT (n,4,4), scale (n,3), got "
+                       f"{tuple(verts.shape)}, {tuple(tris.shape)}, {tuple(mesh.shape)}, {tuple(mesh_id.shape)}, {tuple(RT.shape)}, "
+                       f"{tuple(scale.shape)}")
+    if F < 1 or H < 1 or W < 1 or H * W >= 2 ** 31 or camK64.numel() not in (9, 9 * F):
+        raise HspError(f"render_depth: frames {F}x{H}x{W} / camK {tuple(camK64.shape)} out of range (F, H, W >= 1, H*W < 2^31, "
+                       "camK (1|F,3,3))")
+    dev = verts.device
+    if depth is None:
+        if dtype not in _FRAME_DEPTH:
+            raise HspError(f"render_depth: dtype expects torch.uint16 or torch.float32, got {dtype}")
+        if over:
+            raise HspError("render_depth: over=True composites over caller-owned frames: pass depth and labels")
+        depth = torch.empty(F, H, W, dtype=dtype, device=dev)
+    if labels is None:
+        if over:
+            raise HspError("render_depth: over=True composites over caller-owned frames: pass depth and labels")
+        labels = torch.empty(F, H, W, dtype=torch.uint8, device=dev)
+    for t, name, ok in ((depth, "depth", depth.dtype in _FRAME_DEPTH if isinstance(depth, torch.Tensor) else False),
+                        (labels, "labels", labels.dtype == torch.uint8 if isinstance(labels, torch.Tensor) else False)):
+        if not ok or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != (F, H, W):
+            raise HspError(f"render_depth: {name} expects a contiguous ({F},{H},{W}) "
+                           f"{'uint16 or float32' if name == 'depth' else 'uint8'} GPU tensor, got "
+                           f"{tuple(t.shape) if isinstance(t, torch.Tensor) else type(t)}")
+    wsb = lib().hsp_render_workspace_bytes(F, H, W, n)
+    ws = _ws(wsb, dev)
+    _run("hsp_render_depth" + _FRAME_DEPTH[depth.dtype],
+         (_p(verts), verts.shape[0], _p(tris), tris.shape[0], _p(mesh), mesh.shape[0], _p(mesh_id), _p(frame_id), _p(label), _p(RT),
+          _p(scale), _p(camK64), camK64.numel() // 9, n, F, H, W, 1 if over else 0, _p(depth), _p(labels), _p(ws), wsb, _stream()),
+         key=f"n{n}F{F}", abytes=F * H * W * (16 + depth.element_size() + 1))
+    return depth, labels
+
+
+def label_boxes(labels_img, frame_id, label):
+    """the tight box and the pixel count of each instance's label (include/hsp.h: hsp_label_boxes): labels_img (F,H,W) uint8,
+    frame_id / label (n,) int32 -> (boxes (n,4) int32 = (x1, y1, x2, y2) with x2, y2 exclusive, count (n,) int32); zeros where
+    the frame holds no pixel of the label."""
+    labels_img = _req(labels_img, torch.uint8, "label_boxes.labels_img")
+    frame_id, label, n = _req_instances("label_boxes", frame_id, label)
+    if labels_img.dim() != 3 or labels_img.numel() == 0 or labels_img.shape[1] * labels_img.shape[2] >= 2 ** 31 or n < 1:
+        raise HspError(f"label_boxes: expects labels_img (F,H,W) uint8 with H*W < 2^31 and n >= 1, got {tuple(labels_img.shape)}, n {n}")
+    F, H, W = labels_img.shape
+    boxes = torch.empty(n, 4, dtype=torch.int32, device=labels_img.device)
+    count = torch.empty(n, dtype=torch.int32, device=labels_img.device)
+    _run("hsp_label_boxes", (_p(labels_img), _p(frame_id), _p(label), n, F, H, W, _p(boxes), _p(count), _stream()),
+         key=f"n{n}", abytes=n * (H * W + 28))
+    return boxes, count
+
+
 def _to_pcl(name, depth, each, camK64, src, choose):
     """what ``frame_to_pcl`` and ``frames_to_pcl`` share; ``each``: a frame per instance is allowed and n is bounded"""
     src = _req(src, torch.int32, f"{name}.src")

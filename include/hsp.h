@@ -1567,6 +1567,70 @@ size_t hsp_eval_ap_workspace_bytes(int slots, int T, int C);
 int hsp_eval_ap(const int8_t *match, int slots, int T, const int32_t *order, const int32_t *seg_off, const int32_t *gt_count,
                 int C, double *aps, void *ws, size_t ws_bytes, hspStream_t stream);
 
+/* ---- depth frames rendered from meshes and poses ------------------------------------------------------------
+ * A z-buffered triangle rasteriser: n instances of triangle meshes, each under its own pose and per-axis scale, drawn into F
+ * frames in the formats the front ends above read -- depth in millimetres (uint16, or fp32) and a uint8 label image.  The
+ * reference has no counterpart: its synthetic frames are rendered off line and read from files.  Nothing is uploaded and
+ * nothing is read back; every call can be captured.
+ *
+ * Data.  verts (V,3) fp32 in model units; tris (T,3) int32, indices relative to the first vertex of their mesh;
+ * mesh (n_mesh,4) int32 = (first vertex, vertex count, first triangle, triangle count), every row inside verts and tris.
+ * Instance j of n draws mesh mesh_id[j] into frame frame_id[j] in [0, F) under label label[j] in [1, 255]; its pose is rt[j]
+ * (16 fp32 row-major, what hsp_generate_rt writes; the fourth row is not read), its scale[j] 3 fp32, the metres per model
+ * unit along each axis.  camK (camK_rows, 9) DOUBLE with camK_rows 1 (one camera for all) or F (one per frame); K0, K2, K4, K5
+ * are read.  depth (F,H,W), labels (F,H,W).
+ *
+ * Arithmetic: float64, every operation named below is ONE rounding, in the order written (the kernels spell them
+ * __dmul_rn / __dadd_rn / __dsub_rn / __ddiv_rn); a float32 input enters by its exact conversion.
+ *   vertex      m_i = double(scale_i) * double(v_i), i = 0, 1, 2
+ *               X = ((R00 * m0 + R01 * m1) + R02 * m2) + t_x, Y and Z likewise with R's second and third row
+ *               u = (K0 * X) / Z + K2,   v = (K4 * Y) / Z + K5
+ *               a vertex is recomputed for every triangle that names it: the same operations on the same inputs, the same bits
+ *   drop        a triangle is dropped if a vertex has Z <= 0 or a u, v or Z that is not finite.  THERE IS NO CLIPPING: a
+ *               triangle that crosses the camera plane is not drawn at all.
+ *   samples     the integer pixel coordinates (px, py): the grid hsp_frame_to_pcl_* back-projects, so a rendered pixel's
+ *               point lies on the ray it was sampled on
+ *   edges       for k = 0, 1, 2: c = vertex k of the row, a and b the other two with index a < index b (a repeated index
+ *               drops the triangle);  e_k(q) = (u_b - u_a) * (q_y - v_a) - (v_b - v_a) * (q_x - u_a),  A_k = e_k(P_c);
+ *               A_k == 0 or not finite drops the triangle.  Two triangles that share an edge evaluate the same e there.
+ *   candidates  the pixels of the frame with floor(min u) <= px <= ceil(max u) and floor(min v) <= py <= ceil(max v) over the
+ *               three vertices (min, max, floor and ceil are exact; in exact arithmetic no pixel outside them is inside)
+ *   inside      a candidate with, for all three k, e_k(p) >= 0 where A_k > 0 and e_k(p) <= 0 where A_k < 0: edges are
+ *               inclusive and both facings are drawn
+ *   depth       l_k = e_k(p) / A_k,  inv = (l0 / Z0 + l1 / Z1) + l2 / Z2,  Z = ((l0 + l1) + l2) / inv,  zmm = Z * 1000
+ *   word        _u16: q = rint(zmm), half to even; the fragment is kept iff 1 <= q <= 65535, its word is q
+ *               _f32: f = (float) zmm; kept iff f is finite and > 0, its word is the bit pattern of f
+ *   visibility  per pixel the smallest 64-bit key (word << 32) | j over the kept fragments of its frame wins: the nearest
+ *               surface, and among equal depth words the lower instance index.  over == 0: a pixel no fragment reaches gets
+ *               depth 0 and label 0.  over == 1: an existing pixel with depth > 0 (fp32: finite and > 0) enters with the key
+ *               (its word << 32) | 0xFFFFFFFF and keeps its label where it wins -- a rendered surface at the same word goes in
+ *               front of it --, any other existing pixel counts as empty and is written as depth 0, label 0.
+ * The frames are a pure function of the inputs: a minimum does not depend on the order the fragments arrive in.
+ *
+ * hsp_label_boxes: boxes[j] = (x1, y1, x2, y2) int32 with x1, y1 the least column and row of frame frame_id[j] whose label is
+ * label[j] and x2, y2 the greatest column and row PLUS ONE (the exclusive convention of the annotations the training loader
+ * reads, what hsp_dzi_windows takes; get_bbox's snapping to multiples of 40 is not applied); count[j] (n) int32 the number of
+ * such pixels.  No such pixel, or a frame_id / label out of range: zeros and a count of 0.  Integer min, max and add only.
+ *
+ * Limits: 0 <= n <= 65535 (hsp_label_boxes: n >= 1), F, H, W >= 1, H * W < 2^31, over 0 or 1, camK_rows 1 or F, V, T, n_mesh
+ * >= 1; with n == 0 the instance and mesh pointers are not read (they may be NULL) and the frames are cleared, or with over
+ * left as they are (empty pixels written as zeros).  A NULL pointer or a size out of range is HSP_ERR_BAD_ARG before any launch;
+ * ws NULL, off a 16-byte boundary or below hsp_render_workspace_bytes(F, H, W, n) (0 for sizes out of range) is
+ * HSP_ERR_WORKSPACE.  On the device a mesh_id, frame_id or label out of range, or a mesh row that leaves verts or tris, makes
+ * that instance draw nothing and a vertex index outside its mesh drops the triangle: nothing is read out of bounds.  (The
+ * host checks the indices of a mesh set once, when it is built.) */
+size_t hsp_render_workspace_bytes(int F, int H, int W, int n);
+int hsp_render_depth_u16(const float *verts, int V, const int32_t *tris, int T, const int32_t *mesh, int n_mesh,
+                         const int32_t *mesh_id, const int32_t *frame_id, const int32_t *label, const float *rt,
+                         const float *scale, const double *camK, int camK_rows, int n, int F, int H, int W, int over,
+                         uint16_t *depth, uint8_t *labels, void *ws, size_t ws_bytes, hspStream_t stream);
+int hsp_render_depth_f32(const float *verts, int V, const int32_t *tris, int T, const int32_t *mesh, int n_mesh,
+                         const int32_t *mesh_id, const int32_t *frame_id, const int32_t *label, const float *rt,
+                         const float *scale, const double *camK, int camK_rows, int n, int F, int H, int W, int over,
+                         float *depth, uint8_t *labels, void *ws, size_t ws_bytes, hspStream_t stream);
+int hsp_label_boxes(const uint8_t *labels, const int32_t *frame_id, const int32_t *label, int n, int F, int H, int W,
+                    int32_t *boxes, int32_t *count, hspStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
