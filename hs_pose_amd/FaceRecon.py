@@ -149,7 +149,11 @@ class FaceRecon(nn.Module):
         if self._bf16 is not None:
             self._bf16.refresh()                      # fp32 master weights -> this step's bf16 working copies (one launch)
         else:
-            ops.x3_refresh()                          # fp32 weights -> the three bf16 slices of the x3 products (one launch)
+            # fp32 weights -> the three bf16 slices of the x3 products, and every layer's directions -> their normalised table
+            # (ops.X3Planes.register_dirs: the receptive-field kernels then load it instead of normalising per workgroup): one launch
+            for layer in (self.conv_0, self.conv_1, self.conv_2, self.conv_3, self.conv_4):
+                ops.x3_planes.register_dirs(layer.directions)
+            ops.x3_refresh()
         with gcn3d.knn_scope():
             # the two coarse levels' vertices, neighbour lists and up-sampling maps in one launch, up front (they depend on the
             # coordinates and the pool rows -- host-drawn, or under the 'fps' sampler picked from the coordinates -- only)

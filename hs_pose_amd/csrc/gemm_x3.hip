@@ -24,6 +24,7 @@
 // 16-byte chunks of row r stored at chunk ^ ((r >> 2) & 3) -- conflict-free for the 16-lane groups of ds_read_b128.  Two
 // workgroups per CU alternate staging and MFMA phases.
 #include "common.h"
+#include "rf_dirs.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -580,6 +581,9 @@ __global__ __launch_bounds__(256) void gemm_x3_reduce_kernel(const float* __rest
 // transpose == 1: src is (K, N) -> plane[p][n][k] = slice_p(src[k][n]).  Plane row pitch kp (>= K rounded up to 32; the
 // columns k >= K are zero: written once when the buffer is allocated), plane stride ps elements.  tile0 counts pieces of
 // 32 (n) x 64 (k) OUTPUT elements: ceil(N / 32) * ceil(K / 64) per entry.
+// transpose == 2: not a weight -- src is the raw (3, cols) direction parameter of a receptive-field layer (pitch ld, cols a
+// multiple of 4) and dst its column-normalised fp32 copy (3, cols), by the function the rf kernels normalise with (rf_dirs.h):
+// the table they load instead (hsp_rf_dirs_hat_bind).  ceil(cols / 1024) pieces; kp and ps unused.
 __global__ __launch_bounds__(256) void split_params_x3_kernel(const HspSplitDesc* __restrict__ tab, int n) {
     // a workgroup writes a 32 (n) x 64 (k) piece of the three planes; a thread owns k PAIRS (one dword store per plane)
     __shared__ float tile[64][33];
@@ -587,6 +591,19 @@ __global__ __launch_bounds__(256) void split_params_x3_kernel(const HspSplitDesc
     while (e + 1 < n && (int)blockIdx.x >= tab[e + 1].tile0) ++e;
     const HspSplitDesc d = tab[e];
     const int t = (int)blockIdx.x - d.tile0;
+    if (d.transpose == 2) {                                            // a direction parameter: 256 threads x 4 columns a piece
+        const int j = (t * 256 + (int)threadIdx.x) << 2;
+        if (j < d.cols) {
+            float4 d0, d1, d2;
+            load_dirs_raw(d.src, d.ld, j, d0, d1, d2);
+            normalise_dirs(d0, d1, d2);
+            float* hat = reinterpret_cast<float*>(d.dst);
+            *reinterpret_cast<float4*>(hat + j) = d0;
+            *reinterpret_cast<float4*>(hat + d.cols + j) = d1;
+            *reinterpret_cast<float4*>(hat + 2 * d.cols + j) = d2;
+        }
+        return;
+    }
     const int Nn = d.transpose ? d.cols : d.rows, Kk = d.transpose ? d.rows : d.cols;
     const int tk = (Kk + 63) >> 6;
     const int n0 = (t / tk) * 32, k0 = (t % tk) * 64;

@@ -12,34 +12,29 @@
 // HBM-bound kernels: algorithmic bytes/point (fwd) = k*S*C*4 (gather, L2) + (S+1)*C*4/own row ... see DESIGN.md.
 #include "common.h"
 #include "folds.h"
+#include "rf_dirs.h"
 #include <stdlib.h>
 #include <atomic>
+#include <mutex>
 #include <type_traits>
+#include <vector>
 
 namespace hsp {
 
 #define RF_THREADS 256
+// forward workgroups per CU below 2048 / below 8192 points (rf_fwd, where the measurements stand; -D for the A/B)
+#ifndef RF_FWD_WGS_TINY
+#define RF_FWD_WGS_TINY 4
+#endif
+#ifndef RF_FWD_WGS_SMALL
+#define RF_FWD_WGS_SMALL 4
+#endif
 
-// F.normalize(directions, dim=0) for the 4 columns j..j+3 of the raw (3, S*C) parameter
-// (reference gcn3d.py:100,166): D / max(||D||_col, 1e-12).  Folded into every kernel so the normalised
-// copy is never materialised and its Jacobian is applied by rf_dirs_reduce_kernel.
-__device__ __forceinline__ void normalise_dirs(float4& d0, float4& d1, float4& d2) {
-#define RF_NRM(X)                                                                                    \
-    {                                                                                                \
-        const float n2 = norm2_chain(d0.X, d1.X, d2.X);                                              \
-        const float nr = fmaxf(sqrtf(n2), 1e-12f);           /* correctly rounded, as ATen's */          \
-        d0.X = __fdiv_rn(d0.X, nr); d1.X = __fdiv_rn(d1.X, nr); d2.X = __fdiv_rn(d2.X, nr);          \
-    }
-    RF_NRM(x) RF_NRM(y) RF_NRM(z) RF_NRM(w)
-#undef RF_NRM
-}
-__device__ __forceinline__ void load_dirs_normed(const float* __restrict__ dirs, int SC, int j, float4& d0,
-                                                 float4& d1, float4& d2) {
-    d0 = *reinterpret_cast<const float4*>(dirs + j);
-    d1 = *reinterpret_cast<const float4*>(dirs + SC + j);
-    d2 = *reinterpret_cast<const float4*>(dirs + 2 * SC + j);
-    normalise_dirs(d0, d1, d2);
-}
+// F.normalize(directions, dim=0) of the raw (3, S*C) parameter (rf_dirs.h: normalise_dirs, load_dirs_normed) is part of every
+// kernel here, and its Jacobian is applied by rf_dirs_reduce_kernel.  Where the caller has bound a normalised table to the
+// parameter (hsp_rf_dirs_hat_bind: a network's registry refreshes it once per forward, in the launch that splits its weights)
+// the kernels load the table -- the same bits -- and a workgroup's prologue has no square root and no division left; with no
+// table they normalise in the prologue.  `hat` below is that table or null.
 
 // relu(theta) of the forward kernels.  theta = R^ . D^ is the cosine of two unit vectors, so relu == clamp to [0, 1] up to the
 // rounding of the three-term chain: fmed3(x, 0, 1) is folded by the compiler into the LAST FMA as its clamp modifier
@@ -81,13 +76,18 @@ __device__ __forceinline__ float rf_dot3(const R3 r, float d0, float d1, float d
 
 // the normalised directions of a thread's NCH column groups tid, tid + 256, ... (a slot past the last group reads group 0)
 template <int NCH>
-__device__ __forceinline__ void rf_load_dirs(const float* dirs, int SC, int tid, float4 (&d0)[NCH], float4 (&d1)[NCH],
-                                             float4 (&d2)[NCH]) {
+__device__ __forceinline__ void rf_load_dirs(const float* dirs, const float* hat, int SC, int tid, float4 (&d0)[NCH],
+                                             float4 (&d1)[NCH], float4 (&d2)[NCH]) {
     const int nq = SC >> 2;
+    const float* src = hat ? hat : dirs;
 #pragma unroll
     for (int u = 0; u < NCH; ++u) {
         const int cq = tid + u * RF_THREADS;
-        load_dirs_normed(dirs, SC, (cq < nq ? cq : 0) << 2, d0[u], d1[u], d2[u]);
+        load_dirs_raw(src, SC, (cq < nq ? cq : 0) << 2, d0[u], d1[u], d2[u]);
+    }
+    if (!hat) {
+#pragma unroll
+        for (int u = 0; u < NCH; ++u) normalise_dirs(d0[u], d1[u], d2[u]);
     }
 }
 
@@ -163,6 +163,7 @@ template <bool SURFACE, int NCH, bool WF, typename FT>
 __global__ __launch_bounds__(RF_THREADS) void rf_fwd_kernel(const float* __restrict__ xyz,
                                                             const int32_t* __restrict__ idx,
                                                             const float* __restrict__ dirs,
+                                                            const float* __restrict__ hat,
                                                             const FT* __restrict__ fm, int B, int N, int k,
                                                             int S, int C, FT* __restrict__ out,
                                                             uint16_t* __restrict__ argrow,
@@ -177,7 +178,7 @@ __global__ __launch_bounds__(RF_THREADS) void rf_fwd_kernel(const float* __restr
     const int fstride = (S + 1) * C;
     const float invS_div = (float)S;
     float4 d0[NCH], d1[NCH], d2[NCH];
-    rf_load_dirs<NCH>(dirs, SC, tid, d0, d1, d2);
+    rf_load_dirs<NCH>(dirs, hat, SC, tid, d0, d1, d2);
     const PointIter it(B);
     for (int b = it.b0; b < B; b += it.bstep) {
         const float* xb = xyz + (size_t)b * N * 3;
@@ -225,6 +226,7 @@ template <bool SURFACE, int NCH, bool WF, typename FT>
 __global__ __launch_bounds__(RF_THREADS) void rf_fwd_pipe_kernel(const float* __restrict__ xyz,
                                                                  const int32_t* __restrict__ idx,
                                                                  const float* __restrict__ dirs,
+                                                                 const float* __restrict__ hat,
                                                                  const FT* __restrict__ fm, int B, int N, int k,
                                                                  int S, int C, FT* __restrict__ out,
                                                                  uint16_t* __restrict__ argrow,
@@ -241,7 +243,7 @@ __global__ __launch_bounds__(RF_THREADS) void rf_fwd_pipe_kernel(const float* __
     const int spare0 = nq - (NCH - 1) * RF_THREADS;           // first thread without a group in the last slot
     const float invS_div = (float)S;
     float4 d0[NCH], d1[NCH], d2[NCH];
-    rf_load_dirs<NCH>(dirs, SC, tid, d0, d1, d2);
+    rf_load_dirs<NCH>(dirs, hat, SC, tid, d0, d1, d2);
     const PointIter it(B);
     auto dirs_phase = [&](int b, int i, int buf) {
         const int t = tid - spare0;
@@ -324,7 +326,7 @@ __global__ __launch_bounds__(RF_THREADS) void rf_fwd_pipe_kernel(const float* __
 
 template <int NCH>
 __global__ __launch_bounds__(RF_THREADS) void rf_conv_bwd_csr_kernel(
-    const float* __restrict__ xyz, const float* __restrict__ dirs, const float* __restrict__ fm,
+    const float* __restrict__ xyz, const float* __restrict__ dirs, const float* __restrict__ hat, const float* __restrict__ fm,
     const uint16_t* __restrict__ argrow, const float* __restrict__ gout, const int32_t* __restrict__ rev_off,
     const int32_t* __restrict__ rev_edge, int B, int N, int k, int S, int C, float* __restrict__ gfm,
     float* __restrict__ ws) {
@@ -340,7 +342,7 @@ __global__ __launch_bounds__(RF_THREADS) void rf_conv_bwd_csr_kernel(
     const int cq4 = C >> 2;
 
     float4 d0[NCH], d1[NCH], d2[NCH], gd0[NCH], gd1[NCH], gd2[NCH];
-    rf_load_dirs<NCH>(dirs, SC, tid, d0, d1, d2);
+    rf_load_dirs<NCH>(dirs, hat, SC, tid, d0, d1, d2);
 #pragma unroll
     for (int u = 0; u < NCH; ++u) gd0[u] = gd1[u] = gd2[u] = make_float4(0.f, 0.f, 0.f, 0.f);
     const PointIter it(B);
@@ -556,7 +558,7 @@ __device__ __forceinline__ void rf_bwd_wg_map(int& b, int& tile) {
 //           centre columns copied by the first C / TC tiles of a cloud after their flush.
 //   D > 0   the batched form: every independent load of the set-up -- directions, xyz, the centre columns' share, the scale
 //           pass's grad_out rows, the sweep's first D stages -- is issued as fixed-size register batches with clamped addresses
-//           BEFORE anything waits (the tile is zeroed and the directions normalised under that one round trip); the sweep runs
+//           BEFORE anything waits (the tile is zeroed under that one round trip); the sweep runs
 //           a D-deep register ring of (argrow, fwin[, grad_out][, the point]) stages, unrolled by D so that it rotates by
 //           renaming; the centre columns are spread over all tiles of the cloud.
 //   RG > 0  (D > 0, not SURFACE, RS == 1, ceil(N / PL) <= RG): the scale pass's grad_out rows ARE the sweep's -- same thread,
@@ -577,7 +579,7 @@ __host__ __device__ constexpr int rf_tile_waves(int tc, bool surface, int rs, in
 }
 template <int TC, bool SURFACE, bool FWIN, typename FT, int RS = 1, int D = 0, int RG = 0>
 __global__ __launch_bounds__(RF_TILE_THREADS, rf_tile_waves(TC, SURFACE, RS, D)) void rf_bwd_tile_kernel(
-    const float* __restrict__ xyz, const float* __restrict__ dirs, const FT* __restrict__ fwin,
+    const float* __restrict__ xyz, const float* __restrict__ dirs, const float* __restrict__ hat, const FT* __restrict__ fwin,
     const uint16_t* __restrict__ argrow, const FT* __restrict__ gout, int B, int N, int S, int C,
     FT* __restrict__ gfm, float* __restrict__ gd_part) {
     static_assert(RG == 0 || (D > 0 && !SURFACE && RS == 1), "resident grad_out rows: batched whole-cloud conv tiles only");
@@ -646,9 +648,7 @@ __global__ __launch_bounds__(RF_TILE_THREADS, rf_tile_waves(TC, SURFACE, RS, D))
             return s;
         };
         // ---- 1. issue: nothing below waits before the last of these loads is out
-        d0 = *reinterpret_cast<const float4*>(dirs + j);
-        d1 = *reinterpret_cast<const float4*>(dirs + SC + j);
-        d2 = *reinterpret_cast<const float4*>(dirs + 2 * SC + j);
+        load_dirs_raw(hat ? hat : dirs, SC, j, d0, d1, d2);
         const int n3 = 3 * (r1 - r0);
         const float* xsrc = xb + r0 * 3;
         float xv[RF_XB];
@@ -690,10 +690,9 @@ __global__ __launch_bounds__(RF_TILE_THREADS, rf_tile_waves(TC, SURFACE, RS, D))
         Stage st[NST];
 #pragma unroll
         for (int u = 0; u < (D < NST ? D : NST); ++u) st[u] = load_stage(pl + u * PL);
-        // ---- 2. under that round trip: zero the tile (one 128-bit LDS store per piece), normalise the directions
+        // ---- 2. under that round trip: zero the tile (one 128-bit LDS store per piece)
         if (!SURFACE)
             for (int q = tid; q < NR * G; q += RF_TILE_THREADS) *reinterpret_cast<rf_v4f*>(acc + q * 4) = rf_v4f{0.f, 0.f, 0.f, 0.f};
-        normalise_dirs(d0, d1, d2);
         // ---- 3. consume
 #pragma unroll
         for (int u = 0; u < RF_XB; ++u) {
@@ -736,6 +735,10 @@ __global__ __launch_bounds__(RF_TILE_THREADS, rf_tile_waves(TC, SURFACE, RS, D))
                 }
             rf_tile_scale(vm, invS, N, wmax, tid, fx_scale, fx_inv);
         }
+        // no table bound to the parameter: normalise here.  (As a branch in step 2, where the unconditional normalisation used to
+        // hide under the round trip, it cost the 16-column resident instance 5 spilled registers at its 128-VGPR bound; here, with
+        // the set-up batches consumed, every instance keeps the registers and the occupancy it had.)
+        if (!hat) normalise_dirs(d0, d1, d2);
         __syncthreads();
         // ---- 4. sweep: each thread takes its points pl, pl + PL, ... in that order (the direction gradient's rounding)
         auto stage_point = [&](const Stage& s, RawT graw, int p) {   // (a bf16 piece is widened here, where it is used)
@@ -773,7 +776,7 @@ __global__ __launch_bounds__(RF_TILE_THREADS, rf_tile_waves(TC, SURFACE, RS, D))
         }
         rf_tile_scale(vm, invS, N, wmax, tid, fx_scale, fx_inv);
     }
-    load_dirs_normed(dirs, SC, j, d0, d1, d2);
+    load_dirs_normed(dirs, hat, SC, j, d0, d1, d2);
     __syncthreads();
     // software pipeline: the next point's winning rows / their support values / gradient are in flight while
     // this one is processed; with FWIN every global read of the loop is a coalesced stream
@@ -860,6 +863,41 @@ static int rf_bwd_grid(long long points, int SC) {
 
 using namespace hsp;
 
+// The normalised tables bound to direction parameters, keyed by the parameter's device address: host state of the process, like
+// the tile schedule below.  Every launcher here looks its `dirs` argument up when the call is issued (a captured graph keeps what
+// it was captured with); the binder keeps parameter and table alive while bound and answers for the table holding
+// normalise_dirs of the parameter's current values when a kernel that was handed it runs.
+namespace {
+struct RfDirsHat { const float* dirs; int SC; const float* hat; };
+std::mutex g_rf_hat_mutex;
+std::vector<RfDirsHat> g_rf_hat;
+}  // namespace
+
+static const float* rf_dirs_hat_find(const float* dirs, int SC) {
+    std::lock_guard<std::mutex> lock(g_rf_hat_mutex);
+    for (const RfDirsHat& e : g_rf_hat)
+        if (e.dirs == dirs) return e.SC == SC ? e.hat : nullptr;     // (another shape under this address: not this parameter)
+    return nullptr;
+}
+
+extern "C" int hsp_rf_dirs_hat_bind(const float* dirs, int SC, const float* hat) {
+    if (!dirs || SC <= 0 || (SC & 3)) return HSP_ERR_BAD_ARG;
+    if (hat && (((uintptr_t)hat & 15) || hat == dirs)) return HSP_ERR_BAD_ARG;     // read with 16-byte loads
+    std::lock_guard<std::mutex> lock(g_rf_hat_mutex);
+    for (size_t i = 0; i < g_rf_hat.size(); ++i)
+        if (g_rf_hat[i].dirs == dirs) {
+            if (hat) g_rf_hat[i] = RfDirsHat{dirs, SC, hat};
+            else g_rf_hat.erase(g_rf_hat.begin() + (long)i);
+            return HSP_OK;
+        }
+    if (hat) g_rf_hat.push_back(RfDirsHat{dirs, SC, hat});
+    return HSP_OK;
+}
+
+extern "C" const float* hsp_rf_dirs_hat_lookup(const float* dirs, int SC) {
+    return dirs && SC > 0 ? rf_dirs_hat_find(dirs, SC) : nullptr;
+}
+
 static int rf_check(const void* a, const void* b, const void* c, int B, int N, int k, int S, int C) {
     if (!a || !b || !c || B <= 0 || N <= 0 || k <= 0 || S <= 0 || C <= 0) return HSP_ERR_BAD_ARG;
     if (N > 65535 || (C & 3)) return HSP_ERR_UNSUPPORTED;   // winning rows are stored as uint16; float4 column groups
@@ -915,15 +953,21 @@ static int rf_fwd(const float* xyz, const int32_t* idx, const float* dirs, const
     // slower inside the matrix-core form of round 4, tools/experiments/.  Removed.)
     const RfFwdPlan plan = rf_fwd_plan(k, S, C);
     if (!plan.nch) return HSP_ERR_UNSUPPORTED;            // S*C <= 4096, (S*C + 5 k) floats of LDS
-    // workgroups per CU: 8 for the large layers; small clouds amortise a workgroup's prologue (direction loads + normalisation)
-    // over more points with 6 / 4 (measured at B = 16: N = 257 55.3 -> 52.4 us, N = 64 24.3 -> 23.6 us)
+    const float* hat = rf_dirs_hat_find(dirs, S * C);
+    // workgroups per CU: 8 for the large layers, 4 below 8192 points.  Measured at B = 16 with the normalised table bound (no
+    // normalisation left in the prologue; event-timed launches, three alternations):
+    //   N = 257, C = 256 (4112 points):  4: 40.2 - 40.6 us   5: 40.8 - 41.2   6 (the setting until then): 41.4 - 41.6   8: 41.4 - 41.6
+    //   N = 64,  C = 512 (1024 points):  4: 19.19 - 19.28 us  6: 19.24 - 19.29  8: 19.25 - 19.27  2: 18.82 - 18.95
+    // At N = 64 the point schedule gives an XCD's workgroups the indices 0 .. 63 of its two clouds: from 2 per CU (64 per XCD) on,
+    // the same 512 workgroups work and the rest leave at once, so 4 / 6 / 8 are one setting.  2 per CU measured 0.3 us less but is
+    // not taken: below 2048 points lie the single-cloud inference shapes too, where it halves the workgroups and was not measured.
     const long long npts = (long long)B * N;
-    const int grid = persistent_blocks(npts, npts < 2048 ? 4 : npts < 8192 ? 6 : 8);
+    const int grid = persistent_blocks(npts, npts < 2048 ? RF_FWD_WGS_TINY : npts < 8192 ? RF_FWD_WGS_SMALL : 8);
     rf_dispatch_nch(plan.nch, !SURFACE && fwin, [&](auto nch, auto wf) {
         constexpr int NCH = decltype(nch)::value;
         constexpr bool WF = !SURFACE && decltype(wf)::value;
         auto kern = plan.pipe ? rf_fwd_pipe_kernel<SURFACE, NCH, WF, FT> : rf_fwd_kernel<SURFACE, NCH, WF, FT>;
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(RF_THREADS), plan.lds, as_stream(stream), xyz, idx, dirs, fm, B, N, k, S, C, out,
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(RF_THREADS), plan.lds, as_stream(stream), xyz, idx, dirs, hat, fm, B, N, k, S, C, out,
                            argrow, fwin);
     });
     return check_launch();
@@ -982,8 +1026,9 @@ extern "C" int hsp_rf_conv_bwd(const float* xyz, const float* dirs_n, const floa
     const size_t lds = (size_t)(RF_EB * (C + 8)) * 4;
     if (lds > 64 * 1024) return HSP_ERR_UNSUPPORTED;
     float* wsf = reinterpret_cast<float*>(ws);
+    const float* hat = rf_dirs_hat_find(dirs_n, SC);
     rf_dispatch_nch(nch, false, [&](auto n, auto) {
-        hipLaunchKernelGGL((rf_conv_bwd_csr_kernel<decltype(n)::value>), dim3(grid), dim3(RF_THREADS), lds, st, xyz, dirs_n, fm, argrow,
+        hipLaunchKernelGGL((rf_conv_bwd_csr_kernel<decltype(n)::value>), dim3(grid), dim3(RF_THREADS), lds, st, xyz, dirs_n, hat, fm, argrow,
                            grad_out, rev_off, rev_edge, B, N, k, S, C, grad_fm, wsf);
     });
     rc = check_launch();
@@ -1096,10 +1141,11 @@ static int rf_bwd_scatter(const float* xyz, const float* dirs, const FT* fm, con
     hipStream_t st = as_stream(stream);
     float* part = reinterpret_cast<float*>(ws);
     const bool legacy = g_rf_bwd_legacy.load() != 0;
+    const float* hat = rf_dirs_hat_find(dirs, SC);
     if (plan.rs == 2) {
         const int nr = (N + 1) / 2;
         const size_t lds2 = ((size_t)nr * 16 + 3 * (size_t)nr) * 4;
-        rc = rf_tile_launch<16, SURFACE, FWIN, FT, 2>(legacy, N, dim3(SC / 16, B, 2), lds2, st, xyz, dirs, fm, argrow, gout, B, N, S, C,
+        rc = rf_tile_launch<16, SURFACE, FWIN, FT, 2>(legacy, N, dim3(SC / 16, B, 2), lds2, st, xyz, dirs, hat, fm, argrow, gout, B, N, S, C,
                                                       gfm, part);
         if (rc) return rc;
         if (pending) { *pending = HspDirsPending{part, dirs, gdirs, 2 * B, SC}; return HSP_OK; }
@@ -1110,7 +1156,7 @@ static int rf_bwd_scatter(const float* xyz, const float* dirs, const FT* fm, con
     size_t lds = ((SURFACE ? 0 : (size_t)N * tc) + 3 * (size_t)N) * 4;
     if (lds < RF_TILE_THREADS * 12 * 4) lds = RF_TILE_THREADS * 12 * 4;
     dim3 grid(SC / tc, B);
-#define RF_TILE_LAUNCH(TC) rc = rf_tile_launch<TC, SURFACE, FWIN, FT, 1>(legacy, N, grid, lds, st, xyz, dirs, fm, argrow, gout, B, N, S, C, gfm, part);
+#define RF_TILE_LAUNCH(TC) rc = rf_tile_launch<TC, SURFACE, FWIN, FT, 1>(legacy, N, grid, lds, st, xyz, dirs, hat, fm, argrow, gout, B, N, S, C, gfm, part);
     if (tc == 64) RF_TILE_LAUNCH(64) else if (tc == 32) RF_TILE_LAUNCH(32) else if (tc == 16) RF_TILE_LAUNCH(16)
     else if (tc == 8) RF_TILE_LAUNCH(8) else RF_TILE_LAUNCH(4)
 #undef RF_TILE_LAUNCH

@@ -282,7 +282,8 @@ class HSlayer_surface(nn.Module):
         int32 neighbour index (directions are recomputed in-kernel) instead of the reference's
         materialised (bs,N,k,3) receptive field."""
         idx = neighbor_index[:, :, :neighbor_num] if neighbor_index.shape[2] != neighbor_num else neighbor_index
-        # F.normalize(self.directions, dim=0) and its Jacobian are applied inside the kernels
+        # F.normalize(self.directions, dim=0) and its Jacobian are applied inside the kernels (a parameter registered with a
+        # network's ops.X3Planes: the kernels load the table its refresh() normalised, the same bits)
         return ops.rf_surface(vertices, idx.to(torch.int32), self.directions, self.support_num)
 
     def ORL_forward(self, feature, vertices, neighbor_num):

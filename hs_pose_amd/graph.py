@@ -27,6 +27,7 @@ buffers, nothing is drawn or uploaded before a replay, and the owner's one actio
 ``GraphedStep`` and ``GraphedNetwork`` keep the host draws.
 """
 import contextlib
+import gc
 import os
 
 import torch
@@ -156,9 +157,19 @@ class _Capture:
             torch.cuda.synchronize()
             self._joined = True
         graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph, pool=None if share_pool is None else share_pool.pool(),
-                              stream=self.side if on_warmup_stream else None, capture_error_mode="thread_local"):
-            fn()
+        # No cyclic garbage collection while the stream captures: a pass that starts inside ``fn`` may destroy a dead cycle that
+        # holds an earlier captured graph (frame._TrackGraph's closures refer to the object that owns its GraphedInference), and
+        # destroying a graph while this thread captures aborted the process (torch.cuda.graph no longer collects on entry).
+        # Whatever died waits for the first pass after the capture.
+        gc_was_on = gc.isenabled()
+        gc.disable()
+        try:
+            with torch.cuda.graph(graph, pool=None if share_pool is None else share_pool.pool(),
+                                  stream=self.side if on_warmup_stream else None, capture_error_mode="thread_local"):
+                fn()
+        finally:
+            if gc_was_on:
+                gc.enable()
         return graph
 
 

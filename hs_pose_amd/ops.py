@@ -7,6 +7,7 @@ return code.  No CPU fallback: a non-GPU tensor is an error.
 import ctypes
 import functools
 import os
+import weakref
 
 import torch
 
@@ -393,7 +394,7 @@ class _RFSurface(torch.autograd.Function):
     def forward(ctx, xyz, idx, dirs_n, S):
         xyz = _req(xyz, torch.float32, "rf_surface.xyz")
         idx = _req(idx, torch.int32, "rf_surface.idx")
-        dirs_n = _req(dirs_n, torch.float32, "rf_surface.dirs")
+        dirs_n = dirs_fresh(_req(dirs_n, torch.float32, "rf_surface.dirs"))
         B, N, k = idx.shape
         SC = dirs_n.shape[1]
         K = SC // S
@@ -411,7 +412,7 @@ class _RFSurface(torch.autograd.Function):
         g = _req(g, torch.float32, "rf_surface.grad")
         B, N, k = idx.shape
         SC = dirs_n.shape[1]
-        gd = torch.empty_like(dirs_n)
+        gd = torch.empty_like(dirs_fresh(dirs_n))
         L = lib()
         wsb = L.hsp_rf_bwd_scatter_workspace_bytes(B, SC)
         ws = _ws(wsb, g.device)
@@ -997,11 +998,14 @@ class X3Planes:
     another matrix while its entry lives; the registry -- tables, planes and references -- goes away with the network.  A table
     that was replaced (a matrix registered later) is parked, not freed, ONCE a hipGraph capture has read this registry: the captured
     graph may still point to it.  A registry no capture has touched (ad-hoc callers, gradient checks) frees what it replaces, so the
-    ``max_entries`` bound of the process-wide registry does bound device memory."""
+    ``max_entries`` bound of the process-wide registry does bound device memory.  The network also registers the direction
+    parameters of its receptive-field layers (``register_dirs``): refresh() normalises them in the same launch."""
 
     def __init__(self, max_entries=0):
         self.entries = {}            # key -> dict(src (kept alive), planes, N, K, kp, transpose, ver: src._version at the split)
+        self.dirs = {}               # (address, SC) -> direction entry: dict(src (kept alive), hat, SC, ver, bound) -- register_dirs
         self.table = None            # device table of every entry (rebuilt when an entry is added)
+        weakref.finalize(self, X3Planes._release_dirs, self.dirs).atexit = False
         self.total_tiles = 0
         self._old_tables = []
         self._captured = False       # a capture has read planes / the table of this registry
@@ -1038,7 +1042,7 @@ class X3Planes:
             self._split([e])                                   # this matrix now ...
             if self.table is not None:
                 self._park(self.table)
-            self.table, self.total_tiles = self._table_of(list(self.entries.values()))   # ... and the table of all for refresh()
+            self.table, self.total_tiles = self._table_of(self._all())                    # ... and the table of all for refresh()
         elif e["ver"] != e["src"]._version and not torch.cuda.is_current_stream_capturing():
             # the weights moved in place (optimizer.step, load_state_dict) since these planes were cut and nobody called
             # refresh(): a stand-alone module / a direct ops.linear_rows caller.  Re-split this matrix now.
@@ -1046,11 +1050,64 @@ class X3Planes:
             e["ver"] = e["src"]._version
         return e["planes"], e["kp"], e["N"] * e["kp"]
 
+    def _all(self):
+        return list(self.entries.values()) + list(self.dirs.values())
+
+    # ---- direction parameters of receptive-field layers: F.normalize(directions, dim=0) once per forward ----------------------
+    # A registered (3, S*C) parameter gets a table ``hat`` of the same shape that refresh() fills in the launch that splits the
+    # weights (HspSplitDesc.transpose = 2: the rf kernels' own normalisation, csrc/rf_dirs.h).  Once filled it is BOUND in the
+    # library (hsp_rf_dirs_hat_bind, host state keyed by the parameter's address): every rf kernel called with that parameter then
+    # loads the table instead of normalising in each workgroup's prologue -- the same bits.  Registering launches nothing, and an
+    # entry no refresh() has filled yet is not bound: that forward normalises in-kernel.  (The tables only ride: a registry with
+    # no weight entry -- clouds so small that no product goes to gemm_x3 -- launches nothing, and its directions stay unbound.)
+    def register_dirs(self, D):
+        """make ``D``, the raw (3, S*C) fp32 direction parameter of a layer, an entry that refresh() normalises"""
+        k_ = (D.data_ptr(), D.shape[-1])
+        if k_ in self.dirs:
+            return
+        if D.dim() != 2 or D.shape[0] != 3 or D.shape[1] % 4 or D.dtype != torch.float32 or not D.is_cuda or not D.is_contiguous():
+            raise HspError("register_dirs: directions must be a contiguous (3, S*C) fp32 GPU matrix, S*C a multiple of 4")
+        if torch.cuda.is_current_stream_capturing():           # (no table can be built here: this parameter stays as it was)
+            return
+        src = D.detach()
+        self.dirs[k_] = dict(src=src, hat=torch.empty_like(src), SC=D.shape[1], ver=None, bound=False, dirs=True)
+        if self.entries:                                       # (else the first weight's registration builds the table)
+            self._park(self.table)
+            self.table, self.total_tiles = self._table_of(self._all())
+
+    @staticmethod
+    def _bind_dirs(e):
+        prev = _dirs_bound.get(e["src"].data_ptr())
+        if prev is not None and prev is not e:                 # the same parameter in another registry: the later table serves both
+            prev["bound"] = False
+        check(lib().hsp_rf_dirs_hat_bind(e["src"].data_ptr(), e["SC"], e["hat"].data_ptr()), "hsp_rf_dirs_hat_bind")
+        _dirs_bound[e["src"].data_ptr()] = e
+        e["bound"] = True
+
+    @staticmethod
+    def _unbind_dirs(e):
+        if e["bound"] and _dirs_bound.get(e["src"].data_ptr()) is e:
+            lib().hsp_rf_dirs_hat_bind(e["src"].data_ptr(), e["SC"], None)
+            del _dirs_bound[e["src"].data_ptr()]
+        e["bound"] = False
+
+    @staticmethod
+    def _release_dirs(dirs):
+        """the registry is gone (weakref.finalize): nothing refreshes its tables any more"""
+        for e in dirs.values():
+            X3Planes._unbind_dirs(e)
+        dirs.clear()
+
     def _table_of(self, ents):
         tab = (HspSplitDesc * len(ents))()
         tile0 = 0
         for i, e in enumerate(ents):
             W = e["src"]
+            if "dirs" in e:
+                tab[i].src, tab[i].dst = W.data_ptr(), e["hat"].data_ptr()
+                tab[i].rows, tab[i].cols, tab[i].ld, tab[i].transpose, tab[i].tile0 = 3, e["SC"], W.stride(0), 2, tile0
+                tile0 += (e["SC"] + 1023) // 1024                         # pieces of 256 threads x 4 columns
+                continue
             tab[i].src, tab[i].dst = W.data_ptr(), e["planes"].data_ptr()
             tab[i].rows, tab[i].cols, tab[i].ld = W.shape[0], W.shape[1], W.stride(0)
             tab[i].transpose, tab[i].kp, tab[i].tile0, tab[i].ps = int(e["transpose"]), e["kp"], tile0, e["N"] * e["kp"]
@@ -1067,11 +1124,28 @@ class X3Planes:
             return
         if not self._captured and torch.cuda.is_current_stream_capturing():
             self._captured = True
-        ents = list(self.entries.values())
-        _run("hsp_split_params_x3", (_p(self.table), len(ents), self.total_tiles, _stream()), key=f"n{len(ents)}",
-             abytes=sum(10 * e["N"] * e["K"] for e in ents))
-        for e in ents:
+        ents, dirs = list(self.entries.values()), list(self.dirs.values())      # (the table holds both, in this order)
+        _run("hsp_split_params_x3", (_p(self.table), len(ents) + len(dirs), self.total_tiles, _stream()), key=f"n{len(ents)}",
+             abytes=sum(10 * e["N"] * e["K"] for e in ents) + sum(24 * e["SC"] for e in dirs))
+        for e in ents + dirs:
             e["ver"] = e["src"]._version
+        for e in dirs:
+            if not e["bound"]:                                 # first fill, or unbound by dirs_fresh since the last one
+                self._bind_dirs(e)
+
+
+_dirs_bound = {}        # address of a direction parameter -> its entry, while the library holds a table for it (X3Planes._bind_dirs)
+
+
+def dirs_fresh(directions):
+    """call before handing ``directions`` to an rf kernel: a bound table that no longer matches the parameter -- moved in place
+    (optimizer.step, load_state_dict) with no refresh() since, the case of a stand-alone layer or a direct caller between two
+    forwards of the network -- is unbound, and the kernels normalise the new values themselves until the next refresh().  The
+    host check ``X3Planes.planes`` makes for weights; inside a capture nothing is touched."""
+    e = _dirs_bound.get(directions.data_ptr())
+    if e is not None and e["ver"] != e["src"]._version and not torch.cuda.is_current_stream_capturing():
+        X3Planes._unbind_dirs(e)
+    return directions
 
 
 x3_planes = X3Planes(max_entries=256)   # the CURRENT registry (a process-wide one until a network installs its own: x3_scope)
@@ -1494,7 +1568,7 @@ def _rf_conv_fwd_raw(xyz, idx, directions, fm, S, need_bwd=True):
     winners' support values, all the column-tile backward needs of fm once a cloud's fm outgrows L2 (hsp_rf_conv_wants_fwin);
     smaller layers and the gather-form backward (DETERMINISTIC, fp32 rows only) read fm itself."""
     B, N, k = idx.shape
-    SC = directions.shape[1]
+    SC = dirs_fresh(directions).shape[1]
     C = SC // S
     sfx, es = _sfx(fm), _es(fm)
     out = torch.empty(B, N, C, dtype=fm.dtype, device=xyz.device)
@@ -1521,7 +1595,7 @@ def _rf_conv_bwd_raw(xyz, idx, directions, fm, arg, gF3, S):
     """fm: either fm (B,N,(S+1)C) or the forward's fwin (B,N,SC) (told apart by the width); fp32 / bf16 rows (bf16 has no
     gather form: it takes the column-tile scatter whatever DETERMINISTIC says, and needs no ``idx``)."""
     B, N, _ = gF3.shape
-    SC = directions.shape[1]
+    SC = dirs_fresh(directions).shape[1]
     C = SC // S
     sfx, es = _sfx(gF3), _es(gF3)
     gfm = torch.empty(B, N, (S + 1) * C, dtype=gF3.dtype, device=gF3.device)
@@ -1740,7 +1814,7 @@ class _SurfaceLayer(torch.autograd.Function):
         w_ste, w_conv2 = w_ste3.squeeze(-1), w_conv23.squeeze(-1)
         xyz = _req(xyz, torch.float32, "surface_layer.xyz")
         idx_x = _req(idx_x, torch.int32, "surface_layer.idx")
-        directions = _req(directions, torch.float32, "surface_layer.directions")
+        directions = dirs_fresh(_req(directions, torch.float32, "surface_layer.directions"))
         B, N, _ = xyz.shape
         SC = directions.shape[1]
         C = SC // S
@@ -1829,7 +1903,7 @@ class _SurfaceLayer(torch.autograd.Function):
         if not small:
             gfg_n = _mm_nn(gt, Wb, alpha=1.0 / N)
         _orl_bwd_accumulate_raw(gfg_n, idx_x, arg_o, k, gF3, extra=g, counts=cnt_o)
-        gD = torch.empty_like(directions)
+        gD = torch.empty_like(dirs_fresh(directions))
         L = lib()
         wsb = L.hsp_rf_bwd_scatter_workspace_bytes(B, SC)
         ws = _ws(wsb, g.device)
@@ -1855,7 +1929,7 @@ def hs_layer(xyz, X, idx_f, idx_x, k, S, weights, bias, directions, w_ste, w_con
                 and idx_x.dtype == torch.int32 and idx_f.is_contiguous() and idx_x.is_contiguous()
                 and _exact_layer_ok(X.shape[1], X.shape[2], directions.shape[1] // S, (X, weights))):
             from ._ext import ext                      # inference: the layer's launch sequence issued from C++ in one call
-            return ext().hs_layer_forward(xyz, X, idx_f, idx_x, k, S, weights, bias, directions, w_ste, w_conv2)
+            return ext().hs_layer_forward(xyz, X, idx_f, idx_x, k, S, weights, bias, dirs_fresh(directions), w_ste, w_conv2)
     return _HSLayer.apply(xyz, X, idx_f, idx_x, k, S, weights, bias, directions, w_ste, w_conv2, bn_shift,
                           bool(out_f32) and X.dtype == torch.bfloat16)
 
@@ -1869,7 +1943,7 @@ def surface_layer(xyz, idx_x, k, S, directions, w_ste, w_conv2, relu=False, out_
             and idx_x.is_contiguous() and idx_x.shape[2] == k
             and _exact_layer_ok(xyz.shape[1], 3, directions.shape[1] // S, (w_conv2.squeeze(-1),))):
         from ._ext import ext
-        y = ext().surface_layer_forward(xyz, idx_x, k, S, directions, w_ste, w_conv2, relu)
+        y = ext().surface_layer_forward(xyz, idx_x, k, S, dirs_fresh(directions), w_ste, w_conv2, relu)
         return (y, y.view_as(y)) if relu else y
     return _SurfaceLayer.apply(xyz, idx_x, k, S, directions, w_ste, w_conv2, relu, out_dtype)
 

@@ -201,6 +201,15 @@ int hsp_rf_bwd_scatter_plan(int B, int N, int S, int C, int surface, int *row_sp
  * columns), kept for the A/B and the tests.  Process-wide; read when a call is issued, so a captured graph keeps the schedule it
  * was captured with.  Returns the previous value, or HSP_ERR_BAD_ARG (and changes nothing) for anything but 0 / 1. */
 int hsp_rf_bwd_set_schedule(int legacy);
+/* Host-only: bind a column-normalised copy `hat` (3, SC) fp32, 16-byte aligned, of the raw direction parameter `dirs` (3, SC).
+ * Every hsp_rf_* forward and backward entry point (fp32 and bf16 rows, scatter, gather and _partial forms) called with that `dirs`
+ * address and that S*C afterwards loads `hat` instead of normalising `dirs` in each workgroup's prologue; the direction
+ * gradient's Jacobian still reads `dirs`.  `hat` must hold, when such a kernel runs, exactly what the kernel would compute --
+ * hsp_split_params_x3 writes it for an HspSplitDesc with transpose = 2 -- so results are the same bits bound or unbound.  The
+ * caller keeps both buffers alive while bound.  hat = NULL unbinds.  Process-wide; read when a call is issued, so a captured graph
+ * keeps the table it was captured with.  Launches nothing.  hsp_rf_dirs_hat_lookup returns the table bound to (dirs, SC) or NULL. */
+int hsp_rf_dirs_hat_bind(const float *dirs, int SC, const float *hat);
+const float *hsp_rf_dirs_hat_lookup(const float *dirs, int SC);
 /* Backward, GATHER form over rev_off/rev_edge = hsp_rev_build(idx) of the SAME idx the forward used:
  * every grad_fm row is summed in ascending edge order (no atomics, bit-reproducible).
  * The rows of one neighbour list idx[b,i,:] must be DISTINCT: a hit is "the winner of (i, j) is this row", so a row listed
@@ -510,7 +519,9 @@ int hsp_gemm_wave_f32(const float *A1, int lda1, const float *B1, int ldb1, int 
  * three bf16 planes (N, ldp), plane p at P + p * ps elements, columns k >= K zero, ldp >= K rounded up to 32 -- written once
  * per step for every weight by hsp_split_params_x3 (HspSplitDesc: src (rows, cols) fp32 with pitch ld; transpose = 0: src is
  * (N, K); 1: src is (K, N), i.e. the product wants src^T; kp = plane row pitch, ps = plane stride, both in elements and even; tile0 =
- * number of 32 (n) x 64 (k) output pieces, ceil(N / 32) * ceil(K / 64) each, of the entries before; table in DEVICE memory).  Covers N >= 64 and 16-byte aligned
+ * number of 32 (n) x 64 (k) output pieces, ceil(N / 32) * ceil(K / 64) each, of the entries before; table in DEVICE memory;
+ * transpose = 2: not a weight but the raw (3, cols) direction parameter of a receptive-field layer, cols % 4 == 0: dst = its
+ * column-normalised fp32 copy (3, cols) for hsp_rf_dirs_hat_bind, ceil(cols / 1024) pieces, kp and ps unused).  Covers N >= 64 and 16-byte aligned
  * activation rows (hsp_gemm_x3_supported; anything else: hsp_gemm_rows_f32); epilogues: none, bias, resid + cloud_bias.
  * Deep-K products with few tiles split K over workgroups (ws: hsp_gemm_x3_workspace_bytes) and fold in a fixed order. */
 typedef struct HspSplitDesc { const float *src; void *dst; int rows, cols, ld, transpose, kp, tile0; long long ps; } HspSplitDesc;
