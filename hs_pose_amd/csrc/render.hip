@@ -302,6 +302,9 @@ struct BoxAcc {
     }
 };
 
+// GUARD: a label without a pixel gets the box (0, 0, 1, 1) -- a positive side for hsp_dzi_windows -- instead of zeros; the
+// count stays 0.  One body for hsp_label_boxes and hsp_label_boxes_guarded: where the count is positive they write the same bits.
+template <bool GUARD>
 __global__ __launch_bounds__(1024) void label_boxes_kernel(const uint8_t* __restrict__ labels, const int32_t* __restrict__ frame_id,
                                                            const int32_t* __restrict__ label, int F, int H, int W,
                                                            int32_t* __restrict__ boxes, int32_t* __restrict__ count) {
@@ -347,7 +350,8 @@ __global__ __launch_bounds__(1024) void label_boxes_kernel(const uint8_t* __rest
         for (int w = 1; w < 16; ++w) acc.join(s_acc[w]);
         int32_t* __restrict__ b = boxes + (size_t)j * 4;
         const bool any = acc.cnt > 0;
-        b[0] = any ? acc.x1 : 0; b[1] = any ? acc.y1 : 0; b[2] = any ? acc.x2 + 1 : 0; b[3] = any ? acc.y2 + 1 : 0;
+        b[0] = any ? acc.x1 : 0; b[1] = any ? acc.y1 : 0; b[2] = any ? acc.x2 + 1 : (GUARD ? 1 : 0);
+        b[3] = any ? acc.y2 + 1 : (GUARD ? 1 : 0);
         count[j] = acc.cnt;
     }
 }
@@ -438,9 +442,21 @@ extern "C" int hsp_render_depth_f32(const float* verts, int V, const int32_t* tr
                         depth, labels, ws, ws_bytes, stream);
 }
 
+template <bool GUARD>
+static int label_boxes(const uint8_t* labels, const int32_t* frame_id, const int32_t* label, int n, int F, int H, int W,
+                       int32_t* boxes, int32_t* count, hspStream_t stream) {
+    if (!labels || !frame_id || !label || !boxes || !count || n < 1 || n > 65535 || !frame_sizes_ok(F, H, W)) return HSP_ERR_BAD_ARG;
+    hipLaunchKernelGGL(label_boxes_kernel<GUARD>, dim3(n), dim3(1024), 0, as_stream(stream), labels, frame_id, label, F, H, W, boxes,
+                       count);
+    return check_launch();
+}
+
 extern "C" int hsp_label_boxes(const uint8_t* labels, const int32_t* frame_id, const int32_t* label, int n, int F, int H, int W,
                                int32_t* boxes, int32_t* count, hspStream_t stream) {
-    if (!labels || !frame_id || !label || !boxes || !count || n < 1 || n > 65535 || !frame_sizes_ok(F, H, W)) return HSP_ERR_BAD_ARG;
-    hipLaunchKernelGGL(label_boxes_kernel, dim3(n), dim3(1024), 0, as_stream(stream), labels, frame_id, label, F, H, W, boxes, count);
-    return check_launch();
+    return label_boxes<false>(labels, frame_id, label, n, F, H, W, boxes, count, stream);
+}
+
+extern "C" int hsp_label_boxes_guarded(const uint8_t* labels, const int32_t* frame_id, const int32_t* label, int n, int F, int H,
+                                       int W, int32_t* boxes, int32_t* count, hspStream_t stream) {
+    return label_boxes<true>(labels, frame_id, label, n, F, H, W, boxes, count, stream);
 }

@@ -6,6 +6,7 @@ return code.  No CPU fallback: a non-GPU tensor is an error.
 """
 import ctypes
 import functools
+import math
 import os
 import weakref
 
@@ -3135,20 +3136,123 @@ def render_depth(verts, tris, mesh, mesh_id, frame_id, label, RT, scale, camK64,
     return depth, labels
 
 
+def _outs(name, spec, out, device):
+    """the outputs of a call by name: ``spec`` name -> (shape, dtype); a tensor of ``out`` (a dict, or None) is taken where it
+    is a contiguous device tensor of that dtype and element count, every other one is made fresh"""
+    got = {}
+    for k, (shape, dtype) in spec.items():
+        t = None if out is None else out.get(k)
+        if t is None:
+            t = torch.empty(shape, dtype=dtype, device=device)
+        elif not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype and t.is_contiguous()
+                  and t.numel() == math.prod(shape)):
+            raise HspError(f"{name}: out[{k!r}] expects a contiguous {tuple(shape)} {dtype} GPU tensor, got "
+                           f"{tuple(t.shape) if isinstance(t, torch.Tensor) else type(t)}")
+        got[k] = t
+    return got
+
+
+def _label_boxes(name, labels_img, frame_id, label, out=None):
+    """what ``label_boxes`` and ``label_boxes_guarded`` share: the entry point hsp_<name> on labels_img (F,H,W) uint8"""
+    labels_img = _req(labels_img, torch.uint8, f"{name}.labels_img")
+    frame_id, label, n = _req_instances(name, frame_id, label)
+    if labels_img.dim() != 3 or labels_img.numel() == 0 or labels_img.shape[1] * labels_img.shape[2] >= 2 ** 31 or n < 1:
+        raise HspError(f"{name}: expects labels_img (F,H,W) uint8 with H*W < 2^31 and n >= 1, got {tuple(labels_img.shape)}, n {n}")
+    F, H, W = labels_img.shape
+    boxes, count = _outs(name, {"boxes": ((n, 4), torch.int32), "count": ((n,), torch.int32)},
+                         None if out is None else dict(boxes=out[0], count=out[1]), labels_img.device).values()
+    _run(f"hsp_{name}", (_p(labels_img), _p(frame_id), _p(label), n, F, H, W, _p(boxes), _p(count), _stream()),
+         key=f"n{n}", abytes=n * (H * W + 28))
+    return boxes, count
+
+
 def label_boxes(labels_img, frame_id, label):
     """the tight box and the pixel count of each instance's label (include/hsp.h: hsp_label_boxes): labels_img (F,H,W) uint8,
     frame_id / label (n,) int32 -> (boxes (n,4) int32 = (x1, y1, x2, y2) with x2, y2 exclusive, count (n,) int32); zeros where
     the frame holds no pixel of the label."""
-    labels_img = _req(labels_img, torch.uint8, "label_boxes.labels_img")
-    frame_id, label, n = _req_instances("label_boxes", frame_id, label)
-    if labels_img.dim() != 3 or labels_img.numel() == 0 or labels_img.shape[1] * labels_img.shape[2] >= 2 ** 31 or n < 1:
-        raise HspError(f"label_boxes: expects labels_img (F,H,W) uint8 with H*W < 2^31 and n >= 1, got {tuple(labels_img.shape)}, n {n}")
-    F, H, W = labels_img.shape
-    boxes = torch.empty(n, 4, dtype=torch.int32, device=labels_img.device)
-    count = torch.empty(n, dtype=torch.int32, device=labels_img.device)
-    _run("hsp_label_boxes", (_p(labels_img), _p(frame_id), _p(label), n, F, H, W, _p(boxes), _p(count), _stream()),
-         key=f"n{n}", abytes=n * (H * W + 28))
-    return boxes, count
+    return _label_boxes("label_boxes", labels_img, frame_id, label)
+
+
+def label_boxes_guarded(labels_img, frame_id, label, out=None):
+    """``label_boxes`` for boxes that stay on the device (include/hsp.h: hsp_label_boxes_guarded): where the frame holds no
+    pixel of the label the box is (0, 0, 1, 1) -- a finite window for ``dzi_windows_device`` -- and the count 0.
+    ``out`` = (boxes (n,4), count (n,)) int32: caller-owned outputs."""
+    return _label_boxes("label_boxes_guarded", labels_img, frame_id, label, out)
+
+
+SCENE_PARAMS = ("size_lo", "size_hi", "distance_lo", "distance_hi", "elev_lo", "elev_hi", "roll", "W", "H", "fx", "fy", "cx0", "cy0")
+
+
+def scene_draw(key, ext, cls, mean_shape, sym, params, distractors, M, out=None):
+    """M synthetic items and their distractors drawn on the device under ``key`` (include/hsp.h: hsp_scene_draw).  ext
+    (n_mesh,3) float64, cls (n_mesh,), mean_shape (n_mesh,3) and sym (n_mesh,4) fp32: one row per mesh, on the device; params:
+    the 13 host numbers of ``SCENE_PARAMS`` in that order; distractors (D,8) float64 on the device, or None
+    -> a dict: the render's instance rows mesh_id, frame_id, label (n,) int32, RT (n,4,4), scale (n,3) fp32 with
+    n = M (1 + D), the item rows obj_id (M,), gt_R (M,3,3), gt_t, gt_s, mean_shape (M,3), sym (M,4), nocs_scale (M,), aug_bb,
+    aug_rt_t (M,3), aug_rt_r (M,3,3) fp32, and angles (M,6) float64 = (yaw, elev, roll, ax, ay, az) degrees.  ``out``: a dict
+    of caller-owned tensors under those names; the ones it lacks are made fresh."""
+    key = _req_key(key, "scene_draw")
+    ext = _req(ext, torch.float64, "scene_draw.ext")
+    cls, mean_shape, sym = (_req(t, torch.float32, f"scene_draw.{n}") for t, n in ((cls, "cls"), (mean_shape, "mean_shape"),
+                                                                                  (sym, "sym")))
+    n_mesh, M = ext.shape[0] if ext.dim() == 2 else 0, int(M)
+    if n_mesh < 1 or tuple(ext.shape) != (n_mesh, 3) or cls.numel() != n_mesh or tuple(mean_shape.shape) != (n_mesh, 3) \
+            or tuple(sym.shape) != (n_mesh, 4):
+        raise HspError(f"scene_draw: expects ext (n_mesh,3) f64, cls (n_mesh,), mean_shape (n_mesh,3), sym (n_mesh,4), got "
+                       f"{tuple(ext.shape)}, {tuple(cls.shape)}, {tuple(mean_shape.shape)}, {tuple(sym.shape)}")
+    D = 0
+    if distractors is not None:
+        distractors = _req(distractors, torch.float64, "scene_draw.distractors")
+        if distractors.dim() != 2 or distractors.shape[1] != 8:
+            raise HspError(f"scene_draw: distractors expects (D,8) float64, got {tuple(distractors.shape)}")
+        D = distractors.shape[0]
+    params = [float(v) for v in params]
+    if len(params) != len(SCENE_PARAMS) or not all(math.isfinite(v) for v in params) \
+            or not (0 < params[0] <= params[1] and 0 < params[2] <= params[3]):
+        raise HspError(f"scene_draw: params expects {len(SCENE_PARAMS)} finite numbers {SCENE_PARAMS} with 0 < lo <= hi for size and "
+                       f"distance, got {params}")
+    if not 1 <= M <= 65535 or D > 254:
+        raise HspError(f"scene_draw: M {M} / D {D} out of range (1 <= M <= 65535, D <= 254)")
+    n, f32 = M * (1 + D), torch.float32
+    o = _outs("scene_draw", {"mesh_id": ((n,), torch.int32), "frame_id": ((n,), torch.int32), "label": ((n,), torch.int32),
+                             "RT": ((n, 4, 4), f32), "scale": ((n, 3), f32), "obj_id": ((M,), f32), "gt_R": ((M, 3, 3), f32),
+                             "gt_t": ((M, 3), f32), "gt_s": ((M, 3), f32), "mean_shape": ((M, 3), f32), "sym": ((M, 4), f32),
+                             "nocs_scale": ((M,), f32), "aug_bb": ((M, 3), f32), "aug_rt_t": ((M, 3), f32),
+                             "aug_rt_r": ((M, 3, 3), f32), "angles": ((M, 6), torch.float64)}, out, ext.device)
+    _run("hsp_scene_draw", (_p(key), _p(ext), _p(cls), _p(mean_shape), _p(sym), (ctypes.c_double * len(params))(*params),
+                            _p(distractors if D else None), M, n_mesh, D, *(_p(t) for t in o.values()), _stream()),
+         key=f"M{M}D{D}", abytes=n * 88 + M * 216 + 16)
+    return o
+
+
+def mesh_sample(verts, tris, mesh, cum, ext, mesh_id, scale, key, n_model, out=None):
+    """``n_model`` surface points of each item's mesh in units of the object's diagonal, drawn on the device under ``key``
+    (include/hsp.h: hsp_mesh_sample): verts / tris / mesh a packed mesh set, cum (T,) float64 its running triangle areas per
+    mesh (``render.MeshSet.cum_area``), ext (n_mesh,3) float64, mesh_id (M,) int32 and scale (M,3) fp32 the items' rows
+    -> model_point (M, n_model, 3) fp32 (``out`` when given)."""
+    key = _req_key(key, "mesh_sample")
+    verts = _req(verts, torch.float32, "mesh_sample.verts")
+    tris = _req(tris, torch.int32, "mesh_sample.tris")
+    mesh = _req(mesh, torch.int32, "mesh_sample.mesh")
+    cum = _req(cum, torch.float64, "mesh_sample.cum")
+    ext = _req(ext, torch.float64, "mesh_sample.ext")
+    mesh_id = _req(mesh_id, torch.int32, "mesh_sample.mesh_id")
+    scale = _req(scale.detach(), torch.float32, "mesh_sample.scale")
+    M, n_model = mesh_id.numel(), int(n_model)
+    if verts.dim() != 2 or verts.shape[1] != 3 or tris.dim() != 2 or tris.shape[1] != 3 or mesh.dim() != 2 or mesh.shape[1] != 4 \
+            or 0 in (verts.shape[0], tris.shape[0], mesh.shape[0]) or cum.shape != (tris.shape[0],) \
+            or tuple(ext.shape) != (mesh.shape[0], 3) or mesh_id.dim() != 1 or tuple(scale.shape) != (M, 3):
+        raise HspError(f"mesh_sample: expects verts (V,3), tris (T,3), mesh (n_mesh,4), cum (T,), ext (n_mesh,3), mesh_id (M,), scale "
+                       f"(M,3), got {tuple(verts.shape)}, {tuple(tris.shape)}, {tuple(mesh.shape)}, {tuple(cum.shape)}, "
+                       f"{tuple(ext.shape)}, {tuple(mesh_id.shape)}, {tuple(scale.shape)}")
+    if not 1 <= M <= 65535 or not 1 <= n_model <= 2 ** 20:
+        raise HspError(f"mesh_sample: M {M} / n_model {n_model} out of range (1 <= M <= 65535, 1 <= n_model <= 2^20)")
+    model = _outs("mesh_sample", {"model_point": ((M, n_model, 3), torch.float32)}, None if out is None else dict(model_point=out),
+                  verts.device)["model_point"]
+    _run("hsp_mesh_sample", (_p(verts), verts.shape[0], _p(tris), tris.shape[0], _p(mesh), mesh.shape[0], _p(cum), _p(ext),
+                             _p(mesh_id), _p(scale), _p(key), M, n_model, _p(model), _stream()),
+         key=f"M{M}n{n_model}", abytes=M * n_model * (12 + 36 + 12))
+    return model
 
 
 def _to_pcl(name, depth, each, camK64, src, choose):

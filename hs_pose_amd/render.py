@@ -6,6 +6,7 @@ from meshes and poses"; csrc/render.hip), in the formats the front ends read: ui
 ``render_frames``   instances of a mesh set under poses and scales -> (depth, labels)
 ``label_boxes``     the tight box and pixel count of each instance's label, on the device
 ``SyntheticItems``  seeded training items -- pose, size, rendered frame, ground truth -- as the two dicts ``train.FrameTrainStep`` takes
+``SceneSource``     the same items drawn on the device under a step's key: no host generator, no upload, no read-back
 
 There is no CPU path: the frames are made by the kernels or not at all.  The numpy statement the kernels are held to lives with
 the tests (tests/_render_ref.py)."""
@@ -168,9 +169,33 @@ class MeshSet:
         self.verts = torch.from_numpy(np.concatenate([v for v, _ in self.meshes])).to(self.device)
         self.tris = torch.from_numpy(np.concatenate([f for _, f in self.meshes])).to(self.device)
         self.table = torch.tensor(rows, dtype=torch.int32).to(self.device)
+        self._cum = self._ext = None
 
     def __len__(self):
         return len(self.meshes)
+
+    @property
+    def cum_area(self):
+        """(T,) float64 on the device, built on first use: per mesh the running sum of its triangles' areas
+        0.5 |(b - a) x (c - a)| in float64, restarting at each mesh (include/hsp.h: hsp_mesh_sample).  A mesh without area is
+        refused, as ``sample_points`` refuses it."""
+        if self._cum is None:
+            cums = []
+            for k, (v, f) in enumerate(self.meshes):
+                a, b, c = (v[f[:, i]].astype(np.float64) for i in range(3))
+                cum = np.cumsum(0.5 * np.linalg.norm(np.cross(b - a, c - a), axis=1))
+                if not cum[-1] > 0:
+                    raise ValueError(f"MeshSet.cum_area: mesh {k} has no area")
+                cums.append(cum)
+            self._cum = torch.from_numpy(np.concatenate(cums)).to(self.device)
+        return self._cum
+
+    @property
+    def extents(self):
+        """(n_mesh,3) float64 on the device, built on first use: ``extent(k)`` of every mesh"""
+        if self._ext is None:
+            self._ext = torch.from_numpy(np.stack([self.extent(k) for k in range(len(self))])).to(self.device)
+        return self._ext
 
     def extent(self, k):
         """(3,) float64: max - min of mesh k's vertices along each axis, in model units"""
@@ -349,3 +374,74 @@ class SyntheticItems:
                      aug_bb=up(aug_bb), aug_rt_t=up(aug_t), aug_rt_r=up(aug_r))
         self.last = dict(RT=RT, scale=scale, mesh_ids=mesh_ids, sizes=dims)
         return frames, items
+
+
+class SceneSource:
+    """``SyntheticItems`` with every draw made on the device under a step's key (include/hsp.h: "scenes drawn under a step's
+    key"): the same arguments without ``rng``, the same distributions, not the same draws.  The per-mesh tables, the camera and
+    the distractor table go up once, here.
+
+    ``draw(M, key, out=None)``: key the (2,) int64 device tensor {seed, call} of a ``pc_sample.DeviceSampler`` -> the two dicts
+    ``train.FrameTrainStep`` takes, with ``bboxes_d`` (M,4) int32 on the device -- ``ops.label_boxes_guarded``'s, so a label
+    without a pixel has the box (0, 0, 1, 1) and the front end rejects it by count --, no ``bboxes_xyxy``, ``inst_ids`` all 1 on
+    the device and K (1,9) float64 on the device.  Four steps: ``ops.scene_draw`` -> ``ops.mesh_sample`` ->
+    ``render_frames(out=...)`` -> ``ops.label_boxes_guarded``.  ``out``: ``buffers(M)``, with any of its tensors replaced
+    by the caller's own static ones; given it the call allocates no output, uploads nothing, reads nothing back and can be
+    captured.
+    ``last`` keeps the device tensors of the last draw (the render's instance rows, angles, count among them)."""
+
+    def __init__(self, meshes, class_ids, mean_shapes, sym_infos, K, H, W, distance=(0.6, 1.4), size=(0.08, 0.3), n_model=1024,
+                 elev=(10.0, 60.0), roll=10.0, distractors=()):
+        dev = meshes.device
+        host = [np.asarray(class_ids, dtype=np.float32).reshape(-1), np.asarray(mean_shapes, dtype=np.float32).reshape(-1, 3),
+                np.asarray(sym_infos, dtype=np.float32).reshape(-1, 4)]
+        if not len(meshes) == len(host[0]) == len(host[1]) == len(host[2]):
+            raise ValueError("SceneSource: class_ids, mean_shapes and sym_infos expect one row per mesh")
+        self.meshes, self.H, self.W, self.n_model = meshes, int(H), int(W), int(n_model)
+        K = np.asarray(K, dtype=np.float64).reshape(3, 3)
+        distance, size, elev = tuple(distance), tuple(size), tuple(elev)
+        if not (0 < distance[0] <= distance[1] and 0 < size[0] <= size[1]):
+            raise ValueError(f"SceneSource: distance {distance} / size {size} expect 0 < lo <= hi")
+        self.params = (*size, *distance, *elev, float(roll), self.W, self.H, K[0, 0], K[1, 1], K[0, 2], K[1, 2])
+        if len(distractors) > 254:
+            raise ValueError("SceneSource: at most 254 distractors (labels 2 ... 255)")
+        rows = []
+        for spec in distractors:
+            if not 0 <= int(spec["mesh"]) < len(meshes):
+                raise ValueError(f"SceneSource: distractor mesh {spec['mesh']} outside [0, {len(meshes)})")
+            rows.append([int(spec["mesh"]), *spec["size"], *spec.get("offset", (0, 0, 0)), 1.0 if spec.get("rest", False) else 0.0])
+        self.D = len(rows)
+        self.cls, self.mean_shapes, self.sym_infos = (torch.from_numpy(a).to(dev) for a in host)
+        self.distractors = torch.tensor(rows, dtype=torch.float64).reshape(-1, 8).to(dev) if rows else None
+        self.K = torch.from_numpy(K.reshape(1, 9).copy()).to(dev)
+        self.ext, self.cum = meshes.extents, meshes.cum_area            # (built and uploaded here, not inside a capture)
+        self.last = None
+
+    def buffers(self, M):
+        """every device tensor one ``draw(M)`` writes, by name: what ``out`` may hold"""
+        dev, M = self.meshes.device, int(M)
+        n, f32, i32 = M * (1 + self.D), torch.float32, torch.int32
+        spec = dict(mesh_id=((n,), i32), frame_id=((n,), i32), label=((n,), i32), RT=((n, 4, 4), f32), scale=((n, 3), f32),
+                    obj_id=((M,), f32), gt_R=((M, 3, 3), f32), gt_t=((M, 3), f32), gt_s=((M, 3), f32), mean_shape=((M, 3), f32),
+                    sym=((M, 4), f32), nocs_scale=((M,), f32), aug_bb=((M, 3), f32), aug_rt_t=((M, 3), f32),
+                    aug_rt_r=((M, 3, 3), f32), angles=((M, 6), torch.float64), model_point=((M, self.n_model, 3), f32),
+                    depth=((M, self.H, self.W), torch.uint16), labels=((M, self.H, self.W), torch.uint8), bboxes_d=((M, 4), i32),
+                    count=((M,), i32))
+        out = {k: torch.zeros(shape, dtype=dtype, device=dev) for k, (shape, dtype) in spec.items()}
+        out["inst_ids"] = torch.ones(M, dtype=i32, device=dev)
+        return out
+
+    ITEM_KEYS = ("obj_id", "gt_R", "gt_t", "gt_s", "mean_shape", "sym", "model_point", "nocs_scale", "aug_bb", "aug_rt_t", "aug_rt_r")
+
+    def draw(self, M, key, out=None):
+        M, ms = int(M), self.meshes
+        o = self.buffers(M) if out is None else dict(out)
+        o.update(ops.scene_draw(key, self.ext, self.cls, self.mean_shapes, self.sym_infos, self.params, self.distractors, M, out=o))
+        ops.mesh_sample(ms.verts, ms.tris, ms.table, self.cum, self.ext, o["mesh_id"][:M], o["scale"][:M], key, self.n_model,
+                        out=o["model_point"])
+        render_frames(ms, o["mesh_id"], o["RT"], o["scale"], self.K, self.H, self.W, frame_ids=o["frame_id"], labels=o["label"],
+                      F=M, out=(o["depth"], o["labels"]))
+        ops.label_boxes_guarded(o["labels"], o["frame_id"][:M], o["label"][:M], out=(o["bboxes_d"], o["count"]))
+        self.last = o
+        frames = dict(depth=o["depth"], labels=o["labels"], inst_ids=o["inst_ids"], bboxes_d=o["bboxes_d"], K=self.K)
+        return frames, {k: o[k] for k in self.ITEM_KEYS}

@@ -13,6 +13,8 @@ optimizer of ``hs_pose_amd.solver``:
 
 ``FrameTrainStep`` is that step started from raw frames: the training loader's front end (``pc_sample.train_batch_to_pcl``), the
 choice of the kept items (``pc_sample.train_batch_select``) and ``graph.GraphedTrainStep``'s body as ONE replay.
+``RenderedTrainStep`` is ``FrameTrainStep`` with the frames themselves drawn and rendered at the head of that replay
+(``render.SceneSource``): a synthetic training step as a pure function of the sampler's {seed, call} and the mesh set.
 """
 import math
 
@@ -210,6 +212,7 @@ class FrameTrainStep:
         dzi = (float(FLAGS.DZI_PAD_SCALE), float(FLAGS.DZI_SCALE_RATIO), float(FLAGS.DZI_SHIFT_RATIO))
 
         def front_end():
+            self._scene()
             if self.draws is not None:                          # the windows of this replay, drawn under its key
                 ops.dzi_windows_device(self.bboxes_d, self.sampler.key, self.H, self.W, self.out_size, *dzi, out=self.xf)
             PC, self.status = pc_sample.train_batch_to_pcl(self.depth, self.labels, self.inst_ids, self.xf, None, self.K,
@@ -228,6 +231,9 @@ class FrameTrainStep:
                                         apply=apply, horizon=horizon, gate_info=self.info if apply == "graph" else None,
                                         accumulate=accumulate, global_step=global_step)
         self.sampler.set_state(state)
+
+    def _scene(self):
+        """what the captured prologue begins with: nothing here -- the frames are loaded (``RenderedTrainStep`` draws them)"""
 
     @staticmethod
     def _K_rows(K):
@@ -294,3 +300,39 @@ class FrameTrainStep:
             return False
         self.graphed.apply()
         return True
+
+
+class RenderedTrainStep(FrameTrainStep):
+    """``FrameTrainStep`` under device draws whose M items are not loaded but DRAWN: the captured prologue begins with
+    ``source.draw(M, key, out=<the step's static buffers>)`` (``render.SceneSource``: the scene under the replay's key, the
+    model points, the render, the guarded label boxes), then ``hsp_dzi_windows`` on those boxes, ``train_batch_to_pcl`` and
+    ``train_batch_select`` as there, then ``GraphedTrainStep``'s body.  ``run()`` is ``sampler.advance()`` and one replay, then
+    ``FrameTrainStep``'s check and apply rules, word for word (``apply='graph'`` included: ``run(check=False)`` is then safe and
+    never waits).  No generator of the host's is touched, nothing is uploaded but the key, nothing is read back unless ``check``
+    asks; equal sampler states give equal steps.  ``sel``, ``info``, ``status`` and ``batch`` are ``FrameTrainStep``'s; ``scene``
+    holds every static tensor of the drawn scene (``SceneSource.buffers``).  There is nothing to ``load``.
+
+    An item whose label has no pixel in its frame (hidden behind a distractor, say) gets the guarded box (0, 0, 1, 1): its
+    window is finite and empty, the front end rejects it by count and the selection moves on to a spare.
+
+    The remaining arguments are ``FrameTrainStep``'s; the draws are always the device's, so ``DZI_TYPE`` other than 'uniform'
+    raises as it does there."""
+
+    def __init__(self, network, optimizer, source, M, keep, sampler=None, **kw):
+        if "draws" in kw:
+            raise ValueError("RenderedTrainStep: the draws are always the device's; pass sampler=")
+        dev = source.meshes.device
+        sampler = pc_sample.draws_only(pc_sample.resolve_sampler("device" if sampler is None else sampler, dev), "RenderedTrainStep")
+        if sampler is None:
+            raise ValueError("RenderedTrainStep: expects a device sampler")
+        self.source, self.scene = source, source.buffers(M)
+        frames, items = source.draw(M, sampler.key, out=self.scene)      # (eager: what the static buffers start from)
+        super().__init__(network, optimizer, frames, items, keep, sampler=sampler, draws=sampler, **kw)
+
+    def _scene(self):
+        if self.scene["depth"] is not self.depth:                        # first call: draw into the step's own static buffers
+            self.scene.update(depth=self.depth, labels=self.labels, bboxes_d=self.bboxes_d, inst_ids=self.inst_ids, **self.items)
+        self.source.draw(self.M, self.sampler.key, out=self.scene)
+
+    def load(self, frames=None, items=None):
+        raise TypeError("RenderedTrainStep: the items are drawn inside the replay; there is nothing to load")

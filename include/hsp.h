@@ -1435,6 +1435,8 @@ int hsp_pose_augment(const float *PC, const float *gt_R, const float *gt_t, cons
  *   augmentation of cloud b:           j = 0x81000000 | b        (b < 2^24)
  *   DZI window of item i:              j = 0x82000000 | i        (i < 65535)
  *   Dropout of site s:                 j = 0x83000000 | s        (s < 2^24)
+ *   scene of item i:                   j = 0x84000000 | i        (i < 2^24; section "scenes drawn under a step's key")
+ *   model points of item i:            j = 0x85000000 | i        (i < 2^24; the same section)
  * A stream of words under kj and a tag T is  word(i) = absorb(absorb(kj, T), i), i = 0, 1, ... (uint32).
  * A word w becomes an fp32 uniform as  float(w >> 8) * 2^-24  and a float64 uniform as  double(w) * 2^-32: both conversions are
  * exact and give values in [0, 1).
@@ -1641,6 +1643,86 @@ int hsp_render_depth_f32(const float *verts, int V, const int32_t *tris, int T, 
                          float *depth, uint8_t *labels, void *ws, size_t ws_bytes, hspStream_t stream);
 int hsp_label_boxes(const uint8_t *labels, const int32_t *frame_id, const int32_t *label, int n, int F, int H, int W,
                     int32_t *boxes, int32_t *count, hspStream_t stream);
+
+/* ---- scenes drawn under a step's key --------------------------------------------------------------------------------------
+ * The last host draw of a synthetic training step, made on the device: the poses, sizes, ground truth and augmentation rows of M
+ * items and of D distractors per item (hsp_scene_draw) and the items' model points (hsp_mesh_sample), as keyed draws of the
+ * step -- the rules of that section hold: plain C++, vector stores, uint32 arithmetic for the draws, no atomics, no workspace,
+ * every output slot has one writer, key the DEVICE pointer to {seed, call}.  The same DISTRIBUTIONS as render.SyntheticItems
+ * draws on numpy's generator, not the same draws.  Two purposes join the table of that section:
+ *   scene of item i:                   j = 0x84000000 | i        (i < 2^24), tag 0xfffffff9
+ *   model points of item i:            j = 0x85000000 | i        (i < 2^24), tag 0xfffffff8
+ * All real arithmetic is float64, every operation named below ONE rounding in the order written, nothing contracted; an fp32
+ * input enters by its exact conversion; u_q = the float64 uniform of word(q) of the item's stream.
+ *
+ * hsp_scene_draw.  Tables on the device, one row per mesh: ext (n_mesh,3) DOUBLE the extent of the mesh along each axis in
+ * model units, cls (n_mesh) fp32 its category, mean_shape (n_mesh,3), sym (n_mesh,4) fp32.  params: 13 doubles ON THE HOST, read
+ * when the call is made (a captured launch keeps them): size lo, hi (metres, of the LARGEST side), distance lo, hi (metres),
+ * elev lo, hi, roll (degrees), W, H (pixels), fx, fy, cx0, cy0 (the camera's K0, K4, K2, K5).  distractors (D,8) DOUBLE on the
+ * device = (mesh, sx, sy, sz, ox, oy, oz, rest): the mesh index as a double, the size in metres, the offset in metres in the
+ * item's frame, rest != 0 "lies under the item"; not read when D == 0 (it may be NULL).  For item i:
+ *   mesh        k = (uint64(word(0)) * n_mesh) >> 32
+ *   scale       side = lo + (hi - lo) * u1;  s = (float)(side / max(ext_k)), max over the three extents; all three scale
+ *               components equal s
+ *   size        dims = ext_k * (double)s
+ *   depth       z = dlo + (dhi - dlo) * u2
+ *   centre      px = (W - 1) * u3,  py = (H - 1) * u4: the pixel the centre projects to, inside the frame
+ *   t           ((z * (px - cx0)) / fx, (z * (py - cy0)) / fy, z), rounded to fp32
+ *   angles      degrees: yaw = 360 * u5, elev = elo + (ehi - elo) * u6, roll = (-r) + (2 * r) * u7
+ *   R           Rz(roll) Rx(180 + elev) Ry(yaw), with Rx(a) = [1 0 0; 0 c -s; 0 s c], Ry(a) = [c 0 s; 0 1 0; -s 0 c],
+ *               Rz(a) = [c -s 0; s c 0; 0 0 1], c and s the float64 cosine and sine of a * (pi / 180) (the constant pi / 180
+ *               rounded once); the two products left to right, an entry of a product (a0 * b0 + a1 * b1) + a2 * b2 with the
+ *               zeros and ones multiplied like any other entry; the result rounded to fp32
+ *   aug_bb      0.8 + 0.4 * u8, u9, u10, rounded to fp32
+ *   aug_rt_r    Rz(az) Ry(ay) Rx(ax) of ax, ay, az = -15 + 30 * u11, u12, u13 degrees, products as above, rounded to fp32
+ *   aug_rt_t    (-50 + 100 * u14, u15, u16) / 1000, rounded to fp32
+ * Everything else comes from the ROUNDED fp32 R, t and s (the ground truth is the rendered pose exactly): gt_R = R, gt_t = t,
+ * nocs_scale = (float) sqrt((d0 * d0 + d1 * d1) + d2 * d2) over dims, gt_s = (float)(dims - (double) mean_shape_k), obj_id,
+ * mean_shape and sym the rows of mesh k.  Distractor d of item i, with m its mesh and size its (sx, sy, sz):
+ *   scale = (float)(size / ext_m) component by component;  off = (ox, oy, oz), with rest  off_y = off_y - (0.5 * dims_y +
+ *   0.5 * size_y);  t_d = (float)(((R_r0 * off_0 + R_r1 * off_1) + R_r2 * off_2) + t_r), r = 0, 1, 2;  its rotation is R.
+ *   A mesh entry outside [0, n_mesh) or not finite: mesh_id -1 and scale 0 -- the renderer draws nothing for it.
+ * Outputs, n = M * (1 + D) instance rows with the items first, then distractor 0's M rows, then distractor 1's, ...: mesh_id,
+ * frame_id (= i), label (1 for an item, 2 + d for distractor d) (n) int32, rt (n,16) fp32 row-major with the fourth row
+ * (0, 0, 0, 1), scale (n,3) fp32: what hsp_render_depth_u16 reads.  Item rows (M rows each) fp32: obj_id (M), gt_R (M,9),
+ * gt_t, gt_s, mean_shape_out (M,3), sym_out (M,4), nocs_scale (M), aug_bb, aug_rt_t (M,3), aug_rt_r (M,9); angles (M,6) DOUBLE
+ * = (yaw, elev, roll, ax, ay, az) in degrees -- the draws themselves, because sine and cosine may differ in the last place
+ * between two libraries: two implementations agree on angles bit for bit and on R and aug_rt_r to one fp32 rounding.
+ * A NULL pointer, M outside 1..65535, n_mesh < 1, D outside 0..254, a parameter that is not finite, lo > hi or lo <= 0 for size
+ * or distance: HSP_ERR_BAD_ARG before any launch.
+ *
+ * hsp_mesh_sample: model_point (M, n_model, 3) fp32, n_model surface points of each item's mesh in units of the object's
+ * diagonal, one lane per point.  verts, tris, mesh: the packed mesh set of the renderer's section; cum (T) DOUBLE: per mesh the
+ * running sum of its triangles' areas 0.5 * |(b - a) x (c - a)|, restarting at each mesh's first triangle (made once on the
+ * host in float64; a mesh without area is refused there); ext as above; mesh_id (M) int32 and scale (M,3) fp32: the first M
+ * rows hsp_scene_draw wrote, or the caller's own.  For point n of item i, with k = mesh_id[i], u0, u1, u2 the float64 uniforms
+ * of word(3 n), word(3 n + 1), word(3 n + 2) of the model-point stream of item i:
+ *   triangle    x = u0 * cum_last (the mesh's last entry); the first triangle of mesh k with cum > x, found by bisection, the
+ *               last one where there is none -- searchsorted on the right side, so a triangle without area is never picked
+ *   point       if u1 + u2 > 1: u1 = 1 - u1, u2 = 1 - u2 (reflection: no square root, no transcendental);
+ *               p = (a + u1 * (b - a)) + u2 * (c - a) per component, a, b, c the triangle's vertices in its row's order
+ *   output      dims_c = ext_k,c * (double) scale_c;  diag = sqrt((d0 * d0 + d1 * d1) + d2 * d2) -- the float64 value whose
+ *               rounding is hsp_scene_draw's nocs_scale, made again by the same operations, not passed through memory;
+ *               model_point[i,n,c] = (float)((p_c * (double) scale_c) / diag)
+ * A mesh_id outside [0, n_mesh), a mesh row that leaves verts or tris, or a vertex index outside its mesh gives a zero point:
+ * nothing is read out of bounds.  A NULL pointer, V, T, n_mesh < 1, M outside 1..65535, n_model outside 1..2^20:
+ * HSP_ERR_BAD_ARG.
+ *
+ * hsp_label_boxes_guarded: hsp_label_boxes with one clause added -- where the count is 0 the box is (0, 0, 1, 1), not zeros;
+ * the same kernel body, the same bits where the count is positive, the same limits.  For boxes that never visit the host:
+ * hsp_dzi_windows gives a row that is not finite for a box without a positive side, and a host caller keeps such boxes out.
+ * The guarded box gives a finite window that holds no pixel of the label; hsp_crop_compact then counts 0 valid pixels, the
+ * training front end rejects the item by that count (status bit 1), and hsp_batch_select moves on to a spare. */
+int hsp_scene_draw(const unsigned long long *key, const double *ext, const float *cls, const float *mean_shape, const float *sym,
+                   const double *params, const double *distractors, int M, int n_mesh, int D, int32_t *mesh_id,
+                   int32_t *frame_id, int32_t *label, float *rt, float *scale, float *obj_id, float *gt_R, float *gt_t,
+                   float *gt_s, float *mean_shape_out, float *sym_out, float *nocs_scale, float *aug_bb, float *aug_rt_t,
+                   float *aug_rt_r, double *angles, hspStream_t stream);
+int hsp_mesh_sample(const float *verts, int V, const int32_t *tris, int T, const int32_t *mesh, int n_mesh, const double *cum,
+                    const double *ext, const int32_t *mesh_id, const float *scale, const unsigned long long *key, int M,
+                    int n_model, float *model_point, hspStream_t stream);
+int hsp_label_boxes_guarded(const uint8_t *labels, const int32_t *frame_id, const int32_t *label, int n, int F, int H, int W,
+                            int32_t *boxes, int32_t *count, hspStream_t stream);
 
 #ifdef __cplusplus
 }
