@@ -657,15 +657,7 @@ extern "C" int hsp_fps_f32(const float* xyz, int B, int N, int n_samples, int32_
     if (!ws || ws_bytes < hsp_fps_workspace_bytes(B, N)) return HSP_ERR_WORKSPACE;
     hipStream_t st = as_stream(stream);
     const size_t lds = (size_t)N * 3 * sizeof(float);
-#define FPS_REG(THREADS, PPT)                                                                                          \
-    do {                                                                                                               \
-        auto kern = fps_reg_kernel<THREADS, PPT>;                                                                      \
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                                        \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                      \
-        if (e != hipSuccess) { set_last_hip_error(e); return HSP_ERR_LAUNCH; }                                         \
-        hipLaunchKernelGGL(kern, dim3(B), dim3(THREADS), lds, st, xyz, N, n_samples, sel);                             \
-        return check_launch();                                                                                         \
-    } while (0)
+#define FPS_REG(THREADS, PPT) return launch_lds(fps_reg_kernel<THREADS, PPT>, dim3(B), dim3(THREADS), lds, st, xyz, N, n_samples, sel)
     if (N <= 12288) {                                          // coordinates fit LDS (144 KB) and a few dozen registers
         if (N <= 64 * 2) FPS_REG(64, 2);
         if (N <= 256 * 2) FPS_REG(256, 2);
@@ -700,15 +692,8 @@ extern "C" int hsp_fps_levels_f32(const float* xyz, int B, int N0, int N1, int N
     if (!hsp_fps_levels_takes(N0)) return HSP_ERR_UNSUPPORTED;   // (nothing launched)
     hipStream_t st = as_stream(stream);
     const size_t lds = (size_t)N0 * 3 * sizeof(float);
-#define FPS_LV(THREADS, PPT)                                                                                           \
-    do {                                                                                                               \
-        auto kern = fps_levels_kernel<THREADS, PPT>;                                                                   \
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                                        \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                      \
-        if (e != hipSuccess) { set_last_hip_error(e); return HSP_ERR_LAUNCH; }                                         \
-        hipLaunchKernelGGL(kern, dim3(B), dim3(THREADS), lds, st, xyz, N0, N1, N2, sel1, v1, v2);                      \
-        return check_launch();                                                                                         \
-    } while (0)
+#define FPS_LV(THREADS, PPT) \
+    return launch_lds(fps_levels_kernel<THREADS, PPT>, dim3(B), dim3(THREADS), lds, st, xyz, N0, N1, N2, sel1, v1, v2)
     if (N0 <= 64 * 2) FPS_LV(64, 2);                           // (the shapes of hsp_fps_f32's register kernel)
     if (N0 <= 256 * 2) FPS_LV(256, 2);
     if (N0 <= 256 * 5) FPS_LV(256, 5);

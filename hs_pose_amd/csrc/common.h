@@ -125,11 +125,38 @@ __device__ __forceinline__ float3 unit_dir_fast(float px, float py, float pz, fl
 typedef unsigned short bf16_t;
 
 __device__ __forceinline__ float bf16_bits_to_f32(unsigned v) { return __uint_as_float(v << 16); }
-__device__ __forceinline__ unsigned f32_to_bf16_bits(float f) {            // round to nearest even; NaN stays NaN
+// round to nearest even; NaN stays NaN.  (R = bf16_t narrows the result where each case makes it: the form gemm_rows.hip's
+// epilogue stores were compiled from -- the same bits, and the register allocation its 128-row bf16 tiles were measured with)
+template <typename R = unsigned> __device__ __forceinline__ R f32_to_bf16_bits(float f) {
     unsigned u = __float_as_uint(f);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x40u;
+    if ((u & 0x7fffffffu) > 0x7f800000u) return (R)((u >> 16) | 0x40u);
     u += 0x7fffu + ((u >> 16) & 1u);
-    return u >> 16;
+    return (R)(u >> 16);
+}
+// a packed bf16 pair (one dword, the lower address in the low half) widened to two floats; two dwords to four
+__device__ __forceinline__ float2 bf16x2_to_f32(unsigned u) { return make_float2(__uint_as_float(u << 16), __uint_as_float(u & 0xffff0000u)); }
+__device__ __forceinline__ float4 bf16x4_to_f32(uint2 u) {
+    const float2 a = bf16x2_to_f32(u.x), b = bf16x2_to_f32(u.y);
+    return make_float4(a.x, a.y, b.x, b.y);
+}
+
+// The exact three-way split of an fp32 into bf16 planes, x = hi + mid + lo by truncation: hi = the top half of x, r1 = x - hi
+// (exact), mid = the top half of r1, r2 = r1 - mid (exact, <= 8 significant bits), lo = the top half of r2.  x3_split leaves
+// the remainders of a value; x3_pair packs a plane's dword of two neighbours, x3_pair(x0, x1) / (r1 of both) / (r2 of both) for
+// hi / mid / lo (one v_perm_b32: the high halves of two dwords, the lower address in the low half).
+__device__ __forceinline__ void x3_split(float x, float& r1, float& r2) {
+    r1 = x - __uint_as_float(__float_as_uint(x) & 0xffff0000u);
+    r2 = r1 - __uint_as_float(__float_as_uint(r1) & 0xffff0000u);
+}
+__device__ __forceinline__ unsigned x3_pair(float v0, float v1) {
+    return __builtin_amdgcn_perm(__float_as_uint(v1), __float_as_uint(v0), 0x07060302u);
+}
+
+// every lane gets the sum over the wave's 64 lanes (xor butterfly, fixed order)
+template <typename V> __device__ __forceinline__ V wave_sum(V v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
 }
 
 template <typename FT> struct Feat;
@@ -149,11 +176,7 @@ template <> struct Feat<bf16_t> {
     static __device__ __forceinline__ float ld(const bf16_t* p) { return bf16_bits_to_f32(*p); }
     static __device__ __forceinline__ void st(bf16_t* p, float v) { *p = (bf16_t)f32_to_bf16_bits(v); }
     static __device__ __forceinline__ void st_nt(bf16_t* p, float v) { __builtin_nontemporal_store((bf16_t)f32_to_bf16_bits(v), p); }
-    static __device__ __forceinline__ float4 ld4(const bf16_t* p) {                                  // 8-byte aligned
-        const uint2 u = *reinterpret_cast<const uint2*>(p);
-        return make_float4(__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xffff0000u), __uint_as_float(u.y << 16),
-                           __uint_as_float(u.y & 0xffff0000u));
-    }
+    static __device__ __forceinline__ float4 ld4(const bf16_t* p) { return bf16x4_to_f32(*reinterpret_cast<const uint2*>(p)); }   // 8-byte aligned
     static __device__ __forceinline__ uint2 pack4(float4 v) {
         return make_uint2(f32_to_bf16_bits(v.x) | (f32_to_bf16_bits(v.y) << 16), f32_to_bf16_bits(v.z) | (f32_to_bf16_bits(v.w) << 16));
     }

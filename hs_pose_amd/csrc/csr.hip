@@ -176,13 +176,7 @@ extern "C" int hsp_rev_build(const int32_t* idx, int B, int Nq, int Nsrc, int k,
     bool in_lds;
     const size_t lds = rev_build_lds(Nsrc, Nq, k, &in_lds);
     auto kern = in_lds ? rev_build_kernel<true> : rev_build_kernel<false>;
-    if (lds > 60 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) { set_last_hip_error(e); return HSP_ERR_LAUNCH; }
-    }
-    hipLaunchKernelGGL(kern, dim3(B), dim3(REV_THREADS), lds, as_stream(stream), idx, Nq, Nsrc, k, kstride, rev_off,
-                       rev_edge);
-    return check_launch();
+    return launch_lds(kern, dim3(B), dim3(REV_THREADS), lds, as_stream(stream), idx, Nq, Nsrc, k, kstride, rev_off, rev_edge);
 }
 
 extern "C" int hsp_rev_build_sel(const int32_t* idx, const int32_t* qsel, int qsel_stride, int B, int Nidx, int Nq, int Nsrc, int k,
@@ -197,13 +191,8 @@ extern "C" int hsp_rev_build_sel(const int32_t* idx, const int32_t* qsel, int qs
     bool in_lds;
     const size_t lds = rev_build_lds(Nsrc, Nq, k, &in_lds);
     auto kern = in_lds ? rev_build_sel_kernel<true> : rev_build_sel_kernel<false>;
-    if (lds > 60 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) { set_last_hip_error(e); return HSP_ERR_LAUNCH; }
-    }
-    hipLaunchKernelGGL(kern, dim3(B), dim3(REV_THREADS), lds, as_stream(stream), idx, qsel, qsel_stride, Nidx, Nq, Nsrc, k, kstride,
-                       rev_off, rev_edge);
-    return check_launch();
+    return launch_lds(kern, dim3(B), dim3(REV_THREADS), lds, as_stream(stream), idx, qsel, qsel_stride, Nidx, Nq, Nsrc, k, kstride,
+                      rev_off, rev_edge);
 }
 
 extern "C" int hsp_rev_build_multi(int nmaps, const int32_t* const* idx, int B, const int* Nq, const int* Nsrc, const int* k,
@@ -220,11 +209,5 @@ extern "C" int hsp_rev_build_multi(int nmaps, const int32_t* const* idx, int B, 
         lds = lds > lds_i ? lds : lds_i;
         tab.m[i] = RevBuildMap{idx[i], rev_off[i], rev_edge[i], Nq[i], Nsrc[i], k[i], kstride[i], in_lds ? 1 : 0};
     }
-    if (lds > 60 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(rev_build_multi_kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) { set_last_hip_error(e); return HSP_ERR_LAUNCH; }
-    }
-    hipLaunchKernelGGL(rev_build_multi_kernel, dim3(B, nmaps), dim3(REV_THREADS), lds, as_stream(stream), tab);
-    return check_launch();
+    return launch_lds(rev_build_multi_kernel, dim3(B, nmaps), dim3(REV_THREADS), lds, as_stream(stream), tab);
 }

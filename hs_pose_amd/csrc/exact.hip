@@ -258,15 +258,9 @@ extern "C" int hsp_bn_eval_f32(const float* x, long long R, int C, const float* 
 extern "C" int hsp_quad_outer_f32(const float* x, int B, int N, int C, float* quad, hspStream_t stream) {
     if (!x || !quad || B <= 0 || N <= 0 || C <= 0) return HSP_ERR_BAD_ARG;
     const size_t lds = (size_t)64 * (C + 1) * sizeof(float);
-    if (lds <= 64 * 1024 + 1024 && lds <= 160 * 1024) {
-        if (lds > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(quad_outer_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) { set_last_hip_error(e); return HSP_ERR_LAUNCH; }
-        }
-        hipLaunchKernelGGL(quad_outer_kernel, dim3((N + 63) / 64, B), dim3(64), lds, as_stream(stream), x, N, C, quad);
-    } else {
-        hipLaunchKernelGGL(quad_outer_wide_kernel, dim3((N + 255) / 256, B), dim3(256), 0, as_stream(stream), x, N, C, quad);
-    }
+    if (lds <= 64 * 1024 + 1024 && lds <= 160 * 1024)
+        return launch_lds(quad_outer_kernel, dim3((N + 63) / 64, B), dim3(64), lds, as_stream(stream), x, N, C, quad);
+    hipLaunchKernelGGL(quad_outer_wide_kernel, dim3((N + 255) / 256, B), dim3(256), 0, as_stream(stream), x, N, C, quad);
     return check_launch();
 }
 

@@ -1227,12 +1227,8 @@ static int fps_ids(const D* depth, int H, int W, const double* camK, int camK_ro
     if ((long long)H * W > 2147483647LL || (camK_rows != 1 && camK_rows != n) || (long long)n * S > 2147483647LL)
         return HSP_ERR_BAD_ARG;
     const size_t lds = (size_t)(src_stride < FPS_IDS_CAP ? src_stride : FPS_IDS_CAP) * 3 * sizeof(float);
-    auto kern = fps_ids_kernel<D>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) { set_last_hip_error(e); return HSP_ERR_LAUNCH; }
-    hipLaunchKernelGGL(kern, dim3(n), dim3(FPS_IDS_THREADS), lds, as_stream(stream), depth, H, W, camK, camK_rows, src, src_stride,
-                       count, S, min_pts, min_depth_pts, choose, status);
-    return check_launch();
+    return launch_lds(fps_ids_kernel<D>, dim3(n), dim3(FPS_IDS_THREADS), lds, as_stream(stream), depth, H, W, camK, camK_rows, src,
+                      src_stride, count, S, min_pts, min_depth_pts, choose, status);
 }
 
 extern "C" int hsp_fps_ids_f32(const float* depth, int H, int W, const double* camK, int camK_rows, const int32_t* src,

@@ -232,9 +232,7 @@ __global__ __launch_bounds__(ORLT_WG) void orl_tile_kernel(const FT* __restrict_
                     f[n] = make_float4(v.x, v.y, v.z, v.w);
                 }
                 else {
-                    const uint2 u2 = *reinterpret_cast<const uint2*>(rp);
-                    f[n] = make_float4(__uint_as_float(u2.x << 16), __uint_as_float(u2.x & 0xffff0000u), __uint_as_float(u2.y << 16),
-                                       __uint_as_float(u2.y & 0xffff0000u));
+                    f[n] = bf16x4_to_f32(*reinterpret_cast<const uint2*>(rp));
                 }
             }
             ORL_STAMP(3 + 3 * (i0 / PASS));
@@ -530,10 +528,8 @@ __global__ __launch_bounds__(NT) void scatter_tile_bwd_kernel(const FT* __restri
                         g01 = *reinterpret_cast<const float2*>(gout + row * gstride + j);
                         g23 = *reinterpret_cast<const float2*>(gout + row * gstride + j + 2);
                     } else {                                          // (rows of a bf16 column block: 4-byte aligned)
-                        const unsigned u0 = *reinterpret_cast<const unsigned*>(gout + row * gstride + j);
-                        const unsigned u1 = *reinterpret_cast<const unsigned*>(gout + row * gstride + j + 2);
-                        g01 = make_float2(__uint_as_float(u0 << 16), __uint_as_float(u0 & 0xffff0000u));
-                        g23 = make_float2(__uint_as_float(u1 << 16), __uint_as_float(u1 & 0xffff0000u));
+                        g01 = bf16x2_to_f32(*reinterpret_cast<const unsigned*>(gout + row * gstride + j));
+                        g23 = bf16x2_to_f32(*reinterpret_cast<const unsigned*>(gout + row * gstride + j + 2));
                     }
                     float* a = acc + m * TC + cg * 4;
                     if (g01.x != 0.f) atomicAdd(a + 0, g01.x);
@@ -678,25 +674,13 @@ static int launch_scatter_tile(int tc, const FT* gout, const float* gbc, int gst
     const size_t lds = (size_t)Nsrc * tc * 4;
     dim3 grid(C / tc, B);
     const int nt = scatter_tile_threads(tc, B, C);
-#define SC_LAUNCH_NT(TC, NT_)                                                                                      \
-    {                                                                                                              \
-        auto kern = scatter_tile_bwd_kernel<TC, MODE, FT, NT_>;                                                    \
-        if (lds > 64 * 1024) {                                                                                     \
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                                \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);              \
-            if (e != hipSuccess) { set_last_hip_error(e); return HSP_ERR_LAUNCH; }                                 \
-        }                                                                                                          \
-        hipLaunchKernelGGL(kern, grid, dim3(NT_), lds, st, gout, gbc, gstride, gbcast, idx, idx_shared, qsel, qstride, argmax, \
-                           Nsrc, Nidx, Nq, kstride, C, gfeat, accumulate, extra);                                  \
-    }
-#define SC_LAUNCH(TC)                                                                                              \
-    {                                                                                                              \
-        if (nt == 1024) SC_LAUNCH_NT(TC, 1024) else if (nt == 512) SC_LAUNCH_NT(TC, 512) else SC_LAUNCH_NT(TC, 256) \
-    }
-    if (tc == 16) SC_LAUNCH(16) else if (tc == 8) SC_LAUNCH(8) else SC_LAUNCH(4)
+#define SC_LAUNCH_NT(TC, NT_)                                                                                                  \
+    launch_lds(scatter_tile_bwd_kernel<TC, MODE, FT, NT_>, grid, dim3(NT_), lds, st, gout, gbc, gstride, gbcast, idx, idx_shared, \
+               qsel, qstride, argmax, Nsrc, Nidx, Nq, kstride, C, gfeat, accumulate, extra)
+#define SC_LAUNCH(TC) (nt == 1024 ? SC_LAUNCH_NT(TC, 1024) : nt == 512 ? SC_LAUNCH_NT(TC, 512) : SC_LAUNCH_NT(TC, 256))
+    return tc == 16 ? SC_LAUNCH(16) : tc == 8 ? SC_LAUNCH(8) : SC_LAUNCH(4);
 #undef SC_LAUNCH_NT
 #undef SC_LAUNCH
-    return check_launch();
 }
 
 // gather form of the same backward over the reverse-edge index (csr.hip): one thread per
@@ -1092,12 +1076,11 @@ __device__ __forceinline__ void grow_ld(const FT* __restrict__ p, float (&v)[VEC
         const float4 t = *reinterpret_cast<const float4*>(p);
         v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
     } else if constexpr (VEC == 2) {
-        const unsigned w = *reinterpret_cast<const unsigned*>(p);
-        v[0] = __uint_as_float(w << 16); v[1] = __uint_as_float(w & 0xffff0000u);
+        const float2 t = bf16x2_to_f32(*reinterpret_cast<const unsigned*>(p));
+        v[0] = t.x; v[1] = t.y;
     } else {
-        const uint2 w = *reinterpret_cast<const uint2*>(p);
-        v[0] = __uint_as_float(w.x << 16); v[1] = __uint_as_float(w.x & 0xffff0000u);
-        v[2] = __uint_as_float(w.y << 16); v[3] = __uint_as_float(w.y & 0xffff0000u);
+        const float4 t = bf16x4_to_f32(*reinterpret_cast<const uint2*>(p));
+        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
     }
 }
 template <typename FT, int VEC>
@@ -1109,8 +1092,7 @@ __device__ __forceinline__ void grow_st(FT* __restrict__ p, const float (&v)[VEC
     } else if constexpr (VEC == 2) {
         *reinterpret_cast<unsigned*>(p) = f32_to_bf16_bits(v[0]) | (f32_to_bf16_bits(v[1]) << 16);
     } else {
-        *reinterpret_cast<uint2*>(p) = make_uint2(f32_to_bf16_bits(v[0]) | (f32_to_bf16_bits(v[1]) << 16),
-                                                  f32_to_bf16_bits(v[2]) | (f32_to_bf16_bits(v[3]) << 16));
+        *reinterpret_cast<uint2*>(p) = Feat<bf16_t>::pack4(make_float4(v[0], v[1], v[2], v[3]));
     }
 }
 
@@ -1379,11 +1361,6 @@ static int orl_global_fwd_impl(const FT* feat, const int32_t* idx, int B, int N,
         const long long coff = (reinterpret_cast<uintptr_t>(ws) & 15) ? -1 : hsp_orl_counts_offset(B, N, k, kstride, C, ws_bytes);
         if (coff >= 0) {
             unsigned short* counts = reinterpret_cast<unsigned short*>(static_cast<char*>(ws) + coff);
-            auto kern = orl_tile_kernel<FT, 20, true>;
-            if (lds_tile > 64 * 1024) {
-                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024);
-                if (e != hipSuccess) { set_last_hip_error(e); return HSP_ERR_LAUNCH; }
-            }
             if (!tile) {
                 // a cloud under 128 points keeps the chunked form's fg (its fold order); the slab kernel then only counts
                 const int rows = chunk_rows(B, N, C);
@@ -1392,21 +1369,13 @@ static int orl_global_fwd_impl(const FT* feat, const int32_t* idx, int B, int N,
                 hipLaunchKernelGGL(orl_partial_kernel<FT>, dim3(nchunk, B), dim3(256), 0, st, feat, idx, N, k, kstride, C, argmax, part, nchunk, rows);
                 hipLaunchKernelGGL(chunk_fold_kernel, dim3((B * C + 255) / 256), dim3(256), 0, st, part, B, nchunk, C, 1.0f / (float)N, fg);
             }
-            hipLaunchKernelGGL(kern, dim3(C / ORLT_TC * B), dim3(ORLT_WG), lds_tile, st, feat, idx, B, N, C, argmax,
-                               tile ? fg : static_cast<float*>(nullptr), 1.0f / (float)N, counts);
-            return check_launch();
+            return launch_lds(orl_tile_kernel<FT, 20, true>, dim3(C / ORLT_TC * B), dim3(ORLT_WG), lds_tile, st, feat, idx, B, N, C, argmax,
+                              tile ? fg : static_cast<float*>(nullptr), 1.0f / (float)N, counts);
         }
     }
-    if (tile) {                                              // fg written by the kernel itself
-        auto kern = orl_tile_kernel<FT, 20>;
-        if (lds_tile > 64 * 1024) {                          // per device, so on every such launch (a process may drive several GPUs)
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024);
-            if (e != hipSuccess) { set_last_hip_error(e); return HSP_ERR_LAUNCH; }
-        }
-        hipLaunchKernelGGL(kern, dim3(C / ORLT_TC * B), dim3(ORLT_WG), lds_tile, st, feat, idx, B, N, C, argmax, fg, 1.0f / (float)N,
-                           static_cast<unsigned short*>(nullptr));
-        return check_launch();
-    }
+    if (tile)                                                // fg written by the kernel itself
+        return launch_lds(orl_tile_kernel<FT, 20>, dim3(C / ORLT_TC * B), dim3(ORLT_WG), lds_tile, st, feat, idx, B, N, C, argmax, fg,
+                          1.0f / (float)N, static_cast<unsigned short*>(nullptr));
     const int rows = chunk_rows(B, N, C);
     const int nchunk = (N + rows - 1) / rows;
     float* part = reinterpret_cast<float*>(ws);

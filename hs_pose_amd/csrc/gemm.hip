@@ -86,8 +86,8 @@ __device__ __forceinline__ void wgrad_body(const int bid, const FT* __restrict__
             } else {
                 const unsigned x = __builtin_amdgcn_raw_buffer_load_b32(ra, va, (kk + 2 * u) * lda * 2, 0);
                 const unsigned y = __builtin_amdgcn_raw_buffer_load_b32(rb, vb, (kk + 2 * u) * ldb * 2, 0);
-                aa[u] = make_float2(__uint_as_float(x << 16), __uint_as_float(x & 0xffff0000u));
-                bb[u] = make_float2(__uint_as_float(y << 16), __uint_as_float(y & 0xffff0000u));
+                aa[u] = bf16x2_to_f32(x);
+                bb[u] = bf16x2_to_f32(y);
             }
         }
     };
@@ -357,8 +357,9 @@ __global__ __launch_bounds__(256) void wgrad_bf16_mfma_kernel(const unsigned sho
                 const unsigned w[4] = {r[j].x, r[j].y, r[j].z, r[j].w};
 #pragma unroll
                 for (int d = 0; d < 4; ++d) {
-                    cs[2 * d] += __uint_as_float(w[d] << 16);
-                    cs[2 * d + 1] += __uint_as_float(w[d] & 0xffff0000u);
+                    const float2 f = bf16x2_to_f32(w[d]);
+                    cs[2 * d] += f.x;
+                    cs[2 * d + 1] += f.y;
                 }
             }
         }
@@ -517,10 +518,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_x3_kernel(const float* __restric
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 v[j] = e == 0 ? r[j].x : e == 1 ? r[j].y : e == 2 ? r[j].z : r[j].w;
-                const float h = __uint_as_float(__float_as_uint(v[j]) & 0xffff0000u);
-                r1[j] = v[j] - h;
-                const float mm = __uint_as_float(__float_as_uint(r1[j]) & 0xffff0000u);
-                r2[j] = r1[j] - mm;
+                x3_split(v[j], r1[j], r2[j]);
             }
             uint4 ch, cm, cl;
             unsigned* ph = reinterpret_cast<unsigned*>(&ch);
@@ -528,9 +526,9 @@ __global__ __launch_bounds__(256, 2) void wgrad_x3_kernel(const float* __restric
             unsigned* pl = reinterpret_cast<unsigned*>(&cl);
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                ph[i] = __builtin_amdgcn_perm(__float_as_uint(v[2 * i + 1]), __float_as_uint(v[2 * i]), 0x07060302u);
-                pm[i] = __builtin_amdgcn_perm(__float_as_uint(r1[2 * i + 1]), __float_as_uint(r1[2 * i]), 0x07060302u);
-                pl[i] = __builtin_amdgcn_perm(__float_as_uint(r2[2 * i + 1]), __float_as_uint(r2[2 * i]), 0x07060302u);
+                ph[i] = x3_pair(v[2 * i], v[2 * i + 1]);
+                pm[i] = x3_pair(r1[2 * i], r1[2 * i + 1]);
+                pl[i] = x3_pair(r2[2 * i], r2[2 * i + 1]);
             }
             char* dst = img + ((mc << 2) + e) * PITCH + (kb8 << 4);
             *reinterpret_cast<uint4*>(dst) = ch;
@@ -787,11 +785,8 @@ static int wgrad_launch(const FT* A, int lda, const FT* B, int ldb, int M, int N
         return check_launch();
     }
     const size_t lds = (size_t)4 * 4 * 16 * 64 * sizeof(float) + (size_t)4 * 64 * sizeof(float2);
-    auto kern = wgrad_kernel<COLSUM, 4, FT>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) { set_last_hip_error(e); return HSP_ERR_LAUNCH; }
-    hipLaunchKernelGGL(kern, dim3(tiles * (sk / 4)), dim3(256), lds, st, A, lda, B, ldb, M, N, K, sk, ks, part, cs_part);
-    return check_launch();
+    return launch_lds(wgrad_kernel<COLSUM, 4, FT>, dim3(tiles * (sk / 4)), dim3(256), lds, st, A, lda, B, ldb, M, N, K, sk, ks, part,
+                      cs_part);
 }
 
 template <typename FT>
@@ -814,24 +809,11 @@ static int wgrad_impl(const FT* A, int lda, const FT* B, int ldb, int M, int N, 
             const int lds = 4 * 128 * 128;
             const unsigned short* a = reinterpret_cast<const unsigned short*>(A);
             const unsigned short* b = reinterpret_cast<const unsigned short*>(B);
-#define WG_BF16_LAUNCH(CS, RG)                                                                                                  \
-    do {                                                                                                                       \
-        auto kern = wgrad_bf16_mfma_kernel<CS, RG>;                                                                            \
-        static bool attr_set = false;                                                                                          \
-        if (!attr_set) {                                                                                                       \
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds); \
-            if (e != hipSuccess) { set_last_hip_error(e); return HSP_ERR_LAUNCH; }                                             \
-            attr_set = true;                                                                                                   \
-        }                                                                                                                      \
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, a, lda, b, ldb, M, N, K, ks, part, cs_part);                   \
-    } while (0)
-            if (pl.ragged) {
-                if (colsum_B) WG_BF16_LAUNCH(true, true); else WG_BF16_LAUNCH(false, true);
-            } else {
-                if (colsum_B) WG_BF16_LAUNCH(true, false); else WG_BF16_LAUNCH(false, false);
-            }
+#define WG_BF16_LAUNCH(CS, RG) \
+    launch_lds(wgrad_bf16_mfma_kernel<CS, RG>, dim3(grid), dim3(256), lds, st, a, lda, b, ldb, M, N, K, ks, part, cs_part)
+            const int rc = pl.ragged ? (colsum_B ? WG_BF16_LAUNCH(true, true) : WG_BF16_LAUNCH(false, true))
+                                     : (colsum_B ? WG_BF16_LAUNCH(true, false) : WG_BF16_LAUNCH(false, false));
 #undef WG_BF16_LAUNCH
-            int rc = check_launch();
             if (rc) return rc;
             if (pending) { *pending = HspWgradPending{part, cs_part, C, colsum_B, sk2, M, N, ldc}; return HSP_OK; }
             const long long total = (long long)M * (N >> 2) + (colsum_B ? (N >> 2) : 0);
@@ -943,16 +925,8 @@ static int wgrad_pair_impl(const float* A0, int lda0, const float* B0, int ldb0,
                 rider = ColsumRider{cs_x, cs_out, cs_N, cs_C, nchunk, rows, tpb, 8 / tpb};
                 rider_blocks = cs_B * (8 / tpb);
             }
-            static bool attr_set = false;
-            if (!attr_set) {
-                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_pair_kernel),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                if (e != hipSuccess) { set_last_hip_error(e); return HSP_ERR_LAUNCH; }
-                attr_set = true;
-            }
-            hipLaunchKernelGGL(wgrad_pair_kernel, dim3(blocks0 + blocks1 + rider_blocks), dim3(256), lds, as_stream(stream), p0, p1,
-                               blocks0, blocks0 + blocks1, rider);
-            int rc = check_launch();
+            const int rc = launch_lds(wgrad_pair_kernel, dim3(blocks0 + blocks1 + rider_blocks), dim3(256), lds, as_stream(stream), p0,
+                                      p1, blocks0, blocks0 + blocks1, rider);
             if (rc) return rc;
             pending[0] = HspWgradPending{p0.part, nullptr, C0, nullptr, sk0 / 4, M0, N0, ldc0};
             pending[1] = HspWgradPending{p1.part, nullptr, C1, nullptr, sk1 / 4, M1, N1, ldc1};

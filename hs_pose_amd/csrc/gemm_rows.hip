@@ -63,14 +63,6 @@ struct GemmRowsArgs {
 
 #define GR_TM_GROUP 16                     // row panels per tile-order group
 
-__device__ __forceinline__ float bf16_to_f32(unsigned short v) { return __uint_as_float((unsigned)v << 16); }
-__device__ __forceinline__ unsigned short f32_to_bf16(float f) {              // round to nearest even; NaN stays NaN
-    unsigned u = __float_as_uint(f);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (unsigned short)((u >> 16) | 0x40);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (unsigned short)(u >> 16);
-}
-
 // T: float or unsigned short (bf16 bits).  WM, WN: 32x32 MFMA tiles per wave along M / N (block tile = 64*WM x 64*WN).
 // LB1 / LB2: layout of B1 / B2 -- 1 "nt" (N,K) k contiguous, 2 "nn" (K,N) n contiguous (fp32 only), 0 (LB2) = no 2nd source.
 // MODE 1: every operand 16-byte aligned (base and row pitch): 16-byte staging loads; MODE 2: 8-byte aligned (an even fp32
@@ -344,7 +336,7 @@ __global__ __launch_bounds__(256) void gemm_rows_kernel(const GemmRowsArgs g) {
                     if (!cok || row >= g.M) continue;
                     if (g.resid) {
                         if (ES == 4 || g.r_f32) v += reinterpret_cast<const float*>(g.resid)[(size_t)row * g.ldr + col];
-                        else v += bf16_to_f32(reinterpret_cast<const unsigned short*>(g.resid)[(size_t)row * g.ldr + col]);
+                        else v += bf16_bits_to_f32(reinterpret_cast<const unsigned short*>(g.resid)[(size_t)row * g.ldr + col]);
                     }
                     if (g.xyz3) {      // the K = 3 product on raw fp32 coordinates (HSlayer_surface's STE, gcn3d.py:85)
                         const float* p3 = g.xyz3 + (size_t)row * 3;
@@ -361,7 +353,7 @@ __global__ __launch_bounds__(256) void gemm_rows_kernel(const GemmRowsArgs g) {
                         bn2_out[y] += d * d;
                     }
                     if (ES == 4 || g.c_f32) reinterpret_cast<float*>(g.C)[(size_t)row * g.ldc + col] = v;
-                    else if (!pack2) reinterpret_cast<unsigned short*>(g.C)[(size_t)row * g.ldc + col] = f32_to_bf16(v);
+                    else if (!pack2) reinterpret_cast<unsigned short*>(g.C)[(size_t)row * g.ldc + col] = f32_to_bf16_bits<bf16_t>(v);
                     else keep[r] = v;
                 }
                 if (ES == 2 && !g.c_f32 && pack2) {
@@ -376,7 +368,7 @@ __global__ __launch_bounds__(256) void gemm_rows_kernel(const GemmRowsArgs g) {
                         const float got = __shfl_xor(give, 1);
                         const int r = 2 * p + (odd ? 1 : 0);
                         const int row = m0 + wm0 + 32 * x + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                        const unsigned lo = f32_to_bf16(odd ? got : mine), hi = f32_to_bf16(odd ? mine : got);
+                        const unsigned lo = f32_to_bf16_bits(odd ? got : mine), hi = f32_to_bf16_bits(odd ? mine : got);
                         if (row < g.M && (col | 1) < g.N)      // (pack2: N is even, so the pair is inside or outside together)
                             *reinterpret_cast<unsigned*>(reinterpret_cast<unsigned short*>(g.C) + (size_t)row * g.ldc + (col & ~1)) =
                                 lo | (hi << 16);
@@ -466,7 +458,7 @@ __global__ __launch_bounds__(256) void gemm_rows_reduce_kernel(const GemmRowsArg
         if (g.bias) v += g.bias[col];
         if (g.resid) {
             if (sizeof(T) == 4 || g.r_f32) v += reinterpret_cast<const float*>(g.resid)[(size_t)row * g.ldr + col];
-            else v += bf16_to_f32(reinterpret_cast<const unsigned short*>(g.resid)[(size_t)row * g.ldr + col]);
+            else v += bf16_bits_to_f32(reinterpret_cast<const unsigned short*>(g.resid)[(size_t)row * g.ldr + col]);
         }
         if (g.xyz3) {
             const float* p3 = g.xyz3 + (size_t)row * 3;
@@ -474,7 +466,7 @@ __global__ __launch_bounds__(256) void gemm_rows_reduce_kernel(const GemmRowsArg
         }
         if (g.cbias) v += g.cbias[(size_t)(row / g.rows_per_cloud) * g.N + col];
         if (sizeof(T) == 4 || g.c_f32) reinterpret_cast<float*>(g.C)[(size_t)row * g.ldc + col] = v;
-        else reinterpret_cast<unsigned short*>(g.C)[(size_t)row * g.ldc + col] = f32_to_bf16(v);
+        else reinterpret_cast<unsigned short*>(g.C)[(size_t)row * g.ldc + col] = f32_to_bf16_bits<bf16_t>(v);
     }
 }
 
@@ -521,17 +513,8 @@ static int launch_cfg(const GemmRowsArgs& a, int lb1, int lb2, float* a_ws, size
     const dim3 grid((unsigned)nb), block(256);
 #define GR_LAUNCH(L1, L2, BNP)                                                                                          \
     do {                                                                                                               \
-        auto kern = gemm_rows_kernel<T, WM, WN, L1, L2, MODE, BNP>;                                                    \
-        static bool attr_set = false;                                                                                  \
-        if (!attr_set) {                                                                                               \
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                                    \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                  \
-            if (e != hipSuccess) { set_last_hip_error(e); return HSP_ERR_LAUNCH; }                                     \
-            attr_set = true;                                                                                           \
-        }                                                                                                              \
-        hipLaunchKernelGGL(kern, grid, block, lds, st, g);                                                             \
-        int rc_ = check_launch();                                                                                      \
-        if (rc_ || g.nsplit == 1) return rc_;                                                                          \
+        int rc_ = launch_lds(gemm_rows_kernel<T, WM, WN, L1, L2, MODE, BNP>, grid, block, lds, st, g);                 \
+        if (rc_ || g.nsplit == 1) return rc_;                                                                        \
         const long long tot_ = (long long)g.M * g.N;                                                                   \
         long long rg_ = (tot_ + 255) / 256;                                                                            \
         if (rg_ > HSP_NUM_CU * 8) rg_ = HSP_NUM_CU * 8;                                                                \

@@ -58,17 +58,12 @@ struct X3Args {
 __device__ __forceinline__ void x3_split8(const float (&x)[8], u32x4& hi, u32x4& mid, u32x4& lo) {
     float r1[8], r2[8];
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const float h = __uint_as_float(__float_as_uint(x[i]) & 0xffff0000u);
-        r1[i] = x[i] - h;                                                  // exact
-        const float m = __uint_as_float(__float_as_uint(r1[i]) & 0xffff0000u);
-        r2[i] = r1[i] - m;                                                 // exact, <= 8 significant bits
-    }
+    for (int i = 0; i < 8; ++i) x3_split(x[i], r1[i], r2[i]);
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {                                          // v_perm_b32: high halves of two dwords
-        hi[i] = __builtin_amdgcn_perm(__float_as_uint(x[2 * i + 1]), __float_as_uint(x[2 * i]), 0x07060302u);
-        mid[i] = __builtin_amdgcn_perm(__float_as_uint(r1[2 * i + 1]), __float_as_uint(r1[2 * i]), 0x07060302u);
-        lo[i] = __builtin_amdgcn_perm(__float_as_uint(r2[2 * i + 1]), __float_as_uint(r2[2 * i]), 0x07060302u);
+    for (int i = 0; i < 4; ++i) {
+        hi[i] = x3_pair(x[2 * i], x[2 * i + 1]);
+        mid[i] = x3_pair(r1[2 * i], r1[2 * i + 1]);
+        lo[i] = x3_pair(r2[2 * i], r2[2 * i + 1]);
     }
 }
 
@@ -633,19 +628,13 @@ __global__ __launch_bounds__(256) void split_params_x3_kernel(const HspSplitDesc
         const int nn = n0 + ly + 8 * j, k = k0 + 2 * lx;
         if (nn >= Nn || k >= Kk) continue;
         float r1[2], r2[2];
-        const float xs[2] = {x0[j], x1[j]};
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            const float h = __uint_as_float(__float_as_uint(xs[q]) & 0xffff0000u);
-            r1[q] = xs[q] - h;
-            const float m = __uint_as_float(__float_as_uint(r1[q]) & 0xffff0000u);
-            r2[q] = r1[q] - m;
-        }
+        x3_split(x0[j], r1[0], r2[0]);
+        x3_split(x1[j], r1[1], r2[1]);
         const size_t o = ((size_t)nn * d.kp + k) >> 1;                 // dword index inside a plane
         const size_t psd = (size_t)d.ps >> 1;
-        dst[o] = __builtin_amdgcn_perm(__float_as_uint(xs[1]), __float_as_uint(xs[0]), 0x07060302u);
-        dst[psd + o] = __builtin_amdgcn_perm(__float_as_uint(r1[1]), __float_as_uint(r1[0]), 0x07060302u);
-        dst[2 * psd + o] = __builtin_amdgcn_perm(__float_as_uint(r2[1]), __float_as_uint(r2[0]), 0x07060302u);
+        dst[o] = x3_pair(x0[j], x1[j]);
+        dst[psd + o] = x3_pair(r1[0], r1[1]);
+        dst[2 * psd + o] = x3_pair(r2[0], r2[1]);
     }
 }
 
@@ -792,21 +781,9 @@ static int gemm_x3_impl(const float* A1, int lda1, const hsp_bf16_t* P1, int ldp
             g.tiles_m = nt; g.tiles_n = P; g.nsplit = 1; g.ws = nullptr;
             const dim3 pgrid((unsigned)(P * R)), pblock(256);
             const size_t lds = (size_t)2 * 3 * 32 * 128 * 2;             // 48 KB
-#define X3_PANEL(EPI_)                                                                                                    \
-    do {                                                                                                                  \
-        auto kern = gemm_x3_panel_kernel<EPI_>;                                                                           \
-        static bool attr_set = false;                                                                                     \
-        if (!attr_set) {                                                                                                  \
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-            if (e != hipSuccess) { set_last_hip_error(e); return HSP_ERR_LAUNCH; }                                        \
-            attr_set = true;                                                                                              \
-        }                                                                                                                 \
-        hipLaunchKernelGGL(kern, pgrid, pblock, lds, st, g);                                                              \
-    } while (0)
-            if (epi0) X3_PANEL(1);
-            else X3_PANEL(0);
+#define X3_PANEL(EPI_) launch_lds(gemm_x3_panel_kernel<EPI_>, pgrid, pblock, lds, st, g)
+            return epi0 ? X3_PANEL(1) : X3_PANEL(0);
 #undef X3_PANEL
-            return check_launch();
         }
     }
     const int wm = pl.wm, bm = 64 * wm;
@@ -902,10 +879,7 @@ __global__ __launch_bounds__(256) void small_rows_nt_kernel(const float* __restr
                 if (m < M) p[m] = __fmaf_rn(sA[m * K + k], w, p[m]);
         }
 #pragma unroll
-        for (int m = 0; m < SR_MAXM; ++m) {
-#pragma unroll
-            for (int o = 32; o >= 1; o >>= 1) p[m] += __shfl_xor(p[m], o, 64);
-        }
+        for (int m = 0; m < SR_MAXM; ++m) p[m] = wave_sum(p[m]);
         if (lane == 0) {
 #pragma unroll
             for (int m = 0; m < SR_MAXM; ++m)

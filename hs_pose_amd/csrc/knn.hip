@@ -1533,14 +1533,19 @@ static int knn_feat_rem_mode(int B, int N, int C) {
 static size_t knn_feat_small_lds(int N, int C, int QT) {
     const int ntiles = (N + 31) / 32, rem = (N & 31) <= 4 ? (N & 31) : 0;
     const size_t fl = (size_t)(QT + rem) * (C + 4) + (size_t)ntiles * 32 * KF_CT_STRIDE + (size_t)ntiles * 32 + (size_t)QT * (ntiles * 32 + 1);
-    // (the selection scratch aliases the candidate chunks: (128 + N) int2 per wave)
-    const int nw = ntiles > 8 ? ntiles : 8;
-    const size_t scratch = (size_t)nw * (128 + N) * 2, chunks = (size_t)ntiles * 32 * KF_CT_STRIDE;
-    return (fl + (scratch > chunks ? scratch - chunks : 0)) * 4;
+    return fl * 4;
+}
+// The selection scratch ((128 + N) int2 per wave) is not part of that sum: the kernel lays it over the candidate chunks, which lie
+// directly before quadl / dl -- a scratch longer than the chunks would run into those, and words added at the end of the allocation
+// would not help.  So such a shape is declined rather than sized: none is today (64 <= N <= 320; tightest at N = 64 with 3072
+// words of scratch on 4352 of chunks).
+static bool knn_feat_small_scratch_fits(int N) {
+    const int ntiles = (N + 31) / 32, nw = ntiles > 8 ? ntiles : 8;
+    return (size_t)nw * (128 + N) * 2 <= (size_t)ntiles * 32 * KF_CT_STRIDE;
 }
 static int knn_feat_small_qt(int B, int N, int C) {           // 0: not this kernel's shape
     if (N < 64 || N > 320 || (C & 63) || C >= 512 ||   // (C >= 512: ATen sums |x|^2 in cascade levels, quad_kernel)
-        (size_t)N * C * 4 >= ((size_t)1 << 31)) return 0;
+        (size_t)N * C * 4 >= ((size_t)1 << 31) || !knn_feat_small_scratch_fits(N)) return 0;
     const int rem = (N & 31) <= 4 ? (N & 31) : 0;
     const int per_cloud = HSP_NUM_CU / B > 0 ? HSP_NUM_CU / B : 1;      // workgroups a cloud may have
     int qt = (N + per_cloud - 1) / per_cloud;
@@ -1603,9 +1608,9 @@ __global__ __launch_bounds__(256) void quad_bf16_kernel(const bf16_t* __restrict
             const unsigned w[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                const float a = __uint_as_float(w[e] << 16), b = __uint_as_float(w[e] & 0xffff0000u);
-                s = __fmaf_rn(a, a, s);
-                s = __fmaf_rn(b, b, s);
+                const float2 ab = bf16x2_to_f32(w[e]);
+                s = __fmaf_rn(ab.x, ab.x, s);
+                s = __fmaf_rn(ab.y, ab.y, s);
             }
         }
     }

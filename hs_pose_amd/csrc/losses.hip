@@ -283,11 +283,6 @@ __device__ __forceinline__ void sym_targets(const PointCtx& q, const CloudGT& c,
     }
 }
 
-template <typename V> __device__ __forceinline__ V wave_sum(V v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 // ---- kernel 2: points pass 1 -- one workgroup per cloud ---------------------------------------------------------------
 constexpr int PTS_THREADS = 512;
 __global__ __launch_bounds__(PTS_THREADS) void loss_points_kernel(

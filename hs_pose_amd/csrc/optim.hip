@@ -18,18 +18,6 @@
 
 namespace hsp {
 
-struct RowDesc {            // mirrors HspRowDesc (include/hsp.h)
-    long long offset;       // first element in the flat buffers
-    int len;                // elements
-    int gc;                 // subtract the row mean of the gradient first
-};
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s);
-    return v;
-}
-
 // The sweep of a squared norm, stated once: element -> lane -> partial.  `quad(i)` yields the i-th float4 of the swept
 // buffer, `one(i)` element i of its tail (block 0 only); four accumulators per lane, a wave fold, four waves through LDS,
 // part[blockIdx.x].  sumsq_partial_kernel reads its values, grad_accumulate_kernel makes (and stores) them on the way: equal
@@ -195,20 +183,15 @@ __global__ __launch_bounds__(64) void step_gate_accum_kernel(const float* __rest
     ctl[HSP_STEP_CTL_APPLY] = apply;
 }
 
-struct StepEntry {          // mirrors HspStepEntry (include/hsp.h)
-    float step_lr;
-    int flags;
-};
-
 // one wave per row.  ctl == nullptr (hsp_ranger_step): step_lr / adaptive / lookahead are the host's, in `a`.  Otherwise
 // (hsp_ranger_step_gated) the wave leaves unless the gate said apply, and takes the three from the table entry the gate named;
 // everything below the head is the same code for both.
 __global__ __launch_bounds__(256) void ranger_rows_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                           float* __restrict__ m, float* __restrict__ v,
                                                           float* __restrict__ slow,
-                                                          const RowDesc* __restrict__ rows, int nrows,
+                                                          const HspRowDesc* __restrict__ rows, int nrows,
                                                           const float* __restrict__ gnorm_sq,
-                                                          const StepEntry* __restrict__ table, const int* __restrict__ ctl,
+                                                          const HspStepEntry* __restrict__ table, const int* __restrict__ ctl,
                                                           int horizon, RangerArgs a) {
     const int lane = threadIdx.x & 63;
     const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -218,13 +201,13 @@ __global__ __launch_bounds__(256) void ranger_rows_kernel(float* __restrict__ p,
         if (ctl[HSP_STEP_CTL_APPLY] == 0) return;
         const int idx = ctl[HSP_STEP_CTL_INDEX];
         if (idx < 0 || idx >= horizon) return;             // (the gate never names such an entry)
-        const StepEntry en = table[idx];
+        const HspStepEntry en = table[idx];
         a.step_lr = en.step_lr;
         a.adaptive = (en.flags & HSP_STEP_ADAPTIVE) != 0;
         a.lookahead = (en.flags & HSP_STEP_LOOKAHEAD) != 0;
         fill_slow = (en.flags & HSP_STEP_FILL_SLOW) != 0;
     }
-    const RowDesc rd = rows[r];
+    const HspRowDesc rd = rows[r];
     float clip = 1.0f;
     if (gnorm_sq) {
         clip = clip_coef(gnorm_sq[0], a.max_norm);
@@ -358,13 +341,12 @@ extern "C" int hsp_ranger_step(float* params, const float* grads, float* exp_avg
                                float weight_decay, float step_lr, int adaptive, int lookahead, float la_alpha,
                                int gc_after, const float* gnorm_sq, float max_norm, hspStream_t stream) {
     if (!params || !grads || !exp_avg || !exp_avg_sq || !slow || !rows || nrows <= 0) return HSP_ERR_BAD_ARG;
-    static_assert(sizeof(RowDesc) == sizeof(HspRowDesc), "row descriptor layout");
     RangerArgs a;
     a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.weight_decay = weight_decay; a.step_lr = step_lr;
     a.la_alpha = la_alpha; a.max_norm = max_norm; a.adaptive = adaptive; a.lookahead = lookahead; a.gc_after = gc_after;
     hipLaunchKernelGGL(ranger_rows_kernel, dim3((nrows + 3) / 4), dim3(256), 0, as_stream(stream), params, grads, exp_avg,
-                       exp_avg_sq, slow, reinterpret_cast<const RowDesc*>(rows), nrows, gnorm_sq,
-                       static_cast<const StepEntry*>(nullptr), static_cast<const int*>(nullptr), 0, a);
+                       exp_avg_sq, slow, rows, nrows, gnorm_sq,
+                       static_cast<const HspStepEntry*>(nullptr), static_cast<const int*>(nullptr), 0, a);
     return check_launch();
 }
 
@@ -380,12 +362,11 @@ extern "C" int hsp_ranger_step_gated(float* params, const float* grads, float* e
                                      const HspStepEntry* table, const int32_t* ctl, int horizon, hspStream_t stream) {
     if (!params || !grads || !exp_avg || !exp_avg_sq || !slow || !rows || nrows <= 0) return HSP_ERR_BAD_ARG;
     if (!table || !ctl || horizon <= 0) return HSP_ERR_BAD_ARG;
-    static_assert(sizeof(StepEntry) == sizeof(HspStepEntry), "step entry layout");
     RangerArgs a;
     a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.weight_decay = weight_decay; a.step_lr = 0.f;
     a.la_alpha = la_alpha; a.max_norm = max_norm; a.adaptive = 0; a.lookahead = 0; a.gc_after = gc_after;
     hipLaunchKernelGGL(ranger_rows_kernel, dim3((nrows + 3) / 4), dim3(256), 0, as_stream(stream), params, grads, exp_avg,
-                       exp_avg_sq, slow, reinterpret_cast<const RowDesc*>(rows), nrows, gnorm_sq,
-                       reinterpret_cast<const StepEntry*>(table), ctl, horizon, a);
+                       exp_avg_sq, slow, rows, nrows, gnorm_sq,
+                       table, ctl, horizon, a);
     return check_launch();
 }

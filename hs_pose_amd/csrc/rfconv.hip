@@ -295,8 +295,7 @@ __global__ __launch_bounds__(RF_THREADS) void rf_fwd_pipe_kernel(const float* __
                         return make_float4(__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]), __uint_as_float(v[3]));
                     } else {
                         const auto v = __builtin_amdgcn_raw_buffer_load_b64(frs, (int)(voff + sOff[n]), 0, 0);
-                        return make_float4(__uint_as_float(v[0] << 16), __uint_as_float(v[0] & 0xffff0000u),
-                                           __uint_as_float(v[1] << 16), __uint_as_float(v[1] & 0xffff0000u));
+                        return bf16x4_to_f32(make_uint2(v[0], v[1]));
                     }
                 };
                 rf_group_body<SURFACE, WF, FT>(d0[u], d1[u], d2[u], sR, sIdx, k, fetch, smax + j,
@@ -500,10 +499,7 @@ template <> struct Raw4<float> {
 template <> struct Raw4<bf16_t> {
     typedef uint2 T;
     static __device__ __forceinline__ T ld(const bf16_t* p) { return *reinterpret_cast<const uint2*>(p); }
-    static __device__ __forceinline__ float4 wide(T u) {
-        return make_float4(__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xffff0000u), __uint_as_float(u.y << 16),
-                           __uint_as_float(u.y & 0xffff0000u));
-    }
+    static __device__ __forceinline__ float4 wide(T u) { return bf16x4_to_f32(u); }
     static __device__ __forceinline__ void st(bf16_t* p, T v) { *reinterpret_cast<uint2*>(p) = v; }
 };
 typedef float rf_v4f __attribute__((ext_vector_type(4)));
@@ -1097,25 +1093,16 @@ template <int TC, bool SURFACE, int RS> struct RfSched {
     static constexpr int resident = (SURFACE || RS > 1) ? 0 : (TC == 16 ? 9 : (TC == 32 ? 5 : (TC == 64 ? 2 : 0)));   // rows per thread
 };
 
-template <typename K, typename... A>
-static int rf_tile_issue(K kern, dim3 grid, size_t lds, hipStream_t st, A... args) {
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) { set_last_hip_error(e); return HSP_ERR_LAUNCH; }
-    }
-    hipLaunchKernelGGL(kern, grid, dim3(RF_TILE_THREADS), lds, st, args...);
-    return check_launch();
-}
-
 // one (tile width, row ranges) under the schedule in force when the call is issued (a captured graph keeps what it was captured with)
 template <int TC, bool SURFACE, bool FWIN, typename FT, int RS, typename... A>
 static int rf_tile_launch(bool legacy, int N, dim3 grid, size_t lds, hipStream_t st, A... args) {
     typedef RfSched<TC, SURFACE, RS> Sch;
-    if (legacy) return rf_tile_issue(rf_bwd_tile_kernel<TC, SURFACE, FWIN, FT, RS, 0, 0>, grid, lds, st, args...);
+    const dim3 block(RF_TILE_THREADS);
+    if (legacy) return launch_lds(rf_bwd_tile_kernel<TC, SURFACE, FWIN, FT, RS, 0, 0>, grid, block, lds, st, args...);
     constexpr int PL = RF_TILE_THREADS / (TC / 4);
     if constexpr (Sch::resident > 0) {
         if ((N + PL - 1) / PL <= Sch::resident)
-            return rf_tile_issue(rf_bwd_tile_kernel<TC, SURFACE, FWIN, FT, RS, Sch::depth, Sch::resident>, grid, lds, st, args...);
+            return launch_lds(rf_bwd_tile_kernel<TC, SURFACE, FWIN, FT, RS, Sch::depth, Sch::resident>, grid, block, lds, st, args...);
     }
     if constexpr (Sch::resident > 0 && TC == 16) {
         // pick_tile_cols gives a whole cloud 16 columns only while (16 + 3) N floats fit 80 KB: N <= 1077, nine rows per thread.
@@ -1123,7 +1110,7 @@ static int rf_tile_launch(bool legacy, int N, dim3 grid, size_t lds, hipStream_t
         static_assert(80 * 1024 / ((16 + 3) * 4) <= Sch::resident * PL, "the 16-column whole-cloud tile must always be resident");
         return HSP_ERR_UNSUPPORTED;
     } else {
-        return rf_tile_issue(rf_bwd_tile_kernel<TC, SURFACE, FWIN, FT, RS, Sch::depth_stream, 0>, grid, lds, st, args...);
+        return launch_lds(rf_bwd_tile_kernel<TC, SURFACE, FWIN, FT, RS, Sch::depth_stream, 0>, grid, block, lds, st, args...);
     }
 }
 
