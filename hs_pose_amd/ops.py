@@ -396,30 +396,15 @@ class _RFSurface(torch.autograd.Function):
         xyz = _req(xyz, torch.float32, "rf_surface.xyz")
         idx = _req(idx, torch.int32, "rf_surface.idx")
         dirs_n = dirs_fresh(_req(dirs_n, torch.float32, "rf_surface.dirs"))
-        B, N, k = idx.shape
-        SC = dirs_n.shape[1]
-        K = SC // S
-        out = torch.empty(B, N, K, dtype=torch.float32, device=xyz.device)
-        arg = torch.empty(B, N, SC, dtype=torch.uint16, device=xyz.device)
-        _run("hsp_rf_surface_fwd", (_p(xyz), _p(idx), _p(dirs_n), B, N, k, S, K, _p(out), _p(arg), _stream()),
-             key=f"B{B}N{N}k{k}S{S}C{K}", abytes=B * N * (12 + 4 * k + 4 * K + SC) + 12 * SC)
-        ctx.save_for_backward(xyz, idx, dirs_n, arg)
+        out, arg = _rf_surface_fwd_raw(xyz, idx, dirs_n, S, torch.float32)
+        ctx.save_for_backward(xyz, dirs_n, arg)
         ctx.S = S
         return out
 
     @staticmethod
     def backward(ctx, g):
-        xyz, idx, dirs_n, arg = ctx.saved_tensors
-        g = _req(g, torch.float32, "rf_surface.grad")
-        B, N, k = idx.shape
-        SC = dirs_n.shape[1]
-        gd = torch.empty_like(dirs_fresh(dirs_n))
-        L = lib()
-        wsb = L.hsp_rf_bwd_scatter_workspace_bytes(B, SC)
-        ws = _ws(wsb, g.device)
-        _rf_bwd_dirs_call("hsp_rf_surface_bwd", "", (_p(xyz), _p(dirs_n), _p(arg), _p(g), B, N, ctx.S, SC // ctx.S, _p(gd)), ws, wsb,
-                          (dirs_n, gd), key=f"B{B}N{N}S{ctx.S}C{SC // ctx.S}", abytes=B * N * (12 + 4 * (SC // ctx.S) + SC) + 24 * SC)
-        return None, None, gd, None
+        xyz, dirs_n, arg = ctx.saved_tensors
+        return None, None, _rf_surface_bwd_raw(xyz, dirs_n, arg, _req(g, torch.float32, "rf_surface.grad"), ctx.S), None
 
 
 class _RFConv(torch.autograd.Function):
@@ -429,12 +414,8 @@ class _RFConv(torch.autograd.Function):
         idx = _req(idx, torch.int32, "rf_conv.idx")
         dirs_n = _req(dirs_n, torch.float32, "rf_conv.dirs")
         fm = _req(fm, torch.float32, "rf_conv.fm")
-        B, N, k = idx.shape
-        SC = dirs_n.shape[1]
-        C = SC // S
-        if fm.shape[-1] != (S + 1) * C:
+        if fm.shape[-1] != (S + 1) * (dirs_n.shape[1] // S):
             raise HspError("rf_conv: fm must have (S+1)*C columns")
-        out = torch.empty(B, N, C, dtype=torch.float32, device=xyz.device)
         out, arg, fwin = _rf_conv_fwd_raw(xyz, idx, dirs_n, fm, S, any(ctx.needs_input_grad))
         ctx.save_for_backward(xyz, idx, dirs_n, fwin if fwin is not None else fm, arg)
         ctx.S = S
@@ -445,9 +426,6 @@ class _RFConv(torch.autograd.Function):
         xyz, idx, dirs_n, fm, arg = ctx.saved_tensors          # fm: the winners' support values (or fm itself
                                                                  # in DETERMINISTIC mode)
         g = _req(g, torch.float32, "rf_conv.grad")
-        B, N, k = idx.shape
-        SC = dirs_n.shape[1]
-        C = SC // ctx.S
         gfm, gd = _rf_conv_bwd_raw(xyz, idx, dirs_n, fm, arg, g, ctx.S)
         return None, None, gd, gfm, None
 
@@ -518,19 +496,44 @@ def _pool_bwd_raw(g, idx, qsel, qstride, arg, B, Nsrc, Nidx, Nq, kstride, C, gfe
     """the pooling backward of gather_max / pool_layer: gfeat (B,Nsrc,C) overwritten; ``qstride`` as _qsel_dims returns it.  Default:
     the column-tile LDS scatter (fp32 LDS adds in the order the waves arrive).  With FLAGS.reproducible: the ORDERED form -- the
     gather over the reverse index of the kept rows' lists (``k`` columns of idx), every row's sum in ascending query order."""
-    es = _es(g)
+    dims = (B, Nsrc, Nidx, Nq, kstride, C)
     if FLAGS.reproducible:
-        off, edge = rev_index_sel(idx, qsel, qstride, k, Nsrc)
-        _run("hsp_gather_max_bwd_csr" + _sfx(g), (_p(g), 0, _p(arg), _p(off), _p(edge), B, Nsrc, Nq, k, C, _p(gfeat), _stream()),
-             key=f"B{B}Ns{Nsrc}Nq{Nq}k{k}C{C}", abytes=B * (es * Nsrc * C + 4 * (Nsrc + Nq * k) + Nq * (es + 1) * C))
-        return
-    key, ab = f"B{B}Ns{Nsrc}Nq{Nq}C{C}", B * (es * Nsrc * C + Nq * (4 * kstride + (es + 1) * C))
-    if qstride:
-        _run("hsp_gather_max_bwd_sel" + _sfx(g), (_p(g), 0, _p(idx), _p(qsel), qstride, _p(arg), B, Nsrc, Nidx, Nq, kstride, C,
-                                                  _p(gfeat), 0, _vp(0), _stream()), key=key + "pc", abytes=ab + 4 * (B - 1) * Nq)
+        _gather_max_bwd_csr_raw(g, False, idx, qsel, qstride, arg, k, dims, gfeat)
     else:
-        _run("hsp_gather_max_bwd" + _sfx(g), (_p(g), 0, _p(idx), _p(qsel), _p(arg), B, Nsrc, Nidx, Nq, kstride, C, _p(gfeat),
-                                              0, _vp(0), _stream()), key=key, abytes=ab)
+        _gather_max_bwd_raw(g, 0, idx, qsel, qstride, arg, dims, gfeat)
+
+
+def _gather_max_bwd_raw(g, mode, idx, qsel, qstride, arg_or_counts, dims, gfeat, accumulate=False, extra=None):
+    """the LDS-tile backward of a neighbourhood max (``_sel`` exactly where ``qstride`` != 0): gfeat (B,Nsrc,C) = [gfeat + extra +,
+    with ``accumulate``] the gradient routed to the winning rows.  ``mode`` is the entry point's grad_bcast: 0 -- g (B,Nq,C), one per
+    query; 1 -- g (B,C), one per cloud (integer counts: fixed order); 2 -- g (B,C) and the winner counts themselves in place of the
+    arg-max bytes (no idx: a stream pass).  dims = (B, Nsrc, Nidx, Nq, kstride, C)."""
+    B, Nsrc, Nidx, Nq, kstride, C = dims
+    es = _es(gfeat)
+    key = f"B{B}Ns{Nsrc}Nq{Nq}C{C}"
+    if mode == 2:
+        key, ab = key + "cnt+", B * Nq * C * (3 * es + 2)
+    elif mode == 1:
+        key, ab = key + ("bc+" if accumulate else "bc"), B * Nq * ((3 if accumulate else 1) * es * C + 4 * kstride + C)
+    else:
+        ab = B * (es * Nsrc * C + Nq * (4 * kstride + (es + 1) * C))
+    tail = (_p(arg_or_counts), B, Nsrc, Nidx, Nq, kstride, C, _p(gfeat), 1 if accumulate else 0, _p(extra), _stream())
+    if qstride:                                             # kept rows per cloud
+        _run("hsp_gather_max_bwd_sel" + _sfx(gfeat), (_p(g), mode, _p(idx), _p(qsel), qstride, *tail), key=key + "pc",
+             abytes=ab + 4 * (B - 1) * Nq)
+    else:
+        _run("hsp_gather_max_bwd" + _sfx(gfeat), (_p(g), mode, _p(idx), _p(qsel), *tail), key=key, abytes=ab)
+
+
+def _gather_max_bwd_csr_raw(g, bcast, idx, qsel, qstride, arg, k, dims, gfeat):
+    """the same gradient in gather form over the reverse index of the (kept rows') lists, every row's sum in ascending query
+    order: gfeat overwritten.  ``bcast``: g is one row per cloud (B,C) instead of one per query."""
+    B, Nsrc, _, Nq, _, C = dims
+    es = _es(gfeat)
+    off, edge = rev_index_sel(idx, qsel, qstride, k, Nsrc)
+    _run("hsp_gather_max_bwd_csr" + _sfx(gfeat), (_p(g), 1 if bcast else 0, _p(arg), _p(off), _p(edge), B, Nsrc, Nq, k, C, _p(gfeat),
+                                                 _stream()), key=f"B{B}Ns{Nsrc}Nq{Nq}k{k}C{C}" + ("bc" if bcast else ""),
+         abytes=B * Nq * (es * C + 8 * k + C) if bcast else B * (es * Nsrc * C + 4 * (Nsrc + Nq * k) + Nq * (es + 1) * C))
 
 
 class _OrlGlobal(torch.autograd.Function):
@@ -555,13 +558,9 @@ class _OrlGlobal(torch.autograd.Function):
         g = _req(gfg / N, torch.float32, "orl.grad")
         gfeat = torch.empty(B, N, C, dtype=torch.float32, device=g.device)
         if DETERMINISTIC:      # gather form over the reverse-edge index (shared by the layers of a resolution)
-            off, edge = rev_index(idx, ctx.k, N)
-            _run("hsp_gather_max_bwd_csr", (_p(g), 1, _p(arg), _p(off), _p(edge), B, N, N, ctx.k, C, _p(gfeat), _stream()),
-                 key=f"B{B}Ns{N}Nq{N}k{ctx.k}C{C}bc", abytes=B * N * (4 * C + 8 * ctx.k + C))
+            _gather_max_bwd_csr_raw(g, True, idx, None, 0, arg, ctx.k, (B, N, N, N, kstride, C), gfeat)
         else:                  # LDS tile kernel; broadcast gradient => integer counts => reproducible as well
-            _run("hsp_gather_max_bwd", (_p(g), 1, _p(idx), _vp(0), _p(arg), B, N, N, N, kstride, C, _p(gfeat), 0, _vp(0),
-                                        _stream()),
-                 key=f"B{B}Ns{N}Nq{N}C{C}bc", abytes=B * N * (4 * C + 4 * kstride + C))
+            _gather_max_bwd_raw(g, 1, idx, None, 0, arg, (B, N, N, N, kstride, C), gfeat)
         return gfeat, None, None
 
 
@@ -906,6 +905,31 @@ def _ld(t):
     return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
 
 
+def _gemm_dims(A1, B1, nn1=False, A2=None):
+    """(M, N, K1, K2, flops, key) of the product  A1 op(B1) [+ A2 op(B2)]  of the ``gemm_rows`` contract"""
+    M, K1 = A1.shape
+    N = B1.shape[1] if nn1 else B1.shape[0]
+    K2 = A2.shape[1] if A2 is not None else 0
+    return M, N, K1, K2, 2 * M * N * (K1 + K2), f"M{M}N{N}K{K1}" + (f"+{K2}" if K2 else "")
+
+
+def _gemm_sources(A1, w1, K1, A2, w2, K2):
+    """the operand prefix the dense entry points share: (A1, lda1, *w1, K1, A2, lda2, *w2, K2).  w*: a source's weight side as its
+    entry point takes it -- ``_w(B)`` (pointer, pitch), ``_w(B, nn)`` (pointer, pitch, layout) or x3 planes (pointer, pitch, plane
+    stride)"""
+    return (_p(A1), _ld(A1), *w1, K1, _p(A2), _ld(A2) if A2 is not None else 0, *w2, K2)
+
+
+def _w(B, nn=None):
+    return (_p(B), _ld(B) if B is not None else 0) + (() if nn is None else (1 if nn else 0,))
+
+
+def _gemm_epilogue(M, N, bias, resid, cloud_bias, rows_per_cloud, alpha, out, xyz=()):
+    """(M, N, bias, resid, ldr, cloud_bias, rows_per_cloud, alpha, [xyz3, w3,] out, ldo): what follows the sources"""
+    return (M, N, _p(bias), _p(resid), _ld(resid) if resid is not None else 0, _p(cloud_bias), int(rows_per_cloud), float(alpha),
+            *map(_p, xyz), _p(out), _ld(out))
+
+
 def gemm_rows(A1, B1, nn1=False, A2=None, B2=None, nn2=False, bias=None, resid=None, cloud_bias=None, rows_per_cloud=0,
               out=None, alpha=1.0, xyz3=None, w3=None):
     """out (M,N) = alpha * (A1 @ op(B1) [+ A2 @ op(B2)]) [+ bias] [+ resid] [+ cloud_bias[row // rows_per_cloud]]   (csrc/gemm_rows.hip)
@@ -922,15 +946,11 @@ def gemm_rows(A1, B1, nn1=False, A2=None, B2=None, nn2=False, bias=None, resid=N
             raise HspError(f"gemm_rows.{nm}: expected a {dt} GPU tensor")
     if out is not None and (not out.is_cuda or out.dtype not in (dt, torch.float32)):
         raise HspError(f"gemm_rows.out: expected a {dt} (or, for bf16 operands, fp32) GPU tensor")
-    M, K1 = A1.shape
-    N = B1.shape[1] if nn1 else B1.shape[0]
+    M, N, K1, K2, flops, key = _gemm_dims(A1, B1, nn1, A2)
     if (B1.shape[0] if nn1 else B1.shape[1]) != K1:
         raise HspError("gemm_rows: A1 / B1 inner dimensions differ")
-    K2 = 0
-    if A2 is not None:
-        K2 = A2.shape[1]
-        if A2.shape[0] != M or (B2.shape[1] if nn2 else B2.shape[0]) != N or (B2.shape[0] if nn2 else B2.shape[1]) != K2:
-            raise HspError("gemm_rows: second source has the wrong shape")
+    if A2 is not None and (A2.shape[0] != M or (B2.shape[1] if nn2 else B2.shape[0]) != N or (B2.shape[0] if nn2 else B2.shape[1]) != K2):
+        raise HspError("gemm_rows: second source has the wrong shape")
     if out is None:
         out = torch.empty(M, N, dtype=dt, device=A1.device)
     for t_ in (bias, cloud_bias, xyz3, w3):
@@ -938,26 +958,18 @@ def gemm_rows(A1, B1, nn1=False, A2=None, B2=None, nn2=False, bias=None, resid=N
             raise HspError("gemm_rows: bias / cloud_bias / xyz3 / w3 must be contiguous fp32 GPU tensors")
     if (xyz3 is None) != (w3 is None) or (xyz3 is not None and (xyz3.shape != (M, 3) or w3.shape != (N, 3))):
         raise HspError("gemm_rows: xyz3 (M,3) and w3 (N,3) go together")
-    flops = 2 * M * N * (K1 + K2)
     es = 4 if dt == torch.float32 else 2
     ab = es * (M * (K1 + K2) + N * (K1 + K2) + M * N * (2 if resid is not None else 1))
-    key = f"M{M}N{N}K{K1}" + (f"+{K2}" if K2 else "")
     wsb = lib().hsp_gemm_rows_workspace_bytes(M, N, K1, K2, es)       # split-K partial tiles (0 for most shapes)
     ws = _ws(wsb, A1.device) if wsb else None
+    epilogue = _gemm_epilogue(M, N, bias, resid, cloud_bias, rows_per_cloud, alpha, out, (xyz3, w3))
     if dt == torch.float32:
-        _run("hsp_gemm_rows_f32", (_p(A1), _ld(A1), _p(B1), _ld(B1), 1 if nn1 else 0, K1,
-                                   _p(A2), _ld(A2) if A2 is not None else 0, _p(B2), _ld(B2) if B2 is not None else 0,
-                                   1 if nn2 else 0, K2, M, N, _p(bias), _p(resid), _ld(resid) if resid is not None else 0,
-                                   _p(cloud_bias), int(rows_per_cloud), float(alpha), _p(xyz3), _p(w3), _p(out), _ld(out),
-                                   _p(ws), wsb, _stream()),
+        _run("hsp_gemm_rows_f32", (*_gemm_sources(A1, _w(B1, nn1), K1, A2, _w(B2, nn2), K2), *epilogue, _p(ws), wsb, _stream()),
              key=key, abytes=ab, aflops=flops)
     else:
         if nn1 or nn2:
             raise HspError("gemm_rows: bf16 operands must be (N,K) (pass the transposed copy)")
-        _run("hsp_gemm_rows_bf16", (_p(A1), _ld(A1), _p(B1), _ld(B1), K1,
-                                    _p(A2), _ld(A2) if A2 is not None else 0, _p(B2), _ld(B2) if B2 is not None else 0, K2,
-                                    M, N, _p(bias), _p(resid), _ld(resid) if resid is not None else 0, _p(cloud_bias),
-                                    int(rows_per_cloud), float(alpha), _p(xyz3), _p(w3), _p(out), _ld(out),
+        _run("hsp_gemm_rows_bf16", (*_gemm_sources(A1, _w(B1), K1, A2, _w(B2), K2), *epilogue,
                                     1 if out.dtype == torch.float32 else 0, _p(ws), wsb, _stream()),
              key=key + "bf16", abytes=ab, aflops=flops)
     return out
@@ -971,19 +983,12 @@ def gemm_wave(A1, B1, nn1=False, A2=None, B2=None, nn2=False, bias=None, resid=N
               out=None, alpha=1.0, xyz3=None, w3=None, cfg=0):
     """the contract of ``gemm_rows`` (fp32 only) on the LDS-free wave-level kernel (csrc/gemm_wave.hip): K1, K2 multiples of
     32, N of 32, 16-byte aligned rows.  ``cfg`` != 0 forces a tile / cut (include/hsp.h), for tuning."""
-    M, K1 = A1.shape
-    N = B1.shape[1] if nn1 else B1.shape[0]
-    K2 = A2.shape[1] if A2 is not None else 0
+    M, N, K1, K2, flops, key = _gemm_dims(A1, B1, nn1, A2)
     if out is None:
         out = torch.empty(M, N, dtype=torch.float32, device=A1.device)
-    flops = 2 * M * N * (K1 + K2)
-    ab = 4 * (M * (K1 + K2) + N * (K1 + K2) + M * N * (2 if resid is not None else 1))
-    _run("hsp_gemm_wave_f32", (_p(A1), _ld(A1), _p(B1), _ld(B1), 1 if nn1 else 0, K1,
-                               _p(A2), _ld(A2) if A2 is not None else 0, _p(B2), _ld(B2) if B2 is not None else 0,
-                               1 if nn2 else 0, K2, M, N, _p(bias), _p(resid), _ld(resid) if resid is not None else 0,
-                               _p(cloud_bias), int(rows_per_cloud), float(alpha), _p(xyz3), _p(w3), _p(out), _ld(out),
-                               int(cfg), _stream()),
-         key=f"M{M}N{N}K{K1}" + (f"+{K2}" if K2 else ""), abytes=ab, aflops=flops)
+    _run("hsp_gemm_wave_f32", (*_gemm_sources(A1, _w(B1, nn1), K1, A2, _w(B2, nn2), K2),
+                               *_gemm_epilogue(M, N, bias, resid, cloud_bias, rows_per_cloud, alpha, out, (xyz3, w3)), int(cfg), _stream()),
+         key=key, abytes=4 * (M * (K1 + K2) + N * (K1 + K2) + M * N * (2 if resid is not None else 1)), aflops=flops)
     return out
 
 
@@ -1115,9 +1120,13 @@ class X3Planes:
             tile0 += ((e["N"] + 31) // 32) * ((e["K"] + 63) // 64)        # pieces of 32 (n) x 64 (k) output elements
         return upload_table(tab, ents[0]["src"].device), tile0
 
+    @staticmethod
+    def _launch(table, n, tiles, key, abytes):
+        _run("hsp_split_params_x3", (_p(table), n, tiles, _stream()), key=key, abytes=abytes)
+
     def _split(self, ents):
         tab, tiles = self._table_of(ents)
-        _run("hsp_split_params_x3", (_p(tab), len(ents), tiles, _stream()), key=f"n{len(ents)}")
+        self._launch(tab, len(ents), tiles, f"n{len(ents)}", 0)
         return tab
 
     def refresh(self):
@@ -1126,8 +1135,8 @@ class X3Planes:
         if not self._captured and torch.cuda.is_current_stream_capturing():
             self._captured = True
         ents, dirs = list(self.entries.values()), list(self.dirs.values())      # (the table holds both, in this order)
-        _run("hsp_split_params_x3", (_p(self.table), len(ents) + len(dirs), self.total_tiles, _stream()), key=f"n{len(ents)}",
-             abytes=sum(10 * e["N"] * e["K"] for e in ents) + sum(24 * e["SC"] for e in dirs))
+        self._launch(self.table, len(ents) + len(dirs), self.total_tiles, f"n{len(ents)}",
+                     sum(10 * e["N"] * e["K"] for e in ents) + sum(24 * e["SC"] for e in dirs))
         for e in ents + dirs:
             e["ver"] = e["src"]._version
         for e in dirs:
@@ -1183,11 +1192,11 @@ def _gemm_route(A1, B1, nn1=False, A2=None, B2=None, nn2=False, bias=None, resid
     """the kernel family (``_lib.GEMM_ROUTE_*``) a product of the ``gemm_rows`` contract goes to: the library's answer
     (``hsp_gemm_route``, include/hsp.h) to the call described as an ``HspGemmCall``.  out None: a dense result the wrapper allocates;
     bn: the BatchNorm-partials form asked for (``_lib.GEMM_BN_*``)"""
-    N = B1.shape[1] if nn1 else B1.shape[0]
+    M, N, K1, K2, _, _ = _gemm_dims(A1, B1, nn1, A2)
     two = A2 is not None
     call = HspGemmCall(A1.data_ptr(), B1.data_ptr(), A2.data_ptr() if two else None, B2.data_ptr() if two else None,
                        resid.data_ptr() if resid is not None else None, out.data_ptr() if out is not None else None,
-                       A1.shape[0], N, A1.shape[1], A2.shape[1] if two else 0, int(nn1), int(nn2), A1.element_size(),
+                       M, N, K1, K2, int(nn1), int(nn2), A1.element_size(),
                        _ld(A1), _ld(B1), _ld(A2) if two else 0, _ld(B2) if two else 0, _ld(resid) if resid is not None else 0,
                        _ld(out) if out is not None else N, bias is not None, cloud_bias is not None, xyz3 is not None, bool(relu),
                        alpha == 1.0, int(rows_per_cloud), bn, GEMM_X3)
@@ -1198,19 +1207,13 @@ def gemm_x3_bn(A1, B1, A2, B2, resid, cloud_bias, rows_per_cloud, out):
     """the layer's out product  A1 B1^T + A2 B2^T + resid + cloud_bias[cloud]  on csrc/gemm_x3.hip that also leaves the first pass
     of the BatchNorm that follows: returns ONE tensor (1 + 2 tiles, N): row 0 = the shift the kernel chose, rows 1.. = the
     (tiles, 2, N) shifted partial sums"""
-    M, K1 = A1.shape
-    N = B1.shape[0]
-    P1, ldp1, ps1 = x3_planes.planes(B1, False)
-    P2, ldp2, ps2 = x3_planes.planes(B2, False)
+    M, N, K1, K2, flops, key = _gemm_dims(A1, B1, False, A2)
     # (64-row tiles whatever the shape: the layout include/hsp.h gives for hsp_gemm_x3_bn_f32.  hsp_gemm_x3_bn_tiles speaks for
     # hsp_gemm_x3_bias_bn_f32, whose tiles are 128 rows on large products)
     buf = torch.empty(1 + 2 * ((M + 63) // 64), N, dtype=torch.float32, device=A1.device)
-    bn_shift, part = buf[0], buf[1:]
-    _run("hsp_gemm_x3_bn_f32", (_p(A1), _ld(A1), _p(P1), ldp1, ps1, K1, _p(A2), _ld(A2), _p(P2), ldp2, ps2, A2.shape[1], M, N,
-                                _p(resid), _ld(resid), _p(cloud_bias), int(rows_per_cloud), _p(out), _ld(out), _p(bn_shift),
-                                _p(part), _stream()),
-         key=f"M{M}N{N}K{K1}+{A2.shape[1]}bn", abytes=4 * (M * (K1 + A2.shape[1]) + 2 * M * N) + 6 * N * (K1 + A2.shape[1]),
-         aflops=2 * M * N * (K1 + A2.shape[1]))
+    _run("hsp_gemm_x3_bn_f32", (*_gemm_sources(A1, _x3w(B1, False), K1, A2, _x3w(B2, False), K2), M, N, _p(resid), _ld(resid),
+                                _p(cloud_bias), int(rows_per_cloud), _p(out), _ld(out), _p(buf[0]), _p(buf[1:]), _stream()),
+         key=key + "bn", abytes=4 * (M * (K1 + K2) + 2 * M * N) + 6 * N * (K1 + K2), aflops=flops)
     return buf
 
 
@@ -1218,22 +1221,20 @@ def linear_bn_part_ok(x2, W, bias):
     """a Linear (R, K) x (N, K)^T + bias whose product can also leave the first pass of the train-mode BatchNorm behind it
     (``hsp_gemm_x3_bias_bn_f32``)"""
     N = W.shape[0]
-    return (bias is not None and _takes("hsp_bn_takes", x2.shape[0], N)
+    return (bias is not None and _bn_takes(x2.shape[0], N)
             and _gemm_route(x2, W, bias=bias, bn=BN_LINEAR) == ROUTE_X3_BN)
 
 
 def linear_bn_part(x2, W, bias):
     """(x2 W^T + bias,  BatchNorm first-pass buffer (1 + 2 tiles, N): row 0 = the shift (the bias), rows 1.. = (tiles, 2, N)
     shifted column sums of the result) -- the layout ``bn_relu(..., partial=)`` folds"""
-    M, K1 = x2.shape
-    N = W.shape[0]
-    P1, ldp1, ps1 = x3_planes.planes(W, False)
+    M, N, K1, _, flops, key = _gemm_dims(x2, W)
+    w1 = _x3w(W, False)
     tiles = lib().hsp_gemm_x3_bn_tiles(M, N)
     out = torch.empty(M, N, dtype=torch.float32, device=x2.device)
     buf = torch.empty(1 + 2 * tiles, N, dtype=torch.float32, device=x2.device)
-    _run("hsp_gemm_x3_bias_bn_f32", (_p(x2), _ld(x2), _p(P1), ldp1, ps1, K1, M, N, _p(bias), _p(out), N, _p(buf[0]), _p(buf[1:]),
-                                     _stream()),
-         key=f"M{M}N{N}K{K1}bn", abytes=4 * (M * K1 + M * N) + 6 * N * K1, aflops=2 * M * N * K1)
+    _run("hsp_gemm_x3_bias_bn_f32", (_p(x2), _ld(x2), *w1, K1, M, N, _p(bias), _p(out), N, _p(buf[0]), _p(buf[1:]), _stream()),
+         key=key + "bn", abytes=4 * (M * K1 + M * N) + 6 * N * K1, aflops=flops)
     return out, buf
 
 
@@ -1242,24 +1243,22 @@ def gemm_x3(A1, B1, nn1=False, A2=None, B2=None, nn2=False, bias=None, resid=Non
     """the contract of ``gemm_rows`` (fp32 in, fp32 out) with the products formed on the bf16 matrix cores from exact three-way
     bf16 splits of both operands (csrc/gemm_x3.hip): B* are the fp32 weight matrices, split (and transposed where ``nn``) by
     ``x3_planes``"""
-    M, K1 = A1.shape
-    N = B1.shape[1] if nn1 else B1.shape[0]
-    P1, ldp1, ps1 = x3_planes.planes(B1, nn1)
-    K2, P2, ldp2, ps2 = 0, None, 0, 0
-    if A2 is not None:
-        K2 = A2.shape[1]
-        P2, ldp2, ps2 = x3_planes.planes(B2, nn2)
+    M, N, K1, K2, flops, key = _gemm_dims(A1, B1, nn1, A2)
+    w1, w2 = _x3w(B1, nn1), _x3w(B2, nn2) if A2 is not None else (_vp(0), 0, 0)
     if out is None:
         out = torch.empty(M, N, dtype=torch.float32, device=A1.device)
     wsb = lib().hsp_gemm_x3_workspace_bytes(M, N, K1, K2)
     ws = _ws(wsb, A1.device) if wsb else None
-    flops = 2 * M * N * (K1 + K2)
-    ab = 4 * (M * (K1 + K2) + M * N * (2 if resid is not None else 1)) + 6 * N * (K1 + K2)
-    _run("hsp_gemm_x3_f32", (_p(A1), _ld(A1), _p(P1), ldp1, ps1, K1, _p(A2), _ld(A2) if A2 is not None else 0, _p(P2), ldp2, ps2, K2,
-                             M, N, _p(bias), _p(resid), _ld(resid) if resid is not None else 0, _p(cloud_bias), int(rows_per_cloud),
-                             float(alpha), _p(out), _ld(out), _p(ws), wsb, _stream()),
-         key=f"M{M}N{N}K{K1}" + (f"+{K2}" if K2 else ""), abytes=ab, aflops=flops)
+    _run("hsp_gemm_x3_f32", (*_gemm_sources(A1, w1, K1, A2, w2, K2), *_gemm_epilogue(M, N, bias, resid, cloud_bias, rows_per_cloud, alpha, out),
+                             _p(ws), wsb, _stream()),
+         key=key, abytes=4 * (M * (K1 + K2) + M * N * (2 if resid is not None else 1)) + 6 * N * (K1 + K2), aflops=flops)
     return out
+
+
+def _x3w(W, transpose):
+    """a source's weight side for the x3 entry points: (planes, pitch, plane stride) of the fp32 matrix W from the current registry"""
+    P, ldp, ps = x3_planes.planes(W, transpose)
+    return _p(P), ldp, ps
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1327,6 +1326,8 @@ _copies = {}
 def copies_of(param):
     """(bf16 copy, bf16 transposed copy) of a WHOLE 2-D parameter, as ``ops_bf16.Bf16Params`` registered and last refreshed them"""
     hit = _copies.get(param.data_ptr())
+    if hit is not None and hit[2] is not None and hit[2]() is None:
+        hit = None                            # registered by a Bf16Params that has died: the address now belongs to another tensor
     if hit is not None:                       # the address may have been re-used by another tensor since: the shape must match
         c, ct = hit[0], hit[1]
         shape = tuple(param.shape)
@@ -1546,22 +1547,44 @@ def _orl_bwd_accumulate_raw(gfg_over_n, idx_x, arg, k, gF3, extra=None, counts=N
     (the reverse-edge form of DETERMINISTIC is fp32-only).  ``counts``: that number as the forward left it (``_orl_fwd_counts_raw``) --
     then a stream pass, same bits"""
     B, N, C = gF3.shape
+    dims = (B, N, N, N, idx_x.shape[2], C)
     if DETERMINISTIC and gF3.dtype == torch.float32:
         tmp = torch.empty_like(gF3)
-        off, edge = rev_index(idx_x, k, N)
-        _run("hsp_gather_max_bwd_csr", (_p(gfg_over_n), 1, _p(arg), _p(off), _p(edge), B, N, N, k, C, _p(tmp), _stream()),
-             key=f"B{B}Ns{N}Nq{N}k{k}C{C}bc", abytes=B * N * (4 * C + 8 * k + C))
+        _gather_max_bwd_csr_raw(gfg_over_n, True, idx_x, None, 0, arg, k, dims, tmp)
         gF3.add_(tmp)
         if extra is not None:
             gF3.add_(extra)
     elif counts is not None:
-        _run("hsp_gather_max_bwd" + _sfx(gF3), (_p(gfg_over_n), 2, _vp(0), _vp(0), _p(counts), B, N, N, N, idx_x.shape[2], C,
-                                                _p(gF3), 1, _p(extra), _stream()),
-             key=f"B{B}Ns{N}Nq{N}C{C}cnt+", abytes=B * N * C * (3 * _es(gF3) + 2))
+        _gather_max_bwd_raw(gfg_over_n, 2, None, None, 0, counts, dims, gF3, True, extra)
     else:
-        _run("hsp_gather_max_bwd" + _sfx(gF3), (_p(gfg_over_n), 1, _p(idx_x), _vp(0), _p(arg), B, N, N, N, idx_x.shape[2], C,
-                                                _p(gF3), 1, _p(extra), _stream()),
-             key=f"B{B}Ns{N}Nq{N}C{C}bc+", abytes=B * N * (3 * _es(gF3) * C + 4 * idx_x.shape[2] + C))
+        _gather_max_bwd_raw(gfg_over_n, 1, idx_x, None, 0, arg, dims, gF3, True, extra)
+
+
+def _rf_surface_fwd_raw(xyz, idx, directions, S, out_dtype):
+    """(F3 (B,N,C) in ``out_dtype``, argrow (B,N,SC) uint16) of HSlayer_surface.graph_conv; the caller has passed ``directions``
+    through ``dirs_fresh``.  (Deliberate: the fp32 figures count a one-byte arg-max slot -- DESIGN.md section 4 --, the bf16 ones
+    the two-byte winning-row slot the kernels write; here and in the backward.)"""
+    B, N, k = idx.shape
+    SC = directions.shape[1]
+    C = SC // S
+    F3 = torch.empty(B, N, C, dtype=out_dtype, device=xyz.device)
+    arg = torch.empty(B, N, SC, dtype=torch.uint16, device=xyz.device)
+    slot = 1 if out_dtype == torch.float32 else 2
+    _run("hsp_rf_surface_fwd" + _sfx(F3), (_p(xyz), _p(idx), _p(directions), B, N, k, S, C, _p(F3), _p(arg), _stream()),
+         key=f"B{B}N{N}k{k}S{S}C{C}", abytes=B * N * (12 + 4 * k + _es(F3) * C + slot * SC) + 12 * SC)
+    return F3, arg
+
+
+def _rf_surface_bwd_raw(xyz, directions, arg, g, S):
+    """gD (3,SC): the direction gradient of ``_rf_surface_fwd_raw`` for the fp32 / bf16 gradient rows g (B,N,C)"""
+    B, N, C = g.shape
+    SC = S * C
+    gD = torch.empty_like(dirs_fresh(directions))
+    wsb = lib().hsp_rf_bwd_scatter_workspace_bytes(B, SC)
+    ws = _ws(wsb, g.device)
+    _rf_bwd_dirs_call("hsp_rf_surface_bwd", _sfx(g), (_p(xyz), _p(directions), _p(arg), _p(g), B, N, S, C, _p(gD)), ws, wsb,
+                      (directions, gD), key=f"B{B}N{N}S{S}C{C}", abytes=B * N * (12 + _es(g) * C + (1 if _es(g) == 4 else 2) * SC) + 24 * SC)
+    return gD
 
 
 def _rf_conv_fwd_raw(xyz, idx, directions, fm, S, need_bwd=True):
@@ -1821,13 +1844,7 @@ class _SurfaceLayer(torch.autograd.Function):
         C = SC // S
         if idx_x.shape[2] != k:
             raise HspError("surface_layer: idx must have exactly k columns")
-        F3 = torch.empty(B, N, C, dtype=out_dtype, device=xyz.device)
-        arg = torch.empty(B, N, SC, dtype=torch.uint16, device=xyz.device)
-        # (deliberate: the fp32 figures count a one-byte arg-max slot -- DESIGN.md section 4 --, the bf16 ones the two-byte
-        # winning-row slot the kernels write; here and in the backward)
-        slot = 1 if out_dtype == torch.float32 else 2
-        _run("hsp_rf_surface_fwd" + _sfx(F3), (_p(xyz), _p(idx_x), _p(directions), B, N, k, S, C, _p(F3), _p(arg), _stream()),
-             key=f"B{B}N{N}k{k}S{S}C{C}", abytes=B * N * (12 + 4 * k + _es(F3) * C + slot * SC) + 12 * SC)
+        F3, arg = _rf_surface_fwd_raw(xyz, idx_x, directions, S, out_dtype)
         F2, x2 = F3.view(B * N, C), xyz.view(B * N, 3)
         out3 = torch.empty(B, N, C, dtype=out_dtype, device=xyz.device)
         if _exact and _exact_layer_ok(N, 3, C, (w_conv2, F2)):                # (fp32 rows only)
@@ -1869,7 +1886,6 @@ class _SurfaceLayer(torch.autograd.Function):
         g = _reqf(g, "surface_layer.grad", like=F3)
         f32 = g.dtype == torch.float32
         B, N, C = F3.shape
-        SC = directions.shape[1]
         g2, F2, x2 = g.view(B * N, C), F3.view(B * N, C), xyz.view(B * N, 3)
         Wb = w_conv2[:, C:]
         g_conv2 = torch.empty_like(w_conv2)
@@ -1904,13 +1920,7 @@ class _SurfaceLayer(torch.autograd.Function):
         if not small:
             gfg_n = _mm_nn(gt, Wb, alpha=1.0 / N)
         _orl_bwd_accumulate_raw(gfg_n, idx_x, arg_o, k, gF3, extra=g, counts=cnt_o)
-        gD = torch.empty_like(dirs_fresh(directions))
-        L = lib()
-        wsb = L.hsp_rf_bwd_scatter_workspace_bytes(B, SC)
-        ws = _ws(wsb, g.device)
-        _rf_bwd_dirs_call("hsp_rf_surface_bwd", _sfx(g), (_p(xyz), _p(directions), _p(arg), _p(gF3), B, N, S, C, _p(gD)), ws, wsb,
-                          (directions, gD), key=f"B{B}N{N}S{S}C{C}",
-                          abytes=B * N * (12 + _es(g) * C + (1 if f32 else 2) * SC) + 24 * SC)
+        gD = _rf_surface_bwd_raw(xyz, directions, arg, gF3, S)
         if not own_ste:
             # (C,3): three columns -- not a matrix-core shape
             g_ste = wgrad(g2, x2) if f32 else g2.float().t() @ x2
@@ -2270,34 +2280,89 @@ def _rows_pitch(t, C):
     return t.contiguous(), C
 
 
+# The BatchNorm entry points, each marshalled here and nowhere else (ops_bf16's heads call these too).  x (..., C) are contiguous
+# rows, R = their number; the entry is chosen by (dtype of the rows read, dtype of the rows written): fp32 -> fp32 "", bf16 -> bf16
+# "_bf16", fp32 -> bf16 "_mixed".  The forwards return (y, saved mean, saved invstd), the backwards (dx, d weight, d bias).
+def _bn_takes(R, C):
+    """the widths / row counts the BatchNorm kernels take"""
+    return _takes("hsp_bn_takes", R, C)
+
+
+def _bn_sfx(src, dst):
+    return "_bf16" if src == torch.bfloat16 else "_mixed" if dst == torch.bfloat16 else ""
+
+
+def _bn_alloc(x, ydtype, workspace=True):
+    """(R, C, rows like x in ``ydtype``, two fp32 (C,) vectors, ws, ws_bytes): what a train-mode pass over x writes -- y, mean,
+    invstd forward; dx, d weight, d bias backward"""
+    C = x.shape[-1]
+    R = x.numel() // C
+    wsb = lib().hsp_bn_workspace_bytes(R, C) if workspace else 0
+    return (R, C, torch.empty_like(x, dtype=ydtype), torch.empty(C, dtype=torch.float32, device=x.device),
+            torch.empty(C, dtype=torch.float32, device=x.device), _ws(wsb, x.device) if workspace else None, wsb)
+
+
+def _bn_fwd_raw(x, state, relu, ydtype, partial=None):
+    """train-mode relu(bn(x)); state = (weight, bias, running_mean, running_var, num_batches, eps, momentum).  ``partial`` = (part
+    (tiles, 2, C), tiles, shift (C,)): the first pass over fp32 rows as the producing product left it -- fold + apply only"""
+    weight, bias, running_mean, running_var, num_batches, eps, momentum = state
+    R, C, y, mean, invstd, ws, wsb = _bn_alloc(x, ydtype, workspace=partial is None)
+    head = (_p(x), R, C, _p(weight), _p(bias), float(eps), float(momentum), 1 if relu else 0, _p(y), _p(mean), _p(invstd),
+            _p(running_mean), _p(running_var), _p(num_batches))
+    key, ab = f"R{R}C{C}", (_es(x) + _es(y)) * R * C
+    if partial is None:
+        _run("hsp_bn_relu_fwd" + _bn_sfx(x.dtype, ydtype), (*head, _p(ws), wsb, _stream()), key=key, abytes=ab)
+    else:
+        _run("hsp_bn_relu_fwd_partials" + _bn_sfx(x.dtype, ydtype), (*head, _p(partial[0]), partial[1], _p(partial[2]), _stream()),
+             key=key, abytes=ab)
+    return y, mean, invstd
+
+
+def _bn_apply_raw(x, running_mean, invstd, weight, bias, relu):
+    """eval mode: relu(bn(x)) from the running statistics for bf16 / fp32 rows -> bf16 rows"""
+    C = x.shape[-1]
+    y = torch.empty_like(x, dtype=torch.bfloat16)
+    _run("hsp_bn_relu_apply" + _bn_sfx(x.dtype, y.dtype), (_p(x), x.numel() // C, C, _p(running_mean), _p(invstd), _p(weight), _p(bias),
+                                                          1 if relu else 0, _p(y), _stream()),
+         key=f"R{x.numel() // C}C{C}", abytes=(_es(x) + 2) * x.numel())
+    return y
+
+
+def _bn_bwd_raw(x, dy, weight, bias, mean, invstd, relu):
+    R, C, dx, dg, db, ws, wsb = _bn_alloc(dy, dy.dtype)
+    _run("hsp_bn_relu_bwd" + _bn_sfx(x.dtype, dy.dtype),
+         (_p(x), _p(dy), R, C, _p(weight), _p(bias), _p(mean), _p(invstd), 1 if relu else 0, _p(dx), _p(dg), _p(db), _p(ws), wsb,
+          _stream()), key=f"R{R}C{C}", abytes=(_es(x) + 2 * _es(dy)) * R * C)
+    return dx, dg, db
+
+
+def _bn_bwd2_raw(x, dys, weight, bias, mean, invstd, relu):
+    """``_bn_bwd_raw`` for fp32 rows whose result went to two consumers: their gradients dys (one or two, walked at their own row
+    pitch) are added as they are read"""
+    R, C, dx, dg, db, ws, wsb = _bn_alloc(x, x.dtype)
+    (d0, ld0) = _rows_pitch(dys[0], C)
+    (d1, ld1) = _rows_pitch(dys[1], C) if len(dys) > 1 else (None, 0)
+    _run("hsp_bn_relu_bwd2", (_p(x), _p(d0), ld0, _p(d1), ld1, R, C, _p(weight), _p(bias), _p(mean), _p(invstd), 1 if relu else 0,
+                              _p(dx), _p(dg), _p(db), _p(ws), wsb, _stream()), key=f"R{R}C{C}", abytes=4 * (2 + len(dys)) * R * C)
+    return dx, dg, db
+
+
 class _BNRelu(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, running_mean, running_var, num_batches, eps, momentum, relu, out_dtype=None, fork=False,
                 partial=None):
         x = _reqf(x, "bn_relu.x")
-        C = x.shape[-1]
-        R = x.numel() // C
         # "mixed": fp32 rows in (a pre-BatchNorm tensor keeps its mantissa: |mean| >> std per channel is common), bf16 out
         mixed = out_dtype == torch.bfloat16 and x.dtype == torch.float32
-        y = torch.empty_like(x, dtype=torch.bfloat16) if mixed else torch.empty_like(x)
         ctx.mixed = mixed
-        mean = torch.empty(C, dtype=torch.float32, device=x.device)
-        invstd = torch.empty(C, dtype=torch.float32, device=x.device)
-        L = lib()
-        wsb = L.hsp_bn_workspace_bytes(R, C)
-        ws = _ws(wsb, x.device)
         if partial is not None and partial.numel() and not mixed and x.dtype == torch.float32 and running_mean is not None:
             # the first pass (row 0 of ``partial``: the shift; then the shifted column sums per row tile) was left by the producer's
-            # epilogue (hsp_gemm_x3_bn_f32): fold + apply only
-            _run("hsp_bn_relu_fwd_partials", (_p(x), R, C, _p(weight), _p(bias), float(eps), float(momentum), 1 if relu else 0, _p(y),
-                                              _p(mean), _p(invstd), _p(running_mean), _p(running_var), _p(num_batches),
-                                              _p(partial[1:]), (partial.shape[0] - 1) // 2, _p(partial[0]), _stream()),
-                 key=f"R{R}C{C}", abytes=8 * R * C)
+            # epilogue (hsp_gemm_x3_bn_f32)
+            partial = (partial[1:], (partial.shape[0] - 1) // 2, partial[0])
         else:
-            _run("hsp_bn_relu_fwd" + ("_mixed" if mixed else _sfx(x)), (_p(x), R, C, _p(weight), _p(bias), float(eps), float(momentum), 1 if relu else 0,
-                                               _p(y), _p(mean), _p(invstd), _p(running_mean), _p(running_var), _p(num_batches),
-                                               _p(ws), wsb, _stream()),
-                 key=f"R{R}C{C}", abytes=(_es(x) + _es(y)) * R * C)
+            partial = None
+        y, mean, invstd = _bn_fwd_raw(x, (weight, bias, running_mean, running_var, num_batches, eps, momentum), relu,
+                                      torch.bfloat16 if mixed else x.dtype, partial)
         ctx.save_for_backward(x, weight, bias, mean, invstd)
         ctx.relu = relu
         ctx.fork = fork
@@ -2312,31 +2377,14 @@ class _BNRelu(torch.autograd.Function):
     @staticmethod
     def backward(ctx, *dys):
         x, weight, bias, mean, invstd = ctx.saved_tensors
-        C = x.shape[-1]
-        R = x.numel() // C
         dys = [d for d in dys if d is not None]
         if not dys:
             return (None,) * 12
-        L = lib()
-        wsb = L.hsp_bn_workspace_bytes(R, C)
-        ws = _ws(wsb, x.device)
-        dg = torch.empty_like(weight)
-        db = torch.empty_like(bias)
         if ctx.fork and not ctx.mixed and x.dtype == torch.float32 and all(d.is_cuda and d.dtype == torch.float32 for d in dys):
-            (d0, ld0) = _rows_pitch(dys[0], C)
-            (d1, ld1) = _rows_pitch(dys[1], C) if len(dys) > 1 else (None, 0)
-            dx = torch.empty_like(x)
-            _run("hsp_bn_relu_bwd2", (_p(x), _p(d0), ld0, _p(d1), ld1, R, C, _p(weight), _p(bias), _p(mean), _p(invstd),
-                                      1 if ctx.relu else 0, _p(dx), _p(dg), _p(db), _p(ws), wsb, _stream()),
-                 key=f"R{R}C{C}", abytes=4 * (2 + len(dys)) * R * C)
-            return dx, dg, db, None, None, None, None, None, None, None, None, None
+            return (*_bn_bwd2_raw(x, dys, weight, bias, mean, invstd, ctx.relu), *(None,) * 9)
         dy = dys[0] if len(dys) == 1 else dys[0] + dys[1]
         dy = _reqf(dy, "bn_relu.grad", like=None if ctx.mixed else x)
-        dx = torch.empty_like(dy)
-        _run("hsp_bn_relu_bwd" + ("_mixed" if ctx.mixed else _sfx(x)), (_p(x), _p(dy), R, C, _p(weight), _p(bias), _p(mean), _p(invstd),
-                                           1 if ctx.relu else 0, _p(dx), _p(dg), _p(db), _p(ws), wsb, _stream()),
-             key=f"R{R}C{C}", abytes=(_es(x) + 2 * _es(dy)) * R * C)
-        return dx, dg, db, None, None, None, None, None, None, None, None, None
+        return (*_bn_bwd_raw(x, dy, weight, bias, mean, invstd, ctx.relu), *(None,) * 9)
 
 
 def _eval_invstd(bn):
@@ -2389,19 +2437,14 @@ def bn_relu(x, bn, relu=True, out_dtype=None, fork=False, partial=None):
     TWICE (two tensors over the same rows) for a tensor with two consumers -- their gradients then reach the BatchNorm backward
     separately and are added inside its kernels."""
     C = x.shape[-1]
-    takes = lambda: C > 0 and _takes("hsp_bn_takes", x.numel() // C, C)        # noqa: E731  (the BatchNorm kernels' widths)
+    takes = lambda: C > 0 and _bn_takes(x.numel() // C, C)        # noqa: E731  (the BatchNorm kernels' widths)
     fused = (bn.training and bn.affine and bn.track_running_stats and bn.momentum is not None and x.is_cuda
              and x.dtype in _FEAT_DTYPES and takes())
     want_bf16 = x.dtype == torch.bfloat16 or out_dtype == torch.bfloat16
     if not fused and want_bf16:                      # eval mode, bf16 rows out: running statistics, fused affine + ReLU
         if bn.training or not bn.affine or not takes():
             raise HspError("bn_relu: this BatchNorm configuration is not built for bf16 rows")
-        xc = _reqf(x, "bn_relu.x")
-        y = torch.empty_like(xc, dtype=torch.bfloat16)
-        invstd = torch.rsqrt(bn.running_var + bn.eps)
-        _run("hsp_bn_relu_apply" + ("_bf16" if xc.dtype == torch.bfloat16 else "_mixed"),
-             (_p(xc), xc.numel() // C, C, _p(bn.running_mean), _p(invstd), _p(bn.weight), _p(bn.bias), 1 if relu else 0, _p(y),
-              _stream()), key=f"R{xc.numel() // C}C{C}", abytes=(_es(xc) + 2) * xc.numel())
+        y = _bn_apply_raw(_reqf(x, "bn_relu.x"), bn.running_mean, torch.rsqrt(bn.running_var + bn.eps), bn.weight, bn.bias, relu)
         return (y, y) if fork else y
     if (not fused and not bn.training and bn.affine and bn.track_running_stats and x.is_cuda and x.dtype == torch.float32
             and C % 4 == 0 and x.is_contiguous()):
@@ -2427,6 +2470,22 @@ def bn_relu(x, bn, relu=True, out_dtype=None, fork=False, partial=None):
 def _csr_takes(g, C, gstride):
     """True where ``hsp_gather_rows_bwd_csr(_bf16)`` takes the C-column gradient (segment) g at row stride ``gstride``"""
     return _takes("hsp_gather_rows_bwd_csr_takes", _es(g), C, gstride, g.data_ptr() % 16)
+
+
+def _gather_rows_bwd_raw(g, gstride, idx, shared, dims, gfeat):
+    """gfeat (B,Nsrc,C) = the fp32 gradient rows g (row stride ``gstride``) added to the rows idx lists, in arrival order"""
+    B, Nsrc, Nq, C = dims
+    _run("hsp_gather_rows_bwd", (_p(g), gstride, _p(idx), shared, B, Nsrc, Nq, C, _p(gfeat), _stream()),
+         key=f"B{B}Ns{Nsrc}Nq{Nq}C{C}", abytes=B * (4 * Nsrc * C + Nq * (4 + 4 * C)))
+
+
+def _gather_rows_bwd_csr_raw(g, gstride, idx, dims, gfeat):
+    """the same in gather form over the reverse map of the per-cloud idx (B,Nq) (memoised on idx), ascending query order; fp32 /
+    bf16 rows.  The caller has asked ``_csr_takes``."""
+    B, Nsrc, Nq, C = dims
+    off, edge = rev_index(idx, 1, Nsrc)
+    _run("hsp_gather_rows_bwd_csr" + _sfx(g), (_p(g), gstride, _p(off), _p(edge), B, Nsrc, Nq, C, _p(gfeat), _stream()),
+         key=f"B{B}Ns{Nsrc}Nq{Nq}C{C}", abytes=B * (_es(g) * Nsrc * C + Nq * (4 + _es(g) * C)))
 
 
 class _GatherRows(torch.autograd.Function):
@@ -2461,12 +2520,9 @@ class _GatherRows(torch.autograd.Function):
             # the gather form over the reverse map (ascending query order) wherever both entries take the operands -- a per-cloud
             # map, the widths / strides / alignment of the concat backward's segments, a cloud whose histogram the reverse build
             # holds --, decided before anything is launched; today's launch otherwise
-            off, edge = rev_index(idx, 1, Nsrc)
-            _run("hsp_gather_rows_bwd_csr", (_p(g), gstride, _p(off), _p(edge), B, Nsrc, Nq, C, _p(gfeat), _stream()),
-                 key=f"B{B}Ns{Nsrc}Nq{Nq}C{C}", abytes=B * (4 * Nsrc * C + Nq * (4 + 4 * C)))
-            return gfeat, None
-        _run("hsp_gather_rows_bwd", (_p(g), gstride, _p(idx), shared, B, Nsrc, Nq, C, _p(gfeat), _stream()),
-             key=f"B{B}Ns{Nsrc}Nq{Nq}C{C}", abytes=B * (4 * Nsrc * C + Nq * (4 + 4 * C)))
+            _gather_rows_bwd_csr_raw(g, gstride, idx, (B, Nsrc, Nq, C), gfeat)
+        else:
+            _gather_rows_bwd_raw(g, gstride, idx, shared, (B, Nsrc, Nq, C), gfeat)
         return gfeat, None
 
 
@@ -2617,14 +2673,11 @@ class _AssembleFeat(torch.autograd.Function):
                 gfeat = torch.empty(B, Ns, w, dtype=g.dtype, device=g.device)
                 if _csr_takes(gs, w, W):
                     # gather form over the reverse map (memoised on idx: fm_2 and fm_3 share one); deterministic
-                    off, edge = rev_index(idx, 1, Ns)
-                    _run("hsp_gather_rows_bwd_csr" + _sfx(g), (_p(gs), W, _p(off), _p(edge), B, Ns, N, w, _p(gfeat), _stream()),
-                         key=f"B{B}Ns{Ns}Nq{N}C{w}", abytes=B * (es * Ns * w + N * (4 + es * w)))
+                    _gather_rows_bwd_csr_raw(gs, W, idx, (B, Ns, N, w), gfeat)
                 elif g.dtype == torch.bfloat16:
                     raise HspError("assemble_feat backward: bf16 segments must be even-width and 4-byte aligned")
                 else:
-                    _run("hsp_gather_rows_bwd", (_p(gs), W, _p(idx), 0, B, Ns, N, w, _p(gfeat), _stream()),
-                         key=f"B{B}Ns{Ns}Nq{N}C{w}", abytes=B * (4 * Ns * w + N * (4 + 4 * w)))
+                    _gather_rows_bwd_raw(gs, W, idx, 0, (B, Ns, N, w), gfeat)
                 grads.append(gfeat)
             elif kd == 3:
                 grads.append(None)                                 # ids carry no gradient

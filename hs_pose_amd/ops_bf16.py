@@ -31,8 +31,7 @@ class Bf16Params:
 
     def __init__(self, specs):
         dev = specs[0][0].device
-        for key in [k_ for k_, v_ in _copies.items() if v_[2] is not None and v_[2]() is None]:
-            del _copies[key]                  # entries whose Bf16Params is gone
+        me = weakref.ref(self)
         self.entries = []
         self.pitched = any(len(sp) > 3 and sp[3] for sp in specs)
         tab = ((HspCastPitchedDesc if self.pitched else HspCastDesc) * len(specs))()
@@ -46,7 +45,7 @@ class Bf16Params:
             c = torch.empty(rows, ldd, dtype=BF16, device=dev)[:, :cols] if want else None
             ct = torch.empty(cols, rows, dtype=BF16, device=dev) if want_t else None
             self.entries.append((w2, c, ct))
-            _copies[w2.data_ptr()] = (c, ct, weakref.ref(self))
+            _copies[w2.data_ptr()] = (c, ct, me)
             row = (w2.data_ptr(), c.data_ptr() if c is not None else 0, ct.data_ptr() if ct is not None else 0, rows, cols,
                    w2.stride(0), tiles)
             tab[i] = row + ((ldd, rows) if self.pitched else ())          # src, dst, dstT, rows, cols, ld, tile0[, ldd, lddT]
@@ -55,6 +54,14 @@ class Bf16Params:
         self.n = len(specs)
         self.table = upload_table(tab, dev)
         self.ptrs = [w2.data_ptr() for w2, _, _ in self.entries]
+        weakref.finalize(self, Bf16Params._release, self.ptrs, me).atexit = False
+
+    @staticmethod
+    def _release(ptrs, me):
+        """this Bf16Params is gone (weakref.finalize): its copies leave the registry (an address a later one took over stays)"""
+        for ptr in ptrs:
+            if ptr in _copies and _copies[ptr][2] is me:
+                del _copies[ptr]
 
     def refresh(self):
         """round the current fp32 master weights into the working copies (call at the top of every forward)"""
@@ -89,20 +96,14 @@ def _bn_fwd(y, bn):
     R, C = y.shape
     if not _bn_ok(bn, R, C):
         raise HspError("bf16 heads: this BatchNorm configuration is not built")
-    a = torch.empty(R, C, dtype=BF16, device=y.device)
     if not bn.training:
-        invstd = _eval_invstd(bn)
-        _run("hsp_bn_relu_apply_mixed", (_p(y), R, C, _p(bn.running_mean), _p(invstd), _p(bn.weight), _p(bn.bias), 1, _p(a),
-                                         _stream()), key=f"R{R}C{C}", abytes=6 * R * C)
-        return a, None, None
-    mean = torch.empty(C, dtype=torch.float32, device=y.device)
-    invstd = torch.empty(C, dtype=torch.float32, device=y.device)
-    wsb = lib().hsp_bn_workspace_bytes(R, C)
-    ws = _ws(wsb, y.device)
-    _run("hsp_bn_relu_fwd_mixed", (_p(y), R, C, _p(bn.weight), _p(bn.bias), float(bn.eps), float(bn.momentum), 1, _p(a), _p(mean),
-                                   _p(invstd), _p(bn.running_mean), _p(bn.running_var), _p(bn.num_batches_tracked), _p(ws), wsb,
-                                   _stream()), key=f"R{R}C{C}", abytes=6 * R * C)
-    return a, mean, invstd
+        return ops._bn_apply_raw(y, bn.running_mean, _eval_invstd(bn), bn.weight, bn.bias, True), None, None
+    return ops._bn_fwd_raw(y, _bn_state(bn), True, BF16)
+
+
+def _bn_state(bn):
+    """a BatchNorm module's tensors and constants as ``ops._bn_fwd_raw`` takes them"""
+    return bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked, bn.eps, bn.momentum
 
 
 def _eval_invstd(bn):
@@ -119,13 +120,13 @@ def _eval_invstd(bn):
 
 
 def _bn_ok(bn, R, C):
-    return bn.affine and bn.track_running_stats and bn.momentum is not None and ops._takes("hsp_bn_takes", R, C)
+    return bn.affine and bn.track_running_stats and bn.momentum is not None and ops._bn_takes(R, C)
 
 
 def _product_bn(x, Wc, b, bn, out_cols, cloud_bias=None, rows_per_cloud=0, xyz3=None, w3=None):
     """y = x Wc^T + b (+ cloud_bias[row // rows_per_cloud]) (+ xyz3 . w3) in fp32 and a = relu(bn(y)) in bf16 -> (a, y, saved mean,
     saved invstd).  Train mode: the product leaves the BatchNorm's first pass in its epilogue (hsp_gemm_rows_bn_bf16) and
-    hsp_bn_relu_fwd_partials_mixed folds it and applies (y is read once); eval mode / more row tiles than the fold takes:
+    ``ops._bn_fwd_raw`` folds it and applies (y is read once); eval mode / more row tiles than the fold takes:
     hsp_gemm_rows_bf16 + _bn_fwd."""
     R, K = x.shape
     C = out_cols
@@ -139,29 +140,14 @@ def _product_bn(x, Wc, b, bn, out_cols, cloud_bias=None, rows_per_cloud=0, xyz3=
     _run("hsp_gemm_rows_bn_bf16", (_p(x), ops._ld(x), _p(Wc), ops._ld(Wc), K, R, C, _p(b), _p(cloud_bias), int(rows_per_cloud),
                                    _p(xyz3), _p(w3), _p(y), C, _p(buf[0]), _p(buf[1:]), _stream()),
          key=f"M{R}N{C}K{K}bn", abytes=2 * (R + C) * K + 4 * R * C, aflops=2 * R * C * K)
-    a = torch.empty(R, C, dtype=BF16, device=x.device)
-    mean = torch.empty(C, dtype=torch.float32, device=x.device)
-    invstd = torch.empty(C, dtype=torch.float32, device=x.device)
-    _run("hsp_bn_relu_fwd_partials_mixed", (_p(y), R, C, _p(bn.weight), _p(bn.bias), float(bn.eps), float(bn.momentum), 1, _p(a),
-                                            _p(mean), _p(invstd), _p(bn.running_mean), _p(bn.running_var),
-                                            _p(bn.num_batches_tracked), _p(buf[1:]), tiles, _p(buf[0]), _stream()),
-         key=f"R{R}C{C}", abytes=6 * R * C)
-    return y, a, mean, invstd
+    return (y,) + ops._bn_fwd_raw(y, _bn_state(bn), True, BF16, (buf[1:], tiles, buf[0]))
 
 
 def _bn_bwd(y, da, gamma, beta, mean, invstd):
     """(bf16 gradient of y, d gamma, d beta) of relu(bn(y)) under train-mode statistics"""
     if mean is None:
         raise HspError("bf16 heads: no backward through an eval-mode BatchNorm")
-    R, C = y.shape
-    da = _b(da, "bn_relu.grad")
-    g = torch.empty(R, C, dtype=BF16, device=y.device)
-    dg, db = torch.empty_like(gamma), torch.empty_like(beta)
-    wsb = lib().hsp_bn_workspace_bytes(R, C)
-    ws = _ws(wsb, y.device)
-    _run("hsp_bn_relu_bwd_mixed", (_p(y), _p(da), R, C, _p(gamma), _p(beta), _p(mean), _p(invstd), 1, _p(g), _p(dg), _p(db),
-                                   _p(ws), wsb, _stream()), key=f"R{R}C{C}", abytes=8 * R * C)
-    return g, dg, db
+    return ops._bn_bwd_raw(y, _b(da, "bn_relu.grad"), gamma, beta, mean, invstd, True)
 
 
 def _wgrad_now(A2, B2, colsum=False):
@@ -318,9 +304,7 @@ class _FanBN(torch.autograd.Function):
 def gemm_rows_acc(A1, B1, A2, B2, resid, out):
     """out = A1 B1^T (+ A2 B2^T) + resid for bf16 rows / (N,K) bf16 weights and an fp32 ``resid``; out fp32 or bf16
     (hsp_gemm_rows_acc_bf16).  out may be resid itself."""
-    M, K1 = A1.shape
-    N = B1.shape[0]
-    K2 = A2.shape[1] if A2 is not None else 0
+    M, N, K1, K2, flops, _ = ops._gemm_dims(A1, B1, False, A2)
     for t_ in (A1, B1, A2, B2):
         if t_ is not None and (t_.dtype != BF16 or not t_.is_cuda):
             raise HspError("gemm_rows_acc: bf16 GPU operands")
@@ -328,11 +312,9 @@ def gemm_rows_acc(A1, B1, A2, B2, resid, out):
         raise HspError("gemm_rows_acc: fp32 resid and out of shape (M, N)")
     wsb = lib().hsp_gemm_rows_workspace_bytes(M, N, K1, K2, 2)
     ws = _ws(wsb, A1.device) if wsb else None
-    _run("hsp_gemm_rows_acc_bf16", (_p(A1), ops._ld(A1), _p(B1), ops._ld(B1), K1, _p(A2), ops._ld(A2) if A2 is not None else 0,
-                                    _p(B2), ops._ld(B2) if B2 is not None else 0, K2, M, N, _p(resid), ops._ld(resid), _p(out),
+    _run("hsp_gemm_rows_acc_bf16", (*ops._gemm_sources(A1, ops._w(B1), K1, A2, ops._w(B2), K2), M, N, _p(resid), ops._ld(resid), _p(out),
                                     ops._ld(out), 1 if out.dtype == torch.float32 else 0, _p(ws), wsb, _stream()),
-         key=f"M{M}N{N}K{K1}+{K2}acc", abytes=2 * (M + N) * (K1 + K2) + 4 * M * N + ops._es(out) * M * N,
-         aflops=2 * M * N * (K1 + K2))
+         key=f"M{M}N{N}K{K1}+{K2}acc", abytes=2 * (M + N) * (K1 + K2) + 4 * M * N + ops._es(out) * M * N, aflops=flops)
     return out
 
 
@@ -385,13 +367,3 @@ def fan_bn(x, xyz, layers):
 
 def linear_rows(x2, w, b=None):
     return _LinearBf16.apply(x2, w, b)
-
-
-# The layer nodes and their kernel wrappers live in ``ops`` and take both dtypes.  Their former names here stay as plain aliases
-# (no code of their own) for callers written against them.
-hs_layer = ops.hs_layer
-_wgrad, _orl_fwd, _colsum, _rf_conv_fwd = ops.wgrad, ops._orl_fwd_raw, ops.colsum_rows, ops._rf_conv_fwd_raw
-
-
-def _rf_conv_bwd(xyz, directions, fm, arg, gF3, S):
-    return ops._rf_conv_bwd_raw(xyz, None, directions, fm, arg, gF3, S)
