@@ -669,6 +669,12 @@ def orl_global(feat, idx, k):
 #             gF = g + g Wa  (+= ORL scatter of gfg/N, accumulated by the kernel) ; gWa = g^T F
 #             gfm, gD = graph_conv_bwd(gF) ; gW = X^T gfm ; gb = colsum(gfm)
 #             gX = g Wste + gfm W^T ; gWste = g^T X
+# HS_layer and HSlayer_surface differ in how F comes about (graph_conv over fm = X W + b, or over the raw coordinates) and in the
+# STE's rows (X, or the three coordinates); everything after F in forward and before gF in backward is stated once for both:
+# ``_conv2_orl_fwd`` (the ORL forward, t, the out product; the exact forms) and ``_conv2_orl_bwd`` (the per-cloud chain gt, gWb,
+# gfg in two launches or four, gWa through the node's own weight-gradient call, g Wa, the ORL accumulation).  A node keeps
+# what is its own: its receptive-field kernels, fm and the input gradient (HS_layer), the relu fork (surface), and the extent of
+# its WgradBatch -- HS_layer folds its three parameter gradients in one launch, the surface layer its one at once.
 # The same chain runs on fp32 and on bf16 feature rows (hs_pose_amd/ops_bf16.py says what bf16 stores); each kernel wrapper picks
 # its entry point by the rows' dtype and each product its weight operand (``_weight_of``).  Where a dtype departs from the chain:
 #   fp32 only   the eval-mode forward in the reference's operation order and the C++ one-call inference forms (exact_scope)
@@ -829,6 +835,30 @@ def wgrad(A2, B2, out=None, colsum=False):
     if A2.dtype == torch.bfloat16:             # (the general tile kernel below is the fp32 rows' fallback only)
         raise HspError("bf16 weight gradient: shape or row pitch outside the split-K kernels (hsp_wgrad_plan)")
     return _wgrad_fallback(A2, B2, out, colsum)
+
+
+def _wgrad_now(A2, B2, colsum=False):
+    """``wgrad`` whose result is read at once (re-laid out by the caller): never left pending for the step's fold"""
+    sf = StepFolds.current
+    held = sf.bare_wgrad if sf is not None else None
+    if sf is not None:
+        sf.bare_wgrad = False
+    try:
+        return wgrad(A2, B2, colsum=colsum)
+    finally:
+        if sf is not None:
+            sf.bare_wgrad = held
+
+
+def _wgrad_thin(x2, g, colsum=False, now=False):
+    """(Cin, Cout) = x2^T g [, the column sums of g] for a thin per-point output layer (the 3- and 30-wide last layers of
+    FaceRecon.py:48,68 over B*N rows): g (R, Cout < 64) fp32, zero-padded to 64 columns in x2's dtype, takes the split-K kernel
+    -- the library's 16448-deep 30 x 128 product is a 100 us launch.  ``now``: through ``_wgrad_now``"""
+    R, Cout = g.shape
+    gp = torch.zeros(R, 64, dtype=x2.dtype, device=g.device)
+    gp[:, :Cout] = g
+    res = (_wgrad_now if now else wgrad)(x2, gp, colsum=colsum)
+    return (res[0][:, :Cout], res[1][:Cout]) if colsum else res[:, :Cout]
 
 
 def _wgrad_plan(M, N, K, lda, ldb, dtype, al16, ragged_entry=0):
@@ -1439,14 +1469,25 @@ ORL_COUNTS = True
 ORL_COUNTS_MIN_N = 128
 
 
-def _orl_fwd_counts_raw(F3, idx_x, k, ask=True):
+def _orl_fwd_launch(F3, idx_x, k, wsb, off):
     """(fg (B,C) fp32, argmax (B,N,C) uint8, counts): mean over points of the neighbourhood max of fp32 / bf16 rows, one pass, no
-    (B,N,C) max tensor.  counts: the winner counts (B,N,C) uint16 of this call for ``_orl_bwd_accumulate_raw`` (a view of a
-    workspace tensor of its own), or None -- always three results -- where they are not asked for (``ask``: a forward nothing
-    will differentiate has no use for them), ORL_COUNTS is off or the forward does not produce them"""
+    (B,N,C) max tensor, on a workspace of ``wsb`` bytes.  counts: the winner counts (B,N,C) uint16 the kernel leaves from byte
+    ``off`` of that workspace on (a view of it), or None (``off`` < 0: the plain workspace)"""
     B, N, C = F3.shape
     fg = torch.empty(B, C, dtype=torch.float32, device=F3.device)
     arg = torch.empty(B, N, C, dtype=torch.uint8, device=F3.device)
+    ws = _ws(wsb, F3.device)
+    cnt = ws[off:off + 2 * B * N * C].view(torch.uint16).view(B, N, C) if off >= 0 else None
+    _run("hsp_orl_global_fwd" + _sfx(F3), (_p(F3), _p(idx_x), B, N, k, idx_x.shape[2], C, _p(fg), _p(arg), _p(ws), wsb, _stream()),
+         key=f"B{B}N{N}k{k}C{C}", abytes=B * N * (_es(F3) * C + 4 * k + C + (2 * C if cnt is not None else 0)))
+    return fg, arg, cnt
+
+
+def _orl_fwd_counts_raw(F3, idx_x, k, ask=True):
+    """``_orl_fwd_launch`` for a layer node: (fg, argmax, counts) with the winner counts of this call for
+    ``_orl_bwd_accumulate_raw``, or None -- always three results -- where they are not asked for (``ask``: a forward nothing
+    will differentiate has no use for them), ORL_COUNTS is off or the forward does not produce them"""
+    B, N, C = F3.shape
     L = lib()
     wsb = L.hsp_orl_workspace_bytes(B, N, C)
     off = -1
@@ -1455,16 +1496,12 @@ def _orl_fwd_counts_raw(F3, idx_x, k, ask=True):
         off = L.hsp_orl_counts_offset(B, N, k, idx_x.shape[2], C, full)
         if off >= 0:
             wsb = full
-    ws = _ws(wsb, F3.device)
-    cnt = ws[off:off + 2 * B * N * C].view(torch.uint16).view(B, N, C) if off >= 0 else None
-    _run("hsp_orl_global_fwd" + _sfx(F3), (_p(F3), _p(idx_x), B, N, k, idx_x.shape[2], C, _p(fg), _p(arg), _p(ws), wsb, _stream()),
-         key=f"B{B}N{N}k{k}C{C}", abytes=B * N * (_es(F3) * C + 4 * k + C + (2 * C if cnt is not None else 0)))
-    return fg, arg, cnt
+    return _orl_fwd_launch(F3, idx_x, k, wsb, off)
 
 
 def _orl_fwd_raw(F3, idx_x, k):
-    """(fg, argmax) of ``_orl_fwd_counts_raw`` on the plain workspace: no counts asked for"""
-    return _orl_fwd_counts_raw(F3, idx_x, k, ask=False)[:2]
+    """(fg, argmax) of ``_orl_fwd_launch`` on the plain workspace: no counts"""
+    return _orl_fwd_launch(F3, idx_x, k, lib().hsp_orl_workspace_bytes(*F3.shape), -1)[:2]
 
 
 def _residual_bias(out3, f3, t2):
@@ -1734,8 +1771,76 @@ def _layer_out_exact(F2, w_conv2, fg, N, out3, ste=None, xyz3=None, w3=None, rel
     return out3
 
 
+def _conv2_orl_fwd(F3, idx_x, k, w_conv2, out3, x2, w_ste, exact, need_bwd, relu=False, bn_shift=None):
+    """Both layers after F: fg = mean_i max_n F[idx_x] ; out3 = x2 Wste^T + F Wa^T + F + (fg Wb^T)[cloud], conv2 = [Wa | Wb].
+    x2: the STE's rows -- the layer's input rows (HS_layer) or the raw coordinates (HSlayer_surface: they and ``relu`` ride in the
+    out product's epilogue).  THREE COLUMNS MEAN COORDINATES, here as in ``_layer_out_rows_plain``: rows of exactly three columns
+    take the epilogue form, never the STE product (no HS_layer of the network has a three-wide input).  ``exact``: the reference's operation order (fp32 rows).  ``need_bwd``: a
+    backward will follow (it asks the ORL forward for its winner counts).  Returns (fg (B,C) fp32, arg_o (B,N,C) uint8,
+    cnt_o | None, part | None): ``part``, with ``bn_shift``, is the BatchNorm first pass of out3 where the product left it"""
+    B, N, C = F3.shape
+    F2 = F3.view(B * N, C)
+    if exact:
+        fg, arg_o = _orl_fwd_exact(F3, idx_x, k)
+        ste = dict(xyz3=x2, w3=w_ste.contiguous()) if x2.shape[1] == 3 else dict(ste=gemm_wave(x2, w_ste, False))
+        _layer_out_exact(F2, w_conv2, fg, N, out3, relu=relu, **ste)
+        return fg, arg_o, None, None
+    fg, arg_o, cnt_o = _orl_fwd_counts_raw(F3, idx_x, k, ask=need_bwd and N >= ORL_COUNTS_MIN_N)
+    t2 = _mm_nt(fg, w_conv2[:, C:])                                            # fp32 (B,C): the per-cloud half of conv2
+    return fg, arg_o, cnt_o, _layer_out_rows(x2, w_ste, F2, w_conv2, t2, out3, relu=relu, bn_shift=bn_shift)
+
+
+def _conv2_orl_bwd(g, fg, w_conv2, idx_x, arg_o, cnt_o, k, x3, wgrads, xyz=None):
+    """Both layers' backward down to gF: returns (gF3 = g + g Wa + the ORL term, g_conv2 = [g^T F | gt^T fg], g_ste | None) for
+    the gradient rows g (B,N,C), gt = sum_i g per cloud.
+    ``wgrads(gWa, colsum_of)``: the node's weight gradients that need only g, g^T F into ``gWa`` among them (in place, ldc = 2C);
+    with ``colsum_of`` = (g, mom) it asks for gt as a rider of that launch (``wgrad_pair``) and returns whether it rode.
+    ``xyz`` (HSlayer_surface): the STE gradient g^T xyz (C,3) comes out of the per-cloud chain where its kernels take the shape
+    (``own_ste``: the coordinate moments of g, no library GEMM for a three-column product); None where the node has to form it.
+    ``x3``: the forward's weight-plane registry, for the g Wa product.
+    The per-cloud chain gt, gWb = gt^T fg, gfg / N = gt Wb / N is two launches where ``_orl_bwd_small_ok`` (``small``: fp32
+    rows), with COLSUM_RIDER gt rides in the node's pair launch, which then comes first; otherwise a column sum, ``_tiny_tn``
+    (the surface layer's STE gradient as its rider) and a 16-row product."""
+    B, N, C = g.shape
+    f32 = g.dtype == torch.float32
+    g2 = g.view(B * N, C)
+    Wb = w_conv2[:, C:]
+    g_conv2 = torch.empty_like(w_conv2)
+    gWa, gWb = g_conv2[:, :C], g_conv2[:, C:]
+    own_ste = xyz is not None and _ste_moments_ok(C) and (f32 or _takes("hsp_small_outer_takes", B))
+    small = f32 and (xyz is None or own_ste) and _orl_bwd_small_ok(B, N, C, xyz is not None)
+    rider = small and xyz is None and COLSUM_RIDER
+    g_ste = torch.empty(C, 3, dtype=torch.float32, device=g.device) if own_ste else None
+    mom = None
+    if rider:
+        mom = torch.empty(B, C, dtype=torch.float32, device=g.device)
+        rode = wgrads(gWa, (g, mom))
+        # (declined -- the rider did not fit beside the pair: the column sum as a launch of its own, after the pair)
+        gfg_n = _orl_bwd_small(g, None, fg, Wb, gWb, mom=mom if rode else None)
+    else:
+        if small:
+            gfg_n = _orl_bwd_small(g, xyz, fg, Wb, gWb, gste=g_ste)           # the whole chain (and the STE rider): two launches
+        elif own_ste:
+            mom = colsum_rows_xyz(g, xyz)                                      # gt and the per-cloud coordinate moments of g: one pass
+            gt = mom[:, :C]
+        else:
+            gt = colsum_rows(g)                                                # fp32 (B,C) = sum_i g
+        wgrads(gWa, None)
+        if not small:
+            _tiny_tn(gt, fg, gWb, mom=mom, gste=g_ste)                         # gWb = gt^T fg (tiny), straight into its column block
+    gF3 = torch.empty(B, N, C, dtype=g.dtype, device=g.device)
+    with x3_scope(x3):
+        _mm_nn(g2, w_conv2, out=gF3.view(B * N, C), cols=slice(0, C))          # g Wa ...
+    if not small:
+        gfg_n = _mm_nn(gt, Wb, alpha=1.0 / N)
+    _orl_bwd_accumulate_raw(gfg_n, idx_x, arg_o, k, gF3, extra=g, counts=cnt_o)        # ... + g + the ORL term, one pass
+    return gF3, g_conv2, g_ste
+
+
 class _HSLayer(torch.autograd.Function):
-    """HS_layer.forward (gcn3d.py:143-156) on fp32 or bf16 feature rows; parameters are the fp32 masters (gradients fp32)."""
+    """HS_layer.forward (gcn3d.py:143-156) on fp32 or bf16 feature rows; parameters are the fp32 masters (gradients fp32).
+    Its own: fm = X W + b, graph_conv, and in backward their gradients and gX; after F / before gF the shared tail
+    (``_conv2_orl_fwd`` / ``_conv2_orl_bwd``), its weight-gradient call there the pair g^T F, g^T X in one launch."""
 
     @staticmethod
     def forward(ctx, xyz, X, idx_f, idx_x, k, S, weights, bias, directions, w_ste3, w_conv23, bn_shift=None, out_f32=False):
@@ -1759,19 +1864,10 @@ class _HSLayer(torch.autograd.Function):
         if fwin is not None:
             fm = fwin                                                          # fm itself is no longer needed
         fm = fm.view(B, N, -1)
-        F2 = F3.view(B * N, C)
         # (returned as is: not a view.  bf16 rows ahead of a BatchNorm, ``out_f32``: written in fp32 -- the per-channel mean is
         # often >> the std, bf16 would leave the normalised value a handful of significant bits; the gradient comes back bf16)
         out3 = torch.empty(B, N, C, dtype=torch.float32 if out_f32 else X.dtype, device=X.device)
-        if exact:
-            fg, arg_o = _orl_fwd_exact(F3, idx_x, k)
-            cnt_o = None
-            _layer_out_exact(F2, w_conv2, fg, N, out3, ste=gemm_wave(X2, w_ste, False))
-            part = None
-        else:
-            fg, arg_o, cnt_o = _orl_fwd_counts_raw(F3, idx_x, k, ask=need_bwd and N >= ORL_COUNTS_MIN_N)    # fp32 (B,C)
-            t2 = _mm_nt(fg, w_conv2[:, C:])                                    # fp32 (B,C): the per-cloud half of conv2
-            part = _layer_out_rows(X2, w_ste, F2, w_conv2, t2, out3, bn_shift=bn_shift)          # X Wste^T + F Wa^T + F + t[b]
+        fg, arg_o, cnt_o, part = _conv2_orl_fwd(F3, idx_x, k, w_conv2, out3, X2, w_ste, exact, need_bwd, bn_shift=bn_shift)
         ctx.save_for_backward(xyz, X, idx_f, idx_x, fm, arg, F3, arg_o, fg, weights, directions, w_ste3, w_conv23, cnt_o)
         ctx.k, ctx.S, ctx.x3 = k, S, x3_planes
         if bn_shift is not None:
@@ -1796,32 +1892,13 @@ class _HSLayer(torch.autograd.Function):
         B, N, Cin = X.shape
         C = F3.shape[2]
         g2, X2, F2 = g.view(B * N, C), X.view(B * N, Cin), F3.view(B * N, C)
-        Wb = w_conv2[:, C:]
-        small = f32 and _orl_bwd_small_ok(B, N, C, False)
-        g_conv2 = torch.empty_like(w_conv2)
-        rider = small and COLSUM_RIDER
-        if rider:
-            pass                                                               # (gt rides in the pair launch below)
-        elif small:
-            gfg_n = _orl_bwd_small(g, None, fg, Wb, g_conv2[:, C:])            # gt = sum_i g, gWb = gt^T fg, gt Wb / N: two launches
-        else:
-            gt = colsum_rows(g)                                                # fp32 (B,C) = sum_i g
-        with WgradBatch(), x3_scope(ctx.x3):                                   # the three parameter gradients: one fold launch
-            g_ste = torch.empty(C, Cin, dtype=torch.float32, device=g.device)
-            if rider:
-                mom = torch.empty(B, C, dtype=torch.float32, device=g.device)
-                rode = wgrad_pair(g2, F2, g_conv2[:, :C], g2, X2, g_ste, colsum_of=(g, mom))
-                # (declined -- the rider did not fit beside the pair: the column sum as a launch of its own, after the pair)
-                gfg_n = _orl_bwd_small(g, None, fg, Wb, g_conv2[:, C:], mom=mom if rode else None)
-            else:
-                wgrad_pair(g2, F2, g_conv2[:, :C], g2, X2, g_ste)              # gWa (in place, ldc = 2C) and gWste: one split-K launch
-            if not small:
-                _tiny_tn(gt, fg, g_conv2[:, C:])                               # gWb = gt^T fg (tiny), straight into its column block
-            gF3 = torch.empty(B, N, C, dtype=g.dtype, device=g.device)
-            _mm_nn(g2, w_conv2, out=gF3.view(B * N, C), cols=slice(0, C))      # g Wa ...
-            if not small:
-                gfg_n = _mm_nn(gt, Wb, alpha=1.0 / N)
-            _orl_bwd_accumulate_raw(gfg_n, idx_x, arg_o, k, gF3, extra=g, counts=cnt_o)    # ... + g + the ORL term, one pass
+        g_ste = torch.empty(C, Cin, dtype=torch.float32, device=g.device)
+
+        def wgrads(gWa, colsum_of):                                            # gWa and gWste: one split-K launch
+            return wgrad_pair(g2, F2, gWa, g2, X2, g_ste, colsum_of=colsum_of)
+        # the three parameter gradients: one fold launch; every product of the backward on the forward's weight planes
+        with WgradBatch(), x3_scope(ctx.x3):
+            gF3, g_conv2, _ = _conv2_orl_bwd(g, fg, w_conv2, idx_x, arg_o, cnt_o, k, ctx.x3, wgrads)
             gfm, gD = _rf_conv_bwd_raw(xyz, idx_f, directions, fm.view(B, N, -1), arg, gF3, S)
             gfm2 = gfm.view(B * N, -1)
             gW, gb = wgrad(X2, gfm2, colsum=True)                              # X^T gfm and the bias gradient
@@ -1831,7 +1908,9 @@ class _HSLayer(torch.autograd.Function):
 
 
 class _SurfaceLayer(torch.autograd.Function):
-    """HSlayer_surface.forward (gcn3d.py:79-90) as one node producing fp32 or bf16 rows; xyz carries no gradient."""
+    """HSlayer_surface.forward (gcn3d.py:79-90) as one node producing fp32 or bf16 rows; xyz carries no gradient.
+    Its own: graph_conv over the coordinates, the relu fork and, where the tail's moment kernels decline, the STE gradient;
+    after F / before gF the shared tail (``_conv2_orl_fwd`` / ``_conv2_orl_bwd``) with the coordinates as the STE's rows."""
 
     @staticmethod
     def forward(ctx, xyz, idx_x, k, S, directions, w_ste3, w_conv23, relu=False, out_dtype=torch.float32):
@@ -1845,16 +1924,10 @@ class _SurfaceLayer(torch.autograd.Function):
         if idx_x.shape[2] != k:
             raise HspError("surface_layer: idx must have exactly k columns")
         F3, arg = _rf_surface_fwd_raw(xyz, idx_x, directions, S, out_dtype)
-        F2, x2 = F3.view(B * N, C), xyz.view(B * N, 3)
         out3 = torch.empty(B, N, C, dtype=out_dtype, device=xyz.device)
-        if _exact and _exact_layer_ok(N, 3, C, (w_conv2, F2)):                # (fp32 rows only)
-            fg, arg_o = _orl_fwd_exact(F3, idx_x, k)
-            cnt_o = None
-            _layer_out_exact(F2, w_conv2, fg, N, out3, xyz3=x2, w3=w_ste.contiguous(), relu=relu)
-        else:
-            fg, arg_o, cnt_o = _orl_fwd_counts_raw(F3, idx_x, k, ask=any(ctx.needs_input_grad) and N >= ORL_COUNTS_MIN_N)
-            t2 = _mm_nt(fg, w_conv2[:, C:])
-            _layer_out_rows(x2, w_ste, F2, w_conv2, t2, out3, relu=relu)
+        exact = _exact and _exact_layer_ok(N, 3, C, (w_conv2, F3.view(B * N, C)))                # (fp32 rows only)
+        fg, arg_o, cnt_o, _ = _conv2_orl_fwd(F3, idx_x, k, w_conv2, out3, xyz.view(B * N, 3), w_ste, exact,
+                                             any(ctx.needs_input_grad), relu=relu)
         ctx.k, ctx.S, ctx.relu, ctx.x3 = k, S, relu, x3_planes
         if relu:
             # relu(conv_0(...)) (FaceRecon.py:88) inside the node: the relu rides in the product's epilogue, the result is handed
@@ -1887,42 +1960,17 @@ class _SurfaceLayer(torch.autograd.Function):
         f32 = g.dtype == torch.float32
         B, N, C = F3.shape
         g2, F2, x2 = g.view(B * N, C), F3.view(B * N, C), xyz.view(B * N, 3)
-        Wb = w_conv2[:, C:]
-        g_conv2 = torch.empty_like(w_conv2)
-        own_ste = _ste_moments_ok(C) and (f32 or _takes("hsp_small_outer_takes", B))
-        small = f32 and own_ste and _orl_bwd_small_ok(B, N, C, True)
-        if small:
-            # the same chain (column sums + coordinate moments, gWb with the STE rider, gt Wb / N) in two launches
-            g_ste = torch.empty(C, 3, dtype=torch.float32, device=g.device)
-            gfg_n = _orl_bwd_small(g, xyz, fg, Wb, g_conv2[:, C:], gste=g_ste)
-        elif own_ste:
-            # gt = sum_i g and the per-cloud coordinate moments of g in one pass; the STE gradient g^T xyz is their sum over the
-            # batch, taken as a rider of the gt^T fg launch: no library GEMM for the (C, 3) product
-            mom = colsum_rows_xyz(g, xyz)
-            gt = mom[:, :C]
-            g_ste = torch.empty(C, 3, dtype=torch.float32, device=g.device)
-        else:
-            gt = colsum_rows(g)
-        if f32:
-            with WgradBatch():                              # (its fold goes out with the step's folds inside a StepFolds scope)
-                wgrad(g2, F2, out=g_conv2[:, :C])
-        else:
-            wgrad(g2, F2, out=g_conv2[:, :C])               # (bf16: hsp_wgrad_bf16 folds itself, one launch)
-        if small:
-            pass                                            # (gWb and the STE gradient came out of the pair launch above)
-        elif own_ste:
-            _tiny_tn(gt, fg, g_conv2[:, C:], mom=mom, gste=g_ste)
-        else:
-            _tiny_tn(gt, fg, g_conv2[:, C:])
-        gF3 = torch.empty(B, N, C, dtype=g.dtype, device=g.device)
-        with x3_scope(ctx.x3):
-            _mm_nn(g2, w_conv2, out=gF3.view(B * N, C), cols=slice(0, C))
-        if not small:
-            gfg_n = _mm_nn(gt, Wb, alpha=1.0 / N)
-        _orl_bwd_accumulate_raw(gfg_n, idx_x, arg_o, k, gF3, extra=g, counts=cnt_o)
+
+        def wgrads(gWa, _):
+            if f32:
+                with WgradBatch():                          # (its fold goes out with the step's folds inside a StepFolds scope)
+                    wgrad(g2, F2, out=gWa)
+            else:
+                wgrad(g2, F2, out=gWa)                      # (bf16: hsp_wgrad_bf16 folds itself, one launch)
+        gF3, g_conv2, g_ste = _conv2_orl_bwd(g, fg, w_conv2, idx_x, arg_o, cnt_o, k, ctx.x3, wgrads, xyz=xyz)
         gD = _rf_surface_bwd_raw(xyz, directions, arg, gF3, S)
-        if not own_ste:
-            # (C,3): three columns -- not a matrix-core shape
+        if g_ste is None:
+            # (the moment kernels do not take the shape.  (C,3): three columns -- not a matrix-core shape)
             g_ste = wgrad(g2, x2) if f32 else g2.float().t() @ x2
         return None, None, None, None, gD, g_ste.unsqueeze_(-1), g_conv2.unsqueeze_(-1), None, None
 
@@ -1999,12 +2047,8 @@ class _LinearRows(torch.autograd.Function):
             gwt, gb = wgrad(x2, g, colsum=True)                 # (Cin, Cout) = dW^T, column sums of g = db
             gw = gwt.t()
         elif _thin_wgrad_ok(Cout, Cin, R, g):
-            # a thin per-point output layer (the 3- and 30-wide last layers of FaceRecon.py:48,68 over B*N rows): g padded to
-            # 64 zero columns takes the split-K kernel -- the library's 16448-deep 30 x 128 product is a 100 us launch
-            gp = g.new_zeros(R, 64)
-            gp[:, :Cout] = g
-            gwt, gbp = wgrad(x2, gp, colsum=True)
-            gw, gb = gwt[:, :Cout].t(), gbp[:Cout]
+            gwt, gb = _wgrad_thin(x2, g, colsum=True)
+            gw = gwt.t()
         else:
             if _takes("hsp_small_outer_takes", R) and g.stride(1) == 1 and x2.stride(1) == 1:
                 gw = _tiny_tn(g, x2, torch.empty(Cout, Cin, dtype=torch.float32, device=g.device))   # per-cloud rows (the towers' conv4)
@@ -2147,16 +2191,7 @@ class _CloudCatLinear(torch.autograd.Function):
         with x3_scope(ctx.x3):
             g_fg = gemm_own(gt, W[:, :Cg], True) if ctx.needs_input_grad[0] else None
             gx = gemm_own(g, W[:, Cg:Cg + Cx], True) if ctx.needs_input_grad[1] else None
-        sf = StepFolds.current                                    # (the result is re-laid out below: fold now, not at the step's end)
-        held = sf.bare_wgrad if sf is not None else None
-        if sf is not None:
-            sf.bare_wgrad = False
-        try:
-            gwt = wgrad(xin, g)                                   # (Cx + 3, Cout) = the [x | xyz] block of dW^T
-        finally:
-            if sf is not None:
-                sf.bare_wgrad = held
-        gW[:, Cg:] = gwt.t()
+        gW[:, Cg:] = _wgrad_now(xin, g).t()                       # (Cx + 3, Cout) = the [x | xyz] block of dW^T, re-laid out here
         return g_fg, gx, None, gW, (gt.sum(0) if ctx.has_bias else None)
 
 

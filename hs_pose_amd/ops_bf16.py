@@ -150,19 +150,6 @@ def _bn_bwd(y, da, gamma, beta, mean, invstd):
     return ops._bn_bwd_raw(y, _b(da, "bn_relu.grad"), gamma, beta, mean, invstd, True)
 
 
-def _wgrad_now(A2, B2, colsum=False):
-    """ops.wgrad whose result is read at once (re-laid out by the caller): never left pending for the step's fold"""
-    sf = ops.StepFolds.current
-    held = sf.bare_wgrad if sf is not None else None
-    if sf is not None:
-        sf.bare_wgrad = False
-    try:
-        return ops.wgrad(A2, B2, colsum=colsum)
-    finally:
-        if sf is not None:
-            sf.bare_wgrad = held
-
-
 def _xyz_moments(g2, xyz, B):
     """(Cout, 3) = g^T xyz over all rows: the per-cloud coordinate moments of g (one pass, hsp_colsum_rows_xyz_bf16) summed over
     the B clouds -- the xyz columns' block of a weight gradient, no product"""
@@ -233,7 +220,7 @@ class _CloudCatBN(torch.autograd.Function):
         if ctx.needs_input_grad[2]:
             _, WT = copies_of(W[:, Cg:Cg + Cx])
             gx = ops.gemm_rows(g, WT)
-        gW[:, Cg:Cg + Cx] = _wgrad_now(x, g).t()
+        gW[:, Cg:Cg + Cx] = ops._wgrad_now(x, g).t()
         return None, g_fg, gx, None, gW, (gt.sum(0) if ctx.has_bias else None), dg, db
 
 
@@ -278,7 +265,7 @@ class _FanBN(torch.autograd.Function):
                 gwt, gb = ops.wgrad(x, g, colsum=True)
                 gw = gwt.t()
             else:
-                gwt, gb = _wgrad_now(x, g, colsum=True)
+                gwt, gb = ops._wgrad_now(x, g, colsum=True)
                 gw = torch.empty_like(w)
                 gw[:, :K] = gwt.t()
                 gw[:, K:] = _xyz_moments(g, xyz, xyz.shape[0])[1]
@@ -339,11 +326,9 @@ class _LinearBf16(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             # a K = Cout <= 30 product (no bf16 MFMA shape): fp32 on the hand-written kernel, rounded once to bf16
             gx = ops.gemm_rows(g, w, True).to(BF16)
-        gp = torch.zeros(R, 64, dtype=BF16, device=g.device)           # g on 64 zero-padded columns: the split-K kernel's shape
-        gp[:, :Cout] = g
-        gwt = _wgrad_now(x, gp)
+        gwt = ops._wgrad_thin(x, g, now=True)                           # (g rounded to bf16 on the padded columns)
         gb = ops.colsum_rows(g.view(1, R, Cout)).view(Cout) if ctx.has_bias else None      # (from the fp32 g)
-        return gx, gwt[:, :Cout].t(), gb
+        return gx, gwt.t(), gb
 
 
 def dense_bn(x, w, b, bn):

@@ -4,7 +4,10 @@
 A family is the literal head of ``_run``'s first argument -- a string, the left end of a ``+`` chain, the head of an f-string, either
 arm of a conditional --, so ``"hsp_gather_max_bwd" + sfx`` and ``"hsp_gather_max_bwd_sel" + sfx`` are two families and a suffix
 choice stays inside its wrapper.  A function that passes one of its own parameters on as that head (``_rf_bwd_dirs_call``'s ``base``
-and ``base + "_partial"``) is no site itself: the calls that hand it a literal are."""
+and ``base + "_partial"``) is no site itself: the calls that hand it a literal are.
+
+The same walk holds the two layer nodes to ONE conv2 + ORL tail each way (every wrapper of that tail is called from one function
+body of ops.py), and "fold this weight gradient now" and "pad a thin gradient to 64 columns" to one statement each, in ops.py."""
 import ast
 import gc
 import glob
@@ -126,6 +129,71 @@ def test_ops_bf16_holds_no_batchnorm_entry_and_no_alias():
         elif isinstance(node, ast.Assign):
             top |= {n.id for t in node.targets for n in ast.walk(t) if isinstance(n, ast.Name)}
     assert not top & set(DELETED_ALIASES)
+
+
+# ---- the layer nodes' shared tails, "fold now", "thin pad" ----------------------------------------------------------------------
+
+# the wrappers of the conv2 + ORL tail: each is called from one function body of ops.py (the forward or the backward tail)
+TAIL_WRAPPERS = ("_orl_fwd_exact", "_orl_fwd_counts_raw", "_layer_out_exact", "_layer_out_rows", "_orl_bwd_small", "_orl_bwd_accumulate_raw")
+
+
+def _tree(name):
+    return ast.parse(open(os.path.join(PKG, name)).read())
+
+
+def _body(fn):
+    """one function BODY: its name with the line of its ``def`` (two classes' ``forward`` are two bodies), or 'module'"""
+    return f"{fn.name}:{fn.lineno}" if fn else "module"
+
+
+def _bare_wgrad_assigners(tree, skip_classes=()):
+    """the function bodies (or 'module') that assign to an attribute ``bare_wgrad``, outside the classes listed"""
+    out = set()
+
+    def walk(node, fn):
+        for child in ast.iter_child_nodes(node):
+            if isinstance(child, ast.ClassDef) and child.name in skip_classes:
+                continue
+            inner = child if isinstance(child, (ast.FunctionDef, ast.AsyncFunctionDef)) else fn
+            if isinstance(child, (ast.Assign, ast.AugAssign, ast.AnnAssign)):
+                targets = child.targets if isinstance(child, ast.Assign) else [child.target]
+                if any(isinstance(n, ast.Attribute) and n.attr == "bare_wgrad" for t in targets for n in ast.walk(t)):
+                    out.add(_body(fn))
+            walk(child, inner)
+    walk(tree, None)
+    return out
+
+
+def _tail_callers(tree):
+    """{wrapper: the function bodies that call it}"""
+    callers = {name: set() for name in TAIL_WRAPPERS}
+    for fn, c in _calls_by_function(tree):
+        if _callee(c) in callers:
+            callers[_callee(c)].add(_body(fn))
+    return callers
+
+
+def test_each_tail_wrapper_is_called_from_one_function():
+    assert not {k: sorted(v) for k, v in _tail_callers(_tree("ops.py")).items() if len(v) != 1}
+
+
+def test_the_walk_tells_two_methods_of_one_name_apart():
+    """the nodes' methods share their names: a wrapper called from two classes' ``forward``, or a save and restore of
+    ``bare_wgrad`` in two classes' ``backward``, is two bodies"""
+    two = ast.parse("class A:\n    def forward(s):\n        _orl_fwd_exact()\n        sf.bare_wgrad = 0\n"
+                    "class B:\n    def forward(s):\n        _orl_fwd_exact()\n        sf.bare_wgrad = 0\n")
+    assert len(_tail_callers(two)["_orl_fwd_exact"]) == 2 and len(_bare_wgrad_assigners(two)) == 2
+
+
+def test_fold_now_is_stated_once():
+    assert len(_bare_wgrad_assigners(_tree("ops.py"), skip_classes=("StepFolds", "WgradBatch"))) == 1
+    assert not _bare_wgrad_assigners(_tree("ops_bf16.py"))
+
+
+def test_ops_bf16_pads_no_thin_gradient():
+    pads = [c.lineno for _, c in _calls_by_function(_tree("ops_bf16.py"))
+            if _callee(c) in ("zeros", "new_zeros") and any(isinstance(a, ast.Constant) and a.value == 64 for a in c.args)]
+    assert not pads
 
 
 # ---- ops._copies ---------------------------------------------------------------------------------------------------------------

@@ -6,9 +6,12 @@ ops.py marshals an entry point that alters a call, its order, its roofline figur
     python tools/record_op_calls.py tests/golden/call_records.json        # (re)write the fixture -- from the commit it speaks for
 
 Inputs come from a seeded CPU generator (one seed per case name: a case does not depend on which others ran) and are uploaded.
-Only public names of ``ops`` / ``ops_bf16`` are used.  Gradients are left out of the hashes where a backward adds in arrival order
-(the default pooling backward with a per-query gradient, ``hsp_gather_rows_bwd``): there the records alone are compared.
+Only public names of ``ops`` / ``ops_bf16`` are used.  A case runs under each mode it lists: a module switch or FLAGS field set for
+its extent, or (``exact``) inside ``ops.exact_scope`` with autograd recording -- the layer nodes' own exact forward.
+Gradients are left out of the hashes where a backward adds in arrival order (the default pooling backward with a per-query
+gradient, ``hsp_gather_rows_bwd``): there the records alone are compared.
 """
+import contextlib
 import hashlib
 import json
 import os
@@ -25,10 +28,12 @@ F32, BF = torch.float32, torch.bfloat16
 B, K, C = 2, 20, 128          # clouds, neighbours, channels
 N_CHUNKED, N_COUNTS = 64, 160  # below / above ops.ORL_COUNTS_MIN_N: the chunked ORL forward, the slab form that leaves counts
 
-# every switch a case may be run under: name -> (owner, attribute, value)
+# every switch a case may be run under: name -> (owner, attribute, value); owner "scope": the context manager of ``ops`` by that name
 MODES = {"default": None, "det": ("ops", "DETERMINISTIC", True), "repro": ("flags", "reproducible", True),
-         "nocounts": ("ops", "ORL_COUNTS", False), "rider": ("ops", "COLSUM_RIDER", True)}
+         "nocounts": ("ops", "ORL_COUNTS", False), "rider": ("ops", "COLSUM_RIDER", True),
+         "exact": ("scope", "exact_scope", True), "nodiet": ("ops", "LAUNCH_DIET", False)}
 GEOMETRY = ("default", "det", "repro")        # pooling / ORL / receptive-field / row-gather cases run under all three
+TAILS = ("exact", "nodiet")                   # the layer nodes' exact-scope forward (autograd recording) and four-launch chain
 CASES = {}                                    # "<case>/<mode>" -> (function, mode)
 
 
@@ -122,12 +127,12 @@ def _surface(inp, n, dtype, relu):
     return fwd, list(p.values())
 
 
-@case(*GEOMETRY)
+@case(*GEOMETRY, *TAILS)
 def surface_layer_f32(inp):
     return _surface(inp, N_CHUNKED, F32, False)
 
 
-@case(*GEOMETRY, "nocounts")
+@case(*GEOMETRY, "nocounts", *TAILS)
 def surface_layer_f32_relu_counts(inp):
     return _surface(inp, N_COUNTS, F32, True)
 
@@ -152,12 +157,12 @@ def _hs(inp, b, n, dtype, bn_shift=False, out_f32=False):
     return fwd, [X] + list(p.values())
 
 
-@case(*GEOMETRY)
+@case(*GEOMETRY, *TAILS)
 def hs_layer_f32_chunked(inp):
     return _hs(inp, B, N_CHUNKED, F32)
 
 
-@case(*GEOMETRY, "nocounts")
+@case(*GEOMETRY, "nocounts", *TAILS)
 def hs_layer_f32_counts(inp):
     return _hs(inp, B, N_COUNTS, F32)
 
@@ -486,19 +491,32 @@ def adds_in_arrival_order(calls):
     return False
 
 
-def run_case(name, dev):
-    """{"calls": [[entry point, key, abytes, aflops], ...], "outputs": [sha256, ...], "grads": [sha256 | None, ...] | None}"""
+@contextlib.contextmanager
+def _mode(switch):
+    """the case's switch set for the extent of the block"""
     from hs_pose_amd import ops
     from hs_pose_amd.config import FLAGS
-    fn, mode = CASES[name]
-    switch = MODES[mode]
-    owner = None
-    if switch is not None:
+    if switch is None:
+        yield
+    elif switch[0] == "scope":
+        with getattr(ops, switch[1])(switch[2]):
+            yield
+    else:
         owner = ops if switch[0] == "ops" else FLAGS
         before = getattr(owner, switch[1])
         setattr(owner, switch[1], switch[2])
+        try:
+            yield
+        finally:
+            setattr(owner, switch[1], before)
+
+
+def run_case(name, dev):
+    """{"calls": [[entry point, key, abytes, aflops], ...], "outputs": [sha256, ...], "grads": [sha256 | None, ...] | None}"""
+    from hs_pose_amd import ops
+    fn, mode = CASES[name]
     timer = ops.KernelTimer()
-    try:
+    with _mode(MODES[mode]):
         with ops.x3_scope(ops.X3Planes()):          # a registry of its own: the split launches do not depend on earlier cases
             inp = Inputs(dev, name.split("/")[0])
             fwd, leaves = fn(inp)
@@ -511,9 +529,6 @@ def run_case(name, dev):
             finally:
                 ops.set_timer(prev)
             torch.cuda.synchronize()
-    finally:
-        if owner is not None:
-            setattr(owner, switch[1], before)
     calls = [[n, k, int(ab), int(fl)] for n, k, ab, fl, _, _ in timer.records]
     grads = None
     if leaves and not adds_in_arrival_order(calls):
