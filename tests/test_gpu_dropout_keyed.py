@@ -41,6 +41,33 @@ def test_forward_and_backward_equal_restatement(dev, ref, R, C, p):
             assert np.array_equal(xd.grad.cpu().numpy(), want_g), (call, site)
 
 
+def test_grid_stride_wraps(dev, ref):
+    """2049 x 256 = 524 544 elements, more than the 256 * HSP_NUM_CU * 8 = 524 288 threads of the capped grid: the second trip of
+    either kernel's stride loop; forward, mask and backward bit for bit"""
+    from hs_pose_amd import ops
+    R, C, p, call, site = 2049, 256, 0.2, CALLS[0], 2
+    assert R * C > 256 * 256 * 8 >= (R - 1) * C
+    x = ref.hash_tensor((R, C), 24, 2.0)
+    g = ref.hash_tensor((R, C), 25, 1.0)
+    key = _sampler(dev, call).advance()
+    xd, gd = x.to(dev), g.to(dev)
+    out, keep, gx = torch.full_like(xd, float("nan")), torch.full((R, C), 9, dtype=torch.uint8, device=dev), torch.full_like(xd, float("nan"))
+    ops._run("hsp_dropout_keyed_fwd", (ops._p(xd), ops._p(key), site, p, R, C, ops._p(out), ops._p(keep), ops._stream()))
+    ops._run("hsp_dropout_bwd", (ops._p(gd), ops._p(keep), p, R, C, ops._p(gx), ops._stream()))
+    torch.cuda.synchronize()
+    want, want_keep = dref.dropout(x.numpy(), SEED, call, site, p)
+    assert 0 < want_keep[-1].sum() < C                                            # (the rows of the second trip keep and drop)
+    assert np.array_equal(keep.cpu().numpy(), want_keep)
+    assert np.array_equal(out.view(torch.int32).cpu().numpy(), want.view(np.int32))
+    want_g = (g.numpy() * want_keep.astype(np.float32) * dref.scale_of(p)).astype(np.float32)
+    assert np.array_equal(gx.view(torch.int32).cpu().numpy(), want_g.view(np.int32))
+    # and through the autograd node, as the cases above
+    xa = xd.clone().requires_grad_(True)
+    oa = ops.dropout_keyed(xa, key, site, p)
+    oa.backward(gd)
+    assert torch.equal(oa.detach().view(torch.int32), out.view(torch.int32)) and torch.equal(xa.grad.view(torch.int32), gx.view(torch.int32))
+
+
 def test_keep_bytes_and_two_forwards_before_a_backward(dev, ref):
     """the mask the C entry writes equals the restatement's; a backward uses ITS forward's saved mask although another forward
     under another key ran in between"""

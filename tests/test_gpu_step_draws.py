@@ -52,7 +52,7 @@ def test_pool_rows_equal_restatement(dev, n0):
             assert np.array_equal(b.cpu().numpy(), w)
 
 
-def _augment_case(B, N, dev):
+def _augment_case(B, N, dev, M=32):
     g = torch.Generator().manual_seed(B * 10007 + N)
     r = lambda *shape: torch.rand(*shape, generator=g)
     q, _ = torch.linalg.qr(r(B, 3, 3) - 0.5)
@@ -62,18 +62,18 @@ def _augment_case(B, N, dev):
     sym = torch.zeros(B, 4)
     sym[::2, 0] = 1.0
     case = dict(PC=PC, gt_R=q, gt_t=PC.mean(1) + 0.01 * (r(B, 3) - 0.5), gt_s=0.02 * (r(B, 3) - 0.5), mean_shape=0.12 + 0.03 * r(B, 3),
-                sym=sym, aug_bb=0.8 + 0.4 * r(B, 3), aug_rt_t=0.02 * (r(B, 3) - 0.5), aug_rt_r=q2, model_point=r(B, 32, 3) - 0.5,
+                sym=sym, aug_bb=0.8 + 0.4 * r(B, 3), aug_rt_t=0.02 * (r(B, 3) - 0.5), aug_rt_r=q2, model_point=r(B, M, 3) - 0.5,
                 nocs_scale=0.2 + 0.2 * r(B), obj_ids=obj)
     return {k: v.contiguous().to(dev) for k, v in case.items()}
 
 
-@pytest.mark.parametrize("N", [8, 256, 1028])
-@pytest.mark.parametrize("B", [1, 3, 16])
-def test_keyed_augmentation_equals_fed_augmentation(dev, flags, B, N):
+@pytest.mark.parametrize("B,N,M", [pytest.param(B, N, 32, id=f"{B}-{N}") for N in (8, 256, 1028) for B in (1, 3, 16)] +
+                         [pytest.param(3, 257, 1024, id="3-257-M1024")])    # (the loader's model size: four trips of the model loop)
+def test_keyed_augmentation_equals_fed_augmentation(dev, flags, B, N, M):
     """hsp_pose_augment_keyed == hsp_pose_augment fed the restated uniforms and jitter factors, every output bit for bit, with
     every probability at 0, at 1 and at its default"""
     from hs_pose_amd import augment, ops
-    case = _augment_case(B, N, dev)
+    case = _augment_case(B, N, dev, M)
     order = ("PC", "gt_R", "gt_t", "gt_s", "mean_shape", "sym", "aug_bb", "aug_rt_t", "aug_rt_r", "model_point", "nocs_scale", "obj_ids")
     default = (flags.aug_bb_pro, flags.aug_rt_pro, flags.aug_bc_pro, flags.aug_pc_pro)
     settings = [default, (0.0,) * 4, (1.0,) * 4] + [tuple(v if i == q else d for i, d in enumerate(default)) for q in range(4) for v in (0.0, 1.0)]
@@ -84,7 +84,7 @@ def test_keyed_augmentation_equals_fed_augmentation(dev, flags, B, N):
             s = _sampler(dev, call)
             got = ops.pose_augment_keyed(s.advance(), *[case[k] for k in order], flags.aug_pc_r, p_bb, p_rt, p_bc, p_pc)
             outs = [torch.empty_like(g) for g in got]
-            ops._run("hsp_pose_augment", [ops._p(case[k]) for k in order] + [ops._p(draws_d), ops._p(noise_d), B, N, 32, p_bb, p_rt,
+            ops._run("hsp_pose_augment", [ops._p(case[k]) for k in order] + [ops._p(draws_d), ops._p(noise_d), B, N, M, p_bb, p_rt,
                                                                              p_bc, p_pc] + [ops._p(o) for o in outs] + [ops._stream()])
             for name, g, w in zip(("PC", "R", "t", "s"), got, outs):
                 assert torch.equal(g.view(torch.int32), w.view(torch.int32)), (name, B, N, call, p_bb, p_rt, p_bc, p_pc)
