@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <limits.h>
 #include <math.h>
+#include <type_traits>
 
 #include "hsp.h"
 
@@ -37,6 +38,17 @@ inline int launch_lds(void (*kern)(P...), dim3 grid, dim3 block, size_t lds, hip
     }
     hipLaunchKernelGGL(kern, grid, block, lds, st, args...);
     return check_launch();
+}
+
+// run-time values as template arguments of a launch: f(std::true_type{} | std::false_type{}), and f(int_c<V>{}) for the V that
+// equals v -- the last V where none does
+template <int V> using int_c = std::integral_constant<int, V>;
+template <class F>
+inline auto with_bool(bool b, F f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
+template <int V, int... Rest, class F>
+inline auto with_int(int v, F f) {
+    if constexpr (sizeof...(Rest) == 0) return f(int_c<V>{});
+    else return v == V ? f(int_c<V>{}) : with_int<Rest...>(v, f);
 }
 
 // knn.hip -> knn_exact.hip: the xyz search by (distance, index) plus per-row flags: bit 0 "two of the k + drop + 1 nearest are equally

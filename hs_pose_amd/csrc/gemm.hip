@@ -33,6 +33,8 @@ using f32x16 = __attribute__((ext_vector_type(16))) float;
 //         fill the chip -- without multiplying the partial sums the reduce kernel has to read.
 // FT: storage type of A and B (float, or bf16_t: the pair of columns a lane owns is one 4-byte load, widened to fp32 --
 // the products still run on the fp32 MFMA, exact and in the same order as for fp32 operands)
+// dynamic LDS of every KB = 4 launch: the epilogue's buf[wave][acc][r][lane] and csb[wave][lane]
+constexpr size_t WGRAD_KB4_LDS = (size_t)4 * 4 * 16 * 64 * sizeof(float) + (size_t)4 * 64 * sizeof(float2);
 template <bool COLSUM, int KB, typename FT>
 __device__ __forceinline__ void wgrad_body(const int bid, const FT* __restrict__ A, int lda,
                                            const FT* __restrict__ B, int ldb, int M, int N, int K,
@@ -203,53 +205,11 @@ __global__ __launch_bounds__(256) void wgrad_pair_kernel(const WgradProb p0, con
                                 p.part, nullptr);
 }
 
-// C[m][n] = sum_s part[s][m][n]; likewise colsum.  Workgroup = 64 float4 elements x 4 slice groups:
-// group g sums slices g, g+4, ... with loads in flight, the 4 groups are folded through LDS in a
-// fixed order (deterministic).
-__global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restrict__ part, int SK, int M, int N,
-                                                           float* __restrict__ C, int ldc,
-                                                           const float* __restrict__ cs_part,
-                                                           float* __restrict__ colsum) {
+// the fold of ONE problem in a launch of its own (every fold-now entry): wgrad_fold_body (folds.h) over the problem's blocks,
+// so its summation order is the one of the two table kernels below by construction
+__global__ __launch_bounds__(256) void wgrad_reduce_kernel(const HspWgradPending pr) {
     __shared__ float4 red[4][64];
-    const int le = threadIdx.x & 63, sg = threadIdx.x >> 6;
-    const int nq = N >> 2;
-    const long long total = (long long)M * nq;                 // float4 elements of C
-    const long long ncs = colsum ? (N >> 2) : 0;               // float4 elements of colsum
-    const long long e = (long long)blockIdx.x * 64 + le;
-    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-    const float* src = nullptr;
-    size_t stride = 0;
-    if (e < total) { src = part + (size_t)e * 4; stride = (size_t)M * N; }
-    else if (e < total + ncs) { src = cs_part + (size_t)(e - total) * 4; stride = (size_t)N; }
-    if (src) {
-        float4 s2 = make_float4(0.f, 0.f, 0.f, 0.f);
-        int sl = sg;
-        for (; sl + 4 < SK; sl += 8) {
-            const float4 v = *reinterpret_cast<const float4*>(src + (size_t)sl * stride);
-            const float4 u = *reinterpret_cast<const float4*>(src + (size_t)(sl + 4) * stride);
-            s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
-            s2.x += u.x; s2.y += u.y; s2.z += u.z; s2.w += u.w;
-        }
-        if (sl < SK) {
-            const float4 v = *reinterpret_cast<const float4*>(src + (size_t)sl * stride);
-            s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
-        }
-        s.x += s2.x; s.y += s2.y; s.z += s2.z; s.w += s2.w;
-    }
-    red[sg][le] = s;
-    __syncthreads();
-    if (sg == 0 && src) {
-        float4 r = red[0][le];
-#pragma unroll
-        for (int g = 1; g < 4; ++g) { const float4 v = red[g][le]; r.x += v.x; r.y += v.y; r.z += v.z; r.w += v.w; }
-        if (e < total) {
-            const int m = (int)(e / nq), q = (int)(e - (long long)m * nq);
-            float* c = C + (size_t)m * ldc + (q << 2);
-            c[0] = r.x; c[1] = r.y; c[2] = r.z; c[3] = r.w;    // ldc need not be a multiple of 4
-        } else {
-            *reinterpret_cast<float4*>(colsum + (size_t)(e - total) * 4) = r;
-        }
-    }
+    wgrad_fold_body(pr, (int)blockIdx.x, red);
 }
 
 // the same fold for up to HSP_FOLD_MAX_WGRAD weight-gradient problems in ONE launch (the three parameter gradients of an HS
@@ -784,9 +744,24 @@ static int wgrad_launch(const FT* A, int lda, const FT* B, int ldb, int M, int N
                            sk, ks, part, cs_part);
         return check_launch();
     }
-    const size_t lds = (size_t)4 * 4 * 16 * 64 * sizeof(float) + (size_t)4 * 64 * sizeof(float2);
-    return launch_lds(wgrad_kernel<COLSUM, 4, FT>, dim3(tiles * (sk / 4)), dim3(256), lds, st, A, lda, B, ldb, M, N, K, sk, ks, part,
-                      cs_part);
+    return launch_lds(wgrad_kernel<COLSUM, 4, FT>, dim3(tiles * (sk / 4)), dim3(256), WGRAD_KB4_LDS, st, A, lda, B, ldb, M, N, K, sk, ks,
+                      part, cs_part);
+}
+
+// workgroups of one problem's fold: 64 float4 elements each, C (M x N/4) first, then the column sums (N/4) -- the element
+// order wgrad_fold_body assumes, for the stand-alone launch and for both block tables
+static int wgrad_fold_blocks(int M, int N, bool colsum) {
+    const long long total = (long long)M * (N >> 2) + (colsum ? (N >> 2) : 0);
+    return (int)((total + 63) / 64);
+}
+
+// the end of every weight-gradient call, given its partial-sum launch's return code: the fold is left to the caller
+// (*pending) or launched here
+static int wgrad_finish(int rc, const HspWgradPending& p, HspWgradPending* pending, hipStream_t st) {
+    if (rc) return rc;
+    if (pending) { *pending = p; return HSP_OK; }
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)wgrad_fold_blocks(p.M, p.N, p.colsum != nullptr)), dim3(256), 0, st, p);
+    return check_launch();
 }
 
 template <typename FT>
@@ -800,58 +775,34 @@ static int wgrad_impl(const FT* A, int lda, const FT* B, int ldb, int M, int N, 
     if (!ws || ws_bytes < hsp_wgrad_workspace_bytes(M, N, K)) return HSP_ERR_WORKSPACE;
     const int ks = pl.ks;
     hipStream_t st = as_stream(stream);
+    // every form leaves pl.nparts partial sums of C at the head of the workspace and their column sums right behind them
+    float* part = reinterpret_cast<float*>(ws);
+    float* cs_part = part + (size_t)pl.nparts * M * N;
+    const HspWgradPending fold{part, cs_part, C, colsum_B, pl.nparts, M, N, ldc};
+    const int grid128 = ((M + 127) >> 7) * (N >> 7) * pl.sk;   // (the two 128 x 128 tile forms)
     if constexpr (sizeof(FT) == 2) {
         if (pl.form == HSP_WGRAD_FORM_BF16) {
-            const int sk2 = pl.sk;
-            float* part = reinterpret_cast<float*>(ws);
-            float* cs_part = part + (size_t)sk2 * M * N;
-            const int grid = ((M + 127) >> 7) * (N >> 7) * sk2;
-            const int lds = 4 * 128 * 128;
             const unsigned short* a = reinterpret_cast<const unsigned short*>(A);
             const unsigned short* b = reinterpret_cast<const unsigned short*>(B);
-#define WG_BF16_LAUNCH(CS, RG) \
-    launch_lds(wgrad_bf16_mfma_kernel<CS, RG>, dim3(grid), dim3(256), lds, st, a, lda, b, ldb, M, N, K, ks, part, cs_part)
-            const int rc = pl.ragged ? (colsum_B ? WG_BF16_LAUNCH(true, true) : WG_BF16_LAUNCH(false, true))
-                                     : (colsum_B ? WG_BF16_LAUNCH(true, false) : WG_BF16_LAUNCH(false, false));
-#undef WG_BF16_LAUNCH
-            if (rc) return rc;
-            if (pending) { *pending = HspWgradPending{part, cs_part, C, colsum_B, sk2, M, N, ldc}; return HSP_OK; }
-            const long long total = (long long)M * (N >> 2) + (colsum_B ? (N >> 2) : 0);
-            hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((total + 63) / 64)), dim3(256), 0, st, part, sk2, M, N, C, ldc,
-                               cs_part, colsum_B);
-            return check_launch();
+            return wgrad_finish(with_bool(pl.ragged, [&](auto rg) {
+                return with_bool(colsum_B != nullptr, [&](auto cs) {
+                    return launch_lds(wgrad_bf16_mfma_kernel<decltype(cs)::value, decltype(rg)::value>, dim3(grid128), dim3(256),
+                                      4 * 128 * 128, st, a, lda, b, ldb, M, N, K, ks, part, cs_part);
+                });
+            }), fold, pending, st);
         }
     }
     if constexpr (sizeof(FT) == 4) {
-        if (pl.form == HSP_WGRAD_FORM_X3) {
-            const int sk2 = pl.sk;
-            float* part = reinterpret_cast<float*>(ws);
-            float* cs_part = part + (size_t)sk2 * M * N;
-            const int grid = ((M + 127) >> 7) * (N >> 7) * sk2;
-            const int lds = 6 * 128 * 80;
-            if (colsum_B) hipLaunchKernelGGL(wgrad_x3_kernel<true>, dim3(grid), dim3(256), lds, st, A, lda, B, ldb, M, N, K, ks, part, cs_part);
-            else hipLaunchKernelGGL(wgrad_x3_kernel<false>, dim3(grid), dim3(256), lds, st, A, lda, B, ldb, M, N, K, ks, part, cs_part);
-            int rc = check_launch();
-            if (rc) return rc;
-            if (pending) { *pending = HspWgradPending{part, cs_part, C, colsum_B, sk2, M, N, ldc}; return HSP_OK; }
-            const long long total = (long long)M * (N >> 2) + (colsum_B ? (N >> 2) : 0);
-            hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((total + 63) / 64)), dim3(256), 0, st, part, sk2, M, N, C, ldc,
-                               cs_part, colsum_B);
-            return check_launch();
-        }
+        if (pl.form == HSP_WGRAD_FORM_X3)
+            return wgrad_finish(with_bool(colsum_B != nullptr, [&](auto cs) {
+                return launch_lds(wgrad_x3_kernel<decltype(cs)::value>, dim3(grid128), dim3(256), 6 * 128 * 80, st, A, lda, B, ldb, M, N,
+                                  K, ks, part, cs_part);
+            }), fold, pending, st);
     }
-    const int sk = pl.sk, kb = pl.form == HSP_WGRAD_FORM_F32_KB4 ? 4 : 1;
-    const int nparts = pl.nparts;
-    float* part = reinterpret_cast<float*>(ws);
-    float* cs_part = part + (size_t)nparts * M * N;
-    int rc = colsum_B ? wgrad_launch<true, FT>(A, lda, B, ldb, M, N, K, sk, ks, kb, part, cs_part, st)
-                      : wgrad_launch<false, FT>(A, lda, B, ldb, M, N, K, sk, ks, kb, part, cs_part, st);
-    if (rc) return rc;
-    if (pending) { *pending = HspWgradPending{part, cs_part, C, colsum_B, nparts, M, N, ldc}; return HSP_OK; }
-    const long long total = (long long)M * (N >> 2) + (colsum_B ? (N >> 2) : 0);
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((total + 63) / 64)), dim3(256), 0, st, part, nparts, M, N, C,
-                       ldc, cs_part, colsum_B);
-    return check_launch();
+    const int kb = pl.form == HSP_WGRAD_FORM_F32_KB4 ? 4 : 1;
+    return wgrad_finish(with_bool(colsum_B != nullptr, [&](auto cs) {
+        return wgrad_launch<decltype(cs)::value, FT>(A, lda, B, ldb, M, N, K, pl.sk, ks, kb, part, cs_part, st);
+    }), fold, pending, st);
 }
 
 extern "C" int hsp_wgrad_f32(const float* A, int lda, const float* B, int ldb, int M, int N, int K, float* C, int ldc,
@@ -908,7 +859,6 @@ static int wgrad_pair_impl(const float* A0, int lda0, const float* B0, int ldb0,
             const WgradProb p0{A0, B0, reinterpret_cast<float*>(ws0), lda0, ldb0, M0, N0, K0, sk0, ks0};
             const WgradProb p1{A1, B1, reinterpret_cast<float*>(ws1), lda1, ldb1, M1, N1, K1, sk1, ks1};
             const int blocks0 = (M0 >> 6) * (N0 >> 6) * (sk0 / 4), blocks1 = (M1 >> 6) * (N1 >> 6) * (sk1 / 4);
-            const size_t lds = (size_t)4 * 4 * 16 * 64 * sizeof(float) + (size_t)4 * 64 * sizeof(float2);
             ColsumRider rider{nullptr, nullptr, 0, 0, 0, 0, 1, 1};
             int rider_blocks = 0;
             if (cs_x) {
@@ -917,7 +867,7 @@ static int wgrad_pair_impl(const float* A0, int lda0, const float* B0, int ldb0,
                 int rows, nchunk;
                 if (!cs_out || cs_B <= 0 || cs_N <= 0 || cs_C <= 0) return HSP_ERR_BAD_ARG;
                 if (!colsum_cloud_plan(cs_B, cs_N, cs_C, &rows, &nchunk)) return HSP_ERR_UNSUPPORTED;
-                if (((size_t)4 * 256 + (size_t)nchunk * (cs_C >> 5)) * sizeof(float4) > lds) return HSP_ERR_UNSUPPORTED;
+                if (((size_t)4 * 256 + (size_t)nchunk * (cs_C >> 5)) * sizeof(float4) > WGRAD_KB4_LDS) return HSP_ERR_UNSUPPORTED;
                 const long long room = 2LL * HSP_NUM_CU - blocks0 - blocks1;
                 int tpb = 1;
                 while (tpb <= 8 && (long long)cs_B * (8 / tpb) > room) tpb <<= 1;
@@ -925,8 +875,8 @@ static int wgrad_pair_impl(const float* A0, int lda0, const float* B0, int ldb0,
                 rider = ColsumRider{cs_x, cs_out, cs_N, cs_C, nchunk, rows, tpb, 8 / tpb};
                 rider_blocks = cs_B * (8 / tpb);
             }
-            const int rc = launch_lds(wgrad_pair_kernel, dim3(blocks0 + blocks1 + rider_blocks), dim3(256), lds, as_stream(stream), p0,
-                                      p1, blocks0, blocks0 + blocks1, rider);
+            const int rc = launch_lds(wgrad_pair_kernel, dim3(blocks0 + blocks1 + rider_blocks), dim3(256), WGRAD_KB4_LDS, as_stream(stream),
+                                      p0, p1, blocks0, blocks0 + blocks1, rider);
             if (rc) return rc;
             pending[0] = HspWgradPending{p0.part, nullptr, C0, nullptr, sk0 / 4, M0, N0, ldc0};
             pending[1] = HspWgradPending{p1.part, nullptr, C1, nullptr, sk1 / 4, M1, N1, ldc1};
@@ -955,27 +905,32 @@ extern "C" int hsp_wgrad_partial_pair_colsum_f32(const float* A0, int lda0, cons
                            ws_bytes1, pending, x, B, N, C, out, stream);
 }
 
+static bool wgrad_pending_ok(const HspWgradPending& p) {
+    return p.part && p.C && p.nparts > 0 && p.M > 0 && p.N > 0 && !(p.N & 3) && p.ldc >= p.N && !(p.colsum && !p.cs_part);
+}
+
+// the weight-gradient half of both fold tables: copies the n entries and gives entry i the blocks [first[i], first[i + 1]).
+// Returns the block count, or -1 where an entry is not a foldable problem.
+static int wgrad_fold_table(const HspWgradPending* in, int n, HspWgradPending* out, int* first) {
+    int blocks = 0;
+    for (int i = 0; i < n; ++i) {
+        if (!wgrad_pending_ok(in[i])) return -1;
+        first[i] = blocks;
+        blocks += wgrad_fold_blocks(in[i].M, in[i].N, in[i].colsum != nullptr);
+        out[i] = in[i];
+    }
+    first[n] = blocks;
+    return blocks;
+}
+
 extern "C" int hsp_wgrad_fold(const HspWgradPending* pending, int n, hspStream_t stream) {
     if (!pending || n <= 0 || n > HSP_FOLD_MAX_WGRAD) return HSP_ERR_BAD_ARG;
     WgradFoldTab tab;
     tab.n = n;
-    int blocks = 0;
-    for (int i = 0; i < n; ++i) {
-        const HspWgradPending& p = pending[i];
-        if (!p.part || !p.C || p.nparts <= 0 || p.M <= 0 || p.N <= 0 || (p.N & 3) || p.ldc < p.N || (p.colsum && !p.cs_part))
-            return HSP_ERR_BAD_ARG;
-        tab.first[i] = blocks;
-        const long long total = (long long)p.M * (p.N >> 2) + (p.colsum ? (p.N >> 2) : 0);
-        blocks += (int)((total + 63) / 64);
-        tab.p[i] = p;
-    }
-    tab.first[n] = blocks;
+    const int blocks = wgrad_fold_table(pending, n, tab.p, tab.first);
+    if (blocks < 0) return HSP_ERR_BAD_ARG;
     hipLaunchKernelGGL(wgrad_reduce_multi_kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), tab);
     return check_launch();
-}
-
-static bool wgrad_pending_ok(const HspWgradPending& p) {
-    return p.part && p.C && p.nparts > 0 && p.M > 0 && p.N > 0 && !(p.N & 3) && p.ldc >= p.N && !(p.colsum && !p.cs_part);
 }
 
 extern "C" int hsp_step_fold(const HspWgradPending* wgrads, int nw, const HspDirsPending* dirs, int nd, hspStream_t stream) {
@@ -983,16 +938,8 @@ extern "C" int hsp_step_fold(const HspWgradPending* wgrads, int nw, const HspDir
     if (nw + nd == 0) return HSP_OK;
     StepFoldTab tab;
     tab.nw = nw; tab.nd = nd;
-    int blocks = 0;
-    for (int i = 0; i < nw; ++i) {
-        const HspWgradPending& p = wgrads[i];
-        if (!wgrad_pending_ok(p)) return HSP_ERR_BAD_ARG;
-        tab.wfirst[i] = blocks;
-        const long long total = (long long)p.M * (p.N >> 2) + (p.colsum ? (p.N >> 2) : 0);
-        blocks += (int)((total + 63) / 64);
-        tab.w[i] = p;
-    }
-    tab.wfirst[nw] = blocks;
+    const int blocks = wgrad_fold_table(wgrads, nw, tab.w, tab.wfirst);
+    if (blocks < 0) return HSP_ERR_BAD_ARG;
     int dblocks = 0;
     for (int i = 0; i < nd; ++i) {
         const HspDirsPending& p = dirs[i];

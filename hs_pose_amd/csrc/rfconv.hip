@@ -841,6 +841,15 @@ __global__ __launch_bounds__(1024) void rf_dirs_reduce_kernel(const float* __res
     dirs_fold_body<1024>(ws, nblk, SC, dirs, out, (int)blockIdx.x, red);          // (folds.h; also inside hsp_step_fold)
 }
 
+// the end of every direction-gradient backward, once its partials launch is out: the fold of the nparts partials is left to
+// the caller (*pending, the *_partial entries) or launched here
+static int rf_dirs_finish(const float* part, int nparts, int SC, const float* dirs, float* gdirs, hipStream_t st,
+                          HspDirsPending* pending) {
+    if (pending) { *pending = HspDirsPending{part, dirs, gdirs, nparts, SC}; return HSP_OK; }
+    hipLaunchKernelGGL(rf_dirs_reduce_kernel, dim3((SC + 63) / 64), dim3(1024), 0, st, part, nparts, SC, dirs, gdirs);
+    return check_launch();
+}
+
 // backward grid: persistent, capped so that the per-block direction-gradient partials stay <= 8 MiB
 static int rf_bwd_grid_max(int SC) {
     long long g = (8ll << 20) / (12ll * SC);
@@ -926,16 +935,10 @@ extern "C" int hsp_rf_fwd_plan(int k, int S, int C, int* pipelined) {
 // the run-time column slots per thread (1..4) and WF as template arguments: launch(integral_constant<int, NCH>, bool_constant<WF>)
 template <class F>
 static void rf_dispatch_nch(int nch, bool wf, F launch) {
-    auto with_wf = [&](auto n) {
+    with_int<1, 2, 3, 4>(nch, [&](auto n) {
         if (wf) launch(n, std::true_type{});
         else launch(n, std::false_type{});
-    };
-    switch (nch) {
-        case 1: with_wf(std::integral_constant<int, 1>{}); break;
-        case 2: with_wf(std::integral_constant<int, 2>{}); break;
-        case 3: with_wf(std::integral_constant<int, 3>{}); break;
-        default: with_wf(std::integral_constant<int, 4>{}); break;
-    }
+    });
 }
 
 template <bool SURFACE, typename FT>
@@ -1029,8 +1032,14 @@ extern "C" int hsp_rf_conv_bwd(const float* xyz, const float* dirs_n, const floa
     });
     rc = check_launch();
     if (rc) return rc;
-    hipLaunchKernelGGL(rf_dirs_reduce_kernel, dim3((SC + 63) / 64), dim3(1024), 0, st, wsf, grid, SC, dirs_n, grad_dirs_n);
-    return check_launch();
+    return rf_dirs_finish(wsf, grid, SC, dirs_n, grad_dirs_n, st, nullptr);
+}
+
+// dynamic LDS of a tile launch over `rows` rows: acc[rows][tc] (the surface kernel keeps none) + xyz[rows][3], and never less
+// than the RF_TILE_THREADS x 12 floats of the kernel's direction fold.  The plan's fit tests and the launch both ask here.
+static size_t rf_tile_lds(int rows, int tc, bool surface) {
+    const size_t lds = ((surface ? 0 : (size_t)rows * tc) + 3 * (size_t)rows) * 4;
+    return lds < RF_TILE_THREADS * 12 * 4 ? RF_TILE_THREADS * 12 * 4 : lds;
 }
 
 // column-tile scatter: the widest tile whose acc[N][TC] + xyz[N][3] fits two workgroups per CU, else one
@@ -1041,7 +1050,7 @@ static int pick_tile_cols(int N, int C, bool surface, int B = 0, int SC = 0) {
     for (int pass = 0; pass < 2; ++pass)
         for (int tc = 64; tc >= 4; tc >>= 1) {
             if (tc > 16 && (long long)(SC / tc) * B < 2 * HSP_NUM_CU) continue;   // ... while the grid still fills the chip
-            if (C % tc == 0 && ((size_t)N * tc + 3 * (size_t)N) * 4 <= (pass == 0 ? 80u : 156u) * 1024) return tc;
+            if (C % tc == 0 && rf_tile_lds(N, tc, false) <= (pass == 0 ? 80u : 156u) * 1024) return tc;
         }
     return 0;
 }
@@ -1052,23 +1061,22 @@ extern "C" size_t hsp_rf_bwd_scatter_workspace_bytes(int B, int SC) {
 }
 
 // dense clouds: two half-cloud tiles of 16 columns instead of one whole-cloud tile of <= 8 (see rf_bwd_tile_kernel)
-static bool rf_use_row_split(int N, int C, bool surface, int tc_whole) {
-    if (surface || tc_whole >= 16 || C % 16) return false;
-    const int nr = (N + 1) / 2;
-    return ((size_t)nr * 16 + 3 * (size_t)nr) * 4 <= 156u * 1024;
+static bool rf_use_row_split(int half_rows, int C, bool surface, int tc_whole) {
+    return !surface && tc_whole < 16 && C % 16 == 0 && rf_tile_lds(half_rows, 16, false) <= 156u * 1024;
 }
 
-// which tile kernel a shape runs: tile width (0: declined) and the number of row ranges (2: the half-cloud form).  The one source
-// of truth of rf_bwd_scatter and of hsp_rf_bwd_scatter_plan.
-struct RfBwdPlan { int tc, rs; };
+// which tile kernel a shape runs and what its launch needs: tile width (0: declined), the number of row ranges (2: the
+// half-cloud form), the rows of one tile and the launch's dynamic LDS.  The one source of truth of rf_bwd_scatter and of
+// hsp_rf_bwd_scatter_plan.
+struct RfBwdPlan { int tc, rs, rows; size_t lds; };
 static RfBwdPlan rf_bwd_plan(int B, int N, int S, int C, bool surface) {
-    const int tc = pick_tile_cols(N, C, surface, B, S * C);
-    if (rf_use_row_split(N, C, surface, tc)) return RfBwdPlan{16, 2};
-    return RfBwdPlan{tc, tc ? 1 : 0};
+    const int tc = pick_tile_cols(N, C, surface, B, S * C), nr = (N + 1) / 2;   // nr: the rows of a cloud's larger half
+    if (rf_use_row_split(nr, C, surface, tc)) return RfBwdPlan{16, 2, nr, rf_tile_lds(nr, 16, false)};
+    return RfBwdPlan{tc, tc ? 1 : 0, N, tc ? rf_tile_lds(N, tc, surface) : 0};
 }
 
 extern "C" int hsp_rf_bwd_scatter_plan(int B, int N, int S, int C, int surface, int* row_split) {
-    RfBwdPlan p{0, 0};
+    RfBwdPlan p{0, 0, 0, 0};
     if (B > 0 && N > 0 && N <= 65535 && S > 0 && C > 0 && !(C & 3) && (long long)S * C <= (1 << 24))
         p = rf_bwd_plan(B, N, S, C, surface != 0);
     if (row_split) *row_split = p.rs;
@@ -1124,33 +1132,19 @@ static int rf_bwd_scatter(const float* xyz, const float* dirs, const FT* fm, con
     const int SC = S * C;
     if (!ws || ws_bytes < hsp_rf_bwd_scatter_workspace_bytes(B, SC)) return HSP_ERR_WORKSPACE;
     const RfBwdPlan plan = rf_bwd_plan(B, N, S, C, SURFACE);
-    const int tc = plan.tc;
+    if (!plan.tc) return HSP_ERR_UNSUPPORTED;
     hipStream_t st = as_stream(stream);
     float* part = reinterpret_cast<float*>(ws);
     const bool legacy = g_rf_bwd_legacy.load() != 0;
     const float* hat = rf_dirs_hat_find(dirs, SC);
-    if (plan.rs == 2) {
-        const int nr = (N + 1) / 2;
-        const size_t lds2 = ((size_t)nr * 16 + 3 * (size_t)nr) * 4;
-        rc = rf_tile_launch<16, SURFACE, FWIN, FT, 2>(legacy, N, dim3(SC / 16, B, 2), lds2, st, xyz, dirs, hat, fm, argrow, gout, B, N, S, C,
-                                                      gfm, part);
-        if (rc) return rc;
-        if (pending) { *pending = HspDirsPending{part, dirs, gdirs, 2 * B, SC}; return HSP_OK; }
-        hipLaunchKernelGGL(rf_dirs_reduce_kernel, dim3((SC + 63) / 64), dim3(1024), 0, st, part, 2 * B, SC, dirs, gdirs);
-        return check_launch();
-    }
-    if (!tc) return HSP_ERR_UNSUPPORTED;
-    size_t lds = ((SURFACE ? 0 : (size_t)N * tc) + 3 * (size_t)N) * 4;
-    if (lds < RF_TILE_THREADS * 12 * 4) lds = RF_TILE_THREADS * 12 * 4;
-    dim3 grid(SC / tc, B);
-#define RF_TILE_LAUNCH(TC) rc = rf_tile_launch<TC, SURFACE, FWIN, FT, 1>(legacy, N, grid, lds, st, xyz, dirs, hat, fm, argrow, gout, B, N, S, C, gfm, part);
-    if (tc == 64) RF_TILE_LAUNCH(64) else if (tc == 32) RF_TILE_LAUNCH(32) else if (tc == 16) RF_TILE_LAUNCH(16)
-    else if (tc == 8) RF_TILE_LAUNCH(8) else RF_TILE_LAUNCH(4)
-#undef RF_TILE_LAUNCH
+    auto tile = [&](auto tc, auto rs) {
+        return rf_tile_launch<decltype(tc)::value, SURFACE, FWIN, FT, decltype(rs)::value>(
+            legacy, N, dim3(SC / plan.tc, B, plan.rs), plan.lds, st, xyz, dirs, hat, fm, argrow, gout, B, N, S, C, gfm, part);
+    };
+    // (the half-cloud form is built at 16 columns only; a whole cloud takes 64 ... 4)
+    rc = plan.rs == 2 ? tile(int_c<16>{}, int_c<2>{}) : with_int<64, 32, 16, 8, 4>(plan.tc, [&](auto tc) { return tile(tc, int_c<1>{}); });
     if (rc) return rc;
-    if (pending) { *pending = HspDirsPending{part, dirs, gdirs, B, SC}; return HSP_OK; }
-    hipLaunchKernelGGL(rf_dirs_reduce_kernel, dim3((SC + 63) / 64), dim3(1024), 0, st, part, B, SC, dirs, gdirs);
-    return check_launch();
+    return rf_dirs_finish(part, plan.rs * B, SC, dirs, gdirs, st, pending);   // one partial per cloud and row range
 }
 
 // every scatter-backward entry point: pending_required = the *_partial entries, which leave the direction-gradient fold pending

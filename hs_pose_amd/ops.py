@@ -686,6 +686,18 @@ def orl_global(feat, idx, k):
 #               surface layer: the STE gradient from the coordinate moments only up to 64 clouds, else g^T xyz in fp32 by torch
 # ------------------------------------------------------------------------------------------------
 
+def _flush_folds(entry, key, wgrads, dirs=None):
+    """empty the lists of pending folds -- items (pending struct, what keeps its memory alive ...) -- through ``entry``, at most
+    FOLD_MAX_WGRAD + FOLD_MAX_DIRS a launch.  dirs None: ``hsp_wgrad_fold``'s arguments, else ``hsp_step_fold``'s; key: over w, d"""
+    while wgrads or dirs:
+        w, d = wgrads[:FOLD_MAX_WGRAD], (dirs or [])[:FOLD_MAX_DIRS]
+        del wgrads[:len(w)], (dirs or [])[:len(d)]
+        args = [(HspWgradPending * max(len(w), 1))(*[c[0] for c in w]), len(w)]
+        if dirs is not None:
+            args += [(HspDirsPending * max(len(d), 1))(*[c[0] for c in d]), len(d)]
+        _run(entry, (*args, _stream()), key=key.format(w=len(w), d=len(d)))
+
+
 def _wgrad_fallback(A2, B2, out, colsum):
     """A2^T B2 for the shapes the split-K kernels do not take (an output dimension that is no multiple of 64 and too small for
     the ragged form, e.g. a 3-wide coordinate block): the general tile kernel on a transposed copy of A2"""
@@ -723,11 +735,7 @@ class WgradBatch:
         return False
 
     def flush(self):
-        cap = StepFolds.MAX_WGRAD
-        while self.items:
-            chunk, self.items = self.items[:cap], self.items[cap:]
-            arr = (HspWgradPending * len(chunk))(*[c[0] for c in chunk])
-            _run("hsp_wgrad_fold", (arr, len(chunk), _stream()), key=f"n{len(chunk)}")
+        _flush_folds("hsp_wgrad_fold", "n{w}", self.items)
 
 
 class StepFolds:
@@ -742,7 +750,6 @@ class StepFolds:
     very tensors the nodes return; an accumulation into an existing ``.grad`` would read them before the fold):
     ``graph.GraphedStep`` and ``graph.GraphedNetwork``, whose captures replay the fold with the rest of the step."""
     current = None
-    MAX_WGRAD, MAX_DIRS = FOLD_MAX_WGRAD, FOLD_MAX_DIRS
 
     def __init__(self, bare_wgrad=False):
         """bare_wgrad: also defer ``wgrad`` calls made outside a ``WgradBatch`` (``linear_rows``' backward, which returns a
@@ -767,12 +774,7 @@ class StepFolds:
         return False
 
     def flush(self):
-        while self.wgrads or self.dirs:
-            w, self.wgrads = self.wgrads[:self.MAX_WGRAD], self.wgrads[self.MAX_WGRAD:]
-            d, self.dirs = self.dirs[:self.MAX_DIRS], self.dirs[self.MAX_DIRS:]
-            wa = (HspWgradPending * max(len(w), 1))(*[c[0] for c in w])
-            da = (HspDirsPending * max(len(d), 1))(*[c[0] for c in d])
-            _run("hsp_step_fold", (wa, len(w), da, len(d), _stream()), key=f"w{len(w)}d{len(d)}")
+        _flush_folds("hsp_step_fold", "w{w}d{d}", self.wgrads, self.dirs)
 
 
 def _hold(t):
@@ -782,17 +784,22 @@ def _hold(t):
     return None if t is None else t.untyped_storage()
 
 
+def _wgrad_sink():
+    """where a weight gradient's pending fold goes: the items of the open ``WgradBatch``, else those of a ``StepFolds`` scope that
+    defers bare ``wgrad`` calls too, else None -- the call folds at once"""
+    batch, sf = WgradBatch.current, StepFolds.current
+    return batch.items if batch is not None else sf.wgrads if sf is not None and sf.bare_wgrad else None
+
+
 def _rf_bwd_dirs_call(base, sfx, args_before_ws, ws, wsb, keep, key, abytes):
     """run the receptive-field backward entry point ``base + sfx`` (args ..., ws, ws_bytes, stream); inside a ``StepFolds`` scope
     its form ``base + "_partial" + sfx``, whose direction-gradient fold goes out with the step's other folds.  keep: tensors the
     pending fold reads / writes (kept alive until it has run)."""
-    sf = StepFolds.current
-    if sf is None:
-        _run(base + sfx, (*args_before_ws, _p(ws), wsb, _stream()), key=key, abytes=abytes)
-        return
-    pend = HspDirsPending()
-    _run(base + "_partial" + sfx, (*args_before_ws, _p(ws), wsb, ctypes.byref(pend), _stream()), key=key, abytes=abytes)
-    sf.dirs.append((pend, ws) + tuple(_hold(t) for t in keep))
+    sf, pend = StepFolds.current, HspDirsPending()
+    _run(base + ("" if sf is None else "_partial") + sfx,
+         (*args_before_ws, _p(ws), wsb, *(() if sf is None else (ctypes.byref(pend),)), _stream()), key=key, abytes=abytes)
+    if sf is not None:
+        sf.dirs.append((pend, ws) + tuple(_hold(t) for t in keep))
 
 
 def _wgrad_custom(A2, B2, out, colsum, entry="hsp_wgrad"):
@@ -800,24 +807,16 @@ def _wgrad_custom(A2, B2, out, colsum, entry="hsp_wgrad"):
     K, M = A2.shape
     N = B2.shape[1]
     cs = torch.empty(N, dtype=torch.float32, device=A2.device) if colsum else None
-    L = lib()
-    wsb = L.hsp_wgrad_workspace_bytes(M, N, K)
+    wsb = lib().hsp_wgrad_workspace_bytes(M, N, K)
     ws = _ws(wsb, A2.device)
-    sfx = "bf16" if A2.dtype == torch.bfloat16 else "f32"
-    es = 2 if A2.dtype == torch.bfloat16 else 4
-    batch = WgradBatch.current
-    sf = StepFolds.current
-    sink = batch.items if batch is not None else sf.wgrads if sf is not None and sf.bare_wgrad else None
+    sfx, es = ("bf16", 2) if A2.dtype == torch.bfloat16 else ("f32", 4)
+    sink, pend = _wgrad_sink(), HspWgradPending()
+    _run(f"{entry}{'' if sink is None else '_partial'}_{sfx}",
+         (_p(A2), A2.stride(0), _p(B2), B2.stride(0), M, N, K, _p(out), out.stride(0), _p(cs), _p(ws), wsb,
+          *(() if sink is None else (ctypes.byref(pend),)), _stream()),
+         key=f"M{M}N{N}K{K}", abytes=es * K * (M + N) + 4 * M * N, aflops=2 * M * N * K)
     if sink is not None:
-        pend = HspWgradPending()
-        _run(f"{entry}_partial_{sfx}", (_p(A2), A2.stride(0), _p(B2), B2.stride(0), M, N, K, _p(out), out.stride(0), _p(cs),
-                                        _p(ws), wsb, ctypes.byref(pend), _stream()),
-             key=f"M{M}N{N}K{K}", abytes=es * K * (M + N) + 4 * M * N, aflops=2 * M * N * K)
         sink.append((pend, ws, _hold(out), _hold(cs)))
-    else:
-        _run(f"{entry}_{sfx}", (_p(A2), A2.stride(0), _p(B2), B2.stride(0), M, N, K, _p(out), out.stride(0), _p(cs),
-                                _p(ws), wsb, _stream()),
-             key=f"M{M}N{N}K{K}", abytes=es * K * (M + N) + 4 * M * N, aflops=2 * M * N * K)
     return (out, cs) if colsum else out
 
 
@@ -894,13 +893,13 @@ def _wgrad_entry_of(A2, B2, out, ask=None):
 
 
 def wgrad_pair(A0, B0, out0, A1, B1, out1, colsum_of=None):
-    """(A0^T B0 -> out0, A1^T B1 -> out1) inside a ``WgradBatch``: ONE split-K launch for both when each is a K-sliced problem the
-    hand-written kernel takes (the two parameter gradients of an HS layer that depend only on the incoming gradient: g^T F and
+    """(A0^T B0 -> out0, A1^T B1 -> out1) where the folds stay pending (``_wgrad_sink``: an HS layer's ``WgradBatch``): ONE
+    split-K launch for both when each is a K-sliced problem the hand-written kernel takes (the two parameter gradients of an HS layer that depend only on the incoming gradient: g^T F and
     g^T X -- each alone leaves most of the chip idle); otherwise, and for bf16 rows (the pair kernel is fp32), two ``wgrad`` calls.
     ``colsum_of`` = (g (B,N,C) fp32, mom (B,C)): ask for mom = the per-cloud column sums of g (``hsp_colsum_cloud_f32``'s bits) as a
     rider of that launch; returns True where it rode along, False (mom untouched, the products issued as without it) elsewhere."""
-    batch = WgradBatch.current
-    if (batch is None or A0.dtype != torch.float32 or not _wgrad_entry_of(A0, B0, out0, _wgrad_sliced)
+    sink = _wgrad_sink()
+    if (sink is None or A0.dtype != torch.float32 or not _wgrad_entry_of(A0, B0, out0, _wgrad_sliced)
             or not _wgrad_entry_of(A1, B1, out1, _wgrad_sliced)):
         wgrad(A0, B0, out=out0)
         wgrad(A1, B1, out=out1)
@@ -923,8 +922,8 @@ def wgrad_pair(A0, B0, out0, A1, B1, out1, colsum_of=None):
                     may_decline=True)
     if not rode:
         _run("hsp_wgrad_partial_pair_f32", (*pair, _stream()), key=key, abytes=ab, aflops=2 * (M0 * N0 * K0 + M1 * N1 * K1))
-    batch.items.append((HspWgradPending.from_buffer_copy(pend[0]), ws0, _hold(out0)))
-    batch.items.append((HspWgradPending.from_buffer_copy(pend[1]), ws1, _hold(out1)))
+    sink.append((HspWgradPending.from_buffer_copy(pend[0]), ws0, _hold(out0)))
+    sink.append((HspWgradPending.from_buffer_copy(pend[1]), ws1, _hold(out1)))
     return rode
 
 

@@ -234,16 +234,20 @@ def _dtype(c):
     return BF if "bf16" in c.entry else torch.float32
 
 
-def _run_wgrad(c, a, b, colsum, dev, short=0):
-    """one call through the C ABI inside the moats -> (rc, C, colsum, workspace)"""
+def _run_wgrad(c, a, b, colsum, dev, short=0, pend=None):
+    """one call through the C ABI inside the moats -> (rc, C, colsum, workspace); pend (an HspWgradPending): through the case's
+    ``_partial`` entry, which leaves the fold pending and describes it there"""
     L = _L()
     av, bv = _in_moat(a, c.lda, dev, c.al16), _in_moat(b, c.ldb, dev, c.al16)
     out = Out(c.M, c.N, c.N + 1, dev)
     cs = Out(1, c.N, c.N, dev) if colsum else None
     wsb = L.hsp_wgrad_workspace_bytes(c.M, c.N, c.K)
     ws = Ws(wsb, dev)
-    rc = getattr(L, _entry(c))(_vp(av), c.lda, _vp(bv), c.ldb, c.M, c.N, c.K, _vp(out.v), c.N + 1, _vp(cs.v if cs else None),
-                               _vp(ws.buf), wsb - short, _stream())
+    entry, tail = _entry(c), (_stream(),)
+    if pend is not None:                                                   # hsp_wgrad[_ragged]_partial_<rows>
+        entry, tail = "_partial_".join(entry.rsplit("_", 1)), (ctypes.byref(pend), _stream())
+    rc = getattr(L, entry)(_vp(av), c.lda, _vp(bv), c.ldb, c.M, c.N, c.K, _vp(out.v), c.N + 1, _vp(cs.v if cs else None),
+                           _vp(ws.buf), wsb - short, *tail)
     torch.cuda.synchronize()
     return rc, out, cs, ws
 
@@ -299,6 +303,24 @@ def test_wgrad(dev, c):
             if colsum:
                 _hold(cs.v[0], wcs, Tcs, what + " colsum", FORM_NAME[form] + " colsum", A_SUM)
                 first = (out.v.clone(), cs.v.clone())
+                _partial_then_fold_gives(first, c, a, b, parts, dev, what)
+
+
+def _partial_then_fold_gives(first, c, a, b, parts, dev, what):
+    """the case's ``_partial`` entry, then its pending fold through hsp_wgrad_fold and, in a second run, through hsp_step_fold: the
+    bits of the fold-now call (``first``), from the plan's count of partial sums, inside the moats"""
+    L = _L()
+    for fold in ("hsp_wgrad_fold", "hsp_step_fold"):
+        pend = HspWgradPending()
+        rc, out, cs, ws = _run_wgrad(c, a, b, True, dev, pend=pend)
+        assert rc == 0, f"{what}: the partial entry's rc {rc}"
+        assert pend.nparts == parts, f"{what}: {pend.nparts} partial sums pending, the plan says {parts}"
+        p = ctypes.byref(pend)
+        rc = L.hsp_wgrad_fold(p, 1, _stream()) if fold == "hsp_wgrad_fold" else L.hsp_step_fold(p, 1, None, 0, _stream())
+        torch.cuda.synchronize()
+        assert rc == 0, f"{what}: {fold} rc {rc}"
+        assert torch.equal(out.v, first[0]) and torch.equal(cs.v, first[1]), f"{what}: partial + {fold} differs from the fold-now call"
+        assert out.intact() and cs.intact() and ws.intact(), f"{what}: partial + {fold} wrote outside the output or past the workspace"
 
 
 @pytest.mark.parametrize("c", gc.WGRAD_DECLINED, ids=_ids)

@@ -89,6 +89,33 @@ def test_step_fold_equals_standalone_folds(dev, ref):
     assert L.hsp_step_fold(None, 1, None, 0, None) == -1
 
 
+@pytest.mark.parametrize("B,N,S,C", [(1, 1078, 1, 16), (2, 1079, 2, 16)], ids=["B1-N1078", "B2-N1079"])
+def test_step_fold_of_half_cloud_partials(dev, ref, B, N, S, C):
+    """the half-cloud form of the scatter backward (two row ranges per cloud) leaves 2 B partials pending; ONE hsp_step_fold over
+    them == the fold-now entry's grad_dirs, bit for bit, beside an equal grad_fm"""
+    from hs_pose_amd.ops import _p, _run, _stream, _ws
+    from hs_pose_amd._lib import lib, HspDirsPending
+    L = lib()
+    rs = ctypes.c_int(0)
+    assert L.hsp_rf_bwd_scatter_plan(B, N, S, C, 0, ctypes.byref(rs)) == 16 and rs.value == 2
+    xyz, dirs, fwin, arg, g = _rf_case(ref, dev, B, N, 4, S, C, 720 + N)
+    SC = S * C
+    wsb = L.hsp_rf_bwd_scatter_workspace_bytes(B, SC)
+    gfm0, gd0 = torch.empty(B, N, (S + 1) * C, device=dev), torch.empty(3, SC, device=dev)
+    _run("hsp_rf_conv_bwd_scatter", (_p(xyz), _p(dirs), _p(None), _p(fwin), _p(arg), _p(g), B, N, S, C, _p(gfm0), _p(gd0),
+                                     _p(_ws(wsb, dev)), wsb, _stream()))
+    gfm1, gd1 = torch.empty_like(gfm0), torch.full_like(gd0, float("nan"))
+    ws = _ws(wsb, dev)
+    p = HspDirsPending()
+    _run("hsp_rf_conv_bwd_scatter_partial", (_p(xyz), _p(dirs), _p(None), _p(fwin), _p(arg), _p(g), B, N, S, C, _p(gfm1), _p(gd1),
+                                             _p(ws), wsb, ctypes.byref(p), _stream()))
+    assert p.nparts == 2 * B and p.SC == SC
+    _run("hsp_step_fold", (None, 0, ctypes.byref(p), 1, _stream()))
+    torch.cuda.synchronize()
+    assert torch.isfinite(gd0).all() and torch.equal(gd0, gd1)
+    assert torch.equal(gfm0, gfm1)
+
+
 def test_step_folds_scope_on_the_stack(dev):
     """ops.StepFolds around an eager backward of the HS stack (every .grad None first): one hsp_step_fold launch at the exit and
     the same parameter gradients as the plain backward of a twin network"""
